@@ -194,7 +194,14 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: only the launch / barrier / counter all-reduce plumbing of the ranks (gloo), with "
                          "synthetic counters; used by the CPU test of --gpus N")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy "
+                         "(float32 / float64, a fixed sample where an output is large): two builds run with the same "
+                         "arguments can then be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -676,6 +683,74 @@ def sharpened_numerics(eng, ref_net, planes):
             "within_tolerance": bool(m["policy_max_abs"] <= 1e-4 and m["value_max_abs"] <= 1e-4)}
 
 
+DUMP_POLICY_ROWS = 1024         # policy rows written by --dump-outputs (2086 float32 each)
+DUMP_GAMES = 4096               # games whose root statistics --dump-outputs writes
+DUMP_SEED = 20261015            # the fixed sample of rows / games
+
+
+def _dump_sample(n, k):
+    """k indices of range(n), the same for every run with the same n (all of them when n <= k), ascending."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(DUMP_SEED).choice(n, k, replace=False))
+
+
+def _write_dump(d, arrays, log):
+    """arrays: name -> numpy array (float32 / float64 only) -> d/<name>.npy"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    log(f"dumped {len(arrays)} outputs ({total / 2**20:.1f} MiB) to {d}")
+
+
+def dump_selfplay(d, eng, timed_counters, log):
+    """The self-play round's outputs after the last timed step, as a caller of SelfPlayEngine.step receives them:
+    the network's evaluation of the leaves the last round queued, by queue SLOT (the compact queue's row order follows the
+    kernel's atomics and is not reproducible, its slots are): value of every slot and the policy rows (raw logits where the
+    engine runs on logits) of a fixed sample of DUMP_POLICY_ROWS slots, with evaluated = 1 where the slot held a new leaf
+    (0 elsewhere, and zeros in value / policy); the search's root statistics of every game (or a fixed sample of DUMP_GAMES
+    games) and the counters of the timed leg summed over the ranks (timed_counters: a dict, written in its order -- main's
+    `keys`)."""
+    import numpy as np
+    s = eng.search
+    torch.cuda.synchronize()
+    out = {}
+    row_of_slot = np.arange(s.slots)                   # the queue row that holds a slot's evaluation, -1: none this round
+    if eng.compact:
+        n = int(s.q_count.item())
+        slots = s.q_rows[:n].cpu().numpy().astype(np.int64)
+        assert n <= s.slots and (slots >= 0).all() and (slots < s.slots).all()
+        row_of_slot = np.full(s.slots, -1, dtype=np.int64)
+        row_of_slot[slots] = np.arange(n)
+    have = row_of_slot >= 0
+    value = s.value.cpu().numpy()[np.maximum(row_of_slot, 0)]
+    out["evaluated"] = have.astype(np.float32)
+    out["value"] = np.where(have, value, 0.0).astype(np.float32)
+    pick = _dump_sample(s.slots, DUMP_POLICY_ROWS)
+    rows = torch.from_numpy(np.maximum(row_of_slot[pick], 0)).to(s.policy.device)
+    policy = s.policy[rows].cpu().numpy()
+    out["policy_slots"] = pick.astype(np.float64)
+    out["policy"] = np.where(have[pick][:, None], policy, 0.0).astype(np.float32)
+    st = s.root_stats()
+    games = _dump_sample(s.G, DUMP_GAMES)
+    out["root_games"] = games.astype(np.float64)
+    out["root_moves"] = st["moves"][games].astype(np.float64)
+    out["root_n"] = st["n"][games].astype(np.float64)
+    out["root_w"] = st["w"][games].astype(np.float64)
+    out["root_p"] = st["p"][games].astype(np.float32)
+    out["root_sum_n"] = st["sum_n"][games].astype(np.float64)
+    out["root_counts"] = st["counts"][games].astype(np.float64)
+    out["timed_counters"] = np.array([float(v) for v in timed_counters.values()], dtype=np.float64)
+    _write_dump(d, out, log)
+
+
 def run_arena(args, cfg, max_plies=None):
     """BASELINE configs[3]: the evaluator arena on the arena worker (worker/evaluator.py::EvaluateWorker.play_games):
     BestModel vs NextGenerationModel (two random-init networks, seeds 0 / 1), 200 paired games played concurrently,
@@ -716,6 +791,11 @@ def run_arena(args, cfg, max_plies=None):
     d = {k: b[1][k] - a[1][k] for k in a[1]}
     rounds = b[2] - a[2]
     table = score_table(results)
+    if args.dump_outputs:
+        import numpy as np
+        # the arena's result as play_games returns it: (value, plies) of every game, in game order
+        _write_dump(args.dump_outputs, {"arena_results": np.array(results, dtype=np.float64)},
+                    lambda m: print(f"[bench] {m}", file=sys.stderr, flush=True))
     fl = flops_per_position(model_cfg)
     out = {"metric": "mcts_node_expansions_per_sec", "value": d["expansions"] / dt, "unit": "expansions/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -1055,6 +1135,8 @@ def main():
 
     dt, d, k_ms, blk_ms = run_leg(args.steps, 1)
     log(f"timed {args.steps} steps in {dt:.2f}s")
+    if args.dump_outputs and rank == 0:
+        dump_selfplay(args.dump_outputs, eng, {k: d[k] for k in keys}, log)
     n_sus = args.sustained_rounds
     if n_sus is None:
         n_sus = 3000 if (world == 1 and args.config == "normal" and not args.graph) else 0

@@ -507,6 +507,22 @@ def test_self_play_rank_rendezvous(monkeypatch):
     assert [p.communicate(timeout=120)[0].strip().splitlines()[-1] for p in ps] == ["3", "3"]
 
 
+def test_bench_dump_outputs_helpers(tmp_path):
+    """bench.py --dump-outputs: the sample of a large output is the same fixed set of rows on every run (all rows of a small
+    one), and only float32 / float64 arrays are written."""
+    sys.path.insert(0, ROOT) if ROOT not in sys.path else None
+    import bench
+    a, b = bench._dump_sample(32768, 1024), bench._dump_sample(32768, 1024)
+    assert len(a) == 1024 and (a == b).all() and (np.diff(a) > 0).all() and a[-1] < 32768
+    assert (bench._dump_sample(10, 1024) == np.arange(10)).all()
+    d = tmp_path / "dump"
+    bench._write_dump(str(d), {"x": np.arange(6, dtype=np.float32).reshape(2, 3), "y": np.zeros(4)}, lambda m: None)
+    x, y = np.load(d / "x.npy"), np.load(d / "y.npy")
+    assert x.dtype == np.float32 and x.shape == (2, 3) and y.dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench._write_dump(str(d), {"z": np.zeros(4, dtype=np.int32)}, lambda m: None)
+
+
 def test_bench_arithmetic_labels():
     """bench.py: the dtype label and the matrix-pipe cost of a tower arithmetic name (what `dtype` / `roofline` in the line say)."""
     sys.path.insert(0, ROOT) if ROOT not in sys.path else None

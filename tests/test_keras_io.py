@@ -63,12 +63,9 @@ def test_hdf5_reader_rejects_other_files(tmp_path):
     ("model_128_l1_config", dict(cnn_filter_num=128, res_layer_num=7, input_depth=28, policy_filters=32, value_filters=4)),
 ])
 def test_reference_topologies(name, want):
-    """The facts below were read off the reference's own data/model/*.json with the importer (golden: the values are
-    committed here because /root/reference does not travel); when the reference is present the files are re-parsed."""
+    """The reference's own data/model/*.json (copies: tests/golden/reference_model/) through the importer."""
     from cchess_alphazero.lib import keras_io
-    path = f"/root/reference/data/model/{name}.json"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present on this machine")
+    path = os.path.join(GOLD, "reference_model", f"{name}.json")
     cfg = keras_io.config_from_keras(json.load(open(path)))
     for k, v in want.items():
         assert cfg[k] == v

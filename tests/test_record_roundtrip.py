@@ -1,10 +1,10 @@
 """play records written by the engine (tests/golden/engine_records.json, produced on an MI355X by
-tools/make_engine_records.py) are valid input for the reference's trainer.  The oracle replays every record on
-any machine; where the reference itself is present (build container) its own ``expanding_data``
-(worker/optimize.py:234-281) parses them and must produce the same planes / policies / values."""
+tools/make_engine_records.py) are valid input for the reference's trainer.  The oracle replays every record; the
+reference's own ``expanding_data`` (worker/optimize.py:234-281) parsed them into the planes / policies / values recorded
+in tests/golden/trainer_records.json (tests/golden/make_golden_trainer.py), and the oracle's replay must give the same."""
+import hashlib
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -41,34 +41,22 @@ def test_engine_records_replay_with_oracle():
 
 
 def test_reference_trainer_parses_engine_records():
-    if not os.path.isdir("/root/reference/cchess_alphazero"):
-        pytest.skip("reference not present on this machine")
-    from unittest.mock import MagicMock
-    saved_path, saved_mods = list(sys.path), dict(sys.modules)
-    try:
-        for k in [k for k in sys.modules if k == "cchess_alphazero" or k.startswith("cchess_alphazero.")]:
-            del sys.modules[k]
-        sys.path[:0] = ["/root/reference", "/root/reference/cchess_alphazero"]
-        for name in ("tensorflow", "keras", "keras.engine", "keras.engine.topology", "keras.engine.training",
-                     "keras.layers", "keras.layers.convolutional", "keras.layers.core", "keras.layers.merge",
-                     "keras.layers.normalization", "keras.regularizers", "keras.backend", "keras.models",
-                     "keras.optimizers", "keras.callbacks", "keras.utils", "keras.utils.training_utils"):
-            sys.modules.setdefault(name, MagicMock())
-        import cchess_alphazero.worker.optimize as opt
-        for g in _games():
-            out = opt.expanding_data(g["data"])
-            assert out is not None
-            planes, policy, value = out
-            n = g["turns"]
-            assert planes.shape == (n, 14, 10, 9) and policy.shape == (n, 2086) and value.shape == (n,)
-            state = g["data"][0]
-            for i, (mv, v) in enumerate(g["data"][1:]):
-                assert (planes[i] == xo.state_to_planes(state)).all()
-                assert policy[i].argmax() == xo.label_of_str(mv) and policy[i].sum() == 1
-                assert value[i] == v
-                state = xo.step(state, mv)
-    finally:
-        sys.path[:] = saved_path
-        for k in [k for k in sys.modules if k not in saved_mods]:
-            del sys.modules[k]
-        sys.modules.update(saved_mods)
+    """The reference's expanding_data on every engine record, as recorded by tests/golden/make_golden_trainer.py
+    (trainer_records.json): the same planes / policies / values as the oracle's replay of the record."""
+    with open(os.path.join(HERE, "golden", "trainer_records.json")) as f:
+        ref = {r["game_id"]: r for r in json.load(f)["games"]}
+    games = _games()
+    assert sorted(ref) == sorted(g["game_id"] for g in games)
+    for g in games:
+        r = ref[g["game_id"]]
+        n = g["turns"]
+        assert r["planes_shape"] == [n, 14, 10, 9] and r["policy_shape"] == [n, 2086] and r["value_shape"] == [n]
+        planes = []
+        state = g["data"][0]
+        for i, (mv, v) in enumerate(g["data"][1:]):
+            planes.append(np.asarray(xo.state_to_planes(state), dtype=np.float32))
+            assert r["policy_argmax"][i] == xo.label_of_str(mv) and r["policy_sum"][i] == 1
+            assert r["value"][i] == v
+            state = xo.step(state, mv)
+        got = hashlib.sha256(np.ascontiguousarray(np.stack(planes), dtype=np.float32).tobytes()).hexdigest()
+        assert got == r["planes_sha256"], g["game_id"]
