@@ -401,7 +401,9 @@ def test_whole_game_tree_is_kept(gpu):
     s.close()
 
 
-def run_selfplay(gpu, pc, spec, G, seed, games_wanted, max_rounds=200000, **kw):
+def run_selfplay(gpu, pc, spec, G, seed, games_wanted, max_rounds=200000, drained=None, before_close=None, **kw):
+    """drained: a list that receives every record in the order drained (duplicates included); before_close(s): called
+    with the search object after the last round, before it is freed."""
     s = gpu.S.Search(pc, G, seed=seed, **kw)
     ev = stub_eval(gpu, spec)
     s.start_selfplay(seed=seed, first_game_id=0)
@@ -414,9 +416,13 @@ def run_selfplay(gpu, pc, spec, G, seed, games_wanted, max_rounds=200000, **kw):
         if r % 64 == 63:
             for rec in s.drain_records():
                 recs[rec["game_id"]] = rec
+                if drained is not None:
+                    drained.append(rec)
             if all(g in recs for g in range(games_wanted)):
                 break
     ctr = s.counters()
+    if before_close is not None:
+        before_close(s)
     s.close()
     return recs, ctr
 
