@@ -105,10 +105,6 @@ def _declare(L):
         L.cz_tower_plain.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
         L.cz_tower_pairs.restype = i32
         L.cz_tower_pairs.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-        L.cz_tower_c6.restype = i32
-        L.cz_tower_c6.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp]
-        L.cz_tower_c6_heads.restype = i32
-        L.cz_tower_c6_heads.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     if hasattr(L, "cz_heads_tail"):
         L.cz_heads_tail.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp, vp]
         L.cz_heads_tail.restype = i32
@@ -578,29 +574,6 @@ def tower_pairs(x, blocks, out=None, heads=None, count=None):
                            _ptr(hw), _ptr(hb), _ptr(pf), _ptr(vf), npol, nval, x[0].shape[0], _dt_code(x[0].dtype),
                            _ptr(count), _stream()), "cz_tower_pairs")
     return out if heads is None else (pf, vf)
-
-
-def tower_c6(x, blocks, out, count=None):
-    """cz_tower_c6: the consecutive c6 residual blocks `blocks` = [(w1_packed, bias1, w2_packed, bias2), ...] (2 .. 8) in ONE
-    launch, activations in LDS between them; x / out: c6 operand pairs (f16 [N, 90, 128], int8 [N, 90, 256]).  Bit-identical to
-    len(blocks) resblock() calls."""
-    require_gpu()
-    bl = _block_list(blocks)
-    a = bl.arrays
-    check(lib().cz_tower_c6(_ptr(x[0]), _ptr(x[1]), bl.n, a[0], a[1], a[2], a[3], _ptr(out[0]), _ptr(out[1]), x[0].shape[0],
-                            _ptr(count), _stream()), "cz_tower_c6")
-    return out
-
-
-def tower_c6_heads(x, blocks, head_w, head_b, n_policy, policy_feat, value_feat, count=None):
-    """cz_tower_c6_heads: tower_c6 ending on the tower's last block, the 1x1 head convolutions as the chain's exit."""
-    require_gpu()
-    bl = _block_list(blocks)
-    a = bl.arrays
-    check(lib().cz_tower_c6_heads(_ptr(x[0]), _ptr(x[1]), bl.n, a[0], a[1], a[2], a[3], _ptr(head_w), _ptr(head_b),
-                                  _ptr(policy_feat), _ptr(value_feat), x[0].shape[0], n_policy, head_w.shape[0] - n_policy,
-                                  _ptr(count), _stream()), "cz_tower_c6_heads")
-    return policy_feat, value_feat
 
 
 def resblock_pipelined(enable=None):

@@ -674,11 +674,16 @@ __global__ __launch_bounds__((C / 32 / CTW + 4) * 64, (C / 32 / CTW + 4 + 3) / 4
 
 // ---- kernel 2p: a CHAIN of residual blocks on plain 2-byte operands (256 filters: the `deep` 20 x 256 fp16 tower) ---------------
 // k_resblock<E, 256, 1, 1, false, 2> keeps X | Y | a staging image and sends every block's result through the copy waves to HBM and
-// back.  With one board per workgroup and plain operands the second epilogue can write its result IN PLACE over the skip operand
-// (a lane reads and writes only its own 8 bytes), which is block b + 1's input: a workgroup takes a board through ALL blocks of
-// the tower in X | Y, HBM sees it at the entry and the exit, the matrix waves never wait for a refill between blocks.  Same K loop
-// (conv_kloop, two channel tiles per wave) and the same epilogue arithmetic in the same order: bit-identical to ch.n launches of
-// k_resblock (BASELINE configs[4]; reference tower agent/model.py:41-43).
+// back.  Here a workgroup takes a PAIR of boards through ALL blocks of the tower, HBM sees a board at the chain's entry and exit.
+// What bounds the chain is energy per board (EXPERIMENTS Part III): per board and convolution 1.18 MB of packed filter come from
+// L2 into the CU, and a filter fragment feeding SIX pixel tiles (two boards) instead of three halves that stream per board at the
+// same LDS reads per MFMA.  Two boards with X | Y each do not fit 160 KB; they do with ONE image per board: after K loop 1
+// (barrier: every wave has read all of X) a lane moves its own skip values out of X (a lane reads and writes only its own 8
+// bytes) and writes relu(conv1 + b1) over them -- X now IS Y --, and epilogue 2 writes relu(conv2 + b2 + skip) to the same 8
+// bytes again, which is block b + 1's input.  192 accumulator + 96 skip registers per wave: four matrix waves, no copy waves, one
+// wave per SIMD (512 registers); the matrix waves fetch and store the pair themselves, once per chain.  K loop
+// (conv_kloop<E, 256, 2, 1, 2>) and epilogue arithmetic are k_resblock's, per accumulator tile in the same order: bit-identical
+// to ch.n launches of k_resblock (BASELINE configs[4]; reference tower agent/model.py:41-43).
 namespace pl {
 constexpr int MAX_BLOCKS = 24;
 struct Chain {
@@ -690,170 +695,6 @@ struct Chain {
 };
 }  // namespace pl
 
-template <typename E, int C, int CTW>
-__global__ __launch_bounds__((C / 32 / CTW + 4) * 64, (C / 32 / CTW + 4 + 3) / 4) void k_tower_plain(
-    const E* __restrict__ xh, pl::Chain ch, E* __restrict__ yh, int n_boards, const int32_t* __restrict__ n_dev)
-{
-    if (n_dev) {
-        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
-        n_boards = nd < n_boards ? nd : n_boards;
-    }
-    typedef Geom<C, 1, 1> G;
-    constexpr int NT = G::NT, CT = G::CT / CTW, CTHR = RB_COPY_THREADS;
-    constexpr int LITER = (G::CHUNKS + CTHR - 1) / CTHR;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * G::REGION];
-    unsigned char* X = lds;
-    unsigned char* Y = lds + G::REGION;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int NB = ch.n;
-    int t = blockIdx.x;
-    if (t >= n_boards) return;
-    const int stride = gridDim.x;
-
-    if (wave >= CT) {                                   // ---- copy waves ----
-        const int ctid = tid - CT * 64;
-        uint4 v[1][LITER];
-        tile_load<E, C, 1, 1, CTHR>(xh, nullptr, t, n_boards, ctid, v);
-        tile_write<C, 1, 1, CTHR>(X, ctid, v);
-        zero_rows_write<C, 1, 1, CTHR>(X, ctid);
-        zero_rows_write<C, 1, 1, CTHR>(Y, ctid);
-        for (;;) {
-            __syncthreads();                                   // A: X holds board t
-            const int tn = t + stride;
-            const bool has_next = tn < n_boards;
-            int ct2 = ctid;
-            asm volatile("" : "+v"(ct2));
-            if (has_next) tile_load<E, C, 1, 1, CTHR>(xh, nullptr, tn, n_boards, ct2, v);
-            for (int b = 0; b < NB; ++b) {
-                __syncthreads();                               // B
-                __syncthreads();                               // C: block b's result is in X
-            }
-            // the chain's result to HBM; the same chunks take the next board
-            uint4* dst = reinterpret_cast<uint4*>(yh + (size_t)t * 90 * C);
-#pragma unroll
-            for (int it = 0; it < LITER; ++it) {
-                const int i = it * CTHR + ct2;
-                if (!((it + 1) * CTHR <= G::CHUNKS || i < G::CHUNKS)) continue;
-                const int row = i / G::CPR, chn = i % G::CPR;
-                unsigned char* a = X + row * G::RB + ((chn ^ (row & G::SWZ)) << 4);
-                const uint4 o = *reinterpret_cast<const uint4*>(a);
-                if (has_next) *reinterpret_cast<uint4*>(a) = v[0][it];
-                dst[i] = o;
-            }
-            if (!has_next) break;
-            t = tn;
-        }
-        return;
-    }
-
-    // ---- matrix waves ----
-    const int wg = wave * CTW;                                 // first channel tile of this wave
-    const int kb = lane >> 5, ln = lane & 31;
-    for (;;) {
-        __syncthreads();                                       // A
-        const bool has_next = t + stride < n_boards;
-        for (int blk = 0; blk < NB; ++blk) {
-            const uint4* wq1 = reinterpret_cast<const uint4*>(ch.w1[blk]) + wg * 64 + lane;
-            const uint4* wq2 = reinterpret_cast<const uint4*>(ch.w2[blk]) + wg * 64 + lane;
-            const float* b1 = ch.b1[blk];
-            const float* b2 = ch.b2[blk];
-            f32x16 acc[CTW * NT];
-            __builtin_amdgcn_s_setprio(3);
-            conv_kloop<E, C, 1, 1, CTW>(X, wq1, lane, acc);
-            __builtin_amdgcn_s_setprio(0);
-            f32x4 bq[CTW][4];                                  // (k_resblock's bias_fetch)
-            auto bias_fetch = [&](const float* bp) {
-#pragma unroll
-                for (int c = 0; c < CTW; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) bq[c][g] = *reinterpret_cast<const f32x4*>(bp + (wg + c) * 32 + g * 8 + kb * 4);
-#pragma unroll
-                for (int c = 0; c < CTW; ++c)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(bq[c][g]));
-            };
-            bias_fetch(b1);
-            int ln2 = ln, kb2 = kb;
-            asm volatile("" : "+v"(ln2), "+v"(kb2));
-            // epilogue 1: relu(acc + b1) -> Y (k_resblock's)
-#pragma unroll
-            for (int cp = 0; cp < CTW * NT; ++cp) {
-                const int p = cp % NT, c = cp / NT;
-                const int q = p * 32 + ln2;
-                if (q < 90) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int chn = (wg + c) * 32 + g * 8 + kb2 * 4;
-                        const f32x4 bv = bq[c][g];
-                        const float vv[4] = {acc[cp][g * 4 + 0] + bv[0], acc[cp][g * 4 + 1] + bv[1], acc[cp][g * 4 + 2] + bv[2],
-                                             acc[cp][g * 4 + 3] + bv[3]};
-                        const int off = q * G::RB + (((chn >> 3) ^ (q & G::SWZ)) << 4) + (chn & 7) * 2;
-                        Quad<E> hi;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float r = vv[i] > 0.0f ? vv[i] : 0.0f;
-                            hi.e[i] = (E)r;
-                        }
-                        *reinterpret_cast<Quad<E>*>(Y + off) = hi;
-                    }
-                }
-            }
-            __syncthreads();                                   // B: Y complete
-            __builtin_amdgcn_s_setprio(3);
-            conv_kloop<E, C, 1, 1, CTW>(Y, wq2, lane, acc);
-            __builtin_amdgcn_s_setprio(0);
-            bias_fetch(b2);
-            asm volatile("" : "+v"(ln2), "+v"(kb2));
-            // epilogue 2: relu(acc + b2 + x) -> X, in place over the skip operand (this lane's own 8 bytes)
-#pragma unroll
-            for (int cp = 0; cp < CTW * NT; ++cp) {
-                const int p = cp % NT, c = cp / NT;
-                const int q = p * 32 + ln2;
-                if (q < 90) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int chn = (wg + c) * 32 + g * 8 + kb2 * 4;
-                        const f32x4 bv = bq[c][g];
-                        const int off = q * G::RB + (((chn >> 3) ^ (q & G::SWZ)) << 4) + (chn & 7) * 2;
-                        const Quad<E> sh = *reinterpret_cast<const Quad<E>*>(X + off);
-                        float vv[4] = {acc[cp][g * 4 + 0] + bv[0], acc[cp][g * 4 + 1] + bv[1], acc[cp][g * 4 + 2] + bv[2],
-                                       acc[cp][g * 4 + 3] + bv[3]};
-                        Quad<E> o;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            vv[i] += (float)sh.e[i];
-                            vv[i] = vv[i] > 0.0f ? vv[i] : 0.0f;
-                            o.e[i] = (E)vv[i];
-                        }
-                        *reinterpret_cast<Quad<E>*>(X + off) = o;
-                    }
-                }
-            }
-            __syncthreads();                                   // C: the block's result is in X
-        }
-        if (!has_next) break;
-        t += stride;
-    }
-}
-
-// ---- kernel 2pp: the same chain for a PAIR of boards per workgroup, ONE LDS image per board -------------------------------------
-// What bounds k_tower_plain is energy per board (EXPERIMENTS Part III): per board and convolution 1.18 MB of packed filter come
-// from L2 into the CU.  Here a filter fragment feeds SIX pixel tiles (two boards) instead of three: half the filter stream per
-// board, same LDS reads per MFMA.  Two boards with X | Y each do not fit 160 KB; they do with ONE image per board: after K loop 1
-// (barrier: every wave has read all of X) a lane moves its own skip values from X into registers (96 values per board) and
-// writes relu(conv1 + b1) over them -- X now IS Y --, and epilogue 2 writes relu(conv2 + b2 + skip) to the same 8 bytes again.
-// 192 accumulator + 96 skip registers per wave: four matrix waves, no copy waves, one wave per SIMD (512 registers); the matrix
-// waves fetch and store the pair themselves, once per chain.  K loop (conv_kloop<E, 256, 2, 1, 2>) and epilogue arithmetic are
-// k_resblock's, per accumulator tile in the same order: bit-identical to k_tower_plain and to ch.n launches of k_resblock.
-#ifndef CZ_TP2_BIAS_EARLY
-#define CZ_TP2_BIAS_EARLY 1
-#endif
-#ifndef CZ_TP2_TILE_FENCE
-#define CZ_TP2_TILE_FENCE 0
-#endif
-#ifndef CZ_TP2_SKIP_LDS
-#define CZ_TP2_SKIP_LDS 1
-#endif
 template <typename E, int C, int CTW>
 __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
     const E* __restrict__ xh, pl::Chain ch, E* __restrict__ yh, int n_boards, const int32_t* __restrict__ n_dev)
@@ -867,7 +708,7 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
     constexpr int LITER = (G::CHUNKS + NTHR - 1) / NTHR;
     // X: the pair's image.  SK: the FIRST board's skip values while its intermediate activation sits in X (the second board's wait
     // in registers: 48 -- all 96 in registers left no room beside 192 accumulators and the K loop's rings: half of them spilled)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[G::REGION + (CZ_TP2_SKIP_LDS ? 90 * G::RB : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[G::REGION + 90 * G::RB];
     unsigned char* X = lds;
     unsigned char* SK = lds + G::REGION;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -908,7 +749,7 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
             const float* b1 = ch.b1[blk];
             const float* b2 = ch.b2[blk];
             f32x16 acc[CTW * NT];
-            c8k::u32x2 skip[CZ_TP2_SKIP_LDS ? CTW * 3 : CTW * NT][4];          // (packed: four 2-byte values in two registers)
+            c8k::u32x2 skip[CTW * 3][4];          // (packed: four 2-byte values in two registers)
             f32x4 bq[CTW][4];
             // the biases of this wave's channels: all eight loads in flight across the barrier, materialised once (left to the
             // compiler there was one load and one vmcnt(0) per 8-byte store: 48 L2 round trips in a row per epilogue)
@@ -927,9 +768,9 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
             __builtin_amdgcn_s_setprio(3);
             conv_kloop<E, C, 2, 1, CTW>(X, wq1, lane, acc);
             __builtin_amdgcn_s_setprio(0);
-            if (CZ_TP2_BIAS_EARLY) bias_request(b1);
+            bias_request(b1);
             __syncthreads();                                   // K1: every wave has read X
-            if (CZ_TP2_BIAS_EARLY) bias_pin();
+            bias_pin();
             int ln2 = ln, kb2 = kb;
             asm volatile("" : "+v"(ln2), "+v"(kb2));
             // epilogue 1: skip <- X, X <- relu(acc + b1)   (this lane's own 8 bytes)
@@ -942,13 +783,12 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int chn = (wg + c) * 32 + g * 8 + kb2 * 4;
-                        const f32x4 bv = CZ_TP2_BIAS_EARLY ? bq[c][g] : *reinterpret_cast<const f32x4*>(b1 + chn);
+                        const f32x4 bv = bq[c][g];
                         const float vv[4] = {acc[cp][g * 4 + 0] + bv[0], acc[cp][g * 4 + 1] + bv[1], acc[cp][g * 4 + 2] + bv[2],
                                              acc[cp][g * 4 + 3] + bv[3]};
                         const int off = row * G::RB + (((chn >> 3) ^ (row & G::SWZ)) << 4) + (chn & 7) * 2;
                         const c8k::u32x2 sk = *reinterpret_cast<const c8k::u32x2*>(X + off);
-                        if (!CZ_TP2_SKIP_LDS) skip[cp][g] = sk;
-                        else if (p < 3) *reinterpret_cast<c8k::u32x2*>(SK + off) = sk;
+                        if (p < 3) *reinterpret_cast<c8k::u32x2*>(SK + off) = sk;
                         else skip[c * 3 + p - 3][g] = sk;
                         Quad<E> hi;
 #pragma unroll
@@ -959,15 +799,14 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
                         *reinterpret_cast<Quad<E>*>(X + off) = hi;
                     }
                 }
-                if (CZ_TP2_TILE_FENCE) __builtin_amdgcn_sched_barrier(0);     // one accumulator tile at a time (they leave the AGPRs 16 by 16)
             }
             __syncthreads();                                   // B: X holds the intermediate activation
             __builtin_amdgcn_s_setprio(3);
             conv_kloop<E, C, 2, 1, CTW>(X, wq2, lane, acc);
             __builtin_amdgcn_s_setprio(0);
-            if (CZ_TP2_BIAS_EARLY) bias_request(b2);
+            bias_request(b2);
             __syncthreads();                                   // K2: every wave has read it
-            if (CZ_TP2_BIAS_EARLY) bias_pin();
+            bias_pin();
             asm volatile("" : "+v"(ln2), "+v"(kb2));
             // epilogue 2: X <- relu(acc + b2 + skip)
 #pragma unroll
@@ -979,12 +818,11 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int chn = (wg + c) * 32 + g * 8 + kb2 * 4;
-                        const f32x4 bv = CZ_TP2_BIAS_EARLY ? bq[c][g] : *reinterpret_cast<const f32x4*>(b2 + chn);
+                        const f32x4 bv = bq[c][g];
                         const int off = row * G::RB + (((chn >> 3) ^ (row & G::SWZ)) << 4) + (chn & 7) * 2;
                         float vv[4] = {acc[cp][g * 4 + 0] + bv[0], acc[cp][g * 4 + 1] + bv[1], acc[cp][g * 4 + 2] + bv[2],
                                        acc[cp][g * 4 + 3] + bv[3]};
-                        const c8k::u32x2 sk = !CZ_TP2_SKIP_LDS ? skip[cp][g]
-                                              : (p < 3 ? *reinterpret_cast<const c8k::u32x2*>(SK + off) : skip[c * 3 + p - 3][g]);
+                        const c8k::u32x2 sk = p < 3 ? *reinterpret_cast<const c8k::u32x2*>(SK + off) : skip[c * 3 + p - 3][g];
                         const Quad<E> sh = __builtin_bit_cast(Quad<E>, sk);
                         Quad<E> o;
 #pragma unroll
@@ -996,7 +834,6 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
                         *reinterpret_cast<Quad<E>*>(X + off) = o;
                     }
                 }
-                if (CZ_TP2_TILE_FENCE) __builtin_amdgcn_sched_barrier(0);
             }
             __syncthreads();                                   // C: the block's result is in X
         }
@@ -1018,11 +855,8 @@ __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
 // timing build (tools/rb_stamps.py; never the default library): shader-cycle stamps of one matrix wave's and one copy
 // wave's sections of one steady-state board of k_resblock_c8
 __device__ long long g_rb_stamps[32];
-__device__ int g_rb_knob;              // timing experiments (wrong results): bits switch parts of the c6 store path off
 #define RB_STAMP(i) do { if (stamp_on) g_rb_stamps[i] = clock64(); } while (0)
-#define RB_KNOB() g_rb_knob
 #else
-#define RB_KNOB() 0
 #define RB_STAMP(i) do { } while (0)
 #endif
 
@@ -1047,9 +881,6 @@ __device__ int g_rb_knob;              // timing experiments (wrong results): bi
 // over the occupied squares (see k_resblock_pipe<FIRST> below: the same algorithm, here producing the c8 triple) instead
 // of loading it.  HEADS: the last block; the copy waves apply the two 1 x 1 head convolutions to the staged activation.
 // Arithmetic and its order are k_conv3x3_c8's: bit-identical to two cz_conv3x3_c8 launches.
-#ifndef CZ_FIRST_TERMS
-#define CZ_FIRST_TERMS 1
-#endif
 constexpr int CZ_FIRST_PRIO = 3;   // issue priority of the copy waves while they compute the fused input layer (the matrix waves
                                    // run their K loops at 3; at 0 the gather starves: first block 3.53 -> 3.48 ms)
 namespace rb8 {
@@ -1178,8 +1009,6 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
         //  from pass B's mapping, 16 bytes at a 64-byte lane stride, cost 0.1 ms per launch more; streaming (nt) stores 0.13.)
         const int k_out = C6 ? __builtin_amdgcn_readfirstlane(pack_ints(w2p)[3]) : 0;
         auto store_tile_c6 = [&](int to, int ct2) __attribute__((always_inline)) {
-            const int knob = RB_KNOB();
-            if (knob & 4) return;
             const size_t ebase = (size_t)to * 90 * C;
             const float s_hi = __builtin_ldexpf(1.0f, k_out), s_lo = __builtin_ldexpf(1.0f, k_out - cf8::X_LO_SHIFT);
             struct alignas(16) H8 { Quad<_Float16> a, b; };
@@ -1193,7 +1022,7 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 H8 h;
                 h.a.e[0] = (_Float16)f0.x; h.a.e[1] = (_Float16)f0.y; h.a.e[2] = (_Float16)f0.z; h.a.e[3] = (_Float16)f0.w;
                 h.b.e[0] = (_Float16)f1.x; h.b.e[1] = (_Float16)f1.y; h.b.e[2] = (_Float16)f1.z; h.b.e[3] = (_Float16)f1.w;
-                if (!(knob & 1)) reinterpret_cast<uint4*>(yh + ebase)[i] = __builtin_bit_cast(uint4, h);
+                reinterpret_cast<uint4*>(yh + ebase)[i] = __builtin_bit_cast(uint4, h);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
@@ -1218,18 +1047,17 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 const u32x6 pl = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(al, bl, s_lo);
                 const u32x6 pv = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(av, bv, s_hi);
                 unsigned char* row = yc + ebase * 2 + (size_t)qq * 2 * C;
-                if (knob & 2) continue;
                 *reinterpret_cast<uint4*>(row + 16 * c6_chunk(0, blk)) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-                *reinterpret_cast<uint2*>(row + 16 * c6_chunk(0, blk) + 16 + c6_tail_half(qq)) = make_uint2(pl[4], pl[5]);
+                *reinterpret_cast<uint2*>(row + 16 * c6_chunk(0, blk) + 16) = make_uint2(pl[4], pl[5]);
                 *reinterpret_cast<uint4*>(row + 16 * c6_chunk(1, blk)) = make_uint4(pv[0], pv[1], pv[2], pv[3]);
-                *reinterpret_cast<uint2*>(row + 16 * c6_chunk(1, blk) + 16 + c6_tail_half(qq)) = make_uint2(pv[4], pv[5]);
+                *reinterpret_cast<uint2*>(row + 16 * c6_chunk(1, blk) + 16) = make_uint2(pv[4], pv[5]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
         // (two call sites each; a wrapper lambda around them was NOT inlined by the compiler: a call inside the kernel, 2.5x
         //  the scratch and 17 % of the launch time)
         // (k_out == CZ_C6_OUT_C8: the last c6 block of a hybrid c6>N tower hands a c8 image to the c8 blocks behind it)
-#define CZ_STORE_BOARD(to, ct2) do { if (C6 && !HEADS && !yf && k_out != CZ_C6_OUT_C8 && !(RB_KNOB() & 8)) store_tile_c6(to, ct2); else store_tile(to, ct2); } while (0)
+#define CZ_STORE_BOARD(to, ct2) do { if (C6 && !HEADS && !yf && k_out != CZ_C6_OUT_C8) store_tile_c6(to, ct2); else store_tile(to, ct2); } while (0)
         // registers -> X image.  Loaded boards: 16-byte chunks of both parts; FIRST: the thread's 8 channels of a pixel are
         // one 16-byte chunk of the f16 row and two 8-byte pieces of the c8 row [lo8 x 128 | e4m3(x) x 128]
         auto write_x = [&](int ct2) {
@@ -1323,10 +1151,7 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 cur_tap[it] = 0;
             }
         };
-        // CZ_FIRST_TERMS (build switch, 1 or 2): table rows fetched per chunk and ROUND.  A round is one L2 round trip; with 2 the
-        // walk of a board takes half as many of them (two rows in flight per chunk) at 48 more registers; the rows are added
-        // in the same order either way (bit-identical results).  max_rounds counts TERMS.
-#if CZ_FIRST_TERMS == 1
+        // one table row per chunk and ROUND, a round being one L2 round trip (two rows per round: rejected, EXPERIMENTS.md)
         auto first_rounds = [&](int max_rounds) {
 #pragma unroll 1
             for (int round = 0; round < max_rounds; ++round) {
@@ -1365,60 +1190,6 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 }
             }
         };
-#else
-        auto first_rounds = [&](int max_rounds) {
-            constexpr int FT = CZ_FIRST_TERMS;
-#pragma unroll 1
-            for (int round = 0; round < max_rounds; round += FT) {
-                uint32_t any = 0u;
-                bool act[FT][LITER];
-                const float4* tp[FT][LITER];
-#pragma unroll
-                for (int k = 0; k < FT; ++k) {
-#pragma unroll
-                    for (int it = 0; it < LITER; ++it) {
-                        if (cur_m[it] == 0u && occ[it] != 0u) {
-                            const int tap = __builtin_ctz(occ[it]);
-                            occ[it] &= occ[it] - 1u;
-                            const int p = prow + 16 * it;
-                            cur_tap[it] = tap;
-                            cur_m[it] = mk[p + (tap / 5 - 2) * 9 + (tap % 5 - 2)];
-                        }
-                        any |= cur_m[it];
-                        act[k][it] = cur_m[it] != 0u;
-                        tp[k][it] = nullptr;
-                        if (act[k][it]) {
-                            const int c = __builtin_ctz(cur_m[it]);
-                            tp[k][it] = reinterpret_cast<const float4*>(fa.table + ((size_t)(c * 25 + cur_tap[it]) * 128 + c8 * 8));
-                            cur_m[it] &= cur_m[it] - 1u;
-                        }
-                    }
-                }
-                if (!__ballot(any != 0u)) break;
-                float4 wa[FT][LITER], wb[FT][LITER];
-#pragma unroll
-                for (int k = 0; k < FT; ++k)
-#pragma unroll
-                    for (int it = 0; it < LITER; ++it) {
-                        wa[k][it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        wb[k][it] = wa[k][it];
-                        if (act[k][it]) {
-                            wa[k][it] = tp[k][it][0];
-                            wb[k][it] = tp[k][it][1];
-                        }
-                    }
-#pragma unroll
-                for (int k = 0; k < FT; ++k)
-#pragma unroll
-                    for (int it = 0; it < LITER; ++it) {
-                        if (act[k][it]) {
-                            acc[it][0] += wa[k][it].x; acc[it][1] += wa[k][it].y; acc[it][2] += wa[k][it].z; acc[it][3] += wa[k][it].w;
-                            acc[it][4] += wb[k][it].x; acc[it][5] += wb[k][it].y; acc[it][6] += wb[k][it].z; acc[it][7] += wb[k][it].w;
-                        }
-                    }
-            }
-        };
-#endif
         auto first_end = [&]() {                              // ReLU, c8 split, pack (see write_x)
 #pragma unroll
             for (int it = 0; it < LITER; ++it) {
@@ -1585,9 +1356,9 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 const int q = pp == 0 ? kb2 * 32 + ln2 : 64 + ln2;
                 if (pp == 0 || (kb2 == 0 && q < 90)) {
                     unsigned char* d0 = Y + PART + c6_lds_off(q, c6_chunk(0, wave));
-                    unsigned char* t0 = Y + PART + c6_lds_off(q, c6_chunk(0, wave) + 1) + c6_tail_half(q);
+                    unsigned char* t0 = Y + PART + c6_lds_off(q, c6_chunk(0, wave) + 1);
                     unsigned char* d1 = Y + PART + c6_lds_off(q, c6_chunk(1, wave));
-                    unsigned char* t1 = Y + PART + c6_lds_off(q, c6_chunk(1, wave) + 1) + c6_tail_half(q);
+                    unsigned char* t1 = Y + PART + c6_lds_off(q, c6_chunk(1, wave) + 1);
                     *reinterpret_cast<uint4*>(d0) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
                     *reinterpret_cast<uint2*>(t0) = make_uint2(pl[4], pl[5]);
                     *reinterpret_cast<uint4*>(d1) = make_uint4(pv[0], pv[1], pv[2], pv[3]);
@@ -1602,7 +1373,7 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
                 f32x32 xl;
                 if (!FIRST) {
                     const uint4 hd4 = *reinterpret_cast<const uint4*>(X + PART + c6_lds_off(row, c6_chunk(0, wave)));
-                    const uint2 tl2 = *reinterpret_cast<const uint2*>(X + PART + c6_lds_off(row, c6_chunk(0, wave) + 1) + c6_tail_half(row));
+                    const uint2 tl2 = *reinterpret_cast<const uint2*>(X + PART + c6_lds_off(row, c6_chunk(0, wave) + 1));
                     // the upper lane half wants the odd elements: it shifts the piece down by one element (6 bits), so that
                     // every lane reads element 2 r for its register r  (a select between xl[2 r] and xl[2 r + 1] is
                     // turned into a variable vector index by the compiler: 31 v_cndmask per element)
@@ -1684,7 +1455,7 @@ __global__ __launch_bounds__(512, 2) void k_resblock_c8(
     __syncthreads();                                           // E1
 }
 
-// (kernel 2d, the chains of residual blocks in one launch -- k_tower, k_tower_pairs -- live in csrc/xq_tower.hip)
+// (kernel 2d, the chain of 128-filter pair blocks in one launch -- k_tower_pairs4 -- lives in csrc/xq_tower.hip)
 
 // ---- kernel 2b: the residual block, software-pipelined over boards (128 filters, split operands) ------------------
 // Same arithmetic as k_resblock (bit-identical results), different schedule: the second epilogue of board t-1
@@ -2550,9 +2321,6 @@ __global__ __launch_bounds__((C / 32) * 64 + ip::COPY_THREADS, 1) void k_resbloc
 // pieces.  XF / YF as in k_resblock_ip_c8 (<0, 0> c8, <1, 1> c6, <0, 1> the tower's first c6 block; a chain runs one of them).  Per accumulator tile the same products in the same order and the same
 // epilogue arithmetic as k_resblock_ip_c8: bit-identical.
 constexpr int IP4_EXIT_PAIRS = 2, IP4_EXIT_HEADS = 3;
-#ifndef CZ_IP4_PROBE        // timing experiments (wrong results; 0 in the product): bit 0 = no epilogue 1, bit 1 = no epilogue 2
-#define CZ_IP4_PROBE 0
-#endif
 // MIX (with <1, 1>): the chain starts the tower -- its block 0 reads the input layer's c8 image (first filter c8-packed: CZ_F16C86)
 template <int C, int XF, int YF, bool MIX = false>
 __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
@@ -2568,8 +2336,11 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
     constexpr int CHUNKS = 180 * CPR, LITER = (CHUNKS + NTHR - 1) / NTHR;
     // exit_mode (the chain's LAST block, 128 filters: cz_tower's exits): 0 = the operand pair / fp32 (yf_last); IP4_EXIT_PAIRS =
     // (hi, lo) fp16 pairs [n][90][C] to yh and yc; IP4_EXIT_HEADS = the six 1 x 1 head features (hd).  Both stage relu(acc) as fp32
-    // in the board's dead image ([pixel][64 channels] per part, 16-byte chunks swizzled by the pixel) and apply k_tower's exit
-    // arithmetic, item for item: bit-identical to k_tower's exits.
+    // in the board's dead image ([pixel][64 channels] per part, 16-byte chunks swizzled by the pixel); the board's two waves then
+    // take items i = (pixel i >> 2, 32-channel block i & 3).  PAIRS: hi = fp16(r), lo = fp16(r - hi) per value, bit-identical to
+    // block-by-block launches.  HEADS: per item and head output the dot product over the block's 32 channels in channel order,
+    // the pixel's four items summed as (a0 + a1) + (a2 + a3), + bias, relu -- within the bound tests/test_gpu_tower.py asserts
+    // against the one-block HEADS kernels (their sums associate differently).
     constexpr int HW_OFF = BIAS_OFF + 2 * 2 * C * 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds[HW_OFF + (C == 128 ? 6 * C * 4 : 0)];   // bias[2 buffers][2 convolutions][C] | head filters
     const int NB = ch.n;
@@ -2747,7 +2518,6 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
 #pragma unroll
             for (int c = 0; c < CTW; ++c) {
                 const int tc = tile0 + c;
-                if (CZ_IP4_PROBE & 1) continue;
                 if (YF) {
 #pragma unroll
                     for (int pp = 0; pp < 2; ++pp) {
@@ -2839,8 +2609,7 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             auto stg = [&](int q, int chn) {
                 return (chn >> 6) * PSTR + (bd * 90 + q) * RB + (((((chn & 63) >> 2)) ^ (q & 15)) << 4);
             };
-            if (CZ_IP4_PROBE & 2) {
-            } else if (C == 128 && ex != 0) {
+            if (C == 128 && ex != 0) {
 #pragma unroll
                 for (int c = 0; c < CTW; ++c)
 #pragma unroll
@@ -2894,7 +2663,7 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             }
             __syncthreads();                                    // C: the result is in the images
             if (C == 128 && ex != 0) {
-                // the exit of board 2 t + bd by its two waves: item i = (pixel i >> 2, 32-channel block i & 3), as k_tower's copy waves
+                // the exit of board 2 t + bd by its two waves: item i = (pixel i >> 2, 32-channel block i & 3)
                 const int board = 2 * t + bd;
                 struct alignas(16) H8 { Quad<_Float16> a, b; };
                 const float* hwl = reinterpret_cast<const float*>(lds + HW_OFF);
@@ -3250,10 +3019,6 @@ inline float f16_bits_to_f32(uint16_t b)
 }  // namespace
 
 #ifdef CZ_RB_STAMPS
-extern "C" int cz_debug_rb_knob(int v)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_rb_knob), &v, sizeof(int)) == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-}
 extern "C" int cz_debug_rb_stamps(long long* out32_host)
 {
     return hipMemcpyFromSymbol(out32_host, HIP_SYMBOL(g_rb_stamps), sizeof(long long) * 32) == hipSuccess ? CZ_OK : CZ_ERR_HIP;
@@ -3935,8 +3700,7 @@ extern "C" int czi_tower4_launch(const void* x_hi, const void* x_img, int n_bloc
 }
 
 // n_blocks (1 .. 24) consecutive residual blocks of a 256-filter tower on plain fp16 / bf16 operands in one launch
-// (k_tower_plain2: a pair of boards per workgroup, one LDS image per board; k_tower_plain with CZ_TOWER_PLAIN_PAIR=0): the `deep`
-// 20 x 256 configuration is ONE launch.  Filters: cz_conv3x3_pack_weights(parts = 1).
+// (k_tower_plain2: a pair of boards per workgroup, one LDS image per board): the `deep` 20 x 256 configuration is ONE launch.  Filters: cz_conv3x3_pack_weights(parts = 1).
 extern "C" int cz_tower_plain(const void* x, int n_blocks, const void* const* w1_packed, const float* const* bias1,
                               const void* const* w2_packed, const float* const* bias2, void* y, int n_boards, int channels,
                               int dtype, const int32_t* n_dev, void* stream)
@@ -3962,27 +3726,14 @@ extern "C" int cz_tower_plain(const void* x, int n_blocks, const void* const* w1
         return CZ_ERR_HIP;
     }
     hipStream_t st = (hipStream_t)stream;
-    // CZ_TOWER_PLAIN_PAIR=0: one board per workgroup in X | Y (k_tower_plain, round 6's first version; A/B and the tests)
-    const char* pair_env = getenv("CZ_TOWER_PLAIN_PAIR");       // (read per call: the tests run both)
-    const bool pair = !(pair_env && pair_env[0] == '0');
-    if (pair) {
-        const int n_pairs = (n_boards + 1) / 2;
-        const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
-        if (dtype == CZ_F16)
-            hipLaunchKernelGGL((k_tower_plain2<_Float16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const _Float16*)x, ch,
-                               (_Float16*)y, n_boards, n_dev);
-        else
-            hipLaunchKernelGGL((k_tower_plain2<__bf16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const __bf16*)x, ch,
-                               (__bf16*)y, n_boards, n_dev);
-    } else {
-        const unsigned blocks = (unsigned)(n_boards < n_cu ? n_boards : n_cu);
-        if (dtype == CZ_F16)
-            hipLaunchKernelGGL((k_tower_plain<_Float16, 256, 2>), dim3(blocks), dim3((256 / 32 / 2 + 4) * 64), 0, st, (const _Float16*)x, ch,
-                               (_Float16*)y, n_boards, n_dev);
-        else
-            hipLaunchKernelGGL((k_tower_plain<__bf16, 256, 2>), dim3(blocks), dim3((256 / 32 / 2 + 4) * 64), 0, st, (const __bf16*)x, ch,
-                               (__bf16*)y, n_boards, n_dev);
-    }
+    const int n_pairs = (n_boards + 1) / 2;
+    const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
+    if (dtype == CZ_F16)
+        hipLaunchKernelGGL((k_tower_plain2<_Float16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const _Float16*)x, ch,
+                           (_Float16*)y, n_boards, n_dev);
+    else
+        hipLaunchKernelGGL((k_tower_plain2<__bf16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const __bf16*)x, ch,
+                           (__bf16*)y, n_boards, n_dev);
     if (hipGetLastError() != hipSuccess) {
         czi_set_error("cz_tower_plain: launch failed");
         return CZ_ERR_HIP;

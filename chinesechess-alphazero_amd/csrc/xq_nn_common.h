@@ -122,8 +122,7 @@ constexpr int RB = 256;
 //     channel of element e = 8 (e >> 3) + ((e >> 1) & 3) + 4 (e & 1)          (cz_conv3x3_c6_pack_weights: the same)
 // and the inverse conversion (sequential) hands accumulator register r of lane half kb its channel at element 2 r + kb.
 // In a 256-byte image row (HBM and LDS alike) piece (kind, block b, half kb) has its 16-byte head in logical chunk
-// 8 kind + 4 b + 2 kb -- where the e4m3 piece's first half sits -- and its 8-byte tail at the start of the next chunk
-// (c6_tail_half: with the CZ_C6_TAIL_SWZ build switch, its upper half for rows with bit 4 set -- measured and left off).
+// 8 kind + 4 b + 2 kb -- where the e4m3 piece's first half sits -- and its 8-byte tail at the start of the next chunk.
 // x_hi6 = bf6(x 2^-k), x_lo6 = bf6((x - f16(x)) 2^(11 - k)) with the image's exponent k from the calibration
 // (2^k * 28 >= the tensor's largest value; the conversion saturates), carried by the packed filters that read / write it.
 typedef __attribute__((ext_vector_type(6))) unsigned int u32x6;
@@ -135,8 +134,6 @@ __device__ __forceinline__ const int* pack_ints(const void* packed)
 __device__ __forceinline__ int c6_chunk(int kind, int blk32) { return 8 * kind + 4 * (blk32 >> 1) + 2 * (blk32 & 1); }
 // byte offsets of a piece's head inside a part's pixel row `row` (LDS: chunks swizzled by the row)
 __device__ __forceinline__ int c6_lds_off(int row, int chunk) { return row * RB + ((chunk ^ (row & 15)) << 4); }
-// byte offset of a piece's 8-byte tail inside its chunk (xq_c8_kloop.h CZ_C6_TAIL_SWZ): the upper half for rows with bit 4 set
-__device__ __forceinline__ int c6_tail_half(int row) { return CZ_C6_TAIL_SWZ ? (row >> 1) & 8 : 0; }
 
 }  // namespace rb8
 

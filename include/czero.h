@@ -359,48 +359,34 @@ int cz_input_conv_q(const void* planes, int planes_dtype, int in_planes, const v
 int cz_resblock_q(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1, const void* w2_packed,
                   const float* bias2, void* y_hi, void* y_lo, float* y_f32, int n_boards, int channels, int dtype,
                   int parts, const int32_t* n_dev, void* stream);
-/* (round 5) n_blocks (2 .. 8) CONSECUTIVE c6 residual blocks of a 128-filter tower in ONE launch (k_tower_c6): the same
- * arithmetic as n_blocks calls of cz_resblock(dtype CZ_F16C6) -- bit-identical results -- with the activations staying in the
- * CU's LDS between the blocks (a workgroup takes a pair of boards through the whole chain; HBM sees a board at the chain's
- * entry and exit only).  Replaces the inner part of the residual tower, agent/model.py:41-43 (`for _ in range(res_layer_num):
- * x = self._build_residual_block(x)`).  w1_packed / bias1 / w2_packed / bias2: HOST arrays of n_blocks DEVICE pointers
- * (cz_conv3x3_c6_pack_weights filters; every block's second filter carries a c6 output exponent, block b + 1 reads the image
- * block b writes).  x / y: c6 operand pairs [n_boards][90][128] f16 + [n_boards][90][256] bytes.  n_dev: compact queue (DEVICE
- * int32, may be NULL): min(n_boards, *n_dev) boards. */
-int cz_tower_c6(const void* x_hi, const void* x_c6, int n_blocks, const void* const* w1_packed, const float* const* bias1,
-                const void* const* w2_packed, const float* const* bias2, void* y_hi, void* y_c6, int n_boards,
-                const int32_t* n_dev, void* stream);
-/* The same chain ending on the tower's LAST block with the 1 x 1 head convolutions as its exit (cz_resblock_heads' outputs:
- * policy_feat [n][n_policy * 90], value_feat [n][n_value * 90] fp32, ReLU'd; agent/model.py:46-60, the heads' first layers).  The
- * head dot products are summed over a pixel's four 32-channel partial sums: equal to cz_resblock_heads up to the rounding of
- * that summation order (2e-6 relative). */
-int cz_tower_c6_heads(const void* x_hi, const void* x_c6, int n_blocks, const void* const* w1_packed, const float* const* bias1,
-                      const void* const* w2_packed, const float* const* bias2, const float* head_w, const float* head_b,
-                      float* policy_feat, float* value_feat, int n_boards, int n_policy, int n_value, const int32_t* n_dev,
-                      void* stream);
 /* (round 6) The chain for EVERY tower arithmetic.  A chain block's two images (the one its first convolution reads = the one the
  * block before wrote, and its intermediate image) each have a format: */
 #define CZ_IMG_C8 0      /* f16 + e4m3 corrections (cz_conv3x3_c8_pack_weights filters read it) */
 #define CZ_IMG_C6 1      /* f16 + bf6 pieces with an exponent (cz_conv3x3_c6_pack_weights) */
 #define CZ_IMG_PAIR 2    /* (hi, lo) fp16 / bf16 pair (cz_conv3x3_pack_weights, parts = 2) */
 #define CZ_EXIT_HEADS 3  /* exit only: the 1 x 1 head convolutions instead of an image */
-/* cz_tower: n_blocks (1 .. 8) consecutive residual blocks on the c8 OR the c6 arithmetic in ONE launch -- bit-identical to
- * n_blocks calls of cz_resblock with the matching dtype.  Kernel (end of round 6): k_resblock_ip4_c8<128> -- a pair of boards
- * per workgroup with one LDS image each, both epilogues in place, FOUR matrix waves of two channel tiles (a pixel fragment from
- * LDS feeds two MFMAs, no copy waves); environment CZ_TOWER4=0: k_tower (the pair alternating through X | X | Y with copy waves
- * converting the staged result) -- same bits, 6 % slower in the engine.  fmt_x[b] / fmt_y[b] (HOST int arrays; NULL = all CZ_IMG_C6): the
+/* cz_tower: n_blocks (1 .. 8) consecutive residual blocks of a 128-filter tower on the c8 OR the c6 arithmetic in ONE launch --
+ * bit-identical to n_blocks calls of cz_resblock with the matching dtype, with the activations staying in the CU's LDS between
+ * the blocks (HBM sees a board at the chain's entry and exit only).  Kernel: k_resblock_ip4_c8<128> -- a pair of boards per
+ * workgroup with one LDS image each, both epilogues in place, FOUR matrix waves of two channel tiles (a pixel fragment from LDS
+ * feeds two MFMAs, no copy waves).  w1_packed / bias1 / w2_packed / bias2: HOST arrays of n_blocks DEVICE pointers
+ * (cz_conv3x3_c8_pack_weights / cz_conv3x3_c6_pack_weights filters; block b + 1 reads the image block b writes).  x / y: operand
+ * pairs [n_boards][90][128] f16 + [n_boards][90][256] bytes.  fmt_x[b] / fmt_y[b] (HOST int arrays; NULL = all CZ_IMG_C6): the
  * format of the image block b's first / second filter reads -- one format per chain (all CZ_IMG_C8 or all CZ_IMG_C6; a hybrid
  * tower is one chain per arithmetic).  exit_fmt: what the last block's result becomes -- CZ_IMG_C6 / CZ_IMG_C8: that operand
  * pair in (y_hi, y_img) (a c6 chain whose last block carries y_exp = 127 ends on CZ_IMG_C8: the hand-over of a "c6>N" tower);
  * CZ_IMG_PAIR (c8 chains): (hi, lo) fp16 pairs, y_img = the lo array [n][90][128] f16: the hand-over of a "c8>N" tower to its
  * f16x3 blocks (cz_resblock's y_f32 + cz_split_bias_act in one); CZ_EXIT_HEADS: the head features (cz_resblock_heads'
- * outputs; y_hi / y_img unused).  Replaces agent/model.py:41-43 for those blocks. */
+ * outputs: policy_feat [n][n_policy * 90], value_feat [n][n_value * 90] fp32, ReLU'd; y_hi / y_img unused), the head dot
+ * products summed over a pixel's four 32-channel partial sums: equal to cz_resblock_heads up to the rounding of that order.
+ * n_dev: compact queue (DEVICE int32, may be NULL): min(n_boards, *n_dev) boards.  Replaces agent/model.py:41-43 for those
+ * blocks. */
 int cz_tower(const void* x_hi, const void* x_img, int n_blocks, const void* const* w1_packed, const float* const* bias1,
              const void* const* w2_packed, const float* const* bias2, const int* fmt_x, const int* fmt_y, int exit_fmt,
              void* y_hi, void* y_img, const float* head_w, const float* head_b, float* policy_feat, float* value_feat,
              int n_policy, int n_value, int n_boards, const int32_t* n_dev, void* stream);
-/* cz_tower_pairs: the same for (hi, lo) pair blocks (f16x3 / bf16x3 arithmetic, dtype CZ_F16 / CZ_BF16; k_tower_pairs):
- * bit-identical to n_blocks calls of cz_resblock(parts = 2).  head_w != NULL: the chain ends on the tower's last block and
+/* cz_tower_pairs: the same for (hi, lo) pair blocks (f16x3 / bf16x3 arithmetic, dtype CZ_F16 / CZ_BF16; k_tower_pairs4<E, 128>,
+ * the four-wave shape of k_resblock_ip4_c8): bit-identical to n_blocks calls of cz_resblock(parts = 2).  head_w != NULL: the chain ends on the tower's last block and
  * writes the head features (from hi + lo of the block's result) instead of (y_hi, y_lo). */
 int cz_tower_pairs(const void* x_hi, const void* x_lo, int n_blocks, const void* const* w1_packed, const float* const* bias1,
                    const void* const* w2_packed, const float* const* bias2, void* y_hi, void* y_lo, const float* head_w,
@@ -424,7 +410,7 @@ int cz_resblock_chain(const void* x_hi, const void* x_img, int n_blocks, const v
  * (dtype CZ_F16 / CZ_BF16, cz_conv3x3_pack_weights with parts = 1) in ONE launch -- BASELINE configs[4], the 20 x 256 fp16 tower,
  * is a single launch: a workgroup takes a PAIR of boards through all blocks with ONE LDS image per board (a filter fragment
  * feeds both boards; the intermediate activation overwrites the block's input, whose values wait as the skip operand in
- * registers / spare LDS; environment CZ_TOWER_PLAIN_PAIR=0: one board in two images).  Bit-identical to n_blocks calls of
+ * registers / spare LDS; k_tower_plain2).  Bit-identical to n_blocks calls of
  * cz_resblock(parts = 1).  x / y: [n_boards][90][256]. */
 int cz_tower_plain(const void* x, int n_blocks, const void* const* w1_packed, const float* const* bias1,
                    const void* const* w2_packed, const float* const* bias2, void* y, int n_boards, int channels, int dtype,

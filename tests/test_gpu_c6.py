@@ -137,8 +137,8 @@ def test_c6_saturation_is_graceful():
 
 @pytest.mark.parametrize("blocks", [4, 7])
 def test_chained_c6_tower_is_bit_identical_to_block_by_block(blocks):
-    """cz_tower_c6 (k_tower_c6, round 5): the consecutive c6 inner blocks in ONE launch, activations staying in LDS (a workgroup
-    takes a pair of boards through the chain; results staged inside the dead image of the other slot and converted in place).
+    """cz_tower on c6 blocks (k_resblock_ip4_c8<128>): the consecutive c6 inner blocks in ONE launch, activations staying in LDS
+    (a workgroup takes a pair of boards through the chain, one image per board, both epilogues in place).
     Same arithmetic, accumulation order and conversions as one k_resblock_c8<.., C6> launch per block: the network's outputs are
     IDENTICAL -- for batch sizes that give the workgroups one board (the odd-count path: the board runs in both slots), two,
     three, and many; through the compact queue as well."""
@@ -173,7 +173,8 @@ def test_chained_c6_tower_is_bit_identical_to_block_by_block(blocks):
 
 @pytest.mark.parametrize("blocks", [3, 7])
 def test_chain_through_the_last_block_with_the_heads_as_its_exit(blocks):
-    """cz_tower_c6_heads (the default where the whole tower is c6; CZ_TOWER_HEADS=0 switches it off): the chain ends on the tower's last block and the 1 x 1 head convolutions are
+    """cz_tower with the CZ_EXIT_HEADS exit (the default where the whole tower is c6; CZ_TOWER_HEADS=0 switches it off): the
+    chain ends on the tower's last block and the 1 x 1 head convolutions are
     its exit pass.  The head dot products are summed in a different order than the unchained launch's (four 32-channel partial
     sums per pixel instead of sixteen 8-channel ones), everything else is identical: policy / value agree to float32 rounding."""
     import torch

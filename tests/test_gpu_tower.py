@@ -36,10 +36,19 @@ def _launches(g, planes, **kw):
     return out, launches
 
 
-@pytest.mark.parametrize("tower4", ["1", "0"])          # cz_tower on k_resblock_ip4_c8<128> (default) / on k_tower (CZ_TOWER4=0)
+def _queue(n, host_count):
+    """The board count of a forward over n boards: on the host (host_count "1": the whole batch) or on the device (host_count
+    "0": the compact queue -- the rows permuted, the count a quarter short of the launch shape).  Returns (kwargs, count)."""
+    if host_count == "1":
+        return {}, n
+    import torch
+    m = n - n // 4
+    return {"rows": torch.randperm(n, device="cuda").int(), "count": torch.tensor([m], dtype=torch.int32, device="cuda")}, m
+
+
+@pytest.mark.parametrize("host_count", ["1", "0"])
 @pytest.mark.parametrize("arith", ARITHS)
-def test_chained_tower_is_bit_identical_to_block_by_block(arith, tower4, monkeypatch):
-    monkeypatch.setenv("CZ_TOWER4", tower4)
+def test_chained_tower_is_bit_identical_to_block_by_block(arith, host_count):
     import torch
     from cchess_alphazero.agent.model import tower_plan
     blocks = 7
@@ -48,12 +57,14 @@ def test_chained_tower_is_bit_identical_to_block_by_block(arith, tower4, monkeyp
     want = [len(st[1]) if st[0] in ("tower", "pairs") else 1 for st in tower_plan(g.block_kinds(), chain_heads=False)]
     for n in (1, 37, 256, 300, 700, 1100):
         planes = planes_all[:n].contiguous()
+        kw, m = _queue(n, host_count)
         g.chain_blocks = False
-        (p0, v0), l0 = _launches(g, planes)
+        (p0, v0), l0 = _launches(g, planes, **kw)
         assert l0 == [1] * blocks, l0
         g.chain_blocks = True
-        (p1, v1), l1 = _launches(g, planes)
+        (p1, v1), l1 = _launches(g, planes, **kw)
         assert l1 == want, (l1, want)
+        p0, v0, p1, v1 = p0[:m], v0[:m], p1[:m], v1[:m]
         assert torch.isfinite(p1).all() and torch.isfinite(v1).all()
         assert torch.equal(p0, p1) and torch.equal(v0, v1), (arith, n, (p0 - p1).abs().max().item(), (v0 - v1).abs().max().item())
     # compact queue: rows / count on the device
@@ -86,9 +97,9 @@ def test_short_towers_chain_too(arith, blocks):
                 assert torch.equal(p0, p1) and torch.equal(v0, v1), (arith, blocks, n)
 
 
-@pytest.mark.parametrize("tower4", ["1", "0"])
+@pytest.mark.parametrize("host_count", ["1", "0"])
 @pytest.mark.parametrize("arith", ["c6>5", "c8", "c8>3", "f16x3"])
-def test_heads_as_the_last_chains_exit(arith, tower4, monkeypatch):
+def test_heads_as_the_last_chains_exit(arith, host_count):
     """The default: the tower's last block is inside the last chain and the 1 x 1 head convolutions are its exit pass.  The head
     dot products are summed over four 32-channel partial sums per pixel (the one-block HEADS kernels: sixteen 8-channel ones);
     the pair chains take the block's value as hi + lo of its operand pair (k_resblock<HEADS> keeps the fp32 value: an fp16 pair
@@ -96,16 +107,17 @@ def test_heads_as_the_last_chains_exit(arith, tower4, monkeypatch):
     value agree to float32 rounding."""
     import torch
     from cchess_alphazero.agent.model import tower_plan
-    monkeypatch.setenv("CZ_TOWER4", tower4)
     g, planes_all = _net(arith, 7)
     want = [len(st[1]) if st[0] in ("tower", "pairs") else 1 for st in tower_plan(g.block_kinds())]
     for n in (1, 37, 300, 700):
         planes = planes_all[:n].contiguous()
+        kw, m = _queue(n, host_count)
         g.chain_heads = False
-        p0, v0 = (t.clone() for t in g(planes))
+        p0, v0 = (t.clone() for t in g(planes, **kw))
         g.chain_heads = True
-        (p1, v1), l1 = _launches(g, planes)
+        (p1, v1), l1 = _launches(g, planes, **kw)
         assert l1 == want and sum(l1) == 7, (l1, want)
+        p0, v0, p1, v1 = p0[:m], v0[:m], p1[:m], v1[:m]
         assert torch.isfinite(p1).all() and (p0 - p1).abs().max().item() < 5e-6 and (v0 - v1).abs().max().item() < 3e-5, \
             (arith, n, (p0 - p1).abs().max().item(), (v0 - v1).abs().max().item())
 
@@ -131,22 +143,6 @@ def test_the_guards_choice_for_a_peaked_policy_runs_as_three_launches():
     assert launches == [1, n8 - 1, 7 - n8], (name, launches)
     m = measure_against_reference(g, reference_forward_f64(net, planes), planes)
     assert within_guard(m, tol=1e-4, logit_tol=LOGIT_TOL * 1.5), m           # (fresh positions, not the calibration set)
-
-
-@pytest.mark.parametrize("arith", ["c6", "c8", "c6>3", "c8>3"])
-def test_both_chain_kernels_give_the_same_bits(arith, monkeypatch):
-    """cz_tower on k_tower (CZ_TOWER4=0) and on the four-wave pair kernel k_resblock_ip4_c8<128> (round 6, default): same
-    products in the same order per accumulator tile, the exits (operand image, fp16 pairs, head features) computed item for item
-    the same way -- identical network outputs, heads exit included."""
-    import torch
-    g, planes_all = _net(arith, 7)
-    for n in (1, 37, 300, 1100):
-        planes = planes_all[:n].contiguous()
-        monkeypatch.setenv("CZ_TOWER4", "0")
-        p0, v0 = (t.clone() for t in g(planes))
-        monkeypatch.setenv("CZ_TOWER4", "1")
-        p1, v1 = g(planes)
-        assert torch.equal(p0, p1) and torch.equal(v0, v1), (arith, n, (p0 - p1).abs().max().item())
 
 
 def test_bf16_pairs_keep_their_heads_launch():
@@ -205,11 +201,11 @@ def test_192_filter_tower_chains_are_bit_identical(arith, blocks, monkeypatch):
 
 
 @pytest.mark.parametrize("dtype,blocks", [("float16", 20), ("float16", 3), ("bfloat16", 5), ("float16", 26)])
-def test_deep_tower_on_plain_operands_is_one_launch(dtype, blocks, monkeypatch):
+def test_deep_tower_on_plain_operands_is_one_launch(dtype, blocks):
     """cz_tower_plain (BASELINE configs[4]: 20 x 256, fp16 MFMA evaluation): all blocks of a 256-filter tower on plain 2-byte
     operands in one launch (24 at most) -- a pair of boards per workgroup with ONE LDS image per board (k_tower_plain2: the
-    skip values wait in registers while the intermediate activation overwrites them), or CZ_TOWER_PLAIN_PAIR=0: one board in
-    two images (k_tower_plain).  Both equal to one k_resblock launch per block."""
+    skip values wait in registers while the intermediate activation overwrites them).  Equal to one k_resblock launch per
+    block."""
     import torch
     from cchess_alphazero.agent.model import CChessNet, InferenceNet, calibration_planes
     torch.manual_seed(13)
@@ -223,23 +219,19 @@ def test_deep_tower_on_plain_operands_is_one_launch(dtype, blocks, monkeypatch):
         (p0, v0), l0 = _launches(g, planes)
         assert l0 == [1] * blocks, l0
         g.chain_blocks = True
-        for pair in ("1", "0"):
-            monkeypatch.setenv("CZ_TOWER_PLAIN_PAIR", pair)
-            (p1, v1), l1 = _launches(g, planes)
-            assert l1 == ([24, blocks - 24] if blocks > 24 else [blocks]), l1
-            assert torch.isfinite(p1).all() and torch.equal(p0, p1) and torch.equal(v0, v1), \
-                (dtype, blocks, n, pair, (p0 - p1).abs().max().item())
+        (p1, v1), l1 = _launches(g, planes)
+        assert l1 == ([24, blocks - 24] if blocks > 24 else [blocks]), l1
+        assert torch.isfinite(p1).all() and torch.equal(p0, p1) and torch.equal(v0, v1), \
+            (dtype, blocks, n, (p0 - p1).abs().max().item())
     # the board count on the device (cz_tower_plain's n_dev; an odd count: the last pair is half empty, rows beyond it untouched)
     from cchess_alphazero import _native
     bl = [g._block_params(i) for i in range(min(blocks, 3))]
     x = (torch.randn((300, 90, 256), device="cuda") * 0.5).to(getattr(torch, dtype))
     want = _native.tower_plain(x[:189].contiguous(), bl, torch.empty_like(x[:189]))
     count = torch.tensor([189], dtype=torch.int32, device="cuda")
-    for pair in ("1", "0"):
-        monkeypatch.setenv("CZ_TOWER_PLAIN_PAIR", pair)
-        y = torch.full_like(x, 7.0)
-        _native.tower_plain(x, bl, y, count=count)
-        assert torch.equal(y[:189], want) and bool((y[189:] == 7.0).all()), (dtype, pair)
+    y = torch.full_like(x, 7.0)
+    _native.tower_plain(x, bl, y, count=count)
+    assert torch.equal(y[:189], want) and bool((y[189:] == 7.0).all()), dtype
 
 
 def test_tower_entry_points_reject_what_they_cannot_run():

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU (round 5): the chained c6 tower (cz_tower_c6): its bit-identity test, then per-launch times of the 7 x 128 tower with the
+# GPU (round 5): the chained c6 tower (cz_tower on c6 blocks): its bit-identity test, then per-launch times of the 7 x 128 tower with the
 # inner blocks one per launch (CZ_TOWER_CHAIN=0) and chained (=1), alternating.
 set -u
 mkdir -p gpurun_out
