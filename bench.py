@@ -10,11 +10,14 @@ one ResNet forward over the evaluation queue.  Workload at N=1 = BASELINE.json c
 4096 concurrent games per GPU, 800 sims/move, 7-block x 128-filter net, random-init weights, synthetic self-play
 from the opening position.  Games shard across ranks (disjoint game ids, no data-path collective); RCCL is used
 only to all-reduce the counters.  `--gpus N` without a launcher re-executes itself under torch.distributed.run.
-Rank 0 prints ONE JSON line: the timed steps (`value`), and at N=1 a sustained leg of 3000 more rounds in the same
-invocation (`sustained` / `value_sustained`: games in every phase, finished games replaced, measured plies/s and
-games/hour, tree memory, tree_resets), the roofline of the dominant kernel measured with HIP events on its stream,
-the rule-kernel micro-suite and the CPU baseline (the C port of the reference's tree + rules on every CPU the
-container may use).  `--config eval` times the evaluator arena on the arena worker instead.
+Rank 0 prints ONE JSON line: the timed steps (`value`) and the roofline of the dominant kernel measured with HIP
+events on its stream during those steps.  A plain run does nothing else: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line.  `--full` adds, in the same invocation: at N=1 a sustained leg of 3000 more rounds
+(`sustained` / `value_sustained`: games in every phase, finished games replaced, measured plies/s and games/hour, tree
+memory, tree_resets), the numerics check of the network against the fp32 PyTorch module, the short legs of the other
+BASELINE configurations (`other_configs`), the rule-kernel micro-suite and the CPU baseline (the C port of the
+reference's tree + rules on every CPU the container may use).  `--config eval` times the evaluator arena on the arena
+worker instead.
 """
 import argparse
 import json
@@ -160,7 +163,7 @@ def emit(out):
     print(line, flush=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -176,6 +179,10 @@ def parse():
     ap.add_argument("--dtype", default=None, choices=["float32", "bfloat16", "float16"])
     ap.add_argument("--trunk", default=None, choices=["mfma", "library"],
                     help="residual tower: hand-written MFMA convolution (default) or MIOpen")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the "
+                         "sustained leg, the numerics check, other_configs, the micro-suite and the CPU baseline (the "
+                         "--no-* options below leave out single parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-micro", action="store_true", help="skip the 1M-board rule-kernel micro-suite")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
@@ -183,8 +190,8 @@ def parse():
     ap.add_argument("--plain-resblock", action="store_true",
                     help="A/B: residual blocks on k_resblock instead of the software-pipelined k_resblock_pipe")
     ap.add_argument("--sustained-rounds", type=int, default=None,
-                    help="rounds of the sustained leg that follows the timed steps (default 3000 at N=1 for the "
-                         "'normal' config, 0 otherwise)")
+                    help="rounds of the sustained leg that follows the timed steps (default 3000 with --full at N=1 "
+                         "for the 'normal' config, 0 otherwise)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short legs of the other single-GPU BASELINE configurations (other_configs)")
     ap.add_argument("--other-config-seconds", type=float, default=6.0, help="timed seconds per other_configs leg")
@@ -198,10 +205,24 @@ def parse():
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy "
                          "(float32 / float64, a fixed sample where an output is large): two builds run with the same "
                          "arguments can then be compared output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     return args
+
+
+def extra_legs(args, world):
+    """What a self-play run does after its timed steps besides --dump-outputs.  A plain run: nothing, unless
+    --sustained-rounds asks for a sustained leg.  --full: the sustained leg (3000 rounds by default at N=1 for the
+    'normal' config without --graph), the numerics check, and at N=1 other_configs ('normal' config only), the
+    micro-suite and the CPU baseline, each unless its --no-* option is given."""
+    n_sus = args.sustained_rounds
+    if n_sus is None:
+        n_sus = 3000 if (args.full and world == 1 and args.config == "normal" and not args.graph) else 0
+    one = args.full and world == 1
+    return {"sustained_rounds": n_sus, "numerics_check": args.full,
+            "other_configs": one and args.config == "normal" and not args.no_other_configs,
+            "micro_suite": one and not args.no_micro, "cpu_baseline": one and not args.no_cpu_baseline}
 
 
 def spawn_ranks(args):
@@ -966,7 +987,8 @@ def other_configs(args, log):
                  "accumulate, random-init weights, from INIT_STATE"))
 
     def arena():
-        ns = argparse.Namespace(config="eval", games=None, sims_per_round=None, dtype=None, trunk=None, warmup=2, steps=16)
+        ns = argparse.Namespace(config="eval", games=None, sims_per_round=None, dtype=None, trunk=None, warmup=2, steps=16,
+                                dump_outputs=None)
         r = run_arena(ns, build_config(ns), max_plies=ns.warmup + ns.steps + 1)
         keep = ("value", "unit", "steps", "ms_per_step", "dtype", "sims_per_s", "ms_per_round", "rounds_timed",
                 "compact_queue", "rows_evaluated_per_round_whole_arena", "network_tflops")
@@ -1137,9 +1159,8 @@ def main():
     log(f"timed {args.steps} steps in {dt:.2f}s")
     if args.dump_outputs and rank == 0:
         dump_selfplay(args.dump_outputs, eng, {k: d[k] for k in keys}, log)
-    n_sus = args.sustained_rounds
-    if n_sus is None:
-        n_sus = 3000 if (world == 1 and args.config == "normal" and not args.graph) else 0
+    extra = extra_legs(args, world)
+    n_sus = extra["sustained_rounds"]
     sus = None
     mem_timed = eng.search.memory_info()
     if n_sus > 0:
@@ -1352,13 +1373,14 @@ def main():
             out["quote"] = ("value = the K timed steps the contract asks for (games in the opening phase); "
                             "value_sustained = the 3000-round leg of the same invocation, games in every phase: the figure "
                             "to quote for self-play throughput")
-        out["numerics_check"] = numerics_check(eng, ref_net, cfg)
-        out["numerics_within_tolerance"] = out["numerics_check"]["within_tolerance"]
-        out["numerics_logit_max_abs"] = out["numerics_check"]["policy_logit_max_abs_diff"]
-        sh = out["numerics_check"].get("sharpened") or {}
-        if "guard_selected_measured" in sh:
-            out["numerics_peaked_policy_max_abs"] = sh["guard_selected_measured"]["policy_max_abs"]
-            out["numerics_peaked_arith"] = sh["guard_selected"]
+        if extra["numerics_check"]:
+            out["numerics_check"] = numerics_check(eng, ref_net, cfg)
+            out["numerics_within_tolerance"] = out["numerics_check"]["within_tolerance"]
+            out["numerics_logit_max_abs"] = out["numerics_check"]["policy_logit_max_abs_diff"]
+            sh = out["numerics_check"].get("sharpened") or {}
+            if "guard_selected_measured" in sh:
+                out["numerics_peaked_policy_max_abs"] = sh["guard_selected_measured"]["policy_max_abs"]
+                out["numerics_peaked_arith"] = sh["guard_selected"]
         out["roofline_frac"] = (out.get("roofline") or {}).get("frac")
         out["collective"] = collective
     eng.close()                                              # every rank; the legs below need the device memory
@@ -1367,12 +1389,12 @@ def main():
     gc.collect()
     torch.cuda.empty_cache()                                 # (the search object sizes its pool from the FREE memory)
     if rank == 0:
-        if world == 1 and args.config == "normal" and not args.no_other_configs:
+        if extra["other_configs"]:
             out["other_configs"] = other_configs(args, log)
-        if not args.no_micro and world == 1:
+        if extra["micro_suite"]:
             out["micro_suite"] = micro_suite()
             log("micro-suite done")
-        if not args.no_cpu_baseline and world == 1:          # the CPU leg is reported at N = 1 only
+        if extra["cpu_baseline"]:                            # the CPU leg is reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_baseline_seconds)
             out["cpu_tree_only_expansions_per_s"] = out["cpu_baseline"]["value"]
             out["cpu_with_network_estimate"] = out["cpu_baseline"]["with_network_estimate"]["value"]

@@ -308,6 +308,27 @@ def test_bench_configs_follow_baseline():
         (64, 4, "bfloat16", "library")
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_extra_legs():
+    """bench.py: a plain run times its steps and nothing else (a sustained leg only when --sustained-rounds asks for one);
+    --full adds the sustained leg, the numerics check, other_configs, the micro-suite and the CPU baseline, each of which its
+    --no-* option leaves out again."""
+    import bench
+    none = {"sustained_rounds": 0, "numerics_check": False, "other_configs": False, "micro_suite": False,
+            "cpu_baseline": False}
+    assert bench.extra_legs(bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "4"]), 1) == none
+    assert bench.extra_legs(bench.parse(["--config", "eval"]), 1) == none
+    assert bench.extra_legs(bench.parse(["--sustained-rounds", "400"]), 1) == dict(none, sustained_rounds=400)
+    full = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "4", "--full"])
+    assert bench.extra_legs(full, 1) == {"sustained_rounds": 3000, "numerics_check": True, "other_configs": True,
+                                         "micro_suite": True, "cpu_baseline": True}
+    assert bench.extra_legs(full, 2) == dict(none, numerics_check=True)            # the single-GPU legs run at N = 1 only
+    assert bench.extra_legs(bench.parse(["--full", "--config", "deep"]), 1) == dict(
+        none, numerics_check=True, micro_suite=True, cpu_baseline=True)
+    assert bench.extra_legs(bench.parse(["--full", "--graph"]), 1)["sustained_rounds"] == 0
+    trimmed = bench.parse(["--full", "--sustained-rounds", "0", "--no-micro", "--no-cpu-baseline", "--no-other-configs"])
+    assert bench.extra_legs(trimmed, 1) == dict(none, numerics_check=True)
+
+
 def test_bench_gpus_flag_spawns_that_many_ranks():
     """`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run with N ranks (the
     driver's own command shape) and reports n_gpus = the number of ranks that took part in the counter all-reduce;

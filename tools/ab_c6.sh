@@ -4,7 +4,7 @@
 export CZ_BENCH_FULL_LINE=1   # bench.py prints its full record on stdout for these scripts (round 5: the default is the compact line)
 export TMPDIR=/tmp
 for a in c8 c6 c8 c6; do
-  CZ_TOWER_ARITH=$a timeout 200 python bench.py --steps 30 --warmup 6 --sustained-rounds 0 --no-micro --no-cpu-baseline --no-other-configs --no-dist 2>/dev/null > /tmp/w.json
+  CZ_TOWER_ARITH=$a timeout 200 python bench.py --full --steps 30 --warmup 6 --sustained-rounds 0 --no-micro --no-cpu-baseline --no-other-configs --no-dist 2>/dev/null > /tmp/w.json
   python - $a <<'PY'
 import json, sys
 d = json.loads(open("/tmp/w.json").readline())
