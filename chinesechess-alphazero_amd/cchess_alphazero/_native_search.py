@@ -1,5 +1,6 @@
 """ctypes binding of the batched search object of libczero.so (cz_search_* in include/czero.h)."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -13,6 +14,13 @@ COUNTER_NAMES = ["sims", "expansions", "terminal_sims", "repetition_sims", "park
                  "cyc_select", "cyc_rules", "cyc_hash", "cyc_expand", "cyc_rep", "cyc_attach", "cyc_resume_load",
                  "cyc_kernel_select", "cyc_kernel_backup"]
 MAX_NO_ACT = 32          # csrc/xq_search.h: banned root moves per game and ply
+VISIT_STRIDE = 784       # include/czero.h cz_visit_entry: 16-byte header, uint16 label[128], int32 n[128]
+VISIT_BANNED = 0x8000    # label bit: the edge is banned at that ply (no_act)
+GAME_VISITS_LOST = 4     # finished-game record flag: the game has no complete visit record
+
+# One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
+# was banned at that ply; the root's own count; the ply; whether the player resigned there.
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign")
 
 
 class SearchCfg(C.Structure):
@@ -58,13 +66,16 @@ def declare(L):
     L.cz_search_game_counters.argtypes = [vp, vp, vp]
     L.cz_search_game_counters.restype = i32
     L.cz_search_drain_records.argtypes = [vp, C.POINTER(C.c_uint), vp, i32, C.POINTER(C.c_int), vp]
+    L.cz_search_record_visits.argtypes = [vp, i32, i32, vp]
+    L.cz_search_drain_visits.argtypes = [vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
     for n in ("cz_search_create", "cz_search_destroy", "cz_search_info", "cz_search_start_selfplay",
               "cz_search_set_roots", "cz_search_round", "cz_search_reset_trees", "cz_search_pending",
               "cz_search_root_stats", "cz_search_choose", "cz_search_counters", "cz_search_drain_records",
-              "cz_debug_sqrt", "cz_search_set_sims", "cz_search_policy_logits"):
+              "cz_debug_sqrt", "cz_search_set_sims", "cz_search_policy_logits", "cz_search_record_visits",
+              "cz_search_drain_visits"):
         getattr(L, n).restype = i32
 
 
@@ -147,6 +158,10 @@ class Search:
         self.masks = None                      # leaf_masks(): [slots, 96] int32 occupancy boards beside the planes
         self.planes_off = False                # leaf_planes(False): new leaves are written as occupancy boards only
         self._cursor = C.c_uint(0)
+        self.visit_capacity = 0                # record_visits(): entries the device ring holds, 0 = off
+        self._visits = {}                      # game id -> [(ply, raw entry)] of games not finished yet
+        self._raw_visits = []                  # fetched entries not yet sorted by game (pull_visits(defer=True))
+        self._visits_dropped = 0
 
     # -- lifetime --
     def close(self):
@@ -209,6 +224,62 @@ class Search:
         """The policy rows given to round() are raw logits (agent/model.py forward(logits=True)): the priors are formed from
         the legal moves' logits alone -- the softmax denominator cancels in the reference's renormalisation."""
         _native.check(self.L.cz_search_policy_logits(self.h, int(bool(on))), "cz_search_policy_logits")
+
+    def record_visits(self, on=True, capacity=0):
+        """Self-play: every searched ply writes its root's visit counts into a device ring (cz_search_record_visits);
+        drain_records(with_visits=True) hands them out with the games.  capacity: ring entries (0 = 64 per game); drain it
+        (pull_visits / drain_records) at least every capacity / (8 * n_games) rounds and nothing is dropped.  Switch it on
+        before start_selfplay() (games already under way come out without visits) and before a graph capture."""
+        _native.check(self.L.cz_search_record_visits(self.h, int(bool(on)), int(capacity), self._stream()),
+                      "cz_search_record_visits")
+        self.visit_capacity = (int(capacity) or 64 * self.G) if on else 0
+        self._visits = {}
+        self._raw_visits = []
+        self._visits_dropped = 0
+
+    def pull_visits(self, defer=False):
+        """Move the entries waiting in the device ring to the host (kept until their game's record is drained).
+        Returns the number of entries moved; synchronises the stream.  defer=True only copies them: the host-side sorting
+        waits for ingest_visits() (or the next drain), which a caller runs once the next round is queued on the device."""
+        if not self.visit_capacity:
+            return 0
+        n, dropped = C.c_int(0), C.c_uint64(0)
+        _native.check(self.L.cz_search_drain_visits(self.h, None, 0, C.byref(n), C.byref(dropped), self._stream()),
+                      "cz_search_drain_visits")
+        if n.value == 0:
+            self._visits_dropped = int(dropped.value)
+            if not defer:
+                self.ingest_visits()
+            return 0
+        buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
+        _native.check(self.L.cz_search_drain_visits(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(dropped),
+                                                    self._stream()), "cz_search_drain_visits")
+        self._visits_dropped = int(dropped.value)
+        self._raw_visits.append(buf)
+        if not defer:
+            self.ingest_visits()
+        return n.value
+
+    def ingest_visits(self):
+        """Sort the entries fetched by pull_visits(defer=True) by game."""
+        raw, self._raw_visits = self._raw_visits, []
+        for buf in raw:
+            gids = buf[:, 0:4].copy().view(np.uint32)[:, 0]
+            plies = buf[:, 4:6].copy().view(np.uint16)[:, 0]
+            for i in range(buf.shape[0]):      # kept trimmed to the root's edges until the game's record arrives
+                ne = int(buf[i, 6])
+                row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
+                self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
+
+    @staticmethod
+    def parse_visit_entry(row):
+        """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges]) -> VisitEntry."""
+        a = np.frombuffer(row, dtype=np.uint8)
+        ne = int(a[6])
+        lab = a[16:16 + 2 * ne].view(np.uint16)
+        return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
+                          banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
+                          ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -372,9 +443,16 @@ class Search:
         return action.cpu().numpy()
 
     def counters(self):
+        """The counters summed over the games; with record_visits on also `visits_dropped` (ring entries lost, as of now)."""
         out = (C.c_uint64 * self.n_counters)()
         _native.check(self.L.cz_search_counters(self.h, out, self._stream()), "cz_search_counters")
-        return {k: int(out[i]) for i, k in enumerate(COUNTER_NAMES[:self.n_counters])}
+        d = {k: int(out[i]) for i, k in enumerate(COUNTER_NAMES[:self.n_counters])}
+        if self.visit_capacity:
+            n, dropped = C.c_int(0), C.c_uint64(0)
+            _native.check(self.L.cz_search_drain_visits(self.h, None, 0, C.byref(n), C.byref(dropped), self._stream()),
+                          "cz_search_drain_visits")
+            d["visits_dropped"] = int(dropped.value)
+        return d
 
     def game_counters(self):
         """The counters per game, before the sum: numpy uint64 [G, n_counters] (columns: COUNTER_NAMES)."""
@@ -384,8 +462,15 @@ class Search:
                       "cz_search_game_counters")
         return out
 
-    def drain_records(self, max_records=4096):
-        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, moves[labels])."""
+    def drain_records(self, max_records=4096, with_visits=False):
+        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, moves[labels]).
+        with_visits (record_visits on): each dict also has `visits`, the game's VisitEntry list in ply order -- one per
+        searched ply, the resignation ply included, the appended king capture not -- or None when the game's record is
+        incomplete (an entry was dropped, or the game began before recording was switched on)."""
+        if with_visits and not self.visit_capacity:
+            raise ValueError("drain_records(with_visits=True) needs record_visits() on")
+        if self.visit_capacity:
+            self.pull_visits()                 # (every entry of a game is written before its record)
         buf = np.zeros((max_records, self.record_stride), dtype=np.uint8)
         n = C.c_int(0)
         _native.check(self.L.cz_search_drain_records(self.h, C.byref(self._cursor), buf.ctypes.data, max_records,
@@ -397,6 +482,11 @@ class Search:
             mv = buf[i, 16:16 + 2 * min(turns, self.max_plies + 2)].view(np.uint16)
             out.append(dict(game_id=int(buf[i, :4].view(np.uint32)[0]), turns=turns, value=int(hdr[2]),
                             store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv.copy()))
+            if self.visit_capacity:
+                ents = sorted(self._visits.pop(out[-1]["game_id"], []), key=lambda e: e[0])
+                if with_visits:
+                    ok = not (hdr[3] & GAME_VISITS_LOST) and [p for p, _ in ents] == list(range(len(ents)))
+                    out[-1]["visits"] = [self.parse_visit_entry(r) for _, r in ents] if ok else None
         return out
 
 

@@ -91,6 +91,8 @@ class EngineConfig(_Section):
                                                   # columns, the priors come from the legal moves' logits (cz_search_policy_logits)
                          leaf_masks=True,         # the search kernel also writes every leaf as a 96-word occupancy board, which the
                                                   # first block's fused input layer takes instead of scanning the planes
+                         record_visits=False,     # play records carry each searched move's root visit counts:
+                                                  # items [move, value, pi] (run.py self --record-visits)
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

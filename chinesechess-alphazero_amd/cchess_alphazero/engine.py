@@ -22,10 +22,14 @@ from cchess_alphazero._native_search import Search
 from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE
+from cchess_alphazero.lib.data_helper import pi_from_visits
 
 logger = getLogger(__name__)
 
 _PLANES_CODE = {torch.float32: _native.F32, torch.float16: _native.F16, torch.bfloat16: _native.BF16}
+# record_visits: the device ring holds 8 plies per game per round for this many rounds (one round records at most 8 plies
+# of a game), and the engine moves it to the host this often -- no entry can be dropped
+VISIT_DRAIN_ROUNDS = 16
 
 
 def bytes_per_expansion(mean_depth, mean_edges, mean_leaf_moves):
@@ -37,11 +41,12 @@ def bytes_per_expansion(mean_depth, mean_edges, mean_leaf_moves):
 class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
-                 use_history=False, trunk=None):
+                 use_history=False, trunk=None, record_visits=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
-        filter count allows) or "library" (MIOpen), see agent/model.py InferenceNet."""
+        filter count allows) or "library" (MIOpen), see agent/model.py InferenceNet.  record_visits: every searched
+        ply's root visit counts go into the records (drain: items [move, value, pi]); None = config.engine.record_visits."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -81,6 +86,12 @@ class SelfPlayEngine:
         self.rounds = 0
         self.seed = seed
         self._graph = None
+        if record_visits is None:
+            record_visits = getattr(getattr(config, "engine", None), "record_visits", False)
+        self.record_visits = bool(record_visits)
+        self._since_pull = 0
+        if self.record_visits:
+            self.search.record_visits(True, capacity=8 * VISIT_DRAIN_ROUNDS * self.search.G)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -231,6 +242,14 @@ class SelfPlayEngine:
             self._round()
             self._forward()
         self.rounds += 1
+        if self.record_visits:
+            # the entries fetched by the previous pull are sorted while this round runs; a pull itself waits for the
+            # device, so the host work is kept out of that gap
+            self.search.ingest_visits()
+            self._since_pull += 1
+            if self._since_pull >= VISIT_DRAIN_ROUNDS:
+                self.search.pull_visits(defer=True)
+                self._since_pull = 0
 
     def capture_graph(self, warmup=2):
         """Capture kernel + network forward of one round into a HIP graph (no host work per round)."""
@@ -242,6 +261,9 @@ class SelfPlayEngine:
                 self._forward()
                 self.rounds += 1
         torch.cuda.current_stream(self.device).wait_stream(side)
+        if self.record_visits:
+            self.search.pull_visits()
+            self._since_pull = 0
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._round()
@@ -254,15 +276,24 @@ class SelfPlayEngine:
 
     def drain(self, max_records=4096):
         """Finished games since the last call, as the reference's play-record lists
-        ([init_state, [move, value], ...], self_play.py:202-208) plus metadata."""
+        ([init_state, [move, value], ...], self_play.py:202-208) plus metadata.  With record_visits a searched move's
+        item is [move, value, pi] (lib/data_helper.py pi_from_visits); the appended king capture, and every move of a game
+        whose visit record is incomplete (`visits` None), keep the two-element form."""
         out = []
-        for r in self.search.drain_records(max_records):
+        for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
+            vis = r.get("visits")
             data = [INIT_STATE]
             for i, m in enumerate(r["moves"]):
-                data.append([ActionLabelsRed[int(m)], v if i % 2 == 0 else -v])
+                item = [ActionLabelsRed[int(m)], v if i % 2 == 0 else -v]
+                if vis is not None and i < len(vis) and not vis[i].resign:
+                    e = vis[i]
+                    item.append(pi_from_visits(e.moves, e.n, e.banned, ActionLabelsRed))
+                data.append(item)
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
                             resigned=r["resigned"], data=data))
+            if self.record_visits:
+                out[-1]["visits"] = vis
         return out
 
     def close(self):

@@ -1,7 +1,11 @@
 """Play-record files (reference: cchess_alphazero/lib/data_helper.py and SelfPlayWorker.save_play_data,
 worker/self_play.py:214-251).  The format is what the reference's ``opt`` trainer reads:
 one JSON list ``[init_state, [move, value], [move, value], ...]`` per file (``nb_game_in_file`` games are
-concatenated into one flat list, as the reference does)."""
+concatenated into one flat list, as the reference does).
+
+With ``engine.record_visits`` on, a searched move's item is ``[move, value, pi]``: pi = ``[[move, count], ...]``, the
+root's visit counts when the move was chosen (see ``pi_from_visits``).  The reference's trainer reads only ``item[0]``
+and ``item[1]`` (worker/optimize.py:245-246), so such files feed it unchanged."""
 import json
 import os
 from datetime import datetime, timedelta, timezone
@@ -9,6 +13,14 @@ from glob import glob
 from logging import getLogger
 
 logger = getLogger(__name__)
+
+
+def pi_from_visits(moves, n, banned, labels):
+    """One searched ply's root (edge order: label indices, visit counts, banned flags) -> the record's pi, a list of
+    ``[move, count]`` in edge order without banned edges and edges that have no visit.  count / sum(counts) is the
+    policy calc_policy returns (agent/player.py:375-406: banned edges zeroed, then normalised).  labels: label index ->
+    move string (ActionLabelsRed; the moves are in the mover's frame, like the record's moves)."""
+    return [[labels[int(m)], int(c)] for m, c, b in zip(moves, n, banned) if not b and int(c) > 0]
 
 
 def get_game_data_filenames(rc):
@@ -48,7 +60,7 @@ class PlayDataWriter:
         return s if self.world == 1 else f"{s}-r{self.rank}"
 
     def add_game(self, data):
-        """data: [init_state, [move, value], ...] of one stored game."""
+        """data: [init_state, [move, value], ...] of one stored game (items may carry pi: [move, value, pi])."""
         self.buffer += data
         idx, self.idx = self.idx, self.idx + 1
         if idx % self.config.play_data.nb_game_in_file != 0:

@@ -34,6 +34,8 @@ _FLAGS = [
     ("--net-dtype", dict(choices=["float32", "bfloat16", "float16"], help="engine: network precision")),
     ("--max-rounds", dict(type=int, help="engine: stop after this many lock-step rounds (default: never)")),
     ("--max-games", dict(type=int, help="engine: stop after this many finished games (default: never)")),
+    ("--record-visits", dict(action="store_true",
+                             help="(self) play records carry each searched move's root visit counts: [move, value, pi]")),
 ]
 
 
@@ -62,6 +64,8 @@ def build_config(args):
     if args.net_dtype:
         engine.net_dtype = args.net_dtype
     engine.max_rounds, engine.max_games = args.max_rounds, args.max_games
+    if args.record_visits:
+        engine.record_visits = True
     return config
 
 

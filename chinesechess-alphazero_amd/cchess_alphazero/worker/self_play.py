@@ -158,7 +158,8 @@ class SelfPlayWorker:
                     logger.info(f"rounds={r} games={c['games']} plies={c['plies']} "
                                 f"expansions/s={c['expansions'] / dt:.0f} games/h={c['games'] / dt * 3600:.0f} "
                                 f"tree_resets={lc['tree_resets']} overflow_sims={lc['overflow_sims']} "
-                                f"no_act_truncated={lc.get('no_act_truncated', 0)}")
+                                f"no_act_truncated={lc.get('no_act_truncated', 0)}"
+                                + (f" visits_dropped={lc['visits_dropped']}" if "visits_dropped" in lc else ""))
                 if max_games is not None and c["games"] >= max_games:
                     break
             if max_rounds is not None and r >= max_rounds:

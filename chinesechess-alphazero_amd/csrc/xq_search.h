@@ -149,7 +149,34 @@ struct GameRecord {
     uint32_t game_id;
     int32_t turns;
     int32_t value;      // from red's view: +1 red won, -1 black won, 0 draw (self_play.py:190-191)
-    uint32_t flags;     // bit 0 store, bit 1 resigned
+    uint32_t flags;     // bit 0 store, bit 1 resigned, bit 2 (visit recording on only) an entry of the game was dropped
+};
+constexpr uint32_t GAME_VISITS_LOST = 4u;
+
+// ---- root visit record of self-play (cz_search_record_visits) ----
+// One entry per searched ply, written by k_advance right after the move is chosen: the root's edges in edge order
+// (get_legal_moves order, the reference's node.a), each with its exact visit count.  Fixed-stride entries in a ring
+// that is never overwritten: an entry that finds the ring full is dropped and counted.  The buffers reach k_advance
+// as an argument of its own (SearchParams / SearchBuffers go to every search kernel and stay as they are).
+constexpr int VISIT_MAX_EDGES = 128;               // = MAXMOVES
+constexpr uint16_t VISIT_BANNED = 0x8000;          // label bit: the edge is in the ply's no_act list
+constexpr uint32_t VISIT_RESIGN = 1u;              // entry flag: the player resigned at this ply
+struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
+    uint32_t game_id;
+    uint16_t ply;       // turns when the move was chosen
+    uint8_t n_edges;
+    uint8_t flags;
+    int32_t sum_n;      // the root's own visit count
+    uint32_t reserved;
+};
+constexpr int VISIT_STRIDE = (int)sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES + 4 * VISIT_MAX_EDGES;   // 784 B
+
+struct VisitRing {
+    uint8_t* ring;                  // [cap][VISIT_STRIDE]; NULL = recording off
+    unsigned int* ctl;              // [0] entries ever reserved, [1] entries the host has drained (written between launches)
+    unsigned long long* dropped;    // [1] entries that found the ring full
+    uint8_t* g_lost;                // [G] the game in slot g lost an entry (or started before recording was switched on)
+    unsigned int cap;
 };
 
 }  // namespace xq

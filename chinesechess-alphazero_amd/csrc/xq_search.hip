@@ -1187,7 +1187,7 @@ XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView
 }
 
 XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameView& gv, int turns, int value,
-                      bool store, bool resigned)
+                      bool store, bool resigned, uint32_t extra_flags)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -1200,7 +1200,7 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
         hdr->game_id = B.g_game_id[g];
         hdr->turns = turns;
         hdr->value = value;
-        hdr->flags = (store ? 1u : 0u) | (resigned ? 2u : 0u);
+        hdr->flags = (store ? 1u : 0u) | (resigned ? 2u : 0u) | extra_flags;
     }
     uint16_t* mv = reinterpret_cast<uint16_t*>(rec + sizeof(GameRecord));
     const uint16_t* acts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
@@ -1210,8 +1210,58 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
     if (resigned) count(gv, CT_RESIGNS);
 }
 
+// Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
+// counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
+XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns, bool resigned)
+{
+    const int lane = lane_id();
+    const int g = gv.g;
+    const int root = uni(B.g_root[g]);
+    if (root < 0) return;
+    char* base = rec_ptr(gv, (uint32_t)root);
+    const NodeHdr hdr = load_hdr(base);
+    int nm = (int)(hdr.meta & 0xFF);
+    const uint16_t* pm = node_mv(base, nm);
+    if (nm > VISIT_MAX_EDGES) nm = VISIT_MAX_EDGES;
+    unsigned int pos = 0;
+    int drop = 0;
+    if (lane == 0) {
+        pos = atomicAdd(&V.ctl[0], 1u);
+        drop = pos - V.ctl[1] >= V.cap ? 1 : 0;             // full: never overwrite what the host has not drained
+        if (drop) {
+            atomicAdd(V.dropped, 1ull);
+            V.g_lost[g] = 1;
+        }
+    }
+    pos = uniu(pos);
+    if (uni(drop)) return;
+    uint8_t* e = V.ring + (size_t)(pos % V.cap) * VISIT_STRIDE;
+    uint16_t* lab = reinterpret_cast<uint16_t*>(e + sizeof(VisitEntryHdr));
+    int32_t* cnt = reinterpret_cast<int32_t*>(e + sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES);
+    const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+    const int n_no_act = uni((int)B.g_n_no_act[g]);
+    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
+    for (int j = lane; j < nm; j += 64) {
+        const uint16_t mv = pm[j];
+        bool banned = false;
+        for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+        lab[j] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+        cnt[j] = sb ? sb[j].n : 0;
+    }
+    if (lane == 0) {
+        VisitEntryHdr* h = reinterpret_cast<VisitEntryHdr*>(e);
+        h->game_id = B.g_game_id[g];
+        h->ply = (uint16_t)turns;
+        h->n_edges = (uint8_t)nm;
+        h->flags = (uint8_t)(resigned ? VISIT_RESIGN : 0u);
+        h->sum_n = hdr.sum_n;
+        h->reserved = 0u;
+    }
+}
+
 // One ply of SelfPlayWorker.start_game after the search finished (self_play.py:124-212).
-XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L)
+XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
+                       const VisitRing& V)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -1222,6 +1272,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     uint16_t* hacts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
     const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
     const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
+    if (V.ring) emit_visits(B, gv, V, turns, action < 0);
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;
     int value = 0;
@@ -1313,7 +1364,13 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     bool store = true;
     if (turns < 10) store = philox_uniform(P.seed, game_id, 0, 1) > 0.9;   // :194-200
     wave_sync_global();
-    emit_record(P, B, gv, turns, value, store, resigned);
+    uint32_t extra = 0u;
+    if (V.ring) {                                                       // the next game in this slot starts complete
+        int lost = 0;
+        if (lane == 0) { lost = V.g_lost[g]; V.g_lost[g] = 0; }
+        extra = uni(lost) ? GAME_VISITS_LOST : 0u;
+    }
+    emit_record(P, B, gv, turns, value, store, resigned, extra);
     new_game(P, B, gv, L, game_id + P.game_id_stride);
 }
 
@@ -1502,7 +1559,7 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
 
 // End of a search: external mode marks the game READY; self-play mode plays the move, applies the game rules
 // and sets up the next search (or the next game).
-__global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B)
+__global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B, VisitRing V)
 {
     __shared__ SearchLDS L;
     const int g = blockIdx.x;
@@ -1512,7 +1569,7 @@ __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B)
     counters_begin(gv);
     if (P.mode == MODE_SELFPLAY) {
         for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
-            advance_game(P, B, gv, L);
+            advance_game(P, B, gv, L, V);
             if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
         }
     } else if (lane_id() == 0) {
@@ -1822,6 +1879,8 @@ struct cz_search {
     int device = 0;
     int prev_compact = 0;             // the previous round built a compact queue: its results are indexed by compact row
     int keep_chunks_created = 0;      // P.keep_chunks as sized at creation (cz_search_set_sims never goes below it)
+    VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
+    void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
 };
 
 namespace {
@@ -2035,6 +2094,7 @@ int cz_search_create(const cz_search_cfg* c, cz_search** out)
 int cz_search_destroy(cz_search* s)
 {
     if (!s) return CZ_OK;
+    (void)hipFree(s->vis_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
     delete s;
@@ -2107,6 +2167,8 @@ int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id
     s->P.seed = seed;
     s->P.game_id_stride = game_id_stride ? game_id_stride : (uint32_t)s->P.G;
     hipError_t e = hipMemsetAsync(s->B.ring_tail, 0, sizeof(unsigned int), (hipStream_t)stream);
+    if (e == hipSuccess && s->V.ring)                 // the games start now: their visit records will be complete
+        e = hipMemsetAsync(s->V.g_lost, 0, (size_t)s->P.G, (hipStream_t)stream);
     if (e != hipSuccess) return serr_hip("cz_search_start_selfplay", e);
     hipLaunchKernelGGL(k_pool_commit, dim3(1), dim3(1), 0, (hipStream_t)stream, s->B);
     hipLaunchKernelGGL(k_start_selfplay, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, first_game_id);
@@ -2141,7 +2203,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool hist = s->P.in_planes == 28;
     if (hist) hipLaunchKernelGGL(k_sim<true>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_BACKUP, consume_compact, q_rows, q_count);
     else hipLaunchKernelGGL(k_sim<false>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_BACKUP, consume_compact, q_rows, q_count);
-    hipLaunchKernelGGL(k_advance, grid, block, 0, st, s->P, s->B);
+    hipLaunchKernelGGL(k_advance, grid, block, 0, st, s->P, s->B, s->V);
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     if (hist) hipLaunchKernelGGL(k_sim<true>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_SELECT, compact, q_rows, q_count);
     else hipLaunchKernelGGL(k_sim<false>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_SELECT, compact, q_rows, q_count);
@@ -2197,6 +2259,82 @@ int cz_search_policy_logits(cz_search* s, int on)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_policy_logits: null handle");
     s->P.policy_logits = on ? 1 : 0;
+    return CZ_OK;
+}
+
+static_assert(sizeof(cz_visit_entry) == sizeof(VisitEntryHdr) && VISIT_STRIDE == 784, "czero.h: visit entry layout");
+static_assert(VISIT_MAX_EDGES == MAXMOVES, "a root has at most MAXMOVES edges");
+
+int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_visits: null handle");
+    if (capacity < 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity < 0");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffers
+    if (e != hipSuccess) return serr_hip("cz_search_record_visits", e);
+    (void)hipFree(s->vis_mem);
+    s->vis_mem = nullptr;
+    s->V = VisitRing{};
+    if (!on) return CZ_OK;
+    // default: 64 entries per game -- one k_advance launch records at most 8 plies of a game (the loop in k_advance),
+    // so a caller that drains at least every 8 rounds never loses an entry
+    const long long cap = capacity > 0 ? capacity : 64ll * s->P.G;
+    if (cap > 0x7fffffffll) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity too large");
+    const size_t ring_b = align_up((size_t)cap * VISIT_STRIDE), ctl_b = 256, G = (size_t)s->P.G;
+    e = hipMalloc(&s->vis_mem, ring_b + ctl_b + align_up(G));
+    if (e != hipSuccess) { s->vis_mem = nullptr; return serr_hip("cz_search_record_visits: hipMalloc", e); }
+    char* base = (char*)s->vis_mem;
+    e = hipMemsetAsync(base + ring_b, 0, ctl_b, st);
+    // games already under way lack their earlier plies: they are reported without visits
+    if (e == hipSuccess) e = hipMemsetAsync(base + ring_b + ctl_b, s->P.mode == MODE_SELFPLAY ? 1 : 0, G, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(s->vis_mem);
+        s->vis_mem = nullptr;
+        return serr_hip("cz_search_record_visits", e);
+    }
+    s->V.ring = (uint8_t*)base;
+    s->V.ctl = (unsigned int*)(base + ring_b);
+    s->V.dropped = (unsigned long long*)(base + ring_b + 16);   // (cz_search_drain_visits reads ctl and dropped in one copy)
+    s->V.g_lost = (uint8_t*)(base + ring_b + ctl_b);
+    s->V.cap = (unsigned int)cap;
+    return CZ_OK;
+}
+
+int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out, void* stream)
+{
+    if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits: bad argument");
+    if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits: visit recording is off");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned int ctl[6] = {0u, 0u, 0u, 0u, 0u, 0u};        // tail, head, -, -, dropped (64 bit): one copy
+    static_assert(sizeof(unsigned long long) == 8, "dropped counter is 64-bit");
+    hipError_t e = hipMemcpyAsync(ctl, s->V.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return serr_hip("cz_search_drain_visits", e);
+    unsigned long long dropped = 0ull;
+    memcpy(&dropped, &ctl[4], sizeof(dropped));
+    const unsigned int tail = ctl[0], head = ctl[1], cap = s->V.cap;
+    // reservations at or beyond head + cap were dropped by the kernel (and counted): the valid entries are [head, head + cap)
+    const unsigned int valid = tail - head < cap ? tail - head : cap;
+    if (dropped_out) *dropped_out = (uint64_t)dropped;
+    if (!host_buf) { *n_out = (int)valid; return CZ_OK; }
+    // all or nothing: a partial drain would have to remember where the dropped reservations lie
+    if (valid > (unsigned int)max_entries)
+        return serr(CZ_ERR_ARG, "cz_search_drain_visits: host_buf holds fewer entries than are waiting (ask with host_buf = NULL)");
+    const unsigned int k = valid;
+    unsigned int done = 0;
+    while (done < k && e == hipSuccess) {                // at most two runs: the ring may wrap once
+        const unsigned int at = (head + done) % cap;
+        const unsigned int run = (cap - at) < (k - done) ? (cap - at) : (k - done);
+        e = hipMemcpyAsync((char*)host_buf + (size_t)done * VISIT_STRIDE, s->V.ring + (size_t)at * VISIT_STRIDE,
+                           (size_t)run * VISIT_STRIDE, hipMemcpyDeviceToHost, st);
+        done += run;
+    }
+    const unsigned int new_head = tail;
+    if (e == hipSuccess) e = hipMemcpyAsync(s->V.ctl + 1, &new_head, sizeof(new_head), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return serr_hip("cz_search_drain_visits", e);
+    *n_out = (int)k;
     return CZ_OK;
 }
 

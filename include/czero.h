@@ -128,7 +128,8 @@ typedef struct cz_game_record {
     uint32_t game_id;
     int32_t turns;                   /* number of moves recorded */
     int32_t value;                   /* +1 red won, -1 black won, 0 draw (self_play.py:190-191) */
-    uint32_t flags;                  /* bit 0: store (self_play.py:194-200), bit 1: ended by resignation */
+    uint32_t flags;                  /* bit 0: store (self_play.py:194-200), bit 1: ended by resignation,
+                                        bit 2: (visit recording on) the game has no complete visit record */
 } cz_game_record;
 
 int cz_search_create(const cz_search_cfg* cfg, cz_search** out);   /* allocates device memory on the current device */
@@ -226,6 +227,35 @@ int cz_search_game_counters(cz_search* s, uint64_t* host_out, void* stream);
 /* copies finished-game records (record_stride bytes each) written since *cursor into HOST memory */
 int cz_search_drain_records(cz_search* s, unsigned int* cursor, void* host_buf, int max_records, int* n_out,
                             void* stream);
+/* ---- root visit record of self-play (off by default) ----
+ * on = 1: from now on every searched ply of a self-play game writes one entry -- the root's visit counts at the moment
+ * the move is chosen (calc_policy, agent/player.py:375-406, before the temperature), the resignation ply included; an
+ * appended king capture (self_play.py:177-184) is not searched and has none.  capacity = entries the device ring holds
+ * (0 = 64 * n_games).  One round records at most 8 plies of a game (a search with nothing left to do ends in the same
+ * launch), so a caller that drains at least every capacity / (8 * n_games) rounds loses nothing.  The ring is never
+ * overwritten: an entry that finds it full is dropped and counted, and the game's finished-game record then carries
+ * flag bit 2.  Games already under way when recording is switched on carry bit 2 as well; cz_search_start_selfplay
+ * starts every game complete.  on = 0 frees the buffers.  Synchronises the stream; not while a captured graph that
+ * holds the old buffers may still replay.  Device memory: capacity * 784 bytes + n_games + 256. */
+int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream);
+/* one ring entry, 784 bytes: this header, then uint16 label[128] (the root's edges in edge order, get_legal_moves
+ * order = the reference's node.a; mover frame like the record's moves; bit 15 set = banned at this ply, in its no_act
+ * list), then int32 n[128] (exact visit counts, carried-over visits of the reused subtree included).  Entries of one
+ * game appear in ply order, before the game's record. */
+typedef struct cz_visit_entry {
+    uint32_t game_id;
+    uint16_t ply;                    /* turns when the move was chosen */
+    uint8_t n_edges;
+    uint8_t flags;                   /* bit 0: the player resigned at this ply */
+    int32_t sum_n;                   /* the root's own visit count */
+    uint32_t reserved;
+} cz_visit_entry;
+/* Copies every entry written since the last call into HOST host_buf (784 bytes each) and frees their ring space;
+ * *n_out = entries copied.  host_buf = NULL: *n_out = entries waiting, nothing is consumed.  CZ_ERR_ARG when more are
+ * waiting than max_entries (nothing is consumed).  dropped_out (HOST, or NULL) = entries dropped since recording was
+ * switched on.  Synchronises the stream. */
+int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out,
+                           void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
