@@ -115,6 +115,16 @@ def _declare(L):
     for name in ("cz_label_tables", "cz_movegen", "cz_done", "cz_step", "cz_encode", "cz_check_or_catch",
                  "cz_be_catched", "cz_has_attack", "cz_rules_fused"):
         getattr(L, name).restype = i32
+    if hasattr(L, "cz_replay_games"):
+        L.cz_replay_games.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        L.cz_replay_games.restype = i32
+    if hasattr(L, "cz_gather_planes"):
+        L.cz_gather_planes.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+        L.cz_gather_planes.restype = i32
+    if hasattr(L, "cz_policy_value_loss"):
+        L.cz_policy_value_loss.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, C.c_float, C.c_float,
+                                           vp, vp, vp, vp, vp]
+        L.cz_policy_value_loss.restype = i32
     if hasattr(L, "cz_search_create"):
         from . import _native_search
         _native_search.declare(L)
@@ -209,6 +219,65 @@ def encode(boards, dtype=F32):
     planes = torch.empty((n, 14, 10, 9), dtype=torch_dtype(dtype), device=boards.device)
     check(lib().cz_encode(_dev(boards, torch.int8), n, C.c_void_p(planes.data_ptr()), dtype, _stream()), "cz_encode")
     return planes
+
+
+# ---- trainer data path and loss (csrc/xq_train.hip) ------------------------------------------------------------------
+def _opt(t, dtype):
+    return None if t is None else _dev(t, dtype)
+
+
+def replay_games(init_boards, labels, offsets):
+    """init_boards int8 [G, 90], labels uint16 [P], offsets int32 [G + 1] (device) -> (boards int8 [P, 90], prev int32 [P],
+    bad_ply int32 [G]): every game's positions before each move, game-major; prev = the position two plies earlier or -1;
+    bad_ply = the ply of a game's first invalid move, -1 if none (cz_replay_games)."""
+    import torch
+    require_gpu()
+    g, p = init_boards.shape[0], labels.shape[0]
+    dev = init_boards.device
+    boards = torch.empty((p, NSQ), dtype=torch.int8, device=dev)
+    prev = torch.empty((p,), dtype=torch.int32, device=dev)
+    bad = torch.empty((g,), dtype=torch.int32, device=dev)
+    check(lib().cz_replay_games(_dev(init_boards, torch.int8), _dev(labels, torch.uint16), _dev(offsets, torch.int32), g, p,
+                                _dev(boards, torch.int8), _dev(prev, torch.int32), _dev(bad, torch.int32), _stream()),
+          "cz_replay_games")
+    return boards, prev, bad
+
+
+def gather_planes(boards, prev, idx, depth=14, out=None):
+    """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B]); depth 28 adds the position prev[i]
+    (zero planes where prev is -1) (cz_gather_planes)."""
+    import torch
+    require_gpu()
+    b = idx.shape[0]
+    if out is None:
+        out = torch.empty((b, depth, 10, 9), dtype=torch.float32, device=idx.device)
+    assert out.shape == (b, depth, 10, 9)
+    check(lib().cz_gather_planes(_dev(boards, torch.int8), _opt(prev, torch.int32), boards.shape[0], _dev(idx, torch.int32),
+                                 b, depth, _dev(out, torch.float32), _stream()), "cz_gather_planes")
+    return out
+
+
+def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0):
+    """Per-row policy loss, squared value error and the gradients of w_p mean(policy loss) + w_v mean(sq. error) with
+    respect to the logits [B, 2086] and the value [B] (cz_policy_value_loss; mode 0 played one-hot, 1 visit counts).
+    logits may have a leading dimension > 2086 (a row-strided view).  Visit arrays with no entries (or None) leave every
+    row on the played move's one-hot."""
+    import torch
+    require_gpu()
+    assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
+        and logits.stride(1) == 1
+    b, dev = logits.shape[0], logits.device
+    pl = torch.empty((b,), dtype=torch.float32, device=dev)
+    se = torch.empty((b,), dtype=torch.float32, device=dev)
+    gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
+    gv = torch.empty((b,), dtype=torch.float32, device=dev)
+    check(lib().cz_policy_value_loss(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
+                                     _dev(idx, torch.int32), b, played.shape[0], _opt(row_ptr, torch.int32),
+                                     _opt(vis_label, torch.uint16), _opt(vis_count, torch.int32),
+                                     0 if vis_label is None else vis_label.shape[0], _dev(played, torch.uint16), _dev(z, torch.float32), int(mode), float(w_p), float(w_v),
+                                     _dev(pl, torch.float32), _dev(se, torch.float32), _dev(gl, torch.float32),
+                                     _dev(gv, torch.float32), _stream()), "cz_policy_value_loss")
+    return pl, se, gl, gv
 
 
 def check_or_catch(boards, moves):

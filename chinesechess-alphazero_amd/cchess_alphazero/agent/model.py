@@ -69,14 +69,16 @@ class CChessNet(nn.Module):
             x = blk(x)
         return x
 
-    def forward(self, x):
+    def forward(self, x, logits=False):
+        """-> (policy [B, 2086], value [B]); logits=True returns the policy head's logits instead of its softmax (the
+        trainer's loss, worker/optimize.py, takes the logits)."""
         x = self.trunk(x)
         p = F.relu(self.policy_bn(self.policy_conv(x)))
         p = self.policy_out(p.flatten(1))                      # Flatten order C,H,W (channels_first)
         v = F.relu(self.value_bn(self.value_conv(x)))
         v = F.relu(self.value_dense(v.flatten(1)))
         v = torch.tanh(self.value_out(v))
-        return F.softmax(p, dim=1), v.squeeze(1)
+        return (p if logits else F.softmax(p, dim=1)), v.squeeze(1)
 
     @classmethod
     def from_model_config(cls, mc):

@@ -25,6 +25,12 @@ def save_as_best_model(model):
     return model.save(*_best_paths(model))
 
 
+def save_as_next_generation_model(model):
+    """The trainer's hand-over to ``run.py eval`` (reference lib/model_helper.py, optimize.py:204-210)."""
+    rc = model.config.resource
+    return model.save(rc.next_generation_config_path, rc.next_generation_weight_path)
+
+
 def need_to_reload_best_model_weight(model):
     """True when the digest of the best-weight file differs from the digest of the weights in memory."""
     logger.debug("start reload the best model if changed")

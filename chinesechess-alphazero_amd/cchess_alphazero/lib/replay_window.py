@@ -1,0 +1,217 @@
+"""The trainer's replay window on the device (run.py opt, worker/optimize.py).
+
+The reference keeps its window as dense float32 arrays, 14 x 90 planes plus 2086 policy values per position
+(worker/optimize.py:261-281, about 13.4 KB a position).  Here a position costs its 90-byte board, the index of the
+position two plies back, the played label, the value and its visit counts in CSR form (about 100 B plus 6 B per visited
+edge); the minibatch's planes are built when it is drawn (``cz_gather_planes``) and the loss reads the sparse targets
+directly (``cz_policy_value_loss``), so neither planes nor dense targets exist for the whole window.
+
+Record files are replayed on the device, one wavefront per game (``cz_replay_games``): the boards are those of
+``record_decoder.expand_records`` bit for bit, and the positions are kept in the order ``expanding_data`` produces.
+
+Positions and visit entries are indexed with int32: a window holds at most 2^31 - 1 of each.  At `distribute`'s 90 M
+positions the visit entries reach that limit at about 24 visited edges per position (not measured on real records); a
+load beyond it raises ValueError instead of wrapping.
+"""
+from logging import getLogger
+
+import numpy as np
+import torch
+
+from cchess_alphazero import _native
+from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
+from cchess_alphazero.environment.static_env import state_to_array
+from cchess_alphazero.lib.record_decoder import split_games
+
+logger = getLogger(__name__)
+
+_LABEL = {m: i for i, m in enumerate(ActionLabelsRed)}
+MODES = {"played": 0, "visits": 1}
+INT32_MAX = 2 ** 31 - 1         # positions and visit entries are indexed with int32 (prev, row_ptr, the kernels' counts)
+
+
+class ReplayWindow:
+    """Positions of whole record files, appended in load order.  ``capacity`` is ``trainer.dataset_size``: ``full`` turns
+    true once it is reached, and the file that reaches it is kept whole (the reference's fill_queue checks the size before
+    each file).  depth 28 = ``has_history`` networks (state_history_to_planes)."""
+
+    def __init__(self, capacity, depth=14, device="cuda"):
+        if depth not in (14, 28):
+            raise ValueError(f"depth={depth}: expected 14 or 28")
+        _native.require_gpu()
+        self.capacity, self.depth = int(capacity), depth
+        self.device = torch.device(device)
+        self.n = 0                      # positions
+        self.nnz = 0                    # visit entries
+        self.n_games = 0
+        self.files = []                 # the files loaded, in load order
+        self._alloc(0, 0)
+
+    def _alloc(self, n, nnz):
+        d = self.device
+        self.boards = torch.empty((n, 90), dtype=torch.int8, device=d)
+        self.prev = torch.empty((n,), dtype=torch.int32, device=d)
+        self.played = torch.empty((n,), dtype=torch.uint16, device=d)
+        self.z = torch.empty((n,), dtype=torch.float32, device=d)
+        self.row_ptr = torch.zeros((n + 1,), dtype=torch.int32, device=d)
+        self.vis_label = torch.empty((nnz,), dtype=torch.uint16, device=d)
+        self.vis_count = torch.empty((nnz,), dtype=torch.int32, device=d)
+
+    def _reserve(self, n, nnz):
+        """Grow the device arrays to hold n positions and nnz entries: positions double up to the capacity and no further
+        (the file that crosses the capacity gets exactly the room it needs), visit entries double up to INT32_MAX."""
+        if n > self.boards.shape[0]:
+            cap = min(self.capacity, max(n, 1 << 16, 2 * self.boards.shape[0])) if n <= self.capacity else n
+            for name in ("boards", "prev", "played", "z"):
+                old = getattr(self, name)
+                new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
+                new[:self.n] = old[:self.n]
+                setattr(self, name, new)
+            rp = torch.zeros((cap + 1,), dtype=torch.int32, device=self.device)
+            rp[:self.n + 1] = self.row_ptr[:self.n + 1]
+            self.row_ptr = rp
+        if nnz > self.vis_label.shape[0]:
+            cap = min(INT32_MAX, max(nnz, 2 * self.vis_label.shape[0], 1 << 16))
+            for name in ("vis_label", "vis_count"):
+                old = getattr(self, name)
+                new = torch.empty((cap,), dtype=old.dtype, device=self.device)
+                new[:self.nnz] = old[:self.nnz]
+                setattr(self, name, new)
+
+    @property
+    def full(self):
+        return self.n >= self.capacity
+
+    def __len__(self):
+        return self.n
+
+    def load_file(self, path):
+        """Append the games of one record file.  Returns the number of positions added."""
+        from cchess_alphazero.lib.data_helper import read_game_data_from_file
+        data = read_game_data_from_file(path)
+        if not isinstance(data, list) or (data and not isinstance(data[0], str)):
+            raise ValueError(f"{path}: not a play record (a list that starts with a state string)")
+        n = self.add_games(split_games(data), source=path)
+        self.files.append(path)
+        return n
+
+    def add_games(self, games, source=None):
+        """games: ``[init_state, [move, value(, pi)], ...]`` lists.  Raises ValueError (naming the game and the ply) for a
+        move that is not a label or whose from-square is empty, and for items that are not ``[move, value(, pi)]``; the
+        window is unchanged then.  The window holds at most INT32_MAX positions and INT32_MAX visit entries (int32 indices:
+        about 24 visited edges per position at `distribute`'s 90 M positions); a load beyond either raises ValueError."""
+        where = f" in {source}" if source else ""
+        for gi, g in enumerate(games):
+            if not isinstance(g[0], str) or g[0].split(" ")[0].count("/") != 9:
+                raise ValueError(f"Game {gi} does not start with a state string{where}")
+        lens = [len(g) - 1 for g in games]
+        P = int(sum(lens))
+        if P == 0:
+            self.n_games += len(games)
+            return 0
+        labels = np.empty(P, dtype=np.uint16)
+        vals = np.empty(P, dtype=np.float32)
+        nvis = np.zeros(P, dtype=np.int64)
+        vl, vc = [], []
+        k = 0
+        lookup = _LABEL
+        for gi, g in enumerate(games):
+            if not isinstance(g[0], str):
+                raise ValueError(f"Game {gi} does not start with a state string{where}")
+            for t, item in enumerate(g[1:]):
+                try:
+                    lab = lookup.get(item[0])
+                    if lab is None:
+                        raise ValueError(f"Invalid move {item[0]!r} (game {gi}, ply {t}){where}")
+                    labels[k] = lab
+                    vals[k] = float(item[1])
+                    if len(item) >= 3:
+                        pi = item[2]
+                        for mv, c in pi:
+                            lb = lookup.get(mv)
+                            if lb is None:
+                                raise ValueError(f"Invalid visit move {mv!r} (game {gi}, ply {t}){where}")
+                            c = int(c)
+                            if c < 0:
+                                raise ValueError(f"Negative visit count (game {gi}, ply {t}){where}")
+                            vl.append(lb)
+                            vc.append(c)
+                        if len(pi) != len({mv for mv, _ in pi}):
+                            raise ValueError(f"Repeated visit move (game {gi}, ply {t}){where}")
+                        nvis[k] = len(pi)
+                except (TypeError, IndexError, KeyError) as e:
+                    raise ValueError(f"Malformed item {item!r} (game {gi}, ply {t}){where}: {e}") from None
+                k += 1
+        if self.n + P > INT32_MAX or self.nnz + len(vl) > INT32_MAX:
+            raise ValueError(f"the window would hold more than {INT32_MAX} positions or visit entries (int32 indices){where}")
+        dev = self.device
+        init = torch.from_numpy(np.stack([state_to_array(g[0]) for g in games])).to(dev)
+        offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+        boards, prev, bad = _native.replay_games(init, torch.from_numpy(labels).to(dev), torch.from_numpy(offsets).to(dev))
+        bad = bad.cpu().numpy()
+        if (bad != -1).any():
+            gi = int(np.flatnonzero(bad != -1)[0])
+            t = int(bad[gi])
+            raise ValueError(f"No chessman in {games[gi][1 + t][0]} (game {gi}, ply {t}){where}")
+        nnz = len(vl)
+        n0, z0 = self.n, self.nnz
+        self._reserve(n0 + P, z0 + nnz)
+        self.boards[n0:n0 + P] = boards
+        self.prev[n0:n0 + P] = torch.where(prev >= 0, prev + n0, prev)
+        self.played[n0:n0 + P] = torch.from_numpy(labels).to(dev)
+        self.z[n0:n0 + P] = torch.from_numpy(vals).to(dev)
+        rp = (z0 + np.cumsum(nvis)).astype(np.int32)
+        self.row_ptr[n0 + 1:n0 + P + 1] = torch.from_numpy(rp).to(dev)
+        if nnz:
+            self.vis_label[z0:z0 + nnz] = torch.from_numpy(np.asarray(vl, dtype=np.uint16)).to(dev)
+            self.vis_count[z0:z0 + nnz] = torch.from_numpy(np.asarray(vc, dtype=np.int32)).to(dev)
+        self.n, self.nnz = n0 + P, z0 + nnz
+        self.n_games += len(games)
+        return P
+
+    def planes(self, idx):
+        """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B] on the device)."""
+        return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth)
+
+    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0)):
+        """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
+        differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss)."""
+        return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]))
+
+    def dense_targets(self, idx, targets="visits"):
+        """Host float32 [B, 2086] policy targets of the positions idx as the loss kernel forms them (tests, tools)."""
+        rp = self.row_ptr[:self.n + 1].cpu().numpy()
+        lab = self.vis_label[:self.nnz].cpu().numpy()
+        cnt = self.vis_count[:self.nnz].cpu().numpy()
+        played = self.played[:self.n].cpu().numpy()
+        idx = np.asarray(idx.cpu() if hasattr(idx, "cpu") else idx)
+        out = np.zeros((len(idx), _native.NLABELS), dtype=np.float32)
+        for r, i in enumerate(idx):
+            lo, hi = rp[i], rp[i + 1]
+            total = int(cnt[lo:hi].sum())
+            if targets == "visits" and total > 0:
+                for k in range(lo, hi):
+                    out[r, lab[k]] = np.float32(int(cnt[k]) / total)
+            else:
+                out[r, played[i]] = 1.0
+        return out
+
+
+class _PolicyValueLoss(torch.autograd.Function):
+    """w_p * mean(policy loss) + w_v * mean(value loss) of a minibatch; backward hands out the kernel's gradients."""
+
+    @staticmethod
+    def forward(ctx, logits, v, idx, win, mode, w_p, w_v):
+        n = win.n
+        pl, se, gl, gv = _native.policy_value_loss(
+            logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
+            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v)
+        ctx.save_for_backward(gl, gv)
+        pm, vm = pl.mean(), se.mean()
+        ctx.mark_non_differentiable(pm, vm)
+        return w_p * pm + w_v * vm, pm, vm
+
+    @staticmethod
+    def backward(ctx, g_total, _g_pm, _g_vm):
+        gl, gv = ctx.saved_tensors
+        return g_total * gl, g_total * gv, None, None, None, None, None

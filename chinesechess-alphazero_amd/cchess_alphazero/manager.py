@@ -1,6 +1,7 @@
 """Command line of ``run.py`` -- same sub-commands and flags as the reference's cchess_alphazero/manager.py.
-``self`` (the hot path) and ``eval`` (the arena) are served by the MI355X engine; the other
-sub-commands of the reference (opt, play, sl, ob) are outside the scope table and say so."""
+``self`` (the hot path), ``opt`` (the trainer, worker/optimize.py) and ``eval`` (the arena) are served by
+the MI355X engine; the other sub-commands of the reference (play, sl, ob) are outside the scope table and say
+so."""
 import argparse
 from logging import getLogger
 
@@ -36,6 +37,9 @@ _FLAGS = [
     ("--max-games", dict(type=int, help="engine: stop after this many finished games (default: never)")),
     ("--record-visits", dict(action="store_true",
                              help="(self) play records carry each searched move's root visit counts: [move, value, pi]")),
+    ("--policy-targets", dict(choices=["played", "visits"], default="played",
+                              help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
+                                   "visit counts")),
 ]
 
 
@@ -66,6 +70,7 @@ def build_config(args):
     engine.max_rounds, engine.max_games = args.max_rounds, args.max_games
     if args.record_visits:
         engine.record_visits = True
+    config.trainer.policy_targets = args.policy_targets
     return config
 
 
@@ -74,7 +79,7 @@ def start():
     config = build_config(args)
     config.resource.create_directories()
     rc = config.resource
-    setup_logger(rc.play_log_path if args.cmd == 'self' else (rc.eval_log_path if args.cmd == 'eval' else rc.main_log_path))
+    setup_logger({'self': rc.play_log_path, 'eval': rc.eval_log_path, 'opt': rc.opt_log_path}.get(args.cmd, rc.main_log_path))
     logger.info('Config type: %s' % (args.type))
     if args.cmd == 'self':
         if args.ucci:
@@ -89,5 +94,8 @@ def start():
         #  compute_elo.py:88 -- so a repeated position is still played at tau = 0.5, player.py:460-461)
         from cchess_alphazero.worker import evaluator
         return evaluator.start(config)
+    if args.cmd == 'opt':                                   # reference manager.py:85-87
+        from cchess_alphazero.worker import optimize
+        return optimize.start(config)
     raise SystemExit(f"`run.py {args.cmd}` is not part of the MI355X self-play hot path (SURVEY 8): use the reference "
                      f"implementation for it; the play records written by `run.py self` are in the reference's format")

@@ -1,0 +1,272 @@
+"""``run.py opt`` worker (reference: cchess_alphazero/worker/optimize.py, OptimizeWorker :38-232): trains the best model
+on the play records of ``run.py self`` and hands the result to ``run.py eval`` as the next generation.
+
+File selection, the window size, the learning-rate schedule, the epochs, the validation split, the step count and the
+saving follow the reference.  The data path runs on the device: record files are replayed into a ``ReplayWindow``
+(lib/replay_window.py: boards, previous-position indices, labels, values and sparse visit counts, no dense planes), each
+minibatch's planes are gathered and encoded by ``cz_gather_planes`` and the loss and its gradients with respect to the
+logits and the value come from ``cz_policy_value_loss``.  The network's forward and backward passes are fp32 torch
+autograd.
+
+Deliberate deviations from the reference:
+  - record files are split into games with ``split_games``: the reference flat-parses a file with several games
+    (nb_game_in_file > 1) as one game;
+  - only the files actually loaded into the window are moved to ``data_dir/trained`` (the reference also moves files
+    whose loading futures it dropped, so their positions are never trained on); an unreadable file is skipped and left
+    where it is (the reference deletes it);
+  - ``--policy-targets visits`` trains the policy on the records' root visit counts (items [move, value, pi]); the
+    default, ``played``, is the reference's one-hot of the played move;
+  - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
+    after a learning-rate change;
+  - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
+  - a missing ``trainer.load_step`` (the ``normal`` configuration) means no limit, where the reference raises
+    AttributeError; the next generation is saved only after at least one training pass;
+  - one device: with several in ``--gpu`` the first one trains (no multi-GPU data parallelism).
+"""
+import os
+import shutil
+import time
+from logging import getLogger
+
+import numpy as np
+
+from cchess_alphazero.lib.data_helper import get_game_data_filenames
+
+logger = getLogger(__name__)
+
+VALIDATION_SPLIT = 0.02          # Keras fit(validation_split=0.02), optimize.py:120-133
+
+
+def select_files(files, last_file, tc):
+    """The files of the next training pass, or None when there is not enough new data (training() :60-89).
+    files: the play-data files, sorted; last_file: the last file of the previous pass (None at the start)."""
+    offset = tc.min_games_to_begin_learn
+    if len(files) < offset or (last_file is not None and last_file in files
+                               and files.index(last_file) + 1 + offset > len(files)):
+        return None
+    load_step = getattr(tc, "load_step", None)                  # missing (normal): no limit
+    if last_file is not None and last_file in files:
+        idx = files.index(last_file) + 1
+        return files[idx:] if load_step is None else files[idx:idx + load_step]
+    if load_step is not None and len(files) > load_step:
+        return files[:load_step]
+    return list(files)
+
+
+def decide_learning_rate(lr_schedules, total_steps):
+    ret = None
+    for step, lr in lr_schedules:
+        if total_steps >= step:
+            ret = lr
+    return ret
+
+
+def validation_split(n):
+    """(training indices, validation indices) of a window of n positions: the last 2 % in load order validate
+    (Keras: split_at = int(n * (1 - validation_split)))."""
+    split_at = int(n * (1. - VALIDATION_SPLIT))
+    return np.arange(split_at), np.arange(split_at, n)
+
+
+def steps_of_pass(n, batch_size, epochs):
+    """The reference's step count of one pass (train_epoch :134): full batches of the whole window, times the epochs."""
+    return (n // batch_size) * epochs
+
+
+def l2_parameters(net):
+    """The weights under Keras' kernel_regularizer=l2: every convolution's and dense layer's kernel (no biases, no
+    BatchNorm parameters), agent/model.py:37-78 of the reference."""
+    import torch.nn as nn
+    return [m.weight for m in net.modules() if isinstance(m, (nn.Conv2d, nn.Linear))]
+
+
+def input_depth(config):
+    return 28 if (config.opts.has_history or getattr(config.model, "input_depth", 14) == 28) else 14
+
+
+def start(config):
+    """Entry point of ``run.py opt`` (reference :32-34)."""
+    import torch
+    devices = str(config.opts.device_list).split(",")
+    if len(devices) > 1:
+        logger.info(f"multi-GPU training is not supported: training on device {devices[0]} only")
+    torch.cuda.set_device(int(devices[0]))
+    return OptimizeWorker(config).start()
+
+
+class OptimizeWorker:
+    def __init__(self, config):
+        self.config = config
+        self.model = None
+        self.opt = None
+        self.window = None
+        self.count = 0                  # training passes
+        self.total_steps = config.trainer.start_total_steps
+        self.depth = input_depth(config)
+        self.targets = getattr(config.trainer, "policy_targets", "played")
+        self.rng = np.random.default_rng(config.engine.base_seed)
+        self.history = []               # per epoch: the logged losses
+
+    def start(self):
+        self.model = self.load_model()
+        return self.training()
+
+    # ---- the model ---------------------------------------------------------------------------------------------------
+    def load_model(self):
+        """The best model, or (``--new`` / none there) a freshly built one saved as best (reference :185-190)."""
+        from cchess_alphazero.agent.model import CChessModel
+        from cchess_alphazero.lib.model_helper import load_best_model_weight, save_as_best_model
+        model = CChessModel(self.config)
+        if self.config.opts.new or not load_best_model_weight(model):
+            self.config.model.input_depth = self.depth
+            model.build(seed=self.config.engine.base_seed)
+            save_as_best_model(model)
+        if model.model.cfg["input_depth"] != self.depth:
+            raise ValueError(f"the best model takes {model.model.cfg['input_depth']} input planes, the trainer makes "
+                             f"{self.depth} (opts.has_history / model.input_depth)")
+        model.model.cuda().train()
+        return model
+
+    def compile_model(self):
+        """One SGD optimiser for the whole process (reference :136-146: lr 0.02, momentum, no Nesterov)."""
+        import torch
+        self.opt = torch.optim.SGD(self.model.model.parameters(), lr=0.02, momentum=self.config.trainer.momentum,
+                                   nesterov=False)
+        self.l2 = l2_parameters(self.model.model)
+
+    def update_learning_rate(self, total_steps):
+        lr = decide_learning_rate(self.config.trainer.lr_schedules, total_steps)
+        if lr:
+            for g in self.opt.param_groups:
+                g["lr"] = lr
+            logger.debug(f"total step={total_steps}, set learning rate to {lr}")
+
+    def save_current_model(self, send=False):
+        from cchess_alphazero.lib.model_helper import save_as_best_model, save_as_next_generation_model
+        logger.info("Save as ng model" if send else "Save as best model")
+        (save_as_next_generation_model if send else save_as_best_model)(self.model)
+
+    # ---- the loop ----------------------------------------------------------------------------------------------------
+    def new_window(self):
+        from cchess_alphazero.lib.replay_window import ReplayWindow
+        return ReplayWindow(self.config.trainer.dataset_size, depth=self.depth)
+
+    def training(self):
+        """The reference's loop (:55-104): take the next files, fill the window, train epoch_to_checkpoint epochs when it
+        holds more than a batch, save as best, move the files to `trained`; when the data runs out, save the next
+        generation (after at least one pass) and return the total step count."""
+        self.compile_model()
+        tc = self.config.trainer
+        total_steps = self.total_steps
+        last_file = None
+        self.window = self.new_window()
+        while True:
+            files = select_files(get_game_data_filenames(self.config.resource), last_file, tc)
+            if files is None:
+                if self.count > 0:
+                    self.save_current_model(send=True)
+                else:
+                    logger.info("not enough play data to train on")
+                break
+            last_file = files[-1]
+            logger.info(f"Last file = {last_file}")
+            order = list(files)
+            self.rng.shuffle(order)
+            self.fill_window(order)
+            self.update_learning_rate(total_steps)
+            if len(self.window) > tc.batch_size:
+                total_steps += self.train_epoch(tc.epoch_to_checkpoint)
+                self.save_current_model(send=False)
+                self.update_learning_rate(total_steps)
+                self.count += 1
+                loaded = list(self.window.files)
+                self.window = self.new_window()
+                self.backup_play_data(loaded)
+        self.total_steps = total_steps
+        return total_steps
+
+    def fill_window(self, order):
+        """Load files from the end of the shuffled list until the window holds dataset_size positions; the file that
+        reaches it is loaded whole (fill_queue :148-171)."""
+        n0, t0 = len(self.window), time.time()
+        while order and not self.window.full:
+            path = order.pop()
+            try:
+                self.window.load_file(path)
+            except (OSError, ValueError, TypeError, IndexError, KeyError, AttributeError) as e:   # one bad file: skip it
+                logger.error(f"Error when loading data {path}: {e}")
+        logger.info(f"window: {len(self.window)} positions (+{len(self.window) - n0} in {time.time() - t0:.2f} s) from "
+                     f"{len(self.window.files)} files")
+
+    def train_epoch(self, epochs):
+        """epochs passes over the window's first 98 % in a fresh order each, the last 2 % validating; returns the
+        reference's step count (:106-134)."""
+        import torch
+        tc = self.config.trainer
+        win, net = self.window, self.model.model
+        n = len(win)
+        tr, va = validation_split(n)
+        dev = win.device
+        va_d = torch.from_numpy(va.astype(np.int32)).to(dev)
+        bs = tc.batch_size
+        for ep in range(epochs):
+            perm = torch.from_numpy(self.rng.permutation(tr).astype(np.int32)).to(dev)
+            net.train()
+            sums = torch.zeros(3, dtype=torch.float64, device=dev)
+            t0 = time.time()
+            for b in range(0, len(tr), bs):
+                idx = perm[b:b + bs]
+                loss, pm, vm = self.step(idx)
+                sums += torch.stack([loss.detach(), pm, vm]).double() * len(idx)
+            tr_loss = (sums / max(1, len(tr))).tolist()
+            va_loss = self.evaluate(va_d) if len(va) else [float("nan")] * 3
+            self.history.append(dict(train=tr_loss, val=va_loss))
+            logger.info(f"epoch {ep + 1}/{epochs}: {len(tr)} positions in {time.time() - t0:.1f} s; "
+                        f"loss {tr_loss[0]:.4f} policy {tr_loss[1]:.4f} value {tr_loss[2]:.4f} - "
+                        f"val_loss {va_loss[0]:.4f} val_policy {va_loss[1]:.4f} val_value {va_loss[2]:.4f}")
+        return steps_of_pass(n, bs, epochs)
+
+    def l2_term(self):
+        return self.config.model.l2_reg * sum((w * w).sum() for w in self.l2)
+
+    def step(self, idx):
+        """One SGD step on the window positions idx; returns (total loss incl. L2, policy loss, value loss)."""
+        tc = self.config.trainer
+        logits, v = self.model.model(self.window.planes(idx), logits=True)
+        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights)
+        loss = total + self.l2_term()
+        self.opt.zero_grad(set_to_none=True)
+        loss.backward()
+        self.opt.step()
+        return loss, pm, vm
+
+    def evaluate(self, idx_all):
+        """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]."""
+        import torch
+        tc = self.config.trainer
+        net = self.model.model
+        net.eval()
+        sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
+        with torch.no_grad():
+            for b in range(0, idx_all.shape[0], tc.batch_size):
+                idx = idx_all[b:b + tc.batch_size]
+                logits, v = net(self.window.planes(idx), logits=True)
+                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights)
+                sums += torch.stack([pm, vm]).double() * len(idx)
+            p, v = (sums / idx_all.shape[0]).tolist()
+            l2 = float(self.l2_term())
+        net.train()
+        w = tc.loss_weights
+        return [w[0] * p + w[1] * v + l2, p, v]
+
+    def backup_play_data(self, files):
+        """Move the files of the pass to data_dir/trained (:212-224)."""
+        backup_folder = os.path.join(self.config.resource.data_dir, "trained")
+        os.makedirs(backup_folder, exist_ok=True)
+        cnt = 0
+        for f in files:
+            try:
+                shutil.move(f, backup_folder)
+            except OSError:
+                cnt += 1
+        logger.info(f"backup {len(files)} files, {cnt} failed")

@@ -1,0 +1,276 @@
+// xq_train.hip -- the trainer's data path and loss for gfx950 (run.py opt, worker/optimize.py) + their C-ABI entry points.
+//
+//   k_replay_games       one wavefront per game replays all of a record's plies (the boards of expanding_data,
+//                        reference worker/optimize.py:234-258) with step_board, the move application of k_step
+//   k_gather_planes      one wavefront per minibatch row: window index -> 14 or 28 float32 input planes (state_to_planes /
+//                        state_history_to_planes, environment/static_env.py:137-194) with wave_encode, the encoder of k_encode
+//   k_policy_value_loss  one wavefront per minibatch row: softmax, Keras 2.0.8's clipped categorical cross-entropy against the
+//                        played move's one-hot or the record's visit counts, squared value error, and their gradients
+//
+// The contract (shapes, order, error reporting, bit-identity) is stated in include/czero.h.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "xq_rules.h"
+#include "../../include/czero.h"
+
+using namespace xq;
+
+extern "C" void czi_set_error(const char* msg);
+
+namespace {
+
+inline int grid_for(int n)
+{
+    const int cap = 256 * 32;            // as xq_kernels.hip: 256 CUs x up to 32 single-wave workgroups, the rest grid-stride
+    return n < cap ? (n > 0 ? n : 1) : cap;
+}
+
+int launch_status(const char* what)
+{
+    if (hipGetLastError() != hipSuccess) {
+        czi_set_error(what);
+        return CZ_ERR_HIP;
+    }
+    return CZ_OK;
+}
+
+XQ_D float wave_sum_f32(float v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // every lane ends with the same bits
+    return v;
+}
+
+XQ_D double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+XQ_D void zero_planes(float* __restrict__ out)   // 14 planes: 315 float4
+{
+    for (int q = lane_id(); q < 315; q += 64) reinterpret_cast<float4*>(out)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+constexpr int LOSS_COLS = (NLABELS + 63) / 64;       // 33 logits per lane
+constexpr float CCE_EPS = 1e-7f;                     // Keras 2.0.8 epsilon(); the upper clip is float(1 - 1e-7)
+constexpr float CCE_HI = (float)(1.0 - 1e-7);
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void k_replay_games(const int8_t* __restrict__ init, const uint16_t* __restrict__ labels,
+                                                    const int32_t* __restrict__ offsets, int n_games, int n_pos,
+                                                    int8_t* __restrict__ boards, int32_t* __restrict__ prev,
+                                                    int32_t* __restrict__ bad)
+{
+    __shared__ int8_t bd[2][BOARD_LDS];
+    const int lane = lane_id();
+    for (int g = blockIdx.x; g < n_games; g += gridDim.x) {
+        const int o0 = offsets[g], o1 = offsets[g + 1];
+        if (o0 < 0 || o1 < o0 || o1 > n_pos) {           // nothing written for a game whose span is not inside [0, n_pos)
+            if (lane == 0) bad[g] = -2;
+            continue;
+        }
+        load_board(init + (size_t)g * NSQ, bd[0]);
+        int cur = 0, bad_ply = -1;
+        for (int t = o0; t < o1; ++t) {
+            store_board(bd[cur], boards + (size_t)t * NSQ);
+            if (lane == 0) prev[t] = t - o0 >= 2 ? t - 2 : -1;
+            if (bad_ply >= 0) continue;                  // after an invalid move the board stays as it was (as cz_step)
+            const int label = labels[t];
+            bool moved = false;
+            if (label < NLABELS) {
+                const int ft = label_ft(label);
+                const int f = ft >> 8, to = ft & 0xFF;
+                if (bd[cur][f] != 0) {
+                    step_board(bd[cur], f, to, bd[cur ^ 1]);
+                    cur ^= 1;
+                    moved = true;
+                }
+            }
+            if (!moved) bad_ply = t - o0;
+        }
+        if (lane == 0) bad[g] = bad_ply;
+        wave_sync();
+    }
+}
+
+__global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__ boards, const int32_t* __restrict__ prev,
+                                                     int n_pos, const int32_t* __restrict__ idx, int n_rows, int depth,
+                                                     float* __restrict__ planes)
+{
+    __shared__ int8_t bd[BOARD_LDS];
+    for (int r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int i = idx[r];
+        float* out = planes + (size_t)r * depth * 90;
+        if (i < 0 || i >= n_pos) {                       // out-of-range index: zero planes, nothing read
+            zero_planes(out);
+            if (depth == 28) zero_planes(out + 1260);
+            continue;
+        }
+        load_board(boards + (size_t)i * NSQ, bd);
+        wave_encode<0>(bd, out);
+        if (depth == 28) {
+            const int p = prev[i];
+            if (p >= 0 && p < n_pos) {
+                wave_sync();
+                load_board(boards + (size_t)p * NSQ, bd);
+                wave_encode<0>(bd, out + 1260);
+            } else {
+                zero_planes(out + 1260);
+            }
+        }
+        wave_sync();
+    }
+}
+
+__global__ __launch_bounds__(64) void k_policy_value_loss(
+    const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx, int n_rows,
+    int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
+    const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z, int mode,
+    float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
+    float* __restrict__ grad_logits, float* __restrict__ grad_v)
+{
+    __shared__ float tgt[LOSS_COLS * 64];            // the row's dense target, built from the sparse entries
+    const int lane = lane_id();
+    const float inv_b = 1.0f / (float)n_rows;
+    const float c = w_p * inv_b;
+    for (int r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int i = idx[r];
+        float* g = grad_logits + (size_t)r * NLABELS;
+        if (i < 0 || i >= n_pos) {                       // out-of-range index: zero loss and gradient, nothing read
+            for (int j = lane; j < NLABELS; j += 64) g[j] = 0.f;
+            if (lane == 0) {
+                policy_loss[r] = 0.f;
+                value_sqerr[r] = 0.f;
+                grad_v[r] = 0.f;
+            }
+            continue;
+        }
+#pragma unroll
+        for (int k = 0; k < LOSS_COLS; ++k) tgt[lane + 64 * k] = 0.f;
+        wave_sync();
+        double total = 0.0;
+        int lo = 0, hi = 0;
+        if (mode == 1 && nnz > 0) {
+            lo = row_ptr[i];
+            hi = row_ptr[i + 1];
+            if (lo < 0 || hi > nnz || hi < lo) lo = hi = 0;   // a span outside [0, nnz): no visits, nothing read
+            for (int k = lo + lane; k < hi; k += 64) total += (double)vis_count[k];
+            total = wave_sum_f64(total);
+        }
+        if (total > 0.0) {
+            for (int k = lo + lane; k < hi; k += 64) {
+                const int lab = vis_label[k];
+                if (lab < NLABELS) tgt[lab] = (float)((double)vis_count[k] / total);   // float64 quotient, rounded once
+            }
+        } else if (lane == 0) {
+            const int lab = played[i];
+            if (lab < NLABELS) tgt[lab] = 1.f;
+        }
+        wave_sync();
+        // softmax over the row, max subtracted, all in fp32
+        const float* zr = logits + (size_t)r * ld;
+        float e[LOSS_COLS];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < LOSS_COLS; ++k) {
+            const int j = lane + 64 * k;
+            e[k] = j < NLABELS ? zr[j] : -INFINITY;
+            mx = fmaxf(mx, e[k]);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < LOSS_COLS; ++k) {
+            const int j = lane + 64 * k;
+            e[k] = j < NLABELS ? expf(e[k] - mx) : 0.f;
+            s += e[k];
+        }
+        s = wave_sum_f32(s);
+        // loss = -sum t log(clip(p)); S = sum t m, m = 1 where the clip passes the gradient (eps < p < 1 - eps)
+        float loss = 0.f, S = 0.f;
+#pragma unroll
+        for (int k = 0; k < LOSS_COLS; ++k) {
+            const float p = e[k] / s;
+            e[k] = p;
+            const float t = tgt[lane + 64 * k];
+            if (t != 0.f) {
+                const float pc = fminf(fmaxf(p, CCE_EPS), CCE_HI);
+                loss -= t * logf(pc);
+                if (p > CCE_EPS && p < CCE_HI) S += t;
+            }
+        }
+        loss = wave_sum_f32(loss);
+        S = wave_sum_f32(S);
+#pragma unroll
+        for (int k = 0; k < LOSS_COLS; ++k) {
+            const int j = lane + 64 * k;
+            if (j < NLABELS) {
+                const float p = e[k];
+                const float tm = (p > CCE_EPS && p < CCE_HI) ? tgt[j] : 0.f;
+                g[j] = c * (p * S - tm);
+            }
+        }
+        if (lane == 0) {
+            const float d = v[r] - z[i];
+            policy_loss[r] = loss;
+            value_sqerr[r] = d * d;
+            grad_v[r] = w_v * (2.f * d) * inv_b;
+        }
+        wave_sync();
+    }
+}
+
+// ---- C-ABI ----------------------------------------------------------------------------
+extern "C" {
+
+int cz_replay_games(const int8_t* init_boards, const uint16_t* labels, const int32_t* offsets, int n_games, int n_pos,
+                    int8_t* boards, int32_t* prev, int32_t* bad_ply, void* stream)
+{
+    if (n_games == 0) return CZ_OK;
+    if (n_games < 0 || n_pos < 0 || !init_boards || !offsets || !bad_ply || (n_pos > 0 && (!labels || !boards || !prev))) {
+        czi_set_error("cz_replay_games: bad argument");
+        return CZ_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_replay_games, dim3(grid_for(n_games)), dim3(64), 0, (hipStream_t)stream, init_boards, labels,
+                       offsets, n_games, n_pos, boards, prev, bad_ply);
+    return launch_status("cz_replay_games: launch failed");
+}
+
+int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, int n_rows, int depth,
+                     float* planes, void* stream)
+{
+    if (n_rows == 0) return CZ_OK;
+    if (n_rows < 0 || n_pos < 0 || (depth != 14 && depth != 28) || !idx || !planes || (n_pos > 0 && !boards) ||
+        (depth == 28 && n_pos > 0 && !prev)) {
+        czi_set_error("cz_gather_planes: bad argument (depth 14 or 28)");
+        return CZ_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_gather_planes, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, boards, prev, n_pos, idx,
+                       n_rows, depth, planes);
+    return launch_status("cz_gather_planes: launch failed");
+}
+
+int cz_policy_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, int n_rows, int n_pos,
+                         const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                         const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                         float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
+{
+    if (n_rows == 0) return CZ_OK;
+    if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !v || !idx || !policy_loss ||
+        !value_sqerr || !grad_logits || !grad_v || (n_pos > 0 && (!played || !z)) ||
+        nnz < 0 || (mode == 1 && nnz > 0 && (!row_ptr || !vis_label || !vis_count))) {
+        czi_set_error("cz_policy_value_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
+        return CZ_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_policy_value_loss, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
+                       n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, mode, w_p, w_v, policy_loss, value_sqerr,
+                       grad_logits, grad_v);
+    return launch_status("cz_policy_value_loss: launch failed");
+}
+
+}  // extern "C"

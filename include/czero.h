@@ -498,6 +498,51 @@ int cz_debug_noise(uint64_t seed, uint32_t game_key, double alpha, int n_moves, 
 /* test hook: y[i] = sqrt((double)(x[i] + 1)) exactly as the PUCT kernel computes it */
 int cz_debug_sqrt(const int32_t* x, double* y, int n, void* stream);
 
+/* ---- trainer data path and loss (csrc/xq_train.hip; run.py opt, cchess_alphazero/worker/optimize.py) ----------------
+ * Replaces the reference trainer's expanding_data / convert_to_trainging_data (worker/optimize.py:234-281) and the Keras
+ * loss of compile_model (:139-146).  A "window" is n_pos positions in game-major order (game 0's plies, then game 1's ...:
+ * the order expanding_data produces). */
+
+/* Replay every game of a batch of records, one wavefront per game.  init_boards[n_games][90]: each game's initial board;
+ * labels[n_pos]: the move labels of all games flat; offsets[n_games + 1] (DEVICE): game g owns positions
+ * offsets[g] .. offsets[g+1]-1, offsets non-decreasing, offsets[n_games] <= n_pos.
+ * Writes boards[n_pos][90] (the position BEFORE each move, flipped to its mover exactly as cz_step flips: the same
+ * step_board code, so every board equals cz_step's bit for bit), prev[n_pos] (the index of the position two plies
+ * earlier in the same game -- the history[-5] of state_history_to_planes --, -1 for a game's first two positions) and
+ * bad_ply[n_games]: -1, or the ply (0-based within the game) of the first move with a bad label or an empty from-square
+ * (the reference raises ValueError there); the game's later boards repeat the board at that ply.  bad_ply[g] = -2: the
+ * game's offsets are out of order or beyond n_pos, nothing of it is written. */
+int cz_replay_games(const int8_t* init_boards, const uint16_t* labels, const int32_t* offsets, int n_games, int n_pos,
+                    int8_t* boards, int32_t* prev, int32_t* bad_ply, void* stream);
+
+/* Minibatch gather fused with the encoding, one wavefront per row: planes[n_rows][depth][10][9] float32 for the window
+ * positions idx[n_rows].  Planes 0-13 are state_to_planes of boards[idx[r]], bit-identical to cz_encode(CZ_F32) (the
+ * same wave_encode); depth 28 adds planes 14-27 = the encoding of boards[prev[idx[r]]], zero when prev is -1
+ * (state_history_to_planes).  An index outside [0, n_pos) gives zero planes.  prev may be NULL for depth 14. */
+int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, int n_rows, int depth,
+                     float* planes, void* stream);
+
+/* Policy / value loss of a minibatch and its gradients, one wavefront per row, no atomics: per-row outputs, so a sum
+ * over them on the host side is deterministic.
+ *   logits[n_rows][ld] fp32 (ld >= 2086), v[n_rows] = the value head after tanh, idx[n_rows] = window positions;
+ *   window targets: played[n_pos] (labels), z[n_pos] (values), and for mode 1 the visit counts in CSR form:
+ *   row_ptr[n_pos + 1], vis_label[nnz], vis_count[nnz] (>= 0; the labels of one row distinct).  With nnz = 0 the three
+ *   may be NULL and every row takes the one-hot; a row whose span row_ptr[i] .. row_ptr[i+1] is not inside [0, nnz)
+ *   counts as a row without visits (nothing outside the arrays is read).
+ * Target t: mode 1 (visits) on a row whose counts sum to more than 0: t_k = count_k / sum, divided in float64 and rounded
+ * once to float32 (the bits of lib/record_decoder._visit_targets); otherwise (mode 0 played, or no visits) the one-hot
+ * of played.  p = softmax(logits) in fp32 after subtracting the row max; eps = 1e-7f, hi = float(1 - 1e-7).
+ *   policy_loss[r] = -sum_k t_k log(clip(p_k, eps, hi))      (Keras 2.0.8 categorical_crossentropy of the softmax)
+ *   value_sqerr[r] = (v - z)^2
+ *   grad_logits[r][2086] = (w_p / n_rows) (p_j S - t_j m_j), m_j = 1 where eps < p_j < hi else 0, S = sum_k t_k m_k
+ *                          (the exact gradient of the clipped loss through the softmax)
+ *   grad_v[r] = w_v 2 (v - z) / n_rows
+ * The gradients are those of w_p mean(policy_loss) + w_v mean(value_sqerr).  An index outside [0, n_pos) gives zeros. */
+int cz_policy_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, int n_rows, int n_pos,
+                         const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                         const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                         float* value_sqerr, float* grad_logits, float* grad_v, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
