@@ -600,7 +600,7 @@ def tower(x, blocks, exit_fmt, out=None, heads=None, count=None, fmt_x=None, fmt
 
 
 def resblock_chain(x, blocks, out=None, out_f32=None, count=None, dtype_code=None):
-    """cz_resblock_chain: consecutive 192-filter blocks (a BlockList or [(w1_packed, bias1, w2_packed, bias2), ...], 1 .. 8) of one
+    """cz_resblock_chain: consecutive 192-filter blocks (a BlockList or [(w1_packed, bias1, w2_packed, bias2), ...], 1 .. 12) of one
     staged arithmetic in one launch; x: the c8 (uint8 image) or c6 (int8 image) operand pair; out: the same kind of pair, or
     out_f32 [N, 90, 192] for the last block.  dtype_code=F16C86: a c6 chain that starts the tower (x = the input layer's c8 image,
     block 0's first filter c8-packed).  Bit-identical to len(blocks) resblock() calls."""

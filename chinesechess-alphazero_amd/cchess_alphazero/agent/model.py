@@ -15,6 +15,7 @@ import hashlib
 import json
 import os
 from logging import getLogger
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -163,6 +164,27 @@ def ip_segments(kinds, max_chain=12, first_alone=False):
     return segs
 
 
+_IMG_DTYPE = {"c6": torch.int8, "c8": torch.uint8}          # the image's element type tags the arithmetic (_native._pair_code)
+
+
+class _Step(NamedTuple):
+    """One launch of InferenceNet's trunk (InferenceNet._build_plan; _trunk_mfma runs them).  call: the _native entry point;
+    blocks: the residual blocks it runs; x / y: the operand kinds it reads / writes (InferenceNet._view; "planes": the input);
+    to: where it writes -- "next" (the other operand buffer, the current one after the launch), "last" (the fp32 trunk
+    output), "heads" (the head features) or "pairs" (fp32 into last, then re-split into the buffer it read as (hi, lo) fp16
+    pairs: a c8>N tower's hand-over); bl: a chain's BlockList; code: its dtype code or exit format; w: a single block's
+    (w1, b1, w2, b2); timed: recorded in InferenceNet.block_events."""
+    call: str
+    blocks: tuple
+    x: str
+    y: Optional[str]
+    to: str
+    bl: object = None
+    code: Optional[int] = None
+    w: tuple = None
+    timed: bool = True
+
+
 def events_ms(events):
     """Per-BLOCK times (ms) of the tower launches recorded in InferenceNet.block_events: a (start, end) pair is one residual
     block; (start, end, m) is a launch of m chained blocks (cz_tower / cz_tower_pairs), counted as m blocks of elapsed / m each, so that the
@@ -257,7 +279,7 @@ class InferenceNet(nn.Module):
         # PyTorch tail they replace (A/B runs)
         self.fused_tail = os.environ.get("CZ_FUSED_TAIL", "1") != "0"
         self.block_events = None            # bench.py: list collecting (start, end[, blocks]) HIP events around tower launches
-        self.last_plan = None               # tower_plan's steps of the last chained forward
+        self.last_plan = None               # the launches of the last chained forward (_build_plan's labels)
         # consecutive blocks as one launch (cz_tower / cz_tower_pairs, tower_plan; CZ_TOWER_CHAIN=0: one launch per block)
         self.chain_blocks = os.environ.get("CZ_TOWER_CHAIN", "1") != "0"
         self.chain_heads = os.environ.get("CZ_TOWER_HEADS", "1") != "0"
@@ -311,6 +333,7 @@ class InferenceNet(nn.Module):
                 self.register_buffer(name, t.view(torch.int16) if t.dtype in (torch.bfloat16, torch.float16) else t)
             del self._packed_in, self._in_table, self._in_bias32, self._head_w, self._head_b, self._tail_pack
         self._bufs = {}
+        self._plans = {}                    # _plan's launch plans, per switch setting
         self.eval()
         for p in self.parameters():
             p.requires_grad_(False)
@@ -398,123 +421,163 @@ class InferenceNet(nn.Module):
         return [tuple(t[:n] for t in b) for b in bufs], last[:n]
 
     @staticmethod
-    def _as_f16_pair(pair):
-        """A c8 operand pair's storage seen as an (hi, lo) fp16 pair (same bytes: [n, 90, 2C] u8 = [n, 90, C] f16); an (hi, lo)
-        pair of the operand dtype (f16x3 / bf16x3 towers) as it is."""
-        return (pair[0], pair[1].view(torch.float16)) if pair[1].dtype in (torch.uint8, torch.int8) else pair
+    def _view(buf, kind):
+        """An operand buffer of _operands as the tuple a kernel takes for `kind`.  The c8 family's storage (f16, image bytes)
+        serves every kind: "c6" tags the image int8, "c8" uint8 (the element type selects the kernel), "pair" reads the image
+        bytes as the lo half of an (hi, lo) fp16 pair.  Buffers of (hi, lo) / (hi,) operands are "pair" as they are."""
+        dtype = buf[0].dtype if kind == "pair" else _IMG_DTYPE[kind]
+        return buf if buf[-1].dtype == dtype else (buf[0], buf[1].view(dtype))
+
+    def _first_fused(self, planes_dtype):
+        """The input layer computed inside block 0's launch (cz_input_resblock, which also takes the occupancy boards):
+        128 filters, split operands, uint8 planes, fused blocks, a tower of >= 2 blocks -- but not a hybrid tower whose only
+        c8 block is the first (it hands fp32 over right after it: that block stays on cz_resblock)."""
+        return (self.trunk == "mfma" and self.fused_blocks and self.fused_input and self.filters == 128 and self.parts == 2
+                and len(self.res) >= 2 and planes_dtype == torch.uint8 and not (self.arith == "c8" and self.c8_blocks == 1))
+
+    def _plan(self, planes_dtype, heads):
+        """The trunk's launches for planes of `planes_dtype` (heads: the caller takes the head features from the tower), as
+        (steps, last_plan labels or None): built on the first forward of a switch setting and kept until the module's tensors
+        are replaced (_apply)."""
+        six_wave = self.filters == 192 and os.environ.get("CZ_IP_PAIR", "1")[:1] == "0"
+        key = (planes_dtype, heads, self.chain_blocks, self.chain_heads, self.fused_blocks, self.fused_input, self.fused_heads,
+               six_wave)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self._build_plan(planes_dtype, heads, six_wave)
+        return plan
+
+    def _build_plan(self, planes_dtype, heads, six_wave):
+        from cchess_alphazero import _native
+        kinds, c, two = self.block_kinds(), self.filters, self.parts == 2
+        nblk = len(kinds)
+        n8 = self.c8_blocks if self.arith == "c8" else 0        # blocks [0, n8) on the c8 / c6 arithmetics
+        # whole residual block in one launch where k_resblock exists for the shape
+        fused = self.fused_blocks and (c in (128, 192) or (c == 256 and not two))
+        first = self._first_fused(planes_dtype)
+        if self.c6 and not (fused and (first or c == 192)):
+            raise RuntimeError("arith='c6' runs on the fused kernels only (128 filters: uint8 planes, fused input layer and blocks)")
+        heads = heads and fused and two and c == 128            # the tower's last launch writes the head features
+        out = "heads" if heads else "last"
+
+        def chain(blk, *fmt):
+            return _native.BlockList([self._block_params(i) for i in blk], *fmt)
+        if first:
+            steps = [_Step("input_resblock", (0,), "planes", kinds[0], "next", w=self._block_params(0))]
+        else:
+            # (a c6 tower's input layer writes a c8 image: its first block's first filter is a c8 filter)
+            steps = [_Step("input_conv", (), "planes", "pair" if kinds[0] == "pair" else "c8", "next", timed=False)]
+        labels = None
+        if fused and self.chain_blocks and first:
+            # (round 5 / 6) the blocks behind the fused input layer as CHAINS, one launch for consecutive blocks with the
+            # activations staying in LDS (tower_plan): the 7 x 128 benchmark tower is FIRST | blocks 1 .. 6 with the head
+            # convolutions as the chain's exit, a c8>3 tower FIRST | 1 .. 2 (exit: fp16 pairs) | 3 .. 6 (heads).  The head
+            # convolutions as a pair chain's exit read the block's value as hi + lo: fp16 pairs stand for it to 2^-22, bf16
+            # pairs only to 2^-17 -- bf16x3 (the guard's last resort before the fp32 library trunk) keeps its HEADS launch
+            chain_heads = self.chain_heads and not (kinds[-1] == "pair" and self.operand_dtype == torch.bfloat16)
+            labels = tower_plan(kinds, heads_exit=heads, chain_heads=chain_heads)
+            img = {"c6": _native.IMG_C6, "c8": _native.IMG_C8, "pair": _native.IMG_PAIR, "heads": _native.EXIT_HEADS}
+            for st in labels[1:]:
+                if st[0] == "block":                            # the tower's last block on its own launch
+                    steps.append(_Step("resblock_heads" if heads else "resblock", (st[1],), kinds[st[1]], None, out,
+                                       w=self._block_params(st[1])))
+                    continue
+                blk = tuple(st[1])
+                if st[0] == "tower":                            # exit: the image the next launch reads, or "heads"
+                    fmt = [img[kinds[blk[0]]]] * len(blk)       # (one arithmetic per launch)
+                    steps.append(_Step("tower", blk, kinds[blk[0]], st[2], "heads" if st[2] == "heads" else "next",
+                                       chain(blk, fmt, fmt), img[st[2]]))
+                else:                                           # "pairs", with the heads as the exit or not
+                    steps.append(_Step("tower_pairs", blk, "pair", "pair", "heads" if st[2] else "next", chain(blk)))
+        elif fused and self.chain_blocks and c == 192 and two:
+            # the 192-filter tower behind cz_input_conv: one cz_resblock_chain launch per arithmetic (ip_segments)
+            segs = ip_segments(kinds, first_alone=six_wave)
+            labels = [("chain192" if kind == "chain" else "block192", blk, kinds[blk[0]]) for kind, blk in segs]
+            for kind, blk in segs:
+                blk = tuple(blk)
+                k, nk = kinds[blk[0]], (kinds[blk[-1] + 1] if blk[-1] + 1 < nblk else None)
+                if kind == "block":                             # a c6 tower's block 0 on the six-wave kernels: c8 image in
+                    steps.append(_Step("resblock", blk, "c8", "c6", "next", w=self._block_params(0), code=_native.F16C86))
+                    continue
+                first6 = k == "c6" and blk[0] == 0              # (a c6 chain that starts the tower reads the c8 image)
+                to = "last" if nk is None else "pairs" if nk == "pair" and k == "c8" else "next"
+                steps.append(_Step("resblock_chain", blk, "c8" if first6 else k, nk, to, chain(blk),
+                                   _native.F16C86 if first6 else None))
+        elif fused and self.chain_blocks and c == 256:
+            # the deep tower on plain operands: cz_tower_plain launches of 24 blocks at most
+            for lo in range(0, nblk, 24):
+                blk = tuple(range(lo, min(nblk, lo + 24)))
+                steps.append(_Step("tower_plain", blk, "pair", "pair", "next" if blk[-1] + 1 < nblk else "last", chain(blk)))
+            labels = [("chain256", list(st.blocks), "plain") for st in steps[1:]]
+        else:
+            # one launch per block (fused) or per convolution
+            for i in range(1 if first else 0, nblk):
+                k = kinds[i]
+                call = "resblock" if fused else "conv3x3_c8" if k == "c8" else "conv3x3"
+                to = out if i + 1 == nblk else "pairs" if i + 1 == n8 else "next"
+                if to == "heads":
+                    call = "resblock_heads"
+                # (192 filters, c6: block 0 reads the input layer's c8 image -- its own dtype code)
+                code = _native.F16C86 if self.c6 and i == 0 else None
+                steps.append(_Step(call, (i,), k, k, to, w=self._block_params(i), code=code, timed=fused))
+        return steps, labels
 
     def _trunk_mfma(self, planes, heads=None, rows=None, count=None, masks=None):
         """planes: the evaluation queue as the search kernel wrote it ([n, in_planes, 10, 9], any supported dtype).
         heads = (n_policy, policy_feat, value_feat): fold the 1x1 head convolutions into the last block where the
-        kernel exists for the shape (returns None then), else returns the [n, 90, c] trunk output."""
+        kernel exists for the shape (returns None then), else returns the [n, 90, c] trunk output.
+        Compact queue (rows / count on the device): board i = planes[rows[i]] for i < count; the launch shapes stay those of
+        the whole queue, the kernels read the count themselves."""
         from cchess_alphazero import _native
-        n, c = planes.shape[0], self.filters
-        (cur, tmp, nxt), last = self._operands(n, planes.device)
-        # compact queue (rows / count on the device): board i = planes[rows[i]] for i < count; the launch shapes stay
-        # those of the whole queue, the kernels read the count themselves
-        nblk = len(self.res)
-        n8 = self.c8_blocks if self.arith == "c8" else 0        # blocks [0, n8) on the c8 arithmetic
-        # whole residual block in one launch where k_resblock exists for the shape
-        fused = self.fused_blocks and ((c in (128, 192)) or (c == 256 and self.parts == 1))
-        # input layer + first block in one launch: 128 filters, split operands, byte planes, a tower of >= 2 blocks
-        # (a hybrid tower whose only c8 block is the first hands fp32 over after it: that block stays on cz_resblock)
-        if self.c6 and c == 128 and planes.dtype != torch.uint8:
+        if self.c6 and self.filters == 128 and planes.dtype != torch.uint8:
             # c6 exists on the fused kernels only, whose input layer is a gather over the OCCUPIED squares of byte planes:
             # the feature planes are 0 / 1 by construction (environment/static_env.py state_to_planes), in any dtype
             planes = (planes != 0).to(torch.uint8)
-        first_fused = (fused and self.fused_input and c == 128 and self.parts == 2 and nblk >= 2 and
-                       planes.dtype == torch.uint8 and n8 != 1)
-        if self.c6 and not (fused and (first_fused or c == 192)):
-            raise RuntimeError("arith='c6' runs on the fused kernels only (128 filters: uint8 planes, fused input layer and blocks)")
-        if not first_fused:
-            if self.arith == "c8" and n8 == 0:                  # (cannot happen through the constructor; kept total)
-                cur, tmp, nxt = (self._as_f16_pair(t) for t in (cur, tmp, nxt))
-            # (a c6 tower's input layer writes a c8 image: its first block's first filter is a c8 filter)
-            cur_in = (cur[0], cur[1].view(torch.uint8)) if self.c6 else cur
-            _native.input_conv(planes.contiguous(), self.in_w.view(self.operand_dtype), self.in_bias32, cur_in,
-                               rows=rows, count=count)
-        # (round 5 / 6) the blocks behind the fused input layer run as CHAINS -- one launch for consecutive blocks with the
-        # activations staying in LDS (cz_tower for c6 / c8 blocks, cz_tower_pairs for f16x3 / bf16x3 ones; tower_plan): the 7 x 128
-        # benchmark tower is FIRST | blocks 1 .. 6 with the head convolutions as the chain's exit, a c8>3 tower FIRST | 1 .. 2 (exit:
-        # fp16 pairs) | 3 .. 6 (heads)
-        if fused and first_fused and self.chain_blocks:
-            return self._tower_chained(planes, cur, nxt, last, heads, rows, count, masks)
-        if fused and c == 192 and self.parts == 2 and self.chain_blocks:
-            return self._tower_192(cur, nxt, last, count)
-        if fused and c == 256 and self.parts == 1 and self.chain_blocks:
-            # the deep tower on plain operands: all blocks in one cz_tower_plain launch (24 at most per launch)
-            key = ("plan256", self.tb0a.data_ptr())
-            if key not in self._bufs:
-                self._bufs[key] = [_native.BlockList([self._block_params(i) for i in range(lo, min(nblk, lo + 24))])
-                                   for lo in range(0, nblk, 24)]
-            self.last_plan = [("chain256", list(range(24 * j, 24 * j + bl.n)), "plain") for j, bl in enumerate(self._bufs[key])]
-            x = cur[0]
-            for j, bl in enumerate(self._bufs[key]):
-                ev = None
-                if self.block_events is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                y = last if j + 1 == len(self._bufs[key]) else nxt[0]
-                _native.tower_plain(x, bl, y, count=count)
-                x = y
-                if ev is not None:
-                    ev[1].record()
-                    self.block_events.append(ev + (bl.n,) if bl.n > 1 else ev)
-            return last
-        for i in range(nblk):
-            w1 = getattr(self, f"tw{i}a").view(self.operand_dtype)
-            w2 = getattr(self, f"tw{i}b").view(self.operand_dtype)
-            if self.c6:
-                # the image tensors' element type is the tag that selects the kernel: int8 = a c6 block (its input AND output
-                # pair, also where the last c6 block of a hybrid tower writes a c8 image), uint8 = a c8 block
-                tag = torch.int8 if i < self.c6_blocks else torch.uint8
-                cur, tmp, nxt = ((t[0], t[1].view(tag)) for t in (cur, tmp, nxt))
-            if fused:
-                b1, b2 = getattr(self, f"tb{i}a"), getattr(self, f"tb{i}b")
-                ev = None
-                if self.block_events is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                if i == 0 and first_fused:
-                    _native.input_resblock(planes.contiguous(), self.in_table32, self.in_bias32, w1, b1, w2, b2, out=nxt,
-                                           rows=rows, count=count, masks=masks)
-                    cur, nxt = nxt, cur
-                elif i + 1 == n8 and n8 < nblk:
-                    # the last c8 block of a hybrid tower: fp32 out, re-split into (hi, lo) fp16 pairs for the f16x3 blocks
-                    _native.resblock(cur, w1, b1, w2, b2, out_f32=last, count=count)
-                    cur, tmp, nxt = (self._as_f16_pair(t) for t in (cur, tmp, nxt))
-                    _native.split_bias_act(last, None, cur, relu=False)
-                elif i + 1 < nblk:
-                    # (192 filters, c6: block 0 reads the input layer's c8 image -- its own dtype code)
-                    code = _native.F16C86 if (self.c6 and i == 0 and not first_fused) else None
-                    _native.resblock(cur, w1, b1, w2, b2, out=nxt, count=count, dtype_code=code)
-                    cur, nxt = nxt, cur
-                elif heads is not None and self.parts == 2 and c == 128:
-                    _native.resblock_heads(cur, w1, b1, w2, b2, self.head_w32, self.head_b32, heads[0], heads[1],
-                                           heads[2], count=count)
-                elif self.parts == 2:
-                    _native.resblock(cur, w1, b1, w2, b2, out_f32=last, count=count)
-                else:
-                    _native.resblock(cur, w1, b1, w2, b2, out=(last,), count=count)
-                if ev is not None:
-                    ev[1].record()
-                    self.block_events.append(ev)
-                continue
-            if i == n8 and 0 < n8:          # (per-convolution launches, hybrid tower: the same re-split)
-                cur, tmp, nxt = (self._as_f16_pair(t) for t in (cur, tmp, nxt))
-                _native.split_bias_act(last, None, cur, relu=False)
-            conv = _native.conv3x3_c8 if i < n8 else _native.conv3x3
-            conv(cur, w1, getattr(self, f"tb{i}a"), out=tmp)
-            if i + 1 < nblk and i + 1 != n8:
-                conv(tmp, w2, getattr(self, f"tb{i}b"), skip=cur, out=nxt)
+        steps, labels = self._plan(planes.dtype, heads is not None)
+        if labels is not None:
+            self.last_plan = labels
+        (cur, tmp, nxt), last = self._operands(planes.shape[0], planes.device)
+        to_last = {"out_f32": last} if self.parts == 2 else {"out": (last,)}
+        hd = (self.head_w32, self.head_b32) + tuple(heads) if heads is not None else None
+        for st in steps:
+            ev = None
+            if st.timed and self.block_events is not None:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            x = self._view(cur, st.x) if st.x != "planes" else None
+            y = self._view(nxt, st.y) if st.to == "next" else None
+            dst = {"out": y} if y is not None else to_last
+            if st.call == "input_conv":
+                _native.input_conv(planes.contiguous(), self.in_w.view(self.operand_dtype), self.in_bias32, y, rows=rows,
+                                   count=count)
+            elif st.call == "input_resblock":
+                _native.input_resblock(planes.contiguous(), self.in_table32, self.in_bias32, *st.w, out=y, rows=rows,
+                                       count=count, masks=masks)
+            elif st.call == "resblock":
+                _native.resblock(x, *st.w, **dst, count=count, dtype_code=st.code)
+            elif st.call == "resblock_heads":
+                _native.resblock_heads(x, *st.w, *hd, count=count)
+            elif st.call == "tower":
+                _native.tower(x, st.bl, st.code, out=y, heads=hd if y is None else None, count=count)
+            elif st.call == "tower_pairs":
+                _native.tower_pairs(x, st.bl, out=y, heads=hd if y is None else None, count=count)
+            elif st.call == "resblock_chain":
+                _native.resblock_chain(x, st.bl, **dst, count=count, dtype_code=st.code)
+            elif st.call == "tower_plain":
+                _native.tower_plain(x[0], st.bl, y[0] if y is not None else last, count=count)
+            else:                                               # conv3x3 / conv3x3_c8: one launch per convolution
+                t = self._view(tmp, st.x)
+                getattr(_native, st.call)(x, st.w[0], st.w[1], out=t)
+                getattr(_native, st.call)(t, st.w[2], st.w[3], skip=x, **dst)
+            if st.to == "next":
                 cur, nxt = nxt, cur
-            elif self.parts == 2:
-                conv(tmp, w2, getattr(self, f"tb{i}b"), skip=cur, out_f32=last)
-            else:
-                conv(tmp, w2, getattr(self, f"tb{i}b"), skip=cur, out=(last,))
-        if heads is not None and fused and self.parts == 2 and c == 128:
-            return None                                                  # the head features are already written
-        return last                                                      # [n, 90, c] channels-last trunk output
+            elif st.to == "pairs":
+                # the last c8 block of a hybrid tower wrote fp32: re-split into (hi, lo) fp16 pairs for the f16x3 blocks
+                _native.split_bias_act(last, None, self._view(cur, "pair"), relu=False)
+            if ev is not None:
+                ev[1].record()
+                self.block_events.append(ev + (len(st.blocks),) if len(st.blocks) > 1 else ev)
+        return None if steps[-1].to == "heads" else last                # else [n, 90, c] channels-last trunk output
 
     def block_kinds(self):
         """Per residual block, the arithmetic its launch runs (tower_plan's kinds): "c6" / "c8" / "pair"."""
@@ -529,141 +592,11 @@ class InferenceNet(nn.Module):
         od = self.operand_dtype
         return (getattr(self, f"tw{i}a").view(od), getattr(self, f"tb{i}a"), getattr(self, f"tw{i}b").view(od), getattr(self, f"tb{i}b"))
 
-    def _tower_chained(self, planes, cur, nxt, last, heads, rows, count, masks):
-        """The fused 128-filter tower as tower_plan's launches.  cur / nxt: two operand buffers of _operands (storage: (f16, image
-        bytes) for the c8 / c6 family, (hi, lo) otherwise); returns like _trunk_mfma."""
-        from cchess_alphazero import _native
-        kinds = self.block_kinds()
-        nblk = len(kinds)
-        heads_ok = heads is not None and self.parts == 2 and self.filters == 128
-        # the head convolutions as a pair chain's exit read the block's value as hi + lo: fp16 pairs stand for it to 2^-22, bf16
-        # pairs only to 2^-17 -- bf16x3 (the guard's last resort before the fp32 library trunk) keeps its HEADS launch, which
-        # works on the fp32 value
-        chain_heads = self.chain_heads and not (kinds[-1] == "pair" and self.operand_dtype == torch.bfloat16)
-        key = ("plan", heads_ok, chain_heads, self.tb0a.data_ptr())     # (device pointers inside: rebuilt if the module moved)
-        if key not in self._bufs:
-            # launch steps + the per-launch pointer arrays, built once (invalidated with the buffers on a weight repack)
-            plan = []
-            for step in tower_plan(kinds, heads_exit=heads_ok, chain_heads=chain_heads):
-                if step[0] in ("tower", "pairs"):
-                    blk = step[1]
-                    fmt = [_native.IMG_C6 if kinds[blk[0]] == "c6" else _native.IMG_C8] * len(blk)     # (one arithmetic per launch)
-                    bl = _native.BlockList([self._block_params(i) for i in blk], *((fmt, fmt) if step[0] == "tower" else ()))
-                    plan.append(step + (bl,))
-                else:
-                    plan.append(step)
-            self._bufs[key] = plan
-        self.last_plan = [st[:3] if st[0] != "first" else st for st in self._bufs[key]]      # (bench.py: what a forward launches)
-        img_tag = {"c6": torch.int8, "c8": torch.uint8}
-
-        def view(t, kind):                      # an operand buffer seen as the pair of `kind`
-            if kind == "pair":
-                return (t[0], t[1].view(t[0].dtype)) if t[1].dtype in (torch.uint8, torch.int8) else t
-            return (t[0], t[1].view(img_tag[kind]))
-        fmt_code = {"c6": _native.IMG_C6, "c8": _native.IMG_C8, "pair": _native.IMG_PAIR}
-        hd = (self.head_w32, self.head_b32, heads[0], heads[1], heads[2]) if heads_ok else None
-        done_heads = False
-        for step in self._bufs[key]:
-            ev = None
-            if self.block_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            if step[0] == "first":
-                w1, b1, w2, b2 = self._block_params(0)
-                _native.input_resblock(planes.contiguous(), self.in_table32, self.in_bias32, w1, b1, w2, b2,
-                                       out=view(nxt, kinds[0]), rows=rows, count=count, masks=masks)
-                cur, nxt = nxt, cur
-                nb = 1
-            elif step[0] == "tower":
-                _, blk, ex, bl = step
-                nb = len(blk)
-                if ex == "heads":
-                    _native.tower(view(cur, kinds[blk[0]]), bl, _native.EXIT_HEADS, heads=hd, count=count)
-                    done_heads = True
-                else:
-                    _native.tower(view(cur, kinds[blk[0]]), bl, fmt_code[ex], out=view(nxt, ex), count=count)
-                    cur, nxt = nxt, cur
-            elif step[0] == "pairs":
-                _, blk, with_heads, bl = step
-                nb = len(blk)
-                if with_heads:
-                    _native.tower_pairs(view(cur, "pair"), bl, heads=hd, count=count)
-                    done_heads = True
-                else:
-                    _native.tower_pairs(view(cur, "pair"), bl, out=view(nxt, "pair"), count=count)
-                    cur, nxt = nxt, cur
-            else:                               # the last block on its own launch
-                i = step[1]
-                nb = 1
-                w1, b1, w2, b2 = self._block_params(i)
-                x = view(cur, kinds[i])
-                if heads_ok:
-                    _native.resblock_heads(x, w1, b1, w2, b2, self.head_w32, self.head_b32, heads[0], heads[1], heads[2],
-                                           count=count)
-                    done_heads = True
-                else:
-                    _native.resblock(x, w1, b1, w2, b2, out_f32=last, count=count)
-            if ev is not None:
-                ev[1].record()
-                self.block_events.append(ev + (nb,) if nb > 1 else ev)
-        return None if done_heads else last
-
-    def _tower_192(self, cur, nxt, last, count):
-        """The 192-filter tower (every split arithmetic) behind cz_input_conv as ip_segments' launches; returns the fp32 trunk output."""
-        from cchess_alphazero import _native
-        kinds = self.block_kinds()
-        nblk = len(kinds)
-        legacy = os.environ.get("CZ_IP_PAIR", "1")[:1] == "0"          # (the six-wave kernels: block 0 of a c6 tower on its own launch)
-        key = ("plan192", legacy, self.tb0a.data_ptr())
-        if key not in self._bufs:
-            self._bufs[key] = [(kind, blk, _native.BlockList([self._block_params(i) for i in blk]))
-                               for kind, blk in ip_segments(kinds, first_alone=legacy)]
-        self.last_plan = [("chain192" if kind == "chain" else "block192", blk, kinds[blk[0]]) for kind, blk, _ in self._bufs[key]]
-        tag = {"c6": torch.int8, "c8": torch.uint8}
-        for kind, blk, bl in self._bufs[key]:
-            ev = None
-            if self.block_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            k, i1 = kinds[blk[0]], blk[-1]
-            tower_end = i1 + 1 == nblk
-            to_pairs = k == "c8" and not tower_end and kinds[i1 + 1] == "pair"
-            if k == "pair":
-                x = self._as_f16_pair(cur)
-                w1, b1, w2, b2 = bl.blocks[0]
-                if kind == "chain" and tower_end:   # consecutive pair blocks in one launch (k_tower_pairs4<E, 192>)
-                    _native.resblock_chain(x, bl, out_f32=last, count=count)
-                elif kind == "chain":
-                    _native.resblock_chain(x, bl, out=self._as_f16_pair(nxt), count=count)
-                    cur, nxt = nxt, cur
-                elif tower_end:
-                    _native.resblock(x, w1, b1, w2, b2, out_f32=last, count=count)
-                else:
-                    _native.resblock(x, w1, b1, w2, b2, out=self._as_f16_pair(nxt), count=count)
-                    cur, nxt = nxt, cur
-            elif kind == "block":                   # a c6 tower's block 0: c8 image in, c6 (or, c6>1, c8) image out
-                w1, b1, w2, b2 = bl.blocks[0]
-                _native.resblock((cur[0], cur[1].view(torch.uint8)), w1, b1, w2, b2, out=(nxt[0], nxt[1].view(torch.int8)),
-                                 count=count, dtype_code=_native.F16C86)
-                cur, nxt = nxt, cur
-            else:
-                # (a c6 chain that starts the tower reads the input layer's c8 image: CZ_F16C86)
-                first6 = k == "c6" and blk[0] == 0
-                x = (cur[0], cur[1].view(torch.uint8 if first6 else tag[k]))
-                code = _native.F16C86 if first6 else None
-                # (a c6 chain whose last block hands over to c8 blocks writes a c8 image)
-                out_tag = tag[kinds[i1 + 1]] if (k == "c6" and not tower_end and kinds[i1 + 1] == "c8") else tag[k]
-                if tower_end or to_pairs:
-                    _native.resblock_chain(x, bl, out_f32=last, count=count, dtype_code=code)
-                    if to_pairs:                    # the hand-over of a c8>N tower: re-split into (hi, lo) fp16 pairs
-                        _native.split_bias_act(last, None, self._as_f16_pair(cur), relu=False)
-                else:
-                    _native.resblock_chain(x, bl, out=(nxt[0], nxt[1].view(out_tag)), count=count, dtype_code=code)
-                    cur, nxt = nxt, cur
-            if ev is not None:
-                ev[1].record()
-                self.block_events.append(ev + (len(blk),) if len(blk) > 1 else ev)
-        return last
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .cuda() / .cpu() replace the module's tensors: the plans' BlockLists hold pointers to the old ones
+        out = super()._apply(fn, *args, **kwargs)
+        self._plans = {}
+        return out
 
     def _head_feats(self, n, npol, device):
         key = ("hf", n, str(device))
@@ -694,14 +627,9 @@ class InferenceNet(nn.Module):
 
     def takes_masks(self, planes_dtype=torch.uint8):
         """True when forward(masks=...) reads the occupancy boards INSTEAD of the planes: the input layer fused into the
-        first residual block (_trunk_mfma's `first_fused`) -- the engine then lets the search kernel skip the planes
+        first residual block (_first_fused) -- the engine then lets the search kernel skip the planes
         (Search.leaf_planes(False))."""
-        if self.trunk != "mfma" or planes_dtype != torch.uint8:
-            return False
-        c, nblk = self.filters, len(self.res)
-        n8 = self.c8_blocks if self.arith == "c8" else 0
-        fused = self.fused_blocks and ((c in (128, 192)) or (c == 256 and self.parts == 1))
-        return bool(fused and self.fused_input and c == 128 and self.parts == 2 and nblk >= 2 and n8 != 1)
+        return self._first_fused(planes_dtype)
 
     def supports_logits(self):
         """True when forward(logits=True) is available: the hand-written dense tail on 6 head filters."""
