@@ -208,9 +208,10 @@ class InferenceNet(nn.Module):
                      with bf16 / fp16 they are plain 2-byte operands.
     arith (trunk="mfma", dtype float32; CZ_TOWER_ARITH overrides the default) -- how an fp32 product is formed:
       "bf16x3"  (hi, lo) bf16 pairs, w_hi x_hi + w_lo x_hi + w_hi x_lo: 2^-17 per product whatever the operands' range;
-      "f16x3"   the same three MFMAs on (hi, lo) fp16 pairs: 22 bits per operand, ~8x more accurate on networks whose
-                activations and folded filters sit in fp16's range (round 4; tools/f16x3_probe.py: the matrix unit honours
-                fp16 subnormals, which the filters' lo parts are), less accurate than bf16x3 when they are tiny;
+      "f16x3"   the same three MFMAs on (hi, lo) fp16 pairs: up to 22 bits per operand, 4-12x more accurate on networks
+                whose activations and folded filters sit in fp16's range (the matrix unit honours fp16 subnormals, which the
+                filters' lo parts are; their step 2^-24 leaves a 0.02 tap ~19.5 bits: 3x at 256 filters), less accurate than
+                bf16x3 when they are tiny -- tests/test_gpu_f16x3.py, bounds in tests/f16_pairs.py;
       "c8"      (128 / 192 filters) an fp16 main term plus two block-scaled fp8 correction terms (csrc/xq_conv.hip,
                 k_resblock_c8 / k_resblock_ip_c8): one fp16 and two fp8 matrix instructions per 64 input channels, 2^-16
                 per product;

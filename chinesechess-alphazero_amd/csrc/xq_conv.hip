@@ -28,6 +28,9 @@
 //     hi*hi + hi*lo + lo*hi in fp32 -- three bf16 MFMAs (1/16 the cost of an fp32 MFMA each) give a product error of
 //     ~1e-5 relative, which keeps policy/value within the 1e-4 the parity contract asks for while running at several
 //     times the fp32 matrix rate.  The epilogue re-splits its fp32 result into (hi, lo) for the next layer.
+//     E = _Float16 ("f16x3"): (hi, lo) fp16 pairs, the same three MFMAs; a pair holds v to 2^-22 |v| + 2^-25 because the
+//     matrix unit honours fp16 subnormals (a filter tap's lo part usually is one).  Every kernel on these pairs is held to
+//     a float64 model of exactly this arithmetic, element by element: tests/test_gpu_f16x3.py, bounds in tests/f16_pairs.py.
 //   * epilogue fused: + bias, + skip (read as hi + lo), ReLU, split / convert, store.  The last trunk layer can
 //     emit fp32 directly (y_f32) for the policy/value heads.
 #include <hip/hip_runtime.h>

@@ -15,7 +15,7 @@
 // values, a product is accumulated as w_hi x_hi + w_lo x_hi + w_hi x_lo in fp32 by v_mfma_f32_32x32x16_{bf16,f16}.
 // dtype CZ_BF16: dropped term and representation error 2^-17 relative per product; CZ_F16 (round 4, what the network
 // uses unless bf16x3 was asked for): (hi, lo) fp16 pairs hold 22 bits where fp16's range holds the lo part (features are
-// O(1), fp16 subnormal inputs are honoured by the matrix unit -- tools/f16x3_probe.py), 2^-21 class, same cost.  Order: K-steps of 16 features in index
+// O(1), fp16 subnormal inputs are honoured by the matrix unit -- tests/test_gpu_f16x3.py), 2^-21 class, same cost.  Order: K-steps of 16 features in index
 // order, the three terms of a step in the order above; the softmax statistics are accumulated per lane over its label
 // tiles in index order, combined across the two half-waves and the four waves of a position tile in a fixed order.
 // Weights are packed on the host in fragment order (cz_fc_pack_weights); they stream from L2 (3 MB for the policy
