@@ -315,12 +315,19 @@ int cz_conv3x3_c8(const void* x_hi, const void* x_c8, const void* w_packed, cons
                   const void* skip_hi, const void* skip_c8, void* y_hi, void* y_c8, float* y_f32,
                   int n_boards, int channels, int relu, void* stream);
 
-/* The c6 tower arithmetic (round 4; k_resblock_c8<.., C6>, 128 filters, whole residual blocks only): the c8 sum with the
- * two correction operands in bf6 (e3m2) -- v_mfma_scale_f32_32x32x64_f8f6f4 retires bf6 operands in 32 cycles, e4m3 ones in
- * 64 (tools/probes/bf6_probe.hip), so a product costs 1.5 instead of 2.0 MFMA-equivalents; per-product accuracy ~2^-15.
- * Activation images keep the c8 pair's shape (x_hi f16 [n][90][128], image bytes [n][90][256]); the image holds, per pixel
+/* The c6 tower arithmetic (round 4; k_resblock_c8<.., C6>; 128 and, since round 6, 192 filters; whole residual blocks only): the
+ * c8 sum with the two correction operands in bf6 (e3m2) -- v_mfma_scale_f32_32x32x64_f8f6f4 retires bf6 operands in 32 cycles, e4m3 ones in
+ * 64 (tools/probes/bf6_probe.hip), so a product costs 1.5 instead of 2.0 MFMA-equivalents; per-product accuracy ~2^-15
+ * (measured on whole blocks against float64, tests/test_gpu_c6_elements.py: 2^-15.1, c8 2^-16.1, bf16x3 2^-17.3).
+ * Activation images keep the c8 pair's shape (x_hi f16 [n][90][C], image bytes [n][90][2 C]); the image holds, per pixel
  * and 32-channel block, a 24-byte piece bf6((x - f16(x)) 2^(11 - k)) and a piece bf6(x 2^-k) (layout: csrc/xq_conv.hip,
- * namespace rb8), k = the image's exponent, 2^k * 28 >= max |x| (from calibration activations; the conversion saturates).
+ * namespace rb8), k = the image's exponent, 2^k * 28 >= max |x| (from calibration activations; the conversion rounds to
+ * nearest even and saturates at 28 2^k, the lo piece at 28 2^(k - 11)).  Of a pixel's 2 C bytes the first C carry the lo
+ * pieces, the last C the value pieces; piece w sits in the 24 bytes at 32 w of its half, element e (6 bits at bit 6 e) =
+ * channel 32 w + 8 (e >> 3) + ((e >> 1) & 3) + 4 (e & 1).  The 8 bytes behind each piece belong to no piece: their content
+ * is unspecified (kernels that stage the image in LDS copy what lies there) and no kernel reads them as data.  The value
+ * the image stands for (the skip operand) is x_hi + lo6 2^(k - 11), an fp32 number; tests/c6_model.py encodes and decodes
+ * the format, and the kernels' images are held to it byte for byte.
  * Filters: cz_conv3x3_c6_pack_weights(w, 128, x_exp, y_exp, out) -- same size as cz_conv3x3_c8_packed_bytes(128) -- with
  * the exponents of the image the convolution READS and of the one it WRITES; a block's w1 / w2 must agree on the
  * intermediate image's exponent, consecutive blocks on the stream image's.  Entry points (dtype CZ_F16C6): cz_resblock,

@@ -26,9 +26,10 @@ def bf6_round(x):
     a = np.minimum(np.abs(x), 28.0)
     d = np.abs(a[..., None] - GRID)
     best = d.argmin(-1)
-    # ties: argmin takes the lower code; the even one may be the upper
-    tie = np.isclose(np.take_along_axis(d, best[..., None], -1)[..., 0],
-                     np.take_along_axis(d, np.minimum(best + 1, 31)[..., None], -1)[..., 0], rtol=0, atol=0)
+    # ties: argmin takes the lower code; the even one may be the upper.  (Code 31 = 28 has no upper neighbour: a clamped
+    # value sits on it, distance 0, and must not be compared with itself.)
+    up = np.minimum(best + 1, 31)
+    tie = (best < 31) & (np.take_along_axis(d, best[..., None], -1)[..., 0] == np.take_along_axis(d, up[..., None], -1)[..., 0])
     best = np.where(tie & (best % 2 == 1), best + 1, best)
     return np.sign(x) * GRID[best]
 
@@ -87,10 +88,21 @@ def test_bf6_conversion_on_a_sweep():
     from cchess_alphazero import _native
     vals = sorted(set([float(g) for g in GRID] + [float((GRID[i] + GRID[i + 1]) / 2) for i in range(31)] +
                       [0.01, 0.03, 0.031, 0.0313, 0.09, 27.0, 27.9]))
-    vals = vals[:96]                                             # (three 32-blocks of channels 0 .. 127 are enough)
+    assert len(vals) <= 96                                       # (three 32-blocks of channels 0 .. 127 are enough)
     w = torch.zeros(128, 128, 3, 3)
     w[0, :len(vals), 0, 0] = torch.tensor(vals) / 2.0            # largest 14 -> shift 0 would put 27.9 / 2 < 16: sh = 0
     w[0, 127, 0, 0] = -15.0                                      # fixes row 0's shift at 0 ([8, 16))
+    # row 1 (largest magnitude 15 -> shift 0 as well): exact ties in both directions -- 9 and 13 go DOWN to the even codes of 8
+    # and 12, 11 and 15 go UP to those of 12 and 16 --, with both signs
+    row1 = [9.0, 11.0, 13.0, 15.0, -9.0, -11.0, -13.0, -15.0]
+    w[1, :len(row1), 0, 0] = torch.tensor(row1)
+    assert bf6_round(np.array(row1)).tolist() == [8.0, 12.0, 12.0, 16.0, -8.0, -12.0, -12.0, -16.0]
+    # saturation: a row's shift keeps its largest magnitude in [8, 16), so no filter value reaches 28 and the packer cannot be
+    # asked; the numpy reference (which tests/c6_model.py's image encoder is checked against, and through it the kernels'
+    # conversion instruction, tests/test_gpu_c6_elements.py) must clamp: 26 is the last tie (24 | 28 -> the even code of 24),
+    # 30 would tie with the missing code 32
+    sat = np.array([26.0, 27.0, 28.0, 29.0, 30.0, 31.0, 448.0, 1e30, -28.5, -30.0, -1e9])
+    assert bf6_round(sat).tolist() == [24.0, 28.0, 28.0, 28.0, 28.0, 28.0, 28.0, 28.0, -28.0, -28.0, -28.0]
     pk = _native.pack_conv3x3_c6_weights(w, 0, 0).numpy()
     main_u4 = (9 * 8 + W_PAD_STEPS) * 4 * 64
     sh = int(pk[(main_u4 + (9 * 2 + 1) * 2 * 4 * 2 * 64 + 1) * 16:].view(np.int8)[0])
@@ -109,3 +121,9 @@ def test_bf6_conversion_on_a_sweep():
     want = bf6_round(src)
     for c in range(128):
         assert got[c] == want[c], (c, src[c], got[c], want[c])
+    lane = 1                                                      # row o = 1, channels 0 .. 31
+    piece = np.concatenate([c6[lane * 16: lane * 16 + 16], c6[1024 + lane * 8: 1024 + lane * 8 + 8]])
+    bits = int.from_bytes(piece.tobytes(), "little")
+    got1 = {channel_of(e): bf6_value((bits >> (6 * e)) & 63) for e in range(32)}
+    assert int(pk[(main_u4 + (9 * 2 + 1) * 2 * 4 * 2 * 64 + 1) * 16:].view(np.int8)[1]) == 0
+    assert [got1[c] for c in range(len(row1))] == bf6_round(np.array(row1)).tolist()

@@ -11,6 +11,9 @@ Pinned three ways, all against float64:
     workgroup, later boards with the deferred epilogue in flight, the last one) or which queue row it is computed in;
   * the tolerance north_star states (policy / value within 1e-4 of the reference network) through the load-time guard
     (GUARD_TOL 5e-5 on calibration positions, 1e-4 with margin on fresh ones), chain c6 -> c8 -> c8>N -> f16x3 -> bf16x3.
+These are network-level checks (a maximum over centred logits).  The kernels themselves -- every image byte they write, the skip
+path, each convolution and every entry point, element by element against float64 on the decoded operands -- are pinned in
+tests/test_gpu_c6_elements.py (model and bounds: tests/c6_model.py).
 """
 import os
 import sys
