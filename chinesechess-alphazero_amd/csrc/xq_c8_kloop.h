@@ -69,8 +69,21 @@ struct Filter {
     int scale_w_hi, scale_w_lo;      // E8M0 scale bytes of the two correction MFMAs (127 - shift), per lane: this row's
 };
 
+// the correction operands' shifts, one pair per OUTPUT CHANNEL (the matrix instruction reads the A operand's E8M0 scale
+// per lane = per row): 2 x CH signed bytes behind the 16-byte block of ints, this lane's row = wave * 32 + (lane & 31)
 template <int CH = 128>
-__device__ __forceinline__ Filter make_filter(const void* packed, int wave, int lane)
+__device__ __forceinline__ void load_filter_shifts(const void* packed, int wave, int lane, int& shift_hi, int& shift_lo)
+{
+    constexpr int MAIN_U4 = Geo<CH>::MAIN_U4, C8_U4 = Geo<CH>::C8_U4;
+    const signed char* rs = reinterpret_cast<const signed char*>(reinterpret_cast<const uint4*>(packed) + MAIN_U4 + C8_U4 + 1);
+    const int row = wave * 32 + (lane & 31);
+    shift_hi = (int)rs[row];
+    shift_lo = (int)rs[CH + row];
+}
+
+// (the shifts handed in: a caller that has requested them ahead of time, load_filter_shifts)
+template <int CH = 128>
+__device__ __forceinline__ Filter make_filter(const void* packed, int wave, int lane, int shift_hi, int shift_lo)
 {
     constexpr int MAIN_U4 = Geo<CH>::MAIN_U4, C8_U4 = Geo<CH>::C8_U4;
     Filter f;
@@ -78,13 +91,17 @@ __device__ __forceinline__ Filter make_filter(const void* packed, int wave, int 
     f.lane_main = wave * 1024 + lane * 16;
     f.lane_c8 = MAIN_U4 * 16 + wave * 2048 + lane * 16;
     f.lane_c6t = MAIN_U4 * 16 + wave * 2048 + 1024 + lane * 8;
-    // the correction operands' shifts, one pair per OUTPUT CHANNEL (the matrix instruction reads the A operand's E8M0 scale
-    // per lane = per row): 2 x CH signed bytes behind the 16-byte block of ints, this lane's row = wave * 32 + (lane & 31)
-    const signed char* rs = reinterpret_cast<const signed char*>(reinterpret_cast<const uint4*>(packed) + MAIN_U4 + C8_U4 + 1);
-    const int row = wave * 32 + (lane & 31);
-    f.scale_w_hi = 127 - (int)rs[row];
-    f.scale_w_lo = 127 - (int)rs[CH + row];
+    f.scale_w_hi = 127 - shift_hi;
+    f.scale_w_lo = 127 - shift_lo;
     return f;
+}
+
+template <int CH = 128>
+__device__ __forceinline__ Filter make_filter(const void* packed, int wave, int lane)
+{
+    int shift_hi, shift_lo;
+    load_filter_shifts<CH>(packed, wave, lane, shift_hi, shift_lo);
+    return make_filter<CH>(packed, wave, lane, shift_hi, shift_lo);
 }
 
 // Hooks: work another part of a kernel wants done in the shadow of the MFMAs (a residual block's second epilogue).
@@ -283,6 +300,185 @@ __device__ __forceinline__ void kloop(const unsigned char* lds, const Image img,
 // to it; what changes is the traffic: a pixel fragment read from LDS feeds CTW MFMAs, and six channel tiles spread evenly over
 // four SIMDs (with one tile per wave two SIMDs carry two matrix waves and two carry one).  flt[c]: the wave's c-th channel tile
 // (make_filter with the tile index in place of the wave index); acc[c * NT + i]: channel tile c, pixel tile i.
+//
+// The loop comes in two halves so that a caller can have the prologue's filter fragments in flight under whatever runs in
+// front of the loop (k_resblock_ip4_c8: an epilogue): kloop_ctw_issue requests wf / wcr -- they depend on nothing but the
+// filter -- into a CtwFrags, kloop_ctw_run does the LDS prologue and the loop on them.  kloop_ctw is the two back to back.
+template <int CTW> struct CtwFrags {
+    f16x8 wf[4][CTW];                                   // fp16 filter fragments, slot = K-step % 4
+    i32x8 wcr[2][CTW];                                  // correction filter pieces by kind
+};
+
+// nothing to do at the loop's hook points (kloop_ctw_run's Hook; a timing build stamps the first MFMA there)
+struct NoHook {
+    __device__ __forceinline__ void first_mfma() {}
+};
+
+// PARTS: 1 = the fp16 fragments, 2 = the correction pieces, 3 = both (a caller short of registers may request one part early)
+template <int CTW, int CH, int FMT, int PARTS = 3>
+__device__ __forceinline__ void kloop_ctw_issue(const Filter* flt, CtwFrags<CTW>& st)
+{
+    constexpr int CT = Geo<CH>::CT, STEP_B = CT * 1024, BLK_B = 2 * CT * 2048;
+    if (FMT == 1 && (PARTS & 2)) {                                     // (registers 6, 7 of a bf6 operand are not read)
+#pragma unroll
+        for (int c = 0; c < CTW; ++c) { st.wcr[0][c][6] = st.wcr[0][c][7] = st.wcr[1][c][6] = st.wcr[1][c][7] = 0; }
+    }
+    if (PARTS & 1)
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int c = 0; c < CTW; ++c)
+            st.wf[s][c] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(flt[c].rsrc, flt[c].lane_main, s * STEP_B, 0));
+    if (PARTS & 2)
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int c = 0; c < CTW; ++c) {
+            i32x8& d = st.wcr[q][c];
+            const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(flt[c].rsrc, flt[c].lane_c8, q * (BLK_B / 2), 0);
+            d[0] = (int)t.x; d[1] = (int)t.y; d[2] = (int)t.z; d[3] = (int)t.w;
+            if (FMT == 0) {
+                const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(flt[c].rsrc, flt[c].lane_c8 + 1024, q * (BLK_B / 2), 0);
+                d[4] = (int)u.x; d[5] = (int)u.y; d[6] = (int)u.z; d[7] = (int)u.w;
+            } else {
+                const u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(flt[c].rsrc, flt[c].lane_c6t, q * (BLK_B / 2), 0);
+                d[4] = (int)u.x; d[5] = (int)u.y;
+            }
+        }
+}
+
+// ISSUE: 0 = the caller has requested all of st; else the PARTS still to request, which happens here (3: kloop_ctw)
+template <int CTW, int NT, int CH, int FMT, typename Hook = NoHook, int ISSUE = 0>
+__device__ __forceinline__ void kloop_ctw_run(const unsigned char* lds, const Image img, const Filter* flt, CtwFrags<CTW>& st,
+                                              int lane, f32x16* acc, int scale_x_lo, int scale_x, Hook hook = Hook())
+{
+    typedef Geo<CH> G;
+    constexpr int RB = G::RB, CPR = G::CPR, SWZ = G::SWZ, KK = G::KK, NB = G::NB, CT = G::CT;
+    const int kb = lane >> 5, ln = lane & 31;
+    int qy[3], qx[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int q = t * 32 + ln;
+        qy[t] = q < 90 ? q / 9 : 100;
+        qx[t] = q - (q / 9) * 9;
+    }
+    auto tap_row = [&](int dy, int dx, int p) {
+        const int t = p % 3;
+        const bool ok = (unsigned)(qy[t] + dy) < 10u && (unsigned)(qx[t] + dx) < 9u;
+        const int nominal = (p / 3) * 90 + t * 32 + ln + dy * 9 + dx;
+        const int row = ok ? img.row_base + nominal : img.zrow + (nominal & 15);
+        return row * RB + (((kb ^ nominal) & SWZ) << 4);
+    };
+    const int lane_c = (kb * 3) << 4;
+    auto load_px = [&](int pre_p, int kk) {
+        const int off = G::POW2 ? pre_p ^ (kk << 5) : (pre_p ^ ((kk & 3) << 5)) + ((kk >> 2) << 7);
+        return __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(lds + off));
+    };
+    auto load_c8 = [&](i32x8& d, int pre_p, int q, int b, int h) {
+        const int c0 = q * (CPR / 2) + 4 * b + h;
+        const int off = G::POW2 ? pre_p ^ lane_c ^ (c0 << 4) : (pre_p ^ lane_c ^ ((c0 & 7) << 4)) + ((c0 >> 3) << 7);
+        if (FMT == 0 || h == 0) {
+            const u32x4 t = *reinterpret_cast<const u32x4*>(lds + img.part_bytes + off);
+            d[4 * h + 0] = t.x; d[4 * h + 1] = t.y; d[4 * h + 2] = t.z; d[4 * h + 3] = t.w;
+        } else {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(lds + img.part_bytes + off);
+            d[4] = t.x; d[5] = t.y;
+        }
+    };
+    constexpr int STEP_B = CT * 1024, BLK_B = 2 * CT * 2048;
+    auto load_w = [&](int c, int step_soff) {
+        return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(flt[c].rsrc, flt[c].lane_main, step_soff, 0));
+    };
+    auto load_wc = [&](i32x8& d, int c, int blk_soff, int q, int h) {
+        if (FMT == 0 || h == 0) {
+            const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(flt[c].rsrc, flt[c].lane_c8 + h * 1024, blk_soff + q * (BLK_B / 2), 0);
+            d[4 * h + 0] = (int)t.x; d[4 * h + 1] = (int)t.y; d[4 * h + 2] = (int)t.z; d[4 * h + 3] = (int)t.w;
+        } else {
+            const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(flt[c].rsrc, flt[c].lane_c6t, blk_soff + q * (BLK_B / 2), 0);
+            d[4] = (int)t.x; d[5] = (int)t.y;
+        }
+    };
+    f16x8 (&wf)[4][CTW] = st.wf;
+    f16x8 px[3][NT];
+    i32x8 cx[NT];
+    i32x8 (&wcr)[2][CTW] = st.wcr;
+    int pre[NT], pre_n[NT];
+    if (FMT == 1) {
+#pragma unroll
+        for (int p = 0; p < NT; ++p) { cx[p][6] = 0; cx[p][7] = 0; }
+        if (ISSUE & 2) {
+#pragma unroll
+            for (int c = 0; c < CTW; ++c) { wcr[0][c][6] = wcr[0][c][7] = wcr[1][c][6] = wcr[1][c][7] = 0; }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < NT; ++p) pre[p] = tap_row(-1, -1, p);
+    if (ISSUE) kloop_ctw_issue<CTW, CH, FMT, ISSUE>(flt, st);
+#pragma unroll
+    for (int p = 0; p < NT; ++p) {
+        px[0][p] = load_px(pre[p], 0);
+        px[1][p] = load_px(pre[p], 1);
+    }
+    static_assert((3 * KK) % 3 == 0, "ring indices are static per iteration");
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j) {
+        const int soff_j = j * (3 * KK * STEP_B), boff_j = j * (3 * NB * BLK_B);
+#pragma unroll
+        for (int tt = 0; tt < 3; ++tt) {
+            const int ndy = tt < 2 ? j - 1 : (j < 2 ? j : 1), ndx = tt < 2 ? tt : (j < 2 ? -1 : 1);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+#pragma unroll
+                    for (int k2 = 0; k2 < 2; ++k2) {
+                        const int kk = b * 4 + half * 2 + k2;
+                        const int g = tt * KK + kk;
+#pragma unroll
+                        for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                            for (int c = 0; c < CTW; ++c)
+                                acc[c * NT + i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kk & 3][c], px[g % 3][i], acc[c * NT + i], 0, 0, 0);
+                            if (tt == 0 && kk == 0 && i == 0 && j == 0) hook.first_mfma();
+                            const int kn = kk + 2;
+                            px[(g + 2) % 3][i] = kn < KK ? load_px(pre[i], kn) : load_px(pre_n[i], kn - KK);
+                            const int s6 = k2 * NT + i;                    // piece s6 of the 2 NT pixel pieces of this half block
+                            load_c8(cx[s6 >> 1], pre[s6 >> 1], half, b, s6 & 1);
+                            if (i < CTW) {                                 // the filter pieces of the kind used one group ago, next block
+                                const int q = 1 - half;
+                                const int blk_next = tt * NB + b + (half == 0 ? 0 : 1);
+                                load_wc(wcr[q][i], i, boff_j + blk_next * BLK_B, q, k2);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                        for (int c = 0; c < CTW; ++c)
+                            acc[c * NT + i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                                wcr[half][c], cx[i], acc[c * NT + i], FMT ? 3 : 0, FMT ? 3 : 0, 0,
+                                half ? flt[c].scale_w_lo : flt[c].scale_w_hi, 0, half ? scale_x : scale_x_lo);
+                        if (i < 2) {                                       // the fp16 fragments of the two K-steps just retired, one block ahead
+                            const int kk = b * 4 + half * 2 + i;
+#pragma unroll
+                            for (int c = 0; c < CTW; ++c) wf[kk & 3][c] = load_w(c, soff_j + (tt * KK + kk + 4) * STEP_B);
+                        }
+                        if (b == 0 && half == 0) pre_n[i] = tap_row(ndy, ndx, i);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < NT; ++p) pre[p] = pre_n[p];
+        }
+    }
+}
+
+// The whole loop in one piece, for callers that have nothing to run between the request and the loop (the 192-filter kernels,
+// tools/probes/c8_kloop_probe.hip): kloop_ctw_issue + kloop_ctw_run written out as the one function they were cut from.  (Calling
+// the two back to back instead is the same instruction stream per accumulator tile but not the same register allocation: the
+// 192-filter c6 chain that starts the tower went from 276 to 420 bytes of scratch per lane that way.)
 template <int CTW, int NT, int CH, int FMT>
 __device__ __forceinline__ void kloop_ctw(const unsigned char* lds, const Image img, const Filter* flt, int lane, f32x16* acc,
                                           int scale_x_lo, int scale_x)

@@ -2324,6 +2324,42 @@ __global__ __launch_bounds__((C / 32) * 64 + ip::COPY_THREADS, 1) void k_resbloc
 // pieces.  XF / YF as in k_resblock_ip_c8 (<0, 0> c8, <1, 1> c6, <0, 1> the tower's first c6 block; a chain runs one of them).  Per accumulator tile the same products in the same order and the same
 // epilogue arithmetic as k_resblock_ip_c8: bit-identical.
 constexpr int IP4_EXIT_PAIRS = 2, IP4_EXIT_HEADS = 3;
+// Between the K loops (128 filters; PF below): one wave per SIMD has nothing else to run while it waits for a load, so whatever
+// a phase needs from global memory is requested one phase early and consumed behind the next barrier (plain loads survive
+// __syncthreads()):
+//   * K loop 2's first filter fragments (c8k::kloop_ctw_issue) are requested before epilogue 1 -- on c6 the correction pieces
+//     only (CZ_IP4_K2_EARLY_C6 = 2: with the fp16 fragments as well the c6 kernel spills) --, the NEXT block's K loop 1
+//     fragments (the next pair's block 0 behind the last block) before epilogue 2 / the exit;
+//   * block g + 2's biases are loaded before epilogue 1 and stored to LDS behind barrier B;
+//   * the exits read a step's LDS operands one step ahead of the arithmetic on them.
+// Per accumulator tile the products and every sum keep their order: bit-identical.  At 192 filters the kernel spills already
+// and keeps the plain order (PF = 0).  CZ_IP4_PREFETCH (variant builds, tools/ip4_stamps.py): a mask of the items above
+// (1 K loop 2's fragments, 16 the next K loop 1's, 4 biases, 8 exits), 0 = the plain order everywhere.  (Requesting the next
+// block's scale bytes and exponent words a block early as well measured 0.6 % slower: EXPERIMENTS.md.)
+#ifndef CZ_IP4_PREFETCH
+#define CZ_IP4_PREFETCH 29
+#endif
+#ifndef CZ_IP4_K2_EARLY_C6
+#define CZ_IP4_K2_EARLY_C6 2
+#endif
+#ifdef CZ_IP4_STAMPS
+// timing build (tools/ip4_stamps.py; never the default library): shader-cycle stamps of one wave per board around the phases
+// of every block of workgroup 0's second pair -- [board][block][IP4_STAMP_*]
+__device__ long long g_ip4_stamps[2 * 12 * 16];
+#define IP4_STAMP(i) do { if (stamp_on) g_ip4_stamps[(bd * 12 + blk) * 16 + (i)] = clock64(); } while (0)
+struct Ip4FirstMfma {
+    long long* at;
+    __device__ __forceinline__ void first_mfma() { if (at) *at = clock64(); }
+};
+#define IP4_HOOK(i) Ip4FirstMfma{stamp_on ? &g_ip4_stamps[(bd * 12 + blk) * 16 + (i)] : nullptr}
+// (the whole K loop, with the stamp behind its first MFMA)
+#define IP4_KLOOP(FMT, flt, sxl, sx, i) do { c8k::CtwFrags<CTW> st_; \
+        c8k::kloop_ctw_run<CTW, NT, C, FMT, Ip4FirstMfma, 3>(lds, img, flt, st_, lane, acc, sxl, sx, IP4_HOOK(i)); } while (0)
+#else
+#define IP4_KLOOP(FMT, flt, sxl, sx, i) c8k::kloop_ctw<CTW, NT, C, FMT>(lds, img, flt, lane, acc, sxl, sx)
+#define IP4_STAMP(i) do { } while (0)
+#define IP4_HOOK(i) c8k::NoHook()
+#endif
 // MIX (with <1, 1>): the chain starts the tower -- its block 0 reads the input layer's c8 image (first filter c8-packed: CZ_F16C86)
 template <int C, int XF, int YF, bool MIX = false>
 __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
@@ -2474,27 +2510,49 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             *reinterpret_cast<c8k::u32x2*>(P1 + choff(bd, q, c1 + 1)) = c8k::u32x2{pv[4], pv[5]};
         }
     };
+    constexpr int PF = C == 128 ? (CZ_IP4_PREFETCH) : 0;        // what is requested a phase early (the mask above the kernel)
+    constexpr int K2E = YF ? (CZ_IP4_K2_EARLY_C6) : 3;          // the parts of K loop 2's fragments requested before epilogue 1
+    static_assert(!MIX || PF == 0, "the early requests assume one image format per chain");
+    static_assert(C <= NTHR, "a thread carries one bias of each convolution");
+    // the first fragments of block blk's K loop 1 (they depend on the filter alone)
+    c8k::CtwFrags<CTW> frags;
+    auto issue_k1 = [&](int blk) __attribute__((always_inline)) {
+        c8k::Filter f[CTW];
+#pragma unroll
+        for (int c = 0; c < CTW; ++c) f[c] = c8k::make_filter<C>(ch.w1[blk], tile0 + c, lane, 0, 0);
+        c8k::kloop_ctw_issue<CTW, C, XF>(f, frags);
+    };
+    if (PF & 16) issue_k1(0);
+#ifdef CZ_IP4_STAMPS
+    int pair_no = 0;
+#endif
     int g = 0;                                                  // running block count: its parity picks the bias buffer
     for (;;) {
         __syncthreads();                                        // A: the images hold pair t, the bias buffers are written
+#ifdef CZ_IP4_STAMPS
+        const bool stamp_on = blockIdx.x == 0 && (wave & 1) == 0 && pair_no == 1;
+        ++pair_no;
+#endif
         for (int blk = 0; blk < NB; ++blk, ++g) {
+            IP4_STAMP(0);
             const void* w1p = ch.w1[blk];
             const void* w2p = ch.w2[blk];
+            const int blk_next = blk + 1 == NB ? 0 : blk + 1;
+            static_assert(!MIX || (XF == 1 && YF == 1), "a c6 chain whose first block reads a c8 image");
+            const bool xf = MIX ? blk != 0 : XF != 0;           // the format of the image this block's first convolution reads
             c8k::Filter flt1[CTW], flt2[CTW];
 #pragma unroll
             for (int c = 0; c < CTW; ++c) {
                 flt1[c] = c8k::make_filter<C>(w1p, tile0 + c, lane);
                 flt2[c] = c8k::make_filter<C>(w2p, tile0 + c, lane);
             }
-            const float* bias1 = reinterpret_cast<const float*>(lds + BIAS_OFF) + (g & 1) * 2 * C;
-            const float* bias2 = bias1 + C;
             const int* ints1 = reinterpret_cast<const int*>(reinterpret_cast<const uint4*>(w1p) + c8k::Geo<C>::MAIN_U4 + c8k::Geo<C>::C8_U4);
             const int* ints2 = reinterpret_cast<const int*>(reinterpret_cast<const uint4*>(w2p) + c8k::Geo<C>::MAIN_U4 + c8k::Geo<C>::C8_U4);
-            static_assert(!MIX || (XF == 1 && YF == 1), "a c6 chain whose first block reads a c8 image");
-            const bool xf = MIX ? blk != 0 : XF != 0;           // the format of the image this block's first convolution reads
             const int k_x = xf ? __builtin_amdgcn_readfirstlane(ints1[2]) : 0;
             const int k_y = YF ? __builtin_amdgcn_readfirstlane(ints2[2]) : 0;
             const int k_out = YF ? __builtin_amdgcn_readfirstlane(ints2[3]) : CZ_C6_OUT_C8;
+            const float* bias1 = reinterpret_cast<const float*>(lds + BIAS_OFF) + (g & 1) * 2 * C;
+            const float* bias2 = bias1 + C;
             float* yf = blk == NB - 1 ? yf_last : nullptr;      // fp32 output: the chain's last block only
             f32x16 acc[CTW * NT];
 #pragma unroll
@@ -2510,12 +2568,23 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                 }
             const c8k::Image img{bd * 90, ip::ROW_Z, PSTR};
             __builtin_amdgcn_s_setprio(3);
-            if (MIX && !xf) c8k::kloop_ctw<CTW, NT, C, 0>(lds, img, flt1, lane, acc, 127 - cf8::X_LO_SHIFT, 127);
-            else c8k::kloop_ctw<CTW, NT, C, XF>(lds, img, flt1, lane, acc, 127 + k_x - cf8::X_LO_SHIFT, 127 + k_x);
+            IP4_STAMP(1);
+            if (MIX && !xf) IP4_KLOOP(0, flt1, 127 - cf8::X_LO_SHIFT, 127, 2);
+            else if (!(PF & 16)) IP4_KLOOP(XF, flt1, 127 + k_x - cf8::X_LO_SHIFT, 127 + k_x, 2);
+            else c8k::kloop_ctw_run<CTW, NT, C, XF>(lds, img, flt1, frags, lane, acc, 127 + k_x - cf8::X_LO_SHIFT, 127 + k_x, IP4_HOOK(2));
             __builtin_amdgcn_s_setprio(0);
+            IP4_STAMP(3);
             __syncthreads();                                    // K1: both waves of a board have read its image
+            IP4_STAMP(4);
             int ln2 = ln, kb2 = kb;
             asm volatile("" : "+v"(ln2), "+v"(kb2));
+            // in flight under epilogue 1: K loop 2's first fragments, block g + 2's biases
+            if (PF & 1) c8k::kloop_ctw_issue<CTW, C, YF, K2E>(flt2, frags);
+            float nb1 = 0.0f, nb2 = 0.0f;
+            if ((PF & 4) && NB > 1 && tid < C) {
+                nb1 = ch.b1[(g + 2) % NB][tid];
+                nb2 = ch.b2[(g + 2) % NB][tid];
+            }
             // epilogue 1, in place: this lane's skip elements out of the image, relu(acc) in the operand format over them, the
             // freed accumulators restart at b2 + skip
 #pragma unroll
@@ -2599,13 +2668,27 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                     }
                 }
             }
+            IP4_STAMP(5);
             __syncthreads();                                    // B: the images hold the intermediate activation; block g's biases are consumed
-            if (NB > 1) write_bias(g + 2);
+            if ((PF & 4) && NB > 1) {
+                if (tid < C) {                                  // (write_bias(g + 2), its loads made before epilogue 1)
+                    float* dst = reinterpret_cast<float*>(lds + BIAS_OFF) + (g & 1) * 2 * C;
+                    dst[tid] = nb1;
+                    dst[C + tid] = nb2;
+                }
+            } else if (NB > 1) write_bias(g + 2);
+            IP4_STAMP(6);
             __builtin_amdgcn_s_setprio(3);
-            c8k::kloop_ctw<CTW, NT, C, YF>(lds, img, flt2, lane, acc, 127 + k_y - cf8::X_LO_SHIFT, 127 + k_y);
+            if (!(PF & 1)) IP4_KLOOP(YF, flt2, 127 + k_y - cf8::X_LO_SHIFT, 127 + k_y, 7);
+            else c8k::kloop_ctw_run<CTW, NT, C, YF, decltype(IP4_HOOK(7)), 3 ^ K2E>(lds, img, flt2, frags, lane, acc, 127 + k_y - cf8::X_LO_SHIFT, 127 + k_y, IP4_HOOK(7));
             __builtin_amdgcn_s_setprio(0);
+            IP4_STAMP(8);
             __syncthreads();                                    // K2: both waves of a board have read it
+            IP4_STAMP(9);
             asm volatile("" : "+v"(ln2), "+v"(kb2));
+            // in flight under epilogue 2 and the exit: the next block's K loop 1 fragments (behind the last block: block 0's,
+            // for the next pair)
+            if (PF & 16) issue_k1(blk_next);
             // epilogue 2: relu(acc) -> the operand triple over the image, or fp32 straight to HBM for the last block of a tower
             const int ex = blk == NB - 1 ? exit_mode : 0;
             // byte offset of channels chn .. chn + 3 (fp32) of pixel q in the board's staging (128 filters)
@@ -2664,7 +2747,9 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                     }
                 }
             }
+            IP4_STAMP(10);
             __syncthreads();                                    // C: the result is in the images
+            IP4_STAMP(11);
             if (C == 128 && ex != 0) {
                 // the exit of board 2 t + bd by its two waves: item i = (pixel i >> 2, 32-channel block i & 3)
                 const int board = 2 * t + bd;
@@ -2679,10 +2764,21 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                         if (board >= n_boards) continue;
                         const size_t ebase = (size_t)board * 90 * C;
                         _Float16* yl = reinterpret_cast<_Float16*>(yc);
+                        // (PF & 8: a step's two quads are read while the step before is converted and stored)
+                        float4 fq[2][2];
+                        auto ld = [&](int k8) {
+                            fq[k8 & 1][0] = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 8 * k8));
+                            fq[k8 & 1][1] = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 8 * k8 + 4));
+                        };
+                        if (PF & 8) ld(0);
 #pragma unroll
                         for (int k8 = 0; k8 < 4; ++k8) {
-                            const float4 f0 = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 8 * k8));
-                            const float4 f1 = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 8 * k8 + 4));
+                            if (!(PF & 8)) ld(k8);
+                            else if (k8 + 1 < 4) {
+                                ld(k8 + 1);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                            const float4 f0 = fq[k8 & 1][0], f1 = fq[k8 & 1][1];
                             const float r[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
                             H8 hi, lo;
 #pragma unroll
@@ -2694,9 +2790,37 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                             }
                             reinterpret_cast<u4*>(yh + ebase)[qq * 16 + b32 * 4 + k8] = __builtin_bit_cast(u4, hi);
                             reinterpret_cast<u4*>(yl + ebase)[qq * 16 + b32 * 4 + k8] = __builtin_bit_cast(u4, lo);
+                            if (PF & 8) __builtin_amdgcn_sched_barrier(0);
                         }
                     } else {
                         float a6[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                        if (PF & 8) {
+                            // a step's feature quad and six weight quads in registers of their own, the next step's requested
+                            // before this one's arithmetic; the six sums side by side, each in the plain loop's order
+                            float4 fq[2], wq[2][6];
+                            auto ld = [&](int k4) {
+                                fq[k4 & 1] = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 4 * k4));
+#pragma unroll
+                                for (int o = 0; o < 6; ++o)
+                                    wq[k4 & 1][o] = *reinterpret_cast<const float4*>(hwl + o * C + b32 * 32 + 4 * k4);
+                            };
+                            ld(0);
+#pragma unroll
+                            for (int k4 = 0; k4 < 8; ++k4) {
+                                if (k4 + 1 < 8) ld(k4 + 1);
+                                __builtin_amdgcn_sched_barrier(0);
+                                const float4 f = fq[k4 & 1];
+#pragma unroll
+                                for (int o = 0; o < 6; ++o) a6[o] += f.x * wq[k4 & 1][o].x;
+#pragma unroll
+                                for (int o = 0; o < 6; ++o) a6[o] += f.y * wq[k4 & 1][o].y;
+#pragma unroll
+                                for (int o = 0; o < 6; ++o) a6[o] += f.z * wq[k4 & 1][o].z;
+#pragma unroll
+                                for (int o = 0; o < 6; ++o) a6[o] += f.w * wq[k4 & 1][o].w;
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        } else
 #pragma unroll
                         for (int k4 = 0; k4 < 8; ++k4) {
                             const float4 f = *reinterpret_cast<const float4*>(lds + stg(qq, b32 * 32 + 4 * k4));
@@ -2723,12 +2847,18 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                     }
                 }
             }
+            IP4_STAMP(12);
         }
+#ifdef CZ_IP4_STAMPS
+        const int blk = NB - 1;                                 // (the pair's own phases: in the last block's row)
+#endif
         if (!yf_last && exit_mode == 0) drain(t);
+        IP4_STAMP(13);
         t += stride;
         if (t >= n_pairs) break;
         __syncthreads();                                        // (drain has read the images)
         fill(t);
+        IP4_STAMP(14);
     }
 }
 
@@ -3020,6 +3150,13 @@ inline float f16_bits_to_f32(uint16_t b)
 }
 
 }  // namespace
+
+#ifdef CZ_IP4_STAMPS
+extern "C" int cz_debug_ip4_stamps(long long* out384_host)
+{
+    return hipMemcpyFromSymbol(out384_host, HIP_SYMBOL(g_ip4_stamps), sizeof(g_ip4_stamps)) == hipSuccess ? CZ_OK : CZ_ERR_HIP;
+}
+#endif
 
 #ifdef CZ_RB_STAMPS
 extern "C" int cz_debug_rb_stamps(long long* out32_host)
