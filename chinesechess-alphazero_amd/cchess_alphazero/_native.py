@@ -125,6 +125,16 @@ def _declare(L):
         L.cz_policy_value_loss.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, C.c_float, C.c_float,
                                            vp, vp, vp, vp, vp]
         L.cz_policy_value_loss.restype = i32
+    if hasattr(L, "cz_label_mirror"):
+        L.cz_label_mirror.argtypes = [vp]
+        L.cz_label_mirror.restype = i32
+    if hasattr(L, "cz_gather_planes_m"):
+        L.cz_gather_planes_m.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
+        L.cz_gather_planes_m.restype = i32
+    if hasattr(L, "cz_policy_value_loss_m"):
+        L.cz_policy_value_loss_m.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, C.c_float,
+                                             C.c_float, vp, vp, vp, vp, vp]
+        L.cz_policy_value_loss_m.restype = i32
     if hasattr(L, "cz_search_create"):
         from . import _native_search
         _native_search.declare(L)
@@ -153,6 +163,19 @@ def label_tables():
         check(lib().cz_label_tables(lo.ctypes.data, ft.ctypes.data), "cz_label_tables")
         _tables = (lo.reshape(NSQ, NSQ), (ft >> 8).astype(np.uint8), (ft & 0xFF).astype(np.uint8))
     return _tables
+
+
+_mirror = None
+
+
+def label_mirror():
+    """uint16 [2086]: the label of each move's left-right mirror image, "x0y0x1y1" -> "(8-x0)y0(8-x1)y1" (cz_label_mirror)."""
+    global _mirror
+    if _mirror is None:
+        m = np.zeros(NLABELS, dtype=np.uint16)
+        check(lib().cz_label_mirror(m.ctypes.data), "cz_label_mirror")
+        _mirror = m
+    return _mirror
 
 
 def _stream():
@@ -243,25 +266,39 @@ def replay_games(init_boards, labels, offsets):
     return boards, prev, bad
 
 
-def gather_planes(boards, prev, idx, depth=14, out=None):
+def _flags(mirror, b):
+    import torch
+    assert mirror.shape == (b,), (tuple(mirror.shape), b)
+    return _dev(mirror, torch.uint8)
+
+
+def gather_planes(boards, prev, idx, depth=14, out=None, mirror=None):
     """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B]); depth 28 adds the position prev[i]
-    (zero planes where prev is -1) (cz_gather_planes)."""
+    (zero planes where prev is -1) (cz_gather_planes).  mirror: uint8 [B] on the device, a row with a nonzero flag gets the
+    planes of the left-right mirrored position (cz_gather_planes_m); None calls the unflagged entry point."""
     import torch
     require_gpu()
     b = idx.shape[0]
     if out is None:
         out = torch.empty((b, depth, 10, 9), dtype=torch.float32, device=idx.device)
     assert out.shape == (b, depth, 10, 9)
+    if mirror is not None:
+        check(lib().cz_gather_planes_m(_dev(boards, torch.int8), _opt(prev, torch.int32), boards.shape[0],
+                                       _dev(idx, torch.int32), _flags(mirror, b), b, depth, _dev(out, torch.float32),
+                                       _stream()), "cz_gather_planes_m")
+        return out
     check(lib().cz_gather_planes(_dev(boards, torch.int8), _opt(prev, torch.int32), boards.shape[0], _dev(idx, torch.int32),
                                  b, depth, _dev(out, torch.float32), _stream()), "cz_gather_planes")
     return out
 
 
-def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0):
+def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0,
+                      mirror=None):
     """Per-row policy loss, squared value error and the gradients of w_p mean(policy loss) + w_v mean(sq. error) with
     respect to the logits [B, 2086] and the value [B] (cz_policy_value_loss; mode 0 played one-hot, 1 visit counts).
     logits may have a leading dimension > 2086 (a row-strided view).  Visit arrays with no entries (or None) leave every
-    row on the played move's one-hot."""
+    row on the played move's one-hot.  mirror: uint8 [B] on the device, a flagged row's target labels go through
+    label_mirror() (cz_policy_value_loss_m); None calls the unflagged entry point."""
     import torch
     require_gpu()
     assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
@@ -271,6 +308,16 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
     se = torch.empty((b,), dtype=torch.float32, device=dev)
     gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
     gv = torch.empty((b,), dtype=torch.float32, device=dev)
+    if mirror is not None:
+        check(lib().cz_policy_value_loss_m(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
+                                           _dev(idx, torch.int32), _flags(mirror, b), b, played.shape[0],
+                                           _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16),
+                                           _opt(vis_count, torch.int32), 0 if vis_label is None else vis_label.shape[0],
+                                           _dev(played, torch.uint16), _dev(z, torch.float32), int(mode), float(w_p),
+                                           float(w_v), _dev(pl, torch.float32), _dev(se, torch.float32),
+                                           _dev(gl, torch.float32), _dev(gv, torch.float32), _stream()),
+              "cz_policy_value_loss_m")
+        return pl, se, gl, gv
     check(lib().cz_policy_value_loss(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
                                      _dev(idx, torch.int32), b, played.shape[0], _opt(row_ptr, torch.int32),
                                      _opt(vis_label, torch.uint16), _opt(vis_count, torch.int32),

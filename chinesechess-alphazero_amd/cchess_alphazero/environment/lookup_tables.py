@@ -42,6 +42,19 @@ def flip_policy(pol):
     return np.asarray([pol[ind] for ind in Unflipped_index])
 
 
+def mirror_move(x):
+    """The move on the left-right mirrored board, file x <-> 8 - x (the rules do not tell the two wings apart)."""
+    return f"{8 - int(x[0])}{x[1]}{8 - int(x[2])}{x[3]}"
+
+
+MirrorLabels = [_index[mirror_move(x)] for x in ActionLabelsRed]      # label index -> label index, an involution
+
+
+def mirror_policy(pol):
+    """The policy of the mirrored position: out[MirrorLabels[i]] = pol[i]."""
+    return np.asarray([pol[ind] for ind in MirrorLabels])
+
+
 def label_index(move):
     """4-digit move string -> label index (KeyError if the move is not in the label set)."""
     return _index[move]

@@ -158,6 +158,12 @@ def fliped_state(state):
     return array_to_state(-state_to_array(state)[::-1])
 
 
+def mirror_state(state):
+    """The left-right mirrored position (file x <-> 8 - x): every row of the state string reversed.  Legal moves, `done`
+    and the planes of the mirrored state are the mirror images of the state's (lookup_tables.mirror_move)."""
+    return array_to_state(state_to_array(state).reshape(10, 9)[:, ::-1].reshape(90))
+
+
 _S2B = str.maketrans("kKeEmMsS", "nNbBaAkK")
 _B2S = str.maketrans("nNbBaAkK", "kKeEmMsS")
 

@@ -169,17 +169,24 @@ class ReplayWindow:
         self.n_games += len(games)
         return P
 
-    def planes(self, idx):
-        """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B] on the device)."""
-        return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth)
+    def planes(self, idx, mirror=None):
+        """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B] on the device).  mirror: uint8 [B] on the
+        device, or None: a row with a nonzero flag is the left-right mirrored position (cz_gather_planes_m)."""
+        return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth, mirror=mirror)
 
-    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0)):
+    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None):
         """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
-        differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss)."""
-        return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]))
+        differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss).  mirror: the flags given to
+        ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m)."""
+        return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror)
 
-    def dense_targets(self, idx, targets="visits"):
-        """Host float32 [B, 2086] policy targets of the positions idx as the loss kernel forms them (tests, tools)."""
+    def dense_targets(self, idx, targets="visits", mirror=None):
+        """Host float32 [B, 2086] policy targets of the positions idx as the loss kernel forms them (tests, tools); mirror:
+        per-row flags (anything np.asarray takes, or a tensor), a flagged row's labels go through _native.label_mirror()."""
+        if mirror is None:
+            flags, M = np.zeros(len(idx), dtype=bool), None
+        else:
+            flags, M = np.asarray(mirror.cpu() if hasattr(mirror, "cpu") else mirror) != 0, _native.label_mirror()
         rp = self.row_ptr[:self.n + 1].cpu().numpy()
         lab = self.vis_label[:self.nnz].cpu().numpy()
         cnt = self.vis_count[:self.nnz].cpu().numpy()
@@ -191,9 +198,9 @@ class ReplayWindow:
             total = int(cnt[lo:hi].sum())
             if targets == "visits" and total > 0:
                 for k in range(lo, hi):
-                    out[r, lab[k]] = np.float32(int(cnt[k]) / total)
+                    out[r, M[lab[k]] if flags[r] else lab[k]] = np.float32(int(cnt[k]) / total)
             else:
-                out[r, played[i]] = 1.0
+                out[r, M[played[i]] if flags[r] else played[i]] = 1.0
         return out
 
 
@@ -201,11 +208,11 @@ class _PolicyValueLoss(torch.autograd.Function):
     """w_p * mean(policy loss) + w_v * mean(value loss) of a minibatch; backward hands out the kernel's gradients."""
 
     @staticmethod
-    def forward(ctx, logits, v, idx, win, mode, w_p, w_v):
+    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None):
         n = win.n
         pl, se, gl, gv = _native.policy_value_loss(
             logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
-            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v)
+            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror)
         ctx.save_for_backward(gl, gv)
         pm, vm = pl.mean(), se.mean()
         ctx.mark_non_differentiable(pm, vm)
@@ -214,4 +221,4 @@ class _PolicyValueLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_pm, _g_vm):
         gl, gv = ctx.saved_tensors
-        return g_total * gl, g_total * gv, None, None, None, None, None
+        return g_total * gl, g_total * gv, None, None, None, None, None, None

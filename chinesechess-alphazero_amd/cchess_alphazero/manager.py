@@ -40,6 +40,9 @@ _FLAGS = [
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
+    ("--augment", dict(choices=["none", "mirror"], default="none",
+                       help="(opt) mirror: every training row of every epoch is the left-right mirrored position with "
+                            "probability 1/2 (planes and policy targets, in the trainer's kernels)")),
 ]
 
 
@@ -71,6 +74,7 @@ def build_config(args):
     if args.record_visits:
         engine.record_visits = True
     config.trainer.policy_targets = args.policy_targets
+    config.trainer.augment = args.augment
     return config
 
 

@@ -16,6 +16,13 @@ Deliberate deviations from the reference:
     where it is (the reference deletes it);
   - ``--policy-targets visits`` trains the policy on the records' root visit counts (items [move, value, pi]); the
     default, ``played``, is the reference's one-hot of the played move;
+  - ``--augment mirror`` (default ``none``: the reference, no augmentation) shows every training row of every epoch as
+    its left-right mirror image with probability 1/2 -- Xiangqi's rules do not tell the two wings apart, so the image
+    is a position the same game could have reached.  ``cz_gather_planes_m`` mirrors the 90-byte board and
+    ``cz_policy_value_loss_m`` the sparse target labels; no dense tensor is flipped.  The flags come from a generator of
+    their own, so the shuffles are those of a run without the option; validation rows are never mirrored, and the
+    epoch also reports the validation losses of the all-mirrored rows (``val_mirror``): its gap to ``val`` shows how
+    unevenly the network treats the two wings;
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -104,7 +111,12 @@ class OptimizeWorker:
         self.total_steps = config.trainer.start_total_steps
         self.depth = input_depth(config)
         self.targets = getattr(config.trainer, "policy_targets", "played")
+        self.augment = getattr(config.trainer, "augment", "none")
+        if self.augment not in ("none", "mirror"):
+            raise ValueError(f"trainer.augment={self.augment!r}: expected none or mirror")
         self.rng = np.random.default_rng(config.engine.base_seed)
+        # the mirror flags have their own stream: self.rng draws what it draws without the option
+        self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
         self.history = []               # per epoch: the logged losses
 
     def start(self):
@@ -211,37 +223,55 @@ class OptimizeWorker:
         bs = tc.batch_size
         for ep in range(epochs):
             perm = torch.from_numpy(self.rng.permutation(tr).astype(np.int32)).to(dev)
+            flags = self.mirror_flags(len(tr))
+            flags_d = torch.from_numpy(flags).to(dev) if flags is not None else None
             net.train()
             sums = torch.zeros(3, dtype=torch.float64, device=dev)
             t0 = time.time()
             for b in range(0, len(tr), bs):
                 idx = perm[b:b + bs]
-                loss, pm, vm = self.step(idx)
+                loss, pm, vm = self.step(idx, None if flags_d is None else flags_d[b:b + bs])
                 sums += torch.stack([loss.detach(), pm, vm]).double() * len(idx)
             tr_loss = (sums / max(1, len(tr))).tolist()
             va_loss = self.evaluate(va_d) if len(va) else [float("nan")] * 3
-            self.history.append(dict(train=tr_loss, val=va_loss))
+            entry = dict(train=tr_loss, val=va_loss)
             logger.info(f"epoch {ep + 1}/{epochs}: {len(tr)} positions in {time.time() - t0:.1f} s; "
                         f"loss {tr_loss[0]:.4f} policy {tr_loss[1]:.4f} value {tr_loss[2]:.4f} - "
                         f"val_loss {va_loss[0]:.4f} val_policy {va_loss[1]:.4f} val_value {va_loss[2]:.4f}")
+            if flags is not None:
+                vm_loss = self.evaluate(va_d, mirror=True) if len(va) else [float("nan")] * 3
+                entry["val_mirror"] = vm_loss
+                logger.info(f"epoch {ep + 1}/{epochs}: {int(flags.sum())} of {len(tr)} training rows mirrored; all "
+                            f"validation rows mirrored: val_loss {vm_loss[0]:.4f} val_policy {vm_loss[1]:.4f} "
+                            f"val_value {vm_loss[2]:.4f}")
+            self.history.append(entry)
         return steps_of_pass(n, bs, epochs)
+
+    def mirror_flags(self, n):
+        """uint8 [n]: one fair coin per training row of an epoch from the flags' own generator; None without
+        ``--augment mirror`` (nothing is drawn then)."""
+        if self.aug_rng is None:
+            return None
+        return self.aug_rng.integers(0, 2, size=n, dtype=np.uint8)
 
     def l2_term(self):
         return self.config.model.l2_reg * sum((w * w).sum() for w in self.l2)
 
-    def step(self, idx):
-        """One SGD step on the window positions idx; returns (total loss incl. L2, policy loss, value loss)."""
+    def step(self, idx, mirror=None):
+        """One SGD step on the window positions idx; returns (total loss incl. L2, policy loss, value loss).  mirror:
+        uint8 [B] on the device, the rows to train on as their mirror image (planes and targets alike), or None."""
         tc = self.config.trainer
-        logits, v = self.model.model(self.window.planes(idx), logits=True)
-        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights)
+        logits, v = self.model.model(self.window.planes(idx, mirror=mirror), logits=True)
+        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror)
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         self.opt.step()
         return loss, pm, vm
 
-    def evaluate(self, idx_all):
-        """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]."""
+    def evaluate(self, idx_all, mirror=False):
+        """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the
+        mirror images of all rows."""
         import torch
         tc = self.config.trainer
         net = self.model.model
@@ -250,8 +280,9 @@ class OptimizeWorker:
         with torch.no_grad():
             for b in range(0, idx_all.shape[0], tc.batch_size):
                 idx = idx_all[b:b + tc.batch_size]
-                logits, v = net(self.window.planes(idx), logits=True)
-                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights)
+                flags = torch.ones(idx.shape[0], dtype=torch.uint8, device=idx.device) if mirror else None
+                logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
+                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags)
                 sums += torch.stack([pm, vm]).double() * len(idx)
             p, v = (sums / idx_all.shape[0]).tolist()
             l2 = float(self.l2_term())

@@ -7,6 +7,12 @@
 //   k_policy_value_loss  one wavefront per minibatch row: softmax, Keras 2.0.8's clipped categorical cross-entropy against the
 //                        played move's one-hot or the record's visit counts, squared value error, and their gradients
 //
+// Mirror augmentation (run.py opt --augment mirror): both per-step kernels take an optional per-row flag array.  A flagged
+// row is the left-right mirror image of its position (file x <-> 8 - x, a symmetry of the rules): its board is mirrored in
+// LDS before the one encoder runs, and its target labels go through the label mirror M before they are scattered into the
+// row's dense target.  The flag is the same for the 64 lanes of a row's wavefront, so the branch is wave-uniform; a NULL
+// array is the unflagged kernel.
+//
 // The contract (shapes, order, error reporting, bit-identity) is stated in include/czero.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -54,6 +60,33 @@ XQ_D void zero_planes(float* __restrict__ out)   // 14 planes: 315 float4
     for (int q = lane_id(); q < 315; q += 64) reinterpret_cast<float4*>(out)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+XQ_D int mirror_sq(int s)       // (x, y) -> (8 - x, y)
+{
+    const int y = s / 9;
+    return s + 8 - 2 * (s - y * 9);
+}
+
+// The board of the mirrored position, in place: every lane reads its one or two source squares, then writes.
+XQ_D void mirror_board(int8_t* b)
+{
+    const int lane = lane_id();
+    const int8_t p0 = b[mirror_sq(lane)];
+    const int8_t p1 = lane < 26 ? b[mirror_sq(lane + 64)] : (int8_t)0;
+    wave_sync();
+    b[lane] = p0;
+    if (lane < 26) b[lane + 64] = p1;
+    wave_sync();
+}
+
+// M(label): from what the device already holds (lab_ft -> mirror both squares -> label_of) instead of a third table; the
+// label set is closed under the mirror (cz_label_mirror, tests/test_mirror_cpu.py), and a row has a few dozen labels at
+// most, so the two dependent table reads are not worth 4 KB more constant data.  label < NLABELS.
+XQ_D int mirror_label(int label)
+{
+    const int ft = label_ft(label);
+    return label_of(mirror_sq(ft >> 8), mirror_sq(ft & 0xFF));
+}
+
 constexpr int LOSS_COLS = (NLABELS + 63) / 64;       // 33 logits per lane
 constexpr float CCE_EPS = 1e-7f;                     // Keras 2.0.8 epsilon(); the upper clip is float(1 - 1e-7)
 constexpr float CCE_HI = (float)(1.0 - 1e-7);
@@ -98,12 +131,14 @@ __global__ __launch_bounds__(64) void k_replay_games(const int8_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__ boards, const int32_t* __restrict__ prev,
-                                                     int n_pos, const int32_t* __restrict__ idx, int n_rows, int depth,
+                                                     int n_pos, const int32_t* __restrict__ idx,
+                                                     const uint8_t* __restrict__ mirror, int n_rows, int depth,
                                                      float* __restrict__ planes)
 {
     __shared__ int8_t bd[BOARD_LDS];
     for (int r = blockIdx.x; r < n_rows; r += gridDim.x) {
         const int i = idx[r];
+        const bool mir = mirror != nullptr && mirror[r] != 0;   // wave-uniform: one row, one wavefront
         float* out = planes + (size_t)r * depth * 90;
         if (i < 0 || i >= n_pos) {                       // out-of-range index: zero planes, nothing read
             zero_planes(out);
@@ -111,12 +146,14 @@ __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__
             continue;
         }
         load_board(boards + (size_t)i * NSQ, bd);
+        if (mir) mirror_board(bd);
         wave_encode<0>(bd, out);
         if (depth == 28) {
             const int p = prev[i];
             if (p >= 0 && p < n_pos) {
                 wave_sync();
                 load_board(boards + (size_t)p * NSQ, bd);
+                if (mir) mirror_board(bd);
                 wave_encode<0>(bd, out + 1260);
             } else {
                 zero_planes(out + 1260);
@@ -127,8 +164,8 @@ __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__
 }
 
 __global__ __launch_bounds__(64) void k_policy_value_loss(
-    const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx, int n_rows,
-    int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
+    const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx,
+    const uint8_t* __restrict__ mirror, int n_rows, int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
     const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z, int mode,
     float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
     float* __restrict__ grad_logits, float* __restrict__ grad_v)
@@ -139,6 +176,7 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
     const float c = w_p * inv_b;
     for (int r = blockIdx.x; r < n_rows; r += gridDim.x) {
         const int i = idx[r];
+        const bool mir = mirror != nullptr && mirror[r] != 0;   // wave-uniform: one row, one wavefront
         float* g = grad_logits + (size_t)r * NLABELS;
         if (i < 0 || i >= n_pos) {                       // out-of-range index: zero loss and gradient, nothing read
             for (int j = lane; j < NLABELS; j += 64) g[j] = 0.f;
@@ -163,11 +201,13 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
         }
         if (total > 0.0) {
             for (int k = lo + lane; k < hi; k += 64) {
-                const int lab = vis_label[k];
+                int lab = vis_label[k];
+                if (mir && lab < NLABELS) lab = mirror_label(lab);
                 if (lab < NLABELS) tgt[lab] = (float)((double)vis_count[k] / total);   // float64 quotient, rounded once
             }
         } else if (lane == 0) {
-            const int lab = played[i];
+            int lab = played[i];
+            if (mir && lab < NLABELS) lab = mirror_label(lab);
             if (lab < NLABELS) tgt[lab] = 1.f;
         }
         wave_sync();
@@ -241,8 +281,8 @@ int cz_replay_games(const int8_t* init_boards, const uint16_t* labels, const int
     return launch_status("cz_replay_games: launch failed");
 }
 
-int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, int n_rows, int depth,
-                     float* planes, void* stream)
+int cz_gather_planes_m(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, const uint8_t* mirror,
+                       int n_rows, int depth, float* planes, void* stream)
 {
     if (n_rows == 0) return CZ_OK;
     if (n_rows < 0 || n_pos < 0 || (depth != 14 && depth != 28) || !idx || !planes || (n_pos > 0 && !boards) ||
@@ -251,14 +291,20 @@ int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const
         return CZ_ERR_ARG;
     }
     hipLaunchKernelGGL(k_gather_planes, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, boards, prev, n_pos, idx,
-                       n_rows, depth, planes);
+                       mirror, n_rows, depth, planes);
     return launch_status("cz_gather_planes: launch failed");
 }
 
-int cz_policy_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, int n_rows, int n_pos,
-                         const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
-                         const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
-                         float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
+int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, int n_rows, int depth,
+                     float* planes, void* stream)
+{
+    return cz_gather_planes_m(boards, prev, n_pos, idx, nullptr, n_rows, depth, planes, stream);
+}
+
+int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                           float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
 {
     if (n_rows == 0) return CZ_OK;
     if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !v || !idx || !policy_loss ||
@@ -268,9 +314,33 @@ int cz_policy_value_loss(const float* logits, int ld, const float* v, const int3
         return CZ_ERR_ARG;
     }
     hipLaunchKernelGGL(k_policy_value_loss, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
-                       n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, mode, w_p, w_v, policy_loss, value_sqerr,
-                       grad_logits, grad_v);
+                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, mode, w_p, w_v, policy_loss,
+                       value_sqerr, grad_logits, grad_v);
     return launch_status("cz_policy_value_loss: launch failed");
+}
+
+int cz_policy_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, int n_rows, int n_pos,
+                         const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                         const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                         float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
+{
+    return cz_policy_value_loss_m(logits, ld, v, idx, nullptr, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z,
+                                  mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v, stream);
+}
+
+// HOST table of the label mirror M, from the same two tables the device path reads.
+int cz_label_mirror(uint16_t* out)
+{
+    if (!out) {
+        czi_set_error("cz_label_mirror: bad argument");
+        return CZ_ERR_ARG;
+    }
+    for (int l = 0; l < NLABELS; ++l) {
+        const int ft = h_tab.lab_ft[l];
+        const int f = ft >> 8, t = ft & 0xFF;
+        out[l] = h_tab.label_of[(f + 8 - 2 * (f % 9)) * NSQ + (t + 8 - 2 * (t % 9))];
+    }
+    return CZ_OK;
 }
 
 }  // extern "C"

@@ -59,6 +59,10 @@ int cz_device_count(void);
 /* HOST buffers. label_of[90*90] (from*90+to -> label, 0xFFFF none), lab_ft[2086] (from<<8|to).
  * Replaces create_action_labels / ActionLabelsRed, environment/lookup_tables.py:62-134. */
 int cz_label_tables(uint16_t* label_of, uint16_t* lab_ft);
+/* HOST buffer. out[2086]: the label of the left-right mirrored move, "x0y0x1y1" -> "(8-x0)y0(8-x1)y1".  The label set is
+ * closed under it; the map is an involution with 90 fixed points (the moves inside the centre file).  The table the
+ * flagged rows of cz_gather_planes_m / cz_policy_value_loss_m follow. */
+int cz_label_mirror(uint16_t* out);
 
 /* ---- batched rules: one wavefront per board ------------------------------------------- */
 
@@ -528,6 +532,13 @@ int cz_replay_games(const int8_t* init_boards, const uint16_t* labels, const int
  * (state_history_to_planes).  An index outside [0, n_pos) gives zero planes.  prev may be NULL for depth 14. */
 int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, int n_rows, int depth,
                      float* planes, void* stream);
+/* The same kernel with a per-row mirror flag (run.py opt --augment mirror).  mirror[n_rows] (DEVICE, uint8) or NULL = no
+ * row flagged = cz_gather_planes, bit for bit.  A row with a nonzero flag gets the planes of the left-right mirrored
+ * position: planes_m[r][p][y][x] == planes[r][p][y][8 - x] for all 14 or 28 planes, exactly (the board is mirrored in LDS
+ * and encoded by the same wave_encode; at depth 28 the position two plies back is mirrored too, a missing one stays
+ * zero).  An index outside [0, n_pos) gives zero planes whatever its flag. */
+int cz_gather_planes_m(const int8_t* boards, const int32_t* prev, int n_pos, const int32_t* idx, const uint8_t* mirror,
+                       int n_rows, int depth, float* planes, void* stream);
 
 /* Policy / value loss of a minibatch and its gradients, one wavefront per row, no atomics: per-row outputs, so a sum
  * over them on the host side is deterministic.
@@ -549,6 +560,15 @@ int cz_policy_value_loss(const float* logits, int ld, const float* v, const int3
                          const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
                          const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
                          float* value_sqerr, float* grad_logits, float* grad_v, void* stream);
+/* The same kernel with the per-row mirror flag of cz_gather_planes_m (mirror[n_rows] DEVICE uint8, or NULL = no row flagged =
+ * cz_policy_value_loss, bit for bit).  A flagged row's policy target is the unflagged row's with every label sent through
+ * cz_label_mirror's map: the played label in mode 0 and in the no-visits fallback, every vis_label entry in mode 1; the
+ * counts, their float64 total and the quotients are untouched, and so are the value target, the clip, the softmax and the
+ * gradient formulas.  So a flagged row gives the bits of an unflagged row of a window holding the mirrored game's record. */
+int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                           float* value_sqerr, float* grad_logits, float* grad_v, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Trainer throughput (run.py opt, worker/optimize.py) on one device.
 
-    python tools/train_rate.py [--games 200] [--steps 20] [--warmup 5] [--batch 512]
+    python tools/train_rate.py [--games 200] [--steps 20] [--warmup 5] [--batch 512] [--mirror] [--repeats 1]
 
 Reports, as one JSON line:
   - the window fill rate in positions/s: ReplayWindow.add_games (cz_replay_games, sparse visit targets) and
@@ -10,6 +10,9 @@ Reports, as one JSON line:
   - one training step (batch 512) on the 7x256 `normal` model and on the benchmark's 7x128 model, split into gather
     (cz_gather_planes), forward + backward (torch fp32 autograd), loss (cz_policy_value_loss) and optimiser (SGD with
     momentum), timed with device events after warm-up (median over the timed steps, milliseconds).
+  - with --mirror: the same steps once more with random per-row mirror flags (run.py opt --augment mirror:
+    cz_gather_planes_m / cz_policy_value_loss_m), as `step_ms_<model>_mirror` beside the unflagged figures of the same
+    call; --repeats N alternates the two variants N times (`..._repeats`: every repeat's medians).
 """
 import argparse
 import json
@@ -65,7 +68,7 @@ def fill_rates(games, repeats=3):
     return {"positions": n, **{f"{k}_positions_per_s": round(n / v) for k, v in out.items()}}
 
 
-def step_times(window, filters, blocks, batch, warmup, steps, targets="visits"):
+def step_times(window, filters, blocks, batch, warmup, steps, targets="visits", mirror=False):
     import torch
     from cchess_alphazero.agent.model import CChessNet
     from cchess_alphazero.worker.optimize import l2_parameters
@@ -78,12 +81,13 @@ def step_times(window, filters, blocks, batch, warmup, steps, targets="visits"):
     for s in range(warmup + steps):
         idx = torch.from_numpy(rng.integers(0, len(window), size=batch).astype(np.int32)).cuda()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        flags = torch.from_numpy(rng.integers(0, 2, size=batch, dtype=np.uint8)).cuda() if mirror else None
         ev[0].record()
-        x = window.planes(idx)
+        x = window.planes(idx, mirror=flags) if mirror else window.planes(idx)
         ev[1].record()
         logits, v = net(x, logits=True)
         ev[2].record()
-        total, _, _ = window.loss(logits, v, idx, targets)
+        total, _, _ = window.loss(logits, v, idx, targets, mirror=flags) if mirror else window.loss(logits, v, idx, targets)
         ev[3].record()
         opt.zero_grad(set_to_none=True)
         (total + 1e-4 * sum((w * w).sum() for w in l2)).backward()
@@ -110,6 +114,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--mirror", action="store_true", help="also time the steps with random per-row mirror flags")
+    ap.add_argument("--repeats", type=int, default=1, help="repeats of each variant (alternating with --mirror)")
     args = ap.parse_args()
     import torch
     from cchess_alphazero import _native
@@ -123,7 +129,15 @@ def main():
     res["window_bytes_per_position"] = round((win.n * (90 + 4 + 2 + 4 + 4) + win.nnz * 6) / win.n, 1)
     res["visited_edges_per_position"] = round(win.nnz / win.n, 1)
     for name, (f, b) in (("normal_7x256", (256, 7)), ("bench_7x128", (128, 7))):
-        res[f"step_ms_{name}"] = step_times(win, f, b, args.batch, args.warmup, args.steps)
+        runs = {False: [], True: []}
+        for _ in range(max(1, args.repeats)):
+            for m in ((False, True) if args.mirror else (False,)):
+                runs[m].append(step_times(win, f, b, args.batch, args.warmup, args.steps, mirror=m))
+        res[f"step_ms_{name}"] = runs[False][0]
+        if args.mirror:
+            res[f"step_ms_{name}_mirror"] = runs[True][0]
+        if args.repeats > 1:
+            res[f"step_ms_{name}_repeats"] = {"plain": runs[False], **({"mirror": runs[True]} if args.mirror else {})}
     res["batch"] = args.batch
     print(json.dumps(res))
 
