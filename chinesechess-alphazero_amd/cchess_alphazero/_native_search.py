@@ -17,6 +17,8 @@ MAX_NO_ACT = 32          # csrc/xq_search.h: banned root moves per game and ply
 VISIT_STRIDE = 784       # include/czero.h cz_visit_entry: 16-byte header, uint16 label[128], int32 n[128]
 VISIT_BANNED = 0x8000    # label bit: the edge is banned at that ply (no_act)
 GAME_VISITS_LOST = 4     # finished-game record flag: the game has no complete visit record
+GAME_BOOK_SHIFT = 8      # finished-game record flags, bits 8-31: book index + 1 of the start position, 0 = INIT_STATE
+BOOK_MAX = (1 << 24) - 2  # include/czero.h CZ_BOOK_MAX
 
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
 # was banned at that ply; the root's own count; the ply; whether the player resigned there.
@@ -68,6 +70,9 @@ def declare(L):
     L.cz_search_drain_records.argtypes = [vp, C.POINTER(C.c_uint), vp, i32, C.POINTER(C.c_int), vp]
     L.cz_search_record_visits.argtypes = [vp, i32, i32, vp]
     L.cz_search_drain_visits.argtypes = [vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
+    if hasattr(L, "cz_search_set_book"):                # (absent from an older library selected with CZ_LIB for an A/B)
+        L.cz_search_set_book.argtypes = [vp, vp, i32, C.c_double, vp]
+        L.cz_search_set_book.restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -236,6 +241,22 @@ class Search:
         self._visits = {}
         self._raw_visits = []
         self._visits_dropped = 0
+
+    def set_book(self, boards=None, rate=1.0):
+        """Self-play start-position book (cz_search_set_book): boards int8 [n, 90] in the mover's frame (numpy or a tensor;
+        lib/book.py book_boards), copied into the search object; None / empty clears it.  Game `game_id` starts from
+        boards[game_id % n] iff philox_uniform(seed, game_id, 0, 2) < rate, else from INIT_STATE.  Call it before
+        start_selfplay() and before a graph capture."""
+        n = 0 if boards is None else len(boards)
+        ptr = None
+        if n:
+            if hasattr(boards, "detach"):
+                boards = boards.detach().cpu().numpy()
+            boards = np.ascontiguousarray(boards, dtype=np.int8)
+            assert boards.shape == (n, 90), boards.shape
+            ptr = boards.ctypes.data_as(C.c_void_p)
+        _native.check(self.L.cz_search_set_book(self.h, ptr, n, float(rate), self._stream()), "cz_search_set_book")
+        self.book_size = n
 
     def pull_visits(self, defer=False):
         """Move the entries waiting in the device ring to the host (kept until their game's record is drained).
@@ -463,7 +484,8 @@ class Search:
         return out
 
     def drain_records(self, max_records=4096, with_visits=False):
-        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, moves[labels]).
+        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, book_index, moves[labels]);
+        book_index: which position of set_book() the game started from, None = INIT_STATE (the kernel's own decision).
         with_visits (record_visits on): each dict also has `visits`, the game's VisitEntry list in ply order -- one per
         searched ply, the resignation ply included, the appended king capture not -- or None when the game's record is
         incomplete (an entry was dropped, or the game began before recording was switched on)."""
@@ -481,7 +503,9 @@ class Search:
             turns = int(hdr[1])
             mv = buf[i, 16:16 + 2 * min(turns, self.max_plies + 2)].view(np.uint16)
             out.append(dict(game_id=int(buf[i, :4].view(np.uint32)[0]), turns=turns, value=int(hdr[2]),
-                            store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv.copy()))
+                            store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv.copy(),
+                            book_index=((int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT) - 1
+                            if (int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT else None))
             if self.visit_capacity:
                 ents = sorted(self._visits.pop(out[-1]["game_id"], []), key=lambda e: e[0])
                 if with_visits:

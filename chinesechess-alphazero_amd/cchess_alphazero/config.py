@@ -93,6 +93,8 @@ class EngineConfig(_Section):
                                                   # first block's fused input layer takes instead of scanning the planes
                          record_visits=False,     # play records carry each searched move's root visit counts:
                                                   # items [move, value, pi] (run.py self --record-visits)
+                         book_path=None,          # start-position book (run.py self / eval --book FILE, lib/book.py): games
+                         book_rate=1.0,           # start from its positions with this probability, else from INIT_STATE
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -41,12 +41,15 @@ def bytes_per_expansion(mean_depth, mean_edges, mean_leaf_moves):
 class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
-                 use_history=False, trunk=None, record_visits=None):
+                 use_history=False, trunk=None, record_visits=None, book=None, book_rate=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
         filter count allows) or "library" (MIOpen), see agent/model.py InferenceNet.  record_visits: every searched
-        ply's root visit counts go into the records (drain: items [move, value, pi]); None = config.engine.record_visits."""
+        ply's root visit counts go into the records (drain: items [move, value, pi]); None = config.engine.record_visits.
+        book: start positions (state strings in the mover's frame, lib/book.py load_book; None = the file
+        config.engine.book_path, if set): game `game_id` starts from book[game_id % n] with probability book_rate (None =
+        config.engine.book_rate), otherwise from INIT_STATE.  The side that moves first plays "red" in every count."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -92,6 +95,16 @@ class SelfPlayEngine:
         self._since_pull = 0
         if self.record_visits:
             self.search.record_visits(True, capacity=8 * VISIT_DRAIN_ROUNDS * self.search.G)
+        ec = getattr(config, "engine", None)
+        book_path = os.environ.get("CZ_BOOK") or getattr(ec, "book_path", None)     # (CZ_BOOK: a book for bench.py / the tools)
+        if book is None and book_path:
+            from cchess_alphazero.lib.book import load_book
+            book = load_book(book_path)
+        self.book = list(book) if book else []
+        self.book_rate = float(getattr(ec, "book_rate", 1.0) if book_rate is None else book_rate)
+        if self.book:                                          # handed over before start() and before a graph capture
+            from cchess_alphazero.lib.book import book_boards
+            self.search.set_book(book_boards(self.book), self.book_rate)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -276,14 +289,17 @@ class SelfPlayEngine:
 
     def drain(self, max_records=4096):
         """Finished games since the last call, as the reference's play-record lists
-        ([init_state, [move, value], ...], self_play.py:202-208) plus metadata.  With record_visits a searched move's
+        ([init_state, [move, value], ...], self_play.py:202-208) plus metadata.  Element 0 is the game's real first state:
+        INIT_STATE, or the book position (mover's frame) the kernel started it from -- `book_index`, None for INIT_STATE;
+        the values alternate from the first mover's view ("red").  With record_visits a searched move's
         item is [move, value, pi] (lib/data_helper.py pi_from_visits); the appended king capture, and every move of a game
         whose visit record is incomplete (`visits` None), keep the two-element form."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
             vis = r.get("visits")
-            data = [INIT_STATE]
+            bi = r["book_index"]
+            data = [INIT_STATE if bi is None else self.book[bi]]
             for i, m in enumerate(r["moves"]):
                 item = [ActionLabelsRed[int(m)], v if i % 2 == 0 else -v]
                 if vis is not None and i < len(vis) and not vis[i].resign:
@@ -291,7 +307,7 @@ class SelfPlayEngine:
                     item.append(pi_from_visits(e.moves, e.n, e.banned, ActionLabelsRed))
                 data.append(item)
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
-                            resigned=r["resigned"], data=data))
+                            resigned=r["resigned"], book_index=bi, data=data))
             if self.record_visits:
                 out[-1]["visits"] = vis
         return out

@@ -37,6 +37,10 @@ _FLAGS = [
     ("--max-games", dict(type=int, help="engine: stop after this many finished games (default: never)")),
     ("--record-visits", dict(action="store_true",
                              help="(self) play records carry each searched move's root visit counts: [move, value, pi]")),
+    ("--book", dict(metavar="FILE", help="(self, eval) start-position book: one state string or FEN per line; self-play game "
+                                         "i starts from position i mod n, the arena plays each position once per colour")),
+    ("--book-rate", dict(type=float, default=1.0, metavar="P",
+                         help="(self) a game starts from the book with probability P, otherwise from the opening position")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -73,6 +77,9 @@ def build_config(args):
     engine.max_rounds, engine.max_games = args.max_rounds, args.max_games
     if args.record_visits:
         engine.record_visits = True
+    if not 0.0 <= args.book_rate <= 1.0:
+        raise SystemExit(f"--book-rate {args.book_rate}: expected 0 <= P <= 1")
+    engine.book_path, engine.book_rate = args.book, args.book_rate
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -33,32 +33,46 @@ def load_model(config, config_path, weight_path, seed=None):
     return model
 
 
+def _tally(t, idx, value):
+    """Adds game idx (value from red's view) to the list t = [total_score, rw, rd, rf, bw, bd, bf] (reference :105-135)."""
+    even = idx % 2 == 0
+    if (value == 1 and even) or (value == -1 and not even):        # best model won
+        t[6 if even else 3] += 1
+    elif (value == 1 and not even) or (value == -1 and even):      # next generation won
+        t[4 if even else 1] += 1
+    else:
+        t[5 if even else 2] += 1
+    score = 0 if value == -1 else (1 if value == 1 else 0.5)
+    t[0] += (1 - score) if even else score
+
+
 def score_table(results):
     """results: list of (value from red's view, turns) indexed by game idx.  Returns the reference's tuple
     (total_score, red_new_win, red_new_draw, red_new_fail, black_new_win, black_new_draw, black_new_fail)
     where even idx = best model plays red (reference :105-135)."""
-    total = 0.0
-    rw = rd = rf = bw = bd = bf = 0
+    t = [0.0, 0, 0, 0, 0, 0, 0]
     for idx, (value, _) in enumerate(results):
-        even = idx % 2 == 0
-        if (value == 1 and even) or (value == -1 and not even):        # best model won
-            if even:
-                bf += 1
-            else:
-                rf += 1
-        elif (value == 1 and not even) or (value == -1 and even):      # next generation won
-            if even:
-                bw += 1
-            else:
-                rw += 1
-        else:
-            if even:
-                bd += 1
-            else:
-                rd += 1
-        score = 0 if value == -1 else (1 if value == 1 else 0.5)
-        total += (1 - score) if even else score
-    return (total, rw, rd, rf, bw, bd, bf)
+        _tally(t, idx, value)
+    return tuple(t)
+
+
+def book_states(book, indices):
+    """Arena games from a book: game idx starts from book[(idx // 2) % n] -- colours alternate by idx % 2, so each
+    position is played once with each colour before the next one comes up."""
+    return [book[(int(i) // 2) % len(book)] for i in indices]
+
+
+def position_table(results, n_positions):
+    """The score table per book position: one dict(games, score, table) per position, `table` being score_table's tuple
+    over the games of that position (game idx belongs to position (idx // 2) % n_positions; "red" = the side that moves
+    first from it).  The entries add up to score_table(results), field by field."""
+    rows = [[0.0, 0, 0, 0, 0, 0, 0] for _ in range(n_positions)]
+    games = [0] * n_positions
+    for idx, (value, _) in enumerate(results):
+        p = (idx // 2) % n_positions
+        _tally(rows[p], idx, value)
+        games[p] += 1
+    return [dict(games=games[p], score=rows[p][0], table=tuple(rows[p])) for p in range(n_positions)]
 
 
 class EvaluateWorker:
@@ -93,9 +107,12 @@ class EvaluateWorker:
         # input convolution's grid over all 6400 queue rows of a model.  Off unless asked for.
         self.compact = False
 
-    def start(self):
+    def start(self, book=None):
+        """book: start positions (state strings in the mover's frame); game idx starts from book[(idx // 2) % n].
+        self.position_scores then holds the per-position table (position_table)."""
         n = self.config.eval.game_num * max(1, self.config.play.max_processes)
-        results = self.play_games(n)
+        results = self.play_games(n, init_state=book_states(book, range(n)) if book else None)
+        self.position_scores = position_table(results, len(book)) if book else None
         return score_table(results)
 
     def _capture_round(self, s, k, stream):
@@ -126,7 +143,8 @@ class EvaluateWorker:
         the moves are picked on the device and the game rules are applied to all boards with the batched rule
         kernels.  Per-game bookkeeping is vectorised; the only per-game Python work is the (rare) repeated position.
         u_fn(idx, ply) -> uniform draw of np.random.choice (default: NumPy's global RNG, like the reference);
-        init_state: start position (default INIT_STATE); trace: dict filled with idx -> [one dict per searched ply];
+        init_state: start position in the mover's frame (default INIT_STATE), one for all games or a list with one per
+        game (book_states); the side that moves first is "red" in every result; trace: dict filled with idx -> [one dict per searched ply];
         stats: dict that receives the search counters (rounds, expansions, ...); on_ply(ply, counters_fn): called at
         the start of every ply (bench.py times plies with it); sims_per_round: K (default config.play.search_threads);
         stop_after_plies: stop after that many plies (benchmark legs only: the games still running are reported as they stand)."""
@@ -144,7 +162,11 @@ class EvaluateWorker:
         dev = searches[0].device
         K = searches[0].K
         max_plies = 2 * int(pc.max_game_length) + 2
-        boards = torch.from_numpy(np.tile(state_to_array(init_state or INIT_STATE), (G, 1))).to(dev)
+        if init_state is None or isinstance(init_state, str):
+            init_state = [init_state or INIT_STATE] * G
+        if len(init_state) != G:
+            raise ValueError(f"init_state: {len(init_state)} start positions for {G} games")
+        boards = torch.from_numpy(np.stack([state_to_array(s) for s in init_state])).to(dev)
         hist = torch.zeros((max_plies + 1, G, 90), dtype=torch.int8, device=dev)      # position searched at each ply
         acts = torch.zeros((max_plies + 1, G), dtype=torch.int32, device=dev)         # move played at each ply
         turns = 0
@@ -342,12 +364,22 @@ def start(config):
     model_ng = load_model(config, rc.next_generation_config_path, rc.next_generation_weight_path, seed=1)
     pipes = (model_bt.get_pipes(need_reload=False), model_ng.get_pipes(need_reload=False))
     worker = EvaluateWorker(config, pipes[0], pipes[1], pid=0)
-    total, rw, rd, rf, bw, bd, bf = worker.start()
+    book = None
+    if getattr(config.engine, "book_path", None):
+        from cchess_alphazero.lib.book import load_book
+        book = load_book(config.engine.book_path)
+        logger.info(f"start-position book {config.engine.book_path}: {len(book)} positions, each played once per colour")
+    total, rw, rd, rf, bw, bd, bf = worker.start(book=book)
     game_num = config.eval.game_num * max(1, config.play.max_processes)
     logger.info(f"Evaluate over, next generation win {total}/{game_num} = {total * 100 / game_num:.2f}%")
     logger.info("red\tblack\twin\tdraw\tloss")
     logger.info(f"new\told\t{rw}\t{rd}\t{rf}")
     logger.info(f"old\tnew\t{bw}\t{bd}\t{bf}")
+    if book:                                                # (red = the side that moves first from the book position)
+        logger.info("position\tgames\tscore\tnew red w/d/l\tnew black w/d/l")
+        for p, row in enumerate(worker.position_scores):
+            t = row["table"]
+            logger.info(f"{p}\t{row['games']}\t{row['score']}\t{t[1]}/{t[2]}/{t[3]}\t{t[4]}/{t[5]}/{t[6]}")
     model_bt.close_pipes()
     model_ng.close_pipes()
     return total, (rw, rd, rf, bw, bd, bf)

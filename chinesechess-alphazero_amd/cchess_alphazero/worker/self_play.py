@@ -83,6 +83,11 @@ class SelfPlayWorker:
                                      seed=ec.base_seed, max_nodes_per_game=ec.max_nodes_per_game,
                                      pool_chunks=ec.pool_chunks, max_depth=ec.max_depth,
                                      sims_per_round=ec.sims_per_round)
+        # (a start-position book, config.engine.book_path / book_rate, is loaded and handed to the search by the engine;
+        #  game i starts from position i mod n, so the id stride below spreads the book evenly over the ranks)
+        if self.engine.book:
+            logger.info(f"Process {self.pid}-{self.rank}: start-position book {ec.book_path}: {len(self.engine.book)} "
+                        f"positions, rate {self.engine.book_rate}")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:
@@ -91,7 +96,8 @@ class SelfPlayWorker:
     def _harvest(self):
         for g in self.engine.drain():
             logger.debug(f"Process {self.pid}-{self.rank} game {g['game_id']} turn={g['turns'] / 2}, "
-                         f"winner = {g['value']:.2f} (1 = red, -1 = black, 0 draw)")
+                         f"winner = {g['value']:.2f} (1 = red, -1 = black, 0 draw; red = the first mover)"
+                         + (f" book position {g['book_index']}" if g.get("book_index") is not None else ""))
             if g["store"]:
                 path = self.writer.add_game(g["data"])
                 self.stored_games += 1

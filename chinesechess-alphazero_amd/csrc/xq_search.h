@@ -91,6 +91,10 @@ struct SearchParams {
     int record_stride;      // bytes per finished-game record
     int policy_logits;      // the network rows hold raw LOGITS (cz_search_policy_logits): priors = exp(l - max over the
                             // node's moves), then the usual renormalisation over them
+    // start-position book of self-play (cz_search_set_book); read by new_game / emit_record only
+    int book_n;             // positions in the book, 0 = none: every game starts from INIT_STATE
+    double book_rate;       // a game starts from the book iff philox_uniform(seed, game_id, 0, 2) < book_rate
+    const int8_t* book;     // [book_n][90] boards in the mover's frame, owned by the search object
 };
 
 struct SearchBuffers {
@@ -149,9 +153,12 @@ struct GameRecord {
     uint32_t game_id;
     int32_t turns;
     int32_t value;      // from red's view: +1 red won, -1 black won, 0 draw (self_play.py:190-191)
-    uint32_t flags;     // bit 0 store, bit 1 resigned, bit 2 (visit recording on only) an entry of the game was dropped
+    uint32_t flags;     // bit 0 store, bit 1 resigned, bit 2 (visit recording on only) an entry of the game was dropped;
+                        // bits 8-31: book index + 1 of the game's start position, 0 = INIT_STATE (cz_search_set_book)
 };
 constexpr uint32_t GAME_VISITS_LOST = 4u;
+constexpr int GAME_BOOK_SHIFT = 8;
+constexpr int BOOK_MAX = (1 << 24) - 2;    // positions a book may hold: what the 24-bit index + 1 field can name
 
 // ---- root visit record of self-play (cz_search_record_visits) ----
 // One entry per searched ply, written by k_advance right after the move is chosen: the root's edges in edge order

@@ -1158,13 +1158,32 @@ XQ_D void set_init_board(int8_t* gb)
     }
 }
 
-// (re)start a self-play game in slot g (SelfPlayWorker.start_game, self_play.py:95-116)
+// Start position of game `game_id` (cz_search_set_book): the index into the book, or -1 for INIT_STATE.  A pure function
+// of (seed, game_id, book): new_game and emit_record both ask it, no per-game state is kept.  Stream 0 draws 0 and 1 are the
+// resign and store lotteries; rates 0 and 1 decide without a draw.
+XQ_D int book_index(const SearchParams& P, uint32_t game_id)
+{
+    if (P.book_n <= 0 || !(P.book_rate > 0.0)) return -1;
+    if (P.book_rate < 1.0 && !(philox_uniform(P.seed, game_id, 0, 2) < P.book_rate)) return -1;
+    return (int)(game_id % (uint32_t)P.book_n);
+}
+
+XQ_D void set_book_board(int8_t* gb, const int8_t* src)
+{
+    const int lane = lane_id();
+    for (int s = lane; s < BOARD_LDS; s += 64) gb[s] = s < NSQ ? src[s] : (int8_t)0;
+}
+
+// (re)start a self-play game in slot g (SelfPlayWorker.start_game, self_play.py:95-116; with a book the position its
+// INIT_STATE stands for: turns, no_eat_count, history and "red = the first mover" as from the opening position)
 XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, uint32_t game_id)
 {
     const int lane = lane_id();
     const int g = gv.g;
     clear_tree(P, B, gv, L.chtab);
-    set_init_board(B.g_board + (size_t)g * BOARD_LDS);
+    const int bi = book_index(P, game_id);
+    if (bi < 0) set_init_board(B.g_board + (size_t)g * BOARD_LDS);
+    else set_book_board(B.g_board + (size_t)g * BOARD_LDS, P.book + (size_t)bi * NSQ);
     wave_sync_global();
     const int8_t* gb = B.g_board + (size_t)g * BOARD_LDS;
     L.r.bd[1][lane] = gb[lane];
@@ -1200,7 +1219,8 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
         hdr->game_id = B.g_game_id[g];
         hdr->turns = turns;
         hdr->value = value;
-        hdr->flags = (store ? 1u : 0u) | (resigned ? 2u : 0u) | extra_flags;
+        hdr->flags = (store ? 1u : 0u) | (resigned ? 2u : 0u) | extra_flags
+                     | ((uint32_t)(book_index(P, B.g_game_id[g]) + 1) << GAME_BOOK_SHIFT);
     }
     uint16_t* mv = reinterpret_cast<uint16_t*>(rec + sizeof(GameRecord));
     const uint16_t* acts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
@@ -1881,6 +1901,7 @@ struct cz_search {
     int keep_chunks_created = 0;      // P.keep_chunks as sized at creation (cz_search_set_sims never goes below it)
     VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
     void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
+    void* book_mem = nullptr;         // the start-position book (cz_search_set_book): P.book points here
 };
 
 namespace {
@@ -2095,6 +2116,7 @@ int cz_search_destroy(cz_search* s)
 {
     if (!s) return CZ_OK;
     (void)hipFree(s->vis_mem);
+    (void)hipFree(s->book_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
     delete s;
@@ -2298,6 +2320,34 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
     s->V.dropped = (unsigned long long*)(base + ring_b + 16);   // (cz_search_drain_visits reads ctl and dropped in one copy)
     s->V.g_lost = (uint8_t*)(base + ring_b + ctl_b);
     s->V.cap = (unsigned int)cap;
+    return CZ_OK;
+}
+
+static_assert(BOOK_MAX + 1 < (1 << 24), "the book index + 1 has to fit bits 8-31 of cz_game_record.flags");
+static_assert(CZ_BOOK_MAX == BOOK_MAX, "czero.h: book capacity");
+
+int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_book: null handle");
+    if (n < 0 || n > BOOK_MAX) return serr(CZ_ERR_ARG, "cz_search_set_book: n outside 0 .. CZ_BOOK_MAX");
+    if (n > 0 && !boards) return serr(CZ_ERR_ARG, "cz_search_set_book: null boards");
+    if (!(rate >= 0.0 && rate <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_book: rate outside [0, 1]");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still read the old book
+    if (e != hipSuccess) return serr_hip("cz_search_set_book", e);
+    void* mem = nullptr;
+    if (n > 0) {                                         // the new book is complete before the old one goes
+        e = hipMalloc(&mem, (size_t)n * NSQ);
+        if (e != hipSuccess) return serr_hip("cz_search_set_book: hipMalloc", e);
+        e = hipMemcpyAsync(mem, boards, (size_t)n * NSQ, hipMemcpyDefault, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { (void)hipFree(mem); return serr_hip("cz_search_set_book", e); }
+    }
+    (void)hipFree(s->book_mem);
+    s->book_mem = mem;
+    s->P.book = (const int8_t*)mem;
+    s->P.book_n = n;
+    s->P.book_rate = n > 0 ? rate : 0.0;
     return CZ_OK;
 }
 

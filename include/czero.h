@@ -131,10 +131,15 @@ typedef struct cz_search_cfg {
 typedef struct cz_game_record {
     uint32_t game_id;
     int32_t turns;                   /* number of moves recorded */
-    int32_t value;                   /* +1 red won, -1 black won, 0 draw (self_play.py:190-191) */
+    int32_t value;                   /* +1 red won, -1 black won, 0 draw (self_play.py:190-191); "red" = the side that
+                                        made the game's first move, also when the game started from a book position */
     uint32_t flags;                  /* bit 0: store (self_play.py:194-200), bit 1: ended by resignation,
-                                        bit 2: (visit recording on) the game has no complete visit record */
+                                        bit 2: (visit recording on) the game has no complete visit record,
+                                        bits 8-31: the game's start position: book index + 1, 0 = INIT_STATE
+                                        (cz_search_set_book; written by the kernel, the host never redraws the lottery) */
 } cz_game_record;
+#define CZ_GAME_BOOK_SHIFT 8
+#define CZ_BOOK_MAX ((1 << 24) - 2)  /* positions a book may hold: every index + 1 fits bits 8-31 of flags */
 
 int cz_search_create(const cz_search_cfg* cfg, cz_search** out);   /* allocates device memory on the current device */
 int cz_search_destroy(cz_search* s);
@@ -152,6 +157,20 @@ int cz_search_memory_info(cz_search* s, int64_t* host_out, void* stream);
 /* self-play mode: every slot plays games from INIT_STATE forever; slot g starts with game id
  * first_game_id + g and continues with + game_id_stride after each finished game (0 = n_games). */
 int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id, uint32_t game_id_stride, void* stream);
+
+/* Start-position book of self-play.  boards [n][90] int8 in the MOVER's frame (+t the side to move, at rows 0-4, as in
+ * cz_search_set_roots; a position with black to move is handed over flipped, static_env.fliped_state), host or device
+ * memory; they are copied into memory the search object owns (n * 90 bytes), n <= CZ_BOOK_MAX.  n = 0 clears the book.
+ * Game `game_id` starts from boards[game_id % n] iff philox_uniform(seed, game_id, stream 0, draw 2) < rate, otherwise
+ * from INIT_STATE (draws 0 and 1 of stream 0 stay the resign and store lotteries; rate 0 and rate 1 draw nothing).  A
+ * book game is SelfPlayWorker.start_game with INIT_STATE replaced: turns = 0, no_eat_count = 0, an empty history, and
+ * the first mover plays the part of "red" -- tau decay, min_resign_turn, the < 10 plies store lottery, max_game_length,
+ * the sign of `value` and the red_wins / black_wins counters all count from the book position.  The caller vouches for
+ * the positions (one king each, not already over: cchess_alphazero/lib/book.py checks them).  Without a book every
+ * kernel, record and counter is what it was.  Call it before cz_search_start_selfplay and before a graph capture (the
+ * captured launches hold the book's address), like cz_search_record_visits; synchronises the stream.
+ * CZ_ERR_ARG: n < 0, n > CZ_BOOK_MAX, boards NULL with n > 0, rate outside [0, 1] -- the object keeps its book. */
+int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, void* stream);
 
 /* external mode (CChessPlayer.action): set the position to search for each game.  boards [G][90];
  * turns [G] or NULL; no_act [G][32] + n_no_act [G] or NULL (at most 32 banned moves per game); increase_temp / enable_resign [G] or NULL;
