@@ -19,10 +19,13 @@ VISIT_BANNED = 0x8000    # label bit: the edge is banned at that ply (no_act)
 GAME_VISITS_LOST = 4     # finished-game record flag: the game has no complete visit record
 GAME_BOOK_SHIFT = 8      # finished-game record flags, bits 8-31: book index + 1 of the start position, 0 = INIT_STATE
 BOOK_MAX = (1 << 24) - 2  # include/czero.h CZ_BOOK_MAX
+MOVE_FAST = 0x8000       # finished-game record, moves[i] bit 15: ply i was a fast search (cz_search_set_playout_cap)
+VISIT_FAST = 2           # visit entry flag: the ply was a fast search
 
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
-# was banned at that ply; the root's own count; the ply; whether the player resigned there.
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign")
+# was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
+# search of the playout cap (set_playout_cap).
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast")
 
 
 class SearchCfg(C.Structure):
@@ -73,6 +76,9 @@ def declare(L):
     if hasattr(L, "cz_search_set_book"):                # (absent from an older library selected with CZ_LIB for an A/B)
         L.cz_search_set_book.argtypes = [vp, vp, i32, C.c_double, vp]
         L.cz_search_set_book.restype = i32
+    if hasattr(L, "cz_search_set_playout_cap"):
+        L.cz_search_set_playout_cap.argtypes = [vp, i32, C.c_double, vp]
+        L.cz_search_set_playout_cap.restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -258,6 +264,15 @@ class Search:
         _native.check(self.L.cz_search_set_book(self.h, ptr, n, float(rate), self._stream()), "cz_search_set_book")
         self.book_size = n
 
+    def set_playout_cap(self, fast_sims=0, full_rate=0.25):
+        """Self-play playout cap randomization (cz_search_set_playout_cap): ply `turns` of game `game_id` is a FULL search
+        (simulation_num_per_move simulations, root noise) iff philox_uniform(seed, game_id, 2, turns) < full_rate, otherwise
+        a FAST one (fast_sims simulations, no root noise); rates 0 and 1 draw nothing.  fast_sims = 0 switches it off.
+        drain_records() marks the fast plies (`fast`).  Call it before start_selfplay() and before a graph capture."""
+        _native.check(self.L.cz_search_set_playout_cap(self.h, int(fast_sims), float(full_rate), self._stream()),
+                      "cz_search_set_playout_cap")
+        self.fast_sims, self.full_rate = int(fast_sims), float(full_rate)
+
     def pull_visits(self, defer=False):
         """Move the entries waiting in the device ring to the host (kept until their game's record is drained).
         Returns the number of entries moved; synchronises the stream.  defer=True only copies them: the host-side sorting
@@ -300,7 +315,7 @@ class Search:
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
-                          ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1))
+                          ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -484,8 +499,10 @@ class Search:
         return out
 
     def drain_records(self, max_records=4096, with_visits=False):
-        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, book_index, moves[labels]);
-        book_index: which position of set_book() the game started from, None = INIT_STATE (the kernel's own decision).
+        """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, book_index, moves[labels],
+        fast); book_index: which position of set_book() the game started from, None = INIT_STATE (the kernel's own decision);
+        fast: one bool per move, True where the ply was a fast search of the playout cap (set_playout_cap; bit 15 of the
+        record's move, masked out of `moves`), False for the appended king capture.
         with_visits (record_visits on): each dict also has `visits`, the game's VisitEntry list in ply order -- one per
         searched ply, the resignation ply included, the appended king capture not -- or None when the game's record is
         incomplete (an entry was dropped, or the game began before recording was switched on)."""
@@ -503,7 +520,8 @@ class Search:
             turns = int(hdr[1])
             mv = buf[i, 16:16 + 2 * min(turns, self.max_plies + 2)].view(np.uint16)
             out.append(dict(game_id=int(buf[i, :4].view(np.uint32)[0]), turns=turns, value=int(hdr[2]),
-                            store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv.copy(),
+                            store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv & (MOVE_FAST - 1),
+                            fast=((mv & MOVE_FAST) != 0).tolist(),
                             book_index=((int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT) - 1
                             if (int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT else None))
             if self.visit_capacity:

@@ -95,6 +95,9 @@ class EngineConfig(_Section):
                                                   # items [move, value, pi] (run.py self --record-visits)
                          book_path=None,          # start-position book (run.py self / eval --book FILE, lib/book.py): games
                          book_rate=1.0,           # start from its positions with this probability, else from INIT_STATE
+                         fast_sims=0,             # playout cap randomization (run.py self --fast-sims N --full-rate P): a ply
+                         full_rate=0.25,          # is a full search with probability full_rate, else fast_sims simulations
+                                                  # without root noise, and its row is not trained on; 0 = off
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -41,7 +41,8 @@ def bytes_per_expansion(mean_depth, mean_edges, mean_leaf_moves):
 class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
-                 use_history=False, trunk=None, record_visits=None, book=None, book_rate=None):
+                 use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
+                 full_rate=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -49,7 +50,10 @@ class SelfPlayEngine:
         ply's root visit counts go into the records (drain: items [move, value, pi]); None = config.engine.record_visits.
         book: start positions (state strings in the mover's frame, lib/book.py load_book; None = the file
         config.engine.book_path, if set): game `game_id` starts from book[game_id % n] with probability book_rate (None =
-        config.engine.book_rate), otherwise from INIT_STATE.  The side that moves first plays "red" in every count."""
+        config.engine.book_rate), otherwise from INIT_STATE.  The side that moves first plays "red" in every count.
+        fast_sims, full_rate: playout cap randomization (None = config.engine.fast_sims / full_rate; fast_sims 0 = off): a
+        ply is a full search with probability full_rate, otherwise a fast one of fast_sims simulations without root noise,
+        whose record item carries the training weight 0 (drain)."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -105,6 +109,10 @@ class SelfPlayEngine:
         if self.book:                                          # handed over before start() and before a graph capture
             from cchess_alphazero.lib.book import book_boards
             self.search.set_book(book_boards(self.book), self.book_rate)
+        self.fast_sims = int(getattr(ec, "fast_sims", 0) if fast_sims is None else fast_sims)
+        self.full_rate = float(getattr(ec, "full_rate", 0.25) if full_rate is None else full_rate)
+        if self.fast_sims:                                     # likewise before start() and before a graph capture
+            self.search.set_playout_cap(self.fast_sims, self.full_rate)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -293,7 +301,10 @@ class SelfPlayEngine:
         INIT_STATE, or the book position (mover's frame) the kernel started it from -- `book_index`, None for INIT_STATE;
         the values alternate from the first mover's view ("red").  With record_visits a searched move's
         item is [move, value, pi] (lib/data_helper.py pi_from_visits); the appended king capture, and every move of a game
-        whose visit record is incomplete (`visits` None), keep the two-element form."""
+        whose visit record is incomplete (`visits` None), keep the two-element form.  With a playout cap (fast_sims) the
+        item of a FAST ply is [move, value, pi or None, 0]: element 2 is pi where a full ply would carry it, else None;
+        element 3 is the row's training weight (lib/replay_window.py keeps the position, the trainer skips the row).  A
+        full ply's item is unchanged.  `fast_plies` counts the game's fast plies."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
@@ -305,9 +316,11 @@ class SelfPlayEngine:
                 if vis is not None and i < len(vis) and not vis[i].resign:
                     e = vis[i]
                     item.append(pi_from_visits(e.moves, e.n, e.banned, ActionLabelsRed))
+                if r["fast"][i]:
+                    item += [None] * (3 - len(item)) + [0]
                 data.append(item)
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
-                            resigned=r["resigned"], book_index=bi, data=data))
+                            resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]), data=data))
             if self.record_visits:
                 out[-1]["visits"] = vis
         return out

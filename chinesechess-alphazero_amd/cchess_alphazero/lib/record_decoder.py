@@ -28,8 +28,10 @@ def split_games(data):
 
 def expand_records(games, dtype=_native.F32, targets="played"):
     """games: list of ``[init_state, [move, value], ...]`` (items may be ``[move, value, pi]``, written with
-    engine.record_visits).  Returns device tensors (planes [N,14,10,9], policy, value [N] float32) and the per-game
-    offsets, positions ordered game by game, ply by ply (the order ``expanding_data`` produces).
+    engine.record_visits, or ``[move, value, pi or None, weight]``, written with a playout cap: like the reference's
+    expanding_data this keeps every position and ignores the weight).  Returns device tensors (planes [N,14,10,9],
+    policy, value [N] float32) and the per-game offsets, positions ordered game by game, ply by ply (the order
+    ``expanding_data`` produces).
     targets="played": policy = the played move's label index [N] int64 (the reference trainer's one-hot).
     targets="visits": policy = dense float32 [N, 2086] search policies: count / sum(counts) over pi for items that
     carry one, the one-hot of the played move for items that do not."""
@@ -76,7 +78,7 @@ def _visit_targets(items, played):
     rows, cols, w = [], [], []
     has_pi = np.zeros(n, dtype=bool)
     for r, item in enumerate(items):
-        if len(item) < 3:
+        if len(item) < 3 or item[2] is None:         # (a fast ply without visit recording: [move, value, None, 0])
             continue
         total = sum(c for _, c in item[2])
         if total <= 0:

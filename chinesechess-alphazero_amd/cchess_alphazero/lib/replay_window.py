@@ -45,6 +45,7 @@ class ReplayWindow:
         self.nnz = 0                    # visit entries
         self.n_games = 0
         self.files = []                 # the files loaded, in load order
+        self._trainable = np.zeros(0, dtype=np.uint8)   # host, grown with the device arrays (_reserve)
         self._alloc(0, 0)
 
     def _alloc(self, n, nnz):
@@ -67,6 +68,9 @@ class ReplayWindow:
                 new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
                 new[:self.n] = old[:self.n]
                 setattr(self, name, new)
+            tr = np.empty(cap, dtype=np.uint8)
+            tr[:self.n] = self._trainable[:self.n]
+            self._trainable = tr
             rp = torch.zeros((cap + 1,), dtype=torch.int32, device=self.device)
             rp[:self.n + 1] = self.row_ptr[:self.n + 1]
             self.row_ptr = rp
@@ -85,6 +89,12 @@ class ReplayWindow:
     def __len__(self):
         return self.n
 
+    @property
+    def trainable(self):
+        """uint8 per position: 0 = a weight-0 row (a fast ply of the playout cap), kept for the history planes and the
+        prev links, never drawn by the trainer."""
+        return self._trainable[:self.n]
+
     def load_file(self, path):
         """Append the games of one record file.  Returns the number of positions added."""
         from cchess_alphazero.lib.data_helper import read_game_data_from_file
@@ -96,10 +106,13 @@ class ReplayWindow:
         return n
 
     def add_games(self, games, source=None):
-        """games: ``[init_state, [move, value(, pi)], ...]`` lists.  Raises ValueError (naming the game and the ply) for a
-        move that is not a label or whose from-square is empty, and for items that are not ``[move, value(, pi)]``; the
-        window is unchanged then.  The window holds at most INT32_MAX positions and INT32_MAX visit entries (int32 indices:
-        about 24 visited edges per position at `distribute`'s 90 M positions); a load beyond either raises ValueError."""
+        """games: ``[init_state, [move, value(, pi)], ...]`` lists; an item may also be ``[move, value, pi or None, weight]``
+        with weight 0 or 1 (engine.py drain: 0 = a fast ply of the playout cap): the position is kept like every other --
+        history planes and ``prev`` links run through it -- and ``trainable`` is 0 for it.  Raises ValueError (naming the
+        game and the ply) for a move that is not a label or whose from-square is empty, for a weight other than 0 or 1,
+        and for items that are not of these forms; the window is unchanged then.  The window holds at most INT32_MAX
+        positions and INT32_MAX visit entries (int32 indices: about 24 visited edges per position at `distribute`'s 90 M
+        positions); a load beyond either raises ValueError."""
         where = f" in {source}" if source else ""
         for gi, g in enumerate(games):
             if not isinstance(g[0], str) or g[0].split(" ")[0].count("/") != 9:
@@ -112,6 +125,7 @@ class ReplayWindow:
         labels = np.empty(P, dtype=np.uint16)
         vals = np.empty(P, dtype=np.float32)
         nvis = np.zeros(P, dtype=np.int64)
+        train = np.ones(P, dtype=np.uint8)
         vl, vc = [], []
         k = 0
         lookup = _LABEL
@@ -125,7 +139,12 @@ class ReplayWindow:
                         raise ValueError(f"Invalid move {item[0]!r} (game {gi}, ply {t}){where}")
                     labels[k] = lab
                     vals[k] = float(item[1])
-                    if len(item) >= 3:
+                    if len(item) >= 4:
+                        w = item[3]
+                        if isinstance(w, bool) or not isinstance(w, (int, float)) or w not in (0, 1):
+                            raise ValueError(f"Training weight {w!r}: expected 0 or 1 (game {gi}, ply {t}){where}")
+                        train[k] = int(w)
+                    if len(item) >= 3 and not (len(item) >= 4 and item[2] is None):
                         pi = item[2]
                         for mv, c in pi:
                             lb = lookup.get(mv)
@@ -165,9 +184,14 @@ class ReplayWindow:
         if nnz:
             self.vis_label[z0:z0 + nnz] = torch.from_numpy(np.asarray(vl, dtype=np.uint16)).to(dev)
             self.vis_count[z0:z0 + nnz] = torch.from_numpy(np.asarray(vc, dtype=np.int32)).to(dev)
+        self._trainable[n0:n0 + P] = train
         self.n, self.nnz = n0 + P, z0 + nnz
         self.n_games += len(games)
         return P
+
+    def training_rows(self):
+        """The window positions a trainer may draw, ascending (int64): all but the weight-0 rows."""
+        return np.flatnonzero(self.trainable)
 
     def planes(self, idx, mirror=None):
         """float32 planes [B, depth, 10, 9] of the window positions idx (int32 [B] on the device).  mirror: uint8 [B] on the

@@ -41,6 +41,11 @@ _FLAGS = [
                                          "i starts from position i mod n, the arena plays each position once per colour")),
     ("--book-rate", dict(type=float, default=1.0, metavar="P",
                          help="(self) a game starts from the book with probability P, otherwise from the opening position")),
+    ("--fast-sims", dict(type=int, default=0, metavar="N",
+                         help="(self) playout cap randomization: a ply is a full search with probability --full-rate, otherwise "
+                              "a fast one of N simulations without root noise whose row is not trained on (0 = off)")),
+    ("--full-rate", dict(type=float, default=0.25, metavar="P",
+                         help="(self, with --fast-sims) probability that a ply is a full search")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -80,6 +85,12 @@ def build_config(args):
     if not 0.0 <= args.book_rate <= 1.0:
         raise SystemExit(f"--book-rate {args.book_rate}: expected 0 <= P <= 1")
     engine.book_path, engine.book_rate = args.book, args.book_rate
+    if not 0 <= args.fast_sims <= config.play.simulation_num_per_move:
+        raise SystemExit(f"--fast-sims {args.fast_sims}: expected 0 <= N <= simulation_num_per_move "
+                         f"({config.play.simulation_num_per_move})")
+    if not 0.0 <= args.full_rate <= 1.0:
+        raise SystemExit(f"--full-rate {args.full_rate}: expected 0 <= P <= 1")
+    engine.fast_sims, engine.full_rate = args.fast_sims, args.full_rate
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -186,7 +186,11 @@ class OptimizeWorker:
             self.rng.shuffle(order)
             self.fill_window(order)
             self.update_learning_rate(total_steps)
-            if len(self.window) > tc.batch_size:
+            # (positions, like the reference's len(dataset[0]) -- those a step may draw: weight-0 rows do not count.
+            #  This loop asks a window for nothing but its length, its files and load_file -- tests/test_trainer_cpu.py
+            #  drives it with such a stand-in -- so a window that has no weights counts every position)
+            rows = getattr(self.window, "training_rows", None)
+            if (len(rows()) if rows is not None else len(self.window)) > tc.batch_size:
                 total_steps += self.train_epoch(tc.epoch_to_checkpoint)
                 self.save_current_model(send=False)
                 self.update_learning_rate(total_steps)
@@ -212,12 +216,21 @@ class OptimizeWorker:
 
     def train_epoch(self, epochs):
         """epochs passes over the window's first 98 % in a fresh order each, the last 2 % validating; returns the
-        reference's step count (:106-134)."""
+        reference's step count (:106-134).  Weight-0 rows (fast plies of a playout cap, lib/replay_window.py `trainable`)
+        are dropped from both sides AFTER the split, which is taken over all positions; the step count is that of the
+        rows left.  A window without such rows gives the indices, draws and steps it always gave."""
         import torch
         tc = self.config.trainer
         win, net = self.window, self.model.model
         n = len(win)
         tr, va = validation_split(n)
+        skipped = n - len(win.training_rows())
+        if skipped:
+            keep = win.trainable[:n] != 0
+            tr, va = tr[keep[tr]], va[keep[va]]
+            logger.info(f"window: {skipped} of {n} positions carry the training weight 0 (fast plies) and are skipped: "
+                        f"{len(tr)} training and {len(va)} validation rows")
+        self.skipped_rows = skipped
         dev = win.device
         va_d = torch.from_numpy(va.astype(np.int32)).to(dev)
         bs = tc.batch_size
@@ -245,7 +258,7 @@ class OptimizeWorker:
                             f"validation rows mirrored: val_loss {vm_loss[0]:.4f} val_policy {vm_loss[1]:.4f} "
                             f"val_value {vm_loss[2]:.4f}")
             self.history.append(entry)
-        return steps_of_pass(n, bs, epochs)
+        return steps_of_pass(n - skipped, bs, epochs)
 
     def mirror_flags(self, n):
         """uint8 [n]: one fair coin per training row of an epoch from the flags' own generator; None without

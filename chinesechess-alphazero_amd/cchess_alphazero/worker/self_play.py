@@ -88,13 +88,21 @@ class SelfPlayWorker:
         if self.engine.book:
             logger.info(f"Process {self.pid}-{self.rank}: start-position book {ec.book_path}: {len(self.engine.book)} "
                         f"positions, rate {self.engine.book_rate}")
+        # (the playout cap, config.engine.fast_sims / full_rate, is likewise set by the engine)
+        if self.engine.fast_sims:
+            logger.info(f"Process {self.pid}-{self.rank}: playout cap: a ply is a full search "
+                        f"({self.config.play.simulation_num_per_move} simulations) with probability {self.engine.full_rate}, "
+                        f"otherwise {self.engine.fast_sims} simulations without root noise")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:
             self.engine.capture_graph()
 
     def _harvest(self):
+        full = fast = 0
         for g in self.engine.drain():
+            fast += g.get("fast_plies", 0)
+            full += len(g["data"]) - 1 - g.get("fast_plies", 0)
             logger.debug(f"Process {self.pid}-{self.rank} game {g['game_id']} turn={g['turns'] / 2}, "
                          f"winner = {g['value']:.2f} (1 = red, -1 = black, 0 draw; red = the first mover)"
                          + (f" book position {g['book_index']}" if g.get("book_index") is not None else ""))
@@ -103,6 +111,8 @@ class SelfPlayWorker:
                 self.stored_games += 1
                 if path:
                     logger.info(f"Process {self.pid} save play data to {path}")
+        if self.engine.fast_sims and full + fast:
+            logger.info(f"Process {self.pid}-{self.rank}: drained {full} full plies (training rows) and {fast} fast plies")
 
     def reload_best_model(self):
         """The reference's self-play picks up a new best model while it runs: its prediction thread re-checks the

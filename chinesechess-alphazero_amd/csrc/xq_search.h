@@ -95,6 +95,9 @@ struct SearchParams {
     int book_n;             // positions in the book, 0 = none: every game starts from INIT_STATE
     double book_rate;       // a game starts from the book iff philox_uniform(seed, game_id, 0, 2) < book_rate
     const int8_t* book;     // [book_n][90] boards in the mover's frame, owned by the search object
+    // playout cap randomization of self-play (cz_search_set_playout_cap); read through ply_is_fast only
+    int fast_sims;          // simulations of a fast ply, 0 = off: every ply is a full search of `sims`
+    double full_rate;       // ply `turns` is a full search iff philox_uniform(seed, game_id, 2, turns) < full_rate
 };
 
 struct SearchBuffers {
@@ -159,6 +162,8 @@ struct GameRecord {
 constexpr uint32_t GAME_VISITS_LOST = 4u;
 constexpr int GAME_BOOK_SHIFT = 8;
 constexpr int BOOK_MAX = (1 << 24) - 2;    // positions a book may hold: what the 24-bit index + 1 field can name
+constexpr uint16_t MOVE_FAST = 0x8000;     // record moves[i], bit 15: ply i was a fast search (cz_search_set_playout_cap);
+                                           // labels are below 2086.  Never set on the appended king capture
 
 // ---- root visit record of self-play (cz_search_record_visits) ----
 // One entry per searched ply, written by k_advance right after the move is chosen: the root's edges in edge order
@@ -168,6 +173,7 @@ constexpr int BOOK_MAX = (1 << 24) - 2;    // positions a book may hold: what th
 constexpr int VISIT_MAX_EDGES = 128;               // = MAXMOVES
 constexpr uint16_t VISIT_BANNED = 0x8000;          // label bit: the edge is in the ply's no_act list
 constexpr uint32_t VISIT_RESIGN = 1u;              // entry flag: the player resigned at this ply
+constexpr uint32_t VISIT_FAST = 2u;                // entry flag: the ply was a fast search (cz_search_set_playout_cap)
 struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
     uint32_t game_id;
     uint16_t ply;       // turns when the move was chosen

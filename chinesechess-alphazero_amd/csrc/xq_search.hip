@@ -450,7 +450,7 @@ XQ_D Picked select_edge(const SearchParams& P, char* base, const EdgeStat* sb, i
                 if (rc.n_no_act) {
                     for (int k = 0; k < rc.n_no_act; ++k) valid = valid && (rc.no_act[k] != mv);
                 }
-                const float a = P.one_minus_eps_f32 * p;
+                const float a = (rc.noise ? P.one_minus_eps_f32 : 1.0f) * p;   // (no rows: eps = 0, also on a fast ply of the playout cap)
                 double p_ = (double)a;
                 if (rc.noise) p_ = p_ + P.noise_eps * rc.noise[(size_t)rc.sim * MAXMOVES + j];   // player.py:304
                 u = P.c_puct * p_ * xx / (double)(1 + n);
@@ -967,8 +967,20 @@ XQ_D bool reserve_ply(const SearchParams& P, const SearchBuffers& B, const GameV
     return ok;
 }
 
+// Playout cap randomization (cz_search_set_playout_cap): is ply `turns` of self-play game `game_id` a FAST search?  A pure
+// function of (seed, game_id, turns), like book_index: begin_search, k_noise, k_sim, emit_visits and emit_record all ask
+// it, no per-game state is kept.  Stream 2 of the game's generator (stream 0: the per-game lotteries, stream 1: the move
+// choice); rates 0 and 1 decide without a draw.  External mode never has fast plies.
+XQ_D bool ply_is_fast(const SearchParams& P, uint32_t game_id, int turns)
+{
+    if (P.fast_sims <= 0 || P.mode != MODE_SELFPLAY || P.full_rate >= 1.0) return false;
+    if (!(P.full_rate > 0.0)) return true;
+    return !(philox_uniform(P.seed, game_id, 2, (uint64_t)turns) < P.full_rate);
+}
+
 // Start the search of the position in g_board (CChessPlayer.action, player.py:145-164): find the
-// root in the tree, apply the reuse rule, reserve the ply's memory.
+// root in the tree, apply the reuse rule, reserve the ply's memory.  In self-play the ply's budget is fast_sims on a
+// fast ply of the playout cap (a reused root that already has more visits searches nothing: tasks = 0).
 XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L)
 {
     const int lane = lane_id();
@@ -982,8 +994,9 @@ XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const Game
     int root = hash_lookup(gv, P, L.key, h, &slot);
     int done_n = root >= 0 ? uni(*reinterpret_cast<const int32_t*>(rec_ptr(gv, (uint32_t)root) + NODE_OFF_HDR)) : 0;   // :153-155
     const int n_no_act = uni((int)B.g_n_no_act[g]), inc = uni((int)B.g_increase_temp[g]);
-    if (n_no_act > 0 || inc || done_n == P.sims) done_n = 0;                      // :156-158
-    int tasks = P.sims - done_n;
+    const int sims = ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g])) ? P.fast_sims : P.sims;
+    if (n_no_act > 0 || inc || done_n == sims) done_n = 0;                        // :156-158
+    int tasks = sims - done_n;
     if (tasks < 0) tasks = 0;
     // Memory policy: the reference keeps a game's tree for the whole game (self_play.py:84,98-100) and so does the
     // engine as long as the pool has chunks.  Only when the coming ply cannot be reserved is the game's tree dropped
@@ -992,7 +1005,7 @@ XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const Game
         clear_tree(P, B, gv, L.chtab);
         count(gv, CT_TREE_RESETS);
         root = -1;
-        tasks = P.sims;
+        tasks = sims;
         done_n = 0;
         (void)reserve_ply(P, B, gv, L.chtab, tasks);     // within keep_chunks by construction; else overflow_sims counts
     }
@@ -1205,7 +1218,9 @@ XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView
     begin_search(P, B, gv, L);
 }
 
-XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameView& gv, int turns, int value,
+// searched: the first `searched` moves came from searches (the rest is the appended king capture): those of fast plies
+// carry MOVE_FAST in the record; g_hist_act itself stays clean, the repetition scan reads it.
+XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameView& gv, int turns, int searched, int value,
                       bool store, bool resigned, uint32_t extra_flags)
 {
     const int lane = lane_id();
@@ -1225,6 +1240,12 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
     uint16_t* mv = reinterpret_cast<uint16_t*>(rec + sizeof(GameRecord));
     const uint16_t* acts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
     for (int i = lane; i < turns && i < P.max_plies + 2; i += 64) mv[i] = acts[i];
+    if (P.fast_sims > 0) {                    // playout cap: one wave-uniform lottery per searched ply (cold: once a game)
+        wave_sync_global();
+        const uint32_t game_id = uniu(B.g_game_id[g]);
+        for (int i = 0; i < searched && i < P.max_plies + 2; ++i)
+            if (ply_is_fast(P, game_id, i) && lane == 0) mv[i] = (uint16_t)(acts[i] | MOVE_FAST);
+    }
     count(gv, CT_GAMES);
     count(gv, value > 0 ? CT_RED_WINS : (value < 0 ? CT_BLACK_WINS : CT_DRAWS));
     if (resigned) count(gv, CT_RESIGNS);
@@ -1232,7 +1253,7 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
 
 // Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
-XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns, bool resigned)
+XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns, bool resigned, bool fast)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -1273,7 +1294,7 @@ XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRin
         h->game_id = B.g_game_id[g];
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
-        h->flags = (uint8_t)(resigned ? VISIT_RESIGN : 0u);
+        h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u));
         h->sum_n = hdr.sum_n;
         h->reserved = 0u;
     }
@@ -1292,7 +1313,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     uint16_t* hacts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
     const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
     const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
-    if (V.ring) emit_visits(B, gv, V, turns, action < 0);
+    if (V.ring) emit_visits(B, gv, V, turns, action < 0, ply_is_fast(P, game_id, turns));
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;
     int value = 0;
@@ -1375,6 +1396,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
         begin_search(P, B, gv, L);
         return;
     }
+    const int searched = turns;
     if (final_move != NOMOVE) {                                         // :177-184
         if (lane == 0 && turns < P.max_plies + 2) hacts[turns] = (uint16_t)final_move;
         turns += 1;
@@ -1390,7 +1412,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
         if (lane == 0) { lost = V.g_lost[g]; V.g_lost[g] = 0; }
         extra = uni(lost) ? GAME_VISITS_LOST : 0u;
     }
-    emit_record(P, B, gv, turns, value, store, resigned, extra);
+    emit_record(P, B, gv, turns, searched, value, store, resigned, extra);
     new_game(P, B, gv, L, game_id + P.game_id_stride);
 }
 
@@ -1422,8 +1444,10 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
     const RoundIO io{planes, P.planes_dtype, P.in_planes, B.leaf_masks, B.leaf_planes_off != 0};
     int active = uni(B.g_active[g]);
     Arena ar{uniu(B.g_heap_top[g]), uni(B.g_nchunks[g]), uni(B.g_node_count[g])};
+    // (no root noise on a fast ply of the playout cap: k_noise drew no rows for it)
+    const bool noisy = P.noise_eps != 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
     const RootCtx rc{false, uni((int)B.g_n_no_act[g]), B.g_no_act + (size_t)g * MAX_NO_ACT,
-                     P.noise_eps != 0.0 ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0};
+                     noisy ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0};
     int resume_i = P.K;
     // the slot table as it is when the launch starts, slot i on lane i: one load per array instead of one dependent
     // round trip per slot and field (a simulation only ever changes its own slot, and each slot is visited once per list)
@@ -1613,6 +1637,7 @@ __global__ __launch_bounds__(256) void k_noise(SearchParams P, SearchBuffers B)
     __shared__ int s_nm;
     const int g = blockIdx.x;
     if (g >= P.G || B.g_phase[g] != PH_SEARCH) return;
+    if (ply_is_fast(P, B.g_game_id[g], B.g_turns[g])) return;   // playout cap: no root noise on a fast ply, the epoch stays
     // a new batch starts only when nothing is in flight (k_sim(BACKUP) may just have finished the old one)
     if (B.g_active[g] != 0) return;
     const int tasks = B.g_tasks_left[g];
@@ -2250,6 +2275,8 @@ int cz_search_round_q(cz_search* s, const float* policy, const float* value, voi
 int cz_search_set_sims(cz_search* s, int simulation_num_per_move)
 {
     if (!s || simulation_num_per_move < 1) return serr(CZ_ERR_ARG, "cz_search_set_sims: bad argument");
+    if (simulation_num_per_move < s->P.fast_sims)
+        return serr(CZ_ERR_ARG, "cz_search_set_sims: below the playout cap's fast_sims (cz_search_set_playout_cap)");
     // (a search longer than the chunks a game can own ends in counted overflow_sims, it is not refused here)
     s->P.sims = simulation_num_per_move;
     // a game that has to drop its tree keeps enough chunks for one full search of the NEW length (never fewer than it
@@ -2348,6 +2375,22 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
     s->P.book = (const int8_t*)mem;
     s->P.book_n = n;
     s->P.book_rate = n > 0 ? rate : 0.0;
+    return CZ_OK;
+}
+
+static_assert(CZ_MOVE_FAST == MOVE_FAST && CZ_VISIT_FAST == VISIT_FAST, "czero.h: playout cap flags");
+
+int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: null handle");
+    if (fast_sims < 0 || fast_sims > s->P.sims)
+        return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: fast_sims outside 0 .. simulation_num_per_move");
+    if (fast_sims > 0 && !(full_rate >= 0.0 && full_rate <= 1.0))
+        return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: full_rate outside [0, 1]");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the schedule they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_playout_cap", e);
+    s->P.fast_sims = fast_sims;
+    s->P.full_rate = fast_sims > 0 ? full_rate : 0.0;
     return CZ_OK;
 }
 

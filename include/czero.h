@@ -140,6 +140,9 @@ typedef struct cz_game_record {
 } cz_game_record;
 #define CZ_GAME_BOOK_SHIFT 8
 #define CZ_BOOK_MAX ((1 << 24) - 2)  /* positions a book may hold: every index + 1 fits bits 8-31 of flags */
+#define CZ_MOVE_FAST 0x8000          /* the record's uint16 moves[i], bit 15: ply i was a FAST search of the playout cap
+                                        (cz_search_set_playout_cap); labels are below 2086.  Searched plies only: never
+                                        set on the appended king capture.  Mask it out before reading the label */
 
 int cz_search_create(const cz_search_cfg* cfg, cz_search** out);   /* allocates device memory on the current device */
 int cz_search_destroy(cz_search* s);
@@ -171,6 +174,25 @@ int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id
  * captured launches hold the book's address), like cz_search_record_visits; synchronises the stream.
  * CZ_ERR_ARG: n < 0, n > CZ_BOOK_MAX, boards NULL with n > 0, rate outside [0, 1] -- the object keeps its book. */
 int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, void* stream);
+
+/* Playout cap randomization of self-play (KataGo: Wu 2019, section 3.1; the reference has no such option).  With
+ * fast_sims > 0 every ply of every self-play game is either a FULL search -- simulation_num_per_move simulations, root
+ * noise as configured: what every ply is without this call -- or a FAST one: fast_sims simulations and NO root noise
+ * (no Dirichlet rows are drawn for the game at that ply, its noise epoch does not advance).  Ply `turns` of game
+ * `game_id` is full iff philox_uniform(seed, game_id, stream 2, draw turns) < full_rate (stream 0 holds the per-game
+ * lotteries, stream 1 the move choice); full_rate >= 1 makes every ply full and full_rate <= 0 every ply fast, both
+ * without a draw.  The ply's budget S replaces simulation_num_per_move in the reuse rule of CChessPlayer.action
+ * (player.py:153-158): done = the reused root's visit count, reset to 0 by bans, increase_temp or done == S; the ply
+ * runs max(0, S - done) simulations, so a fast ply whose reused root already has more than fast_sims visits searches
+ * nothing and moves at once.  Move choice (temperature, resignation, bans), the game rules and the store lottery are
+ * unchanged.  The finished-game record marks fast plies with CZ_MOVE_FAST in moves[i], a visit entry with
+ * CZ_VISIT_FAST; fast plies still write their visit entry.  Chunk reservation stays sized by the full budget; no
+ * counter is added.  fast_sims = 0 (the state after cz_search_create) switches it off: every kernel then produces the
+ * bits it produced before.  Self-play only: external mode (cz_search_set_roots) never looks at it.  Call it before
+ * cz_search_start_selfplay and before a graph capture (the captured launches hold the parameters), like
+ * cz_search_set_book; synchronises the stream.  CZ_ERR_ARG: fast_sims < 0 or > simulation_num_per_move, full_rate
+ * outside [0, 1] with fast_sims > 0 -- the object keeps its setting; cz_search_set_sims below fast_sims is refused. */
+int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, void* stream);
 
 /* external mode (CChessPlayer.action): set the position to search for each game.  boards [G][90];
  * turns [G] or NULL; no_act [G][32] + n_no_act [G] or NULL (at most 32 banned moves per game); increase_temp / enable_resign [G] or NULL;
@@ -269,10 +291,12 @@ typedef struct cz_visit_entry {
     uint32_t game_id;
     uint16_t ply;                    /* turns when the move was chosen */
     uint8_t n_edges;
-    uint8_t flags;                   /* bit 0: the player resigned at this ply */
+    uint8_t flags;                   /* bit 0: the player resigned at this ply; bit 1 (CZ_VISIT_FAST): the ply was a
+                                        fast search of the playout cap (cz_search_set_playout_cap) */
     int32_t sum_n;                   /* the root's own visit count */
     uint32_t reserved;
 } cz_visit_entry;
+#define CZ_VISIT_FAST 2u
 /* Copies every entry written since the last call into HOST host_buf (784 bytes each) and frees their ring space;
  * *n_out = entries copied.  host_buf = NULL: *n_out = entries waiting, nothing is consumed.  CZ_ERR_ARG when more are
  * waiting than max_entries (nothing is consumed).  dropped_out (HOST, or NULL) = entries dropped since recording was
