@@ -2342,6 +2342,57 @@ constexpr int IP4_EXIT_PAIRS = 2, IP4_EXIT_HEADS = 3;
 #ifndef CZ_IP4_K2_EARLY_C6
 #define CZ_IP4_K2_EARLY_C6 2
 #endif
+// The in-place epilogues and the staging in front of the exits run with every wave behind the same barrier and nothing
+// beside them, so their time is their instruction count.  CZ_IP4_EPI (variant builds, as CZ_IP4_PREFETCH): a mask of what
+// is taken out of them, each item with the same values in the same order -- bit-identical; 0 = the earlier instruction forms.
+//    1  relu(acc) is ONE v_max_f32 0, x (ip4::relu1): the compiler puts a canonicalising v_max_f32 x, x in front of
+//       a > 0 ? a : 0, which only alters signalling NaNs, and MFMA / v_pk_add_f32 results hold none;
+//    2  the fp16 halves of a quad are converted two at a time (v_cvt_pk_f16_f32, round to nearest even: ip4::Half4);
+//    4  (128 filters) an epilogue computes a swizzled row base per pixel tile -- the f16 row with the key and the lane's
+//       half chunk folded in, the piece row -- and forms every access with one xor of a compile-time chunk;
+//    8  (with 4) the padding lanes of pixel tile 2 (pixels 90 .. 95) get a dump row behind the head filters as their base
+//       instead of exec masking around every store;
+//   16  (with 4, c6) pixel tile 2 of BOTH channel tiles of a wave is one unit: the trade leaves tile0's 32 channels of pixel
+//       64 + ln in the lower lanes and tile0 + 1's in the upper ones, every lane stores a piece (self-paired, each unit
+//       made every piece twice).  Epilogue 1 reads the skip elements of both tiles before that unit writes;
+// (Requesting the next pair's images ahead of the exit as well costs the c6 chain 36 bytes of scratch: EXPERIMENTS.md.)
+#ifndef CZ_IP4_EPI
+#define CZ_IP4_EPI 31
+#endif
+namespace ip4 {
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+// (The asm is opaque to the compiler's MFMA -> VALU hazard recogniser: `a` must never be a raw MFMA destination.  Here every
+// operand has gone through v_accvgpr_read or v_pk_add_f32 first.)
+template <bool ONE> __device__ __forceinline__ float relu1(float a)
+{
+    if (ONE) {
+        float r;
+        asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(a));
+        return r;
+    }
+    return a > 0.0f ? a : 0.0f;
+}
+// four fp32 values -> their fp16 quad (the 8 bytes of a Quad<_Float16>), and the quad's values back
+struct Half4 {
+    f16x2 a, b;
+    template <bool PK> __device__ __forceinline__ void set(const float* r)
+    {
+        if (PK) {
+            a = __builtin_convertvector(f32x2{r[0], r[1]}, f16x2);
+            b = __builtin_convertvector(f32x2{r[2], r[3]}, f16x2);
+        } else {
+            a[0] = (_Float16)r[0]; a[1] = (_Float16)r[1];
+            b[0] = (_Float16)r[2]; b[1] = (_Float16)r[3];
+        }
+    }
+    __device__ __forceinline__ float get(int i) const { return (float)(i < 2 ? a[i] : b[i - 2]); }
+    __device__ __forceinline__ c8k::u32x2 bits() const
+    {
+        return c8k::u32x2{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)};
+    }
+};
+}  // namespace ip4
 #ifdef CZ_IP4_STAMPS
 // timing build (tools/ip4_stamps.py; never the default library): shader-cycle stamps of one wave per board around the phases
 // of every block of workgroup 0's second pair -- [board][block][IP4_STAMP_*]
@@ -2381,7 +2432,16 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
     // the pixel's four items summed as (a0 + a1) + (a2 + a3), + bias, relu -- within the bound tests/test_gpu_tower.py asserts
     // against the one-block HEADS kernels (their sums associate differently).
     constexpr int HW_OFF = BIAS_OFF + 2 * 2 * C * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[HW_OFF + (C == 128 ? 6 * C * 4 : 0)];   // bias[2 buffers][2 convolutions][C] | head filters
+    constexpr int DUMP_OFF = HW_OFF + 6 * C * 4;                // (128 filters) one row for the stores of padding lanes
+    static_assert(C != 128 || DUMP_OFF % RB == 0, "the dump row is swizzled like an image row");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[HW_OFF + (C == 128 ? 6 * C * 4 + RB : 0)];   // bias[2 buffers][2 convolutions][C] | head filters | dump row
+    // what is taken out of the epilogues (the mask above the kernel).  The c6 chain that starts a 192-filter tower keeps the
+    // code before: with items 1 and 2 its scratch grows (276 -> 444 bytes per lane)
+    constexpr int EP = MIX ? 0 : (CZ_IP4_EPI);
+    constexpr bool EADR = C == 128 && (EP & 4) != 0;            // row bases per epilogue
+    constexpr bool EDMP = EADR && (EP & 8) != 0;                // padding lanes store to the dump row
+    constexpr bool EC6U = EADR && XF == 1 && YF == 1 && !MIX;   // the c6 units on row bases
+    constexpr bool EMRG = EC6U && (EP & 16) != 0;               // tile 2 of both channel tiles in one unit
     const int NB = ch.n;
     if (n_dev) {
         const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
@@ -2478,15 +2538,17 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
                 const int chn = tc * 32 + gg * 8 + kb2 * 4;
-                Quad<_Float16> hq;
+                float r[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(a[gg * 4 + i]);
+                ip4::Half4 hq;
+                hq.template set<(EP & 2) != 0>(r);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float r = a[gg * 4 + i] > 0.0f ? a[gg * 4 + i] : 0.0f;
-                    hq.e[i] = (_Float16)r;
-                    a[gg * 4 + i] = r;
-                    (h ? lo_b : lo_a)[gg * 4 + i] = r - (float)hq.e[i];
+                    a[gg * 4 + i] = r[i];
+                    (h ? lo_b : lo_a)[gg * 4 + i] = r[i] - hq.get(i);
                 }
-                if (q < 90) *reinterpret_cast<Quad<_Float16>*>(lds + choff(bd, key, chn >> 3) + (chn & 7) * 2) = hq;
+                if (q < 90) *reinterpret_cast<c8k::u32x2*>(lds + choff(bd, key, chn >> 3) + (chn & 7) * 2) = hq.bits();
             }
         }
         if (pp == 1) lo_b = lo_a;
@@ -2508,6 +2570,110 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             *reinterpret_cast<c8k::u32x2*>(P1 + choff(bd, q, c0 + 1)) = c8k::u32x2{pl[4], pl[5]};
             *reinterpret_cast<u4*>(P1 + choff(bd, q, c1)) = u4{pv[0], pv[1], pv[2], pv[3]};
             *reinterpret_cast<c8k::u32x2*>(P1 + choff(bd, q, c1 + 1)) = c8k::u32x2{pv[4], pv[5]};
+        }
+    };
+    // ---- the epilogues on row bases (EADR; 128 filters: RB = 256, the swizzle covers the row's 16 chunks) ----
+    // An access of pixel q, chunk ck is row(q) * RB + ((ck ^ q) & 15) * 16 + const: with base = row(q) * RB + ((q & 15) ^ ck0) * 16
+    // + const it is base ^ (ck1 << 4) for any split ck = ck0 ^ ck1 -- ck0 takes the wave's first channel tile and the lane's
+    // half, ck1 is known at compile time.  EDMP: a padding lane's base is its own 16-byte slot of the dump row (the xor keeps
+    // it inside the row), so it reads rubbish for pixels nobody stores and writes where nobody reads.
+    struct EpiBases {
+        int h[3];               // pixel tile tt, f16 row: this lane's quad of chunk 4 tile0 (^ 4 c + gg)
+        int p[3];               // pixel tile tt, piece row (part 1): chunk 2 tile0 (^ 2 c + j, ^ 8 for the value piece)
+        int s[3];               // pixel tile tt, fp32 staging row: chunk kb (^ 8 c + 2 gg)
+        int pw01;               // the piece this lane writes after a trade of tiles (0, 1): pixel 32 kb + ln
+        int dump;
+        bool ok2;               // pixel 64 + ln exists
+    };
+    auto epi_bases = [&](EpiBases& e, int ln2, int kb2, bool pieces, bool staging) __attribute__((always_inline)) {
+        e.ok2 = 64 + ln2 < 90;
+        e.dump = DUMP_OFF + ((ln2 - 26) * 2 + kb2) * 16;
+#pragma unroll
+        for (int tt = 0; tt < 3; ++tt) {
+            const int q = tt * 32 + ln2;
+            const int key = tt < 2 || e.ok2 ? q : 89;           // (without the dump row a padding lane reads row 89)
+            const int row = (bd * 90 + key) * RB;
+            const bool dmp = EDMP && tt == 2;
+            if (!staging) e.h[tt] = dmp && !e.ok2 ? e.dump : row + (((key & 15) ^ (4 * tile0)) << 4) + kb2 * 8;
+            if (pieces) e.p[tt] = dmp && !e.ok2 ? e.dump : PSTR + row + (((key & 15) ^ (2 * tile0)) << 4);
+            if (staging) e.s[tt] = dmp && !e.ok2 ? e.dump : (tile0 >> 1) * PSTR + row + (((key & 15) ^ kb2) << 4);
+        }
+        if (pieces) {
+            const int q = kb2 * 32 + ln2;
+            e.pw01 = PSTR + (bd * 90 + q) * RB + (((q & 15) ^ (2 * tile0)) << 4);
+        }
+    };
+    // write_c6_unit on row bases.  pp = 0: pixel tiles (0, 1) of relative channel tile c; pp = 1: tile 2 of c with itself; pp = 2
+    // (EMRG): aa / ab = tile 2 of relative channel tiles 0 / 1 -- the lower lanes leave the trade with tile0's 32 channels
+    // of pixel 64 + ln, the upper lanes with tile0 + 1's, and both store their piece.
+    auto c6_unit = [&](f32x16& aa, f32x16& ab, int pp, int c, int k, const EpiBases& e, int kb2) __attribute__((always_inline)) {
+        using rb8::u32x6;
+        const float s_hi = __builtin_ldexpf(1.0f, k), s_lo = __builtin_ldexpf(1.0f, k - cf8::X_LO_SHIFT);
+        f32x16 lo_a, lo_b;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (h == 1 && pp == 1) break;
+            const int tt = pp == 0 ? h : 2;
+            const int x = pp == 2 ? h : c;
+            f32x16& a = h ? ab : aa;
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) {
+                float r[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(a[gg * 4 + i]);
+                ip4::Half4 hq;
+                hq.template set<(EP & 2) != 0>(r);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a[gg * 4 + i] = r[i];
+                    (h ? lo_b : lo_a)[gg * 4 + i] = r[i] - hq.get(i);
+                }
+                if (EDMP || tt < 2 || e.ok2) *reinterpret_cast<c8k::u32x2*>(lds + (e.h[tt] ^ ((4 * x + gg) << 4))) = hq.bits();
+            }
+        }
+        if (pp == 1) lo_b = lo_a;
+        f32x16 av, bv, al, bl;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const auto sv = __builtin_amdgcn_permlane32_swap(__float_as_uint(aa[r]), __float_as_uint(pp == 1 ? aa[r] : ab[r]), false, false);
+            const auto sl = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo_a[r]), __float_as_uint(lo_b[r]), false, false);
+            av[r] = __uint_as_float(sv[0]); bv[r] = __uint_as_float(sv[1]);
+            al[r] = __uint_as_float(sl[0]); bl[r] = __uint_as_float(sl[1]);
+        }
+        const u32x6 pl = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(al, bl, s_lo);
+        const u32x6 pv = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(av, bv, s_hi);
+        // the piece row of the pixel this lane holds, and the chunk of its channel tile that the base does not carry
+        const bool pok = pp == 0 || (e.ok2 && (pp == 2 || kb2 == 0));
+        int pw = pp == 0 ? e.pw01 : pp == 2 ? e.p[2] ^ (kb2 << 5) : e.p[2];
+        if (EDMP && pp == 1) pw = kb2 == 0 ? pw : e.dump;
+        const int pc = pp == 2 ? 0 : 2 * c;
+        if (EDMP || pok) {
+            *reinterpret_cast<u4*>(lds + (pw ^ (pc << 4))) = u4{pl[0], pl[1], pl[2], pl[3]};
+            *reinterpret_cast<c8k::u32x2*>(lds + (pw ^ ((pc + 1) << 4))) = c8k::u32x2{pl[4], pl[5]};
+            *reinterpret_cast<u4*>(lds + (pw ^ ((8 + pc) << 4))) = u4{pv[0], pv[1], pv[2], pv[3]};
+            *reinterpret_cast<c8k::u32x2*>(lds + (pw ^ ((9 + pc) << 4))) = c8k::u32x2{pv[4], pv[5]};
+        }
+    };
+    // (epilogue 1) b2 + this lane's skip elements of pixel tile tt, relative channel tile c, out of a c6 image
+    auto c6_skip = [&](f32x16& sk, int tt, int c, int k_x, const float* bias2, const EpiBases& e, int kb2) __attribute__((always_inline)) {
+        const u4 hd4 = *reinterpret_cast<const u4*>(lds + (e.p[tt] ^ ((2 * c) << 4)));
+        const c8k::u32x2 tl2 = *reinterpret_cast<const c8k::u32x2*>(lds + (e.p[tt] ^ ((2 * c + 1) << 4)));
+        const uint32_t wv[7] = {hd4.x, hd4.y, hd4.z, hd4.w, tl2.x, tl2.y, 0u};
+        const uint32_t sh6 = (uint32_t)kb2 * 6u;
+        rb8::u32x6 pc;
+#pragma unroll
+        for (int w = 0; w < 6; ++w) pc[w] = __builtin_amdgcn_alignbit(wv[w + 1], wv[w], sh6);
+        const rb8::f32x32 xl = __builtin_amdgcn_cvt_scalef32_pk32_f32_bf6(pc, __builtin_ldexpf(1.0f, k_x - cf8::X_LO_SHIFT));
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+            const int chn = (tile0 + c) * 32 + gg * 8 + kb2 * 4;
+            const float4 bv = *reinterpret_cast<const float4*>(bias2 + chn);
+            float vv[4] = {bv.x, bv.y, bv.z, bv.w};
+            const Quad<_Float16> xq = *reinterpret_cast<const Quad<_Float16>*>(lds + (e.h[tt] ^ ((4 * c + gg) << 4)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) vv[i] += (float)xq.e[i] + xl[2 * (gg * 4 + i)];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sk[gg * 4 + i] = vv[i];
         }
     };
     constexpr int PF = C == 128 ? (CZ_IP4_PREFETCH) : 0;        // what is requested a phase early (the mask above the kernel)
@@ -2587,10 +2753,30 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             }
             // epilogue 1, in place: this lane's skip elements out of the image, relu(acc) in the operand format over them, the
             // freed accumulators restart at b2 + skip
+            EpiBases eb;
+            if (EC6U) epi_bases(eb, ln2, kb2, true, false);
 #pragma unroll
             for (int c = 0; c < CTW; ++c) {
                 const int tc = tile0 + c;
-                if (YF) {
+                if (EC6U) {
+                    f32x16 sk[2];
+                    c6_skip(sk[0], 0, c, k_x, bias2, eb, kb2);
+                    c6_skip(sk[1], 1, c, k_x, bias2, eb, kb2);
+                    c6_unit(acc[c * NT + 0], acc[c * NT + 1], 0, c, k_y, eb, kb2);
+                    acc[c * NT + 0] = sk[0];
+                    acc[c * NT + 1] = sk[1];
+                    if (!EMRG) {
+                        c6_skip(sk[0], 2, c, k_x, bias2, eb, kb2);
+                        c6_unit(acc[c * NT + 2], acc[c * NT + 2], 1, c, k_y, eb, kb2);
+                        acc[c * NT + 2] = sk[0];
+                    } else if (c == CTW - 1) {                  // tile 2 of both channel tiles: every skip read before the unit writes
+                        c6_skip(sk[0], 2, 0, k_x, bias2, eb, kb2);
+                        c6_skip(sk[1], 2, 1, k_x, bias2, eb, kb2);
+                        c6_unit(acc[0 * NT + 2], acc[1 * NT + 2], 2, 0, k_y, eb, kb2);
+                        acc[0 * NT + 2] = sk[0];
+                        acc[1 * NT + 2] = sk[1];
+                    }
+                } else if (YF) {
 #pragma unroll
                     for (int pp = 0; pp < 2; ++pp) {
                         f32x16 sk[2];
@@ -2655,7 +2841,7 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                             cf8::add_pair4(vv, *reinterpret_cast<const Quad<_Float16>*>(lds + ox), *reinterpret_cast<const uint32_t*>(lds + oxl));
                             float r[4];
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) r[i] = acc[c * NT + p][gg * 4 + i] > 0.0f ? acc[c * NT + p][gg * 4 + i] : 0.0f;
+                            for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(acc[c * NT + p][gg * 4 + i]);
                             const cf8::Split4 o = cf8::split4(r);
                             if (q < 90) {
                                 *reinterpret_cast<Quad<_Float16>*>(lds + ox) = o.hi;
@@ -2695,7 +2881,23 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
             auto stg = [&](int q, int chn) {
                 return (chn >> 6) * PSTR + (bd * 90 + q) * RB + (((((chn & 63) >> 2)) ^ (q & 15)) << 4);
             };
-            if (C == 128 && ex != 0) {
+            if (EADR && ex != 0) {
+                EpiBases es;
+                epi_bases(es, ln2, kb2, false, true);
+#pragma unroll
+                for (int c = 0; c < CTW; ++c)
+#pragma unroll
+                    for (int p = 0; p < NT; ++p)
+                        if (EDMP || p < 2 || es.ok2) {
+#pragma unroll
+                            for (int gg = 0; gg < 4; ++gg) {
+                                float r[4];
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(acc[c * NT + p][gg * 4 + i]);
+                                *reinterpret_cast<float4*>(lds + (es.s[p] ^ ((8 * c + 2 * gg) << 4))) = make_float4(r[0], r[1], r[2], r[3]);
+                            }
+                        }
+            } else if (C == 128 && ex != 0) {
 #pragma unroll
                 for (int c = 0; c < CTW; ++c)
 #pragma unroll
@@ -2707,11 +2909,20 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                                 const int chn = (tile0 + c) * 32 + gg * 8 + kb2 * 4;
                                 float r[4];
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) r[i] = acc[c * NT + p][gg * 4 + i] > 0.0f ? acc[c * NT + p][gg * 4 + i] : 0.0f;
+                                for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(acc[c * NT + p][gg * 4 + i]);
                                 *reinterpret_cast<float4*>(lds + stg(q, chn)) = make_float4(r[0], r[1], r[2], r[3]);
                             }
                         }
                     }
+            } else if (EC6U && !yf && k_out != CZ_C6_OUT_C8) {
+                EpiBases eb2;
+                epi_bases(eb2, ln2, kb2, true, false);
+#pragma unroll
+                for (int c = 0; c < CTW; ++c) {
+                    c6_unit(acc[c * NT + 0], acc[c * NT + 1], 0, c, k_out, eb2, kb2);
+                    if (!EMRG) c6_unit(acc[c * NT + 2], acc[c * NT + 2], 1, c, k_out, eb2, kb2);
+                }
+                if (EMRG) c6_unit(acc[0 * NT + 2], acc[1 * NT + 2], 2, 0, k_out, eb2, kb2);
             } else
 #pragma unroll
             for (int c = 0; c < CTW; ++c) {
@@ -2730,7 +2941,7 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
                                 const int chn = tc * 32 + gg * 8 + kb2 * 4;
                                 float r[4];
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) r[i] = acc[c * NT + p][gg * 4 + i] > 0.0f ? acc[c * NT + p][gg * 4 + i] : 0.0f;
+                                for (int i = 0; i < 4; ++i) r[i] = ip4::relu1<(EP & 1) != 0>(acc[c * NT + p][gg * 4 + i]);
                                 if (yf) {
                                     if (board < n_boards)
                                         *reinterpret_cast<float4*>(yf + ((size_t)board * 90 + q) * C + chn) = make_float4(r[0], r[1], r[2], r[3]);

@@ -2,7 +2,10 @@
 """Per-launch times of the 7 x 128 tower (benchmark weights, calibration positions) for a list of arithmetics: HIP events
 around every residual-block launch of InferenceNet (block_events), 32768 positions, mean of the timed repetitions.
 
-    python tools/time_tower_launches.py [c8,c6] [32768] [masks]"""
+    python tools/time_tower_launches.py [c8,c6] [32768] [masks]
+
+A/B of variant builds of the chain kernel (-DCZ_IP4_PREFETCH=<mask>, -DCZ_IP4_EPI=<mask>: build.py --out variants/<name>.so -D...):
+run it once per library with CZ_LIB=<path>, alternating, and compare the chained launches' ms per block."""
 import json
 import os
 import sys
