@@ -8,9 +8,10 @@ state string (the side to move at the bottom, in upper case -- environment/stati
 recorded -- in the frame of the side that moves first, which takes the part of "red".
 
 ``load_book`` checks every position before anything is used: ten rows of nine files, known piece letters, exactly one
-king per side, and, with the package's own rule functions, that the game is not already over (``done``) and that a side
-can still attack (``has_attack_chessman``).  Those two run on the GPU like every rule of the package; ``rules`` takes any
-other object with the two functions (the tests pass the C oracle, a tool may pass ``None`` to check the form alone).
+king per side, elephants and advisors on squares they can reach (a move from any other has no action label), and, with
+the package's own rule functions, that the game is not already over (``done``) and that a side can still attack
+(``has_attack_chessman``).  Those two run on the GPU like every rule of the package; ``rules`` takes any other object
+with the two functions (the tests pass the C oracle, a tool may pass ``None`` to check the form alone).
 """
 import numpy as np
 
@@ -72,7 +73,33 @@ def parse_position(line):
     for king, side in (("S", "the side to move"), ("s", "the other side")):
         if state.count(king) != 1:
             raise ValueError(f"{state.count(king)} kings of {side}, expected exactly one")
+    err = _check_squares(state)
+    if err:
+        raise ValueError(err)
     return array_to_state(state_to_array(state))          # (canonical form: digits merged)
+
+
+# (file, rank) from the owner's own back rank: the only squares an elephant / an advisor ever stands on.  Their moves
+# from anywhere else have no action label, which the search indexes the policy with.
+_ELEPHANT_SQUARES = {(2, 0), (6, 0), (0, 2), (4, 2), (8, 2), (2, 4), (6, 4)}
+_ADVISOR_SQUARES = {(3, 0), (5, 0), (4, 1), (3, 2), (5, 2)}
+
+
+def _check_squares(state):
+    """Elephants and advisors stand on squares of their own; returns an error text or None."""
+    for r, row in enumerate(state.split("/")):
+        x = 0
+        for ch in row:
+            if ch.isdigit():
+                x += int(ch)
+                continue
+            squares = {"e": _ELEPHANT_SQUARES, "m": _ADVISOR_SQUARES}.get(ch.lower())
+            rank = 9 - r if ch.isupper() else r           # (row 1 of the string is the other side's back rank)
+            if squares is not None and (x, rank) not in squares:
+                name = "elephant" if ch.lower() == "e" else "advisor"
+                return f"{name} {ch!r} in row {r + 1}, file {x + 1}: no {name} can reach that square"
+            x += 1
+    return None
 
 
 def load_book(path, rules=_PackageRules):

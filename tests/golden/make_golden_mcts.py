@@ -324,7 +324,7 @@ def gen_games():
 
 
 def _arena_game(ev, s):
-    cfg = make_cfg(s["sims"], c_puct=s.get("c_puct", 1.0), tau_decay_rate=0.0,
+    cfg = make_cfg(s["sims"], c_puct=s.get("c_puct", 1.0), tau_decay_rate=s.get("tau", 0.0),
                    max_game_length=s["max_game_length"])
     cfg.opts.evaluate = bool(s.get("evaluate", False))
     seed, idx = s["seed"], s["idx"]

@@ -72,6 +72,36 @@ def test_every_rejection_names_file_and_line(tmp_path, name, line, needle):
     assert needle in msg, msg
 
 
+MISPLACED = [
+    # an elephant on a square no elephant reaches: its moves have no action label (the oracle's player dies on it)
+    ("black elephant", "3s1e3/4m4/4e4/9/r8/6K2/9/4E3R/4M4/2E1S4", "elephant 'e' in row 1, file 6"),
+    ("red elephant", "3s5/4m4/4e4/9/r8/6K2/9/3E4R/4M4/2E1S4", "elephant 'E' in row 8, file 4"),
+    ("elephant across the river", "3s5/4m4/9/9/2E6/9/9/8R/4M4/4S4", "elephant 'E' in row 5, file 3"),
+    ("red advisor", "3s5/4m4/9/9/9/9/9/8R/9/3SM4", "advisor 'M' in row 10, file 5"),
+    ("black advisor", "3s5/3m5/9/9/9/9/9/8R/4M4/4S4", "advisor 'm' in row 2, file 4"),
+    ("in a FEN", "3k1b3/9/9/9/9/9/9/8R/9/4K4 w", "elephant 'e' in row 1, file 6"),
+]
+
+
+@pytest.mark.parametrize("name,line,needle", MISPLACED, ids=[r[0] for r in MISPLACED])
+def test_elephants_and_advisors_off_their_squares_are_refused(tmp_path, name, line, needle):
+    """Refused by the parser, before any rule function sees the position."""
+    path = _write(tmp_path, f"{MID}\n{line}\n")
+    with pytest.raises(ValueError) as e:
+        bk.load_book(path, rules=None)
+    assert str(e.value).startswith(f"{path}:2: ") and needle in str(e.value), str(e.value)
+
+
+def test_every_elephant_and_advisor_square_is_accepted(tmp_path):
+    """All seven elephant squares and five advisor squares of both sides, and every position of the golden books."""
+    lines = ["3s5/9/9/9/R8/2E3E2/9/E3E3E/9/2E1S1E2", "3s5/9/9/9/R8/9/9/3M1M3/4M4/3MSM3"]
+    lines += [fliped_state(s) for s in lines]               # ... the same squares seen from the other side
+    path = _write(tmp_path, "\n".join(lines) + "\n")
+    assert bk.load_book(path, rules=None) == lines
+    for name in ("book.txt", "endgame_book.txt"):
+        assert bk.load_book(os.path.join(GOLDEN, name), rules=xo)
+
+
 def test_empty_book_is_rejected(tmp_path):
     path = _write(tmp_path, "# nothing\n\n")
     with pytest.raises(ValueError, match="no position"):

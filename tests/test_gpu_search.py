@@ -1,7 +1,9 @@
 """-m gpu: the HIP MCTS / self-play kernels (through the C-ABI) against the oracle (oracle/xq_mcts.c)
 and against the golden vectors recorded from the reference's own CChessPlayer / SelfPlayWorker.
 The network is stubbed by the exact-arithmetic stub of tests/stub_net.py (torch version on the GPU),
-so visit counts, W sums (float64, compared bit for bit) and priors (float32) must be identical."""
+so visit counts, W sums (float64, compared bit for bit) and priors (float32) must be identical.
+The game loops' rare endings (120 plies without a capture, no attacker left, three free repetitions, bans, the history
+scan past 64 plies): tests/test_gpu_endings.py, with tests/test_endings_oracle_cpu.py and tests/game_endings.py."""
 import json
 import os
 import types
