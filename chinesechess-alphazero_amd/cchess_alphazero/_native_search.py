@@ -21,11 +21,13 @@ GAME_BOOK_SHIFT = 8      # finished-game record flags, bits 8-31: book index + 1
 BOOK_MAX = (1 << 24) - 2  # include/czero.h CZ_BOOK_MAX
 MOVE_FAST = 0x8000       # finished-game record, moves[i] bit 15: ply i was a fast search (cz_search_set_playout_cap)
 VISIT_FAST = 2           # visit entry flag: the ply was a fast search
+VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (cz_search_set_forced_playouts)
 
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
 # was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
-# search of the playout cap (set_playout_cap).
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast")
+# search of the playout cap (set_playout_cap); whether n holds the PRUNED counts of set_forced_playouts, and then
+# raw_total, the sum of the raw counts of the non-banned edges (0 otherwise).
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total")
 
 
 class SearchCfg(C.Structure):
@@ -79,6 +81,15 @@ def declare(L):
     if hasattr(L, "cz_search_set_playout_cap"):
         L.cz_search_set_playout_cap.argtypes = [vp, i32, C.c_double, vp]
         L.cz_search_set_playout_cap.restype = i32
+    if hasattr(L, "cz_search_set_forced_playouts"):
+        L.cz_search_set_forced_playouts.argtypes = [vp, C.c_double, vp]
+        L.cz_search_set_forced_playouts.restype = i32
+    if hasattr(L, "cz_search_root_targets"):
+        L.cz_search_root_targets.argtypes = [vp, vp, vp, vp]
+        L.cz_search_root_targets.restype = i32
+    if hasattr(L, "cz_policy_target_prune"):
+        L.cz_policy_target_prune.argtypes = [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp]
+        L.cz_policy_target_prune.restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -273,6 +284,25 @@ class Search:
                       "cz_search_set_playout_cap")
         self.fast_sims, self.full_rate = int(fast_sims), float(full_rate)
 
+    def set_forced_playouts(self, k=0.0):
+        """Forced playouts and policy target pruning (cz_search_set_forced_playouts; include/czero.h has the arithmetic):
+        with k > 0 a root child that has been tried is visited at least sqrt(k * p * N) times -- in self-play on full plies
+        only, in external mode in every search -- and self-play's visit entries of those plies hold the PRUNED counts
+        (`pruned`, `raw_total`).  k = 0 switches it off.  Call it before start_selfplay() and before a graph capture."""
+        _native.check(self.L.cz_search_set_forced_playouts(self.h, float(k), self._stream()),
+                      "cz_search_set_forced_playouts")
+        self.forced_k = float(k)
+
+    def root_targets(self):
+        """The pruned counts of every current root (cz_search_root_targets; edge order of root_stats, bans of the current
+        set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
+        import torch
+        n = torch.empty((self.G, _native.MAXMOVES), dtype=torch.int32, device=self.device)
+        raw = torch.empty((self.G,), dtype=torch.int32, device=self.device)
+        _native.check(self.L.cz_search_root_targets(self.h, C.c_void_p(n.data_ptr()), C.c_void_p(raw.data_ptr()),
+                                                    self._stream()), "cz_search_root_targets")
+        return dict(n=n.cpu().numpy(), raw_total=raw.cpu().numpy())
+
     def pull_visits(self, defer=False):
         """Move the entries waiting in the device ring to the host (kept until their game's record is drained).
         Returns the number of entries moved; synchronises the stream.  defer=True only copies them: the host-side sorting
@@ -307,6 +337,14 @@ class Search:
                 row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
                 self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
 
+    def waiting_visits(self):
+        """The entries fetched so far whose game's record has not been drained: {game_id: [VisitEntry, ...] in ply order}.
+        Fetches what waits in the device ring first; the entries stay and still go out with their games (tools that look
+        at plies before their games end)."""
+        self.pull_visits()
+        return {gid: [self.parse_visit_entry(row) for _, row in sorted(rows, key=lambda e: e[0])]
+                for gid, rows in self._visits.items()}
+
     @staticmethod
     def parse_visit_entry(row):
         """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges]) -> VisitEntry."""
@@ -315,7 +353,8 @@ class Search:
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
-                          ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST))
+                          ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
+                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -550,3 +589,25 @@ def debug_sqrt(x):
     _native.check(_native.lib().cz_debug_sqrt(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), x.numel(),
                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_debug_sqrt")
     return y
+
+
+def policy_target_prune(labels, n, w, p, n_edges, c_puct, k):
+    """cz_policy_target_prune: the pruning arithmetic of set_forced_playouts on caller-supplied rows.  labels uint16 (bit
+    15 = banned), n int32, w float64, p float32, all [rows, 128] cuda tensors; n_edges uint8 [rows].  Returns (pruned
+    counts int32 [rows, 128], raw_total int32 [rows]) on the device."""
+    import torch
+    _native.require_gpu()
+    rows = int(n_edges.numel())
+    want = ((labels, torch.uint16), (n, torch.int32), (w, torch.float64), (p, torch.float32))
+    for t, dt in want:
+        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"policy_target_prune: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
+    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
+        raise ValueError("policy_target_prune: n_edges must be a contiguous cuda uint8 tensor")
+    out = torch.empty((rows, _native.MAXMOVES), dtype=torch.int32, device=n.device)
+    raw = torch.empty((rows,), dtype=torch.int32, device=n.device)
+    _native.check(_native.lib().cz_policy_target_prune(
+        C.c_void_p(labels.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(p.data_ptr()),
+        C.c_void_p(n_edges.data_ptr()), rows, float(c_puct), float(k), C.c_void_p(out.data_ptr()),
+        C.c_void_p(raw.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_policy_target_prune")
+    return out, raw

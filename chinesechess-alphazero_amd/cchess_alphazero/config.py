@@ -98,6 +98,9 @@ class EngineConfig(_Section):
                          fast_sims=0,             # playout cap randomization (run.py self --fast-sims N --full-rate P): a ply
                          full_rate=0.25,          # is a full search with probability full_rate, else fast_sims simulations
                                                   # without root noise, and its row is not trained on; 0 = off
+                         forced_playouts=0.0,     # forced playouts + policy target pruning (run.py self --forced-playouts
+                                                  # K, needs record_visits): a tried root child gets at least
+                                                  # sqrt(K * p * N) visits, the recorded counts are pruned; 0 = off
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -42,7 +42,7 @@ class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
-                 full_rate=None):
+                 full_rate=None, forced_playouts=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -53,7 +53,10 @@ class SelfPlayEngine:
         config.engine.book_rate), otherwise from INIT_STATE.  The side that moves first plays "red" in every count.
         fast_sims, full_rate: playout cap randomization (None = config.engine.fast_sims / full_rate; fast_sims 0 = off): a
         ply is a full search with probability full_rate, otherwise a fast one of fast_sims simulations without root noise,
-        whose record item carries the training weight 0 (drain)."""
+        whose record item carries the training weight 0 (drain).
+        forced_playouts: k of forced playouts and policy target pruning (None = config.engine.forced_playouts; 0 = off):
+        on full plies a tried root child is visited at least sqrt(k * p * N) times, and the recorded visit counts -- the
+        pi of drain()'s items -- are the pruned ones (include/czero.h).  The moves are chosen from the raw counts."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -113,6 +116,12 @@ class SelfPlayEngine:
         self.full_rate = float(getattr(ec, "full_rate", 0.25) if full_rate is None else full_rate)
         if self.fast_sims:                                     # likewise before start() and before a graph capture
             self.search.set_playout_cap(self.fast_sims, self.full_rate)
+        self.forced_playouts = float(getattr(ec, "forced_playouts", 0.0) if forced_playouts is None else forced_playouts)
+        if self.forced_playouts and not self.record_visits:
+            raise ValueError("forced_playouts needs record_visits: forcing without the pruned visit counts only distorts "
+                             "what a trainer sees")
+        if self.forced_playouts:                               # likewise
+            self.search.set_forced_playouts(self.forced_playouts)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -304,7 +313,9 @@ class SelfPlayEngine:
         whose visit record is incomplete (`visits` None), keep the two-element form.  With a playout cap (fast_sims) the
         item of a FAST ply is [move, value, pi or None, 0]: element 2 is pi where a full ply would carry it, else None;
         element 3 is the row's training weight (lib/replay_window.py keeps the position, the trainer skips the row).  A
-        full ply's item is unchanged.  `fast_plies` counts the game's fast plies."""
+        full ply's item is unchanged.  `fast_plies` counts the game's fast plies.  With forced playouts
+        pi comes from the pruned counts; `pruned_visits` is the number of root visits pruning removed from the game's
+        entries, sum of raw_total - sum of the non-banned pruned counts (0 without forced playouts)."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
@@ -319,8 +330,10 @@ class SelfPlayEngine:
                 if r["fast"][i]:
                     item += [None] * (3 - len(item)) + [0]
                 data.append(item)
+            pruned = [e for e in vis or [] if e.pruned]
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
-                            resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]), data=data))
+                            resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]),
+                            pruned_visits=sum(e.raw_total - int(e.n[~e.banned].sum()) for e in pruned), data=data))
             if self.record_visits:
                 out[-1]["visits"] = vis
         return out

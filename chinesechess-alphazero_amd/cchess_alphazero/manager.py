@@ -46,6 +46,10 @@ _FLAGS = [
                               "a fast one of N simulations without root noise whose row is not trained on (0 = off)")),
     ("--full-rate", dict(type=float, default=0.25, metavar="P",
                          help="(self, with --fast-sims) probability that a ply is a full search")),
+    ("--forced-playouts", dict(type=float, default=0.0, metavar="K",
+                               help="(self, with --record-visits) forced playouts and policy target pruning: on full plies a "
+                                    "tried root move is visited at least sqrt(K * prior * visits) times and the recorded "
+                                    "counts are pruned of the visits that forcing added (0 = off; the paper uses 2)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -91,6 +95,12 @@ def build_config(args):
     if not 0.0 <= args.full_rate <= 1.0:
         raise SystemExit(f"--full-rate {args.full_rate}: expected 0 <= P <= 1")
     engine.fast_sims, engine.full_rate = args.fast_sims, args.full_rate
+    if not 0.0 <= args.forced_playouts < float("inf"):
+        raise SystemExit(f"--forced-playouts {args.forced_playouts}: expected a finite K >= 0")
+    if args.forced_playouts and not engine.record_visits:
+        raise SystemExit(f"--forced-playouts {args.forced_playouts} needs --record-visits: forcing without the pruned "
+                         "visit counts only distorts what the trainer sees")
+    engine.forced_playouts = args.forced_playouts
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

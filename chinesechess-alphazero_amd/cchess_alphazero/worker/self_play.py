@@ -93,14 +93,19 @@ class SelfPlayWorker:
             logger.info(f"Process {self.pid}-{self.rank}: playout cap: a ply is a full search "
                         f"({self.config.play.simulation_num_per_move} simulations) with probability {self.engine.full_rate}, "
                         f"otherwise {self.engine.fast_sims} simulations without root noise")
+        if self.engine.forced_playouts:
+            logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
+                        f"the recorded visit counts are pruned (policy target pruning)")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:
             self.engine.capture_graph()
 
     def _harvest(self):
-        full = fast = 0
+        full = fast = pruned = raw = 0
         for g in self.engine.drain():
+            pruned += g.get("pruned_visits", 0)
+            raw += sum(e.raw_total for e in g.get("visits") or [] if e.pruned)
             fast += g.get("fast_plies", 0)
             full += len(g["data"]) - 1 - g.get("fast_plies", 0)
             logger.debug(f"Process {self.pid}-{self.rank} game {g['game_id']} turn={g['turns'] / 2}, "
@@ -113,6 +118,9 @@ class SelfPlayWorker:
                     logger.info(f"Process {self.pid} save play data to {path}")
         if self.engine.fast_sims and full + fast:
             logger.info(f"Process {self.pid}-{self.rank}: drained {full} full plies (training rows) and {fast} fast plies")
+        if self.engine.forced_playouts and raw:
+            logger.info(f"Process {self.pid}-{self.rank}: policy target pruning removed {pruned} of {raw} root visits "
+                        f"({100.0 * pruned / raw:.1f} %)")
 
     def reload_best_model(self):
         """The reference's self-play picks up a new best model while it runs: its prediction thread re-checks the

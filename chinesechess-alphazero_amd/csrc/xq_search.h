@@ -98,6 +98,9 @@ struct SearchParams {
     // playout cap randomization of self-play (cz_search_set_playout_cap); read through ply_is_fast only
     int fast_sims;          // simulations of a fast ply, 0 = off: every ply is a full search of `sims`
     double full_rate;       // ply `turns` is a full search iff philox_uniform(seed, game_id, 2, turns) < full_rate
+    // forced playouts + policy target pruning (cz_search_set_forced_playouts); read by k_sim's root context, emit_visits
+    // and k_root_targets only
+    double forced_k;        // 0 = off; a tried root child is visited at least sqrt(forced_k * p * N) times
 };
 
 struct SearchBuffers {
@@ -174,13 +177,14 @@ constexpr int VISIT_MAX_EDGES = 128;               // = MAXMOVES
 constexpr uint16_t VISIT_BANNED = 0x8000;          // label bit: the edge is in the ply's no_act list
 constexpr uint32_t VISIT_RESIGN = 1u;              // entry flag: the player resigned at this ply
 constexpr uint32_t VISIT_FAST = 2u;                // entry flag: the ply was a fast search (cz_search_set_playout_cap)
+constexpr uint32_t VISIT_PRUNED = 4u;              // entry flag: n[] holds the PRUNED counts (cz_search_set_forced_playouts)
 struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
     uint32_t game_id;
     uint16_t ply;       // turns when the move was chosen
     uint8_t n_edges;
     uint8_t flags;
     int32_t sum_n;      // the root's own visit count
-    uint32_t reserved;
+    uint32_t raw_total; // VISIT_PRUNED: sum of the raw counts of the non-banned edges; otherwise 0
 };
 constexpr int VISIT_STRIDE = (int)sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES + 4 * VISIT_MAX_EDGES;   // 784 B
 

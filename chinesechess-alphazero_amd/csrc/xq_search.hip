@@ -408,7 +408,25 @@ struct RootCtx {
     const uint16_t* no_act;
     const double* noise;        // this game's Dirichlet rows [K][MAXMOVES] written by k_noise (NULL when eps == 0)
     int sim;
+    bool force;                 // forced playouts at this root (cz_search_set_forced_playouts; never on a fast ply)
 };
+
+// The root's side of the selection, one text for select_edge's scoring loop and its forcing pass: the two must agree bit
+// for bit.  Ban test (player.py:298-300), the prior this simulation uses (:304), the exploration term (:306).
+XQ_D bool root_banned(const RootCtx& rc, uint16_t mv)
+{
+    bool banned = false;
+    for (int k = 0; k < rc.n_no_act; ++k) banned = banned || (rc.no_act[k] == mv);
+    return banned;
+}
+XQ_D double root_prior(const SearchParams& P, const RootCtx& rc, float p, int j)
+{
+    const float a = (rc.noise ? P.one_minus_eps_f32 : 1.0f) * p;   // (no rows: eps = 0, also on a fast ply of the playout cap)
+    double p_ = (double)a;
+    if (rc.noise) p_ = p_ + P.noise_eps * rc.noise[(size_t)rc.sim * MAXMOVES + j];   // player.py:304
+    return p_;
+}
+XQ_D double root_u(const SearchParams& P, double p_, double xx, int n) { return P.c_puct * p_ * xx / (double)(1 + n); }
 
 struct Picked {
     int j;              // edge index inside the node, -1 = none
@@ -447,13 +465,8 @@ XQ_D Picked select_edge(const SearchParams& P, char* base, const EdgeStat* sb, i
             const double q = n ? w / (double)n : 0.0;
             double u;
             if (rc.is_root) {
-                if (rc.n_no_act) {
-                    for (int k = 0; k < rc.n_no_act; ++k) valid = valid && (rc.no_act[k] != mv);
-                }
-                const float a = (rc.noise ? P.one_minus_eps_f32 : 1.0f) * p;   // (no rows: eps = 0, also on a fast ply of the playout cap)
-                double p_ = (double)a;
-                if (rc.noise) p_ = p_ + P.noise_eps * rc.noise[(size_t)rc.sim * MAXMOVES + j];   // player.py:304
-                u = P.c_puct * p_ * xx / (double)(1 + n);
+                if (rc.n_no_act) valid = !root_banned(rc, mv);
+                u = root_u(P, root_prior(P, rc, p, j), xx, n);
             } else {
                 const float a = P.c_puct_f32 * p;
                 u = (double)a * xx / (double)(1 + n);
@@ -466,6 +479,24 @@ XQ_D Picked select_edge(const SearchParams& P, char* base, const EdgeStat* sb, i
         }
         if (h == 0) win0 = valid && win; else win1 = valid && win;
         if (valid && score >= best_s) { best_s = score; best_j = j; }   // h = 1 has the larger index: wins ties
+    }
+    if (rc.is_root && rc.force) {
+        // forced playouts, a pass of its own so that the loop above stays what it was: a tried root child with
+        // n < sqrt(k * p_ * sum_n) scores +infinity.  Compared squared: integers times integers against a product, no
+        // square root and nothing a contraction could fuse.  Not for a banned edge or one whose score was rejected.
+#pragma nounroll
+        for (int h = 0; h < halves; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm || !sb) continue;                       // (a fresh statistics block: nothing tried yet)
+            const EdgeStat es = sb[j];
+            const int n = es.n;
+            if (n <= 0 || root_banned(rc, pm[j])) continue;
+            const double p_ = root_prior(P, rc, pp[j], j);
+            if (!((double)n * (double)n < P.forced_k * p_ * (double)sum_n)) continue;
+            if (!(es.w / (double)n + root_u(P, p_, xx, n) >= -99999999.0)) continue;
+            best_s = __builtin_inf();
+            best_j = j;                                         // h = 1 has the larger index: wins ties
+        }
     }
     // proven-win shortcut: first edge in order with q > 1 - 1e-7 (player.py:309-311)
     const int first_win = lowest_bit(__ballot(win0), __ballot(win1));
@@ -1251,9 +1282,63 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
     if (resigned) count(gv, CT_RESIGNS);
 }
 
+// Policy target pruning (include/czero.h, cz_search_set_forced_playouts): one wavefront, edge j = lane + 64 h.  lab[h]
+// carries VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise; the pruned counts replace n[].
+// All arithmetic in float64, in the order czero.h writes it.  Returns S, the raw total of the non-banned edges.
+XQ_D int prune_targets(int nm, const uint16_t lab[2], int n[2], const double w[2], const float p[2], double c_puct, double k)
+{
+    const int lane = lane_id();
+    long long s = 0;
+    int bn = -1, bl = 0x10000;              // this lane's candidate for c*: greatest n, then lowest label
+    double bw = 0.0;
+    float bp = 0.0f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED);
+        if (!live) continue;
+        s += n[h];
+        const int l = lab[h] & 0x7FFF;
+        if (n[h] > bn || (n[h] == bn && l < bl)) { bn = n[h]; bl = l; bw = w[h]; bp = p[h]; }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        s += __shfl_xor(s, d, 64);
+        const int on = __shfl_xor(bn, d, 64), ol = __shfl_xor(bl, d, 64);
+        const double ow = __shfl_xor(bw, d, 64);
+        const float op = __shfl_xor(bp, d, 64);
+        if (on > bn || (on == bn && ol < bl)) { bn = on; bl = ol; bw = ow; bp = op; }
+    }
+    const int S = (int)s;
+    if (S <= 0) return 0;                   // nothing searched (or everything banned): the counts stay
+    const double Sd = (double)S;
+    const double sq = __dsqrt_rn(Sd);
+    const double e_star = bw / (double)bn + ((c_puct * (double)bp) * sq) / (double)(1 + bn);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED);
+        if (!live || n[h] <= 0 || (int)(lab[h] & 0x7FFF) == bl) continue;
+        const double nj = (double)n[h], pj = (double)p[h];
+        const double f = floor(__dsqrt_rn((k * pj) * Sd));
+        const double d = e_star - w[h] / nj;
+        double need = nj;
+        if (d > 0.0) {
+            need = ceil(((c_puct * pj) * sq) / d - 1.0);
+            need = need < 0.0 ? 0.0 : (need > nj ? nj : need);
+        }
+        const double keep = nj - f;
+        int m = (int)(need > keep ? need : keep);
+        if (m < n[h] && m <= 1) m = 0;
+        n[h] = m;
+    }
+    return S;
+}
+
 // Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
-XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns, bool resigned, bool fast)
+// prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
+// raw_total); the tree keeps the raw counts and choose_action has already used them.
+XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns,
+                      bool resigned, bool fast, bool prune)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -1282,21 +1367,47 @@ XQ_D void emit_visits(const SearchBuffers& B, const GameView& gv, const VisitRin
     const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
     const int n_no_act = uni((int)B.g_n_no_act[g]);
     const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
-    for (int j = lane; j < nm; j += 64) {
-        const uint16_t mv = pm[j];
-        bool banned = false;
-        for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-        lab[j] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-        cnt[j] = sb ? sb[j].n : 0;
+    int raw_total = 0;
+    if (!prune) {
+        for (int j = lane; j < nm; j += 64) {
+            const uint16_t mv = pm[j];
+            bool banned = false;
+            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+            lab[j] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+            cnt[j] = sb ? sb[j].n : 0;
+        }
+    } else {
+        uint16_t el[2] = {0, 0};
+        int en[2] = {0, 0};
+        double ew[2] = {0.0, 0.0};
+        float ep[2] = {0.0f, 0.0f};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            const uint16_t mv = pm[j];
+            bool banned = false;
+            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+            if (sb) { const EdgeStat es = sb[j]; en[h] = es.n; ew[h] = es.w; }
+            ep[h] = node_p(base)[j];
+        }
+        raw_total = prune_targets(nm, el, en, ew, ep, P.c_puct, P.forced_k);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j < nm) { lab[j] = el[h]; cnt[j] = en[h]; }
+        }
     }
+    const bool pruned = raw_total > 0;      // S == 0: nothing to prune, the entry is the one written without pruning
     if (lane == 0) {
         VisitEntryHdr* h = reinterpret_cast<VisitEntryHdr*>(e);
         h->game_id = B.g_game_id[g];
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
-        h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u));
+        h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u));
         h->sum_n = hdr.sum_n;
-        h->reserved = 0u;
+        h->raw_total = (uint32_t)raw_total;
     }
 }
 
@@ -1313,7 +1424,10 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     uint16_t* hacts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
     const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
     const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
-    if (V.ring) emit_visits(B, gv, V, turns, action < 0, ply_is_fast(P, game_id, turns));
+    if (V.ring) {
+        const bool fast = ply_is_fast(P, game_id, turns);
+        emit_visits(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast);
+    }
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;
     int value = 0;
@@ -1445,9 +1559,11 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
     int active = uni(B.g_active[g]);
     Arena ar{uniu(B.g_heap_top[g]), uni(B.g_nchunks[g]), uni(B.g_node_count[g])};
     // (no root noise on a fast ply of the playout cap: k_noise drew no rows for it)
+    // and no forced playouts either: a fast ply has no noise to examine
     const bool noisy = P.noise_eps != 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
+    const bool force = P.forced_k > 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
     const RootCtx rc{false, uni((int)B.g_n_no_act[g]), B.g_no_act + (size_t)g * MAX_NO_ACT,
-                     noisy ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0};
+                     noisy ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0, force};
     int resume_i = P.K;
     // the slot table as it is when the launch starts, slot i on lane i: one load per array instead of one dependent
     // round trip per slot and field (a simulation only ever changes its own slot, and each slot is visited once per list)
@@ -1826,6 +1942,76 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
         if (sum_n) sum_n[g] = root_sum_n;
         if (counts) counts[g] = (uint8_t)nm;
     }
+}
+
+// Pruned policy targets of every current root (cz_search_root_targets): what emit_visits would record for it, with
+// the bans of the current set_roots
+__global__ __launch_bounds__(64) void k_root_targets(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
+                                                    int32_t* __restrict__ raw_total)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    const int root = B.g_root[g];
+    const int n_no_act = B.g_n_no_act[g];
+    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
+    int nm = 0;
+    uint16_t el[2] = {0, 0};
+    int en[2] = {0, 0};
+    double ew[2] = {0.0, 0.0};
+    float ep[2] = {0.0f, 0.0f};
+    if (root >= 0) {
+        char* base = rec_ptr(gv, (uint32_t)root);
+        const NodeHdr hdr = load_hdr(base);
+        nm = (int)(hdr.meta & 0xFF);
+        if (nm > MAXMOVES) nm = MAXMOVES;
+        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
+        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            const uint16_t mv = pm[j];
+            bool banned = false;
+            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+            if (sb) { const EdgeStat es = sb[j]; en[h] = es.n; ew[h] = es.w; }
+            ep[h] = node_p(base)[j];
+        }
+    }
+    const int S = prune_targets(nm, el, en, ew, ep, P.c_puct, P.forced_k);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) n[(size_t)g * MAXMOVES + lane + 64 * h] = lane + 64 * h < nm ? en[h] : 0;
+    if (lane == 0) raw_total[g] = S;
+}
+
+// cz_policy_target_prune: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
+__global__ __launch_bounds__(64) void k_policy_target_prune(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
+                                                           const double* __restrict__ w, const float* __restrict__ p,
+                                                           const uint8_t* __restrict__ n_edges, int rows, double c_puct,
+                                                           double k, int32_t* __restrict__ out_n,
+                                                           int32_t* __restrict__ out_raw_total)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    int nm = n_edges[r];
+    if (nm > MAXMOVES) nm = MAXMOVES;
+    uint16_t el[2] = {0, 0};
+    int en[2] = {0, 0};
+    double ew[2] = {0.0, 0.0};
+    float ep[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
+        if (lane + 64 * h < nm) { el[h] = labels[i]; en[h] = n[i]; ew[h] = w[i]; ep[h] = p[i]; }
+    }
+    const int S = prune_targets(nm, el, en, ew, ep, c_puct, k);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) out_n[(size_t)r * MAXMOVES + lane + 64 * h] = lane + 64 * h < nm ? en[h] : 0;
+    if (lane == 0) out_raw_total[r] = S;
 }
 
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
@@ -2391,6 +2577,43 @@ int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, voi
     if (e != hipSuccess) return serr_hip("cz_search_set_playout_cap", e);
     s->P.fast_sims = fast_sims;
     s->P.full_rate = fast_sims > 0 ? full_rate : 0.0;
+    return CZ_OK;
+}
+
+static_assert(CZ_VISIT_PRUNED == VISIT_PRUNED && sizeof(cz_visit_entry) == sizeof(VisitEntryHdr), "czero.h: visit entry");
+
+static bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.7976931348623157e308; }   // (false for NaN and infinity)
+
+int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: null handle");
+    if (!finite_nonneg(k)) return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: k negative or not finite");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_forced_playouts", e);
+    s->P.forced_k = k;
+    return CZ_OK;
+}
+
+int cz_search_root_targets(cz_search* s, int32_t* n, int32_t* raw_total, void* stream)
+{
+    if (!s || !n || !raw_total) return serr(CZ_ERR_ARG, "cz_search_root_targets: null argument");
+    hipLaunchKernelGGL(k_root_targets, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, n, raw_total);
+    S_LAUNCH_CHECK("cz_search_root_targets");
+    return CZ_OK;
+}
+
+int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                           const uint8_t* n_edges, int rows, double c_puct, double k, int32_t* out_n,
+                           int32_t* out_raw_total, void* stream)
+{
+    if (!labels || !n || !w || !p || !n_edges || !out_n || !out_raw_total || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_policy_target_prune: null argument or rows < 0");
+    if (!finite_nonneg(k) || !finite_nonneg(c_puct))
+        return serr(CZ_ERR_ARG, "cz_policy_target_prune: k or c_puct negative or not finite");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_policy_target_prune, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows,
+                       c_puct, k, out_n, out_raw_total);
+    S_LAUNCH_CHECK("cz_policy_target_prune");
     return CZ_OK;
 }
 

@@ -194,6 +194,63 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * outside [0, 1] with fast_sims > 0 -- the object keeps its setting; cz_search_set_sims below fast_sims is refused. */
 int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, void* stream);
 
+/* Forced playouts and policy target pruning (KataGo: Wu 2019, section 3.2, the companion of the playout cap; the
+ * reference has no such option).  k = 0 (the state after cz_search_create) switches both off: every kernel then
+ * produces the bits it produced before.  The paper uses k = 2.
+ *
+ * FORCED PLAYOUTS (search).  With k > 0 the selection at the ROOT (select_action_q_and_u with is_root_node,
+ * player.py:286-320; no other node) treats an edge as forced when it is not banned, its score q + u is not rejected
+ * (score >= -99999999), n > 0 and
+ *       (double)n * (double)n < k * p_ * (double)sum_n                      [evaluated as (k * p_) * sum_n]
+ * where n and sum_n are the values that selection reads -- virtual losses of simulations in flight included, sum_n
+ * before this simulation's increment -- and p_ is the prior this simulation uses, root noise included.  That is
+ * n < sqrt(k p_ sum_n) without a square root: exact in float64, nothing to contract.  A forced edge's score is
+ * +infinity; everything else is unchanged: the proven-win shortcut (first edge with q > 1 - 1e-7) keeps precedence,
+ * among several forced edges the `>=` arg-max takes the last in edge order, nodes with more than 64 moves included.
+ * In self-play it applies on FULL plies only: a fast ply of the playout cap never forces (it has no noise).  In
+ * external mode (cz_search_set_roots) it applies whenever it has been set -- which is how a single search is tested;
+ * worker/evaluator.py (the arena), agent/player.py (CChessPlayer) and uci.py never set it.
+ *
+ * POLICY TARGET PRUNING (record).  Forcing spends visits the search would not have made on the move's merits; they
+ * are removed from the recorded targets, not from the tree.  Given a root's edges -- labels with the banned bit
+ * (0x8000), raw visit counts n, w (float64), float32 priors p WITHOUT noise (a noise row lives for one simulation),
+ * c_puct and k -- all arithmetic in float64, in the order written:
+ *   S   = sum of n_j over the non-banned edges (it must fit int32).  S == 0: nothing is pruned.
+ *   c*  = the non-banned edge with the greatest n, ties to the LOWEST label: what cz_search_choose plays at tau = 0.
+ *   sq  = sqrt((double)S), correctly rounded
+ *   E*  = q* + ((c_puct * p*) * sq) / (1 + n*)                 with q = w / n
+ *   for every other non-banned edge with n_j > 0:
+ *     f_j    = floor(sqrt((k * p_j) * S))
+ *     d_j    = E* - q_j
+ *     need_j = n_j if d_j <= 0, otherwise ceil(((c_puct * p_j) * sq) / d_j - 1) clamped to [0, n_j] in float64 before
+ *              the conversion to an integer
+ *     m_j    = max(need_j, n_j - f_j)
+ *     if m_j < n_j and m_j <= 1 then m_j = 0
+ *   c* keeps n*; edges with n_j = 0 stay 0; banned edges keep their raw count and their flag.
+ * (need_j is the smallest count at which the edge's own PUCT score no longer exceeds E*; at most f_j visits are
+ * taken away; an edge cut down to a single visit is noise and goes altogether.)
+ * In self-play, with k > 0, record_visits on and the ply not fast, the ply's visit entry holds the pruned counts, its
+ * flags carry CZ_VISIT_PRUNED and its header word raw_total = S; when S == 0 (no move, every move banned) and on fast
+ * plies and with k = 0 the entry is written byte for byte as before, raw_total = 0.  The move is still chosen from the
+ * raw counts in the tree (temperature, resignation, bans); neither the tree nor the game loop changes; no counter is
+ * added.
+ *
+ * Call it before cz_search_start_selfplay and before a graph capture (the captured launches hold the parameters), like
+ * cz_search_set_playout_cap; synchronises the stream.  CZ_ERR_ARG: s NULL, k < 0 or not finite -- the object keeps its
+ * setting. */
+int cz_search_set_forced_playouts(cz_search* s, double k, void* stream);
+/* The pruned counts of every current root, as a visit entry of that root would hold them: n [G][128] int32 (0 past the
+ * root's edges), raw_total [G] int32 = S, both DEVICE.  Same inputs as cz_search_root_stats; the bans are those of the
+ * current cz_search_set_roots; c_puct is the object's, k its cz_search_set_forced_playouts setting (k = 0: the raw
+ * counts).  A root that is not in the tree reports zeros. */
+int cz_search_root_targets(cz_search* s, int32_t* n, int32_t* raw_total, void* stream);
+/* The pruning arithmetic on its own, one wavefront per row: labels / n / w / p [rows][128] and n_edges [rows] (<= 128),
+ * out_n [rows][128] (0 past n_edges), out_raw_total [rows], all DEVICE.  Labels of a row are distinct.  CZ_ERR_ARG: a
+ * NULL pointer, rows < 0, c_puct or k negative or not finite. */
+int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                           const uint8_t* n_edges, int rows, double c_puct, double k,
+                           int32_t* out_n, int32_t* out_raw_total, void* stream);
+
 /* external mode (CChessPlayer.action): set the position to search for each game.  boards [G][90];
  * turns [G] or NULL; no_act [G][32] + n_no_act [G] or NULL (at most 32 banned moves per game); increase_temp / enable_resign [G] or NULL;
  * select_mask [G] or NULL (only games with a non-zero byte are touched).  Trees are kept (subtree reuse).
@@ -292,11 +349,16 @@ typedef struct cz_visit_entry {
     uint16_t ply;                    /* turns when the move was chosen */
     uint8_t n_edges;
     uint8_t flags;                   /* bit 0: the player resigned at this ply; bit 1 (CZ_VISIT_FAST): the ply was a
-                                        fast search of the playout cap (cz_search_set_playout_cap) */
+                                        fast search of the playout cap (cz_search_set_playout_cap); bit 2
+                                        (CZ_VISIT_PRUNED): n[] holds the pruned policy targets, not the raw counts
+                                        (cz_search_set_forced_playouts) */
     int32_t sum_n;                   /* the root's own visit count */
-    uint32_t reserved;
+    uint32_t raw_total;              /* CZ_VISIT_PRUNED: sum of the RAW counts of the non-banned edges (S), so that
+                                        raw_total - sum of the non-banned n[] = visits pruned; otherwise 0 (this word
+                                        was `reserved`, always 0, before pruning existed) */
 } cz_visit_entry;
 #define CZ_VISIT_FAST 2u
+#define CZ_VISIT_PRUNED 4u
 /* Copies every entry written since the last call into HOST host_buf (784 bytes each) and frees their ring space;
  * *n_out = entries copied.  host_buf = NULL: *n_out = entries waiting, nothing is consumed.  CZ_ERR_ARG when more are
  * waiting than max_entries (nothing is consumed).  dropped_out (HOST, or NULL) = entries dropped since recording was

@@ -1,0 +1,513 @@
+"""-m gpu: forced playouts and policy target pruning (cz_search_set_forced_playouts, cz_search_root_targets,
+cz_policy_target_prune; run.py self --forced-playouts K --record-visits).
+
+The yardstick is tests/forced_playouts_oracle.py, a Python restatement of the reference's search for one search thread
+with the forcing rule and prune() in it; tests/test_forced_playouts_cpu.py pins it to the C oracle at k = 0.  Single
+searches, the pruning arithmetic and ply 0 of self-play are compared with it exactly; the later plies and K = 8 are held
+by invariants and by determinism.  With k = 0 the records, the visit entries and the counters are what they were."""
+import ctypes as C
+import json
+import logging
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import forced_playouts_oracle as fo
+import stub_net
+from oracle import xq_oracle as xo
+from test_gpu_book import GOLDEN, _engine_cfg
+from test_gpu_search import (assert_root_equal, boards_tensor, gpu, no_act_tensors, oracle_cfg, play_config,  # noqa: F401
+                             stub_eval)
+from test_gpu_trainer import window_of
+
+pytestmark = pytest.mark.gpu
+ERR_ARG = -1                                                # include/czero.h CZ_ERR_ARG
+SPEC = dict(kind="hash", salt=5)
+G = 32
+
+
+# ---- 1. off is off -----------------------------------------------------------------------------------------------------
+def _entry_key(e):
+    return (e.ply, e.moves.tolist(), e.n.tolist(), e.banned.tolist(), e.sum_n, e.resign, e.fast, e.pruned, e.raw_total)
+
+
+def _selfplay_raw(gpu, pc, seed, rounds, setup):
+    """The bytes of the finished-game records and of the visit entries, as the two device rings hand them out, and all
+    counters after a fixed number of rounds.  A record is its 16-byte header and the `turns` moves it holds; an entry its
+    16-byte header and the n_edges labels and counts it holds (the ring slot's other bytes belong to no entry).  Both
+    sorted: games that end in one launch reach the rings in any order."""
+    s = gpu.S.Search(pc, G, seed=seed)
+    setup(s)
+    s.record_visits(True)
+    ev = stub_eval(gpu, SPEC)
+    s.start_selfplay(seed=seed, first_game_id=0)
+    recs, entries = [], []
+    cur = C.c_uint(0)
+
+    def drain():
+        n = C.c_int(0)
+        buf = np.zeros((4096, s.record_stride), dtype=np.uint8)
+        gpu.N.check(s.L.cz_search_drain_records(s.h, C.byref(cur), buf.ctypes.data, 4096, C.byref(n), s._stream()), "drain")
+        for i in range(n.value):
+            turns = int(buf[i, 4:8].view(np.int32)[0])
+            recs.append(buf[i, :16 + 2 * turns].tobytes())
+        gpu.N.check(s.L.cz_search_drain_visits(s.h, None, 0, C.byref(n), None, s._stream()), "count")
+        vbuf = np.zeros((max(1, n.value), gpu.S.VISIT_STRIDE), dtype=np.uint8)
+        gpu.N.check(s.L.cz_search_drain_visits(s.h, vbuf.ctypes.data, n.value, C.byref(n), None, s._stream()), "visits")
+        for i in range(n.value):
+            ne = int(vbuf[i, 6])
+            entries.append(vbuf[i, :16 + 2 * ne].tobytes() + vbuf[i, 16 + 256:16 + 256 + 4 * ne].tobytes())
+    for r in range(rounds):
+        s.round()
+        p, v = ev(s.planes)
+        s.policy.copy_(p)
+        s.value.copy_(v)
+        if r % 16 == 15:                                    # (before either ring can fill)
+            drain()
+    drain()
+    ctr = s.counters()
+    s.close()
+    assert ctr["visits_dropped"] == 0
+    return sorted(recs), sorted(entries), ctr
+
+
+@pytest.mark.parametrize("K", [1, 8])
+def test_k_0_leaves_every_record_entry_and_counter(gpu, K):
+    pc = play_config(simulation_num_per_move=16, search_threads=K, tau_decay_rate=0.9, max_game_length=8,
+                     enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
+    rounds = 400 if K == 1 else 120
+    base, vis0, c0 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: None)
+    zero, vis1, c1 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.set_forced_playouts(0.0))
+    back, vis2, c2 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: (s.set_forced_playouts(2.0), s.set_forced_playouts(0.0)))
+    assert len(base) >= G and len(vis0) > len(base)
+    assert zero == base and back == base
+    assert vis1 == vis0 and vis2 == vis0
+    assert c0 == c1 == c2
+    for e in vis0:                                          # no CZ_VISIT_PRUNED, the header word stays 0
+        assert not e[7] & gpu.S.VISIT_PRUNED and e[12:16] == bytes(4)
+    # ... and k = 2 does change them: same seed
+    forced, vis3, c3 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.set_forced_playouts(2.0))
+    assert forced != base and vis3 != vis0
+    assert any(e[7] & gpu.S.VISIT_PRUNED and e[12:16] != bytes(4) for e in vis3)
+
+
+# ---- 2. single searches against the oracle -------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def oracle_runs():
+    """The oracle's searches of every case at k = 2, computed once."""
+    return [(c, fo.run_case(c, 2.0)) for c in fo.cases()]
+
+
+def test_single_searches_match_the_oracle(gpu, oracle_runs):
+    pc = play_config(simulation_num_per_move=fo.SIMS, search_threads=1, noise_eps=0.0, tau_decay_rate=0.0)
+    kinds = set()
+    for c, (res, osearch) in oracle_runs:
+        s = gpu.S.Search(pc, 1, seed=7)
+        s.set_forced_playouts(2.0)
+        ev = stub_eval(gpu, dict(kind="hash", salt=c["salt"]))
+        for r in res:
+            na, nn = no_act_tensors(gpu, [r["no_act"]])
+            s.set_roots(boards_tensor(gpu, [r["state"]]), no_act=na, n_no_act=nn)
+            s.run_until_idle(ev)
+            what = f"{c['name']} {r['state']}"
+            assert_root_equal(s.root_stats(), 0, r["stats"], what)
+            t = s.root_targets()
+            nm = len(r["targets"])
+            assert int(t["raw_total"][0]) == r["raw_total"], what
+            assert (t["n"][0, :nm] == r["targets"]).all(), (what, t["n"][0, :nm], r["targets"])
+            assert (t["n"][0, nm:] == 0).all(), what
+        ctr = s.counters()
+        for key in ("sims", "expansions", "terminal_sims", "repetition_sims"):
+            assert ctr[key] == getattr(osearch, key), (c["name"], key)
+        kinds.add(c["kind"])
+        kinds.add("wide" if len(res[0]["targets"]) > 64 else None)
+        # the same object with k = 0 reports the raw counts
+        s.set_forced_playouts(0.0)
+        t0, st = s.root_targets(), s.root_stats()
+        live = np.array([xo.label_str(int(m)) not in res[-1]["no_act"] for m in st["moves"][0, :nm]])
+        assert (t0["n"][0, :nm] == st["n"][0, :nm]).all() and int(t0["raw_total"][0]) == int(st["n"][0, :nm][live].sum())
+        s.close()
+    assert kinds >= {"ban", "reuse", "wide"}
+    assert sum(o.forced_picks > 0 for _, (_, o) in oracle_runs) * 2 >= len(oracle_runs)
+
+
+# ---- 3. the pruning arithmetic alone ---------------------------------------------------------------------------------------
+C_PUCT, K2 = 1.5, 2.0
+
+
+def _row(nm, n, q, p, labels=None, banned=()):
+    n = np.asarray(n, dtype=np.int32)
+    w = np.asarray(q, dtype=np.float64) * n
+    lab = np.arange(10, 10 + nm, dtype=np.uint16) if labels is None else np.asarray(labels, dtype=np.uint16)
+    lab = lab.copy()
+    for j in banned:
+        lab[j] |= fo.BANNED
+    return dict(labels=lab, n=n, w=w, p=np.asarray(p, dtype=np.float32))
+
+
+def _random_row(rng, nm, ban=0.0):
+    n = rng.integers(0, 60, nm) * (rng.random(nm) < 0.7)
+    p = rng.random(nm) ** 4
+    p = (p / p.sum()).astype(np.float32)
+    lab = rng.permutation(2086)[:nm]
+    return _row(nm, n, rng.uniform(-1, 1, nm), p, labels=lab, banned=np.flatnonzero(rng.random(nm) < ban))
+
+
+def _e_star(n, q, p, S):
+    return q + ((C_PUCT * float(np.float32(p))) * math.sqrt(float(S))) / float(1 + n)
+
+
+def _special_rows():
+    rng = np.random.default_rng(5)
+    rows = {}
+    for nm in (1, 2, 63, 64, 65, 127, 128):
+        rows[f"edges_{nm}"] = _random_row(rng, nm)
+    r = _random_row(rng, 100)
+    r["n"][80] = 500
+    rows["c_star_in_the_second_half"] = r
+    r = _random_row(rng, 40)
+    r["n"][[3, 30]] = 400                       # a tie: the lower LABEL is c*, here the later edge
+    r["labels"][3], r["labels"][30] = 2000, 7
+    r["labels"][[j for j in range(40) if j not in (3, 30)]] = np.arange(100, 138)
+    rows["tie"] = r
+    r = _random_row(rng, 50)
+    r["labels"] |= fo.BANNED
+    rows["all_banned"] = r
+    r = _random_row(rng, 50, ban=0.2)
+    r["n"][(r["labels"] & fo.BANNED) == 0] = 0
+    rows["S_0"] = r
+    # hand-made: edge 0 is c* (n 90, q 0.5, p 0.5), S = 100 with the edges below
+    n = [90, 3, 2, 1, 4]
+    q = [0.5, 5.0, -1.0, -1.0, 0.0]
+    p = [0.5, 0.3, 0.01, 0.001, 0.1]
+    e = _e_star(90, 0.5, 0.5, 100)
+    r = _row(5, n, q, p)
+    r["w"][4] = 4.0 * np.nextafter(e, -np.inf)  # q_4 one ulp below E*: the quotient is far above 2^31
+    rows["hand_made"] = r
+    return rows
+
+
+def test_policy_target_prune_alone(gpu):
+    t = gpu.torch
+    rows = _special_rows()
+    rng = np.random.default_rng(11)
+    for i in range(64):
+        rows[f"random_{i}"] = _random_row(rng, int(rng.integers(1, 129)), ban=0.1 * (i % 3))
+    names = list(rows)
+    R, M = len(names), 128
+    lab = np.zeros((R, M), dtype=np.uint16)
+    n = np.zeros((R, M), dtype=np.int32)
+    w = np.zeros((R, M), dtype=np.float64)
+    p = np.zeros((R, M), dtype=np.float32)
+    ne = np.zeros(R, dtype=np.uint8)
+    # past n_edges: values that would change the result if they were read
+    n[:], w[:], p[:] = 10 ** 6, 10.0 ** 6, 1.0
+    for i, name in enumerate(names):
+        r = rows[name]
+        k = len(r["n"])
+        ne[i] = k
+        lab[i, :k], n[i, :k], w[i, :k], p[i, :k] = r["labels"], r["n"], r["w"], r["p"]
+    out, raw = gpu.S.policy_target_prune(t.from_numpy(lab.view(np.int16)).cuda().view(t.uint16), t.from_numpy(n).cuda(),
+                                         t.from_numpy(w).cuda(), t.from_numpy(p).cuda(), t.from_numpy(ne).cuda(),
+                                         C_PUCT, K2)
+    out, raw = out.cpu().numpy(), raw.cpu().numpy()
+    want = {}
+    for i, name in enumerate(names):
+        r = rows[name]
+        k = len(r["n"])
+        want[name] = fo.prune(r["labels"], r["n"], r["w"], r["p"], C_PUCT, K2)
+        assert int(raw[i]) == want[name][1], name
+        assert (out[i, :k] == want[name][0]).all(), (name, out[i, :k], want[name][0])
+        assert (out[i, k:] == 0).all(), name
+    # the special rows are what their names say
+    r, (m, S) = rows["c_star_in_the_second_half"], want["c_star_in_the_second_half"]
+    assert m[80] == 500 and (m <= r["n"]).all() and m.sum() < r["n"].sum()
+    r, (m, S) = rows["tie"], want["tie"]
+    e3 = _e_star(400, r["w"][3] / 400, r["p"][3], S)
+    e30 = _e_star(400, r["w"][30] / 400, r["p"][30], S)
+    assert e3 != e30 and m[30] == 400                       # (which of the two is c* matters to every other edge)
+    assert (want["all_banned"][0] == rows["all_banned"]["n"]).all() and want["all_banned"][1] == 0
+    assert (want["S_0"][0] == rows["S_0"]["n"]).all() and want["S_0"][1] == 0
+    r, (m, S) = rows["hand_made"], want["hand_made"]
+    assert S == 100
+    assert m.tolist() == [90,       # c* keeps its count
+                          3,        # q_j >= E*: d_j <= 0, the edge keeps every visit
+                          0,        # need 0, f_j = 1: reduced to exactly 1, which is removed
+                          1,        # f_j = 0: an unreduced single visit stays
+                          4]        # d_j = one ulp: clamped in float64, not after the conversion
+    e = _e_star(90, 0.5, 0.5, 100)
+    d = e - r["w"][4] / 4.0
+    assert 0.0 < d and ((C_PUCT * float(np.float32(0.1))) * 10.0) / d > 2.0 ** 31
+    assert math.floor(math.sqrt((K2 * float(np.float32(0.01))) * 100.0)) == 1
+    assert math.floor(math.sqrt((K2 * float(np.float32(0.001))) * 100.0)) == 0
+    # arguments
+    L = gpu.N.lib()
+    a = [t.from_numpy(x).cuda() for x in (lab.view(np.int16), n, w, p, ne)]
+    ptr = [C.c_void_p(x.data_ptr()) for x in a] + [C.c_void_p(t.empty_like(a[1]).data_ptr()),
+                                                   C.c_void_p(t.empty(R, dtype=t.int32, device="cuda").data_ptr())]
+    st = C.c_void_p(t.cuda.current_stream().cuda_stream)
+    for bad_k in (-1.0, float("nan"), float("inf")):
+        assert L.cz_policy_target_prune(*ptr[:5], R, C_PUCT, bad_k, *ptr[5:], st) == ERR_ARG
+    assert L.cz_policy_target_prune(None, *ptr[1:5], R, C_PUCT, K2, *ptr[5:], st) == ERR_ARG
+    assert L.cz_policy_target_prune(*ptr[:5], -1, C_PUCT, K2, *ptr[5:], st) == ERR_ARG
+    assert L.cz_policy_target_prune(*ptr[:5], 0, C_PUCT, K2, *ptr[5:], st) == 0
+
+
+# ---- self-play helpers -----------------------------------------------------------------------------------------------------
+def _book():
+    from cchess_alphazero.lib.book import load_book
+
+    class _OracleRules:
+        @staticmethod
+        def check(states):
+            return [xo.done(s)[0] for s in states], [xo.has_attack_chessman(s) for s in states]
+    return load_book(os.path.join(GOLDEN, "book.txt"), rules=_OracleRules)
+
+
+def _play(gpu, pc, seed, k, max_rounds=60000, **kw):
+    """Self-play through SelfPlayEngine with the stub evaluator and the visit record until every slot has finished a game."""
+    from cchess_alphazero.engine import SelfPlayEngine
+    eng = SelfPlayEngine(_engine_cfg(pc), G, evaluator=stub_eval(gpu, SPEC), seed=seed, record_visits=True,
+                         forced_playouts=k, **kw)
+    i_games = gpu.S.COUNTER_NAMES.index("games")
+    games = []
+    try:
+        eng.start(0, 0)
+        for r in range(max_rounds):
+            eng.step()
+            if r % 16 == 15:
+                games += eng.drain()
+                if eng.search.game_counters()[:, i_games].min() >= 1:
+                    break
+        else:
+            raise AssertionError(f"not finished after {max_rounds} rounds: {len(games)} games")
+        games += eng.drain()
+        ctr = eng.counters()
+    finally:
+        eng.close()
+    assert len({g["game_id"] for g in games}) == len(games) >= G
+    return sorted(games, key=lambda g: g["game_id"]), ctr
+
+
+# ---- 4. self-play, ply 0 exactly ---------------------------------------------------------------------------------------
+def test_selfplay_ply_0_matches_the_oracle(gpu):
+    book = _book()
+    pc = play_config(simulation_num_per_move=120, search_threads=1, noise_eps=0.0, tau_decay_rate=0.0, max_game_length=1)
+    games, ctr = _play(gpu, pc, 3, 2.0, book=book, book_rate=1.0)
+    assert ctr["tree_resets"] == 0 and ctr["overflow_sims"] == 0 and ctr["visits_dropped"] == 0
+    want = {}
+    pruned_somewhere = 0
+    for g in games[:G]:
+        assert g["game_id"] < G and g["book_index"] == g["game_id"] % len(book)
+        state = book[g["book_index"]]
+        if state not in want:
+            o = fo.Search(fo.play_cfg(120), SPEC["salt"], 2.0)
+            o.search(state)
+            want[state] = (o.node_stats(state), o.targets(state), o.best_move(state))
+        st, (targets, raw), best = want[state]
+        e = g["visits"][0]
+        assert g["data"][0] == state and e.ply == 0 and not e.fast and not e.banned.any()
+        assert e.pruned and e.raw_total == raw == int(st["n"].sum()), g["game_id"]
+        assert e.sum_n == st["sum_n"] and (e.moves == st["moves"]).all()
+        assert (e.n == targets).all(), (g["game_id"], e.n, targets)
+        assert g["data"][1][0] == best, g["game_id"]
+        pruned_somewhere += int(raw > targets.sum())
+    assert len(want) == min(G, len(book)) and pruned_somewhere > 0
+
+
+# ---- 5. self-play, every ply, by invariant -------------------------------------------------------------------------------
+def _check_invariants(games, pc, capped):
+    n_pruned = n_fast = removed = 0
+    for g in games:
+        vis = g["visits"]
+        assert vis is not None
+        moves = [it[0] for it in g["data"][1:]]
+        state, seen = g["data"][0], []
+        for i, e in enumerate(vis):
+            live = ~e.banned
+            assert e.ply == i
+            if e.fast:
+                assert capped and not e.pruned and e.raw_total == 0
+                n_fast += 1
+            else:
+                assert e.pruned == (int(e.n[live].sum()) > 0), (g["game_id"], i)
+            if e.pruned:                                        # (so at least one edge is not banned)
+                n_pruned += 1
+                total = int(e.n[live].sum())
+                assert 0 < total <= e.raw_total <= e.sum_n, (g["game_id"], i)
+                removed += e.raw_total - total
+                # the greatest count is unique, or c* is the first of the greatest in label order
+                top = np.flatnonzero(live & (e.n == e.n[live].max()))
+                star = top[np.argmin(e.moves[top])]
+                tau = pc.tau_decay_rate ** (i + 1) if i < 30 and pc.tau_decay_rate else 0.0
+                if tau < 0.1 and state not in seen and not e.resign:        # tau = 0 (a repeated position may raise it)
+                    assert xo.label_str(int(e.moves[star])) == moves[i], (g["game_id"], i)
+            if not e.resign:
+                seen.append(state)
+                state = xo.step(state, moves[i])
+        assert g["pruned_visits"] == sum(e.raw_total - int(e.n[~e.banned].sum()) for e in vis if e.pruned)
+    return n_pruned, n_fast, removed
+
+
+@pytest.mark.parametrize("K,noise_eps,fast_sims", [(1, 0.0, 0), (8, 0.25, 0), (8, 0.0, 12)])
+def test_selfplay_invariants_and_determinism(gpu, K, noise_eps, fast_sims):
+    pc = play_config(simulation_num_per_move=48, search_threads=K, noise_eps=noise_eps, tau_decay_rate=0.6,
+                     max_game_length=6, enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
+    kw = dict(fast_sims=fast_sims, full_rate=0.5) if fast_sims else {}
+    games, ctr = _play(gpu, pc, 17, 2.0, **kw)
+    assert ctr["tree_resets"] == 0 and ctr["overflow_sims"] == 0 and ctr["visits_dropped"] == 0
+    n_pruned, n_fast, removed = _check_invariants(games, pc, bool(fast_sims))
+    print(f"K={K} eps={noise_eps} fast_sims={fast_sims}: {len(games)} games, {n_pruned} pruned entries, {n_fast} fast, "
+          f"{removed} visits removed")
+    assert n_pruned > 0 and removed > 0 and (n_fast > 0) == bool(fast_sims)
+    again, ctr2 = _play(gpu, pc, 17, 2.0, **kw)
+    # (a run stops at a drain after every slot finished a game: both runs stop at the same round)
+    assert [(g["game_id"], g["data"], [_entry_key(e) for e in g["visits"]]) for g in again] == \
+           [(g["game_id"], g["data"], [_entry_key(e) for e in g["visits"]]) for g in games]
+    assert ctr2 == ctr
+
+
+# ---- 6. records reach the trainer ------------------------------------------------------------------------------------------
+def test_pruned_records_reach_the_trainer(gpu):
+    t = gpu.torch
+    pc = play_config(simulation_num_per_move=48, search_threads=4, noise_eps=0.25, tau_decay_rate=0.6, max_game_length=6)
+    games, _ = _play(gpu, pc, 23, 2.0)
+    assert sum(g["pruned_visits"] for g in games) > 0
+    data = [g["data"] for g in games if g["turns"] > 0]
+    assert json.loads(json.dumps(data)) == data
+    for g in games:                                             # pi is the pruned entry, zero counts omitted
+        for item, e in zip(g["data"][1:], g["visits"]):
+            if len(item) >= 3:
+                assert e.pruned and sorted(c for _, c in item[2]) == sorted(int(c) for c in e.n[~e.banned] if c > 0)
+        assert g["pruned_visits"] == sum(e.raw_total - int(e.n[~e.banned].sum()) for e in g["visits"] if e.pruned)
+    win = window_of(data)
+    m = len(win)
+    assert m == sum(len(d) - 1 for d in data) and win.trainable.all()
+    dense = win.dense_targets(np.arange(m), "visits")
+    # float32 quotients of at most 128 edges: each within 2^-24 relative, so the sum is within 128 * 2^-24 of 1
+    assert np.abs(dense.astype(np.float64).sum(axis=1) - 1.0).max() <= 128 * 2.0 ** -24
+    # the loss kernel on uniform logits: -sum t log softmax = log(2086) * sum t, per row
+    idx = t.arange(m, dtype=t.int32, device="cuda")
+    logits = t.zeros((m, 2086), dtype=t.float32, device="cuda")
+    pl, _, gl, _ = gpu.N.policy_value_loss(logits, t.zeros(m, dtype=t.float32, device="cuda"), idx, win.played[:m],
+                                           win.z[:m], win.row_ptr[:m + 1], win.vis_label[:win.nnz],
+                                           win.vis_count[:win.nnz], 1, 1.0, 1.0)
+    # float32 throughout: log(2086) = 7.64 to 2^-24 relative, times a sum of <= 128 targets as above
+    assert np.abs(pl.cpu().numpy().astype(np.float64) / math.log(2086.0) - 1.0).max() <= 256 * 2.0 ** -24
+    # d loss / d logits = (softmax - t) / m: its rows sum to (1 - sum t) / m
+    assert np.abs(gl.cpu().numpy().astype(np.float64).sum(axis=1)).max() * m <= 4096 * 2.0 ** -24
+
+
+# ---- 7. arguments, and the callers that never force ------------------------------------------------------------------------
+def test_setter_argument_errors_leave_the_setting(gpu):
+    pc = play_config(simulation_num_per_move=16, search_threads=4, max_game_length=6)
+    s = gpu.S.Search(pc, 2, seed=1)
+    st = s._stream()
+    s.set_forced_playouts(2.0)
+    for bad in (-1.0, -1e-300, float("nan"), float("inf"), float("-inf")):
+        assert s.L.cz_search_set_forced_playouts(s.h, bad, st) == ERR_ARG, bad
+    assert s.L.cz_search_set_forced_playouts(None, 2.0, st) == ERR_ARG
+    with pytest.raises(gpu.N.NativeError):
+        s.set_forced_playouts(-2.0)
+    assert s.forced_k == 2.0
+    s.close()
+    # the engine refuses forcing without the visit record: the pruned counts would have nowhere to go
+    from cchess_alphazero.engine import SelfPlayEngine
+    with pytest.raises(ValueError, match="record_visits"):
+        SelfPlayEngine(_engine_cfg(pc), 2, evaluator=stub_eval(gpu, SPEC), forced_playouts=2.0)
+    # and on the device: after a refused call the object still forces with k = 2, its search is the oracle's forced one
+    c = fo.cases()[0]
+    ev = stub_eval(gpu, dict(kind="hash", salt=c["salt"]))
+    s = gpu.S.Search(play_config(simulation_num_per_move=fo.SIMS, search_threads=1), 1, seed=1)
+    s.set_forced_playouts(2.0)
+    assert s.L.cz_search_set_forced_playouts(s.h, -1.0, s._stream()) == ERR_ARG
+    s.set_roots(boards_tensor(gpu, [c["state"]]))
+    s.run_until_idle(ev)
+    res, _ = fo.run_case(c, 2.0)
+    assert_root_equal(s.root_stats(), 0, res[0]["stats"], "k stays 2 after the refused calls")
+    s.close()
+
+
+def test_player_facade_is_untouched_by_a_forced_selfplay_run(gpu, tmp_path, monkeypatch):
+    """CChessPlayer never sets k: after a forced self-play run on another object its search is the oracle's, bit for bit."""
+    from cchess_alphazero.agent.player import CChessPlayer
+    from cchess_alphazero.config import Config
+    pc = play_config(simulation_num_per_move=24, search_threads=4, max_game_length=3)
+    games, _ = _play(gpu, pc, 5, 2.0)
+    assert any(e.pruned for g in games for e in g["visits"])
+    monkeypatch.setenv("DATA_DIR", str(tmp_path / "data"))
+    monkeypatch.setenv("PROJECT_DIR", str(tmp_path))
+    cfg = Config("mini")
+    c = fo.cases()[1]
+    for k, v in dict(simulation_num_per_move=fo.SIMS, search_threads=1, noise_eps=0, tau_decay_rate=0, c_puct=1.5).items():
+        setattr(cfg.play, k, v)
+    pl = CChessPlayer(cfg, search_tree=None, pipes=stub_net.StubPipe(lambda p: stub_net.hash_stub_numpy(p, c["salt"])),
+                      enable_resign=False)
+    pl.action(c["state"], 0, None)
+    node = pl.tree[c["state"]]
+    ref = xo.Player(fo.play_cfg(), dict(kind="hash", salt=c["salt"]))
+    ref.search(c["state"])
+    st = ref.node_stats(c["state"])
+    assert [xo.label_of_str(m) for m in node.legal_moves] == st["moves"].tolist()
+    assert [node.a[m].n for m in node.legal_moves] == st["n"].tolist() and node.sum_n == st["sum_n"]
+    assert np.array([node.a[m].w for m in node.legal_moves], dtype=np.float64).tobytes() == st["w"].tobytes()
+    forced, _ = fo.run_case(c, 2.0)
+    assert forced[0]["stats"]["n"].tolist() != st["n"].tolist()             # (forcing would have shown)
+    pl.close()
+    ref.close()
+
+
+# ---- 8. the command line -----------------------------------------------------------------------------------------------
+def test_run_py_self_with_forced_playouts_then_opt(tmp_path, monkeypatch):
+    from cchess_alphazero import manager
+    from cchess_alphazero.agent.model import CChessModel
+    from cchess_alphazero.lib.data_helper import get_game_data_filenames, read_game_data_from_file
+    from cchess_alphazero.lib.record_decoder import split_games
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, "chinesechess-alphazero_amd")
+    env = dict(os.environ, DATA_DIR=str(tmp_path / "data"), PROJECT_DIR=str(tmp_path), PYTHONPATH=pkg)
+    run = [sys.executable, os.path.join(pkg, "cchess_alphazero", "run.py"), "self", "--type", "mini"]
+    r = subprocess.run(run + ["--forced-playouts", "2"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "needs --record-visits" in r.stderr
+    r = subprocess.run(run + ["--games-per-gpu", "32", "--forced-playouts", "2", "--record-visits", "--max-games", "8"],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with open(tmp_path / "logs" / "play.log") as f:
+        log = f.read()
+    assert "forced playouts k = 2.0" in log
+    m = re.search(r"policy target pruning removed (\d+) of (\d+) root visits", log)
+    assert m and 0 < int(m.group(1)) < int(m.group(2))
+    monkeypatch.setenv("DATA_DIR", str(tmp_path / "data"))
+    monkeypatch.setenv("PROJECT_DIR", str(tmp_path))
+    build = manager.build_config
+
+    def small(args):                                        # the command line's config at test size
+        cfg = build(args)
+        cfg.model.cnn_filter_num, cfg.model.res_layer_num = 32, 2
+        cfg.trainer.batch_size = 16
+        return cfg
+    monkeypatch.setattr(manager, "build_config", small)
+    cfg = small(manager.create_parser().parse_args(["opt"]))
+    rc = cfg.resource
+    files = get_game_data_filenames(rc)
+    assert files
+    items = [it for p in files for g in split_games(read_game_data_from_file(p)) for it in g[1:]]
+    assert any(len(it) == 3 and it[2] for it in items) and not any(len(it) == 4 for it in items)
+    model = CChessModel(cfg)
+    model.build(seed=0)
+    model.save(rc.model_best_config_path, rc.model_best_weight_path)
+    monkeypatch.setattr(sys, "argv", ["run.py", "opt", "--type", "mini", "--policy-targets", "visits"])
+    handlers, level = list(logging.getLogger().handlers), logging.getLogger().level
+    try:
+        total = manager.start()
+    finally:
+        logging.getLogger().setLevel(level)
+        for h in logging.getLogger().handlers[len(handlers):]:
+            logging.getLogger().removeHandler(h)
+            h.close()
+    assert total > 0
