@@ -26,8 +26,9 @@ VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
 # was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
 # search of the playout cap (set_playout_cap); whether n holds the PRUNED counts of set_forced_playouts, and then
-# raw_total, the sum of the raw counts of the non-banned edges (0 otherwise).
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total")
+# raw_total, the sum of the raw counts of the non-banned edges (0 otherwise); q, the root's search value of the ply
+# (record_values; None with the value record off and where the ring held NaN, "no value").
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q", defaults=(None,))
 
 
 class SearchCfg(C.Structure):
@@ -90,6 +91,15 @@ def declare(L):
     if hasattr(L, "cz_policy_target_prune"):
         L.cz_policy_target_prune.argtypes = [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp]
         L.cz_policy_target_prune.restype = i32
+    if hasattr(L, "cz_search_record_values"):
+        L.cz_search_record_values.argtypes = [vp, i32, vp]
+        L.cz_search_record_values.restype = i32
+        L.cz_search_drain_visits_q.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
+        L.cz_search_drain_visits_q.restype = i32
+        L.cz_search_root_value.argtypes = [vp, vp, vp]
+        L.cz_search_root_value.restype = i32
+        L.cz_root_value.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
+        L.cz_root_value.restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -181,6 +191,7 @@ class Search:
         self.planes_off = False                # leaf_planes(False): new leaves are written as occupancy boards only
         self._cursor = C.c_uint(0)
         self.visit_capacity = 0                # record_visits(): entries the device ring holds, 0 = off
+        self.values_on = False                 # record_values(): every entry comes with the root's search value
         self._visits = {}                      # game id -> [(ply, raw entry)] of games not finished yet
         self._raw_visits = []                  # fetched entries not yet sorted by game (pull_visits(defer=True))
         self._visits_dropped = 0
@@ -255,6 +266,7 @@ class Search:
         _native.check(self.L.cz_search_record_visits(self.h, int(bool(on)), int(capacity), self._stream()),
                       "cz_search_record_visits")
         self.visit_capacity = (int(capacity) or 64 * self.G) if on else 0
+        self.values_on = False                 # (the library frees the value ring with the visit ring)
         self._visits = {}
         self._raw_visits = []
         self._visits_dropped = 0
@@ -293,6 +305,23 @@ class Search:
                       "cz_search_set_forced_playouts")
         self.forced_k = float(k)
 
+    def record_values(self, on=True):
+        """Self-play: every visit entry comes with the root's search value q (cz_search_record_values; include/czero.h has
+        the arithmetic): VisitEntry.q, None where the root had no value.  Needs record_visits() on, and a later
+        record_visits() call switches it off again.  Call it before start_selfplay() and before a graph capture.  Entries
+        fetched before the switch keep what they had."""
+        _native.check(self.L.cz_search_record_values(self.h, int(bool(on)), self._stream()), "cz_search_record_values")
+        self.values_on = bool(on)
+
+    def root_value(self):
+        """The search value of every current root, as a visit entry of that root would carry it (cz_search_root_value;
+        bans of the current set_roots, the counts of root_targets as weights): float64 [G], NaN = no value."""
+        import torch
+        q = torch.empty((self.G,), dtype=torch.float64, device=self.device)
+        _native.check(self.L.cz_search_root_value(self.h, C.c_void_p(q.data_ptr()), self._stream()),
+                      "cz_search_root_value")
+        return q.cpu().numpy()
+
     def root_targets(self):
         """The pruned counts of every current root (cz_search_root_targets; edge order of root_stats, bans of the current
         set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
@@ -318,10 +347,16 @@ class Search:
                 self.ingest_visits()
             return 0
         buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
-        _native.check(self.L.cz_search_drain_visits(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(dropped),
-                                                    self._stream()), "cz_search_drain_visits")
+        q = None
+        if self.values_on:
+            q = np.empty((n.value,), dtype=np.float64)
+            _native.check(self.L.cz_search_drain_visits_q(self.h, buf.ctypes.data, q.ctypes.data, n.value, C.byref(n),
+                                                          C.byref(dropped), self._stream()), "cz_search_drain_visits_q")
+        else:
+            _native.check(self.L.cz_search_drain_visits(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(dropped),
+                                                        self._stream()), "cz_search_drain_visits")
         self._visits_dropped = int(dropped.value)
-        self._raw_visits.append(buf)
+        self._raw_visits.append((buf, q))
         if not defer:
             self.ingest_visits()
         return n.value
@@ -329,12 +364,14 @@ class Search:
     def ingest_visits(self):
         """Sort the entries fetched by pull_visits(defer=True) by game."""
         raw, self._raw_visits = self._raw_visits, []
-        for buf in raw:
+        for buf, q in raw:
             gids = buf[:, 0:4].copy().view(np.uint32)[:, 0]
             plies = buf[:, 4:6].copy().view(np.uint16)[:, 0]
             for i in range(buf.shape[0]):      # kept trimmed to the root's edges until the game's record arrives
                 ne = int(buf[i, 6])
                 row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
+                if q is not None:              # the entry's value rides behind its edges
+                    row += q[i:i + 1].tobytes()
                 self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
 
     def waiting_visits(self):
@@ -347,14 +384,19 @@ class Search:
 
     @staticmethod
     def parse_visit_entry(row):
-        """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges]) -> VisitEntry."""
+        """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges], then with the value
+        record on its float64 q) -> VisitEntry."""
         a = np.frombuffer(row, dtype=np.uint8)
         ne = int(a[6])
+        q = None
+        if len(a) == 24 + 6 * ne:
+            q = float(a[16 + 6 * ne:].view(np.float64)[0])
+            q = None if q != q else q
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
-                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]))
+                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q)
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -611,3 +653,27 @@ def policy_target_prune(labels, n, w, p, n_edges, c_puct, k):
         C.c_void_p(n_edges.data_ptr()), rows, float(c_puct), float(k), C.c_void_p(out.data_ptr()),
         C.c_void_p(raw.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_policy_target_prune")
     return out, raw
+
+
+def root_value_rows(labels, m, n, w, n_edges):
+    """cz_root_value: the root-value arithmetic of record_values on caller-supplied rows.  labels uint16 (bit 15 = banned),
+    m int32 (the recorded counts), n int32 and w float64 (the raw statistics), all [rows, 128] cuda tensors; n_edges uint8
+    [rows].  Returns float64 [rows] on the device, NaN = no value."""
+    import torch
+    _native.require_gpu()
+    rows = int(n_edges.numel())
+    want = ((labels, torch.uint16), (m, torch.int32), (n, torch.int32), (w, torch.float64))
+    for t, dt in want:
+        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"root_value_rows: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
+    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
+        raise ValueError("root_value_rows: n_edges must be a contiguous cuda uint8 tensor")
+    out = torch.empty((rows,), dtype=torch.float64, device=n.device)
+    _native.check(_native.lib().cz_root_value(
+        C.c_void_p(labels.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(w.data_ptr()),
+        C.c_void_p(n_edges.data_ptr()), rows, C.c_void_p(out.data_ptr()),
+        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_root_value")
+    return out
+
+
+Search.root_value_rows = staticmethod(root_value_rows)

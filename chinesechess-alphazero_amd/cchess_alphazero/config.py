@@ -101,6 +101,8 @@ class EngineConfig(_Section):
                          forced_playouts=0.0,     # forced playouts + policy target pruning (run.py self --forced-playouts
                                                   # K, needs record_visits): a tried root child gets at least
                                                   # sqrt(K * p * N) visits, the recorded counts are pruned; 0 = off
+                         record_q=False,          # play records carry each searched ply's root search value (run.py self
+                                                  # --record-q, needs record_visits): items [move, value, pi, weight, q]
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

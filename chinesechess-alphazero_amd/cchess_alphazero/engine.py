@@ -22,7 +22,7 @@ from cchess_alphazero._native_search import Search
 from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE
-from cchess_alphazero.lib.data_helper import pi_from_visits
+from cchess_alphazero.lib.data_helper import record_item
 
 logger = getLogger(__name__)
 
@@ -42,7 +42,7 @@ class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
-                 full_rate=None, forced_playouts=None):
+                 full_rate=None, forced_playouts=None, record_q=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -56,7 +56,9 @@ class SelfPlayEngine:
         whose record item carries the training weight 0 (drain).
         forced_playouts: k of forced playouts and policy target pruning (None = config.engine.forced_playouts; 0 = off):
         on full plies a tried root child is visited at least sqrt(k * p * N) times, and the recorded visit counts -- the
-        pi of drain()'s items -- are the pruned ones (include/czero.h).  The moves are chosen from the raw counts."""
+        pi of drain()'s items -- are the pruned ones (include/czero.h).  The moves are chosen from the raw counts.
+        record_q: every searched ply's root search value goes into the records (None = config.engine.record_q; needs
+        record_visits): drain()'s items become [move, value, pi or None, weight, q] (cz_search_record_values)."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -122,6 +124,11 @@ class SelfPlayEngine:
                              "what a trainer sees")
         if self.forced_playouts:                               # likewise
             self.search.set_forced_playouts(self.forced_playouts)
+        self.record_q = bool(getattr(ec, "record_q", False) if record_q is None else record_q)
+        if self.record_q and not self.record_visits:
+            raise ValueError("record_q needs record_visits: the search values ride beside the visit entries")
+        if self.record_q:                                      # likewise
+            self.search.record_values(True)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -315,7 +322,10 @@ class SelfPlayEngine:
         element 3 is the row's training weight (lib/replay_window.py keeps the position, the trainer skips the row).  A
         full ply's item is unchanged.  `fast_plies` counts the game's fast plies.  With forced playouts
         pi comes from the pruned counts; `pruned_visits` is the number of root visits pruning removed from the game's
-        entries, sum of raw_total - sum of the non-banned pruned counts (0 without forced playouts)."""
+        entries, sum of raw_total - sum of the non-banned pruned counts (0 without forced playouts).  With record_q the
+        item of every ply that has a visit entry is [move, value, pi or None, weight, q] (lib/data_helper.py record_item):
+        weight 1 on a full ply and 0 on a fast one, q the root's search value rounded to 6 places or None; the appended
+        king capture, a resignation and games whose visit record is incomplete keep the shorter forms."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
@@ -323,13 +333,9 @@ class SelfPlayEngine:
             bi = r["book_index"]
             data = [INIT_STATE if bi is None else self.book[bi]]
             for i, m in enumerate(r["moves"]):
-                item = [ActionLabelsRed[int(m)], v if i % 2 == 0 else -v]
-                if vis is not None and i < len(vis) and not vis[i].resign:
-                    e = vis[i]
-                    item.append(pi_from_visits(e.moves, e.n, e.banned, ActionLabelsRed))
-                if r["fast"][i]:
-                    item += [None] * (3 - len(item)) + [0]
-                data.append(item)
+                e = vis[i] if vis is not None and i < len(vis) and not vis[i].resign else None
+                data.append(record_item(ActionLabelsRed[int(m)], v if i % 2 == 0 else -v, e, r["fast"][i], self.record_q,
+                                        ActionLabelsRed))
             pruned = [e for e in vis or [] if e.pruned]
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
                             resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]),

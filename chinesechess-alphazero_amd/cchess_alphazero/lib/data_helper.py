@@ -5,7 +5,10 @@ concatenated into one flat list, as the reference does).
 
 With ``engine.record_visits`` on, a searched move's item is ``[move, value, pi]``: pi = ``[[move, count], ...]``, the
 root's visit counts when the move was chosen (see ``pi_from_visits``).  The reference's trainer reads only ``item[0]``
-and ``item[1]`` (worker/optimize.py:245-246), so such files feed it unchanged."""
+and ``item[1]`` (worker/optimize.py:245-246), so such files feed it unchanged.
+
+With a playout cap the item of a fast ply is ``[move, value, pi or None, 0]``; with ``engine.record_q`` on every searched
+ply's item is ``[move, value, pi or None, weight, q]`` (``record_item``)."""
 import json
 import os
 from datetime import datetime, timedelta, timezone
@@ -21,6 +24,33 @@ def pi_from_visits(moves, n, banned, labels):
     policy calc_policy returns (agent/player.py:375-406: banned edges zeroed, then normalised).  labels: label index ->
     move string (ActionLabelsRed; the moves are in the mover's frame, like the record's moves)."""
     return [[labels[int(m)], int(c)] for m, c, b in zip(moves, n, banned) if not b and int(c) > 0]
+
+
+def record_item(move, value, entry=None, fast=False, record_q=False, labels=None):
+    """One ply's record item (engine.py drain).  entry: the ply's VisitEntry, or None where the ply has none to show (the
+    appended king capture, a resignation, a game whose visit record is incomplete).
+      [move, value]                          no entry, a full ply
+      [move, value, pi]                      an entry (pi_from_visits)
+      [move, value, pi or None, 0]           a fast ply of the playout cap: training weight 0
+      [move, value, pi or None, weight, q]   record_q on and an entry: weight 1 on a full ply, 0 on a fast one;
+                                             q = round(entry.q, 6), None where the root had no value
+    Without an entry record_q changes nothing, and with record_q off the items are what they were."""
+    item = [move, value]
+    if entry is not None:
+        item.append(pi_from_visits(entry.moves, entry.n, entry.banned, labels))
+    if fast:
+        item += [None] * (3 - len(item)) + [0]
+    if record_q and entry is not None:
+        if not fast:
+            item.append(1)
+        item.append(None if entry.q is None else round(float(entry.q), 6))
+    return item
+
+
+def mean_abs_q_minus_z(data):
+    """(sum of |q - z|, count) over the items of one game's record list that carry a q (self-play's log line)."""
+    d = [abs(it[4] - it[1]) for it in data[1:] if len(it) >= 5 and it[4] is not None]
+    return sum(d), len(d)
 
 
 def get_game_data_filenames(rc):

@@ -2,8 +2,8 @@
 
 The reference keeps its window as dense float32 arrays, 14 x 90 planes plus 2086 policy values per position
 (worker/optimize.py:261-281, about 13.4 KB a position).  Here a position costs its 90-byte board, the index of the
-position two plies back, the played label, the value and its visit counts in CSR form (about 100 B plus 6 B per visited
-edge); the minibatch's planes are built when it is drawn (``cz_gather_planes``) and the loss reads the sparse targets
+position two plies back, the played label, the value, the root's search value q (float32, NaN where the record has
+none) and its visit counts in CSR form (about 104 B plus 6 B per visited edge); the minibatch's planes are built when it is drawn (``cz_gather_planes``) and the loss reads the sparse targets
 directly (``cz_policy_value_loss``), so neither planes nor dense targets exist for the whole window.
 
 Record files are replayed on the device, one wavefront per game (``cz_replay_games``): the boards are those of
@@ -28,6 +28,22 @@ logger = getLogger(__name__)
 _LABEL = {m: i for i, m in enumerate(ActionLabelsRed)}
 MODES = {"played": 0, "visits": 1}
 INT32_MAX = 2 ** 31 - 1         # positions and visit entries are indexed with int32 (prev, row_ptr, the kernels' counts)
+Q_BOUND = 2.0                   # |q| of a record item: every value the search backs up is a network value in [-1, 1] or a
+                                # terminal one, done.v * 2 = +-2 (csrc/xq_search.hip backup), so every edge's w / n and their
+                                # weighted mean lie in [-2, 2]
+
+
+def mix_targets(z, q, q_ratio):
+    """The value targets of cz_policy_value_loss_q on the host: t = z + L * (q - z) in float32, a rounded difference, a
+    rounded product and a rounded sum; t = z where q is NaN.  z, q: float32 arrays."""
+    z = np.asarray(z, dtype=np.float32)
+    q = np.asarray(q, dtype=np.float32)
+    lam = np.float32(q_ratio)
+    if lam == 0:
+        return z.copy()
+    with np.errstate(invalid="ignore"):
+        t = z + lam * (q - z)
+    return np.where(np.isnan(q), z, t).astype(np.float32)
 
 
 class ReplayWindow:
@@ -54,6 +70,7 @@ class ReplayWindow:
         self.prev = torch.empty((n,), dtype=torch.int32, device=d)
         self.played = torch.empty((n,), dtype=torch.uint16, device=d)
         self.z = torch.empty((n,), dtype=torch.float32, device=d)
+        self.q = torch.empty((n,), dtype=torch.float32, device=d)
         self.row_ptr = torch.zeros((n + 1,), dtype=torch.int32, device=d)
         self.vis_label = torch.empty((nnz,), dtype=torch.uint16, device=d)
         self.vis_count = torch.empty((nnz,), dtype=torch.int32, device=d)
@@ -63,7 +80,7 @@ class ReplayWindow:
         (the file that crosses the capacity gets exactly the room it needs), visit entries double up to INT32_MAX."""
         if n > self.boards.shape[0]:
             cap = min(self.capacity, max(n, 1 << 16, 2 * self.boards.shape[0])) if n <= self.capacity else n
-            for name in ("boards", "prev", "played", "z"):
+            for name in ("boards", "prev", "played", "z", "q"):
                 old = getattr(self, name)
                 new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
                 new[:self.n] = old[:self.n]
@@ -110,7 +127,9 @@ class ReplayWindow:
         with weight 0 or 1 (engine.py drain: 0 = a fast ply of the playout cap): the position is kept like every other --
         history planes and ``prev`` links run through it -- and ``trainable`` is 0 for it.  Raises ValueError (naming the
         game and the ply) for a move that is not a label or whose from-square is empty, for a weight other than 0 or 1,
-        and for items that are not of these forms; the window is unchanged then.  The window holds at most INT32_MAX
+        and for items that are not of these forms; the window is unchanged then.  A fifth element is the root's search
+        value q of the ply (engine.py drain with record_q): None or a finite number in [-Q_BOUND, Q_BOUND], anything else
+        raises the same ValueError; ``q`` holds NaN for None, for shorter items and so for every older record.  The window holds at most INT32_MAX
         positions and INT32_MAX visit entries (int32 indices: about 24 visited edges per position at `distribute`'s 90 M
         positions); a load beyond either raises ValueError."""
         where = f" in {source}" if source else ""
@@ -126,6 +145,7 @@ class ReplayWindow:
         vals = np.empty(P, dtype=np.float32)
         nvis = np.zeros(P, dtype=np.int64)
         train = np.ones(P, dtype=np.uint8)
+        qs = np.full(P, np.nan, dtype=np.float32)
         vl, vc = [], []
         k = 0
         lookup = _LABEL
@@ -144,6 +164,12 @@ class ReplayWindow:
                         if isinstance(w, bool) or not isinstance(w, (int, float)) or w not in (0, 1):
                             raise ValueError(f"Training weight {w!r}: expected 0 or 1 (game {gi}, ply {t}){where}")
                         train[k] = int(w)
+                    if len(item) >= 5 and item[4] is not None:
+                        q = item[4]
+                        if isinstance(q, bool) or not isinstance(q, (int, float)) or not -Q_BOUND <= q <= Q_BOUND:
+                            raise ValueError(f"Search value {q!r}: expected None or a finite number in "
+                                             f"[-{Q_BOUND:g}, {Q_BOUND:g}] (game {gi}, ply {t}){where}")
+                        qs[k] = q
                     if len(item) >= 3 and not (len(item) >= 4 and item[2] is None):
                         pi = item[2]
                         for mv, c in pi:
@@ -179,6 +205,7 @@ class ReplayWindow:
         self.prev[n0:n0 + P] = torch.where(prev >= 0, prev + n0, prev)
         self.played[n0:n0 + P] = torch.from_numpy(labels).to(dev)
         self.z[n0:n0 + P] = torch.from_numpy(vals).to(dev)
+        self.q[n0:n0 + P] = torch.from_numpy(qs).to(dev)
         rp = (z0 + np.cumsum(nvis)).astype(np.int32)
         self.row_ptr[n0 + 1:n0 + P + 1] = torch.from_numpy(rp).to(dev)
         if nnz:
@@ -198,11 +225,18 @@ class ReplayWindow:
         device, or None: a row with a nonzero flag is the left-right mirrored position (cz_gather_planes_m)."""
         return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth, mirror=mirror)
 
-    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None):
+    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0):
         """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
         differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss).  mirror: the flags given to
-        ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m)."""
-        return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror)
+        ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m).  q_ratio L > 0: the value
+        target is z + L (q - z) where the position has a q (cz_policy_value_loss_q), and the value loss is against it."""
+        return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
+                                      float(q_ratio))
+
+    def value_targets(self, idx, q_ratio=0.0):
+        """Host float32 [B] value targets of the positions idx as the loss kernel forms them (tests, tools): mix_targets."""
+        idx = np.asarray(idx.cpu() if hasattr(idx, "cpu") else idx).astype(np.int64)
+        return mix_targets(self.z[:self.n].cpu().numpy()[idx], self.q[:self.n].cpu().numpy()[idx], q_ratio)
 
     def dense_targets(self, idx, targets="visits", mirror=None):
         """Host float32 [B, 2086] policy targets of the positions idx as the loss kernel forms them (tests, tools); mirror:
@@ -232,11 +266,12 @@ class _PolicyValueLoss(torch.autograd.Function):
     """w_p * mean(policy loss) + w_v * mean(value loss) of a minibatch; backward hands out the kernel's gradients."""
 
     @staticmethod
-    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None):
+    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None, q_ratio=0.0):
         n = win.n
         pl, se, gl, gv = _native.policy_value_loss(
             logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
-            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror)
+            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
+            q=win.q[:n] if q_ratio else None, q_ratio=q_ratio)
         ctx.save_for_backward(gl, gv)
         pm, vm = pl.mean(), se.mean()
         ctx.mark_non_differentiable(pm, vm)
@@ -245,4 +280,4 @@ class _PolicyValueLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_pm, _g_vm):
         gl, gv = ctx.saved_tensors
-        return g_total * gl, g_total * gv, None, None, None, None, None, None
+        return g_total * gl, g_total * gv, None, None, None, None, None, None, None

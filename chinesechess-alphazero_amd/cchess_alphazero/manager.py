@@ -50,6 +50,12 @@ _FLAGS = [
                                help="(self, with --record-visits) forced playouts and policy target pruning: on full plies a "
                                     "tried root move is visited at least sqrt(K * prior * visits) times and the recorded "
                                     "counts are pruned of the visits that forcing added (0 = off; the paper uses 2)")),
+    ("--record-q", dict(action="store_true",
+                        help="(self, with --record-visits) play records carry each searched ply's root search value: "
+                             "[move, value, pi, weight, q], for run.py opt --q-ratio")),
+    ("--q-ratio", dict(type=float, default=0.0, metavar="L",
+                       help="(opt) value target z + L (q - z): the game result mixed with the records' root search values "
+                            "where they have one (0 <= L <= 1; 0 = the game result alone, the reference)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -101,6 +107,13 @@ def build_config(args):
         raise SystemExit(f"--forced-playouts {args.forced_playouts} needs --record-visits: forcing without the pruned "
                          "visit counts only distorts what the trainer sees")
     engine.forced_playouts = args.forced_playouts
+    if args.record_q and not engine.record_visits:
+        raise SystemExit("--record-q needs --record-visits: the search values ride beside the visit entries")
+    if args.record_q:
+        engine.record_q = True
+    if not 0.0 <= args.q_ratio <= 1.0:
+        raise SystemExit(f"--q-ratio {args.q_ratio}: expected 0 <= L <= 1")
+    config.trainer.q_ratio = args.q_ratio
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

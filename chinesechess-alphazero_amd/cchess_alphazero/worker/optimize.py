@@ -23,6 +23,11 @@ Deliberate deviations from the reference:
     their own, so the shuffles are those of a run without the option; validation rows are never mirrored, and the
     epoch also reports the validation losses of the all-mirrored rows (``val_mirror``): its gap to ``val`` shows how
     unevenly the network treats the two wings;
+  - ``--q-ratio L`` (default 0: the reference, the game result z alone) trains the value head towards z + L (q - z)
+    where a record item carries the root's search value q (``run.py self --record-q``; rows without one keep z).  The
+    target is formed in ``cz_policy_value_loss_q``; with L > 0 the logged value losses are against the mixed target and
+    every epoch also reports ``val_value_z``, the validation value loss against z alone, so that runs with different L
+    stay comparable (with L = 0 that is ``val``'s own value loss and nothing is added);
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -114,6 +119,9 @@ class OptimizeWorker:
         self.augment = getattr(config.trainer, "augment", "none")
         if self.augment not in ("none", "mirror"):
             raise ValueError(f"trainer.augment={self.augment!r}: expected none or mirror")
+        self.q_ratio = float(getattr(config.trainer, "q_ratio", 0.0))
+        if not 0.0 <= self.q_ratio <= 1.0:
+            raise ValueError(f"trainer.q_ratio={self.q_ratio!r}: expected 0 <= L <= 1")
         self.rng = np.random.default_rng(config.engine.base_seed)
         # the mirror flags have their own stream: self.rng draws what it draws without the option
         self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
@@ -257,6 +265,10 @@ class OptimizeWorker:
                 logger.info(f"epoch {ep + 1}/{epochs}: {int(flags.sum())} of {len(tr)} training rows mirrored; all "
                             f"validation rows mirrored: val_loss {vm_loss[0]:.4f} val_policy {vm_loss[1]:.4f} "
                             f"val_value {vm_loss[2]:.4f}")
+            if self.q_ratio:
+                entry["val_value_z"] = self.evaluate(va_d, q_ratio=0.0)[2] if len(va) else float("nan")
+                logger.info(f"epoch {ep + 1}/{epochs}: value targets z + {self.q_ratio:g} (q - z); against z alone: "
+                            f"val_value_z {entry['val_value_z']:.4f}")
             self.history.append(entry)
         return steps_of_pass(n - skipped, bs, epochs)
 
@@ -275,16 +287,22 @@ class OptimizeWorker:
         uint8 [B] on the device, the rows to train on as their mirror image (planes and targets alike), or None."""
         tc = self.config.trainer
         logits, v = self.model.model(self.window.planes(idx, mirror=mirror), logits=True)
-        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror)
+        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
+                                         **self._q_args(self.q_ratio))
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         self.opt.step()
         return loss, pm, vm
 
-    def evaluate(self, idx_all, mirror=False):
+    @staticmethod
+    def _q_args(q_ratio):
+        # (nothing is passed at 0: the loop asks no more of a window's loss() than it did without the option)
+        return dict(q_ratio=q_ratio) if q_ratio else {}
+
+    def evaluate(self, idx_all, mirror=False, q_ratio=None):
         """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the
-        mirror images of all rows."""
+        mirror images of all rows.  q_ratio: the value targets' mix, None = the trainer's own."""
         import torch
         tc = self.config.trainer
         net = self.model.model
@@ -295,7 +313,8 @@ class OptimizeWorker:
                 idx = idx_all[b:b + tc.batch_size]
                 flags = torch.ones(idx.shape[0], dtype=torch.uint8, device=idx.device) if mirror else None
                 logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
-                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags)
+                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags,
+                                             **self._q_args(self.q_ratio if q_ratio is None else q_ratio))
                 sums += torch.stack([pm, vm]).double() * len(idx)
             p, v = (sums / idx_all.shape[0]).tolist()
             l2 = float(self.l2_term())

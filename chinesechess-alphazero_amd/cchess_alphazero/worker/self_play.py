@@ -13,7 +13,7 @@ from logging import getLogger
 
 import numpy as np
 
-from cchess_alphazero.lib.data_helper import PlayDataWriter
+from cchess_alphazero.lib.data_helper import PlayDataWriter, mean_abs_q_minus_z
 
 logger = getLogger(__name__)
 
@@ -93,6 +93,9 @@ class SelfPlayWorker:
             logger.info(f"Process {self.pid}-{self.rank}: playout cap: a ply is a full search "
                         f"({self.config.play.simulation_num_per_move} simulations) with probability {self.engine.full_rate}, "
                         f"otherwise {self.engine.fast_sims} simulations without root noise")
+        if self.engine.record_q:
+            logger.info(f"Process {self.pid}-{self.rank}: the records carry each searched ply's root search value q "
+                        f"(items [move, value, pi, weight, q])")
         if self.engine.forced_playouts:
             logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
                         f"the recorded visit counts are pruned (policy target pruning)")
@@ -103,6 +106,7 @@ class SelfPlayWorker:
 
     def _harvest(self):
         full = fast = pruned = raw = 0
+        dq_sum, dq_n = 0.0, 0
         for g in self.engine.drain():
             pruned += g.get("pruned_visits", 0)
             raw += sum(e.raw_total for e in g.get("visits") or [] if e.pruned)
@@ -112,12 +116,18 @@ class SelfPlayWorker:
                          f"winner = {g['value']:.2f} (1 = red, -1 = black, 0 draw; red = the first mover)"
                          + (f" book position {g['book_index']}" if g.get("book_index") is not None else ""))
             if g["store"]:
+                if self.engine.record_q:
+                    d, k = mean_abs_q_minus_z(g["data"])
+                    dq_sum, dq_n = dq_sum + d, dq_n + k
                 path = self.writer.add_game(g["data"])
                 self.stored_games += 1
                 if path:
                     logger.info(f"Process {self.pid} save play data to {path}")
         if self.engine.fast_sims and full + fast:
             logger.info(f"Process {self.pid}-{self.rank}: drained {full} full plies (training rows) and {fast} fast plies")
+        if self.engine.record_q and dq_n:
+            logger.info(f"Process {self.pid}-{self.rank}: search values of {dq_n} plies written, mean |q - z| = "
+                        f"{dq_sum / dq_n:.4f}")
         if self.engine.forced_playouts and raw:
             logger.info(f"Process {self.pid}-{self.rank}: policy target pruning removed {pruned} of {raw} root visits "
                         f"({100.0 * pruned / raw:.1f} %)")

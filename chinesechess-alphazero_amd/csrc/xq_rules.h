@@ -86,6 +86,29 @@ XQ_D double wave_max_f64(double v)          // v is never NaN
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 #undef XQ_DPP_STEP_MAX_F64
+// Sum over the 64 lanes on the same ladder, in the fixed order of wave_incl_scan (a lane without a source adds +0.0):
+// every call with the same 64 values returns the same bits.  Rounded adds, nothing to contract.
+#define XQ_DPP_STEP_ADD_F64(v, ctrl, rmask, bound)                                                                   \
+    do {                                                                                                             \
+        const long long b_ = __double_as_longlong(v);                                                               \
+        const int lo_ = __builtin_amdgcn_update_dpp(0, (int)b_, ctrl, rmask, 0xF, bound);                           \
+        const int hi_ = __builtin_amdgcn_update_dpp(0, (int)(b_ >> 32), ctrl, rmask, 0xF, bound);                   \
+        v = __dadd_rn(v, __longlong_as_double((long long)(((unsigned long long)(unsigned int)hi_ << 32) | (unsigned int)lo_))); \
+    } while (0)
+XQ_D double wave_add_f64(double v)
+{
+    XQ_DPP_STEP_ADD_F64(v, 0x111, 0xF, true);
+    XQ_DPP_STEP_ADD_F64(v, 0x112, 0xF, true);
+    XQ_DPP_STEP_ADD_F64(v, 0x114, 0xF, true);
+    XQ_DPP_STEP_ADD_F64(v, 0x118, 0xF, true);
+    XQ_DPP_STEP_ADD_F64(v, 0x142, 0xA, false);
+    XQ_DPP_STEP_ADD_F64(v, 0x143, 0xC, false);
+    const long long b = __double_as_longlong(v);
+    const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)b, 63);
+    const unsigned int hi = (unsigned int)__builtin_amdgcn_readlane((int)(b >> 32), 63);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+#undef XQ_DPP_STEP_ADD_F64
 #define XQ_DPP_STEP_MAX_F32(v, ctrl, rmask)                                                                          \
     do {                                                                                                             \
         const float o_ = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), ctrl, rmask, 0xF, false)); \

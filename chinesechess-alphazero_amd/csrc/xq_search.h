@@ -194,6 +194,9 @@ struct VisitRing {
     unsigned long long* dropped;    // [1] entries that found the ring full
     uint8_t* g_lost;                // [G] the game in slot g lost an entry (or started before recording was switched on)
     unsigned int cap;
+    // value record (cz_search_record_values): the root's search value of the entry in the same slot, a ring of its own
+    // because the 784-byte entry has no free word; written by emit_visits in the entry's reservation
+    double* q;                      // [cap]; NULL = off
 };
 
 }  // namespace xq

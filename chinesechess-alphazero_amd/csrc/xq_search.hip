@@ -1333,6 +1333,27 @@ XQ_D int prune_targets(int nm, const uint16_t lab[2], int n[2], const double w[2
     return S;
 }
 
+// Root search value (include/czero.h, cz_search_record_values): one wavefront, edge j = lane + 64 h.  lab[h] carries
+// VISIT_BANNED, m is the count the visit entry records (pruned or raw), n / w the raw statistics.  Float64 throughout:
+// q_root = (sum m_j * (w_j / n_j)) / (sum m_j) over the non-banned edges with n_j > 0; NaN when that leaves nothing.  The
+// lane's two terms first, then the DPP ladder of wave_add_f64: a fixed order, no LDS permute.  All 64 lanes call it.
+XQ_D double root_value(int nm, const uint16_t lab[2], const int m[2], const int n[2], const double w[2])
+{
+    const int lane = lane_id();
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED) && n[h] > 0;
+        if (!live) continue;
+        const double mj = (double)m[h];
+        num = __dadd_rn(num, __dmul_rn(mj, w[h] / (double)n[h]));
+        den = __dadd_rn(den, mj);                   // integers below 2^53: exact in any order
+    }
+    num = wave_add_f64(num);
+    den = wave_add_f64(den);
+    return den > 0.0 ? num / den : __builtin_nan("");
+}
+
 // Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
@@ -1400,6 +1421,23 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         }
     }
     const bool pruned = raw_total > 0;      // S == 0: nothing to prune, the entry is the one written without pruning
+    if (V.q) {
+        // the value record (cz_search_record_values): the entry's slot in a ring of its own, from the labels and counts
+        // this lane has just written and the raw statistics in the tree
+        uint16_t ql[2] = {0, 0};
+        int qm[2] = {0, 0}, qn[2] = {0, 0};
+        double qw[2] = {0.0, 0.0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            ql[h] = lab[j];
+            qm[h] = cnt[j];
+            if (sb) { const EdgeStat es = sb[j]; qn[h] = es.n; qw[h] = es.w; }
+        }
+        const double q = root_value(nm, ql, qm, qn, qw);
+        if (lane == 0) V.q[pos % V.cap] = q;
+    }
     if (lane == 0) {
         VisitEntryHdr* h = reinterpret_cast<VisitEntryHdr*>(e);
         h->game_id = B.g_game_id[g];
@@ -2014,6 +2052,70 @@ __global__ __launch_bounds__(64) void k_policy_target_prune(const uint16_t* __re
     if (lane == 0) out_raw_total[r] = S;
 }
 
+// Search value of every current root (cz_search_root_value): what the value record would hold for it -- the counts of
+// k_root_targets as m, the raw statistics as n / w
+__global__ __launch_bounds__(64) void k_root_value(SearchParams P, SearchBuffers B, double* __restrict__ q)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    const int root = B.g_root[g];
+    const int n_no_act = B.g_n_no_act[g];
+    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
+    int nm = 0;
+    uint16_t el[2] = {0, 0};
+    int en[2] = {0, 0}, em[2] = {0, 0};
+    double ew[2] = {0.0, 0.0};
+    float ep[2] = {0.0f, 0.0f};
+    if (root >= 0) {
+        char* base = rec_ptr(gv, (uint32_t)root);
+        const NodeHdr hdr = load_hdr(base);
+        nm = (int)(hdr.meta & 0xFF);
+        if (nm > MAXMOVES) nm = MAXMOVES;
+        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
+        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            const uint16_t mv = pm[j];
+            bool banned = false;
+            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+            if (sb) { const EdgeStat es = sb[j]; en[h] = em[h] = es.n; ew[h] = es.w; }
+            ep[h] = node_p(base)[j];
+        }
+    }
+    prune_targets(nm, el, em, ew, ep, P.c_puct, P.forced_k);
+    const double v = root_value(nm, el, em, en, ew);
+    if (lane == 0) q[g] = v;
+}
+
+// cz_root_value: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
+__global__ __launch_bounds__(64) void k_root_value_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m,
+                                                       const int32_t* __restrict__ n, const double* __restrict__ w,
+                                                       const uint8_t* __restrict__ n_edges, int rows,
+                                                       double* __restrict__ out_q)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    int nm = n_edges[r];
+    if (nm > MAXMOVES) nm = MAXMOVES;
+    uint16_t el[2] = {0, 0};
+    int em[2] = {0, 0}, en[2] = {0, 0};
+    double ew[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
+        if (lane + 64 * h < nm) { el[h] = labels[i]; em[h] = m[i]; en[h] = n[i]; ew[h] = w[i]; }
+    }
+    const double v = root_value(nm, el, em, en, ew);
+    if (lane == 0) out_q[r] = v;
+}
+
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
 // the LAST maximum, banned moves are skipped at the root only -- until a node that was never selected from (the
 // reference creates a node's edges at its first selection: an empty `a` ends the line), a terminal / unlinked child or
@@ -2112,6 +2214,7 @@ struct cz_search {
     int keep_chunks_created = 0;      // P.keep_chunks as sized at creation (cz_search_set_sims never goes below it)
     VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
     void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
+    void* q_mem = nullptr;            // the value ring V.q (cz_search_record_values), allocated only while that is on
     void* book_mem = nullptr;         // the start-position book (cz_search_set_book): P.book points here
 };
 
@@ -2327,6 +2430,7 @@ int cz_search_destroy(cz_search* s)
 {
     if (!s) return CZ_OK;
     (void)hipFree(s->vis_mem);
+    (void)hipFree(s->q_mem);
     (void)hipFree(s->book_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
@@ -2508,7 +2612,9 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
     hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffers
     if (e != hipSuccess) return serr_hip("cz_search_record_visits", e);
     (void)hipFree(s->vis_mem);
+    (void)hipFree(s->q_mem);                             // the value ring shares the visit ring's slots: it goes with it
     s->vis_mem = nullptr;
+    s->q_mem = nullptr;
     s->V = VisitRing{};
     if (!on) return CZ_OK;
     // default: 64 entries per game -- one k_advance launch records at most 8 plies of a game (the loop in k_advance),
@@ -2617,10 +2723,60 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
     return CZ_OK;
 }
 
-int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out, void* stream)
+int cz_search_record_values(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_values: null handle");
+    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_values: needs cz_search_record_visits on");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
+    if (e != hipSuccess) return serr_hip("cz_search_record_values", e);
+    if (!on) {
+        (void)hipFree(s->q_mem);
+        s->q_mem = nullptr;
+        s->V.q = nullptr;
+        return CZ_OK;
+    }
+    if (s->V.q) return CZ_OK;                            // already on: the ring and what waits in it stay
+    void* mem = nullptr;
+    const size_t bytes = (size_t)s->V.cap * sizeof(double);
+    e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return serr_hip("cz_search_record_values: hipMalloc", e);
+    // entries already waiting in the visit ring were written without a value: NaN, "no value"
+    e = hipMemsetAsync(mem, 0xFF, bytes, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip("cz_search_record_values", e); }
+    s->q_mem = mem;
+    s->V.q = (double*)mem;
+    return CZ_OK;
+}
+
+int cz_search_root_value(cz_search* s, double* q, void* stream)
+{
+    if (!s || !q) return serr(CZ_ERR_ARG, "cz_search_root_value: null argument");
+    hipLaunchKernelGGL(k_root_value, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, q);
+    S_LAUNCH_CHECK("cz_search_root_value");
+    return CZ_OK;
+}
+
+int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, const double* w, const uint8_t* n_edges,
+                  int rows, double* out_q, void* stream)
+{
+    if (!labels || !m || !n || !w || !n_edges || !out_q || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_root_value: null argument or rows < 0");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_root_value_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, n, w, n_edges, rows,
+                       out_q);
+    S_LAUNCH_CHECK("cz_root_value");
+    return CZ_OK;
+}
+
+// cz_search_drain_visits and cz_search_drain_visits_q: q_buf NULL = the entries alone
+static int drain_visits(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out, uint64_t* dropped_out,
+                        void* stream)
 {
     if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits: bad argument");
     if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits: visit recording is off");
+    if (q_buf && !s->V.q) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: value recording is off");
     hipStream_t st = (hipStream_t)stream;
     unsigned int ctl[6] = {0u, 0u, 0u, 0u, 0u, 0u};        // tail, head, -, -, dropped (64 bit): one copy
     static_assert(sizeof(unsigned long long) == 8, "dropped counter is 64-bit");
@@ -2644,6 +2800,8 @@ int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n
         const unsigned int run = (cap - at) < (k - done) ? (cap - at) : (k - done);
         e = hipMemcpyAsync((char*)host_buf + (size_t)done * VISIT_STRIDE, s->V.ring + (size_t)at * VISIT_STRIDE,
                            (size_t)run * VISIT_STRIDE, hipMemcpyDeviceToHost, st);
+        if (q_buf && e == hipSuccess)
+            e = hipMemcpyAsync(q_buf + done, s->V.q + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
         done += run;
     }
     const unsigned int new_head = tail;
@@ -2652,6 +2810,18 @@ int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n
     if (e != hipSuccess) return serr_hip("cz_search_drain_visits", e);
     *n_out = (int)k;
     return CZ_OK;
+}
+
+int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out, void* stream)
+{
+    return drain_visits(s, host_buf, nullptr, max_entries, n_out, dropped_out, stream);
+}
+
+int cz_search_drain_visits_q(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out,
+                             uint64_t* dropped_out, void* stream)
+{
+    if (host_buf && !q_buf) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: null q_buf");
+    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, max_entries, n_out, dropped_out, stream);
 }
 
 int cz_search_reset_trees(cz_search* s, void* stream)

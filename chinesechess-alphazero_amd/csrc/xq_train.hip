@@ -166,7 +166,8 @@ __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__
 __global__ __launch_bounds__(64) void k_policy_value_loss(
     const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx,
     const uint8_t* __restrict__ mirror, int n_rows, int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
-    const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z, int mode,
+    const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z,
+    const float* __restrict__ q, float q_ratio, int mode,
     float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
     float* __restrict__ grad_logits, float* __restrict__ grad_v)
 {
@@ -256,7 +257,12 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
             }
         }
         if (lane == 0) {
-            const float d = v[r] - z[i];
+            float t = z[i];
+            if (q != nullptr) {                          // z/q mix (cz_policy_value_loss_q): rounded step by step, no fma
+                const float qi = q[i];
+                if (qi == qi) t = __fadd_rn(t, __fmul_rn(q_ratio, __fsub_rn(qi, t)));
+            }
+            const float d = v[r] - t;
             policy_loss[r] = loss;
             value_sqerr[r] = d * d;
             grad_v[r] = w_v * (2.f * d) * inv_b;
@@ -301,12 +307,18 @@ int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const
     return cz_gather_planes_m(boards, prev, n_pos, idx, nullptr, n_rows, depth, planes, stream);
 }
 
-int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
                            int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
-                           const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
-                           float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, int mode, float w_p,
+                           float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           void* stream)
 {
+    if (!(q_ratio >= 0.f && q_ratio <= 1.f)) {
+        czi_set_error("cz_policy_value_loss_q: q_ratio outside [0, 1]");
+        return CZ_ERR_ARG;
+    }
     if (n_rows == 0) return CZ_OK;
+    if (q_ratio == 0.f) q = nullptr;                     // the kernel's own test: no q, the target is z
     if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !v || !idx || !policy_loss ||
         !value_sqerr || !grad_logits || !grad_v || (n_pos > 0 && (!played || !z)) ||
         nnz < 0 || (mode == 1 && nnz > 0 && (!row_ptr || !vis_label || !vis_count))) {
@@ -314,9 +326,18 @@ int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const in
         return CZ_ERR_ARG;
     }
     hipLaunchKernelGGL(k_policy_value_loss, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
-                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, mode, w_p, w_v, policy_loss,
-                       value_sqerr, grad_logits, grad_v);
+                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, mode, w_p, w_v,
+                       policy_loss, value_sqerr, grad_logits, grad_v);
     return launch_status("cz_policy_value_loss: launch failed");
+}
+
+int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
+                           float* value_sqerr, float* grad_logits, float* grad_v, void* stream)
+{
+    return cz_policy_value_loss_q(logits, ld, v, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z,
+                                  nullptr, 0.f, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v, stream);
 }
 
 int cz_policy_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, int n_rows, int n_pos,

@@ -365,6 +365,44 @@ typedef struct cz_visit_entry {
  * switched on.  Synchronises the stream. */
 int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out,
                            void* stream);
+/* ---- root value record of self-play (off by default; the reference has no such option) ----
+ * The search's own estimate of the root position, recorded beside each visit entry so that a trainer can mix it with
+ * the game result (Lc0's q_ratio).  on = 0 (the state after cz_search_create): no kernel, record, counter or entry
+ * differs by a bit from what it was before this existed.
+ *
+ * THE ARITHMETIC.  Given a root's edges as a visit entry sees them -- labels with the banned bit (0x8000), the raw
+ * statistics n_j (int32) and w_j (float64, from the root mover's view: the q = w / n that cz_search_choose takes its
+ * maxq from) and m_j, the count the visit entry records for the edge (the PRUNED count when the entry is
+ * CZ_VISIT_PRUNED, the raw count n_j otherwise) -- all arithmetic in float64:
+ *       q_root = ( sum_j m_j * (w_j / n_j) ) / ( sum_j m_j )      over non-banned edges with n_j > 0
+ * Each quotient and each product is rounded once; the numerator is summed in a fixed order (edge j and j + 64 in lane
+ * j, then one ladder over the 64 lanes), so equal inputs give equal bits; the denominator is a sum of integers, exact.
+ * Without pruning or bans this is sum w / sum n.  With forced playouts the visits that forcing added do not drag the
+ * value towards moves the search rejected.  sum m_j = 0 -- no edge, every edge banned, a root that was never selected
+ * from -- gives NaN: "no value".  Every backed-up value lies in [-2, 2] (a network value in [-1, 1], a terminal one
+ * +-2, player.py:204-208) and a finished search has no virtual loss outstanding, so |w_j| <= 2 n_j and |q_root| <= 2.
+ *
+ * THE RING.  The 784-byte cz_visit_entry has no free word, so the values live in a ring of their own, double q[capacity],
+ * indexed by the slot of the visit entry: the kernel writes both in one reservation, a dropped entry drops its value.
+ * Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting); every call of
+ * cz_search_record_visits frees the value ring as well, so switch the values on after it.  Call it before
+ * cz_search_start_selfplay and before a graph capture, like the other setters; synchronises the stream.  Entries
+ * already waiting when it is switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.
+ * No counter is added; the move, the tree and the visit entries do not change. */
+int cz_search_record_values(cz_search* s, int on, void* stream);
+/* cz_search_drain_visits that also copies the entries' values into HOST q_buf[max_entries], q_buf[i] beside entry i.
+ * host_buf = NULL counts (q_buf unused).  CZ_ERR_ARG also when host_buf is given and q_buf is NULL or the value record
+ * is off.  cz_search_drain_visits itself keeps working with the values on; it drops the values of what it consumes. */
+int cz_search_drain_visits_q(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out,
+                             uint64_t* dropped_out, void* stream);
+/* The value an entry of each current root would carry: q [G] float64 DEVICE.  Same inputs as cz_search_root_targets:
+ * the bans of the current cz_search_set_roots, m = the counts cz_search_root_targets reports for the object's c_puct
+ * and k (k = 0: the raw counts).  A root that is not in the tree reports NaN.  Works with the record off. */
+int cz_search_root_value(cz_search* s, double* q, void* stream);
+/* The arithmetic on its own, one wavefront per row: labels / m / n / w [rows][128] and n_edges [rows] (<= 128), out_q
+ * [rows], all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
+int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, const double* w, const uint8_t* n_edges,
+                  int rows, double* out_q, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
@@ -674,6 +712,19 @@ int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const in
                            int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
                            const uint16_t* played, const float* z, int mode, float w_p, float w_v, float* policy_loss,
                            float* value_sqerr, float* grad_logits, float* grad_v, void* stream);
+/* The same kernel with a mixed value target (run.py opt --q-ratio L; the value record of cz_search_record_values):
+ * q[n_pos] (DEVICE float32, NaN = the position has no search value) and q_ratio = L.  The row's value target is
+ *       t = z + L * (q - z)
+ * formed in float32 as a rounded difference, a rounded product and a rounded sum -- no fused multiply-add, so NumPy
+ * float32 reproduces it bit for bit -- and t = z where q is NaN; value_sqerr = (v - t)^2, grad_v = w_v 2 (v - t) / n_rows.
+ * q = NULL or q_ratio = 0 takes the path of cz_policy_value_loss_m, bit for bit; the two entries above forward here
+ * with NULL.  The policy outputs never depend on q, and q does not change under the mirror.  CZ_ERR_ARG also for a
+ * q_ratio outside [0, 1] (NaN included). */
+int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, int mode, float w_p,
+                           float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           void* stream);
 
 #ifdef __cplusplus
 }

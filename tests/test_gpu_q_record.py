@@ -1,0 +1,619 @@
+"""-m gpu: the root value record and the z/q value mix (cz_search_record_values, cz_search_drain_visits_q,
+cz_search_root_value, cz_root_value, cz_policy_value_loss_q; run.py self --record-q, run.py opt --q-ratio L).
+
+The yardstick of the arithmetic is tests/q_record_oracle.py (math.fsum).  Its bound, 1e-13: a root has at most 128 float64
+terms m_j q_j, so the kernel's summation error is at most 128 * 2^-53 * sum m_j |q_j|; after the division by sum m_j that
+is about 1.4e-14 * max |q_j|, and 1e-13 leaves room for |q| up to 2 and the roundings of the quotients.  With the record
+off, the rings' bytes, the records and the counters are what they were."""
+import copy
+import ctypes as C
+import json
+import logging
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import forced_playouts_oracle as fo
+import q_record_oracle as qo
+from oracle import xq_oracle as xo
+from test_gpu_book import _engine_cfg
+from test_gpu_forced_playouts import _book, _entry_key
+from test_gpu_search import boards_tensor, gpu, no_act_tensors, play_config, stub_eval  # noqa: F401  (gpu: fixture)
+from test_gpu_trainer import dev, random_games, small_config, window_of  # noqa: F401  (dev: fixture)
+
+pytestmark = pytest.mark.gpu
+ERR_ARG = -1                                                # include/czero.h CZ_ERR_ARG
+SPEC = dict(kind="hash", salt=5)
+TOL = 1e-13
+M = 128
+
+
+# ---- 1. the arithmetic alone ---------------------------------------------------------------------------------------------
+def _row(labels, m, n, w):
+    return dict(labels=np.asarray(labels, dtype=np.uint16), m=np.asarray(m, dtype=np.int32), n=np.asarray(n, dtype=np.int32),
+                w=np.asarray(w, dtype=np.float64))
+
+
+def _random_row(rng, nm, ban=0.0, pruned=False):
+    n = (rng.integers(1, 60, nm) * (rng.random(nm) < 0.7)).astype(np.int32)
+    w = rng.uniform(-2, 2, nm) * n
+    m = n.copy()
+    if pruned:                                              # some edges lose visits, some all of them
+        cut = rng.random(nm) < 0.5
+        m[cut] = (m[cut] * rng.random(int(cut.sum()))).astype(np.int32)
+    lab = rng.permutation(2086)[:nm].astype(np.uint16)
+    lab[rng.random(nm) < ban] |= qo.BANNED
+    return _row(lab, m, n, w)
+
+
+def _special_rows():
+    rng = np.random.default_rng(5)
+    rows = {
+        "no_bans": _row([1, 2, 3], [10, 30, 60], [10, 30, 60], [5.0, -15.0, 30.0]),
+        "bans": _row([1, 2 | qo.BANNED, 3], [4, 1000, 4], [4, 1000, 4], [2.0, 1000.0, -1.0]),
+        "pruned_m": _row([1, 2, 3], [90, 0, 2], [90, 6, 4], [45.0, -6.0, 1.0]),
+        "n_0": _row([1, 2], [3, 5], [3, 0], [1.5, 9.0]),
+        "all_banned": _row([1 | qo.BANNED, 2 | qo.BANNED], [3, 4], [3, 4], [1.0, 1.0]),
+        "one_edge": _row([7], [1], [3], [-2.0]),
+        "no_edge": _row([], [], [], []),
+        "never_selected": _row([1, 2, 3], [0, 0, 0], [0, 0, 0], [0.0, 0.0, 0.0]),
+        "all_pruned_away": _row([1, 2], [0, 0], [5, 5], [1.0, 1.0]),
+    }
+    for nm in (2, 63, 64, 65, 127, 128):
+        rows[f"edges_{nm}"] = _random_row(rng, nm, pruned=nm % 2 == 1)
+    r = _random_row(rng, 100)
+    r["labels"][:64] |= qo.BANNED                           # only the lanes' second edges count
+    r["n"][64:] = np.maximum(r["n"][64:], 1)
+    r["m"][64:] = r["n"][64:]
+    rows["second_half_only"] = r
+    return rows
+
+
+def test_root_value_alone(gpu):
+    t = gpu.torch
+    rows = _special_rows()
+    rng = np.random.default_rng(11)
+    for i in range(56):
+        rows[f"random_{i}"] = _random_row(rng, int(rng.integers(1, 129)), ban=0.1 * (i % 3), pruned=i % 2 == 1)
+    names = list(rows)
+    R = len(names)
+    assert 65 <= R <= 75
+    lab = np.zeros((R, M), dtype=np.uint16)
+    m = np.zeros((R, M), dtype=np.int32)
+    n = np.zeros((R, M), dtype=np.int32)
+    w = np.zeros((R, M), dtype=np.float64)
+    ne = np.zeros(R, dtype=np.uint8)
+    m[:], n[:], w[:] = 10 ** 6, 10 ** 6, 10.0 ** 9          # past n_edges: values that would change the result if read
+    for i, name in enumerate(names):
+        r = rows[name]
+        k = len(r["n"])
+        ne[i] = k
+        lab[i, :k], m[i, :k], n[i, :k], w[i, :k] = r["labels"], r["m"], r["n"], r["w"]
+    dev_args = [t.from_numpy(lab.view(np.int16)).cuda().view(t.uint16), t.from_numpy(m).cuda(), t.from_numpy(n).cuda(),
+                t.from_numpy(w).cuda(), t.from_numpy(ne).cuda()]
+    got = gpu.S.root_value_rows(*dev_args).cpu().numpy()
+    assert gpu.S.Search.root_value_rows is gpu.S.root_value_rows
+    worst = 0.0
+    for i, name in enumerate(names):
+        r = rows[name]
+        want = qo.root_value(r["labels"], r["m"], r["n"], r["w"])
+        assert qo.same_value(float(got[i]), want, TOL), (name, got[i], want)
+        if want == want:
+            worst = max(worst, abs(float(got[i]) - want))
+    print(f"cz_root_value: {R} rows, max |delta| = {worst:.3e} (bound {TOL:g})")
+    for name in ("all_banned", "no_edge", "never_selected", "all_pruned_away"):
+        assert math.isnan(got[names.index(name)]), name
+    assert got[names.index("no_bans")] == 0.2 and got[names.index("one_edge")] == -2.0 / 3
+    assert not np.isnan(got[names.index("second_half_only")])
+    # twice the same bits
+    assert gpu.S.root_value_rows(*dev_args).cpu().numpy().tobytes() == got.tobytes()
+    # arguments
+    L = gpu.N.lib()
+    out = t.empty(R, dtype=t.float64, device="cuda")
+    ptr = [C.c_void_p(x.data_ptr()) for x in dev_args]
+    st = C.c_void_p(t.cuda.current_stream().cuda_stream)
+    po = C.c_void_p(out.data_ptr())
+    for i in range(5):
+        assert L.cz_root_value(*(ptr[:i] + [None] + ptr[i + 1:]), R, po, st) == ERR_ARG, i
+    assert L.cz_root_value(*ptr, R, None, st) == ERR_ARG
+    assert L.cz_root_value(*ptr, -1, po, st) == ERR_ARG
+    assert L.cz_root_value(*ptr, 0, po, st) == 0
+
+
+# ---- 2. single searches, external mode -----------------------------------------------------------------------------------
+def _check_roots(s, bans, what):
+    st, tg, q = s.root_stats(), s.root_targets(), s.root_value()
+    pruned = 0
+    for g in range(s.G):
+        c = int(st["counts"][g])
+        lab = st["moves"][g, :c].copy()
+        for j in range(c):
+            if xo.label_str(int(lab[j])) in bans[g]:
+                lab[j] |= qo.BANNED
+        want = qo.root_value(lab, tg["n"][g, :c], st["n"][g, :c], st["w"][g, :c])
+        assert want == want and abs(want) <= 2.0, (what, g)
+        assert qo.same_value(float(q[g]), want, TOL), (what, g, q[g], want)
+        pruned += int((tg["n"][g, :c] != st["n"][g, :c]).any())
+    return pruned, st
+
+
+@pytest.mark.parametrize("K", [1, 8])
+def test_root_value_of_single_searches(gpu, K, positions_1k):
+    wide = [c for c in fo.cases() if c["name"] == "wide"][0]["state"]
+    widest = max((p for p in positions_1k if not p["done"][0]), key=lambda p: len(p["moves"].split()))["state"]
+    picks = [positions_1k[i]["state"] for i in (100, 250, 400, 550)]
+    states = [xo.INIT_STATE] + picks + [widest, wide, picks[1]]
+    assert len(states) == 8
+    # (no live position of the file has more than 64 moves -- its widest fills all but the last lanes of the first half;
+    #  the root with more is the one tests/forced_playouts_oracle.py adds for the same reason)
+    assert len(xo.get_legal_moves(wide)) > 64 >= len(xo.get_legal_moves(widest)) >= 60
+    pc = play_config(simulation_num_per_move=64, search_threads=K)
+    ev = stub_eval(gpu, SPEC)
+    for k in (0.0, 2.0):
+        s = gpu.S.Search(pc, 8, seed=7)
+        s.set_forced_playouts(k)
+        bans = [[]] * 7 + [xo.get_legal_moves(states[7])[:3]]
+        na, nn = no_act_tensors(gpu, bans)
+        s.set_roots(boards_tensor(gpu, states), no_act=na, n_no_act=nn)
+        s.run_until_idle(ev)
+        pruned, st = _check_roots(s, bans, f"K={K} k={k} ply 0")
+        # a second ply: every game plays its most visited move and searches on in the kept subtree; the last root stays
+        # and bans that move instead, so a banned edge holds visits
+        best = []
+        for g in range(8):
+            c = int(st["counts"][g])
+            n = st["n"][g, :c].astype(np.int64)
+            n[[xo.label_str(int(mv)) in bans[g] for mv in st["moves"][g, :c]]] = -1
+            best.append(xo.label_str(int(st["moves"][g, int(n.argmax())])))
+        nxt = [xo.step(states[g], best[g]) for g in range(7)] + [states[7]]
+        nxt = [states[g] if xo.done(x)[0] else x for g, x in enumerate(nxt)]       # (a finished game searches on where it is)
+        bans2 = [[]] * 7 + [[best[7]]]
+        na, nn = no_act_tensors(gpu, bans2)
+        s.set_roots(boards_tensor(gpu, nxt), turns=gpu.torch.ones(8, dtype=gpu.torch.int32, device="cuda"), no_act=na,
+                    n_no_act=nn)
+        s.run_until_idle(ev)
+        pruned2, st2 = _check_roots(s, bans2, f"K={K} k={k} ply 1")
+        c = int(st2["counts"][7])
+        j = [xo.label_str(int(mv)) for mv in st2["moves"][7, :c]].index(best[7])
+        assert st2["n"][7, j] > 0                           # the banned edge's visits are in the tree and not in the value
+        ctr = s.counters()
+        assert ctr["tree_resets"] == 0 and ctr["overflow_sims"] == 0
+        assert (pruned + pruned2 > 0) == (k > 0), (K, k, pruned, pruned2)
+        s.close()
+
+
+# ---- self-play helpers -----------------------------------------------------------------------------------------------------
+def _play(gpu, pc, G, seed, k, record_q=True, max_rounds=60000, **kw):
+    """Self-play through SelfPlayEngine with the stub evaluator and the visit record until every slot has finished a game."""
+    from cchess_alphazero.engine import SelfPlayEngine
+    eng = SelfPlayEngine(_engine_cfg(pc), G, evaluator=stub_eval(gpu, SPEC), seed=seed, record_visits=True,
+                         forced_playouts=k, record_q=record_q, **kw)
+    assert eng.search.values_on == record_q
+    i_games = gpu.S.COUNTER_NAMES.index("games")
+    games = []
+    try:
+        eng.start(0, 0)
+        for r in range(max_rounds):
+            eng.step()
+            if r % 16 == 15:
+                games += eng.drain()
+                if eng.search.game_counters()[:, i_games].min() >= 1:
+                    break
+        else:
+            raise AssertionError(f"not finished after {max_rounds} rounds: {len(games)} games")
+        games += eng.drain()
+        ctr = eng.counters()
+    finally:
+        eng.close()
+    assert len({g["game_id"] for g in games}) == len(games) >= G
+    return sorted(games, key=lambda g: g["game_id"]), ctr
+
+
+# ---- 3. self-play, ply 0 exactly -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", [2.0, 0.0])
+def test_selfplay_ply_0_value_matches_the_oracle(gpu, k):
+    G = 32
+    book = _book()
+    pc = play_config(simulation_num_per_move=120, search_threads=1, noise_eps=0.0, tau_decay_rate=0.0, max_game_length=1)
+    games, ctr = _play(gpu, pc, G, 3, k, book=book, book_rate=1.0)
+    assert ctr["tree_resets"] == 0 and ctr["overflow_sims"] == 0 and ctr["visits_dropped"] == 0
+    want = {}
+    weighted = 0
+    for g in games[:G]:
+        state = book[g["book_index"]]
+        if state not in want:
+            o = fo.Search(fo.play_cfg(120), SPEC["salt"], k)
+            o.search(state)
+            st, (targets, raw) = o.node_stats(state), o.targets(state)
+            want[state] = (st, targets, qo.root_value(st["moves"], targets, st["n"], st["w"]), o.best_move(state))
+        st, targets, q, best = want[state]
+        e = g["visits"][0]
+        assert g["data"][0] == state and e.ply == 0 and (e.moves == st["moves"]).all() and (e.n == targets).all()
+        assert e.pruned == (k > 0)
+        assert e.q is not None and qo.same_value(e.q, q, TOL), (g["game_id"], e.q, q)
+        item = g["data"][1]
+        assert len(item) == 5 and item[0] == best and item[3] == 1 and item[4] == round(e.q, 6), g["game_id"]
+        raw_q = qo.root_value(st["moves"], st["n"], st["n"], st["w"])
+        weighted += int(abs(raw_q - q) > TOL)
+    assert len(want) == min(G, len(book))
+    assert (weighted > 0) == (k > 0)                        # with pruning the weights are not the raw counts, and it shows
+
+
+# ---- 4. self-play, whole games ---------------------------------------------------------------------------------------------
+def _strip_q(data):
+    """The record without its value column: what the same run writes with record_q off."""
+    out = [data[0]]
+    for it in data[1:]:
+        out.append(it if len(it) < 5 else (it[:3] if it[3] == 1 else it[:4]))
+    return out
+
+
+@pytest.mark.parametrize("K,fast_sims", [(1, 0), (4, 0), (1, 12), (4, 12)])
+def test_selfplay_games_carry_values(gpu, K, fast_sims):
+    G = 17
+    pc = play_config(simulation_num_per_move=48, search_threads=K, noise_eps=0.25 if K > 1 else 0.0, tau_decay_rate=0.6,
+                     max_game_length=6, enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
+    kw = dict(fast_sims=fast_sims, full_rate=0.5) if fast_sims else {}
+    k = 2.0 if fast_sims else 0.0
+    games, ctr = _play(gpu, pc, G, 17, k, **kw)
+    assert ctr["visits_dropped"] == 0 and ctr["tree_resets"] == 0
+    n_q = n_none = n_fast = 0
+    for g in games:
+        vis = g["visits"]
+        assert vis is not None
+        items = g["data"][1:]
+        for i, e in enumerate(vis):
+            assert e.q is None or (math.isfinite(e.q) and abs(e.q) <= 2.0), (g["game_id"], i, e.q)
+            if e.resign:
+                assert i == len(vis) - 1 and len(items) == i          # the resignation ply has an entry and no item
+                continue
+            it = items[i]
+            assert len(it) == 5 and it[3] == (0 if e.fast else 1), (g["game_id"], i, it)
+            assert it[4] == (None if e.q is None else round(e.q, 6))
+            n_q += e.q is not None
+            n_none += e.q is None
+            n_fast += e.fast
+        for it in items[len(vis):]:                                     # the appended king capture
+            assert len(it) == 2
+        assert len(items) - len(vis) in (-1, 0, 1)
+    data = [g["data"] for g in games]
+    assert json.loads(json.dumps(data)) == data
+    print(f"K={K} fast_sims={fast_sims}: {len(games)} games, {n_q} values, {n_none} without, {n_fast} fast plies")
+    assert n_q > 0 and (n_fast > 0) == bool(fast_sims)
+    # two runs, the same bytes
+    again, ctr2 = _play(gpu, pc, G, 17, k, **kw)
+    key = lambda gs: [(g["game_id"], g["data"], [_entry_key(e) + (None if e.q is None else np.float64(e.q).tobytes(),)  # noqa: E731
+                                                 for e in g["visits"]]) for g in gs]
+    assert key(again) == key(games) and ctr2 == ctr
+    # the value column is the only addition
+    off, ctr0 = _play(gpu, pc, G, 17, k, record_q=False, **kw)
+    assert ctr0 == ctr
+    assert [g["game_id"] for g in off] == [g["game_id"] for g in games]
+    for a, b in zip(off, games):
+        assert a["data"] == _strip_q(b["data"]), a["game_id"]
+        assert [_entry_key(e) for e in a["visits"]] == [_entry_key(e) for e in b["visits"]]
+        assert all(e.q is None for e in a["visits"])
+        assert {k_: v for k_, v in a.items() if k_ not in ("data", "visits")} == \
+               {k_: v for k_, v in b.items() if k_ not in ("data", "visits")}
+
+
+# ---- 5. off means off ------------------------------------------------------------------------------------------------------
+def _selfplay_raw(gpu, pc, seed, rounds, setup, with_q=False):
+    """test_gpu_forced_playouts._selfplay_raw with the setup AFTER the visit ring is on (the value record needs it): the
+    bytes of the finished-game records and of the visit entries as the device rings hand them out, the counters, and with
+    with_q the values cz_search_drain_visits_q hands out beside the entries."""
+    G = 32
+    s = gpu.S.Search(pc, G, seed=seed)
+    s.record_visits(True)
+    setup(s)
+    ev = stub_eval(gpu, SPEC)
+    s.start_selfplay(seed=seed, first_game_id=0)
+    recs, entries = [], []
+    cur = C.c_uint(0)
+
+    def drain():
+        n = C.c_int(0)
+        buf = np.zeros((4096, s.record_stride), dtype=np.uint8)
+        gpu.N.check(s.L.cz_search_drain_records(s.h, C.byref(cur), buf.ctypes.data, 4096, C.byref(n), s._stream()), "drain")
+        for i in range(n.value):
+            turns = int(buf[i, 4:8].view(np.int32)[0])
+            recs.append(buf[i, :16 + 2 * turns].tobytes())
+        gpu.N.check(s.L.cz_search_drain_visits(s.h, None, 0, C.byref(n), None, s._stream()), "count")
+        vbuf = np.zeros((max(1, n.value), gpu.S.VISIT_STRIDE), dtype=np.uint8)
+        qbuf = np.zeros(max(1, n.value), dtype=np.float64)
+        if with_q:
+            gpu.N.check(s.L.cz_search_drain_visits_q(s.h, vbuf.ctypes.data, qbuf.ctypes.data, n.value, C.byref(n), None,
+                                                     s._stream()), "visits_q")
+        else:
+            gpu.N.check(s.L.cz_search_drain_visits(s.h, vbuf.ctypes.data, n.value, C.byref(n), None, s._stream()), "visits")
+        for i in range(n.value):
+            ne = int(vbuf[i, 6])
+            row = vbuf[i, :16 + 2 * ne].tobytes() + vbuf[i, 16 + 256:16 + 256 + 4 * ne].tobytes()
+            entries.append((row, qbuf[i:i + 1].tobytes()) if with_q else row)
+    for r in range(rounds):
+        s.round()
+        p, v = ev(s.planes)
+        s.policy.copy_(p)
+        s.value.copy_(v)
+        if r % 16 == 15:                                    # (before either ring can fill)
+            drain()
+    drain()
+    ctr = s.counters()
+    s.close()
+    assert ctr["visits_dropped"] == 0
+    return sorted(recs), sorted(entries), ctr
+
+
+@pytest.mark.parametrize("K", [1, 8])
+def test_values_off_leaves_every_record_entry_and_counter(gpu, K):
+    pc = play_config(simulation_num_per_move=16, search_threads=K, tau_decay_rate=0.9, max_game_length=8,
+                     enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
+    rounds = 400 if K == 1 else 120
+    base, vis0, c0 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: None)
+    off, vis1, c1 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.record_values(False))
+    back, vis2, c2 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: (s.record_values(True), s.record_values(False)))
+    assert len(base) >= 32 and len(vis0) > len(base)
+    assert off == base and back == base
+    assert vis1 == vis0 and vis2 == vis0
+    assert c0 == c1 == c2
+    # with the values ON the visit ring and the records still hold the same bytes, through either drain
+    on, vis3, c3 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.record_values(True))
+    assert on == base and vis3 == vis0 and c3 == c0
+    on_q, vis4, c4 = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.record_values(True), with_q=True)
+    assert on_q == base and sorted(row for row, _ in vis4) == vis0 and c4 == c0
+    qs = np.array([np.frombuffer(q, dtype=np.float64)[0] for _, q in vis4])
+    assert np.isfinite(qs).sum() > len(qs) // 2 and (np.abs(qs[np.isfinite(qs)]) <= 2.0).all()
+    assert len({q for _, q in vis4}) > 8                    # (values of their entries, not a constant)
+
+
+# ---- 6. the loss kernel -----------------------------------------------------------------------------------------------------
+def _games_with_q(seed, n_games, nan_rate=0.3):
+    """random_games with visit counts, every item widened to [move, value, pi or None, 1, q or None]."""
+    rng = np.random.default_rng(seed)
+    games = random_games(seed, n_games, max_plies=30, pi=True)
+    for g in games:
+        for it in g[1:]:
+            it += [None] * (3 - len(it)) + [1, None if rng.random() < nan_rate else round(float(rng.uniform(-2, 2)), 6)]
+    return games
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_loss_kernel_with_a_mixed_value_target(dev, mirror):
+    import torch
+    from cchess_alphazero import _native
+    from cchess_alphazero.lib.replay_window import mix_targets
+    B = 64
+    w = window_of(_games_with_q(41, 10))
+    n = len(w)
+    rng = np.random.default_rng(6)
+    idx_h = rng.integers(0, n, size=B).astype(np.int32)
+    idx = torch.from_numpy(idx_h).to(dev)
+    logits = torch.from_numpy(rng.normal(0, 2, size=(B, 2086)).astype(np.float32)).to(dev)
+    v = torch.from_numpy(np.tanh(rng.normal(size=B)).astype(np.float32)).to(dev)
+    flags = torch.from_numpy(rng.integers(0, 2, size=B).astype(np.uint8)).to(dev) if mirror else None
+    wp, wv = 1.25, 0.75
+    args = (w.played[:n], w.z[:n], w.row_ptr[:n + 1], w.vis_label[:w.nnz], w.vis_count[:w.nnz], 1, wp, wv)
+    old = _native.policy_value_loss(logits, v, idx, *args, mirror=flags)
+    z = w.z[:n].cpu().numpy()[idx_h]
+    q = w.q[:n].cpu().numpy()[idx_h]
+    assert np.isnan(q).any() and (~np.isnan(q)).sum() > B // 2
+    vv = v.cpu().numpy().astype(np.float64)
+    for lam in (0.0, 0.3, 1.0):
+        pl, se, gl, gv = _native.policy_value_loss(logits, v, idx, *args, mirror=flags, q=w.q[:n], q_ratio=lam)
+        assert torch.equal(pl, old[0]) and torch.equal(gl, old[2]), lam         # the policy side never sees q
+        t = mix_targets(z, q, lam)                                              # NumPy float32, step by step
+        assert (t == w.value_targets(idx, lam)).all()
+        assert np.allclose(se.cpu().numpy(), (vv - t.astype(np.float64)) ** 2, rtol=1e-6, atol=1e-9), lam
+        vg = v.clone().requires_grad_(True)
+        (wv * ((vg - torch.from_numpy(t).to(dev)) ** 2).mean()).backward()
+        assert (vg.grad - gv).abs().max().item() < 1e-6, lam
+        # the kernel's own float32 arithmetic on the same target: the same bits
+        d = v.cpu().numpy() - t
+        assert se.cpu().numpy().tobytes() == (d * d).astype(np.float32).tobytes(), lam
+        if lam == 0.0:
+            assert torch.equal(se, old[1]) and torch.equal(gv, old[3])
+        else:
+            assert not torch.equal(se, old[1])
+            nan = torch.from_numpy(np.isnan(q)).to(dev)
+            assert torch.equal(se[nan], old[1][nan]) and torch.equal(gv[nan], old[3][nan])      # t = z where q is NaN
+    # q = NULL through the new entry point: the old bits, whatever the ratio
+    L = _native.lib()
+    out = [torch.empty_like(x) for x in old]
+    p = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    call = lambda qp, lam: L.cz_policy_value_loss_q(  # noqa: E731
+        p(logits), logits.stride(0), p(v), p(idx), p(flags), B, n, p(w.row_ptr), p(w.vis_label), p(w.vis_count), w.nnz,
+        p(w.played), p(w.z), qp, lam, 1, wp, wv, *[p(x) for x in out], st)
+    assert call(None, 0.7) == 0
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(out, old))
+    for bad in (-0.1, 1.5, float("nan")):
+        assert call(p(w.q), bad) == ERR_ARG, bad
+
+
+# ---- 7. the window ----------------------------------------------------------------------------------------------------------
+def test_window_keeps_q_and_refuses_a_malformed_one(dev):
+    games = _games_with_q(43, 6)
+    w = window_of(games)
+    items = [it for g in games for it in g[1:]]
+    n = len(w)
+    assert n == len(items) and w.trainable.all()
+    q = w.q[:n].cpu().numpy()
+    want = np.array([np.nan if it[4] is None else it[4] for it in items], dtype=np.float32)
+    assert q.dtype == np.float32 and q.tobytes() == want.tobytes()
+    idx = np.arange(n)
+    z = w.z[:n].cpu().numpy()
+    for lam in (0.0, 0.5, 1.0):
+        t = w.value_targets(idx, lam)
+        ref = qo.mix_f64(z, q, float(np.float32(lam)))
+        assert t.dtype == np.float32 and np.abs(t - ref).max() <= 8 * 2.0 ** -24       # (tests/test_q_record_cpu.py has the bound)
+        assert (t[np.isnan(q)] == z[np.isnan(q)]).all()
+    assert w.value_targets(idx, 0.0).tobytes() == z.tobytes()
+    # shorter items and older records mix freely: NaN
+    old = random_games(44, 3, pi=True)
+    w.add_games(old)
+    assert np.isnan(w.q[n:len(w)].cpu().numpy()).all() and w.q[:n].cpu().numpy().tobytes() == want.tobytes()
+    # a malformed q raises, names the game and the ply, and leaves the window as it was
+    before = (len(w), w.nnz, w.n_games, w.q[:len(w)].cpu().numpy().tobytes(), w.z[:len(w)].cpu().numpy().tobytes())
+    long = next(g for g in games if len(g) >= 3)
+    for bad in (2.5, -2.0001, float("nan"), float("inf"), "0.5", True, [0.5]):
+        g = [copy.deepcopy(long), copy.deepcopy(long)]
+        g[1][2][4] = bad
+        with pytest.raises(ValueError, match=r"game 1, ply 1"):
+            w.add_games(g)
+        assert (len(w), w.nnz, w.n_games, w.q[:len(w)].cpu().numpy().tobytes(), w.z[:len(w)].cpu().numpy().tobytes()) == before
+    for ok in (2, -2.0, 0, None):
+        g = [copy.deepcopy(long)]
+        g[0][1][4] = ok
+        got = window_of(g).q[0].item()
+        assert math.isnan(got) if ok is None else got == ok
+
+
+def test_q_ratio_over_old_records_is_a_pass_with_0(dev, tmp_path, monkeypatch):
+    """Records written before the value record have no q: every row's target is z, and a trainer with --q-ratio 0.5 walks
+    the same parameters as one with 0, bit for bit."""
+    import torch
+    from cchess_alphazero.agent.model import CChessModel
+    from cchess_alphazero.worker.optimize import OptimizeWorker
+    games = random_games(21, 10, pi=True)
+    states = []
+    # (the convolutions' backward pass repeats bit for bit only in the library's deterministic mode: without it two
+    #  passes with the SAME ratio already differ after one step, in the 7th digit -- measured, not this option's doing)
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+    for lam in (0.0, 0.5):
+        cfg = small_config(tmp_path, monkeypatch, batch_size=32, policy_targets="visits", q_ratio=lam)
+        ow = OptimizeWorker(cfg)
+        assert ow.q_ratio == lam
+        ow.model = CChessModel(cfg)
+        ow.model.build(seed=3)
+        ow.model.model.cuda().train()
+        ow.compile_model()
+        ow.update_learning_rate(0)
+        ow.window = window_of(games)
+        assert np.isnan(ow.window.q[:len(ow.window)].cpu().numpy()).all()
+        rng = np.random.default_rng(0)
+        losses = []
+        for _ in range(3):
+            idx = rng.permutation(len(ow.window))[:32].astype(np.int32)
+            losses.append([x.item() for x in ow.step(torch.from_numpy(idx).to(dev))])
+        val = ow.evaluate(torch.arange(32, dtype=torch.int32, device=dev))
+        states.append((losses, val, {k: v.clone() for k, v in ow.model.model.state_dict().items()}))
+    assert states[0][0] == states[1][0] and states[0][1] == states[1][1]
+    for name, a in states[0][2].items():
+        assert torch.equal(a, states[1][2][name]), name
+    with pytest.raises(ValueError, match="q_ratio"):
+        OptimizeWorker(small_config(tmp_path, monkeypatch, q_ratio=1.5))
+
+
+# ---- 8. arguments -----------------------------------------------------------------------------------------------------------
+def test_record_values_argument_errors_leave_the_setting(gpu):
+    pc = play_config(simulation_num_per_move=16, search_threads=4, max_game_length=6)
+    s = gpu.S.Search(pc, 2, seed=1)
+    st = s._stream()
+    L = s.L
+    # without the visit ring: refused, and the object stays off
+    assert L.cz_search_record_values(s.h, 1, st) == ERR_ARG
+    with pytest.raises(gpu.N.NativeError):
+        s.record_values(True)
+    assert not s.values_on
+    assert L.cz_search_record_values(s.h, 0, st) == 0           # switching off what is off is no error
+    assert L.cz_search_record_values(None, 1, st) == ERR_ARG
+    s.record_visits(True, capacity=64)
+    s.record_values(True)
+    assert s.values_on
+    n = C.c_int(-1)
+    buf = np.zeros((64, gpu.S.VISIT_STRIDE), dtype=np.uint8)
+    qb = np.zeros(64, dtype=np.float64)
+    assert L.cz_search_drain_visits_q(s.h, None, None, 0, C.byref(n), None, st) == 0 and n.value == 0
+    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, None, 64, C.byref(n), None, st) == ERR_ARG       # no q_buf
+    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, -1, C.byref(n), None, st) == ERR_ARG
+    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, 64, None, None, st) == ERR_ARG
+    assert L.cz_search_root_value(s.h, None, st) == ERR_ARG
+    assert L.cz_search_root_value(None, C.c_void_p(gpu.torch.empty(2, dtype=gpu.torch.float64, device="cuda").data_ptr()),
+                                  st) == ERR_ARG
+    # the setting is kept after the refusals: a short self-play run still hands out values
+    s.start_selfplay(seed=1)
+    ev = stub_eval(gpu, SPEC)
+    for _ in range(40):
+        s.round()
+        p, v = ev(s.planes)
+        s.policy.copy_(p)
+        s.value.copy_(v)
+    ents = [e for es in s.waiting_visits().values() for e in es]
+    assert ents and sum(e.q is not None for e in ents) > 0
+    # a root that is not in the tree has no value; the visit ring going takes the value ring with it
+    s.record_visits(False)
+    assert not s.values_on
+    assert L.cz_search_record_values(s.h, 1, st) == ERR_ARG
+    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, 64, C.byref(n), None, st) == ERR_ARG
+    s.close()
+    s = gpu.S.Search(pc, 2, seed=1)
+    assert np.isnan(s.root_value()).all()
+    s.close()
+    from cchess_alphazero.engine import SelfPlayEngine
+    with pytest.raises(ValueError, match="record_visits"):
+        SelfPlayEngine(_engine_cfg(pc), 2, evaluator=stub_eval(gpu, SPEC), record_q=True)
+
+
+# ---- 9. the command line ----------------------------------------------------------------------------------------------------
+def test_run_py_self_with_record_q_then_opt_with_q_ratio(tmp_path, monkeypatch):
+    from cchess_alphazero import manager
+    from cchess_alphazero.agent.model import CChessModel
+    from cchess_alphazero.lib.data_helper import get_game_data_filenames, read_game_data_from_file
+    from cchess_alphazero.lib.record_decoder import split_games
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, "chinesechess-alphazero_amd")
+    env = dict(os.environ, DATA_DIR=str(tmp_path / "data"), PROJECT_DIR=str(tmp_path), PYTHONPATH=pkg)
+    run = [sys.executable, os.path.join(pkg, "cchess_alphazero", "run.py"), "self", "--type", "mini"]
+    r = subprocess.run(run + ["--record-q"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "needs --record-visits" in r.stderr
+    r = subprocess.run(run + ["--games-per-gpu", "32", "--record-visits", "--record-q", "--forced-playouts", "2",
+                              "--fast-sims", "8", "--max-games", "8"], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with open(tmp_path / "logs" / "play.log") as f:
+        log = f.read()
+    assert "root search value q" in log
+    m = re.search(r"search values of (\d+) plies written, mean \|q - z\| = ([0-9.]+)", log)
+    assert m and int(m.group(1)) > 0 and 0.0 <= float(m.group(2)) <= 3.0
+    monkeypatch.setenv("DATA_DIR", str(tmp_path / "data"))
+    monkeypatch.setenv("PROJECT_DIR", str(tmp_path))
+    build = manager.build_config
+
+    def small(args):                                        # the command line's config at test size
+        cfg = build(args)
+        cfg.model.cnn_filter_num, cfg.model.res_layer_num = 32, 2
+        cfg.trainer.batch_size = 16
+        return cfg
+    monkeypatch.setattr(manager, "build_config", small)
+    cfg = small(manager.create_parser().parse_args(["opt"]))
+    rc = cfg.resource
+    files = get_game_data_filenames(rc)
+    assert files
+    items = [it for p in files for g in split_games(read_game_data_from_file(p)) for it in g[1:]]
+    five = [it for it in items if len(it) == 5]
+    assert five and {it[3] for it in five} == {0, 1} and any(it[4] is not None for it in five)
+    assert all(it[4] is None or abs(it[4]) <= 2.0 for it in five) and all(len(it) in (2, 5) for it in items)
+    model = CChessModel(cfg)
+    model.build(seed=0)
+    model.save(rc.model_best_config_path, rc.model_best_weight_path)
+    digest0 = model.digest
+    monkeypatch.setattr(sys, "argv", ["run.py", "opt", "--type", "mini", "--q-ratio", "0.5", "--policy-targets", "visits"])
+    handlers, level = list(logging.getLogger().handlers), logging.getLogger().level
+    try:
+        total = manager.start()
+    finally:
+        logging.getLogger().setLevel(level)
+        for h in logging.getLogger().handlers[len(handlers):]:
+            logging.getLogger().removeHandler(h)
+            h.close()
+    assert total > 0
+    with open(rc.opt_log_path) as f:
+        vz = re.findall(r"val_value_z ([0-9.a-z+-]+)", f.read())
+    assert vz and all(math.isfinite(float(x)) for x in vz)
+    best = CChessModel(cfg)
+    assert best.load(rc.model_best_config_path, rc.model_best_weight_path) and best.digest != digest0
