@@ -383,6 +383,12 @@ def bias_act_(x, bias, residual=None, relu=True):
     global _DT_CODE
     if _DT_CODE is None:
         _DT_CODE = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+    # the kernel reads bias and residual as x's element type, through raw pointers: anything else would be read as garbage
+    if bias.dtype != x.dtype or bias.device != x.device:
+        raise ValueError(f"bias_act_: bias is {bias.dtype} on {bias.device}, x is {x.dtype} on {x.device}")
+    if residual is not None and (residual.dtype != x.dtype or residual.device != x.device or residual.shape != x.shape):
+        raise ValueError(f"bias_act_: residual is {residual.dtype} {tuple(residual.shape)} on {residual.device}, "
+                         f"x is {x.dtype} {tuple(x.shape)} on {x.device}")
     c = bias.numel()
     check(lib().cz_bias_act(C.c_void_p(x.data_ptr()), C.c_void_p(bias.data_ptr()),
                             C.c_void_p(residual.data_ptr()) if residual is not None else None,

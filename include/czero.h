@@ -635,7 +635,12 @@ int cz_head_convs(const void* x, int dtype, const float* w, const float* bias, f
  *                            cz_search_policy_logits(h, 1), which needs the legal moves' entries only
  * Precision: operands as (hi, lo) pairs, three MFMAs per product, fp32 accumulation -- the tower's arithmetic: 2^-17 per
  * product with bf16 pairs, 2^-21 class with fp16 pairs (22 bits per operand; the head features are O(1), well inside
- * fp16's range, and the matrix unit honours fp16 subnormals -- tools/f16x3_probe.py). */
+ * fp16's range, and the matrix unit honours fp16 subnormals -- tools/f16x3_probe.py).
+ * Range: the features are split into pairs inside the kernel and nothing checks them.  CZ_F16: |feature| < 65 504 (fp16's
+ * largest value; a larger feature becomes inf and the row's outputs NaN); the per-element bounds are tested up to 3.0e4
+ * (tests/test_gpu_heads.py).  CZ_BF16: fp32's whole range.  A search guard's activation_max covers the tower only, not these
+ * features.  Shapes: n_labels may be any even number >= 2 and n_hidden any number >= 1 (partial and odd counts of 32-wide
+ * label tiles included); only the feature counts are fixed to 180 or 360. */
 int cz_heads_tail(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
                   int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed, const float* bias1,
                   int n_hidden, const float* w2, float b2, float* policy, float* value, float* stats_scratch,

@@ -1,5 +1,7 @@
 """Float64 model of the fp16-pair ("f16x3") tower arithmetic and the per-element bounds its kernels are held to
-(tests/test_gpu_f16x3.py; the bounds themselves are tested on faulty arithmetic in tests/test_f16x3_bounds_cpu.py).
+(tests/test_gpu_f16x3.py; the bounds themselves are tested on faulty arithmetic in tests/test_f16x3_bounds_cpu.py), and,
+in the second part of this docstring, of the heads' dense tail on fp16 or bf16 pairs (tests/test_gpu_heads.py,
+tests/test_dense_bounds_cpu.py).
 
 The arithmetic.  An fp32 operand v is stored as hi = fp16(v), lo = fp16(v - hi), both rounded to nearest even, and a
 product is formed as  w_hi x_hi + w_lo x_hi + w_hi x_lo  (w_lo x_lo is dropped), accumulated in fp32.
@@ -31,7 +33,65 @@ The bounds, per output element y of a convolution with bias b and optional (hi, 
 
 Everything here works on numpy float64 arrays and on torch float64 tensors alike (only slicing, matmul, abs and
 arithmetic), so the CPU test feeds the check the very function the GPU tests use.  Activations are channels-last
-[n, 90, C] (the kernels' layout), filters [C_out, C_in, K, K]."""
+[n, 90, C] (the kernels' layout), filters [C_out, C_in, K, K].
+
+THE DENSE TAIL OF THE HEADS (csrc/xq_heads.hip: k_fc_tile, k_policy_normalize; pair_dense, DenseCheck, stat_rel,
+softmax_check, value_check below).
+
+Dense layers on (hi, lo) pairs.  y = sum_k (w_hi x_hi + w_lo x_hi + w_hi x_lo) + b over K-steps of 16 features in index
+order, the three terms of a step one matrix instruction each (in that order), fp32 accumulation, one fp32 addition for the
+bias.  Features [n, F], weights [n_out, F].
+
+Pair formats.  fp16: e(v) as derived above (F16_PAIR).  bf16 (BF16_PAIR): bf16 keeps 8 significant bits, so
+hi = bf16(v) is off by at most half a unit of the 8th bit, |v - hi| <= 2^-8 |v|; the remainder v - hi is exact in fp32 (it has
+at most 16 significant bits) and lo = bf16(v - hi) rounds it to 8 more bits: |v - hi - lo| <= 2^-8 |v - hi| <= 2^-16 |v|.  bf16
+has fp32's exponent range, so lo is a normal number down to 2^-126; below that its step is 2^-133 (absolute error 2^-134):
+e(v) = 2^-16 |v| + 2^-134.  The dropped term is |w_lo x_lo| <= 2^-16 |w x|.  A value that is exactly 0 has e = 0 in either format
+(DenseCheck uses that: the features are zero after a ReLU half of the time).
+
+Logits, per element (DenseCheck):
+(a) same operands:  ACC + U (|y| + |b|),  ACC = LAMBDA U sqrt(sum_s N_s / 3 (|P_(s-1)| + A_s)^2), N_s = 3 min(16, F - 16 s)
+    (the accumulation model of the convolution's bound (a)), and the bias addition is one rounding of at most U |y + b|.
+(b) exact fp32 operands:  (a) + sum_k (|w_lo x_lo| + e(w) |x| + |w_hi + w_lo| e(x)).
+
+Value output  v = tanh(d), d = sum_j relu(y_j + b1_j) w2_j + b2  (value_check).  ReLU is 1-Lipschitz, so a hidden unit is off by
+at most its logit bound B_j.  The kernel's fp32 dot (the library is built with -ffp-contract=off: a product and an addition
+round separately): a lane adds its T = 32 ceil(tiles / 8) hidden units (tiles = ceil(n_hidden / 32); 2 tiles x 16 accumulator
+rows per pass over the label tiles) one after the other, 2 T roundings; one shuffle addition joins the half-waves; the four
+waves' sums are added to 0 in turn (the first addition is exact: 3 roundings).  Every one of these roundings is at most U times
+a partial sum of |h_j w2_j| over a subset of the units, and a term passes through at most n = 2 T + 4 of them, so their sum
+is at most gamma_n A with A = sum_j (|h_j| + B_j) |w2_j|, gamma_n = n U / (1 - n U).  The bias: U (|d - b2| + |b2|), one rounding of
+the sum; b2 itself must be the fp32 value the kernel is handed (value_check refuses any other: a double such as 0.13 would
+add its own conversion error, up to U |b2|, which this bound does not carry).
+    |delta d| <= sum_j B_j |w2_j| + gamma_n A + U (|d - b2| + |b2|);  tanh is 1-Lipschitz;  + TANH_REL |v| for tanhf.
+
+Softmax output  p_j = exp(l_j) / sum_k exp(l_k)  (softmax_check).  With logits off by delta_k, |delta_k| <= B_k, the exact
+softmax of the kernel's logits is p_j exp(delta_j) sum_k exp(l_k) / sum_k exp(l_k + delta_k), a factor within
+exp(+-(B_j + max_k B_k)) of p_j.  The kernel's own arithmetic on its logits adds the relative error STAT.  A quotient below
+the smallest normal float 2^-126 keeps no relative accuracy, so the bound is
+    |delta p_j| <= (expm1(B_j + max_k B_k) + STAT) p_j + 2^-126.
+
+STAT, by counting roundings (first order in U; the products of two such terms are below 1e-9 of p).  fexp(x) =
+v_exp_f32(x log2e): the fp32 constant and the product are each off by U relative, moving the exponent by 2 U |x| log2e, the
+result by 2 U |x| relative; x itself is a rounded difference, U |x| more; the instruction adds EXP2_REL: 3 U |x| + EXP2_REL.
+A lane walks G = 8 ceil(tiles / 8) groups of four labels (tiles = ceil(n_labels / 32)).  In each it rescales its sum
+(one fexp, one product: EXP2_REL + U + 3 U Delta, Delta the rise of the running maximum) and adds four terms (4 U, all terms
+positive).  The half-waves are joined by a rescaling and an addition (EXP2_REL + 2 U + 3 U Delta), the four waves by a rescaling
+and four additions (EXP2_REL + 5 U + 3 U Delta).  The term of label k therefore carries at most
+(G + 2) EXP2_REL + (5 G + 11) U + 3 U t_k, where t_k = max - l_k is what its own argument and all later rises add up to.
+Weighted by p_k the last part is 3 U sum_k p_k t_k <= 3 U ln(n_labels) (sum_k p_k t_k = H(p) - ln(sum) <= the entropy).
+k_policy_normalize: t_j = fl(l_j - max) moves exp by U t_j, and t_j <= 126 ln 2 < 88 where p_j >= 2^-126; expf adds EXPF_REL;
+the division is correctly rounded (measured: 1.000 U): U.
+    STAT = (G + 2) EXP2_REL + (5 G + 11 + 3 ln n_labels) U + 88 U + EXPF_REL + U.
+For 2086 labels G = 72 and STAT = 708 U = 4.2e-5.
+
+Library terms, MEASURED (the ROCm installation carries no accuracy statement for them): on an MI355X on 2026-10-17, fp32
+results of the device library's exp, exp2 (the v_exp_f32 instruction plus a scaling for denormal results) and tanh, called
+through PyTorch's elementwise kernels, against float64 of the same fp32 arguments, 2^25 arguments each (uniform random and an
+even grid): exp on [-87, 0] 1.411 U relative, exp2 on [-125, 0] 1.393 U, tanh on [-20, 20] 2.486 U relative (|x| > 2^-12;
+1.067 U on [2^-42, 0.25]).  Each constant is twice the measured maximum, rounded up.
+tests/test_gpu_heads.py::test_library_terms_through_the_kernels holds the kernels' own tanhf / expf / fexp calls to these
+constants on exact arguments (measured there: 0.42 and 0.47 of the constants)."""
 import numpy as np
 
 U = 2.0 ** -24                  # fp32 unit roundoff
@@ -42,9 +102,13 @@ LAMBDA = 8.0
 CAP = 3.0e4                     # the guard's f16x3 admission cap on |activation| (agent/model.py guard_search)
 
 
-def pair_err(v):
-    """The format bound e(v) of an fp16 (hi, lo) pair standing for v."""
-    return PAIR_REL * abs(v) + PAIR_ABS
+F16_PAIR = (PAIR_REL, PAIR_ABS)                 # (relative, absolute) part of e(v), fp16 pairs: derived above
+BF16_PAIR = (2.0 ** -16, 2.0 ** -134)           # bf16 pairs: derived in the module docstring's dense-layer part
+
+
+def pair_err(v, fmt=F16_PAIR):
+    """The format bound e(v) of a (hi, lo) pair of format `fmt` (F16_PAIR, BF16_PAIR) standing for v."""
+    return fmt[0] * abs(v) + fmt[1]
 
 
 def split16(v):
@@ -149,3 +213,112 @@ def mixed_activations(shape, rng, cap=CAP):
     v = np.where(kind == 4, logu(-3.0, 2.0), v)
     v = np.where(kind == 5, logu(2.0, np.log2(cap)), v)
     return v.astype(np.float32)
+
+
+# ---- the dense tail of the heads (csrc/xq_heads.hip: k_fc_tile, k_policy_normalize) -----------------------------------------
+# (derivations: the module docstring's part THE DENSE TAIL OF THE HEADS)
+EXPF_REL = 3.0 * U
+EXP2_REL = 3.0 * U
+TANH_REL = 5.0 * U
+P_FLOOR = 2.0 ** -126
+
+
+def split_pair(v, fmt=F16_PAIR):
+    """(hi, lo) of an fp32 numpy array in pair format `fmt`, as float32 arrays, both parts rounded to nearest even."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    if fmt is F16_PAIR:
+        hi, lo = split16(v)
+        return hi.astype(np.float32), lo.astype(np.float32)
+
+    def bf16(a):
+        u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+        u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+        return u.astype(np.uint32).view(np.float32)
+    hi = bf16(v)
+    return hi, bf16(v - hi)
+
+
+def _fn(t, name):
+    return getattr(np, name)(t) if isinstance(t, np.ndarray) else getattr(t, name)()
+
+
+def _rowmax(t):
+    return t.max(axis=1, keepdims=True) if isinstance(t, np.ndarray) else t.amax(dim=1, keepdim=True)
+
+
+def pair_dense(x_hi, x_lo, w_hi, w_lo):
+    """sum_k (w_hi x_hi + w_lo x_hi + w_hi x_lo) in float64 for features [n, F] and weights [n_out, F] (the products of the
+    2-byte values are exact, the sums good to 2^-50), and the accumulation bound ACC for it, K-step by K-step."""
+    f = x_hi.shape[-1]
+    y = q = None
+    for k0 in range(0, f, 16):
+        k = slice(k0, k0 + 16)
+        xh, xl, wh, wl = x_hi[:, k], x_lo[:, k], w_hi[:, k].T, w_lo[:, k].T
+        c = xh @ wh + xh @ wl + xl @ wh
+        a = abs(xh) @ abs(wh) + abs(xh) @ abs(wl) + abs(xl) @ abs(wh)
+        s = a if y is None else abs(y) + a
+        m = 3 * min(16, f - k0)
+        q = m / 3.0 * s * s if q is None else q + m / 3.0 * s * s
+        y = c if y is None else y + c
+    return y, LAMBDA * U * q ** 0.5
+
+
+class DenseCheck:
+    """The per-element check of a dense layer on (hi, lo) pairs of format `fmt`, its float64 parts computed once for the
+    operands: x_pair / w_pair the pairs' values, x / w the fp32 operands they split; all float64, numpy arrays or torch
+    tensors on one device.  Features [n, F], weights [n_out, F]."""
+
+    def __init__(self, x_pair, w_pair, x, w, fmt=F16_PAIR):
+        (xh, xl), (wh, wl) = x_pair, w_pair
+        self.y3, self.acc = pair_dense(xh, xl, wh, wl)
+        self.exact = x @ w.T
+        ex, ew = pair_err(x, fmt) * (x != 0), pair_err(w, fmt) * (w != 0)
+        self.rep = abs(xl) @ abs(wl).T + abs(x) @ ew.T + ex @ abs(wh + wl).T
+
+    def bounds(self, bias):
+        """(y_a, bound_a, y_b, bound_b): the logits y + bias on the same / the exact operands and their bounds."""
+        ba = self.acc + U * (abs(self.y3) + abs(bias))
+        return self.y3 + bias, ba, self.exact + bias, ba + self.rep
+
+    def ratios(self, got, bias):
+        """Worst |error| / bound over the elements against (a) and (b); got: the kernel's logits as float64."""
+        ya, ba, yb, bb = self.bounds(bias)
+        return float((abs(got - ya) / ba).max()), float((abs(got - yb) / bb).max())
+
+
+def stat_rel(n_labels):
+    """STAT of the module docstring (dense tail, softmax output) for a softmax over n_labels."""
+    g = 8 * -(-(-(-n_labels // 32)) // 8)
+    return (g + 2) * EXP2_REL + (5 * g + 11 + 3 * float(np.log(n_labels))) * U + 88 * U + EXPF_REL + U
+
+
+def softmax_check(logits, bound):
+    """(p, bound_p): the float64 softmax of the reference logits [n, n_labels] and the bound on the kernel's probabilities,
+    given the per-element bound on its logits."""
+    e = _fn(logits - _rowmax(logits), "exp")
+    p = e / e.sum(1)[:, None]
+    return p, (_fn(bound + _rowmax(bound), "expm1") + stat_rel(logits.shape[1])) * p + P_FLOOR
+
+
+def value_check(hidden, bound, w2, b2):
+    """(v, bound_v, d): the float64 value tanh(relu(hidden) . w2 + b2) of the reference pre-activations hidden [n, n_hidden]
+    (bias included), the bound on the kernel's value given the per-element bound on its pre-activations, and d.  b2: a Python
+    float that fp32 holds exactly."""
+    assert float(np.float32(b2)) == b2, "b2 must be exact in fp32: the kernel takes it as a float"
+    h = hidden * (hidden > 0)
+    t = 32 * -(-(-(-hidden.shape[1] // 32)) // 8)
+    n = 2 * t + 4
+    d0 = h @ w2
+    v = _fn(d0 + b2, "tanh")
+    bd = bound @ abs(w2) + n * U / (1.0 - n * U) * ((h + bound) @ abs(w2)) + U * (abs(d0) + abs(b2))
+    return v, bd + TANH_REL * abs(v), d0 + b2
+
+
+def dense_features(kind, n, f, rng):
+    """The fp32 head features [n, f] of the dense tests: "O(1)" = relu(randn) 1.5, or "mixed" = mixed_activations over
+    [n, 90, f / 90] (row r draws from regime r % 3; at most CAP) with rows 5, 12, 19, ... all zero."""
+    if kind == "mixed":
+        x = mixed_activations((n, 90, f // 90), rng, cap=CAP).reshape(n, f)
+        x[5::7] = 0.0
+        return x
+    return (np.maximum(rng.standard_normal((n, f)), 0.0) * 1.5).astype(np.float32)
