@@ -39,6 +39,40 @@ def lib():
     return _lib
 
 
+def _nn_signatures():
+    """name -> (restype, argtypes) of the network entry points and their packers (include/czero.h)."""
+    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
+    return {
+        "cz_bias_act": (i32, [vp, vp, vp, sz, i32, i32, i32, vp]),
+        "cz_conv3x3": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "cz_conv3x3_packed_elems": (sz, [i32, i32]),
+        "cz_conv3x3_pack_weights": (i32, [vp, i32, i32, i32, vp]),
+        "cz_head_convs": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "cz_input_conv": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "cz_input_conv_packed_elems": (sz, [i32, i32, i32]),
+        "cz_input_conv_pack_weights": (i32, [vp, i32, i32, i32, i32, vp]),
+        "cz_resblock_heads": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+        "cz_resblock": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+        "cz_input_conv_q": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "cz_resblock_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+        "cz_resblock_heads_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "cz_split_bias_act": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
+        "cz_conv3x3_c8_packed_bytes": (sz, [i32]),
+        "cz_conv3x3_c8_pack_weights": (i32, [vp, i32, vp]),
+        "cz_conv3x3_c6_pack_weights": (i32, [vp, i32, i32, i32, vp]),
+        "cz_conv3x3_c8": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "cz_input_resblock": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "cz_input_resblock_m": (i32, [vp, vp, i32] + [vp] * 8 + [i32] * 3 + [vp] * 3),
+        "cz_tower": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "cz_resblock_chain": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "cz_tower_plain": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "cz_tower_pairs": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+        "cz_heads_tail": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "cz_fc_packed_elems": (sz, [i32, i32]),
+        "cz_fc_pack_weights": (i32, [vp, i32, i32, i32, vp]),
+    }
+
+
 def _declare(L):
     vp, i32 = C.c_void_p, C.c_int
     L.cz_version.restype = i32
@@ -53,65 +87,10 @@ def _declare(L):
     L.cz_be_catched.argtypes = [vp, vp, i32, vp, vp]
     L.cz_has_attack.argtypes = [vp, i32, vp, vp]
     L.cz_rules_fused.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
-    if hasattr(L, "cz_bias_act"):
-        L.cz_bias_act.argtypes = [vp, vp, vp, C.c_size_t, i32, i32, i32, vp]
-        L.cz_bias_act.restype = i32
-    if hasattr(L, "cz_conv3x3"):
-        L.cz_conv3x3.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.cz_conv3x3.restype = i32
-        L.cz_conv3x3_packed_elems.argtypes = [i32, i32]
-        L.cz_conv3x3_packed_elems.restype = C.c_size_t
-        L.cz_conv3x3_pack_weights.argtypes = [vp, i32, i32, i32, vp]
-        L.cz_conv3x3_pack_weights.restype = i32
-        L.cz_head_convs.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.cz_head_convs.restype = i32
-        L.cz_input_conv.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.cz_input_conv.restype = i32
-        L.cz_input_conv_packed_elems.argtypes = [i32, i32, i32]
-        L.cz_input_conv_packed_elems.restype = C.c_size_t
-        L.cz_input_conv_pack_weights.argtypes = [vp, i32, i32, i32, i32, vp]
-        L.cz_input_conv_pack_weights.restype = i32
-        L.cz_resblock_heads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.cz_resblock_heads.restype = i32
-        L.cz_resblock.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.cz_input_conv_q.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.cz_resblock_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-        L.cz_resblock_heads_q.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-        for _n in ("cz_input_conv_q", "cz_resblock_q", "cz_resblock_heads_q"):
-            getattr(L, _n).restype = i32
-        L.cz_resblock.restype = i32
-        L.cz_split_bias_act.argtypes = [vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, vp]
-        L.cz_split_bias_act.restype = i32
-    if hasattr(L, "cz_conv3x3_c8"):
-        L.cz_conv3x3_c8_packed_bytes.argtypes = [i32]
-        L.cz_conv3x3_c8_packed_bytes.restype = C.c_size_t
-        L.cz_conv3x3_c8_pack_weights.argtypes = [vp, i32, vp]
-        L.cz_conv3x3_c8_pack_weights.restype = i32
-        L.cz_conv3x3_c6_pack_weights.argtypes = [vp, i32, i32, i32, vp]
-        L.cz_conv3x3_c6_pack_weights.restype = i32
-        L.cz_conv3x3_c8.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        L.cz_conv3x3_c8.restype = i32
-    if hasattr(L, "cz_input_resblock"):
-        L.cz_input_resblock.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
-        L.cz_input_resblock.restype = i32
-    if hasattr(L, "cz_tower"):
-        L.cz_input_resblock_m.restype = i32
-        L.cz_input_resblock_m.argtypes = [vp, vp, i32] + [vp] * 8 + [i32] * 3 + [vp] * 3
-        L.cz_tower.restype = i32
-        L.cz_tower.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-        L.cz_resblock_chain.restype = i32
-        L.cz_resblock_chain.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-        L.cz_tower_plain.restype = i32
-        L.cz_tower_plain.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-        L.cz_tower_pairs.restype = i32
-        L.cz_tower_pairs.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    if hasattr(L, "cz_heads_tail"):
-        L.cz_heads_tail.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp, vp]
-        L.cz_heads_tail.restype = i32
-        L.cz_fc_packed_elems.argtypes = [i32, i32]
-        L.cz_fc_packed_elems.restype = C.c_size_t
-        L.cz_fc_pack_weights.argtypes = [vp, i32, i32, i32, vp]
-        L.cz_fc_pack_weights.restype = i32
+    for name, (restype, argtypes) in _nn_signatures().items():
+        if hasattr(L, name):            # each entry point on its own: an older or partial library declares what it has
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     for name in ("cz_label_tables", "cz_movegen", "cz_done", "cz_step", "cz_encode", "cz_check_or_catch",
                  "cz_be_catched", "cz_has_attack", "cz_rules_fused"):
         getattr(L, name).restype = i32

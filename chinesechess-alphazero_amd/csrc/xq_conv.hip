@@ -42,24 +42,9 @@
 #include "../../include/czero.h"
 #include "xq_c8_kloop.h"
 #include "xq_nn_common.h"
-
-extern "C" void czi_set_error(const char* msg);
-// csrc/xq_tower.hip: a chain of (hi, lo) pair blocks on four matrix waves (k_tower_pairs4<E, 128 / 192>)
-extern "C" int czi_pairs4_launch(const void* x_hi, const void* x_lo, int n_blocks, const void* const* w1, const float* const* b1,
-                                 const void* const* w2, const float* const* b2, void* y_hi, void* y_lo, const float* head_w,
-                                 const float* head_b, float* pol, float* val, int n_pol, int n_boards, int channels, int dtype,
-                                 int n_cu, const int32_t* n_dev, void* stream, float* y_f32);
+#include "xq_nn_launch.h"
 
 namespace {
-
-// Compact evaluation queue (cz_*_q entry points): the number of boards comes from DEVICE memory (no host
-// synchronisation, the launch shape stays fixed so that a round can be replayed from a HIP graph) and the input
-// convolution gathers its planes through a row list.  Set by the _q entry points around the ordinary dispatch code.
-struct QueueCtx {
-    const int32_t* rows = nullptr;      // [n] queue slot of compact board i (input convolution only)
-    const int32_t* n_dev = nullptr;     // [1] boards to process (<= the n_boards argument)
-};
-thread_local QueueCtx g_q;
 
 // ---- geometry shared by both kernels -----------------------------------------------------------------------------
 template <int C, int P, int PARTS> struct Geom {
@@ -689,18 +674,11 @@ __global__ __launch_bounds__((C / 32 / CTW + 4) * 64, (C / 32 / CTW + 4 + 3) / 4
 // to ch.n launches of k_resblock (BASELINE configs[4]; reference tower agent/model.py:41-43).
 namespace pl {
 constexpr int MAX_BLOCKS = 24;
-struct Chain {
-    const void* w1[MAX_BLOCKS];
-    const void* w2[MAX_BLOCKS];
-    const float* b1[MAX_BLOCKS];
-    const float* b2[MAX_BLOCKS];
-    int n;
-};
 }  // namespace pl
 
 template <typename E, int C, int CTW>
 __global__ __launch_bounds__(C / 32 / CTW * 64, 1) void k_tower_plain2(
-    const E* __restrict__ xh, pl::Chain ch, E* __restrict__ yh, int n_boards, const int32_t* __restrict__ n_dev)
+    const E* __restrict__ xh, BlockChain<pl::MAX_BLOCKS> ch, E* __restrict__ yh, int n_boards, const int32_t* __restrict__ n_dev)
 {
     if (n_dev) {
         const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
@@ -1819,14 +1797,7 @@ __global__ __launch_bounds__(512, 1) void k_resblock_pipe(
 // cz_conv3x3 launches.  The last block of a tower writes fp32 (y_f32) straight from the accumulators' epilogue instead.
 namespace ip {
 constexpr int ROW_Y = 90, ROW_Z = 192, ROWS = ROW_Z + 16, COPY_THREADS = 128;       // (ROW_Z: a multiple of 16)
-constexpr int MAX_BLOCKS = 12;
-struct Chain {                      // k_resblock_ip_c8: the consecutive blocks a launch takes every board through (1 .. 12)
-    const void* w1[MAX_BLOCKS];
-    const void* w2[MAX_BLOCKS];
-    const float* b1[MAX_BLOCKS];
-    const float* b2[MAX_BLOCKS];
-    int n;
-};
+constexpr int MAX_BLOCKS = 12;       // k_resblock_ip_c8: the consecutive blocks a launch takes every board through (1 .. 12)
 }
 
 template <typename E, int C>
@@ -2027,7 +1998,7 @@ __global__ __launch_bounds__((C / 32) * 64 + ip::COPY_THREADS, 1) void k_resbloc
 // switch per block; y_f32 applies to the chain's last block.  Same arithmetic as ch.n one-block launches: bit-identical.
 template <int C, int XF = 0, int YF = 0>
 __global__ __launch_bounds__((C / 32) * 64 + ip::COPY_THREADS, 1) void k_resblock_ip_c8(
-    const _Float16* __restrict__ xh, const unsigned char* __restrict__ xc, ip::Chain ch, _Float16* __restrict__ yh,
+    const _Float16* __restrict__ xh, const unsigned char* __restrict__ xc, BlockChain<ip::MAX_BLOCKS> ch, _Float16* __restrict__ yh,
     unsigned char* __restrict__ yc, float* __restrict__ yf_last, int n_boards, const int32_t* __restrict__ n_dev)
 {
     typedef Geom<C, 1, 2> G;
@@ -2414,7 +2385,7 @@ struct Ip4FirstMfma {
 // MIX (with <1, 1>): the chain starts the tower -- its block 0 reads the input layer's c8 image (first filter c8-packed: CZ_F16C86)
 template <int C, int XF, int YF, bool MIX = false>
 __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
-    const _Float16* __restrict__ xh, const unsigned char* __restrict__ xc, ip::Chain ch, _Float16* __restrict__ yh,
+    const _Float16* __restrict__ xh, const unsigned char* __restrict__ xc, BlockChain<ip::MAX_BLOCKS> ch, _Float16* __restrict__ yh,
     unsigned char* __restrict__ yc, float* __restrict__ yf_last, int n_boards, const int32_t* __restrict__ n_dev,
     int exit_mode, HeadArgs hd)
 {
@@ -3303,61 +3274,200 @@ __global__ __launch_bounds__(256) void k_split_bias_act(const float* __restrict_
     }
 }
 
+// ---- launches ------------------------------------------------------------------------------------------------------------
+// One function per kernel, each kernel launched from one place; an entry point ends in nn_launched().
+struct ConvCall {
+    const void *xh, *xl, *wp;
+    const float* bias;
+    const void *sh, *sl;
+    void *yh, *yl;
+    float* yf;
+    int n, relu;
+    hipStream_t st;
+};
+
 template <typename E, int C, int P, int PARTS, int MINW = 1>
-int launch_conv(const void* xh, const void* xl, const void* wp, const float* bias, const void* sh, const void* sl,
-                void* yh, void* yl, float* yf, int n_boards, int relu, hipStream_t st)
+void launch_conv(const ConvCall& a)
 {
-    const unsigned blocks = (unsigned)((n_boards + P - 1) / P);
-    hipLaunchKernelGGL((k_conv3x3<E, C, P, PARTS, MINW>), dim3(blocks), dim3(C / 32 * 64), 0, st, (const E*)xh,
-                       (const E*)xl, (const E*)wp, bias, (const E*)sh, (const E*)sl, (E*)yh, (E*)yl, yf, n_boards,
-                       relu);
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
+    hipLaunchKernelGGL((k_conv3x3<E, C, P, PARTS, MINW>), dim3((unsigned)((a.n + P - 1) / P)), dim3(C / 32 * 64), 0, a.st,
+                       (const E*)a.xh, (const E*)a.xl, (const E*)a.wp, a.bias, (const E*)a.sh, (const E*)a.sl, (E*)a.yh,
+                       (E*)a.yl, a.yf, a.n, a.relu);
 }
 
 template <typename E>
-int dispatch_conv(int channels, int parts, const void* xh, const void* xl, const void* wp, const float* bias,
-                  const void* sh, const void* sl, void* yh, void* yl, float* yf, int n, int relu, hipStream_t st)
+bool dispatch_conv(int channels, int parts, const ConvCall& a)       // false: no kernel for that
 {
-#define CZ_CONV_ARGS xh, xl, wp, bias, sh, sl, yh, yl, yf, n, relu, st
-    if (channels == 128 && parts == 2) return launch_conv<E, 128, 2, 2, 1>(CZ_CONV_ARGS);
-    if (channels == 128 && parts == 1) return launch_conv<E, 128, 2, 1, 2>(CZ_CONV_ARGS);   // 2 workgroups / CU
-    if (channels == 192 && parts == 2) return launch_conv<E, 192, 1, 2, 1>(CZ_CONV_ARGS);
-    if (channels == 192 && parts == 1) return launch_conv<E, 192, 2, 1, 1>(CZ_CONV_ARGS);
-    if (channels == 256 && parts == 2) return launch_conv<E, 256, 1, 2>(xh, xl, wp, bias, sh, sl, yh, yl, yf, n, relu, st);
-    if (channels == 256 && parts == 1) return launch_conv<E, 256, 2, 1>(xh, xl, wp, bias, sh, sl, yh, yl, yf, n, relu, st);
-    if (channels == 32 && parts == 2) return launch_conv<E, 32, 2, 2>(xh, xl, wp, bias, sh, sl, yh, yl, yf, n, relu, st);
-    if (channels == 32 && parts == 1) return launch_conv<E, 32, 4, 1>(xh, xl, wp, bias, sh, sl, yh, yl, yf, n, relu, st);
-    return CZ_ERR_ARG;
+    if (channels == 128 && parts == 2) launch_conv<E, 128, 2, 2, 1>(a);
+    else if (channels == 128 && parts == 1) launch_conv<E, 128, 2, 1, 2>(a);   // 2 workgroups / CU
+    else if (channels == 192 && parts == 2) launch_conv<E, 192, 1, 2, 1>(a);
+    else if (channels == 192 && parts == 1) launch_conv<E, 192, 2, 1, 1>(a);
+    else if (channels == 256 && parts == 2) launch_conv<E, 256, 1, 2>(a);
+    else if (channels == 256 && parts == 1) launch_conv<E, 256, 2, 1>(a);
+    else if (channels == 32 && parts == 2) launch_conv<E, 32, 2, 2>(a);
+    else if (channels == 32 && parts == 1) launch_conv<E, 32, 4, 1>(a);
+    else return false;
+    return true;
 }
 
-// round-to-nearest-even conversions on the host (pack_weights)
-inline uint16_t f32_to_bf16_bits(float f)
+template <int C, int P>
+void launch_conv_c8(const ConvCall& a)
 {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
+    hipLaunchKernelGGL((k_conv3x3_c8<C, P>), dim3((unsigned)((a.n + P - 1) / P)), dim3(C / 32 * 64), 0, a.st,
+                       (const _Float16*)a.xh, (const unsigned char*)a.xl, (const uint4*)a.wp, a.bias, (const _Float16*)a.sh,
+                       (const unsigned char*)a.sl, (_Float16*)a.yh, (unsigned char*)a.yl, a.yf, a.n, a.relu);
 }
-inline float bf16_bits_to_f32(uint16_t h)
+
+struct InputConvCall {
+    const void *planes, *wp;
+    const float* bias;
+    void *yh, *yl;
+    int n, in_planes, relu;
+    QueueCtx q;
+    hipStream_t st;
+};
+
+template <typename E, typename PT, int C, int PARTS, bool C8 = false>
+void launch_input_conv(const InputConvCall& a)
 {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
+    constexpr int P = 2;
+    const dim3 grid((unsigned)((a.n + P - 1) / P)), block(C / 32 * 64);
+    if (a.in_planes <= 16)
+        hipLaunchKernelGGL((k_input_conv<E, PT, C, 1, P, PARTS, C8>), grid, block, 0, a.st, (const PT*)a.planes, (const E*)a.wp,
+                           a.bias, (E*)a.yh, (E*)a.yl, a.n, a.in_planes, a.relu, a.q.rows, a.q.n_dev);
+    else
+        hipLaunchKernelGGL((k_input_conv<E, PT, C, 2, P, PARTS, C8>), grid, block, 0, a.st, (const PT*)a.planes, (const E*)a.wp,
+                           a.bias, (E*)a.yh, (E*)a.yl, a.n, a.in_planes, a.relu, a.q.rows, a.q.n_dev);
 }
-inline uint16_t f32_to_f16_bits(float f)
+
+template <typename E, typename PT>
+bool dispatch_input_conv(int channels, int parts, const InputConvCall& a)
 {
-    const _Float16 h = (_Float16)f;
-    uint16_t b;
-    memcpy(&b, &h, 2);
-    return b;
+    if (channels == 128) { if (parts == 2) launch_input_conv<E, PT, 128, 2>(a); else launch_input_conv<E, PT, 128, 1>(a); }
+    else if (channels == 192) { if (parts == 2) launch_input_conv<E, PT, 192, 2>(a); else launch_input_conv<E, PT, 192, 1>(a); }
+    else if (channels == 256) { if (parts == 2) launch_input_conv<E, PT, 256, 2>(a); else launch_input_conv<E, PT, 256, 1>(a); }
+    else if (channels == 32) { if (parts == 2) launch_input_conv<E, PT, 32, 2>(a); else launch_input_conv<E, PT, 32, 1>(a); }
+    else return false;
+    return true;
 }
-inline float f16_bits_to_f32(uint16_t b)
+
+template <typename E>
+bool dispatch_input_conv_pt(int planes_dtype, int channels, int parts, const InputConvCall& a)
 {
-    _Float16 h;
-    memcpy(&h, &b, 2);
-    return (float)h;
+    switch (planes_dtype) {
+    case CZ_F32: return dispatch_input_conv<E, float>(channels, parts, a);
+    case CZ_F16: return dispatch_input_conv<E, _Float16>(channels, parts, a);
+    case CZ_BF16: return dispatch_input_conv<E, __bf16>(channels, parts, a);
+    case CZ_U8: return dispatch_input_conv<E, unsigned char>(channels, parts, a);
+    }
+    return false;
+}
+
+// one residual block: the operands, the two packed filters, one of the three outputs, the board count on both sides
+struct BlockCall {
+    const void *xh, *xl, *w1;
+    const float* b1;
+    const void* w2;
+    const float* b2;
+    void *yh, *yl;
+    float* yf;
+    int n, n_cu;
+    const int32_t* n_dev;
+    hipStream_t st;
+};
+
+template <typename E, int C, int PARTS, int P, bool HEADS = false, int CTW = 1>
+void launch_resblock(const BlockCall& a, HeadArgs hd = HeadArgs{})
+{
+    hipLaunchKernelGGL((k_resblock<E, C, PARTS, P, HEADS, CTW>), dim3(nn_grid((a.n + P - 1) / P, a.n_cu)),
+                       dim3((C / 32 / CTW + 4) * 64), 0, a.st, (const E*)a.xh, (const E*)a.xl, (const E*)a.w1, a.b1,
+                       (const E*)a.w2, a.b2, (E*)a.yh, (E*)a.yl, a.yf, a.n, hd, a.n_dev);
+}
+
+template <bool FIRST, bool HEADS, bool C6 = false>
+void launch_resblock_c8(const BlockCall& a, HeadArgs hd = HeadArgs{}, FirstArgs fa = FirstArgs{})
+{
+    hipLaunchKernelGGL((k_resblock_c8<FIRST, HEADS, C6>), dim3(nn_grid(a.n, a.n_cu)), dim3(512), 0, a.st, (const _Float16*)a.xh,
+                       (const unsigned char*)a.xl, a.w1, a.b1, a.w2, a.b2, (_Float16*)a.yh, (unsigned char*)a.yl, a.yf, a.n, hd,
+                       a.n_dev, fa);
+}
+
+template <typename E, bool FIRST = false>
+void launch_resblock_pipe(const BlockCall& a, FirstArgs fa = FirstArgs{})
+{
+    hipLaunchKernelGGL((k_resblock_pipe<E, FIRST>), dim3(nn_grid(a.n, a.n_cu)), dim3(512), 0, a.st, (const E*)a.xh,
+                       (const E*)a.xl, (const E*)a.w1, a.b1, (const E*)a.w2, a.b2, (E*)a.yh, (E*)a.yl, a.n, a.n_dev, fa);
+}
+
+int g_resblock_pipelined = 1;       // cz_resblock_pipelined(): 128-filter split blocks on k_resblock_pipe
+
+template <typename E>
+bool dispatch_resblock(int channels, int parts, const BlockCall& a)
+{
+    if (channels == 128 && parts == 2 && !a.yf && g_resblock_pipelined)
+        // (operand-pair output: the software-pipelined kernel; the last block of a tower -- fp32 / head output --
+        //  stays on k_resblock)
+        launch_resblock_pipe<E>(a);
+    else if (channels == 128 && parts == 2) launch_resblock<E, 128, 2, 1>(a);
+    else if (channels == 192 && parts == 2)
+        hipLaunchKernelGGL((k_resblock_ip<E, 192>), dim3(nn_grid(a.n, a.n_cu)), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0, a.st,
+                           (const E*)a.xh, (const E*)a.xl, (const E*)a.w1, a.b1, (const E*)a.w2, a.b2, (E*)a.yh, (E*)a.yl, a.yf,
+                           a.n, a.n_dev);
+    else if (channels == 128 && parts == 1) launch_resblock<E, 128, 1, 2>(a);
+    else if (channels == 192 && parts == 1) launch_resblock<E, 192, 1, 1>(a);
+    // 256 filters, plain operands: two channel tiles per matrix wave (4 + 4 waves), see conv_kloop; the tuning hook's
+    // 0 keeps the one-tile schedule (8 + 4 waves) for A/B runs
+    else if (channels == 256 && parts == 1 && g_resblock_pipelined) launch_resblock<E, 256, 1, 1, false, 2>(a);
+    else if (channels == 256 && parts == 1) launch_resblock<E, 256, 1, 1>(a);
+    else return false;
+    return true;
+}
+
+// the staged chains (c8 / c6 images): operands, the block list, one of the two outputs
+struct ChainCall {
+    const void *xh, *xc;
+    const BlockChain<ip::MAX_BLOCKS>& ch;
+    void *yh, *yc;
+    float* yf;
+    int n, n_cu;
+    const int32_t* n_dev;
+    hipStream_t st;
+};
+
+// a pair of boards per workgroup on four matrix waves of C / 64 channel tiles
+template <int C, int XF, int YF, bool MIX = false>
+void launch_ip4(const ChainCall& a, int exit_mode = 0, HeadArgs hd = HeadArgs{})
+{
+    hipLaunchKernelGGL((k_resblock_ip4_c8<C, XF, YF, MIX>), dim3(nn_grid((a.n + 1) / 2, a.n_cu)), dim3(256), 0, a.st,
+                       (const _Float16*)a.xh, (const unsigned char*)a.xc, a.ch, (_Float16*)a.yh, (unsigned char*)a.yc, a.yf, a.n,
+                       a.n_dev, exit_mode, hd);
+}
+
+// 192 filters: that (pair), or one board on six matrix waves (k_resblock_ip_c8; there is no MIX there)
+template <int XF, int YF, bool MIX = false>
+void launch_ip192(bool pair, const ChainCall& a)
+{
+    if (pair)
+        launch_ip4<192, XF, YF, MIX>(a);
+    else
+        hipLaunchKernelGGL((k_resblock_ip_c8<192, XF, YF>), dim3(nn_grid(a.n, a.n_cu)), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0,
+                           a.st, (const _Float16*)a.xh, (const unsigned char*)a.xc, a.ch, (_Float16*)a.yh, (unsigned char*)a.yc,
+                           a.yf, a.n, a.n_dev);
+}
+
+// The 192-filter blocks on c8 (CZ_F16C8), on c6 (CZ_F16C6), or behind the input layer's c8 image (CZ_F16C86): as cz_resblock's
+// one block (first filter cz_conv3x3_c8_pack_weights', second cz_conv3x3_c6_pack_weights'), or tower_start: as the c6 chain
+// that starts the tower, which exists on the four-wave kernel only.
+int launch_chain192(const char* name, int dtype, bool tower_start, const ChainCall& a)
+{
+    const bool pair = nn_ip_pair();
+    if (dtype == CZ_F16C86 && tower_start) {
+        if (!pair)
+            return nn_error(CZ_ERR_ARG, "cz_resblock_chain: CZ_F16C86 (a c6 chain that starts the tower) exists on the four-wave kernel only (CZ_IP_PAIR=0 is set)");
+        launch_ip192<1, 1, true>(true, a);
+    } else if (dtype == CZ_F16C8) launch_ip192<0, 0>(pair, a);
+    else if (dtype == CZ_F16C6) launch_ip192<1, 1>(pair, a);
+    else launch_ip192<0, 1>(pair, a);
+    return nn_launched(name);
 }
 
 }  // namespace
@@ -3594,28 +3704,13 @@ extern "C" int cz_conv3x3_c8(const void* x_hi, const void* x_c8, const void* w_p
                              int n_boards, int channels, int relu, void* stream)
 {
     if (n_boards < 0 || !x_hi || !x_c8 || !w_packed || !bias || (channels != 128 && channels != 192) ||
-        (!y_f32 && (!y_hi || !y_c8)) || (skip_hi && !skip_c8)) {
-        czi_set_error("cz_conv3x3_c8: bad argument (128 or 192 filters; output: y_f32, or the operand pair y_hi + y_c8)");
-        return CZ_ERR_ARG;
-    }
+        (!y_f32 && (!y_hi || !y_c8)) || (skip_hi && !skip_c8))
+        return nn_error(CZ_ERR_ARG, "cz_conv3x3_c8: bad argument (128 or 192 filters; output: y_f32, or the operand pair y_hi + y_c8)");
     if (n_boards == 0) return CZ_OK;
-    if (channels == 128) {
-        constexpr int P = 2;
-        hipLaunchKernelGGL((k_conv3x3_c8<128, P>), dim3((unsigned)((n_boards + P - 1) / P)), dim3(128 / 32 * 64), 0,
-                           (hipStream_t)stream, (const _Float16*)x_hi, (const unsigned char*)x_c8, (const uint4*)w_packed, bias,
-                           (const _Float16*)skip_hi, (const unsigned char*)skip_c8, (_Float16*)y_hi, (unsigned char*)y_c8,
-                           y_f32, n_boards, relu);
-    } else {
-        hipLaunchKernelGGL((k_conv3x3_c8<192, 1>), dim3((unsigned)n_boards), dim3(192 / 32 * 64), 0,
-                           (hipStream_t)stream, (const _Float16*)x_hi, (const unsigned char*)x_c8, (const uint4*)w_packed, bias,
-                           (const _Float16*)skip_hi, (const unsigned char*)skip_c8, (_Float16*)y_hi, (unsigned char*)y_c8,
-                           y_f32, n_boards, relu);
-    }
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_conv3x3_c8: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
+    const ConvCall a{x_hi, x_c8, w_packed, bias, skip_hi, skip_c8, y_hi, y_c8, y_f32, n_boards, relu, (hipStream_t)stream};
+    if (channels == 128) launch_conv_c8<128, 2>(a);
+    else launch_conv_c8<192, 1>(a);
+    return nn_launched("cz_conv3x3_c8");
 }
 
 extern "C" int cz_conv3x3(const void* x_hi, const void* x_lo, const void* w_packed, const float* bias,
@@ -3623,24 +3718,13 @@ extern "C" int cz_conv3x3(const void* x_hi, const void* x_lo, const void* w_pack
                           int n_boards, int channels, int dtype, int parts, int relu, void* stream)
 {
     if (n_boards < 0 || !w_packed || !bias || !x_hi || (parts == 2 && !x_lo) || (parts != 1 && parts != 2) ||
-        (!y_f32 && (!y_hi || (parts == 2 && !y_lo))) || (skip_hi && parts == 2 && !skip_lo)) {
-        czi_set_error("cz_conv3x3: bad argument");
-        return CZ_ERR_ARG;
-    }
+        (!y_f32 && (!y_hi || (parts == 2 && !y_lo))) || (skip_hi && parts == 2 && !skip_lo))
+        return nn_error(CZ_ERR_ARG, "cz_conv3x3: bad argument");
     if (n_boards == 0) return CZ_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == CZ_BF16)
-        rc = dispatch_conv<__bf16>(channels, parts, x_hi, x_lo, w_packed, bias, skip_hi, skip_lo, y_hi, y_lo, y_f32,
-                                   n_boards, relu, st);
-    else if (dtype == CZ_F16)
-        rc = dispatch_conv<_Float16>(channels, parts, x_hi, x_lo, w_packed, bias, skip_hi, skip_lo, y_hi, y_lo, y_f32,
-                                     n_boards, relu, st);
-    else
-        rc = CZ_ERR_ARG;
-    if (rc == CZ_ERR_ARG) czi_set_error("cz_conv3x3: unsupported channels / dtype (channels 32|128|192|256, bf16|f16)");
-    else if (rc != CZ_OK) czi_set_error("cz_conv3x3: launch failed");
-    return rc;
+    const ConvCall a{x_hi, x_lo, w_packed, bias, skip_hi, skip_lo, y_hi, y_lo, y_f32, n_boards, relu, (hipStream_t)stream};
+    if (!(dtype == CZ_BF16 ? dispatch_conv<__bf16>(channels, parts, a) : dtype == CZ_F16 && dispatch_conv<_Float16>(channels, parts, a)))
+        return nn_error(CZ_ERR_ARG, "cz_conv3x3: unsupported channels / dtype (channels 32|128|192|256, bf16|f16)");
+    return nn_launched("cz_conv3x3");
 }
 
 extern "C" size_t cz_input_conv_packed_elems(int channels, int in_planes, int parts)
@@ -3686,46 +3770,84 @@ extern "C" int cz_input_conv_pack_weights(const float* w_oihw, int channels, int
 }
 
 namespace {
-template <typename E, typename PT, int C>
-int launch_input_conv(const void* planes, int in_planes, const void* wp, const float* bias, void* yh, void* yl,
-                      int n, int parts, int relu, hipStream_t st)
+// cz_input_conv and cz_input_conv_q
+int input_conv(QueueCtx q, const void* planes, int planes_dtype, int in_planes, const void* w_packed, const float* bias,
+               void* y_hi, void* y_lo, int n_boards, int channels, int dtype, int parts, int relu, void* stream)
 {
-    constexpr int P = 2;
-    const unsigned blocks = (unsigned)((n + P - 1) / P);
-#define CZ_IC(IC16, PARTS)                                                                                       \
-    hipLaunchKernelGGL((k_input_conv<E, PT, C, IC16, P, PARTS>), dim3(blocks), dim3(C / 32 * 64), 0, st,           \
-                       (const PT*)planes, (const E*)wp, bias, (E*)yh, (E*)yl, n, in_planes, relu, g_q.rows, g_q.n_dev)
-    if (in_planes <= 16) {
-        if (parts == 2) CZ_IC(1, 2); else CZ_IC(1, 1);
-    } else {
-        if (parts == 2) CZ_IC(2, 2); else CZ_IC(2, 1);
+    if (n_boards < 0 || !planes || !w_packed || !bias || !y_hi || (parts == 2 && !y_lo) || (parts != 1 && parts != 2) ||
+        in_planes < 1 || in_planes > 32)
+        return nn_error(CZ_ERR_ARG, "cz_input_conv: bad argument");
+    if (n_boards == 0) return CZ_OK;
+    const InputConvCall a{planes, w_packed, bias, y_hi, y_lo, n_boards, in_planes, relu, q, (hipStream_t)stream};
+    bool ok = false;
+    if (dtype == CZ_BF16)
+        ok = dispatch_input_conv_pt<__bf16>(planes_dtype, channels, parts, a);
+    else if (dtype == CZ_F16)
+        ok = dispatch_input_conv_pt<_Float16>(planes_dtype, channels, parts, a);
+    else if (dtype == CZ_F16C8 && (channels == 128 || channels == 192) && parts == 2 &&
+             (planes_dtype == CZ_U8 || planes_dtype == CZ_F32)) {
+        // f16-split filters (cz_input_conv_pack_weights with CZ_F16), output = the c8 operand pair (y_lo = the c8 image)
+        ok = true;
+        if (channels == 128 && planes_dtype == CZ_U8) launch_input_conv<_Float16, unsigned char, 128, 2, true>(a);
+        else if (channels == 128) launch_input_conv<_Float16, float, 128, 2, true>(a);
+        else if (planes_dtype == CZ_U8) launch_input_conv<_Float16, unsigned char, 192, 2, true>(a);
+        else launch_input_conv<_Float16, float, 192, 2, true>(a);
     }
-#undef CZ_IC
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
+    if (!ok) return nn_error(CZ_ERR_ARG, "cz_input_conv: unsupported channels / dtype");
+    return nn_launched("cz_input_conv");
 }
 
-template <typename E, typename PT>
-int dispatch_input_conv(int channels, const void* planes, int in_planes, const void* wp, const float* bias, void* yh,
-                        void* yl, int n, int parts, int relu, hipStream_t st)
+// cz_resblock_heads and cz_resblock_heads_q
+int resblock_heads(const int32_t* n_dev, const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
+                   const void* w2_packed, const float* bias2, const float* head_w, const float* head_b, float* policy_feat,
+                   float* value_feat, int n_boards, int channels, int dtype, int n_policy, int n_value, void* stream)
 {
-    if (channels == 128) return launch_input_conv<E, PT, 128>(planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    if (channels == 192) return launch_input_conv<E, PT, 192>(planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    if (channels == 256) return launch_input_conv<E, PT, 256>(planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    if (channels == 32) return launch_input_conv<E, PT, 32>(planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    return CZ_ERR_ARG;
+    if (n_boards < 0 || !x_hi || !x_lo || !w1_packed || !w2_packed || !bias1 || !bias2 || !head_w || !head_b ||
+        !policy_feat || !value_feat || n_policy < 1 || n_value < 1 || n_policy + n_value != 6)
+        return nn_error(CZ_ERR_ARG, "cz_resblock_heads: bad argument (split operands; n_policy + n_value == 6)");
+    if (n_boards == 0) return CZ_OK;
+    if (channels != 128 || (dtype != CZ_BF16 && dtype != CZ_F16 && dtype != CZ_F16C8 && dtype != CZ_F16C6))
+        return nn_error(CZ_ERR_ARG, "cz_resblock_heads: 128 filters, bf16 / f16 split operands only (use cz_resblock + cz_head_convs)");
+    const int n_cu = nn_cu_count("cz_resblock_heads");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    const HeadArgs hd{head_w, head_b, policy_feat, value_feat, n_policy};
+    const BlockCall a{x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, nullptr, nullptr, nullptr, n_boards, n_cu, n_dev,
+                      (hipStream_t)stream};
+    if (dtype == CZ_BF16) launch_resblock<__bf16, 128, 2, 1, true>(a, hd);
+    else if (dtype == CZ_F16C8) launch_resblock_c8<false, true>(a, hd);
+    else if (dtype == CZ_F16C6) launch_resblock_c8<false, true, true>(a, hd);
+    else launch_resblock<_Float16, 128, 2, 1, true>(a, hd);
+    return nn_launched("cz_resblock_heads");
 }
 
-template <typename E>
-int dispatch_input_conv_pt(int planes_dtype, int channels, const void* planes, int in_planes, const void* wp,
-                           const float* bias, void* yh, void* yl, int n, int parts, int relu, hipStream_t st)
+// cz_resblock and cz_resblock_q
+int resblock(const int32_t* n_dev, const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
+             const void* w2_packed, const float* bias2, void* y_hi, void* y_lo, float* y_f32, int n_boards, int channels,
+             int dtype, int parts, void* stream)
 {
-    switch (planes_dtype) {
-    case CZ_F32: return dispatch_input_conv<E, float>(channels, planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    case CZ_F16: return dispatch_input_conv<E, _Float16>(channels, planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    case CZ_BF16: return dispatch_input_conv<E, __bf16>(channels, planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    case CZ_U8: return dispatch_input_conv<E, unsigned char>(channels, planes, in_planes, wp, bias, yh, yl, n, parts, relu, st);
-    }
-    return CZ_ERR_ARG;
+    if (n_boards < 0 || !x_hi || !w1_packed || !w2_packed || !bias1 || !bias2 || (parts != 1 && parts != 2) ||
+        (parts == 2 && (!x_lo || (!y_f32 && (!y_hi || !y_lo)))) || (parts == 1 && (!y_hi || y_f32)))
+        return nn_error(CZ_ERR_ARG, "cz_resblock: bad argument (parts = 1 writes y_hi only; y_f32 needs parts = 2)");
+    if (n_boards == 0) return CZ_OK;
+    const int n_cu = nn_cu_count("cz_resblock");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    const BlockCall a{x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards, n_cu, n_dev, st};
+    bool ok = true;
+    if (dtype == CZ_BF16) ok = dispatch_resblock<__bf16>(channels, parts, a);
+    else if (dtype == CZ_F16) ok = dispatch_resblock<_Float16>(channels, parts, a);
+    else if (dtype == CZ_F16C8 && channels == 128 && parts == 2) launch_resblock_c8<false, false>(a);
+    else if (dtype == CZ_F16C6 && channels == 128 && parts == 2) launch_resblock_c8<false, false, true>(a);
+    else if ((dtype == CZ_F16C8 || dtype == CZ_F16C6 || dtype == CZ_F16C86) && channels == 192 && parts == 2) {
+        // 192 filters: the two-image in-place block, as a chain of one
+        BlockChain<ip::MAX_BLOCKS> ch{};
+        fill_chain(ch, "cz_resblock", 1, &w1_packed, &bias1, &w2_packed, &bias2);
+        return launch_chain192("cz_resblock", dtype, false, ChainCall{x_hi, x_lo, ch, y_hi, y_lo, y_f32, n_boards, n_cu, n_dev, st});
+    } else ok = false;
+    if (!ok)
+        return nn_error(CZ_ERR_ARG, "cz_resblock: supported: 128 / 192 filters (split or plain operands), 256 filters (plain), bf16 / f16; "
+                                    "use cz_conv3x3 otherwise");
+    return nn_launched("cz_resblock");
 }
 }  // namespace
 
@@ -3733,115 +3855,8 @@ extern "C" int cz_input_conv(const void* planes, int planes_dtype, int in_planes
                              const float* bias, void* y_hi, void* y_lo, int n_boards, int channels, int dtype,
                              int parts, int relu, void* stream)
 {
-    if (n_boards < 0 || !planes || !w_packed || !bias || !y_hi || (parts == 2 && !y_lo) || (parts != 1 && parts != 2) ||
-        in_planes < 1 || in_planes > 32) {
-        czi_set_error("cz_input_conv: bad argument");
-        return CZ_ERR_ARG;
-    }
-    if (n_boards == 0) return CZ_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = CZ_ERR_ARG;
-    if (dtype == CZ_BF16)
-        rc = dispatch_input_conv_pt<__bf16>(planes_dtype, channels, planes, in_planes, w_packed, bias, y_hi, y_lo,
-                                            n_boards, parts, relu, st);
-    else if (dtype == CZ_F16)
-        rc = dispatch_input_conv_pt<_Float16>(planes_dtype, channels, planes, in_planes, w_packed, bias, y_hi, y_lo,
-                                              n_boards, parts, relu, st);
-    else if (dtype == CZ_F16C8 && (channels == 128 || channels == 192) && parts == 2 &&
-             (planes_dtype == CZ_U8 || planes_dtype == CZ_F32)) {
-        // f16-split filters (cz_input_conv_pack_weights with CZ_F16), output = the c8 operand pair (y_lo = the c8 image)
-        constexpr int P = 2;
-        const unsigned blocks = (unsigned)((n_boards + P - 1) / P);
-#define CZ_IC8(CH, PT, IC16)                                                                                          \
-        hipLaunchKernelGGL((k_input_conv<_Float16, PT, CH, IC16, P, 2, true>), dim3(blocks), dim3(CH / 32 * 64), 0, st,   \
-                           (const PT*)planes, (const _Float16*)w_packed, bias, (_Float16*)y_hi, (_Float16*)y_lo, n_boards,    \
-                           in_planes, relu, g_q.rows, g_q.n_dev)
-#define CZ_IC8C(CH)                                                                                                   \
-        do {                                                                                                          \
-            if (planes_dtype == CZ_U8) { if (in_planes <= 16) CZ_IC8(CH, unsigned char, 1); else CZ_IC8(CH, unsigned char, 2); } \
-            else { if (in_planes <= 16) CZ_IC8(CH, float, 1); else CZ_IC8(CH, float, 2); }                              \
-        } while (0)
-        if (channels == 128) CZ_IC8C(128); else CZ_IC8C(192);
-#undef CZ_IC8C
-#undef CZ_IC8
-        rc = hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-    }
-    if (rc == CZ_ERR_ARG) czi_set_error("cz_input_conv: unsupported channels / dtype");
-    else if (rc != CZ_OK) czi_set_error("cz_input_conv: launch failed");
-    return rc;
-}
-
-namespace {
-template <typename E, int C, int PARTS, int P, bool HEADS = false, int CTW = 1>
-int launch_resblock(const void* xh, const void* xl, const void* w1, const float* b1, const void* w2, const float* b2,
-                    void* yh, void* yl, float* yf, int n, int n_cu, hipStream_t st, HeadArgs hd = HeadArgs{})
-{
-    const int tiles = (n + P - 1) / P;
-    const unsigned blocks = (unsigned)(tiles < n_cu ? tiles : n_cu);
-    hipLaunchKernelGGL((k_resblock<E, C, PARTS, P, HEADS, CTW>), dim3(blocks), dim3((C / 32 / CTW + 4) * 64), 0, st,
-                       (const E*)xh, (const E*)xl, (const E*)w1, b1, (const E*)w2, b2, (E*)yh, (E*)yl, yf, n, hd,
-                       g_q.n_dev);
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-}
-
-template <bool FIRST, bool HEADS, bool C6 = false>
-int launch_resblock_c8(const void* xh, const void* xc, const void* w1, const float* b1, const void* w2, const float* b2,
-                       void* yh, void* yc, float* yf, int n, int n_cu, hipStream_t st, HeadArgs hd, const int32_t* n_dev,
-                       FirstArgs fa)
-{
-    const unsigned blocks = (unsigned)(n < n_cu ? n : n_cu);
-    hipLaunchKernelGGL((k_resblock_c8<FIRST, HEADS, C6>), dim3(blocks), dim3(512), 0, st, (const _Float16*)xh,
-                       (const unsigned char*)xc, w1, b1, w2, b2, (_Float16*)yh, (unsigned char*)yc, yf, n, hd, n_dev, fa);
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-}
-
-int g_resblock_pipelined = 1;       // cz_resblock_pipelined(): 128-filter split blocks on k_resblock_pipe
-int g_first_w1_rounds = 6;          // cz_input_resblock: gather rounds done under K loop 1 (tuning hook: CZ_FIRST_W1_ROUNDS)
-
-template <typename E>
-int dispatch_resblock(int channels, int parts, const void* xh, const void* xl, const void* w1, const float* b1,
-                      const void* w2, const float* b2, void* yh, void* yl, float* yf, int n, int n_cu, hipStream_t st)
-{
-#define CZ_RB_ARGS xh, xl, w1, b1, w2, b2, yh, yl, yf, n, n_cu, st
-    if (channels == 128 && parts == 2 && !yf && g_resblock_pipelined) {
-        // (operand-pair output: the software-pipelined kernel; the last block of a tower -- fp32 / head output --
-        //  stays on k_resblock)
-        const unsigned blocks = (unsigned)(n < n_cu ? n : n_cu);
-        hipLaunchKernelGGL((k_resblock_pipe<E>), dim3(blocks), dim3(512), 0, st, (const E*)xh, (const E*)xl,
-                           (const E*)w1, b1, (const E*)w2, b2, (E*)yh, (E*)yl, n, g_q.n_dev, FirstArgs{});
-        return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-    }
-    if (channels == 128 && parts == 2) {
-        return launch_resblock<E, 128, 2, 1>(CZ_RB_ARGS);
-    }
-    if (channels == 192 && parts == 2) {
-        const unsigned blocks = (unsigned)(n < n_cu ? n : n_cu);
-        hipLaunchKernelGGL((k_resblock_ip<E, 192>), dim3(blocks), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0, st,
-                           (const E*)xh, (const E*)xl, (const E*)w1, b1, (const E*)w2, b2, (E*)yh, (E*)yl, yf, n, g_q.n_dev);
-        return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-    }
-    if (channels == 128 && parts == 1) return launch_resblock<E, 128, 1, 2>(CZ_RB_ARGS);
-    if (channels == 192 && parts == 1) return launch_resblock<E, 192, 1, 1>(CZ_RB_ARGS);
-    // 256 filters, plain operands: two channel tiles per matrix wave (4 + 4 waves), see conv_kloop; the tuning hook's
-    // 0 keeps the one-tile schedule (8 + 4 waves) for A/B runs
-    if (channels == 256 && parts == 1 && g_resblock_pipelined) return launch_resblock<E, 256, 1, 1, false, 2>(CZ_RB_ARGS);
-    if (channels == 256 && parts == 1) return launch_resblock<E, 256, 1, 1>(CZ_RB_ARGS);
-#undef CZ_RB_ARGS
-    return CZ_ERR_ARG;
-}
-}  // namespace
-
-static int device_cu_count()
-{
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        if (const char* e = getenv("CZ_FIRST_W1_ROUNDS")) g_first_w1_rounds = atoi(e);      // (A/B runs of the fused input layer)
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        n_cu = prop.multiProcessorCount;
-    }
-    return n_cu;
+    return input_conv(QueueCtx{nullptr, nullptr}, planes, planes_dtype, in_planes, w_packed, bias, y_hi, y_lo, n_boards, channels,
+                      dtype, parts, relu, stream);
 }
 
 extern "C" int cz_resblock_heads(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
@@ -3849,98 +3864,42 @@ extern "C" int cz_resblock_heads(const void* x_hi, const void* x_lo, const void*
                                  float* policy_feat, float* value_feat, int n_boards, int channels, int dtype,
                                  int n_policy, int n_value, void* stream)
 {
-    if (n_boards < 0 || !x_hi || !x_lo || !w1_packed || !w2_packed || !bias1 || !bias2 || !head_w || !head_b ||
-        !policy_feat || !value_feat || n_policy < 1 || n_value < 1 || n_policy + n_value != 6) {
-        czi_set_error("cz_resblock_heads: bad argument (split operands; n_policy + n_value == 6)");
-        return CZ_ERR_ARG;
-    }
-    if (n_boards == 0) return CZ_OK;
-    if (channels != 128 || (dtype != CZ_BF16 && dtype != CZ_F16 && dtype != CZ_F16C8 && dtype != CZ_F16C6)) {
-        czi_set_error("cz_resblock_heads: 128 filters, bf16 / f16 split operands only (use cz_resblock + cz_head_convs)");
-        return CZ_ERR_ARG;
-    }
-    const int n_cu = device_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_resblock_heads: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    const HeadArgs hd{head_w, head_b, policy_feat, value_feat, n_policy};
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == CZ_BF16)
-        rc = launch_resblock<__bf16, 128, 2, 1, true>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, nullptr, nullptr,
-                                                       nullptr, n_boards, n_cu, st, hd);
-    else if (dtype == CZ_F16C8)
-        rc = launch_resblock_c8<false, true>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, nullptr, nullptr, nullptr,
-                                             n_boards, n_cu, st, hd, g_q.n_dev, FirstArgs{});
-    else if (dtype == CZ_F16C6)
-        rc = launch_resblock_c8<false, true, true>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, nullptr, nullptr, nullptr,
-                                                   n_boards, n_cu, st, hd, g_q.n_dev, FirstArgs{});
-    else
-        rc = launch_resblock<_Float16, 128, 2, 1, true>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, nullptr,
-                                                         nullptr, nullptr, n_boards, n_cu, st, hd);
-    if (rc != CZ_OK) czi_set_error("cz_resblock_heads: launch failed");
-    return rc;
+    return resblock_heads(nullptr, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, head_w, head_b, policy_feat, value_feat,
+                          n_boards, channels, dtype, n_policy, n_value, stream);
 }
 
 extern "C" int cz_resblock(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
                            const void* w2_packed, const float* bias2, void* y_hi, void* y_lo, float* y_f32,
                            int n_boards, int channels, int dtype, int parts, void* stream)
 {
-    if (n_boards < 0 || !x_hi || !w1_packed || !w2_packed || !bias1 || !bias2 || (parts != 1 && parts != 2) ||
-        (parts == 2 && (!x_lo || (!y_f32 && (!y_hi || !y_lo)))) || (parts == 1 && (!y_hi || y_f32))) {
-        czi_set_error("cz_resblock: bad argument (parts = 1 writes y_hi only; y_f32 needs parts = 2)");
-        return CZ_ERR_ARG;
-    }
-    if (n_boards == 0) return CZ_OK;
-    const int n_cu = device_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_resblock: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = CZ_ERR_ARG;
-    if (dtype == CZ_BF16)
-        rc = dispatch_resblock<__bf16>(channels, parts, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo,
-                                       y_f32, n_boards, n_cu, st);
-    else if (dtype == CZ_F16)
-        rc = dispatch_resblock<_Float16>(channels, parts, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo,
-                                         y_f32, n_boards, n_cu, st);
-    else if (dtype == CZ_F16C8 && channels == 128 && parts == 2)
-        rc = launch_resblock_c8<false, false>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards,
-                                              n_cu, st, HeadArgs{}, g_q.n_dev, FirstArgs{});
-    else if (dtype == CZ_F16C6 && channels == 128 && parts == 2)
-        rc = launch_resblock_c8<false, false, true>(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards,
-                                                    n_cu, st, HeadArgs{}, g_q.n_dev, FirstArgs{});
-    else if ((dtype == CZ_F16C8 || dtype == CZ_F16C6 || dtype == CZ_F16C86) && channels == 192 && parts == 2) {
-        // 192 filters: the two-image in-place block on c8, on c6 (round 6), or as the tower's first c6 block behind the input
-        // layer's c8 image (CZ_F16C86: the first filter is cz_conv3x3_c8_pack_weights', the second cz_conv3x3_c6_pack_weights')
-        ip::Chain ch{};
-        ch.n = 1;
-        ch.w1[0] = w1_packed; ch.w2[0] = w2_packed; ch.b1[0] = bias1; ch.b2[0] = bias2;
-        // CZ_IP_PAIR=0: one board on six matrix waves (k_resblock_ip_c8); default: a pair on four waves of three channel tiles
-        const char* pair_env = getenv("CZ_IP_PAIR");
-        const bool pair = !(pair_env && pair_env[0] == '0');
-        const int units = pair ? (n_boards + 1) / 2 : n_boards;
-        const unsigned blocks = (unsigned)(units < n_cu ? units : n_cu);
-#define CZ_IP_LAUNCH(XF, YF) do { \
-            if (pair) hipLaunchKernelGGL((k_resblock_ip4_c8<192, XF, YF>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi, \
-                                         (const unsigned char*)x_lo, ch, (_Float16*)y_hi, (unsigned char*)y_lo, y_f32, n_boards, g_q.n_dev, 0, HeadArgs{}); \
-            else hipLaunchKernelGGL((k_resblock_ip_c8<192, XF, YF>), dim3(blocks), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0, st, \
-                                    (const _Float16*)x_hi, (const unsigned char*)x_lo, ch, (_Float16*)y_hi, (unsigned char*)y_lo, y_f32, \
-                                    n_boards, g_q.n_dev); } while (0)
-        if (dtype == CZ_F16C8) CZ_IP_LAUNCH(0, 0);
-        else if (dtype == CZ_F16C6) CZ_IP_LAUNCH(1, 1);
-        else CZ_IP_LAUNCH(0, 1);
-#undef CZ_IP_LAUNCH
-        rc = hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
-    }
-    if (rc == CZ_ERR_ARG)
-        czi_set_error("cz_resblock: supported: 128 / 192 filters (split or plain operands), 256 filters (plain), bf16 / f16; "
-                      "use cz_conv3x3 otherwise");
-    else if (rc != CZ_OK)
-        czi_set_error("cz_resblock: launch failed");
-    return rc;
+    return resblock(nullptr, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards, channels, dtype, parts,
+                    stream);
+}
+
+// ---- compact evaluation queue: the same kernels with a device-side board count (and a row gather in the input layer) ----
+extern "C" int cz_input_conv_q(const void* planes, int planes_dtype, int in_planes, const void* w_packed,
+                               const float* bias, void* y_hi, void* y_lo, int n_boards, int channels, int dtype,
+                               int parts, int relu, const int32_t* rows, const int32_t* n_dev, void* stream)
+{
+    return input_conv(QueueCtx{rows, n_dev}, planes, planes_dtype, in_planes, w_packed, bias, y_hi, y_lo, n_boards, channels,
+                      dtype, parts, relu, stream);
+}
+
+extern "C" int cz_resblock_q(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
+                             const void* w2_packed, const float* bias2, void* y_hi, void* y_lo, float* y_f32,
+                             int n_boards, int channels, int dtype, int parts, const int32_t* n_dev, void* stream)
+{
+    return resblock(n_dev, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards, channels, dtype, parts,
+                    stream);
+}
+
+extern "C" int cz_resblock_heads_q(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
+                                   const void* w2_packed, const float* bias2, const float* head_w, const float* head_b,
+                                   float* policy_feat, float* value_feat, int n_boards, int channels, int dtype,
+                                   int n_policy, int n_value, const int32_t* n_dev, void* stream)
+{
+    return resblock_heads(n_dev, x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, head_w, head_b, policy_feat, value_feat,
+                          n_boards, channels, dtype, n_policy, n_value, stream);
 }
 
 // n_blocks (1 .. 12) consecutive residual blocks of a 192-filter tower on ONE staged arithmetic in one launch (k_resblock_ip_c8's
@@ -3954,100 +3913,31 @@ extern "C" int cz_resblock_chain(const void* x_hi, const void* x_img, int n_bloc
     const bool pairs = dtype == CZ_F16 || dtype == CZ_BF16;     // (hi, lo) pair blocks: x_img / y_img are the lo tensors
     if (n_boards < 0 || !x_hi || !x_img || !w1_packed || !w2_packed || !bias1 || !bias2 || n_blocks < 1 ||
         n_blocks > ip::MAX_BLOCKS || channels != 192 || (dtype != CZ_F16C8 && dtype != CZ_F16C6 && dtype != CZ_F16C86 && !pairs) ||
-        (!y_f32 && (!y_hi || !y_img))) {
-        czi_set_error("cz_resblock_chain: bad argument (192 filters, 1 .. 12 blocks, dtype CZ_F16C8 / CZ_F16C6 / CZ_F16C86 with y_f32 or y_hi + y_img, "
-                      "or CZ_F16 / CZ_BF16 pair blocks with y_f32 or y_hi + y_lo)");
-        return CZ_ERR_ARG;
-    }
-    if (pairs) {
-        for (int b = 0; b < n_blocks; ++b)
-            if (!w1_packed[b] || !w2_packed[b] || !bias1[b] || !bias2[b]) {
-                czi_set_error("cz_resblock_chain: null block parameter");
-                return CZ_ERR_ARG;
-            }
-        if (n_boards == 0) return CZ_OK;
-        const int n_cu_p = device_cu_count();
-        if (n_cu_p < 0) {
-            czi_set_error("cz_resblock_chain: cannot query the device");
-            return CZ_ERR_HIP;
-        }
-        const int rc = czi_pairs4_launch(x_hi, x_img, n_blocks, w1_packed, bias1, w2_packed, bias2, y_hi, y_img, nullptr, nullptr, nullptr,
-                                         nullptr, 0, n_boards, 192, dtype, n_cu_p, n_dev, stream, y_f32);
-        if (rc != CZ_OK) czi_set_error("cz_resblock_chain: launch failed");
-        return rc;
-    }
-    ip::Chain ch{};
-    ch.n = n_blocks;
-    for (int b = 0; b < n_blocks; ++b) {
-        if (!w1_packed[b] || !w2_packed[b] || !bias1[b] || !bias2[b]) {
-            czi_set_error("cz_resblock_chain: null block parameter");
-            return CZ_ERR_ARG;
-        }
-        ch.w1[b] = w1_packed[b]; ch.w2[b] = w2_packed[b]; ch.b1[b] = bias1[b]; ch.b2[b] = bias2[b];
-    }
+        (!y_f32 && (!y_hi || !y_img)))
+        return nn_error(CZ_ERR_ARG, "cz_resblock_chain: bad argument (192 filters, 1 .. 12 blocks, dtype CZ_F16C8 / CZ_F16C6 / CZ_F16C86 with y_f32 or y_hi + y_img, "
+                                    "or CZ_F16 / CZ_BF16 pair blocks with y_f32 or y_hi + y_lo)");
+    BlockChain<ip::MAX_BLOCKS> ch{};
+    if (!fill_chain(ch, "cz_resblock_chain", n_blocks, w1_packed, bias1, w2_packed, bias2)) return CZ_ERR_ARG;
     if (n_boards == 0) return CZ_OK;
-    const int n_cu = device_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_resblock_chain: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // a pair of boards per workgroup on four matrix waves of three channel tiles (k_resblock_ip4_c8);
-    // CZ_IP_PAIR=0: one board on six matrix waves (k_resblock_ip_c8; A/B runs, the tests run both)
-    const char* pair_env = getenv("CZ_IP_PAIR");
-    if (dtype == CZ_F16C86 && pair_env && pair_env[0] == '0') {
-        czi_set_error("cz_resblock_chain: CZ_F16C86 (a c6 chain that starts the tower) exists on the four-wave kernel only (CZ_IP_PAIR=0 is set)");
-        return CZ_ERR_ARG;
-    } else if (!(pair_env && pair_env[0] == '0')) {
-        const int n_pairs = (n_boards + 1) / 2;
-        const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
-        if (dtype == CZ_F16C86)
-            hipLaunchKernelGGL((k_resblock_ip4_c8<192, 1, 1, true>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi,
-                               (const unsigned char*)x_img, ch, (_Float16*)y_hi, (unsigned char*)y_img, y_f32, n_boards, n_dev, 0, HeadArgs{});
-        else if (dtype == CZ_F16C8)
-            hipLaunchKernelGGL((k_resblock_ip4_c8<192, 0, 0>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi,
-                               (const unsigned char*)x_img, ch, (_Float16*)y_hi, (unsigned char*)y_img, y_f32, n_boards, n_dev, 0, HeadArgs{});
-        else
-            hipLaunchKernelGGL((k_resblock_ip4_c8<192, 1, 1>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi,
-                               (const unsigned char*)x_img, ch, (_Float16*)y_hi, (unsigned char*)y_img, y_f32, n_boards, n_dev, 0, HeadArgs{});
-    } else {
-        const unsigned blocks = (unsigned)(n_boards < n_cu ? n_boards : n_cu);
-        if (dtype == CZ_F16C8)
-            hipLaunchKernelGGL((k_resblock_ip_c8<192, 0, 0>), dim3(blocks), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0, st, (const _Float16*)x_hi,
-                               (const unsigned char*)x_img, ch, (_Float16*)y_hi, (unsigned char*)y_img, y_f32, n_boards, n_dev);
-        else
-            hipLaunchKernelGGL((k_resblock_ip_c8<192, 1, 1>), dim3(blocks), dim3(192 / 32 * 64 + ip::COPY_THREADS), 0, st, (const _Float16*)x_hi,
-                               (const unsigned char*)x_img, ch, (_Float16*)y_hi, (unsigned char*)y_img, y_f32, n_boards, n_dev);
-    }
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_resblock_chain: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
+    const int n_cu = nn_cu_count("cz_resblock_chain");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    if (pairs)
+        return czi_pairs4_launch("cz_resblock_chain", x_hi, x_img, &ch, y_hi, y_img, nullptr, nullptr, nullptr, nullptr, 0, n_boards,
+                                 192, dtype, n_cu, n_dev, stream, y_f32);
+    return launch_chain192("cz_resblock_chain", dtype, true,
+                           ChainCall{x_hi, x_img, ch, y_hi, y_img, y_f32, n_boards, n_cu, n_dev, (hipStream_t)stream});
 }
 
-// cz_tower's launches on the four-wave kernel (csrc/xq_tower.hip): a chain of 128-filter blocks of one staged arithmetic
-// (c6: 1, c8: 0); exit: 0 = the operand pair (c6 image, or the c8 image a c6 chain hands over), IP4_EXIT_PAIRS, IP4_EXIT_HEADS.
-extern "C" int czi_tower4_launch(const void* x_hi, const void* x_img, int n_blocks, const void* const* w1, const float* const* b1,
-                                 const void* const* w2, const float* const* b2, int c6, int exit_mode, void* y_hi, void* y_img,
-                                 const float* head_w, const float* head_b, float* pol, float* val, int n_pol, int n_boards,
-                                 int n_cu, const int32_t* n_dev, void* stream)
+// cz_tower's launches on the four-wave kernel (csrc/xq_nn_launch.h)
+extern "C" int czi_tower4_launch(const char* name, const void* x_hi, const void* x_img, const BlockChain<12>* ch, int c6,
+                                 int exit_mode, void* y_hi, void* y_img, const float* head_w, const float* head_b, float* pol,
+                                 float* val, int n_pol, int n_boards, int n_cu, const int32_t* n_dev, void* stream)
 {
-    if (n_blocks > ip::MAX_BLOCKS) return CZ_ERR_ARG;
     const HeadArgs hd{head_w, head_b, pol, val, n_pol};
-    hipStream_t st = (hipStream_t)stream;
-    ip::Chain ch{};
-    ch.n = n_blocks;
-    for (int b = 0; b < n_blocks; ++b) { ch.w1[b] = w1[b]; ch.w2[b] = w2[b]; ch.b1[b] = b1[b]; ch.b2[b] = b2[b]; }
-    const int n_pairs = (n_boards + 1) / 2;
-    const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
-    if (c6)
-        hipLaunchKernelGGL((k_resblock_ip4_c8<128, 1, 1>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi, (const unsigned char*)x_img,
-                           ch, (_Float16*)y_hi, (unsigned char*)y_img, (float*)nullptr, n_boards, n_dev, exit_mode, hd);
-    else
-        hipLaunchKernelGGL((k_resblock_ip4_c8<128, 0, 0>), dim3(blocks), dim3(256), 0, st, (const _Float16*)x_hi, (const unsigned char*)x_img,
-                           ch, (_Float16*)y_hi, (unsigned char*)y_img, (float*)nullptr, n_boards, n_dev, exit_mode, hd);
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
+    const ChainCall a{x_hi, x_img, *ch, y_hi, y_img, nullptr, n_boards, n_cu, n_dev, (hipStream_t)stream};
+    if (c6) launch_ip4<128, 1, 1>(a, exit_mode, hd);
+    else launch_ip4<128, 0, 0>(a, exit_mode, hd);
+    return nn_launched(name);
 }
 
 // n_blocks (1 .. 24) consecutive residual blocks of a 256-filter tower on plain fp16 / bf16 operands in one launch
@@ -4057,47 +3947,56 @@ extern "C" int cz_tower_plain(const void* x, int n_blocks, const void* const* w1
                               int dtype, const int32_t* n_dev, void* stream)
 {
     if (n_boards < 0 || !x || !y || !w1_packed || !w2_packed || !bias1 || !bias2 || n_blocks < 1 || n_blocks > pl::MAX_BLOCKS ||
-        channels != 256 || (dtype != CZ_F16 && dtype != CZ_BF16)) {
-        czi_set_error("cz_tower_plain: bad argument (256 filters, plain f16 / bf16 operands, 1 .. 24 blocks)");
-        return CZ_ERR_ARG;
-    }
-    pl::Chain ch{};
-    ch.n = n_blocks;
-    for (int b = 0; b < n_blocks; ++b) {
-        if (!w1_packed[b] || !w2_packed[b] || !bias1[b] || !bias2[b]) {
-            czi_set_error("cz_tower_plain: null block parameter");
-            return CZ_ERR_ARG;
-        }
-        ch.w1[b] = w1_packed[b]; ch.w2[b] = w2_packed[b]; ch.b1[b] = bias1[b]; ch.b2[b] = bias2[b];
-    }
+        channels != 256 || (dtype != CZ_F16 && dtype != CZ_BF16))
+        return nn_error(CZ_ERR_ARG, "cz_tower_plain: bad argument (256 filters, plain f16 / bf16 operands, 1 .. 24 blocks)");
+    BlockChain<pl::MAX_BLOCKS> ch{};
+    if (!fill_chain(ch, "cz_tower_plain", n_blocks, w1_packed, bias1, w2_packed, bias2)) return CZ_ERR_ARG;
     if (n_boards == 0) return CZ_OK;
-    const int n_cu = device_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_tower_plain: cannot query the device");
-        return CZ_ERR_HIP;
-    }
+    const int n_cu = nn_cu_count("cz_tower_plain");
+    if (n_cu < 0) return CZ_ERR_HIP;
     hipStream_t st = (hipStream_t)stream;
-    const int n_pairs = (n_boards + 1) / 2;
-    const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
+    const dim3 grid(nn_grid((n_boards + 1) / 2, n_cu)), block(256 / 32 / 2 * 64);
     if (dtype == CZ_F16)
-        hipLaunchKernelGGL((k_tower_plain2<_Float16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const _Float16*)x, ch,
-                           (_Float16*)y, n_boards, n_dev);
+        hipLaunchKernelGGL((k_tower_plain2<_Float16, 256, 2>), grid, block, 0, st, (const _Float16*)x, ch, (_Float16*)y, n_boards, n_dev);
     else
-        hipLaunchKernelGGL((k_tower_plain2<__bf16, 256, 2>), dim3(blocks), dim3(256 / 32 / 2 * 64), 0, st, (const __bf16*)x, ch,
-                           (__bf16*)y, n_boards, n_dev);
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_tower_plain: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
+        hipLaunchKernelGGL((k_tower_plain2<__bf16, 256, 2>), grid, block, 0, st, (const __bf16*)x, ch, (__bf16*)y, n_boards, n_dev);
+    return nn_launched("cz_tower_plain");
 }
 
 // The input layer and the first residual block in one launch (k_resblock_pipe<FIRST>): the 5 x 5 input convolution of
 // the one-hot feature planes is a gather over the occupied squares, done by the block's copy waves.
+// With the positions' occupancy boards handed in (masks [n][96] uint32 DEVICE, word = plane position, bit c = plane c shows
+// a piece there: what cz_search_leaf_masks makes the search kernel write beside the planes) the copy waves skip deriving them
+// from the 1260 plane bytes, and the planes are not read at all.  masks = NULL: exactly cz_input_resblock.
 extern "C" int cz_input_resblock_m(const void* planes_u8, const uint32_t* masks, int in_planes, const float* in_table,
                                    const float* in_bias, const void* w1_packed, const float* bias1, const void* w2_packed,
                                    const float* bias2, void* y_hi, void* y_lo, int n_boards, int channels, int dtype,
-                                   const int32_t* rows, const int32_t* n_dev, void* stream);
+                                   const int32_t* rows, const int32_t* n_dev, void* stream)
+{
+    if (n_boards < 0 || (!planes_u8 && !masks) || !in_table || !in_bias || !w1_packed || !w2_packed || !bias1 || !bias2 || !y_hi ||
+        !y_lo || in_planes < 1 || in_planes > 32 || (in_planes * 90) % 4 != 0)
+        return nn_error(CZ_ERR_ARG, "cz_input_resblock: bad argument (u8 planes, in_planes even and <= 32)");
+    if (channels != 128 || (dtype != CZ_BF16 && dtype != CZ_F16 && dtype != CZ_F16C8 && dtype != CZ_F16C6))
+        return nn_error(CZ_ERR_ARG, "cz_input_resblock: 128 filters; bf16 / f16 split operands or the c8 / c6 pair (use cz_input_conv + cz_resblock)");
+    if (n_boards == 0) return CZ_OK;
+    const int n_cu = nn_cu_count("cz_input_resblock");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    // 6 of the ~12-16 term rounds of a board under K loop 1, the rest under K loop 2: measured on one box, extra time of
+    // the launch against an inner block's: 0 rounds +0.43 ms, 3: +0.26, 6: +0.14, 9: +0.22 (window 2 also drains the result)
+    // (tuning hook for A/B runs of the fused input layer: CZ_FIRST_W1_ROUNDS, read once per process)
+    static const char* const w1_env = getenv("CZ_FIRST_W1_ROUNDS");
+    static const int w1_rounds = w1_env ? atoi(w1_env) : 6;
+    const FirstArgs fa{(const unsigned char*)planes_u8, in_table, in_bias, rows, masks, in_planes, w1_rounds};
+    const BlockCall a{nullptr, nullptr, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, nullptr, n_boards, n_cu, n_dev,
+                      (hipStream_t)stream};
+    // CZ_F16C6: y_lo = a c6 image; w1: cz_conv3x3_c8_pack_weights' (the gather's image is c8), w2: ..._c6_...
+    // CZ_F16C8: y_lo = the c8 image, the filters are cz_conv3x3_c8_pack_weights' (k_resblock_c8<FIRST>)
+    if (dtype == CZ_F16C6) launch_resblock_c8<true, false, true>(a, HeadArgs{}, fa);
+    else if (dtype == CZ_F16C8) launch_resblock_c8<true, false>(a, HeadArgs{}, fa);
+    else if (dtype == CZ_BF16) launch_resblock_pipe<__bf16, true>(a, fa);
+    else launch_resblock_pipe<_Float16, true>(a, fa);
+    return nn_launched("cz_input_resblock");
+}
 
 extern "C" int cz_input_resblock(const void* planes_u8, int in_planes, const float* in_table, const float* in_bias,
                                  const void* w1_packed, const float* bias1, const void* w2_packed, const float* bias2,
@@ -4106,65 +4005,6 @@ extern "C" int cz_input_resblock(const void* planes_u8, int in_planes, const flo
 {
     return cz_input_resblock_m(planes_u8, nullptr, in_planes, in_table, in_bias, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo,
                                n_boards, channels, dtype, rows, n_dev, stream);
-}
-
-// ... with the positions' occupancy boards handed in (masks [n][96] uint32 DEVICE, word = plane position, bit c = plane c shows
-// a piece there: what cz_search_leaf_masks makes the search kernel write beside the planes): the copy waves skip deriving them
-// from the 1260 plane bytes.  masks = NULL: exactly cz_input_resblock.  With masks the planes are not read at all.
-extern "C" int cz_input_resblock_m(const void* planes_u8, const uint32_t* masks, int in_planes, const float* in_table,
-                                   const float* in_bias, const void* w1_packed, const float* bias1, const void* w2_packed,
-                                   const float* bias2, void* y_hi, void* y_lo, int n_boards, int channels, int dtype,
-                                   const int32_t* rows, const int32_t* n_dev, void* stream)
-{
-    if (n_boards < 0 || (!planes_u8 && !masks) || !in_table || !in_bias || !w1_packed || !w2_packed || !bias1 || !bias2 || !y_hi ||
-        !y_lo || in_planes < 1 || in_planes > 32 || (in_planes * 90) % 4 != 0) {
-        czi_set_error("cz_input_resblock: bad argument (u8 planes, in_planes even and <= 32)");
-        return CZ_ERR_ARG;
-    }
-    if (channels != 128 || (dtype != CZ_BF16 && dtype != CZ_F16 && dtype != CZ_F16C8 && dtype != CZ_F16C6)) {
-        czi_set_error("cz_input_resblock: 128 filters; bf16 / f16 split operands or the c8 / c6 pair (use cz_input_conv + cz_resblock)");
-        return CZ_ERR_ARG;
-    }
-    if (n_boards == 0) return CZ_OK;
-    const int n_cu = device_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_input_resblock: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)(n_boards < n_cu ? n_boards : n_cu);
-    // 6 of the ~12-16 term rounds of a board under K loop 1, the rest under K loop 2: measured on one box, extra time of
-    // the launch against an inner block's: 0 rounds +0.43 ms, 3: +0.26, 6: +0.14, 9: +0.22 (window 2 also drains the result)
-    const FirstArgs fa{(const unsigned char*)planes_u8, in_table, in_bias, rows, masks, in_planes, g_first_w1_rounds};
-    if (dtype == CZ_F16C6) {          // y_lo = a c6 image; w1: cz_conv3x3_c8_pack_weights' (the gather's image is c8), w2: ..._c6_...
-        if (launch_resblock_c8<true, false, true>(nullptr, nullptr, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, nullptr,
-                                                  n_boards, n_cu, st, HeadArgs{}, n_dev, fa) != CZ_OK) {
-            czi_set_error("cz_input_resblock: launch failed");
-            return CZ_ERR_HIP;
-        }
-        return CZ_OK;
-    }
-    if (dtype == CZ_F16C8) {          // y_lo = the c8 image, the filters are cz_conv3x3_c8_pack_weights' (k_resblock_c8<FIRST>)
-        if (launch_resblock_c8<true, false>(nullptr, nullptr, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, nullptr, n_boards,
-                                            n_cu, st, HeadArgs{}, n_dev, fa) != CZ_OK) {
-            czi_set_error("cz_input_resblock: launch failed");
-            return CZ_ERR_HIP;
-        }
-        return CZ_OK;
-    }
-    if (dtype == CZ_BF16)
-        hipLaunchKernelGGL((k_resblock_pipe<__bf16, true>), dim3(blocks), dim3(512), 0, st, (const __bf16*)nullptr,
-                           (const __bf16*)nullptr, (const __bf16*)w1_packed, bias1, (const __bf16*)w2_packed, bias2,
-                           (__bf16*)y_hi, (__bf16*)y_lo, n_boards, n_dev, fa);
-    else
-        hipLaunchKernelGGL((k_resblock_pipe<_Float16, true>), dim3(blocks), dim3(512), 0, st, (const _Float16*)nullptr,
-                           (const _Float16*)nullptr, (const _Float16*)w1_packed, bias1, (const _Float16*)w2_packed, bias2,
-                           (_Float16*)y_hi, (_Float16*)y_lo, n_boards, n_dev, fa);
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_input_resblock: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
 }
 
 // test / tuning hook: 1 (default) = 128-filter split residual blocks with operand-pair output run on the
@@ -4176,67 +4016,28 @@ extern "C" int cz_resblock_pipelined(int enable)
     return old;
 }
 
-// ---- compact evaluation queue: the same kernels with a device-side board count (and a row gather in the input layer) ----
-extern "C" int cz_input_conv_q(const void* planes, int planes_dtype, int in_planes, const void* w_packed,
-                               const float* bias, void* y_hi, void* y_lo, int n_boards, int channels, int dtype,
-                               int parts, int relu, const int32_t* rows, const int32_t* n_dev, void* stream)
+template <typename E, int PARTS>
+static void launch_split(unsigned blocks, hipStream_t st, const float* x, const float* bias, void* y_hi, void* y_lo, size_t nquad,
+                         int cquad, int relu)
 {
-    g_q = QueueCtx{rows, n_dev};
-    const int rc = cz_input_conv(planes, planes_dtype, in_planes, w_packed, bias, y_hi, y_lo, n_boards, channels, dtype,
-                                 parts, relu, stream);
-    g_q = QueueCtx{};
-    return rc;
-}
-
-extern "C" int cz_resblock_q(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
-                             const void* w2_packed, const float* bias2, void* y_hi, void* y_lo, float* y_f32,
-                             int n_boards, int channels, int dtype, int parts, const int32_t* n_dev, void* stream)
-{
-    g_q = QueueCtx{nullptr, n_dev};
-    const int rc = cz_resblock(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, y_f32, n_boards, channels,
-                               dtype, parts, stream);
-    g_q = QueueCtx{};
-    return rc;
-}
-
-extern "C" int cz_resblock_heads_q(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1,
-                                   const void* w2_packed, const float* bias2, const float* head_w, const float* head_b,
-                                   float* policy_feat, float* value_feat, int n_boards, int channels, int dtype,
-                                   int n_policy, int n_value, const int32_t* n_dev, void* stream)
-{
-    g_q = QueueCtx{nullptr, n_dev};
-    const int rc = cz_resblock_heads(x_hi, x_lo, w1_packed, bias1, w2_packed, bias2, head_w, head_b, policy_feat,
-                                     value_feat, n_boards, channels, dtype, n_policy, n_value, stream);
-    g_q = QueueCtx{};
-    return rc;
+    hipLaunchKernelGGL((k_split_bias_act<E, PARTS>), dim3(blocks), dim3(256), 0, st, x, bias, (E*)y_hi, (E*)y_lo, nquad, cquad, relu);
 }
 
 extern "C" int cz_split_bias_act(const float* x, const float* bias, void* y_hi, void* y_lo, size_t n_elems,
                                  int channels, int dtype, int parts, int relu, void* stream)
 {
     if (!x || !y_hi || (parts == 2 && !y_lo) || (parts != 1 && parts != 2) || channels <= 0 || channels % 4 != 0 ||
-        n_elems % (size_t)channels != 0 || (dtype != CZ_BF16 && dtype != CZ_F16)) {
-        czi_set_error("cz_split_bias_act: bad argument");
-        return CZ_ERR_ARG;
-    }
+        n_elems % (size_t)channels != 0 || (dtype != CZ_BF16 && dtype != CZ_F16))
+        return nn_error(CZ_ERR_ARG, "cz_split_bias_act: bad argument");
     if (n_elems == 0) return CZ_OK;
     hipStream_t st = (hipStream_t)stream;
     const size_t nquad = n_elems / 4;
-    size_t blocks = (nquad + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
+    const size_t tiles = (nquad + 255) / 256;
+    const unsigned blocks = (unsigned)(tiles < 256 * 16 ? tiles : 256 * 16);
     const int cquad = channels / 4;
-#define CZ_SPLIT(E, PARTS)                                                                                     \
-    hipLaunchKernelGGL((k_split_bias_act<E, PARTS>), dim3((unsigned)blocks), dim3(256), 0, st, x, bias, (E*)y_hi, \
-                       (E*)y_lo, nquad, cquad, relu)
-    if (dtype == CZ_BF16) {
-        if (parts == 2) CZ_SPLIT(__bf16, 2); else CZ_SPLIT(__bf16, 1);
-    } else {
-        if (parts == 2) CZ_SPLIT(_Float16, 2); else CZ_SPLIT(_Float16, 1);
-    }
-#undef CZ_SPLIT
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_split_bias_act: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
+    if (dtype == CZ_BF16 && parts == 2) launch_split<__bf16, 2>(blocks, st, x, bias, y_hi, y_lo, nquad, cquad, relu);
+    else if (dtype == CZ_BF16) launch_split<__bf16, 1>(blocks, st, x, bias, y_hi, y_lo, nquad, cquad, relu);
+    else if (parts == 2) launch_split<_Float16, 2>(blocks, st, x, bias, y_hi, y_lo, nquad, cquad, relu);
+    else launch_split<_Float16, 1>(blocks, st, x, bias, y_hi, y_lo, nquad, cquad, relu);
+    return nn_launched("cz_split_bias_act");
 }

@@ -25,8 +25,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/czero.h"
-
-extern "C" void czi_set_error(const char* msg);
+#include "xq_nn_launch.h"
 
 namespace {
 
@@ -297,46 +296,12 @@ __global__ __launch_bounds__(256) void k_policy_normalize(float* __restrict__ p,
     }
 }
 
-inline uint16_t host_bf16(float f)
+// one dense layer's launch (dtype: the packed pairs', CZ_BF16 or CZ_F16)
+template <int MODE, int F>
+void launch_fc(int dtype, unsigned blocks, hipStream_t st, const FcArgs& a, int n_boards, const int32_t* n_dev)
 {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float host_bf16_f(uint16_t h)
-{
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-inline uint16_t host_f16(float f)
-{
-    const _Float16 h = (_Float16)f;
-    uint16_t b;
-    memcpy(&b, &h, 2);
-    return b;
-}
-inline float host_f16_f(uint16_t b)
-{
-    _Float16 h;
-    memcpy(&h, &b, 2);
-    return (float)h;
-}
-
-int device_cus()
-{
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        n_cu = prop.multiProcessorCount;
-    }
-    return n_cu;
+    if (dtype == CZ_BF16) hipLaunchKernelGGL((k_fc_tile<MODE, F, __bf16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev);
+    else hipLaunchKernelGGL((k_fc_tile<MODE, F, _Float16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev);
 }
 
 }  // namespace
@@ -365,11 +330,11 @@ extern "C" int cz_fc_pack_weights(const float* w, int n_out, int n_in, int dtype
                     const int o = lt * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + j;
                     if (o >= n_out || k >= n_in) continue;
                     const float v = w[(size_t)o * n_in + k];
-                    const uint16_t hi = dtype == CZ_BF16 ? host_bf16(v) : host_f16(v);
+                    const uint16_t hi = dtype == CZ_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
                     const size_t base = (((size_t)lt * (ksteps + FC_PAD_STEPS) + ks) * 2) * 64 * 8;
                     out[base + (size_t)lane * 8 + j] = hi;
                     out[base + 64 * 8 + (size_t)lane * 8 + j] =
-                        dtype == CZ_BF16 ? host_bf16(v - host_bf16_f(hi)) : host_f16(v - host_f16_f(hi));
+                        dtype == CZ_BF16 ? f32_to_bf16_bits(v - bf16_bits_to_f32(hi)) : f32_to_f16_bits(v - f16_bits_to_f32(hi));
                 }
     return CZ_OK;
 }
@@ -381,32 +346,22 @@ extern "C" int cz_heads_tail(const float* policy_feat, int n_policy_feat, const 
 {
     if (!policy_feat || !wp_packed || !bias_p || !value_feat || !w1_packed || !bias1 || !w2 || !policy || !value ||
         !stats_scratch || n_boards < 0 || (dtype != CZ_BF16 && dtype != CZ_F16) || n_labels < 2 || (n_labels & 1) || n_hidden < 1 || n_policy_feat < 1 ||
-        (n_policy_feat != 180 && n_policy_feat != 360) || (n_value_feat != 180 && n_value_feat != 360)) {
-        czi_set_error("cz_heads_tail: bad argument (n_labels even; 180 or 360 features per head: 2 or 4 filters x 90 squares; "
-                      "dtype of the packed pairs: CZ_BF16 or CZ_F16)");
-        return CZ_ERR_ARG;
-    }
+        (n_policy_feat != 180 && n_policy_feat != 360) || (n_value_feat != 180 && n_value_feat != 360))
+        return nn_error(CZ_ERR_ARG, "cz_heads_tail: bad argument (n_labels even; 180 or 360 features per head: 2 or 4 filters x 90 squares; "
+                                    "dtype of the packed pairs: CZ_BF16 or CZ_F16)");
     if (n_boards == 0) return CZ_OK;
-    const int n_cu = device_cus();
-    if (n_cu < 0) {
-        czi_set_error("cz_heads_tail: cannot query the device");
-        return CZ_ERR_HIP;
-    }
+    const int n_cu = nn_cu_count("cz_heads_tail");
+    if (n_cu < 0) return CZ_ERR_HIP;
     hipStream_t st = (hipStream_t)stream;
     const int row_tiles = (n_boards + TILE_ROWS - 1) / TILE_ROWS;
+    const unsigned blocks = nn_grid(row_tiles, 2 * n_cu);
     {
         FcArgs a{};
         a.feat = policy_feat; a.wp = wp_packed; a.bias = bias_p; a.F = n_policy_feat;
         a.ksteps = (n_policy_feat + 15) / 16; a.n_out = n_labels; a.n_tiles = (n_labels + 31) / 32;
         a.logits = policy; a.stats = reinterpret_cast<float2*>(stats_scratch);
-        const unsigned blocks = (unsigned)(row_tiles < 2 * n_cu ? row_tiles : 2 * n_cu);
-#define CZ_FC(MODE, FEAT)                                                                                              \
-        do {                                                                                                          \
-            if (dtype == CZ_BF16) hipLaunchKernelGGL((k_fc_tile<MODE, FEAT, __bf16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev); \
-            else hipLaunchKernelGGL((k_fc_tile<MODE, FEAT, _Float16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev);                \
-        } while (0)
-        if (n_policy_feat == 360) CZ_FC(FC_POLICY, 360);
-        else CZ_FC(FC_POLICY, 180);
+        if (n_policy_feat == 360) launch_fc<FC_POLICY, 360>(dtype, blocks, st, a, n_boards, n_dev);
+        else launch_fc<FC_POLICY, 180>(dtype, blocks, st, a, n_boards, n_dev);
         if (normalize) {              // (0: `policy` keeps the raw logits -- cz_search_policy_logits takes them as they are)
             size_t nb = ((size_t)n_boards + 3) / 4;
             if (nb > (size_t)n_cu * 16) nb = (size_t)n_cu * 16;
@@ -419,14 +374,8 @@ extern "C" int cz_heads_tail(const float* policy_feat, int n_policy_feat, const 
         a.feat = value_feat; a.wp = w1_packed; a.bias = bias1; a.F = n_value_feat;
         a.ksteps = (n_value_feat + 15) / 16; a.n_out = n_hidden; a.n_tiles = (n_hidden + 31) / 32;
         a.w2 = w2; a.b2 = b2; a.value = value;
-        const unsigned blocks = (unsigned)(row_tiles < 2 * n_cu ? row_tiles : 2 * n_cu);
-        if (n_value_feat == 180) CZ_FC(FC_VALUE, 180);
-        else CZ_FC(FC_VALUE, 360);
-#undef CZ_FC
+        if (n_value_feat == 180) launch_fc<FC_VALUE, 180>(dtype, blocks, st, a, n_boards, n_dev);
+        else launch_fc<FC_VALUE, 360>(dtype, blocks, st, a, n_boards, n_dev);
     }
-    if (hipGetLastError() != hipSuccess) {
-        czi_set_error("cz_heads_tail: launch failed");
-        return CZ_ERR_HIP;
-    }
-    return CZ_OK;
+    return nn_launched("cz_heads_tail");
 }

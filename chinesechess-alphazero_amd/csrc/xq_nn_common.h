@@ -1,11 +1,25 @@
 // xq_nn_common.h -- device helpers shared by the network translation units (csrc/xq_conv.hip, csrc/xq_tower.hip):
-// MFMA wrappers, the operand formats' conversions (c8 triple, c6 pieces), the head / input-layer argument blocks and the
-// f16x3 / bf16x3 K loop with its in-place second epilogue (k_resblock_pipe's).  Everything sits in an anonymous namespace:
-// each translation unit gets its own copy.
+// MFMA wrappers, the operand formats' conversions (c8 triple, c6 pieces), the head / input-layer argument blocks, the chain
+// kernels' block list and the f16x3 / bf16x3 K loop with its in-place second epilogue (k_resblock_pipe's).  BlockChain is a
+// global type (it crosses translation units, csrc/xq_nn_launch.h); everything else sits in an anonymous namespace: each
+// translation unit gets its own copy.  The host code that launches the kernels shares csrc/xq_nn_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "xq_c8_kloop.h"
+
+// The consecutive residual blocks a chain kernel takes every board through in one launch, as a kernel argument: MAX = 24 for
+// k_tower_plain2, 12 for k_resblock_ip_c8, k_resblock_ip4_c8 and k_tower_pairs4.  Filled by fill_chain (csrc/xq_nn_launch.h).
+template <int MAX> struct BlockChain {
+    const void* w1[MAX];
+    const void* w2[MAX];
+    const float* b1[MAX];
+    const float* b2[MAX];
+    int n;
+};
+static_assert(sizeof(BlockChain<12>) == 4 * 12 * 8 + 8 && sizeof(BlockChain<24>) == 4 * 24 * 8 + 8 &&
+              offsetof(BlockChain<12>, n) == 4 * 12 * 8, "the layout of the kernels' argument blocks");
 
 namespace {
 

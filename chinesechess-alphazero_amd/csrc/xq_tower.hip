@@ -22,13 +22,7 @@
 #include "../../include/czero.h"
 #include "xq_c8_kloop.h"
 #include "xq_nn_common.h"
-
-extern "C" void czi_set_error(const char* msg);
-// csrc/xq_conv.hip: cz_tower's launches on the four-wave pair kernel (k_resblock_ip4_c8<128>)
-extern "C" int czi_tower4_launch(const void* x_hi, const void* x_img, int n_blocks, const void* const* w1, const float* const* b1,
-                                 const void* const* w2, const float* const* b2, int c6, int exit_mode, void* y_hi, void* y_img,
-                                 const float* head_w, const float* head_b, float* pol, float* val, int n_pol, int n_boards,
-                                 int n_cu, const int32_t* n_dev, void* stream);
+#include "xq_nn_launch.h"
 
 // ---- kernel: the chain of PAIR blocks on four matrix waves (round 6) -----------------------------------------------------------
 // k_resblock_pipe's arithmetic (three MFMAs per product: w_hi x_hi, w_lo x_hi, w_hi x_lo in that order per K-step; epilogue 1
@@ -43,13 +37,6 @@ extern "C" int czi_tower4_launch(const void* x_hi, const void* x_img, int n_bloc
 // of k_resblock_pipe; the heads exit within the bound tests/test_gpu_tower.py asserts.
 namespace tw4 {
 constexpr int MAX_BLOCKS = 12;
-struct Chain {
-    const void* w1[MAX_BLOCKS];
-    const void* w2[MAX_BLOCKS];
-    const float* b1[MAX_BLOCKS];
-    const float* b2[MAX_BLOCKS];
-    int n;
-};
 }  // namespace tw4
 
 template <int CH> struct Tp4 {                  // geometry for CH filters (128: 256-byte rows; 192: 384-byte rows, chunks swizzled in groups of 8)
@@ -149,7 +136,7 @@ __device__ __forceinline__ void pairs_kloop_ctw(const unsigned char* lds, int ro
 
 template <typename E, int CH>
 __global__ __launch_bounds__(256, 1) void k_tower_pairs4(
-    const E* __restrict__ xh, const E* __restrict__ xl, tw4::Chain ch, E* __restrict__ yh, E* __restrict__ yl, int n_boards,
+    const E* __restrict__ xh, const E* __restrict__ xl, BlockChain<tw4::MAX_BLOCKS> ch, E* __restrict__ yh, E* __restrict__ yl, int n_boards,
     const int32_t* __restrict__ n_dev, HeadArgs hd, int heads, float* __restrict__ yf_last)
 {
     typedef Tp4<CH> G;
@@ -366,41 +353,33 @@ __global__ __launch_bounds__(256, 1) void k_tower_pairs4(
 }
 
 // the pair chains' launches (cz_tower_pairs: 128 filters; cz_resblock_chain in csrc/xq_conv.hip: 192 filters, no heads exit)
-extern "C" int czi_pairs4_launch(const void* x_hi, const void* x_lo, int n_blocks, const void* const* w1, const float* const* b1,
-                                 const void* const* w2, const float* const* b2, void* y_hi, void* y_lo, const float* head_w,
-                                 const float* head_b, float* pol, float* val, int n_pol, int n_boards, int channels, int dtype,
-                                 int n_cu, const int32_t* n_dev, void* stream, float* y_f32)
+template <typename E, int CH>
+static void launch_pairs4(const void* x_hi, const void* x_lo, const BlockChain<tw4::MAX_BLOCKS>& ch, void* y_hi, void* y_lo,
+                          HeadArgs hd, int heads, int n_boards, int n_cu, const int32_t* n_dev, hipStream_t st, float* y_f32)
 {
-    if (n_blocks > tw4::MAX_BLOCKS || (channels != 128 && channels != 192) || (head_w && channels != 128)) return CZ_ERR_ARG;
-    tw4::Chain ch{};
-    ch.n = n_blocks;
-    for (int b = 0; b < n_blocks; ++b) { ch.w1[b] = w1[b]; ch.w2[b] = w2[b]; ch.b1[b] = b1[b]; ch.b2[b] = b2[b]; }
+    hipLaunchKernelGGL((k_tower_pairs4<E, CH>), dim3(nn_grid((n_boards + 1) / 2, n_cu)), dim3(256), 0, st, (const E*)x_hi,
+                       (const E*)x_lo, ch, (E*)y_hi, (E*)y_lo, n_boards, n_dev, hd, heads, y_f32);
+}
+
+extern "C" int czi_pairs4_launch(const char* name, const void* x_hi, const void* x_lo, const BlockChain<12>* ch, void* y_hi,
+                                 void* y_lo, const float* head_w, const float* head_b, float* pol, float* val, int n_pol,
+                                 int n_boards, int channels, int dtype, int n_cu, const int32_t* n_dev, void* stream,
+                                 float* y_f32)
+{
+    if ((channels != 128 && channels != 192) || (head_w && channels != 128)) return CZ_ERR_ARG;
     const HeadArgs hd = head_w ? HeadArgs{head_w, head_b, pol, val, n_pol} : HeadArgs{};
-    const int n_pairs = (n_boards + 1) / 2;
-    const unsigned blocks = (unsigned)(n_pairs < n_cu ? n_pairs : n_cu);
+    const int heads = head_w ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-#define CZ_P4(E, CH) hipLaunchKernelGGL((k_tower_pairs4<E, CH>), dim3(blocks), dim3(256), 0, st, (const E*)x_hi, (const E*)x_lo, ch, \
-                                        (E*)y_hi, (E*)y_lo, n_boards, n_dev, hd, head_w ? 1 : 0, y_f32)
-    if (channels == 128) { if (dtype == CZ_F16) CZ_P4(_Float16, 128); else CZ_P4(__bf16, 128); }
-    else { if (dtype == CZ_F16) CZ_P4(_Float16, 192); else CZ_P4(__bf16, 192); }
-#undef CZ_P4
-    return hipGetLastError() == hipSuccess ? CZ_OK : CZ_ERR_HIP;
+    if (channels == 128 && dtype == CZ_F16) launch_pairs4<_Float16, 128>(x_hi, x_lo, *ch, y_hi, y_lo, hd, heads, n_boards, n_cu, n_dev, st, y_f32);
+    else if (channels == 128) launch_pairs4<__bf16, 128>(x_hi, x_lo, *ch, y_hi, y_lo, hd, heads, n_boards, n_cu, n_dev, st, y_f32);
+    else if (dtype == CZ_F16) launch_pairs4<_Float16, 192>(x_hi, x_lo, *ch, y_hi, y_lo, hd, heads, n_boards, n_cu, n_dev, st, y_f32);
+    else launch_pairs4<__bf16, 192>(x_hi, x_lo, *ch, y_hi, y_lo, hd, heads, n_boards, n_cu, n_dev, st, y_f32);
+    return nn_launched(name);
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------
 constexpr int TOWER_MAX_BLOCKS = 8;     // blocks per chain of cz_tower / cz_tower_pairs (model.tower_plan splits longer towers)
-
-static int tower_cu_count()
-{
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        n_cu = prop.multiProcessorCount;
-    }
-    return n_cu;
-}
+static_assert(TOWER_MAX_BLOCKS <= tw4::MAX_BLOCKS, "a chain fits the kernels' block list");
 
 // One chain of c6 / c8 blocks.  fmt_x / fmt_y: per block, CZ_IMG_C8 or CZ_IMG_C6 (NULL: all CZ_IMG_C6); exit_fmt: CZ_IMG_C8 /
 // CZ_IMG_C6 / CZ_IMG_PAIR, or CZ_EXIT_HEADS.
@@ -414,39 +393,25 @@ extern "C" int cz_tower(const void* x_hi, const void* x_img, int n_blocks, const
     if (n_boards < 0 || !x_hi || !x_img || !w1_packed || !w2_packed || !bias1 || !bias2 || n_blocks < 1 ||
         n_blocks > TOWER_MAX_BLOCKS || (!heads && (!y_hi || !y_img)) ||
         (heads && (!head_w || !head_b || !policy_feat || !value_feat || n_policy < 1 || n_value < 1 || n_policy + n_value != 6)) ||
-        (!heads && exit_fmt != CZ_IMG_C8 && exit_fmt != CZ_IMG_C6 && exit_fmt != CZ_IMG_PAIR)) {
-        czi_set_error("cz_tower: bad argument (1 .. 8 blocks; exit CZ_IMG_C8 / CZ_IMG_C6 / CZ_IMG_PAIR with y_hi + y_img, or "
-                      "CZ_EXIT_HEADS with n_policy + n_value == 6)");
-        return CZ_ERR_ARG;
-    }
+        (!heads && exit_fmt != CZ_IMG_C8 && exit_fmt != CZ_IMG_C6 && exit_fmt != CZ_IMG_PAIR))
+        return nn_error(CZ_ERR_ARG, "cz_tower: bad argument (1 .. 8 blocks; exit CZ_IMG_C8 / CZ_IMG_C6 / CZ_IMG_PAIR with y_hi + y_img, or "
+                                    "CZ_EXIT_HEADS with n_policy + n_value == 6)");
     const int fmt0 = fmt_x ? fmt_x[0] : CZ_IMG_C6;
-    for (int b = 0; b < n_blocks; ++b) {
-        if (!w1_packed[b] || !w2_packed[b] || !bias1[b] || !bias2[b]) {
-            czi_set_error("cz_tower: null block parameter");
-            return CZ_ERR_ARG;
-        }
+    BlockChain<tw4::MAX_BLOCKS> ch{};
+    for (int b = 0; b < n_blocks; ++b) {            // (block by block: a block's pointers are checked before its formats)
+        if (!fill_chain(ch, "cz_tower", b + 1, w1_packed, bias1, w2_packed, bias2, b)) return CZ_ERR_ARG;
         const int fx = fmt_x ? fmt_x[b] : CZ_IMG_C6, fy = fmt_y ? fmt_y[b] : CZ_IMG_C6;
-        if ((fx != CZ_IMG_C8 && fx != CZ_IMG_C6) || fy != fx || fx != fmt0) {
-            czi_set_error("cz_tower: one image format per chain, CZ_IMG_C8 or CZ_IMG_C6 (a hybrid tower is one chain per "
-                          "arithmetic -- the exit of the first hands over; pair blocks: cz_tower_pairs)");
-            return CZ_ERR_ARG;
-        }
+        if ((fx != CZ_IMG_C8 && fx != CZ_IMG_C6) || fy != fx || fx != fmt0)
+            return nn_error(CZ_ERR_ARG, "cz_tower: one image format per chain, CZ_IMG_C8 or CZ_IMG_C6 (a hybrid tower is one chain per "
+                                        "arithmetic -- the exit of the first hands over; pair blocks: cz_tower_pairs)");
     }
-    if (!heads && ((fmt0 == CZ_IMG_C6 && exit_fmt == CZ_IMG_PAIR) || (fmt0 == CZ_IMG_C8 && exit_fmt == CZ_IMG_C6))) {
-        czi_set_error("cz_tower: a c6 chain ends on a c6 or c8 image, a c8 chain on a c8 image or fp16 pairs");
-        return CZ_ERR_ARG;
-    }
+    if (!heads && ((fmt0 == CZ_IMG_C6 && exit_fmt == CZ_IMG_PAIR) || (fmt0 == CZ_IMG_C8 && exit_fmt == CZ_IMG_C6)))
+        return nn_error(CZ_ERR_ARG, "cz_tower: a c6 chain ends on a c6 or c8 image, a c8 chain on a c8 image or fp16 pairs");
     if (n_boards == 0) return CZ_OK;
-    const int n_cu = tower_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_tower: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    const int rc = czi_tower4_launch(x_hi, x_img, n_blocks, w1_packed, bias1, w2_packed, bias2, fmt0 == CZ_IMG_C6,
-                                     heads ? 3 : (exit_fmt == CZ_IMG_PAIR ? 2 : 0), y_hi, y_img, head_w, head_b, policy_feat,
-                                     value_feat, n_policy, n_boards, n_cu, n_dev, stream);
-    if (rc != CZ_OK) czi_set_error("cz_tower: launch failed");
-    return rc;
+    const int n_cu = nn_cu_count("cz_tower");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    return czi_tower4_launch("cz_tower", x_hi, x_img, &ch, fmt0 == CZ_IMG_C6, heads ? 3 : (exit_fmt == CZ_IMG_PAIR ? 2 : 0), y_hi,
+                             y_img, head_w, head_b, policy_feat, value_feat, n_policy, n_boards, n_cu, n_dev, stream);
 }
 
 // A chain of PAIR blocks ((hi, lo) operands of dtype CZ_F16 or CZ_BF16; cz_conv3x3_pack_weights filters with parts = 2):
@@ -460,25 +425,14 @@ extern "C" int cz_tower_pairs(const void* x_hi, const void* x_lo, int n_blocks, 
     const bool heads = head_w != nullptr;
     if (n_boards < 0 || !x_hi || !x_lo || !w1_packed || !w2_packed || !bias1 || !bias2 || n_blocks < 1 ||
         n_blocks > TOWER_MAX_BLOCKS || (dtype != CZ_F16 && dtype != CZ_BF16) || (!heads && (!y_hi || !y_lo)) ||
-        (heads && (!head_b || !policy_feat || !value_feat || n_policy < 1 || n_value < 1 || n_policy + n_value != 6))) {
-        czi_set_error("cz_tower_pairs: bad argument (1 .. 8 blocks of (hi, lo) f16 / bf16 operands; y_hi + y_lo, or the head "
-                      "arguments with n_policy + n_value == 6)");
-        return CZ_ERR_ARG;
-    }
-    for (int b = 0; b < n_blocks; ++b) {
-        if (!w1_packed[b] || !w2_packed[b] || !bias1[b] || !bias2[b]) {
-            czi_set_error("cz_tower_pairs: null block parameter");
-            return CZ_ERR_ARG;
-        }
-    }
+        (heads && (!head_b || !policy_feat || !value_feat || n_policy < 1 || n_value < 1 || n_policy + n_value != 6)))
+        return nn_error(CZ_ERR_ARG, "cz_tower_pairs: bad argument (1 .. 8 blocks of (hi, lo) f16 / bf16 operands; y_hi + y_lo, or the head "
+                                    "arguments with n_policy + n_value == 6)");
+    BlockChain<tw4::MAX_BLOCKS> ch{};
+    if (!fill_chain(ch, "cz_tower_pairs", n_blocks, w1_packed, bias1, w2_packed, bias2)) return CZ_ERR_ARG;
     if (n_boards == 0) return CZ_OK;
-    const int n_cu = tower_cu_count();
-    if (n_cu < 0) {
-        czi_set_error("cz_tower_pairs: cannot query the device");
-        return CZ_ERR_HIP;
-    }
-    const int rc = czi_pairs4_launch(x_hi, x_lo, n_blocks, w1_packed, bias1, w2_packed, bias2, y_hi, y_lo, head_w, head_b,
-                                     policy_feat, value_feat, n_policy, n_boards, 128, dtype, n_cu, n_dev, stream, nullptr);
-    if (rc != CZ_OK) czi_set_error("cz_tower_pairs: launch failed");
-    return rc;
+    const int n_cu = nn_cu_count("cz_tower_pairs");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    return czi_pairs4_launch("cz_tower_pairs", x_hi, x_lo, &ch, y_hi, y_lo, head_w, head_b, policy_feat, value_feat, n_policy,
+                             n_boards, 128, dtype, n_cu, n_dev, stream, nullptr);
 }
