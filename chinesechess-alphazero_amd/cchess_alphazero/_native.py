@@ -118,6 +118,10 @@ def _declare(L):
         L.cz_policy_value_loss_q.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, C.c_float, i32,
                                              C.c_float, C.c_float, vp, vp, vp, vp, vp]
         L.cz_policy_value_loss_q.restype = i32
+    if hasattr(L, "cz_policy_value_loss_w"):
+        L.cz_policy_value_loss_w.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, C.c_float, vp, i32,
+                                             C.c_float, C.c_float, vp, vp, vp, vp, vp]
+        L.cz_policy_value_loss_w.restype = i32
     if hasattr(L, "cz_search_create"):
         from . import _native_search
         _native_search.declare(L)
@@ -276,14 +280,16 @@ def gather_planes(boards, prev, idx, depth=14, out=None, mirror=None):
 
 
 def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0,
-                      mirror=None, q=None, q_ratio=0.0):
+                      mirror=None, q=None, q_ratio=0.0, row_w=None):
     """Per-row policy loss, squared value error and the gradients of w_p mean(policy loss) + w_v mean(sq. error) with
     respect to the logits [B, 2086] and the value [B] (cz_policy_value_loss; mode 0 played one-hot, 1 visit counts).
     logits may have a leading dimension > 2086 (a row-strided view).  Visit arrays with no entries (or None) leave every
     row on the played move's one-hot.  mirror: uint8 [B] on the device, a flagged row's target labels go through
     label_mirror() (cz_policy_value_loss_m); None calls the unflagged entry point.  q: float32 [n_pos] on the device (NaN =
     no search value) with q_ratio L: the value target is z + L (q - z) (cz_policy_value_loss_q, mirror flags or none);
-    q None calls the entry points above."""
+    q None calls the entry points above.  row_w: float32 [n_pos] on the device, the training weight of every window
+    position (cz_policy_value_loss_w, with or without mirror flags and q): it scales the row's gradients, pl and se stay
+    the unweighted per-row values; None calls the entry points above."""
     import torch
     require_gpu()
     assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
@@ -293,6 +299,18 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
     se = torch.empty((b,), dtype=torch.float32, device=dev)
     gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
     gv = torch.empty((b,), dtype=torch.float32, device=dev)
+    if row_w is not None:
+        assert row_w.shape == z.shape and (q is None or q.shape == z.shape), (tuple(row_w.shape), tuple(z.shape))
+        check(lib().cz_policy_value_loss_w(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
+                                           _dev(idx, torch.int32), None if mirror is None else _flags(mirror, b), b,
+                                           played.shape[0], _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16),
+                                           _opt(vis_count, torch.int32), 0 if vis_label is None else vis_label.shape[0],
+                                           _dev(played, torch.uint16), _dev(z, torch.float32), _opt(q, torch.float32),
+                                           float(q_ratio) if q is not None else 0.0, _dev(row_w, torch.float32), int(mode),
+                                           float(w_p), float(w_v), _dev(pl, torch.float32), _dev(se, torch.float32),
+                                           _dev(gl, torch.float32), _dev(gv, torch.float32), _stream()),
+              "cz_policy_value_loss_w")
+        return pl, se, gl, gv
     if q is not None:
         assert q.shape == z.shape, (tuple(q.shape), tuple(z.shape))
         check(lib().cz_policy_value_loss_q(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),

@@ -27,8 +27,9 @@ VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (
 # was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
 # search of the playout cap (set_playout_cap); whether n holds the PRUNED counts of set_forced_playouts, and then
 # raw_total, the sum of the raw counts of the non-banned edges (0 otherwise); q, the root's search value of the ply
-# (record_values; None with the value record off and where the ring held NaN, "no value").
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q", defaults=(None,))
+# (record_values; None with the value record off and where the ring held NaN, "no value"); s, the policy surprise of the
+# ply, KL(recorded counts || priors without noise) (record_surprise; None with that record off and for NaN).
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s", defaults=(None, None))
 
 
 class SearchCfg(C.Structure):
@@ -100,6 +101,18 @@ def declare(L):
         L.cz_search_root_value.restype = i32
         L.cz_root_value.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
         L.cz_root_value.restype = i32
+    if hasattr(L, "cz_search_record_surprise"):
+        L.cz_search_record_surprise.argtypes = [vp, i32, vp]
+        L.cz_search_record_surprise.restype = i32
+    if hasattr(L, "cz_search_drain_visits_qs"):
+        L.cz_search_drain_visits_qs.argtypes = [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
+        L.cz_search_drain_visits_qs.restype = i32
+    if hasattr(L, "cz_search_root_surprise"):
+        L.cz_search_root_surprise.argtypes = [vp, vp, vp]
+        L.cz_search_root_surprise.restype = i32
+    if hasattr(L, "cz_root_surprise"):
+        L.cz_root_surprise.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        L.cz_root_surprise.restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -192,6 +205,7 @@ class Search:
         self._cursor = C.c_uint(0)
         self.visit_capacity = 0                # record_visits(): entries the device ring holds, 0 = off
         self.values_on = False                 # record_values(): every entry comes with the root's search value
+        self.surprise_on = False               # record_surprise(): every entry comes with the ply's policy surprise
         self._visits = {}                      # game id -> [(ply, raw entry)] of games not finished yet
         self._raw_visits = []                  # fetched entries not yet sorted by game (pull_visits(defer=True))
         self._visits_dropped = 0
@@ -267,6 +281,7 @@ class Search:
                       "cz_search_record_visits")
         self.visit_capacity = (int(capacity) or 64 * self.G) if on else 0
         self.values_on = False                 # (the library frees the value ring with the visit ring)
+        self.surprise_on = False               # (and the surprise ring)
         self._visits = {}
         self._raw_visits = []
         self._visits_dropped = 0
@@ -322,6 +337,25 @@ class Search:
                       "cz_search_root_value")
         return q.cpu().numpy()
 
+    def record_surprise(self, on=True):
+        """Self-play: every visit entry comes with the ply's policy surprise s, the Kullback-Leibler divergence of the
+        recorded counts from the root's priors without noise (cz_search_record_surprise; include/czero.h has the
+        arithmetic): VisitEntry.s, None where the root had none.  Needs record_visits() on, and a later record_visits()
+        call switches it off again.  Call it before start_selfplay() and before a graph capture.  Entries fetched before
+        the switch keep what they had."""
+        _native.check(self.L.cz_search_record_surprise(self.h, int(bool(on)), self._stream()),
+                      "cz_search_record_surprise")
+        self.surprise_on = bool(on)
+
+    def root_surprise(self):
+        """The policy surprise of every current root, as a visit entry of that root would carry it
+        (cz_search_root_surprise; bans of the current set_roots, the counts of root_targets): float64 [G], NaN = none."""
+        import torch
+        out = torch.empty((self.G,), dtype=torch.float64, device=self.device)
+        _native.check(self.L.cz_search_root_surprise(self.h, C.c_void_p(out.data_ptr()), self._stream()),
+                      "cz_search_root_surprise")
+        return out.cpu().numpy()
+
     def root_targets(self):
         """The pruned counts of every current root (cz_search_root_targets; edge order of root_stats, bans of the current
         set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
@@ -348,7 +382,15 @@ class Search:
             return 0
         buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
         q = None
-        if self.values_on:
+        if self.surprise_on:
+            # both rings beside the entries; a value record that is off leaves q at NaN, "no value"
+            q = np.full((n.value,), np.nan, dtype=np.float64)
+            sp = np.empty((n.value,), dtype=np.float64)
+            _native.check(self.L.cz_search_drain_visits_qs(self.h, buf.ctypes.data, q.ctypes.data if self.values_on else None,
+                                                           sp.ctypes.data, n.value, C.byref(n), C.byref(dropped),
+                                                           self._stream()), "cz_search_drain_visits_qs")
+            q = np.stack([q, sp], axis=1)
+        elif self.values_on:
             q = np.empty((n.value,), dtype=np.float64)
             _native.check(self.L.cz_search_drain_visits_q(self.h, buf.ctypes.data, q.ctypes.data, n.value, C.byref(n),
                                                           C.byref(dropped), self._stream()), "cz_search_drain_visits_q")
@@ -370,7 +412,7 @@ class Search:
             for i in range(buf.shape[0]):      # kept trimmed to the root's edges until the game's record arrives
                 ne = int(buf[i, 6])
                 row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
-                if q is not None:              # the entry's value rides behind its edges
+                if q is not None:              # the entry's value (and surprise) ride behind its edges
                     row += q[i:i + 1].tobytes()
                 self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
 
@@ -385,18 +427,22 @@ class Search:
     @staticmethod
     def parse_visit_entry(row):
         """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges], then with the value
-        record on its float64 q) -> VisitEntry."""
+        record on its float64 q, with the surprise record on float64 q (NaN with the value record off) and s) ->
+        VisitEntry."""
         a = np.frombuffer(row, dtype=np.uint8)
         ne = int(a[6])
-        q = None
-        if len(a) == 24 + 6 * ne:
-            q = float(a[16 + 6 * ne:].view(np.float64)[0])
+        q = sp = None
+        if len(a) >= 24 + 6 * ne:
+            q = float(a[16 + 6 * ne:24 + 6 * ne].view(np.float64)[0])
             q = None if q != q else q
+        if len(a) == 32 + 6 * ne:
+            sp = float(a[24 + 6 * ne:].view(np.float64)[0])
+            sp = None if sp != sp else sp
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
-                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q)
+                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp)
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -677,3 +723,27 @@ def root_value_rows(labels, m, n, w, n_edges):
 
 
 Search.root_value_rows = staticmethod(root_value_rows)
+
+
+def root_surprise_rows(labels, m, p, n_edges):
+    """cz_root_surprise: the policy-surprise arithmetic of record_surprise on caller-supplied rows.  labels uint16 (bit 15 =
+    banned), m int32 (the recorded counts) and p float32 (the priors without noise), all [rows, 128] cuda tensors; n_edges
+    uint8 [rows].  Returns float64 [rows] on the device, NaN = no surprise."""
+    import torch
+    _native.require_gpu()
+    rows = int(n_edges.numel())
+    want = ((labels, torch.uint16), (m, torch.int32), (p, torch.float32))
+    for t, dt in want:
+        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"root_surprise_rows: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
+    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
+        raise ValueError("root_surprise_rows: n_edges must be a contiguous cuda uint8 tensor")
+    out = torch.empty((rows,), dtype=torch.float64, device=m.device)
+    _native.check(_native.lib().cz_root_surprise(
+        C.c_void_p(labels.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(p.data_ptr()),
+        C.c_void_p(n_edges.data_ptr()), rows, C.c_void_p(out.data_ptr()),
+        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_root_surprise")
+    return out
+
+
+Search.root_surprise_rows = staticmethod(root_surprise_rows)

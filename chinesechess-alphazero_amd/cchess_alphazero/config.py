@@ -103,6 +103,9 @@ class EngineConfig(_Section):
                                                   # sqrt(K * p * N) visits, the recorded counts are pruned; 0 = off
                          record_q=False,          # play records carry each searched ply's root search value (run.py self
                                                   # --record-q, needs record_visits): items [move, value, pi, weight, q]
+                         record_surprise=False,   # play records carry each recorded ply's policy surprise (run.py self
+                                                  # --record-surprise, needs record_visits): items [move, value, pi,
+                                                  # weight, q or None, s]
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -42,7 +42,7 @@ class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
-                 full_rate=None, forced_playouts=None, record_q=None):
+                 full_rate=None, forced_playouts=None, record_q=None, record_surprise=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -58,7 +58,10 @@ class SelfPlayEngine:
         on full plies a tried root child is visited at least sqrt(k * p * N) times, and the recorded visit counts -- the
         pi of drain()'s items -- are the pruned ones (include/czero.h).  The moves are chosen from the raw counts.
         record_q: every searched ply's root search value goes into the records (None = config.engine.record_q; needs
-        record_visits): drain()'s items become [move, value, pi or None, weight, q] (cz_search_record_values)."""
+        record_visits): drain()'s items become [move, value, pi or None, weight, q] (cz_search_record_values).
+        record_surprise: every ply with a visit entry records its policy surprise s, the Kullback-Leibler divergence of
+        the recorded counts from the root's priors (None = config.engine.record_surprise; needs record_visits): drain()'s
+        items become [move, value, pi or None, weight, q or None, s] (cz_search_record_surprise)."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -129,6 +132,11 @@ class SelfPlayEngine:
             raise ValueError("record_q needs record_visits: the search values ride beside the visit entries")
         if self.record_q:                                      # likewise
             self.search.record_values(True)
+        self.record_surprise = bool(getattr(ec, "record_surprise", False) if record_surprise is None else record_surprise)
+        if self.record_surprise and not self.record_visits:
+            raise ValueError("record_surprise needs record_visits: the surprises ride beside the visit entries")
+        if self.record_surprise:                               # likewise
+            self.search.record_surprise(True)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -325,7 +333,9 @@ class SelfPlayEngine:
         entries, sum of raw_total - sum of the non-banned pruned counts (0 without forced playouts).  With record_q the
         item of every ply that has a visit entry is [move, value, pi or None, weight, q] (lib/data_helper.py record_item):
         weight 1 on a full ply and 0 on a fast one, q the root's search value rounded to 6 places or None; the appended
-        king capture, a resignation and games whose visit record is incomplete keep the shorter forms."""
+        king capture, a resignation and games whose visit record is incomplete keep the shorter forms.  With
+        record_surprise such an item is [move, value, pi or None, weight, q or None, s]: s the ply's policy surprise
+        rounded to 6 places or None, q None with record_q off."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
@@ -335,7 +345,7 @@ class SelfPlayEngine:
             for i, m in enumerate(r["moves"]):
                 e = vis[i] if vis is not None and i < len(vis) and not vis[i].resign else None
                 data.append(record_item(ActionLabelsRed[int(m)], v if i % 2 == 0 else -v, e, r["fast"][i], self.record_q,
-                                        ActionLabelsRed))
+                                        ActionLabelsRed, record_surprise=self.record_surprise))
             pruned = [e for e in vis or [] if e.pruned]
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
                             resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]),

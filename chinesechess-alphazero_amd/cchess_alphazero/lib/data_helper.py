@@ -8,7 +8,8 @@ root's visit counts when the move was chosen (see ``pi_from_visits``).  The refe
 and ``item[1]`` (worker/optimize.py:245-246), so such files feed it unchanged.
 
 With a playout cap the item of a fast ply is ``[move, value, pi or None, 0]``; with ``engine.record_q`` on every searched
-ply's item is ``[move, value, pi or None, weight, q]`` (``record_item``)."""
+ply's item is ``[move, value, pi or None, weight, q]``, with ``engine.record_surprise`` on
+``[move, value, pi or None, weight, q or None, s]`` (``record_item``)."""
 import json
 import os
 from datetime import datetime, timedelta, timezone
@@ -26,7 +27,7 @@ def pi_from_visits(moves, n, banned, labels):
     return [[labels[int(m)], int(c)] for m, c, b in zip(moves, n, banned) if not b and int(c) > 0]
 
 
-def record_item(move, value, entry=None, fast=False, record_q=False, labels=None):
+def record_item(move, value, entry=None, fast=False, record_q=False, labels=None, record_surprise=False):
     """One ply's record item (engine.py drain).  entry: the ply's VisitEntry, or None where the ply has none to show (the
     appended king capture, a resignation, a game whose visit record is incomplete).
       [move, value]                          no entry, a full ply
@@ -34,16 +35,21 @@ def record_item(move, value, entry=None, fast=False, record_q=False, labels=None
       [move, value, pi or None, 0]           a fast ply of the playout cap: training weight 0
       [move, value, pi or None, weight, q]   record_q on and an entry: weight 1 on a full ply, 0 on a fast one;
                                              q = round(entry.q, 6), None where the root had no value
-    Without an entry record_q changes nothing, and with record_q off the items are what they were."""
+      [move, value, pi or None, weight, q or None, s]
+                                             record_surprise on and an entry: weight as above, q None with record_q off,
+                                             s = round(entry.s, 6), None where the root had no surprise
+    Without an entry neither option changes anything, and with both off the items are what they were."""
     item = [move, value]
     if entry is not None:
         item.append(pi_from_visits(entry.moves, entry.n, entry.banned, labels))
     if fast:
         item += [None] * (3 - len(item)) + [0]
-    if record_q and entry is not None:
+    if (record_q or record_surprise) and entry is not None:
         if not fast:
             item.append(1)
-        item.append(None if entry.q is None else round(float(entry.q), 6))
+        item.append(None if not record_q or entry.q is None else round(float(entry.q), 6))
+        if record_surprise:
+            item.append(None if entry.s is None else round(float(entry.s), 6))
     return item
 
 
@@ -51,6 +57,14 @@ def mean_abs_q_minus_z(data):
     """(sum of |q - z|, count) over the items of one game's record list that carry a q (self-play's log line)."""
     d = [abs(it[4] - it[1]) for it in data[1:] if len(it) >= 5 and it[4] is not None]
     return sum(d), len(d)
+
+
+def surprise_sums(data):
+    """(sum of s over full plies, their count, sum over fast plies, their count) over the items of one game's record list
+    that carry a policy surprise (self-play's log line); a fast ply is one with training weight 0."""
+    full = [it[5] for it in data[1:] if len(it) >= 6 and it[5] is not None and it[3] != 0]
+    fast = [it[5] for it in data[1:] if len(it) >= 6 and it[5] is not None and it[3] == 0]
+    return sum(full), len(full), sum(fast), len(fast)
 
 
 def get_game_data_filenames(rc):

@@ -2,8 +2,8 @@
 
 The reference keeps its window as dense float32 arrays, 14 x 90 planes plus 2086 policy values per position
 (worker/optimize.py:261-281, about 13.4 KB a position).  Here a position costs its 90-byte board, the index of the
-position two plies back, the played label, the value, the root's search value q (float32, NaN where the record has
-none) and its visit counts in CSR form (about 104 B plus 6 B per visited edge); the minibatch's planes are built when it is drawn (``cz_gather_planes``) and the loss reads the sparse targets
+position two plies back, the played label, the value, the root's search value q and the ply's policy surprise s
+(float32 each, NaN where the record has none) and its visit counts in CSR form (about 104 B plus 6 B per visited edge); the minibatch's planes are built when it is drawn (``cz_gather_planes``) and the loss reads the sparse targets
 directly (``cz_policy_value_loss``), so neither planes nor dense targets exist for the whole window.
 
 Record files are replayed on the device, one wavefront per game (``cz_replay_games``): the boards are those of
@@ -31,6 +31,31 @@ INT32_MAX = 2 ** 31 - 1         # positions and visit entries are indexed with i
 Q_BOUND = 2.0                   # |q| of a record item: every value the search backs up is a network value in [-1, 1] or a
                                 # terminal one, done.v * 2 = +-2 (csrc/xq_search.hip backup), so every edge's w / n and their
                                 # weighted mean lie in [-2, 2]
+S_BOUND = 70.0                  # a record item's policy surprise lies in [0, ln 1e30] (include/czero.h CZ_SURPRISE_BOUND)
+
+
+def surprise_weights(s, trainable, game_offsets, alpha):
+    """Per-row training weights from the records' policy surprise (KataGo's policy surprise weighting; run.py opt
+    --surprise-weight A).  s: the rows' surprise, NaN = none; trainable: 0 marks a weight-0 row; game_offsets: [G + 1]
+    row offsets of the games; alpha = A.  Per game, F = the rows with trainable = 1 and a finite s, S = the sum of s over
+    F: with S > 0 a row of F gets (1 - A) + A |F| s / S, so the weights over F sum to |F| -- a game's total is what it
+    was, A of it handed out in proportion to the surprise.  Every other trainable row gets 1, a weight-0 row 0.  Float64
+    arithmetic, float32 result."""
+    s = np.asarray(s, dtype=np.float64)
+    tr = np.asarray(trainable) != 0
+    a = float(alpha)
+    w = tr.astype(np.float64)
+    offs = np.asarray(game_offsets, dtype=np.int64)
+    for lo, hi in zip(offs[:-1], offs[1:]):
+        f = tr[lo:hi] & np.isfinite(s[lo:hi])
+        nf = int(f.sum())
+        if nf == 0:
+            continue
+        sf = s[lo:hi][f]
+        total = float(sf.sum())
+        if total > 0:
+            w[lo:hi][f] = (1.0 - a) + a * nf * sf / total
+    return w.astype(np.float32)
 
 
 def mix_targets(z, q, q_ratio):
@@ -51,9 +76,15 @@ class ReplayWindow:
     true once it is reached, and the file that reaches it is kept whole (the reference's fill_queue checks the size before
     each file).  depth 28 = ``has_history`` networks (state_history_to_planes)."""
 
-    def __init__(self, capacity, depth=14, device="cuda"):
+    def __init__(self, capacity, depth=14, device="cuda", surprise_weight=0.0):
+        """surprise_weight A > 0: the window also holds ``w``, every position's training weight from the records' policy
+        surprise (surprise_weights), on the device for ``loss(..., surprise=True)``; at 0 no such array exists."""
         if depth not in (14, 28):
             raise ValueError(f"depth={depth}: expected 14 or 28")
+        if isinstance(surprise_weight, bool) or not 0.0 <= float(surprise_weight) <= 1.0:
+            raise ValueError(f"surprise_weight={surprise_weight!r}: expected 0 <= A <= 1")
+        self.surprise_weight = float(surprise_weight)
+        self.w = None
         _native.require_gpu()
         self.capacity, self.depth = int(capacity), depth
         self.device = torch.device(device)
@@ -71,6 +102,9 @@ class ReplayWindow:
         self.played = torch.empty((n,), dtype=torch.uint16, device=d)
         self.z = torch.empty((n,), dtype=torch.float32, device=d)
         self.q = torch.empty((n,), dtype=torch.float32, device=d)
+        self.s = torch.empty((n,), dtype=torch.float32, device=d)
+        if self.surprise_weight:
+            self.w = torch.empty((n,), dtype=torch.float32, device=d)
         self.row_ptr = torch.zeros((n + 1,), dtype=torch.int32, device=d)
         self.vis_label = torch.empty((nnz,), dtype=torch.uint16, device=d)
         self.vis_count = torch.empty((nnz,), dtype=torch.int32, device=d)
@@ -80,7 +114,7 @@ class ReplayWindow:
         (the file that crosses the capacity gets exactly the room it needs), visit entries double up to INT32_MAX."""
         if n > self.boards.shape[0]:
             cap = min(self.capacity, max(n, 1 << 16, 2 * self.boards.shape[0])) if n <= self.capacity else n
-            for name in ("boards", "prev", "played", "z", "q"):
+            for name in ("boards", "prev", "played", "z", "q", "s") + (("w",) if self.w is not None else ()):
                 old = getattr(self, name)
                 new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
                 new[:self.n] = old[:self.n]
@@ -129,7 +163,10 @@ class ReplayWindow:
         game and the ply) for a move that is not a label or whose from-square is empty, for a weight other than 0 or 1,
         and for items that are not of these forms; the window is unchanged then.  A fifth element is the root's search
         value q of the ply (engine.py drain with record_q): None or a finite number in [-Q_BOUND, Q_BOUND], anything else
-        raises the same ValueError; ``q`` holds NaN for None, for shorter items and so for every older record.  The window holds at most INT32_MAX
+        raises the same ValueError; ``q`` holds NaN for None, for shorter items and so for every older record.  A sixth element
+        is the ply's policy surprise s (engine.py drain with record_surprise): None or a finite number in [0, S_BOUND],
+        anything else raises the same ValueError; ``s`` holds NaN for None and for shorter items, and with surprise_weight
+        > 0 ``w`` gets the new games' weights (surprise_weights).  The window holds at most INT32_MAX
         positions and INT32_MAX visit entries (int32 indices: about 24 visited edges per position at `distribute`'s 90 M
         positions); a load beyond either raises ValueError."""
         where = f" in {source}" if source else ""
@@ -146,6 +183,7 @@ class ReplayWindow:
         nvis = np.zeros(P, dtype=np.int64)
         train = np.ones(P, dtype=np.uint8)
         qs = np.full(P, np.nan, dtype=np.float32)
+        ss = np.full(P, np.nan, dtype=np.float32)
         vl, vc = [], []
         k = 0
         lookup = _LABEL
@@ -170,6 +208,12 @@ class ReplayWindow:
                             raise ValueError(f"Search value {q!r}: expected None or a finite number in "
                                              f"[-{Q_BOUND:g}, {Q_BOUND:g}] (game {gi}, ply {t}){where}")
                         qs[k] = q
+                    if len(item) >= 6 and item[5] is not None:
+                        sp = item[5]
+                        if isinstance(sp, bool) or not isinstance(sp, (int, float)) or not 0.0 <= sp <= S_BOUND:
+                            raise ValueError(f"Policy surprise {sp!r}: expected None or a finite number in "
+                                             f"[0, {S_BOUND:g}] (game {gi}, ply {t}){where}")
+                        ss[k] = sp
                     if len(item) >= 3 and not (len(item) >= 4 and item[2] is None):
                         pi = item[2]
                         for mv, c in pi:
@@ -206,6 +250,9 @@ class ReplayWindow:
         self.played[n0:n0 + P] = torch.from_numpy(labels).to(dev)
         self.z[n0:n0 + P] = torch.from_numpy(vals).to(dev)
         self.q[n0:n0 + P] = torch.from_numpy(qs).to(dev)
+        self.s[n0:n0 + P] = torch.from_numpy(ss).to(dev)
+        if self.w is not None:                  # a game's weights depend on that game's rows alone
+            self.w[n0:n0 + P] = torch.from_numpy(surprise_weights(ss, train, offsets, self.surprise_weight)).to(dev)
         rp = (z0 + np.cumsum(nvis)).astype(np.int32)
         self.row_ptr[n0 + 1:n0 + P + 1] = torch.from_numpy(rp).to(dev)
         if nnz:
@@ -225,13 +272,17 @@ class ReplayWindow:
         device, or None: a row with a nonzero flag is the left-right mirrored position (cz_gather_planes_m)."""
         return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth, mirror=mirror)
 
-    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0):
+    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0, surprise=False):
         """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
         differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss).  mirror: the flags given to
         ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m).  q_ratio L > 0: the value
-        target is z + L (q - z) where the position has a q (cz_policy_value_loss_q), and the value loss is against it."""
+        target is z + L (q - z) where the position has a q (cz_policy_value_loss_q), and the value loss is against it.
+        surprise=True (a window with surprise_weight > 0): row r counts with the weight w[idx[r]] in the gradients
+        (cz_policy_value_loss_w) and in the returned means, mean(w[idx] * loss) -- still divided by B."""
+        if surprise and self.w is None:
+            raise ValueError("loss(surprise=True) needs a window built with surprise_weight > 0")
         return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
-                                      float(q_ratio))
+                                      float(q_ratio), bool(surprise))
 
     def value_targets(self, idx, q_ratio=0.0):
         """Host float32 [B] value targets of the positions idx as the loss kernel forms them (tests, tools): mix_targets."""
@@ -266,8 +317,18 @@ class _PolicyValueLoss(torch.autograd.Function):
     """w_p * mean(policy loss) + w_v * mean(value loss) of a minibatch; backward hands out the kernel's gradients."""
 
     @staticmethod
-    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None, q_ratio=0.0):
+    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None, q_ratio=0.0, surprise=False):
         n = win.n
+        if surprise:
+            pl, se, gl, gv = _native.policy_value_loss(
+                logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
+                win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
+                q=win.q[:n] if q_ratio else None, q_ratio=q_ratio, row_w=win.w[:n])
+            ctx.save_for_backward(gl, gv)
+            wr = win.w[:n][idx.long()]
+            pm, vm = (wr * pl).mean(), (wr * se).mean()     # the loss whose gradients the kernel returned
+            ctx.mark_non_differentiable(pm, vm)
+            return w_p * pm + w_v * vm, pm, vm
         pl, se, gl, gv = _native.policy_value_loss(
             logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
             win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
@@ -280,4 +341,4 @@ class _PolicyValueLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_pm, _g_vm):
         gl, gv = ctx.saved_tensors
-        return g_total * gl, g_total * gv, None, None, None, None, None, None, None
+        return g_total * gl, g_total * gv, None, None, None, None, None, None, None, None

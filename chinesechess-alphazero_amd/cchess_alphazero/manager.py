@@ -56,6 +56,14 @@ _FLAGS = [
     ("--q-ratio", dict(type=float, default=0.0, metavar="L",
                        help="(opt) value target z + L (q - z): the game result mixed with the records' root search values "
                             "where they have one (0 <= L <= 1; 0 = the game result alone, the reference)")),
+    ("--record-surprise", dict(action="store_true",
+                               help="(self, with --record-visits) play records carry each recorded ply's policy surprise, "
+                                    "KL(visit counts || network prior): [move, value, pi, weight, q, s], for run.py opt "
+                                    "--surprise-weight")),
+    ("--surprise-weight", dict(type=float, default=0.0, metavar="A",
+                               help="(opt) policy surprise weighting: within a game, the share A of the training weight goes "
+                                    "to the rows in proportion to their recorded surprise (0 <= A <= 1; 0 = uniform, the "
+                                    "reference; KataGo uses 0.5)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -114,6 +122,13 @@ def build_config(args):
     if not 0.0 <= args.q_ratio <= 1.0:
         raise SystemExit(f"--q-ratio {args.q_ratio}: expected 0 <= L <= 1")
     config.trainer.q_ratio = args.q_ratio
+    if args.record_surprise and not engine.record_visits:
+        raise SystemExit("--record-surprise needs --record-visits: the surprises ride beside the visit entries")
+    if args.record_surprise:
+        engine.record_surprise = True
+    if not 0.0 <= args.surprise_weight <= 1.0:
+        raise SystemExit(f"--surprise-weight {args.surprise_weight}: expected 0 <= A <= 1")
+    config.trainer.surprise_weight = args.surprise_weight
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -28,6 +28,13 @@ Deliberate deviations from the reference:
     target is formed in ``cz_policy_value_loss_q``; with L > 0 the logged value losses are against the mixed target and
     every epoch also reports ``val_value_z``, the validation value loss against z alone, so that runs with different L
     stay comparable (with L = 0 that is ``val``'s own value loss and nothing is added);
+  - ``--surprise-weight A`` (default 0: every trainable row counts alike, the reference) weights the training rows by the
+    records' policy surprise s (``run.py self --record-surprise``), KataGo's policy surprise weighting: within a game a
+    row with an s gets (1 - A) + A |F| s / S (lib/replay_window.py ``surprise_weights``), so a game's total weight is
+    unchanged and rows without an s keep 1.  The weight scales the row's gradients in ``cz_policy_value_loss_w`` and the
+    logged training losses are the weighted means, still divided by the batch size; KataGo replicates rows in proportion
+    to their weight instead, which this matches in expectation.  Validation is never weighted, so ``val`` stays
+    comparable between runs with different A.  Fast plies keep the weight 0 (KataGo gives them a surprise-based one);
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -122,6 +129,9 @@ class OptimizeWorker:
         self.q_ratio = float(getattr(config.trainer, "q_ratio", 0.0))
         if not 0.0 <= self.q_ratio <= 1.0:
             raise ValueError(f"trainer.q_ratio={self.q_ratio!r}: expected 0 <= L <= 1")
+        self.surprise_weight = float(getattr(config.trainer, "surprise_weight", 0.0))
+        if not 0.0 <= self.surprise_weight <= 1.0:
+            raise ValueError(f"trainer.surprise_weight={self.surprise_weight!r}: expected 0 <= A <= 1")
         self.rng = np.random.default_rng(config.engine.base_seed)
         # the mirror flags have their own stream: self.rng draws what it draws without the option
         self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
@@ -169,7 +179,9 @@ class OptimizeWorker:
     # ---- the loop ----------------------------------------------------------------------------------------------------
     def new_window(self):
         from cchess_alphazero.lib.replay_window import ReplayWindow
-        return ReplayWindow(self.config.trainer.dataset_size, depth=self.depth)
+        # (nothing is passed at 0: the window is built as it was without the option)
+        extra = dict(surprise_weight=self.surprise_weight) if self.surprise_weight else {}
+        return ReplayWindow(self.config.trainer.dataset_size, depth=self.depth, **extra)
 
     def training(self):
         """The reference's loop (:55-104): take the next files, fill the window, train epoch_to_checkpoint epochs when it
@@ -239,6 +251,12 @@ class OptimizeWorker:
             logger.info(f"window: {skipped} of {n} positions carry the training weight 0 (fast plies) and are skipped: "
                         f"{len(tr)} training and {len(va)} validation rows")
         self.skipped_rows = skipped
+        if self.surprise_weight:
+            wt = win.w[:n].cpu().numpy()[tr]
+            with_s = int(np.isfinite(win.s[:n].cpu().numpy()[tr]).sum())
+            logger.info(f"window: training rows weighted by policy surprise, A = {self.surprise_weight:g}: {with_s} of "
+                        f"{len(tr)} carry an s; weights min {wt.min() if len(wt) else 1.0:.4f} mean "
+                        f"{wt.mean() if len(wt) else 1.0:.4f} max {wt.max() if len(wt) else 1.0:.4f}")
         dev = win.device
         va_d = torch.from_numpy(va.astype(np.int32)).to(dev)
         bs = tc.batch_size
@@ -288,7 +306,7 @@ class OptimizeWorker:
         tc = self.config.trainer
         logits, v = self.model.model(self.window.planes(idx, mirror=mirror), logits=True)
         total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
-                                         **self._q_args(self.q_ratio))
+                                         **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -299,6 +317,11 @@ class OptimizeWorker:
     def _q_args(q_ratio):
         # (nothing is passed at 0: the loop asks no more of a window's loss() than it did without the option)
         return dict(q_ratio=q_ratio) if q_ratio else {}
+
+    @staticmethod
+    def _s_args(surprise_weight):
+        # (likewise; only training steps are weighted, evaluate() never passes it)
+        return dict(surprise=True) if surprise_weight else {}
 
     def evaluate(self, idx_all, mirror=False, q_ratio=None):
         """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the

@@ -13,7 +13,7 @@ from logging import getLogger
 
 import numpy as np
 
-from cchess_alphazero.lib.data_helper import PlayDataWriter, mean_abs_q_minus_z
+from cchess_alphazero.lib.data_helper import PlayDataWriter, mean_abs_q_minus_z, surprise_sums
 
 logger = getLogger(__name__)
 
@@ -96,6 +96,9 @@ class SelfPlayWorker:
         if self.engine.record_q:
             logger.info(f"Process {self.pid}-{self.rank}: the records carry each searched ply's root search value q "
                         f"(items [move, value, pi, weight, q])")
+        if getattr(self.engine, "record_surprise", False):
+            logger.info(f"Process {self.pid}-{self.rank}: the records carry each recorded ply's policy surprise s "
+                        f"(items [move, value, pi, weight, q, s])")
         if self.engine.forced_playouts:
             logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
                         f"the recorded visit counts are pruned (policy target pruning)")
@@ -107,6 +110,8 @@ class SelfPlayWorker:
     def _harvest(self):
         full = fast = pruned = raw = 0
         dq_sum, dq_n = 0.0, 0
+        record_s = getattr(self.engine, "record_surprise", False)
+        sp = [0.0, 0, 0.0, 0]
         for g in self.engine.drain():
             pruned += g.get("pruned_visits", 0)
             raw += sum(e.raw_total for e in g.get("visits") or [] if e.pruned)
@@ -119,6 +124,8 @@ class SelfPlayWorker:
                 if self.engine.record_q:
                     d, k = mean_abs_q_minus_z(g["data"])
                     dq_sum, dq_n = dq_sum + d, dq_n + k
+                if record_s:
+                    sp = [a + b for a, b in zip(sp, surprise_sums(g["data"]))]
                 path = self.writer.add_game(g["data"])
                 self.stored_games += 1
                 if path:
@@ -128,6 +135,9 @@ class SelfPlayWorker:
         if self.engine.record_q and dq_n:
             logger.info(f"Process {self.pid}-{self.rank}: search values of {dq_n} plies written, mean |q - z| = "
                         f"{dq_sum / dq_n:.4f}")
+        if record_s and sp[1] + sp[3]:
+            logger.info(f"Process {self.pid}-{self.rank}: policy surprise of {sp[1]} full plies written, mean s = "
+                        f"{sp[0] / max(sp[1], 1):.4f}; of {sp[3]} fast plies, mean s = {sp[2] / max(sp[3], 1):.4f}")
         if self.engine.forced_playouts and raw:
             logger.info(f"Process {self.pid}-{self.rank}: policy target pruning removed {pruned} of {raw} root visits "
                         f"({100.0 * pruned / raw:.1f} %)")

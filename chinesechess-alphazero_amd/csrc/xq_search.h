@@ -187,6 +187,7 @@ struct VisitEntryHdr {                             // followed by uint16 label[1
     uint32_t raw_total; // VISIT_PRUNED: sum of the raw counts of the non-banned edges; otherwise 0
 };
 constexpr int VISIT_STRIDE = (int)sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES + 4 * VISIT_MAX_EDGES;   // 784 B
+constexpr double SURPRISE_R_FLOOR = 1e-30;          // floor of the normalised prior in root_surprise (czero.h): s <= ln 1e30 < 70
 
 struct VisitRing {
     uint8_t* ring;                  // [cap][VISIT_STRIDE]; NULL = recording off
@@ -197,6 +198,8 @@ struct VisitRing {
     // value record (cz_search_record_values): the root's search value of the entry in the same slot, a ring of its own
     // because the 784-byte entry has no free word; written by emit_visits in the entry's reservation
     double* q;                      // [cap]; NULL = off
+    // surprise record (cz_search_record_surprise): KL(recorded counts || noise-free priors) of the same entry, likewise
+    double* s;                      // [cap]; NULL = off
 };
 
 }  // namespace xq

@@ -1354,6 +1354,39 @@ XQ_D double root_value(int nm, const uint16_t lab[2], const int m[2], const int 
     return den > 0.0 ? num / den : __builtin_nan("");
 }
 
+// Policy surprise (include/czero.h, cz_search_record_surprise): one wavefront, edge j = lane + 64 h.  lab[h] carries
+// VISIT_BANNED, m is the count the visit entry records (pruned or raw), p the float32 prior WITHOUT noise.  Float64
+// throughout, every operation rounded once: s = sum t_j log(t_j / r_j) over the non-banned edges with m_j > 0, t_j =
+// m_j / M, r_j = max(p_j / P, 1e-30), clamped at 0 from below; NaN when M = 0 or P is not positive.  Each sum takes the
+// lane's two terms first, then the DPP ladder of wave_add_f64: a fixed order, no LDS permute.  All 64 lanes call it.
+XQ_D double root_surprise(int nm, const uint16_t lab[2], const int m[2], const float p[2])
+{
+    const int lane = lane_id();
+    double M = 0.0, Ps = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED);
+        if (!live) continue;
+        M = __dadd_rn(M, (double)m[h]);             // integers below 2^53: exact in any order
+        Ps = __dadd_rn(Ps, (double)p[h]);
+    }
+    M = wave_add_f64(M);
+    Ps = wave_add_f64(Ps);
+    if (!(M > 0.0) || !(Ps > 0.0)) return __builtin_nan("");   // wave-uniform: both are wave sums
+    double s = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED) && m[h] > 0;
+        if (!live) continue;
+        const double t = (double)m[h] / M;
+        double r = (double)p[h] / Ps;
+        r = r > SURPRISE_R_FLOOR ? r : SURPRISE_R_FLOOR;    // (a NaN prior takes the floor as well)
+        s = __dadd_rn(s, __dmul_rn(t, log(t / r)));
+    }
+    s = wave_add_f64(s);
+    return s > 0.0 ? s : 0.0;
+}
+
 // Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
@@ -1437,6 +1470,23 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         }
         const double q = root_value(nm, ql, qm, qn, qw);
         if (lane == 0) V.q[pos % V.cap] = q;
+    }
+    if (V.s) {
+        // the surprise record (cz_search_record_surprise): likewise, from the labels and counts this lane has just
+        // written and the root's priors without noise
+        uint16_t sl[2] = {0, 0};
+        int sm[2] = {0, 0};
+        float sp[2] = {0.0f, 0.0f};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            sl[h] = lab[j];
+            sm[h] = cnt[j];
+            sp[h] = node_p(base)[j];
+        }
+        const double sv = root_surprise(nm, sl, sm, sp);
+        if (lane == 0) V.s[pos % V.cap] = sv;
     }
     if (lane == 0) {
         VisitEntryHdr* h = reinterpret_cast<VisitEntryHdr*>(e);
@@ -2116,6 +2166,69 @@ __global__ __launch_bounds__(64) void k_root_value_rows(const uint16_t* __restri
     if (lane == 0) out_q[r] = v;
 }
 
+// Policy surprise of every current root (cz_search_root_surprise): what the surprise record would hold for it -- the
+// counts of k_root_targets as m, the priors without noise as p
+__global__ __launch_bounds__(64) void k_root_surprise(SearchParams P, SearchBuffers B, double* __restrict__ out)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    const int root = B.g_root[g];
+    const int n_no_act = B.g_n_no_act[g];
+    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
+    int nm = 0;
+    uint16_t el[2] = {0, 0};
+    int em[2] = {0, 0};
+    double ew[2] = {0.0, 0.0};
+    float ep[2] = {0.0f, 0.0f};
+    if (root >= 0) {
+        char* base = rec_ptr(gv, (uint32_t)root);
+        const NodeHdr hdr = load_hdr(base);
+        nm = (int)(hdr.meta & 0xFF);
+        if (nm > MAXMOVES) nm = MAXMOVES;
+        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
+        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            const uint16_t mv = pm[j];
+            bool banned = false;
+            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+            if (sb) { const EdgeStat es = sb[j]; em[h] = es.n; ew[h] = es.w; }
+            ep[h] = node_p(base)[j];
+        }
+    }
+    prune_targets(nm, el, em, ew, ep, P.c_puct, P.forced_k);
+    const double v = root_surprise(nm, el, em, ep);
+    if (lane == 0) out[g] = v;
+}
+
+// cz_root_surprise: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
+__global__ __launch_bounds__(64) void k_root_surprise_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m,
+                                                          const float* __restrict__ p, const uint8_t* __restrict__ n_edges,
+                                                          int rows, double* __restrict__ out)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    int nm = n_edges[r];
+    if (nm > MAXMOVES) nm = MAXMOVES;
+    uint16_t el[2] = {0, 0};
+    int em[2] = {0, 0};
+    float ep[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
+        if (lane + 64 * h < nm) { el[h] = labels[i]; em[h] = m[i]; ep[h] = p[i]; }
+    }
+    const double v = root_surprise(nm, el, em, ep);
+    if (lane == 0) out[r] = v;
+}
+
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
 // the LAST maximum, banned moves are skipped at the root only -- until a node that was never selected from (the
 // reference creates a node's edges at its first selection: an empty `a` ends the line), a terminal / unlinked child or
@@ -2215,6 +2328,7 @@ struct cz_search {
     VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
     void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
     void* q_mem = nullptr;            // the value ring V.q (cz_search_record_values), allocated only while that is on
+    void* s_mem = nullptr;            // the surprise ring V.s (cz_search_record_surprise), likewise
     void* book_mem = nullptr;         // the start-position book (cz_search_set_book): P.book points here
 };
 
@@ -2431,6 +2545,7 @@ int cz_search_destroy(cz_search* s)
     if (!s) return CZ_OK;
     (void)hipFree(s->vis_mem);
     (void)hipFree(s->q_mem);
+    (void)hipFree(s->s_mem);
     (void)hipFree(s->book_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
@@ -2613,8 +2728,10 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
     if (e != hipSuccess) return serr_hip("cz_search_record_visits", e);
     (void)hipFree(s->vis_mem);
     (void)hipFree(s->q_mem);                             // the value ring shares the visit ring's slots: it goes with it
+    (void)hipFree(s->s_mem);                             // and so does the surprise ring
     s->vis_mem = nullptr;
     s->q_mem = nullptr;
+    s->s_mem = nullptr;
     s->V = VisitRing{};
     if (!on) return CZ_OK;
     // default: 64 entries per game -- one k_advance launch records at most 8 plies of a game (the loop in k_advance),
@@ -2770,13 +2887,62 @@ int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, co
     return CZ_OK;
 }
 
-// cz_search_drain_visits and cz_search_drain_visits_q: q_buf NULL = the entries alone
-static int drain_visits(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out, uint64_t* dropped_out,
-                        void* stream)
+static_assert(CZ_SURPRISE_BOUND == 70 && SURPRISE_R_FLOOR == 1e-30, "czero.h: ln(1 / the floor) = 69.08 < the bound");
+
+int cz_search_record_surprise(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_surprise: null handle");
+    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_surprise: needs cz_search_record_visits on");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
+    if (e != hipSuccess) return serr_hip("cz_search_record_surprise", e);
+    if (!on) {
+        (void)hipFree(s->s_mem);
+        s->s_mem = nullptr;
+        s->V.s = nullptr;
+        return CZ_OK;
+    }
+    if (s->V.s) return CZ_OK;                            // already on: the ring and what waits in it stay
+    void* mem = nullptr;
+    const size_t bytes = (size_t)s->V.cap * sizeof(double);
+    e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return serr_hip("cz_search_record_surprise: hipMalloc", e);
+    // entries already waiting in the visit ring were written without a surprise: NaN, "no surprise"
+    e = hipMemsetAsync(mem, 0xFF, bytes, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip("cz_search_record_surprise", e); }
+    s->s_mem = mem;
+    s->V.s = (double*)mem;
+    return CZ_OK;
+}
+
+int cz_search_root_surprise(cz_search* s, double* out, void* stream)
+{
+    if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_surprise: null argument");
+    hipLaunchKernelGGL(k_root_surprise, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, out);
+    S_LAUNCH_CHECK("cz_search_root_surprise");
+    return CZ_OK;
+}
+
+int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, const uint8_t* n_edges, int rows,
+                     double* out, void* stream)
+{
+    if (!labels || !m || !p || !n_edges || !out || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_root_surprise: null argument or rows < 0");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_root_surprise_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, p, n_edges, rows, out);
+    S_LAUNCH_CHECK("cz_root_surprise");
+    return CZ_OK;
+}
+
+// cz_search_drain_visits, _q and _qs: q_buf / s_buf NULL = that ring is not copied
+static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
+                        uint64_t* dropped_out, void* stream)
 {
     if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits: bad argument");
     if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits: visit recording is off");
     if (q_buf && !s->V.q) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: value recording is off");
+    if (s_buf && !s->V.s) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qs: surprise recording is off");
     hipStream_t st = (hipStream_t)stream;
     unsigned int ctl[6] = {0u, 0u, 0u, 0u, 0u, 0u};        // tail, head, -, -, dropped (64 bit): one copy
     static_assert(sizeof(unsigned long long) == 8, "dropped counter is 64-bit");
@@ -2802,6 +2968,8 @@ static int drain_visits(cz_search* s, void* host_buf, double* q_buf, int max_ent
                            (size_t)run * VISIT_STRIDE, hipMemcpyDeviceToHost, st);
         if (q_buf && e == hipSuccess)
             e = hipMemcpyAsync(q_buf + done, s->V.q + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (s_buf && e == hipSuccess)
+            e = hipMemcpyAsync(s_buf + done, s->V.s + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
         done += run;
     }
     const unsigned int new_head = tail;
@@ -2814,14 +2982,21 @@ static int drain_visits(cz_search* s, void* host_buf, double* q_buf, int max_ent
 
 int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out, void* stream)
 {
-    return drain_visits(s, host_buf, nullptr, max_entries, n_out, dropped_out, stream);
+    return drain_visits(s, host_buf, nullptr, nullptr, max_entries, n_out, dropped_out, stream);
 }
 
 int cz_search_drain_visits_q(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out,
                              uint64_t* dropped_out, void* stream)
 {
     if (host_buf && !q_buf) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: null q_buf");
-    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, max_entries, n_out, dropped_out, stream);
+    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, nullptr, max_entries, n_out, dropped_out, stream);
+}
+
+int cz_search_drain_visits_qs(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
+                              uint64_t* dropped_out, void* stream)
+{
+    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, host_buf ? s_buf : nullptr, max_entries, n_out,
+                        dropped_out, stream);
 }
 
 int cz_search_reset_trees(cz_search* s, void* stream)

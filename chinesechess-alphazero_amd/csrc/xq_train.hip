@@ -167,7 +167,7 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
     const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx,
     const uint8_t* __restrict__ mirror, int n_rows, int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
     const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z,
-    const float* __restrict__ q, float q_ratio, int mode,
+    const float* __restrict__ q, float q_ratio, const float* __restrict__ row_w, int mode,
     float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
     float* __restrict__ grad_logits, float* __restrict__ grad_v)
 {
@@ -191,6 +191,9 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
 #pragma unroll
         for (int k = 0; k < LOSS_COLS; ++k) tgt[lane + 64 * k] = 0.f;
         wave_sync();
+        // row weight (cz_policy_value_loss_w): scales the row's gradients only; 1.0f leaves every bit where it was
+        const float wi = row_w != nullptr ? row_w[i] : 1.f;
+        const float cr = row_w != nullptr ? __fmul_rn(c, wi) : c;
         double total = 0.0;
         int lo = 0, hi = 0;
         if (mode == 1 && nnz > 0) {
@@ -253,7 +256,7 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
             if (j < NLABELS) {
                 const float p = e[k];
                 const float tm = (p > CCE_EPS && p < CCE_HI) ? tgt[j] : 0.f;
-                g[j] = c * (p * S - tm);
+                g[j] = cr * (p * S - tm);
             }
         }
         if (lane == 0) {
@@ -265,7 +268,8 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
             const float d = v[r] - t;
             policy_loss[r] = loss;
             value_sqerr[r] = d * d;
-            grad_v[r] = w_v * (2.f * d) * inv_b;
+            const float gv = w_v * (2.f * d) * inv_b;
+            grad_v[r] = row_w != nullptr ? __fmul_rn(gv, wi) : gv;
         }
         wave_sync();
     }
@@ -307,10 +311,10 @@ int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const
     return cz_gather_planes_m(boards, prev, n_pos, idx, nullptr, n_rows, depth, planes, stream);
 }
 
-int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
                            int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
-                           const uint16_t* played, const float* z, const float* q, float q_ratio, int mode, float w_p,
-                           float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
                            void* stream)
 {
     if (!(q_ratio >= 0.f && q_ratio <= 1.f)) {
@@ -326,9 +330,20 @@ int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const in
         return CZ_ERR_ARG;
     }
     hipLaunchKernelGGL(k_policy_value_loss, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
-                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, mode, w_p, w_v,
-                       policy_loss, value_sqerr, grad_logits, grad_v);
+                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, row_w, mode, w_p,
+                       w_v, policy_loss, value_sqerr, grad_logits, grad_v);
     return launch_status("cz_policy_value_loss: launch failed");
+}
+
+int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, int mode, float w_p,
+                           float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           void* stream)
+{
+    return cz_policy_value_loss_w(logits, ld, v, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z,
+                                  q, q_ratio, nullptr, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v,
+                                  stream);
 }
 
 int cz_policy_value_loss_m(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,

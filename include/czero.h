@@ -403,6 +403,50 @@ int cz_search_root_value(cz_search* s, double* q, void* stream);
  * [rows], all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
 int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, const double* w, const uint8_t* n_edges,
                   int rows, double* out_q, void* stream);
+/* ---- policy surprise record of self-play (off by default; the reference has no such option) ----
+ * How far the search moved away from the network's prior at each recorded ply, so that a trainer can give the plies the
+ * policy head learns most from more weight (KataGo's policy surprise weighting, Wu 2019).  on = 0 (the state after
+ * cz_search_create): no kernel output, ring byte, record, counter or entry differs by a bit from what it was before
+ * this existed.
+ *
+ * THE ARITHMETIC.  Given a root's edges as a visit entry sees them -- labels with the banned bit (0x8000), m_j, the
+ * count the visit entry records for the edge (the PRUNED count when the entry is CZ_VISIT_PRUNED, the raw count
+ * otherwise) and p_j, the float32 prior WITHOUT root noise -- all arithmetic in float64, every operation rounded once,
+ * no fused multiply-add; the live edges are the non-banned j < n_edges:
+ *       M = sum m_j (integers: exact)        P = sum (double) p_j                 over the live edges
+ *       t_j = m_j / M                        r_j = max(p_j / P, 1e-30)
+ *       s = sum t_j * log(t_j / r_j)         over the live edges with m_j > 0
+ *       surprise = max(s, 0)
+ * the Kullback-Leibler divergence of the recorded policy target from the normalised prior.  M = 0 or not P > 0 -- no
+ * edge, every edge banned, a root that was never selected from -- gives NaN: "no surprise".  Each sum is taken in a
+ * fixed order (edge j and j + 64 in lane j, then one ladder over the 64 lanes), so equal inputs give equal bits.
+ * t_j <= 1 and r_j >= 1e-30 bound every logarithm by ln 1e30, and sum t_j = 1, so 0 <= surprise <= ln 1e30 = 69.08 <
+ * CZ_SURPRISE_BOUND.  log is the device library's float64 logarithm (DESIGN.md names the routine and its accuracy).
+ *
+ * THE RING.  Like the value record: double s[capacity], indexed by the slot of the visit entry, written by the kernel
+ * in the entry's reservation for every ply that gets an entry (fast plies of the playout cap included); a dropped
+ * entry drops its surprise.  Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting);
+ * every call of cz_search_record_visits frees this ring as well, so switch it on after that.  Call it before
+ * cz_search_start_selfplay and before a graph capture; synchronises the stream.  Entries already waiting when it is
+ * switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.  No counter is added; the move,
+ * the tree, the visit entries and the value ring do not change. */
+#define CZ_SURPRISE_BOUND 70
+int cz_search_record_surprise(cz_search* s, int on, void* stream);
+/* cz_search_drain_visits that also copies the entries' values into HOST q_buf[max_entries] and their surprises into
+ * HOST s_buf[max_entries], beside entry i.  q_buf / s_buf = NULL: that ring is not copied (it has to be NULL when its
+ * record is off: CZ_ERR_ARG otherwise).  host_buf = NULL counts.  cz_search_drain_visits and cz_search_drain_visits_q
+ * keep working with the surprise record on; they drop the surprises of what they consume. */
+int cz_search_drain_visits_qs(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
+                              uint64_t* dropped_out, void* stream);
+/* The surprise an entry of each current root would carry: out [G] float64 DEVICE.  Same conventions as
+ * cz_search_root_value: the bans of the current cz_search_set_roots, m = the counts cz_search_root_targets reports for
+ * the object's c_puct and k (k = 0: the raw counts).  A root that is not in the tree reports NaN.  Works with the record
+ * off. */
+int cz_search_root_surprise(cz_search* s, double* out, void* stream);
+/* The arithmetic on its own, one wavefront per row: labels / m / p [rows][128] (uint16 / int32 / float32) and n_edges
+ * [rows] (<= 128), out [rows] float64, all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
+int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, const uint8_t* n_edges, int rows,
+                     double* out, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
@@ -729,6 +773,19 @@ int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const in
                            int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
                            const uint16_t* played, const float* z, const float* q, float q_ratio, int mode, float w_p,
                            float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           void* stream);
+/* The same kernel with a training weight per row (run.py opt --surprise-weight A): row_w[n_pos] (DEVICE float32,
+ * indexed by window position like z and q).  The weight scales the row's share of the gradients only: the scale of row
+ * r with i = idx[r] is __fmul_rn(w_p / n_rows, row_w[i]) for grad_logits and grad_v[r] is its unweighted value times
+ * row_w[i], each one rounded product -- a weight of 1.0f gives the unweighted bits.  policy_loss[r] and value_sqerr[r]
+ * stay the row's unweighted values.  The division stays by n_rows, not by the sum of the weights: the weights average 1
+ * over a game, which matches replicating rows in proportion to their weight in expectation.  row_w = NULL takes the
+ * path of cz_policy_value_loss_q, bit for bit; the entries above forward here with NULL.  A weight that is negative or
+ * not finite is the caller's error and is not checked here. */
+int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
                            void* stream);
 
 #ifdef __cplusplus
