@@ -77,42 +77,26 @@ def declare(L):
     L.cz_search_drain_records.argtypes = [vp, C.POINTER(C.c_uint), vp, i32, C.POINTER(C.c_int), vp]
     L.cz_search_record_visits.argtypes = [vp, i32, i32, vp]
     L.cz_search_drain_visits.argtypes = [vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
-    if hasattr(L, "cz_search_set_book"):                # (absent from an older library selected with CZ_LIB for an A/B)
-        L.cz_search_set_book.argtypes = [vp, vp, i32, C.c_double, vp]
-        L.cz_search_set_book.restype = i32
-    if hasattr(L, "cz_search_set_playout_cap"):
-        L.cz_search_set_playout_cap.argtypes = [vp, i32, C.c_double, vp]
-        L.cz_search_set_playout_cap.restype = i32
-    if hasattr(L, "cz_search_set_forced_playouts"):
-        L.cz_search_set_forced_playouts.argtypes = [vp, C.c_double, vp]
-        L.cz_search_set_forced_playouts.restype = i32
-    if hasattr(L, "cz_search_root_targets"):
-        L.cz_search_root_targets.argtypes = [vp, vp, vp, vp]
-        L.cz_search_root_targets.restype = i32
-    if hasattr(L, "cz_policy_target_prune"):
-        L.cz_policy_target_prune.argtypes = [vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, vp, vp, vp]
-        L.cz_policy_target_prune.restype = i32
-    if hasattr(L, "cz_search_record_values"):
-        L.cz_search_record_values.argtypes = [vp, i32, vp]
-        L.cz_search_record_values.restype = i32
-        L.cz_search_drain_visits_q.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
-        L.cz_search_drain_visits_q.restype = i32
-        L.cz_search_root_value.argtypes = [vp, vp, vp]
-        L.cz_search_root_value.restype = i32
-        L.cz_root_value.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
-        L.cz_root_value.restype = i32
-    if hasattr(L, "cz_search_record_surprise"):
-        L.cz_search_record_surprise.argtypes = [vp, i32, vp]
-        L.cz_search_record_surprise.restype = i32
-    if hasattr(L, "cz_search_drain_visits_qs"):
-        L.cz_search_drain_visits_qs.argtypes = [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp]
-        L.cz_search_drain_visits_qs.restype = i32
-    if hasattr(L, "cz_search_root_surprise"):
-        L.cz_search_root_surprise.argtypes = [vp, vp, vp]
-        L.cz_search_root_surprise.restype = i32
-    if hasattr(L, "cz_root_surprise"):
-        L.cz_root_surprise.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-        L.cz_root_surprise.restype = i32
+    d = C.c_double
+    optional = {                                        # (absent from an older library selected with CZ_LIB for an A/B)
+        "cz_search_set_book": [vp, vp, i32, d, vp],
+        "cz_search_set_playout_cap": [vp, i32, d, vp],
+        "cz_search_set_forced_playouts": [vp, d, vp],
+        "cz_search_root_targets": [vp, vp, vp, vp],
+        "cz_policy_target_prune": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
+        "cz_search_record_values": [vp, i32, vp],
+        "cz_search_drain_visits_q": [vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
+        "cz_search_root_value": [vp, vp, vp],
+        "cz_root_value": [vp, vp, vp, vp, vp, i32, vp, vp],
+        "cz_search_record_surprise": [vp, i32, vp],
+        "cz_search_drain_visits_qs": [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
+        "cz_search_root_surprise": [vp, vp, vp],
+        "cz_root_surprise": [vp, vp, vp, vp, i32, vp, vp],
+    }
+    for name, argtypes in optional.items():
+        if hasattr(L, name):
+            getattr(L, name).argtypes = argtypes
+            getattr(L, name).restype = i32
     L.cz_debug_sqrt.argtypes = [vp, vp, i32, vp]
     L.cz_debug_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_double, i32, vp, i32, vp]
     L.cz_debug_noise.restype = i32
@@ -331,11 +315,7 @@ class Search:
     def root_value(self):
         """The search value of every current root, as a visit entry of that root would carry it (cz_search_root_value;
         bans of the current set_roots, the counts of root_targets as weights): float64 [G], NaN = no value."""
-        import torch
-        q = torch.empty((self.G,), dtype=torch.float64, device=self.device)
-        _native.check(self.L.cz_search_root_value(self.h, C.c_void_p(q.data_ptr()), self._stream()),
-                      "cz_search_root_value")
-        return q.cpu().numpy()
+        return self._root_outputs("cz_search_root_value", ((self.G,), "float64"))[0]
 
     def record_surprise(self, on=True):
         """Self-play: every visit entry comes with the ply's policy surprise s, the Kullback-Leibler divergence of the
@@ -350,21 +330,21 @@ class Search:
     def root_surprise(self):
         """The policy surprise of every current root, as a visit entry of that root would carry it
         (cz_search_root_surprise; bans of the current set_roots, the counts of root_targets): float64 [G], NaN = none."""
-        import torch
-        out = torch.empty((self.G,), dtype=torch.float64, device=self.device)
-        _native.check(self.L.cz_search_root_surprise(self.h, C.c_void_p(out.data_ptr()), self._stream()),
-                      "cz_search_root_surprise")
-        return out.cpu().numpy()
+        return self._root_outputs("cz_search_root_surprise", ((self.G,), "float64"))[0]
 
     def root_targets(self):
         """The pruned counts of every current root (cz_search_root_targets; edge order of root_stats, bans of the current
         set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
+        n, raw = self._root_outputs("cz_search_root_targets", ((self.G, _native.MAXMOVES), "int32"), ((self.G,), "int32"))
+        return dict(n=n, raw_total=raw)
+
+    def _root_outputs(self, fn, *outs):
+        """Allocate the device outputs `outs` ((shape, dtype name), ...), call fn(handle, outputs..., stream) and return
+        them as numpy arrays."""
         import torch
-        n = torch.empty((self.G, _native.MAXMOVES), dtype=torch.int32, device=self.device)
-        raw = torch.empty((self.G,), dtype=torch.int32, device=self.device)
-        _native.check(self.L.cz_search_root_targets(self.h, C.c_void_p(n.data_ptr()), C.c_void_p(raw.data_ptr()),
-                                                    self._stream()), "cz_search_root_targets")
-        return dict(n=n.cpu().numpy(), raw_total=raw.cpu().numpy())
+        ts = [torch.empty(shape, dtype=getattr(torch, dt), device=self.device) for shape, dt in outs]
+        _native.check(getattr(self.L, fn)(self.h, *[C.c_void_p(t.data_ptr()) for t in ts], self._stream()), fn)
+        return [t.cpu().numpy() for t in ts]
 
     def pull_visits(self, defer=False):
         """Move the entries waiting in the device ring to the host (kept until their game's record is drained).
@@ -382,18 +362,18 @@ class Search:
             return 0
         buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
         q = None
-        if self.surprise_on:
-            # both rings beside the entries; a value record that is off leaves q at NaN, "no value"
+        if self.values_on or self.surprise_on:
+            # both rings beside the entries; a record that is off is not copied and leaves q at NaN, "no value"
             q = np.full((n.value,), np.nan, dtype=np.float64)
             sp = np.empty((n.value,), dtype=np.float64)
-            _native.check(self.L.cz_search_drain_visits_qs(self.h, buf.ctypes.data, q.ctypes.data if self.values_on else None,
-                                                           sp.ctypes.data, n.value, C.byref(n), C.byref(dropped),
-                                                           self._stream()), "cz_search_drain_visits_qs")
-            q = np.stack([q, sp], axis=1)
-        elif self.values_on:
-            q = np.empty((n.value,), dtype=np.float64)
-            _native.check(self.L.cz_search_drain_visits_q(self.h, buf.ctypes.data, q.ctypes.data, n.value, C.byref(n),
-                                                          C.byref(dropped), self._stream()), "cz_search_drain_visits_q")
+            rings = [q.ctypes.data if self.values_on else None, sp.ctypes.data if self.surprise_on else None]
+            fn = "cz_search_drain_visits_qs"
+            if not hasattr(self.L, fn):        # (an older library selected with CZ_LIB: it has the value record alone)
+                fn, rings = "cz_search_drain_visits_q", rings[:1]
+            _native.check(getattr(self.L, fn)(self.h, buf.ctypes.data, *rings, n.value, C.byref(n), C.byref(dropped),
+                                              self._stream()), fn)
+            if self.surprise_on:
+                q = np.stack([q, sp], axis=1)
         else:
             _native.check(self.L.cz_search_drain_visits(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(dropped),
                                                         self._stream()), "cz_search_drain_visits")
@@ -679,25 +659,33 @@ def debug_sqrt(x):
     return y
 
 
+def _row_args(fn, n_edges, *want):
+    """The argument check of the *_rows helpers: every (tensor, dtype name) of `want` a contiguous cuda tensor [rows, 128],
+    n_edges a contiguous cuda uint8 tensor [rows].  Returns (rows, the tensors' pointers, n_edges' pointer, the stream)."""
+    import torch
+    _native.require_gpu()
+    rows = int(n_edges.numel())
+    for t, dt in want:
+        dt = getattr(torch, dt)
+        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{fn}: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
+    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
+        raise ValueError(f"{fn}: n_edges must be a contiguous cuda uint8 tensor")
+    return (rows, [C.c_void_p(t.data_ptr()) for t, _ in want], C.c_void_p(n_edges.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
 def policy_target_prune(labels, n, w, p, n_edges, c_puct, k):
     """cz_policy_target_prune: the pruning arithmetic of set_forced_playouts on caller-supplied rows.  labels uint16 (bit
     15 = banned), n int32, w float64, p float32, all [rows, 128] cuda tensors; n_edges uint8 [rows].  Returns (pruned
     counts int32 [rows, 128], raw_total int32 [rows]) on the device."""
     import torch
-    _native.require_gpu()
-    rows = int(n_edges.numel())
-    want = ((labels, torch.uint16), (n, torch.int32), (w, torch.float64), (p, torch.float32))
-    for t, dt in want:
-        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"policy_target_prune: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
-    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
-        raise ValueError("policy_target_prune: n_edges must be a contiguous cuda uint8 tensor")
+    rows, ptrs, ne, stream = _row_args("policy_target_prune", n_edges, (labels, "uint16"), (n, "int32"), (w, "float64"),
+                                       (p, "float32"))
     out = torch.empty((rows, _native.MAXMOVES), dtype=torch.int32, device=n.device)
     raw = torch.empty((rows,), dtype=torch.int32, device=n.device)
-    _native.check(_native.lib().cz_policy_target_prune(
-        C.c_void_p(labels.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(p.data_ptr()),
-        C.c_void_p(n_edges.data_ptr()), rows, float(c_puct), float(k), C.c_void_p(out.data_ptr()),
-        C.c_void_p(raw.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_policy_target_prune")
+    _native.check(_native.lib().cz_policy_target_prune(*ptrs, ne, rows, float(c_puct), float(k), C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(raw.data_ptr()), stream), "cz_policy_target_prune")
     return out, raw
 
 
@@ -706,19 +694,10 @@ def root_value_rows(labels, m, n, w, n_edges):
     m int32 (the recorded counts), n int32 and w float64 (the raw statistics), all [rows, 128] cuda tensors; n_edges uint8
     [rows].  Returns float64 [rows] on the device, NaN = no value."""
     import torch
-    _native.require_gpu()
-    rows = int(n_edges.numel())
-    want = ((labels, torch.uint16), (m, torch.int32), (n, torch.int32), (w, torch.float64))
-    for t, dt in want:
-        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"root_value_rows: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
-    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
-        raise ValueError("root_value_rows: n_edges must be a contiguous cuda uint8 tensor")
+    rows, ptrs, ne, stream = _row_args("root_value_rows", n_edges, (labels, "uint16"), (m, "int32"), (n, "int32"),
+                                       (w, "float64"))
     out = torch.empty((rows,), dtype=torch.float64, device=n.device)
-    _native.check(_native.lib().cz_root_value(
-        C.c_void_p(labels.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(w.data_ptr()),
-        C.c_void_p(n_edges.data_ptr()), rows, C.c_void_p(out.data_ptr()),
-        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_root_value")
+    _native.check(_native.lib().cz_root_value(*ptrs, ne, rows, C.c_void_p(out.data_ptr()), stream), "cz_root_value")
     return out
 
 
@@ -730,19 +709,9 @@ def root_surprise_rows(labels, m, p, n_edges):
     banned), m int32 (the recorded counts) and p float32 (the priors without noise), all [rows, 128] cuda tensors; n_edges
     uint8 [rows].  Returns float64 [rows] on the device, NaN = no surprise."""
     import torch
-    _native.require_gpu()
-    rows = int(n_edges.numel())
-    want = ((labels, torch.uint16), (m, torch.int32), (p, torch.float32))
-    for t, dt in want:
-        if t.dtype != dt or tuple(t.shape) != (rows, _native.MAXMOVES) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"root_surprise_rows: expected a contiguous cuda {dt} tensor [{rows}, {_native.MAXMOVES}]")
-    if n_edges.dtype != torch.uint8 or not n_edges.is_cuda or not n_edges.is_contiguous():
-        raise ValueError("root_surprise_rows: n_edges must be a contiguous cuda uint8 tensor")
+    rows, ptrs, ne, stream = _row_args("root_surprise_rows", n_edges, (labels, "uint16"), (m, "int32"), (p, "float32"))
     out = torch.empty((rows,), dtype=torch.float64, device=m.device)
-    _native.check(_native.lib().cz_root_surprise(
-        C.c_void_p(labels.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(p.data_ptr()),
-        C.c_void_p(n_edges.data_ptr()), rows, C.c_void_p(out.data_ptr()),
-        C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_root_surprise")
+    _native.check(_native.lib().cz_root_surprise(*ptrs, ne, rows, C.c_void_p(out.data_ptr()), stream), "cz_root_surprise")
     return out
 
 

@@ -99,7 +99,7 @@ struct SearchParams {
     int fast_sims;          // simulations of a fast ply, 0 = off: every ply is a full search of `sims`
     double full_rate;       // ply `turns` is a full search iff philox_uniform(seed, game_id, 2, turns) < full_rate
     // forced playouts + policy target pruning (cz_search_set_forced_playouts); read by k_sim's root context, emit_visits
-    // and k_root_targets only
+    // and k_root_records only
     double forced_k;        // 0 = off; a tried root child is visited at least sqrt(forced_k * p * N) times
 };
 

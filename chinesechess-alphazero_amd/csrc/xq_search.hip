@@ -1282,6 +1282,65 @@ XQ_D void emit_record(const SearchParams& P, const SearchBuffers& B, const GameV
     if (resigned) count(gv, CT_RESIGNS);
 }
 
+// A root's edges as one wavefront holds them, edge j = lane + 64 h: the label with VISIT_BANNED, the raw statistics n / w,
+// the float32 prior WITHOUT noise.  What an edge at or beyond nm, or an array the source lacks, would hold is zero.
+struct RootEdges {
+    int nm, sum_n;
+    uint16_t lab[2];
+    int n[2];
+    double w[2];
+    float p[2];
+};
+
+// ... of the game's current root in the tree, with the bans of g_no_act; no root: nm = 0.  All 64 lanes call it.
+XQ_D RootEdges load_root_edges(const SearchBuffers& B, const GameView& gv)
+{
+    RootEdges E{};
+    const int lane = lane_id();
+    const int g = gv.g;
+    const int root = uni(B.g_root[g]);
+    if (root < 0) return E;
+    char* base = rec_ptr(gv, (uint32_t)root);
+    const NodeHdr hdr = load_hdr(base);
+    const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
+    E.nm = (int)(hdr.meta & 0xFF) > MAXMOVES ? MAXMOVES : (int)(hdr.meta & 0xFF);
+    E.sum_n = hdr.sum_n;
+    const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+    const int n_no_act = uni((int)B.g_n_no_act[g]);
+    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j >= E.nm) continue;
+        const uint16_t mv = pm[j];
+        bool banned = false;
+        for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
+        E.lab[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
+        if (sb) { const EdgeStat es = sb[j]; E.n[h] = es.n; E.w[h] = es.w; }
+        E.p[h] = node_p(base)[j];
+    }
+    return E;
+}
+
+// ... of row r of caller-supplied arrays [rows][128]; a NULL array stays zero
+XQ_D RootEdges load_row_edges(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
+                              const double* __restrict__ w, const float* __restrict__ p,
+                              const uint8_t* __restrict__ n_edges, int r)
+{
+    RootEdges E{};
+    E.nm = n_edges[r] > MAXMOVES ? MAXMOVES : n_edges[r];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane_id() + 64 * h;
+        if (lane_id() + 64 * h >= E.nm) continue;
+        E.lab[h] = labels[i];
+        if (n) E.n[h] = n[i];
+        if (w) E.w[h] = w[i];
+        if (p) E.p[h] = p[i];
+    }
+    return E;
+}
+
 // Policy target pruning (include/czero.h, cz_search_set_forced_playouts): one wavefront, edge j = lane + 64 h.  lab[h]
 // carries VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise; the pruned counts replace n[].
 // All arithmetic in float64, in the order czero.h writes it.  Returns S, the raw total of the non-banned edges.
@@ -1396,13 +1455,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
 {
     const int lane = lane_id();
     const int g = gv.g;
-    const int root = uni(B.g_root[g]);
-    if (root < 0) return;
-    char* base = rec_ptr(gv, (uint32_t)root);
-    const NodeHdr hdr = load_hdr(base);
-    int nm = (int)(hdr.meta & 0xFF);
-    const uint16_t* pm = node_mv(base, nm);
-    if (nm > VISIT_MAX_EDGES) nm = VISIT_MAX_EDGES;
+    if (uni(B.g_root[g]) < 0) return;
     unsigned int pos = 0;
     int drop = 0;
     if (lane == 0) {
@@ -1418,74 +1471,23 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
     uint8_t* e = V.ring + (size_t)(pos % V.cap) * VISIT_STRIDE;
     uint16_t* lab = reinterpret_cast<uint16_t*>(e + sizeof(VisitEntryHdr));
     int32_t* cnt = reinterpret_cast<int32_t*>(e + sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES);
-    const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
-    const int n_no_act = uni((int)B.g_n_no_act[g]);
-    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
-    int raw_total = 0;
-    if (!prune) {
-        for (int j = lane; j < nm; j += 64) {
-            const uint16_t mv = pm[j];
-            bool banned = false;
-            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-            lab[j] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-            cnt[j] = sb ? sb[j].n : 0;
-        }
-    } else {
-        uint16_t el[2] = {0, 0};
-        int en[2] = {0, 0};
-        double ew[2] = {0.0, 0.0};
-        float ep[2] = {0.0f, 0.0f};
+    const RootEdges E = load_root_edges(B, gv);
+    const int nm = E.nm;
+    int m[2] = {E.n[0], E.n[1]};            // the counts the entry records: raw, or pruned
+    const int raw_total = prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k) : 0;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            const uint16_t mv = pm[j];
-            bool banned = false;
-            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-            if (sb) { const EdgeStat es = sb[j]; en[h] = es.n; ew[h] = es.w; }
-            ep[h] = node_p(base)[j];
-        }
-        raw_total = prune_targets(nm, el, en, ew, ep, P.c_puct, P.forced_k);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j < nm) { lab[j] = el[h]; cnt[j] = en[h]; }
-        }
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j < nm) { lab[j] = E.lab[h]; cnt[j] = m[h]; }
     }
     const bool pruned = raw_total > 0;      // S == 0: nothing to prune, the entry is the one written without pruning
+    // the value and the surprise record (cz_search_record_values, _surprise): the entry's slot in a ring of their own
     if (V.q) {
-        // the value record (cz_search_record_values): the entry's slot in a ring of its own, from the labels and counts
-        // this lane has just written and the raw statistics in the tree
-        uint16_t ql[2] = {0, 0};
-        int qm[2] = {0, 0}, qn[2] = {0, 0};
-        double qw[2] = {0.0, 0.0};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            ql[h] = lab[j];
-            qm[h] = cnt[j];
-            if (sb) { const EdgeStat es = sb[j]; qn[h] = es.n; qw[h] = es.w; }
-        }
-        const double q = root_value(nm, ql, qm, qn, qw);
+        const double q = root_value(nm, E.lab, m, E.n, E.w);
         if (lane == 0) V.q[pos % V.cap] = q;
     }
     if (V.s) {
-        // the surprise record (cz_search_record_surprise): likewise, from the labels and counts this lane has just
-        // written and the root's priors without noise
-        uint16_t sl[2] = {0, 0};
-        int sm[2] = {0, 0};
-        float sp[2] = {0.0f, 0.0f};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            sl[h] = lab[j];
-            sm[h] = cnt[j];
-            sp[h] = node_p(base)[j];
-        }
-        const double sv = root_surprise(nm, sl, sm, sp);
+        const double sv = root_surprise(nm, E.lab, m, E.p);
         if (lane == 0) V.s[pos % V.cap] = sv;
     }
     if (lane == 0) {
@@ -1494,7 +1496,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
         h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u));
-        h->sum_n = hdr.sum_n;
+        h->sum_n = E.sum_n;
         h->raw_total = (uint32_t)raw_total;
     }
 }
@@ -2032,201 +2034,68 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
     }
 }
 
-// Pruned policy targets of every current root (cz_search_root_targets): what emit_visits would record for it, with
-// the bans of the current set_roots
-__global__ __launch_bounds__(64) void k_root_targets(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
-                                                    int32_t* __restrict__ raw_total)
+// What emit_visits would record for every current root, with the bans of the current set_roots (cz_search_root_targets,
+// _root_value, _root_surprise): the pruned counts n [G][128] and their raw total, the search value q, the policy
+// surprise s.  A NULL output is not computed.  One wavefront per game.
+__global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
+                                                    int32_t* __restrict__ raw_total, double* __restrict__ q,
+                                                    double* __restrict__ s)
 {
     __shared__ uint32_t chtab[MAX_CHUNKS];
     const int g = blockIdx.x;
     if (g >= P.G) return;
     const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
     const int lane = lane_id();
-    const int root = B.g_root[g];
-    const int n_no_act = B.g_n_no_act[g];
-    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
-    int nm = 0;
-    uint16_t el[2] = {0, 0};
-    int en[2] = {0, 0};
-    double ew[2] = {0.0, 0.0};
-    float ep[2] = {0.0f, 0.0f};
-    if (root >= 0) {
-        char* base = rec_ptr(gv, (uint32_t)root);
-        const NodeHdr hdr = load_hdr(base);
-        nm = (int)(hdr.meta & 0xFF);
-        if (nm > MAXMOVES) nm = MAXMOVES;
-        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
-        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
+    const RootEdges E = load_root_edges(B, gv);
+    int m[2] = {E.n[0], E.n[1]};
+    const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k);
+    if (n) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            const uint16_t mv = pm[j];
-            bool banned = false;
-            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-            if (sb) { const EdgeStat es = sb[j]; en[h] = es.n; ew[h] = es.w; }
-            ep[h] = node_p(base)[j];
-        }
+        for (int h = 0; h < 2; ++h) n[(size_t)g * MAXMOVES + lane + 64 * h] = lane + 64 * h < E.nm ? m[h] : 0;
     }
-    const int S = prune_targets(nm, el, en, ew, ep, P.c_puct, P.forced_k);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) n[(size_t)g * MAXMOVES + lane + 64 * h] = lane + 64 * h < nm ? en[h] : 0;
-    if (lane == 0) raw_total[g] = S;
+    if (raw_total && lane == 0) raw_total[g] = S;
+    if (q) {
+        const double v = root_value(E.nm, E.lab, m, E.n, E.w);
+        if (lane == 0) q[g] = v;
+    }
+    if (s) {
+        const double v = root_surprise(E.nm, E.lab, m, E.p);
+        if (lane == 0) s[g] = v;
+    }
 }
 
-// cz_policy_target_prune: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
-__global__ __launch_bounds__(64) void k_policy_target_prune(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
-                                                           const double* __restrict__ w, const float* __restrict__ p,
-                                                           const uint8_t* __restrict__ n_edges, int rows, double c_puct,
-                                                           double k, int32_t* __restrict__ out_n,
-                                                           int32_t* __restrict__ out_raw_total)
+// cz_policy_target_prune, cz_root_value, cz_root_surprise: the same arithmetic on caller-supplied rows [rows][128], one
+// wavefront per row.  out_n (with out_raw_total): the counts n are pruned; otherwise m holds the recorded counts.  A
+// NULL input reads as zeros, a NULL output is not computed.
+__global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m_in,
+                                                   const int32_t* __restrict__ n, const double* __restrict__ w,
+                                                   const float* __restrict__ p, const uint8_t* __restrict__ n_edges,
+                                                   int rows, double c_puct, double k, int32_t* __restrict__ out_n,
+                                                   int32_t* __restrict__ out_raw_total, double* __restrict__ out_q,
+                                                   double* __restrict__ out_s)
 {
     const int r = blockIdx.x;
     if (r >= rows) return;
     const int lane = lane_id();
-    int nm = n_edges[r];
-    if (nm > MAXMOVES) nm = MAXMOVES;
-    uint16_t el[2] = {0, 0};
-    int en[2] = {0, 0};
-    double ew[2] = {0.0, 0.0};
-    float ep[2] = {0.0f, 0.0f};
+    const RootEdges E = load_row_edges(labels, n, w, p, n_edges, r);
+    int m[2] = {E.n[0], E.n[1]};
+    if (out_n) {
+        const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, c_puct, k);
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
-        if (lane + 64 * h < nm) { el[h] = labels[i]; en[h] = n[i]; ew[h] = w[i]; ep[h] = p[i]; }
+        for (int h = 0; h < 2; ++h) out_n[(size_t)r * MAXMOVES + lane + 64 * h] = lane + 64 * h < E.nm ? m[h] : 0;
+        if (lane == 0) out_raw_total[r] = S;
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) m[h] = lane + 64 * h < E.nm ? m_in[(size_t)r * MAXMOVES + lane + 64 * h] : 0;
     }
-    const int S = prune_targets(nm, el, en, ew, ep, c_puct, k);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) out_n[(size_t)r * MAXMOVES + lane + 64 * h] = lane + 64 * h < nm ? en[h] : 0;
-    if (lane == 0) out_raw_total[r] = S;
-}
-
-// Search value of every current root (cz_search_root_value): what the value record would hold for it -- the counts of
-// k_root_targets as m, the raw statistics as n / w
-__global__ __launch_bounds__(64) void k_root_value(SearchParams P, SearchBuffers B, double* __restrict__ q)
-{
-    __shared__ uint32_t chtab[MAX_CHUNKS];
-    const int g = blockIdx.x;
-    if (g >= P.G) return;
-    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
-    const int lane = lane_id();
-    const int root = B.g_root[g];
-    const int n_no_act = B.g_n_no_act[g];
-    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
-    int nm = 0;
-    uint16_t el[2] = {0, 0};
-    int en[2] = {0, 0}, em[2] = {0, 0};
-    double ew[2] = {0.0, 0.0};
-    float ep[2] = {0.0f, 0.0f};
-    if (root >= 0) {
-        char* base = rec_ptr(gv, (uint32_t)root);
-        const NodeHdr hdr = load_hdr(base);
-        nm = (int)(hdr.meta & 0xFF);
-        if (nm > MAXMOVES) nm = MAXMOVES;
-        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
-        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            const uint16_t mv = pm[j];
-            bool banned = false;
-            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-            if (sb) { const EdgeStat es = sb[j]; en[h] = em[h] = es.n; ew[h] = es.w; }
-            ep[h] = node_p(base)[j];
-        }
+    if (out_q) {
+        const double v = root_value(E.nm, E.lab, m, E.n, E.w);
+        if (lane == 0) out_q[r] = v;
     }
-    prune_targets(nm, el, em, ew, ep, P.c_puct, P.forced_k);
-    const double v = root_value(nm, el, em, en, ew);
-    if (lane == 0) q[g] = v;
-}
-
-// cz_root_value: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
-__global__ __launch_bounds__(64) void k_root_value_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m,
-                                                       const int32_t* __restrict__ n, const double* __restrict__ w,
-                                                       const uint8_t* __restrict__ n_edges, int rows,
-                                                       double* __restrict__ out_q)
-{
-    const int r = blockIdx.x;
-    if (r >= rows) return;
-    const int lane = lane_id();
-    int nm = n_edges[r];
-    if (nm > MAXMOVES) nm = MAXMOVES;
-    uint16_t el[2] = {0, 0};
-    int em[2] = {0, 0}, en[2] = {0, 0};
-    double ew[2] = {0.0, 0.0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
-        if (lane + 64 * h < nm) { el[h] = labels[i]; em[h] = m[i]; en[h] = n[i]; ew[h] = w[i]; }
+    if (out_s) {
+        const double v = root_surprise(E.nm, E.lab, m, E.p);
+        if (lane == 0) out_s[r] = v;
     }
-    const double v = root_value(nm, el, em, en, ew);
-    if (lane == 0) out_q[r] = v;
-}
-
-// Policy surprise of every current root (cz_search_root_surprise): what the surprise record would hold for it -- the
-// counts of k_root_targets as m, the priors without noise as p
-__global__ __launch_bounds__(64) void k_root_surprise(SearchParams P, SearchBuffers B, double* __restrict__ out)
-{
-    __shared__ uint32_t chtab[MAX_CHUNKS];
-    const int g = blockIdx.x;
-    if (g >= P.G) return;
-    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
-    const int lane = lane_id();
-    const int root = B.g_root[g];
-    const int n_no_act = B.g_n_no_act[g];
-    const uint16_t* no_act = B.g_no_act + (size_t)g * MAX_NO_ACT;
-    int nm = 0;
-    uint16_t el[2] = {0, 0};
-    int em[2] = {0, 0};
-    double ew[2] = {0.0, 0.0};
-    float ep[2] = {0.0f, 0.0f};
-    if (root >= 0) {
-        char* base = rec_ptr(gv, (uint32_t)root);
-        const NodeHdr hdr = load_hdr(base);
-        nm = (int)(hdr.meta & 0xFF);
-        if (nm > MAXMOVES) nm = MAXMOVES;
-        const uint16_t* pm = node_mv(base, (int)(hdr.meta & 0xFF));
-        const EdgeStat* sb = hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = lane + 64 * h;
-            if (j >= nm) continue;
-            const uint16_t mv = pm[j];
-            bool banned = false;
-            for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == mv);
-            el[h] = (uint16_t)(mv | (banned ? VISIT_BANNED : 0));
-            if (sb) { const EdgeStat es = sb[j]; em[h] = es.n; ew[h] = es.w; }
-            ep[h] = node_p(base)[j];
-        }
-    }
-    prune_targets(nm, el, em, ew, ep, P.c_puct, P.forced_k);
-    const double v = root_surprise(nm, el, em, ep);
-    if (lane == 0) out[g] = v;
-}
-
-// cz_root_surprise: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
-__global__ __launch_bounds__(64) void k_root_surprise_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m,
-                                                          const float* __restrict__ p, const uint8_t* __restrict__ n_edges,
-                                                          int rows, double* __restrict__ out)
-{
-    const int r = blockIdx.x;
-    if (r >= rows) return;
-    const int lane = lane_id();
-    int nm = n_edges[r];
-    if (nm > MAXMOVES) nm = MAXMOVES;
-    uint16_t el[2] = {0, 0};
-    int em[2] = {0, 0};
-    float ep[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
-        if (lane + 64 * h < nm) { el[h] = labels[i]; em[h] = m[i]; ep[h] = p[i]; }
-    }
-    const double v = root_surprise(nm, el, em, ep);
-    if (lane == 0) out[r] = v;
 }
 
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
@@ -2327,8 +2196,6 @@ struct cz_search {
     int keep_chunks_created = 0;      // P.keep_chunks as sized at creation (cz_search_set_sims never goes below it)
     VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
     void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
-    void* q_mem = nullptr;            // the value ring V.q (cz_search_record_values), allocated only while that is on
-    void* s_mem = nullptr;            // the surprise ring V.s (cz_search_record_surprise), likewise
     void* book_mem = nullptr;         // the start-position book (cz_search_set_book): P.book points here
 };
 
@@ -2544,8 +2411,8 @@ int cz_search_destroy(cz_search* s)
 {
     if (!s) return CZ_OK;
     (void)hipFree(s->vis_mem);
-    (void)hipFree(s->q_mem);
-    (void)hipFree(s->s_mem);
+    (void)hipFree(s->V.q);
+    (void)hipFree(s->V.s);
     (void)hipFree(s->book_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
@@ -2719,19 +2586,42 @@ int cz_search_policy_logits(cz_search* s, int on)
 static_assert(sizeof(cz_visit_entry) == sizeof(VisitEntryHdr) && VISIT_STRIDE == 784, "czero.h: visit entry layout");
 static_assert(VISIT_MAX_EDGES == MAXMOVES, "a root has at most MAXMOVES edges");
 
+// Switch a side ring of the visit ring (one double per slot: V.q, V.s) on or off; `what` names the caller in errors
+static int side_ring(cz_search* s, double*& ring, int on, hipStream_t st, const char* what)
+{
+    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
+    if (e != hipSuccess) return serr_hip(what, e);
+    if (on && ring) return CZ_OK;                        // already on: the ring and what waits in it stay
+    (void)hipFree(ring);
+    ring = nullptr;
+    if (!on) return CZ_OK;
+    void* mem = nullptr;
+    const size_t bytes = (size_t)s->V.cap * sizeof(double);
+    e = hipMalloc(&mem, bytes);
+    char where[64];
+    snprintf(where, sizeof(where), "%s: hipMalloc", what);
+    if (e != hipSuccess) return serr_hip(where, e);
+    // entries already waiting in the visit ring were written without this record: NaN, "none"
+    e = hipMemsetAsync(mem, 0xFF, bytes, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip(what, e); }
+    ring = (double*)mem;
+    return CZ_OK;
+}
+
 int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_visits: null handle");
     if (capacity < 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity < 0");
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffers
-    if (e != hipSuccess) return serr_hip("cz_search_record_visits", e);
+    // the value and the surprise ring share the visit ring's slots: they go with it.  side_ring waits for the stream:
+    // no launch in flight may still use the old buffers
+    if (side_ring(s, s->V.q, 0, st, "cz_search_record_visits") != CZ_OK
+        || side_ring(s, s->V.s, 0, st, "cz_search_record_visits") != CZ_OK)
+        return CZ_ERR_HIP;
+    hipError_t e = hipSuccess;
     (void)hipFree(s->vis_mem);
-    (void)hipFree(s->q_mem);                             // the value ring shares the visit ring's slots: it goes with it
-    (void)hipFree(s->s_mem);                             // and so does the surprise ring
     s->vis_mem = nullptr;
-    s->q_mem = nullptr;
-    s->s_mem = nullptr;
     s->V = VisitRing{};
     if (!on) return CZ_OK;
     // default: 64 entries per game -- one k_advance launch records at most 8 plies of a game (the loop in k_advance),
@@ -2820,7 +2710,8 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
 int cz_search_root_targets(cz_search* s, int32_t* n, int32_t* raw_total, void* stream)
 {
     if (!s || !n || !raw_total) return serr(CZ_ERR_ARG, "cz_search_root_targets: null argument");
-    hipLaunchKernelGGL(k_root_targets, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, n, raw_total);
+    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, n, raw_total,
+                       (double*)nullptr, (double*)nullptr);
     S_LAUNCH_CHECK("cz_search_root_targets");
     return CZ_OK;
 }
@@ -2834,8 +2725,8 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
     if (!finite_nonneg(k) || !finite_nonneg(c_puct))
         return serr(CZ_ERR_ARG, "cz_policy_target_prune: k or c_puct negative or not finite");
     if (rows == 0) return CZ_OK;
-    hipLaunchKernelGGL(k_policy_target_prune, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows,
-                       c_puct, k, out_n, out_raw_total);
+    hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, (const int32_t*)nullptr, n, w, p,
+                       n_edges, rows, c_puct, k, out_n, out_raw_total, (double*)nullptr, (double*)nullptr);
     S_LAUNCH_CHECK("cz_policy_target_prune");
     return CZ_OK;
 }
@@ -2844,33 +2735,14 @@ int cz_search_record_values(cz_search* s, int on, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_values: null handle");
     if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_values: needs cz_search_record_visits on");
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
-    if (e != hipSuccess) return serr_hip("cz_search_record_values", e);
-    if (!on) {
-        (void)hipFree(s->q_mem);
-        s->q_mem = nullptr;
-        s->V.q = nullptr;
-        return CZ_OK;
-    }
-    if (s->V.q) return CZ_OK;                            // already on: the ring and what waits in it stay
-    void* mem = nullptr;
-    const size_t bytes = (size_t)s->V.cap * sizeof(double);
-    e = hipMalloc(&mem, bytes);
-    if (e != hipSuccess) return serr_hip("cz_search_record_values: hipMalloc", e);
-    // entries already waiting in the visit ring were written without a value: NaN, "no value"
-    e = hipMemsetAsync(mem, 0xFF, bytes, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip("cz_search_record_values", e); }
-    s->q_mem = mem;
-    s->V.q = (double*)mem;
-    return CZ_OK;
+    return side_ring(s, s->V.q, on, (hipStream_t)stream, "cz_search_record_values");
 }
 
 int cz_search_root_value(cz_search* s, double* q, void* stream)
 {
     if (!s || !q) return serr(CZ_ERR_ARG, "cz_search_root_value: null argument");
-    hipLaunchKernelGGL(k_root_value, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, q);
+    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
+                       (int32_t*)nullptr, q, (double*)nullptr);
     S_LAUNCH_CHECK("cz_search_root_value");
     return CZ_OK;
 }
@@ -2881,8 +2753,8 @@ int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, co
     if (!labels || !m || !n || !w || !n_edges || !out_q || rows < 0)
         return serr(CZ_ERR_ARG, "cz_root_value: null argument or rows < 0");
     if (rows == 0) return CZ_OK;
-    hipLaunchKernelGGL(k_root_value_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, n, w, n_edges, rows,
-                       out_q);
+    hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, n, w, (const float*)nullptr,
+                       n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr, out_q, (double*)nullptr);
     S_LAUNCH_CHECK("cz_root_value");
     return CZ_OK;
 }
@@ -2893,33 +2765,14 @@ int cz_search_record_surprise(cz_search* s, int on, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_surprise: null handle");
     if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_surprise: needs cz_search_record_visits on");
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
-    if (e != hipSuccess) return serr_hip("cz_search_record_surprise", e);
-    if (!on) {
-        (void)hipFree(s->s_mem);
-        s->s_mem = nullptr;
-        s->V.s = nullptr;
-        return CZ_OK;
-    }
-    if (s->V.s) return CZ_OK;                            // already on: the ring and what waits in it stay
-    void* mem = nullptr;
-    const size_t bytes = (size_t)s->V.cap * sizeof(double);
-    e = hipMalloc(&mem, bytes);
-    if (e != hipSuccess) return serr_hip("cz_search_record_surprise: hipMalloc", e);
-    // entries already waiting in the visit ring were written without a surprise: NaN, "no surprise"
-    e = hipMemsetAsync(mem, 0xFF, bytes, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip("cz_search_record_surprise", e); }
-    s->s_mem = mem;
-    s->V.s = (double*)mem;
-    return CZ_OK;
+    return side_ring(s, s->V.s, on, (hipStream_t)stream, "cz_search_record_surprise");
 }
 
 int cz_search_root_surprise(cz_search* s, double* out, void* stream)
 {
     if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_surprise: null argument");
-    hipLaunchKernelGGL(k_root_surprise, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, out);
+    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
+                       (int32_t*)nullptr, (double*)nullptr, out);
     S_LAUNCH_CHECK("cz_search_root_surprise");
     return CZ_OK;
 }
@@ -2930,7 +2783,9 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
     if (!labels || !m || !p || !n_edges || !out || rows < 0)
         return serr(CZ_ERR_ARG, "cz_root_surprise: null argument or rows < 0");
     if (rows == 0) return CZ_OK;
-    hipLaunchKernelGGL(k_root_surprise_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, p, n_edges, rows, out);
+    hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, (const int32_t*)nullptr,
+                       (const double*)nullptr, p, n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr,
+                       (double*)nullptr, out);
     S_LAUNCH_CHECK("cz_root_surprise");
     return CZ_OK;
 }

@@ -20,6 +20,7 @@ import pytest
 import forced_playouts_oracle as fo
 import stub_net
 from oracle import xq_oracle as xo
+from selfplay_raw import selfplay_raw
 from test_gpu_book import GOLDEN, _engine_cfg
 from test_gpu_search import (assert_root_equal, boards_tensor, gpu, no_act_tensors, oracle_cfg, play_config,  # noqa: F401
                              stub_eval)
@@ -37,43 +38,9 @@ def _entry_key(e):
 
 
 def _selfplay_raw(gpu, pc, seed, rounds, setup):
-    """The bytes of the finished-game records and of the visit entries, as the two device rings hand them out, and all
-    counters after a fixed number of rounds.  A record is its 16-byte header and the `turns` moves it holds; an entry its
-    16-byte header and the n_edges labels and counts it holds (the ring slot's other bytes belong to no entry).  Both
-    sorted: games that end in one launch reach the rings in any order."""
-    s = gpu.S.Search(pc, G, seed=seed)
-    setup(s)
-    s.record_visits(True)
-    ev = stub_eval(gpu, SPEC)
-    s.start_selfplay(seed=seed, first_game_id=0)
-    recs, entries = [], []
-    cur = C.c_uint(0)
-
-    def drain():
-        n = C.c_int(0)
-        buf = np.zeros((4096, s.record_stride), dtype=np.uint8)
-        gpu.N.check(s.L.cz_search_drain_records(s.h, C.byref(cur), buf.ctypes.data, 4096, C.byref(n), s._stream()), "drain")
-        for i in range(n.value):
-            turns = int(buf[i, 4:8].view(np.int32)[0])
-            recs.append(buf[i, :16 + 2 * turns].tobytes())
-        gpu.N.check(s.L.cz_search_drain_visits(s.h, None, 0, C.byref(n), None, s._stream()), "count")
-        vbuf = np.zeros((max(1, n.value), gpu.S.VISIT_STRIDE), dtype=np.uint8)
-        gpu.N.check(s.L.cz_search_drain_visits(s.h, vbuf.ctypes.data, n.value, C.byref(n), None, s._stream()), "visits")
-        for i in range(n.value):
-            ne = int(vbuf[i, 6])
-            entries.append(vbuf[i, :16 + 2 * ne].tobytes() + vbuf[i, 16 + 256:16 + 256 + 4 * ne].tobytes())
-    for r in range(rounds):
-        s.round()
-        p, v = ev(s.planes)
-        s.policy.copy_(p)
-        s.value.copy_(v)
-        if r % 16 == 15:                                    # (before either ring can fill)
-            drain()
-    drain()
-    ctr = s.counters()
-    s.close()
-    assert ctr["visits_dropped"] == 0
-    return sorted(recs), sorted(entries), ctr
+    """selfplay_raw with the setup BEFORE the visit ring is switched on; the entries as their rows alone."""
+    recs, entries, ctr = selfplay_raw(gpu, pc, seed, rounds, G, setup_before=setup)
+    return recs, [row for row, _, _ in entries], ctr
 
 
 @pytest.mark.parametrize("K", [1, 8])

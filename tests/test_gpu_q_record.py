@@ -21,6 +21,7 @@ import pytest
 import forced_playouts_oracle as fo
 import q_record_oracle as qo
 from oracle import xq_oracle as xo
+from selfplay_raw import selfplay_raw
 from test_gpu_book import _engine_cfg
 from test_gpu_forced_playouts import _book, _entry_key
 from test_gpu_search import boards_tensor, gpu, no_act_tensors, play_config, stub_eval  # noqa: F401  (gpu: fixture)
@@ -304,49 +305,10 @@ def test_selfplay_games_carry_values(gpu, K, fast_sims):
 
 # ---- 5. off means off ------------------------------------------------------------------------------------------------------
 def _selfplay_raw(gpu, pc, seed, rounds, setup, with_q=False):
-    """test_gpu_forced_playouts._selfplay_raw with the setup AFTER the visit ring is on (the value record needs it): the
-    bytes of the finished-game records and of the visit entries as the device rings hand them out, the counters, and with
-    with_q the values cz_search_drain_visits_q hands out beside the entries."""
-    G = 32
-    s = gpu.S.Search(pc, G, seed=seed)
-    s.record_visits(True)
-    setup(s)
-    ev = stub_eval(gpu, SPEC)
-    s.start_selfplay(seed=seed, first_game_id=0)
-    recs, entries = [], []
-    cur = C.c_uint(0)
-
-    def drain():
-        n = C.c_int(0)
-        buf = np.zeros((4096, s.record_stride), dtype=np.uint8)
-        gpu.N.check(s.L.cz_search_drain_records(s.h, C.byref(cur), buf.ctypes.data, 4096, C.byref(n), s._stream()), "drain")
-        for i in range(n.value):
-            turns = int(buf[i, 4:8].view(np.int32)[0])
-            recs.append(buf[i, :16 + 2 * turns].tobytes())
-        gpu.N.check(s.L.cz_search_drain_visits(s.h, None, 0, C.byref(n), None, s._stream()), "count")
-        vbuf = np.zeros((max(1, n.value), gpu.S.VISIT_STRIDE), dtype=np.uint8)
-        qbuf = np.zeros(max(1, n.value), dtype=np.float64)
-        if with_q:
-            gpu.N.check(s.L.cz_search_drain_visits_q(s.h, vbuf.ctypes.data, qbuf.ctypes.data, n.value, C.byref(n), None,
-                                                     s._stream()), "visits_q")
-        else:
-            gpu.N.check(s.L.cz_search_drain_visits(s.h, vbuf.ctypes.data, n.value, C.byref(n), None, s._stream()), "visits")
-        for i in range(n.value):
-            ne = int(vbuf[i, 6])
-            row = vbuf[i, :16 + 2 * ne].tobytes() + vbuf[i, 16 + 256:16 + 256 + 4 * ne].tobytes()
-            entries.append((row, qbuf[i:i + 1].tobytes()) if with_q else row)
-    for r in range(rounds):
-        s.round()
-        p, v = ev(s.planes)
-        s.policy.copy_(p)
-        s.value.copy_(v)
-        if r % 16 == 15:                                    # (before either ring can fill)
-            drain()
-    drain()
-    ctr = s.counters()
-    s.close()
-    assert ctr["visits_dropped"] == 0
-    return sorted(recs), sorted(entries), ctr
+    """selfplay_raw with the setup AFTER the visit ring is on (the value record needs it); the entries as their rows, with
+    with_q as (row, the value cz_search_drain_visits_q hands out beside it)."""
+    recs, entries, ctr = selfplay_raw(gpu, pc, seed, rounds, 32, setup_after=setup, drain="q" if with_q else "plain")
+    return recs, [(row, q) if with_q else row for row, q, _ in entries], ctr
 
 
 @pytest.mark.parametrize("K", [1, 8])

@@ -22,6 +22,7 @@ import forced_playouts_oracle as fo
 import stub_net
 import surprise_oracle as so
 from oracle import xq_oracle as xo
+from selfplay_raw import selfplay_raw
 from test_gpu_book import _engine_cfg
 from test_gpu_forced_playouts import _entry_key
 from test_gpu_q_record import _games_with_q, _play
@@ -292,53 +293,11 @@ def test_selfplay_games_carry_the_oracles_surprise(gpu, k):
 
 
 # ---- 4. off means off, the older drains, the full ring ---------------------------------------------------------------------
-def _selfplay_raw(gpu, pc, seed, rounds, setup, drain="q", capacity=0, G=16):
-    """The bytes of the finished-game records and of the visit entries as the device rings hand them out through the entry
-    point `drain` ("plain": cz_search_drain_visits, "q": ..._q, "qs": ..._qs, "s": ..._qs with q_buf NULL), the counters."""
-    s = gpu.S.Search(pc, G, seed=seed)
-    s.record_visits(True, capacity=capacity)
-    s.set_playout_cap(4, 0.5)
-    setup(s)
-    ev = stub_eval(gpu, SPEC)
-    s.start_selfplay(seed=seed, first_game_id=0)
-    recs, entries = [], []
-    cur = C.c_uint(0)
-
-    def pull():
-        n = C.c_int(0)
-        buf = np.zeros((4096, s.record_stride), dtype=np.uint8)
-        gpu.N.check(s.L.cz_search_drain_records(s.h, C.byref(cur), buf.ctypes.data, 4096, C.byref(n), s._stream()), "drain")
-        for i in range(n.value):
-            turns = int(buf[i, 4:8].view(np.int32)[0])
-            recs.append(buf[i, :16 + 2 * turns].tobytes())
-        gpu.N.check(s.L.cz_search_drain_visits(s.h, None, 0, C.byref(n), None, s._stream()), "count")
-        vbuf = np.zeros((max(1, n.value), gpu.S.VISIT_STRIDE), dtype=np.uint8)
-        qbuf = np.full(max(1, n.value), -7.0, dtype=np.float64)
-        sbuf = np.full(max(1, n.value), -7.0, dtype=np.float64)
-        st = s._stream()
-        if drain == "plain":
-            gpu.N.check(s.L.cz_search_drain_visits(s.h, vbuf.ctypes.data, n.value, C.byref(n), None, st), "visits")
-        elif drain == "q":
-            gpu.N.check(s.L.cz_search_drain_visits_q(s.h, vbuf.ctypes.data, qbuf.ctypes.data, n.value, C.byref(n), None, st),
-                        "visits_q")
-        else:
-            gpu.N.check(s.L.cz_search_drain_visits_qs(s.h, vbuf.ctypes.data, qbuf.ctypes.data if drain == "qs" else None,
-                                                      sbuf.ctypes.data, n.value, C.byref(n), None, st), "visits_qs")
-        for i in range(n.value):
-            ne = int(vbuf[i, 6])
-            row = vbuf[i, :16 + 2 * ne].tobytes() + vbuf[i, 16 + 256:16 + 256 + 4 * ne].tobytes()
-            entries.append((row, qbuf[i:i + 1].tobytes(), sbuf[i:i + 1].tobytes()))
-    for r in range(rounds):
-        s.round()
-        p, v = ev(s.planes)
-        s.policy.copy_(p)
-        s.value.copy_(v)
-        if r % 16 == 15:
-            pull()
-    pull()
-    ctr = s.counters()
-    s.close()
-    return sorted(recs), sorted(entries), ctr
+def _selfplay_raw(gpu, pc, seed, rounds, setup, drain="q", capacity=0, G=16, before=None):
+    """selfplay_raw with the playout cap (4, 0.5) and `setup` AFTER the visit ring is on (`before`: ahead of it); entries
+    (row, q bytes, s bytes), -7.0 where the drain writes none; a ring of `capacity` may drop entries."""
+    return selfplay_raw(gpu, pc, seed, rounds, G, setup_before=before, setup_after=setup, capacity=capacity,
+                        playout_cap=(4, 0.5), drain=drain, fill=-7.0, no_drops=False)
 
 
 def _check_raw_surprises(recs, entries):
@@ -400,6 +359,33 @@ def test_surprise_off_leaves_every_record_entry_value_and_counter(gpu):
     assert set(vis) <= set(vis_qs)
     checked, with_s = _check_raw_surprises(recs, vis)
     assert checked > len(vis) // 2 and with_s > 0
+
+
+@pytest.mark.parametrize("k", [0.0, 2.0])
+def test_a_record_that_is_off_never_changes_the_others(gpu, k):
+    """Values and surprise on against values only, surprise only and neither, with pruning (k = 2) as well: the records,
+    the entries, the values, the surprises and the counters are the same bytes wherever two runs both have them."""
+    pc = play_config(simulation_num_per_move=16, search_threads=4, tau_decay_rate=0.9, max_game_length=8,
+                     enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
+
+    def run(values, surprise, drain):
+        def setup(s):
+            s.set_forced_playouts(k)
+            s.record_values(values)
+            s.record_surprise(surprise)
+        recs, vis, ctr = _selfplay_raw(gpu, pc, 31, 240, setup, drain=drain)
+        assert ctr["visits_dropped"] == 0
+        return recs, vis, ctr
+    recs, vis, ctr = run(True, True, "qs")
+    assert len(recs) >= 16 and len(vis) > len(recs)
+    assert len({q for _, q, _ in vis}) > 8 and len({sb for _, _, sb in vis}) > 8
+    assert any(row[7] & gpu.S.VISIT_PRUNED for row, _, _ in vis) == (k > 0)
+    recs_q, vis_q, ctr_q = run(True, False, "q")
+    assert recs_q == recs and ctr_q == ctr and [(row, q) for row, q, _ in vis_q] == [(row, q) for row, q, _ in vis]
+    recs_s, vis_s, ctr_s = run(False, True, "s")
+    assert recs_s == recs and ctr_s == ctr and [(row, sb) for row, _, sb in vis_s] == [(row, sb) for row, _, sb in vis]
+    recs_p, vis_p, ctr_p = run(False, False, "plain")
+    assert recs_p == recs and ctr_p == ctr and [row for row, _, _ in vis_p] == [row for row, _, _ in vis]
 
 
 # ---- 5. the loss kernel -----------------------------------------------------------------------------------------------------
