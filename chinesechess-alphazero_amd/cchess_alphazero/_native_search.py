@@ -92,6 +92,7 @@ def declare(L):
         "cz_search_drain_visits_qs": [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
         "cz_search_root_surprise": [vp, vp, vp],
         "cz_root_surprise": [vp, vp, vp, vp, i32, vp, vp],
+        "cz_search_set_leaf_mirror": [vp, d, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -193,6 +194,8 @@ class Search:
         self._visits = {}                      # game id -> [(ply, raw entry)] of games not finished yet
         self._raw_visits = []                  # fetched entries not yet sorted by game (pull_visits(defer=True))
         self._visits_dropped = 0
+        self.leaf_mirror = 0.0                 # set_leaf_mirror(): the rate at which a new leaf is evaluated mirrored
+        self.mirrored = None                   # set_leaf_mirror(flags=True): [slots] uint8, 1 = the slot's leaf is mirrored
 
     # -- lifetime --
     def close(self):
@@ -303,6 +306,21 @@ class Search:
         _native.check(self.L.cz_search_set_forced_playouts(self.h, float(k), self._stream()),
                       "cz_search_set_forced_playouts")
         self.forced_k = float(k)
+
+    def set_leaf_mirror(self, rate=0.0, flags=False):
+        """Random leaf mirror (cz_search_set_leaf_mirror; include/czero.h has the frames and the coin): a new leaf is written
+        to its queue slot as the left-right mirror image of its position with probability `rate`, and its policy row is then
+        read in the mirrored frame (column _native.label_mirror()[a] for move a); the value is taken as it is.  The plain
+        network needs nothing more.  flags=True keeps self.mirrored ([slots] uint8 on the device, 1 = the slot's leaf was
+        written mirrored) for an evaluator that has to know, and for counting the mirrored share; once allocated it stays.
+        rate 0 switches it off.  Both modes; it may be called between rounds, and before a graph capture."""
+        import torch
+        if flags and self.mirrored is None:
+            self.mirrored = torch.zeros((self.slots,), dtype=torch.uint8, device=self.device)
+        ptr = C.c_void_p(self.mirrored.data_ptr()) if self.mirrored is not None else None
+        _native.check(self.L.cz_search_set_leaf_mirror(self.h, float(rate), ptr, self._stream()),
+                      "cz_search_set_leaf_mirror")
+        self.leaf_mirror = float(rate)
 
     def record_values(self, on=True):
         """Self-play: every visit entry comes with the root's search value q (cz_search_record_values; include/czero.h has

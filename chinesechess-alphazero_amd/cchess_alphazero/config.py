@@ -106,6 +106,9 @@ class EngineConfig(_Section):
                          record_surprise=False,   # play records carry each recorded ply's policy surprise (run.py self
                                                   # --record-surprise, needs record_visits): items [move, value, pi,
                                                   # weight, q or None, s]
+                         leaf_mirror=0.0,         # random leaf mirror (run.py self / eval --leaf-mirror P): a new leaf is shown to
+                                                  # the network as its left-right mirror image with probability P, its policy
+                                                  # row read back through the label mirror (cz_search_set_leaf_mirror); 0 = off
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -42,7 +42,7 @@ class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
-                 full_rate=None, forced_playouts=None, record_q=None, record_surprise=None):
+                 full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -61,7 +61,10 @@ class SelfPlayEngine:
         record_visits): drain()'s items become [move, value, pi or None, weight, q] (cz_search_record_values).
         record_surprise: every ply with a visit entry records its policy surprise s, the Kullback-Leibler divergence of
         the recorded counts from the root's priors (None = config.engine.record_surprise; needs record_visits): drain()'s
-        items become [move, value, pi or None, weight, q or None, s] (cz_search_record_surprise)."""
+        items become [move, value, pi or None, weight, q or None, s] (cz_search_record_surprise).
+        leaf_mirror: the rate at which the search shows a new leaf to the network as its left-right mirror image (None =
+        config.engine.leaf_mirror; 0 = off), reading that leaf's policy row back through the label mirror
+        (cz_search_set_leaf_mirror).  The network and the records need nothing: rows and moves stay in their own frames."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -137,6 +140,11 @@ class SelfPlayEngine:
             raise ValueError("record_surprise needs record_visits: the surprises ride beside the visit entries")
         if self.record_surprise:                               # likewise
             self.search.record_surprise(True)
+        self.leaf_mirror = float(getattr(ec, "leaf_mirror", 0.0) if leaf_mirror is None else leaf_mirror)
+        if not 0.0 <= self.leaf_mirror <= 1.0:
+            raise ValueError(f"leaf_mirror {self.leaf_mirror}: expected 0 <= P <= 1")
+        if self.leaf_mirror:                                   # likewise
+            self.search.set_leaf_mirror(self.leaf_mirror)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -199,7 +207,9 @@ class SelfPlayEngine:
         playouts; the positions a search actually asks about are more tactical).  Takes up to n of the positions the last round
         asked about -- the compact queue's rows q_rows[:q_count]; slots that were never written (empty boards) are dropped --,
         evaluates the float64 reference and the running network on them and returns measure_against_reference's figures + `ok`
-        (within_guard: policy / value within GUARD_TOL, logits within LOGIT_TOL) + `positions`.  A failing audit is logged; the
+        (within_guard: policy / value within GUARD_TOL, logits within LOGIT_TOL) + `positions`.  With a leaf mirror
+        (leaf_mirror) some of those rows hold mirrored positions: both networks are given the same rows, so the comparison
+        needs no flags.  A failing audit is logged; the
         caller decides (worker/self_play.py asks for the next more exact arithmetic and rebuilds the network through the
         load-time guard on its standard calibration set)."""
         from cchess_alphazero.agent.model import measure_against_reference, reference_forward_f64, within_guard

@@ -64,6 +64,11 @@ _FLAGS = [
                                help="(opt) policy surprise weighting: within a game, the share A of the training weight goes "
                                     "to the rows in proportion to their recorded surprise (0 <= A <= 1; 0 = uniform, the "
                                     "reference; KataGo uses 0.5)")),
+    ("--leaf-mirror", dict(type=float, default=0.0, metavar="P",
+                           help="(self, eval) random leaf mirror: the search shows every new leaf to the network as its "
+                                "left-right mirror image with probability P and reads the policy back through the label "
+                                "mirror, so that the network's wing bias averages out of the search (0 = off; 0.5 = a fair "
+                                "coin)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -129,6 +134,9 @@ def build_config(args):
     if not 0.0 <= args.surprise_weight <= 1.0:
         raise SystemExit(f"--surprise-weight {args.surprise_weight}: expected 0 <= A <= 1")
     config.trainer.surprise_weight = args.surprise_weight
+    if not 0.0 <= args.leaf_mirror <= 1.0:                  # (false for NaN too)
+        raise SystemExit(f"--leaf-mirror {args.leaf_mirror}: expected 0 <= P <= 1")
+    engine.leaf_mirror = args.leaf_mirror
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -95,6 +95,8 @@ class EvaluateWorker:
         self.evaluators = evaluators
         self.dtype = dtype
         self.seed = seed
+        # random leaf mirror of both models' searches (run.py eval --leaf-mirror P, cz_search_set_leaf_mirror); 0 = off
+        self.leaf_mirror = float(getattr(getattr(config, "engine", None), "leaf_mirror", 0.0) or 0.0)
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -155,6 +157,9 @@ class EvaluateWorker:
         G = len(idx)
         searches = [Search(pc, G, planes_dtype=self.dtype, evaluate=getattr(self.config.opts, "evaluate", False),
                            seed=self.seed + k, sims_per_round=sims_per_round) for k in range(2)]
+        if self.leaf_mirror:                                   # (before any round, and before the compact form's graph capture)
+            for s in searches:
+                s.set_leaf_mirror(self.leaf_mirror)
 
         def counters_now():
             c = [s.counters() for s in searches]

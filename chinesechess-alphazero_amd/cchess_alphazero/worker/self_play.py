@@ -102,6 +102,9 @@ class SelfPlayWorker:
         if self.engine.forced_playouts:
             logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
                         f"the recorded visit counts are pruned (policy target pruning)")
+        if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
+            logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
+                        f"mirror image with probability {self.engine.leaf_mirror}")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:

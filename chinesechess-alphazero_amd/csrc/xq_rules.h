@@ -434,15 +434,16 @@ XQ_D void wave_encode(const int8_t* b, void* __restrict__ out)
 // Same planes through a per-board code row: codes[pos] = channel (0..13) of the piece on the square that plane
 // position pos = i*9 + j shows (row i of the planes is y = 9 - i), 0xFF for an empty square.  One LDS byte write
 // per square, then each output element is a byte compare instead of two divisions and a board lookup.
+// `mirror`: the planes (and the code row) of the left-right mirror image, file x -> 8 - x; b itself is only read.
 template <int DT>
-XQ_D void wave_encode_codes(const int8_t* b, uint8_t* codes, void* __restrict__ out)
+XQ_D void wave_encode_codes(const int8_t* b, uint8_t* codes, void* __restrict__ out, bool mirror = false)
 {
     const int lane = lane_id();
     wave_sync();
     for (int s = lane; s < NSQ; s += 64) {
         const int p = b[s];
         const int y = s / 9, x = s - y * 9;
-        codes[(9 - y) * 9 + x] = (uint8_t)(p == 0 ? 0xFF : (p > 0 ? p - 1 : 6 - p));
+        codes[(9 - y) * 9 + (mirror ? 8 - x : x)] = (uint8_t)(p == 0 ? 0xFF : (p > 0 ? p - 1 : 6 - p));
     }
     wave_sync();
     for (int q = lane; q < 315; q += 64) {

@@ -38,7 +38,9 @@ constexpr int CHILD_TERM_LOSS = -3;    // done() == (True, -1)
 enum SimState : uint8_t { SIM_IDLE = 0, SIM_LEAF = 1, SIM_PARKED = 2,
                           SIM_DEFERRED = 3 };   // ended on a terminal / repeated position; backed up when the phase's descents are over (never outlives a launch)
 
-enum NodeFlag : uint32_t { NODE_WAITING = 1u << 8 };    // low 8 bits of node_meta = move count
+enum NodeFlag : uint32_t { NODE_WAITING = 1u << 8,      // low 8 bits of node_meta = move count
+                           NODE_MIRRORED = 1u << 9 };   // set beside NODE_WAITING: the leaf is evaluated in its mirror image
+                                                        // (cz_search_set_leaf_mirror); cleared with it when the priors attach
 
 enum GameMode : int { MODE_EXTERNAL = 0, MODE_SELFPLAY = 1 };
 
@@ -101,12 +103,16 @@ struct SearchParams {
     // forced playouts + policy target pruning (cz_search_set_forced_playouts); read by k_sim's root context, emit_visits
     // and k_root_records only
     double forced_k;        // 0 = off; a tried root child is visited at least sqrt(forced_k * p * N) times
+    // random leaf mirror (cz_search_set_leaf_mirror); read through leaf_coin only
+    double leaf_mirror;     // 0 = off; a new leaf is evaluated mirrored iff philox_uniform(seed, key, 3, turns << 32 | node id) < leaf_mirror
 };
 
 struct SearchBuffers {
     // ---- optional caller-owned output (cz_search_leaf_masks): one 96-word occupancy board per queue slot ----
     uint32_t* leaf_masks;   // [G*K][96] or NULL
     int leaf_planes_off;    // cz_search_leaf_planes(0): with leaf_masks set, the planes of a new leaf are NOT written
+    // ---- optional caller-owned output (cz_search_set_leaf_mirror): 1 = the slot's leaf was written mirrored ----
+    uint8_t* leaf_flags;    // [G*K] or NULL
     // ---- trees ----
     char* pool;             // [n_chunks] x 1 MiB
     uint32_t* pool_ring;    // [n_chunks] free chunk numbers; entries [head, tail) are free

@@ -28,6 +28,7 @@
 #include "xq_rules.h"
 #include "xq_search.h"
 #include "xq_noise.h"
+#include "xq_mirror.h"
 #include "../../include/czero.h"
 
 using namespace xq;
@@ -169,6 +170,24 @@ XQ_D double philox_uniform(uint64_t seed, uint32_t game_id, uint32_t stream, uin
     return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) / 9007199254740992.0;
 }
 
+// ---- random leaf mirror (cz_search_set_leaf_mirror) ---------------------------------------------
+// M(label) in one read (the attach side sits in a chain of dependent loads: leaf_pre_b).  Built at compile time from
+// label_of / lab_ft, the tables cz_label_mirror reads.
+static __device__ const MirrorTab d_mirror = make_mirror_tab();
+XQ_D int row_col(int label, bool mirrored) { return mirrored ? (int)d_mirror.m[label] : label; }
+
+// Is the new leaf `id` (its node record's id: no two nodes of a tree share one) evaluated in its mirror image?  Stream 3
+// of the generator (0: the per-game lotteries, 1: the move choice, 2: the playout cap), keyed like the root noise by game
+// id and game slot, draw (turns of the root << 32 | id); rates 0 and 1 decide without a draw.  Wave-uniform.
+XQ_D bool leaf_coin(const SearchParams& P, const SearchBuffers& B, int g, uint32_t id)
+{
+    if (!(P.leaf_mirror > 0.0)) return false;
+    if (P.leaf_mirror >= 1.0) return true;
+    const uint32_t key = uniu(B.g_game_id[g]) + (uint32_t)g * 2654435761u;
+    const uint64_t idx = ((uint64_t)uniu((uint32_t)B.g_turns[g]) << 32) | id;
+    return philox_uniform(P.seed, key, 3, idx) < P.leaf_mirror;
+}
+
 // (the root noise generator -- NoiseRng, gamma_draw, dirichlet0 -- lives in xq_noise.h: host + device, CPU-tested)
 
 // ---- packed keys and the transposition hash ----------------------------------------------------
@@ -307,9 +326,11 @@ XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float*
     const int nm = (int)(meta & 0xFF);
     float* pp = node_p(base);
     const uint16_t* pm = node_mv(base, nm);
+    // a mirrored leaf's row is in the mirrored frame: the entry of move a is column M(a); p[] and the moves stay as they are
+    const bool mir = (meta & NODE_MIRRORED) != 0u;
     float q0 = 0.0f, q1 = 0.0f;
-    if (lane < nm) q0 = prow[pm[lane]];
-    if (lane + 64 < nm) q1 = prow[pm[lane + 64]];
+    if (lane < nm) q0 = prow[row_col(pm[lane], mir)];
+    if (lane + 64 < nm) q1 = prow[row_col(pm[lane + 64], mir)];
     if (logits) logits_to_weights(q0, q1, nm);
     if (lane < nm) L.pr[lane] = q0;
     if (lane + 64 < nm) L.pr[lane + 64] = q1;
@@ -323,7 +344,7 @@ XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float*
     if (lane < nm) pp[lane] = L.pr[lane] / all_p;
     if (lane + 64 < nm) pp[lane + 64] = L.pr[lane + 64] / all_p;
     // p[j] is written and later read (select_edge) by the same lane, the header by lane 0: no global fence
-    if (lane == 0) store_meta(base, meta & ~(uint32_t)NODE_WAITING);
+    if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
     wave_sync();
 }
 
@@ -356,8 +377,9 @@ XQ_D void leaf_pre_b(LeafPre& lp, uint32_t meta, const float* __restrict__ prow)
     const int lane = lane_id();
     const int nm = (int)(meta & 0xFF);
     lp.p0 = 0.0f; lp.p1 = 0.0f;
-    if (lane < nm) lp.p0 = prow[lp.m0];
-    if (lane + 64 < nm) lp.p1 = prow[lp.m1];
+    const bool mir = (meta & NODE_MIRRORED) != 0u;             // (the row of a mirrored leaf: column M(label), one table read)
+    if (lane < nm) lp.p0 = prow[row_col(lp.m0, mir)];
+    if (lane + 64 < nm) lp.p1 = prow[row_col(lp.m1, mir)];
 }
 
 // `lp`: this leaf's prefetched labels / edge ids / row entries.  `next`: issued between this leaf's edge-statistics load and
@@ -388,7 +410,7 @@ XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS
     if (all_p == 0.0f) all_p = 1.0f;
     if (lane < nm) pp[lane] = p0 / all_p;
     if (lane + 64 < nm) pp[lane + 64] = p1 / all_p;
-    if (lane == 0) store_meta(base, meta & ~(uint32_t)NODE_WAITING);
+    if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
     // update_tree (player.py:357-366): lane i = level i
     if (lane < depth) {
         const double vi = ((depth - lane) & 1) ? -v : v;
@@ -570,33 +592,38 @@ struct RoundIO {
     int in_planes;
     uint32_t* masks;       // cz_search_leaf_masks: [slots][96] occupancy boards, or NULL
     bool planes_off;       // cz_search_leaf_planes(0): only the occupancy boards are written
+    uint8_t* flags;        // cz_search_set_leaf_mirror: [slots] 1 = the slot's leaf was written mirrored, or NULL
 };
 
 // occupancy-board word of plane position pos (row i = pos / 9 of the planes shows rank y = 9 - i): bit `shift` + plane of the
 // piece on that square, 0 for an empty square or pos >= 90 (state_to_planes, static_env.py:137-156)
-XQ_D uint32_t mask_word(const int8_t* b, int pos, int shift)
+// `mirror`: the word of the mirror image, which shows file 8 - j at column j.
+XQ_D uint32_t mask_word(const int8_t* b, int pos, int shift, bool mirror)
 {
     if (pos >= NSQ) return 0u;
     const int i = pos / 9, j = pos - i * 9;
-    const int p = b[(9 - i) * 9 + j];
+    const int p = b[(9 - i) * 9 + (mirror ? 8 - j : j)];
     return p == 0 ? 0u : 1u << (shift + (p > 0 ? p - 1 : 6 - p));
 }
 
-XQ_D void encode_block(int dtype, const int8_t* b, uint8_t* codes, char* out)
+XQ_D void encode_block(int dtype, const int8_t* b, uint8_t* codes, char* out, bool mirror)
 {
     switch (dtype) {
-    case CZ_F32: wave_encode_codes<0>(b, codes, out); break;
-    case CZ_F16: wave_encode_codes<1>(b, codes, out); break;
-    case CZ_BF16: wave_encode_codes<2>(b, codes, out); break;
-    default: wave_encode_codes<3>(b, codes, out); break;
+    case CZ_F32: wave_encode_codes<0>(b, codes, out, mirror); break;
+    case CZ_F16: wave_encode_codes<1>(b, codes, out, mirror); break;
+    case CZ_BF16: wave_encode_codes<2>(b, codes, out, mirror); break;
+    default: wave_encode_codes<3>(b, codes, out, mirror); break;
     }
 }
 
 // the leaf's input planes into its queue slot: 14 planes (state_to_planes), or 28 with the position two plies
-// earlier (`prev`, NULL = none: zeros) as the second block (state_history_to_planes, static_env.py:158-194)
+// earlier (`prev`, NULL = none: zeros) as the second block (state_history_to_planes, static_env.py:158-194).
+// `mirror` (wave-uniform): the slot holds the mirror image of both positions instead, in all its forms, and says so in the
+// slot's flag.  The mirror is in the index the boards are read with: b and prev are only read, the caller goes on using them.
 template <bool HIST>
-XQ_D void write_planes(const RoundIO& io, const int8_t* b, uint8_t* codes, size_t slot, const int8_t* prev)
+XQ_D void write_planes(const RoundIO& io, const int8_t* b, uint8_t* codes, size_t slot, const int8_t* prev, bool mirror)
 {
+    if (io.flags && lane_id() == 0) io.flags[slot] = mirror ? (uint8_t)1 : (uint8_t)0;
     const size_t esz = io.planes_dtype == CZ_F32 ? 4 : (io.planes_dtype == CZ_U8 ? 1 : 2);
     char* out = (char*)io.planes + slot * (size_t)io.in_planes * 90 * esz;
     // (round 5) a caller whose network reads the occupancy boards alone (cz_input_resblock_m) switches the planes off
@@ -605,14 +632,14 @@ XQ_D void write_planes(const RoundIO& io, const int8_t* b, uint8_t* codes, size_
     if (only_masks) {
         // boards only: one LDS read and a shift per word, straight from the position(s) -- no code row, no encoder pass
         const int lane = lane_id();
-        uint32_t m0 = mask_word(b, lane, 0), m1 = mask_word(b, 64 + lane, 0);
-        if (HIST && prev) { m0 |= mask_word(prev, lane, 14); m1 |= mask_word(prev, 64 + lane, 14); }
+        uint32_t m0 = mask_word(b, lane, 0, mirror), m1 = mask_word(b, 64 + lane, 0, mirror);
+        if (HIST && prev) { m0 |= mask_word(prev, lane, 14, mirror); m1 |= mask_word(prev, 64 + lane, 14, mirror); }
         uint32_t* mo = io.masks + slot * 96;
         mo[lane] = m0;
         if (lane < 32) mo[64 + lane] = m1;
         return;
     }
-    encode_block(io.planes_dtype, b, codes, out);
+    encode_block(io.planes_dtype, b, codes, out, mirror);
     // the same position as an occupancy board (cz_search_leaf_masks): word pos = plane position i * 9 + j, bit c = plane c shows
     // a piece there -- `codes` holds exactly that channel per position after the encoder's pass
     const int lane = lane_id();
@@ -625,7 +652,7 @@ XQ_D void write_planes(const RoundIO& io, const int8_t* b, uint8_t* codes, size_
     if (HIST) {
         char* out2 = out + 1260 * esz;
         if (prev) {
-            encode_block(io.planes_dtype, prev, codes, out2);
+            encode_block(io.planes_dtype, prev, codes, out2, mirror);
             if (io.masks) {
                 const uint32_t c0 = codes[lane], c1 = lane < 26 ? codes[64 + lane] : 0xFFu;
                 m0 |= c0 == 0xFFu ? 0u : 1u << (14 + c0);
@@ -683,9 +710,10 @@ XQ_D uint32_t heap_alloc(Arena& ar, int granules)
 }
 
 // create a node for the position whose packed key is in L.key and whose ordered move list is in `ml` (nm moves);
-// returns the node id or -1 when the game's chunks (or its hash table) are full
+// returns the node id or -1 when the game's chunks (or its hash table) are full.  `mirrored`: the new leaf's coin
+// (leaf_coin), which the node carries in its header until its priors are attached.
 XQ_D int expand_node(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
-                     const MoveList& ml, int nm, int hash_slot, uint64_t h, Arena& ar)
+                     const MoveList& ml, int nm, int hash_slot, uint64_t h, Arena& ar, bool& mirrored)
 {
     const int lane = lane_id();
     nm = nm < MAXMOVES ? nm : MAXMOVES;
@@ -693,6 +721,7 @@ XQ_D int expand_node(const SearchParams& P, const SearchBuffers& B, const GameVi
     const uint32_t id = heap_alloc(ar, NODE_HDR_GRANULES + (6 * nm + 15) / 16);
     if (id == 0u) return -1;
     char* base = rec_ptr(gv, id);
+    mirrored = leaf_coin(P, B, gv.g, id);
     if (lane < KEY_WORDS) reinterpret_cast<uint32_t*>(base)[lane] = L.key[lane];
     float* pp = node_p(base);
     uint16_t* pm = node_mv(base, nm);
@@ -702,7 +731,7 @@ XQ_D int expand_node(const SearchParams& P, const SearchBuffers& B, const GameVi
     }
     if (lane == 0) {
         // sum_n = 1 (player.py:213), no statistics yet: they are allocated when the node is first selected from
-        *reinterpret_cast<int4*>(base + NODE_OFF_HDR) = make_int4(1, (int)((uint32_t)nm | NODE_WAITING), 0, 0);
+        *reinterpret_cast<int4*>(base + NODE_OFF_HDR) = make_int4(1, (int)((uint32_t)nm | NODE_WAITING | (mirrored ? (uint32_t)NODE_MIRRORED : 0u)), 0, 0);
         gv.hash[hash_slot] = ((uint64_t)((uint32_t)(h >> 32) | 1u) << 32) | (uint32_t)(id + 1u);
     }
     ar.ncount += 1;
@@ -744,13 +773,15 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         const uint64_t h = pack_key(L.r.bd[1], L.key);
         int slot;
         int idx = hash_lookup(gv, P, L.key, h, &slot);
-        if (idx < 0) idx = expand_node(P, B, gv, L, L.r.ml[0], nm, slot, h, ar);
+        bool mir = false;
+        if (idx < 0) idx = expand_node(P, B, gv, L, L.r.ml[0], nm, slot, h, ar, mir);
+        else mir = (load_hdr(rec_ptr(gv, (uint32_t)idx)).meta & NODE_MIRRORED) != 0u;   // (the frame its attach will read)
         if (idx < 0) { count(gv, CT_OVERFLOW_SIMS); backup(P, gv, L, 0, 0.0); sim_finish(gv, sim, active); return; }
         if (lane == 0) {
             B.g_root[g] = idx;
             gv.s_state[sim] = SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = 0;
         }
-        write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, 0) : nullptr);
+        write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, 0) : nullptr, mir);
         wave_sync();
         return;
     }
@@ -856,7 +887,8 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
                     if (lane == owner) ep->child = idx;
                     child = idx;
                 } else {
-                    idx = expand_node(P, B, gv, L, L.r.ml[0], d.nmoves, slot, h, ar);     // player.py:211-221
+                    bool mir;
+                    idx = expand_node(P, B, gv, L, L.r.ml[0], d.nmoves, slot, h, ar, mir);     // player.py:211-221
                     if (idx < 0) {
                         count(gv, CT_OVERFLOW_SIMS);
                         backup(P, gv, L, depth, 0.0);
@@ -865,7 +897,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
                     }
                     if (lane == owner) ep->child = idx;
                     if (lane == 0) { gv.s_state[sim] = SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = depth; }
-                    write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, depth) : nullptr);
+                    write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, depth) : nullptr, mir);
                     wave_sync();
                     PROF(CT_CYC_EXPAND);
                     return;
@@ -1645,7 +1677,7 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
 #ifdef CZ_SIM_PROFILE
     const long long prof_k0 = clock64();
 #endif
-    const RoundIO io{planes, P.planes_dtype, P.in_planes, B.leaf_masks, B.leaf_planes_off != 0};
+    const RoundIO io{planes, P.planes_dtype, P.in_planes, B.leaf_masks, B.leaf_planes_off != 0, B.leaf_flags};
     int active = uni(B.g_active[g]);
     Arena ar{uniu(B.g_heap_top[g]), uni(B.g_nchunks[g]), uni(B.g_node_count[g])};
     // (no root noise on a fast ply of the playout cap: k_noise drew no rows for it)
@@ -2704,6 +2736,25 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_forced_playouts", e);
     s->P.forced_k = k;
+    return CZ_OK;
+}
+
+int cz_search_set_leaf_mirror(cz_search* s, double rate, uint8_t* flags_or_null, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_leaf_mirror: null handle");
+    if (!(rate >= 0.0 && rate <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_leaf_mirror: rate outside [0, 1]");   // (NaN too)
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);   // launches in flight keep the rate and the flag array they started with
+    if (e == hipSuccess && flags_or_null && flags_or_null != s->B.leaf_flags) {
+        // a new array starts as the old one (the leaves in flight keep their flags), or as zeros where there was none
+        const size_t n = (size_t)s->P.G * (size_t)s->P.K;
+        e = s->B.leaf_flags ? hipMemcpyAsync(flags_or_null, s->B.leaf_flags, n, hipMemcpyDeviceToDevice, st)
+                            : hipMemsetAsync(flags_or_null, 0, n, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) return serr_hip("cz_search_set_leaf_mirror", e);
+    s->P.leaf_mirror = rate;
+    s->B.leaf_flags = flags_or_null;
     return CZ_OK;
 }
 

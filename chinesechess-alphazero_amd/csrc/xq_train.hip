@@ -18,6 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "xq_rules.h"
+#include "xq_mirror.h"
 #include "../../include/czero.h"
 
 using namespace xq;
@@ -58,33 +59,6 @@ XQ_D double wave_sum_f64(double v)
 XQ_D void zero_planes(float* __restrict__ out)   // 14 planes: 315 float4
 {
     for (int q = lane_id(); q < 315; q += 64) reinterpret_cast<float4*>(out)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-XQ_D int mirror_sq(int s)       // (x, y) -> (8 - x, y)
-{
-    const int y = s / 9;
-    return s + 8 - 2 * (s - y * 9);
-}
-
-// The board of the mirrored position, in place: every lane reads its one or two source squares, then writes.
-XQ_D void mirror_board(int8_t* b)
-{
-    const int lane = lane_id();
-    const int8_t p0 = b[mirror_sq(lane)];
-    const int8_t p1 = lane < 26 ? b[mirror_sq(lane + 64)] : (int8_t)0;
-    wave_sync();
-    b[lane] = p0;
-    if (lane < 26) b[lane + 64] = p1;
-    wave_sync();
-}
-
-// M(label): from what the device already holds (lab_ft -> mirror both squares -> label_of) instead of a third table; the
-// label set is closed under the mirror (cz_label_mirror, tests/test_mirror_cpu.py), and a row has a few dozen labels at
-// most, so the two dependent table reads are not worth 4 KB more constant data.  label < NLABELS.
-XQ_D int mirror_label(int label)
-{
-    const int ft = label_ft(label);
-    return label_of(mirror_sq(ft >> 8), mirror_sq(ft & 0xFF));
 }
 
 constexpr int LOSS_COLS = (NLABELS + 63) / 64;       // 33 logits per lane

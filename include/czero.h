@@ -251,6 +251,42 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
                            const uint8_t* n_edges, int rows, double c_puct, double k,
                            int32_t* out_n, int32_t* out_raw_total, void* stream);
 
+/* Random leaf mirror (AlphaGo Zero's random symmetry at every evaluation, as Leela Zero and KataGo keep it; the
+ * reference has no such option).  The left-right mirror image of a Xiangqi position (file x <-> 8 - x) is a symmetry of
+ * the rules but not of a trained network; with rate > 0 every NEW leaf is shown to the network either as it is or in its
+ * mirror image, so that over the leaves of a search the network's wing bias averages out of the visit counts, the
+ * recorded targets, the search values and the surprise weights.
+ *
+ * THE COIN.  When a leaf is expanded (a new node record, the root of an empty tree included) it is evaluated mirrored
+ * iff philox_uniform(seed, key, stream 3, index) < rate, with key = game_id + slot * 2654435761 (the key of the root
+ * noise; game_id is 0 in external mode until a self-play run set it) and index = (turns of the current root << 32) | the
+ * new node's record id.  Record ids are the tree's own addresses: no two nodes of a game's tree share one, so no two
+ * leaves of a tree share a draw.  Streams 0, 1 and 2 stay the per-game lotteries, the move choice and the playout cap.
+ * rate <= 0 and rate >= 1 decide without a draw.  The decision travels in the node's header beside its waiting flag
+ * and is dropped when the priors are attached: nothing else ever sees it, and a leaf in flight keeps the decision it was
+ * expanded with whatever is set afterwards.
+ *
+ * FRAMES.  A mirrored leaf's queue slot holds the MIRROR IMAGE of the position in every form the slot has: the input
+ * planes in every planes_dtype, the second block of a 28-plane input (the earlier position mirrored too; a missing one
+ * stays zeros) and the occupancy board of cz_search_leaf_masks, with or without the planes.  The network's policy row
+ * for that slot is then in the mirrored frame: the search reads the entry of move `a` at column cz_label_mirror[a].
+ * The value is taken as it is.  Priors, their float32 summation order (move order), the stored p[], the moves and every
+ * record stay in the un-mirrored frame; a network that is exactly mirror-equivariant gives the same search bit for bit
+ * at every rate.
+ *
+ * FLAGS.  flags_or_null: DEVICE uint8 [n_games * sims_per_round] owned by the caller, or NULL.  Whenever a leaf is
+ * written to queue slot game * sims_per_round + sim, flags[slot] is written with it: 1 mirrored, 0 not (a compact queue
+ * of cz_search_round_q names the slot in q_rows).  An evaluator that is not the plain network -- a test's stand-in, a
+ * cache keyed by position -- needs it; the share of mirrored leaves is read from it, no counter is added.  A new array
+ * starts as a copy of the previous one, or as zeros when there was none.
+ *
+ * rate = 0 (the state after cz_search_create) switches it off: nothing is drawn and every kernel produces the bits it
+ * produced before.  Both modes; cz_search_set_roots and cz_search_start_selfplay keep the setting.  It may be called
+ * between rounds; call it before a graph capture (the captured launches hold the rate and the array's address), like
+ * cz_search_set_playout_cap; synchronises the stream.  CZ_ERR_ARG: s NULL, rate NaN or outside [0, 1] -- the object
+ * keeps its setting. */
+int cz_search_set_leaf_mirror(cz_search* s, double rate, uint8_t* flags_or_null, void* stream);
+
 /* external mode (CChessPlayer.action): set the position to search for each game.  boards [G][90];
  * turns [G] or NULL; no_act [G][32] + n_no_act [G] or NULL (at most 32 banned moves per game); increase_temp / enable_resign [G] or NULL;
  * select_mask [G] or NULL (only games with a non-zero byte are touched).  Trees are kept (subtree reuse).

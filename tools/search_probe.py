@@ -4,7 +4,7 @@ the hash-stub network (tests/stub_net.py: microseconds per round instead of 30 m
 games in every phase, trees tens of thousands of nodes deep -- take seconds; then the search round is timed with HIP
 events over the next rounds (per-launch: mean / median / p99).  A/B tool for changes to csrc/xq_search.hip.
 
-    python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1]
+    python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1] [--leaf-mirror P]
 """
 import argparse
 import json
@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--compact", type=int, default=1)
     ap.add_argument("--games", type=int, default=4096)
     ap.add_argument("--masks-only", type=int, default=0, help="1: leaves written as occupancy boards only (cz_search_leaf_planes(0))")
+    ap.add_argument("--leaf-mirror", type=float, default=0.0, help="rate of the random leaf mirror (cz_search_set_leaf_mirror)")
     a = ap.parse_args()
     import types
     import stub_net
@@ -35,6 +36,8 @@ def main():
     if a.masks_only:
         s.leaf_masks(True)
         s.leaf_planes(False)
+    if a.leaf_mirror:
+        s.set_leaf_mirror(a.leaf_mirror, flags=True)
     s.start_selfplay(seed=20260923)
     planes_of = (lambda: s.queue_planes()) if a.masks_only else (lambda: s.planes)   # (the same planes either way: same trees)
 
@@ -78,6 +81,9 @@ def main():
            "search_round_ms": {"mean": sum(t) / len(t), "median": t[len(t) // 2], "p99": t[int(len(t) * 0.99)], "max": t[-1]},
            "mean_depth": c["sum_depth"] / max(1, c["sims"]), "plies": c["plies"], "games": c["games"],
            "tree_resets": c["tree_resets"], "nodes": m["nodes"], "tree_gb": m["tree_bytes"] / 1e9}
+    if a.leaf_mirror:                      # (of the slots as they stand: every slot has held a leaf by now)
+        out["leaf_mirror"] = a.leaf_mirror
+        out["mirrored_share_of_slots"] = float(s.mirrored.float().mean())
     if "cyc_select" in c:                  # CZ_SIM_PROFILE build: shader-clock cycles of wave time per section, per simulation
         n = max(1, c["sims"])
         out["cycles_per_sim"] = {k: c[k] / n for k in c if k.startswith("cyc_")}
