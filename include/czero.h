@@ -115,7 +115,8 @@ typedef struct cz_search_cfg {
                                         i.e. the tree of the longest game is kept whole (self_play.py:84,98-100) */
     int32_t pool_chunks;             /* tree memory shared by all games, in chunks of 1 MiB; 0 = what the games can use,
                                         at most 80 % of the device memory that is free at creation */
-    int32_t max_depth;               /* longest path of one simulation; 0 = 64, at most 128 */
+    int32_t max_depth;               /* longest path of one simulation: one that reaches an evaluated node with this many
+                                        edges behind it backs up 0 (counter depth_overflow); 0 = 128, at most 128 */
     int32_t max_game_length;         /* config.play.max_game_length (full moves) */
     int32_t planes_dtype;            /* CZ_F32 / CZ_F16 / CZ_BF16 / CZ_U8 */
     int32_t min_resign_turn;         /* config.play.min_resign_turn */

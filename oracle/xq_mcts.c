@@ -134,6 +134,7 @@ void xqo_player_set_history(xqo_player *p, int kind, const int8_t prev[90])
     if (kind == 1 && prev) memcpy(p->hist_prev, prev, 90);
 }
 int xqo_player_tree_size(const xqo_player *p) { return p->n_nodes; }
+void xqo_player_set_sims(xqo_player *p, int sims) { p->cfg.simulation_num_per_move = sims; }
 
 /* ---- Dirichlet(alpha * 1_n)[0] ~ Beta(alpha, alpha (n-1)) (player.py:304).  The reference draws
  * from NumPy's global RNG, which cannot be bit-matched; this is a distributional restatement. */
@@ -237,6 +238,13 @@ static void backup(xqo_player *p, Sim *s, double v)
     s->active = 0;
 }
 
+/* the depth at which a simulation is cut: cfg.max_depth, 0 = only the size of the path arrays */
+static int depth_limit(const xqo_player *p)
+{
+    const int d = p->cfg.max_depth;
+    return d > 0 && d < MAXDEPTH ? d : MAXDEPTH;
+}
+
 /* ---- MCTS_search: player.py:198-260 (one descent until the sim stops) -------- */
 static void park(Node *node, int idx)
 {
@@ -280,6 +288,14 @@ static void descend(xqo_player *p, int idx)
         }
         node = tree_find(p, s->board);
         if (!node) {                                                  /* :211-221 expand */
+            /* not in the reference: the engine's tree memory is finite.  An expansion refused because the tree already
+             * holds max_nodes nodes ends the simulation with a value of 0 from where it stands -- the edge it just
+             * selected is in the path, so its virtual loss is returned (csrc/xq_search.hip run_sim: overflow_sims) */
+            if (p->cfg.max_nodes > 0 && p->n_nodes >= p->cfg.max_nodes) {
+                p->ctr.overflow_sims++;
+                backup(p, s, 0.0);
+                return;
+            }
             node = tree_insert(p, s->board);
             node->sum_n = 1;
             node->waiting = 1;
@@ -306,13 +322,23 @@ static void descend(xqo_player *p, int idx)
             p->ctr.parked++;
             return;
         }
+        /* not in the reference: the engine's depth limit (SearchParams.max_depth).  A simulation that arrives at an
+         * evaluated node with that many edges behind it is cut BEFORE it selects: it backs up 0 from its depth and
+         * touches nothing else, so every virtual loss it applied is returned (run_sim: depth_overflow) */
+        if (!p->cfg.cut_after_select && s->depth >= depth_limit(p)) {
+            p->ctr.depth_overflow++;
+            backup(p, s, 0.0);
+            return;
+        }
         e = select_edge(p, node);                                     /* :243 */
         if (e < 0) { backup(p, s, 0.0); return; }                     /* best_action None: cannot happen */
         node->sum_n += 1;                                             /* :245-252 */
         node->n[e] += vl;
         node->w[e] = node->w[e] - (double)vl;
         p->ctr.sum_edges_visited += (uint64_t)node->n_moves;
-        if (s->depth >= MAXDEPTH) { backup(p, s, 0.0); return; }
+        /* cut_after_select (tests only): the cut where this file had it before max_depth existed -- after sum_n and
+         * the virtual loss of the selected edge, which is not in the path and so never gets its virtual loss back */
+        if (s->depth >= depth_limit(p)) { p->ctr.depth_overflow++; backup(p, s, 0.0); return; }
         s->path_node[s->depth] = node;
         s->path_edge[s->depth] = e;
         s->depth++;

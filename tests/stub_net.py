@@ -7,6 +7,12 @@ so that "identical visit counts with the net stubbed to constants" can be checke
 hash stub:  h = mix64(salt + sum_{o: planes[o] != 0} mix64(o + 1))      (o over 14*90 or 28*90 elements)
             policy[a] = x^8 (three float32 squarings), x = ((mix64(h + (a+1)*GOLD) >> 40 & 0xFFFF) + 1) / 65536
             value     = ((mix64(h ^ C2) >> 40 & 0xFFFF) - 32768) / 32768
+peaked stub: the hash stub's policy followed by S more float32 squarings (x^(8 * 2^S)) and a CONSTANT value: a policy as
+            peaked as a trained network's, under which the search follows single lines to depths the hash stub never
+            reaches (past 64 plies at S = 8).  Before the first squaring and after each one, every entry below 2^-60 is set
+            to exactly 0: what survives is >= 2^-60, its square >= 2^-120 is a normal float32, so no result depends on how a
+            device treats subnormals.  Rows whose legal moves all get 0 occur (spread_priors: all_p == 0 -> 1).
+            NumPy and torch only; the oracle takes the NumPy version as a callable.
 Also: the counter-based uniform stream (Philox4x32-10) shared by the oracle and the engine.
 """
 import numpy as np
@@ -58,6 +64,22 @@ def hash_stub_numpy(planes, salt=0):
     return x.astype(np.float32), v.astype(np.float32)
 
 
+PEAK_FLOOR = np.float32(2.0 ** -60)
+
+
+def peaked_stub_numpy(planes, salt=0, squarings=8, value=0.0):
+    """planes [n,14|28,10,9] -> (policy float32 [n,2086], value float32 [n]); see the module text."""
+    x, _ = hash_stub_numpy(planes, salt)
+    tiny = np.finfo(np.float32).tiny
+    x = np.where(x < PEAK_FLOOR, np.float32(0.0), x)
+    for _ in range(int(squarings)):
+        x = x * x
+        assert x.dtype == np.float32 and not ((x != 0) & (x < tiny)).any()       # no subnormal can arise
+        x = np.where(x < PEAK_FLOOR, np.float32(0.0), x)
+    assert x.dtype == np.float32 and ((x == 0) | (x >= PEAK_FLOOR)).all()
+    return x, np.full((len(x),), np.float32(value), dtype=np.float32)
+
+
 def uniform_stub_numpy(planes, value=0.0):
     n = len(planes)
     return (np.full((n, N_LABELS), np.float32(1.0 / 2086.0), dtype=np.float32),
@@ -107,6 +129,28 @@ def hash_stub_torch(planes, salt=0):
     uv = (_mix64_torch(h ^ _s64(C2)) >> 40) & 0xFFFF
     v = (uv.to(torch.float32) - 32768.0) / 32768.0
     return x, v
+
+
+def peaked_stub_torch(planes, salt=0, squarings=8, value=0.0):
+    """peaked_stub_numpy on any device, bit for bit."""
+    import torch
+    x, _ = hash_stub_torch(planes, salt)
+    floor = float(PEAK_FLOOR)
+    zero = torch.zeros((), dtype=torch.float32, device=x.device)
+    x = torch.where(x < floor, zero, x)
+    for _ in range(int(squarings)):
+        x = x * x
+        x = torch.where(x < floor, zero, x)
+    return x, torch.full((x.shape[0],), float(np.float32(value)), dtype=torch.float32, device=x.device)
+
+
+def stub_numpy(spec):
+    """A stub spec (dict(kind=...)) as the callable planes -> (policy, value) that xq_oracle.Player accepts."""
+    if spec["kind"] == "peaked":
+        return lambda planes: peaked_stub_numpy(planes, spec["salt"], spec.get("squarings", 8), spec.get("value", 0.0))
+    if spec["kind"] == "uniform":
+        return lambda planes: uniform_stub_numpy(planes, spec.get("value", 0.0))
+    return lambda planes: hash_stub_numpy(planes, spec["salt"])
 
 
 # ---- pipe protocol of the reference (agent/api.py:37-74): send list[planes] -> recv list[(p, v)] ----

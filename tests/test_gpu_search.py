@@ -3,7 +3,9 @@ and against the golden vectors recorded from the reference's own CChessPlayer / 
 The network is stubbed by the exact-arithmetic stub of tests/stub_net.py (torch version on the GPU),
 so visit counts, W sums (float64, compared bit for bit) and priors (float32) must be identical.
 The game loops' rare endings (120 plies without a capture, no attacker left, three free repetitions, bans, the history
-scan past 64 plies): tests/test_gpu_endings.py, with tests/test_endings_oracle_cpu.py and tests/game_endings.py."""
+scan past 64 plies): tests/test_gpu_endings.py, with tests/test_endings_oracle_cpu.py and tests/game_endings.py.
+Search paths longer than 64 plies and the counted cut-offs (depth_overflow, overflow_sims): tests/test_gpu_search_limits.py,
+with tests/test_search_limits_cpu.py and tests/search_limits.py."""
 import json
 import os
 import types
@@ -56,6 +58,9 @@ def stub_eval(gpu, spec):
             return (gpu.torch.full((n, 2086), np.float32(1.0 / 2086.0), dtype=gpu.torch.float32, device=planes.device),
                     gpu.torch.full((n,), np.float32(val), dtype=gpu.torch.float32, device=planes.device))
         return f
+    if spec["kind"] == "peaked":
+        return lambda planes: stub_net.peaked_stub_torch(planes, spec["salt"], spec.get("squarings", 8),
+                                                         spec.get("value", 0.0))
     return lambda planes: stub_net.hash_stub_torch(planes, spec["salt"])
 
 
