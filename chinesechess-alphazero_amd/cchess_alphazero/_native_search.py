@@ -22,14 +22,18 @@ BOOK_MAX = (1 << 24) - 2  # include/czero.h CZ_BOOK_MAX
 MOVE_FAST = 0x8000       # finished-game record, moves[i] bit 15: ply i was a fast search (cz_search_set_playout_cap)
 VISIT_FAST = 2           # visit entry flag: the ply was a fast search
 VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (cz_search_set_forced_playouts)
+VISIT_GUMBEL = 8         # visit entry flag: n holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
+GUMBEL_MAX_M = 128       # include/czero.h CZ_GUMBEL_MAX_M
 
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
 # was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
 # search of the playout cap (set_playout_cap); whether n holds the PRUNED counts of set_forced_playouts, and then
 # raw_total, the sum of the raw counts of the non-banned edges (0 otherwise); q, the root's search value of the ply
 # (record_values; None with the value record off and where the ring held NaN, "no value"); s, the policy surprise of the
-# ply, KL(recorded counts || priors without noise) (record_surprise; None with that record off and for NaN).
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s", defaults=(None, None))
+# ply, KL(recorded counts || priors without noise) (record_surprise; None with that record off and for NaN); gumbel, whether
+# the ply was a Gumbel root search (set_gumbel): n then holds the policy target scaled to 65536, raw_total as for pruned.
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel",
+                        defaults=(None, None, False))
 
 
 class SearchCfg(C.Structure):
@@ -93,6 +97,11 @@ def declare(L):
         "cz_search_root_surprise": [vp, vp, vp],
         "cz_root_surprise": [vp, vp, vp, vp, i32, vp, vp],
         "cz_search_set_leaf_mirror": [vp, d, vp, vp],
+        "cz_search_set_gumbel": [vp, i32, d, d, vp],
+        "cz_search_root_started": [vp, vp, vp],
+        "cz_search_gumbel_draws": [vp, vp, vp],
+        "cz_search_gumbel_targets": [vp, vp, vp, vp],
+        "cz_gumbel_policy_target": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -196,6 +205,7 @@ class Search:
         self._visits_dropped = 0
         self.leaf_mirror = 0.0                 # set_leaf_mirror(): the rate at which a new leaf is evaluated mirrored
         self.mirrored = None                   # set_leaf_mirror(flags=True): [slots] uint8, 1 = the slot's leaf is mirrored
+        self.gumbel_m = 0                      # set_gumbel(): candidates of the Gumbel root search, 0 = off
 
     # -- lifetime --
     def close(self):
@@ -322,6 +332,31 @@ class Search:
                       "cz_search_set_leaf_mirror")
         self.leaf_mirror = float(rate)
 
+    def set_gumbel(self, m=0, c_visit=50.0, c_scale=1.0):
+        """Gumbel root search with sequential halving (cz_search_set_gumbel; include/czero.h has the rule): with m > 0 the
+        root samples m candidates through Gumbel noise, spends the ply's simulations on them by sequential halving and
+        plays the survivor, without root noise or temperature; self-play's visit entries then hold the policy target
+        softmax(log prior + sigma(completed Q)) scaled to 65536 (`gumbel`, `raw_total`).  m = 0 switches it off.  Refused
+        while forced playouts or the playout cap are on.  Call it before start_selfplay() / set_roots() and before a graph
+        capture."""
+        _native.check(self.L.cz_search_set_gumbel(self.h, int(m), float(c_visit), float(c_scale), self._stream()),
+                      "cz_search_set_gumbel")
+        self.gumbel_m, self.gumbel_visit, self.gumbel_scale = int(m), float(c_visit), float(c_scale)
+
+    def root_started(self):
+        """started [G, 128] int32: the root selections of the current ply per edge (cz_search_root_started)."""
+        return self._root_outputs("cz_search_root_started", ((self.G, _native.MAXMOVES), "int32"))[0]
+
+    def gumbel_draws(self):
+        """The current ply's Gumbel draws g [G, 128] float64 (cz_search_gumbel_draws)."""
+        return self._root_outputs("cz_search_gumbel_draws", ((self.G, _native.MAXMOVES), "float64"))[0]
+
+    def gumbel_targets(self):
+        """What a Gumbel visit entry of every current root would hold (cz_search_gumbel_targets; edge order of root_stats,
+        bans of the current set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
+        n, raw = self._root_outputs("cz_search_gumbel_targets", ((self.G, _native.MAXMOVES), "int32"), ((self.G,), "int32"))
+        return dict(n=n, raw_total=raw)
+
     def record_values(self, on=True):
         """Self-play: every visit entry comes with the root's search value q (cz_search_record_values; include/czero.h has
         the arithmetic): VisitEntry.q, None where the root had no value.  Needs record_visits() on, and a later
@@ -440,7 +475,8 @@ class Search:
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
-                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp)
+                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp,
+                          gumbel=bool(a[7] & VISIT_GUMBEL))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -704,6 +740,21 @@ def policy_target_prune(labels, n, w, p, n_edges, c_puct, k):
     raw = torch.empty((rows,), dtype=torch.int32, device=n.device)
     _native.check(_native.lib().cz_policy_target_prune(*ptrs, ne, rows, float(c_puct), float(k), C.c_void_p(out.data_ptr()),
                                                        C.c_void_p(raw.data_ptr()), stream), "cz_policy_target_prune")
+    return out, raw
+
+
+def gumbel_policy_target(labels, n, w, p, n_edges, c_visit, c_scale):
+    """cz_gumbel_policy_target: the policy target of set_gumbel on caller-supplied rows.  labels uint16 (bit 15 = banned), n
+    int32, w float64, p float32, all [rows, 128] cuda tensors; n_edges uint8 [rows].  Returns (targets int32 [rows, 128]
+    scaled to 65536, raw_total int32 [rows]) on the device."""
+    import torch
+    rows, ptrs, ne, stream = _row_args("gumbel_policy_target", n_edges, (labels, "uint16"), (n, "int32"), (w, "float64"),
+                                       (p, "float32"))
+    out = torch.empty((rows, _native.MAXMOVES), dtype=torch.int32, device=n.device)
+    raw = torch.empty((rows,), dtype=torch.int32, device=n.device)
+    _native.check(_native.lib().cz_gumbel_policy_target(*ptrs, ne, rows, float(c_visit), float(c_scale),
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(raw.data_ptr()), stream),
+                  "cz_gumbel_policy_target")
     return out, raw
 
 

@@ -109,6 +109,9 @@ class EngineConfig(_Section):
                          leaf_mirror=0.0,         # random leaf mirror (run.py self / eval --leaf-mirror P): a new leaf is shown to
                                                   # the network as its left-right mirror image with probability P, its policy
                                                   # row read back through the label mirror (cz_search_set_leaf_mirror); 0 = off
+                         gumbel=0,                # Gumbel root search with sequential halving (run.py self --gumbel M, needs
+                         gumbel_visit=50.0,       # record_visits): M candidates sampled at the root, sigma's c_visit and
+                         gumbel_scale=1.0,        # c_scale; the recorded pi is softmax(log prior + sigma(completed Q)); 0 = off
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

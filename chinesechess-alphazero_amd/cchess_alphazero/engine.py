@@ -42,7 +42,8 @@ class SelfPlayEngine:
     def __init__(self, config, n_games, net=None, dtype=torch.float32, device=None, seed=0,
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
-                 full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None):
+                 full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
+                 gumbel=None, gumbel_visit=None, gumbel_scale=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -64,7 +65,12 @@ class SelfPlayEngine:
         items become [move, value, pi or None, weight, q or None, s] (cz_search_record_surprise).
         leaf_mirror: the rate at which the search shows a new leaf to the network as its left-right mirror image (None =
         config.engine.leaf_mirror; 0 = off), reading that leaf's policy row back through the label mirror
-        (cz_search_set_leaf_mirror).  The network and the records need nothing: rows and moves stay in their own frames."""
+        (cz_search_set_leaf_mirror).  The network and the records need nothing: rows and moves stay in their own frames.
+        gumbel, gumbel_visit, gumbel_scale: Gumbel root search with sequential halving (None = config.engine.gumbel /
+        gumbel_visit / gumbel_scale; gumbel 0 = off; needs record_visits, excludes fast_sims and forced_playouts): the root
+        samples `gumbel` candidates through Gumbel noise, halves them over the ply's simulations and plays the survivor,
+        without root noise or temperature; the pi of drain()'s items is softmax(log prior + sigma(completed Q)) scaled to
+        65536 (include/czero.h, cz_search_set_gumbel)."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -145,6 +151,15 @@ class SelfPlayEngine:
             raise ValueError(f"leaf_mirror {self.leaf_mirror}: expected 0 <= P <= 1")
         if self.leaf_mirror:                                   # likewise
             self.search.set_leaf_mirror(self.leaf_mirror)
+        self.gumbel = int(getattr(ec, "gumbel", 0) if gumbel is None else gumbel)
+        self.gumbel_visit = float(getattr(ec, "gumbel_visit", 50.0) if gumbel_visit is None else gumbel_visit)
+        self.gumbel_scale = float(getattr(ec, "gumbel_scale", 1.0) if gumbel_scale is None else gumbel_scale)
+        if self.gumbel and not self.record_visits:
+            raise ValueError("gumbel needs record_visits: the halving counts are not a policy target")
+        if self.gumbel and (self.fast_sims or self.forced_playouts):
+            raise ValueError("gumbel excludes fast_sims and forced_playouts: each defines its own root rule")
+        if self.gumbel:                                        # likewise
+            self.search.set_gumbel(self.gumbel, self.gumbel_visit, self.gumbel_scale)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py

@@ -69,6 +69,15 @@ _FLAGS = [
                                 "left-right mirror image with probability P and reads the policy back through the label "
                                 "mirror, so that the network's wing bias averages out of the search (0 = off; 0.5 = a fair "
                                 "coin)")),
+    ("--gumbel", dict(type=int, default=0, metavar="M",
+                      help="(self, with --record-visits) Gumbel root search: M candidate moves are sampled at the root through "
+                           "Gumbel noise, the ply's simulations are spent on them by sequential halving and the survivor is "
+                           "played; the recorded pi is softmax(log prior + sigma(completed Q)).  Sound at small --sims "
+                           "(0 = off; the paper uses 16)")),
+    ("--gumbel-visit", dict(type=float, default=50.0, metavar="C", help="(self, with --gumbel) c_visit of sigma")),
+    ("--gumbel-scale", dict(type=float, default=1.0, metavar="C", help="(self, with --gumbel) c_scale of sigma")),
+    ("--sims", dict(type=int, default=None, metavar="N",
+                    help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -108,6 +117,12 @@ def build_config(args):
     if not 0.0 <= args.book_rate <= 1.0:
         raise SystemExit(f"--book-rate {args.book_rate}: expected 0 <= P <= 1")
     engine.book_path, engine.book_rate = args.book, args.book_rate
+    if args.sims is not None:
+        if args.cmd != "self":
+            raise SystemExit("--sims is an option of `run.py self`")
+        if args.sims < 1:
+            raise SystemExit(f"--sims {args.sims}: expected N >= 1")
+        config.play.simulation_num_per_move = args.sims
     if not 0 <= args.fast_sims <= config.play.simulation_num_per_move:
         raise SystemExit(f"--fast-sims {args.fast_sims}: expected 0 <= N <= simulation_num_per_move "
                          f"({config.play.simulation_num_per_move})")
@@ -137,6 +152,19 @@ def build_config(args):
     if not 0.0 <= args.leaf_mirror <= 1.0:                  # (false for NaN too)
         raise SystemExit(f"--leaf-mirror {args.leaf_mirror}: expected 0 <= P <= 1")
     engine.leaf_mirror = args.leaf_mirror
+    if not 0 <= args.gumbel <= 128:
+        raise SystemExit(f"--gumbel {args.gumbel}: expected 0 <= M <= 128")
+    for name in ("gumbel_visit", "gumbel_scale"):
+        if not 0.0 <= getattr(args, name) < float("inf"):
+            raise SystemExit(f"--{name.replace('_', '-')} {getattr(args, name)}: expected a finite C >= 0")
+    if args.gumbel and not engine.record_visits:
+        raise SystemExit(f"--gumbel {args.gumbel} needs --record-visits: the halving counts are not a policy target, the "
+                         "target rides in the visit entries")
+    if args.gumbel and args.fast_sims:
+        raise SystemExit("--gumbel excludes --fast-sims: each defines its own root rule")
+    if args.gumbel and args.forced_playouts:
+        raise SystemExit("--gumbel excludes --forced-playouts: each defines its own root rule")
+    engine.gumbel, engine.gumbel_visit, engine.gumbel_scale = args.gumbel, args.gumbel_visit, args.gumbel_scale
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

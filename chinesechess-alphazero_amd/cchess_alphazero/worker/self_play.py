@@ -102,6 +102,11 @@ class SelfPlayWorker:
         if self.engine.forced_playouts:
             logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
                         f"the recorded visit counts are pruned (policy target pruning)")
+        if getattr(self.engine, "gumbel", 0):
+            logger.info(f"Process {self.pid}-{self.rank}: Gumbel root search: {self.engine.gumbel} candidates, sequential "
+                        f"halving over {self.config.play.simulation_num_per_move} simulations, c_visit = "
+                        f"{self.engine.gumbel_visit}, c_scale = {self.engine.gumbel_scale}; no root noise, no temperature; "
+                        f"the recorded pi is softmax(log prior + sigma(completed Q))")
         if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
             logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
                         f"mirror image with probability {self.engine.leaf_mirror}")

@@ -105,7 +105,13 @@ struct SearchParams {
     double forced_k;        // 0 = off; a tried root child is visited at least sqrt(forced_k * p * N) times
     // random leaf mirror (cz_search_set_leaf_mirror); read through leaf_coin only
     double leaf_mirror;     // 0 = off; a new leaf is evaluated mirrored iff philox_uniform(seed, key, 3, turns << 32 | node id) < leaf_mirror
+    // Gumbel root search with sequential halving (cz_search_set_gumbel); read by begin_search, k_sim's root context,
+    // k_noise, choose_action, emit_visits and k_root_records only
+    int gumbel_m;           // 0 = off; candidates sampled without replacement at the root (<= GUMBEL_MAX_M)
+    double gumbel_visit;    // c_visit of sigma(x) = (c_visit + max_b n_b) * c_scale * x
+    double gumbel_scale;    // c_scale
 };
+constexpr int GUMBEL_MAX_M = 128;
 
 struct SearchBuffers {
     // ---- optional caller-owned output (cz_search_leaf_masks): one 96-word occupancy board per queue slot ----
@@ -158,6 +164,10 @@ struct SearchBuffers {
     int8_t* g_prev_board;   // [G][96] game position two plies before the root (action(hist=...), 28-plane input)
     uint8_t* g_hist_kind;   // [G] 0 no game history, 1 g_prev_board valid, 2 history too short
     int32_t* s_qrow;        // [G][K] compact evaluation-queue row of the slot's leaf (cz_search_round_q), -1 none
+    // ---- Gumbel root search (cz_search_set_gumbel), per game; untouched while the option is off ----
+    int32_t* g_started;     // [G][128] selections of this ply that took root edge j (zeroed by begin_search)
+    double* g_gumbel;       // [G][128] the ply's Gumbel draws g_j, drawn by begin_search
+    int32_t* g_budget;      // [G] the ply's simulation budget n: `tasks` of begin_search
 };
 
 // finished-game record header (followed by uint16 moves[max_plies + 2])
@@ -184,13 +194,14 @@ constexpr uint16_t VISIT_BANNED = 0x8000;          // label bit: the edge is in 
 constexpr uint32_t VISIT_RESIGN = 1u;              // entry flag: the player resigned at this ply
 constexpr uint32_t VISIT_FAST = 2u;                // entry flag: the ply was a fast search (cz_search_set_playout_cap)
 constexpr uint32_t VISIT_PRUNED = 4u;              // entry flag: n[] holds the PRUNED counts (cz_search_set_forced_playouts)
+constexpr uint32_t VISIT_GUMBEL = 8u;              // entry flag: n[] holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
 struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
     uint32_t game_id;
     uint16_t ply;       // turns when the move was chosen
     uint8_t n_edges;
     uint8_t flags;
     int32_t sum_n;      // the root's own visit count
-    uint32_t raw_total; // VISIT_PRUNED: sum of the raw counts of the non-banned edges; otherwise 0
+    uint32_t raw_total; // VISIT_PRUNED / VISIT_GUMBEL: sum of the raw counts of the non-banned edges; otherwise 0
 };
 constexpr int VISIT_STRIDE = (int)sizeof(VisitEntryHdr) + 2 * VISIT_MAX_EDGES + 4 * VISIT_MAX_EDGES;   // 784 B
 constexpr double SURPRISE_R_FLOOR = 1e-30;          // floor of the normalised prior in root_surprise (czero.h): s <= ln 1e30 < 70

@@ -450,6 +450,47 @@ XQ_D double root_prior(const SearchParams& P, const RootCtx& rc, float p, int j)
 }
 XQ_D double root_u(const SearchParams& P, double p_, double xx, int n) { return P.c_puct * p_ * xx / (double)(1 + n); }
 
+// ---- Gumbel root search with sequential halving (include/czero.h, cz_search_set_gumbel) -------------------------------
+// seq(m, n)[t]: how many selections the edge taken by the t-th root selection of the ply must already have.  A phase of
+// the halving with k survivors appends e = max(1, n / (L k)) runs of k equal values, so entry t is found by walking the
+// phases; nothing is stored.  Scalar, wave-uniform.
+XQ_D int gumbel_seq(int m, int n, int t)
+{
+    if (m <= 1) return t;
+    int L = 0;
+    while ((1 << L) < m) ++L;
+    int k = m, pos = 0, base = 0;
+    for (;;) {
+        int e = n / (L * k);
+        if (e < 1) e = 1;
+        if (t < pos + e * k) return base + (t - pos) / k;
+        pos += e * k;
+        base += e;
+        k = k / 2 > 2 ? k / 2 : 2;
+    }
+}
+XQ_D double gumbel_q01(int n, double w)
+{
+    if (n <= 0) return 0.0;
+    const double q = (w / (double)n + 1.0) / 2.0;
+    return q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q);
+}
+XQ_D double gumbel_sigma(double c_visit, double c_scale, int max_n, double x) { return ((c_visit + (double)max_n) * c_scale) * x; }
+// g_j + log p_j + sigma(q01_j); p = 0 scores -infinity
+XQ_D double gumbel_score(double g, float p, double sig)
+{
+    const double lp = p > 0.0f ? log((double)p) : -__builtin_inf();
+    return (g + lp) + sig;
+}
+// arg max of (score, index) over the lanes' candidates (best_j < 0: none), the later edge on a tie: select_edge's vote
+XQ_D int gumbel_argmax(double best_s, int best_j)
+{
+    const double m = wave_max_f64(best_s);
+    const bool top = best_j >= 0 && best_s == m;
+    const uint64_t t1 = __ballot(top && best_j >= 64), t0 = __ballot(top);
+    return t1 ? 64 + (63 - __clzll((long long)t1)) : (t0 ? 63 - __clzll((long long)t0) : -1);
+}
+
 struct Picked {
     int j;              // edge index inside the node, -1 = none
     bool have;          // n / w / child / mv below are valid (winner among the first 64 edges)
@@ -457,9 +498,65 @@ struct Picked {
     double w;
 };
 
-// base: the node's record; sb: its stat block (nullptr: allocated in this visit, every edge is {0, 0, unknown})
-XQ_D Picked select_edge(const SearchParams& P, char* base, const EdgeStat* sb, int sum_n, int nm, const RootCtx& rc)
+// The root's whole selection on a Gumbel ply: this is the t-th root selection of the ply, t = sum started; among the
+// non-banned edges with started_j == seq(m, n)[t] the greatest g_j + log p_j + sigma(q01_j), the later edge on a tie.  No
+// proven-win shortcut, no noise.  The winner's started count goes up by one, written by the lane that reads it (j & 63).
+XQ_D int select_gumbel(int gumbel_m, double c_visit, double c_scale, int32_t* started, const double* gum, int budget,
+                       char* base, const EdgeStat* sb, int nm, int n_no_act, const uint16_t* no_act)
 {
+    const int lane = lane_id();
+    const float* pp = node_p(base);
+    const uint16_t* pm = node_mv(base, nm);
+    int st[2] = {0, 0}, n[2] = {0, 0};
+    double w[2] = {0.0, 0.0};
+    bool live[2] = {false, false};
+    int max_n = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j >= nm) continue;
+        bool banned = false;
+        for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == pm[j]);
+        live[h] = !banned;
+        if (!live[h]) continue;
+        st[h] = started[j];
+        if (sb) { const EdgeStat es = sb[j]; n[h] = es.n; w[h] = es.w; }
+        max_n = n[h] > max_n ? n[h] : max_n;
+    }
+    const int t = __builtin_amdgcn_readlane(wave_incl_scan(st[0] + st[1]), 63);
+    max_n = (int)wave_max_f64((double)max_n);
+    const int n_live = __popcll(__ballot(live[0])) + __popcll(__ballot(live[1]));
+    const int v = gumbel_seq(gumbel_m < n_live ? gumbel_m : n_live, budget, t);
+    double best_s = -__builtin_inf();
+    int best_j = -1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (!live[h] || st[h] != v) continue;
+        const double sc = gumbel_score(gum[j], pp[j],
+                                       gumbel_sigma(c_visit, c_scale, max_n, gumbel_q01(n[h], w[h])));
+        if (sc >= best_s) { best_s = sc; best_j = j; }         // h = 1 has the larger index: wins ties
+    }
+    const int pick = gumbel_argmax(best_s, best_j);
+    if (pick >= 0 && lane == (pick & 63)) started[pick] = st[pick >> 6] + 1;
+    return pick;
+}
+
+// base: the node's record; sb: its stat block (nullptr: allocated in this visit, every edge is {0, 0, unknown}).
+// GUM: the k_sim instantiation that is launched while the Gumbel root search is on -- the others do not hold its code,
+// so their registers and their text are what they were without it.
+template <bool GUM>
+XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, char* base, const EdgeStat* sb, int sum_n,
+                        int nm, const RootCtx& rc)
+{
+    if (GUM && rc.is_root && P.gumbel_m > 0) {                  // wave-uniform
+        Picked r;                                               // (have = false: the caller reloads the edge, this is not the hot path)
+        r.j = select_gumbel(P.gumbel_m, P.gumbel_visit, P.gumbel_scale, B.g_started + (size_t)g * MAXMOVES,
+                            B.g_gumbel + (size_t)g * MAXMOVES, uni(B.g_budget[g]), base, sb, nm, rc.n_no_act, rc.no_act);
+        r.have = false;
+        r.n = 0; r.child = CHILD_UNKNOWN; r.mv = 0; r.w = 0.0;
+        return r;
+    }
     const int lane = lane_id();
     const double xx = __dsqrt_rn((double)(sum_n + 1));
     const float* pp = node_p(base);
@@ -754,7 +851,7 @@ XQ_D int edge_move(const GameView& gv, int node, int edge)
 
 // One descent of simulation `sim` starting at `node` with `depth` path entries already in L.path_*
 // (MCTS_search, player.py:198-260).  `node` < 0 means the root position is not in the tree yet.
-template <bool HIST>
+template <bool HIST, bool GUM>
 XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                   const RoundIO& io, const RootCtx& rc0, int root, int sim, int node, int depth, int* active,
                   Arena& ar, bool fresh, Deferred& df)
@@ -839,7 +936,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         RootCtx rc = rc0;
         rc.is_root = (node == root);                                // player.py:266
         rc.sim = sim;
-        const Picked pk = select_edge(P, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc);
+        const Picked pk = select_edge<GUM>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc);
         if (pk.j < 0) {                                             // "Best action is None": cannot happen
             backup(P, gv, L, depth, 0.0);
             sim_finish(gv, sim, active);
@@ -1073,6 +1170,21 @@ XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const Game
         (void)reserve_ply(P, B, gv, L.chtab, tasks);     // within keep_chunks by construction; else overflow_sims counts
     }
     count(gv, CT_ROOT_REUSED_SIMS, (unsigned long long)done_n);
+    if (P.gumbel_m > 0) {
+        // Gumbel root search: the ply's draws g_j = -log(-log u_j), u_j = stream 4 of the generator keyed like the root
+        // noise, draw (turns << 32 | j); fixed for the whole ply.  started = 0, the budget is what this ply searches.
+        const uint32_t key = uniu(B.g_game_id[g]) + (uint32_t)g * 2654435761u;
+        const uint64_t hi = (uint64_t)uniu((uint32_t)B.g_turns[g]) << 32;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            double u = philox_uniform(P.seed, key, 4, hi | (uint64_t)j);
+            if (u == 0.0) u = 1.1102230246251565e-16;          // 2^-53
+            B.g_gumbel[(size_t)g * MAXMOVES + j] = -log(-log(u));
+            B.g_started[(size_t)g * MAXMOVES + j] = 0;
+        }
+        if (lane == 0) B.g_budget[g] = tasks;
+    }
     if (lane == 0) {
         B.g_root[g] = root;
         B.g_tasks_left[g] = tasks;
@@ -1081,6 +1193,8 @@ XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const Game
     }
     wave_sync_global();
 }
+
+XQ_D int gumbel_choose(const SearchParams& P, const SearchBuffers& B, const GameView& gv);
 
 // ---- calc_policy + apply_temperature + choice (player.py:375-406, 453-470, :195) ---------------------
 // returns the chosen label, or -1 when the player resigns.  u is the uniform draw of np.random.choice.
@@ -1128,6 +1242,7 @@ XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const Game
     }
     maxq = unid(maxq);
     if (maxq < P.resign_threshold && enable_resign && turns > P.min_resign_turn) return -1;   // :397-398
+    if (P.gumbel_m > 0) return gumbel_choose(P, B, gv);         // a Gumbel ply: no temperature, u is not used
     // order the edges by label (the policy vector is indexed by label)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1373,6 +1488,90 @@ XQ_D RootEdges load_row_edges(const uint16_t* __restrict__ labels, const int32_t
     return E;
 }
 
+// The move a Gumbel ply plays (include/czero.h): among the non-banned edges with the greatest started count the greatest
+// g_j + log p_j + sigma(q01_j), with w and n as they are after the last backup; the later edge on a tie.  All 64 lanes.
+XQ_D int gumbel_choose(const SearchParams& P, const SearchBuffers& B, const GameView& gv)
+{
+    const int lane = lane_id();
+    const RootEdges E = load_root_edges(B, gv);
+    const int32_t* started = B.g_started + (size_t)gv.g * MAXMOVES;
+    const double* gum = B.g_gumbel + (size_t)gv.g * MAXMOVES;
+    int st[2] = {-1, -1};
+    int max_n = 0, max_st = -1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j >= E.nm || (E.lab[h] & VISIT_BANNED)) continue;
+        st[h] = started[j];
+        max_st = st[h] > max_st ? st[h] : max_st;
+        max_n = E.n[h] > max_n ? E.n[h] : max_n;
+    }
+    max_st = (int)wave_max_f64((double)max_st);
+    max_n = (int)wave_max_f64((double)max_n);
+    double best_s = -__builtin_inf();
+    int best_j = -1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (st[h] < 0 || st[h] != max_st) continue;
+        const double sc = gumbel_score(gum[j], E.p[h],
+                                       gumbel_sigma(P.gumbel_visit, P.gumbel_scale, max_n, gumbel_q01(E.n[h], E.w[h])));
+        if (sc >= best_s) { best_s = sc; best_j = j; }
+    }
+    const int pick = gumbel_argmax(best_s, best_j);
+    if (pick < 0) return 0;                                     // every edge banned: what calc_policy's empty vector gives
+    const int lab = pick < 64 ? __builtin_amdgcn_readlane((int)E.lab[0], pick) : __builtin_amdgcn_readlane((int)E.lab[1], pick - 64);
+    return lab & 0x7FFF;
+}
+
+// The Gumbel policy target (include/czero.h, cz_search_set_gumbel): one wavefront, edge j = lane + 64 h.  lab[h] carries
+// VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise.  m[] receives floor(65536 pi'_j + 1/2),
+// pi' = softmax(log p + sigma(completed q)); banned edges 0.  Float64, each sum the lane's two terms first and then the
+// DPP ladder.  Returns S, the raw total of the non-banned edges.  All 64 lanes call it.
+XQ_D int gumbel_targets(int nm, const uint16_t lab[2], int m[2], const int n[2], const double w[2], const float p[2],
+                        double c_visit, double c_scale)
+{
+    const int lane = lane_id();
+    bool live[2];
+    int s = 0, max_n = 0;
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        live[h] = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED);
+        m[h] = 0;
+        if (!live[h]) continue;
+        s += n[h];
+        max_n = n[h] > max_n ? n[h] : max_n;
+        if (n[h] > 0) {
+            num = __dadd_rn(num, __dmul_rn((double)p[h], gumbel_q01(n[h], w[h])));
+            den = __dadd_rn(den, (double)p[h]);
+        }
+    }
+    const int S = __builtin_amdgcn_readlane(wave_incl_scan(s), 63);
+    max_n = (int)wave_max_f64((double)max_n);
+    num = wave_add_f64(num);
+    den = wave_add_f64(den);
+    const double vbar = den > 0.0 ? num / den : 0.5;            // (nothing visited, or only edges of prior 0: one half)
+    double sg[2] = {0.0, 0.0}, mx = -__builtin_inf();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!live[h]) continue;
+        sg[h] = gumbel_sigma(c_visit, c_scale, max_n, n[h] > 0 ? gumbel_q01(n[h], w[h]) : vbar);
+        mx = sg[h] > mx ? sg[h] : mx;
+    }
+    mx = wave_max_f64(mx);
+    double e[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (live[h]) e[h] = __dmul_rn((double)p[h], exp(sg[h] - mx));
+    const double tot = wave_add_f64(__dadd_rn(e[0], e[1]));
+    if (!(tot > 0.0)) return S;                                 // no live edge, or every prior 0: all zero
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (live[h]) m[h] = (int)floor(__dadd_rn(__dmul_rn(65536.0, e[h] / tot), 0.5));
+    return S;
+}
+
 // Policy target pruning (include/czero.h, cz_search_set_forced_playouts): one wavefront, edge j = lane + 64 h.  lab[h]
 // carries VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise; the pruned counts replace n[].
 // All arithmetic in float64, in the order czero.h writes it.  Returns S, the raw total of the non-banned edges.
@@ -1483,7 +1682,7 @@ XQ_D double root_surprise(int nm, const uint16_t lab[2], const int m[2], const f
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
 // raw_total); the tree keeps the raw counts and choose_action has already used them.
 XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns,
-                      bool resigned, bool fast, bool prune)
+                      bool resigned, bool fast, bool prune, bool gumbel)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -1506,13 +1705,15 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
     const RootEdges E = load_root_edges(B, gv);
     const int nm = E.nm;
     int m[2] = {E.n[0], E.n[1]};            // the counts the entry records: raw, or pruned
-    const int raw_total = prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k) : 0;
+    // (a Gumbel ply: the counts are the policy target pi' scaled to 65536 -- the halving counts are no target)
+    const int raw_total = gumbel ? gumbel_targets(nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale)
+                                 : (prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k) : 0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int j = lane + 64 * h;
         if (j < nm) { lab[j] = E.lab[h]; cnt[j] = m[h]; }
     }
-    const bool pruned = raw_total > 0;      // S == 0: nothing to prune, the entry is the one written without pruning
+    const bool pruned = !gumbel && raw_total > 0;      // S == 0: nothing to prune, the entry is the one written without pruning
     // the value and the surprise record (cz_search_record_values, _surprise): the entry's slot in a ring of their own
     if (V.q) {
         const double q = root_value(nm, E.lab, m, E.n, E.w);
@@ -1527,7 +1728,8 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         h->game_id = B.g_game_id[g];
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
-        h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u));
+        h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u) |
+                               (gumbel ? VISIT_GUMBEL : 0u));
         h->sum_n = E.sum_n;
         h->raw_total = (uint32_t)raw_total;
     }
@@ -1548,7 +1750,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);
-        emit_visits(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast);
+        emit_visits(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0);
     }
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;
@@ -1658,7 +1860,9 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
 // (move sampling with pow(), game rules, chunk reservation, Gamma sampling).
 constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 
-template <bool HIST>        // HIST: 28 input planes (use_history); kept out of the common 14-plane instantiation
+// HIST: 28 input planes (use_history); kept out of the common 14-plane instantiation.  GUM: the Gumbel root search
+// (cz_search_set_gumbel) is on; likewise.
+template <bool HIST, bool GUM>
 __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                            const float* __restrict__ value, void* planes, int mask, int compact,
                                            int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
@@ -1682,7 +1886,8 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
     Arena ar{uniu(B.g_heap_top[g]), uni(B.g_nchunks[g]), uni(B.g_node_count[g])};
     // (no root noise on a fast ply of the playout cap: k_noise drew no rows for it)
     // and no forced playouts either: a fast ply has no noise to examine
-    const bool noisy = P.noise_eps != 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
+    // (nor on a Gumbel ply, whose root rule replaces both)
+    const bool noisy = P.noise_eps != 0.0 && !(GUM && P.gumbel_m > 0) && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
     const bool force = P.forced_k > 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
     const RootCtx rc{false, uni((int)B.g_n_no_act[g]), B.g_no_act + (size_t)g * MAX_NO_ACT,
                      noisy ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0, force};
@@ -1809,7 +2014,7 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df);
+        run_sim<HIST, GUM>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -1876,6 +2081,7 @@ __global__ __launch_bounds__(256) void k_noise(SearchParams P, SearchBuffers B)
     const int g = blockIdx.x;
     if (g >= P.G || B.g_phase[g] != PH_SEARCH) return;
     if (ply_is_fast(P, B.g_game_id[g], B.g_turns[g])) return;   // playout cap: no root noise on a fast ply, the epoch stays
+    if (P.gumbel_m > 0) return;                                 // nor on a Gumbel ply
     // a new batch starts only when nothing is in flight (k_sim(BACKUP) may just have finished the old one)
     if (B.g_active[g] != 0) return;
     const int tasks = B.g_tasks_left[g];
@@ -2069,9 +2275,10 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
 // What emit_visits would record for every current root, with the bans of the current set_roots (cz_search_root_targets,
 // _root_value, _root_surprise): the pruned counts n [G][128] and their raw total, the search value q, the policy
 // surprise s.  A NULL output is not computed.  One wavefront per game.
+// gumbel (or the option on): the counts are the Gumbel policy targets, as a VISIT_GUMBEL entry holds them.
 __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
                                                     int32_t* __restrict__ raw_total, double* __restrict__ q,
-                                                    double* __restrict__ s)
+                                                    double* __restrict__ s, int gumbel)
 {
     __shared__ uint32_t chtab[MAX_CHUNKS];
     const int g = blockIdx.x;
@@ -2080,7 +2287,8 @@ __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffe
     const int lane = lane_id();
     const RootEdges E = load_root_edges(B, gv);
     int m[2] = {E.n[0], E.n[1]};
-    const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k);
+    const int S = (gumbel || P.gumbel_m > 0) ? gumbel_targets(E.nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale)
+                                             : prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k);
     if (n) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) n[(size_t)g * MAXMOVES + lane + 64 * h] = lane + 64 * h < E.nm ? m[h] : 0;
@@ -2128,6 +2336,24 @@ __global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__
         const double v = root_surprise(E.nm, E.lab, m, E.p);
         if (lane == 0) out_s[r] = v;
     }
+}
+
+// cz_gumbel_policy_target: gumbel_targets on caller-supplied rows [rows][128], one wavefront per row
+__global__ __launch_bounds__(64) void k_gumbel_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
+                                                   const double* __restrict__ w, const float* __restrict__ p,
+                                                   const uint8_t* __restrict__ n_edges, int rows, double c_visit,
+                                                   double c_scale, int32_t* __restrict__ out_m,
+                                                   int32_t* __restrict__ out_raw_total)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    const RootEdges E = load_row_edges(labels, n, w, p, n_edges, r);
+    int m[2];
+    const int S = gumbel_targets(E.nm, E.lab, m, E.n, E.w, E.p, c_visit, c_scale);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) out_m[(size_t)r * MAXMOVES + lane + 64 * h] = m[h];
+    if (lane == 0) out_raw_total[r] = S;
 }
 
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
@@ -2301,6 +2527,9 @@ size_t layout(cz_search* s, char* base, bool dry)
     carve(cur, B.g_prev_board, G * BOARD_LDS, dry);
     carve(cur, B.g_hist_kind, G, dry);
     carve(cur, B.s_qrow, G * K, dry);
+    carve(cur, B.g_started, G * MAXMOVES, dry);
+    carve(cur, B.g_gumbel, G * MAXMOVES, dry);
+    carve(cur, B.g_budget, G, dry);
     return (size_t)(cur - base);
 }
 
@@ -2402,6 +2631,8 @@ int cz_search_create(const cz_search_cfg* c, cz_search** out)
     P.enable_resign_rate = c->enable_resign_rate;
     P.seed = c->seed;
     P.game_id_stride = (uint32_t)P.G;
+    P.gumbel_visit = 50.0;
+    P.gumbel_scale = 1.0;
     P.ring_cap = c->ring_capacity > 0 ? c->ring_capacity : 2 * P.G + 64;
     P.record_stride = (int)((sizeof(GameRecord) + sizeof(uint16_t) * (size_t)(P.max_plies + 2) + 15) & ~(size_t)15);
     if (P.planes_dtype < CZ_F32 || P.planes_dtype > CZ_U8) { delete s; return serr(CZ_ERR_ARG, "cz_search_create: planes_dtype"); }
@@ -2545,19 +2776,27 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
 {
     const dim3 grid(s->P.G), block(64);
     hipStream_t st = (hipStream_t)stream;
-    const bool noise = s->P.noise_eps != 0.0;
+    const bool noise = s->P.noise_eps != 0.0 && s->P.gumbel_m == 0;
     const int compact = q_rows ? 1 : 0;
     // the rows consumed now were written after the PREVIOUS round: by compact row if that round built a compact queue
     const int consume_compact = s->prev_compact;
     s->prev_compact = compact;
     const dim3 nblock(256);
     const bool hist = s->P.in_planes == 28;
-    if (hist) hipLaunchKernelGGL(k_sim<true>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_BACKUP, consume_compact, q_rows, q_count);
-    else hipLaunchKernelGGL(k_sim<false>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_BACKUP, consume_compact, q_rows, q_count);
+    const bool gum = s->P.gumbel_m > 0;
+    auto sim = [&](int mask, int cq) {
+        if (gum) {
+            if (hist) hipLaunchKernelGGL((k_sim<true, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((k_sim<false, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+        } else {
+            if (hist) hipLaunchKernelGGL((k_sim<true, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((k_sim<false, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+        }
+    };
+    sim(SIM_BACKUP, consume_compact);
     hipLaunchKernelGGL(k_advance, grid, block, 0, st, s->P, s->B, s->V);
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
-    if (hist) hipLaunchKernelGGL(k_sim<true>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_SELECT, compact, q_rows, q_count);
-    else hipLaunchKernelGGL(k_sim<false>, grid, block, 0, st, s->P, s->B, policy, value, planes, SIM_SELECT, compact, q_rows, q_count);
+    sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
     return CZ_OK;
 }
@@ -2720,6 +2959,8 @@ int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, voi
         return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: full_rate outside [0, 1]");
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the schedule they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_playout_cap", e);
+    if (fast_sims > 0 && s->P.gumbel_m > 0)
+        return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: the Gumbel root search is on (cz_search_set_gumbel)");
     s->P.fast_sims = fast_sims;
     s->P.full_rate = fast_sims > 0 ? full_rate : 0.0;
     return CZ_OK;
@@ -2735,7 +2976,67 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
     if (!finite_nonneg(k)) return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: k negative or not finite");
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_forced_playouts", e);
+    if (k > 0.0 && s->P.gumbel_m > 0)
+        return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: the Gumbel root search is on (cz_search_set_gumbel)");
     s->P.forced_k = k;
+    return CZ_OK;
+}
+
+static_assert(CZ_VISIT_GUMBEL == VISIT_GUMBEL && CZ_GUMBEL_MAX_M == GUMBEL_MAX_M, "czero.h: Gumbel root search");
+
+int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_gumbel: null handle");
+    if (m < 0 || m > GUMBEL_MAX_M) return serr(CZ_ERR_ARG, "cz_search_set_gumbel: m outside 0 .. 128");
+    if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: c_visit or c_scale negative or not finite");
+    if (m > 0 && (s->P.forced_k > 0.0 || s->P.fast_sims > 0))
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: forced playouts or the playout cap are on, each defines its own root rule");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_gumbel", e);
+    s->P.gumbel_m = m;
+    s->P.gumbel_visit = c_visit;
+    s->P.gumbel_scale = c_scale;
+    return CZ_OK;
+}
+
+int cz_search_root_started(cz_search* s, int32_t* started, void* stream)
+{
+    if (!s || !started) return serr(CZ_ERR_ARG, "cz_search_root_started: null argument");
+    hipError_t e = hipMemcpyAsync(started, s->B.g_started, sizeof(int32_t) * (size_t)s->P.G * MAXMOVES,
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip("cz_search_root_started", e);
+}
+
+int cz_search_gumbel_draws(cz_search* s, double* draws, void* stream)
+{
+    if (!s || !draws) return serr(CZ_ERR_ARG, "cz_search_gumbel_draws: null argument");
+    hipError_t e = hipMemcpyAsync(draws, s->B.g_gumbel, sizeof(double) * (size_t)s->P.G * MAXMOVES,
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip("cz_search_gumbel_draws", e);
+}
+
+int cz_search_gumbel_targets(cz_search* s, int32_t* m, int32_t* raw_total, void* stream)
+{
+    if (!s || !m || !raw_total) return serr(CZ_ERR_ARG, "cz_search_gumbel_targets: null argument");
+    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, m, raw_total,
+                       (double*)nullptr, (double*)nullptr, 1);
+    S_LAUNCH_CHECK("cz_search_gumbel_targets");
+    return CZ_OK;
+}
+
+int cz_gumbel_policy_target(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                            const uint8_t* n_edges, int rows, double c_visit, double c_scale, int32_t* out_m,
+                            int32_t* out_raw_total, void* stream)
+{
+    if (!labels || !n || !w || !p || !n_edges || !out_m || !out_raw_total || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_gumbel_policy_target: null argument or rows < 0");
+    if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
+        return serr(CZ_ERR_ARG, "cz_gumbel_policy_target: c_visit or c_scale negative or not finite");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_gumbel_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows, c_visit,
+                       c_scale, out_m, out_raw_total);
+    S_LAUNCH_CHECK("cz_gumbel_policy_target");
     return CZ_OK;
 }
 
@@ -2762,7 +3063,7 @@ int cz_search_root_targets(cz_search* s, int32_t* n, int32_t* raw_total, void* s
 {
     if (!s || !n || !raw_total) return serr(CZ_ERR_ARG, "cz_search_root_targets: null argument");
     hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, n, raw_total,
-                       (double*)nullptr, (double*)nullptr);
+                       (double*)nullptr, (double*)nullptr, 0);
     S_LAUNCH_CHECK("cz_search_root_targets");
     return CZ_OK;
 }
@@ -2793,7 +3094,7 @@ int cz_search_root_value(cz_search* s, double* q, void* stream)
 {
     if (!s || !q) return serr(CZ_ERR_ARG, "cz_search_root_value: null argument");
     hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
-                       (int32_t*)nullptr, q, (double*)nullptr);
+                       (int32_t*)nullptr, q, (double*)nullptr, 0);
     S_LAUNCH_CHECK("cz_search_root_value");
     return CZ_OK;
 }
@@ -2823,7 +3124,7 @@ int cz_search_root_surprise(cz_search* s, double* out, void* stream)
 {
     if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_surprise: null argument");
     hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
-                       (int32_t*)nullptr, (double*)nullptr, out);
+                       (int32_t*)nullptr, (double*)nullptr, out, 0);
     S_LAUNCH_CHECK("cz_search_root_surprise");
     return CZ_OK;
 }

@@ -388,9 +388,10 @@ typedef struct cz_visit_entry {
     uint8_t flags;                   /* bit 0: the player resigned at this ply; bit 1 (CZ_VISIT_FAST): the ply was a
                                         fast search of the playout cap (cz_search_set_playout_cap); bit 2
                                         (CZ_VISIT_PRUNED): n[] holds the pruned policy targets, not the raw counts
-                                        (cz_search_set_forced_playouts) */
+                                        (cz_search_set_forced_playouts); bit 3 (CZ_VISIT_GUMBEL): n[] holds the Gumbel
+                                        policy target scaled to 65536 (cz_search_set_gumbel) */
     int32_t sum_n;                   /* the root's own visit count */
-    uint32_t raw_total;              /* CZ_VISIT_PRUNED: sum of the RAW counts of the non-banned edges (S), so that
+    uint32_t raw_total;              /* CZ_VISIT_PRUNED, CZ_VISIT_GUMBEL: sum of the RAW counts of the non-banned edges (S), so that
                                         raw_total - sum of the non-banned n[] = visits pruned; otherwise 0 (this word
                                         was `reserved`, always 0, before pruning existed) */
 } cz_visit_entry;
@@ -484,6 +485,82 @@ int cz_search_root_surprise(cz_search* s, double* out, void* stream);
  * [rows] (<= 128), out [rows] float64, all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
 int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, const uint8_t* n_edges, int rows,
                      double* out, void* stream);
+/* ---- Gumbel root search with sequential halving (off by default; the reference has no such option) ----
+ * "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022) at the root: M candidate moves are sampled
+ * without replacement through Gumbel noise, the ply's simulations are spent on them by sequential halving, the survivor
+ * is played and the policy is trained towards softmax(log prior + sigma(completed Q)) instead of visit counts -- a target
+ * that improves on the prior at any budget.  m = 0 (the state after cz_search_create): no kernel output, record, counter
+ * or entry differs by a bit from what it was before this existed, and the per-game state below is not touched.
+ *
+ * Everything is float64 unless said otherwise.  "Edges" are the root's non-banned edges in edge order, p_j the stored
+ * float32 prior WITHOUT noise, n_j / w_j the edge's statistics from the root mover's view.
+ *
+ * DRAWS.  g_j = -log(-log u_j), u_j = philox_uniform(seed, key, stream 4, turns << 32 | j) for edge index j (banned
+ * edges keep their index), key = game id + game slot * 2654435761 like the root noise, so external mode has draws too;
+ * u = 0 is replaced by 2^-53.  Drawn when the ply's search begins and fixed for the whole ply.
+ *
+ * SCHEDULE for m candidates and a budget of n simulations:
+ *       seq(m, n): if m <= 1: return [0, 1, ..., n - 1]
+ *                  L = ceil(log2 m); visits = [0] * m; k = m; out = []
+ *                  while len(out) < n:
+ *                      e = max(1, floor(n / (L * k)))
+ *                      repeat e times: out += visits[:k]; visits[i] += 1 for i < k
+ *                      k = max(2, k // 2)
+ *                  return out[:n]
+ * with m = min(M, number of edges) and n the simulations this ply runs: simulation_num_per_move less the visits the
+ * reused root already has (the `tasks` of the ply).
+ *
+ * ROOT SELECTION.  started_j counts the selections of this ply that took edge j: per-game state, zeroed when the ply's
+ * search begins, independent of the virtual loss and of visits inherited from a reused subtree -- which is why the
+ * schedule is driven by it and not by n_j: with several simulations in flight n_j carries virtual losses, and a reused
+ * root starts with unequal n_j, either of which would break the halving's "all survivors have equal counts".  The t-th
+ * selection at the root, t = sum_j started_j, takes among the edges with started_j == seq(m, n)[t] the greatest
+ *       g_j + log p_j + sigma(q01_j)
+ *       q01_j = clamp((w_j / n_j + 1) / 2, 0, 1) where n_j > 0, else 0
+ *       sigma(x) = ((c_visit + max_b n_b) * c_scale) * x           (max over the edges)
+ * the LATER edge on a tie, as PUCT's `>=` does; p_j = 0 scores -infinity and loses to any finite score.  The first m
+ * selections so pick the m greatest g_j + log p_j (+ sigma of what a reused root knows), the Gumbel top-m sample; from
+ * then on only they are eligible.  The rule replaces the root's whole selection, the proven-win shortcut included;
+ * below the root the search is PUCT as it is.
+ *
+ * MOVE PLAYED.  Among the edges with the greatest started_j the greatest of the same score, w and n as they are after
+ * the last backup.  cz_search_choose ignores u; the resign test is unchanged.  A Gumbel ply has no temperature and no
+ * Dirichlet noise (no rows are drawn, as on a fast ply of the playout cap).
+ *
+ * POLICY TARGET, a pure function of a root row (labels, n, w, p) and (c_visit, c_scale):
+ *       cq_j = q01_j where n_j > 0, else vbar = (sum_{n_b > 0} p_b q01_b) / (sum_{n_b > 0} p_b), 1/2 when that sum is not
+ *              positive (nothing visited)
+ *       pi'_j = p_j exp(sigma(cq_j) - max_b sigma(cq_b)) / sum over the edges
+ *       m_j = floor(65536 pi'_j + 1/2); banned edges 0; all 0 when no edge has a positive prior
+ * The paper also mixes the root's own network value into vbar with weight 1 / (1 + sum n); the node record holds no
+ * value and that weight is below 6 % at 16 simulations, so it is LEFT OUT here.  exp and log are the device library's
+ * float64 routines: m_j may differ by 1 from another implementation's.
+ *
+ * VISIT RECORD.  An entry of a Gumbel ply carries CZ_VISIT_GUMBEL, n[] holds m_j (a trainer that normalises n[] gets
+ * pi') and raw_total the sum of the raw counts of the non-banned edges, as for CZ_VISIT_PRUNED.  The value and the
+ * surprise record keep their definitions over the recorded n[].
+ *
+ * cz_search_set_gumbel: 0 <= m <= CZ_GUMBEL_MAX_M, c_visit and c_scale finite and >= 0 (the paper: 50 and 1), CZ_ERR_ARG
+ * otherwise and when m > 0 while forced playouts or the playout cap are on (each defines its own root rule; their
+ * setters refuse likewise while m > 0).  Call it before cz_search_start_selfplay / cz_search_set_roots and before a
+ * graph capture; synchronises the stream.  Device memory: 1540 bytes per game, allocated at cz_search_create. */
+#define CZ_VISIT_GUMBEL 8u
+#define CZ_GUMBEL_MAX_M 128
+int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, void* stream);
+/* started [G][128] int32 DEVICE: the selections of the current ply per root edge, 0 for banned edges and beyond the
+ * root's edges.  Meaningful once a ply has begun with the option on; before that it holds zeros. */
+int cz_search_root_started(cz_search* s, int32_t* started, void* stream);
+/* draws [G][128] float64 DEVICE: the current ply's g_j. */
+int cz_search_gumbel_draws(cz_search* s, double* draws, void* stream);
+/* What a CZ_VISIT_GUMBEL entry of each current root would hold: m [G][128] int32 and raw_total [G], DEVICE, with the
+ * bans of the current cz_search_set_roots and the object's c_visit / c_scale.  Works with m = 0. */
+int cz_search_gumbel_targets(cz_search* s, int32_t* m, int32_t* raw_total, void* stream);
+/* The target arithmetic on its own, one wavefront per row: labels / n / w / p [rows][128] (uint16 with the banned bit /
+ * int32 / float64 / float32) and n_edges [rows] (<= 128), out_m [rows][128], out_raw_total [rows], all DEVICE.
+ * CZ_ERR_ARG: a NULL pointer, rows < 0, c_visit or c_scale negative or not finite. */
+int cz_gumbel_policy_target(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                            const uint8_t* n_edges, int rows, double c_visit, double c_scale, int32_t* out_m,
+                            int32_t* out_raw_total, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
