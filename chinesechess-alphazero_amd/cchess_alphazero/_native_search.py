@@ -102,6 +102,10 @@ def declare(L):
         "cz_search_gumbel_draws": [vp, vp, vp],
         "cz_search_gumbel_targets": [vp, vp, vp, vp],
         "cz_gumbel_policy_target": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
+        "cz_search_set_gumbel_full": [vp, i32, vp],
+        "cz_search_node_net_value": [vp, vp, i32, vp, vp],
+        "cz_gumbel_policy_target_v": [vp, vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
+        "cz_gumbel_interior_pick": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -206,6 +210,7 @@ class Search:
         self.leaf_mirror = 0.0                 # set_leaf_mirror(): the rate at which a new leaf is evaluated mirrored
         self.mirrored = None                   # set_leaf_mirror(flags=True): [slots] uint8, 1 = the slot's leaf is mirrored
         self.gumbel_m = 0                      # set_gumbel(): candidates of the Gumbel root search, 0 = off
+        self.gumbel_full = False               # set_gumbel_full(): the Gumbel rule below the root and v_mix in the target
 
     # -- lifetime --
     def close(self):
@@ -342,6 +347,32 @@ class Search:
         _native.check(self.L.cz_search_set_gumbel(self.h, int(m), float(c_visit), float(c_scale), self._stream()),
                       "cz_search_set_gumbel")
         self.gumbel_m, self.gumbel_visit, self.gumbel_scale = int(m), float(c_visit), float(c_scale)
+        if not self.gumbel_m:
+            self.gumbel_full = False           # (the library switches it off with m = 0)
+
+    def set_gumbel_full(self, on=True):
+        """The full Gumbel search (cz_search_set_gumbel_full; include/czero.h has the rule): below the root the selection is
+        argmax pi'(a) - N(a) / (1 + sum N) instead of PUCT, and the policy target completes the unvisited edges with v_mix,
+        the root's network value mixed with the visited edges' mean.  Needs set_gumbel(m > 0) first; set_gumbel(0) switches
+        it off.  It does not touch the trees: nodes attached while the Gumbel search was off carry the value 0, so
+        reset_trees() after switching the Gumbel search on over grown trees.  Call it before start_selfplay() / set_roots()
+        and before a graph capture."""
+        _native.check(self.L.cz_search_set_gumbel_full(self.h, 1 if on else 0, self._stream()), "cz_search_set_gumbel_full")
+        self.gumbel_full = bool(on)
+
+    def node_net_value(self, path=None):
+        """v [G] float32: the network value kept in the node node_stats(path) reports (cz_search_node_net_value; kept
+        while set_gumbel is on, 0 for a node attached while it was off); NaN where the position is not linked in the tree
+        or still waits for its evaluation."""
+        import torch
+        pa = np.zeros((self.G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(self.G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        v = torch.empty((self.G,), dtype=torch.float32, device=self.device)
+        _native.check(self.L.cz_search_node_net_value(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
+                                                      pa.shape[1], C.c_void_p(v.data_ptr()), self._stream()),
+                      "cz_search_node_net_value")
+        return v.cpu().numpy()
 
     def root_started(self):
         """started [G, 128] int32: the root selections of the current ply per edge (cz_search_root_started)."""
@@ -756,6 +787,44 @@ def gumbel_policy_target(labels, n, w, p, n_edges, c_visit, c_scale):
                                                         C.c_void_p(out.data_ptr()), C.c_void_p(raw.data_ptr()), stream),
                   "cz_gumbel_policy_target")
     return out, raw
+
+
+def _row_values(fn, v, rows):
+    import torch
+    if v.dtype != torch.float32 or tuple(v.shape) != (rows,) or not v.is_cuda or not v.is_contiguous():
+        raise ValueError(f"{fn}: v must be a contiguous cuda float32 tensor [{rows}]")
+    return C.c_void_p(v.data_ptr())
+
+
+def gumbel_policy_target_v(labels, n, w, p, n_edges, v, c_visit, c_scale):
+    """cz_gumbel_policy_target_v: the policy target of set_gumbel_full on caller-supplied rows -- gumbel_policy_target's
+    arguments and v float32 [rows], the rows' network values.  Returns (targets int32 [rows, 128] scaled to 65536,
+    raw_total int32 [rows]) on the device."""
+    import torch
+    rows, ptrs, ne, stream = _row_args("gumbel_policy_target_v", n_edges, (labels, "uint16"), (n, "int32"),
+                                       (w, "float64"), (p, "float32"))
+    vp = _row_values("gumbel_policy_target_v", v, rows)
+    out = torch.empty((rows, _native.MAXMOVES), dtype=torch.int32, device=n.device)
+    raw = torch.empty((rows,), dtype=torch.int32, device=n.device)
+    _native.check(_native.lib().cz_gumbel_policy_target_v(*ptrs, ne, vp, rows, float(c_visit), float(c_scale),
+                                                          C.c_void_p(out.data_ptr()), C.c_void_p(raw.data_ptr()), stream),
+                  "cz_gumbel_policy_target_v")
+    return out, raw
+
+
+def gumbel_interior_pick(n, w, p, n_edges, v, c_visit, c_scale):
+    """cz_gumbel_interior_pick: the full Gumbel search's selection below the root on caller-supplied rows.  n int32, w
+    float64, p float32, all [rows, 128] cuda tensors; n_edges uint8 [rows]; v float32 [rows].  Returns (pick int32 [rows],
+    -1 for a row without edges; score float64 [rows, 128], 0 past n_edges) on the device."""
+    import torch
+    rows, ptrs, ne, stream = _row_args("gumbel_interior_pick", n_edges, (n, "int32"), (w, "float64"), (p, "float32"))
+    vp = _row_values("gumbel_interior_pick", v, rows)
+    pick = torch.empty((rows,), dtype=torch.int32, device=n.device)
+    score = torch.empty((rows, _native.MAXMOVES), dtype=torch.float64, device=n.device)
+    _native.check(_native.lib().cz_gumbel_interior_pick(*ptrs, ne, vp, rows, float(c_visit), float(c_scale),
+                                                        C.c_void_p(pick.data_ptr()), C.c_void_p(score.data_ptr()), stream),
+                  "cz_gumbel_interior_pick")
+    return pick, score
 
 
 def root_value_rows(labels, m, n, w, n_edges):

@@ -112,6 +112,8 @@ class EngineConfig(_Section):
                          gumbel=0,                # Gumbel root search with sequential halving (run.py self --gumbel M, needs
                          gumbel_visit=50.0,       # record_visits): M candidates sampled at the root, sigma's c_visit and
                          gumbel_scale=1.0,        # c_scale; the recorded pi is softmax(log prior + sigma(completed Q)); 0 = off
+                         gumbel_full=False,       # full Gumbel search (run.py self --gumbel-full, needs gumbel): the Gumbel rule
+                                                  # below the root too, v_mix in the recorded pi (cz_search_set_gumbel_full)
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None)   # None = run forever, like the reference
 

@@ -43,7 +43,7 @@ class SelfPlayEngine:
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
-                 gumbel=None, gumbel_visit=None, gumbel_scale=None):
+                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -70,7 +70,10 @@ class SelfPlayEngine:
         gumbel_visit / gumbel_scale; gumbel 0 = off; needs record_visits, excludes fast_sims and forced_playouts): the root
         samples `gumbel` candidates through Gumbel noise, halves them over the ply's simulations and plays the survivor,
         without root noise or temperature; the pi of drain()'s items is softmax(log prior + sigma(completed Q)) scaled to
-        65536 (include/czero.h, cz_search_set_gumbel)."""
+        65536 (include/czero.h, cz_search_set_gumbel).
+        gumbel_full: the full Gumbel search (None = config.engine.gumbel_full; needs gumbel): below the root the selection
+        is argmax pi'(a) - N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes the unvisited edges with v_mix,
+        the root's network value mixed with the visited edges' mean (cz_search_set_gumbel_full)."""
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -158,8 +161,13 @@ class SelfPlayEngine:
             raise ValueError("gumbel needs record_visits: the halving counts are not a policy target")
         if self.gumbel and (self.fast_sims or self.forced_playouts):
             raise ValueError("gumbel excludes fast_sims and forced_playouts: each defines its own root rule")
+        self.gumbel_full = bool(getattr(ec, "gumbel_full", False) if gumbel_full is None else gumbel_full)
+        if self.gumbel_full and not self.gumbel:
+            raise ValueError("gumbel_full needs gumbel: it completes the Gumbel root search below the root")
         if self.gumbel:                                        # likewise
             self.search.set_gumbel(self.gumbel, self.gumbel_visit, self.gumbel_scale)
+        if self.gumbel_full:
+            self.search.set_gumbel_full(True)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py

@@ -76,6 +76,10 @@ _FLAGS = [
                            "(0 = off; the paper uses 16)")),
     ("--gumbel-visit", dict(type=float, default=50.0, metavar="C", help="(self, with --gumbel) c_visit of sigma")),
     ("--gumbel-scale", dict(type=float, default=1.0, metavar="C", help="(self, with --gumbel) c_scale of sigma")),
+    ("--gumbel-full", dict(action="store_true",
+                           help="(self, with --gumbel) full Gumbel search: below the root the selection is argmax pi'(a) - "
+                                "N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes unvisited moves with v_mix, "
+                                "the root's network value mixed with the visited moves' mean")),
     ("--sims", dict(type=int, default=None, metavar="N",
                     help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
@@ -164,7 +168,10 @@ def build_config(args):
         raise SystemExit("--gumbel excludes --fast-sims: each defines its own root rule")
     if args.gumbel and args.forced_playouts:
         raise SystemExit("--gumbel excludes --forced-playouts: each defines its own root rule")
+    if args.gumbel_full and not args.gumbel:
+        raise SystemExit("--gumbel-full needs --gumbel M: it completes the Gumbel root search below the root")
     engine.gumbel, engine.gumbel_visit, engine.gumbel_scale = args.gumbel, args.gumbel_visit, args.gumbel_scale
+    engine.gumbel_full = bool(args.gumbel_full)
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -107,6 +107,9 @@ class SelfPlayWorker:
                         f"halving over {self.config.play.simulation_num_per_move} simulations, c_visit = "
                         f"{self.engine.gumbel_visit}, c_scale = {self.engine.gumbel_scale}; no root noise, no temperature; "
                         f"the recorded pi is softmax(log prior + sigma(completed Q))")
+        if getattr(self.engine, "gumbel_full", False):
+            logger.info(f"Process {self.pid}-{self.rank}: full Gumbel search: below the root argmax pi'(a) - N(a) / (1 + sum N) "
+                        f"replaces PUCT, unvisited moves are completed with v_mix")
         if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
             logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
                         f"mirror image with probability {self.engine.leaf_mirror}")

@@ -5,7 +5,7 @@
 // the 288 GB of HBM are for.  Trees live in a POOL of 1 MiB chunks shared by all games of the search object:
 //   * a game owns a list of chunks (g_chunk_tab) and bump-allocates variable-size records in them; a record is
 //     addressed by a 32-bit id = local chunk number << 16 | 16-byte granule inside the chunk;
-//   * NODE record  = 48 B packed position | 16 B header {sum_n, move count | flags, stat id, -} | float p[nm] |
+//   * NODE record  = 48 B packed position | 16 B header {sum_n, move count | flags, stat id, net value} | float p[nm] |
 //     uint16 move[nm]: everything a wave needs to price a node's edges is one contiguous run;
 //   * STAT block   = nm x 16 B {double W, int32 N, int32 child}: allocated only when a node is first selected
 //     FROM (two nodes in three are leaves that never are), edge j of a node = granule stat + j, so an edge id is a
@@ -110,6 +110,13 @@ struct SearchParams {
     int gumbel_m;           // 0 = off; candidates sampled without replacement at the root (<= GUMBEL_MAX_M)
     double gumbel_visit;    // c_visit of sigma(x) = (c_visit + max_b n_b) * c_scale * x
     double gumbel_scale;    // c_scale
+    // full Gumbel search (cz_search_set_gumbel_full).  On the device only select_edge<GUM> reads it (the GUM
+    // instantiations of k_sim); the host reads it to launch the FULL instantiations of k_advance and k_root_records, which
+    // hold the full target (search_round_impl, launch_root_records).  While gumbel_m > 0 every attach keeps the leaf's
+    // network value in word 3 of the node header (float32, the node's mover's view; a node attached while gumbel_m = 0
+    // keeps expand_node's 0).
+    int gumbel_full;        // 0 = off; 1: below the root argmax pi'(a) - N(a) / (1 + sum N) replaces PUCT, and the policy
+                            // target completes the unvisited edges with v_mix instead of the visited edges' mean
 };
 constexpr int GUMBEL_MAX_M = 128;
 

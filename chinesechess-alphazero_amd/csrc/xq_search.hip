@@ -280,10 +280,11 @@ XQ_D void backup(const SearchParams& P, const GameView& gv, const SearchLDS& L, 
     wave_sync_global();
 }
 
-// sum_n / (move count | flags) / stat block of a node: one 16-byte load
+// sum_n / (move count | flags) / stat block / network value of a node: one 16-byte load
 struct NodeHdr {
     int sum_n;
     uint32_t meta, stat;
+    uint32_t val;       // the bits of the float32 network value (store_net_value); read by the full Gumbel search only
 };
 XQ_D NodeHdr load_hdr(char* base)
 {
@@ -295,11 +296,16 @@ XQ_D NodeHdr load_hdr(char* base)
     h.sum_n = __builtin_amdgcn_readfirstlane(v.x);
     h.meta = (uint32_t)__builtin_amdgcn_readfirstlane(v.y);
     h.stat = (uint32_t)__builtin_amdgcn_readfirstlane(v.z);
+    h.val = (uint32_t)__builtin_amdgcn_readfirstlane(v.w);
     return h;
 }
 XQ_D void store_sum_n(char* base, int v) { *reinterpret_cast<int32_t*>(base + NODE_OFF_HDR) = v; }
 XQ_D void store_meta(char* base, uint32_t v) { *reinterpret_cast<uint32_t*>(base + NODE_OFF_HDR + 4) = v; }
 XQ_D void store_stat(char* base, uint32_t v) { *reinterpret_cast<uint32_t*>(base + NODE_OFF_HDR + 8) = v; }
+// The leaf's network value, from its mover's view, as the round was handed it (a mirrored leaf's as it is): written by
+// lane 0 beside the store_meta of the attach, and only while the Gumbel root search is on (GUM instantiations of k_sim).
+// A node attached while it was off keeps the 0 of expand_node.
+XQ_D void store_net_value(char* base, float v) { *reinterpret_cast<float*>(base + NODE_OFF_HDR + 12) = v; }
 
 // ---- prior spreading: select_action_q_and_u, player.py:272-284 ----------------------------------
 // Network rows as raw logits (cz_search_policy_logits): the reference spreads the softmax output over the legal moves,
@@ -317,7 +323,10 @@ XQ_D void logits_to_weights(float& q0, float& q1, int nm)
     q1 = h1 ? __expf(q1 - m) : 0.0f;
 }
 
-XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float* __restrict__ prow, bool logits)
+// keep_v: the leaf's network value v goes into the node header as well (k_sim's keep_v: constant false outside the GUM
+// instantiations, so their text does not hold the store)
+XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float* __restrict__ prow, bool logits,
+                        bool keep_v, float v)
 {
     const int lane = lane_id();
     char* base = rec_ptr(gv, (uint32_t)node);
@@ -345,6 +354,7 @@ XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float*
     if (lane + 64 < nm) pp[lane + 64] = L.pr[lane + 64] / all_p;
     // p[j] is written and later read (select_edge) by the same lane, the header by lane 0: no global fence
     if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
+    if (keep_v && lane == 0) store_net_value(base, v);
     wave_sync();
 }
 
@@ -384,9 +394,10 @@ XQ_D void leaf_pre_b(LeafPre& lp, uint32_t meta, const float* __restrict__ prow)
 
 // `lp`: this leaf's prefetched labels / edge ids / row entries.  `next`: issued between this leaf's edge-statistics load and
 // its arithmetic -- the caller's prefetch of the following leaf.
+// keep_v: as attach_policy's; v is float(v) of the slot's float32, so the cast back is exact.
 template <typename Next>
 XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS& L, int node, uint32_t meta, int depth,
-                            const LeafPre& lp, double v, bool logits, Next&& next)
+                            const LeafPre& lp, double v, bool logits, bool keep_v, Next&& next)
 {
     const int lane = lane_id();
     char* base = rec_ptr(gv, (uint32_t)node);
@@ -411,6 +422,7 @@ XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS
     if (lane < nm) pp[lane] = p0 / all_p;
     if (lane + 64 < nm) pp[lane + 64] = p1 / all_p;
     if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
+    if (keep_v && lane == 0) store_net_value(base, (float)v);
     // update_tree (player.py:357-366): lane i = level i
     if (lane < depth) {
         const double vi = ((depth - lane) & 1) ? -v : v;
@@ -491,6 +503,71 @@ XQ_D int gumbel_argmax(double best_s, int best_j)
     return t1 ? 64 + (63 - __clzll((long long)t1)) : (t0 ? 63 - __clzll((long long)t0) : -1);
 }
 
+// ---- full Gumbel search (include/czero.h, cz_search_set_gumbel_full) ----------------------------------------------------
+// v_mix of a node: its own network value v mixed with the visited edges' prior-weighted mean q, N = sum of the edge counts,
+// A = sum of the visited edges' priors, Bq = sum of p_j q01_j over them.  (A NaN value reads as 0: never NaN.)
+XQ_D double gumbel_vmix(float v, int N, double A, double Bq)
+{
+    const double x = ((double)v + 1.0) / 2.0;
+    const double vhat = x > 0.0 ? (x > 1.0 ? 1.0 : x) : 0.0;
+    if (!(A > 0.0)) return vhat;
+    return (vhat + (double)N * (Bq / A)) / (double)(1 + N);
+}
+// The selection below the root: one wavefront, edge j = lane + 64 h of the node's nm edges; n / w as selection reads them
+// (virtual losses included), p the float32 prior, v the node's stored network value.  pi' = softmax(log p + sigma(completed
+// q)), an unvisited edge completed with v_mix; score_j = pi'_j - n_j / (1 + N), returned in score[] (0 past nm); the result
+// is the edge of the greatest score, the later one on a tie, -1 without an edge.  Float64, each sum the lane's two terms
+// first and then the DPP ladder, the maximum and the vote as select_edge's.  All 64 lanes call it.
+XQ_D int gumbel_interior(int nm, const int n[2], const double w[2], const float p[2], float v, double c_visit,
+                         double c_scale, double score[2])
+{
+    const int lane = lane_id();
+    bool live[2];
+    int s = 0, max_n = 0;
+    double A = 0.0, Bq = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        live[h] = lane + 64 * h < nm;
+        score[h] = 0.0;
+        if (!live[h]) continue;
+        s += n[h];
+        max_n = n[h] > max_n ? n[h] : max_n;
+        if (n[h] > 0) {
+            Bq = __dadd_rn(Bq, __dmul_rn((double)p[h], gumbel_q01(n[h], w[h])));
+            A = __dadd_rn(A, (double)p[h]);
+        }
+    }
+    const int N = __builtin_amdgcn_readlane(wave_incl_scan(s), 63);
+    max_n = (int)wave_max_f64((double)max_n);
+    Bq = wave_add_f64(Bq);
+    A = wave_add_f64(A);
+    const double vmix = gumbel_vmix(v, N, A, Bq);
+    double sg[2] = {0.0, 0.0}, mx = -__builtin_inf();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!live[h]) continue;
+        sg[h] = gumbel_sigma(c_visit, c_scale, max_n, n[h] > 0 ? gumbel_q01(n[h], w[h]) : vmix);
+        mx = sg[h] > mx ? sg[h] : mx;
+    }
+    mx = wave_max_f64(mx);
+    double e[2] = {0.0, 0.0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (live[h]) e[h] = __dmul_rn((double)p[h], exp(sg[h] - mx));
+    const double tot = wave_add_f64(__dadd_rn(e[0], e[1]));
+    const double d = (double)(1 + N);
+    double best_s = -__builtin_inf();
+    int best_j = -1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!live[h]) continue;
+        const double pi = tot > 0.0 ? e[h] / tot : 0.0;             // (every prior 0: the least n wins)
+        score[h] = pi - (double)n[h] / d;
+        if (score[h] >= best_s) { best_s = score[h]; best_j = lane + 64 * h; }   // h = 1 has the larger index: wins ties
+    }
+    return gumbel_argmax(best_s, best_j);
+}
+
 struct Picked {
     int j;              // edge index inside the node, -1 = none
     bool have;          // n / w / child / mv below are valid (winner among the first 64 edges)
@@ -544,15 +621,36 @@ XQ_D int select_gumbel(int gumbel_m, double c_visit, double c_scale, int32_t* st
 
 // base: the node's record; sb: its stat block (nullptr: allocated in this visit, every edge is {0, 0, unknown}).
 // GUM: the k_sim instantiation that is launched while the Gumbel root search is on -- the others do not hold its code,
-// so their registers and their text are what they were without it.
+// so their registers and their text are what they were without it.  net_value: the header's fourth word (GUM only).
 template <bool GUM>
 XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, char* base, const EdgeStat* sb, int sum_n,
-                        int nm, const RootCtx& rc)
+                        int nm, const RootCtx& rc, uint32_t net_value)
 {
     if (GUM && rc.is_root && P.gumbel_m > 0) {                  // wave-uniform
         Picked r;                                               // (have = false: the caller reloads the edge, this is not the hot path)
         r.j = select_gumbel(P.gumbel_m, P.gumbel_visit, P.gumbel_scale, B.g_started + (size_t)g * MAXMOVES,
                             B.g_gumbel + (size_t)g * MAXMOVES, uni(B.g_budget[g]), base, sb, nm, rc.n_no_act, rc.no_act);
+        r.have = false;
+        r.n = 0; r.child = CHILD_UNKNOWN; r.mv = 0; r.w = 0.0;
+        return r;
+    }
+    if (GUM && !rc.is_root && P.gumbel_full && P.gumbel_m > 0) {    // wave-uniform
+        // the full search below the root: the whole selection, the proven-win shortcut included, is gumbel_interior's.
+        // Every edge takes part (only roots have bans); edge j is loaded by the lane that owns it, as below.
+        const int lane = lane_id();
+        const float* pp = node_p(base);
+        int n[2] = {0, 0};
+        double w[2] = {0.0, 0.0}, score[2];
+        float p[2] = {0.0f, 0.0f};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            if (sb) { const EdgeStat es = sb[j]; n[h] = es.n; w[h] = es.w; }
+            p[h] = pp[j];
+        }
+        Picked r;
+        r.j = gumbel_interior(nm, n, w, p, __uint_as_float(net_value), P.gumbel_visit, P.gumbel_scale, score);
         r.have = false;
         r.n = 0; r.child = CHILD_UNKNOWN; r.mv = 0; r.w = 0.0;
         return r;
@@ -936,7 +1034,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         RootCtx rc = rc0;
         rc.is_root = (node == root);                                // player.py:266
         rc.sim = sim;
-        const Picked pk = select_edge<GUM>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc);
+        const Picked pk = select_edge<GUM>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc, hdr.val);
         if (pk.j < 0) {                                             // "Best action is None": cannot happen
             backup(P, gv, L, depth, 0.0);
             sim_finish(gv, sim, active);
@@ -1469,6 +1567,14 @@ XQ_D RootEdges load_root_edges(const SearchBuffers& B, const GameView& gv)
     return E;
 }
 
+// the stored network value of the game's current root (store_net_value); no root: 0
+XQ_D float root_net_value(const SearchBuffers& B, const GameView& gv)
+{
+    const int root = uni(B.g_root[gv.g]);
+    if (root < 0) return 0.0f;
+    return __uint_as_float(load_hdr(rec_ptr(gv, (uint32_t)root)).val);
+}
+
 // ... of row r of caller-supplied arrays [rows][128]; a NULL array stays zero
 XQ_D RootEdges load_row_edges(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
                               const double* __restrict__ w, const float* __restrict__ p,
@@ -1528,8 +1634,12 @@ XQ_D int gumbel_choose(const SearchParams& P, const SearchBuffers& B, const Game
 // VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise.  m[] receives floor(65536 pi'_j + 1/2),
 // pi' = softmax(log p + sigma(completed q)); banned edges 0.  Float64, each sum the lane's two terms first and then the
 // DPP ladder.  Returns S, the raw total of the non-banned edges.  All 64 lanes call it.
+// FULL (cz_search_set_gumbel_full): an unvisited edge is completed with v_mix of the root -- gumbel_vmix over the non-banned
+// edges with the root's stored network value v -- instead of the visited edges' mean vbar: the paper's target.  Nothing
+// visited: every edge is completed with vhat and the target is the prior.  The <false> instantiation is the text it was.
+template <bool FULL>
 XQ_D int gumbel_targets(int nm, const uint16_t lab[2], int m[2], const int n[2], const double w[2], const float p[2],
-                        double c_visit, double c_scale)
+                        double c_visit, double c_scale, float v = 0.0f)
 {
     const int lane = lane_id();
     bool live[2];
@@ -1551,7 +1661,8 @@ XQ_D int gumbel_targets(int nm, const uint16_t lab[2], int m[2], const int n[2],
     max_n = (int)wave_max_f64((double)max_n);
     num = wave_add_f64(num);
     den = wave_add_f64(den);
-    const double vbar = den > 0.0 ? num / den : 0.5;            // (nothing visited, or only edges of prior 0: one half)
+    const double vbar = FULL ? gumbel_vmix(v, S, den, num)
+                             : (den > 0.0 ? num / den : 0.5);   // (nothing visited, or only edges of prior 0: one half)
     double sg[2] = {0.0, 0.0}, mx = -__builtin_inf();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1681,6 +1792,8 @@ XQ_D double root_surprise(int nm, const uint16_t lab[2], const int m[2], const f
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
 // raw_total); the tree keeps the raw counts and choose_action has already used them.
+// FULL: a Gumbel ply's target is the full search's (gumbel_targets<true> with the root's stored value).
+template <bool FULL>
 XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns,
                       bool resigned, bool fast, bool prune, bool gumbel)
 {
@@ -1706,7 +1819,8 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
     const int nm = E.nm;
     int m[2] = {E.n[0], E.n[1]};            // the counts the entry records: raw, or pruned
     // (a Gumbel ply: the counts are the policy target pi' scaled to 65536 -- the halving counts are no target)
-    const int raw_total = gumbel ? gumbel_targets(nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale)
+    const int raw_total = gumbel ? gumbel_targets<FULL>(nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale,
+                                                        FULL ? root_net_value(B, gv) : 0.0f)
                                  : (prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k) : 0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1736,6 +1850,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
 }
 
 // One ply of SelfPlayWorker.start_game after the search finished (self_play.py:124-212).
+template <bool FULL>        // (emit_visits')
 XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                        const VisitRing& V)
 {
@@ -1750,7 +1865,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);
-        emit_visits(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0);
+        emit_visits<FULL>(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0);
     }
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;
@@ -1891,6 +2006,8 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
     const bool force = P.forced_k > 0.0 && !ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g]));
     const RootCtx rc{false, uni((int)B.g_n_no_act[g]), B.g_no_act + (size_t)g * MAX_NO_ACT,
                      noisy ? B.noise + (size_t)g * P.K * MAXMOVES : nullptr, 0, force};
+    // while the Gumbel root search is on every attach keeps the leaf's network value in the node header (store_net_value)
+    const bool keep_v = GUM && P.gumbel_m > 0;
     int resume_i = P.K;
     // the slot table as it is when the launch starts, slot i on lane i: one load per array instead of one dependent
     // round trip per slot and field (a simulation only ever changes its own slot, and each slot is visited once per list)
@@ -1947,11 +2064,11 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
             LeafPre nx{0, 0, 0, 0.0f, 0.0f};
             if (depth <= 64) {
                 attach_and_backup(P, gv, L, node, (uint32_t)__builtin_amdgcn_readlane((int)my_meta, i), depth, lp, v,
-                                  P.policy_logits != 0, [&]() {
+                                  P.policy_logits != 0, keep_v, [&]() {
                                       if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
                                   });
             } else {
-                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, keep_v, (float)v);
                 load_path(P, gv, L, i, depth);
                 backup(P, gv, L, depth, v);
                 if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
@@ -1971,7 +2088,7 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
                 const int row = uni(B.s_qrow[slot]);
                 if (row >= 0) slot = (size_t)row;
             }
-            attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0);
+            attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, keep_v, value[slot]);
             load_path(P, gv, L, i, depth);
             backup(P, gv, L, depth, (double)value[slot]);             // float(v) of a float32
             sim_finish(gv, i, &active);
@@ -2046,6 +2163,9 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
 
 // End of a search: external mode marks the game READY; self-play mode plays the move, applies the game rules
 // and sets up the next search (or the next game).
+// FULL: the full Gumbel search is on (cz_search_set_gumbel_full): the visit entries hold its target.  An instantiation of
+// its own, so that the kernel launched while it is off is the text it was.
+template <bool FULL>
 __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B, VisitRing V)
 {
     __shared__ SearchLDS L;
@@ -2056,7 +2176,7 @@ __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B,
     counters_begin(gv);
     if (P.mode == MODE_SELFPLAY) {
         for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
-            advance_game(P, B, gv, L, V);
+            advance_game<FULL>(P, B, gv, L, V);
             if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
         }
     } else if (lane_id() == 0) {
@@ -2217,19 +2337,12 @@ __global__ void k_leaf_rows(SearchParams P, SearchBuffers B, int32_t* __restrict
     if (B.s_state[slot] == SIM_LEAF) rows[atomicAdd(&counts[1], 1)] = slot;
 }
 
-// statistics of the root, or of the node reached from the root along path[g][0 .. path_len) (move labels, NOMOVE ends
-// the path early); a node that is not linked in the tree reports count 0
-__global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
-                                                  int path_len, uint16_t* __restrict__ moves,
-                                                  int32_t* __restrict__ n, double* __restrict__ w,
-                                                  float* __restrict__ p, int32_t* __restrict__ sum_n,
-                                                  uint8_t* __restrict__ counts)
+// the node reached from the game's root along path[g][0 .. path_len) (move labels, NOMOVE ends the path early; NULL: the
+// root), -1 when it is not linked in the tree.  All 64 lanes call it.
+XQ_D int walk_path(const SearchBuffers& B, const GameView& gv, const uint16_t* __restrict__ path, int path_len)
 {
-    __shared__ uint32_t chtab[MAX_CHUNKS];
-    const int g = blockIdx.x;
-    if (g >= P.G) return;
-    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);   // counts go straight to the global block
     const int lane = lane_id();
+    const int g = gv.g;
     int root = B.g_root[g];
     for (int d = 0; path && d < path_len && root >= 0; ++d) {
         const uint16_t mv = path[(size_t)g * path_len + d];
@@ -2247,6 +2360,23 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
         const unsigned long long hit = __ballot(child >= 0);
         root = hit ? __shfl(child, __ffsll((long long)hit) - 1) : -1;
     }
+    return root;
+}
+
+// statistics of the root, or of the node reached from the root along path[g][0 .. path_len) (move labels, NOMOVE ends
+// the path early); a node that is not linked in the tree reports count 0
+__global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                  int path_len, uint16_t* __restrict__ moves,
+                                                  int32_t* __restrict__ n, double* __restrict__ w,
+                                                  float* __restrict__ p, int32_t* __restrict__ sum_n,
+                                                  uint8_t* __restrict__ counts)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);   // counts go straight to the global block
+    const int lane = lane_id();
+    const int root = walk_path(B, gv, path, path_len);
     int nm = 0, root_sum_n = 0;
     char* base = nullptr;
     const EdgeStat* sb = nullptr;
@@ -2275,7 +2405,9 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
 // What emit_visits would record for every current root, with the bans of the current set_roots (cz_search_root_targets,
 // _root_value, _root_surprise): the pruned counts n [G][128] and their raw total, the search value q, the policy
 // surprise s.  A NULL output is not computed.  One wavefront per game.
-// gumbel (or the option on): the counts are the Gumbel policy targets, as a VISIT_GUMBEL entry holds them.
+// gumbel (or the option on): the counts are the Gumbel policy targets, as a VISIT_GUMBEL entry holds them; FULL: the full
+// search's (launched while cz_search_set_gumbel_full is on).
+template <bool FULL>
 __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
                                                     int32_t* __restrict__ raw_total, double* __restrict__ q,
                                                     double* __restrict__ s, int gumbel)
@@ -2287,7 +2419,8 @@ __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffe
     const int lane = lane_id();
     const RootEdges E = load_root_edges(B, gv);
     int m[2] = {E.n[0], E.n[1]};
-    const int S = (gumbel || P.gumbel_m > 0) ? gumbel_targets(E.nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale)
+    const int S = (gumbel || P.gumbel_m > 0) ? gumbel_targets<FULL>(E.nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale,
+                                                                    FULL ? root_net_value(B, gv) : 0.0f)
                                              : prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k);
     if (n) {
 #pragma unroll
@@ -2339,21 +2472,69 @@ __global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__
 }
 
 // cz_gumbel_policy_target: gumbel_targets on caller-supplied rows [rows][128], one wavefront per row
+// FULL (cz_gumbel_policy_target_v): the full search's target, v [rows] the rows' network values
+template <bool FULL>
 __global__ __launch_bounds__(64) void k_gumbel_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
                                                    const double* __restrict__ w, const float* __restrict__ p,
                                                    const uint8_t* __restrict__ n_edges, int rows, double c_visit,
                                                    double c_scale, int32_t* __restrict__ out_m,
-                                                   int32_t* __restrict__ out_raw_total)
+                                                   int32_t* __restrict__ out_raw_total, const float* __restrict__ v)
 {
     const int r = blockIdx.x;
     if (r >= rows) return;
     const int lane = lane_id();
     const RootEdges E = load_row_edges(labels, n, w, p, n_edges, r);
     int m[2];
-    const int S = gumbel_targets(E.nm, E.lab, m, E.n, E.w, E.p, c_visit, c_scale);
+    const int S = gumbel_targets<FULL>(E.nm, E.lab, m, E.n, E.w, E.p, c_visit, c_scale, FULL ? v[r] : 0.0f);
 #pragma unroll
     for (int h = 0; h < 2; ++h) out_m[(size_t)r * MAXMOVES + lane + 64 * h] = m[h];
     if (lane == 0) out_raw_total[r] = S;
+}
+
+// cz_search_node_net_value: the stored network value (store_net_value) of the node k_root_stats reports for the same path;
+// NaN when the position is not linked in the tree or still waits for its evaluation.  One wavefront per game.
+__global__ __launch_bounds__(64) void k_node_net_value(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                      int path_len, float* __restrict__ v)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int node = walk_path(B, gv, path, path_len);
+    float out = __builtin_nanf("");
+    if (node >= 0) {
+        const NodeHdr hdr = load_hdr(rec_ptr(gv, (uint32_t)node));
+        if (!(hdr.meta & NODE_WAITING)) out = __uint_as_float(hdr.val);
+    }
+    if (lane_id() == 0) v[g] = out;
+}
+
+// cz_gumbel_interior_pick: gumbel_interior, the full search's selection below the root, on caller-supplied rows
+// [rows][128], one wavefront per row; out_score [rows][128] (0 past n_edges), out_pick -1 for a row without edges
+__global__ __launch_bounds__(64) void k_gumbel_interior_rows(const int32_t* __restrict__ n, const double* __restrict__ w,
+                                                            const float* __restrict__ p,
+                                                            const uint8_t* __restrict__ n_edges,
+                                                            const float* __restrict__ v, int rows, double c_visit,
+                                                            double c_scale, int32_t* __restrict__ out_pick,
+                                                            double* __restrict__ out_score)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    const int nm = n_edges[r] > MAXMOVES ? MAXMOVES : n_edges[r];
+    int nn[2] = {0, 0};
+    double ww[2] = {0.0, 0.0}, score[2];
+    float pp[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
+        if (lane + 64 * h >= nm) continue;
+        nn[h] = n[i]; ww[h] = w[i]; pp[h] = p[i];
+    }
+    const int pick = gumbel_interior(nm, nn, ww, pp, v[r], c_visit, c_scale, score);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) out_score[(size_t)r * MAXMOVES + lane + 64 * h] = score[h];
+    if (lane == 0) out_pick[r] = pick;
 }
 
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps
@@ -2794,7 +2975,8 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
         }
     };
     sim(SIM_BACKUP, consume_compact);
-    hipLaunchKernelGGL(k_advance, grid, block, 0, st, s->P, s->B, s->V);
+    if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
+    else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
@@ -2984,6 +3166,16 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
 
 static_assert(CZ_VISIT_GUMBEL == VISIT_GUMBEL && CZ_GUMBEL_MAX_M == GUMBEL_MAX_M, "czero.h: Gumbel root search");
 
+// k_root_records, the instantiation of the object's setting (cz_search_set_gumbel_full)
+static void launch_root_records(cz_search* s, hipStream_t st, const SearchParams& P, const SearchBuffers& B, int32_t* n,
+                                int32_t* raw_total, double* q, double* sv, int gumbel)
+{
+    if (P.gumbel_m > 0 && P.gumbel_full)
+        hipLaunchKernelGGL(k_root_records<true>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel);
+    else
+        hipLaunchKernelGGL(k_root_records<false>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel);
+}
+
 int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_set_gumbel: null handle");
@@ -2997,6 +3189,27 @@ int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, vo
     s->P.gumbel_m = m;
     s->P.gumbel_visit = c_visit;
     s->P.gumbel_scale = c_scale;
+    if (m == 0) s->P.gumbel_full = 0;                           // (the full search is an option of the Gumbel root search)
+    return CZ_OK;
+}
+
+int cz_search_set_gumbel_full(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_gumbel_full: null handle");
+    if (on != 0 && on != 1) return serr(CZ_ERR_ARG, "cz_search_set_gumbel_full: on is neither 0 nor 1");
+    if (on && s->P.gumbel_m == 0)
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel_full: the Gumbel root search is off (cz_search_set_gumbel)");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_gumbel_full", e);
+    s->P.gumbel_full = on;
+    return CZ_OK;
+}
+
+int cz_search_node_net_value(cz_search* s, const uint16_t* path, int path_len, float* v, void* stream)
+{
+    if (!s || !v || path_len < 0 || (path_len > 0 && !path)) return serr(CZ_ERR_ARG, "cz_search_node_net_value: bad argument");
+    hipLaunchKernelGGL(k_node_net_value, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, path, path_len, v);
+    S_LAUNCH_CHECK("cz_search_node_net_value");
     return CZ_OK;
 }
 
@@ -3019,7 +3232,7 @@ int cz_search_gumbel_draws(cz_search* s, double* draws, void* stream)
 int cz_search_gumbel_targets(cz_search* s, int32_t* m, int32_t* raw_total, void* stream)
 {
     if (!s || !m || !raw_total) return serr(CZ_ERR_ARG, "cz_search_gumbel_targets: null argument");
-    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, m, raw_total,
+    launch_root_records(s, (hipStream_t)stream, s->P, s->B, m, raw_total,
                        (double*)nullptr, (double*)nullptr, 1);
     S_LAUNCH_CHECK("cz_search_gumbel_targets");
     return CZ_OK;
@@ -3034,9 +3247,38 @@ int cz_gumbel_policy_target(const uint16_t* labels, const int32_t* n, const doub
     if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
         return serr(CZ_ERR_ARG, "cz_gumbel_policy_target: c_visit or c_scale negative or not finite");
     if (rows == 0) return CZ_OK;
-    hipLaunchKernelGGL(k_gumbel_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows, c_visit,
-                       c_scale, out_m, out_raw_total);
+    hipLaunchKernelGGL(k_gumbel_rows<false>, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows,
+                       c_visit, c_scale, out_m, out_raw_total, (const float*)nullptr);
     S_LAUNCH_CHECK("cz_gumbel_policy_target");
+    return CZ_OK;
+}
+
+int cz_gumbel_policy_target_v(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                              const uint8_t* n_edges, const float* v, int rows, double c_visit, double c_scale,
+                              int32_t* out_m, int32_t* out_raw_total, void* stream)
+{
+    if (!labels || !n || !w || !p || !n_edges || !v || !out_m || !out_raw_total || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_gumbel_policy_target_v: null argument or rows < 0");
+    if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
+        return serr(CZ_ERR_ARG, "cz_gumbel_policy_target_v: c_visit or c_scale negative or not finite");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_gumbel_rows<true>, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, p, n_edges, rows,
+                       c_visit, c_scale, out_m, out_raw_total, v);
+    S_LAUNCH_CHECK("cz_gumbel_policy_target_v");
+    return CZ_OK;
+}
+
+int cz_gumbel_interior_pick(const int32_t* n, const double* w, const float* p, const uint8_t* n_edges, const float* v,
+                            int rows, double c_visit, double c_scale, int32_t* out_pick, double* out_score, void* stream)
+{
+    if (!n || !w || !p || !n_edges || !v || !out_pick || !out_score || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_gumbel_interior_pick: null argument or rows < 0");
+    if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
+        return serr(CZ_ERR_ARG, "cz_gumbel_interior_pick: c_visit or c_scale negative or not finite");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_gumbel_interior_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, n, w, p, n_edges, v, rows,
+                       c_visit, c_scale, out_pick, out_score);
+    S_LAUNCH_CHECK("cz_gumbel_interior_pick");
     return CZ_OK;
 }
 
@@ -3062,7 +3304,7 @@ int cz_search_set_leaf_mirror(cz_search* s, double rate, uint8_t* flags_or_null,
 int cz_search_root_targets(cz_search* s, int32_t* n, int32_t* raw_total, void* stream)
 {
     if (!s || !n || !raw_total) return serr(CZ_ERR_ARG, "cz_search_root_targets: null argument");
-    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, n, raw_total,
+    launch_root_records(s, (hipStream_t)stream, s->P, s->B, n, raw_total,
                        (double*)nullptr, (double*)nullptr, 0);
     S_LAUNCH_CHECK("cz_search_root_targets");
     return CZ_OK;
@@ -3093,7 +3335,7 @@ int cz_search_record_values(cz_search* s, int on, void* stream)
 int cz_search_root_value(cz_search* s, double* q, void* stream)
 {
     if (!s || !q) return serr(CZ_ERR_ARG, "cz_search_root_value: null argument");
-    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
+    launch_root_records(s, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
                        (int32_t*)nullptr, q, (double*)nullptr, 0);
     S_LAUNCH_CHECK("cz_search_root_value");
     return CZ_OK;
@@ -3123,7 +3365,7 @@ int cz_search_record_surprise(cz_search* s, int on, void* stream)
 int cz_search_root_surprise(cz_search* s, double* out, void* stream)
 {
     if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_surprise: null argument");
-    hipLaunchKernelGGL(k_root_records, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
+    launch_root_records(s, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
                        (int32_t*)nullptr, (double*)nullptr, out, 0);
     S_LAUNCH_CHECK("cz_search_root_surprise");
     return CZ_OK;

@@ -521,7 +521,7 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
  * the LATER edge on a tie, as PUCT's `>=` does; p_j = 0 scores -infinity and loses to any finite score.  The first m
  * selections so pick the m greatest g_j + log p_j (+ sigma of what a reused root knows), the Gumbel top-m sample; from
  * then on only they are eligible.  The rule replaces the root's whole selection, the proven-win shortcut included;
- * below the root the search is PUCT as it is.
+ * below the root the search is PUCT as it is (cz_search_set_gumbel_full below replaces it there too).
  *
  * MOVE PLAYED.  Among the edges with the greatest started_j the greatest of the same score, w and n as they are after
  * the last backup.  cz_search_choose ignores u; the resign test is unchanged.  A Gumbel ply has no temperature and no
@@ -533,7 +533,8 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
  *       pi'_j = p_j exp(sigma(cq_j) - max_b sigma(cq_b)) / sum over the edges
  *       m_j = floor(65536 pi'_j + 1/2); banned edges 0; all 0 when no edge has a positive prior
  * The paper also mixes the root's own network value into vbar with weight 1 / (1 + sum n); the node record holds no
- * value and that weight is below 6 % at 16 simulations, so it is LEFT OUT here.  exp and log are the device library's
+ * value and that weight is below 6 % at 16 simulations, so it is LEFT OUT here (cz_search_set_gumbel_full, below, keeps
+ * the value and puts it in).  exp and log are the device library's
  * float64 routines: m_j may differ by 1 from another implementation's.
  *
  * VISIT RECORD.  An entry of a Gumbel ply carries CZ_VISIT_GUMBEL, n[] holds m_j (a trainer that normalises n[] gets
@@ -561,6 +562,59 @@ int cz_search_gumbel_targets(cz_search* s, int32_t* m, int32_t* raw_total, void*
 int cz_gumbel_policy_target(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
                             const uint8_t* n_edges, int rows, double c_visit, double c_scale, int32_t* out_m,
                             int32_t* out_raw_total, void* stream);
+/* ---- full Gumbel search: the rule below the root and v_mix (run.py self --gumbel-full) ------------------------------
+ * The two parts of the paper that cz_search_set_gumbel leaves out; an option of it, off after cz_search_create.  With it
+ * off no kernel output, record, counter or entry differs by a bit from what cz_search_set_gumbel alone gives.
+ *
+ * NODE VALUE.  While m > 0 (full on or off) every attach of an evaluated leaf keeps the leaf's network value in the
+ * fourth word of the node header: the float32 the round was handed for the slot, from the node's mover's view -- the
+ * value that is backed up; a leaf evaluated in its mirror image keeps the value as it came.  It costs no memory and no
+ * load: the word was free and travels with the header.  A node attached while m = 0 carries 0.
+ *
+ * SELECTION BELOW THE ROOT.  With full on, at every node that is not the root the whole selection -- PUCT and the
+ * proven-win shortcut -- is replaced by (float64; all edges of the node, only roots have bans; n_j, w_j as selection
+ * reads them, virtual losses of simulations in flight included; p_j the float32 prior; v the node's stored value):
+ *       N      = sum_j n_j
+ *       vhat   = clamp((v + 1) / 2, 0, 1)
+ *       A      = sum_{n_j > 0} p_j          B = sum_{n_j > 0} p_j q01_j
+ *       v_mix  = (vhat + N (B / A)) / (1 + N) where A > 0, else vhat
+ *       cq_j   = q01_j where n_j > 0, else v_mix
+ *       s_j    = sigma(cq_j)                (max_b n_b over the node's edges)
+ *       e_j    = p_j exp(s_j - max_b s_b)   T = sum_j e_j
+ *       pi'_j  = e_j / T                    (0 for every j when T is not > 0)
+ *       score_j = pi'_j - n_j / (1 + N)
+ * and the edge of the greatest score is taken, the LATER edge on a tie.  No exploration constant: the visit counts of a
+ * node follow pi'.  Nothing visited: pi' is the normalised prior.  Every prior 0: the least n_j wins.  The root keeps the
+ * halving; virtual loss, sum_n, expansion, terminal and repeated positions and parking are what they were.  The sums
+ * run over the lane's two edges and then one ladder over the 64 lanes; exp is the device library's float64 routine, so a
+ * score may differ from another implementation's in its last places (1e-12 is generous).
+ *
+ * POLICY TARGET.  With full on vbar is replaced by v_mix of the root -- the formula above over the NON-BANNED edges with
+ * the root's stored value -- which is the paper's target.  Nothing visited: cq_j = vhat for every edge and the target
+ * is the prior.  The target feeds the visit entries, cz_search_root_targets and cz_search_gumbel_targets, and through
+ * the recorded n[] the value and the surprise record, which keep their definitions.
+ *
+ * cz_search_set_gumbel_full: on is 0 or 1.  CZ_ERR_ARG when s is NULL, when on is anything else, or when on = 1 while
+ * m = 0; the object keeps its setting.  cz_search_set_gumbel(m = 0) also switches it off.  Call it before
+ * cz_search_start_selfplay / cz_search_set_roots and before a graph capture; synchronises the stream.  It does not
+ * touch the trees: nodes attached while m = 0 carry the value 0 (vhat = 1/2), so a caller who grew trees before
+ * switching the Gumbel search on should call cz_search_reset_trees first. */
+int cz_search_set_gumbel_full(cz_search* s, int on, void* stream);
+/* v [G] float32 DEVICE: the stored network value of the node cz_search_node_stats would report for the same path
+ * (path NULL / path_len 0: the root); NaN when the position is not linked in the tree or is still waiting for its
+ * evaluation.  0 for a node attached while m = 0. */
+int cz_search_node_net_value(cz_search* s, const uint16_t* path, int path_len, float* v, void* stream);
+/* cz_gumbel_policy_target with v [rows] float32 DEVICE, the rows' network values: the full search's target of
+ * caller-supplied rows.  Same argument checks. */
+int cz_gumbel_policy_target_v(const uint16_t* labels, const int32_t* n, const double* w, const float* p,
+                              const uint8_t* n_edges, const float* v, int rows, double c_visit, double c_scale,
+                              int32_t* out_m, int32_t* out_raw_total, void* stream);
+/* The selection below the root on its own, one wavefront per row through the device function the search calls: n / w / p
+ * [rows][128] (int32 / float64 / float32), n_edges [rows] (<= 128), v [rows] float32; out_pick [rows] int32, -1 for a
+ * row without edges; out_score [rows][128] float64, every edge's score, 0 past n_edges.  All DEVICE.  CZ_ERR_ARG: a NULL
+ * pointer, rows < 0, c_visit or c_scale negative or not finite. */
+int cz_gumbel_interior_pick(const int32_t* n, const double* w, const float* p, const uint8_t* n_edges, const float* v,
+                            int rows, double c_visit, double c_scale, int32_t* out_pick, double* out_score, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate

@@ -3,6 +3,9 @@
 
     python tools/gumbel_cost.py [--rounds 1500] [--ms 0,16] [--reps 2]
     -> one JSON line, also written to --out (default profiles/gumbel_cost.json)
+    python tools/gumbel_cost.py --full [--sims 32] [--ms 16]
+    -> the full Gumbel search (engine.gumbel_full, cz_search_set_gumbel_full): every M > 0 runs with full off and on,
+       alternating, at --sims simulations per move; default --out profiles/gumbel_full_cost.json
 
 Legs walk through the candidate counts M (0 = off), --reps times over, in ONE process, each a fresh engine (same seed,
 same random network) at the configuration's simulations per move, driven the way the self-play worker drives it: HIP
@@ -25,17 +28,19 @@ for p in (ROOT, os.path.join(ROOT, "chinesechess-alphazero_amd")):
         sys.path.insert(0, p)
 
 
-def leg(m, rounds, every):
+def leg(m, rounds, every, full=False, sims=None):
     import torch
     import bench
     from cchess_alphazero.agent.model import CChessNet
     from cchess_alphazero.engine import SelfPlayEngine
     cfg = bench.build_config(types.SimpleNamespace(config="normal", games=None, sims_per_round=None, dtype=None,
                                                    trunk=None))
+    if sims:
+        cfg.play.simulation_num_per_move = sims
     torch.manual_seed(0)
     net = CChessNet.from_model_config(cfg.model)
     eng = SelfPlayEngine(cfg, cfg.engine.games_per_gpu, net=net, dtype=getattr(torch, cfg.engine.net_dtype), seed=20261019,
-                         record_visits=True, gumbel=m)
+                         record_visits=True, gumbel=m, gumbel_full=full)
     try:
         eng.start(0, 0)
         eng.prewarm()
@@ -54,7 +59,7 @@ def leg(m, rounds, every):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         c1 = eng.counters()
-        return dict(gumbel=m, sims=cfg.play.simulation_num_per_move, rounds=rounds, seconds=dt,
+        return dict(gumbel=m, full=bool(full), sims=cfg.play.simulation_num_per_move, rounds=rounds, seconds=dt,
                     expansions_per_s=(c1["expansions"] - c0["expansions"]) / dt, games=games, plies=c1["plies"] - c0["plies"],
                     visits_dropped=c1.get("visits_dropped", 0))
     finally:
@@ -68,24 +73,39 @@ def main():
     ap.add_argument("--ms", default="0,16")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--every", type=int, default=200, help="drain cadence (rounds), the worker's report_every_rounds")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gumbel_cost.json"))
+    ap.add_argument("--full", action="store_true", help="the full Gumbel search: every M > 0 with full off and on")
+    ap.add_argument("--sims", type=int, default=None, help="simulations per move (default: the configuration's; --full: 32)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.full and args.ms == "0,16":
+        args.ms = "16"
+    if args.full and args.sims is None:
+        args.sims = 32
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "gumbel_full_cost.json" if args.full else "gumbel_cost.json")
     ms = [int(x) for x in args.ms.split(",")]
     if not ms or any(not 0 <= m <= 128 for m in ms):
         raise SystemExit(f"--ms {args.ms!r}: expected integers in 0 .. 128")
     legs = []
     for _ in range(args.reps):
         for m in ms:
-            legs.append(leg(m, args.rounds, args.every))
-            print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
+            for full in ((False, True) if args.full and m > 0 else (False,)):
+                legs.append(leg(m, args.rounds, args.every, full, args.sims))
+                print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
     by_m = {}
     for m in ms:
-        xs = [x["expansions_per_s"] for x in legs if x["gumbel"] == m]
-        by_m[str(m)] = dict(expansions_per_s=xs, mean=sum(xs) / len(xs), spread=(max(xs) - min(xs)) / (sum(xs) / len(xs)))
+        for full in (False, True):
+            xs = [x["expansions_per_s"] for x in legs if x["gumbel"] == m and x["full"] == full]
+            if xs:
+                by_m[f"{m}+full" if full else str(m)] = dict(expansions_per_s=xs, mean=sum(xs) / len(xs),
+                                                             spread=(max(xs) - min(xs)) / (sum(xs) / len(xs)))
     base = by_m.get("0", {}).get("mean")
     if base:
         for v in by_m.values():
             v["over_off"] = v["mean"] / base
+    for m in ms:                                                # the full search against the root-only search of the same M
+        if f"{m}+full" in by_m:
+            by_m[f"{m}+full"]["over_root_only"] = by_m[f"{m}+full"]["mean"] / by_m[str(m)]["mean"]
     out = dict(by_m=by_m, legs=legs)
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -3,6 +3,8 @@
 
     python tools/gumbel_effect.py --fresh [--filters 128] [--blocks 7] [--positions 64] [--m 16] [--reps 4]
     -> one JSON line, also written to --out (default profiles/gumbel_effect.json)
+    python tools/gumbel_effect.py --fresh --full
+    -> the same with a third column, the full Gumbel search (--gumbel-full); default --out profiles/gumbel_full_effect.json
 
 The network is the peaked-policy stand-in of a trained one: freshly initialised weights whose policy layer is scaled
 until the largest probability on the positions is >= 0.85 (bench.sharpened_copy; real weights are not obtainable here).
@@ -24,7 +26,7 @@ for p in (ROOT, os.path.join(ROOT, "chinesechess-alphazero_amd")):
         sys.path.insert(0, p)
 
 
-def search_moves(boards, net, sims, threads, seed, play, gumbel=0, noisy=False, rng=None):
+def search_moves(boards, net, sims, threads, seed, play, gumbel=0, noisy=False, rng=None, full=False):
     """The move each root plays: label per position."""
     import torch
     from cchess_alphazero import _native
@@ -37,6 +39,8 @@ def search_moves(boards, net, sims, threads, seed, play, gumbel=0, noisy=False, 
     try:
         if gumbel:
             s.set_gumbel(gumbel)
+        if full:
+            s.set_gumbel_full(True)
         s.set_roots(torch.from_numpy(boards).cuda())
         with torch.no_grad():
             s.run_until_idle(lambda planes: net(planes.contiguous()))
@@ -58,8 +62,11 @@ def main():
     ap.add_argument("--reference-sims", type=int, default=800)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--seed", type=int, default=20261019)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gumbel_effect.json"))
+    ap.add_argument("--full", action="store_true", help="also the full Gumbel search (set_gumbel_full)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "gumbel_full_effect.json" if args.full else "gumbel_effect.json")
     if not args.fresh:
         ap.error("--fresh: no saved weights are available here")
     import numpy as np
@@ -88,15 +95,20 @@ def main():
                filters=args.filters, blocks=args.blocks, policy_layer_scale=scale, max_policy_probability=float(ref[0].max()),
                arith=net.arith_effective, noise_eps=play.noise_eps, tau_decay_rate=play.tau_decay_rate, budgets={})
     for n in [int(x) for x in args.budgets.split(",")]:
-        hit = dict(gumbel=[], puct=[])
+        hit = dict(gumbel=[], puct=[], full=[])
         for rep in range(args.reps):
             seed = args.seed + 1 + rep
             g = np.asarray(search_moves(boards, net, n, K, seed, play, gumbel=args.m))
             p = np.asarray(search_moves(boards, net, n, K, seed, play, noisy=True, rng=np.random.default_rng(seed)))
+            if args.full:
+                f = np.asarray(search_moves(boards, net, n, K, seed, play, gumbel=args.m, full=True))
+                hit["full"].append(float((f == best).mean()))
             hit["gumbel"].append(float((g == best).mean()))
             hit["puct"].append(float((p == best).mean()))
         out["budgets"][str(n)] = dict(gumbel_same_move=float(np.mean(hit["gumbel"])), puct_same_move=float(np.mean(hit["puct"])),
                                       gumbel_by_rep=hit["gumbel"], puct_by_rep=hit["puct"])
+        if args.full:
+            out["budgets"][str(n)].update(full_same_move=float(np.mean(hit["full"])), full_by_rep=hit["full"])
     print(json.dumps(out))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
