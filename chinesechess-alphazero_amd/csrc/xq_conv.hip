@@ -31,6 +31,8 @@
 //     E = _Float16 ("f16x3"): (hi, lo) fp16 pairs, the same three MFMAs; a pair holds v to 2^-22 |v| + 2^-25 because the
 //     matrix unit honours fp16 subnormals (a filter tap's lo part usually is one).  Every kernel on these pairs is held to
 //     a float64 model of exactly this arithmetic, element by element: tests/test_gpu_f16x3.py, bounds in tests/f16_pairs.py.
+//     Plain operands and bf16 pairs are held to the same model (one term per K-step, the bf16 pair format) in
+//     tests/test_gpu_plain_bf16x3.py: cz_conv3x3 and cz_input_conv per element, their 2-byte stores bit for bit.
 //   * epilogue fused: + bias, + skip (read as hi + lo), ReLU, split / convert, store.  The last trunk layer can
 //     emit fp32 directly (y_f32) for the policy/value heads.
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 """Float64 model of the fp16-pair ("f16x3") tower arithmetic and the per-element bounds its kernels are held to
-(tests/test_gpu_f16x3.py; the bounds themselves are tested on faulty arithmetic in tests/test_f16x3_bounds_cpu.py), and,
-in the second part of this docstring, of the heads' dense tail on fp16 or bf16 pairs (tests/test_gpu_heads.py,
-tests/test_dense_bounds_cpu.py).
+(tests/test_gpu_f16x3.py; the bounds themselves are tested on faulty arithmetic in tests/test_f16x3_bounds_cpu.py), of the
+same convolutions on bf16 pairs ("bf16x3") and on plain fp16 / bf16 operands (the part BF16 PAIRS AND PLAIN OPERANDS below;
+tests/test_gpu_plain_bf16x3.py, tests/test_pair_bounds_cpu.py), and, in the last part of this docstring, of the heads' dense
+tail on fp16 or bf16 pairs (tests/test_gpu_heads.py, tests/test_dense_bounds_cpu.py).
 
 The arithmetic.  An fp32 operand v is stored as hi = fp16(v), lo = fp16(v - hi), both rounded to nearest even, and a
 product is formed as  w_hi x_hi + w_lo x_hi + w_hi x_lo  (w_lo x_lo is dropped), accumulated in fp32.
@@ -34,6 +35,32 @@ The bounds, per output element y of a convolution with bias b and optional (hi, 
 Everything here works on numpy float64 arrays and on torch float64 tensors alike (only slicing, matmul, abs and
 arithmetic), so the CPU test feeds the check the very function the GPU tests use.  Activations are channels-last
 [n, 90, C] (the kernels' layout), filters [C_out, C_in, K, K].
+
+BF16 PAIRS AND PLAIN OPERANDS (pair_conv / ConvCheck with fmt=BF16_PAIR, or plain=True).  The kernel is the same K loop
+(csrc/xq_conv.hip conv_kloop) for every operand type: tap-major, K-steps of 16 input channels, three matrix instructions per
+step for pairs (w_hi x_hi, w_lo x_hi, w_hi x_lo) and ONE for plain operands, fp32 accumulation.
+
+bf16 pairs ("bf16x3").  The arithmetic and both bounds are those above with the pair format e(v) = 2^-16 |v| + 2^-134 (BF16_PAIR;
+derived in the dense-layer part below) wherever e() enters: the output pair's e(y) in (a), and e(w), e(x), e(s) in (b).  An
+operand that is exactly 0 splits into (0, 0) and carries e = 0 (taken for bf16 pairs only, as DenseCheck does, so that the fp16
+bounds stay what they were).  Feature planes (0 / 1) are exact in either format: x_exact=True sets e(x) = 0.  A product of two
+bf16 values has at most 16 significant bits and an exponent inside fp32's range: exact in fp32, as a product of two fp16 values
+is (at most 22 bits, down to 2^-48).
+
+Plain operands (parts = 1, fp16 or bf16).  The kernel is handed the 2-byte values themselves, so only bound (a) applies:
+against float64 on the same operands, y_a = sum_k w_T x_T + b + s.
+    * accumulation: the model above with one term per step, N_s = min(16, C_in - 16 s) roundings, A_s = sum over the step of
+      |w_T x_T|:  ACC = LAMBDA U sqrt(sum_s N_s / 3 (|P_(s-1)| + A_s)^2).
+    * epilogue: the kernel adds the bias and then the one skip part in fp32 (k_conv3x3's epilogue: v = acc + b; v += s), one
+      rounding of at most U |result| <= U (|y_conv| + |b| + |s|) per addition: EPI = n_add U (|y_conv| + |b| + |s|), n_add = 2
+      with a skip and 1 without one (the input convolution: bias only).
+    * fp32 output: bound_a = ACC + EPI.  A 2-byte output is the nearest-even cast of that fp32 value v (the GPU tests compare it
+      bit for bit with the cast of the fp32 output of the same launch).  Where a kernel has no fp32 output (cz_input_conv) the
+      2-byte result g = cast(v) is held to the float64 value directly: |g - v| <= ulp(g) / 2, with ulp(g) = 2^(max(e, e_min) - p + 1),
+      2^e <= |g| < 2^(e + 1), p = 11 and e_min = -14 for fp16, p = 8 and e_min = -126 for bf16 (a result that rounds up to a power of
+      two is off by half the spacing BELOW it, which is smaller): bound_a = ACC + EPI + ulp(g) / 2 (half_ulp below).  A store that
+      truncated would be off by up to ulp(g), twice the dominant term.
+ReLU is 1-Lipschitz and maps the reference the same way, so it adds nothing to either bound.
 
 THE DENSE TAIL OF THE HEADS (csrc/xq_heads.hip: k_fc_tile, k_policy_normalize; pair_dense, DenseCheck, stat_rel,
 softmax_check, value_check below).
@@ -92,6 +119,8 @@ even grid): exp on [-87, 0] 1.411 U relative, exp2 on [-125, 0] 1.393 U, tanh on
 1.067 U on [2^-42, 0.25]).  Each constant is twice the measured maximum, rounded up.
 tests/test_gpu_heads.py::test_library_terms_through_the_kernels holds the kernels' own tanhf / expf / fexp calls to these
 constants on exact arguments (measured there: 0.42 and 0.47 of the constants)."""
+import itertools
+
 import numpy as np
 
 U = 2.0 ** -24                  # fp32 unit roundoff
@@ -146,18 +175,24 @@ def conv(x, w):
     return y.reshape(n, 90, w.shape[0])
 
 
-def pair_conv(x_hi, x_lo, w_hi, w_lo):
+def pair_conv(x_hi, x_lo, w_hi, w_lo, plain=False):
     """sum_k (w_hi x_hi + w_lo x_hi + w_hi x_lo) in float64 (products of fp16 values are exact, the sums good to 2^-50),
-    and the accumulation bound ACC of the module docstring for it, K-step by K-step (16 input channels of one tap)."""
+    and the accumulation bound ACC of the module docstring for it, K-step by K-step (16 input channels of one tap).
+    plain=True: one term per step, sum_k w_hi x_hi (x_lo, w_lo unused), and a third of the roundings."""
     n, c_in, c_out = x_hi.shape[0], x_hi.shape[-1], w_hi.shape[0]
     y = q = None
-    for (xh, wh), (xl, wl) in zip(taps(x_hi, w_hi), taps(x_lo, w_lo)):
+    lo_taps = itertools.repeat((None, None)) if plain else taps(x_lo, w_lo)
+    for (xh, wh), (xl, wl) in zip(taps(x_hi, w_hi), lo_taps):
         for c0 in range(0, c_in, 16):
             k = slice(c0, c0 + 16)
-            c = xh[:, k] @ wh[k] + xh[:, k] @ wl[k] + xl[:, k] @ wh[k]
-            a = abs(xh[:, k]) @ abs(wh[k]) + abs(xh[:, k]) @ abs(wl[k]) + abs(xl[:, k]) @ abs(wh[k])
+            if plain:
+                c = xh[:, k] @ wh[k]
+                a = abs(xh[:, k]) @ abs(wh[k])
+            else:
+                c = xh[:, k] @ wh[k] + xh[:, k] @ wl[k] + xl[:, k] @ wh[k]
+                a = abs(xh[:, k]) @ abs(wh[k]) + abs(xh[:, k]) @ abs(wl[k]) + abs(xl[:, k]) @ abs(wh[k])
             s = a if y is None else abs(y) + a              # bound on |partial sum| inside this K-step
-            m = 3 * min(16, c_in - c0)                      # roundings in it: one per product
+            m = (1 if plain else 3) * min(16, c_in - c0)    # roundings in it: one per product
             q = m / 3.0 * s * s if q is None else q + m / 3.0 * s * s
             y = c if y is None else y + c
     return y.reshape(n, 90, c_out), (LAMBDA * U * q ** 0.5).reshape(n, 90, c_out)
@@ -167,29 +202,67 @@ def _relu(t):
     return t * (t > 0)
 
 
-class ConvCheck:
-    """The per-element check of a convolution on fp16 pairs (module docstring), its float64 parts computed once for the
-    operands: x_pair = (x_hi, x_lo), w_pair = (w_hi, w_lo) the pairs' values, x / w the fp32 operands they split; all
-    float64, numpy arrays or torch tensors on one device.  Activations [n, 90, C_in], filters [C_out, C_in, K, K]."""
+F16_PLAIN = (11, -14)           # (significant bits p, smallest normal exponent e_min) of a plain 2-byte output: half_ulp
+BF16_PLAIN = (8, -126)
 
-    def __init__(self, x_pair, w_pair, x, w):
+
+def _err0(v, fmt):
+    """e(v) with e(0) = 0 for bf16 pairs (module docstring, BF16 PAIRS AND PLAIN OPERANDS); fp16 pairs keep e(0) = 2^-25."""
+    return pair_err(v, fmt) * (v != 0) if fmt is BF16_PAIR else pair_err(v, fmt)
+
+
+def half_ulp(g, out_fmt):
+    """ulp(g) / 2 of the 2-byte format out_fmt (F16_PLAIN, BF16_PLAIN) at its values g (float64): the most a nearest-even cast
+    to g can have moved the value it rounded."""
+    p, e_min = out_fmt
+    e = (np.frexp(abs(g))[1] if isinstance(g, np.ndarray) else abs(g).frexp()[1].double()) - 1.0     # 2^e <= |g| < 2^(e + 1)
+    sub = (e <= e_min) | (g == 0)                                # subnormal or zero: the spacing of the smallest binade
+    return 2.0 ** (e * ~sub + e_min * sub - p)
+
+
+class ConvCheck:
+    """The per-element check of a convolution on (hi, lo) pairs of format `fmt` (module docstring), its float64 parts computed
+    once for the operands: x_pair = (x_hi, x_lo), w_pair = (w_hi, w_lo) the pairs' values, x / w the fp32 operands they split;
+    all float64, numpy arrays or torch tensors on one device.  Activations [n, 90, C_in], filters [C_out, C_in, K, K].
+    x_exact: the activations are exact in the format (feature planes), e(x) = 0.
+    plain=True: plain 2-byte operands, x_pair = (x_T,), w_pair = (w_T,) and x = w = None: bound (a) only."""
+
+    def __init__(self, x_pair, w_pair, x=None, w=None, fmt=F16_PAIR, plain=False, x_exact=False):
+        self.fmt, self.plain = fmt, plain
+        if plain:
+            self.y3, self.acc = pair_conv(x_pair[0], None, w_pair[0], None, plain=True)
+            return
         (xh, xl), (wh, wl) = x_pair, w_pair
         self.y3, self.acc = pair_conv(xh, xl, wh, wl)
         self.exact = conv(x, w)
-        self.rep = conv(abs(xl), abs(wl)) + conv(abs(x), pair_err(w)) + conv(pair_err(x), abs(wh + wl))
+        self.rep = conv(abs(xl), abs(wl)) + conv(abs(x), _err0(w, fmt))
+        if not x_exact:
+            self.rep = self.rep + conv(_err0(x, fmt), abs(wh + wl))
 
-    def ratios(self, got, bias, skip=None, relu=False, pair_out=False):
-        """Worst |error| / bound over the output elements against (a) the same operands and (b) the exact fp32 operands.
-        got: the kernel's result as float64 (hi + lo of a pair output); bias [C_out]; skip = (s_hi, s_lo, s) or None."""
-        ya, yb, mag, rep = self.y3 + bias, self.exact + bias, abs(self.y3) + abs(bias), self.rep
+    def ratios(self, got, bias, skip=None, relu=False, pair_out=False, out_fmt=None):
+        """Worst |error| / bound over the output elements against (a) the same operands and (b) the exact fp32 operands
+        (None for plain operands).  got: the kernel's result as float64 (hi + lo of a pair output); bias [C_out];
+        skip = (s_hi, s_lo, s), or (s_T,) for plain operands, or None; out_fmt: F16_PLAIN / BF16_PLAIN when got is a plain
+        2-byte output (adds half_ulp(got))."""
+        ya, mag = self.y3 + bias, abs(self.y3) + abs(bias)
+        if self.plain:
+            if skip is not None:
+                ya, mag = ya + skip[0], mag + abs(skip[0])
+            if relu:
+                ya = _relu(ya)
+            bound_a = self.acc + (1 if skip is None else 2) * U * mag
+            if out_fmt is not None:
+                bound_a = bound_a + half_ulp(got, out_fmt)
+            return float((abs(got - ya) / bound_a).max()), None
+        yb, rep = self.exact + bias, self.rep
         if skip is not None:
             sh, sl, s = skip
-            ya, yb, mag, rep = ya + sh + sl, yb + s, mag + abs(sh) + abs(sl), rep + pair_err(s)
+            ya, yb, mag, rep = ya + sh + sl, yb + s, mag + abs(sh) + abs(sl), rep + _err0(s, self.fmt)
         if relu:
             ya, yb = _relu(ya), _relu(yb)
         bound_a = self.acc + EPI_REL * mag
         if pair_out:
-            bound_a = bound_a + pair_err(ya)
+            bound_a = bound_a + pair_err(ya, self.fmt)
         return float((abs(got - ya) / bound_a).max()), float((abs(got - yb) / (bound_a + rep)).max())
 
     def error(self, got, bias):
@@ -223,6 +296,14 @@ TANH_REL = 5.0 * U
 P_FLOOR = 2.0 ** -126
 
 
+def bf16_round(a, nearest=True):
+    """The bf16 value of fp32 numbers as a float32 array: rounded to nearest even, or (nearest=False) truncated."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    if nearest:
+        u = u + 0x7FFF + ((u >> 16) & 1)
+    return (u & 0xFFFF0000).astype(np.uint32).view(np.float32)
+
+
 def split_pair(v, fmt=F16_PAIR):
     """(hi, lo) of an fp32 numpy array in pair format `fmt`, as float32 arrays, both parts rounded to nearest even."""
     v = np.ascontiguousarray(v, dtype=np.float32)
@@ -230,12 +311,8 @@ def split_pair(v, fmt=F16_PAIR):
         hi, lo = split16(v)
         return hi.astype(np.float32), lo.astype(np.float32)
 
-    def bf16(a):
-        u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
-        u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-        return u.astype(np.uint32).view(np.float32)
-    hi = bf16(v)
-    return hi, bf16(v - hi)
+    hi = bf16_round(v)
+    return hi, bf16_round(v - hi)
 
 
 def _fn(t, name):

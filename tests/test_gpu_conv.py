@@ -83,7 +83,7 @@ def test_conv3x3_identity_filter_is_a_shift():
 @pytest.mark.parametrize("c,dt,parts", [(128, "bfloat16", 2), (128, "bfloat16", 1), (128, "float16", 1),
                                         (256, "float16", 1), (256, "bfloat16", 1), (192, "float16", 1),
                                         (192, "bfloat16", 2), (192, "float16", 2),       # (192 split: k_resblock_ip)
-                                        (128, "float16", 2)])
+                                        (128, "float16", 2), (192, "bfloat16", 1)])      # = all that cz_resblock accepts
 @pytest.mark.parametrize("n", [1, 3, 257, 700])
 def test_resblock_equals_two_convolutions(c, dt, parts, n):
     """cz_resblock (one launch, intermediate in LDS) must be BIT-identical to two cz_conv3x3 launches: same
@@ -382,6 +382,27 @@ def test_resblock_rejects_unsupported_shapes():
     x32 = tuple(torch.zeros((1, 90, 32), device="cuda", dtype=torch.bfloat16) for _ in range(2))
     with pytest.raises(_native.NativeError):
         _native.resblock(x32, w, b, w, b, out=x32)
+    # cz_resblock's table (csrc/xq_conv.hip dispatch_resblock): 128 / 192 filters split or plain, 256 plain, nothing else
+    for c, dt, parts in ((32, torch.float16, 1), (32, torch.bfloat16, 1), (256, torch.bfloat16, 2), (256, torch.float16, 2),
+                         (64, torch.float16, 1)):
+        x = tuple(torch.zeros((1, 90, c), device="cuda", dtype=dt) for _ in range(parts))
+        with pytest.raises(_native.NativeError):
+            _native.resblock(x, w, b, w, b, out=x)
+    # fp32 output needs split operands
+    x1 = (torch.zeros((1, 90, 128), device="cuda", dtype=torch.float16),)
+    with pytest.raises(_native.NativeError):
+        _native.resblock(x1, w, b, w, b, out_f32=torch.zeros((1, 90, 128), device="cuda"))
+    # cz_resblock_heads: 128 filters only;  cz_tower_plain: 256 filters, fp16 / bf16 only
+    hw, hb = torch.zeros((6, 192), device="cuda"), torch.zeros(6, device="cuda")
+    pf, vf = torch.zeros((1, 360), device="cuda"), torch.zeros((1, 180), device="cuda")
+    for c in (192, 256, 32):
+        x = tuple(torch.zeros((1, 90, c), device="cuda", dtype=torch.bfloat16) for _ in range(2))
+        with pytest.raises(_native.NativeError):
+            _native.resblock_heads(x, w, b, w, b, hw, hb, 4, pf, vf)
+    for c, dt in ((128, torch.float16), (192, torch.bfloat16), (256, torch.float32)):
+        x = torch.zeros((1, 90, c), device="cuda", dtype=dt)
+        with pytest.raises(_native.NativeError):
+            _native.tower_plain(x, [(w, b, w, b)], torch.zeros_like(x))
 
 
 @pytest.mark.parametrize("c,in_planes,dt,parts", [(128, 14, "bfloat16", 2), (128, 28, "bfloat16", 2),
