@@ -24,6 +24,16 @@ VISIT_FAST = 2           # visit entry flag: the ply was a fast search
 VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (cz_search_set_forced_playouts)
 VISIT_GUMBEL = 8         # visit entry flag: n holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
 GUMBEL_MAX_M = 128       # include/czero.h CZ_GUMBEL_MAX_M
+EVAL_CACHE_STRIDE = 576  # include/czero.h CZ_EVAL_CACHE_STRIDE: bytes per entry of the evaluation cache
+EVAL_CACHE_LOG2 = (10, 24)   # CZ_EVAL_CACHE_MIN_LOG2 / CZ_EVAL_CACHE_MAX_LOG2: the sizes set_eval_cache takes, besides 0 = off
+
+
+def check_eval_cache_log2(log2_entries, what="eval_cache"):
+    """The argument check of every layer that takes the evaluation cache's size: 0 (off) or 10 .. 24."""
+    v = int(log2_entries)
+    if v != 0 and not EVAL_CACHE_LOG2[0] <= v <= EVAL_CACHE_LOG2[1]:
+        raise ValueError(f"{what} {log2_entries}: expected 0 (off) or {EVAL_CACHE_LOG2[0]} <= LOG2 <= {EVAL_CACHE_LOG2[1]}")
+    return v
 
 # One searched ply's root, as the move was chosen: every edge in edge order (labels, mover frame), its visit count, whether it
 # was banned at that ply; the root's own count; the ply; whether the player resigned there; whether the ply was a fast
@@ -106,6 +116,9 @@ def declare(L):
         "cz_search_node_net_value": [vp, vp, i32, vp, vp],
         "cz_gumbel_policy_target_v": [vp, vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
         "cz_gumbel_interior_pick": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
+        "cz_search_set_eval_cache": [vp, i32, vp],
+        "cz_search_eval_cache_clear": [vp, vp],
+        "cz_search_eval_cache_info": [vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -211,6 +224,7 @@ class Search:
         self.mirrored = None                   # set_leaf_mirror(flags=True): [slots] uint8, 1 = the slot's leaf is mirrored
         self.gumbel_m = 0                      # set_gumbel(): candidates of the Gumbel root search, 0 = off
         self.gumbel_full = False               # set_gumbel_full(): the Gumbel rule below the root and v_mix in the target
+        self.eval_cache = 0                    # set_eval_cache(): log2 of the evaluation cache's entries, 0 = off
 
     # -- lifetime --
     def close(self):
@@ -233,7 +247,10 @@ class Search:
         _native.check(self.L.cz_search_memory_info(self.h, out, self._stream()), "cz_search_memory_info")
         keys = ("pool_chunks", "free_chunks", "held_chunks", "held_chunks_max_game", "tree_bytes", "tree_bytes_max_game",
                 "nodes", "nodes_max_game")
-        return {k: int(out[i]) for i, k in enumerate(keys)}
+        d = {k: int(out[i]) for i, k in enumerate(keys)}
+        # (the library's out[8] stays as it is; the evaluation cache's table is a device allocation beside the pool)
+        d["eval_cache_bytes"] = (EVAL_CACHE_STRIDE << self.eval_cache) if self.eval_cache else 0
+        return d
 
     def _stream(self):
         import torch
@@ -359,6 +376,37 @@ class Search:
         and before a graph capture."""
         _native.check(self.L.cz_search_set_gumbel_full(self.h, 1 if on else 0, self._stream()), "cz_search_set_gumbel_full")
         self.gumbel_full = bool(on)
+
+    def set_eval_cache(self, log2_entries=0):
+        """Cross-game evaluation cache (cz_search_set_eval_cache; include/czero.h has the table and who touches it when): a
+        direct-mapped table of 2**log2_entries network results keyed by position and leaf-mirror bit, shared by all games
+        and kept across games, reset_trees() and set_roots().  A new leaf the table holds takes no queue row -- leaf_rows()
+        and the compact queue do not list it -- and is attached in the next round like an evaluated one: the search
+        produces the bits it produces with the cache off.  log2_entries 0 switches it off and frees the table, otherwise
+        10 .. 24 (576 bytes per entry, an allocation of its own: device_bytes() includes it).  Refused with use_history.
+        The caller empties it (clear_eval_cache) when the network behind the queue changes.  Call it before the rounds
+        and before a graph capture."""
+        if not hasattr(self.L, "cz_search_set_eval_cache"):
+            raise _native.NativeError("this libczero.so has no evaluation cache (cz_search_set_eval_cache)")
+        v = check_eval_cache_log2(log2_entries, "set_eval_cache: log2_entries")
+        _native.check(self.L.cz_search_set_eval_cache(self.h, v, self._stream()), "cz_search_set_eval_cache")
+        self.eval_cache = v
+
+    def clear_eval_cache(self):
+        """Empty the evaluation cache and zero its numbers (cz_search_eval_cache_clear); nothing to do while it is off."""
+        if self.eval_cache:
+            _native.check(self.L.cz_search_eval_cache_clear(self.h, self._stream()), "cz_search_eval_cache_clear")
+
+    def eval_cache_info(self):
+        """dict(entries, probes, hits, stores) of the evaluation cache since it was made or last emptied
+        (cz_search_eval_cache_info): entries 0 = off; probes = new leaves that asked the table, hits = those it answered
+        (no queue row), stores = entries written.  Synchronises the stream."""
+        keys = ("entries", "probes", "hits", "stores")
+        if not hasattr(self.L, "cz_search_eval_cache_info"):
+            return dict.fromkeys(keys, 0)
+        out = (C.c_uint64 * 4)()
+        _native.check(self.L.cz_search_eval_cache_info(self.h, out, self._stream()), "cz_search_eval_cache_info")
+        return {k: int(out[i]) for i, k in enumerate(keys)}
 
     def node_net_value(self, path=None):
         """v [G] float32: the network value kept in the node node_stats(path) reports (cz_search_node_net_value; kept

@@ -18,7 +18,7 @@ from logging import getLogger
 import torch
 
 from cchess_alphazero import _native
-from cchess_alphazero._native_search import Search
+from cchess_alphazero._native_search import Search, check_eval_cache_log2
 from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE
@@ -43,7 +43,7 @@ class SelfPlayEngine:
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
-                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None):
+                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -73,7 +73,16 @@ class SelfPlayEngine:
         65536 (include/czero.h, cz_search_set_gumbel).
         gumbel_full: the full Gumbel search (None = config.engine.gumbel_full; needs gumbel): below the root the selection
         is argmax pi'(a) - N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes the unvisited edges with v_mix,
-        the root's network value mixed with the visited edges' mean (cz_search_set_gumbel_full)."""
+        the root's network value mixed with the visited edges' mean (cz_search_set_gumbel_full).
+        eval_cache: log2 of the entries of the cross-game evaluation cache (None = config.engine.eval_cache; 0 = off, else
+        10 .. 24): network results keyed by position, shared by all games and kept across games; a new leaf the table
+        holds takes no queue row, and the games, records and counters are the ones played without it
+        (cz_search_set_eval_cache).  Every network change empties it (_install).  Excludes use_history."""
+        self.eval_cache = check_eval_cache_log2(getattr(getattr(config, "engine", None), "eval_cache", 0)
+                                                if eval_cache is None else eval_cache)
+        if self.eval_cache and use_history:
+            raise ValueError("eval_cache excludes use_history: the second block of the 28-plane input depends on the "
+                             "simulation's path and the game history, so the network input is not a function of the position")
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -101,6 +110,8 @@ class SelfPlayEngine:
                              max_nodes_per_game=max_nodes_per_game, pool_chunks=pool_chunks, max_depth=max_depth,
                              sims_per_round=sims_per_round, device=self.device, use_history=use_history,
                              pool_fraction=getattr(getattr(config, "engine", None), "pool_fraction", None))
+        if self.eval_cache:                    # the table: before the network's buffers, before start() and a graph capture
+            self.search.set_eval_cache(self.eval_cache)
         self.policy_logits = False             # (an evaluator callable hands over probabilities, like the reference's pipe)
         self._ref_net = net if evaluator is None else None     # (CPU copy of the weights: audit_network's float64 reference)
         if evaluator is None:
@@ -181,6 +192,9 @@ class SelfPlayEngine:
         self.net = built if built is not None else self._build_net(net)
         self.net_arith_effective = self.net.arith_effective
         self.net_calibration = self.net.calibration
+        # the one place every network change passes through (construction, set_network, the rebuild after demote_arith):
+        # what the evaluation cache holds was the old network's
+        self.search.clear_eval_cache()
         # the engine's own queue: raw logits instead of a softmax over all 2086 columns (the search spreads the priors over
         # the legal moves anyway, reference player.py:272-283: the denominator cancels) -- engine.policy_logits = False opts out
         want = getattr(getattr(self.config, "engine", None), "policy_logits", True)

@@ -80,6 +80,11 @@ _FLAGS = [
                            help="(self, with --gumbel) full Gumbel search: below the root the selection is argmax pi'(a) - "
                                 "N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes unvisited moves with v_mix, "
                                 "the root's network value mixed with the visited moves' mean")),
+    ("--eval-cache", dict(type=int, default=0, metavar="LOG2",
+                          help="(self) cross-game evaluation cache: a table of 2**LOG2 network results keyed by position "
+                               "(576 bytes each), shared by all games and kept across games; a new leaf whose position it "
+                               "holds is not evaluated again.  The search stays the same bit for bit (0 = off; 10 <= LOG2 "
+                               "<= 24)")),
     ("--sims", dict(type=int, default=None, metavar="N",
                     help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
@@ -172,6 +177,16 @@ def build_config(args):
         raise SystemExit("--gumbel-full needs --gumbel M: it completes the Gumbel root search below the root")
     engine.gumbel, engine.gumbel_visit, engine.gumbel_scale = args.gumbel, args.gumbel_visit, args.gumbel_scale
     engine.gumbel_full = bool(args.gumbel_full)
+    if args.eval_cache:
+        if args.cmd != "self":
+            raise SystemExit("--eval-cache is an option of `run.py self`: the arena feeds two networks through one search, "
+                             "and a single game's tree is already its own cache")
+        if not 10 <= args.eval_cache <= 24:
+            raise SystemExit(f"--eval-cache {args.eval_cache}: expected 0 (off) or 10 <= LOG2 <= 24")
+        if getattr(config.model, "input_depth", 14) == 28:
+            raise SystemExit("--eval-cache needs the 14-plane input: with 28 planes the second block depends on the "
+                             "simulation's path and the game history, so the network input is not a function of the position")
+    engine.eval_cache = args.eval_cache
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -113,6 +113,9 @@ class SelfPlayWorker:
         if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
             logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
                         f"mirror image with probability {self.engine.leaf_mirror}")
+        if getattr(self.engine, "eval_cache", 0):              # (config.engine.eval_cache, likewise)
+            logger.info(f"Process {self.pid}-{self.rank}: evaluation cache: 2^{self.engine.eval_cache} entries, "
+                        f"{self.engine.search.memory_info()['eval_cache_bytes'] >> 20} MiB, kept across games")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:
@@ -152,6 +155,14 @@ class SelfPlayWorker:
         if self.engine.forced_playouts and raw:
             logger.info(f"Process {self.pid}-{self.rank}: policy target pruning removed {pruned} of {raw} root visits "
                         f"({100.0 * pruned / raw:.1f} %)")
+
+    def _eval_cache_report(self):
+        """The evaluation cache's numbers for the counter line (since the table was last emptied: a reload empties it)."""
+        if not getattr(self.engine, "eval_cache", 0):
+            return ""
+        ci = self.engine.search.eval_cache_info()
+        return (f" eval_cache: probes={ci['probes']} hits={ci['hits']} "
+                f"({100.0 * ci['hits'] / max(ci['probes'], 1):.2f} %) stores={ci['stores']}")
 
     def reload_best_model(self):
         """The reference's self-play picks up a new best model while it runs: its prediction thread re-checks the
@@ -214,7 +225,8 @@ class SelfPlayWorker:
                                 f"expansions/s={c['expansions'] / dt:.0f} games/h={c['games'] / dt * 3600:.0f} "
                                 f"tree_resets={lc['tree_resets']} overflow_sims={lc['overflow_sims']} "
                                 f"no_act_truncated={lc.get('no_act_truncated', 0)}"
-                                + (f" visits_dropped={lc['visits_dropped']}" if "visits_dropped" in lc else ""))
+                                + (f" visits_dropped={lc['visits_dropped']}" if "visits_dropped" in lc else "")
+                                + self._eval_cache_report())
                 if max_games is not None and c["games"] >= max_games:
                     break
             if max_rounds is not None and r >= max_rounds:

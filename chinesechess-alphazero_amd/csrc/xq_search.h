@@ -36,7 +36,9 @@ constexpr int CHILD_TERM_WIN = -2;     // done() == (True, +1): value for the ch
 constexpr int CHILD_TERM_LOSS = -3;    // done() == (True, -1)
 
 enum SimState : uint8_t { SIM_IDLE = 0, SIM_LEAF = 1, SIM_PARKED = 2,
-                          SIM_DEFERRED = 3 };   // ended on a terminal / repeated position; backed up when the phase's descents are over (never outlives a launch)
+                          SIM_DEFERRED = 3,     // ended on a terminal / repeated position; backed up when the phase's descents are over (never outlives a launch)
+                          SIM_CACHED = 4 };     // a new leaf whose evaluation the cache held (cz_search_set_eval_cache): priors in the node, value in
+                                                // s_cval; no queue row, attached with the SIM_LEAF slots of the next round
 
 enum NodeFlag : uint32_t { NODE_WAITING = 1u << 8,      // low 8 bits of node_meta = move count
                            NODE_MIRRORED = 1u << 9 };   // set beside NODE_WAITING: the leaf is evaluated in its mirror image

@@ -12,6 +12,8 @@
 //                     search / the next game (self-play) or mark the game READY (external mode);
 //   k_sim(SELECT)  4. where a batch of K simulations is complete start the next one; every new leaf writes
 //                     its input planes into its fixed slot (game * K + sim) of the evaluation queue.
+// With the evaluation cache on (cz_search_set_eval_cache) a fourth launch comes first: k_cache_fill stores the rows step 1
+// is about to attach, and the k_sim launches are the k_sim_cached instantiations, whose new leaves ask the table in step 4.
 // The host then runs ONE network forward over the whole queue.
 // There is no host decision inside a round and no device->host copy, so a round (kernel + network
 // forward) can be replayed from a HIP graph.
@@ -29,6 +31,7 @@
 #include "xq_search.h"
 #include "xq_noise.h"
 #include "xq_mirror.h"
+#include "xq_evalcache.h"
 #include "../../include/czero.h"
 
 using namespace xq;
@@ -323,6 +326,26 @@ XQ_D void logits_to_weights(float& q0, float& q1, int nm)
     q1 = h1 ? __expf(q1 - m) : 0.0f;
 }
 
+// The priors of a node from its row's entries, lane j holding move j in p0 and move j + 64 in p1 (0 past the node's nm
+// moves): prior j = (p0 or p1 after the call) / the returned sum.  Raw logits first become weights relative to the largest
+// legal one; the sum is the float32 accumulation in move order (select_action_q_and_u, player.py:272-284), the terms read
+// straight from the lanes' registers (a loop over an LDS copy paid an LDS round trip per term).  The one place the priors
+// are formed: the attach of an evaluated leaf and the evaluation cache's fill (k_cache_fill) both call it, so a cached
+// entry holds the attach's bits by construction.
+XQ_D float prior_norm(float& p0, float& p1, int nm, bool logits)
+{
+    if (logits) logits_to_weights(p0, p1, nm);             // (raw logits: weights relative to the largest legal one)
+    float all_p = 0.0f;
+    if (nm > 0) {
+        all_p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), 0));          // int 0 + float32
+        const int n0 = nm < 64 ? nm : 64;
+        for (int j = 1; j < n0; ++j) all_p = all_p + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), j));
+        for (int j = 64; j < nm; ++j) all_p = all_p + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p1), j - 64));
+    }
+    if (all_p == 0.0f) all_p = 1.0f;
+    return all_p;
+}
+
 // keep_v: the leaf's network value v goes into the node header as well (k_sim's keep_v: constant false outside the GUM
 // instantiations, so their text does not hold the store)
 XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float* __restrict__ prow, bool logits,
@@ -340,18 +363,9 @@ XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float*
     float q0 = 0.0f, q1 = 0.0f;
     if (lane < nm) q0 = prow[row_col(pm[lane], mir)];
     if (lane + 64 < nm) q1 = prow[row_col(pm[lane + 64], mir)];
-    if (logits) logits_to_weights(q0, q1, nm);
-    if (lane < nm) L.pr[lane] = q0;
-    if (lane + 64 < nm) L.pr[lane + 64] = q1;
-    wave_sync();
-    float all_p = 0.0f;
-    if (nm > 0) {
-        all_p = L.pr[0];                                   // int 0 + float32
-        for (int j = 1; j < nm; ++j) all_p = all_p + L.pr[j];   // float32 accumulation in move order
-    }
-    if (all_p == 0.0f) all_p = 1.0f;
-    if (lane < nm) pp[lane] = L.pr[lane] / all_p;
-    if (lane + 64 < nm) pp[lane + 64] = L.pr[lane + 64] / all_p;
+    const float all_p = prior_norm(q0, q1, nm, logits);
+    if (lane < nm) pp[lane] = q0 / all_p;
+    if (lane + 64 < nm) pp[lane + 64] = q1 / all_p;
     // p[j] is written and later read (select_edge) by the same lane, the header by lane 0: no global fence
     if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
     if (keep_v && lane == 0) store_net_value(base, v);
@@ -408,17 +422,7 @@ XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS
     EdgeStat* ep = nullptr;
     if (lane < depth) { ep = edge_ptr(gv, (uint32_t)lp.e); cur = *ep; }
     next();
-    if (logits) logits_to_weights(p0, p1, nm);             // (raw logits: weights relative to the largest legal one)
-    // prior spreading (select_action_q_and_u, player.py:272-284): float32 accumulation in move order, the terms read
-    // straight from the lanes' registers (a loop over an LDS copy paid an LDS round trip per term)
-    float all_p = 0.0f;
-    if (nm > 0) {
-        all_p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), 0));          // int 0 + float32
-        const int n0 = nm < 64 ? nm : 64;
-        for (int j = 1; j < n0; ++j) all_p = all_p + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), j));
-        for (int j = 64; j < nm; ++j) all_p = all_p + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p1), j - 64));
-    }
-    if (all_p == 0.0f) all_p = 1.0f;
+    const float all_p = prior_norm(p0, p1, nm, logits);    // prior spreading (select_action_q_and_u, player.py:272-284)
     if (lane < nm) pp[lane] = p0 / all_p;
     if (lane + 64 < nm) pp[lane + 64] = p1 / all_p;
     if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
@@ -938,6 +942,47 @@ XQ_D int expand_node(const SearchParams& P, const SearchBuffers& B, const GameVi
     return (int)id;
 }
 
+// ---- evaluation cache (cz_search_set_eval_cache): the probe of a new leaf -------------------------------------------
+// Called right after expand_node made `node` for the position whose key is in L.key (hash h, coin `mirrored`), in the
+// k_sim(SELECT) launch only; the table is read, never written (k_cache_fill, an earlier launch, is the only writer).  A hit
+// is the full key plus the mirror bit and the move count: the lanes that own p[j] in select_edge (j & 63) copy the entry's
+// priors into the node record, lane 0 leaves the value in the slot's s_cval.  The node stays NODE_WAITING: the caller
+// marks the slot SIM_CACHED and the next round's attach takes it in simulation order with the evaluated leaves.
+XQ_D bool cache_probe(const EvalCache& C, const GameView& gv, const uint32_t* key, uint64_t h, bool mirrored, int nm,
+                      int node, size_t slot)
+{
+    const int lane = lane_id();
+    nm = nm < MAXMOVES ? nm : MAXMOVES;
+    const EvalCacheEntry* e = C.tab + ec_slot(h, mirrored, C.log2);
+    bool ne = false;
+    if (lane < KEY_WORDS) ne = e->key[lane] != key[lane];
+    else if (lane == KEY_WORDS) ne = e->meta != ec_meta(nm, mirrored);
+    const bool hit = __ballot(ne) == 0ull;
+    if (lane == 0) {                                        // (this game's wave is the words' only writer)
+        C.g_probes[gv.g] += 1ull;
+        if (hit) C.g_hits[gv.g] += 1ull;
+    }
+    if (!hit) return false;
+    float* pp = node_p(rec_ptr(gv, (uint32_t)node));
+    if (lane < nm) pp[lane] = e->p[lane];
+    if (lane + 64 < nm) pp[lane + 64] = e->p[lane + 64];
+    if (lane == 0) C.s_cval[slot] = e->value;
+    return true;
+}
+
+// the attach of a SIM_CACHED slot: the priors are in the node already (cache_probe), what is left of attach_policy is the
+// header -- the flags go, the value stays with keep_v
+XQ_D void cached_attach(const GameView& gv, int node, bool keep_v, float v)
+{
+    char* base = rec_ptr(gv, (uint32_t)node);
+    if (lane_id() == 0) {
+        const uint32_t meta = *reinterpret_cast<const uint32_t*>(base + NODE_OFF_HDR + 4);
+        store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));
+        if (keep_v) store_net_value(base, v);
+    }
+    wave_sync();
+}
+
 // move label of path entry (node, edge): edge - stat block = index into the node's move list (rare: repetitions)
 XQ_D int edge_move(const GameView& gv, int node, int edge)
 {
@@ -949,10 +994,12 @@ XQ_D int edge_move(const GameView& gv, int node, int edge)
 
 // One descent of simulation `sim` starting at `node` with `depth` path entries already in L.path_*
 // (MCTS_search, player.py:198-260).  `node` < 0 means the root position is not in the tree yet.
-template <bool HIST, bool GUM>
+// CACHE: the evaluation cache is on (cz_search_set_eval_cache); `probe` (the SELECT launch): a new leaf asks the table C
+// before it takes a queue row.
+template <bool HIST, bool GUM, bool CACHE>
 XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                   const RoundIO& io, const RootCtx& rc0, int root, int sim, int node, int depth, int* active,
-                  Arena& ar, bool fresh, Deferred& df)
+                  Arena& ar, bool fresh, Deferred& df, const EvalCache& C, bool probe)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -969,14 +1016,19 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         int slot;
         int idx = hash_lookup(gv, P, L.key, h, &slot);
         bool mir = false;
+        const bool made = idx < 0;
         if (idx < 0) idx = expand_node(P, B, gv, L, L.r.ml[0], nm, slot, h, ar, mir);
         else mir = (load_hdr(rec_ptr(gv, (uint32_t)idx)).meta & NODE_MIRRORED) != 0u;   // (the frame its attach will read)
         if (idx < 0) { count(gv, CT_OVERFLOW_SIMS); backup(P, gv, L, 0, 0.0); sim_finish(gv, sim, active); return; }
+        bool hit = false;
+        if constexpr (CACHE) {
+            if (probe && made) hit = cache_probe(C, gv, L.key, h, mir, nm, idx, (size_t)g * P.K + sim);
+        }
         if (lane == 0) {
             B.g_root[g] = idx;
-            gv.s_state[sim] = SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = 0;
+            gv.s_state[sim] = hit ? SIM_CACHED : SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = 0;
         }
-        write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, 0) : nullptr, mir);
+        if (!hit) write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, 0) : nullptr, mir);
         wave_sync();
         return;
     }
@@ -1091,8 +1143,12 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
                         return;
                     }
                     if (lane == owner) ep->child = idx;
-                    if (lane == 0) { gv.s_state[sim] = SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = depth; }
-                    write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, depth) : nullptr, mir);
+                    bool hit = false;
+                    if constexpr (CACHE) {
+                        if (probe) hit = cache_probe(C, gv, L.key, h, mir, d.nmoves, idx, (size_t)g * P.K + sim);
+                    }
+                    if (lane == 0) { gv.s_state[sim] = hit ? SIM_CACHED : SIM_LEAF; gv.s_node[sim] = idx; gv.s_depth[sim] = depth; }
+                    if (!hit) write_planes<HIST>(io, L.r.bd[1], L.codes, (size_t)g * P.K + sim, HIST ? history_board(P, B, gv, L, fresh, depth) : nullptr, mir);
                     wave_sync();
                     PROF(CT_CYC_EXPAND);
                     return;
@@ -1977,17 +2033,20 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 
 // HIST: 28 input planes (use_history); kept out of the common 14-plane instantiation.  GUM: the Gumbel root search
 // (cz_search_set_gumbel) is on; likewise.
-template <bool HIST, bool GUM>
-__global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
-                                           const float* __restrict__ value, void* planes, int mask, int compact,
-                                           int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
+// CACHE: the evaluation cache (cz_search_set_eval_cache) is on; likewise, so that the kernels launched while it is off
+// are the text they were.  The body of both kernels: k_sim below (CACHE false, C never read) and k_sim_cached.
+template <bool HIST, bool GUM, bool CACHE>
+XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
+                   const float* __restrict__ value, void* planes, int mask, int compact,
+                   int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C)
 {
-    __shared__ SearchLDS L;
     const int g = blockIdx.x;
     // first kernel of a round: chunks returned during the previous round become takeable (see pool_commit)
     if (g == 0 && (mask & SIM_BACKUP) && lane_id() == 0) {
         pool_commit(B);
         if (q_count) *q_count = 0;          // compact queue of this round: filled by the k_sim(SELECT) launch below
+        // the round's fill (k_cache_fill, the launch before this one) is over: the next round claims with the next stamp
+        if constexpr (CACHE) *C.stamp = *C.stamp + 1u;
     }
     if (g >= P.G) return;
     if (uni((int)B.g_phase[g]) != PH_SEARCH) return;
@@ -2032,17 +2091,24 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
             my_meta = *reinterpret_cast<const uint32_t*>(rec_ptr(gv, (uint32_t)sn_node) + NODE_OFF_HDR + 4);
             my_v = value[my_row];
         }
+        // the leaves the cache answered (SIM_CACHED) join the walk below at their place in simulation order: their value
+        // waits in s_cval, no policy row is read and nothing is prefetched for them
+        uint64_t cached = 0ull;
+        if constexpr (CACHE) {
+            if (sn_state == SIM_CACHED) my_v = C.s_cval[(size_t)g * P.K + lane];
+            cached = __ballot(sn_state == SIM_CACHED);
+        }
         PROF_BEGIN();
         // the evaluated leaves of this game, in simulation order, as a bit set; leaf_at(i) = its wave-uniform fields
-        const uint64_t leaves = __ballot(sn_state == SIM_LEAF) & (P.K < 64 ? (1ull << P.K) - 1ull : ~0ull);
+        const uint64_t leaves = (__ballot(sn_state == SIM_LEAF) | cached) & (P.K < 64 ? (1ull << P.K) - 1ull : ~0ull);
         auto pre_a = [&](LeafPre& lp, int i) {
             const int depth = __builtin_amdgcn_readlane(sn_depth, i);
-            if (depth <= 64)
+            if (depth <= 64 && !((cached >> i) & 1ull))
                 leaf_pre_a(gv, lp, __builtin_amdgcn_readlane(sn_node, i), (uint32_t)__builtin_amdgcn_readlane((int)my_meta, i),
                            depth, gv.path_edge + (size_t)i * P.max_depth);
         };
         auto pre_b = [&](LeafPre& lp, int i) {
-            if (__builtin_amdgcn_readlane(sn_depth, i) <= 64)
+            if (__builtin_amdgcn_readlane(sn_depth, i) <= 64 && !((cached >> i) & 1ull))
                 leaf_pre_b(lp, (uint32_t)__builtin_amdgcn_readlane((int)my_meta, i),
                            policy + (size_t)__builtin_amdgcn_readlane(my_row, i) * NLABELS);
         };
@@ -2062,7 +2128,12 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
             const size_t slot = (size_t)__builtin_amdgcn_readlane(my_row, i);
             const double v = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_v), i));   // float(v) of a float32
             LeafPre nx{0, 0, 0, 0.0f, 0.0f};
-            if (depth <= 64) {
+            if (CACHE && ((cached >> i) & 1ull)) {
+                cached_attach(gv, node, keep_v, (float)v);
+                load_path(P, gv, L, i, depth);
+                backup(P, gv, L, depth, v);
+                if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
+            } else if (depth <= 64) {
                 attach_and_backup(P, gv, L, node, (uint32_t)__builtin_amdgcn_readlane((int)my_meta, i), depth, lp, v,
                                   P.policy_logits != 0, keep_v, [&]() {
                                       if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
@@ -2080,10 +2151,21 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
         resume_i = 0;                                                 // 2. then resume the parked simulations
     } else if ((mask & SIM_BACKUP) && active > 0) {                   // (more than 64 slots per game: slot by slot)
         for (int i = 0; i < P.K; ++i) {
-            if (uni((int)gv.s_state[i]) != SIM_LEAF) continue;
+            const int st = uni((int)gv.s_state[i]);
+            if (st != SIM_LEAF && !(CACHE && st == SIM_CACHED)) continue;
             const int node = uni(gv.s_node[i]);
             const int depth = uni(gv.s_depth[i]);
             size_t slot = (size_t)g * P.K + i;
+            if constexpr (CACHE) {
+                if (st == SIM_CACHED) {                               // answered by the cache: the value waits in s_cval
+                    const float cv = __int_as_float(uni(__float_as_int(C.s_cval[slot])));
+                    cached_attach(gv, node, keep_v, cv);
+                    load_path(P, gv, L, i, depth);
+                    backup(P, gv, L, depth, (double)cv);
+                    sim_finish(gv, i, &active);
+                    continue;
+                }
+            }
             if (compact) {
                 const int row = uni(B.s_qrow[slot]);
                 if (row >= 0) slot = (size_t)row;
@@ -2131,7 +2213,8 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df);
+        run_sim<HIST, GUM, CACHE>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
+                                  (mask & SIM_SELECT) != 0);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -2159,6 +2242,84 @@ __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, 
     count(gv, (mask & SIM_SELECT) ? CT_CYC_KERNEL_SELECT : CT_CYC_KERNEL_BACKUP, (unsigned long long)(clock64() - prof_k0));
 #endif
     counters_flush(gv);
+}
+
+template <bool HIST, bool GUM>
+__global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                           const float* __restrict__ value, void* planes, int mask, int compact,
+                                           int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, GUM, false>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
+}
+
+// k_sim with the evaluation cache on (14 input planes only: cz_search_set_eval_cache refuses the history input)
+template <bool GUM>
+__global__ __launch_bounds__(64, 4) void k_sim_cached(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                                  const float* __restrict__ value, void* planes, int mask, int compact,
+                                                  int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, EvalCache C)
+{
+    __shared__ SearchLDS L;
+    sim_body<false, GUM, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, C);
+}
+
+// The evaluation cache's only writer: the first launch of a round (before k_sim(BACKUP), which attaches the same rows),
+// one wave per queue slot.  A slot that holds an evaluated leaf (SIM_LEAF) of a searching game forms the leaf's priors from
+// its policy row with the attach's own functions (leaf_pre_b, prior_norm: the same bits by construction) and writes key,
+// mirror bit, value, move count and priors into the position's entry, over whatever was there.  Two waves may want one entry
+// in the same launch: one compare-and-swap on the entry's claim word with the round's stamp decides, the loser drops its
+// store and counts nothing -- at most one writer per entry and round, nothing to reset, no wave waits for another.
+__global__ __launch_bounds__(64) void k_cache_fill(SearchParams P, SearchBuffers B, EvalCache C,
+                                                  const float* __restrict__ policy, const float* __restrict__ value,
+                                                  int compact)
+{
+    const int slot = blockIdx.x;
+    if (slot >= P.G * P.K) return;
+    // stamp 0: the first round after the table was made or emptied -- its rows were evaluated before that (by the network
+    // the caller replaced, cz_search_eval_cache_clear) and stay out; 0 is also the claim word of an entry never claimed
+    const uint32_t stamp = uniu(*C.stamp);
+    if (stamp == 0u) return;
+    const int g = slot / P.K;
+    if (uni((int)B.g_phase[g]) != PH_SEARCH) return;                  // (k_sim attaches nothing for such a game either)
+    if (uni((int)B.s_state[slot]) != SIM_LEAF) return;
+    const int lane = lane_id();
+    int row = slot;
+    if (compact) {
+        const int r = uni(B.s_qrow[slot]);
+        if (r >= 0) row = r;
+    }
+    const uint32_t node = uniu((uint32_t)B.s_node[slot]);
+    const uint32_t chunk = uniu(B.g_chunk_tab[(size_t)g * P.max_chunks + (node >> CHUNK_SHIFT)]);
+    char* base = B.pool + ((size_t)chunk << 20) + ((size_t)(node & (uint32_t)(CHUNK_GRANULES - 1)) << 4);   // (rec_ptr)
+    const uint32_t meta = load_hdr(base).meta;
+    if (!(meta & NODE_WAITING)) return;
+    const int nm = (int)(meta & 0xFF);
+    const bool mir = (meta & NODE_MIRRORED) != 0u;
+    const uint32_t* nk = reinterpret_cast<const uint32_t*>(base);
+    const uint32_t kw = lane < KEY_WORDS ? nk[lane] : 0u;
+    const uint64_t h = uni64(hash_of_key(nk));
+    EvalCacheEntry* e = C.tab + ec_slot(h, mir, C.log2);
+    int won = 0;
+    if (lane == 0) {
+        const uint32_t old = __hip_atomic_load(&e->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old != stamp) won = atomicCAS(&e->claim, old, stamp) == old ? 1 : 0;
+    }
+    if (!uni(won)) return;
+    const uint16_t* pm = node_mv(base, nm);
+    LeafPre lp{0, 0, 0, 0.0f, 0.0f};
+    if (lane < nm) lp.m0 = pm[lane];
+    if (lane + 64 < nm) lp.m1 = pm[lane + 64];
+    leaf_pre_b(lp, meta, policy + (size_t)row * NLABELS);
+    float p0 = lp.p0, p1 = lp.p1;
+    const float all_p = prior_norm(p0, p1, nm, P.policy_logits != 0);
+    if (lane < KEY_WORDS) e->key[lane] = kw;
+    if (lane < nm) e->p[lane] = p0 / all_p;
+    if (lane + 64 < nm) e->p[lane + 64] = p1 / all_p;
+    if (lane == 0) {
+        e->value = value[row];
+        e->meta = ec_meta(nm, mir);
+        C.s_stores[slot] += 1ull;                                     // (this slot's wave is the word's only writer)
+    }
 }
 
 // End of a search: external mode marks the game READY; self-play mode plays the move, applies the game rules
@@ -2636,6 +2797,9 @@ struct cz_search {
     VisitRing V{};                    // root visit record (cz_search_record_visits); V.ring NULL = off
     void* vis_mem = nullptr;          // ring + control words + per-game flags, allocated only while recording is on
     void* book_mem = nullptr;         // the start-position book (cz_search_set_book): P.book points here
+    EvalCache C{};                    // evaluation cache (cz_search_set_eval_cache); C.tab NULL = off
+    void* ec_mem = nullptr;           // its bookkeeping (s_cval, stamp, counters), allocated only while the cache is on
+    size_t ec_ctr_bytes = 0;          // the counters at its start: what cz_search_eval_cache_clear zeroes
 };
 
 namespace {
@@ -2858,13 +3022,19 @@ int cz_search_destroy(cz_search* s)
     (void)hipFree(s->V.q);
     (void)hipFree(s->V.s);
     (void)hipFree(s->book_mem);
+    (void)hipFree(s->C.tab);
+    (void)hipFree(s->ec_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
     delete s;
     return CZ_OK;
 }
 
-size_t cz_search_bytes(const cz_search* s) { return s ? s->bytes : 0; }
+size_t cz_search_bytes(const cz_search* s)
+{
+    if (!s) return 0;
+    return s->bytes + (s->C.tab ? (size_t)ec_table_bytes(s->C.log2) : 0);     // (the evaluation cache's table, while it is on)
+}
 
 int cz_search_info(const cz_search* s, int32_t* out)
 {
@@ -2965,8 +3135,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const dim3 nblock(256);
     const bool hist = s->P.in_planes == 28;
     const bool gum = s->P.gumbel_m > 0;
+    const bool cache = s->C.tab != nullptr;
     auto sim = [&](int mask, int cq) {
-        if (gum) {
+        if (cache) {         // (14 planes: cz_search_set_eval_cache refuses the history input)
+            if (gum) hipLaunchKernelGGL((k_sim_cached<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
+            else hipLaunchKernelGGL((k_sim_cached<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
+        } else if (gum) {
             if (hist) hipLaunchKernelGGL((k_sim<true, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
             else hipLaunchKernelGGL((k_sim<false, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         } else {
@@ -2974,6 +3148,9 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
             else hipLaunchKernelGGL((k_sim<false, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         }
     };
+    // evaluation cache: the rows the BACKUP launch is about to attach go into the table first (its only writer)
+    if (cache)
+        hipLaunchKernelGGL(k_cache_fill, dim3(s->P.G * s->P.K), block, 0, st, s->P, s->B, s->C, policy, value, consume_compact);
     sim(SIM_BACKUP, consume_compact);
     if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
@@ -3032,7 +3209,134 @@ int cz_search_leaf_planes(cz_search* s, int on)
 int cz_search_policy_logits(cz_search* s, int on)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_policy_logits: null handle");
-    s->P.policy_logits = on ? 1 : 0;
+    const int mode = on ? 1 : 0;
+    if (mode != s->P.policy_logits && s->C.tab) {
+        // the meaning of a row changes: what the evaluation cache holds was formed under the other one.  This entry has no
+        // stream of its own, so the table is emptied between two device synchronisations.
+        hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return serr_hip("cz_search_policy_logits", e);
+        const int rc = cz_search_eval_cache_clear(s, nullptr);
+        if (rc != CZ_OK) return rc;
+        e = hipDeviceSynchronize();
+        if (e != hipSuccess) return serr_hip("cz_search_policy_logits", e);
+    }
+    s->P.policy_logits = mode;
+    return CZ_OK;
+}
+
+// ---- evaluation cache (include/czero.h; csrc/xq_evalcache.h has the layout and who touches the table when) ----
+static_assert(CZ_EVAL_CACHE_STRIDE == EC_STRIDE && CZ_EVAL_CACHE_MIN_LOG2 == EC_MIN_LOG2 && CZ_EVAL_CACHE_MAX_LOG2 == EC_MAX_LOG2,
+              "czero.h: evaluation cache");
+static_assert(EC_KEY_WORDS == KEY_WORDS && EC_MAX_MOVES == MAXMOVES, "xq_evalcache.h: entry layout");
+
+int cz_search_eval_cache_clear(cz_search* s, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_eval_cache_clear: null handle");
+    if (!s->C.tab) return CZ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(s->C.tab, 0, (size_t)ec_table_bytes(s->C.log2), st);
+    // The counters go and the stamp starts over at 0: the rows of the round that follows were evaluated BEFORE the table was
+    // emptied (by the network the caller is replacing), so that round's fill stores nothing; its k_sim(BACKUP) launch steps
+    // the stamp to 1 and the fills go on.  s_cval stays: slots the cache answered in the last round wait for their attach.
+    if (e == hipSuccess) e = hipMemsetAsync(s->ec_mem, 0, s->ec_ctr_bytes, st);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)s->C.stamp, 0, 1, st);
+    if (e != hipSuccess) return serr_hip("cz_search_eval_cache_clear", e);
+    return CZ_OK;
+}
+
+int cz_search_set_eval_cache(cz_search* s, int log2_entries, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: null handle");
+    if (log2_entries != 0 && (log2_entries < EC_MIN_LOG2 || log2_entries > EC_MAX_LOG2))
+        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: log2_entries must be 0 (off) or 10 .. 24");
+    if (log2_entries != 0 && s->P.in_planes == 28)
+        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: refused with the 28-plane history input: its second plane block "
+                                "depends on the simulation's path and the game history, so the network input is not a "
+                                "function of the position");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipStreamSynchronize(st);             // no launch that holds the old table is still running
+    if (e != hipSuccess) return serr_hip("cz_search_set_eval_cache", e);
+    if (s->C.tab && log2_entries == s->C.log2) return cz_search_eval_cache_clear(s, stream);
+    const size_t G = (size_t)s->P.G, slots = G * (size_t)s->P.K;
+    if (s->C.tab) {
+        // a slot the cache answered keeps its value in s_cval until the next round attaches it, and only the cached
+        // kernels attach it: the table goes or changes size between searches
+        uint8_t* st8 = new (std::nothrow) uint8_t[slots];
+        if (!st8) return serr(CZ_ERR_NOMEM, "cz_search_set_eval_cache: host allocation failed");
+        e = hipMemcpy(st8, s->B.s_state, slots, hipMemcpyDeviceToHost);
+        bool waiting = false;
+        for (size_t i = 0; e == hipSuccess && i < slots; ++i) waiting = waiting || st8[i] == SIM_CACHED;
+        delete[] st8;
+        if (e != hipSuccess) return serr_hip("cz_search_set_eval_cache", e);
+        if (waiting)
+            return serr(CZ_ERR_STATE, "cz_search_set_eval_cache: leaves the cache answered wait for their attach; switch it "
+                                      "off or resize it between searches (after cz_search_reset_trees, cz_search_set_roots "
+                                      "or cz_search_start_selfplay)");
+    }
+    (void)hipFree(s->C.tab);
+    (void)hipFree(s->ec_mem);
+    s->C = EvalCache{};
+    s->ec_mem = nullptr;
+    s->ec_ctr_bytes = 0;
+    if (log2_entries == 0) return CZ_OK;
+    const size_t off_stores = 0, off_probes = off_stores + align_up(8 * slots), off_hits = off_probes + align_up(8 * G),
+                 off_cval = off_hits + align_up(8 * G), off_stamp = off_cval + align_up(4 * slots);
+    const size_t aux = off_stamp + align_up(4);
+    void* tab = nullptr;
+    void* mem = nullptr;
+    e = hipMalloc(&tab, (size_t)ec_table_bytes(log2_entries));
+    if (e == hipSuccess) e = hipMalloc(&mem, aux);
+    if (e != hipSuccess) {
+        (void)hipFree(tab);
+        (void)hipGetLastError();
+        czi_set_error("cz_search_set_eval_cache: out of device memory for the table (the cache stays off)");
+        return e == hipErrorOutOfMemory ? CZ_ERR_NOMEM : serr_hip("cz_search_set_eval_cache: hipMalloc", e);
+    }
+    e = hipMemset(mem, 0, aux);
+    if (e != hipSuccess) { (void)hipFree(tab); (void)hipFree(mem); return serr_hip("cz_search_set_eval_cache: hipMemset", e); }
+    char* m = (char*)mem;
+    s->ec_mem = mem;
+    s->ec_ctr_bytes = off_cval;
+    s->C.tab = (EvalCacheEntry*)tab;
+    s->C.log2 = log2_entries;
+    s->C.s_stores = (unsigned long long*)(m + off_stores);
+    s->C.g_probes = (unsigned long long*)(m + off_probes);
+    s->C.g_hits = (unsigned long long*)(m + off_hits);
+    s->C.s_cval = (float*)(m + off_cval);
+    s->C.stamp = (uint32_t*)(m + off_stamp);
+    const int rc = cz_search_eval_cache_clear(s, stream);
+    if (rc == CZ_OK) e = hipStreamSynchronize(st);
+    if (rc != CZ_OK || e != hipSuccess) {
+        (void)hipFree(tab);
+        (void)hipFree(mem);
+        s->C = EvalCache{};
+        s->ec_mem = nullptr;
+        s->ec_ctr_bytes = 0;
+        return rc != CZ_OK ? rc : serr_hip("cz_search_set_eval_cache", e);
+    }
+    return CZ_OK;
+}
+
+int cz_search_eval_cache_info(cz_search* s, uint64_t* out, void* stream)
+{
+    if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_eval_cache_info: null argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!s->C.tab) return CZ_OK;
+    const size_t G = (size_t)s->P.G, slots = G * (size_t)s->P.K;
+    unsigned long long* host = new (std::nothrow) unsigned long long[slots + 2 * G];
+    if (!host) return serr(CZ_ERR_NOMEM, "cz_search_eval_cache_info: host allocation failed");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(host, s->C.s_stores, 8 * slots, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(host + slots, s->C.g_probes, 8 * G, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(host + slots + G, s->C.g_hits, 8 * G, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {
+        out[0] = 1ull << s->C.log2;
+        for (size_t g = 0; g < G; ++g) { out[1] += host[slots + g]; out[2] += host[slots + G + g]; }
+        for (size_t i = 0; i < slots; ++i) out[3] += host[i];
+    }
+    delete[] host;
+    if (e != hipSuccess) return serr_hip("cz_search_eval_cache_info", e);
     return CZ_OK;
 }
 

@@ -288,6 +288,49 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
  * keeps its setting. */
 int cz_search_set_leaf_mirror(cz_search* s, double rate, uint8_t* flags_or_null, void* stream);
 
+/* ---- cross-game evaluation cache (off by default; the reference has no such option; lc0's NNCache, KataGo's nnCache) ----
+ * A table of network results keyed by position, shared by all games of the search object and kept across games:
+ * cz_search_reset_trees, cz_search_set_roots and the start of a new self-play game do NOT empty it.  A new leaf whose
+ * position the table holds takes no queue row: its priors are copied into the node, its value waits beside the slot,
+ * and the next round attaches it at its place in simulation order with the evaluated leaves -- the node waits for that
+ * attach exactly as an evaluated leaf does, and simulations that reach it park as they do now.  A row's network output
+ * does not depend on its place in the batch and a node's priors are a function of its row and its move list, so THE
+ * SEARCH WITH THE CACHE ON PRODUCES THE BITS OF THE SEARCH WITH IT OFF: visit counts, W, priors, records, counters
+ * (`expansions` keeps counting tree growth; `hits` below says how many of them needed no row).  The caller must keep the
+ * network a function of the row alone and empty the table (cz_search_eval_cache_clear) when the network changes.
+ *
+ * THE TABLE.  Direct-mapped, 2^log2_entries entries of CZ_EVAL_CACHE_STRIDE bytes: the 48-byte packed position, the
+ * leaf-mirror bit the row was evaluated under (cz_search_set_leaf_mirror), the move count, the float32 value and
+ * float p[128], the priors exactly as the attach writes them into the node.  A match is the full position plus the
+ * mirror bit, never the hash alone; an entry is overwritten by the next position that maps to it.  The table is a
+ * device allocation of its own, made by this call from what the chunk pool left (the pool takes at most 80 % of the
+ * free memory); cz_search_bytes includes it while it is on.
+ *
+ * WHO TOUCHES IT WHEN.  Read only by the selection launch of a round (a leaf a resumed simulation creates in the backup
+ * launch does not ask and is evaluated as before); written only by a launch of its own at the start of a round, from
+ * the rows that round attaches, formed by the attach's own device functions; not touched by the backup launch.  All on
+ * the search's stream: a reader only sees entries an earlier launch completed.  No lock, no fence, no wait.  Positions
+ * asked for by several games in the SAME round are all evaluated (not merged).
+ *
+ * cz_search_set_eval_cache: log2_entries 0 switches it off and frees the table, otherwise CZ_EVAL_CACHE_MIN_LOG2 <=
+ * log2_entries <= CZ_EVAL_CACHE_MAX_LOG2 (the size it has already: the table is emptied).  CZ_ERR_ARG: s NULL,
+ * log2_entries outside that, or a search with 28 input planes (use_history: the second plane block depends on the
+ * simulation's path and on the game history, so the input is not a function of the position).  CZ_ERR_NOMEM: the
+ * allocation failed; the search stays usable with the cache off.  CZ_ERR_STATE: the table would go or change size while
+ * leaves it answered wait for their attach -- change it between searches.  Call it after cz_search_create, before the
+ * rounds and before a graph capture (the captured launches hold the table's address); synchronises the stream.
+ * cz_search_policy_logits empties the table when it changes the mode (the meaning of a row changes).
+ * cz_search_eval_cache_clear: empties the table and zeroes the numbers below (enqueued on the stream; leaves already
+ * answered keep their values).  The rows of the ONE round that follows were evaluated before the call -- by the network
+ * the caller is replacing -- and are not stored; the rounds after it store again.  cz_search_eval_cache_info: HOST out[4] = entries (0 = off), probes, hits, stores, summed
+ * since the table was made or last emptied; synchronises the stream. */
+#define CZ_EVAL_CACHE_STRIDE 576
+#define CZ_EVAL_CACHE_MIN_LOG2 10
+#define CZ_EVAL_CACHE_MAX_LOG2 24
+int cz_search_set_eval_cache(cz_search* s, int log2_entries, void* stream);
+int cz_search_eval_cache_clear(cz_search* s, void* stream);
+int cz_search_eval_cache_info(cz_search* s, uint64_t* out, void* stream);
+
 /* external mode (CChessPlayer.action): set the position to search for each game.  boards [G][90];
  * turns [G] or NULL; no_act [G][32] + n_no_act [G] or NULL (at most 32 banned moves per game); increase_temp / enable_resign [G] or NULL;
  * select_mask [G] or NULL (only games with a non-zero byte are touched).  Trees are kept (subtree reuse).
