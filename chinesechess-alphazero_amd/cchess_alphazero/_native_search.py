@@ -10,6 +10,9 @@ COUNTER_NAMES = ["sims", "expansions", "terminal_sims", "repetition_sims", "park
                  "edges_visited", "leaf_moves", "plies", "games", "red_wins", "black_wins", "draws", "resigns",
                  "tree_resets", "overflow_sims", "depth_overflow", "root_reused_sims", "ring_dropped", "chunks_taken",
                  "stat_blocks", "no_act_truncated",
+                 # MCTS solver (set_solver): descents that ended on a proven node, nodes that became WIN or LOSS, plies whose
+                 # remaining simulations a decided root cut
+                 "proven_sims", "proofs", "decided_plies",
                  # only in the CZ_SIM_PROFILE tuning build (the library reports how many counters it has)
                  "cyc_select", "cyc_rules", "cyc_hash", "cyc_expand", "cyc_rep", "cyc_attach", "cyc_resume_load",
                  "cyc_kernel_select", "cyc_kernel_backup"]
@@ -25,6 +28,7 @@ VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (
 VISIT_GUMBEL = 8         # visit entry flag: n holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
 GUMBEL_MAX_M = 128       # include/czero.h CZ_GUMBEL_MAX_M
 EVAL_CACHE_STRIDE = 576  # include/czero.h CZ_EVAL_CACHE_STRIDE: bytes per entry of the evaluation cache
+PROOF_OPEN, PROOF_WIN, PROOF_LOSS = 0, 1, 2   # include/czero.h CZ_PROOF_*: a position's status from its mover's view
 EVAL_CACHE_LOG2 = (10, 24)   # CZ_EVAL_CACHE_MIN_LOG2 / CZ_EVAL_CACHE_MAX_LOG2: the sizes set_eval_cache takes, besides 0 = off
 
 
@@ -119,6 +123,9 @@ def declare(L):
         "cz_search_set_eval_cache": [vp, i32, vp],
         "cz_search_eval_cache_clear": [vp, vp],
         "cz_search_eval_cache_info": [vp, vp, vp],
+        "cz_search_set_solver": [vp, i32, vp],
+        "cz_search_node_proof": [vp, vp, i32, vp, vp, vp, vp, vp],
+        "cz_search_root_decided": [vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -225,6 +232,7 @@ class Search:
         self.gumbel_m = 0                      # set_gumbel(): candidates of the Gumbel root search, 0 = off
         self.gumbel_full = False               # set_gumbel_full(): the Gumbel rule below the root and v_mix in the target
         self.eval_cache = 0                    # set_eval_cache(): log2 of the evaluation cache's entries, 0 = off
+        self.solver = False                    # set_solver(): forced wins and losses are proven in the tree
 
     # -- lifetime --
     def close(self):
@@ -391,6 +399,47 @@ class Search:
         v = check_eval_cache_log2(log2_entries, "set_eval_cache: log2_entries")
         _native.check(self.L.cz_search_set_eval_cache(self.h, v, self._stream()), "cz_search_set_eval_cache")
         self.eval_cache = v
+
+    def set_solver(self, on=True):
+        """MCTS solver (cz_search_set_solver; include/czero.h has the definitions): a node whose every move allows the
+        king's capture is proven lost and the move that leads to it wins; proven nodes end a descent without a network
+        row, a winning root move is taken at once, a decided root starts no further simulation, and at a won root the
+        played move is the winning one.  Refused while the Gumbel root search, forced playouts or the evaluation cache
+        are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
+        if not hasattr(self.L, "cz_search_set_solver"):
+            raise _native.NativeError("this libczero.so has no MCTS solver (cz_search_set_solver)")
+        _native.check(self.L.cz_search_set_solver(self.h, 1 if on else 0, self._stream()), "cz_search_set_solver")
+        self.solver = bool(on)
+
+    def node_proof(self, path=None):
+        """The proof state of the node node_stats(path) reports (cz_search_node_proof): dict(status int8 [G] -- PROOF_OPEN /
+        PROOF_WIN / PROOF_LOSS from the node's mover's view, -1 where the position is not linked in the tree --, dist uint8
+        [G], mark and mark_dist uint8 [G, 128]: per edge the status of its child as the edge holds it, and that child's
+        dist).  Works with the solver off."""
+        import torch
+        G, M = self.G, _native.MAXMOVES
+        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        status = torch.empty((G,), dtype=torch.int8, device=self.device)
+        dist = torch.empty((G,), dtype=torch.uint8, device=self.device)
+        mark = torch.empty((G, M), dtype=torch.uint8, device=self.device)
+        mark_dist = torch.empty((G, M), dtype=torch.uint8, device=self.device)
+        _native.check(self.L.cz_search_node_proof(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
+                                                  pa.shape[1], C.c_void_p(status.data_ptr()), C.c_void_p(dist.data_ptr()),
+                                                  C.c_void_p(mark.data_ptr()), C.c_void_p(mark_dist.data_ptr()),
+                                                  self._stream()), "cz_search_node_proof")
+        return dict(status=status.cpu().numpy(), dist=dist.cpu().numpy(), mark=mark.cpu().numpy(),
+                    mark_dist=mark_dist.cpu().numpy())
+
+    def root_decided(self):
+        """uint8 [G]: 1 where the game's current root is decided -- proven lost, or proven won with a winning move that is
+        not banned this ply (cz_search_root_decided)."""
+        import torch
+        out = torch.empty((self.G,), dtype=torch.uint8, device=self.device)
+        _native.check(self.L.cz_search_root_decided(self.h, C.c_void_p(out.data_ptr()), self._stream()),
+                      "cz_search_root_decided")
+        return out.cpu().numpy()
 
     def clear_eval_cache(self):
         """Empty the evaluation cache and zero its numbers (cz_search_eval_cache_clear); nothing to do while it is off."""

@@ -40,7 +40,7 @@ class VisitState:
 
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
-                 debugging=False, uci=False, use_history=False, side=0):
+                 debugging=False, uci=False, use_history=False, side=0, solver=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -81,6 +81,12 @@ class CChessPlayer:
                               pool_chunks=256 if uci else 0,
                               use_history=use_history)
         self._torch = torch
+        # MCTS solver (cz_search_set_solver): None = config.engine.solver, off by default.  After action() self.proof is the
+        # root's (status, d) -- (0, 0) while the option is off or nothing is proven.
+        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False) if solver is None else solver)
+        self.proof = (0, 0)
+        if self.solver:
+            self._search.set_solver(True)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes):
@@ -258,6 +264,9 @@ class CChessPlayer:
             if self.debugging:
                 order = sorted(node.a.items(), key=lambda kv: -kv[1].n)[:5]
                 self.search_results = {m: (a.n, a.q, a.p) for m, a in order}
+            if self.solver:
+                pr = s.node_proof()
+                self.proof = (max(0, int(pr["status"][0])), int(pr["dist"][0]))
             action = int(s.choose([float(np.random.random_sample())])[0])
             self.last_action = self.labels[action] if action >= 0 else None
             if action < 0:
@@ -276,7 +285,8 @@ class CChessPlayer:
 
     def close_and_return_action(self, state, turns, no_act=None):
         """UCI `stop` (player.py:88-106): end the running search and answer from what has been searched so far.
-        Returns (action, value, depth) or None when the player resigns."""
+        Returns (action, value, depth) -- with the MCTS solver on (action, value, depth, proof) -- or None when the
+        player resigns."""
         self.job_done = True
         self._idle.wait()                                      # the searching thread finishes its in-flight batch
         node = self.tree.get(state)
@@ -289,4 +299,6 @@ class CChessPlayer:
         # the search thread's own choice (same calc_policy / temperature / sampling path) is in last_action
         if self.last_action is None:
             return None
+        if self.solver:                                        # (the UCI front-end prints `score mate N` from it)
+            return self.last_action, value, self.done_tasks // 100, self.proof
         return self.last_action, value, self.done_tasks // 100

@@ -114,6 +114,8 @@ class EngineConfig(_Section):
                          gumbel_scale=1.0,        # c_scale; the recorded pi is softmax(log prior + sigma(completed Q)); 0 = off
                          gumbel_full=False,       # full Gumbel search (run.py self --gumbel-full, needs gumbel): the Gumbel rule
                                                   # below the root too, v_mix in the recorded pi (cz_search_set_gumbel_full)
+                         solver=False,            # MCTS solver (run.py self / eval --solver, UCI option Solver): forced wins and
+                                                  # losses are proven in the search tree (cz_search_set_solver)
                          eval_cache=0,            # cross-game evaluation cache (run.py self --eval-cache LOG2): a table of
                                                   # 2**LOG2 network results keyed by position, kept across games; a new leaf
                                                   # it holds takes no queue row; same search bit for bit; 576 B per entry;

@@ -43,7 +43,7 @@ class SelfPlayEngine:
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
-                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None):
+                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -77,9 +77,16 @@ class SelfPlayEngine:
         eval_cache: log2 of the entries of the cross-game evaluation cache (None = config.engine.eval_cache; 0 = off, else
         10 .. 24): network results keyed by position, shared by all games and kept across games; a new leaf the table
         holds takes no queue row, and the games, records and counters are the ones played without it
-        (cz_search_set_eval_cache).  Every network change empties it (_install).  Excludes use_history."""
+        (cz_search_set_eval_cache).  Every network change empties it (_install).  Excludes use_history.
+        solver: the MCTS solver (None = config.engine.solver; excludes gumbel, forced_playouts and eval_cache): forced wins
+        and losses are proven in the tree from the king captures the search meets, proven positions end a descent without a
+        network row, a decided root starts no further simulation and a won root plays the winning move
+        (cz_search_set_solver).  The records are what the tree holds: no target is rewritten."""
+        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False) if solver is None else solver)
         self.eval_cache = check_eval_cache_log2(getattr(getattr(config, "engine", None), "eval_cache", 0)
                                                 if eval_cache is None else eval_cache)
+        if self.solver and self.eval_cache:
+            raise ValueError("solver excludes eval_cache: the cache has a kernel instantiation of its own")
         if self.eval_cache and use_history:
             raise ValueError("eval_cache excludes use_history: the second block of the 28-plane input depends on the "
                              "simulation's path and the game history, so the network input is not a function of the position")
@@ -179,6 +186,10 @@ class SelfPlayEngine:
             self.search.set_gumbel(self.gumbel, self.gumbel_visit, self.gumbel_scale)
         if self.gumbel_full:
             self.search.set_gumbel_full(True)
+        if self.solver and (self.gumbel or self.forced_playouts):
+            raise ValueError("solver excludes gumbel and forced_playouts: each defines its own root rule")
+        if self.solver:                                        # likewise
+            self.search.set_solver(True)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py

@@ -85,6 +85,10 @@ _FLAGS = [
                                "(576 bytes each), shared by all games and kept across games; a new leaf whose position it "
                                "holds is not evaluated again.  The search stays the same bit for bit (0 = off; 10 <= LOG2 "
                                "<= 24)")),
+    ("--solver", dict(action="store_true",
+                      help="(self, eval) MCTS solver: a position whose every move allows the king's capture is proven lost "
+                           "and the move that leads to it wins; proven positions end a simulation without a network "
+                           "evaluation, a decided root is not searched further and a won root plays the winning move")),
     ("--sims", dict(type=int, default=None, metavar="N",
                     help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
@@ -187,6 +191,15 @@ def build_config(args):
             raise SystemExit("--eval-cache needs the 14-plane input: with 28 planes the second block depends on the "
                              "simulation's path and the game history, so the network input is not a function of the position")
     engine.eval_cache = args.eval_cache
+    if args.solver and args.cmd not in ("self", "eval"):
+        raise SystemExit("--solver is an option of `run.py self` and `run.py eval`")
+    if args.solver and args.gumbel:
+        raise SystemExit("--solver excludes --gumbel: each defines its own root rule")
+    if args.solver and args.forced_playouts:
+        raise SystemExit("--solver excludes --forced-playouts: each defines its own root rule")
+    if args.solver and args.eval_cache:
+        raise SystemExit("--solver excludes --eval-cache: the cache has a kernel instantiation of its own")
+    engine.solver = bool(args.solver)
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

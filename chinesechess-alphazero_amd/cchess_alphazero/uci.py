@@ -22,7 +22,8 @@ logger = getLogger(__name__)
 
 ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference), MI355X-native engine",
              "id version 2.4", "option name gpu spin default 0 min 0 max 7",
-             "option name Threads spin default 10 min 0 max 1024")
+             "option name Threads spin default 10 min 0 max 1024",
+             "option name Solver type check default false")
 
 
 class UCI:
@@ -94,6 +95,8 @@ class UCI:
                 self.config.opts.device_list = args[3]
             elif args[1] == "Threads":
                 self.config.play.search_threads = int(args[3])
+            elif args[1] == "Solver":                     # MCTS solver (cz_search_set_solver): the next `go` searches with it
+                self.config.engine.solver = args[3].lower() == "true"
 
     def cmd_position(self, args):
         if not self.is_ready:
@@ -214,7 +217,8 @@ class UCI:
         if action is None:
             self._worker_answer(player, None)
         else:
-            self._worker_answer(player, (action, player.debug[self.state][1], player.done_tasks // 100))
+            self._worker_answer(player, (action, player.debug[self.state][1], player.done_tasks // 100,
+                                         getattr(player, "proof", None)))
 
     def _worker_answer(self, player, ret):
         with self._lock:
@@ -240,11 +244,17 @@ class UCI:
             self.player = None
         self._worker = None
 
-    def info_best_move(self, action, value, depth):
+    def info_best_move(self, action, value, depth, proof=None):
+        """proof: the root's (status, d) of the MCTS solver, when it is on: a proven root is reported as `score mate N`,
+        N moves of the side to move, negative when it is the one being mated."""
         if not self.is_red_turn:
             value = -value
         duration = max(time() - self.start_time, 1e-9)
-        self._say(f"info depth {depth} score {int(value * 1000)} time {int(duration * 1000)} "
+        score = str(int(value * 1000))
+        mate = mate_in(*proof) if proof else None
+        if mate is not None:
+            score = f"mate {mate}"
+        self._say(f"info depth {depth} score {score} time {int(duration * 1000)} "
                   f"nps {int(depth * 100 / duration) * 1000}")
         ponder = None
         node = self.search_tree.get(senv.step(self.state, action))
@@ -259,6 +269,16 @@ class UCI:
         if ponder:
             line += f" ponder {senv.to_uci_move(flip_move(ponder) if self.is_red_turn else ponder)}"
         self._say(line)
+
+
+def mate_in(status, d):
+    """`score mate N` of a root the MCTS solver has proven: WIN(d) (status 1) is mate in N = (d - 1) / 2 moves -- d counts the
+    king capture, which is never played --, LOSS(d) (status 2) is N = -(d - 2) / 2; None for an OPEN root."""
+    if status == 1:
+        return (d - 1) // 2
+    if status == 2:
+        return -((d - 2) // 2)
+    return None
 
 
 def main(argv=None):

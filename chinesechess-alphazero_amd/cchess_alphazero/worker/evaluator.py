@@ -97,6 +97,8 @@ class EvaluateWorker:
         self.seed = seed
         # random leaf mirror of both models' searches (run.py eval --leaf-mirror P, cz_search_set_leaf_mirror); 0 = off
         self.leaf_mirror = float(getattr(getattr(config, "engine", None), "leaf_mirror", 0.0) or 0.0)
+        # MCTS solver of both models' searches (run.py eval --solver, cz_search_set_solver)
+        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False))
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -160,6 +162,9 @@ class EvaluateWorker:
         if self.leaf_mirror:                                   # (before any round, and before the compact form's graph capture)
             for s in searches:
                 s.set_leaf_mirror(self.leaf_mirror)
+        if self.solver:                                        # (likewise)
+            for s in searches:
+                s.set_solver(True)
 
         def counters_now():
             c = [s.counters() for s in searches]

@@ -113,6 +113,9 @@ class SelfPlayWorker:
         if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
             logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
                         f"mirror image with probability {self.engine.leaf_mirror}")
+        if getattr(self.engine, "solver", False):              # (config.engine.solver, likewise)
+            logger.info(f"Process {self.pid}-{self.rank}: MCTS solver: forced wins and losses are proven in the tree; a "
+                        f"decided root is not searched further, a won root plays the winning move")
         if getattr(self.engine, "eval_cache", 0):              # (config.engine.eval_cache, likewise)
             logger.info(f"Process {self.pid}-{self.rank}: evaluation cache: 2^{self.engine.eval_cache} entries, "
                         f"{self.engine.search.memory_info()['eval_cache_bytes'] >> 20} MiB, kept across games")

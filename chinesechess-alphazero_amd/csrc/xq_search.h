@@ -34,6 +34,14 @@ constexpr int RESERVE_MOVES = 80;      // moves per new node the per-ply reserva
 constexpr int CHILD_UNKNOWN = -1;
 constexpr int CHILD_TERM_WIN = -2;     // done() == (True, +1): value for the child's mover +1 -> x2
 constexpr int CHILD_TERM_LOSS = -3;    // done() == (True, -1)
+// MCTS solver (cz_search_set_solver): a child link that names a node (>= 0) is a 24-bit node id (MAX_CHUNKS x 65536
+// granules) with the edge mark above it -- the Proof of the child as last seen at a backup over the edge.  Every reader of
+// `child` strips the mark (child_id in xq_search.hip); the terminal codes are their own marks.
+constexpr int CHILD_ID_MASK = 0x00FFFFFF;
+constexpr int CHILD_MARK_SHIFT = 24;
+enum Proof : int { PROOF_OPEN = 0, PROOF_WIN = 1, PROOF_LOSS = 2 };   // a position's status, from its mover's view
+constexpr int PROOF_DIST_MAX = 255;    // plies to the terminal position along a line the tree holds: saturates here
+static_assert(MAX_CHUNKS * CHUNK_GRANULES <= CHILD_ID_MASK + 1, "a node id has to fit below the edge mark");
 
 enum SimState : uint8_t { SIM_IDLE = 0, SIM_LEAF = 1, SIM_PARKED = 2,
                           SIM_DEFERRED = 3,     // ended on a terminal / repeated position; backed up when the phase's descents are over (never outlives a launch)
@@ -43,6 +51,9 @@ enum SimState : uint8_t { SIM_IDLE = 0, SIM_LEAF = 1, SIM_PARKED = 2,
 enum NodeFlag : uint32_t { NODE_WAITING = 1u << 8,      // low 8 bits of node_meta = move count
                            NODE_MIRRORED = 1u << 9 };   // set beside NODE_WAITING: the leaf is evaluated in its mirror image
                                                         // (cz_search_set_leaf_mirror); cleared with it when the priors attach
+// MCTS solver: the node's Proof in bits 10-11 of node_meta and its distance in bits 16-23, written once (a first proof is
+// final) by lane 0 like the rest of the header; 0 = OPEN, so a tree grown with the solver off holds OPEN nodes only
+constexpr int NODE_PROOF_SHIFT = 10, NODE_DIST_SHIFT = 16;
 
 enum GameMode : int { MODE_EXTERNAL = 0, MODE_SELFPLAY = 1 };
 
@@ -59,6 +70,9 @@ enum Counter : int {
     CT_TREE_RESETS, CT_OVERFLOW_SIMS, CT_DEPTH_OVERFLOW, CT_ROOT_REUSED_SIMS, CT_RING_DROPPED, CT_CHUNKS_TAKEN,
     CT_STAT_BLOCKS,
     CT_NO_ACT_TRUNCATED,    // self-play: a perpetual-check ban that did not fit the MAX_NO_ACT list of the ply (dropped, counted)
+    CT_PROVEN_SIMS,         // MCTS solver: descents that ended on a proven node (worth +-2, no network row)
+    CT_PROOFS,              // MCTS solver: nodes that became WIN or LOSS
+    CT_DECIDED_PLIES,       // MCTS solver: plies whose remaining simulations a decided root cut
 #ifdef CZ_SIM_PROFILE       // tuning build (tools/ab_search.sh): shader-clock cycles of wave time per section of a simulation
     CT_CYC_SELECT, CT_CYC_RULES, CT_CYC_HASH, CT_CYC_EXPAND, CT_CYC_REP, CT_CYC_ATTACH, CT_CYC_RESUME_LOAD,
     CT_CYC_KERNEL_SELECT, CT_CYC_KERNEL_BACKUP,
@@ -119,6 +133,9 @@ struct SearchParams {
     // keeps expand_node's 0).
     int gumbel_full;        // 0 = off; 1: below the root argmax pi'(a) - N(a) / (1 + sum N) replaces PUCT, and the policy
                             // target completes the unvisited edges with v_mix instead of the visited edges' mean
+    // MCTS solver (cz_search_set_solver); read by the host alone, which launches the SOLVE instantiations of k_sim, k_advance
+    // and k_choose while it is on
+    int solver;             // 0 = off
 };
 constexpr int GUMBEL_MAX_M = 128;
 

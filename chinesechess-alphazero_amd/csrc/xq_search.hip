@@ -125,6 +125,25 @@ XQ_D float* node_p(char* base) { return reinterpret_cast<float*>(base + NODE_OFF
 XQ_D uint16_t* node_mv(char* base, int nm) { return reinterpret_cast<uint16_t*>(base + NODE_OFF_P + 4 * nm); }
 XQ_D EdgeStat* edge_ptr(const GameView& gv, uint32_t edge) { return reinterpret_cast<EdgeStat*>(rec_ptr(gv, edge)); }
 
+// ---- MCTS solver (include/czero.h, cz_search_set_solver): what the words say ------------------------------------------
+// An edge's child link without its mark: what every reader that follows the link uses.  The codes (< 0) stay as they are.
+XQ_D int child_id(int c) { return c < 0 ? c : (c & CHILD_ID_MASK); }
+// The edge mark: the Proof of the child.  A terminal child is marked by its code: (True, +1) is WIN(1), (True, -1) LOSS(0).
+XQ_D int child_mark(int c)
+{
+    if (c >= 0) return (c >> CHILD_MARK_SHIFT) & 3;
+    return c == CHILD_TERM_WIN ? PROOF_WIN : (c == CHILD_TERM_LOSS ? PROOF_LOSS : PROOF_OPEN);
+}
+XQ_D int meta_proof(uint32_t meta) { return (int)(meta >> NODE_PROOF_SHIFT) & 3; }
+XQ_D int meta_dist(uint32_t meta) { return (int)(meta >> NODE_DIST_SHIFT) & 0xFF; }
+// d of a MARKED child, fetched from the child's header (a first proof is final, so the header still says what the mark was
+// made from).  Any lane may ask: the header is lane 0's word, and every store of a proof is followed by a fence (solve_walk).
+XQ_D int child_dist(const GameView& gv, int c)
+{
+    if (c < 0) return c == CHILD_TERM_WIN ? 1 : 0;
+    return meta_dist(*reinterpret_cast<const uint32_t*>(rec_ptr(gv, (uint32_t)(c & CHILD_ID_MASK)) + NODE_OFF_HDR + 4));
+}
+
 // Counters accumulate in LDS while a kernel runs (no global round trip per event) and are flushed once.
 XQ_D void count(const GameView& gv, int which, unsigned long long by = 1)
 {
@@ -748,6 +767,189 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
     return r;
 }
 
+// ---- MCTS solver: selection, marking and deriving (include/czero.h, cz_search_set_solver) -------------------------------
+// Rule 1's edge among the lanes' winning edges (win[h]: edge lane + 64 h is winning and may be taken; ch[h] its child
+// word): the least d, the first in edge order on a tie; -1 without one.  The distances come from the child headers, which
+// is why this runs only once a winning edge exists.  Wave-uniform.
+XQ_D int solve_least(const GameView& gv, const bool win[2], const int ch[2])
+{
+    if ((__ballot(win[0]) | __ballot(win[1])) == 0ull) return -1;
+    const int lane = lane_id();
+    double key = -1.0e300;                                     // max of -(d * 128 + j) = the least (d, j)
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (win[h]) {
+            const double k = -(double)(child_dist(gv, ch[h]) * MAXMOVES + lane + 64 * h);
+            key = k > key ? k : key;
+        }
+    return (int)(-wave_max_f64(key)) & (MAXMOVES - 1);
+}
+
+// Rule 1 at a root: the non-banned winning edge of least d of the node at `base` (nm moves, statistics sb or nullptr), -1
+// without one.  The move choice (choose_action) and the decided-root test ask it.  All 64 lanes call it.
+XQ_D int solve_root_edge(const GameView& gv, char* base, const EdgeStat* sb, int nm, int n_no_act, const uint16_t* no_act)
+{
+    const int lane = lane_id();
+    const uint16_t* pm = node_mv(base, nm);
+    bool win[2] = {false, false};
+    int ch[2] = {CHILD_UNKNOWN, CHILD_UNKNOWN};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j >= nm || !sb) continue;
+        ch[h] = sb[j].child;
+        bool banned = false;
+        for (int k = 0; k < n_no_act; ++k) banned = banned || (no_act[k] == pm[j]);
+        win[h] = !banned && child_mark(ch[h]) == PROOF_LOSS;
+    }
+    return solve_least(gv, win, ch);
+}
+
+// Is the game's root decided -- LOSS, or WIN with a non-banned winning edge?  Then no further simulation starts this ply.
+// *edge (optional): rule 1's edge at such a WIN root, else -1.  All 64 lanes call it; wave-uniform.
+XQ_D bool solve_root_decided(const SearchBuffers& B, const GameView& gv, int* edge)
+{
+    if (edge) *edge = -1;
+    const int root = uni(B.g_root[gv.g]);
+    if (root <= 0) return false;                                // (-1: not in the tree; 0, "none": an object never given a root)
+    char* base = rec_ptr(gv, (uint32_t)root);
+    const NodeHdr hdr = load_hdr(base);
+    const int st = meta_proof(hdr.meta);
+    if (st == PROOF_LOSS) return true;
+    if (st != PROOF_WIN) return false;
+    const int nm = (int)(hdr.meta & 0xFF);
+    const int j = solve_root_edge(gv, base, hdr.stat ? edge_ptr(gv, hdr.stat) : nullptr, nm, uni((int)B.g_n_no_act[gv.g]),
+                                  B.g_no_act + (size_t)gv.g * MAX_NO_ACT);
+    if (edge) *edge = j;
+    return j >= 0;
+}
+
+// select_edge with the solver on, at the root and at OPEN nodes (the SOLVE instantiations of k_sim call it instead):
+//   1. among the non-banned edges a winning one is taken at once, the least d, the first in edge order on a tie;
+//   2. otherwise select_edge's rule -- the same expressions in the same order, the q > 1 - 1e-7 shortcut included -- over
+//      the non-banned edges that are not losing;
+//   3. every non-banned edge losing: over all non-banned edges.
+// Edge j is loaded by the lane that owns it (j & 63), both halves held at once: the marks come with the 16-byte load.
+XQ_D int select_solve(const SearchParams& P, const GameView& gv, char* base, const EdgeStat* sb, int sum_n, int nm,
+                      const RootCtx& rc)
+{
+    const int lane = lane_id();
+    const double xx = __dsqrt_rn((double)(sum_n + 1));
+    const float* pp = node_p(base);
+    const uint16_t* pm = node_mv(base, nm);
+    bool nb[2] = {false, false}, live[2] = {false, false}, win[2] = {false, false}, sure[2] = {false, false};
+    int ch[2] = {CHILD_UNKNOWN, CHILD_UNKNOWN}, mk[2] = {PROOF_OPEN, PROOF_OPEN};
+    double sc[2] = {-1.0e300, -1.0e300};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        if (j >= nm) continue;
+        EdgeStat es{0.0, 0, CHILD_UNKNOWN};
+        if (sb) es = sb[j];
+        const float p = pp[j];
+        const uint16_t mv = pm[j];
+        const int n = es.n;
+        const double w = es.w;
+        const double q = n ? w / (double)n : 0.0;
+        bool valid = true;
+        double u;
+        if (rc.is_root) {
+            if (rc.n_no_act) valid = !root_banned(rc, mv);
+            u = root_u(P, root_prior(P, rc, p, j), xx, n);
+        } else {
+            const float a = P.c_puct_f32 * p;
+            u = (double)a * xx / (double)(1 + n);
+        }
+        if (!valid) continue;
+        nb[h] = true;
+        ch[h] = es.child;
+        mk[h] = child_mark(es.child);
+        win[h] = mk[h] == PROOF_LOSS;
+        const double score = q + u;
+        live[h] = score >= -99999999.0;                         // (a rejected score leaves the edge out, as it does there)
+        sc[h] = score;
+        sure[h] = live[h] && q > (1.0 - 1e-7);
+    }
+    const int won = solve_least(gv, win, ch);                   // rule 1
+    if (won >= 0) return won;
+    // rules 2 and 3: the losing edges stay out unless every non-banned edge is one
+    const bool all_losing = (__ballot(nb[0] && mk[0] != PROOF_WIN) | __ballot(nb[1] && mk[1] != PROOF_WIN)) == 0ull;
+    double best_s = -1.0e300;
+    int best_j = -1;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        live[h] = live[h] && (all_losing || mk[h] != PROOF_WIN);
+        sure[h] = sure[h] && live[h];
+        if (live[h] && sc[h] >= best_s) { best_s = sc[h]; best_j = lane + 64 * h; }   // h = 1 has the larger index: wins ties
+    }
+    const int first_win = lowest_bit(__ballot(sure[0]), __ballot(sure[1]));     // player.py:309-311
+    if (first_win >= 0) return first_win;
+    const double m = wave_max_f64(best_s);                      // player.py:312-314: the LAST maximum, select_edge's vote
+    const bool top = best_j >= 0 && best_s == m;
+    const uint64_t t1 = __ballot(top && best_j >= 64), t0 = __ballot(top);
+    return t1 ? 64 + (63 - __clzll((long long)t1)) : (t0 ? 63 - __clzll((long long)t0) : -1);
+}
+
+// The second step of a backup, after the level-parallel one and only for a value of +-2: the simulation whose path (depth
+// entries) is in L.path_* ended on a terminal child or on a proven node.  Its last edge is marked with that position's
+// status, the node above derived if it is OPEN, and while a node becomes proven the walk goes on one level up; it stops at
+// the first node that stays OPEN (or was proven before).  Sequential over the levels; each level is one scan of the
+// node's edges over both halves, every edge read and written by its owner lane (j & 63), the header by lane 0.  The
+// distances of the marked children come from their headers, any lane asking: hence the fence after every proof stored.
+XQ_D void solve_walk(const GameView& gv, const SearchLDS& L, int depth)
+{
+    if (depth <= 0) return;
+    const int lane = lane_id();
+    int st;
+    {
+        const int c = uni(edge_ptr(gv, (uint32_t)L.path_edge[depth - 1])->child);
+        st = child_mark(c);                                     // a terminal child: its code
+        if (c >= 0) st = meta_proof(load_hdr(rec_ptr(gv, (uint32_t)child_id(c))).meta);
+    }
+    for (int i = depth - 1; i >= 0 && st != PROOF_OPEN; --i) {
+        const int e = L.path_edge[i];
+        char* base = rec_ptr(gv, (uint32_t)L.path_node[i]);
+        const NodeHdr hdr = load_hdr(base);
+        const int nm = (int)(hdr.meta & 0xFF);
+        const int je = (int)((uint32_t)e - hdr.stat);
+        EdgeStat* sb = edge_ptr(gv, hdr.stat);
+        if (lane == (je & 63)) {                                // marking
+            const int c = sb[je].child;
+            if (c >= 0) sb[je].child = (c & CHILD_ID_MASK) | (st << CHILD_MARK_SHIFT);
+        }
+        if (meta_proof(hdr.meta) != PROOF_OPEN) break;          // a first proof is final
+        bool win[2] = {false, false}, lose[2] = {false, false};
+        double near = -1.0e300, far = -1.0;                     // max of -d over the winning edges, max of d over the losing
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j >= nm) continue;
+            const int c = sb[j].child;
+            const int mk = child_mark(c);
+            if (mk == PROOF_OPEN) continue;
+            const double d = (double)child_dist(gv, c);
+            win[h] = mk == PROOF_LOSS;
+            lose[h] = mk == PROOF_WIN;
+            if (win[h]) near = -d > near ? -d : near;
+            else far = d > far ? d : far;
+        }
+        int d;
+        if (__ballot(win[0]) | __ballot(win[1])) {
+            st = PROOF_WIN;
+            d = 1 + (int)(-wave_max_f64(near));
+        } else if (nm > 0 && __popcll(__ballot(lose[0])) + __popcll(__ballot(lose[1])) == nm) {
+            st = PROOF_LOSS;
+            d = 1 + (int)wave_max_f64(far);
+        } else break;
+        d = d < PROOF_DIST_MAX ? d : PROOF_DIST_MAX;
+        if (lane == 0)
+            store_meta(base, hdr.meta | ((uint32_t)st << NODE_PROOF_SHIFT) | ((uint32_t)d << NODE_DIST_SHIFT));
+        count(gv, CT_PROOFS);
+        wave_sync_global();
+    }
+    wave_sync_global();
+}
+
 // ---- simulation bookkeeping --------------------------------------------------------------------------
 XQ_D void sim_finish(const GameView& gv, int sim, int* active)
 {
@@ -996,7 +1198,9 @@ XQ_D int edge_move(const GameView& gv, int node, int edge)
 // (MCTS_search, player.py:198-260).  `node` < 0 means the root position is not in the tree yet.
 // CACHE: the evaluation cache is on (cz_search_set_eval_cache); `probe` (the SELECT launch): a new leaf asks the table C
 // before it takes a queue row.
-template <bool HIST, bool GUM, bool CACHE>
+// SOLVE: the MCTS solver is on (cz_search_set_solver): the arrival on a proven node and select_solve; likewise an
+// instantiation of its own.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false>
 XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                   const RoundIO& io, const RootCtx& rc0, int root, int sim, int node, int depth, int* active,
                   Arena& ar, bool fresh, Deferred& df, const EvalCache& C, bool probe)
@@ -1051,6 +1255,16 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         char* base = rec_ptr(gv, (uint32_t)node);
         const NodeHdr hdr = load_hdr(base);
         const uint32_t meta = hdr.meta;
+        if constexpr (SOLVE) {
+            // arrival: the descent stepped onto a proven node (below the root: a proven root that is searched is not
+            // decided).  Worth what the terminal at the end of its line is worth, from this node's mover; deferred and
+            // flushed like a terminal result, no network row.
+            if (depth >= 1 && meta_proof(meta) != PROOF_OPEN) {
+                count(gv, CT_PROVEN_SIMS);
+                defer_result(gv, sim, depth, meta_proof(meta) == PROOF_WIN ? 2 : -2, df);
+                return;
+            }
+        }
         if (meta & NODE_WAITING) {                                  // player.py:238-242
             if (lane == 0) { gv.s_state[sim] = SIM_PARKED; gv.s_node[sim] = node; gv.s_depth[sim] = depth; }
             count(gv, CT_PARKED);
@@ -1086,7 +1300,12 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         RootCtx rc = rc0;
         rc.is_root = (node == root);                                // player.py:266
         rc.sim = sim;
-        const Picked pk = select_edge<GUM>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc, hdr.val);
+        Picked pk;
+        if constexpr (SOLVE) {                                      // (have = false: the edge is reloaded below)
+            pk = Picked{select_solve(P, gv, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc), false, 0, CHILD_UNKNOWN, 0, 0.0};
+        } else {
+            pk = select_edge<GUM>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc, hdr.val);
+        }
         if (pk.j < 0) {                                             // "Best action is None": cannot happen
             backup(P, gv, L, depth, 0.0);
             sim_finish(gv, sim, active);
@@ -1113,7 +1332,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         count(gv, CT_EDGES_VISITED, (unsigned long long)nm);
         depth += 1;
         wave_sync();
-        int child = pk.have ? pk.child : uni(ep->child);
+        int child = child_id(pk.have ? pk.child : uni(ep->child));  // (without the solver's mark)
         PROF(CT_CYC_SELECT);
         if (child == CHILD_UNKNOWN) {
             // (the table load of the move's squares is issued before the key's so that the two round trips overlap)
@@ -1177,6 +1396,8 @@ XQ_D void load_path(const SearchParams& P, const GameView& gv, SearchLDS& L, int
 }
 
 // apply the deferred terminal / repetition values of the phase that just ended, in index order
+// SOLVE: a value of +-2 (a terminal child, or the solver's arrival on a proven node) is followed by solve_walk
+template <bool SOLVE = false>
 XQ_D void flush_deferred(const SearchParams& P, const GameView& gv, SearchLDS& L, Deferred& df, int* active)
 {
     if (df.lo == 0 && df.hi == 0) return;
@@ -1186,6 +1407,9 @@ XQ_D void flush_deferred(const SearchParams& P, const GameView& gv, SearchLDS& L
         const double v = (double)uni(gv.s_node[i]);
         load_path(P, gv, L, i, depth);
         backup(P, gv, L, depth, v);
+        if constexpr (SOLVE) {
+            if (v == 2.0 || v == -2.0) solve_walk(gv, L, depth);
+        }
         sim_finish(gv, i, active);
     };
     while (df.lo) {
@@ -1352,6 +1576,9 @@ XQ_D int gumbel_choose(const SearchParams& P, const SearchBuffers& B, const Game
 
 // ---- calc_policy + apply_temperature + choice (player.py:375-406, 453-470, :195) ---------------------
 // returns the chosen label, or -1 when the player resigns.  u is the uniform draw of np.random.choice.
+// SOLVE (the MCTS solver is on, an instantiation of its own): at a WIN root with a non-banned winning edge the move is
+// that edge (rule 1 of select_solve), whatever tau is; resignation is tested first.
+template <bool SOLVE = false>
 XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, double u,
                        bool enable_resign)
 {
@@ -1396,6 +1623,10 @@ XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const Game
     }
     maxq = unid(maxq);
     if (maxq < P.resign_threshold && enable_resign && turns > P.min_resign_turn) return -1;   // :397-398
+    if constexpr (SOLVE) {
+        int won = -1;
+        if (solve_root_decided(B, gv, &won) && won >= 0) return uni((int)pm[won]);
+    }
     if (P.gumbel_m > 0) return gumbel_choose(P, B, gv);         // a Gumbel ply: no temperature, u is not used
     // order the edges by label (the policy vector is indexed by label)
 #pragma unroll
@@ -1906,7 +2137,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
 }
 
 // One ply of SelfPlayWorker.start_game after the search finished (self_play.py:124-212).
-template <bool FULL>        // (emit_visits')
+template <bool FULL, bool SOLVE = false>        // (emit_visits', choose_action's)
 XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                        const VisitRing& V)
 {
@@ -1918,7 +2149,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     uint32_t* hkeys = B.g_hist_key + (size_t)g * (P.max_plies + 2) * KEY_WORDS;
     uint16_t* hacts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
     const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
-    const int action = choose_action(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
+    const int action = choose_action<SOLVE>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);
         emit_visits<FULL>(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0);
@@ -2035,7 +2266,8 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // (cz_search_set_gumbel) is on; likewise.
 // CACHE: the evaluation cache (cz_search_set_eval_cache) is on; likewise, so that the kernels launched while it is off
 // are the text they were.  The body of both kernels: k_sim below (CACHE false, C never read) and k_sim_cached.
-template <bool HIST, bool GUM, bool CACHE>
+// SOLVE: the MCTS solver (cz_search_set_solver) is on; likewise.  The body of k_sim_solve too.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
                    int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C)
@@ -2198,11 +2430,20 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         } else if (df.lo != 0 || df.hi != 0) {
             // the descents of this phase (resumed simulations / a fresh batch) are over: the terminal and repetition
             // values they produced are applied now, in index order
-            flush_deferred(P, gv, L, df, &active);
+            flush_deferred<SOLVE>(P, gv, L, df, &active);
             continue;
         } else if ((mask & SIM_SELECT) && active == 0) {              // 3. next lock-step batch (player.py:169-178)
             const int tasks = uni(B.g_tasks_left[g]);
             if (tasks <= 0) break;                                    // search complete: k_advance takes over
+            if constexpr (SOLVE) {
+                // a decided root starts no further simulation this ply: tested before each batch, the first of a ply
+                // included (a root proven in an earlier ply's search costs nothing); nothing is in flight here
+                if (solve_root_decided(B, gv, nullptr)) {
+                    if (lane_id() == 0) B.g_tasks_left[g] = 0;
+                    count(gv, CT_DECIDED_PLIES);
+                    break;
+                }
+            }
             // A batch whose simulations all end on terminal / repeated positions needs no evaluation and the next one
             // could start at once -- in a won endgame that chains hundreds of batches inside one launch and the whole
             // round waits for this wave.  The order of simulations does not depend on where the chain is cut.
@@ -2213,8 +2454,8 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM, CACHE>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
-                                  (mask & SIM_SELECT) != 0);
+        run_sim<HIST, GUM, CACHE, SOLVE>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
+                                         (mask & SIM_SELECT) != 0);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -2261,6 +2502,16 @@ __global__ __launch_bounds__(64, 4) void k_sim_cached(SearchParams P, SearchBuff
 {
     __shared__ SearchLDS L;
     sim_body<false, GUM, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, C);
+}
+
+// k_sim with the MCTS solver on (cz_search_set_solver refuses the Gumbel search, forced playouts and the evaluation cache)
+template <bool HIST>
+__global__ __launch_bounds__(64, 4) void k_sim_solve(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                                 const float* __restrict__ value, void* planes, int mask, int compact,
+                                                 int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
 }
 
 // The evaluation cache's only writer: the first launch of a round (before k_sim(BACKUP), which attaches the same rows),
@@ -2326,7 +2577,8 @@ __global__ __launch_bounds__(64) void k_cache_fill(SearchParams P, SearchBuffers
 // and sets up the next search (or the next game).
 // FULL: the full Gumbel search is on (cz_search_set_gumbel_full): the visit entries hold its target.  An instantiation of
 // its own, so that the kernel launched while it is off is the text it was.
-template <bool FULL>
+// SOLVE: the MCTS solver is on (cz_search_set_solver): choose_action's; likewise.
+template <bool FULL, bool SOLVE = false>
 __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B, VisitRing V)
 {
     __shared__ SearchLDS L;
@@ -2337,7 +2589,7 @@ __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B,
     counters_begin(gv);
     if (P.mode == MODE_SELFPLAY) {
         for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
-            advance_game<FULL>(P, B, gv, L, V);
+            advance_game<FULL, SOLVE>(P, B, gv, L, V);
             if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
         }
     } else if (lane_id() == 0) {
@@ -2516,7 +2768,7 @@ XQ_D int walk_path(const SearchBuffers& B, const GameView& gv, const uint16_t* _
         if (hdr.stat) {
             const EdgeStat* sb = edge_ptr(gv, hdr.stat);
             for (int j = lane; j < pn; j += 64)
-                if (pm[j] == mv) child = sb[j].child;
+                if (pm[j] == mv) child = child_id(sb[j].child);
         }
         const unsigned long long hit = __ballot(child >= 0);
         root = hit ? __shfl(child, __ffsll((long long)hit) - 1) : -1;
@@ -2561,6 +2813,56 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
         if (sum_n) sum_n[g] = root_sum_n;
         if (counts) counts[g] = (uint8_t)nm;
     }
+}
+
+// MCTS solver: the proof state of the root, or of the node reached from it along path[g][0 .. path_len) as in k_root_stats:
+// status [G] (Proof; -1 where the position is not linked in the tree) and dist [G]; per edge the mark (Proof of the child:
+// terminal children by their code) and the marked child's distance, 0 past the node's edges and for an unmarked edge.
+__global__ __launch_bounds__(64) void k_node_proof(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                  int path_len, int8_t* __restrict__ status, uint8_t* __restrict__ dist,
+                                                  uint8_t* __restrict__ mark, uint8_t* __restrict__ mark_dist)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    int node = walk_path(B, gv, path, path_len);
+    if (node == 0) node = -1;                                   // (id 0 is "none": an object never given a root)
+    int nm = 0;
+    uint32_t meta = 0u;
+    const EdgeStat* sb = nullptr;
+    if (node >= 0) {
+        const NodeHdr hdr = load_hdr(rec_ptr(gv, (uint32_t)node));
+        meta = hdr.meta;
+        nm = (int)(meta & 0xFF);
+        if (hdr.stat) sb = edge_ptr(gv, hdr.stat);
+    }
+    for (int j = lane; j < MAXMOVES; j += 64) {
+        int mk = PROOF_OPEN, d = 0;
+        if (j < nm && sb) {
+            const int c = sb[j].child;
+            mk = child_mark(c);
+            if (mk != PROOF_OPEN) d = child_dist(gv, c);
+        }
+        if (mark) mark[(size_t)g * MAXMOVES + j] = (uint8_t)mk;
+        if (mark_dist) mark_dist[(size_t)g * MAXMOVES + j] = (uint8_t)d;
+    }
+    if (lane == 0) {
+        if (status) status[g] = node >= 0 ? (int8_t)meta_proof(meta) : (int8_t)-1;
+        if (dist) dist[g] = (uint8_t)meta_dist(meta);
+    }
+}
+
+// MCTS solver: out [G] = 1 where the game's current root is decided (solve_root_decided), with the bans of the ply
+__global__ __launch_bounds__(64) void k_root_decided(SearchParams P, SearchBuffers B, uint8_t* __restrict__ out)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const bool dec = solve_root_decided(B, gv, nullptr);
+    if (lane_id() == 0) out[g] = dec ? (uint8_t)1 : (uint8_t)0;
 }
 
 // What emit_visits would record for every current root, with the bans of the current set_roots (cz_search_root_targets,
@@ -2739,7 +3041,7 @@ __global__ __launch_bounds__(64) void k_pv(SearchParams P, SearchBuffers B, int 
             moves[(size_t)g * max_len + d] = pm[best_j];
             visits[(size_t)g * max_len + d] = best_n;
         }
-        node = uni(sb[best_j].child);
+        node = child_id(uni(sb[best_j].child));
     }
     for (int i = d + lane; i < max_len; i += 64) {
         moves[(size_t)g * max_len + i] = (uint16_t)NOMOVE;
@@ -2747,6 +3049,7 @@ __global__ __launch_bounds__(64) void k_pv(SearchParams P, SearchBuffers B, int 
     }
 }
 
+template <bool SOLVE>
 __global__ __launch_bounds__(64) void k_choose(SearchParams P, SearchBuffers B, const double* __restrict__ u,
                                               int32_t* __restrict__ action)
 {
@@ -2754,7 +3057,7 @@ __global__ __launch_bounds__(64) void k_choose(SearchParams P, SearchBuffers B, 
     const int g = blockIdx.x;
     if (g >= P.G) return;
     const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, L.chtab);   // counts go straight to the global block
-    const int a = choose_action(P, B, gv, L, u ? u[g] : 0.5, B.g_enable_resign[g] != 0);
+    const int a = choose_action<SOLVE>(P, B, gv, L, u ? u[g] : 0.5, B.g_enable_resign[g] != 0);
     if (lane_id() == 0) action[g] = a;
 }
 
@@ -3136,8 +3439,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool hist = s->P.in_planes == 28;
     const bool gum = s->P.gumbel_m > 0;
     const bool cache = s->C.tab != nullptr;
+    const bool solve = s->P.solver != 0;                        // (never with gum or cache: cz_search_set_solver)
     auto sim = [&](int mask, int cq) {
-        if (cache) {         // (14 planes: cz_search_set_eval_cache refuses the history input)
+        if (solve) {
+            if (hist) hipLaunchKernelGGL((k_sim_solve<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((k_sim_solve<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+        } else if (cache) {         // (14 planes: cz_search_set_eval_cache refuses the history input)
             if (gum) hipLaunchKernelGGL((k_sim_cached<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
             else hipLaunchKernelGGL((k_sim_cached<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
         } else if (gum) {
@@ -3153,6 +3460,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
         hipLaunchKernelGGL(k_cache_fill, dim3(s->P.G * s->P.K), block, 0, st, s->P, s->B, s->C, policy, value, consume_compact);
     sim(SIM_BACKUP, consume_compact);
     if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
+    else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
@@ -3253,6 +3561,8 @@ int cz_search_set_eval_cache(cz_search* s, int log2_entries, void* stream)
         return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: refused with the 28-plane history input: its second plane block "
                                 "depends on the simulation's path and the game history, so the network input is not a "
                                 "function of the position");
+    if (log2_entries != 0 && s->P.solver)
+        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the MCTS solver is on (cz_search_set_solver)");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipStreamSynchronize(st);             // no launch that holds the old table is still running
     if (e != hipSuccess) return serr_hip("cz_search_set_eval_cache", e);
@@ -3464,6 +3774,8 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
     if (e != hipSuccess) return serr_hip("cz_search_set_forced_playouts", e);
     if (k > 0.0 && s->P.gumbel_m > 0)
         return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: the Gumbel root search is on (cz_search_set_gumbel)");
+    if (k > 0.0 && s->P.solver)
+        return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: the MCTS solver is on (cz_search_set_solver)");
     s->P.forced_k = k;
     return CZ_OK;
 }
@@ -3488,12 +3800,53 @@ int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, vo
         return serr(CZ_ERR_ARG, "cz_search_set_gumbel: c_visit or c_scale negative or not finite");
     if (m > 0 && (s->P.forced_k > 0.0 || s->P.fast_sims > 0))
         return serr(CZ_ERR_ARG, "cz_search_set_gumbel: forced playouts or the playout cap are on, each defines its own root rule");
+    if (m > 0 && s->P.solver)
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the MCTS solver is on (cz_search_set_solver)");
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_gumbel", e);
     s->P.gumbel_m = m;
     s->P.gumbel_visit = c_visit;
     s->P.gumbel_scale = c_scale;
     if (m == 0) s->P.gumbel_full = 0;                           // (the full search is an option of the Gumbel root search)
+    return CZ_OK;
+}
+
+// ---- MCTS solver (include/czero.h) ---------------------------------------------------------------------------------------
+static_assert(CZ_PROOF_OPEN == PROOF_OPEN && CZ_PROOF_WIN == PROOF_WIN && CZ_PROOF_LOSS == PROOF_LOSS &&
+              CZ_PROOF_DIST_MAX == PROOF_DIST_MAX, "czero.h: MCTS solver");
+
+int cz_search_set_solver(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_solver: null handle");
+    if (on != 0 && on != 1) return serr(CZ_ERR_ARG, "cz_search_set_solver: on is neither 0 nor 1");
+    if (on && s->P.gumbel_m > 0)
+        return serr(CZ_ERR_ARG, "cz_search_set_solver: the Gumbel root search is on (cz_search_set_gumbel)");
+    if (on && s->P.forced_k > 0.0)
+        return serr(CZ_ERR_ARG, "cz_search_set_solver: forced playouts are on (cz_search_set_forced_playouts)");
+    if (on && s->C.tab)
+        return serr(CZ_ERR_ARG, "cz_search_set_solver: the evaluation cache is on (cz_search_set_eval_cache)");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_solver", e);
+    s->P.solver = on;
+    return CZ_OK;
+}
+
+int cz_search_node_proof(cz_search* s, const uint16_t* path, int path_len, int8_t* status, uint8_t* dist, uint8_t* mark,
+                         uint8_t* mark_dist, void* stream)
+{
+    if (!s || path_len < 0 || path_len > MAXD_LDS || (path_len > 0 && !path) || !status || !dist)
+        return serr(CZ_ERR_ARG, "cz_search_node_proof: bad argument");
+    hipLaunchKernelGGL(k_node_proof, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, path, path_len, status, dist,
+                       mark, mark_dist);
+    S_LAUNCH_CHECK("cz_search_node_proof");
+    return CZ_OK;
+}
+
+int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream)
+{
+    if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_decided: null argument");
+    hipLaunchKernelGGL(k_root_decided, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, out);
+    S_LAUNCH_CHECK("cz_search_root_decided");
     return CZ_OK;
 }
 
@@ -3834,7 +4187,8 @@ int cz_search_pv(cz_search* s, int max_len, uint16_t* moves, int32_t* visits, vo
 int cz_search_choose(cz_search* s, const double* u, int32_t* action, void* stream)
 {
     if (!s || !action) return serr(CZ_ERR_ARG, "cz_search_choose: null argument");
-    hipLaunchKernelGGL(k_choose, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
+    if (s->P.solver) hipLaunchKernelGGL(k_choose<true>, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
+    else hipLaunchKernelGGL(k_choose<false>, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
     S_LAUNCH_CHECK("cz_search_choose");
     return CZ_OK;
 }

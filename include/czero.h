@@ -658,6 +658,63 @@ int cz_gumbel_policy_target_v(const uint16_t* labels, const int32_t* n, const do
  * pointer, rows < 0, c_visit or c_scale negative or not finite. */
 int cz_gumbel_interior_pick(const int32_t* n, const double* w, const float* p, const uint8_t* n_edges, const float* v,
                             int rows, double c_visit, double c_scale, int32_t* out_pick, double* out_score, void* stream);
+/* ---- MCTS solver: forced wins and losses proven in the tree (off by default; the reference has no such option) --------
+ * run.py self / eval --solver, the UCI option Solver.  The search stores that a move leads to a king capture in the edge
+ * (a terminal child); with the solver on it draws the conclusions (Winands, Bjornsson, Saito: Monte-Carlo Tree Search
+ * Solver, 2008; lc0's certainty propagation).  With it off no kernel output, record or counter differs by a bit, and the
+ * kernels launched are the ones launched before it existed.
+ *
+ * STATUS.  A position s in a game's tree is OPEN, WIN(d) or LOSS(d) from its mover's view; d is the number of plies to a
+ * terminal position along a line the tree holds -- a bound, not the shortest line -- and saturates at CZ_PROOF_DIST_MAX.
+ *   terminal child   done(s') == (True, +1) counts as WIN(1), (True, -1) as LOSS(0).
+ *   edge mark        an edge (s, a) carries the status of its child as last seen at a backup over that edge; terminal
+ *                    children are marked by their code.  The edge is WINNING if the mark is LOSS, LOSING if it is WIN.
+ *   marking          a simulation that ends on a terminal child or on a proven node marks the last edge of its path when
+ *                    it is backed up.  Ordinary leaves, repetitions and overflow paths mark nothing.
+ *   deriving         after an edge of an OPEN s was marked: s becomes WIN(1 + min d over its winning edges) if it has a
+ *                    winning edge, LOSS(1 + max d over all edges) if every one of its nm > 0 edges is losing.  The first
+ *                    proof of a node is final.  If s became proven the edge above it on the path is marked and its node
+ *                    derived, and so on upward; the walk stops at the first node that stays OPEN.  Root bans play no part
+ *                    in a status: it belongs to the position.
+ *   arrival          a descent that steps onto a proven node at depth >= 1 ends there, after the repetition test, worth
+ *                    +2 for WIN and -2 for LOSS from that node's mover (what the terminal at the end of the line is
+ *                    worth); deferred and flushed like a terminal result, counted in proven_sims, no network row.
+ * SELECTION, at the root and at OPEN nodes:
+ *   1. among the non-banned edges a winning one is taken at once: the least d, the first in edge order on a tie;
+ *   2. otherwise the reference's rule, its q > 1 - 1e-7 shortcut included, over the non-banned edges that are not losing;
+ *   3. if every non-banned edge is losing, over all non-banned edges.
+ * DECIDED ROOT.  A root is decided if it is LOSS, or WIN with a non-banned winning edge.  A decided root starts no further
+ * simulation this ply -- tested before each batch, the first of a ply included -- and the ply is complete when the
+ * simulations in flight are backed up.
+ * MOVE CHOICE.  At a WIN root with a non-banned winning edge the played move is rule 1's edge, in self-play and in
+ * cz_search_choose, whatever tau is; resignation is tested first.  Everything else is unchanged: the recorded visit
+ * counts, q and surprise are what the tree holds.
+ * COUNTERS, appended to cz_search_counters: proven_sims (arrivals), proofs (nodes that became WIN or LOSS), decided_plies
+ * (plies whose remaining simulations a decided root cut).
+ * Draws and repetition values (they depend on the path), the longest defence at a LOSS root and the shortest mate are
+ * out of scope.
+ *
+ * WHERE IT LIVES.  The status sits in bits 10-11 and d in bits 16-23 of the node header's meta word, the edge mark in bits
+ * 24-25 of the edge's child word (node ids use 24 bits); the distances of marked children are read from their headers.
+ * No memory is added.  The trees keep their proofs when the solver is switched off; the search then ignores them.
+ *
+ * cz_search_set_solver: on is 0 or 1; CZ_ERR_ARG otherwise, when s is NULL, and when on = 1 while the Gumbel root search,
+ * forced playouts or the evaluation cache are on (each has a root rule or a kernel instantiation of its own; their setters
+ * refuse likewise while the solver is on).  Call it before cz_search_start_selfplay / cz_search_set_roots and before a
+ * graph capture; synchronises the stream. */
+#define CZ_PROOF_OPEN 0
+#define CZ_PROOF_WIN 1
+#define CZ_PROOF_LOSS 2
+#define CZ_PROOF_DIST_MAX 255
+int cz_search_set_solver(cz_search* s, int on, void* stream);
+/* The proof state of the node cz_search_node_stats would report for the same path (path NULL / path_len 0: the root;
+ * path_len at most 128): status [G] int8 (CZ_PROOF_*, -1 where the position is not linked in the tree) and dist [G] uint8;
+ * mark [G][128] and mark_dist [G][128] uint8 (either may be NULL): per edge the status of its child as the edge holds it
+ * and that child's d, 0 for an unmarked edge and past the node's edges.  All DEVICE.  Works with the solver off. */
+int cz_search_node_proof(cz_search* s, const uint16_t* path, int path_len, int8_t* status, uint8_t* dist, uint8_t* mark,
+                         uint8_t* mark_dist, void* stream);
+/* out [G] uint8 DEVICE: 1 where the game's current root is decided, with the bans of the current ply. */
+int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
