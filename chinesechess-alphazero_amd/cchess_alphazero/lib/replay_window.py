@@ -29,7 +29,7 @@ _LABEL = {m: i for i, m in enumerate(ActionLabelsRed)}
 MODES = {"played": 0, "visits": 1}
 INT32_MAX = 2 ** 31 - 1         # positions and visit entries are indexed with int32 (prev, row_ptr, the kernels' counts)
 Q_BOUND = 2.0                   # |q| of a record item: every value the search backs up is a network value in [-1, 1] or a
-                                # terminal one, done.v * 2 = +-2 (csrc/xq_search.hip backup), so every edge's w / n and their
+                                # terminal one, done.v * 2 = +-2 (csrc/xq_search_tree.h backup), so every edge's w / n and their
                                 # weighted mean lie in [-2, 2]
 S_BOUND = 70.0                  # a record item's policy surprise lies in [0, ln 1e30] (include/czero.h CZ_SURPRISE_BOUND)
 

@@ -6,8 +6,8 @@
 // exactly what the attach of an evaluated leaf would have written: a search with the table on produces the bits of the
 // search with it off.
 //
-// Who touches the table when (csrc/xq_search.hip): READ only by the k_sim(SELECT) launch (the probe of a new leaf),
-// WRITTEN only by k_cache_fill, the first launch of a round, NOT touched by the k_sim(BACKUP) launch.  All on the search's
+// Who touches the table when: READ only by the k_sim(SELECT) launch (the probe of a new leaf: cache_probe, csrc/xq_search_sim.h),
+// WRITTEN only by k_cache_fill (csrc/xq_search_round.h), the first launch of a round, NOT touched by the k_sim(BACKUP) launch.  All on the search's
 // one stream: a reader only ever sees entries an earlier launch completed.  No lock, no fence, no wait.
 //
 // Everything here is XQ_HD so that tests/test_eval_cache_cpu.py checks the same text (tests/evalcache_harness.cpp).

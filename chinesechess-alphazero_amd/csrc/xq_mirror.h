@@ -1,7 +1,7 @@
 // xq_mirror.h -- the left-right mirror image of a Xiangqi position (file x <-> 8 - x, a symmetry of the rules), device side.
 //
 // Shared by the trainer's mirror augmentation (xq_train.hip: flagged rows of k_gather_planes / k_policy_value_loss) and the
-// search's random leaf mirror (xq_search.hip: cz_search_set_leaf_mirror).  The host's view of the label map is
+// search's random leaf mirror (xq_search_tree.h: d_mirror, leaf_coin; cz_search_set_leaf_mirror).  The host's view of the label map is
 // cz_label_mirror (czero.h).
 #pragma once
 #include "xq_rules.h"

@@ -36,7 +36,7 @@ constexpr int CHILD_TERM_WIN = -2;     // done() == (True, +1): value for the ch
 constexpr int CHILD_TERM_LOSS = -3;    // done() == (True, -1)
 // MCTS solver (cz_search_set_solver): a child link that names a node (>= 0) is a 24-bit node id (MAX_CHUNKS x 65536
 // granules) with the edge mark above it -- the Proof of the child as last seen at a backup over the edge.  Every reader of
-// `child` strips the mark (child_id in xq_search.hip); the terminal codes are their own marks.
+// `child` strips the mark (child_id in xq_search_solver.h); the terminal codes are their own marks.
 constexpr int CHILD_ID_MASK = 0x00FFFFFF;
 constexpr int CHILD_MARK_SHIFT = 24;
 enum Proof : int { PROOF_OPEN = 0, PROOF_WIN = 1, PROOF_LOSS = 2 };   // a position's status, from its mover's view

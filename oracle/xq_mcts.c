@@ -290,7 +290,7 @@ static void descend(xqo_player *p, int idx)
         if (!node) {                                                  /* :211-221 expand */
             /* not in the reference: the engine's tree memory is finite.  An expansion refused because the tree already
              * holds max_nodes nodes ends the simulation with a value of 0 from where it stands -- the edge it just
-             * selected is in the path, so its virtual loss is returned (csrc/xq_search.hip run_sim: overflow_sims) */
+             * selected is in the path, so its virtual loss is returned (csrc/xq_search_sim.h run_sim: overflow_sims) */
             if (p->cfg.max_nodes > 0 && p->n_nodes >= p->cfg.max_nodes) {
                 p->ctr.overflow_sims++;
                 backup(p, s, 0.0);

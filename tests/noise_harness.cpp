@@ -1,6 +1,6 @@
 // tests/noise_harness.cpp -- CPU build of the root-noise generator (chinesechess-alphazero_amd/csrc/xq_noise.h), the
 // same code k_noise runs on the GPU with libm in place of the hardware approximations.  Built with g++ by
-// tests/test_noise_cpu.py; the stream addressing mirrors k_debug_noise (csrc/xq_search.hip).
+// tests/test_noise_cpu.py; the stream addressing mirrors k_debug_noise (csrc/xq_search_aux.h).
 #include <stdint.h>
 #include "../chinesechess-alphazero_amd/csrc/xq_noise.h"
 

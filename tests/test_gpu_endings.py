@@ -1,4 +1,4 @@
-"""-m gpu: the game loops on their rare endings -- advance_game (csrc/xq_search.hip, self-play) and the arena's host loop
+"""-m gpu: the game loops on their rare endings -- advance_game (csrc/xq_search_selfplay.h, self-play) and the arena's host loop
 (worker/evaluator.py, on the rule kernels) at max_game_length = 100, from the sparse endgame positions of
 tests/golden/endgame_book.txt: the 120-plies-without-capture draw BEFORE the length cap, the "no attacking piece" draw,
 three free repetitions, perpetual-check bans, the temperature bump, the length cap, and games of more than 64 plies, where

@@ -1,4 +1,4 @@
-"""-m gpu: the parts of the tree search (csrc/xq_search.hip) that the hash stub never reaches, against the oracle with the
+"""-m gpu: the parts of the tree search (csrc/xq_search_sim.h, xq_search_tree.h) that the hash stub never reaches, against the oracle with the
 same limits (oracle/xq_mcts.h max_depth / max_nodes), bit for bit like tests/test_gpu_search.py:
   1. paths longer than 64 plies: the second pass of every lane loop over a path (backup, find_in_path, load_path), the
      path rows [G][K][max_depth] and the LDS copy past index 64, history_board two plies up such a path;

@@ -2,7 +2,8 @@
 """GPU: the tree kernels alone in a sustained state, quickly.  4096 self-play games (normal search settings) driven by
 the hash-stub network (tests/stub_net.py: microseconds per round instead of 30 ms), so that a few thousand rounds --
 games in every phase, trees tens of thousands of nodes deep -- take seconds; then the search round is timed with HIP
-events over the next rounds (per-launch: mean / median / p99).  A/B tool for changes to csrc/xq_search.hip.
+events over the next rounds (per-launch: mean / median / p99).  A/B tool for changes to the search
+(csrc/xq_search.hip and the csrc/xq_search_*.h it is made of).
 
     python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1] [--leaf-mirror P]
 """
