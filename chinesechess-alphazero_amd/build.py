@@ -17,11 +17,20 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libczero.so")
-SOURCES = ["xq_kernels.hip", "xq_search.hip", "xq_nn_epilogue.hip", "xq_conv.hip", "xq_tower.hip", "xq_heads.hip",
-           "xq_train.hip"]
+SOURCES = ["xq_kernels.hip", "xq_search.hip", "xq_nn_epilogue.hip", "xq_conv.hip", "xq_conv_ip4.hip", "xq_tower.hip",
+           "xq_heads.hip", "xq_train.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-ffp-contract=off",          # PUCT / backup arithmetic must not be fused (bit-parity with the reference)
          "-fno-fast-math"]
+# Flags of single sources, behind FLAGS.  xq_conv_ip4.hip (the 128-filter chains of k_resblock_ip4_c8): MFMA destinations and C
+# operands are ordinary VGPRs instead of AGPRs, which the epilogues' VALU instructions cannot read (csrc/xq_conv_ip4.hip).  Per
+# kernel, not per project: the 192-filter chains and the pair kernels of xq_tower.hip spill more with it (EXPERIMENTS.md).
+EXTRA_FLAGS = {"xq_conv_ip4.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+
+
+def flags_for(source):
+    """The compiler flags of one source of SOURCES (a file name, or a path to it)."""
+    return FLAGS + EXTRA_FLAGS.get(os.path.basename(source), [])
 
 
 def _deps():
@@ -31,7 +40,7 @@ def _deps():
 
 
 def _sources():
-    return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    return [os.path.join(CSRC, s) for s in SOURCES]
 
 
 def needs_build(lib=LIB):
@@ -55,7 +64,7 @@ def build(force=False, verbose=True, defines=(), out=None):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(hdr_t, os.path.getmtime(src)):
             return obj
-        cmd = ["hipcc"] + FLAGS + list(defines) + ["-c", src, "-o", obj]
+        cmd = ["hipcc"] + flags_for(src) + list(defines) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

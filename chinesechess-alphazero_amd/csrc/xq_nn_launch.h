@@ -1,4 +1,4 @@
-// xq_nn_launch.h -- the host side the network entry points share (csrc/xq_conv.hip, csrc/xq_tower.hip, csrc/xq_heads.hip): error
+// xq_nn_launch.h -- the host side the network entry points share (csrc/xq_conv.hip, csrc/xq_conv_ip4.hip, csrc/xq_tower.hip, csrc/xq_heads.hip): error
 // returns, the CU count, grid sizes, the end of a launch, the chain argument's fill, the compact queue's context, the host
 // bf16 / f16 conversions of the packers and the prototypes of the two launches that cross translation units.  Host code only;
 // like xq_nn_common.h everything but those prototypes sits in an anonymous namespace.
@@ -15,7 +15,7 @@ extern "C" void czi_set_error(const char* msg);
 
 // The launches on the four-wave pair kernels, which live in one translation unit and are reached from both.  `name`: the entry
 // point, for nn_launched().  n_cu: nn_cu_count()'s.
-// csrc/xq_conv.hip, k_resblock_ip4_c8<128>: a chain of 128-filter blocks of one staged arithmetic (c6: 1, c8: 0); exit_mode: 0 =
+// csrc/xq_conv_ip4.hip, k_resblock_ip4_c8<128>: a chain of 128-filter blocks of one staged arithmetic (c6: 1, c8: 0); exit_mode: 0 =
 // the operand pair (c6 image, or the c8 image a c6 chain hands over), IP4_EXIT_PAIRS, IP4_EXIT_HEADS.
 extern "C" int czi_tower4_launch(const char* name, const void* x_hi, const void* x_img, const BlockChain<12>* ch, int c6,
                                  int exit_mode, void* y_hi, void* y_img, const float* head_w, const float* head_b, float* pol,

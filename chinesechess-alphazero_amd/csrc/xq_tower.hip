@@ -6,7 +6,7 @@
 // A chain takes a PAIR of boards per workgroup through all its blocks with the activations staying in LDS, so HBM sees a board at
 // the chain's entry and exit only.  A peaked-policy network (what training produces) is sent to c8 / f16x3 blocks by the
 // load-time guard, so every arithmetic has its chain:
-//   cz_tower        c6 / c8 blocks, all of one image format, on k_resblock_ip4_c8<128> (csrc/xq_conv.hip, czi_tower4_launch).
+//   cz_tower        c6 / c8 blocks, all of one image format, on k_resblock_ip4_c8<128> (csrc/xq_conv_ip4.hip, czi_tower4_launch).
 //                   Exit: the operand triple to HBM -- a c6 chain may end on the block that writes a c8 image (the hand-over of a
 //                   c6>N tower) --, (hi, lo) fp16 pairs (the hand-over of a c8>N tower to its f16x3 blocks), or the 1 x 1 head
 //                   convolutions.  (One format per chain: a whole hybrid tower in one launch ran its c8 blocks 6 % slower than

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Mnemonic histogram of every barrier-to-barrier segment of one kernel of csrc/xq_conv.hip (--source: another file of csrc/), from `hipcc -S` with build.py's
-flags (cross-compiles, no GPU; one compiler process).  The segments are in the order of the assembly text, which for the chained
+"""Mnemonic histogram of every barrier-to-barrier segment of one kernel of csrc/xq_conv_ip4.hip (--source: another file of csrc/), from `hipcc -S` with
+the flags build.py gives that source (build.flags_for: the chain unit is compiled with -mllvm -amdgpu-mfma-vgpr-form; cross-compiles, no GPU; one compiler process).  The segments are in the order of the assembly text, which for the chained
 tower kernel is the order of its phases: ... | K loop 1 | epilogue 1 | K loop 2 | epilogue 2 or staging | exit | fill.
 
     python tools/ip4_isa_phases.py [-DNAME[=V] ...] [--kernel SUBSTR] [--source xq_tower.hip] [--asm FILE] [--top N] [--json OUT]
@@ -42,7 +42,7 @@ def compile_asm(defines, source):
     import build
     tmp = tempfile.mkdtemp(prefix="ip4_isa_")
     out = os.path.join(tmp, "kernel.s")
-    cmd = ["hipcc"] + build.FLAGS + list(defines) + ["-w", "-S", "--cuda-device-only", os.path.join(build.CSRC, source), "-o", out]
+    cmd = ["hipcc"] + build.flags_for(source) + list(defines) + ["-w", "-S", "--cuda-device-only", os.path.join(build.CSRC, source), "-o", out]
     try:
         subprocess.check_call(cmd)                  # (-w: the source's warnings belong to the build; errors are shown)
         return open(out).read()
@@ -87,7 +87,7 @@ def main():
     opt = lambda k, d=None: argv[argv.index(k) + 1] if k in argv else d
     sub = opt("--kernel", DEFAULT_KERNEL)
     top = int(opt("--top", "0"))
-    text = open(opt("--asm")).read() if opt("--asm") else compile_asm([a for a in argv if a.startswith("-D")], opt("--source", "xq_conv.hip"))
+    text = open(opt("--asm")).read() if opt("--asm") else compile_asm([a for a in argv if a.startswith("-D")], opt("--source", "xq_conv_ip4.hip"))
     name, body, meta = kernel_text(text, sub)
     segs = segments(body)
     print(name)

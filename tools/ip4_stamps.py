@@ -8,7 +8,7 @@ last chained launch of a forward (blocks 1 - 6, heads exit).  Run on the MI355X:
     CZ_LIB=variants/libczero_ip4_stamps.so python tools/ip4_stamps.py profiles/ip4_stamps.json
     (the plain order, nothing requested early: add -DCZ_IP4_PREFETCH=0 to the build -> profiles/ip4_stamps_parent.json;
      the epilogues as they were before their instruction diet, or single items of it: add -DCZ_IP4_EPI=<mask>, 0 = before,
-     csrc/xq_conv.hip above k_resblock_ip4_c8 -> profiles/ip4_stamps_epilogues_parent.json / ip4_stamps_epilogues.json)
+     csrc/xq_conv_ip4.h above k_resblock_ip4_c8 -> profiles/ip4_stamps_epilogues_parent.json / ip4_stamps_epilogues.json)
 """
 import ctypes as C
 import json
