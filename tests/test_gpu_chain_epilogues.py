@@ -31,6 +31,8 @@ import struct
 
 import pytest
 
+from test_gpu_chain_prefetch import TAIL_FILL, _filled, _image as _filled_image, _tail_kept
+
 pytestmark = pytest.mark.gpu
 
 K_MID_OUT = {"c6k0": 0, "c6k12": 12}
@@ -136,7 +138,13 @@ def test_chain_of_two_equals_block_by_block_on_chosen_values(arith, nonfinite):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     exits = ["image", "hand_over" if c6 else "pairs", "heads"]
     ran = 0
+
+    def same_below(a, b, m):
+        return all(torch.equal(s[:m].contiguous().view(torch.uint8), t[:m].contiguous().view(torch.uint8)) for s, t in zip(a, b))
     for n in (3, 2 * cus * 2 + 1):
+        # the same chain with a device-side count one short of the launch shape, into outputs that start from the byte
+        # TAIL_FILL: the same bytes below the count, the fill from it on
+        short = dict(count=torch.tensor([n - 1], dtype=torch.int32, device="cuda"), fmt_x=fmt, fmt_y=fmt)
         x0 = _image(n, c6)
         _native.input_resblock(_planes(n), g.in_table32, g.in_bias32, *g._block_params(0), out=x0)
         # the first launch left relu(b2) of block 0 in the f16 image: 0 | the finite list
@@ -156,6 +164,9 @@ def test_chain_of_two_equals_block_by_block_on_chosen_values(arith, nonfinite):
                 _native.tower(x0, blocks, _native.IMG_C6 if c6_out else _native.IMG_C8, out=got, fmt_x=fmt, fmt_y=fmt)
                 assert _eq(want, got), tag
                 assert int(want[0].view(torch.int16).ne(0).sum()) > 0 and int(want[1].view(torch.uint8).ne(0).sum()) > 0, tag
+                cut = _filled_image(n, c6_out, TAIL_FILL)
+                _native.tower(x0, blocks, _native.IMG_C6 if c6_out else _native.IMG_C8, out=cut, **short)
+                assert same_below(got, cut, n - 1) and _tail_kept(cut, n - 1, TAIL_FILL), tag
             elif exit_ == "pairs":
                 r = torch.zeros((n, 90, 128), dtype=torch.float32, device="cuda")
                 _native.resblock(mid, *params[1], out_f32=r)
@@ -164,6 +175,9 @@ def test_chain_of_two_equals_block_by_block_on_chosen_values(arith, nonfinite):
                 got = tuple(torch.zeros((n, 90, 128), dtype=torch.float16, device="cuda") for _ in range(2))
                 _native.tower(x0, params, _native.IMG_PAIR, out=got, fmt_x=fmt, fmt_y=fmt)
                 assert _eq(want, got), tag
+                cut = tuple(_filled((n, 90, 128), torch.float16, TAIL_FILL) for _ in range(2))
+                _native.tower(x0, params, _native.IMG_PAIR, out=cut, **short)
+                assert same_below(got, cut, n - 1) and _tail_kept(cut, n - 1, TAIL_FILL), tag
             else:
                 feats = [tuple(torch.zeros((n, kk * 90), dtype=torch.float32, device="cuda") for kk in (npol, nval)) for _ in range(2)]
                 _native.tower(mid, params[1:], _native.EXIT_HEADS, heads=(hw, hb, npol) + feats[0], fmt_x=fmt[:1], fmt_y=fmt[:1])
@@ -171,5 +185,8 @@ def test_chain_of_two_equals_block_by_block_on_chosen_values(arith, nonfinite):
                 assert _eq(feats[0], feats[1]), tag
                 if not nonfinite:
                     assert torch.isfinite(feats[1][0]).all() and torch.isfinite(feats[1][1]).all(), tag
+                cut = tuple(_filled((n, kk * 90), torch.float32, TAIL_FILL) for kk in (npol, nval))
+                _native.tower(x0, params, _native.EXIT_HEADS, heads=(hw, hb, npol) + cut, **short)
+                assert same_below(feats[1], cut, n - 1) and _tail_kept(cut, n - 1, TAIL_FILL), tag
             ran += 1
     assert ran == 6

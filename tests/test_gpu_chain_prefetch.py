@@ -36,10 +36,26 @@ def _net128(arith, blocks, n_max):
     return g, planes
 
 
-def _image(n, c6):
+TAIL_FILL = 0x5A        # the byte the outputs of a launch with a device-side count start from: rows >= the count keep it
+
+
+def _filled(shape, dtype, fill=0):
+    """A tensor whose every BYTE is `fill` (0: zeros)."""
     import torch
-    return (torch.zeros((n, 90, 128), dtype=torch.float16, device="cuda"),
-            torch.zeros((n, 90, 256), dtype=torch.int8 if c6 else torch.uint8, device="cuda"))
+    t = torch.empty(shape, dtype=dtype, device="cuda")
+    t.view(torch.uint8).fill_(fill)
+    return t
+
+
+def _image(n, c6, fill=0):
+    import torch
+    return (_filled((n, 90, 128), torch.float16, fill), _filled((n, 90, 256), torch.int8 if c6 else torch.uint8, fill))
+
+
+def _tail_kept(out, m, fill):
+    """Rows >= m of every tensor of `out` still hold the fill byte."""
+    import torch
+    return all(bool((t[m:].contiguous().view(-1).view(torch.uint8) == fill).all()) for t in out)
 
 
 def _first(g, planes, c6):
@@ -89,27 +105,31 @@ def test_128_filter_chain_equals_block_by_block(arith, blocks, nb, exit_):
                 _native.resblock(cur, *g._block_params(i), out=nxt, count=count)
                 cur = nxt
             tag = (arith, nb, exit_, n, m)
+            fill = TAIL_FILL if short else 0
             if exit_ in ("image", "hand_over"):
                 c6_out = c6 and exit_ == "image"
                 want = _image(n, c6_out)
                 _native.resblock(cur, *g._block_params(nb), out=want, count=count)
-                got = _image(n, c6_out)
+                got = _image(n, c6_out, fill)
                 _native.tower(x0, chain, _native.IMG_C6 if c6_out else _native.IMG_C8, out=got, count=count, fmt_x=fmt, fmt_y=fmt)
                 assert _eq(want, got, m), tag
+                assert _tail_kept(got, m, fill), tag
             elif exit_ == "pairs":
                 r = torch.zeros((n, 90, 128), dtype=torch.float32, device="cuda")
                 _native.resblock(cur, *g._block_params(nb), out_f32=r, count=count)
                 hi = r.to(torch.float16)
                 want = (hi, (r - hi.float()).to(torch.float16))
-                got = tuple(torch.zeros((n, 90, 128), dtype=torch.float16, device="cuda") for _ in range(2))
+                got = tuple(_filled((n, 90, 128), torch.float16, fill) for _ in range(2))
                 _native.tower(x0, chain, _native.IMG_PAIR, out=got, count=count, fmt_x=fmt, fmt_y=fmt)
                 assert _eq(want, got, m), tag
+                assert _tail_kept(got, m, fill), tag
             else:
-                feats = [tuple(torch.zeros((n, k * 90), dtype=torch.float32, device="cuda") for k in (npol, nval)) for _ in range(2)]
+                feats = [tuple(_filled((n, k * 90), torch.float32, fill) for k in (npol, nval)) for _ in range(2)]
                 _native.tower(cur, chain[-1:], _native.EXIT_HEADS, heads=(hw, hb, npol) + feats[0], count=count,
                               fmt_x=fmt[:1], fmt_y=fmt[:1])
                 _native.tower(x0, chain, _native.EXIT_HEADS, heads=(hw, hb, npol) + feats[1], count=count, fmt_x=fmt, fmt_y=fmt)
                 assert torch.isfinite(feats[1][0][:m]).all() and _eq(feats[0], feats[1], m), tag
+                assert _tail_kept(feats[0], m, fill) and _tail_kept(feats[1], m, fill), tag
 
 
 @pytest.mark.parametrize("arith,blocks", [("c6", 2), ("c6", 6), ("c6", 12), ("c8", 1), ("c8", 2), ("c8", 6), ("c8", 12),

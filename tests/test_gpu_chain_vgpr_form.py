@@ -19,7 +19,7 @@ import functools
 import pytest
 
 from test_gpu_chain_epilogues import _net as _chosen_net, _planes as _chosen_planes
-from test_gpu_chain_prefetch import _first, _image, _net128
+from test_gpu_chain_prefetch import TAIL_FILL, _filled, _first, _image, _net128, _tail_kept
 
 pytestmark = pytest.mark.gpu
 
@@ -63,6 +63,7 @@ def _check(tag, x, blocks, last_for, c6, heads, n, m, exits):
     hw, hb, npol = heads
     count = torch.tensor([m], dtype=torch.int32, device="cuda") if m < n else None
     fmt = [_native.IMG_C6 if c6 else _native.IMG_C8] * len(blocks)
+    fill = TAIL_FILL if m < n else 0                        # (a device-side count: rows >= m of the chain's outputs keep this byte)
     cur = x
     for bp in blocks[:-1]:                                  # one launch per block: the one-block kernels
         nxt = _image(n, c6)
@@ -73,7 +74,7 @@ def _check(tag, x, blocks, last_for, c6, heads, n, m, exits):
         chain = blocks[:-1] + [last_for(exit_)]
         if exit_ in ("image", "hand_over"):
             c6_out = c6 and exit_ == "image"
-            want, got = _image(n, c6_out), _image(n, c6_out)
+            want, got = _image(n, c6_out), _image(n, c6_out, fill)
             _native.resblock(cur, *chain[-1], out=want, count=count)
             _native.tower(x, chain, _native.IMG_C6 if c6_out else _native.IMG_C8, out=got, count=count, fmt_x=fmt, fmt_y=fmt)
             assert int(want[0][:m].view(torch.int16).ne(0).sum()) > 0, tag + (exit_,)
@@ -84,14 +85,15 @@ def _check(tag, x, blocks, last_for, c6, heads, n, m, exits):
             if exit_ == "pairs":
                 hi = r.to(torch.float16)
                 want = (hi, (r - hi.float()).to(torch.float16))
-                got = tuple(torch.zeros((n, 90, 128), dtype=torch.float16, device="cuda") for _ in range(2))
+                got = tuple(_filled((n, 90, 128), torch.float16, fill) for _ in range(2))
                 _native.tower(x, chain, _native.IMG_PAIR, out=got, count=count, fmt_x=fmt, fmt_y=fmt)
             else:
                 want = _heads_of(r, hw, hb, npol)
-                got = tuple(torch.zeros((n, k * 90), dtype=torch.float32, device="cuda") for k in (npol, 6 - npol))
+                got = tuple(_filled((n, k * 90), torch.float32, fill) for k in (npol, 6 - npol))
                 _native.tower(x, chain, _native.EXIT_HEADS, heads=(hw, hb, npol) + got, count=count, fmt_x=fmt, fmt_y=fmt)
                 assert not torch.isnan(got[0][:m]).any() and not torch.isnan(got[1][:m]).any(), tag + (exit_,)
         assert _eq(want, got, m), tag + (exit_,)
+        assert _tail_kept(got, m, fill), tag + (exit_,)
 
 
 @pytest.mark.parametrize("nb", [1, 2, 6])
