@@ -13,6 +13,9 @@ COUNTER_NAMES = ["sims", "expansions", "terminal_sims", "repetition_sims", "park
                  # MCTS solver (set_solver): descents that ended on a proven node, nodes that became WIN or LOSS, plies whose
                  # remaining simulations a decided root cut
                  "proven_sims", "proofs", "decided_plies",
+                 # stop rules (set_kld_gain, set_smart_pruning): plies each rule ended and the simulations of those plies
+                 # that were never started
+                 "kld_plies", "kld_sims_cut", "lead_plies", "lead_sims_cut",
                  # only in the CZ_SIM_PROFILE tuning build (the library reports how many counters it has)
                  "cyc_select", "cyc_rules", "cyc_hash", "cyc_expand", "cyc_rep", "cyc_attach", "cyc_resume_load",
                  "cyc_kernel_select", "cyc_kernel_backup"]
@@ -26,6 +29,7 @@ MOVE_FAST = 0x8000       # finished-game record, moves[i] bit 15: ply i was a fa
 VISIT_FAST = 2           # visit entry flag: the ply was a fast search
 VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (cz_search_set_forced_playouts)
 VISIT_GUMBEL = 8         # visit entry flag: n holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
+VISIT_EARLY = 16         # visit entry flag: a stop rule ended the ply before its budget (cz_search_set_kld_gain)
 GUMBEL_MAX_M = 128       # include/czero.h CZ_GUMBEL_MAX_M
 EVAL_CACHE_STRIDE = 576  # include/czero.h CZ_EVAL_CACHE_STRIDE: bytes per entry of the evaluation cache
 PROOF_OPEN, PROOF_WIN, PROOF_LOSS = 0, 1, 2   # include/czero.h CZ_PROOF_*: a position's status from its mover's view
@@ -46,8 +50,9 @@ def check_eval_cache_log2(log2_entries, what="eval_cache"):
 # (record_values; None with the value record off and where the ring held NaN, "no value"); s, the policy surprise of the
 # ply, KL(recorded counts || priors without noise) (record_surprise; None with that record off and for NaN); gumbel, whether
 # the ply was a Gumbel root search (set_gumbel): n then holds the policy target scaled to 65536, raw_total as for pruned.
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel",
-                        defaults=(None, None, False))
+# early, whether a stop rule (set_kld_gain, set_smart_pruning) ended the ply before its budget.
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel early",
+                        defaults=(None, None, False, False))
 
 
 class SearchCfg(C.Structure):
@@ -126,6 +131,9 @@ def declare(L):
         "cz_search_set_solver": [vp, i32, vp],
         "cz_search_node_proof": [vp, vp, i32, vp, vp, vp, vp, vp],
         "cz_search_root_decided": [vp, vp, vp],
+        "cz_search_set_kld_gain": [vp, d, i32, vp],
+        "cz_search_set_smart_pruning": [vp, i32, vp],
+        "cz_search_root_kld": [vp, vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -233,6 +241,8 @@ class Search:
         self.gumbel_full = False               # set_gumbel_full(): the Gumbel rule below the root and v_mix in the target
         self.eval_cache = 0                    # set_eval_cache(): log2 of the evaluation cache's entries, 0 = off
         self.solver = False                    # set_solver(): forced wins and losses are proven in the tree
+        self.kld_gain, self.kld_interval = 0.0, 100   # set_kld_gain(): a ply ends once its root distribution stops moving
+        self.smart_pruning = False             # set_smart_pruning(): a tau = 0 ply ends once its leader cannot be caught
 
     # -- lifetime --
     def close(self):
@@ -441,6 +451,40 @@ class Search:
                       "cz_search_root_decided")
         return out.cpu().numpy()
 
+    def set_kld_gain(self, gain=0.0, interval=100):
+        """KLD-gain stop (cz_search_set_kld_gain; include/czero.h has the rule): every `interval` new root visits the root's
+        visit distribution is compared with the one of the ply's previous checkpoint, and the ply ends when the information
+        gained per simulation falls below `gain`.  gain 0 switches it off.  Refused while the Gumbel root search, the solver
+        or the evaluation cache are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph
+        capture."""
+        if not hasattr(self.L, "cz_search_set_kld_gain"):
+            raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_kld_gain)")
+        _native.check(self.L.cz_search_set_kld_gain(self.h, float(gain), int(interval), self._stream()),
+                      "cz_search_set_kld_gain")
+        self.kld_gain, self.kld_interval = float(gain), int(interval)
+
+    def set_smart_pruning(self, on=True):
+        """Unreachable-lead stop (cz_search_set_smart_pruning; include/czero.h has the rule): a ply whose move is chosen with
+        tau = 0 ends once its most visited non-banned root move leads the second by more than the simulations not yet
+        started -- they could not change the move.  Refused while the Gumbel root search, the solver or the evaluation
+        cache are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
+        if not hasattr(self.L, "cz_search_set_smart_pruning"):
+            raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_smart_pruning)")
+        _native.check(self.L.cz_search_set_smart_pruning(self.h, 1 if on else 0, self._stream()),
+                      "cz_search_set_smart_pruning")
+        self.smart_pruning = bool(on)
+
+    def root_kld(self):
+        """dict(gain float64 [G], checks int32 [G]) of each game's current ply (cz_search_root_kld): the last measured
+        information gain per simulation (NaN: none yet, or both rules off) and the number of checkpoints, the one that took
+        the first snapshot included."""
+        import torch
+        gain = torch.empty((self.G,), dtype=torch.float64, device=self.device)
+        checks = torch.empty((self.G,), dtype=torch.int32, device=self.device)
+        _native.check(self.L.cz_search_root_kld(self.h, C.c_void_p(gain.data_ptr()), C.c_void_p(checks.data_ptr()),
+                                                self._stream()), "cz_search_root_kld")
+        return dict(gain=gain.cpu().numpy(), checks=checks.cpu().numpy())
+
     def clear_eval_cache(self):
         """Empty the evaluation cache and zero its numbers (cz_search_eval_cache_clear); nothing to do while it is off."""
         if self.eval_cache:
@@ -604,7 +648,7 @@ class Search:
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
                           pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp,
-                          gumbel=bool(a[7] & VISIT_GUMBEL))
+                          gumbel=bool(a[7] & VISIT_GUMBEL), early=bool(a[7] & VISIT_EARLY))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane

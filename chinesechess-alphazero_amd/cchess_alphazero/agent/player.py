@@ -40,7 +40,7 @@ class VisitState:
 
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
-                 debugging=False, uci=False, use_history=False, side=0, solver=None):
+                 debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -87,6 +87,14 @@ class CChessPlayer:
         self.proof = (0, 0)
         if self.solver:
             self._search.set_solver(True)
+        # unreachable-lead stop (cz_search_set_smart_pruning): None = config.engine.smart_pruning, off by default.  A search
+        # with a simulation budget whose move is the most visited one ends once the leader cannot be caught.
+        self.smart_pruning = bool(getattr(getattr(config, "engine", None), "smart_pruning", False)
+                                  if smart_pruning is None else smart_pruning)
+        if self.smart_pruning and self.solver:
+            raise ValueError("smart_pruning excludes solver: each defines its own root rule")
+        if self.smart_pruning:
+            self._search.set_smart_pruning(True)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes):

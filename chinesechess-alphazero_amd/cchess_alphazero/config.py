@@ -116,6 +116,11 @@ class EngineConfig(_Section):
                                                   # below the root too, v_mix in the recorded pi (cz_search_set_gumbel_full)
                          solver=False,            # MCTS solver (run.py self / eval --solver, UCI option Solver): forced wins and
                                                   # losses are proven in the search tree (cz_search_set_solver)
+                         kld_gain=0.0,            # KLD-gain stop (run.py self --kld-gain G): a ply ends once the information its
+                         kld_interval=100,        # root visit distribution gains per simulation, measured every kld_interval
+                                                  # root visits, falls below G; 0 = off (cz_search_set_kld_gain)
+                         smart_pruning=False,     # unreachable-lead stop (run.py eval --smart-pruning, UCI option SmartPruning): a
+                                                  # tau = 0 ply ends once the leader cannot be caught (cz_search_set_smart_pruning)
                          eval_cache=0,            # cross-game evaluation cache (run.py self --eval-cache LOG2): a table of
                                                   # 2**LOG2 network results keyed by position, kept across games; a new leaf
                                                   # it holds takes no queue row; same search bit for bit; 576 B per entry;

@@ -43,7 +43,8 @@ class SelfPlayEngine:
                  max_nodes_per_game=0, pool_chunks=0, max_depth=0, sims_per_round=None, evaluator=None,
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
-                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None):
+                 gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
+                 kld_gain=None, kld_interval=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -81,12 +82,27 @@ class SelfPlayEngine:
         solver: the MCTS solver (None = config.engine.solver; excludes gumbel, forced_playouts and eval_cache): forced wins
         and losses are proven in the tree from the king captures the search meets, proven positions end a descent without a
         network row, a decided root starts no further simulation and a won root plays the winning move
-        (cz_search_set_solver).  The records are what the tree holds: no target is rewritten."""
+        (cz_search_set_solver).  The records are what the tree holds: no target is rewritten.
+        kld_gain, kld_interval: the KLD-gain stop (None = config.engine.kld_gain / kld_interval; kld_gain 0 = off; excludes
+        gumbel, solver and eval_cache): every kld_interval new root visits the root's visit distribution is compared with
+        the previous checkpoint's, and the ply ends when the information gained per simulation falls below kld_gain
+        (cz_search_set_kld_gain).  A ply that ended early is marked in its visit entry; the records are unchanged."""
+        ec_ = getattr(config, "engine", None)
+        self.kld_gain = float(getattr(ec_, "kld_gain", 0.0) if kld_gain is None else kld_gain)
+        self.kld_interval = int(getattr(ec_, "kld_interval", 100) if kld_interval is None else kld_interval)
+        if not (0.0 <= self.kld_gain < float("inf")):
+            raise ValueError(f"kld_gain {self.kld_gain}: expected a finite G >= 0")
+        if self.kld_interval < 1:
+            raise ValueError(f"kld_interval {self.kld_interval}: expected N >= 1")
         self.solver = bool(getattr(getattr(config, "engine", None), "solver", False) if solver is None else solver)
         self.eval_cache = check_eval_cache_log2(getattr(getattr(config, "engine", None), "eval_cache", 0)
                                                 if eval_cache is None else eval_cache)
         if self.solver and self.eval_cache:
             raise ValueError("solver excludes eval_cache: the cache has a kernel instantiation of its own")
+        if self.kld_gain and self.eval_cache:
+            raise ValueError("kld_gain excludes eval_cache: the cache has a kernel instantiation of its own")
+        if self.kld_gain and self.solver:
+            raise ValueError("kld_gain excludes solver: each defines its own root rule")
         if self.eval_cache and use_history:
             raise ValueError("eval_cache excludes use_history: the second block of the 28-plane input depends on the "
                              "simulation's path and the game history, so the network input is not a function of the position")
@@ -190,6 +206,10 @@ class SelfPlayEngine:
             raise ValueError("solver excludes gumbel and forced_playouts: each defines its own root rule")
         if self.solver:                                        # likewise
             self.search.set_solver(True)
+        if self.kld_gain and self.gumbel:
+            raise ValueError("kld_gain excludes gumbel: each defines its own root rule")
+        if self.kld_gain:                                      # likewise
+            self.search.set_kld_gain(self.kld_gain, self.kld_interval)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py

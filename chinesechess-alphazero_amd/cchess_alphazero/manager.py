@@ -89,6 +89,17 @@ _FLAGS = [
                       help="(self, eval) MCTS solver: a position whose every move allows the king's capture is proven lost "
                            "and the move that leads to it wins; proven positions end a simulation without a network "
                            "evaluation, a decided root is not searched further and a won root plays the winning move")),
+    ("--kld-gain", dict(type=float, default=0.0, metavar="G",
+                        help="(self) KLD-gain stop: every --kld-interval new root visits the root's visit distribution is "
+                             "compared with the previous checkpoint's, and the ply's search ends when the information gained "
+                             "per simulation falls below G: quiet positions get short searches (0 = off; lc0's training "
+                             "games use values around 1e-5 .. 1e-4)")),
+    ("--kld-interval", dict(type=int, default=100, metavar="N",
+                            help="(self, with --kld-gain) root visits between two checkpoints")),
+    ("--smart-pruning", dict(action="store_true",
+                             help="(eval) unreachable-lead stop: a ply whose move is the most visited one ends once that move "
+                                  "leads the second by more than the simulations not yet started; the move is the one the "
+                                  "full search would have played from the same tree")),
     ("--sims", dict(type=int, default=None, metavar="N",
                     help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
@@ -200,6 +211,23 @@ def build_config(args):
     if args.solver and args.eval_cache:
         raise SystemExit("--solver excludes --eval-cache: the cache has a kernel instantiation of its own")
     engine.solver = bool(args.solver)
+    if not 0.0 <= args.kld_gain < float("inf"):             # (false for NaN too)
+        raise SystemExit(f"--kld-gain {args.kld_gain}: expected a finite G >= 0")
+    if args.kld_interval < 1:
+        raise SystemExit(f"--kld-interval {args.kld_interval}: expected N >= 1")
+    if args.kld_gain and args.cmd != "self":
+        raise SystemExit("--kld-gain is an option of `run.py self`")
+    if args.smart_pruning and args.cmd != "eval":
+        raise SystemExit("--smart-pruning is an option of `run.py eval`")
+    for flag, on in (("--kld-gain", bool(args.kld_gain)), ("--smart-pruning", bool(args.smart_pruning))):
+        if on and args.gumbel:
+            raise SystemExit(f"{flag} excludes --gumbel: each defines its own root rule")
+        if on and args.solver:
+            raise SystemExit(f"{flag} excludes --solver: each defines its own root rule")
+        if on and args.eval_cache:
+            raise SystemExit(f"{flag} excludes --eval-cache: the cache has a kernel instantiation of its own")
+    engine.kld_gain, engine.kld_interval = args.kld_gain, args.kld_interval
+    engine.smart_pruning = bool(args.smart_pruning)
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

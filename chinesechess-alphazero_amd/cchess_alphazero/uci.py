@@ -23,7 +23,8 @@ logger = getLogger(__name__)
 ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference), MI355X-native engine",
              "id version 2.4", "option name gpu spin default 0 min 0 max 7",
              "option name Threads spin default 10 min 0 max 1024",
-             "option name Solver type check default false")
+             "option name Solver type check default false",
+             "option name SmartPruning type check default false")
 
 
 class UCI:
@@ -97,6 +98,8 @@ class UCI:
                 self.config.play.search_threads = int(args[3])
             elif args[1] == "Solver":                     # MCTS solver (cz_search_set_solver): the next `go` searches with it
                 self.config.engine.solver = args[3].lower() == "true"
+            elif args[1] == "SmartPruning":               # unreachable-lead stop (cz_search_set_smart_pruning): likewise, for
+                self.config.engine.smart_pruning = args[3].lower() == "true"   # `go` commands with a simulation budget
 
     def cmd_position(self, args):
         if not self.is_ready:

@@ -99,6 +99,8 @@ class EvaluateWorker:
         self.leaf_mirror = float(getattr(getattr(config, "engine", None), "leaf_mirror", 0.0) or 0.0)
         # MCTS solver of both models' searches (run.py eval --solver, cz_search_set_solver)
         self.solver = bool(getattr(getattr(config, "engine", None), "solver", False))
+        # unreachable-lead stop of both models' searches (run.py eval --smart-pruning, cz_search_set_smart_pruning)
+        self.smart_pruning = bool(getattr(getattr(config, "engine", None), "smart_pruning", False))
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -165,6 +167,9 @@ class EvaluateWorker:
         if self.solver:                                        # (likewise)
             for s in searches:
                 s.set_solver(True)
+        if self.smart_pruning:                                 # (likewise)
+            for s in searches:
+                s.set_smart_pruning(True)
 
         def counters_now():
             c = [s.counters() for s in searches]

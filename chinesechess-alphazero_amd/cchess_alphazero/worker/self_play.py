@@ -116,6 +116,10 @@ class SelfPlayWorker:
         if getattr(self.engine, "solver", False):              # (config.engine.solver, likewise)
             logger.info(f"Process {self.pid}-{self.rank}: MCTS solver: forced wins and losses are proven in the tree; a "
                         f"decided root is not searched further, a won root plays the winning move")
+        if getattr(self.engine, "kld_gain", 0.0):              # (config.engine.kld_gain, likewise)
+            logger.info(f"Process {self.pid}-{self.rank}: KLD-gain stop: a ply's search ends once its root visit "
+                        f"distribution gains less than {self.engine.kld_gain:g} per simulation, measured every "
+                        f"{self.engine.kld_interval} root visits")
         if getattr(self.engine, "eval_cache", 0):              # (config.engine.eval_cache, likewise)
             logger.info(f"Process {self.pid}-{self.rank}: evaluation cache: 2^{self.engine.eval_cache} entries, "
                         f"{self.engine.search.memory_info()['eval_cache_bytes'] >> 20} MiB, kept across games")
@@ -158,6 +162,14 @@ class SelfPlayWorker:
         if self.engine.forced_playouts and raw:
             logger.info(f"Process {self.pid}-{self.rank}: policy target pruning removed {pruned} of {raw} root visits "
                         f"({100.0 * pruned / raw:.1f} %)")
+
+    def _stop_report(self, lc):
+        """The KLD-gain stop's numbers for the counter line: the share of plies it ended and the mean simulations per ply."""
+        if not getattr(self.engine, "kld_gain", 0.0):
+            return ""
+        plies = max(lc.get("plies", 0), 1)
+        return (f" kld_gain: plies_cut={lc.get('kld_plies', 0)} ({100.0 * lc.get('kld_plies', 0) / plies:.1f} %) "
+                f"sims/ply={lc.get('sims', 0) / plies:.1f}")
 
     def _eval_cache_report(self):
         """The evaluation cache's numbers for the counter line (since the table was last emptied: a reload empties it)."""
@@ -229,7 +241,7 @@ class SelfPlayWorker:
                                 f"tree_resets={lc['tree_resets']} overflow_sims={lc['overflow_sims']} "
                                 f"no_act_truncated={lc.get('no_act_truncated', 0)}"
                                 + (f" visits_dropped={lc['visits_dropped']}" if "visits_dropped" in lc else "")
-                                + self._eval_cache_report())
+                                + self._stop_report(lc) + self._eval_cache_report())
                 if max_games is not None and c["games"] >= max_games:
                     break
             if max_rounds is not None and r >= max_rounds:

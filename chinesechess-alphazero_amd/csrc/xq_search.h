@@ -73,12 +73,24 @@ enum Counter : int {
     CT_PROVEN_SIMS,         // MCTS solver: descents that ended on a proven node (worth +-2, no network row)
     CT_PROOFS,              // MCTS solver: nodes that became WIN or LOSS
     CT_DECIDED_PLIES,       // MCTS solver: plies whose remaining simulations a decided root cut
+    CT_KLD_PLIES,           // KLD-gain stop (cz_search_set_kld_gain): plies it ended
+    CT_KLD_SIMS_CUT,        // ... and the simulations of those plies that were never started
+    CT_LEAD_PLIES,          // unreachable-lead stop (cz_search_set_smart_pruning): plies it ended
+    CT_LEAD_SIMS_CUT,       // ... and the simulations of those plies that were never started
 #ifdef CZ_SIM_PROFILE       // tuning build (tools/ab_search.sh): shader-clock cycles of wave time per section of a simulation
     CT_CYC_SELECT, CT_CYC_RULES, CT_CYC_HASH, CT_CYC_EXPAND, CT_CYC_REP, CT_CYC_ATTACH, CT_CYC_RESUME_LOAD,
     CT_CYC_KERNEL_SELECT, CT_CYC_KERNEL_BACKUP,
 #endif
     CT_COUNT
 };
+// Counters a running kernel accumulates in LDS (SearchLDS.ctr; counters_begin / counters_flush walk them).  The stop rules'
+// four count at most once per ply and go straight to the game's global block (count_direct), so the LDS layout -- and with
+// it the text of every kernel that existed before them -- stays what it was.  The tuning build keeps everything in LDS.
+#ifdef CZ_SIM_PROFILE
+constexpr int CT_LDS_COUNT = CT_COUNT;
+#else
+constexpr int CT_LDS_COUNT = CT_KLD_PLIES;
+#endif
 
 struct SearchParams {
     // sizes
@@ -221,6 +233,7 @@ constexpr uint32_t VISIT_RESIGN = 1u;              // entry flag: the player res
 constexpr uint32_t VISIT_FAST = 2u;                // entry flag: the ply was a fast search (cz_search_set_playout_cap)
 constexpr uint32_t VISIT_PRUNED = 4u;              // entry flag: n[] holds the PRUNED counts (cz_search_set_forced_playouts)
 constexpr uint32_t VISIT_GUMBEL = 8u;              // entry flag: n[] holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
+constexpr uint32_t VISIT_EARLY = 16u;              // entry flag: a stop rule ended the ply before its budget (cz_search_set_kld_gain, _smart_pruning)
 struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
     uint32_t game_id;
     uint16_t ply;       // turns when the move was chosen
@@ -243,6 +256,21 @@ struct VisitRing {
     double* q;                      // [cap]; NULL = off
     // surprise record (cz_search_record_surprise): KL(recorded counts || noise-free priors) of the same entry, likewise
     double* s;                      // [cap]; NULL = off
+};
+
+// ---- early stop of a settled ply (cz_search_set_kld_gain, cz_search_set_smart_pruning; csrc/xq_search_stop.h) ----
+// The rules' parameters and their per-game state, allocated only while a rule is on.  Like the visit ring it reaches the
+// kernels that use it (k_sim_stop, k_advance_stop, k_stop_reset) as an argument of its own.
+struct StopState {
+    double gain;            // G of the KLD-gain rule, 0 = that rule is off
+    int interval;           // I: new root visits between two checkpoints
+    int lead;               // 1 = the unreachable-lead rule is on
+    int32_t* prev_n;        // [G][128] m_j: the root's visit counts at the ply's last checkpoint, in edge order
+    int32_t* prev_sum;      // [G] M, their sum; -1 = the snapshot is empty
+    int32_t* start_tasks;   // [G] g_tasks_left at the ply's first test point; -1 = the ply has not reached one yet
+    double* last_gain;      // [G] the last measured g of the ply, NaN = none
+    int32_t* checks;        // [G] checkpoints of the ply, the one that took the first snapshot included
+    uint8_t* cut;           // [G] the rule that ended the ply: 0 none, 1 KLD gain, 2 unreachable lead
 };
 
 }  // namespace xq

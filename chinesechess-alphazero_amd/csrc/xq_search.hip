@@ -31,7 +31,9 @@
 //   xq_search_records.h   RootEdges, gumbel_choose, gumbel_targets, prune_targets, root_value, root_surprise, emit_visits
 //   xq_search_ply.h       the chunk pool, reserve_ply, ply_is_fast, begin_search, choose_action, new_game, the book, emit_record
 //   xq_search_selfplay.h  advance_game
-//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve, k_cache_fill, k_advance, k_noise
+//   xq_search_stop.h      the early stop of a settled ply: stop_reset, ply_settled
+//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop, k_cache_fill, k_advance, k_advance_stop,
+//                         k_stop_reset, k_noise
 //   xq_search_aux.h       every other kernel (k_start_selfplay .. k_debug_sqrt) and walk_path
 // This file keeps the includes and the host side: the opaque search object and the C-ABI entry points.
 #include <hip/hip_runtime.h>
@@ -59,6 +61,7 @@ extern "C" void czi_set_error(const char* msg);   // xq_kernels.hip
 #include "xq_search_records.h"
 #include "xq_search_ply.h"
 #include "xq_search_selfplay.h"
+#include "xq_search_stop.h"
 #include "xq_search_round.h"
 #include "xq_search_aux.h"
 
@@ -78,6 +81,9 @@ struct cz_search {
     EvalCache C{};                    // evaluation cache (cz_search_set_eval_cache); C.tab NULL = off
     void* ec_mem = nullptr;           // its bookkeeping (s_cval, stamp, counters), allocated only while the cache is on
     size_t ec_ctr_bytes = 0;          // the counters at its start: what cz_search_eval_cache_clear zeroes
+    StopState S{};                    // early stop of a settled ply (cz_search_set_kld_gain, cz_search_set_smart_pruning)
+    void* stop_mem = nullptr;         // its per-game state, allocated only while a rule is on; S.prev_sum NULL = both off
+    size_t stop_bytes = 0;
 };
 
 namespace {
@@ -302,6 +308,7 @@ int cz_search_destroy(cz_search* s)
     (void)hipFree(s->book_mem);
     (void)hipFree(s->C.tab);
     (void)hipFree(s->ec_mem);
+    (void)hipFree(s->stop_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
     delete s;
@@ -311,7 +318,8 @@ int cz_search_destroy(cz_search* s)
 size_t cz_search_bytes(const cz_search* s)
 {
     if (!s) return 0;
-    return s->bytes + (s->C.tab ? (size_t)ec_table_bytes(s->C.log2) : 0);     // (the evaluation cache's table, while it is on)
+    return s->bytes + (s->C.tab ? (size_t)ec_table_bytes(s->C.log2) : 0)      // (the evaluation cache's table, while it is on)
+           + s->stop_bytes;                                                    // (the stop rules' state, while one is on)
 }
 
 int cz_search_info(const cz_search* s, int32_t* out)
@@ -383,6 +391,9 @@ int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id
     if (e != hipSuccess) return serr_hip("cz_search_start_selfplay", e);
     hipLaunchKernelGGL(k_pool_commit, dim3(1), dim3(1), 0, (hipStream_t)stream, s->B);
     hipLaunchKernelGGL(k_start_selfplay, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, first_game_id);
+    if (s->stop_mem)                                  // every game's first search begins: empty snapshots
+        hipLaunchKernelGGL(k_stop_reset, dim3((s->P.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->S, s->P.G,
+                           (const uint8_t*)nullptr);
     S_LAUNCH_CHECK("cz_search_start_selfplay");
     return CZ_OK;
 }
@@ -396,6 +407,9 @@ int cz_search_set_roots(cz_search* s, const int8_t* boards, const int32_t* turns
     hipLaunchKernelGGL(k_pool_commit, dim3(1), dim3(1), 0, (hipStream_t)stream, s->B);
     hipLaunchKernelGGL(k_set_roots, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, boards, turns, no_act,
                        n_no_act, increase_temp, enable_resign, select_mask, prev_boards, hist_kind);
+    if (s->stop_mem)                                  // the selected games' searches begin: empty snapshots
+        hipLaunchKernelGGL(k_stop_reset, dim3((s->P.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->S, s->P.G,
+                           select_mask);
     S_LAUNCH_CHECK("cz_search_set_roots");
     return CZ_OK;
 }
@@ -415,8 +429,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool gum = s->P.gumbel_m > 0;
     const bool cache = s->C.tab != nullptr;
     const bool solve = s->P.solver != 0;                        // (never with gum or cache: cz_search_set_solver)
+    const bool stop = s->stop_mem != nullptr;                   // (never with gum, cache or solve: cz_search_set_kld_gain)
     auto sim = [&](int mask, int cq) {
-        if (solve) {
+        if (stop) {
+            if (hist) hipLaunchKernelGGL((k_sim_stop<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
+            else hipLaunchKernelGGL((k_sim_stop<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
+        } else if (solve) {
             if (hist) hipLaunchKernelGGL((k_sim_solve<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
             else hipLaunchKernelGGL((k_sim_solve<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         } else if (cache) {         // (14 planes: cz_search_set_eval_cache refuses the history input)
@@ -434,7 +452,8 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     if (cache)
         hipLaunchKernelGGL(k_cache_fill, dim3(s->P.G * s->P.K), block, 0, st, s->P, s->B, s->C, policy, value, consume_compact);
     sim(SIM_BACKUP, consume_compact);
-    if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
+    if (stop) hipLaunchKernelGGL(k_advance_stop, grid, block, 0, st, s->P, s->B, s->V, s->S);
+    else if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
@@ -538,6 +557,10 @@ int cz_search_set_eval_cache(cz_search* s, int log2_entries, void* stream)
                                 "function of the position");
     if (log2_entries != 0 && s->P.solver)
         return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the MCTS solver is on (cz_search_set_solver)");
+    if (log2_entries != 0 && s->S.gain > 0.0)
+        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the KLD-gain stop is on (cz_search_set_kld_gain)");
+    if (log2_entries != 0 && s->S.lead)
+        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipStreamSynchronize(st);             // no launch that holds the old table is still running
     if (e != hipSuccess) return serr_hip("cz_search_set_eval_cache", e);
@@ -777,6 +800,10 @@ int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, vo
         return serr(CZ_ERR_ARG, "cz_search_set_gumbel: forced playouts or the playout cap are on, each defines its own root rule");
     if (m > 0 && s->P.solver)
         return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the MCTS solver is on (cz_search_set_solver)");
+    if (m > 0 && s->S.gain > 0.0)
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the KLD-gain stop is on (cz_search_set_kld_gain)");
+    if (m > 0 && s->S.lead)
+        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_gumbel", e);
     s->P.gumbel_m = m;
@@ -800,6 +827,10 @@ int cz_search_set_solver(cz_search* s, int on, void* stream)
         return serr(CZ_ERR_ARG, "cz_search_set_solver: forced playouts are on (cz_search_set_forced_playouts)");
     if (on && s->C.tab)
         return serr(CZ_ERR_ARG, "cz_search_set_solver: the evaluation cache is on (cz_search_set_eval_cache)");
+    if (on && s->S.gain > 0.0)
+        return serr(CZ_ERR_ARG, "cz_search_set_solver: the KLD-gain stop is on (cz_search_set_kld_gain)");
+    if (on && s->S.lead)
+        return serr(CZ_ERR_ARG, "cz_search_set_solver: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
     if (e != hipSuccess) return serr_hip("cz_search_set_solver", e);
     s->P.solver = on;
@@ -823,6 +854,121 @@ int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream)
     hipLaunchKernelGGL(k_root_decided, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, out);
     S_LAUNCH_CHECK("cz_search_root_decided");
     return CZ_OK;
+}
+
+// ---- early stop of a settled ply (include/czero.h) ----------------------------------------------------------------------
+static_assert(CZ_VISIT_EARLY == VISIT_EARLY, "czero.h: stop rules");
+
+// The per-game state exists exactly while a rule is on (s->S.gain > 0 or s->S.lead); the stream is idle when this runs.
+static int stop_state_update(cz_search* s, hipStream_t st, const char* what)
+{
+    const bool want = s->S.gain > 0.0 || s->S.lead != 0;
+    if (want == (s->stop_mem != nullptr)) return CZ_OK;
+    if (!want) {
+        (void)hipFree(s->stop_mem);
+        s->stop_mem = nullptr;
+        s->stop_bytes = 0;
+        s->S.prev_n = nullptr; s->S.prev_sum = nullptr; s->S.start_tasks = nullptr; s->S.last_gain = nullptr;
+        s->S.checks = nullptr; s->S.cut = nullptr;
+        return CZ_OK;
+    }
+    const size_t G = (size_t)s->P.G;
+    const size_t off_gain = 0, off_prev = off_gain + align_up(8 * G), off_sum = off_prev + align_up(4 * G * MAXMOVES),
+                 off_start = off_sum + align_up(4 * G), off_checks = off_start + align_up(4 * G),
+                 off_cut = off_checks + align_up(4 * G), bytes = off_cut + align_up(G);
+    void* mem = nullptr;
+    hipError_t e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return serr_hip(what, e);
+    e = hipMemsetAsync(mem, 0, bytes, st);
+    if (e != hipSuccess) { (void)hipFree(mem); return serr_hip(what, e); }
+    char* m = (char*)mem;
+    s->S.last_gain = (double*)(m + off_gain);
+    s->S.prev_n = (int32_t*)(m + off_prev);
+    s->S.prev_sum = (int32_t*)(m + off_sum);
+    s->S.start_tasks = (int32_t*)(m + off_start);
+    s->S.checks = (int32_t*)(m + off_checks);
+    s->S.cut = (uint8_t*)(m + off_cut);
+    // searches under way count as begun now: empty snapshots, the first test point they reach starts their count
+    hipLaunchKernelGGL(k_stop_reset, dim3((s->P.G + 255) / 256), dim3(256), 0, st, s->S, s->P.G, (const uint8_t*)nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(mem);
+        s->S.prev_n = nullptr; s->S.prev_sum = nullptr; s->S.start_tasks = nullptr; s->S.last_gain = nullptr;
+        s->S.checks = nullptr; s->S.cut = nullptr;
+        return serr_hip(what, e);
+    }
+    s->stop_mem = mem;
+    s->stop_bytes = bytes;
+    return CZ_OK;
+}
+
+// what a stop rule excludes, named for `who`; nullptr = nothing in the way
+static const char* stop_excluded(const cz_search* s)
+{
+    if (s->P.gumbel_m > 0) return "the Gumbel root search is on (cz_search_set_gumbel)";
+    if (s->P.solver) return "the MCTS solver is on (cz_search_set_solver)";
+    if (s->C.tab) return "the evaluation cache is on (cz_search_set_eval_cache)";
+    return nullptr;
+}
+
+int cz_search_set_kld_gain(cz_search* s, double gain, int interval, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: null handle");
+    if (!finite_nonneg(gain)) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: gain negative or not finite");
+    if (interval < 1) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: interval < 1");
+    if (gain > 0.0) {
+        if (const char* why = stop_excluded(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "cz_search_set_kld_gain: %s", why);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    }
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_kld_gain", e);
+    const double old_gain = s->S.gain;
+    const int old_interval = s->S.interval;
+    s->S.gain = gain;
+    s->S.interval = interval;
+    const int rc = stop_state_update(s, (hipStream_t)stream, "cz_search_set_kld_gain");
+    if (rc != CZ_OK) { s->S.gain = old_gain; s->S.interval = old_interval; }
+    return rc;
+}
+
+int cz_search_set_smart_pruning(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_smart_pruning: null handle");
+    if (on != 0 && on != 1) return serr(CZ_ERR_ARG, "cz_search_set_smart_pruning: on is neither 0 nor 1");
+    if (on) {
+        if (const char* why = stop_excluded(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "cz_search_set_smart_pruning: %s", why);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    }
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_smart_pruning", e);
+    const int old = s->S.lead;
+    s->S.lead = on;
+    const int rc = stop_state_update(s, (hipStream_t)stream, "cz_search_set_smart_pruning");
+    if (rc != CZ_OK) s->S.lead = old;
+    return rc;
+}
+
+int cz_search_root_kld(cz_search* s, double* gain, int32_t* checks, void* stream)
+{
+    if (!s || !gain || !checks) return serr(CZ_ERR_ARG, "cz_search_root_kld: null argument");
+    const size_t G = (size_t)s->P.G;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (s->stop_mem) {
+        e = hipMemcpyAsync(gain, s->S.last_gain, sizeof(double) * G, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(checks, s->S.checks, sizeof(int32_t) * G, hipMemcpyDeviceToDevice, st);
+    } else {                                                    // both rules off: nothing measured (NaN), no checkpoint
+        e = hipMemsetAsync(gain, 0xFF, sizeof(double) * G, st);
+        if (e == hipSuccess) e = hipMemsetAsync(checks, 0, sizeof(int32_t) * G, st);
+    }
+    return e == hipSuccess ? CZ_OK : serr_hip("cz_search_root_kld", e);
 }
 
 int cz_search_set_gumbel_full(cz_search* s, int on, void* stream)

@@ -161,6 +161,17 @@ XQ_D void begin_search(const SearchParams& P, const SearchBuffers& B, const Game
     wave_sync_global();
 }
 
+// The temperature of the move choice at ply `turns` (player.py:453-461); inc: the ply's increase_temp.  Stated once:
+// choose_action applies it, and the unreachable-lead stop (xq_search_stop.h) asks whether it will be 0.
+XQ_D double ply_tau(const SearchParams& P, int turns, int inc)
+{
+    double tau = 0.0;
+    if (turns < 30 && P.tau_decay_rate != 0.0) tau = pow(P.tau_decay_rate, (double)(turns + 1));
+    if (tau < 0.1 || (turns >= 4 && P.evaluate)) tau = 0.0;
+    if (inc && !P.evaluate) tau = 0.5;
+    return tau;
+}
+
 // ---- calc_policy + apply_temperature + choice (player.py:375-406, 453-470, :195) ---------------------
 // returns the chosen label, or -1 when the player resigns.  u is the uniform draw of np.random.choice.
 // SOLVE (the MCTS solver is on, an instantiation of its own): at a WIN root with a non-banned winning edge the move is
@@ -229,11 +240,7 @@ XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const Game
     }
     wave_sync_global();
     // temperature (player.py:453-461)
-    const int inc = uni((int)B.g_increase_temp[g]);
-    double tau = 0.0;
-    if (turns < 30 && P.tau_decay_rate != 0.0) tau = pow(P.tau_decay_rate, (double)(turns + 1));
-    if (tau < 0.1 || (turns >= 4 && P.evaluate)) tau = 0.0;
-    if (inc && !P.evaluate) tau = 0.5;
+    const double tau = ply_tau(P, turns, uni((int)B.g_increase_temp[g]));
     int chosen = 0;
     if (tau == 0.0) {
         if (lane == 0) {

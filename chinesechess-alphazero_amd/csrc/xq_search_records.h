@@ -278,9 +278,10 @@ XQ_D double root_surprise(int nm, const uint16_t lab[2], const int m[2], const f
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
 // raw_total); the tree keeps the raw counts and choose_action has already used them.
 // FULL: a Gumbel ply's target is the full search's (gumbel_targets<true> with the root's stored value).
+// early: a stop rule ended the ply (VISIT_EARLY; only k_advance_stop ever passes true).
 template <bool FULL>
 XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameView& gv, const VisitRing& V, int turns,
-                      bool resigned, bool fast, bool prune, bool gumbel)
+                      bool resigned, bool fast, bool prune, bool gumbel, bool early = false)
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -328,7 +329,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
         h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u) |
-                               (gumbel ? VISIT_GUMBEL : 0u));
+                               (gumbel ? VISIT_GUMBEL : 0u) | (early ? VISIT_EARLY : 0u));
         h->sum_n = E.sum_n;
         h->raw_total = (uint32_t)raw_total;
     }

@@ -4,7 +4,8 @@
 // text only moves between these headers, and the proof of a move is the unit's device assembly, kernel by kernel
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
-// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve; k_cache_fill, k_advance, k_noise.
+// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop; k_cache_fill, k_advance,
+// k_advance_stop, k_stop_reset, k_noise.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
@@ -13,6 +14,7 @@
 #include "xq_search_sim.h"
 #include "xq_search_ply.h"
 #include "xq_search_selfplay.h"
+#include "xq_search_stop.h"
 #include "xq_noise.h"
 #include "xq_evalcache.h"
 
@@ -29,10 +31,13 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // CACHE: the evaluation cache (cz_search_set_eval_cache) is on; likewise, so that the kernels launched while it is off
 // are the text they were.  The body of both kernels: k_sim below (CACHE false, C never read) and k_sim_cached.
 // SOLVE: the MCTS solver (cz_search_set_solver) is on; likewise.  The body of k_sim_solve too.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false>
+// STOP: a stop rule (cz_search_set_kld_gain, cz_search_set_smart_pruning) is on; likewise.  The body of k_sim_stop too; S is
+// read by that instantiation alone.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
-                   int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C)
+                   int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C,
+                   const StopState& S = StopState{})
 {
     const int g = blockIdx.x;
     // first kernel of a round: chunks returned during the previous round become takeable (see pool_commit)
@@ -206,6 +211,16 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                     break;
                 }
             }
+            if constexpr (STOP) {
+                // a settled ply starts no further simulation either: the same test point, the rules of xq_search_stop.h
+                const int why = ply_settled(P, B, gv, S, tasks);
+                if (why != STOP_NONE) {
+                    if (lane_id() == 0) { B.g_tasks_left[g] = 0; S.cut[g] = (uint8_t)why; }
+                    count_direct(gv, why == STOP_KLD ? CT_KLD_PLIES : CT_LEAD_PLIES);
+                    count_direct(gv, why == STOP_KLD ? CT_KLD_SIMS_CUT : CT_LEAD_SIMS_CUT, (unsigned long long)tasks);
+                    break;
+                }
+            }
             // A batch whose simulations all end on terminal / repeated positions needs no evaluation and the next one
             // could start at once -- in a won endgame that chains hundreds of batches inside one launch and the whole
             // round waits for this wave.  The order of simulations does not depend on where the chain is cut.
@@ -274,6 +289,17 @@ __global__ __launch_bounds__(64, 4) void k_sim_solve(SearchParams P, SearchBuffe
 {
     __shared__ SearchLDS L;
     sim_body<HIST, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
+}
+
+// k_sim with a stop rule on (cz_search_set_kld_gain and cz_search_set_smart_pruning refuse the Gumbel search, the solver and the
+// evaluation cache)
+template <bool HIST>
+__global__ __launch_bounds__(64, 4) void k_sim_stop(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                                const float* __restrict__ value, void* planes, int mask, int compact,
+                                                int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, StopState S)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{}, S);
 }
 
 // The evaluation cache's only writer: the first launch of a round (before k_sim(BACKUP), which attaches the same rows),
@@ -358,6 +384,41 @@ __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B,
         B.g_phase[g] = PH_READY;
     }
     counters_flush(gv);
+}
+
+// k_advance with a stop rule on: the visit entry of a ply that a rule ended carries VISIT_EARLY, and every search that
+// advance_game begins starts with an empty snapshot (stop_reset).  External mode's searches begin in cz_search_set_roots, which
+// launches k_stop_reset.
+__global__ __launch_bounds__(64) void k_advance_stop(SearchParams P, SearchBuffers B, VisitRing V, StopState S)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_active[g]) != 0 || uni(B.g_tasks_left[g]) != 0) return;
+    const GameView gv = make_view(B, P, g, L.ctr, L.chtab);
+    counters_begin(gv);
+    if (P.mode == MODE_SELFPLAY) {
+        for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
+            advance_game<false, false, true>(P, B, gv, L, V, S);
+            stop_reset(S, g);
+            if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
+        }
+    } else if (lane_id() == 0) {
+        B.g_phase[g] = PH_READY;
+    }
+    counters_flush(gv);
+}
+
+// the searches of the games `select_mask` names (NULL: all) begin: cz_search_set_roots, cz_search_start_selfplay
+__global__ void k_stop_reset(StopState S, int G, const uint8_t* __restrict__ select_mask)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G || (select_mask && !select_mask[g])) return;
+    S.prev_sum[g] = -1;
+    S.start_tasks[g] = -1;
+    S.last_gain[g] = __builtin_nan("");
+    S.checks[g] = 0;
+    S.cut[g] = (uint8_t)STOP_NONE;
 }
 
 // Dirichlet(alpha 1_n)[0] for every (simulation slot, root edge) of the batch that the next k_sim(SELECT) launch starts:

@@ -13,9 +13,10 @@
 namespace {
 
 // One ply of SelfPlayWorker.start_game after the search finished (self_play.py:124-212).
-template <bool FULL, bool SOLVE = false>        // (emit_visits', choose_action's)
+// STOP (k_advance_stop, a stop rule is on): the visit entry of a ply that a rule ended says so (VISIT_EARLY, from S.cut).
+template <bool FULL, bool SOLVE = false, bool STOP = false>        // (emit_visits', choose_action's)
 XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
-                       const VisitRing& V)
+                       const VisitRing& V, const StopState& S = StopState{})
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -28,7 +29,9 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     const int action = choose_action<SOLVE>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);
-        emit_visits<FULL>(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0);
+        bool early = false;
+        if constexpr (STOP) early = uni((int)S.cut[g]) != 0;
+        emit_visits<FULL>(P, B, gv, V, turns, action < 0, fast, P.forced_k > 0.0 && !fast, P.gumbel_m > 0, early);
     }
     count(gv, CT_PLIES);
     bool game_over = false, resigned = false;

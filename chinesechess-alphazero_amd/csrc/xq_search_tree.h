@@ -28,7 +28,7 @@ struct SearchLDS {
     uint32_t key[KEY_WORDS + 4];
     int32_t path_node[MAXD_LDS];
     int32_t path_edge[MAXD_LDS];
-    unsigned long long ctr[CT_COUNT];  // counter accumulators of the running kernel
+    unsigned long long ctr[CT_LDS_COUNT];  // counter accumulators of the running kernel
     uint8_t codes[BOARD_LDS];          // plane codes of the leaf being encoded
     double dsc[MAXMOVES];              // sampling scratch
     double cdf[MAXMOVES];
@@ -110,6 +110,14 @@ XQ_D void count(const GameView& gv, int which, unsigned long long by = 1)
 {
     if (lane_id() == 0) gv.lctr[which] += by;
 }
+// a counter at or beyond CT_LDS_COUNT has no LDS accumulator: straight to the game's global block (lane 0 is its only writer)
+XQ_D void count_direct(const GameView& gv, int which, unsigned long long by = 1)
+{
+    if (lane_id() == 0) {
+        if (which < CT_LDS_COUNT) gv.lctr[which] += by;
+        else gv.ctr[which] += by;
+    }
+}
 XQ_D void count_max(const GameView& gv, int which, unsigned long long val)
 {
     if (lane_id() == 0 && gv.lctr[which] < val) gv.lctr[which] = val;
@@ -123,13 +131,13 @@ XQ_D void count_max(const GameView& gv, int which, unsigned long long val)
 #endif
 XQ_D void counters_begin(const GameView& gv)
 {
-    for (int i = lane_id(); i < CT_COUNT; i += 64) gv.lctr[i] = 0;
+    for (int i = lane_id(); i < CT_LDS_COUNT; i += 64) gv.lctr[i] = 0;
     wave_sync();
 }
 XQ_D void counters_flush(const GameView& gv)
 {
     wave_sync_global();
-    for (int i = lane_id(); i < CT_COUNT; i += 64) {
+    for (int i = lane_id(); i < CT_LDS_COUNT; i += 64) {
         const unsigned long long v = gv.lctr[i];
         if (v == 0) continue;
         if (i == CT_MAX_DEPTH) { if (gv.ctr[i] < v) gv.ctr[i] = v; }

@@ -432,8 +432,9 @@ typedef struct cz_visit_entry {
                                         fast search of the playout cap (cz_search_set_playout_cap); bit 2
                                         (CZ_VISIT_PRUNED): n[] holds the pruned policy targets, not the raw counts
                                         (cz_search_set_forced_playouts); bit 3 (CZ_VISIT_GUMBEL): n[] holds the Gumbel
-                                        policy target scaled to 65536 (cz_search_set_gumbel) */
-    int32_t sum_n;                   /* the root's own visit count */
+                                        policy target scaled to 65536 (cz_search_set_gumbel); bit 4 (CZ_VISIT_EARLY): a
+                                        stop rule ended the ply before its budget (cz_search_set_kld_gain) */
+    int32_t sum_n;                  /* the root's own visit count */
     uint32_t raw_total;              /* CZ_VISIT_PRUNED, CZ_VISIT_GUMBEL: sum of the RAW counts of the non-banned edges (S), so that
                                         raw_total - sum of the non-banned n[] = visits pruned; otherwise 0 (this word
                                         was `reserved`, always 0, before pruning existed) */
@@ -715,6 +716,52 @@ int cz_search_node_proof(cz_search* s, const uint16_t* path, int path_len, int8_
                          uint8_t* mark_dist, void* stream);
 /* out [G] uint8 DEVICE: 1 where the game's current root is decided, with the bans of the current ply. */
 int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream);
+/* ---- early stop of a settled ply (both rules off by default; the reference has no such option) ---------------------------
+ * run.py self --kld-gain G [--kld-interval I]; run.py eval --smart-pruning, the UCI option SmartPruning.  Two rules end a
+ * ply's search before its budget is spent.  With both off no kernel output, record or counter differs by a bit, and the
+ * kernels launched are the ones launched before the rules existed.
+ *
+ * TEST POINT.  Both rules are tested at one place only: before a new lock-step batch is started for a game.  There nothing
+ * is in flight for the game, the deferred values are flushed, and tasks, the simulations of the ply not yet started, is
+ * > 0.  A ply that a rule ends gets tasks = 0 and is counted.  Nothing else about the ply changes: move choice, records,
+ * reuse rule and noise stay as they are.
+ *
+ * KLD GAIN (cz_search_set_kld_gain; lc0's KldGainStopper), parameters gain G > 0 and interval I >= 1:
+ *   n_j        the visit count of root edge j, over ALL edges of the root in edge order (banned ones included); N = sum n_j.
+ *              Visits a reused root brings along count, as they do in the reference's budget (tasks = sims - done_n).
+ *   snapshot   (m_j, M) of an earlier checkpoint of the same ply; EMPTY when the ply's search begins (begin_search in
+ *              self-play, cz_search_set_roots in external mode).
+ *   nothing    happens at a test point while the snapshot is non-empty and N < M + I, or while it is empty and fewer than I
+ *              simulations of this ply have finished.
+ *   checkpoint otherwise.  With a non-empty snapshot, in float64:
+ *                  D = sum over j with m_j > 0 of (m_j / M) * log((m_j / M) / (n_j / N)),   g = D / (N - M)
+ *              (each quotient, the logarithm and the product rounded once; n_j >= m_j, so every term is finite).  If
+ *              g < G the ply ends.  Otherwise, or when the snapshot was empty, the snapshot becomes (n_j, N) and the search
+ *              goes on.  A ply therefore runs at least two intervals, rounded up to batches of K, before it can be cut.
+ *   The rule applies to every ply with a budget; fast plies of the playout cap are too short to reach a second checkpoint
+ *   at a sensible I.
+ * UNREACHABLE LEAD (cz_search_set_smart_pruning): on a ply whose move will be chosen with tau = 0 -- tau as cz_search_choose
+ *   and self-play compute it from turns, tau_decay_rate, evaluate and increase_temp -- let a and b be the largest and the
+ *   second-largest n_j over the non-banned root edges (0 where there is no such edge).  The ply ends when a - b > tasks: the
+ *   simulations not yet started cannot change the arg-max.  Plies with tau > 0 are never cut.
+ * With both on, the KLD gain is tested (and its checkpoint taken) first.
+ * COUNTERS, appended to cz_search_counters: kld_plies, kld_sims_cut (tasks when the rule fired, summed), lead_plies,
+ * lead_sims_cut.  RECORD: the visit entry of a ply that a rule ended carries CZ_VISIT_EARLY; its layout is unchanged.
+ *
+ * WHERE IT LIVES.  Per game int32 prev_n[128], int32 prev_sum, int32 start_tasks, float64 last_gain, int32 checks, uint8
+ * cut: one device allocation (about 540 bytes per game) that exists exactly while a rule is on.
+ *
+ * cz_search_set_kld_gain: gain 0 switches the rule off.  CZ_ERR_ARG: s NULL, gain negative or not finite, interval < 1,
+ * and gain > 0 while the Gumbel root search, the MCTS solver or the evaluation cache is on (each has a root rule or a
+ * kernel instantiation of its own; their setters refuse likewise while a stop rule is on).  cz_search_set_smart_pruning: on
+ * is 0 or 1; refused likewise.  Switching a rule on while searches are under way treats them as begun at that moment.
+ * Call them before cz_search_start_selfplay / cz_search_set_roots and before a graph capture; they synchronise the stream. */
+#define CZ_VISIT_EARLY 16u
+int cz_search_set_kld_gain(cz_search* s, double gain, int interval, void* stream);
+int cz_search_set_smart_pruning(cz_search* s, int on, void* stream);
+/* gain [G] float64 and checks [G] int32, DEVICE: the last measured g of each game's current ply (NaN: none yet, or both
+ * rules off) and the number of its checkpoints, the one that took the first snapshot included. */
+int cz_search_root_kld(cz_search* s, double* gain, int32_t* checks, void* stream);
 /* ---- network epilogue -----------------------------------------------------------------------------
  * x = relu?(x + bias[c] (+ residual)) in place over a channels-last activation x[rows][channels]
  * (n_elems = rows * channels, channels % 8 == 0, dtype CZ_F32 / CZ_F16 / CZ_BF16).  Replaces the separate
