@@ -377,8 +377,8 @@ class Search:
         root samples m candidates through Gumbel noise, spends the ply's simulations on them by sequential halving and
         plays the survivor, without root noise or temperature; self-play's visit entries then hold the policy target
         softmax(log prior + sigma(completed Q)) scaled to 65536 (`gumbel`, `raw_total`).  m = 0 switches it off.  Refused
-        while forced playouts or the playout cap are on.  Call it before start_selfplay() / set_roots() and before a graph
-        capture."""
+        beside the features include/czero.h's matrix names for it.  Call it before start_selfplay() / set_roots() and
+        before a graph capture."""
         _native.check(self.L.cz_search_set_gumbel(self.h, int(m), float(c_visit), float(c_scale), self._stream()),
                       "cz_search_set_gumbel")
         self.gumbel_m, self.gumbel_visit, self.gumbel_scale = int(m), float(c_visit), float(c_scale)
@@ -414,8 +414,8 @@ class Search:
         """MCTS solver (cz_search_set_solver; include/czero.h has the definitions): a node whose every move allows the
         king's capture is proven lost and the move that leads to it wins; proven nodes end a descent without a network
         row, a winning root move is taken at once, a decided root starts no further simulation, and at a won root the
-        played move is the winning one.  Refused while the Gumbel root search, forced playouts or the evaluation cache
-        are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
+        played move is the winning one.  Refused beside the features include/czero.h's matrix names for it.
+        Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
         if not hasattr(self.L, "cz_search_set_solver"):
             raise _native.NativeError("this libczero.so has no MCTS solver (cz_search_set_solver)")
         _native.check(self.L.cz_search_set_solver(self.h, 1 if on else 0, self._stream()), "cz_search_set_solver")
@@ -454,8 +454,8 @@ class Search:
     def set_kld_gain(self, gain=0.0, interval=100):
         """KLD-gain stop (cz_search_set_kld_gain; include/czero.h has the rule): every `interval` new root visits the root's
         visit distribution is compared with the one of the ply's previous checkpoint, and the ply ends when the information
-        gained per simulation falls below `gain`.  gain 0 switches it off.  Refused while the Gumbel root search, the solver
-        or the evaluation cache are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph
+        gained per simulation falls below `gain`.  gain 0 switches it off.  Refused beside the features include/czero.h's
+        matrix names for it.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph
         capture."""
         if not hasattr(self.L, "cz_search_set_kld_gain"):
             raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_kld_gain)")
@@ -466,8 +466,8 @@ class Search:
     def set_smart_pruning(self, on=True):
         """Unreachable-lead stop (cz_search_set_smart_pruning; include/czero.h has the rule): a ply whose move is chosen with
         tau = 0 ends once its most visited non-banned root move leads the second by more than the simulations not yet
-        started -- they could not change the move.  Refused while the Gumbel root search, the solver or the evaluation
-        cache are on.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
+        started -- they could not change the move.  Refused beside the features include/czero.h's matrix
+        names for it.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
         if not hasattr(self.L, "cz_search_set_smart_pruning"):
             raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_smart_pruning)")
         _native.check(self.L.cz_search_set_smart_pruning(self.h, 1 if on else 0, self._stream()),

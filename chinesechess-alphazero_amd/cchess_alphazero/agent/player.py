@@ -11,7 +11,7 @@ from logging import getLogger
 
 import numpy as np
 
-from cchess_alphazero import _native
+from cchess_alphazero import _native, search_options
 from cchess_alphazero._native_search import MAX_NO_ACT, Search
 from cchess_alphazero.environment import static_env as senv
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed, label_index
@@ -68,6 +68,11 @@ class CChessPlayer:
         self._idle.set()
         if pipes is None:
             raise ValueError("CChessPlayer needs a pipe to the network (model.get_pipes())")
+        # MCTS solver and unreachable-lead stop (search_options.py): None = config.engine's value, off by default.  After
+        # action() self.proof is the root's (status, d) -- (0, 0) while the solver is off or nothing is proven.
+        opts = search_options.resolve(config, solver=solver, smart_pruning=smart_pruning)
+        search_options.check(opts)
+        vars(self).update(opts)                # self.solver, self.smart_pruning
         pc = self.play_config
         # simulation count from play_config, lock-step batch from config.play (player.py:155-174)
         merged = type("PC", (), dict(vars(pc)))()
@@ -81,20 +86,8 @@ class CChessPlayer:
                               pool_chunks=256 if uci else 0,
                               use_history=use_history)
         self._torch = torch
-        # MCTS solver (cz_search_set_solver): None = config.engine.solver, off by default.  After action() self.proof is the
-        # root's (status, d) -- (0, 0) while the option is off or nothing is proven.
-        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False) if solver is None else solver)
         self.proof = (0, 0)
-        if self.solver:
-            self._search.set_solver(True)
-        # unreachable-lead stop (cz_search_set_smart_pruning): None = config.engine.smart_pruning, off by default.  A search
-        # with a simulation budget whose move is the most visited one ends once the leader cannot be caught.
-        self.smart_pruning = bool(getattr(getattr(config, "engine", None), "smart_pruning", False)
-                                  if smart_pruning is None else smart_pruning)
-        if self.smart_pruning and self.solver:
-            raise ValueError("smart_pruning excludes solver: each defines its own root rule")
-        if self.smart_pruning:
-            self._search.set_smart_pruning(True)
+        search_options.apply(self._search, opts)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes):

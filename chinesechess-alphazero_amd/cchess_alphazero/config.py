@@ -7,6 +7,8 @@ games per GPU, network dtype, arena size) are extra attributes of ``config.engin
 import getpass
 import os
 
+from cchess_alphazero import search_options
+
 
 def _project_dir():
     d = os.path.dirname
@@ -91,42 +93,12 @@ class EngineConfig(_Section):
                                                   # columns, the priors come from the legal moves' logits (cz_search_policy_logits)
                          leaf_masks=True,         # the search kernel also writes every leaf as a 96-word occupancy board, which the
                                                   # first block's fused input layer takes instead of scanning the planes
-                         record_visits=False,     # play records carry each searched move's root visit counts:
-                                                  # items [move, value, pi] (run.py self --record-visits)
                          book_path=None,          # start-position book (run.py self / eval --book FILE, lib/book.py): games
                          book_rate=1.0,           # start from its positions with this probability, else from INIT_STATE
-                         fast_sims=0,             # playout cap randomization (run.py self --fast-sims N --full-rate P): a ply
-                         full_rate=0.25,          # is a full search with probability full_rate, else fast_sims simulations
-                                                  # without root noise, and its row is not trained on; 0 = off
-                         forced_playouts=0.0,     # forced playouts + policy target pruning (run.py self --forced-playouts
-                                                  # K, needs record_visits): a tried root child gets at least
-                                                  # sqrt(K * p * N) visits, the recorded counts are pruned; 0 = off
-                         record_q=False,          # play records carry each searched ply's root search value (run.py self
-                                                  # --record-q, needs record_visits): items [move, value, pi, weight, q]
-                         record_surprise=False,   # play records carry each recorded ply's policy surprise (run.py self
-                                                  # --record-surprise, needs record_visits): items [move, value, pi,
-                                                  # weight, q or None, s]
-                         leaf_mirror=0.0,         # random leaf mirror (run.py self / eval --leaf-mirror P): a new leaf is shown to
-                                                  # the network as its left-right mirror image with probability P, its policy
-                                                  # row read back through the label mirror (cz_search_set_leaf_mirror); 0 = off
-                         gumbel=0,                # Gumbel root search with sequential halving (run.py self --gumbel M, needs
-                         gumbel_visit=50.0,       # record_visits): M candidates sampled at the root, sigma's c_visit and
-                         gumbel_scale=1.0,        # c_scale; the recorded pi is softmax(log prior + sigma(completed Q)); 0 = off
-                         gumbel_full=False,       # full Gumbel search (run.py self --gumbel-full, needs gumbel): the Gumbel rule
-                                                  # below the root too, v_mix in the recorded pi (cz_search_set_gumbel_full)
-                         solver=False,            # MCTS solver (run.py self / eval --solver, UCI option Solver): forced wins and
-                                                  # losses are proven in the search tree (cz_search_set_solver)
-                         kld_gain=0.0,            # KLD-gain stop (run.py self --kld-gain G): a ply ends once the information its
-                         kld_interval=100,        # root visit distribution gains per simulation, measured every kld_interval
-                                                  # root visits, falls below G; 0 = off (cz_search_set_kld_gain)
-                         smart_pruning=False,     # unreachable-lead stop (run.py eval --smart-pruning, UCI option SmartPruning): a
-                                                  # tau = 0 ply ends once the leader cannot be caught (cz_search_set_smart_pruning)
-                         eval_cache=0,            # cross-game evaluation cache (run.py self --eval-cache LOG2): a table of
-                                                  # 2**LOG2 network results keyed by position, kept across games; a new leaf
-                                                  # it holds takes no queue row; same search bit for bit; 576 B per entry;
-                                                  # 0 = off, else 10 .. 24 (cz_search_set_eval_cache)
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
-                         max_rounds=None, max_games=None)   # None = run forever, like the reference
+                         max_rounds=None, max_games=None,   # None = run forever, like the reference
+                         # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
+                         **search_options.DEFAULTS)
 
 
 class Options:

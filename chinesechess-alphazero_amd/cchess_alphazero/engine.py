@@ -17,8 +17,8 @@ from logging import getLogger
 
 import torch
 
-from cchess_alphazero import _native
-from cchess_alphazero._native_search import Search, check_eval_cache_log2
+from cchess_alphazero import _native, search_options
+from cchess_alphazero._native_search import Search
 from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE
@@ -53,59 +53,20 @@ class SelfPlayEngine:
         book: start positions (state strings in the mover's frame, lib/book.py load_book; None = the file
         config.engine.book_path, if set): game `game_id` starts from book[game_id % n] with probability book_rate (None =
         config.engine.book_rate), otherwise from INIT_STATE.  The side that moves first plays "red" in every count.
-        fast_sims, full_rate: playout cap randomization (None = config.engine.fast_sims / full_rate; fast_sims 0 = off): a
-        ply is a full search with probability full_rate, otherwise a fast one of fast_sims simulations without root noise,
-        whose record item carries the training weight 0 (drain).
-        forced_playouts: k of forced playouts and policy target pruning (None = config.engine.forced_playouts; 0 = off):
-        on full plies a tried root child is visited at least sqrt(k * p * N) times, and the recorded visit counts -- the
-        pi of drain()'s items -- are the pruned ones (include/czero.h).  The moves are chosen from the raw counts.
-        record_q: every searched ply's root search value goes into the records (None = config.engine.record_q; needs
-        record_visits): drain()'s items become [move, value, pi or None, weight, q] (cz_search_record_values).
-        record_surprise: every ply with a visit entry records its policy surprise s, the Kullback-Leibler divergence of
-        the recorded counts from the root's priors (None = config.engine.record_surprise; needs record_visits): drain()'s
-        items become [move, value, pi or None, weight, q or None, s] (cz_search_record_surprise).
-        leaf_mirror: the rate at which the search shows a new leaf to the network as its left-right mirror image (None =
-        config.engine.leaf_mirror; 0 = off), reading that leaf's policy row back through the label mirror
-        (cz_search_set_leaf_mirror).  The network and the records need nothing: rows and moves stay in their own frames.
-        gumbel, gumbel_visit, gumbel_scale: Gumbel root search with sequential halving (None = config.engine.gumbel /
-        gumbel_visit / gumbel_scale; gumbel 0 = off; needs record_visits, excludes fast_sims and forced_playouts): the root
-        samples `gumbel` candidates through Gumbel noise, halves them over the ply's simulations and plays the survivor,
-        without root noise or temperature; the pi of drain()'s items is softmax(log prior + sigma(completed Q)) scaled to
-        65536 (include/czero.h, cz_search_set_gumbel).
-        gumbel_full: the full Gumbel search (None = config.engine.gumbel_full; needs gumbel): below the root the selection
-        is argmax pi'(a) - N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes the unvisited edges with v_mix,
-        the root's network value mixed with the visited edges' mean (cz_search_set_gumbel_full).
-        eval_cache: log2 of the entries of the cross-game evaluation cache (None = config.engine.eval_cache; 0 = off, else
-        10 .. 24): network results keyed by position, shared by all games and kept across games; a new leaf the table
-        holds takes no queue row, and the games, records and counters are the ones played without it
-        (cz_search_set_eval_cache).  Every network change empties it (_install).  Excludes use_history.
-        solver: the MCTS solver (None = config.engine.solver; excludes gumbel, forced_playouts and eval_cache): forced wins
-        and losses are proven in the tree from the king captures the search meets, proven positions end a descent without a
-        network row, a decided root starts no further simulation and a won root plays the winning move
-        (cz_search_set_solver).  The records are what the tree holds: no target is rewritten.
-        kld_gain, kld_interval: the KLD-gain stop (None = config.engine.kld_gain / kld_interval; kld_gain 0 = off; excludes
-        gumbel, solver and eval_cache): every kld_interval new root visits the root's visit distribution is compared with
-        the previous checkpoint's, and the ply ends when the information gained per simulation falls below kld_gain
-        (cz_search_set_kld_gain).  A ply that ended early is marked in its visit entry; the records are unchanged."""
-        ec_ = getattr(config, "engine", None)
-        self.kld_gain = float(getattr(ec_, "kld_gain", 0.0) if kld_gain is None else kld_gain)
-        self.kld_interval = int(getattr(ec_, "kld_interval", 100) if kld_interval is None else kld_interval)
-        if not (0.0 <= self.kld_gain < float("inf")):
-            raise ValueError(f"kld_gain {self.kld_gain}: expected a finite G >= 0")
-        if self.kld_interval < 1:
-            raise ValueError(f"kld_interval {self.kld_interval}: expected N >= 1")
-        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False) if solver is None else solver)
-        self.eval_cache = check_eval_cache_log2(getattr(getattr(config, "engine", None), "eval_cache", 0)
-                                                if eval_cache is None else eval_cache)
-        if self.solver and self.eval_cache:
-            raise ValueError("solver excludes eval_cache: the cache has a kernel instantiation of its own")
-        if self.kld_gain and self.eval_cache:
-            raise ValueError("kld_gain excludes eval_cache: the cache has a kernel instantiation of its own")
-        if self.kld_gain and self.solver:
-            raise ValueError("kld_gain excludes solver: each defines its own root rule")
-        if self.eval_cache and use_history:
-            raise ValueError("eval_cache excludes use_history: the second block of the 28-plane input depends on the "
-                             "simulation's path and the game history, so the network input is not a function of the position")
+        fast_sims .. kld_interval, record_visits: the search options of search_options.py under their config.engine names
+        (None = config.engine's value); that table has each one's meaning, range, prerequisite and the options it cannot run
+        beside, and a violation raises its SearchOptionError (a ValueError) before a device is asked for.  What they add to
+        drain()'s items: record_visits [move, value, pi], the playout cap a weight (0 for a fast ply), record_q the root's
+        search value q, record_surprise the ply's surprise s -- [move, value, pi or None, weight, q or None, s]; with
+        forced_playouts pi is the pruned counts, with gumbel softmax(log prior + sigma(completed Q)) scaled to 65536
+        (include/czero.h).  eval_cache: every network change empties it (_install)."""
+        opts = search_options.resolve(
+            config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
+            record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
+            gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
+            solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
+        search_options.check(opts, history=use_history)
+        vars(self).update(opts)                # self.record_visits, self.fast_sims, ... self.kld_interval
         _native.require_gpu()
         self.config = config
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -147,9 +108,6 @@ class SelfPlayEngine:
         self.rounds = 0
         self.seed = seed
         self._graph = None
-        if record_visits is None:
-            record_visits = getattr(getattr(config, "engine", None), "record_visits", False)
-        self.record_visits = bool(record_visits)
         self._since_pull = 0
         if self.record_visits:
             self.search.record_visits(True, capacity=8 * VISIT_DRAIN_ROUNDS * self.search.G)
@@ -163,53 +121,8 @@ class SelfPlayEngine:
         if self.book:                                          # handed over before start() and before a graph capture
             from cchess_alphazero.lib.book import book_boards
             self.search.set_book(book_boards(self.book), self.book_rate)
-        self.fast_sims = int(getattr(ec, "fast_sims", 0) if fast_sims is None else fast_sims)
-        self.full_rate = float(getattr(ec, "full_rate", 0.25) if full_rate is None else full_rate)
-        if self.fast_sims:                                     # likewise before start() and before a graph capture
-            self.search.set_playout_cap(self.fast_sims, self.full_rate)
-        self.forced_playouts = float(getattr(ec, "forced_playouts", 0.0) if forced_playouts is None else forced_playouts)
-        if self.forced_playouts and not self.record_visits:
-            raise ValueError("forced_playouts needs record_visits: forcing without the pruned visit counts only distorts "
-                             "what a trainer sees")
-        if self.forced_playouts:                               # likewise
-            self.search.set_forced_playouts(self.forced_playouts)
-        self.record_q = bool(getattr(ec, "record_q", False) if record_q is None else record_q)
-        if self.record_q and not self.record_visits:
-            raise ValueError("record_q needs record_visits: the search values ride beside the visit entries")
-        if self.record_q:                                      # likewise
-            self.search.record_values(True)
-        self.record_surprise = bool(getattr(ec, "record_surprise", False) if record_surprise is None else record_surprise)
-        if self.record_surprise and not self.record_visits:
-            raise ValueError("record_surprise needs record_visits: the surprises ride beside the visit entries")
-        if self.record_surprise:                               # likewise
-            self.search.record_surprise(True)
-        self.leaf_mirror = float(getattr(ec, "leaf_mirror", 0.0) if leaf_mirror is None else leaf_mirror)
-        if not 0.0 <= self.leaf_mirror <= 1.0:
-            raise ValueError(f"leaf_mirror {self.leaf_mirror}: expected 0 <= P <= 1")
-        if self.leaf_mirror:                                   # likewise
-            self.search.set_leaf_mirror(self.leaf_mirror)
-        self.gumbel = int(getattr(ec, "gumbel", 0) if gumbel is None else gumbel)
-        self.gumbel_visit = float(getattr(ec, "gumbel_visit", 50.0) if gumbel_visit is None else gumbel_visit)
-        self.gumbel_scale = float(getattr(ec, "gumbel_scale", 1.0) if gumbel_scale is None else gumbel_scale)
-        if self.gumbel and not self.record_visits:
-            raise ValueError("gumbel needs record_visits: the halving counts are not a policy target")
-        if self.gumbel and (self.fast_sims or self.forced_playouts):
-            raise ValueError("gumbel excludes fast_sims and forced_playouts: each defines its own root rule")
-        self.gumbel_full = bool(getattr(ec, "gumbel_full", False) if gumbel_full is None else gumbel_full)
-        if self.gumbel_full and not self.gumbel:
-            raise ValueError("gumbel_full needs gumbel: it completes the Gumbel root search below the root")
-        if self.gumbel:                                        # likewise
-            self.search.set_gumbel(self.gumbel, self.gumbel_visit, self.gumbel_scale)
-        if self.gumbel_full:
-            self.search.set_gumbel_full(True)
-        if self.solver and (self.gumbel or self.forced_playouts):
-            raise ValueError("solver excludes gumbel and forced_playouts: each defines its own root rule")
-        if self.solver:                                        # likewise
-            self.search.set_solver(True)
-        if self.kld_gain and self.gumbel:
-            raise ValueError("kld_gain excludes gumbel: each defines its own root rule")
-        if self.kld_gain:                                      # likewise
-            self.search.set_kld_gain(self.kld_gain, self.kld_interval)
+        # every other option that is on: likewise before start() and before a graph capture
+        search_options.apply(self.search, opts, skip=("eval_cache",))
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py

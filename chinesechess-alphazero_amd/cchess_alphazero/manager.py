@@ -5,6 +5,7 @@ so."""
 import argparse
 from logging import getLogger
 
+from cchess_alphazero import search_options
 from cchess_alphazero.config import Config
 from cchess_alphazero.lib.logger import setup_logger
 
@@ -15,7 +16,8 @@ PIECE_STYLES = ('WOOD', 'POLISH', 'DELICATE')
 BOARD_STYLES = ('CANVAS', 'DROPS', 'GREEN', 'QIANHONG', 'SHEET', 'SKELETON', 'WHITE', 'WOOD')
 RANDOMNESS = ('none', 'small', 'medium', 'large')
 
-# (flag, kwargs) -- the reference's options first (manager.py:16-33), then the engine's own
+# (flag, kwargs) -- the reference's options first (manager.py:16-33), then the engine's own; the search options' flags come
+# from their table (search_options.py)
 _FLAGS = [
     ("--new", dict(action="store_true", help="run from new best model")),
     ("--type", dict(default="mini", help="configuration: mini / normal / distribute")),
@@ -35,71 +37,17 @@ _FLAGS = [
     ("--net-dtype", dict(choices=["float32", "bfloat16", "float16"], help="engine: network precision")),
     ("--max-rounds", dict(type=int, help="engine: stop after this many lock-step rounds (default: never)")),
     ("--max-games", dict(type=int, help="engine: stop after this many finished games (default: never)")),
-    ("--record-visits", dict(action="store_true",
-                             help="(self) play records carry each searched move's root visit counts: [move, value, pi]")),
     ("--book", dict(metavar="FILE", help="(self, eval) start-position book: one state string or FEN per line; self-play game "
                                          "i starts from position i mod n, the arena plays each position once per colour")),
     ("--book-rate", dict(type=float, default=1.0, metavar="P",
                          help="(self) a game starts from the book with probability P, otherwise from the opening position")),
-    ("--fast-sims", dict(type=int, default=0, metavar="N",
-                         help="(self) playout cap randomization: a ply is a full search with probability --full-rate, otherwise "
-                              "a fast one of N simulations without root noise whose row is not trained on (0 = off)")),
-    ("--full-rate", dict(type=float, default=0.25, metavar="P",
-                         help="(self, with --fast-sims) probability that a ply is a full search")),
-    ("--forced-playouts", dict(type=float, default=0.0, metavar="K",
-                               help="(self, with --record-visits) forced playouts and policy target pruning: on full plies a "
-                                    "tried root move is visited at least sqrt(K * prior * visits) times and the recorded "
-                                    "counts are pruned of the visits that forcing added (0 = off; the paper uses 2)")),
-    ("--record-q", dict(action="store_true",
-                        help="(self, with --record-visits) play records carry each searched ply's root search value: "
-                             "[move, value, pi, weight, q], for run.py opt --q-ratio")),
     ("--q-ratio", dict(type=float, default=0.0, metavar="L",
                        help="(opt) value target z + L (q - z): the game result mixed with the records' root search values "
                             "where they have one (0 <= L <= 1; 0 = the game result alone, the reference)")),
-    ("--record-surprise", dict(action="store_true",
-                               help="(self, with --record-visits) play records carry each recorded ply's policy surprise, "
-                                    "KL(visit counts || network prior): [move, value, pi, weight, q, s], for run.py opt "
-                                    "--surprise-weight")),
     ("--surprise-weight", dict(type=float, default=0.0, metavar="A",
                                help="(opt) policy surprise weighting: within a game, the share A of the training weight goes "
                                     "to the rows in proportion to their recorded surprise (0 <= A <= 1; 0 = uniform, the "
                                     "reference; KataGo uses 0.5)")),
-    ("--leaf-mirror", dict(type=float, default=0.0, metavar="P",
-                           help="(self, eval) random leaf mirror: the search shows every new leaf to the network as its "
-                                "left-right mirror image with probability P and reads the policy back through the label "
-                                "mirror, so that the network's wing bias averages out of the search (0 = off; 0.5 = a fair "
-                                "coin)")),
-    ("--gumbel", dict(type=int, default=0, metavar="M",
-                      help="(self, with --record-visits) Gumbel root search: M candidate moves are sampled at the root through "
-                           "Gumbel noise, the ply's simulations are spent on them by sequential halving and the survivor is "
-                           "played; the recorded pi is softmax(log prior + sigma(completed Q)).  Sound at small --sims "
-                           "(0 = off; the paper uses 16)")),
-    ("--gumbel-visit", dict(type=float, default=50.0, metavar="C", help="(self, with --gumbel) c_visit of sigma")),
-    ("--gumbel-scale", dict(type=float, default=1.0, metavar="C", help="(self, with --gumbel) c_scale of sigma")),
-    ("--gumbel-full", dict(action="store_true",
-                           help="(self, with --gumbel) full Gumbel search: below the root the selection is argmax pi'(a) - "
-                                "N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes unvisited moves with v_mix, "
-                                "the root's network value mixed with the visited moves' mean")),
-    ("--eval-cache", dict(type=int, default=0, metavar="LOG2",
-                          help="(self) cross-game evaluation cache: a table of 2**LOG2 network results keyed by position "
-                               "(576 bytes each), shared by all games and kept across games; a new leaf whose position it "
-                               "holds is not evaluated again.  The search stays the same bit for bit (0 = off; 10 <= LOG2 "
-                               "<= 24)")),
-    ("--solver", dict(action="store_true",
-                      help="(self, eval) MCTS solver: a position whose every move allows the king's capture is proven lost "
-                           "and the move that leads to it wins; proven positions end a simulation without a network "
-                           "evaluation, a decided root is not searched further and a won root plays the winning move")),
-    ("--kld-gain", dict(type=float, default=0.0, metavar="G",
-                        help="(self) KLD-gain stop: every --kld-interval new root visits the root's visit distribution is "
-                             "compared with the previous checkpoint's, and the ply's search ends when the information gained "
-                             "per simulation falls below G: quiet positions get short searches (0 = off; lc0's training "
-                             "games use values around 1e-5 .. 1e-4)")),
-    ("--kld-interval", dict(type=int, default=100, metavar="N",
-                            help="(self, with --kld-gain) root visits between two checkpoints")),
-    ("--smart-pruning", dict(action="store_true",
-                             help="(eval) unreachable-lead stop: a ply whose move is the most visited one ends once that move "
-                                  "leads the second by more than the simulations not yet started; the move is the one the "
-                                  "full search would have played from the same tree")),
     ("--sims", dict(type=int, default=None, metavar="N",
                     help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
@@ -108,7 +56,7 @@ _FLAGS = [
     ("--augment", dict(choices=["none", "mirror"], default="none",
                        help="(opt) mirror: every training row of every epoch is the left-right mirrored position with "
                             "probability 1/2 (planes and policy targets, in the trainer's kernels)")),
-]
+] + search_options.flags()
 
 
 def create_parser():
@@ -136,8 +84,6 @@ def build_config(args):
     if args.net_dtype:
         engine.net_dtype = args.net_dtype
     engine.max_rounds, engine.max_games = args.max_rounds, args.max_games
-    if args.record_visits:
-        engine.record_visits = True
     if not 0.0 <= args.book_rate <= 1.0:
         raise SystemExit(f"--book-rate {args.book_rate}: expected 0 <= P <= 1")
     engine.book_path, engine.book_rate = args.book, args.book_rate
@@ -147,87 +93,20 @@ def build_config(args):
         if args.sims < 1:
             raise SystemExit(f"--sims {args.sims}: expected N >= 1")
         config.play.simulation_num_per_move = args.sims
-    if not 0 <= args.fast_sims <= config.play.simulation_num_per_move:
-        raise SystemExit(f"--fast-sims {args.fast_sims}: expected 0 <= N <= simulation_num_per_move "
-                         f"({config.play.simulation_num_per_move})")
-    if not 0.0 <= args.full_rate <= 1.0:
-        raise SystemExit(f"--full-rate {args.full_rate}: expected 0 <= P <= 1")
-    engine.fast_sims, engine.full_rate = args.fast_sims, args.full_rate
-    if not 0.0 <= args.forced_playouts < float("inf"):
-        raise SystemExit(f"--forced-playouts {args.forced_playouts}: expected a finite K >= 0")
-    if args.forced_playouts and not engine.record_visits:
-        raise SystemExit(f"--forced-playouts {args.forced_playouts} needs --record-visits: forcing without the pruned "
-                         "visit counts only distorts what the trainer sees")
-    engine.forced_playouts = args.forced_playouts
-    if args.record_q and not engine.record_visits:
-        raise SystemExit("--record-q needs --record-visits: the search values ride beside the visit entries")
-    if args.record_q:
-        engine.record_q = True
+    # the search options: ranges, commands, prerequisites and exclusions are their table's (search_options.py)
+    values = {k: getattr(args, k) for k in search_options.VALUES}
+    try:
+        search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
+                             history=getattr(config.model, "input_depth", 14) == 28)
+    except search_options.SearchOptionError as e:
+        raise SystemExit(str(e))
+    vars(engine).update(values)
     if not 0.0 <= args.q_ratio <= 1.0:
         raise SystemExit(f"--q-ratio {args.q_ratio}: expected 0 <= L <= 1")
     config.trainer.q_ratio = args.q_ratio
-    if args.record_surprise and not engine.record_visits:
-        raise SystemExit("--record-surprise needs --record-visits: the surprises ride beside the visit entries")
-    if args.record_surprise:
-        engine.record_surprise = True
     if not 0.0 <= args.surprise_weight <= 1.0:
         raise SystemExit(f"--surprise-weight {args.surprise_weight}: expected 0 <= A <= 1")
     config.trainer.surprise_weight = args.surprise_weight
-    if not 0.0 <= args.leaf_mirror <= 1.0:                  # (false for NaN too)
-        raise SystemExit(f"--leaf-mirror {args.leaf_mirror}: expected 0 <= P <= 1")
-    engine.leaf_mirror = args.leaf_mirror
-    if not 0 <= args.gumbel <= 128:
-        raise SystemExit(f"--gumbel {args.gumbel}: expected 0 <= M <= 128")
-    for name in ("gumbel_visit", "gumbel_scale"):
-        if not 0.0 <= getattr(args, name) < float("inf"):
-            raise SystemExit(f"--{name.replace('_', '-')} {getattr(args, name)}: expected a finite C >= 0")
-    if args.gumbel and not engine.record_visits:
-        raise SystemExit(f"--gumbel {args.gumbel} needs --record-visits: the halving counts are not a policy target, the "
-                         "target rides in the visit entries")
-    if args.gumbel and args.fast_sims:
-        raise SystemExit("--gumbel excludes --fast-sims: each defines its own root rule")
-    if args.gumbel and args.forced_playouts:
-        raise SystemExit("--gumbel excludes --forced-playouts: each defines its own root rule")
-    if args.gumbel_full and not args.gumbel:
-        raise SystemExit("--gumbel-full needs --gumbel M: it completes the Gumbel root search below the root")
-    engine.gumbel, engine.gumbel_visit, engine.gumbel_scale = args.gumbel, args.gumbel_visit, args.gumbel_scale
-    engine.gumbel_full = bool(args.gumbel_full)
-    if args.eval_cache:
-        if args.cmd != "self":
-            raise SystemExit("--eval-cache is an option of `run.py self`: the arena feeds two networks through one search, "
-                             "and a single game's tree is already its own cache")
-        if not 10 <= args.eval_cache <= 24:
-            raise SystemExit(f"--eval-cache {args.eval_cache}: expected 0 (off) or 10 <= LOG2 <= 24")
-        if getattr(config.model, "input_depth", 14) == 28:
-            raise SystemExit("--eval-cache needs the 14-plane input: with 28 planes the second block depends on the "
-                             "simulation's path and the game history, so the network input is not a function of the position")
-    engine.eval_cache = args.eval_cache
-    if args.solver and args.cmd not in ("self", "eval"):
-        raise SystemExit("--solver is an option of `run.py self` and `run.py eval`")
-    if args.solver and args.gumbel:
-        raise SystemExit("--solver excludes --gumbel: each defines its own root rule")
-    if args.solver and args.forced_playouts:
-        raise SystemExit("--solver excludes --forced-playouts: each defines its own root rule")
-    if args.solver and args.eval_cache:
-        raise SystemExit("--solver excludes --eval-cache: the cache has a kernel instantiation of its own")
-    engine.solver = bool(args.solver)
-    if not 0.0 <= args.kld_gain < float("inf"):             # (false for NaN too)
-        raise SystemExit(f"--kld-gain {args.kld_gain}: expected a finite G >= 0")
-    if args.kld_interval < 1:
-        raise SystemExit(f"--kld-interval {args.kld_interval}: expected N >= 1")
-    if args.kld_gain and args.cmd != "self":
-        raise SystemExit("--kld-gain is an option of `run.py self`")
-    if args.smart_pruning and args.cmd != "eval":
-        raise SystemExit("--smart-pruning is an option of `run.py eval`")
-    for flag, on in (("--kld-gain", bool(args.kld_gain)), ("--smart-pruning", bool(args.smart_pruning))):
-        if on and args.gumbel:
-            raise SystemExit(f"{flag} excludes --gumbel: each defines its own root rule")
-        if on and args.solver:
-            raise SystemExit(f"{flag} excludes --solver: each defines its own root rule")
-        if on and args.eval_cache:
-            raise SystemExit(f"{flag} excludes --eval-cache: the cache has a kernel instantiation of its own")
-    engine.kld_gain, engine.kld_interval = args.kld_gain, args.kld_interval
-    engine.smart_pruning = bool(args.smart_pruning)
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

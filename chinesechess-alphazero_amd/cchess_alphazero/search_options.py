@@ -1,0 +1,196 @@
+"""The search options that travel flag -> config.engine -> engine / player / arena -> Search.set_*, stated once: each one's
+values (key, flag, default, range, help), the run.py commands that take it, what it needs, the Search call that switches it
+on and its self-play log line -- and the pairs that cannot run beside each other.  No torch, no device.
+
+An option is ON when its first value is truthy (every first default is falsy).  OPTIONS is in the order the options were
+added, and a pair of EXCLUDES is (the later option, the earlier one): check() reports in table order, so a refusal reads
+`<later> excludes <earlier>: <reason>`.  csrc/xq_search.hip holds the same matrix for the library's setters
+(tests/test_gpu_search_options.py pins the two to each other)."""
+from collections import namedtuple
+
+INF = float("inf")
+EVAL_CACHE_STRIDE = 576      # include/czero.h CZ_EVAL_CACHE_STRIDE
+
+# ok(v, sims) -> bool (None: any value); `expected` completes "<name> <v>: expected ..."; metavar None = a store_true flag
+Value = namedtuple("Value", "key flag default metavar ok expected help", defaults=(False, None, None, None, None))
+# commands: the run.py commands that accept the option switched on (None: all), command_why: appended to that refusal;
+# needs: (key, reason); refused_with: (context key of check(), reason); setter: the Search method, called with the values;
+# log: str.format template over all values + sims + eval_cache_mib
+Option = namedtuple("Option", "values commands command_why needs refused_with setter log", defaults=(None,) * 6)
+
+
+def _rate(v, sims):
+    return 0.0 <= v <= 1.0              # (false for NaN too)
+
+
+def _finite(v, sims):
+    return 0.0 <= v < INF
+
+
+OPTIONS = (
+    Option([Value("record_visits", "--record-visits",
+                  help="(self) play records carry each searched move's root visit counts: [move, value, pi]")]),
+    Option([Value("fast_sims", "--fast-sims", 0, "N", lambda v, sims: 0 <= v <= (v if sims is None else sims),
+                  "0 <= N <= simulation_num_per_move ({sims})",
+                  "(self) playout cap randomization: a ply is a full search with probability --full-rate, otherwise "
+                  "a fast one of N simulations without root noise whose row is not trained on (0 = off)"),
+            Value("full_rate", "--full-rate", 0.25, "P", _rate, "0 <= P <= 1",
+                  "(self, with --fast-sims) probability that a ply is a full search")],
+           setter="set_playout_cap",
+           log="playout cap: a ply is a full search ({sims} simulations) with probability {full_rate}, otherwise "
+               "{fast_sims} simulations without root noise"),
+    Option([Value("forced_playouts", "--forced-playouts", 0.0, "K", _finite, "a finite K >= 0",
+                  "(self, with --record-visits) forced playouts and policy target pruning: on full plies a "
+                  "tried root move is visited at least sqrt(K * prior * visits) times and the recorded "
+                  "counts are pruned of the visits that forcing added (0 = off; the paper uses 2)")],
+           needs=("record_visits", "forcing without the pruned visit counts only distorts what the trainer sees"),
+           setter="set_forced_playouts",
+           log="forced playouts k = {forced_playouts} on full plies; the recorded visit counts are pruned (policy target "
+               "pruning)"),
+    Option([Value("record_q", "--record-q",
+                  help="(self, with --record-visits) play records carry each searched ply's root search value: "
+                       "[move, value, pi, weight, q], for run.py opt --q-ratio")],
+           needs=("record_visits", "the search values ride beside the visit entries"), setter="record_values",
+           log="the records carry each searched ply's root search value q (items [move, value, pi, weight, q])"),
+    Option([Value("record_surprise", "--record-surprise",
+                  help="(self, with --record-visits) play records carry each recorded ply's policy surprise, "
+                       "KL(visit counts || network prior): [move, value, pi, weight, q, s], for run.py opt "
+                       "--surprise-weight")],
+           needs=("record_visits", "the surprises ride beside the visit entries"), setter="record_surprise",
+           log="the records carry each recorded ply's policy surprise s (items [move, value, pi, weight, q, s])"),
+    Option([Value("leaf_mirror", "--leaf-mirror", 0.0, "P", _rate, "0 <= P <= 1",
+                  "(self, eval) random leaf mirror: the search shows every new leaf to the network as its "
+                  "left-right mirror image with probability P and reads the policy back through the label "
+                  "mirror, so that the network's wing bias averages out of the search (0 = off; 0.5 = a fair "
+                  "coin)")],
+           setter="set_leaf_mirror",
+           log="random leaf mirror: a new leaf is evaluated as its left-right mirror image with probability {leaf_mirror}"),
+    Option([Value("gumbel", "--gumbel", 0, "M", lambda v, sims: 0 <= v <= 128, "0 <= M <= 128",
+                  "(self, with --record-visits) Gumbel root search: M candidate moves are sampled at the root through "
+                  "Gumbel noise, the ply's simulations are spent on them by sequential halving and the survivor is "
+                  "played; the recorded pi is softmax(log prior + sigma(completed Q)).  Sound at small --sims "
+                  "(0 = off; the paper uses 16)"),
+            Value("gumbel_visit", "--gumbel-visit", 50.0, "C", _finite, "a finite C >= 0",
+                  "(self, with --gumbel) c_visit of sigma"),
+            Value("gumbel_scale", "--gumbel-scale", 1.0, "C", _finite, "a finite C >= 0",
+                  "(self, with --gumbel) c_scale of sigma")],
+           needs=("record_visits", "the halving counts are not a policy target, the target rides in the visit entries"),
+           setter="set_gumbel",
+           log="Gumbel root search: {gumbel} candidates, sequential halving over {sims} simulations, c_visit = "
+               "{gumbel_visit}, c_scale = {gumbel_scale}; no root noise, no temperature; the recorded pi is "
+               "softmax(log prior + sigma(completed Q))"),
+    Option([Value("gumbel_full", "--gumbel-full",
+                  help="(self, with --gumbel) full Gumbel search: below the root the selection is argmax pi'(a) - "
+                       "N(a) / (1 + sum N) instead of PUCT, and the recorded pi completes unvisited moves with v_mix, "
+                       "the root's network value mixed with the visited moves' mean")],
+           needs=("gumbel", "it completes the Gumbel root search below the root"), setter="set_gumbel_full",
+           log="full Gumbel search: below the root argmax pi'(a) - N(a) / (1 + sum N) replaces PUCT, unvisited moves are "
+               "completed with v_mix"),
+    Option([Value("eval_cache", "--eval-cache", 0, "LOG2", lambda v, sims: v == 0 or 10 <= v <= 24,
+                  "0 (off) or 10 <= LOG2 <= 24",
+                  "(self) cross-game evaluation cache: a table of 2**LOG2 network results keyed by position "
+                  "(576 bytes each), shared by all games and kept across games; a new leaf whose position it "
+                  "holds is not evaluated again.  The search stays the same bit for bit (0 = off; 10 <= LOG2 "
+                  "<= 24)")],
+           commands=("self",),
+           command_why=": the arena feeds two networks through one search, and a single game's tree is already its own cache",
+           refused_with=("history", "needs the 14-plane input (no use_history): with 28 planes the second block depends on "
+                                    "the simulation's path and the game history, so the network input is not a function of "
+                                    "the position"),
+           setter="set_eval_cache",
+           log="evaluation cache: 2^{eval_cache} entries, {eval_cache_mib} MiB, kept across games"),
+    Option([Value("solver", "--solver",
+                  help="(self, eval) MCTS solver: a position whose every move allows the king's capture is proven lost "
+                       "and the move that leads to it wins; proven positions end a simulation without a network "
+                       "evaluation, a decided root is not searched further and a won root plays the winning move")],
+           commands=("self", "eval"), setter="set_solver",
+           log="MCTS solver: forced wins and losses are proven in the tree; a decided root is not searched further, a won "
+               "root plays the winning move"),
+    Option([Value("kld_gain", "--kld-gain", 0.0, "G", _finite, "a finite G >= 0",
+                  "(self) KLD-gain stop: every --kld-interval new root visits the root's visit distribution is "
+                  "compared with the previous checkpoint's, and the ply's search ends when the information gained "
+                  "per simulation falls below G: quiet positions get short searches (0 = off; lc0's training "
+                  "games use values around 1e-5 .. 1e-4)"),
+            Value("kld_interval", "--kld-interval", 100, "N", lambda v, sims: v >= 1, "N >= 1",
+                  "(self, with --kld-gain) root visits between two checkpoints")],
+           commands=("self",), setter="set_kld_gain",
+           log="KLD-gain stop: a ply's search ends once its root visit distribution gains less than {kld_gain:g} per "
+               "simulation, measured every {kld_interval} root visits"),
+    Option([Value("smart_pruning", "--smart-pruning",
+                  help="(eval) unreachable-lead stop: a ply whose move is the most visited one ends once that move "
+                       "leads the second by more than the simulations not yet started; the move is the one the "
+                       "full search would have played from the same tree")],
+           commands=("eval",), setter="set_smart_pruning"),
+)
+
+_ROOT_RULE = "each defines its own root rule"
+_CACHE = "the cache has a kernel instantiation of its own"
+EXCLUDES = (("gumbel", "fast_sims", _ROOT_RULE), ("gumbel", "forced_playouts", _ROOT_RULE),
+            ("solver", "gumbel", _ROOT_RULE), ("solver", "forced_playouts", _ROOT_RULE), ("solver", "eval_cache", _CACHE),
+            ("kld_gain", "gumbel", _ROOT_RULE), ("kld_gain", "solver", _ROOT_RULE), ("kld_gain", "eval_cache", _CACHE),
+            ("smart_pruning", "gumbel", _ROOT_RULE), ("smart_pruning", "solver", _ROOT_RULE),
+            ("smart_pruning", "eval_cache", _CACHE))
+
+VALUES = {v.key: v for o in OPTIONS for v in o.values}
+DEFAULTS = {k: v.default for k, v in VALUES.items()}
+
+
+class SearchOptionError(ValueError):
+    """A value out of range, an option the command does not take, a missing prerequisite or an excluded pair."""
+
+
+def flags():
+    """(flag, argparse keywords) of every value, for manager._FLAGS."""
+    return [(v.flag, dict(action="store_true", help=v.help) if v.metavar is None else
+             dict(type=type(v.default), default=v.default, metavar=v.metavar, help=v.help)) for v in VALUES.values()]
+
+
+def resolve(config, **overrides):
+    """{key: value} of the keys named: the override, or for None config.engine's value, or without one the default; each
+    in its default's type.  config may lack the engine section."""
+    ec = getattr(config, "engine", None)
+    return {k: type(DEFAULTS[k])(getattr(ec, k, DEFAULTS[k]) if v is None else v) for k, v in overrides.items()}
+
+
+def check(values, flags=False, cmd=None, sims=None, **context):
+    """Raises SearchOptionError for the first violation among the values given (a key that is missing is at its default):
+    per option its ranges, the command, its context rule, what it needs, what it excludes; options in table order.
+    flags: the messages name --kld-gain where they would name kld_gain.  cmd: the run.py command (None: not checked);
+    sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
+    input."""
+    def name(key):
+        return VALUES[key].flag if flags else key
+
+    def on(key):
+        return bool(values.get(key, DEFAULTS[key]))
+    for o in OPTIONS:
+        key = o.values[0].key
+        for v in o.values:
+            if v.ok and v.key in values and not v.ok(values[v.key], sims):
+                raise SearchOptionError(f"{name(v.key)} {values[v.key]}: expected {v.expected.format(sims=sims)}")
+        if not on(key):
+            continue
+        shown = name(key) if o.values[0].metavar is None else f"{name(key)} {values[key]}"
+        if cmd is not None and o.commands and cmd not in o.commands:
+            raise SearchOptionError(f"{name(key)} is an option of " + " and ".join(f"`run.py {c}`" for c in o.commands)
+                                    + (o.command_why or ""))
+        if o.refused_with and context.get(o.refused_with[0]):
+            raise SearchOptionError(f"{name(key)} {o.refused_with[1]}")
+        if o.needs and not on(o.needs[0]):
+            raise SearchOptionError(f"{shown} needs {name(o.needs[0])}: {o.needs[1]}")
+        for later, earlier, why in EXCLUDES:
+            if later == key and on(earlier):
+                raise SearchOptionError(f"{name(later)} excludes {name(earlier)}: {why}")
+
+
+def apply(search, values, skip=()):
+    """Switches on, through their Search methods and in table order, the options that are on among the values given."""
+    for o in OPTIONS:
+        if o.setter and o.values[0].key not in skip and values.get(o.values[0].key):
+            getattr(search, o.setter)(*[values[v.key] for v in o.values])
+
+
+def describe(values, sims):
+    """The self-play log line of every option that is on, in table order."""
+    mib = (EVAL_CACHE_STRIDE << values.get("eval_cache", 0)) >> 20
+    return [o.log.format(sims=sims, eval_cache_mib=mib, **values) for o in OPTIONS if o.log and values.get(o.values[0].key)]

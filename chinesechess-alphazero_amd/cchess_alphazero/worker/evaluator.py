@@ -15,7 +15,7 @@ from logging import getLogger
 
 import numpy as np
 
-from cchess_alphazero import _native
+from cchess_alphazero import _native, search_options
 from cchess_alphazero._native_search import MAX_NO_ACT, Search
 from cchess_alphazero.environment.static_env import INIT_STATE, state_to_array
 
@@ -95,12 +95,10 @@ class EvaluateWorker:
         self.evaluators = evaluators
         self.dtype = dtype
         self.seed = seed
-        # random leaf mirror of both models' searches (run.py eval --leaf-mirror P, cz_search_set_leaf_mirror); 0 = off
-        self.leaf_mirror = float(getattr(getattr(config, "engine", None), "leaf_mirror", 0.0) or 0.0)
-        # MCTS solver of both models' searches (run.py eval --solver, cz_search_set_solver)
-        self.solver = bool(getattr(getattr(config, "engine", None), "solver", False))
-        # unreachable-lead stop of both models' searches (run.py eval --smart-pruning, cz_search_set_smart_pruning)
-        self.smart_pruning = bool(getattr(getattr(config, "engine", None), "smart_pruning", False))
+        # of both models' searches (run.py eval --leaf-mirror P / --solver / --smart-pruning; search_options.py)
+        opts = search_options.resolve(config, leaf_mirror=None, solver=None, smart_pruning=None)
+        search_options.check(opts)
+        vars(self).update(opts)                # self.leaf_mirror, self.solver, self.smart_pruning
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -161,15 +159,8 @@ class EvaluateWorker:
         G = len(idx)
         searches = [Search(pc, G, planes_dtype=self.dtype, evaluate=getattr(self.config.opts, "evaluate", False),
                            seed=self.seed + k, sims_per_round=sims_per_round) for k in range(2)]
-        if self.leaf_mirror:                                   # (before any round, and before the compact form's graph capture)
-            for s in searches:
-                s.set_leaf_mirror(self.leaf_mirror)
-        if self.solver:                                        # (likewise)
-            for s in searches:
-                s.set_solver(True)
-        if self.smart_pruning:                                 # (likewise)
-            for s in searches:
-                s.set_smart_pruning(True)
+        for s in searches:                                     # (before any round, and before the compact form's graph capture)
+            search_options.apply(s, vars(self))                # (the three attributes above)
 
         def counters_now():
             c = [s.counters() for s in searches]

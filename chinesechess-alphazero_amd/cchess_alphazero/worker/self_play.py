@@ -13,6 +13,7 @@ from logging import getLogger
 
 import numpy as np
 
+from cchess_alphazero import search_options
 from cchess_alphazero.lib.data_helper import PlayDataWriter, mean_abs_q_minus_z, surprise_sums
 
 logger = getLogger(__name__)
@@ -88,41 +89,9 @@ class SelfPlayWorker:
         if self.engine.book:
             logger.info(f"Process {self.pid}-{self.rank}: start-position book {ec.book_path}: {len(self.engine.book)} "
                         f"positions, rate {self.engine.book_rate}")
-        # (the playout cap, config.engine.fast_sims / full_rate, is likewise set by the engine)
-        if self.engine.fast_sims:
-            logger.info(f"Process {self.pid}-{self.rank}: playout cap: a ply is a full search "
-                        f"({self.config.play.simulation_num_per_move} simulations) with probability {self.engine.full_rate}, "
-                        f"otherwise {self.engine.fast_sims} simulations without root noise")
-        if self.engine.record_q:
-            logger.info(f"Process {self.pid}-{self.rank}: the records carry each searched ply's root search value q "
-                        f"(items [move, value, pi, weight, q])")
-        if getattr(self.engine, "record_surprise", False):
-            logger.info(f"Process {self.pid}-{self.rank}: the records carry each recorded ply's policy surprise s "
-                        f"(items [move, value, pi, weight, q, s])")
-        if self.engine.forced_playouts:
-            logger.info(f"Process {self.pid}-{self.rank}: forced playouts k = {self.engine.forced_playouts} on full plies; "
-                        f"the recorded visit counts are pruned (policy target pruning)")
-        if getattr(self.engine, "gumbel", 0):
-            logger.info(f"Process {self.pid}-{self.rank}: Gumbel root search: {self.engine.gumbel} candidates, sequential "
-                        f"halving over {self.config.play.simulation_num_per_move} simulations, c_visit = "
-                        f"{self.engine.gumbel_visit}, c_scale = {self.engine.gumbel_scale}; no root noise, no temperature; "
-                        f"the recorded pi is softmax(log prior + sigma(completed Q))")
-        if getattr(self.engine, "gumbel_full", False):
-            logger.info(f"Process {self.pid}-{self.rank}: full Gumbel search: below the root argmax pi'(a) - N(a) / (1 + sum N) "
-                        f"replaces PUCT, unvisited moves are completed with v_mix")
-        if getattr(self.engine, "leaf_mirror", 0.0):           # (config.engine.leaf_mirror, set by the engine as well)
-            logger.info(f"Process {self.pid}-{self.rank}: random leaf mirror: a new leaf is evaluated as its left-right "
-                        f"mirror image with probability {self.engine.leaf_mirror}")
-        if getattr(self.engine, "solver", False):              # (config.engine.solver, likewise)
-            logger.info(f"Process {self.pid}-{self.rank}: MCTS solver: forced wins and losses are proven in the tree; a "
-                        f"decided root is not searched further, a won root plays the winning move")
-        if getattr(self.engine, "kld_gain", 0.0):              # (config.engine.kld_gain, likewise)
-            logger.info(f"Process {self.pid}-{self.rank}: KLD-gain stop: a ply's search ends once its root visit "
-                        f"distribution gains less than {self.engine.kld_gain:g} per simulation, measured every "
-                        f"{self.engine.kld_interval} root visits")
-        if getattr(self.engine, "eval_cache", 0):              # (config.engine.eval_cache, likewise)
-            logger.info(f"Process {self.pid}-{self.rank}: evaluation cache: 2^{self.engine.eval_cache} entries, "
-                        f"{self.engine.search.memory_info()['eval_cache_bytes'] >> 20} MiB, kept across games")
+        # (the search options of config.engine are likewise set by the engine: one line for each that is on)
+        for line in search_options.describe(vars(self.engine), self.config.play.simulation_num_per_move):
+            logger.info(f"Process {self.pid}-{self.rank}: {line}")
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:

@@ -526,6 +526,50 @@ int cz_search_policy_logits(cz_search* s, int on)
     return CZ_OK;
 }
 
+// ---- features that cannot run beside each other (include/czero.h has the matrix and the reasons) -------------------------
+// Host only.  A refused setter names the first excluder that is on, in this order; each phrase stands here once.
+// cchess_alphazero/search_options.py states the same pairs for the layers above (tests/test_gpu_search_options.py).
+enum Feature : int { F_FORCED, F_CAP, F_GUMBEL, F_SOLVER, F_KLD, F_LEAD, F_CACHE, F_COUNT };
+constexpr unsigned fbit(Feature f) { return 1u << f; }
+constexpr struct { bool (*on)(const cz_search*); const char* phrase; unsigned excludes; } FEATURES[F_COUNT] = {
+    {[](const cz_search* s) { return s->P.forced_k > 0.0; }, "forced playouts are on (cz_search_set_forced_playouts)",
+     fbit(F_GUMBEL) | fbit(F_SOLVER)},
+    {[](const cz_search* s) { return s->P.fast_sims > 0; }, "the playout cap is on (cz_search_set_playout_cap)", fbit(F_GUMBEL)},
+    {[](const cz_search* s) { return s->P.gumbel_m > 0; }, "the Gumbel root search is on (cz_search_set_gumbel)",
+     fbit(F_FORCED) | fbit(F_CAP) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+    {[](const cz_search* s) { return s->P.solver != 0; }, "the MCTS solver is on (cz_search_set_solver)",
+     fbit(F_FORCED) | fbit(F_GUMBEL) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE)},
+    {[](const cz_search* s) { return s->S.gain > 0.0; }, "the KLD-gain stop is on (cz_search_set_kld_gain)",
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE)},
+    {[](const cz_search* s) { return s->S.lead != 0; }, "the unreachable-lead stop is on (cz_search_set_smart_pruning)",
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE)},
+    {[](const cz_search* s) { return s->C.tab != nullptr; }, "the evaluation cache is on (cz_search_set_eval_cache)",
+     fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+};
+constexpr bool features_symmetric()
+{
+    for (int a = 0; a < F_COUNT; ++a)
+        for (int b = 0; b <= a; ++b)
+            if ((FEATURES[a].excludes >> b & 1) != (a == b ? 0 : FEATURES[b].excludes >> a & 1)) return false;
+    return true;
+}
+static_assert(features_symmetric(), "the exclusion matrix is symmetric and no feature excludes itself");
+
+// What a setter of feature f does between its argument checks and its assignment.  Switching on is refused beside an excluder:
+// CZ_ERR_ARG, "<entry>: <phrase of the first one that is on>".  Then the stream is idle: launches in flight keep the setting
+// (the table) they started with.
+static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream)
+{
+    for (int o = 0; on && o < F_COUNT; ++o)
+        if ((FEATURES[f].excludes >> o & 1) && FEATURES[o].on(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "%s: %s", entry, FEATURES[o].phrase);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip(entry, e);
+}
+
 // ---- evaluation cache (include/czero.h; csrc/xq_evalcache.h has the layout and who touches the table when) ----
 static_assert(CZ_EVAL_CACHE_STRIDE == EC_STRIDE && CZ_EVAL_CACHE_MIN_LOG2 == EC_MIN_LOG2 && CZ_EVAL_CACHE_MAX_LOG2 == EC_MAX_LOG2,
               "czero.h: evaluation cache");
@@ -555,15 +599,9 @@ int cz_search_set_eval_cache(cz_search* s, int log2_entries, void* stream)
         return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: refused with the 28-plane history input: its second plane block "
                                 "depends on the simulation's path and the game history, so the network input is not a "
                                 "function of the position");
-    if (log2_entries != 0 && s->P.solver)
-        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the MCTS solver is on (cz_search_set_solver)");
-    if (log2_entries != 0 && s->S.gain > 0.0)
-        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the KLD-gain stop is on (cz_search_set_kld_gain)");
-    if (log2_entries != 0 && s->S.lead)
-        return serr(CZ_ERR_ARG, "cz_search_set_eval_cache: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
+    if (const int rc = admit(s, F_CACHE, log2_entries != 0, "cz_search_set_eval_cache", stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipStreamSynchronize(st);             // no launch that holds the old table is still running
-    if (e != hipSuccess) return serr_hip("cz_search_set_eval_cache", e);
+    hipError_t e = hipSuccess;
     if (s->C.tab && log2_entries == s->C.log2) return cz_search_eval_cache_clear(s, stream);
     const size_t G = (size_t)s->P.G, slots = G * (size_t)s->P.K;
     if (s->C.tab) {
@@ -751,10 +789,7 @@ int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, voi
         return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: fast_sims outside 0 .. simulation_num_per_move");
     if (fast_sims > 0 && !(full_rate >= 0.0 && full_rate <= 1.0))
         return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: full_rate outside [0, 1]");
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the schedule they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_playout_cap", e);
-    if (fast_sims > 0 && s->P.gumbel_m > 0)
-        return serr(CZ_ERR_ARG, "cz_search_set_playout_cap: the Gumbel root search is on (cz_search_set_gumbel)");
+    if (const int rc = admit(s, F_CAP, fast_sims > 0, "cz_search_set_playout_cap", stream)) return rc;
     s->P.fast_sims = fast_sims;
     s->P.full_rate = fast_sims > 0 ? full_rate : 0.0;
     return CZ_OK;
@@ -768,12 +803,7 @@ int cz_search_set_forced_playouts(cz_search* s, double k, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: null handle");
     if (!finite_nonneg(k)) return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: k negative or not finite");
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_forced_playouts", e);
-    if (k > 0.0 && s->P.gumbel_m > 0)
-        return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: the Gumbel root search is on (cz_search_set_gumbel)");
-    if (k > 0.0 && s->P.solver)
-        return serr(CZ_ERR_ARG, "cz_search_set_forced_playouts: the MCTS solver is on (cz_search_set_solver)");
+    if (const int rc = admit(s, F_FORCED, k > 0.0, "cz_search_set_forced_playouts", stream)) return rc;
     s->P.forced_k = k;
     return CZ_OK;
 }
@@ -796,16 +826,7 @@ int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, vo
     if (m < 0 || m > GUMBEL_MAX_M) return serr(CZ_ERR_ARG, "cz_search_set_gumbel: m outside 0 .. 128");
     if (!finite_nonneg(c_visit) || !finite_nonneg(c_scale))
         return serr(CZ_ERR_ARG, "cz_search_set_gumbel: c_visit or c_scale negative or not finite");
-    if (m > 0 && (s->P.forced_k > 0.0 || s->P.fast_sims > 0))
-        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: forced playouts or the playout cap are on, each defines its own root rule");
-    if (m > 0 && s->P.solver)
-        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the MCTS solver is on (cz_search_set_solver)");
-    if (m > 0 && s->S.gain > 0.0)
-        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the KLD-gain stop is on (cz_search_set_kld_gain)");
-    if (m > 0 && s->S.lead)
-        return serr(CZ_ERR_ARG, "cz_search_set_gumbel: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_gumbel", e);
+    if (const int rc = admit(s, F_GUMBEL, m > 0, "cz_search_set_gumbel", stream)) return rc;
     s->P.gumbel_m = m;
     s->P.gumbel_visit = c_visit;
     s->P.gumbel_scale = c_scale;
@@ -821,18 +842,7 @@ int cz_search_set_solver(cz_search* s, int on, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_set_solver: null handle");
     if (on != 0 && on != 1) return serr(CZ_ERR_ARG, "cz_search_set_solver: on is neither 0 nor 1");
-    if (on && s->P.gumbel_m > 0)
-        return serr(CZ_ERR_ARG, "cz_search_set_solver: the Gumbel root search is on (cz_search_set_gumbel)");
-    if (on && s->P.forced_k > 0.0)
-        return serr(CZ_ERR_ARG, "cz_search_set_solver: forced playouts are on (cz_search_set_forced_playouts)");
-    if (on && s->C.tab)
-        return serr(CZ_ERR_ARG, "cz_search_set_solver: the evaluation cache is on (cz_search_set_eval_cache)");
-    if (on && s->S.gain > 0.0)
-        return serr(CZ_ERR_ARG, "cz_search_set_solver: the KLD-gain stop is on (cz_search_set_kld_gain)");
-    if (on && s->S.lead)
-        return serr(CZ_ERR_ARG, "cz_search_set_solver: the unreachable-lead stop is on (cz_search_set_smart_pruning)");
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_solver", e);
+    if (const int rc = admit(s, F_SOLVER, on != 0, "cz_search_set_solver", stream)) return rc;
     s->P.solver = on;
     return CZ_OK;
 }
@@ -903,29 +913,12 @@ static int stop_state_update(cz_search* s, hipStream_t st, const char* what)
     return CZ_OK;
 }
 
-// what a stop rule excludes, named for `who`; nullptr = nothing in the way
-static const char* stop_excluded(const cz_search* s)
-{
-    if (s->P.gumbel_m > 0) return "the Gumbel root search is on (cz_search_set_gumbel)";
-    if (s->P.solver) return "the MCTS solver is on (cz_search_set_solver)";
-    if (s->C.tab) return "the evaluation cache is on (cz_search_set_eval_cache)";
-    return nullptr;
-}
-
 int cz_search_set_kld_gain(cz_search* s, double gain, int interval, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: null handle");
     if (!finite_nonneg(gain)) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: gain negative or not finite");
     if (interval < 1) return serr(CZ_ERR_ARG, "cz_search_set_kld_gain: interval < 1");
-    if (gain > 0.0) {
-        if (const char* why = stop_excluded(s)) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "cz_search_set_kld_gain: %s", why);
-            return serr(CZ_ERR_ARG, buf);
-        }
-    }
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_kld_gain", e);
+    if (const int rc0 = admit(s, F_KLD, gain > 0.0, "cz_search_set_kld_gain", stream)) return rc0;
     const double old_gain = s->S.gain;
     const int old_interval = s->S.interval;
     s->S.gain = gain;
@@ -939,15 +932,7 @@ int cz_search_set_smart_pruning(cz_search* s, int on, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_set_smart_pruning: null handle");
     if (on != 0 && on != 1) return serr(CZ_ERR_ARG, "cz_search_set_smart_pruning: on is neither 0 nor 1");
-    if (on) {
-        if (const char* why = stop_excluded(s)) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "cz_search_set_smart_pruning: %s", why);
-            return serr(CZ_ERR_ARG, buf);
-        }
-    }
-    hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the setting they started with
-    if (e != hipSuccess) return serr_hip("cz_search_set_smart_pruning", e);
+    if (const int rc0 = admit(s, F_LEAD, on != 0, "cz_search_set_smart_pruning", stream)) return rc0;
     const int old = s->S.lead;
     s->S.lead = on;
     const int rc = stop_state_update(s, (hipStream_t)stream, "cz_search_set_smart_pruning");

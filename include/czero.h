@@ -176,6 +176,20 @@ int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id
  * CZ_ERR_ARG: n < 0, n > CZ_BOOK_MAX, boards NULL with n > 0, rate outside [0, 1] -- the object keeps its book. */
 int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, void* stream);
 
+/* FEATURES THAT CANNOT RUN BESIDE EACH OTHER.  Seven of the setters below switch on a feature that some of the others
+ * exclude, because each defines its own root rule or, for the evaluation cache, has a kernel instantiation of its own:
+ *
+ *     Gumbel root search   not beside  the playout cap, forced playouts, the MCTS solver, the KLD-gain stop, the lead stop
+ *     MCTS solver          not beside  the Gumbel root search, forced playouts, the evaluation cache, the two stop rules
+ *     evaluation cache     not beside  the MCTS solver, the KLD-gain stop, the unreachable-lead stop
+ *
+ * The relation is symmetric (11 pairs) and everything else composes, the two stop rules with each other included.  A
+ * setter that would switch its feature ON beside one that excludes it returns CZ_ERR_ARG, changes nothing, and
+ * cz_last_error names its entry point and the first excluder that is on, looked for in the order forced playouts, playout
+ * cap, Gumbel root search, MCTS solver, KLD-gain stop, unreachable-lead stop, evaluation cache.  Switching OFF is never
+ * refused.  Each of these setters checks in one order: the handle, its arguments' ranges, the exclusions, then it
+ * synchronises the stream and assigns. */
+
 /* Playout cap randomization of self-play (KataGo: Wu 2019, section 3.1; the reference has no such option).  With
  * fast_sims > 0 every ply of every self-play game is either a FULL search -- simulation_num_per_move simulations, root
  * noise as configured: what every ply is without this call -- or a FAST one: fast_sims simulations and NO root noise
@@ -192,7 +206,8 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * bits it produced before.  Self-play only: external mode (cz_search_set_roots) never looks at it.  Call it before
  * cz_search_start_selfplay and before a graph capture (the captured launches hold the parameters), like
  * cz_search_set_book; synchronises the stream.  CZ_ERR_ARG: fast_sims < 0 or > simulation_num_per_move, full_rate
- * outside [0, 1] with fast_sims > 0 -- the object keeps its setting; cz_search_set_sims below fast_sims is refused. */
+ * outside [0, 1] with fast_sims > 0, an excluder is on (above) -- the object keeps its setting; cz_search_set_sims below
+ * fast_sims is refused. */
 int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, void* stream);
 
 /* Forced playouts and policy target pruning (KataGo: Wu 2019, section 3.2, the companion of the playout cap; the
@@ -237,8 +252,8 @@ int cz_search_set_playout_cap(cz_search* s, int fast_sims, double full_rate, voi
  * added.
  *
  * Call it before cz_search_start_selfplay and before a graph capture (the captured launches hold the parameters), like
- * cz_search_set_playout_cap; synchronises the stream.  CZ_ERR_ARG: s NULL, k < 0 or not finite -- the object keeps its
- * setting. */
+ * cz_search_set_playout_cap; synchronises the stream.  CZ_ERR_ARG: s NULL, k < 0 or not finite, k > 0 beside an excluder
+ * (FEATURES THAT CANNOT RUN BESIDE EACH OTHER, above) -- the object keeps its setting. */
 int cz_search_set_forced_playouts(cz_search* s, double k, void* stream);
 /* The pruned counts of every current root, as a visit entry of that root would hold them: n [G][128] int32 (0 past the
  * root's edges), raw_total [G] int32 = S, both DEVICE.  Same inputs as cz_search_root_stats; the bans are those of the
@@ -314,8 +329,9 @@ int cz_search_set_leaf_mirror(cz_search* s, double rate, uint8_t* flags_or_null,
  *
  * cz_search_set_eval_cache: log2_entries 0 switches it off and frees the table, otherwise CZ_EVAL_CACHE_MIN_LOG2 <=
  * log2_entries <= CZ_EVAL_CACHE_MAX_LOG2 (the size it has already: the table is emptied).  CZ_ERR_ARG: s NULL,
- * log2_entries outside that, or a search with 28 input planes (use_history: the second plane block depends on the
- * simulation's path and on the game history, so the input is not a function of the position).  CZ_ERR_NOMEM: the
+ * log2_entries outside that, a search with 28 input planes (use_history: the second plane block depends on the
+ * simulation's path and on the game history, so the input is not a function of the position), or log2_entries > 0 beside
+ * an excluder (FEATURES THAT CANNOT RUN BESIDE EACH OTHER, above).  CZ_ERR_NOMEM: the
  * allocation failed; the search stays usable with the cache off.  CZ_ERR_STATE: the table would go or change size while
  * leaves it answered wait for their attach -- change it between searches.  Call it after cz_search_create, before the
  * rounds and before a graph capture (the captured launches hold the table's address); synchronises the stream.
@@ -586,9 +602,8 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
  * surprise record keep their definitions over the recorded n[].
  *
  * cz_search_set_gumbel: 0 <= m <= CZ_GUMBEL_MAX_M, c_visit and c_scale finite and >= 0 (the paper: 50 and 1), CZ_ERR_ARG
- * otherwise and when m > 0 while forced playouts or the playout cap are on (each defines its own root rule; their
- * setters refuse likewise while m > 0).  Call it before cz_search_start_selfplay / cz_search_set_roots and before a
- * graph capture; synchronises the stream.  Device memory: 1540 bytes per game, allocated at cz_search_create. */
+ * otherwise and when m > 0 beside an excluder (FEATURES THAT CANNOT RUN BESIDE EACH OTHER, above).  Call it before
+ * cz_search_start_selfplay / cz_search_set_roots and before a graph capture; synchronises the stream.  Device memory: 1540 bytes per game, allocated at cz_search_create. */
 #define CZ_VISIT_GUMBEL 8u
 #define CZ_GUMBEL_MAX_M 128
 int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, void* stream);
@@ -699,10 +714,9 @@ int cz_gumbel_interior_pick(const int32_t* n, const double* w, const float* p, c
  * 24-25 of the edge's child word (node ids use 24 bits); the distances of marked children are read from their headers.
  * No memory is added.  The trees keep their proofs when the solver is switched off; the search then ignores them.
  *
- * cz_search_set_solver: on is 0 or 1; CZ_ERR_ARG otherwise, when s is NULL, and when on = 1 while the Gumbel root search,
- * forced playouts or the evaluation cache are on (each has a root rule or a kernel instantiation of its own; their setters
- * refuse likewise while the solver is on).  Call it before cz_search_start_selfplay / cz_search_set_roots and before a
- * graph capture; synchronises the stream. */
+ * cz_search_set_solver: on is 0 or 1; CZ_ERR_ARG otherwise, when s is NULL, and when on = 1 beside an excluder (FEATURES THAT
+ * CANNOT RUN BESIDE EACH OTHER, above).  Call it before cz_search_start_selfplay / cz_search_set_roots and before a graph
+ * capture; synchronises the stream. */
 #define CZ_PROOF_OPEN 0
 #define CZ_PROOF_WIN 1
 #define CZ_PROOF_LOSS 2
@@ -752,9 +766,8 @@ int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream);
  * cut: one device allocation (about 540 bytes per game) that exists exactly while a rule is on.
  *
  * cz_search_set_kld_gain: gain 0 switches the rule off.  CZ_ERR_ARG: s NULL, gain negative or not finite, interval < 1,
- * and gain > 0 while the Gumbel root search, the MCTS solver or the evaluation cache is on (each has a root rule or a
- * kernel instantiation of its own; their setters refuse likewise while a stop rule is on).  cz_search_set_smart_pruning: on
- * is 0 or 1; refused likewise.  Switching a rule on while searches are under way treats them as begun at that moment.
+ * and gain > 0 beside an excluder (FEATURES THAT CANNOT RUN BESIDE EACH OTHER, above).  cz_search_set_smart_pruning: on is 0
+ * or 1; refused likewise.  Switching a rule on while searches are under way treats them as begun at that moment.
  * Call them before cz_search_start_selfplay / cz_search_set_roots and before a graph capture; they synchronise the stream. */
 #define CZ_VISIT_EARLY 16u
 int cz_search_set_kld_gain(cz_search* s, double gain, int interval, void* stream);
