@@ -68,6 +68,8 @@ def _nn_signatures():
         "cz_tower_plain": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "cz_tower_pairs": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "cz_heads_tail": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp, vp]),
+        "cz_heads_tail_wdl": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp,
+                                    vp, i32, i32, i32, vp, vp]),
         "cz_fc_packed_elems": (sz, [i32, i32]),
         "cz_fc_pack_weights": (i32, [vp, i32, i32, i32, vp]),
     }
@@ -122,6 +124,10 @@ def _declare(L):
         L.cz_policy_value_loss_w.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, C.c_float, vp, i32,
                                              C.c_float, C.c_float, vp, vp, vp, vp, vp]
         L.cz_policy_value_loss_w.restype = i32
+    if hasattr(L, "cz_policy_wdl_loss"):
+        L.cz_policy_wdl_loss.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, C.c_float,
+                                         C.c_float, vp, vp, vp, vp, vp, vp]
+        L.cz_policy_wdl_loss.restype = i32
     if hasattr(L, "cz_search_create"):
         from . import _native_search
         _native_search.declare(L)
@@ -339,6 +345,35 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
                                      _dev(pl, torch.float32), _dev(se, torch.float32), _dev(gl, torch.float32),
                                      _dev(gv, torch.float32), _stream()), "cz_policy_value_loss")
     return pl, se, gl, gv
+
+
+def policy_wdl_loss(logits, vlogits, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0,
+                    mirror=None, row_w=None):
+    """policy_value_loss for a network with a win / draw / loss value head (cz_policy_wdl_loss): vlogits [B, 3] float32, the
+    value head's logits in the order (win, draw, loss).  Returns (pl, ce, se, gl, gv): the per-row policy loss, the value
+    cross-entropy against the class of z (win z > 0, draw z == 0, loss z < 0), the squared error of p_W - p_L against z,
+    and the gradients of w_p mean(pl) + w_v mean(ce) with respect to the logits [B, 2086] and the value logits [B, 3].
+    mirror / row_w / the visit arrays as in policy_value_loss; there is no q: a scalar does not determine a distribution."""
+    import torch
+    require_gpu()
+    assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
+        and logits.stride(1) == 1
+    b, dev = logits.shape[0], logits.device
+    assert tuple(vlogits.shape) == (b, 3), tuple(vlogits.shape)
+    assert row_w is None or row_w.shape == z.shape, (tuple(row_w.shape), tuple(z.shape))
+    pl = torch.empty((b,), dtype=torch.float32, device=dev)
+    ce = torch.empty((b,), dtype=torch.float32, device=dev)
+    se = torch.empty((b,), dtype=torch.float32, device=dev)
+    gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
+    gv = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    check(lib().cz_policy_wdl_loss(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(vlogits, torch.float32),
+                                   _dev(idx, torch.int32), None if mirror is None else _flags(mirror, b), b, played.shape[0],
+                                   _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16), _opt(vis_count, torch.int32),
+                                   0 if vis_label is None else vis_label.shape[0], _dev(played, torch.uint16),
+                                   _dev(z, torch.float32), _opt(row_w, torch.float32), int(mode), float(w_p), float(w_v),
+                                   _dev(pl, torch.float32), _dev(ce, torch.float32), _dev(se, torch.float32),
+                                   _dev(gl, torch.float32), _dev(gv, torch.float32), _stream()), "cz_policy_wdl_loss")
+    return pl, ce, se, gl, gv
 
 
 def check_or_catch(boards, moves):
@@ -573,6 +608,24 @@ def heads_tail(policy_feat, value_feat, wp, bias_p, w1, bias1, w2, b2, policy, v
                               _ptr(value_feat), value_feat.shape[1], _ptr(w1), _ptr(bias1), bias1.shape[0], _ptr(w2),
                               float(b2), _ptr(policy), _ptr(value), _ptr(stats), n, _dt_code(wp.dtype), int(bool(normalize)),
                               _ptr(count) if count is not None else None, _stream()), "cz_heads_tail")
+    return policy, value
+
+
+def heads_tail_wdl(policy_feat, value_feat, wp, bias_p, w1, bias1, w2, b2, policy, value, stats, wdl=None, count=None,
+                   normalize=True):
+    """heads_tail for a win / draw / loss value head (cz_heads_tail_wdl): w2 fp32 [3, n_hidden] on the device, b2 three
+    floats, classes in the order (win, draw, loss).  value [N] = P(win) - P(loss); wdl: optional fp32 [N, 3] that receives
+    the three probabilities.  count / normalize as in heads_tail."""
+    require_gpu()
+    n = policy_feat.shape[0]
+    assert tuple(w2.shape) == (3, bias1.shape[0]) and w2.is_contiguous() and len(b2) == 3, (tuple(w2.shape), b2)
+    assert wdl is None or (tuple(wdl.shape) == (n, 3) and wdl.is_contiguous()), None if wdl is None else tuple(wdl.shape)
+    check(lib().cz_heads_tail_wdl(_ptr(policy_feat), policy_feat.shape[1], _ptr(wp), _ptr(bias_p), policy.shape[1],
+                                  _ptr(value_feat), value_feat.shape[1], _ptr(w1), _ptr(bias1), bias1.shape[0], _ptr(w2),
+                                  float(b2[0]), float(b2[1]), float(b2[2]), _ptr(policy), _ptr(value),
+                                  _ptr(wdl) if wdl is not None else None, _ptr(stats), n, _dt_code(wp.dtype),
+                                  int(bool(normalize)), _ptr(count) if count is not None else None, _stream()),
+          "cz_heads_tail_wdl")
     return policy, value
 
 

@@ -5,6 +5,8 @@ Topology (channels-first, Keras names in brackets): Conv5x5(F) [input_conv] -> B
 N x [Conv3x3 -> BN -> ReLU -> Conv3x3 -> BN -> +skip -> ReLU] -> policy: Conv1x1(4) -> BN -> ReLU ->
 Flatten(C,H,W) -> Dense(2086) softmax; value: Conv1x1(2) -> BN -> ReLU -> Flatten -> Dense(256) ReLU ->
 Dense(1) tanh.  Convs have no bias; BN eps = 1e-3 (Keras default, data/model/*.json).
+value_outputs=3 replaces the value head's end by Dense(3) softmax over (win, draw, loss) for the side to move; the value
+every consumer reads is then P(win) - P(loss).
 
 ``InferenceNet`` is the eval-mode form used by self-play: BatchNorm folded into the convolutions and, with
 trunk="mfma" (the default), every layer on hand-written HIP kernels (csrc/xq_conv.hip, xq_nn_epilogue.hip,
@@ -45,12 +47,17 @@ class CChessNet(nn.Module):
     """Trainable form (BatchNorm layers kept); mirrors CChessModel.build(), model.py:32-66."""
 
     def __init__(self, cnn_filter_num=256, cnn_first_filter_size=5, cnn_filter_size=3, res_layer_num=7,
-                 value_fc_size=256, input_depth=14, policy_filters=4, value_filters=2, n_labels=N_LABELS):
+                 value_fc_size=256, input_depth=14, policy_filters=4, value_filters=2, n_labels=N_LABELS,
+                 value_outputs=1):
+        """value_outputs: 1 = the reference's scalar tanh value head, 3 = a win / draw / loss head (Dense(3) + softmax)."""
         super().__init__()
+        if value_outputs not in (1, 3):
+            raise ValueError(f"value_outputs={value_outputs!r}: 1 (scalar tanh head) or 3 (win / draw / loss head)")
         self.cfg = dict(cnn_filter_num=cnn_filter_num, cnn_first_filter_size=cnn_first_filter_size,
                         cnn_filter_size=cnn_filter_size, res_layer_num=res_layer_num,
                         value_fc_size=value_fc_size, input_depth=input_depth,
-                        policy_filters=policy_filters, value_filters=value_filters, n_labels=n_labels)
+                        policy_filters=policy_filters, value_filters=value_filters, n_labels=n_labels,
+                        value_outputs=value_outputs)
         f = cnn_filter_num
         self.input_conv = nn.Conv2d(input_depth, f, cnn_first_filter_size, padding=cnn_first_filter_size // 2,
                                     bias=False)
@@ -62,7 +69,11 @@ class CChessNet(nn.Module):
         self.value_conv = nn.Conv2d(f, value_filters, 1, bias=False)
         self.value_bn = nn.BatchNorm2d(value_filters, eps=BN_EPS, momentum=0.01)
         self.value_dense = nn.Linear(value_filters * 90, value_fc_size)
-        self.value_out = nn.Linear(value_fc_size, 1)
+        self.value_out = nn.Linear(value_fc_size, value_outputs)
+
+    @property
+    def wdl_head(self):
+        return self.value_out.out_features == 3
 
     def trunk(self, x):
         x = F.relu(self.input_bn(self.input_conv(x)))
@@ -72,21 +83,35 @@ class CChessNet(nn.Module):
 
     def forward(self, x, logits=False):
         """-> (policy [B, 2086], value [B]); logits=True returns the policy head's logits instead of its softmax (the
-        trainer's loss, worker/optimize.py, takes the logits)."""
+        trainer's loss, worker/optimize.py, takes the logits).  A win / draw / loss net (value_outputs=3): value [B] =
+        P(win) - P(loss), and with logits=True the value head's three logits [B, 3] as well."""
         x = self.trunk(x)
         p = F.relu(self.policy_bn(self.policy_conv(x)))
         p = self.policy_out(p.flatten(1))                      # Flatten order C,H,W (channels_first)
         v = F.relu(self.value_bn(self.value_conv(x)))
         v = F.relu(self.value_dense(v.flatten(1)))
-        v = torch.tanh(self.value_out(v))
+        v = self.value_out(v)
+        if self.wdl_head:
+            if logits:
+                return p, v
+            w = F.softmax(v, dim=1)
+            return F.softmax(p, dim=1), w[:, 0] - w[:, 2]
+        v = torch.tanh(v)
         return (p if logits else F.softmax(p, dim=1)), v.squeeze(1)
+
+    def wdl(self, x):
+        """[B, 3] probabilities (win, draw, loss) for the side to move; a win / draw / loss net only."""
+        if not self.wdl_head:
+            raise RuntimeError("wdl(): this network has the scalar value head (value_outputs=1)")
+        return F.softmax(self.forward(x, logits=True)[1], dim=1)
 
     @classmethod
     def from_model_config(cls, mc):
         """mc: the reference's ModelConfig object (configs/*.py)."""
         return cls(cnn_filter_num=mc.cnn_filter_num, cnn_first_filter_size=mc.cnn_first_filter_size,
                    cnn_filter_size=mc.cnn_filter_size, res_layer_num=mc.res_layer_num,
-                   value_fc_size=mc.value_fc_size, input_depth=getattr(mc, "input_depth", 14))
+                   value_fc_size=mc.value_fc_size, input_depth=getattr(mc, "input_depth", 14),
+                   value_outputs=getattr(mc, "value_outputs", 1))
 
 
 def _fold(conv, bn):
@@ -295,7 +320,8 @@ class InferenceNet(nn.Module):
             self.value_conv = _fold(net.value_conv, net.value_bn)
             self.policy_out = nn.Linear(net.policy_out.in_features, net.policy_out.out_features)
             self.value_dense = nn.Linear(net.value_dense.in_features, net.value_dense.out_features)
-            self.value_out = nn.Linear(net.value_out.in_features, 1)
+            self.value_out = nn.Linear(net.value_out.in_features, net.value_out.out_features)
+            self.wdl_head = net.value_out.out_features == 3
             self.policy_out.load_state_dict(net.policy_out.state_dict())
             self.value_dense.load_state_dict(net.value_dense.state_dict())
             self.value_out.load_state_dict(net.value_out.state_dict())
@@ -370,8 +396,11 @@ class InferenceNet(nn.Module):
                            self.policy_out.bias.detach().float().clone(),
                            _native.pack_fc_weights(self.value_dense.weight, tail_dt),
                            self.value_dense.bias.detach().float().clone(),
-                           self.value_out.weight.detach().float().reshape(-1).clone())
-        self._tail_b2 = float(self.value_out.bias.detach().float().item())
+                           # (scalar head: [n_hidden]; win / draw / loss head: [3, n_hidden], cz_heads_tail_wdl)
+                           self.value_out.weight.detach().float().clone() if self.wdl_head
+                           else self.value_out.weight.detach().float().reshape(-1).clone())
+        self._tail_b2 = ([float(b) for b in self.value_out.bias.detach().float()] if self.wdl_head
+                         else float(self.value_out.bias.detach().float().item()))
         self._head_w = torch.cat([self.policy_conv.weight.detach().float().flatten(1),
                                   self.value_conv.weight.detach().float().flatten(1)]).contiguous()
         self._head_b = torch.cat([self.policy_conv.bias.detach().float(), self.value_conv.bias.detach().float()])
@@ -638,14 +667,32 @@ class InferenceNet(nn.Module):
                 self.policy_out.in_features in (180, 360) and self.value_dense.in_features in (180, 360))
 
     @torch.no_grad()
-    def forward(self, planes, rows=None, count=None, out=None, logits=False, masks=None):
+    def _value(self, hidden, out=None, wdl=None):
+        """The torch tails' value from the hidden layer: tanh(Dense(1)), or for a win / draw / loss head P(win) - P(loss) of
+        the three-way softmax (wdl, if given, receives the probabilities).  out: the [n] tensor to write."""
+        v = self.value_out(hidden).float()
+        if self.wdl_head:
+            w = torch.softmax(v, dim=1)
+            if wdl is not None:
+                wdl.copy_(w)
+            v = w[:, 0] - w[:, 2]
+            return v if out is None else out.copy_(v)
+        if wdl is not None:
+            raise RuntimeError("wdl=: this network has the scalar value head")
+        return torch.tanh(v).squeeze(1) if out is None else torch.tanh(v, out=out.view(-1, 1))
+
+    def forward(self, planes, rows=None, count=None, out=None, logits=False, masks=None, wdl=None):
         """planes: the evaluation queue.  rows / count (int32 cuda tensors, cz_search_round_q): evaluate only the
         boards planes[rows[i]], i < count -- the result rows are indexed by i; rows beyond count are undefined.
         out = (policy [n, 2086] fp32, value [n] fp32): write the results there (the engine's queue tensors) instead of
         into fresh tensors.  logits=True (hand-written tail only; see supports_logits): the policy rows are left as raw
         logits -- for a search object in policy_logits mode, which needs the legal moves' entries only.
         masks (int32 [n, 96], Search.leaf_masks): the same positions as occupancy boards; the fused input layer of the first
-        residual block takes them instead of scanning the planes (ignored on every other path)."""
+        residual block takes them instead of scanning the planes (ignored on every other path).
+        wdl (fp32 [n, 3], win / draw / loss networks only): receives the value head's probabilities; out[1] stays the [n]
+        value P(win) - P(loss) the search reads."""
+        if wdl is not None and not self.wdl_head:
+            raise RuntimeError("wdl=: this network has the scalar value head")
         if logits and not self.supports_logits():
             raise RuntimeError("logits=True needs the hand-written dense tail")
         if rows is not None and not self.supports_compact_queue():
@@ -673,6 +720,12 @@ class InferenceNet(nn.Module):
                     key = ("tail_stats", str(planes.device))          # scratch for the rows' (max, sum): grown, never per size
                     if key not in self._bufs or self._bufs[key].shape[0] < n:
                         self._bufs[key] = torch.empty((n, 2), dtype=torch.float32, device=planes.device)
+                    if self.wdl_head:
+                        _native.heads_tail_wdl(pf, vf, self.tail_wp.view(self._tail_dtype), self.tail_bp,
+                                               self.tail_w1.view(self._tail_dtype), self.tail_b1, self.tail_w2,
+                                               self._tail_b2, out[0], out[1], self._bufs[key], wdl=wdl, count=count,
+                                               normalize=not logits)
+                        return out
                     _native.heads_tail(pf, vf, self.tail_wp.view(self._tail_dtype), self.tail_bp,
                                        self.tail_w1.view(self._tail_dtype), self.tail_b1, self.tail_w2,
                                        self._tail_b2, out[0], out[1], self._bufs[key], count=count, normalize=not logits)
@@ -681,10 +734,9 @@ class InferenceNet(nn.Module):
                 v = F.relu(self.value_dense(vf.to(self.dtype)))
                 if out is not None:                            # straight into the search object's queue tensors
                     torch.softmax(p.float(), dim=1, out=out[0])
-                    torch.tanh(self.value_out(v).float(), out=out[1].view(-1, 1))
+                    self._value(v, out[1], wdl)
                     return out
-                v = torch.tanh(self.value_out(v).float())
-                return F.softmax(p.float(), dim=1), v.squeeze(1)
+                return F.softmax(p.float(), dim=1), self._value(v, None, wdl)
             # (other head widths -- CChessNet(policy_filters=..., value_filters=...), keras_io: the fused input layer still
             #  reads the occupancy boards where the engine has switched the planes off: takes_masks)
             last = self._trunk_mfma(planes, rows=rows, count=count, masks=masks)
@@ -702,8 +754,7 @@ class InferenceNet(nn.Module):
         p = self.policy_out(p.flatten(1))                # flatten of an NCHW-shaped tensor: C,H,W order
         v = F.relu(self.value_conv(x))
         v = F.relu(self.value_dense(v.flatten(1)))
-        v = torch.tanh(self.value_out(v).float())
-        return F.softmax(p.float(), dim=1), v.squeeze(1)
+        return F.softmax(p.float(), dim=1), self._value(v, None, wdl)
 
 
 # ---- load-time guard of the reduced tower arithmetics -------------------------------------------------------------
@@ -781,11 +832,12 @@ def calibration_planes(n=CALIBRATION_POSITIONS, input_depth=14, device=None, see
 
 
 @torch.no_grad()
-def reference_forward_f64(net: CChessNet, planes, with_activations=False):
+def reference_forward_f64(net: CChessNet, planes, with_activations=False, with_wdl=False):
     """The reference network (agent/model.py:32-83; BatchNorm in inference mode as Keras predict_on_batch runs it) in float64
     on the device of `planes`: (policy [n, 2086], value [n], logits) and, on request, two more entries: max |activation|
     of every tower tensor (input layer, each block's intermediate and output) and the [1 %, 50 %] quantiles of its nonzero
-    values."""
+    values.  with_wdl (a win / draw / loss net): one further entry at the end, the value head's probabilities [n, 3]; the
+    value is P(win) - P(loss) either way."""
     import copy
     dev = planes.device
     ref = copy.deepcopy(net).eval().double().to(dev)
@@ -822,9 +874,17 @@ def reference_forward_f64(net: CChessNet, planes, with_activations=False):
     p = F.relu(bn(ref.policy_bn, conv(ref.policy_conv, x)))
     logits = ref.policy_out(p.flatten(1))
     v = F.relu(bn(ref.value_bn, conv(ref.value_conv, x)))
-    v = torch.tanh(ref.value_out(F.relu(ref.value_dense(v.flatten(1))))).squeeze(1)
+    v = ref.value_out(F.relu(ref.value_dense(v.flatten(1))))
+    w = None
+    if ref.wdl_head:                                # the value the search reads: P(win) - P(loss)
+        w = F.softmax(v, dim=1)
+        v = w[:, 0] - w[:, 2]
+    else:
+        v = torch.tanh(v).squeeze(1)
     out = (F.softmax(logits, dim=1), v, logits)
-    return out + (acts, small) if with_activations else out
+    if with_activations:
+        out = out + (acts, small)
+    return out + (w,) if with_wdl else out
 
 
 def legal_priors(p, legal):
@@ -1081,7 +1141,8 @@ def flops_per_position(cfg):
     f, k1, k, n = cfg["cnn_filter_num"], cfg["cnn_first_filter_size"], cfg["cnn_filter_size"], cfg["res_layer_num"]
     mac = cfg["input_depth"] * f * k1 * k1 * 90 + 2 * n * f * f * k * k * 90
     mac += f * cfg["policy_filters"] * 90 + cfg["policy_filters"] * 90 * cfg.get("n_labels", N_LABELS)
-    mac += f * cfg["value_filters"] * 90 + cfg["value_filters"] * 90 * cfg["value_fc_size"] + cfg["value_fc_size"]
+    mac += (f * cfg["value_filters"] * 90 + cfg["value_filters"] * 90 * cfg["value_fc_size"] +
+            cfg["value_fc_size"] * cfg.get("value_outputs", 1))
     return 2 * mac
 
 

@@ -165,7 +165,10 @@ class SelfPlayEngine:
         and the exception goes to the caller."""
         if self.evaluator is not None:
             raise RuntimeError("the engine was built on an evaluator callable, not on a network")
-        if net.cfg != self.model_cfg:
+        # (the value head's end is not part of what must match: each InferenceNet carries its own tail and hands the search
+        #  one scalar per leaf, so a scalar net may follow a win / draw / loss one and the other way round)
+        same = lambda cfg: {k: v for k, v in cfg.items() if k != "value_outputs"}
+        if same(net.cfg) != same(self.model_cfg):
             raise ValueError(f"hot reload: topology changed ({self.model_cfg} -> {net.cfg})")
         torch.cuda.synchronize(self.device)
         built = self._build_net(net)                           # may raise: nothing has been touched yet

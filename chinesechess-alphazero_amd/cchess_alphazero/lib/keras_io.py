@@ -92,6 +92,10 @@ def config_from_keras(keras_cfg):
     first = by_name[n["input_conv"]]
     if first.get("data_format", "channels_first") != "channels_first":
         raise KerasFormatError("only channels_first models are supported")
+    units = int(by_name[n["value_out"]].get("units", 1))
+    if units != 1:      # (a win / draw / loss head exists in this package's own model format only)
+        raise KerasFormatError(f"value head {n['value_out']!r} has {units} outputs: Keras-format models carry the scalar "
+                               "tanh value head only")
     block_conv = by_name[n["res"][0][0]] if n["res"] else first
     cfg = dict(cnn_filter_num=int(first["filters"]), cnn_first_filter_size=int(first["kernel_size"][0]),
                cnn_filter_size=int(block_conv["kernel_size"][0]), res_layer_num=len(n["res"]),

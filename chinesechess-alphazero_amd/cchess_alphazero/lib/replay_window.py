@@ -278,9 +278,20 @@ class ReplayWindow:
         ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m).  q_ratio L > 0: the value
         target is z + L (q - z) where the position has a q (cz_policy_value_loss_q), and the value loss is against it.
         surprise=True (a window with surprise_weight > 0): row r counts with the weight w[idx[r]] in the gradients
-        (cz_policy_value_loss_w) and in the returned means, mean(w[idx] * loss) -- still divided by B."""
+        (cz_policy_value_loss_w) and in the returned means, mean(w[idx] * loss) -- still divided by B.
+        v of shape [B, 3] -- the value logits of a win / draw / loss network (CChessNet(value_outputs=3)): the value loss is
+        the cross-entropy against the class of z (cz_policy_wdl_loss), and a fourth entry follows, the mean squared error
+        of P(win) - P(loss) against z: the number a scalar run reports.  q_ratio must be 0 then."""
         if surprise and self.w is None:
             raise ValueError("loss(surprise=True) needs a window built with surprise_weight > 0")
+        if v.dim() == 2:
+            if v.shape[1] != 3:
+                raise ValueError(f"value of shape {tuple(v.shape)}: [B] (scalar head) or [B, 3] (win / draw / loss logits)")
+            if q_ratio:
+                raise ValueError("q_ratio > 0 with a win / draw / loss value head: a scalar q does not determine a "
+                                 "distribution over win / draw / loss")
+            return _PolicyWdlLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
+                                        bool(surprise))
         return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
                                       float(q_ratio), bool(surprise))
 
@@ -342,3 +353,29 @@ class _PolicyValueLoss(torch.autograd.Function):
     def backward(ctx, g_total, _g_pm, _g_vm):
         gl, gv = ctx.saved_tensors
         return g_total * gl, g_total * gv, None, None, None, None, None, None, None, None
+
+
+class _PolicyWdlLoss(torch.autograd.Function):
+    """_PolicyValueLoss for the three value logits of a win / draw / loss head (cz_policy_wdl_loss): the value loss is the
+    cross-entropy; the fourth result is the mean squared error of P(win) - P(loss) against z."""
+
+    @staticmethod
+    def forward(ctx, logits, vlogits, idx, win, mode, w_p, w_v, mirror=None, surprise=False):
+        n = win.n
+        pl, ce, se, gl, gv = _native.policy_wdl_loss(
+            logits.detach(), vlogits.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
+            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
+            row_w=win.w[:n] if surprise else None)
+        ctx.save_for_backward(gl, gv)
+        if surprise:
+            wr = win.w[:n][idx.long()]
+            pm, vm, sm = (wr * pl).mean(), (wr * ce).mean(), (wr * se).mean()
+        else:
+            pm, vm, sm = pl.mean(), ce.mean(), se.mean()
+        ctx.mark_non_differentiable(pm, vm, sm)
+        return w_p * pm + w_v * vm, pm, vm, sm
+
+    @staticmethod
+    def backward(ctx, g_total, _g_pm, _g_vm, _g_sm):
+        gl, gv = ctx.saved_tensors
+        return g_total * gl, g_total * gv, None, None, None, None, None, None, None

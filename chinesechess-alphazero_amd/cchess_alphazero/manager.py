@@ -56,6 +56,11 @@ _FLAGS = [
     ("--augment", dict(choices=["none", "mirror"], default="none",
                        help="(opt) mirror: every training row of every epoch is the left-right mirrored position with "
                             "probability 1/2 (planes and policy targets, in the trainer's kernels)")),
+    ("--value-head", dict(choices=["scalar", "wdl"], default=None,
+                          help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
+                               "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
+                               "(default: what the best model has, scalar for a new one); refused when the best model has "
+                               "the other head")),
 ] + search_options.flags()
 
 
@@ -107,6 +112,12 @@ def build_config(args):
     if not 0.0 <= args.surprise_weight <= 1.0:
         raise SystemExit(f"--surprise-weight {args.surprise_weight}: expected 0 <= A <= 1")
     config.trainer.surprise_weight = args.surprise_weight
+    if args.value_head is not None and args.cmd != "opt":
+        raise SystemExit("--value-head is an option of `run.py opt`")
+    if args.value_head == "wdl" and args.q_ratio > 0.0:
+        raise SystemExit(f"--q-ratio {args.q_ratio:g} with --value-head wdl: a scalar q does not determine a distribution "
+                         "over win / draw / loss")
+    config.trainer.value_head = args.value_head
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

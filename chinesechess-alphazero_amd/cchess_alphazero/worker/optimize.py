@@ -35,6 +35,14 @@ Deliberate deviations from the reference:
     logged training losses are the weighted means, still divided by the batch size; KataGo replicates rows in proportion
     to their weight instead, which this matches in expectation.  Validation is never weighted, so ``val`` stays
     comparable between runs with different A.  Fast plies keep the weight 0 (KataGo gives them a surprise-based one);
+  - ``--value-head wdl`` (default: the head the best model has; a new model gets the reference's scalar head) trains a
+    network whose value head ends in Dense(3) + softmax over (win, draw, loss) for the side to move
+    (``CChessNet(value_outputs=3)``).  Its value loss is the cross-entropy of the three logits against the class of the
+    game result z (``cz_policy_wdl_loss``), which is what ``value`` / ``val_value`` then report; every epoch adds
+    ``val_value_z``, the squared error of P(win) - P(loss) against z (the number a scalar run reports), and the mean
+    predicted draw probability on the validation rows beside their share of drawn results.  ``--q-ratio`` is refused
+    with such a model: a scalar q does not determine a distribution.  The flag is refused when it contradicts the best
+    model's head;
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -132,6 +140,10 @@ class OptimizeWorker:
         self.surprise_weight = float(getattr(config.trainer, "surprise_weight", 0.0))
         if not 0.0 <= self.surprise_weight <= 1.0:
             raise ValueError(f"trainer.surprise_weight={self.surprise_weight!r}: expected 0 <= A <= 1")
+        self.value_head = getattr(config.trainer, "value_head", None)          # None: what the best model has
+        if self.value_head not in (None, "scalar", "wdl"):
+            raise ValueError(f"trainer.value_head={self.value_head!r}: expected scalar or wdl")
+        self.wdl = False                # set by load_model: the model has the win / draw / loss head
         self.rng = np.random.default_rng(config.engine.base_seed)
         # the mirror flags have their own stream: self.rng draws what it draws without the option
         self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
@@ -149,8 +161,17 @@ class OptimizeWorker:
         model = CChessModel(self.config)
         if self.config.opts.new or not load_best_model_weight(model):
             self.config.model.input_depth = self.depth
+            self.config.model.value_outputs = 3 if self.value_head == "wdl" else 1
             model.build(seed=self.config.engine.base_seed)
             save_as_best_model(model)
+        has = "wdl" if model.model.wdl_head else "scalar"
+        if self.value_head is not None and self.value_head != has:
+            raise ValueError(f"--value-head {self.value_head}: the best model has the {has} value head (scalar: Dense(1) + "
+                             f"tanh, wdl: Dense(3) + softmax); train it as it is, or start a new model with --new")
+        self.wdl = has == "wdl"
+        if self.wdl and self.q_ratio:
+            raise ValueError(f"--q-ratio {self.q_ratio:g} with a win / draw / loss value head: a scalar q does not "
+                             "determine a distribution over win / draw / loss (train on z: --q-ratio 0)")
         if model.model.cfg["input_depth"] != self.depth:
             raise ValueError(f"the best model takes {model.model.cfg['input_depth']} input planes, the trainer makes "
                              f"{self.depth} (opts.has_history / model.input_depth)")
@@ -272,8 +293,9 @@ class OptimizeWorker:
                 loss, pm, vm = self.step(idx, None if flags_d is None else flags_d[b:b + bs])
                 sums += torch.stack([loss.detach(), pm, vm]).double() * len(idx)
             tr_loss = (sums / max(1, len(tr))).tolist()
-            va_loss = self.evaluate(va_d) if len(va) else [float("nan")] * 3
-            entry = dict(train=tr_loss, val=va_loss)
+            extra = {}                  # (a win / draw / loss model's further validation figures; nothing is asked otherwise)
+            va_loss = (self.evaluate(va_d, **(dict(extra=extra) if self.wdl else {}))) if len(va) else [float("nan")] * 3
+            entry = dict(train=tr_loss, val=va_loss, **extra)
             logger.info(f"epoch {ep + 1}/{epochs}: {len(tr)} positions in {time.time() - t0:.1f} s; "
                         f"loss {tr_loss[0]:.4f} policy {tr_loss[1]:.4f} value {tr_loss[2]:.4f} - "
                         f"val_loss {va_loss[0]:.4f} val_policy {va_loss[1]:.4f} val_value {va_loss[2]:.4f}")
@@ -283,6 +305,10 @@ class OptimizeWorker:
                 logger.info(f"epoch {ep + 1}/{epochs}: {int(flags.sum())} of {len(tr)} training rows mirrored; all "
                             f"validation rows mirrored: val_loss {vm_loss[0]:.4f} val_policy {vm_loss[1]:.4f} "
                             f"val_value {vm_loss[2]:.4f}")
+            if extra:
+                logger.info(f"epoch {ep + 1}/{epochs}: win / draw / loss head, value = cross-entropy; P(win) - P(loss) "
+                            f"against z: val_value_z {extra['val_value_z']:.4f}; validation rows: mean P(draw) "
+                            f"{extra['val_draw_pred']:.4f}, drawn results {extra['val_draw_share']:.4f}")
             if self.q_ratio:
                 entry["val_value_z"] = self.evaluate(va_d, q_ratio=0.0)[2] if len(va) else float("nan")
                 logger.info(f"epoch {ep + 1}/{epochs}: value targets z + {self.q_ratio:g} (q - z); against z alone: "
@@ -305,8 +331,9 @@ class OptimizeWorker:
         uint8 [B] on the device, the rows to train on as their mirror image (planes and targets alike), or None."""
         tc = self.config.trainer
         logits, v = self.model.model(self.window.planes(idx, mirror=mirror), logits=True)
+        # (a win / draw / loss model returns its three value logits: the window's loss takes them as they are)
         total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
-                                         **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))
+                                         **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))[:3]
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -323,23 +350,33 @@ class OptimizeWorker:
         # (likewise; only training steps are weighted, evaluate() never passes it)
         return dict(surprise=True) if surprise_weight else {}
 
-    def evaluate(self, idx_all, mirror=False, q_ratio=None):
+    def evaluate(self, idx_all, mirror=False, q_ratio=None, extra=None):
         """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the
-        mirror images of all rows.  q_ratio: the value targets' mix, None = the trainer's own."""
+        mirror images of all rows.  q_ratio: the value targets' mix, None = the trainer's own.  extra: a dict that, for a
+        win / draw / loss model, receives val_value_z (the squared error of P(win) - P(loss) against z), val_draw_pred
+        (the mean predicted draw probability) and val_draw_share (the share of rows with z == 0)."""
         import torch
         tc = self.config.trainer
         net = self.model.model
         net.eval()
         sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
+        wdl_sums = torch.zeros(3, dtype=torch.float64, device=idx_all.device)
         with torch.no_grad():
             for b in range(0, idx_all.shape[0], tc.batch_size):
                 idx = idx_all[b:b + tc.batch_size]
                 flags = torch.ones(idx.shape[0], dtype=torch.uint8, device=idx.device) if mirror else None
                 logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
-                _, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags,
-                                             **self._q_args(self.q_ratio if q_ratio is None else q_ratio))
+                res = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags,
+                                       **self._q_args(self.q_ratio if q_ratio is None else q_ratio))
+                pm, vm = res[1], res[2]
                 sums += torch.stack([pm, vm]).double() * len(idx)
+                if v.dim() == 2:
+                    draws = (self.window.z[idx.long()] == 0).double().sum()
+                    wdl_sums += torch.stack([res[3].double() * len(idx), torch.softmax(v, dim=1)[:, 1].double().sum(), draws])
             p, v = (sums / idx_all.shape[0]).tolist()
+            if extra is not None and self.wdl:
+                sq, dp, ds = (wdl_sums / idx_all.shape[0]).tolist()
+                extra.update(val_value_z=sq, val_draw_pred=dp, val_draw_share=ds)
             l2 = float(self.l2_term())
         net.train()
         w = tc.loss_weights

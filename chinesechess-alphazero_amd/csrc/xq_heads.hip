@@ -11,6 +11,8 @@
 //                       the loop: the positions are the COLUMNS of the MFMA, so a lane owns one position
 //   k_policy_normalize  p = exp(logit - max) / sum in place (one streaming pass, rows of 8344 bytes, 8-byte accesses)
 //   k_fc_tile<VALUE>    hidden = relu(feat . W1^T + b1) stays in the accumulators, value = tanh(hidden . w2 + b2)
+//   k_fc_tile<WDL>      the same hidden layer against w2[3][n_hidden]: three logits (win, draw, loss) per position, a
+//                       max-subtracted softmax in fp32, value = (e_W - e_L) / ((e_W + e_L) + e_D) (cz_heads_tail_wdl)
 // Arithmetic: the same split-operand scheme as the tower (xq_conv.hip): every fp32 operand is a (hi, lo) pair of 2-byte
 // values, a product is accumulated as w_hi x_hi + w_lo x_hi + w_hi x_lo in fp32 by v_mfma_f32_32x32x16_{bf16,f16}.
 // dtype CZ_BF16: dropped term and representation error 2^-17 relative per product; CZ_F16 (round 4, what the network
@@ -57,7 +59,7 @@ constexpr int FC_STAGE_ROW = 144;     // bytes per position row of a wave's logi
 constexpr int FC_STAGE_BYTES = 32 * FC_STAGE_ROW;            // per wave
 constexpr int FC_LDS_BYTES = FC_IMG_BYTES + FC_RED_BYTES + (FC_THREADS / 64) * FC_STAGE_BYTES;
 
-enum FcMode { FC_POLICY = 0, FC_VALUE = 1 };
+enum FcMode { FC_POLICY = 0, FC_VALUE = 1, FC_WDL = 2 };
 
 struct FcArgs {
     const float* feat;        // [n][F]
@@ -73,6 +75,17 @@ struct FcArgs {
     float* value;             // [n]
 };
 
+// FC_WDL's arguments: w2 is [3][n_out] (win, draw, loss), b2 the win bias.  A type of its own, so that the other two modes
+// keep the kernel arguments they had.
+struct FcArgsWdl : FcArgs {
+    float b2_draw, b2_loss;
+    float* wdl;               // [n][3] probabilities, or NULL
+};
+template <int MODE> struct FcArgsOf { typedef FcArgs T; };
+template <> struct FcArgsOf<FC_WDL> { typedef FcArgsWdl T; };
+// FC_WDL combines three sums per position: the third lies behind `red`, in the logit staging tiles only FC_POLICY uses
+static_assert(3 * 256 * (int)sizeof(float) <= FC_RED_BYTES + FC_STAGE_BYTES, "the third WDL sum fits the first staging tile");
+
 // F: features per position (180 or 360: 2 or 4 head filters x 90 squares; compile-time so that the staging loop divides
 // by a constant and the K loop unrolls around a weight ring)
 // exp for the running softmax statistics: v_exp_f32 (2^x) on x * log2(e) -- 2 instructions instead of libm's ~25; the
@@ -80,8 +93,35 @@ struct FcArgs {
 // k_policy_normalize.  Half of this kernel's issue slots went to libm exps before (0.277 -> see profiles/r03_*).
 __device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 
+// FC_WDL's finish for one position: the four waves' sums in wave order, then the softmax.  Every step treats win and loss
+// alike (max(max(W, L), D), (e_W + e_L) + e_D), so that swapping the two rows of w2 / b2 negates the value and swaps the two
+// probabilities bit for bit; the value is one quotient of the difference, not a difference of two rounded quotients.
+template <typename A>
+__device__ __forceinline__ void fc_finish_wdl(const A& a, const float* red, int bt, int ln, int board)
+{
+    float dw = 0.0f, dd = 0.0f, dl = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        dw += red[(bt * 4 + q) * 32 + ln];
+        dd += red[256 + (bt * 4 + q) * 32 + ln];
+        dl += red[512 + (bt * 4 + q) * 32 + ln];
+    }
+    dw += a.b2; dd += a.b2_draw; dl += a.b2_loss;
+    const float mx = fmaxf(fmaxf(dw, dl), dd);
+    const float ew = expf(dw - mx), ed = expf(dd - mx), el = expf(dl - mx);
+    const float s = (ew + el) + ed;
+    a.value[board] = (ew - el) / s;
+    if (a.wdl) {
+        float* o = a.wdl + (size_t)board * 3;
+        o[0] = ew / s; o[1] = ed / s; o[2] = el / s;
+    }
+}
+// (the other modes' argument type has no WDL fields: their dead branch calls this)
+template <>
+__device__ __forceinline__ void fc_finish_wdl<FcArgs>(const FcArgs&, const float*, int, int, int) {}
+
 template <int MODE, int F, typename E>
-__global__ __launch_bounds__(FC_THREADS) void k_fc_tile(FcArgs a, int n, const int32_t* __restrict__ n_dev)
+__global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>::T a, int n, const int32_t* __restrict__ n_dev)
 {
     constexpr int KS = (F + 15) / 16;                 // K-steps
     constexpr int RB = KS * 32 + 16;                  // bytes per position row of the feature image; RB / 16 is odd, so
@@ -134,7 +174,8 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(FcArgs a, int n, const i
 
         const unsigned char* brow = lds + (bt * 32 + ln) * RB + kb * 16;
         float m_run = -3.0e38f, s_run = 0.0f;      // policy: running max / sum of exp of this lane's labels
-        float dot = 0.0f;                          // value: partial hidden . w2
+        float dot = 0.0f;                          // value: partial hidden . w2 (WDL: the win row)
+        float dot_d = 0.0f, dot_l = 0.0f;          // WDL: the draw and loss rows
         const int board = row0 + bt * 32 + ln;
         // two label tiles per pass and wave (two independent MFMA chains, one set of position operands), weights through a
         // register ring RING K-steps deep: an L2 round trip is several hundred cycles, a K-step of one tile only 96
@@ -201,12 +242,21 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(FcArgs a, int n, const i
                         s_run = s;
                         // into the wave's staging tile [position][32 labels]; written out in whole rows below
                         *reinterpret_cast<float4*>(stg + ln * FC_STAGE_ROW + (g * 8 + kb * 4) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                    } else if (MODE == FC_VALUE) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (lab + i < a.n_out) {
+                                const float h = v[i] > 0.0f ? v[i] : 0.0f;
+                                dot += h * a.w2[lab + i];
+                            }
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (lab + i < a.n_out) {
                                 const float h = v[i] > 0.0f ? v[i] : 0.0f;
                                 dot += h * a.w2[lab + i];
+                                dot_d += h * a.w2[a.n_out + lab + i];
+                                dot_l += h * a.w2[2 * a.n_out + lab + i];
                             }
                     }
                 }
@@ -249,6 +299,13 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(FcArgs a, int n, const i
         } else {
             const float d = dot + __shfl_xor(dot, 32, 64);
             if (kb == 0) red[(bt * 4 + lq) * 32 + ln] = d;
+            if (MODE == FC_WDL) {
+                const float dd = dot_d + __shfl_xor(dot_d, 32, 64), dl = dot_l + __shfl_xor(dot_l, 32, 64);
+                if (kb == 0) {
+                    red[256 + (bt * 4 + lq) * 32 + ln] = dd;
+                    red[512 + (bt * 4 + lq) * 32 + ln] = dl;
+                }
+            }
         }
         __syncthreads();
         if (lq == 0 && kb == 0 && board < n) {
@@ -264,11 +321,13 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(FcArgs a, int n, const i
                 for (int q = 0; q < 4; ++q)
                     s += red[256 + (bt * 4 + q) * 32 + ln] * fexp(red[(bt * 4 + q) * 32 + ln] - mx);
                 a.stats[board] = make_float2(mx, s);
-            } else {
+            } else if (MODE == FC_VALUE) {
                 float d = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) d += red[(bt * 4 + q) * 32 + ln];
                 a.value[board] = tanhf(d + a.b2);
+            } else {
+                fc_finish_wdl(a, red, bt, ln, board);
             }
         }
         __syncthreads();                    // the image and `red` are reused by the next tile
@@ -298,7 +357,7 @@ __global__ __launch_bounds__(256) void k_policy_normalize(float* __restrict__ p,
 
 // one dense layer's launch (dtype: the packed pairs', CZ_BF16 or CZ_F16)
 template <int MODE, int F>
-void launch_fc(int dtype, unsigned blocks, hipStream_t st, const FcArgs& a, int n_boards, const int32_t* n_dev)
+void launch_fc(int dtype, unsigned blocks, hipStream_t st, const typename FcArgsOf<MODE>::T& a, int n_boards, const int32_t* n_dev)
 {
     if (dtype == CZ_BF16) hipLaunchKernelGGL((k_fc_tile<MODE, F, __bf16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev);
     else hipLaunchKernelGGL((k_fc_tile<MODE, F, _Float16>), dim3(blocks), dim3(FC_THREADS), 0, st, a, n_boards, n_dev);
@@ -339,6 +398,25 @@ extern "C" int cz_fc_pack_weights(const float* w, int n_out, int n_in, int dtype
     return CZ_OK;
 }
 
+// the policy half of the tail: the logits' launch and, with `normalize`, the softmax pass
+static void launch_policy_half(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
+                               int n_labels, float* policy, float* stats_scratch, int n_boards, int dtype, int normalize,
+                               const int32_t* n_dev, int n_cu, unsigned blocks, hipStream_t st)
+{
+    FcArgs a{};
+    a.feat = policy_feat; a.wp = wp_packed; a.bias = bias_p; a.F = n_policy_feat;
+    a.ksteps = (n_policy_feat + 15) / 16; a.n_out = n_labels; a.n_tiles = (n_labels + 31) / 32;
+    a.logits = policy; a.stats = reinterpret_cast<float2*>(stats_scratch);
+    if (n_policy_feat == 360) launch_fc<FC_POLICY, 360>(dtype, blocks, st, a, n_boards, n_dev);
+    else launch_fc<FC_POLICY, 180>(dtype, blocks, st, a, n_boards, n_dev);
+    if (normalize) {              // (0: `policy` keeps the raw logits -- cz_search_policy_logits takes them as they are)
+        size_t nb = ((size_t)n_boards + 3) / 4;
+        if (nb > (size_t)n_cu * 16) nb = (size_t)n_cu * 16;
+        hipLaunchKernelGGL(k_policy_normalize, dim3((unsigned)nb), dim3(256), 0, st, policy,
+                           reinterpret_cast<const float2*>(stats_scratch), n_boards, n_labels, n_dev);
+    }
+}
+
 extern "C" int cz_heads_tail(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
                              int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed,
                              const float* bias1, int n_hidden, const float* w2, float b2, float* policy, float* value,
@@ -355,20 +433,8 @@ extern "C" int cz_heads_tail(const float* policy_feat, int n_policy_feat, const 
     hipStream_t st = (hipStream_t)stream;
     const int row_tiles = (n_boards + TILE_ROWS - 1) / TILE_ROWS;
     const unsigned blocks = nn_grid(row_tiles, 2 * n_cu);
-    {
-        FcArgs a{};
-        a.feat = policy_feat; a.wp = wp_packed; a.bias = bias_p; a.F = n_policy_feat;
-        a.ksteps = (n_policy_feat + 15) / 16; a.n_out = n_labels; a.n_tiles = (n_labels + 31) / 32;
-        a.logits = policy; a.stats = reinterpret_cast<float2*>(stats_scratch);
-        if (n_policy_feat == 360) launch_fc<FC_POLICY, 360>(dtype, blocks, st, a, n_boards, n_dev);
-        else launch_fc<FC_POLICY, 180>(dtype, blocks, st, a, n_boards, n_dev);
-        if (normalize) {              // (0: `policy` keeps the raw logits -- cz_search_policy_logits takes them as they are)
-            size_t nb = ((size_t)n_boards + 3) / 4;
-            if (nb > (size_t)n_cu * 16) nb = (size_t)n_cu * 16;
-            hipLaunchKernelGGL(k_policy_normalize, dim3((unsigned)nb), dim3(256), 0, st, policy,
-                               reinterpret_cast<const float2*>(stats_scratch), n_boards, n_labels, n_dev);
-        }
-    }
+    launch_policy_half(policy_feat, n_policy_feat, wp_packed, bias_p, n_labels, policy, stats_scratch, n_boards, dtype, normalize,
+                       n_dev, n_cu, blocks, st);
     {
         FcArgs a{};
         a.feat = value_feat; a.wp = w1_packed; a.bias = bias1; a.F = n_value_feat;
@@ -378,4 +444,34 @@ extern "C" int cz_heads_tail(const float* policy_feat, int n_policy_feat, const 
         else launch_fc<FC_VALUE, 360>(dtype, blocks, st, a, n_boards, n_dev);
     }
     return nn_launched("cz_heads_tail");
+}
+
+extern "C" int cz_heads_tail_wdl(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
+                                 int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed,
+                                 const float* bias1, int n_hidden, const float* w2, float b2_win, float b2_draw, float b2_loss,
+                                 float* policy, float* value, float* wdl, float* stats_scratch, int n_boards, int dtype,
+                                 int normalize, const int32_t* n_dev, void* stream)
+{
+    if (!policy_feat || !wp_packed || !bias_p || !value_feat || !w1_packed || !bias1 || !w2 || !policy || !value ||
+        !stats_scratch || n_boards < 0 || (dtype != CZ_BF16 && dtype != CZ_F16) || n_labels < 2 || (n_labels & 1) || n_hidden < 1 || n_policy_feat < 1 ||
+        (n_policy_feat != 180 && n_policy_feat != 360) || (n_value_feat != 180 && n_value_feat != 360))
+        return nn_error(CZ_ERR_ARG, "cz_heads_tail_wdl: bad argument (n_labels even; 180 or 360 features per head: 2 or 4 filters x 90 squares; "
+                                    "dtype of the packed pairs: CZ_BF16 or CZ_F16; wdl may be NULL)");
+    if (n_boards == 0) return CZ_OK;
+    const int n_cu = nn_cu_count("cz_heads_tail_wdl");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    const int row_tiles = (n_boards + TILE_ROWS - 1) / TILE_ROWS;
+    const unsigned blocks = nn_grid(row_tiles, 2 * n_cu);
+    launch_policy_half(policy_feat, n_policy_feat, wp_packed, bias_p, n_labels, policy, stats_scratch, n_boards, dtype, normalize,
+                       n_dev, n_cu, blocks, st);
+    {
+        FcArgsWdl a{};
+        a.feat = value_feat; a.wp = w1_packed; a.bias = bias1; a.F = n_value_feat;
+        a.ksteps = (n_value_feat + 15) / 16; a.n_out = n_hidden; a.n_tiles = (n_hidden + 31) / 32;
+        a.w2 = w2; a.b2 = b2_win; a.b2_draw = b2_draw; a.b2_loss = b2_loss; a.value = value; a.wdl = wdl;
+        if (n_value_feat == 180) launch_fc<FC_WDL, 180>(dtype, blocks, st, a, n_boards, n_dev);
+        else launch_fc<FC_WDL, 360>(dtype, blocks, st, a, n_boards, n_dev);
+    }
+    return nn_launched("cz_heads_tail_wdl");
 }

@@ -5,7 +5,9 @@
 //   k_gather_planes      one wavefront per minibatch row: window index -> 14 or 28 float32 input planes (state_to_planes /
 //                        state_history_to_planes, environment/static_env.py:137-194) with wave_encode, the encoder of k_encode
 //   k_policy_value_loss  one wavefront per minibatch row: softmax, Keras 2.0.8's clipped categorical cross-entropy against the
-//                        played move's one-hot or the record's visit counts, squared value error, and their gradients
+//                        played move's one-hot or the record's visit counts, squared value error, and their gradients;
+//                        <WDL = true> (cz_policy_wdl_loss): the same policy half, and for a win / draw / loss value head the
+//                        clipped cross-entropy of its three logits against the class of z, with its gradient
 //
 // Mirror augmentation (run.py opt --augment mirror): both per-step kernels take an optional per-row flag array.  A flagged
 // row is the left-right mirror image of its position (file x <-> 8 - x, a symmetry of the rules): its board is mirrored in
@@ -137,13 +139,14 @@ __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__
     }
 }
 
+template <bool WDL>
 __global__ __launch_bounds__(64) void k_policy_value_loss(
     const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx,
     const uint8_t* __restrict__ mirror, int n_rows, int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
     const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z,
     const float* __restrict__ q, float q_ratio, const float* __restrict__ row_w, int mode,
     float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
-    float* __restrict__ grad_logits, float* __restrict__ grad_v)
+    float* __restrict__ grad_logits, float* __restrict__ grad_v, float* __restrict__ value_ce)
 {
     __shared__ float tgt[LOSS_COLS * 64];            // the row's dense target, built from the sparse entries
     const int lane = lane_id();
@@ -158,7 +161,12 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
             if (lane == 0) {
                 policy_loss[r] = 0.f;
                 value_sqerr[r] = 0.f;
-                grad_v[r] = 0.f;
+                if (WDL) {
+                    value_ce[r] = 0.f;
+                    grad_v[3 * r] = grad_v[3 * r + 1] = grad_v[3 * r + 2] = 0.f;
+                } else {
+                    grad_v[r] = 0.f;
+                }
             }
             continue;
         }
@@ -233,7 +241,29 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
                 g[j] = cr * (p * S - tm);
             }
         }
-        if (lane == 0) {
+        if (WDL) {
+            // v: the row's three value logits (win, draw, loss); the target class is the sign of z.  The same softmax, clip
+            // and gradient mask as the policy half above, on a one-hot target: grad_k = p_k S - t_k m_k with S = m_target.
+            if (lane == 0) {
+                const float zi = z[i];
+                const int tc = zi > 0.f ? 0 : (zi < 0.f ? 2 : 1);
+                const float l0 = v[3 * r], l1 = v[3 * r + 1], l2 = v[3 * r + 2];
+                const float vm = fmaxf(fmaxf(l0, l2), l1);
+                const float e0 = expf(l0 - vm), e1 = expf(l1 - vm), e2 = expf(l2 - vm);
+                const float vs = (e0 + e2) + e1;
+                const float p[3] = {e0 / vs, e1 / vs, e2 / vs};
+                const float pt = tc == 0 ? p[0] : (tc == 1 ? p[1] : p[2]);
+                const float Sv = (pt > CCE_EPS && pt < CCE_HI) ? 1.f : 0.f;
+                const float d = (p[0] - p[2]) - zi;
+                policy_loss[r] = loss;
+                value_sqerr[r] = d * d;
+                value_ce[r] = -logf(fminf(fmaxf(pt, CCE_EPS), CCE_HI));
+                const float cv = w_v * inv_b;
+                const float cvr = row_w != nullptr ? __fmul_rn(cv, wi) : cv;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) grad_v[3 * r + k] = cvr * (p[k] * Sv - (k == tc ? Sv : 0.f));
+            }
+        } else if (lane == 0) {
             float t = z[i];
             if (q != nullptr) {                          // z/q mix (cz_policy_value_loss_q): rounded step by step, no fma
                 const float qi = q[i];
@@ -303,10 +333,29 @@ int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const in
         czi_set_error("cz_policy_value_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
         return CZ_ERR_ARG;
     }
-    hipLaunchKernelGGL(k_policy_value_loss, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
+    hipLaunchKernelGGL(k_policy_value_loss<false>, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
                        mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, row_w, mode, w_p,
-                       w_v, policy_loss, value_sqerr, grad_logits, grad_v);
+                       w_v, policy_loss, value_sqerr, grad_logits, grad_v, (float*)nullptr);
     return launch_status("cz_policy_value_loss: launch failed");
+}
+
+int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                       int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                       const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
+                       float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
+                       void* stream)
+{
+    if (n_rows == 0) return CZ_OK;
+    if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !vlogits || !idx || !policy_loss ||
+        !value_ce || !value_sqerr || !grad_logits || !grad_vlogits || (n_pos > 0 && (!played || !z)) ||
+        nnz < 0 || (mode == 1 && nnz > 0 && (!row_ptr || !vis_label || !vis_count))) {
+        czi_set_error("cz_policy_wdl_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
+        return CZ_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_policy_value_loss<true>, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, vlogits,
+                       idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, (const float*)nullptr, 0.f,
+                       row_w, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_vlogits, value_ce);
+    return launch_status("cz_policy_wdl_loss: launch failed");
 }
 
 int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,

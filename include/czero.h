@@ -1022,6 +1022,21 @@ int cz_heads_tail(const float* policy_feat, int n_policy_feat, const void* wp_pa
                   int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed, const float* bias1,
                   int n_hidden, const float* w2, float b2, float* policy, float* value, float* stats_scratch,
                   int n_boards, int dtype, int normalize, const int32_t* n_dev, void* stream);
+/* The tail of a network with a win / draw / loss value head: Dense(n_hidden, relu) -> Dense(3) -> softmax, classes in the
+ * order (win, draw, loss) for the side to move.  The arguments of cz_heads_tail with w2[3][n_hidden], the three biases by
+ * value, and wdl[n][3] (fp32 output, may be NULL).  With l_k = hidden . w2[k] + b2_k, m = max(max(l_W, l_L), l_D) and
+ * e_k = exp(l_k - m) in fp32, s = (e_W + e_L) + e_D:
+ *   value[n] = (e_W - e_L) / s      the scalar the search consumes, P(win) - P(loss): one quotient, and every step treats
+ *                                   win and loss alike -- swapping rows 0 and 2 of w2 and b2_win with b2_loss negates value
+ *                                   and swaps wdl's outer columns bit for bit
+ *   wdl[n][k] = e_k / s
+ * The policy half is cz_heads_tail's launch; the refusals, n_dev (rows beyond the count are neither computed nor written, in
+ * value and in wdl), dtype, normalize, precision and range are cz_heads_tail's (per-element bounds: tests/wdl_check.py). */
+int cz_heads_tail_wdl(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
+                      int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed, const float* bias1,
+                      int n_hidden, const float* w2, float b2_win, float b2_draw, float b2_loss, float* policy,
+                      float* value, float* wdl, float* stats_scratch, int n_boards, int dtype, int normalize,
+                      const int32_t* n_dev, void* stream);
 /* number of 2-byte elements of a packed dense layer (0 = bad argument); HOST: w[n_out][n_in] fp32 -> (hi, lo) pairs of
  * `dtype` (CZ_BF16 / CZ_F16) in fragment order */
 size_t cz_fc_packed_elems(int n_out, int n_in);
@@ -1120,6 +1135,23 @@ int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const in
                            const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
                            float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
                            void* stream);
+/* The loss of a network with a win / draw / loss value head (CChessNet(value_outputs=3), run.py opt --value-head wdl):
+ * the arguments of cz_policy_value_loss_w without q / q_ratio (a scalar q does not determine a distribution), with
+ * vlogits[n_rows][3] = the value head's three logits in the order (win, draw, loss) for the side to move in place of v,
+ * grad_vlogits[n_rows][3] in place of grad_v, and one more per-row output, value_ce.
+ * The policy half (policy_loss, grad_logits) is cz_policy_value_loss_w's on the same inputs, bit for bit.  Value half of
+ * row r with i = idx[r]: target class c = win if z[i] > 0, loss if z[i] < 0, draw if z[i] == 0; p = softmax(vlogits[r]) in
+ * fp32 after subtracting the row max, summed as (e_W + e_L) + e_D; eps and hi as above;
+ *   value_ce[r]        = -log(clip(p_c, eps, hi))
+ *   grad_vlogits[r][k] = (w_v / n_rows) (p_k S - t_k m_k), t the one-hot of c, S = m_c = 1 where eps < p_c < hi else 0,
+ *                        the factor w_v / n_rows multiplied by row_w[i] first (one rounded product) where row_w is given
+ *   value_sqerr[r]     = ((p_W - p_L) - z)^2, so that runs with either head report a comparable number
+ * The gradients are those of w_p mean(policy_loss) + w_v mean(value_ce).  An index outside [0, n_pos) gives zeros. */
+int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                       int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                       const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
+                       float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
+                       void* stream);
 
 #ifdef __cplusplus
 }
