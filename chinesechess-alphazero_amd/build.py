@@ -17,8 +17,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libczero.so")
-SOURCES = ["xq_kernels.hip", "xq_search.hip", "xq_nn_epilogue.hip", "xq_conv.hip", "xq_conv_ip4.hip", "xq_tower.hip",
-           "xq_heads.hip", "xq_train.hip"]
+SOURCES = ["xq_kernels.hip", "xq_search.hip", "xq_nn_epilogue.hip", "xq_conv.hip", "xq_conv_pack.hip", "xq_conv_ip4.hip",
+           "xq_tower.hip", "xq_heads.hip", "xq_train.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-ffp-contract=off",          # PUCT / backup arithmetic must not be fused (bit-parity with the reference)
          "-fno-fast-math"]

@@ -465,7 +465,7 @@ def pack_conv3x3_weights(w_oihw, dtype, parts):
     return out
 
 
-# ---- the c8 tower arithmetic: fp16 main term + two scaled-fp8 correction terms (csrc/xq_conv.hip, k_conv3x3_c8) ----------
+# ---- the c8 tower arithmetic: fp16 main term + two scaled-fp8 correction terms (csrc/xq_conv_single.h, k_conv3x3_c8) ----------
 C8_X_LO_SHIFT = 11
 
 

@@ -35,7 +35,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
-constexpr int W_PAD_STEPS = 3;
+constexpr int W_PAD_STEPS = 3;   // zero K-steps appended to the packed filter so the prefetch never reads past it
 constexpr int X_LO_SHIFT = 11;
 // geometry of a tower of CH filters (128: 256-byte pixel rows, 16 chunks swizzled by the row's low four bits; 192: 384-byte
 // rows, 24 chunks, swizzled inside aligned groups of eight so that the XOR stays inside the row)

@@ -173,10 +173,7 @@ __global__ __launch_bounds__(256, 1) void k_resblock_ip4_c8(
     constexpr bool EC6U = EADR && XF == 1 && YF == 1 && !MIX;   // the c6 units on row bases
     constexpr bool EMRG = EC6U && (EP & 16) != 0;               // tile 2 of both channel tiles in one unit
     const int NB = ch.n;
-    if (n_dev) {
-        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
-        n_boards = nd < n_boards ? nd : n_boards;
-    }
+    n_boards = nn_live_boards(n_boards, n_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_pairs = (n_boards + 1) / 2;
     int t = blockIdx.x;

@@ -129,10 +129,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
     constexpr int RING = 6;                           // chunk) fall on 16 different 16-byte slots of the 256-byte bank row
     static_assert(F % 4 == 0 && KS <= FC_MAX_KSTEPS, "whole float4s per row");
     __shared__ __attribute__((aligned(16))) unsigned char lds[FC_LDS_BYTES];
-    if (n_dev) {
-        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
-        n = nd < n ? nd : n;
-    }
+    n = nn_live_boards(n, n_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ln = lane & 31, kb = lane >> 5;
     const int bt = wave & 1, lq = wave >> 1;
@@ -338,10 +335,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
 __global__ __launch_bounds__(256) void k_policy_normalize(float* __restrict__ p, const float2* __restrict__ stats, int n,
                                                          int n_out, const int32_t* __restrict__ n_dev)
 {
-    if (n_dev) {
-        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
-        n = nd < n ? nd : n;
-    }
+    n = nn_live_boards(n, n_dev);
     const int half = n_out / 2, lane = threadIdx.x & 63;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
         const float2 st = stats[row];

@@ -45,9 +45,20 @@ template <> struct Mfma<_Float16> {
 };
 
 constexpr int W_RING_MAX = 4;    // weight fragments in flight (register ring); 3 K-steps of prefetch
-constexpr int W_PAD_STEPS = 3;   // zero K-steps appended to the packed filter so the prefetch never reads past it
+using c8k::W_PAD_STEPS;          // zero K-steps appended to the packed filter (defined once, beside the c8 K loop's geometry)
 
 template <typename E> struct alignas(8) Quad { E e[4]; };
+
+// The compact evaluation queue keeps its board count on the device: a kernel handed n_dev works on min(n_boards, *n_dev) boards
+// (wave-uniform); NULL: on n_boards.
+__device__ __forceinline__ int nn_live_boards(int n_boards, const int32_t* n_dev)
+{
+    if (n_dev) {
+        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
+        n_boards = nd < n_boards ? nd : n_boards;
+    }
+    return n_boards;
+}
 
 // sum over the 16 lanes of a DPP row, on every lane of the row: four rotate-and-add steps in the VALU (round 5; the head
 // convolutions' 16-lane butterflies were ds_bpermute round trips through the LDS the matrix waves read their operands from)

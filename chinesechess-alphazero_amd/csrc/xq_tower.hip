@@ -144,10 +144,7 @@ __global__ __launch_bounds__(256, 1) void k_tower_pairs4(
                   BIAS_OFF = G::BIAS_OFF, HW_OFF = G::HW_OFF;
     __shared__ __attribute__((aligned(16))) unsigned char lds[G::LDS_BYTES];
     const int NB = ch.n;
-    if (n_dev) {
-        const int nd = __builtin_amdgcn_readfirstlane(*n_dev);
-        n_boards = nd < n_boards ? nd : n_boards;
-    }
+    n_boards = nn_live_boards(n_boards, n_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_pairs = (n_boards + 1) / 2;
     int t = blockIdx.x;

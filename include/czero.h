@@ -782,7 +782,7 @@ int cz_search_root_kld(cz_search* s, double* gain, int32_t* checks, void* stream
 int cz_bias_act(void* x, const void* bias, const void* residual, size_t n_elems, int channels, int dtype,
                 int relu, void* stream);
 
-/* ---- trunk convolution (hand-written MFMA kernel, csrc/xq_conv.hip) -------------------------------------------
+/* ---- trunk convolution (hand-written MFMA kernel, csrc/xq_conv.hip: k_conv3x3 in csrc/xq_conv_single.h; the packers: csrc/xq_conv_pack.hip) -------------------------------------------
  * Replaces Conv2D(F, 3, padding="same") -> BatchNorm -> (+ skip) -> ReLU of the residual tower
  * (agent/model.py:40-83, BatchNorm folded into w / bias) on channels-last 10x9 boards:
  *   y[n][pix][o] = act( sum_{ky,kx,c} w[o][c][ky][kx] * x[n][pix + (ky-1, kx-1)][c] + bias[o] (+ skip[n][pix][o]) )
@@ -797,7 +797,7 @@ int cz_bias_act(void* x, const void* bias, const void* residual, size_t n_elems,
 int cz_conv3x3(const void* x_hi, const void* x_lo, const void* w_packed, const float* bias, const void* skip_hi,
                const void* skip_lo, void* y_hi, void* y_lo, float* y_f32, int n_boards, int channels, int dtype,
                int parts, int relu, void* stream);
-/* A whole residual block in one launch (csrc/xq_conv.hip, k_resblock):
+/* A whole residual block in one launch (csrc/xq_conv.hip; k_resblock: csrc/xq_conv_block.h, k_resblock_pipe: csrc/xq_conv_pipe.h):
  *   y = relu( conv3x3(relu(conv3x3(x, w1) + bias1), w2) + bias2 + x )          (agent/model.py:68-83)
  * The intermediate activation and the skip operand stay in LDS; HBM sees one read of x and one write of y.
  * Same layouts and `parts` as cz_conv3x3; y_f32 != NULL (parts = 2 only) writes the fp32 result instead of
@@ -812,7 +812,7 @@ int cz_conv3x3(const void* x_hi, const void* x_lo, const void* w_packed, const f
 int cz_resblock(const void* x_hi, const void* x_lo, const void* w1_packed, const float* bias1, const void* w2_packed,
                 const float* bias2, void* y_hi, void* y_lo, float* y_f32, int n_boards, int channels, int dtype,
                 int parts, void* stream);
-/* The c8 tower arithmetic (csrc/xq_conv.hip, k_conv3x3_c8 / k_resblock_c8 / k_resblock_ip_c8, K loop csrc/xq_c8_kloop.h;
+/* The c8 tower arithmetic (csrc/xq_conv.hip: k_conv3x3_c8 in xq_conv_single.h, k_resblock_c8 in xq_conv_block_c8.h, k_resblock_ip_c8 in xq_conv_ip.h; K loop csrc/xq_c8_kloop.h;
  * DESIGN section 7b; what the self-play engine requested by default until the end of round 4 -- now its bf6 sibling c6, below, with c8
  * next in the guard's chain -- and keeps where its load-time check against float64
  * allows -- a host binding these entry points directly owns that check): one 3x3 convolution, 128 or 192
@@ -839,7 +839,7 @@ int cz_conv3x3_c8(const void* x_hi, const void* x_c8, const void* w_packed, cons
  * 64 (tools/probes/bf6_probe.hip), so a product costs 1.5 instead of 2.0 MFMA-equivalents; per-product accuracy ~2^-15
  * (measured on whole blocks against float64, tests/test_gpu_c6_elements.py: 2^-15.1, c8 2^-16.1, bf16x3 2^-17.3).
  * Activation images keep the c8 pair's shape (x_hi f16 [n][90][C], image bytes [n][90][2 C]); the image holds, per pixel
- * and 32-channel block, a 24-byte piece bf6((x - f16(x)) 2^(11 - k)) and a piece bf6(x 2^-k) (layout: csrc/xq_conv.hip,
+ * and 32-channel block, a 24-byte piece bf6((x - f16(x)) 2^(11 - k)) and a piece bf6(x 2^-k) (layout: csrc/xq_nn_common.h,
  * namespace rb8), k = the image's exponent, 2^k * 28 >= max |x| (from calibration activations; the conversion rounds to
  * nearest even and saturates at 28 2^k, the lo piece at 28 2^(k - 11)).  Of a pixel's 2 C bytes the first C carry the lo
  * pieces, the last C the value pieces; piece w sits in the 24 bytes at 32 w of its half, element e (6 bits at bit 6 e) =
@@ -895,7 +895,7 @@ size_t cz_conv3x3_packed_elems(int channels, int parts);
 /* HOST: w_oihw[channels][channels][3][3] fp32 -> MFMA fragment order, split into parts; out_host holds
  * cz_conv3x3_packed_elems() elements */
 int cz_conv3x3_pack_weights(const float* w_oihw, int channels, int dtype, int parts, void* out_host);
-/* The input convolution of the network (csrc/xq_conv.hip, k_input_conv): Conv2D(F, 5, padding="same") -> BatchNorm ->
+/* The input convolution of the network (csrc/xq_conv.hip, k_input_conv in csrc/xq_conv_input.h): Conv2D(F, 5, padding="same") -> BatchNorm ->
  * ReLU on the feature planes (agent/model.py:36-39), BatchNorm folded.  planes: [n_boards][in_planes][10][9] exactly as
  * cz_encode / the search kernel write them (planes_dtype CZ_F32 / CZ_F16 / CZ_BF16 / CZ_U8, in_planes 14 or 28);
  * output: the [n_boards][90][channels] operand (pair) the residual tower reads (dtype CZ_BF16 / CZ_F16, parts as in

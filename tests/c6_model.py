@@ -1,4 +1,5 @@
-"""Float64 model of the c6 tower arithmetic (csrc/xq_conv.hip k_resblock_c8<.., C6>, k_resblock_ip_c8, k_resblock_ip4_c8; K loop
+"""Float64 model of the c6 tower arithmetic (csrc/xq_conv_block_c8.h k_resblock_c8<.., C6>, csrc/xq_conv_ip.h k_resblock_ip_c8,
+csrc/xq_conv_ip4.h k_resblock_ip4_c8; K loop
 csrc/xq_c8_kloop.h FMT = 1): the operand formats as bytes, the value of a convolution and of a residual block on exactly those
 operands, and the per-element bound the kernels are held to (tests/test_gpu_c6_elements.py; the check itself is tested on
 faulty arithmetic in tests/test_c6_model_cpu.py).

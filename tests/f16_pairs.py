@@ -37,7 +37,7 @@ arithmetic), so the CPU test feeds the check the very function the GPU tests use
 [n, 90, C] (the kernels' layout), filters [C_out, C_in, K, K].
 
 BF16 PAIRS AND PLAIN OPERANDS (pair_conv / ConvCheck with fmt=BF16_PAIR, or plain=True).  The kernel is the same K loop
-(csrc/xq_conv.hip conv_kloop) for every operand type: tap-major, K-steps of 16 input channels, three matrix instructions per
+(csrc/xq_conv_kloop.h conv_kloop) for every operand type: tap-major, K-steps of 16 input channels, three matrix instructions per
 step for pairs (w_hi x_hi, w_lo x_hi, w_hi x_lo) and ONE for plain operands, fp32 accumulation.
 
 bf16 pairs ("bf16x3").  The arithmetic and both bounds are those above with the pair format e(v) = 2^-16 |v| + 2^-134 (BF16_PAIR;

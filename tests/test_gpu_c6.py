@@ -1,4 +1,4 @@
-"""-m gpu: the c6 tower arithmetic (k_resblock_c8<.., C6>, csrc/xq_conv.hip; K loop csrc/xq_c8_kloop.h FMT = 1): the c8
+"""-m gpu: the c6 tower arithmetic (k_resblock_c8<.., C6>, csrc/xq_conv_block_c8.h; K loop csrc/xq_c8_kloop.h FMT = 1): the c8
 sum with bf6 (e3m2) correction operands, which the matrix pipe retires in half the time of e4m3 ones.
 
 Pinned three ways, all against float64:

@@ -1,5 +1,5 @@
 """-m gpu: the 128-filter chains of the four-wave pair kernel (k_resblock_ip4_c8<128>, csrc/xq_conv_ip4.hip) are compiled with the
-matrix instructions' accumulators in VALU-visible registers; the one-block kernels (k_resblock_c8, csrc/xq_conv.hip) are not, so
+matrix instructions' accumulators in VALU-visible registers; the one-block kernels (k_resblock_c8, csrc/xq_conv_block_c8.h) are not, so
 they are an independent reference.  A chained launch is compared BYTE FOR BYTE with one launch per block of those kernels at
 the smallest shapes where the pair kernel can go wrong:
 

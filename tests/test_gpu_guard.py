@@ -127,7 +127,7 @@ def test_guard_keeps_the_requested_arithmetic_where_it_is_exact_enough():
 
 
 def test_guard_moves_out_of_range_activations_into_the_operand_formats():
-    """Activations above e4m3's 448 would lose the w_lo x correction silently in the kernels (xq_conv.hip cf8::sat), tiny
+    """Activations above e4m3's 448 would lose the w_lo x correction silently in the kernels (xq_nn_common.h cf8::sat), tiny
     ones fall into its subnormals.  The guard sees every tower tensor's range in the float64 pass and applies exact
     power-of-two scales (InferenceNet act_shift: a reparametrisation of the folded network, outputs unchanged) before it
     measures the candidates; the report carries the ranges before and after."""

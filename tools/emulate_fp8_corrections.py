@@ -164,7 +164,7 @@ def conv_model(x, w, b, mode, pad):
             r = torch.where(pick_other, e_other, e_near)
         y = conv(xh, wh) + conv(xl8, f8(w * sh) / sh) + conv(xh8, q / sl)
     elif mode.startswith("c6k:"):
-        # exactly the c6 kernels' operand model (csrc/xq_conv.hip, k_resblock_c8<.., C6>): bf6 (e3m2) correction operands with
+        # exactly the c6 kernels' operand model (csrc/xq_conv_block_c8.h, k_resblock_c8<.., C6>): bf6 (e3m2) correction operands with
         # FIXED scales -- the image's exponent k (2^k * 28 >= the tensor's calibration maximum; saturating), one power of
         # two per output channel of a filter (the row's largest magnitude in [8, 16))
         k = int(mode[4:])

@@ -1,5 +1,5 @@
 // xq_resblock_x2.h -- kernel 2c8x2 (round 5): the c8 / c6 residual block on TWO boards per filter fragment.
-// Included by xq_conv.hip inside its anonymous namespace, after k_resblock_c8 (it uses Geom / Quad / cf8 / rb8's c6 helpers).
+// Included by xq_conv.hip after xq_conv_block_c8.h (k_resblock_c8), inside an anonymous namespace (it uses Geom / Quad / cf8 / rb8's c6 helpers).
 //
 // Why.  k_resblock_c8 is not matrix-bound any more (round 4: MFMA busy 0.51): every board streams both packed filters --
 // 576 KB per board and convolution -- from L2 through the CU's 64 B/clk vector-memory path, and under the chip's power cap the
