@@ -1,7 +1,7 @@
 """The full Gumbel search (cz_search_set_gumbel_full, run.py self --gumbel-full) restated in Python over gumbel_oracle: the
 definitions of include/czero.h in plain float64 -- v_mix, the improved policy, the score of the selection below the root,
-the full-mode policy target -- and a subclass of gumbel_oracle.Search that keeps every node's network value when the node
-is expanded, selects below the root by argmax pi'(a) - N(a) / (1 + sum N), and completes the target with v_mix.
+the full-mode policy target -- and a subclass of gumbel_oracle.Search that reads the network value every node of search_model
+keeps, selects below the root by argmax pi'(a) - N(a) / (1 + sum N), and completes the target with v_mix.
 
 The sums are Python's, in edge order; the device adds a lane's two edges first and then runs one ladder over the lanes,
 and its exp is another library's.  Scores so agree to ~1e-16 and not to the bit, which is why the GPU comparison rests on
@@ -11,9 +11,8 @@ import math
 
 import numpy as np
 
-import forced_playouts_oracle as fo
 import gumbel_oracle as go
-import stub_net
+import search_model as sm
 from oracle import xq_oracle as xo
 
 BANNED = go.BANNED
@@ -117,14 +116,10 @@ def target_margin(labels, n, w, p, v, c_visit, c_scale):
 
 
 # ---- the search ---------------------------------------------------------------------------------------------------------
-class _Node(fo._Node):
-    __slots__ = ("v",)                  # the network's float32 value of the position, from its mover's view
-
-
 class Search(go.Search):
-    """gumbel_oracle.Search whose nodes keep their network value; full: the rule below the root and v_mix in the target.
-    With full off it is gumbel_oracle.Search bit for bit.  After search(): in_margins, the winner's score minus the best
-    other score at every selection below the root (+inf where the node had one edge)."""
+    """gumbel_oracle.Search with, full on, the rule below the root and v_mix in the target, both over the nodes' kept
+    network values.  With full off it is gumbel_oracle.Search bit for bit.  After search(): in_margins, the winner's score
+    minus the best other score at every selection below the root (+inf where the node had one edge)."""
 
     def __init__(self, cfg, salt, k=0.0, m=0, c_visit=C_VISIT, c_scale=C_SCALE, draws=None, full=False):
         super().__init__(cfg, salt, k, m, c_visit, c_scale, draws)
@@ -143,47 +138,9 @@ class Search(go.Search):
             self.in_margins.append(margin)
         return best, False
 
-    # forced_playouts_oracle.Search._simulate, line by line, with the one addition that the new node keeps its value
-    def _simulate(self):
-        vl = self.cfg.virtual_loss
-        state, path, seen = self.root, [], []
-        while True:
-            d = xo.done(state)
-            if d[0]:
-                self.terminal_sims += 1
-                return self._backup(path, float(d[1] * 2))
-            node = self.tree.get(state)
-            if node is None:
-                node = self.tree[state] = _Node(state)
-                self.expansions += 1
-                pol, val = stub_net.hash_stub_numpy(xo.state_to_planes(state)[None], self.salt)
-                node.pending = pol[0]
-                node.v = np.float32(val[0])
-                return self._backup(path, float(val[0]))
-            if state in seen:
-                mv = node.moves[path[seen.index(state)][1]]
-                if xo.will_check_or_catch(state, mv):
-                    v = -1.0
-                elif xo.be_catched(state, mv):
-                    v = 1.0
-                else:
-                    v = 0.0
-                self.repetition_sims += 1
-                return self._backup(path, v)
-            e, forced = self._select(node, state == self.root)
-            if e < 0:
-                return self._backup(path, 0.0)
-            self.forced_picks += forced
-            node.sum_n += 1
-            node.n[e] += vl
-            node.w[e] = node.w[e] - float(vl)
-            path.append((node, e))
-            seen.append(state)
-            state = xo.step(state, node.moves[e])
-
     def search(self, state, no_act=None, increase_temp=False):
         self.in_margins = []
-        super().search(state, no_act, increase_temp)
+        return super().search(state, no_act, increase_temp)
 
     def net_value(self, state):
         """The kept float32 value of `state`, None when it is not in the tree."""
@@ -194,46 +151,26 @@ class Search(go.Search):
         if not (self.full and self.m > 0):
             return super().targets(state, no_act)
         st = self.node_stats(state)
-        lab = st["moves"].copy()
-        for i, l in enumerate(lab):
-            if xo.label_str(int(l)) in (no_act or ()):
-                lab[i] |= BANNED
-        return target_v(lab, st["n"], st["w"], st["p"], self.tree[state].v, self.c_visit, self.c_scale)
+        return target_v(sm.banned_labels(st["moves"], no_act), st["n"], st["w"], st["p"], self.tree[state].v,
+                        self.c_visit, self.c_scale)
 
 
 def run_case(case, m, sims, draws, c_visit=C_VISIT, c_scale=C_SCALE, full=True):
     """gumbel_oracle.run_case with Search above: per search its dict plus in_margins, net_value (the root's) and, for the
     position under the played move, child_state, child_stats and child_value (None where that position is terminal and so
     not in the tree).  "ban": the ban is the move an unbanned search of the same kind plays."""
-    def new():
-        return Search(fo.play_cfg(sims), case["salt"], 0.0, m, c_visit, c_scale, draws, full)
-    line = [(case["state"], [])]
-    if case["kind"] == "ban":
-        s0 = new()
-        s0.search(case["state"])
-        line = [(case["state"], [s0.played(case["state"])[0]])]
-    s = new()
-    out = []
-    while line:
-        state, no_act = line.pop(0)
-        s.search(state, no_act)
-        t, raw = s.targets(state, no_act)
-        best, margin = s.played(state, no_act)
-        child = xo.step(state, best)
-        out.append(dict(state=state, no_act=no_act, stats=s.node_stats(state), started=list(s.started),
-                        seq_used=list(s.seq_used), margins=list(s.margins), in_margins=list(s.in_margins), targets=t,
-                        raw_total=raw, best=best, best_margin=margin, budget=s.budget, net_value=s.net_value(state),
-                        child_state=child, child_stats=s.node_stats(child), child_value=s.net_value(child)))
-        if case["kind"] == "reuse" and len(out) == 1:
-            line.append((child, []))
-    return out, s
+    def row(s, state, no_act):
+        r = go.case_row(s, state, no_act)
+        child = xo.step(state, r["best"])
+        r.update(in_margins=list(s.in_margins), net_value=s.net_value(state), child_state=child,
+                 child_stats=s.node_stats(child), child_value=s.net_value(child))
+        return r
+    return sm.walk_case(case, lambda: Search(sm.play_cfg(sims), case["salt"], 0.0, m, c_visit, c_scale, draws, full), row)
 
 
 def gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit=C_VISIT, c_scale=C_SCALE, init_state=None, full=True):
-    """gumbel_oracle.gumbel_selfplay_game played by Search above: the loop is that function's own -- it builds its player
-    through the module's name `Search`, which is pointed at this file's class for the call -- so the plies' targets are
-    the full-mode ones.  The result gains `in_margins`, every margin below the root of the whole game, and `margins` /
-    `best_margins`, the root's."""
+    """gumbel_oracle.gumbel_selfplay_game played by Search above, so the plies' targets are the full-mode ones.  The
+    result gains `in_margins`, every margin below the root of the whole game, and `margins` / `best_margins`, the root's."""
     log = dict(in_margins=[], margins=[], best_margins=[])
 
     class Player(Search):
@@ -241,24 +178,16 @@ def gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit=C_VISIT, c_s
             super().__init__(*a, full=full, **kw)
 
         def search(self, state, no_act=None, increase_temp=False):
-            super().search(state, no_act, increase_temp)
+            ran = super().search(state, no_act, increase_temp)
             log["in_margins"] += self.in_margins
             log["margins"] += self.margins
+            return ran
 
         def played(self, state, no_act=None):
             mv, margin = super().played(state, no_act)
             log["best_margins"].append(margin)
             return mv, margin
 
-    # CAUTION: this rebinds a module global of gumbel_oracle for the duration of the call.  It reaches only code that looks
-    # `Search` up in that module at call time, as gumbel_selfplay_game does -- a `from gumbel_oracle import Search`
-    # elsewhere keeps the plain class -- and a process interrupted inside the call (not an exception: `finally` restores
-    # it) leaves the global changed.  Single-threaded test code only.
-    plain = go.Search
-    go.Search = Player
-    try:
-        out = go.gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit, c_scale, init_state)
-    finally:
-        go.Search = plain
+    out = go.gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit, c_scale, init_state, player=Player)
     out.update(log)
     return out

@@ -1,7 +1,7 @@
 """Gumbel root search with sequential halving (cz_search_set_gumbel, run.py self --gumbel M) restated in Python: the
 definitions of include/czero.h in plain float64 -- seq, the score, the policy target -- a subclass of
-forced_playouts_oracle.Search (one search thread, no root noise) with the root rule, `started`, the played move and the
-target, and a self-play loop over it on the model of playout_cap_oracle.capped_selfplay_game.
+search_model.Search (one search thread, no root noise) with the root rule, `started`, the played move and the
+target, and such a search as the player of selfplay_oracle.start_game.
 
 The search takes the ply's Gumbel draws as an INPUT array (edge index -> g): a GPU test feeds it what the device drew, so
 that the comparison is about the search; draws_for() restates the device's generator for the tests of the draws
@@ -12,11 +12,12 @@ import math
 
 import numpy as np
 
-import forced_playouts_oracle as fo
+import search_model as sm
+import selfplay_oracle
 import stub_net
-from oracle import xq_oracle as xo
+from oracle import xq_oracle as xo            # (the tests reach it as go.xo)
 
-BANNED = fo.BANNED
+BANNED = sm.BANNED
 INF = float("inf")
 GUMBEL_STREAM = 4           # stream 0: the per-game lotteries, 1: the move choice, 2: the playout cap, 3: the leaf mirror
 C_VISIT, C_SCALE = 50.0, 1.0
@@ -96,11 +97,11 @@ def target(labels, n, w, p, c_visit=C_VISIT, c_scale=C_SCALE):
 
 
 # ---- the search ---------------------------------------------------------------------------------------------------------
-class Search(fo.Search):
-    """fo.Search with the Gumbel rule at the root.  m = 0 is fo.Search.  draws: the ply's g array (128 entries), or a
-    callable(search index) -> array for searches whose plies differ in their draws.  After search(): started (per root
-    edge), seq_used (the schedule value of every root selection, in order), margins (winner's score minus the best other
-    eligible score, +inf when it stood alone)."""
+class Search(sm.Search):
+    """search_model.Search with the Gumbel rule at the root.  m = 0 is that search.  draws: the ply's g array (128
+    entries), or a callable(search index) -> array for searches whose plies differ in their draws.  After search():
+    started (per root edge), seq_used (the schedule value of every root selection, in order), margins (winner's score
+    minus the best other eligible score, +inf when it stood alone)."""
 
     def __init__(self, cfg, salt, k=0.0, m=0, c_visit=C_VISIT, c_scale=C_SCALE, draws=None):
         super().__init__(cfg, salt, k)
@@ -139,19 +140,19 @@ class Search(fo.Search):
         self.started[best] += 1
         return best, False
 
-    def search(self, state, no_act=None, increase_temp=False):
-        sims = self.cfg.simulation_num_per_move
-        done_n = self.tree[state].sum_n if state in self.tree else 0
-        if no_act or increase_temp or done_n == sims:
-            done_n = 0
-        self.budget = max(0, sims - done_n)
+    def begin_ply(self, state, no_act=None, increase_temp=False):
+        self.budget = super().begin_ply(state, no_act, increase_temp)
         d = self.draws(self.searches) if callable(self.draws) else self.draws
         self.g = None if d is None else np.asarray(d, dtype=np.float64)
         self.started, self.seq_used, self.margins = None, [], []
         self.searches += 1
-        super().search(state, no_act, increase_temp)
+        return self.budget
+
+    def search(self, state, no_act=None, increase_temp=False):
+        ran = super().search(state, no_act, increase_temp)
         if self.started is None and state in self.tree:
             self.started = [0] * len(self.tree[state].moves)
+        return ran
 
     def played(self, state, no_act=None):
         """(the move a Gumbel ply plays, its margin over the best other edge of greatest started)."""
@@ -176,11 +177,7 @@ class Search(fo.Search):
         if self.m <= 0:
             return super().targets(state, no_act)
         st = self.node_stats(state)
-        lab = st["moves"].copy()
-        for i, l in enumerate(lab):
-            if xo.label_str(int(l)) in (no_act or ()):
-                lab[i] |= BANNED
-        return target(lab, st["n"], st["w"], st["p"], self.c_visit, self.c_scale)
+        return target(sm.banned_labels(st["moves"], no_act), st["n"], st["w"], st["p"], self.c_visit, self.c_scale)
 
     def max_q(self, state, no_act=None):
         """choose_action's resign statistic: the greatest q over the non-banned edges, -100 without one."""
@@ -189,50 +186,35 @@ class Search(fo.Search):
         return max(qs, default=-100.0)
 
 
+def case_row(s, state, no_act):
+    """What run_case reports of one search."""
+    t, raw = s.targets(state, no_act)
+    best, margin = s.played(state, no_act)
+    return dict(state=state, no_act=no_act, stats=s.node_stats(state), started=list(s.started),
+                seq_used=list(s.seq_used), margins=list(s.margins), targets=t, raw_total=raw, best=best,
+                best_margin=margin, budget=s.budget)
+
+
 def run_case(case, m, sims, draws, c_visit=C_VISIT, c_scale=C_SCALE):
     """The searches of one of fo.cases() with the Gumbel rule: list of dict(state, no_act, stats, started, seq_used,
     margins, targets, raw_total, best, best_margin, budget) -- two for "reuse" -- plus the Search object.  "ban": the ban
     is the move an unbanned Gumbel search of the position plays."""
-    def new():
-        return Search(fo.play_cfg(sims), case["salt"], 0.0, m, c_visit, c_scale, draws)
-    line = [(case["state"], [])]
-    if case["kind"] == "ban":
-        s0 = new()
-        s0.search(case["state"])
-        line = [(case["state"], [s0.played(case["state"])[0]])]
-    s = new()
-    out = []
-    while line:
-        state, no_act = line.pop(0)
-        s.search(state, no_act)
-        t, raw = s.targets(state, no_act)
-        best, margin = s.played(state, no_act)
-        out.append(dict(state=state, no_act=no_act, stats=s.node_stats(state), started=list(s.started),
-                        seq_used=list(s.seq_used), margins=list(s.margins), targets=t, raw_total=raw, best=best,
-                        best_margin=margin, budget=s.budget))
-        if case["kind"] == "reuse" and len(out) == 1:
-            line.append((xo.step(state, best), []))
-    return out, s
+    return sm.walk_case(case, lambda: Search(sm.play_cfg(sims), case["salt"], 0.0, m, c_visit, c_scale, draws), case_row)
 
 
 # ---- self-play ------------------------------------------------------------------------------------------------------------
-def gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit=C_VISIT, c_scale=C_SCALE, init_state=None):
-    """One self-play game of the engine with the Gumbel root search, search_threads = 1: capped_selfplay_game's loop
-    (SelfPlayWorker.start_game, self_play.py:95-212) with Search above as the player -- ONE player for the whole game, the
-    tree carried from ply to ply -- and choose_action's resign test in front of the played move.  No temperature, no
-    noise.  Returns selfplay_game's dict plus `plies`: per searched ply dict(state, labels, banned, targets, raw_total,
-    started, sum_n, resign)."""
-    enable_resign = xo.philox_uniform(seed, game_id, 0, 0) > cfg.enable_resign_rate
+def gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit=C_VISIT, c_scale=C_SCALE, init_state=None, player=None):
+    """One self-play game of the engine with the Gumbel root search, search_threads = 1: selfplay_oracle.start_game with
+    Search above (or the subclass `player`) as the player -- ONE player for the whole game, the tree carried from ply to
+    ply -- and choose_action's resign test in front of the played move.  No temperature, no noise.  Returns
+    selfplay_game's dict plus `plies`: per searched ply dict(state, labels, banned, targets, raw_total, started, sum_n,
+    resign)."""
+    enable_resign = selfplay_oracle.resign_enabled(cfg, seed, game_id)
     turns_box = [0]
-    pl = Search(cfg, salt, 0.0, m, c_visit, c_scale, draws=lambda _: draws_for(seed, game_id, slot, turns_box[0]))
-    state = init_state or xo.INIT_STATE
-    history = [state]
-    value = turns = no_eat_count = 0
-    game_over = check = resigned = False
-    final_move = None
-    no_act, increase_temp = [], False
+    pl = (player or Search)(cfg, salt, 0.0, m, c_visit, c_scale, draws=lambda _: draws_for(seed, game_id, slot, turns_box[0]))
     plies = []
-    while not game_over:
+
+    def ply(state, turns, no_act, increase_temp):
         turns_box[0] = turns
         pl.search(state, no_act, increase_temp)
         st = pl.node_stats(state)
@@ -241,44 +223,8 @@ def gumbel_selfplay_game(cfg, salt, seed, game_id, slot, m, c_visit=C_VISIT, c_s
         action = None if resign else pl.played(state, no_act)[0]
         plies.append(dict(state=state, labels=st["moves"], banned=np.array([mv in no_act for mv in pl.tree[state].moves]),
                           targets=t, raw_total=raw, started=list(pl.started), sum_n=st["sum_n"], resign=resign))
-        if action is None:
-            value, resigned = -1, True
-            break
-        history.append(action)
-        state, no_eat = xo.new_step(state, action)
-        turns += 1
-        no_eat_count = no_eat_count + 1 if no_eat else 0
-        history.append(state)
-        if no_eat_count >= 120 or turns / 2 >= cfg.max_game_length:
-            game_over, value = True, 0
-        else:
-            d = xo.done(state, need_check=True)
-            game_over, value, final_move = d[0], d[1], d[2]
-            check = d[3] if len(d) > 3 else False
-            if not game_over and not xo.has_attack_chessman(state):
-                game_over, value = True, 0
-            increase_temp, no_act = False, []
-            if not game_over and not check and state in history[:-1]:
-                free_move = 0
-                for i in range(len(history) - 1):
-                    if history[i] == state:
-                        if xo.will_check_or_catch(state, history[i + 1]):
-                            no_act.append(history[i + 1])
-                        elif not xo.be_catched(state, history[i + 1]):
-                            increase_temp = True
-                            free_move += 1
-                            if free_move >= 3:
-                                game_over, value = True, 0
-                                break
-    searched = turns
-    if final_move:
-        history.append(final_move)
-        state = xo.step(state, final_move)
-        turns += 1
-        value = -value
-        history.append(state)
-    if turns % 2 == 1:
-        value = -value
-    store = xo.philox_uniform(seed, game_id, 0, 1) > 0.9 if turns < 10 else True
-    return dict(init_state=history[0], moves=history[1::2], value=value, turns=turns, store=bool(store), searched=searched,
-                resigned=resigned, final_state=state, plies=plies)
+        return action
+
+    out = selfplay_oracle.start_game(cfg, seed, game_id, ply, init_state)
+    out["plies"] = plies
+    return out

@@ -1,7 +1,7 @@
 """Playout cap randomization (cz_search_set_playout_cap, run.py self --fast-sims N --full-rate P) restated over the oracle:
-tests/selfplay_oracle.py's selfplay_game -- ONE oracle player for the whole game, the tree carried from ply to ply -- with
-the ply's budget written into that player's own copy of the configuration before every action() call.  Nothing else of
-the loop changes: move choice, game rules and the store lottery are selfplay_game's, line for line.
+tests/selfplay_oracle.py's start_game played as selfplay_game plays it -- ONE oracle player for the whole game, the tree
+carried from ply to ply -- with the ply's budget written into that player's own copy of the configuration before every
+action() call.  Move choice, game rules and the store lottery are the same code as selfplay_game's.
 
 The lottery, as in the engine: ply `turns` of game `game_id` is a full search iff
 philox(seed, game_id, stream 2, draw turns) < full_rate; rates 0 and 1 draw nothing; fast_sims = 0 switches the cap off.
@@ -49,22 +49,17 @@ def capped_selfplay_game(cfg, stub, seed, game_id, fast_sims, full_rate, init_st
         raise ValueError(f"fast_sims {fast_sims} outside 1 .. {cfg.simulation_num_per_move}")
     if cfg.noise_eps != 0.0:
         raise ValueError("the capped oracle needs noise_eps = 0 (fast plies have no root noise, full plies would)")
-    enable_resign = xo.philox_uniform(seed, game_id, 0, 0) > cfg.enable_resign_rate            # :102-105
-    pl = xo.Player(cfg, stub, enable_resign=enable_resign, seed=seed, game_id=game_id)
+    pl = xo.Player(cfg, stub, enable_resign=so.resign_enabled(cfg, seed, game_id), seed=seed, game_id=game_id)
     inner = _player_cfg(pl, cfg)
     full_sims = cfg.simulation_num_per_move
-    state = init_state or xo.INIT_STATE                                                         # :110
-    history = [state]
-    value = turns = no_eat_count = 0
-    game_over = check = resigned = False
-    final_move = None
-    no_act, increase_temp = [], False
     fast, sum_n, idle_fast = [], [], 0
-    while not game_over:
+
+    def ply(state, turns, no_act, increase_temp):
+        nonlocal idle_fast
         full = ply_is_full(seed, game_id, turns, fast_sims, full_rate)
         inner.simulation_num_per_move = full_sims if full else fast_sims
         before = pl.counters()["sims"]
-        action, _ = pl.action(state, turns, no_act, increase_temp, xo.philox_uniform(seed, game_id, 1, turns))   # :124
+        action, _ = pl.action(state, turns, no_act, increase_temp, xo.philox_uniform(seed, game_id, 1, turns))
         st = pl.node_stats(state)
         fast.append(not full)
         sum_n.append(st["sum_n"])
@@ -73,51 +68,13 @@ def capped_selfplay_game(cfg, stub, seed, game_id, fast_sims, full_rate, init_st
         if trace is not None:
             trace.append(dict(state=state, action=action, moves=st["moves"], n=st["n"], sum_n=st["sum_n"],
                               no_act=list(no_act), inc=increase_temp, fast=not full))
-        if action is None:                                                                      # :126-129
-            value, resigned = -1, True
-            break
-        history.append(action)
-        state, no_eat = xo.new_step(state, action)                                              # :136
-        turns += 1
-        no_eat_count = no_eat_count + 1 if no_eat else 0
-        history.append(state)
-        if no_eat_count >= 120 or turns / 2 >= cfg.max_game_length:                             # :149-151
-            game_over, value = True, 0
-        else:
-            d = xo.done(state, need_check=True)                                                 # :153
-            game_over, value, final_move = d[0], d[1], d[2]
-            check = d[3] if len(d) > 3 else False
-            if not game_over and not xo.has_attack_chessman(state):                             # :154-158
-                game_over, value = True, 0
-            increase_temp, no_act = False, []
-            if not game_over and not check and state in history[:-1]:                           # :161-175
-                free_move = 0
-                for i in range(len(history) - 1):
-                    if history[i] == state:
-                        if xo.will_check_or_catch(state, history[i + 1]):
-                            no_act.append(history[i + 1])
-                        elif not xo.be_catched(state, history[i + 1]):
-                            increase_temp = True
-                            free_move += 1
-                            if free_move >= 3:
-                                game_over, value = True, 0
-                                break
-    searched = turns
-    if final_move:                                                                              # :177-184
-        history.append(final_move)
-        state = xo.step(state, final_move)
-        turns += 1
-        value = -value
-        history.append(state)
-    sims = pl.counters()["sims"]
+        return action
+
+    out = so.start_game(cfg, seed, game_id, ply, init_state)
+    out.update(fast=fast, sum_n=sum_n, sims=pl.counters()["sims"], idle_fast=idle_fast)
     inner.simulation_num_per_move = full_sims
     pl.close()
-    if turns % 2 == 1:                                                                          # :190-191
-        value = -value
-    store = xo.philox_uniform(seed, game_id, 0, 1) > 0.9 if turns < 10 else True                # :194-200
-    return dict(init_state=history[0], moves=history[1::2], value=value, turns=turns, store=bool(store),
-                searched=searched, resigned=resigned, final_state=state, fast=fast, sum_n=sum_n, sims=sims,
-                idle_fast=idle_fast)
+    return out
 
 
 def move_flags(ref):

@@ -1,6 +1,8 @@
-"""SelfPlayWorker.start_game (reference worker/self_play.py:95-212) restated in Python over ONE oracle player and the
-oracle's rule functions (test infrastructure), with the start position as an argument: what `senv.INIT_STATE` is to the
-reference.  tests/test_selfplay_oracle_cpu.py pins it to the C restatement (oracle xqo_selfplay_game, itself pinned to
+"""SelfPlayWorker.start_game (reference worker/self_play.py:95-212) restated in Python over the oracle's rule functions
+(test infrastructure), with the start position as an argument -- what `senv.INIT_STATE` is to the reference -- and the
+player as a callable: start_game is the loop, once, and selfplay_game plays it with ONE oracle player; the capped and the
+Gumbel games (playout_cap_oracle, gumbel_oracle) bring their own.  tests/test_selfplay_oracle_cpu.py pins selfplay_game
+to the C restatement (oracle xqo_selfplay_game, itself pinned to
 games recorded from the reference) from INIT_STATE, and to the reference's own games from other positions
 (tests/golden/book_games.json, K = 1); the GPU's book games are then compared with it for K > 1, where the reference
 is racy and parity is defined by the canonical order.
@@ -28,12 +30,15 @@ def book_lottery(seed, game_id, rate):
     return rate >= 1.0 or xo.philox_uniform(seed, game_id, 0, 2) < rate
 
 
-def selfplay_game(cfg, stub, seed, game_id, init_state=None, trace=None):
-    """cfg: xo.PlayCfg.  Returns dict(init_state, moves [labels as strings], value (from the first mover's view), turns,
-    store, searched (action() calls that returned a move), resigned); `trace` (a list) receives one dict per action()
-    call: state, action, the root's moves and visit counts."""
-    enable_resign = xo.philox_uniform(seed, game_id, 0, 0) > cfg.enable_resign_rate            # :102-105
-    pl = xo.Player(cfg, stub, enable_resign=enable_resign, seed=seed, game_id=game_id)
+def resign_enabled(cfg, seed, game_id):
+    """The game's resign lottery, :102-105."""
+    return xo.philox_uniform(seed, game_id, 0, 0) > cfg.enable_resign_rate
+
+
+def start_game(cfg, seed, game_id, ply, init_state=None):
+    """The loop.  ply(state, turns, no_act, increase_temp) -> the move of the position, None to resign: the player's
+    action() (:124).  Returns dict(init_state, moves [labels as strings], value (from the first mover's view), turns,
+    store, searched (ply() calls that returned a move), resigned, final_state)."""
     state = init_state or xo.INIT_STATE                                                         # :110
     history = [state]
     value = turns = no_eat_count = 0
@@ -41,11 +46,7 @@ def selfplay_game(cfg, stub, seed, game_id, init_state=None, trace=None):
     final_move = None
     no_act, increase_temp = [], False
     while not game_over:
-        action, _ = pl.action(state, turns, no_act, increase_temp, xo.philox_uniform(seed, game_id, 1, turns))   # :124
-        if trace is not None:
-            st = pl.node_stats(state)
-            trace.append(dict(state=state, action=action, moves=st["moves"], n=st["n"], sum_n=st["sum_n"],
-                              no_act=list(no_act), inc=increase_temp))
+        action = ply(state, turns, no_act, increase_temp)                                       # :124
         if action is None:                                                                      # :126-129
             value, resigned = -1, True
             break
@@ -82,9 +83,26 @@ def selfplay_game(cfg, stub, seed, game_id, init_state=None, trace=None):
         turns += 1
         value = -value
         history.append(state)
-    pl.close()
     if turns % 2 == 1:                                                                          # :190-191
         value = -value
     store = xo.philox_uniform(seed, game_id, 0, 1) > 0.9 if turns < 10 else True                # :194-200
     return dict(init_state=history[0], moves=history[1::2], value=value, turns=turns, store=bool(store),
                 searched=searched, resigned=resigned, final_state=state)
+
+
+def selfplay_game(cfg, stub, seed, game_id, init_state=None, trace=None):
+    """start_game played by ONE oracle player.  cfg: xo.PlayCfg.  Returns start_game's dict; `trace` (a list) receives
+    one dict per action() call: state, action, the root's moves and visit counts."""
+    pl = xo.Player(cfg, stub, enable_resign=resign_enabled(cfg, seed, game_id), seed=seed, game_id=game_id)
+
+    def ply(state, turns, no_act, increase_temp):
+        action, _ = pl.action(state, turns, no_act, increase_temp, xo.philox_uniform(seed, game_id, 1, turns))
+        if trace is not None:
+            st = pl.node_stats(state)
+            trace.append(dict(state=state, action=action, moves=st["moves"], n=st["n"], sum_n=st["sum_n"],
+                              no_act=list(no_act), inc=increase_temp))
+        return action
+
+    out = start_game(cfg, seed, game_id, ply, init_state)
+    pl.close()
+    return out

@@ -1,4 +1,4 @@
-"""The MCTS solver (cz_search_set_solver, run.py self / eval --solver) restated in Python: forced_playouts_oracle.Search
+"""The MCTS solver (cz_search_set_solver, run.py self / eval --solver) restated in Python: search_model.Search
 -- the reference's search for one search thread without root noise -- with the definitions of include/czero.h ("MCTS
 solver") in it, and a depth-limited minimax over the oracle's rule functions as the independent yardstick of soundness.
 
@@ -17,10 +17,7 @@ tests/test_solver_cpu.py pins Search(solver=False) to fo.Search bit for bit befo
 import json
 import os
 
-import numpy as np
-
-import forced_playouts_oracle as fo
-import stub_net
+import search_model as sm
 from oracle import xq_oracle as xo
 
 OPEN, WIN, LOSS = 0, 1, 2
@@ -46,20 +43,20 @@ def winning_edge(marks, dists, banned):
     return min(cand)[1] if cand else -1
 
 
-class _Node(fo._Node):
-    __slots__ = ("state", "term", "mark", "status", "dist")
+class _Node(sm.Node):
+    __slots__ = ("term", "mark", "status", "dist")
 
     def __init__(self, state):
         super().__init__(state)
-        self.state = state
         self.term = [OPEN] * len(self.moves)    # WIN / LOSS: the child is terminal (CHILD_TERM_WIN / CHILD_TERM_LOSS)
         self.mark = [OPEN] * len(self.moves)    # the edge mark of a child that is a node
         self.status, self.dist = OPEN, 0
 
 
-class Search(fo.Search):
-    """fo.Search(k = 0) with the solver.  solver=False: every solver rule is off, the search is fo.Search's.
+class Search(sm.Search):
+    """search_model.Search(k = 0) with the solver.  solver=False: every solver rule is off, the search is that one.
     proven_sims counts the descents that ended on a proven node."""
+    node_cls = _Node
 
     def __init__(self, cfg, salt, k=0.0, solver=True):
         if k:
@@ -79,9 +76,6 @@ class Search(fo.Search):
             return self.tree[xo.step(node.state, node.moves[e])].dist
         return 0
 
-    def _banned(self, node, is_root):
-        return [is_root and mv in self.no_act for mv in node.moves]
-
     def rule1(self, node, is_root=True):
         nm = len(node.moves)
         return winning_edge([self.edge_mark(node, j) for j in range(nm)], [self.edge_dist(node, j) for j in range(nm)],
@@ -98,35 +92,7 @@ class Search(fo.Search):
         losing = [self.edge_mark(node, j) == WIN for j in range(len(node.moves))]
         all_losing = all(l for l, b in zip(losing, banned) if not b)
         skip = [b or (l and not all_losing) for l, b in zip(losing, banned)]
-        return self._select_reference(node, is_root, skip)
-
-    def _select_reference(self, node, is_root, skip):
-        """fo.Search._select at k = 0, over the edges that `skip` leaves."""
-        import math
-        cfg = self.cfg
-        xx = math.sqrt(float(node.sum_n + 1))
-        if node.pending is not None:
-            node.spread()
-        best, best_score = -1, -99999999.0
-        for i in range(len(node.moves)):
-            if skip[i]:
-                continue
-            n = node.n[i]
-            q = node.w[i] / float(n) if n else 0.0
-            if is_root:
-                a = np.float32(np.float32(1.0 - cfg.noise_eps) * node.p[i])
-                u = cfg.c_puct * float(a) * xx / float(1 + n)
-            else:
-                a = np.float32(np.float32(cfg.c_puct) * node.p[i])
-                u = float(a) * xx / float(1 + n)
-            score = q + u
-            if q > (1.0 - 1e-7):
-                return i, False
-            if not score >= -99999999.0:
-                continue
-            if score >= best_score:
-                best, best_score = i, score
-        return best, False
+        return self._puct(node, is_root, skip)
 
     # ---- marking and deriving, after the backup of a +-2 ----
     def _walk(self, path, status):
@@ -143,51 +109,22 @@ class Search(fo.Search):
             node.status, node.dist = st, d
             status = st
 
-    # ---- MCTS_search with the terminal codes, the arrival and the walk ----
-    def _simulate(self):
-        vl = self.cfg.virtual_loss
-        state, path, seen = self.root, [], []
-        while True:
-            d = xo.done(state)
-            if d[0]:
-                self.terminal_sims += 1
-                if path:
-                    path[-1][0].term[path[-1][1]] = WIN if d[1] > 0 else LOSS
-                self._backup(path, float(d[1] * 2))
-                if self.solver and path:
-                    self._walk(path, WIN if d[1] > 0 else LOSS)
-                return
-            node = self.tree.get(state)
-            if node is None:
-                node = self.tree[state] = _Node(state)
-                self.expansions += 1
-                pol, val = stub_net.hash_stub_numpy(xo.state_to_planes(state)[None], self.salt)
-                node.pending = pol[0]
-                return self._backup(path, float(val[0]))
-            if state in seen:
-                mv = node.moves[path[seen.index(state)][1]]
-                if xo.will_check_or_catch(state, mv):
-                    v = -1.0
-                elif xo.be_catched(state, mv):
-                    v = 1.0
-                else:
-                    v = 0.0
-                self.repetition_sims += 1
-                return self._backup(path, v)
-            if self.solver and path and node.status != OPEN:        # arrival
-                self.proven_sims += 1
-                self._backup(path, 2.0 if node.status == WIN else -2.0)
-                self._walk(path, node.status)
-                return
-            e, _ = self._select(node, state == self.root)
-            if e < 0:
-                return self._backup(path, 0.0)
-            node.sum_n += 1
-            node.n[e] += vl
-            node.w[e] = node.w[e] - float(vl)
-            path.append((node, e))
-            seen.append(state)
-            state = xo.step(state, node.moves[e])
+    # ---- the simulation's hooks: the terminal codes, the arrival and the walk ----
+    def _terminal(self, path, value):
+        status = WIN if value > 0 else LOSS
+        if path:
+            path[-1][0].term[path[-1][1]] = status
+        super()._terminal(path, value)
+        if self.solver and path:
+            self._walk(path, status)
+
+    def _arrive(self, node, path):
+        if not (self.solver and path and node.status != OPEN):
+            return False
+        self.proven_sims += 1
+        self._backup(path, 2.0 if node.status == WIN else -2.0)
+        self._walk(path, node.status)
+        return True
 
     # ---- the decided root ----
     def decided(self):
@@ -197,14 +134,9 @@ class Search(fo.Search):
         return node.status == LOSS or (node.status == WIN and self.rule1(node) >= 0)
 
     def search(self, state, no_act=None, increase_temp=False):
-        """fo.Search.search, stopping at a decided root.  Returns the number of simulations run."""
-        sims = self.cfg.simulation_num_per_move
-        self.root, self.no_act = state, tuple(no_act or ())
-        done_n = self.tree[state].sum_n if state in self.tree else 0
-        if self.no_act or increase_temp or done_n == sims:
-            done_n = 0
+        """The model's search, stopping at a decided root."""
         ran = 0
-        for _ in range(max(0, sims - done_n)):
+        for _ in range(self.begin_ply(state, no_act, increase_temp)):
             if self.decided():
                 break
             self._simulate()
@@ -282,7 +214,7 @@ def positions():
 
 
 def play_cfg(sims):
-    return fo.play_cfg(sims)
+    return sm.play_cfg(sims)
 
 
 def proven_nodes(search, max_dist=5):

@@ -1,5 +1,5 @@
 """The early stop of a settled ply (cz_search_set_kld_gain, cz_search_set_smart_pruning; run.py self --kld-gain, run.py eval
---smart-pruning) restated in Python: forced_playouts_oracle.Search -- one search thread, the hash stub as network -- with the
+--smart-pruning) restated in Python: search_model.Search -- one search thread, the hash stub as network -- with the
 two rules of include/czero.h word for word at the one test point, before a simulation is started (K = 1: a batch is one
 simulation, nothing is in flight between two of them).
 
@@ -8,7 +8,7 @@ import math
 
 import numpy as np
 
-import forced_playouts_oracle as fo
+import search_model as sm
 from oracle import xq_oracle as xo
 
 KLD, LEAD = "kld", "lead"
@@ -58,8 +58,8 @@ def top_two(n, banned):
     return (live + [0, 0])[0], (live + [0, 0])[1]
 
 
-class Search(fo.Search):
-    """fo.Search with the stop rules.  gain G (0 = the KLD rule is off) and interval I; lead: the unreachable-lead rule is
+class Search(sm.Search):
+    """search_model.Search with the stop rules.  gain G (0 = the KLD rule is off) and interval I; lead: the unreachable-lead rule is
     on; evaluate: config.opts.evaluate of the engine (tau).  measure=True takes every checkpoint and never ends a ply: the
     uncut gain sequence.  After search(): ran (simulations run), cut (None, KLD or LEAD), sims_cut (the budget not started),
     checks (checkpoints of the ply, the one that took the first snapshot included), last_gain (None: nothing measured) and
@@ -101,13 +101,8 @@ class Search(fo.Search):
         return None
 
     def search(self, state, no_act=None, increase_temp=False, turns=0):
-        """fo.Search.search with the test point before every simulation.  Returns the number of simulations run."""
-        sims = self.cfg.simulation_num_per_move
-        self.root, self.no_act = state, tuple(no_act or ())
-        done_n = self.tree[state].sum_n if state in self.tree else 0
-        if self.no_act or increase_temp or done_n == sims:
-            done_n = 0
-        budget = max(0, sims - done_n)
+        """The model's search with the test point before every simulation."""
+        budget = self.begin_ply(state, no_act, increase_temp)
         tau = ply_tau(self.cfg, turns, increase_temp, self.evaluate)
         self._snap = None                                   # the snapshot is empty when the ply's search begins
         self.ran, self.cut, self.sims_cut, self.checks, self.last_gain, self.checkpoints = 0, None, 0, 0, None, []
@@ -151,10 +146,10 @@ _MATES = ("m1", "m2", "wide_m2")
 
 
 def positions():
-    """(name, state, salt): the nine fo.cases() positions and three mates of tests/golden/solver_positions.json."""
+    """(name, state, salt): the nine sm.cases() positions and three mates of tests/golden/solver_positions.json."""
     import solver_oracle as so
     mates = {p["name"]: p for p in so.positions()}
-    return [("fo:" + c["name"], c["state"], c["salt"]) for c in fo.cases()] + [(n, mates[n]["state"], SALT) for n in _MATES]
+    return [("fo:" + c["name"], c["state"], c["salt"]) for c in sm.cases()] + [(n, mates[n]["state"], SALT) for n in _MATES]
 
 
 _UNCUT = {}
@@ -164,7 +159,7 @@ def uncut(name, state, salt, interval, budget=BUDGET):
     """The measuring search of a position: its Search object (checkpoints = the uncut gain sequence)."""
     key = (name, interval, budget)
     if key not in _UNCUT:
-        s = Search(fo.play_cfg(budget), salt, interval=interval, measure=True)
+        s = Search(sm.play_cfg(budget), salt, interval=interval, measure=True)
         s.search(state)
         _UNCUT[key] = s
     return _UNCUT[key]
@@ -217,7 +212,7 @@ def line_cases():
         state, salt = pos[name]
         bans = None
         if ban_ply is not None:
-            free = Search(fo.play_cfg(LINE_SIMS), salt, gain=LINE_G, interval=LINE_I).play_line(state, ban_ply + 1)
+            free = Search(sm.play_cfg(LINE_SIMS), salt, gain=LINE_G, interval=LINE_I).play_line(state, ban_ply + 1)
             bans = {ban_ply: [free[ban_ply]["move"]]}
         out.append((name, state, salt, bans))
     return out
