@@ -30,6 +30,7 @@ VISIT_FAST = 2           # visit entry flag: the ply was a fast search
 VISIT_PRUNED = 4         # visit entry flag: n holds the pruned policy targets (cz_search_set_forced_playouts)
 VISIT_GUMBEL = 8         # visit entry flag: n holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
 VISIT_EARLY = 16         # visit entry flag: a stop rule ended the ply before its budget (cz_search_set_kld_gain)
+VISIT_NO_RESIGN = 32     # visit entry flag (record_maxq on only): the game plays on without resignation
 GUMBEL_MAX_M = 128       # include/czero.h CZ_GUMBEL_MAX_M
 EVAL_CACHE_STRIDE = 576  # include/czero.h CZ_EVAL_CACHE_STRIDE: bytes per entry of the evaluation cache
 PROOF_OPEN, PROOF_WIN, PROOF_LOSS = 0, 1, 2   # include/czero.h CZ_PROOF_*: a position's status from its mover's view
@@ -50,9 +51,11 @@ def check_eval_cache_log2(log2_entries, what="eval_cache"):
 # (record_values; None with the value record off and where the ring held NaN, "no value"); s, the policy surprise of the
 # ply, KL(recorded counts || priors without noise) (record_surprise; None with that record off and for NaN); gumbel, whether
 # the ply was a Gumbel root search (set_gumbel): n then holds the policy target scaled to 65536, raw_total as for pruned.
-# early, whether a stop rule (set_kld_gain, set_smart_pruning) ended the ply before its budget.
-VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel early",
-                        defaults=(None, None, False, False))
+# early, whether a stop rule (set_kld_gain, set_smart_pruning) ended the ply before its budget.  maxq, the number the ply's
+# resignation test compared (record_maxq; None with that record off and for NaN), and no_resign, whether the game plays on
+# without resignation (False with the record off).
+VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel early maxq no_resign",
+                        defaults=(None, None, False, False, None, False))
 
 
 class SearchCfg(C.Structure):
@@ -115,6 +118,11 @@ def declare(L):
         "cz_search_drain_visits_qs": [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
         "cz_search_root_surprise": [vp, vp, vp],
         "cz_root_surprise": [vp, vp, vp, vp, i32, vp, vp],
+        "cz_search_record_maxq": [vp, i32, vp],
+        "cz_search_drain_visits_qsm": [vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
+        "cz_search_root_maxq": [vp, vp, vp],
+        "cz_root_maxq": [vp, vp, vp, vp, i32, vp, vp],
+        "cz_search_set_resign_threshold": [vp, d, vp],
         "cz_search_set_leaf_mirror": [vp, d, vp, vp],
         "cz_search_set_gumbel": [vp, i32, d, d, vp],
         "cz_search_root_started": [vp, vp, vp],
@@ -232,6 +240,8 @@ class Search:
         self.visit_capacity = 0                # record_visits(): entries the device ring holds, 0 = off
         self.values_on = False                 # record_values(): every entry comes with the root's search value
         self.surprise_on = False               # record_surprise(): every entry comes with the ply's policy surprise
+        self.maxq_on = False                   # record_maxq(): every entry comes with the resignation test's max q
+        self.resign_threshold = float(pc.resign_threshold)     # set_resign_threshold() replaces it
         self._visits = {}                      # game id -> [(ply, raw entry)] of games not finished yet
         self._raw_visits = []                  # fetched entries not yet sorted by game (pull_visits(defer=True))
         self._visits_dropped = 0
@@ -319,6 +329,7 @@ class Search:
         self.visit_capacity = (int(capacity) or 64 * self.G) if on else 0
         self.values_on = False                 # (the library frees the value ring with the visit ring)
         self.surprise_on = False               # (and the surprise ring)
+        self.maxq_on = False                   # (and the max-q ring)
         self._visits = {}
         self._raw_visits = []
         self._visits_dropped = 0
@@ -557,6 +568,31 @@ class Search:
         (cz_search_root_surprise; bans of the current set_roots, the counts of root_targets): float64 [G], NaN = none."""
         return self._root_outputs("cz_search_root_surprise", ((self.G,), "float64"))[0]
 
+    def record_maxq(self, on=True):
+        """Self-play: every visit entry comes with the number its ply's resignation test compared with the threshold, the
+        maximum of w / n over the non-banned root edges (cz_search_record_maxq; include/czero.h has the arithmetic):
+        VisitEntry.maxq; and the entries of games that play on without resignation say so (VisitEntry.no_resign).  Needs
+        record_visits() on, and a later record_visits() call switches it off again.  Call it before start_selfplay() and
+        before a graph capture.  Entries fetched before the switch keep what they had."""
+        if not hasattr(self.L, "cz_search_record_maxq"):
+            raise _native.NativeError("this libczero.so has no max-q record (cz_search_record_maxq)")
+        _native.check(self.L.cz_search_record_maxq(self.h, int(bool(on)), self._stream()), "cz_search_record_maxq")
+        self.maxq_on = bool(on)
+
+    def root_maxq(self):
+        """The resignation test's max q of every current root, as a visit entry of that root would carry it
+        (cz_search_root_maxq; bans of the current set_roots): float64 [G], NaN = the root is not in the tree."""
+        return self._root_outputs("cz_search_root_maxq", ((self.G,), "float64"))[0]
+
+    def set_resign_threshold(self, t):
+        """Replace play_config.resign_threshold for every ply chosen after the call (cz_search_set_resign_threshold): t
+        finite.  Synchronises the stream.  A captured graph holds the old value: capture it again."""
+        if not hasattr(self.L, "cz_search_set_resign_threshold"):
+            raise _native.NativeError("this libczero.so cannot change the resign threshold (cz_search_set_resign_threshold)")
+        _native.check(self.L.cz_search_set_resign_threshold(self.h, float(t), self._stream()),
+                      "cz_search_set_resign_threshold")
+        self.resign_threshold = float(t)
+
     def root_targets(self):
         """The pruned counts of every current root (cz_search_root_targets; edge order of root_stats, bans of the current
         set_roots): dict(n int32 [G, 128], raw_total int32 [G])."""
@@ -587,7 +623,19 @@ class Search:
             return 0
         buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
         q = None
-        if self.values_on or self.surprise_on:
+        if self.maxq_on:
+            # all three rings beside the entries; a record that is off is not copied and stays NaN, "none"
+            q = np.full((n.value, 3), np.nan, dtype=np.float64)
+            cols = [np.empty((n.value,), dtype=np.float64) for _ in range(3)]
+            rings = [cols[0].ctypes.data if self.values_on else None, cols[1].ctypes.data if self.surprise_on else None,
+                     cols[2].ctypes.data]
+            fn = "cz_search_drain_visits_qsm"
+            _native.check(getattr(self.L, fn)(self.h, buf.ctypes.data, *rings, n.value, C.byref(n), C.byref(dropped),
+                                              self._stream()), fn)
+            for k, on in enumerate((self.values_on, self.surprise_on, True)):
+                if on:
+                    q[:, k] = cols[k]
+        elif self.values_on or self.surprise_on:
             # both rings beside the entries; a record that is off is not copied and leaves q at NaN, "no value"
             q = np.full((n.value,), np.nan, dtype=np.float64)
             sp = np.empty((n.value,), dtype=np.float64)
@@ -617,7 +665,7 @@ class Search:
             for i in range(buf.shape[0]):      # kept trimmed to the root's edges until the game's record arrives
                 ne = int(buf[i, 6])
                 row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
-                if q is not None:              # the entry's value (and surprise) ride behind its edges
+                if q is not None:              # the entry's value (and surprise, and max q) ride behind its edges
                     row += q[i:i + 1].tobytes()
                 self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
 
@@ -632,23 +680,27 @@ class Search:
     @staticmethod
     def parse_visit_entry(row):
         """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges], then with the value
-        record on its float64 q, with the surprise record on float64 q (NaN with the value record off) and s) ->
-        VisitEntry."""
+        record on its float64 q, with the surprise record on float64 q (NaN with the value record off) and s, with the
+        max-q record on float64 q, s (NaN where that record is off) and maxq) -> VisitEntry."""
         a = np.frombuffer(row, dtype=np.uint8)
         ne = int(a[6])
-        q = sp = None
+        q = sp = mq = None
         if len(a) >= 24 + 6 * ne:
             q = float(a[16 + 6 * ne:24 + 6 * ne].view(np.float64)[0])
             q = None if q != q else q
-        if len(a) == 32 + 6 * ne:
-            sp = float(a[24 + 6 * ne:].view(np.float64)[0])
+        if len(a) >= 32 + 6 * ne:
+            sp = float(a[24 + 6 * ne:32 + 6 * ne].view(np.float64)[0])
             sp = None if sp != sp else sp
+        if len(a) == 40 + 6 * ne:
+            mq = float(a[32 + 6 * ne:].view(np.float64)[0])
+            mq = None if mq != mq else mq
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
                           pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp,
-                          gumbel=bool(a[7] & VISIT_GUMBEL), early=bool(a[7] & VISIT_EARLY))
+                          gumbel=bool(a[7] & VISIT_GUMBEL), early=bool(a[7] & VISIT_EARLY), maxq=mq,
+                          no_resign=bool(a[7] & VISIT_NO_RESIGN))
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane
@@ -995,3 +1047,17 @@ def root_surprise_rows(labels, m, p, n_edges):
 
 
 Search.root_surprise_rows = staticmethod(root_surprise_rows)
+
+
+def root_maxq_rows(labels, n, w, n_edges):
+    """cz_root_maxq: the max-q arithmetic of record_maxq on caller-supplied rows.  labels uint16 (bit 15 = banned), n int32
+    and w float64 (the raw statistics), all [rows, 128] cuda tensors; n_edges uint8 [rows].  Returns float64 [rows] on the
+    device, -100 for a row without a non-banned edge."""
+    import torch
+    rows, ptrs, ne, stream = _row_args("root_maxq_rows", n_edges, (labels, "uint16"), (n, "int32"), (w, "float64"))
+    out = torch.empty((rows,), dtype=torch.float64, device=n.device)
+    _native.check(_native.lib().cz_root_maxq(*ptrs, ne, rows, C.c_void_p(out.data_ptr()), stream), "cz_root_maxq")
+    return out
+
+
+Search.root_maxq_rows = staticmethod(root_maxq_rows)

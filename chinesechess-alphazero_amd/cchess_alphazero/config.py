@@ -97,6 +97,11 @@ class EngineConfig(_Section):
                          book_rate=1.0,           # start from its positions with this probability, else from INIT_STATE
                          use_hip_graph=False, base_seed=0, report_every_rounds=200,
                          max_rounds=None, max_games=None,   # None = run forever, like the reference
+                         # resignation audit (run.py self --resign-audit, lib/resign_audit.py): the no-resign games are
+                         # audited against a grid of thresholds; with a target P (--resign-fp-target) the threshold
+                         # follows the largest one whose false-positive share stays within P, once at least
+                         # resign_audit_min_events games would have resigned there (None = ceil(5 / P))
+                         resign_audit=False, resign_fp_target=0.0, resign_audit_min_events=None,
                          # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
                          **search_options.DEFAULTS)
 

@@ -44,7 +44,7 @@ class SelfPlayEngine:
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
-                 kld_gain=None, kld_interval=None):
+                 kld_gain=None, kld_interval=None, resign_audit=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -59,13 +59,21 @@ class SelfPlayEngine:
         drain()'s items: record_visits [move, value, pi], the playout cap a weight (0 for a fast ply), record_q the root's
         search value q, record_surprise the ply's surprise s -- [move, value, pi or None, weight, q or None, s]; with
         forced_playouts pi is the pruned counts, with gumbel softmax(log prior + sigma(completed Q)) scaled to 65536
-        (include/czero.h).  eval_cache: every network change empties it (_install)."""
+        (include/czero.h).  eval_cache: every network change empties it (_install).
+        resign_audit (None = config.engine.resign_audit; needs record_visits): the max-q record of the search is on --
+        every VisitEntry of drain()'s `visits` carries the number its ply's resignation test compared (maxq) and whether
+        its game plays on without resignation (no_resign): what lib/resign_audit.py audits.  It is a game-loop option,
+        not one of search_options.py's; the records do not change."""
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
             gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
             solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
         search_options.check(opts, history=use_history)
+        self.resign_audit = bool(getattr(getattr(config, "engine", None), "resign_audit", False)
+                                 if resign_audit is None else resign_audit)
+        if self.resign_audit and not opts["record_visits"]:
+            raise ValueError("resign_audit needs record_visits: the max q rides beside the visit entries")
         vars(self).update(opts)                # self.record_visits, self.fast_sims, ... self.kld_interval
         _native.require_gpu()
         self.config = config
@@ -111,6 +119,8 @@ class SelfPlayEngine:
         self._since_pull = 0
         if self.record_visits:
             self.search.record_visits(True, capacity=8 * VISIT_DRAIN_ROUNDS * self.search.G)
+        if self.resign_audit:                  # beside the visit ring: after it, before start() and a graph capture
+            self.search.record_maxq(True)
         ec = getattr(config, "engine", None)
         book_path = os.environ.get("CZ_BOOK") or getattr(ec, "book_path", None)     # (CZ_BOOK: a book for bench.py / the tools)
         if book is None and book_path:
@@ -180,6 +190,24 @@ class SelfPlayEngine:
         self.compact = bool(self._want_compact and self.net.supports_compact_queue())
         if had_graph:
             self.capture_graph()
+
+    def set_resign_threshold(self, t):
+        """Replace config.play.resign_threshold for every ply whose move is chosen after the call
+        (Search.set_resign_threshold).  The threshold is an argument of the kernels: a captured HIP graph holds the old
+        value and is captured again, the way set_network does it.  The games and their trees are not touched."""
+        t = float(t)
+        if t != t or t in (float("inf"), float("-inf")):
+            raise ValueError(f"set_resign_threshold: {t} is not finite")
+        torch.cuda.synchronize(self.device)
+        had_graph = self._graph is not None
+        self._graph = None
+        self.search.set_resign_threshold(t)
+        if had_graph:
+            self.capture_graph()
+
+    @property
+    def resign_threshold(self):
+        return self.search.resign_threshold
 
     def queue_planes(self, n=64):
         """The first n positions of the evaluation queue as planes (a copy) -- rebuilt from the occupancy boards when the

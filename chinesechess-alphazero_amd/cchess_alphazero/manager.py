@@ -61,6 +61,13 @@ _FLAGS = [
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
                                "(default: what the best model has, scalar for a new one); refused when the best model has "
                                "the other head")),
+    ("--resign-audit", dict(action="store_true",
+                            help="(self) audit resignation on the games that play on without it: per threshold of a grid, how "
+                                 "many would have resigned and how many of those went on to win or draw (needs "
+                                 "--record-visits)")),
+    ("--resign-fp-target", dict(type=float, default=0.0, metavar="P",
+                                help="(self) adapt the resign threshold to the largest one whose false-positive share stays "
+                                     "within P (0 < P < 1; 0 = keep the configuration's; needs --resign-audit)")),
 ] + search_options.flags()
 
 
@@ -106,6 +113,13 @@ def build_config(args):
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
     vars(engine).update(values)
+    # the resignation audit: game-loop options, not search options; their one check is the library's
+    from cchess_alphazero.lib.resign_audit import check_options
+    try:
+        check_options(args.resign_audit, args.resign_fp_target, values["record_visits"], cmd=args.cmd)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    engine.resign_audit, engine.resign_fp_target = bool(args.resign_audit), float(args.resign_fp_target)
     if not 0.0 <= args.q_ratio <= 1.0:
         raise SystemExit(f"--q-ratio {args.q_ratio}: expected 0 <= L <= 1")
     config.trainer.q_ratio = args.q_ratio

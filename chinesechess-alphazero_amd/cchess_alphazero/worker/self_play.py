@@ -15,6 +15,7 @@ import numpy as np
 
 from cchess_alphazero import search_options
 from cchess_alphazero.lib.data_helper import PlayDataWriter, mean_abs_q_minus_z, surprise_sums
+from cchess_alphazero.lib.resign_audit import ResignAudit, check_options, reduce_resign_audit
 
 logger = getLogger(__name__)
 
@@ -74,6 +75,19 @@ class SelfPlayWorker:
         self.engine = None
         self.writer = PlayDataWriter(config, rank, world)
         self.stored_games = 0
+        # resignation audit (config.engine.resign_audit, lib/resign_audit.py): the histogram of this rank's no-resign
+        # games since the last best-model reload; resign_audited, the ids of the games it holds, in the order they were
+        # fed; resign_threshold_log, (games in the all-reduced histogram, threshold) of every adaptation
+        ec = config.engine
+        self.resign_audit = None
+        self.resign_fp_target = float(getattr(ec, "resign_fp_target", 0.0) or 0.0)
+        self.resign_min_events = getattr(ec, "resign_audit_min_events", None)
+        self.resign_audited = []
+        self.resign_threshold_log = []
+        check_options(getattr(ec, "resign_audit", False), self.resign_fp_target, getattr(ec, "record_visits", False),
+                      min_events=self.resign_min_events)
+        if getattr(ec, "resign_audit", False):
+            self.resign_audit = ResignAudit(config.play.min_resign_turn)
 
     def _make_engine(self):
         import torch
@@ -92,6 +106,10 @@ class SelfPlayWorker:
         # (the search options of config.engine are likewise set by the engine: one line for each that is on)
         for line in search_options.describe(vars(self.engine), self.config.play.simulation_num_per_move):
             logger.info(f"Process {self.pid}-{self.rank}: {line}")
+        if self.resign_audit is not None:
+            logger.info(f"Process {self.pid}-{self.rank}: resignation audit of the no-resign games, threshold "
+                        f"{self.engine.resign_threshold:g}"
+                        + (f", false-positive target {self.resign_fp_target:g}" if self.resign_fp_target else ""))
         first, stride = game_id_partition(self.rank, self.world, ec.games_per_gpu)
         self.engine.start(first, stride)
         if ec.use_hip_graph:
@@ -106,6 +124,8 @@ class SelfPlayWorker:
             pruned += g.get("pruned_visits", 0)
             raw += sum(e.raw_total for e in g.get("visits") or [] if e.pruned)
             fast += g.get("fast_plies", 0)
+            if self.resign_audit is not None and self.resign_audit.add_game(g.get("visits"), g["value"]):
+                self.resign_audited.append(g["game_id"])
             full += len(g["data"]) - 1 - g.get("fast_plies", 0)
             logger.debug(f"Process {self.pid}-{self.rank} game {g['game_id']} turn={g['turns'] / 2}, "
                          f"winner = {g['value']:.2f} (1 = red, -1 = black, 0 draw; red = the first mover)"
@@ -148,6 +168,35 @@ class SelfPlayWorker:
         return (f" eval_cache: probes={ci['probes']} hits={ci['hits']} "
                 f"({100.0 * ci['hits'] / max(ci['probes'], 1):.2f} %) stores={ci['stores']}")
 
+    def _resign_audit_report(self):
+        """A report boundary of the resignation audit: all-reduce the histogram, log it at the running threshold (rank 0),
+        write this rank's own histogram beside the play data, and with a target move the threshold to what the global
+        histogram allows -- every rank sees the same histogram and picks the same value."""
+        if self.resign_audit is None:
+            return None
+        total = reduce_resign_audit(self.resign_audit)
+        running = self.engine.resign_threshold
+        if self.rank == 0:
+            would, fp, at = total.at(running)
+            logger.info(f"resign audit: {total.games} games audited ({total.skipped} skipped); at threshold {at:g} "
+                        f"{would} would have resigned, {fp} of them false positives"
+                        + (f" ({100.0 * fp / would:.1f} %)" if would else ""))
+        if self.resign_fp_target:
+            t = total.choose_threshold(self.resign_fp_target, self.resign_min_events)
+            if t is not None and t != running:
+                self.engine.set_resign_threshold(t)
+                self.resign_threshold_log.append((total.games, t))
+                logger.info(f"Process {self.pid}-{self.rank}: resign threshold {running:g} -> {t:g} "
+                            f"(false-positive target {self.resign_fp_target:g}, {total.games} games audited)")
+        try:
+            rc = self.config.resource
+            os.makedirs(rc.play_data_dir, exist_ok=True)
+            self.resign_audit.write(os.path.join(rc.play_data_dir, f"resign_audit_{self.rank}.json"),
+                                    threshold=self.engine.resign_threshold)
+        except OSError as e:
+            logger.error(f"resign audit: could not write the histogram: {e}")
+        return total
+
     def reload_best_model(self):
         """The reference's self-play picks up a new best model while it runs: its prediction thread re-checks the
         best-weight digest every 600 s (agent/api.py:37-44, get_pipes(need_reload=True) in self_play.py:62-64).
@@ -160,6 +209,9 @@ class SelfPlayWorker:
             if need_to_reload_best_model_weight(self.model) and load_best_model_weight(self.model):
                 self.engine.set_network(self.model.model)
                 logger.info(f"Process {self.pid}-{self.rank}: best model reloaded, digest {self.model.digest}")
+                if self.resign_audit is not None:      # false positives are a property of the network: the histogram
+                    self.resign_audit.reset()          # starts again, the threshold stays
+                    self.resign_audited = []
                 return True
         except Exception as e:                 # a half-written file: keep playing with the old weights
             logger.error(f"best-model reload failed: {e}")
@@ -202,6 +254,7 @@ class SelfPlayWorker:
                     last_check = time.time()
                     self.reload_best_model()
                 c = reduce_counters(self.engine.counters())
+                self._resign_audit_report()
                 if self.rank == 0:
                     dt = time.time() - t0
                     lc = self.engine.counters()

@@ -234,6 +234,7 @@ constexpr uint32_t VISIT_FAST = 2u;                // entry flag: the ply was a 
 constexpr uint32_t VISIT_PRUNED = 4u;              // entry flag: n[] holds the PRUNED counts (cz_search_set_forced_playouts)
 constexpr uint32_t VISIT_GUMBEL = 8u;              // entry flag: n[] holds the Gumbel policy target scaled to 65536 (cz_search_set_gumbel)
 constexpr uint32_t VISIT_EARLY = 16u;              // entry flag: a stop rule ended the ply before its budget (cz_search_set_kld_gain, _smart_pruning)
+constexpr uint32_t VISIT_NO_RESIGN = 32u;          // entry flag (max-q record on only): the game plays on without resignation (cz_search_record_maxq)
 struct VisitEntryHdr {                             // followed by uint16 label[128], then int32 n[128]
     uint32_t game_id;
     uint16_t ply;       // turns when the move was chosen
@@ -256,6 +257,9 @@ struct VisitRing {
     double* q;                      // [cap]; NULL = off
     // surprise record (cz_search_record_surprise): KL(recorded counts || noise-free priors) of the same entry, likewise
     double* s;                      // [cap]; NULL = off
+    // max-q record (cz_search_record_maxq): the number the ply's resignation test compared, likewise; while it is on the
+    // entries of games that play on without resignation carry VISIT_NO_RESIGN
+    double* mq;                     // [cap]; NULL = off
 };
 
 // ---- early stop of a settled ply (cz_search_set_kld_gain, cz_search_set_smart_pruning; csrc/xq_search_stop.h) ----

@@ -28,7 +28,7 @@
 //   xq_search_select.h    RootCtx and PUCT at the root, the Gumbel helpers, gumbel_interior, select_gumbel, select_edge
 //   xq_search_solver.h    the MCTS solver: its bit fields, solve_*, select_solve
 //   xq_search_sim.h       one simulation: Deferred, write_planes, expand_node, the cache probe, run_sim, flush_deferred
-//   xq_search_records.h   RootEdges, gumbel_choose, gumbel_targets, prune_targets, root_value, root_surprise, emit_visits
+//   xq_search_records.h   RootEdges, gumbel_choose, gumbel_targets, prune_targets, root_value, root_surprise, root_maxq, emit_visits
 //   xq_search_ply.h       the chunk pool, reserve_ply, ply_is_fast, begin_search, choose_action, new_game, the book, emit_record
 //   xq_search_selfplay.h  advance_game
 //   xq_search_stop.h      the early stop of a settled ply: stop_reset, ply_settled
@@ -305,6 +305,7 @@ int cz_search_destroy(cz_search* s)
     (void)hipFree(s->vis_mem);
     (void)hipFree(s->V.q);
     (void)hipFree(s->V.s);
+    (void)hipFree(s->V.mq);
     (void)hipFree(s->book_mem);
     (void)hipFree(s->C.tab);
     (void)hipFree(s->ec_mem);
@@ -689,7 +690,7 @@ int cz_search_eval_cache_info(cz_search* s, uint64_t* out, void* stream)
 static_assert(sizeof(cz_visit_entry) == sizeof(VisitEntryHdr) && VISIT_STRIDE == 784, "czero.h: visit entry layout");
 static_assert(VISIT_MAX_EDGES == MAXMOVES, "a root has at most MAXMOVES edges");
 
-// Switch a side ring of the visit ring (one double per slot: V.q, V.s) on or off; `what` names the caller in errors
+// Switch a side ring of the visit ring (one double per slot: V.q, V.s, V.mq) on or off; `what` names the caller in errors
 static int side_ring(cz_search* s, double*& ring, int on, hipStream_t st, const char* what)
 {
     hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
@@ -717,10 +718,11 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_visits: null handle");
     if (capacity < 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity < 0");
     hipStream_t st = (hipStream_t)stream;
-    // the value and the surprise ring share the visit ring's slots: they go with it.  side_ring waits for the stream:
-    // no launch in flight may still use the old buffers
+    // the value, the surprise and the max-q ring share the visit ring's slots: they go with it.  side_ring waits for the
+    // stream: no launch in flight may still use the old buffers
     if (side_ring(s, s->V.q, 0, st, "cz_search_record_visits") != CZ_OK
-        || side_ring(s, s->V.s, 0, st, "cz_search_record_visits") != CZ_OK)
+        || side_ring(s, s->V.s, 0, st, "cz_search_record_visits") != CZ_OK
+        || side_ring(s, s->V.mq, 0, st, "cz_search_record_visits") != CZ_OK)
         return CZ_ERR_HIP;
     hipError_t e = hipSuccess;
     (void)hipFree(s->vis_mem);
@@ -812,12 +814,12 @@ static_assert(CZ_VISIT_GUMBEL == VISIT_GUMBEL && CZ_GUMBEL_MAX_M == GUMBEL_MAX_M
 
 // k_root_records, the instantiation of the object's setting (cz_search_set_gumbel_full)
 static void launch_root_records(cz_search* s, hipStream_t st, const SearchParams& P, const SearchBuffers& B, int32_t* n,
-                                int32_t* raw_total, double* q, double* sv, int gumbel)
+                                int32_t* raw_total, double* q, double* sv, int gumbel, double* mq = nullptr)
 {
     if (P.gumbel_m > 0 && P.gumbel_full)
-        hipLaunchKernelGGL(k_root_records<true>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel);
+        hipLaunchKernelGGL(k_root_records<true>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel, mq);
     else
-        hipLaunchKernelGGL(k_root_records<false>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel);
+        hipLaunchKernelGGL(k_root_records<false>, dim3(s->P.G), dim3(64), 0, st, P, B, n, raw_total, q, sv, gumbel, mq);
 }
 
 int cz_search_set_gumbel(cz_search* s, int m, double c_visit, double c_scale, void* stream)
@@ -1083,7 +1085,7 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
         return serr(CZ_ERR_ARG, "cz_policy_target_prune: k or c_puct negative or not finite");
     if (rows == 0) return CZ_OK;
     hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, (const int32_t*)nullptr, n, w, p,
-                       n_edges, rows, c_puct, k, out_n, out_raw_total, (double*)nullptr, (double*)nullptr);
+                       n_edges, rows, c_puct, k, out_n, out_raw_total, (double*)nullptr, (double*)nullptr, (double*)nullptr);
     S_LAUNCH_CHECK("cz_policy_target_prune");
     return CZ_OK;
 }
@@ -1111,7 +1113,7 @@ int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, co
         return serr(CZ_ERR_ARG, "cz_root_value: null argument or rows < 0");
     if (rows == 0) return CZ_OK;
     hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, n, w, (const float*)nullptr,
-                       n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr, out_q, (double*)nullptr);
+                       n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr, out_q, (double*)nullptr, (double*)nullptr);
     S_LAUNCH_CHECK("cz_root_value");
     return CZ_OK;
 }
@@ -1142,14 +1144,56 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
     if (rows == 0) return CZ_OK;
     hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, m, (const int32_t*)nullptr,
                        (const double*)nullptr, p, n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr,
-                       (double*)nullptr, out);
+                       (double*)nullptr, out, (double*)nullptr);
     S_LAUNCH_CHECK("cz_root_surprise");
     return CZ_OK;
 }
 
-// cz_search_drain_visits, _q and _qs: q_buf / s_buf NULL = that ring is not copied
+static_assert(CZ_VISIT_NO_RESIGN == VISIT_NO_RESIGN, "czero.h: max-q record flag");
+
+int cz_search_record_maxq(cz_search* s, int on, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_maxq: null handle");
+    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_maxq: needs cz_search_record_visits on");
+    return side_ring(s, s->V.mq, on, (hipStream_t)stream, "cz_search_record_maxq");
+}
+
+int cz_search_root_maxq(cz_search* s, double* out, void* stream)
+{
+    if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_maxq: null argument");
+    launch_root_records(s, (hipStream_t)stream, s->P, s->B, (int32_t*)nullptr,
+                       (int32_t*)nullptr, (double*)nullptr, (double*)nullptr, 0, out);
+    S_LAUNCH_CHECK("cz_search_root_maxq");
+    return CZ_OK;
+}
+
+int cz_root_maxq(const uint16_t* labels, const int32_t* n, const double* w, const uint8_t* n_edges, int rows, double* out,
+                 void* stream)
+{
+    if (!labels || !n || !w || !n_edges || !out || rows < 0)
+        return serr(CZ_ERR_ARG, "cz_root_maxq: null argument or rows < 0");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_row_records, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, (const int32_t*)nullptr, n, w,
+                       (const float*)nullptr, n_edges, rows, 0.0, 0.0, (int32_t*)nullptr, (int32_t*)nullptr,
+                       (double*)nullptr, (double*)nullptr, out);
+    S_LAUNCH_CHECK("cz_root_maxq");
+    return CZ_OK;
+}
+
+int cz_search_set_resign_threshold(cz_search* s, double t, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_resign_threshold: null handle");
+    if (!(t >= -1.7976931348623157e308 && t <= 1.7976931348623157e308))                   // (false for NaN and infinity)
+        return serr(CZ_ERR_ARG, "cz_search_set_resign_threshold: t not finite");
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the threshold they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_resign_threshold", e);
+    s->P.resign_threshold = t;
+    return CZ_OK;
+}
+
+// cz_search_drain_visits, _q, _qs and _qsm: q_buf / s_buf / m_buf NULL = that ring is not copied
 static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
-                        uint64_t* dropped_out, void* stream)
+                        uint64_t* dropped_out, void* stream, double* m_buf = nullptr)
 {
     if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits: bad argument");
     if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits: visit recording is off");
@@ -1182,6 +1226,8 @@ static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_b
             e = hipMemcpyAsync(q_buf + done, s->V.q + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
         if (s_buf && e == hipSuccess)
             e = hipMemcpyAsync(s_buf + done, s->V.s + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (m_buf && e == hipSuccess)
+            e = hipMemcpyAsync(m_buf + done, s->V.mq + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
         done += run;
     }
     const unsigned int new_head = tail;
@@ -1209,6 +1255,15 @@ int cz_search_drain_visits_qs(cz_search* s, void* host_buf, double* q_buf, doubl
 {
     return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, host_buf ? s_buf : nullptr, max_entries, n_out,
                         dropped_out, stream);
+}
+
+int cz_search_drain_visits_qsm(cz_search* s, void* host_buf, double* q_buf, double* s_buf, double* m_buf, int max_entries,
+                               int* n_out, uint64_t* dropped_out, void* stream)
+{
+    if (s && !s->V.mq) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qsm: max-q recording is off");
+    if (host_buf && !m_buf) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qsm: null m_buf");
+    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, host_buf ? s_buf : nullptr, max_entries, n_out,
+                        dropped_out, stream, host_buf ? m_buf : nullptr);
 }
 
 int cz_search_reset_trees(cz_search* s, void* stream)

@@ -221,14 +221,15 @@ __global__ __launch_bounds__(64) void k_root_decided(SearchParams P, SearchBuffe
 }
 
 // What emit_visits would record for every current root, with the bans of the current set_roots (cz_search_root_targets,
-// _root_value, _root_surprise): the pruned counts n [G][128] and their raw total, the search value q, the policy
-// surprise s.  A NULL output is not computed.  One wavefront per game.
+// _root_value, _root_surprise, _root_maxq): the pruned counts n [G][128] and their raw total, the search value q, the policy
+// surprise s, the resignation test's max q (NaN: the root is not in the tree).  A NULL output is not computed.  One
+// wavefront per game.
 // gumbel (or the option on): the counts are the Gumbel policy targets, as a VISIT_GUMBEL entry holds them; FULL: the full
 // search's (launched while cz_search_set_gumbel_full is on).
 template <bool FULL>
 __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffers B, int32_t* __restrict__ n,
                                                     int32_t* __restrict__ raw_total, double* __restrict__ q,
-                                                    double* __restrict__ s, int gumbel)
+                                                    double* __restrict__ s, int gumbel, double* __restrict__ mq)
 {
     __shared__ uint32_t chtab[MAX_CHUNKS];
     const int g = blockIdx.x;
@@ -253,9 +254,15 @@ __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffe
         const double v = root_surprise(E.nm, E.lab, m, E.p);
         if (lane == 0) s[g] = v;
     }
+    if (mq) {
+        // (no root: -1 after a search began on a position the tree does not hold, 0 -- the id that names no record --
+        //  in an object that has not been given roots yet)
+        const double v = uni(B.g_root[g]) <= 0 ? __builtin_nan("") : root_maxq(E.nm, E.lab, E.n, E.w);
+        if (lane == 0) mq[g] = v;
+    }
 }
 
-// cz_policy_target_prune, cz_root_value, cz_root_surprise: the same arithmetic on caller-supplied rows [rows][128], one
+// cz_policy_target_prune, cz_root_value, cz_root_surprise, cz_root_maxq: the same arithmetic on caller-supplied rows [rows][128], one
 // wavefront per row.  out_n (with out_raw_total): the counts n are pruned; otherwise m holds the recorded counts.  A
 // NULL input reads as zeros, a NULL output is not computed.
 __global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__ labels, const int32_t* __restrict__ m_in,
@@ -263,13 +270,18 @@ __global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__
                                                    const float* __restrict__ p, const uint8_t* __restrict__ n_edges,
                                                    int rows, double c_puct, double k, int32_t* __restrict__ out_n,
                                                    int32_t* __restrict__ out_raw_total, double* __restrict__ out_q,
-                                                   double* __restrict__ out_s)
+                                                   double* __restrict__ out_s, double* __restrict__ out_mq)
 {
     const int r = blockIdx.x;
     if (r >= rows) return;
     const int lane = lane_id();
     const RootEdges E = load_row_edges(labels, n, w, p, n_edges, r);
     int m[2] = {E.n[0], E.n[1]};
+    if (out_mq) {                           // cz_root_maxq: the raw statistics alone, no recorded counts
+        const double v = root_maxq(E.nm, E.lab, E.n, E.w);
+        if (lane == 0) out_mq[r] = v;
+        return;
+    }
     if (out_n) {
         const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, c_puct, k);
 #pragma unroll

@@ -5,7 +5,7 @@
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
 // What a finished search records about its root: RootEdges and its two loaders, root_net_value, gumbel_choose, gumbel_targets,
-// prune_targets, root_value, root_surprise, emit_visits.
+// prune_targets, root_value, root_surprise, root_maxq, emit_visits.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_select.h"
@@ -273,6 +273,29 @@ XQ_D double root_surprise(int nm, const uint16_t lab[2], const int m[2], const f
     return s > 0.0 ? s : 0.0;
 }
 
+// The number a ply's resignation test compares (include/czero.h, cz_search_record_maxq): one wavefront, edge j = lane +
+// 64 h.  lab[h] carries VISIT_BANNED, n / w are the raw statistics.  choose_action's arithmetic: the maximum over the
+// non-banned edges of n ? w / n : 0.0 in float64, starting from -100 (so: no such edge gives -100).  A maximum is exact,
+// the lane order is free.  All 64 lanes call it.
+XQ_D double root_maxq(int nm, const uint16_t lab[2], const int n[2], const double w[2])
+{
+    const int lane = lane_id();
+    double maxq = -100.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool live = lane + 64 * h < nm && !(lab[h] & VISIT_BANNED);
+        if (!live) continue;
+        const double q = n[h] ? w[h] / (double)n[h] : 0.0;
+        maxq = q > maxq ? q : maxq;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = __shfl_xor(maxq, d, 64);
+        maxq = o > maxq ? o : maxq;
+    }
+    return unid(maxq);
+}
+
 // Root visit record (cz_search_record_visits): the root's edges as choose_action saw them -- edge order, exact
 // counts, banned edges flagged (calc_policy zeroes them, player.py:375-406) -- for the ply that just chose its move.
 // prune (forced playouts on, a full ply): the counts are the pruned policy targets, the entry says so (VISIT_PRUNED,
@@ -323,13 +346,22 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
         const double sv = root_surprise(nm, E.lab, m, E.p);
         if (lane == 0) V.s[pos % V.cap] = sv;
     }
+    // the max-q record (cz_search_record_maxq): what choose_action compared with the threshold, likewise; while it is on
+    // the entry also says whether its game plays on without resignation
+    bool no_resign = false;
+    if (V.mq) {
+        const double mq = root_maxq(nm, E.lab, E.n, E.w);
+        if (lane == 0) V.mq[pos % V.cap] = mq;
+        no_resign = uni((int)B.g_enable_resign[g]) == 0;
+    }
     if (lane == 0) {
         VisitEntryHdr* h = reinterpret_cast<VisitEntryHdr*>(e);
         h->game_id = B.g_game_id[g];
         h->ply = (uint16_t)turns;
         h->n_edges = (uint8_t)nm;
         h->flags = (uint8_t)((resigned ? VISIT_RESIGN : 0u) | (fast ? VISIT_FAST : 0u) | (pruned ? VISIT_PRUNED : 0u) |
-                               (gumbel ? VISIT_GUMBEL : 0u) | (early ? VISIT_EARLY : 0u));
+                               (gumbel ? VISIT_GUMBEL : 0u) | (early ? VISIT_EARLY : 0u) |
+                               (no_resign ? VISIT_NO_RESIGN : 0u));
         h->sum_n = E.sum_n;
         h->raw_total = (uint32_t)raw_total;
     }

@@ -449,7 +449,9 @@ typedef struct cz_visit_entry {
                                         (CZ_VISIT_PRUNED): n[] holds the pruned policy targets, not the raw counts
                                         (cz_search_set_forced_playouts); bit 3 (CZ_VISIT_GUMBEL): n[] holds the Gumbel
                                         policy target scaled to 65536 (cz_search_set_gumbel); bit 4 (CZ_VISIT_EARLY): a
-                                        stop rule ended the ply before its budget (cz_search_set_kld_gain) */
+                                        stop rule ended the ply before its budget (cz_search_set_kld_gain); bit 5
+                                        (CZ_VISIT_NO_RESIGN, max-q record on only): the game plays on without
+                                        resignation (cz_search_record_maxq) */
     int32_t sum_n;                  /* the root's own visit count */
     uint32_t raw_total;              /* CZ_VISIT_PRUNED, CZ_VISIT_GUMBEL: sum of the RAW counts of the non-banned edges (S), so that
                                         raw_total - sum of the non-banned n[] = visits pruned; otherwise 0 (this word
@@ -545,6 +547,49 @@ int cz_search_root_surprise(cz_search* s, double* out, void* stream);
  * [rows] (<= 128), out [rows] float64, all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
 int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, const uint8_t* n_edges, int rows,
                      double* out, void* stream);
+/* ---- max-q record of self-play: the resignation audit (off by default; the reference has no such option) ----
+ * Self-play resigns when the root's best edge value falls below resign_threshold, and keeps a share of the games playing
+ * on without resignation (philox(seed, game_id, 0, 0) > enable_resign_rate) so that one can measure how often a
+ * resignation would have thrown away a game that was not lost.  This record hands out what that measurement needs: the
+ * number each ply's resignation test compared, and which games play on.  on = 0 (the state after cz_search_create): no
+ * kernel output, ring byte, record, counter or entry differs by a bit from what it was before this existed.
+ *
+ * THE ARITHMETIC.  Given a root's edges as a visit entry sees them -- labels with the banned bit (0x8000), the raw
+ * statistics n_j (int32) and w_j (float64) -- in float64:
+ *       maxq = max( -100, max_j (n_j ? w_j / n_j : 0.0) )         over the non-banned edges j < n_edges
+ * cz_search_choose's and self-play's own arithmetic: the player resigns iff maxq < resign_threshold, resignation is
+ * enabled for the game and turns > min_resign_turn.  A root without a non-banned edge gives -100; a root that was never
+ * selected from gives 0.0.  A maximum is exact, so the order of the lanes does not matter.
+ *
+ * THE RING.  Like the value record: double mq[capacity], indexed by the slot of the visit entry, written by the kernel
+ * in the entry's reservation for every ply that gets an entry; a dropped entry drops its number.  While the record is
+ * on, an entry of a game that plays on without resignation carries CZ_VISIT_NO_RESIGN (bit 5); with it off no entry
+ * does.  Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting); every call of
+ * cz_search_record_visits frees this ring as well, so switch it on after that.  Call it before
+ * cz_search_start_selfplay and before a graph capture; synchronises the stream.  Entries already waiting when it is
+ * switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.  No counter is added; the move,
+ * the tree, the other words of the visit entries, the value and the surprise ring do not change. */
+#define CZ_VISIT_NO_RESIGN 32u
+int cz_search_record_maxq(cz_search* s, int on, void* stream);
+/* cz_search_drain_visits_qs that also copies the entries' max q into HOST m_buf[max_entries], beside entry i.  q_buf /
+ * s_buf = NULL: that ring is not copied (it has to be NULL when its record is off).  m_buf is required with host_buf, and
+ * the max-q record has to be on: CZ_ERR_ARG otherwise.  host_buf = NULL counts.  The older drains keep working with the
+ * max-q record on; they drop the numbers of what they consume. */
+int cz_search_drain_visits_qsm(cz_search* s, void* host_buf, double* q_buf, double* s_buf, double* m_buf, int max_entries,
+                               int* n_out, uint64_t* dropped_out, void* stream);
+/* The max q an entry of each current root would carry: out [G] float64 DEVICE, with the bans of the current
+ * cz_search_set_roots.  A root that is not in the tree reports NaN, a root that was never selected from 0.0.  Works with
+ * the record off. */
+int cz_search_root_maxq(cz_search* s, double* out, void* stream);
+/* The arithmetic on its own, one wavefront per row: labels / n / w [rows][128] (uint16 / int32 / float64) and n_edges
+ * [rows] (<= 128), out [rows] float64, all DEVICE.  CZ_ERR_ARG: a NULL pointer, rows < 0. */
+int cz_root_maxq(const uint16_t* labels, const int32_t* n, const double* w, const uint8_t* n_edges, int rows, double* out,
+                 void* stream);
+/* Replace resign_threshold (cz_search_cfg) for every ply whose move is chosen after the call: what an audit of the
+ * no-resign games adapts.  t must be finite (CZ_ERR_ARG otherwise, the object keeps its value).  The threshold is a
+ * kernel argument, a copy the host holds: the call synchronises the stream and changes that copy, the trees and the
+ * games are not touched.  A captured graph holds the value it was captured with: capture it again after the call. */
+int cz_search_set_resign_threshold(cz_search* s, double t, void* stream);
 /* ---- Gumbel root search with sequential halving (off by default; the reference has no such option) ----
  * "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022) at the root: M candidate moves are sampled
  * without replacement through Gumbel noise, the ply's simulations are spent on them by sequential halving, the survivor
