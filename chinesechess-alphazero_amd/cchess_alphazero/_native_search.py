@@ -23,6 +23,8 @@ MAX_NO_ACT = 32          # csrc/xq_search.h: banned root moves per game and ply
 VISIT_STRIDE = 784       # include/czero.h cz_visit_entry: 16-byte header, uint16 label[128], int32 n[128]
 VISIT_BANNED = 0x8000    # label bit: the edge is banned at that ply (no_act)
 GAME_VISITS_LOST = 4     # finished-game record flag: the game has no complete visit record
+GAME_SCRIPTED = 8        # finished-game record flag: the game walked a script (cz_search_set_script)
+GAME_SCRIPT_MISMATCH = 16  # ... and ended on a move its position does not have, or on moves left over after the game's end
 GAME_BOOK_SHIFT = 8      # finished-game record flags, bits 8-31: book index + 1 of the start position, 0 = INIT_STATE
 BOOK_MAX = (1 << 24) - 2  # include/czero.h CZ_BOOK_MAX
 MOVE_FAST = 0x8000       # finished-game record, moves[i] bit 15: ply i was a fast search (cz_search_set_playout_cap)
@@ -106,6 +108,8 @@ def declare(L):
     d = C.c_double
     optional = {                                        # (absent from an older library selected with CZ_LIB for an A/B)
         "cz_search_set_book": [vp, vp, i32, d, vp],
+        "cz_search_set_script": [vp, vp, vp, vp, vp, i32, vp],
+        "cz_search_script_mismatches": [vp, vp, vp],
         "cz_search_set_playout_cap": [vp, i32, d, vp],
         "cz_search_set_forced_playouts": [vp, d, vp],
         "cz_search_root_targets": [vp, vp, vp, vp],
@@ -349,6 +353,26 @@ class Search:
             ptr = boards.ctypes.data_as(C.c_void_p)
         _native.check(self.L.cz_search_set_book(self.h, ptr, n, float(rate), self._stream()), "cz_search_set_book")
         self.book_size = n
+
+    def set_script(self, init_boards=None, labels=None, offsets=None, z=None):
+        """Scripted games (cz_search_set_script; lib/reanalyse.py pack_scripts makes the arrays): game id i walks script i --
+        from init_boards[i] (int8 [n, 90], first mover's frame) it plays labels[offsets[i]:offsets[i + 1]] (uint16 labels,
+        int32 [n + 1] offsets) and ends with z[i] (int8, first mover's view); every ply is searched as a self-play ply is,
+        only the move is the script's.  Host arrays, copied into the search object; None / empty switches it off.  Needs
+        record_visits() on.  Call it before start_selfplay(0) and before a graph capture; a slot whose next game id has no
+        script goes idle (pending() counts the others).  drain_records() reports `script_index` and `script_mismatch`."""
+        if not hasattr(self.L, "cz_search_set_script"):
+            raise _native.NativeError("this libczero.so has no scripted games (cz_search_set_script)")
+        n = 0 if init_boards is None else len(init_boards)
+        ptrs = [None] * 4
+        if n:
+            arrs = [np.ascontiguousarray(init_boards, dtype=np.int8), np.ascontiguousarray(labels, dtype=np.uint16),
+                    np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(z, dtype=np.int8)]
+            assert arrs[0].shape == (n, 90) and arrs[2].shape == (n + 1,) and arrs[3].shape == (n,), "script array shapes"
+            assert arrs[1].ndim == 1 and len(arrs[1]) >= int(arrs[2][-1]), "labels shorter than offsets[n]"
+            ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrs]
+        _native.check(self.L.cz_search_set_script(self.h, *ptrs, n, self._stream()), "cz_search_set_script")
+        self.script_size = n
 
     def set_playout_cap(self, fast_sims=0, full_rate=0.25):
         """Self-play playout cap randomization (cz_search_set_playout_cap): ply `turns` of game `game_id` is a FULL search
@@ -864,7 +888,8 @@ class Search:
         return action.cpu().numpy()
 
     def counters(self):
-        """The counters summed over the games; with record_visits on also `visits_dropped` (ring entries lost, as of now)."""
+        """The counters summed over the games; with record_visits on also `visits_dropped` (ring entries lost, as of now),
+        with a script set also `script_mismatch` (scripted games that ended on a mismatch since set_script)."""
         out = (C.c_uint64 * self.n_counters)()
         _native.check(self.L.cz_search_counters(self.h, out, self._stream()), "cz_search_counters")
         d = {k: int(out[i]) for i, k in enumerate(COUNTER_NAMES[:self.n_counters])}
@@ -873,6 +898,10 @@ class Search:
             _native.check(self.L.cz_search_drain_visits(self.h, None, 0, C.byref(n), C.byref(dropped), self._stream()),
                           "cz_search_drain_visits")
             d["visits_dropped"] = int(dropped.value)
+        if getattr(self, "script_size", 0):
+            n = C.c_uint64(0)
+            _native.check(self.L.cz_search_script_mismatches(self.h, C.byref(n), self._stream()), "cz_search_script_mismatches")
+            d["script_mismatch"] = int(n.value)
         return d
 
     def game_counters(self):
@@ -887,7 +916,8 @@ class Search:
         """Finished games since the last call: list of dict(game_id, turns, value, store, resigned, book_index, moves[labels],
         fast); book_index: which position of set_book() the game started from, None = INIT_STATE (the kernel's own decision);
         fast: one bool per move, True where the ply was a fast search of the playout cap (set_playout_cap; bit 15 of the
-        record's move, masked out of `moves`), False for the appended king capture.
+        record's move, masked out of `moves`), False for the appended king capture.  script_index: the script a scripted
+        game walked (set_script; its game id), None otherwise; script_mismatch: it ended on a mismatch (store is False).
         with_visits (record_visits on): each dict also has `visits`, the game's VisitEntry list in ply order -- one per
         searched ply, the resignation ply included, the appended king capture not -- or None when the game's record is
         incomplete (an entry was dropped, or the game began before recording was switched on)."""
@@ -904,11 +934,14 @@ class Search:
             hdr = buf[i, :16].view(np.int32)
             turns = int(hdr[1])
             mv = buf[i, 16:16 + 2 * min(turns, self.max_plies + 2)].view(np.uint16)
-            out.append(dict(game_id=int(buf[i, :4].view(np.uint32)[0]), turns=turns, value=int(hdr[2]),
+            out_id = int(buf[i, :4].view(np.uint32)[0])
+            out.append(dict(game_id=out_id, turns=turns, value=int(hdr[2]),
                             store=bool(hdr[3] & 1), resigned=bool(hdr[3] & 2), moves=mv & (MOVE_FAST - 1),
                             fast=((mv & MOVE_FAST) != 0).tolist(),
                             book_index=((int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT) - 1
-                            if (int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT else None))
+                            if (int(hdr[3]) & 0xFFFFFFFF) >> GAME_BOOK_SHIFT else None,
+                            script_index=out_id if hdr[3] & GAME_SCRIPTED else None,
+                            script_mismatch=bool(hdr[3] & GAME_SCRIPT_MISMATCH)))
             if self.visit_capacity:
                 ents = sorted(self._visits.pop(out[-1]["game_id"], []), key=lambda e: e[0])
                 if with_visits:

@@ -21,7 +21,7 @@ from cchess_alphazero import _native, search_options
 from cchess_alphazero._native_search import Search
 from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
-from cchess_alphazero.environment.static_env import INIT_STATE
+from cchess_alphazero.environment.static_env import INIT_STATE, array_to_state
 from cchess_alphazero.lib.data_helper import record_item
 
 logger = getLogger(__name__)
@@ -44,7 +44,7 @@ class SelfPlayEngine:
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
-                 kld_gain=None, kld_interval=None, resign_audit=None):
+                 kld_gain=None, kld_interval=None, resign_audit=None, script=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -63,17 +63,26 @@ class SelfPlayEngine:
         resign_audit (None = config.engine.resign_audit; needs record_visits): the max-q record of the search is on --
         every VisitEntry of drain()'s `visits` carries the number its ply's resignation test compared (maxq) and whether
         its game plays on without resignation (no_resign): what lib/resign_audit.py audits.  It is a game-loop option,
-        not one of search_options.py's; the records do not change."""
+        not one of search_options.py's; the records do not change.
+        script: games to walk again instead of playing new ones (lib/reanalyse.py pack_scripts: init_boards, labels, offsets,
+        z): game id i replays script i, every ply searched as a self-play ply is and only the move taken from the script
+        (Search.set_script).  Needs record_visits; refused beside a book, the resignation audit and what
+        search_options.SCRIPT_EXCLUDES lists.  start(0): slot g walks scripts g, g + G, ... and goes idle after its last;
+        drain() reports `script_index` and `script_mismatch`."""
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
             gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
             solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
-        search_options.check(opts, history=use_history)
+        search_options.check(opts, history=use_history, script=script is not None)
         self.resign_audit = bool(getattr(getattr(config, "engine", None), "resign_audit", False)
                                  if resign_audit is None else resign_audit)
         if self.resign_audit and not opts["record_visits"]:
             raise ValueError("resign_audit needs record_visits: the max q rides beside the visit entries")
+        if script is not None and self.resign_audit:
+            raise ValueError("a script excludes resign_audit: a scripted game has no resignation test")
+        if script is not None and (book or os.environ.get("CZ_BOOK") or getattr(getattr(config, "engine", None), "book_path", None)):
+            raise ValueError("a script excludes a book: every script has its own start position")
         vars(self).update(opts)                # self.record_visits, self.fast_sims, ... self.kld_interval
         _native.require_gpu()
         self.config = config
@@ -133,6 +142,9 @@ class SelfPlayEngine:
             self.search.set_book(book_boards(self.book), self.book_rate)
         # every other option that is on: likewise before start() and before a graph capture
         search_options.apply(self.search, opts, skip=("eval_cache",))
+        self.script = script
+        if script is not None:                 # last: the library checks it against everything that is on
+            self.search.set_script(*script)
 
     def _build_net(self, net):
         """The inference network for these weights with the tower arithmetic checked against float64 (agent/model.py
@@ -259,6 +271,15 @@ class SelfPlayEngine:
         self.arith = nxt
         return True
 
+    def set_script(self, script):
+        """The next scripts of an engine created with one (worker/reanalyse.py: one call per batch); start(0) begins them.  A
+        captured graph holds the old scripts' addresses and is dropped."""
+        if self.script is None:
+            raise ValueError("set_script: the engine was created without a script (SelfPlayEngine(script=...))")
+        self.search.set_script(*script)
+        self.script = script
+        self._graph = None
+
     def start(self, first_game_id=0, game_id_stride=0):
         self.search.start_selfplay(self.seed, first_game_id, game_id_stride)
 
@@ -357,20 +378,25 @@ class SelfPlayEngine:
         weight 1 on a full ply and 0 on a fast one, q the root's search value rounded to 6 places or None; the appended
         king capture, a resignation and games whose visit record is incomplete keep the shorter forms.  With
         record_surprise such an item is [move, value, pi or None, weight, q or None, s]: s the ply's policy surprise
-        rounded to 6 places or None, q None with record_q off."""
+        rounded to 6 places or None, q None with record_q off.
+        A scripted game (script_index: its script, None otherwise) has the script's start position, its moves and, as
+        `value`, its z.  script_mismatch: the script did not fit the rules, the game holds the moves applied before that
+        and store is False."""
         out = []
         for r in self.search.drain_records(max_records, with_visits=self.record_visits):
             v = r["value"]
             vis = r.get("visits")
             bi = r["book_index"]
-            data = [INIT_STATE if bi is None else self.book[bi]]
+            si = r["script_index"]
+            data = [array_to_state(self.script[0][si]) if si is not None else INIT_STATE if bi is None else self.book[bi]]
             for i, m in enumerate(r["moves"]):
                 e = vis[i] if vis is not None and i < len(vis) and not vis[i].resign else None
                 data.append(record_item(ActionLabelsRed[int(m)], v if i % 2 == 0 else -v, e, r["fast"][i], self.record_q,
                                         ActionLabelsRed, record_surprise=self.record_surprise))
             pruned = [e for e in vis or [] if e.pruned]
             out.append(dict(game_id=r["game_id"], turns=r["turns"], value=v, store=r["store"],
-                            resigned=r["resigned"], book_index=bi, fast_plies=sum(r["fast"]),
+                            resigned=r["resigned"], book_index=bi, script_index=r["script_index"],
+                            script_mismatch=r["script_mismatch"], fast_plies=sum(r["fast"]),
                             pruned_visits=sum(e.raw_total - int(e.n[~e.banned].sum()) for e in pruned), data=data))
             if self.record_visits:
                 out[-1]["visits"] = vis

@@ -1,5 +1,6 @@
 """Command line of ``run.py`` -- same sub-commands and flags as the reference's cchess_alphazero/manager.py.
-``self`` (the hot path), ``opt`` (the trainer, worker/optimize.py) and ``eval`` (the arena) are served by
+``self`` (the hot path), ``opt`` (the trainer, worker/optimize.py), ``eval`` (the arena) and ``reanalyse``
+(stored games searched again with the best model, worker/reanalyse.py; the reference has no such command) are served by
 the MI355X engine; the other sub-commands of the reference (play, sl, ob) are outside the scope table and say
 so."""
 import argparse
@@ -11,7 +12,7 @@ from cchess_alphazero.lib.logger import setup_logger
 
 logger = getLogger(__name__)
 
-COMMANDS = ('self', 'opt', 'eval', 'play', 'sl', 'ob')
+COMMANDS = ('self', 'opt', 'eval', 'reanalyse', 'play', 'sl', 'ob')
 PIECE_STYLES = ('WOOD', 'POLISH', 'DELICATE')
 BOARD_STYLES = ('CANVAS', 'DROPS', 'GREEN', 'QIANHONG', 'SHEET', 'SKELETON', 'WHITE', 'WOOD')
 RANDOMNESS = ('none', 'small', 'medium', 'large')
@@ -48,8 +49,15 @@ _FLAGS = [
                                help="(opt) policy surprise weighting: within a game, the share A of the training weight goes "
                                     "to the rows in proportion to their recorded surprise (0 <= A <= 1; 0 = uniform, the "
                                     "reference; KataGo uses 0.5)")),
+    ("--records", dict(metavar="DIR", help="(reanalyse) the record files to walk again (default: data_dir/trained, where "
+                                           "`run.py opt` moves what it has trained on); a finished file moves to DIR/reanalysed")),
+    ("--out", dict(metavar="DIR", help="(reanalyse) where the new records go (default: the play-data directory, under names "
+                                       "`run.py opt` picks up)")),
+    ("--reanalyse-plies", dict(type=int, default=None, metavar="N",
+                               help="(reanalyse) plies of stored games handed to the device at once: a batch is all games of "
+                                    "as many files as fit (default 200000)")),
     ("--sims", dict(type=int, default=None, metavar="N",
-                    help="(self) simulations per move (default: the configuration's simulation_num_per_move)")),
+                    help="(self, reanalyse) simulations per move (default: the configuration's simulation_num_per_move)")),
     ("--policy-targets", dict(choices=["played", "visits"], default="played",
                               help="(opt) policy targets: the played move's one-hot (the reference) or the records' root "
                                    "visit counts")),
@@ -100,16 +108,26 @@ def build_config(args):
         raise SystemExit(f"--book-rate {args.book_rate}: expected 0 <= P <= 1")
     engine.book_path, engine.book_rate = args.book, args.book_rate
     if args.sims is not None:
-        if args.cmd != "self":
-            raise SystemExit("--sims is an option of `run.py self`")
+        if args.cmd not in ("self", "reanalyse"):
+            raise SystemExit("--sims is an option of `run.py self` and `run.py reanalyse`")
         if args.sims < 1:
             raise SystemExit(f"--sims {args.sims}: expected N >= 1")
         config.play.simulation_num_per_move = args.sims
     # the search options: ranges, commands, prerequisites and exclusions are their table's (search_options.py)
     values = {k: getattr(args, k) for k in search_options.VALUES}
+    reanalyse = args.cmd == "reanalyse"
+    if reanalyse:                                           # the new targets are the visit entries
+        values["record_visits"] = True
+        if args.book:
+            raise SystemExit("--book is not an option of `run.py reanalyse`: every stored game has its own start position")
+    elif args.records or args.out or args.reanalyse_plies is not None:
+        raise SystemExit("--records, --out and --reanalyse-plies are options of `run.py reanalyse`")
+    if args.reanalyse_plies is not None and args.reanalyse_plies < 1:
+        raise SystemExit(f"--reanalyse-plies {args.reanalyse_plies}: expected N >= 1")
+    engine.reanalyse_records, engine.reanalyse_out, engine.reanalyse_plies = args.records, args.out, args.reanalyse_plies
     try:
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
-                             history=getattr(config.model, "input_depth", 14) == 28)
+                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse)
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
     vars(engine).update(values)
@@ -142,7 +160,7 @@ def start():
     config = build_config(args)
     config.resource.create_directories()
     rc = config.resource
-    setup_logger({'self': rc.play_log_path, 'eval': rc.eval_log_path, 'opt': rc.opt_log_path}.get(args.cmd, rc.main_log_path))
+    setup_logger({'self': rc.play_log_path, 'reanalyse': rc.play_log_path, 'eval': rc.eval_log_path, 'opt': rc.opt_log_path}.get(args.cmd, rc.main_log_path))
     logger.info('Config type: %s' % (args.type))
     if args.cmd == 'self':
         if args.ucci:
@@ -157,6 +175,9 @@ def start():
         #  compute_elo.py:88 -- so a repeated position is still played at tau = 0.5, player.py:460-461)
         from cchess_alphazero.worker import evaluator
         return evaluator.start(config)
+    if args.cmd == 'reanalyse':
+        from cchess_alphazero.worker import reanalyse
+        return reanalyse.start(config)
     if args.cmd == 'opt':                                   # reference manager.py:85-87
         from cchess_alphazero.worker import optimize
         return optimize.start(config)

@@ -2,6 +2,7 @@
 
     python cchess_alphazero/run.py self [--type mini|normal|distribute] [--gpu 0,1,...]
     python cchess_alphazero/run.py eval [--type ...]
+    python cchess_alphazero/run.py reanalyse [--records DIR] [--out DIR] [--type ...]
 
 The work is done by the MI355X engine (see manager.py / worker/self_play.py).
 """

@@ -131,6 +131,15 @@ EXCLUDES = (("gumbel", "fast_sims", _ROOT_RULE), ("gumbel", "forced_playouts", _
             ("smart_pruning", "gumbel", _ROOT_RULE), ("smart_pruning", "solver", _ROOT_RULE),
             ("smart_pruning", "eval_cache", _CACHE))
 
+# A script (`run.py reanalyse`, SelfPlayEngine(script=...), Search.set_script) is no value of the table -- it has no flag and no
+# config.engine key, the games are its argument -- but it takes part in the exclusions: check(script=True) refuses these
+# beside it and asks for what it needs.  The library's setters hold the same list (csrc/xq_search.hip F_SCRIPT;
+# tests/test_gpu_reanalyse.py pins the two to each other).  A book and the resignation audit, which are not search options
+# either, are refused beside a script by the engine and by the library.
+_SCRIPT = "each defines its own root rule, start position or game end"
+SCRIPT_EXCLUDES = (("gumbel", _SCRIPT), ("solver", _SCRIPT), ("kld_gain", _SCRIPT), ("smart_pruning", _SCRIPT))
+SCRIPT_NEEDS = ("record_visits", "the new targets are the visit entries")
+
 VALUES = {v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 
@@ -157,7 +166,7 @@ def check(values, flags=False, cmd=None, sims=None, **context):
     per option its ranges, the command, its context rule, what it needs, what it excludes; options in table order.
     flags: the messages name --kld-gain where they would name kld_gain.  cmd: the run.py command (None: not checked);
     sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
-    input."""
+    input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES)."""
     def name(key):
         return VALUES[key].flag if flags else key
 
@@ -181,6 +190,12 @@ def check(values, flags=False, cmd=None, sims=None, **context):
         for later, earlier, why in EXCLUDES:
             if later == key and on(earlier):
                 raise SearchOptionError(f"{name(later)} excludes {name(earlier)}: {why}")
+    if context.get("script"):
+        if not on(SCRIPT_NEEDS[0]):
+            raise SearchOptionError(f"a script needs {name(SCRIPT_NEEDS[0])}: {SCRIPT_NEEDS[1]}")
+        for key, why in SCRIPT_EXCLUDES:
+            if on(key):
+                raise SearchOptionError(f"a script excludes {name(key)}: {why}")
 
 
 def apply(search, values, skip=()):

@@ -214,9 +214,12 @@ struct GameRecord {
     int32_t turns;
     int32_t value;      // from red's view: +1 red won, -1 black won, 0 draw (self_play.py:190-191)
     uint32_t flags;     // bit 0 store, bit 1 resigned, bit 2 (visit recording on only) an entry of the game was dropped;
+                        // bits 3-4 (a script set only) GAME_SCRIPTED, GAME_SCRIPT_MISMATCH;
                         // bits 8-31: book index + 1 of the game's start position, 0 = INIT_STATE (cz_search_set_book)
 };
 constexpr uint32_t GAME_VISITS_LOST = 4u;
+constexpr uint32_t GAME_SCRIPTED = 8u;          // flags bit 3: the game walked a script (cz_search_set_script)
+constexpr uint32_t GAME_SCRIPT_MISMATCH = 16u;  // flags bit 4: ... and ended on a mismatch (store = 0)
 constexpr int GAME_BOOK_SHIFT = 8;
 constexpr int BOOK_MAX = (1 << 24) - 2;    // positions a book may hold: what the 24-bit index + 1 field can name
 constexpr uint16_t MOVE_FAST = 0x8000;     // record moves[i], bit 15: ply i was a fast search (cz_search_set_playout_cap);
@@ -275,6 +278,21 @@ struct StopState {
     double* last_gain;      // [G] the last measured g of the ply, NaN = none
     int32_t* checks;        // [G] checkpoints of the ply, the one that took the first snapshot included
     uint8_t* cut;           // [G] the rule that ended the ply: 0 none, 1 KLD gain, 2 unreachable lead
+};
+
+// ---- scripted games (cz_search_set_script; advance_game<SCRIPT>, new_script_game) ----
+// Game id i < n walks script i: from boards[i] it plays labels[offsets[i] .. offsets[i + 1]) and ends with z[i].  Device copies
+// the search object owns.  Like the visit ring it reaches the kernels that use it (k_advance_script, k_start_script) as an
+// argument of its own.
+struct ScriptState {
+    const int8_t* boards;       // [n][90], first mover's frame
+    const uint16_t* labels;     // [offsets[n]]
+    const int32_t* offsets;     // [n + 1]
+    const int8_t* z;            // [n] the game's result from its first mover's view
+    unsigned long long* mismatches;   // [1] the counter script_mismatch: games that ended on a move their position does not have
+                                      // or on moves left over after the rules ended them.  Beside the scripts like the visit
+                                      // ring's `dropped`: enum Counter is what every kernel's counter block is sized by
+    int n;                      // 0 = off
 };
 
 }  // namespace xq

@@ -29,12 +29,13 @@
 //   xq_search_solver.h    the MCTS solver: its bit fields, solve_*, select_solve
 //   xq_search_sim.h       one simulation: Deferred, write_planes, expand_node, the cache probe, run_sim, flush_deferred
 //   xq_search_records.h   RootEdges, gumbel_choose, gumbel_targets, prune_targets, root_value, root_surprise, root_maxq, emit_visits
-//   xq_search_ply.h       the chunk pool, reserve_ply, ply_is_fast, begin_search, choose_action, new_game, the book, emit_record
+//   xq_search_ply.h       the chunk pool, reserve_ply, ply_is_fast, begin_search, choose_action, new_game, the book, emit_record,
+//                         new_script_game, script_move
 //   xq_search_selfplay.h  advance_game
 //   xq_search_stop.h      the early stop of a settled ply: stop_reset, ply_settled
 //   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop, k_cache_fill, k_advance, k_advance_stop,
-//                         k_stop_reset, k_noise
-//   xq_search_aux.h       every other kernel (k_start_selfplay .. k_debug_sqrt) and walk_path
+//                         k_advance_script, k_stop_reset, k_noise
+//   xq_search_aux.h       every other kernel (k_start_selfplay, k_start_script .. k_debug_sqrt) and walk_path
 // This file keeps the includes and the host side: the opaque search object and the C-ABI entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +85,8 @@ struct cz_search {
     StopState S{};                    // early stop of a settled ply (cz_search_set_kld_gain, cz_search_set_smart_pruning)
     void* stop_mem = nullptr;         // its per-game state, allocated only while a rule is on; S.prev_sum NULL = both off
     size_t stop_bytes = 0;
+    ScriptState X{};                  // scripted games (cz_search_set_script); X.n 0 = off
+    void* script_mem = nullptr;       // boards, labels, offsets and z, in one allocation
 };
 
 namespace {
@@ -310,6 +313,7 @@ int cz_search_destroy(cz_search* s)
     (void)hipFree(s->C.tab);
     (void)hipFree(s->ec_mem);
     (void)hipFree(s->stop_mem);
+    (void)hipFree(s->script_mem);
     (void)hipFree(s->pool);
     (void)hipFree(s->slab);
     delete s;
@@ -391,7 +395,8 @@ int cz_search_start_selfplay(cz_search* s, uint64_t seed, uint32_t first_game_id
         e = hipMemsetAsync(s->V.g_lost, 0, (size_t)s->P.G, (hipStream_t)stream);
     if (e != hipSuccess) return serr_hip("cz_search_start_selfplay", e);
     hipLaunchKernelGGL(k_pool_commit, dim3(1), dim3(1), 0, (hipStream_t)stream, s->B);
-    hipLaunchKernelGGL(k_start_selfplay, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, first_game_id);
+    if (s->X.n > 0) hipLaunchKernelGGL(k_start_script, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, s->X, first_game_id);
+    else hipLaunchKernelGGL(k_start_selfplay, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, first_game_id);
     if (s->stop_mem)                                  // every game's first search begins: empty snapshots
         hipLaunchKernelGGL(k_stop_reset, dim3((s->P.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->S, s->P.G,
                            (const uint8_t*)nullptr);
@@ -431,6 +436,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool cache = s->C.tab != nullptr;
     const bool solve = s->P.solver != 0;                        // (never with gum or cache: cz_search_set_solver)
     const bool stop = s->stop_mem != nullptr;                   // (never with gum, cache or solve: cz_search_set_kld_gain)
+    const bool script = s->X.n > 0 && s->P.mode == MODE_SELFPLAY;   // (never with gum, solve or stop: cz_search_set_script)
     auto sim = [&](int mask, int cq) {
         if (stop) {
             if (hist) hipLaunchKernelGGL((k_sim_stop<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
@@ -453,7 +459,8 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     if (cache)
         hipLaunchKernelGGL(k_cache_fill, dim3(s->P.G * s->P.K), block, 0, st, s->P, s->B, s->C, policy, value, consume_compact);
     sim(SIM_BACKUP, consume_compact);
-    if (stop) hipLaunchKernelGGL(k_advance_stop, grid, block, 0, st, s->P, s->B, s->V, s->S);
+    if (script) hipLaunchKernelGGL(k_advance_script, grid, block, 0, st, s->P, s->B, s->V, s->X);
+    else if (stop) hipLaunchKernelGGL(k_advance_stop, grid, block, 0, st, s->P, s->B, s->V, s->S);
     else if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
@@ -530,22 +537,24 @@ int cz_search_policy_logits(cz_search* s, int on)
 // ---- features that cannot run beside each other (include/czero.h has the matrix and the reasons) -------------------------
 // Host only.  A refused setter names the first excluder that is on, in this order; each phrase stands here once.
 // cchess_alphazero/search_options.py states the same pairs for the layers above (tests/test_gpu_search_options.py).
-enum Feature : int { F_FORCED, F_CAP, F_GUMBEL, F_SOLVER, F_KLD, F_LEAD, F_CACHE, F_COUNT };
+enum Feature : int { F_FORCED, F_CAP, F_GUMBEL, F_SOLVER, F_KLD, F_LEAD, F_CACHE, F_SCRIPT, F_COUNT };
 constexpr unsigned fbit(Feature f) { return 1u << f; }
 constexpr struct { bool (*on)(const cz_search*); const char* phrase; unsigned excludes; } FEATURES[F_COUNT] = {
     {[](const cz_search* s) { return s->P.forced_k > 0.0; }, "forced playouts are on (cz_search_set_forced_playouts)",
      fbit(F_GUMBEL) | fbit(F_SOLVER)},
     {[](const cz_search* s) { return s->P.fast_sims > 0; }, "the playout cap is on (cz_search_set_playout_cap)", fbit(F_GUMBEL)},
     {[](const cz_search* s) { return s->P.gumbel_m > 0; }, "the Gumbel root search is on (cz_search_set_gumbel)",
-     fbit(F_FORCED) | fbit(F_CAP) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+     fbit(F_FORCED) | fbit(F_CAP) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_SCRIPT)},
     {[](const cz_search* s) { return s->P.solver != 0; }, "the MCTS solver is on (cz_search_set_solver)",
-     fbit(F_FORCED) | fbit(F_GUMBEL) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE)},
+     fbit(F_FORCED) | fbit(F_GUMBEL) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT)},
     {[](const cz_search* s) { return s->S.gain > 0.0; }, "the KLD-gain stop is on (cz_search_set_kld_gain)",
-     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE)},
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT)},
     {[](const cz_search* s) { return s->S.lead != 0; }, "the unreachable-lead stop is on (cz_search_set_smart_pruning)",
-     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE)},
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT)},
     {[](const cz_search* s) { return s->C.tab != nullptr; }, "the evaluation cache is on (cz_search_set_eval_cache)",
      fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+    {[](const cz_search* s) { return s->X.n > 0; }, "a script is set (cz_search_set_script)",
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
 };
 constexpr bool features_symmetric()
 {
@@ -717,6 +726,7 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_visits: null handle");
     if (capacity < 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity < 0");
+    if (!on && s->X.n > 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: a script is set (cz_search_set_script)");
     hipStream_t st = (hipStream_t)stream;
     // the value, the surprise and the max-q ring share the visit ring's slots: they go with it.  side_ring waits for the
     // stream: no launch in flight may still use the old buffers
@@ -763,6 +773,7 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
     if (n < 0 || n > BOOK_MAX) return serr(CZ_ERR_ARG, "cz_search_set_book: n outside 0 .. CZ_BOOK_MAX");
     if (n > 0 && !boards) return serr(CZ_ERR_ARG, "cz_search_set_book: null boards");
     if (!(rate >= 0.0 && rate <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_book: rate outside [0, 1]");
+    if (n > 0 && s->X.n > 0) return serr(CZ_ERR_ARG, "cz_search_set_book: a script is set (cz_search_set_script)");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still read the old book
     if (e != hipSuccess) return serr_hip("cz_search_set_book", e);
@@ -780,6 +791,64 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
     s->P.book_n = n;
     s->P.book_rate = n > 0 ? rate : 0.0;
     return CZ_OK;
+}
+
+static_assert(CZ_GAME_SCRIPTED == GAME_SCRIPTED && CZ_GAME_SCRIPT_MISMATCH == GAME_SCRIPT_MISMATCH, "czero.h: script flags");
+
+int cz_search_set_script(cz_search* s, const int8_t* init_boards, const uint16_t* labels, const int32_t* offsets,
+                         const int8_t* z, int n, void* stream)
+{
+    const char* const me = "cz_search_set_script";
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_script: null handle");
+    if (n < 0) return serr(CZ_ERR_ARG, "cz_search_set_script: n < 0");
+    if (n > 0 && (!init_boards || !offsets || !z)) return serr(CZ_ERR_ARG, "cz_search_set_script: null argument");
+    if (n > 0) {
+        // a script defines the start position, the move and the end of every game: not beside what defines one of them too
+        if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_set_script: needs cz_search_record_visits on");
+        if (s->P.book_n > 0) return serr(CZ_ERR_ARG, "cz_search_set_script: a book is set (cz_search_set_book)");
+        if (s->V.mq) return serr(CZ_ERR_ARG, "cz_search_set_script: the max-q record is on (cz_search_record_maxq)");
+        if (offsets[0] != 0) return serr(CZ_ERR_ARG, "cz_search_set_script: offsets[0] != 0");
+        for (int i = 0; i < n; ++i) {
+            if (offsets[i + 1] < offsets[i]) return serr(CZ_ERR_ARG, "cz_search_set_script: offsets decrease");
+            if (z[i] < -1 || z[i] > 1) return serr(CZ_ERR_ARG, "cz_search_set_script: z outside -1 .. 1");
+        }
+        if (offsets[n] > 0 && !labels) return serr(CZ_ERR_ARG, "cz_search_set_script: null labels");
+    }
+    if (const int rc = admit(s, F_SCRIPT, n > 0, me, stream)) return rc;   // (then no launch in flight reads the old script)
+    hipStream_t st = (hipStream_t)stream;
+    void* mem = nullptr;
+    ScriptState X{};
+    if (n > 0) {                                         // the new script is complete before the old one goes
+        const size_t total = (size_t)offsets[n];
+        const size_t off_lab = align_up((size_t)n * NSQ), off_off = off_lab + align_up(2 * total),
+                     off_z = off_off + align_up(4 * ((size_t)n + 1)), off_ctr = off_z + align_up((size_t)n);
+        hipError_t e = hipMalloc(&mem, off_ctr + align_up(8));
+        if (e != hipSuccess) return serr_hip("cz_search_set_script: hipMalloc", e);
+        char* m = (char*)mem;
+        e = hipMemsetAsync(m + off_ctr, 0, 8, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m, init_boards, (size_t)n * NSQ, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && total) e = hipMemcpyAsync(m + off_lab, labels, 2 * total, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m + off_off, offsets, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(m + off_z, z, (size_t)n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { (void)hipFree(mem); return serr_hip(me, e); }
+        X = ScriptState{(const int8_t*)m, (const uint16_t*)(m + off_lab), (const int32_t*)(m + off_off), (const int8_t*)(m + off_z),
+                        (unsigned long long*)(m + off_ctr), n};
+    }
+    (void)hipFree(s->script_mem);
+    s->script_mem = mem;
+    s->X = X;
+    return CZ_OK;
+}
+
+int cz_search_script_mismatches(cz_search* s, uint64_t* host_out, void* stream)
+{
+    if (!s || !host_out) return serr(CZ_ERR_ARG, "cz_search_script_mismatches: null argument");
+    *host_out = 0;
+    if (s->X.n == 0) return CZ_OK;
+    hipError_t e = hipMemcpyAsync(host_out, s->X.mismatches, 8, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip("cz_search_script_mismatches", e);
 }
 
 static_assert(CZ_MOVE_FAST == MOVE_FAST && CZ_VISIT_FAST == VISIT_FAST, "czero.h: playout cap flags");
@@ -1155,6 +1224,7 @@ int cz_search_record_maxq(cz_search* s, int on, void* stream)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_record_maxq: null handle");
     if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_maxq: needs cz_search_record_visits on");
+    if (on && s->X.n > 0) return serr(CZ_ERR_ARG, "cz_search_record_maxq: a script is set (cz_search_set_script)");
     return side_ring(s, s->V.mq, on, (hipStream_t)stream, "cz_search_record_maxq");
 }
 

@@ -30,6 +30,20 @@ __global__ __launch_bounds__(64) void k_start_selfplay(SearchParams P, SearchBuf
     new_game(P, B, gv, L, first_game_id + (uint32_t)g);
 }
 
+// k_start_selfplay with a script on: slot g starts on script first_game_id + g, or idle where there is none
+__global__ __launch_bounds__(64) void k_start_script(SearchParams P, SearchBuffers B, ScriptState X, uint32_t first_game_id)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, L.chtab);   // counts go straight to the global block
+    const int lane = lane_id();
+    for (int i = lane; i < P.K; i += 64) gv.s_state[i] = SIM_IDLE;
+    for (int i = lane; i < CT_COUNT; i += 64) gv.ctr[i] = 0;
+    wave_sync_global();
+    new_script_game(P, B, gv, L, X, first_game_id + (uint32_t)g);
+}
+
 __global__ __launch_bounds__(64) void k_set_roots(SearchParams P, SearchBuffers B, const int8_t* __restrict__ boards,
                                                  const int32_t* __restrict__ turns, const uint16_t* __restrict__ no_act,
                                                  const uint8_t* __restrict__ n_no_act, const uint8_t* __restrict__ inc,

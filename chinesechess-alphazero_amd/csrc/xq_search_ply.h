@@ -5,7 +5,7 @@
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
 // Between the searches of a game: the chunk pool (pool_commit, pool_take), clear_tree, reserve_ply, ply_is_fast, begin_search,
-// choose_action, the start positions (set_init_board, the book), new_game, emit_record.
+// choose_action, the start positions (set_init_board, the book), open_game, new_game, new_script_game, script_move, emit_record.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_solver.h"
@@ -344,16 +344,11 @@ XQ_D void set_book_board(int8_t* gb, const int8_t* src)
     for (int s = lane; s < BOARD_LDS; s += 64) gb[s] = s < NSQ ? src[s] : (int8_t)0;
 }
 
-// (re)start a self-play game in slot g (SelfPlayWorker.start_game, self_play.py:95-116; with a book the position its
-// INIT_STATE stands for: turns, no_eat_count, history and "red = the first mover" as from the opening position)
-XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, uint32_t game_id)
+// the rest of a game's start, its position being in g_board (new_game, new_script_game)
+XQ_D void open_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, uint32_t game_id)
 {
     const int lane = lane_id();
     const int g = gv.g;
-    clear_tree(P, B, gv, L.chtab);
-    const int bi = book_index(P, game_id);
-    if (bi < 0) set_init_board(B.g_board + (size_t)g * BOARD_LDS);
-    else set_book_board(B.g_board + (size_t)g * BOARD_LDS, P.book + (size_t)bi * NSQ);
     wave_sync_global();
     const int8_t* gb = B.g_board + (size_t)g * BOARD_LDS;
     L.r.bd[1][lane] = gb[lane];
@@ -373,6 +368,58 @@ XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView
     }
     wave_sync_global();
     begin_search(P, B, gv, L);
+}
+
+// (re)start a self-play game in slot g (SelfPlayWorker.start_game, self_play.py:95-116; with a book the position its
+// INIT_STATE stands for: turns, no_eat_count, history and "red = the first mover" as from the opening position)
+XQ_D void new_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, uint32_t game_id)
+{
+    const int g = gv.g;
+    clear_tree(P, B, gv, L.chtab);
+    const int bi = book_index(P, game_id);
+    if (bi < 0) set_init_board(B.g_board + (size_t)g * BOARD_LDS);
+    else set_book_board(B.g_board + (size_t)g * BOARD_LDS, P.book + (size_t)bi * NSQ);
+    open_game(P, B, gv, L, game_id);
+}
+
+// (re)start slot g on a script (cz_search_set_script): game `game_id` walks script `game_id` from its own start position, like
+// a book game; a slot whose next game id has no script has nothing left to play and goes PH_IDLE.
+XQ_D void new_script_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
+                          const ScriptState& X, uint32_t game_id)
+{
+    const int g = gv.g;
+    clear_tree(P, B, gv, L.chtab);
+    if (game_id >= (uint32_t)X.n) {
+        if (lane_id() == 0) {
+            B.g_game_id[g] = game_id;
+            B.g_tasks_left[g] = 0;
+            B.g_active[g] = 0;
+            B.g_phase[g] = PH_IDLE;
+        }
+        wave_sync_global();
+        return;
+    }
+    set_book_board(B.g_board + (size_t)g * BOARD_LDS, X.boards + (size_t)game_id * NSQ);
+    open_game(P, B, gv, L, game_id);
+}
+
+// What a scripted game plays at ply `turns` instead of choose_action's move: the script's label; SCRIPT_END when the script is
+// exhausted; SCRIPT_BAD when the label is not among the root's edges -- the position's legal moves, banned ones included --
+// or the search left no root to ask: such a move never reaches step_board.
+constexpr int SCRIPT_END = -1, SCRIPT_BAD = -3;
+// off, len: the script's place in X.labels.
+XQ_D int script_move(const SearchBuffers& B, const GameView& gv, const ScriptState& X, int off, int len, int turns)
+{
+    const int lane = lane_id();
+    if (turns >= len) return SCRIPT_END;
+    const uint16_t mv = (uint16_t)uni((int)X.labels[off + turns]);
+    const int root = uni(B.g_root[gv.g]);
+    if (root < 0) return SCRIPT_BAD;
+    char* base = rec_ptr(gv, (uint32_t)root);
+    const int nm = (int)(load_hdr(base).meta & 0xFF);
+    const uint16_t* pm = node_mv(base, nm);
+    const bool hit = (lane < nm && pm[lane] == mv) || (lane + 64 < nm && pm[lane + 64] == mv);
+    return __ballot(hit) ? (int)mv : SCRIPT_BAD;
 }
 
 // searched: the first `searched` moves came from searches (the rest is the appended king capture): those of fast plies

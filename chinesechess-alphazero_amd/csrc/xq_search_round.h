@@ -5,7 +5,7 @@
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
 // The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop; k_cache_fill, k_advance,
-// k_advance_stop, k_stop_reset, k_noise.
+// k_advance_stop, k_advance_script, k_stop_reset, k_noise.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
@@ -405,6 +405,23 @@ __global__ __launch_bounds__(64) void k_advance_stop(SearchParams P, SearchBuffe
         }
     } else if (lane_id() == 0) {
         B.g_phase[g] = PH_READY;
+    }
+    counters_flush(gv);
+}
+
+// k_advance with a script on (cz_search_set_script); launched in self-play mode only, external mode keeps k_advance.  A slot
+// that has walked its last script is PH_IDLE and is left alone by every kernel of the round.
+__global__ __launch_bounds__(64) void k_advance_script(SearchParams P, SearchBuffers B, VisitRing V, ScriptState X)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_active[g]) != 0 || uni(B.g_tasks_left[g]) != 0) return;
+    const GameView gv = make_view(B, P, g, L.ctr, L.chtab);
+    counters_begin(gv);
+    for (int it = 0; it < 8; ++it) {              // a search with nothing to do (fully reused root) ends at once
+        advance_game<false, false, false, true>(P, B, gv, L, V, StopState{}, X);
+        if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
     }
     counters_flush(gv);
 }

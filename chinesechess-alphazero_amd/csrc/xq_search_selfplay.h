@@ -14,9 +14,14 @@ namespace {
 
 // One ply of SelfPlayWorker.start_game after the search finished (self_play.py:124-212).
 // STOP (k_advance_stop, a stop rule is on): the visit entry of a ply that a rule ended says so (VISIT_EARLY, from S.cut).
-template <bool FULL, bool SOLVE = false, bool STOP = false>        // (emit_visits', choose_action's)
+// SCRIPT (k_advance_script, cz_search_set_script): the game walks script X[game_id].  The search's own choice is not made (no
+// resignation test, no temperature, no draw from stream 1): the move is the script's, tested against the root's edges
+// (script_move), and everything after it is the loop's.  The game ends where the rules end it -- the script then has nothing
+// left but, possibly, the rules' final_move -- or where the script ends; its value is X.z, it is stored without a lottery and
+// flagged GAME_SCRIPTED.  Anything else is a mismatch: GAME_SCRIPT_MISMATCH, store = 0, the next script.
+template <bool FULL, bool SOLVE = false, bool STOP = false, bool SCRIPT = false>   // (emit_visits', choose_action's)
 XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
-                       const VisitRing& V, const StopState& S = StopState{})
+                       const VisitRing& V, const StopState& S = StopState{}, const ScriptState& X = ScriptState{})
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -25,8 +30,18 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     int8_t* gb = B.g_board + (size_t)g * BOARD_LDS;
     uint32_t* hkeys = B.g_hist_key + (size_t)g * (P.max_plies + 2) * KEY_WORDS;
     uint16_t* hacts = B.g_hist_act + (size_t)g * (P.max_plies + 2);
-    const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
-    const int action = choose_action<SOLVE>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
+    int action;
+    int script_off = 0, script_len = 0;                                // (a game id beyond the scripts: an empty script)
+    if constexpr (SCRIPT) {
+        if (game_id < (uint32_t)X.n) {
+            script_off = uni(X.offsets[game_id]);
+            script_len = uni(X.offsets[game_id + 1]) - script_off;
+        }
+        action = script_move(B, gv, X, script_off, script_len, turns);
+    } else {
+        const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
+        action = choose_action<SOLVE>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
+    }
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);
         bool early = false;
@@ -37,8 +52,8 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     bool game_over = false, resigned = false;
     int value = 0;
     int final_move = NOMOVE;
-    if (action < 0) {                                                  // resign, :126-129
-        value = -1; game_over = true; resigned = true;
+    if (action < 0) {                                                  // resign, :126-129 (SCRIPT: its end, or a bad move)
+        value = -1; game_over = true; resigned = !SCRIPT;
     } else {
         // state, no_eat = senv.new_step(state, action)  (:133-141)
         L.r.bd[0][lane] = gb[lane];
@@ -115,6 +130,15 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
         begin_search(P, B, gv, L);
         return;
     }
+    bool mismatch = false;
+    if constexpr (SCRIPT) {
+        // the rules ended the game: the script may hold nothing more, or exactly their final_move (appended only then)
+        const int rest = script_len - turns;
+        bool capture = false;
+        if (rest == 1 && final_move != NOMOVE) capture = uni((int)X.labels[script_off + turns]) == final_move;
+        mismatch = action == SCRIPT_BAD || (action >= 0 && rest != 0 && !capture);
+        if (!capture) final_move = NOMOVE;
+    }
     const int searched = turns;
     if (final_move != NOMOVE) {                                         // :177-184
         if (lane == 0 && turns < P.max_plies + 2) hacts[turns] = (uint16_t)final_move;
@@ -123,7 +147,8 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
     }
     if (turns % 2 == 1) value = -value;                                 // :190-191
     bool store = true;
-    if (turns < 10) store = philox_uniform(P.seed, game_id, 0, 1) > 0.9;   // :194-200
+    if constexpr (SCRIPT) store = !mismatch;
+    else if (turns < 10) store = philox_uniform(P.seed, game_id, 0, 1) > 0.9;   // :194-200
     wave_sync_global();
     uint32_t extra = 0u;
     if (V.ring) {                                                       // the next game in this slot starts complete
@@ -131,8 +156,16 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
         if (lane == 0) { lost = V.g_lost[g]; V.g_lost[g] = 0; }
         extra = uni(lost) ? GAME_VISITS_LOST : 0u;
     }
-    emit_record(P, B, gv, turns, searched, value, store, resigned, extra);
-    new_game(P, B, gv, L, game_id + P.game_id_stride);
+    if constexpr (SCRIPT) {
+        value = game_id < (uint32_t)X.n ? uni((int)X.z[game_id]) : 0;
+        extra |= GAME_SCRIPTED | (mismatch ? GAME_SCRIPT_MISMATCH : 0u);
+        if (mismatch && lane == 0) atomicAdd(X.mismatches, 1ull);
+        emit_record(P, B, gv, turns, searched, value, store, resigned, extra);
+        new_script_game(P, B, gv, L, X, game_id + P.game_id_stride);
+    } else {
+        emit_record(P, B, gv, turns, searched, value, store, resigned, extra);
+        new_game(P, B, gv, L, game_id + P.game_id_stride);
+    }
 }
 
 }  // namespace

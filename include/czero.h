@@ -136,6 +136,7 @@ typedef struct cz_game_record {
                                         made the game's first move, also when the game started from a book position */
     uint32_t flags;                  /* bit 0: store (self_play.py:194-200), bit 1: ended by resignation,
                                         bit 2: (visit recording on) the game has no complete visit record,
+                                        bits 3-4: CZ_GAME_SCRIPTED, CZ_GAME_SCRIPT_MISMATCH (cz_search_set_script),
                                         bits 8-31: the game's start position: book index + 1, 0 = INIT_STATE
                                         (cz_search_set_book; written by the kernel, the host never redraws the lottery) */
 } cz_game_record;
@@ -188,7 +189,42 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * cz_last_error names its entry point and the first excluder that is on, looked for in the order forced playouts, playout
  * cap, Gumbel root search, MCTS solver, KLD-gain stop, unreachable-lead stop, evaluation cache.  Switching OFF is never
  * refused.  Each of these setters checks in one order: the handle, its arguments' ranges, the exclusions, then it
- * synchronises the stream and assigns. */
+ * synchronises the stream and assigns.
+ * A script (cz_search_set_script, below) is an eighth member, the last in that order: it is not beside the Gumbel root
+ * search, the MCTS solver, the KLD-gain stop and the unreachable-lead stop, which define a root rule or a ply's end of
+ * their own, and -- outside the table, refused the same way in both directions -- not beside a book (a start position of
+ * its own) and the max-q record of the resignation audit (a scripted game has no resignation test). */
+
+/* Scripted games: walk stored games again (MuZero's Reanalyse).  n games: game id i < n starts from init_boards[i] (90
+ * bytes, the first mover's frame, as cz_replay_games takes them), plays labels[offsets[i] .. offsets[i+1]) and ends with
+ * the result z[i] (first mover's view, -1 / 0 / 1).  HOST pointers, copied to device memory the object owns.  n = 0: off.
+ * Call it before cz_search_start_selfplay and before a graph capture, like cz_search_set_book; needs
+ * cz_search_record_visits on.  Start with first_game_id 0 and the default stride: slot g walks scripts g, g + G, ...; a
+ * slot whose next game id is >= n goes idle and produces nothing more (cz_search_pending counts the slots still walking).
+ * EVERY PLY IS SEARCHED EXACTLY AS A SELF-PLAY PLY IS: root noise from (seed, game_id, turns), the no_act list and
+ * increase_temp of the game loop, the fast / full lottery of the playout cap, forced playouts, the leaf mirror, tree
+ * reuse; the visit entries and the q / s rings hold what they hold in self-play.  Only the move differs: the search's own
+ * choice is not made (no resignation test, no temperature, no draw from stream 1) and ply t applies labels[offsets[i] + t],
+ * after which the loop does what it always does.  Whether the scripted child was visited (its subtree is reused) or not
+ * (the new root starts as a game's first root does) makes no difference.
+ * A game ends where the rules end it -- then the script must hold nothing more, or exactly the rules' final_move, the king
+ * capture the reference appends, which is recorded only then -- or where the script ends while the rules say play on (a
+ * resigned or cut game: that position is still searched and its entry carries CZ_VISIT_RESIGN, "no move").  Its record
+ * has value = z[i], store = 1 without the lottery, resigned = 0 and CZ_GAME_SCRIPTED.
+ * A MISMATCH is a scripted move that is not among the root's edges (the position's legal moves, banned ones included), or
+ * moves left over when the rules end the game.  It never steps the board: the game ends at once with the moves applied so
+ * far, store = 0, CZ_GAME_SCRIPT_MISMATCH and the counter script_mismatch (cz_search_script_mismatches: it lives beside the
+ * scripts, as the visit ring's `dropped` does beside the ring, and starts at 0 with every set_script), and the slot takes
+ * its next script.
+ * Without a script every kernel, record and counter is what it was: the scripted loop is a kernel instantiation of its own.
+ * CZ_ERR_ARG: n < 0, a null array with n > 0, offsets[0] != 0 or decreasing, z outside -1 .. 1, the visit record off, an
+ * excluder on -- the object keeps its script. */
+#define CZ_GAME_SCRIPTED 8u          /* cz_game_record.flags bit 3: the game walked a script */
+#define CZ_GAME_SCRIPT_MISMATCH 16u  /* bit 4: ... and ended on a mismatch */
+int cz_search_set_script(cz_search* s, const int8_t* init_boards, const uint16_t* labels, const int32_t* offsets,
+                         const int8_t* z, int n, void* stream);
+/* HOST out[1]: scripted games that ended on a mismatch since the script was set (0 without one); synchronises the stream */
+int cz_search_script_mismatches(cz_search* s, uint64_t* host_out, void* stream);
 
 /* Playout cap randomization of self-play (KataGo: Wu 2019, section 3.1; the reference has no such option).  With
  * fast_sims > 0 every ply of every self-play game is either a FULL search -- simulation_num_per_move simulations, root
