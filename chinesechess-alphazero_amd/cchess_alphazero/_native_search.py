@@ -58,6 +58,9 @@ def check_eval_cache_log2(log2_entries, what="eval_cache"):
 # without resignation (False with the record off).
 VisitEntry = namedtuple("VisitEntry", "moves n banned sum_n ply resign fast pruned raw_total q s gumbel early maxq no_resign",
                         defaults=(None, None, False, False, None, False))
+# The side columns of a visit entry in the library's order (CZ_VISIT_COL_* of include/czero.h): the VisitEntry field, and the
+# Search attribute that says whether the column is on.
+COLUMNS = (("q", "values_on"), ("s", "surprise_on"), ("maxq", "maxq_on"))
 
 
 class SearchCfg(C.Structure):
@@ -115,15 +118,13 @@ def declare(L):
         "cz_search_root_targets": [vp, vp, vp, vp],
         "cz_policy_target_prune": [vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
         "cz_search_record_values": [vp, i32, vp],
-        "cz_search_drain_visits_q": [vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
         "cz_search_root_value": [vp, vp, vp],
         "cz_root_value": [vp, vp, vp, vp, vp, i32, vp, vp],
         "cz_search_record_surprise": [vp, i32, vp],
-        "cz_search_drain_visits_qs": [vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
         "cz_search_root_surprise": [vp, vp, vp],
         "cz_root_surprise": [vp, vp, vp, vp, i32, vp, vp],
         "cz_search_record_maxq": [vp, i32, vp],
-        "cz_search_drain_visits_qsm": [vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
+        "cz_search_drain_visits_cols": [vp, vp, C.POINTER(vp), i32, C.POINTER(C.c_int), C.POINTER(C.c_uint64), vp],
         "cz_search_root_maxq": [vp, vp, vp],
         "cz_root_maxq": [vp, vp, vp, vp, i32, vp, vp],
         "cz_search_set_resign_threshold": [vp, d, vp],
@@ -331,9 +332,8 @@ class Search:
         _native.check(self.L.cz_search_record_visits(self.h, int(bool(on)), int(capacity), self._stream()),
                       "cz_search_record_visits")
         self.visit_capacity = (int(capacity) or 64 * self.G) if on else 0
-        self.values_on = False                 # (the library frees the value ring with the visit ring)
-        self.surprise_on = False               # (and the surprise ring)
-        self.maxq_on = False                   # (and the max-q ring)
+        for _, flag in COLUMNS:                # (the library frees the side columns with the visit ring)
+            setattr(self, flag, False)
         self._visits = {}
         self._raw_visits = []
         self._visits_dropped = 0
@@ -564,13 +564,19 @@ class Search:
         n, raw = self._root_outputs("cz_search_gumbel_targets", ((self.G, _native.MAXMOVES), "int32"), ((self.G,), "int32"))
         return dict(n=n, raw_total=raw)
 
+    def _record_column(self, fn, flag, on):
+        """Switch one side column of the visit entries (COLUMNS) through its entry point and note it in its attribute."""
+        if not hasattr(self.L, fn):
+            raise _native.NativeError("this libczero.so has no such record (%s)" % fn)
+        _native.check(getattr(self.L, fn)(self.h, int(bool(on)), self._stream()), fn)
+        setattr(self, flag, bool(on))
+
     def record_values(self, on=True):
         """Self-play: every visit entry comes with the root's search value q (cz_search_record_values; include/czero.h has
         the arithmetic): VisitEntry.q, None where the root had no value.  Needs record_visits() on, and a later
         record_visits() call switches it off again.  Call it before start_selfplay() and before a graph capture.  Entries
         fetched before the switch keep what they had."""
-        _native.check(self.L.cz_search_record_values(self.h, int(bool(on)), self._stream()), "cz_search_record_values")
-        self.values_on = bool(on)
+        self._record_column("cz_search_record_values", "values_on", on)
 
     def root_value(self):
         """The search value of every current root, as a visit entry of that root would carry it (cz_search_root_value;
@@ -583,9 +589,7 @@ class Search:
         arithmetic): VisitEntry.s, None where the root had none.  Needs record_visits() on, and a later record_visits()
         call switches it off again.  Call it before start_selfplay() and before a graph capture.  Entries fetched before
         the switch keep what they had."""
-        _native.check(self.L.cz_search_record_surprise(self.h, int(bool(on)), self._stream()),
-                      "cz_search_record_surprise")
-        self.surprise_on = bool(on)
+        self._record_column("cz_search_record_surprise", "surprise_on", on)
 
     def root_surprise(self):
         """The policy surprise of every current root, as a visit entry of that root would carry it
@@ -598,10 +602,7 @@ class Search:
         VisitEntry.maxq; and the entries of games that play on without resignation say so (VisitEntry.no_resign).  Needs
         record_visits() on, and a later record_visits() call switches it off again.  Call it before start_selfplay() and
         before a graph capture.  Entries fetched before the switch keep what they had."""
-        if not hasattr(self.L, "cz_search_record_maxq"):
-            raise _native.NativeError("this libczero.so has no max-q record (cz_search_record_maxq)")
-        _native.check(self.L.cz_search_record_maxq(self.h, int(bool(on)), self._stream()), "cz_search_record_maxq")
-        self.maxq_on = bool(on)
+        self._record_column("cz_search_record_maxq", "maxq_on", on)
 
     def root_maxq(self):
         """The resignation test's max q of every current root, as a visit entry of that root would carry it
@@ -646,36 +647,23 @@ class Search:
                 self.ingest_visits()
             return 0
         buf = np.empty((n.value, VISIT_STRIDE), dtype=np.uint8)
-        q = None
-        if self.maxq_on:
-            # all three rings beside the entries; a record that is off is not copied and stays NaN, "none"
-            q = np.full((n.value, 3), np.nan, dtype=np.float64)
-            cols = [np.empty((n.value,), dtype=np.float64) for _ in range(3)]
-            rings = [cols[0].ctypes.data if self.values_on else None, cols[1].ctypes.data if self.surprise_on else None,
-                     cols[2].ctypes.data]
-            fn = "cz_search_drain_visits_qsm"
-            _native.check(getattr(self.L, fn)(self.h, buf.ctypes.data, *rings, n.value, C.byref(n), C.byref(dropped),
+        on = [getattr(self, flag) for _, flag in COLUMNS]
+        cols = None
+        if any(on):
+            # the columns that are on beside the entries; one that is off is not copied and stays NaN, "none"
+            fn = "cz_search_drain_visits_cols"
+            if not hasattr(self.L, fn):
+                raise _native.NativeError("this libczero.so cannot drain the side columns of the visit entries (%s)" % fn)
+            cols = np.full((len(COLUMNS), n.value), np.nan, dtype=np.float64)
+            ptrs = (C.c_void_p * len(COLUMNS))(*[cols[k].ctypes.data if on[k] else None for k in range(len(COLUMNS))])
+            _native.check(getattr(self.L, fn)(self.h, buf.ctypes.data, ptrs, n.value, C.byref(n), C.byref(dropped),
                                               self._stream()), fn)
-            for k, on in enumerate((self.values_on, self.surprise_on, True)):
-                if on:
-                    q[:, k] = cols[k]
-        elif self.values_on or self.surprise_on:
-            # both rings beside the entries; a record that is off is not copied and leaves q at NaN, "no value"
-            q = np.full((n.value,), np.nan, dtype=np.float64)
-            sp = np.empty((n.value,), dtype=np.float64)
-            rings = [q.ctypes.data if self.values_on else None, sp.ctypes.data if self.surprise_on else None]
-            fn = "cz_search_drain_visits_qs"
-            if not hasattr(self.L, fn):        # (an older library selected with CZ_LIB: it has the value record alone)
-                fn, rings = "cz_search_drain_visits_q", rings[:1]
-            _native.check(getattr(self.L, fn)(self.h, buf.ctypes.data, *rings, n.value, C.byref(n), C.byref(dropped),
-                                              self._stream()), fn)
-            if self.surprise_on:
-                q = np.stack([q, sp], axis=1)
+            cols = np.ascontiguousarray(cols.T)
         else:
             _native.check(self.L.cz_search_drain_visits(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(dropped),
                                                         self._stream()), "cz_search_drain_visits")
         self._visits_dropped = int(dropped.value)
-        self._raw_visits.append((buf, q))
+        self._raw_visits.append((buf, cols))
         if not defer:
             self.ingest_visits()
         return n.value
@@ -683,14 +671,14 @@ class Search:
     def ingest_visits(self):
         """Sort the entries fetched by pull_visits(defer=True) by game."""
         raw, self._raw_visits = self._raw_visits, []
-        for buf, q in raw:
+        for buf, cols in raw:
             gids = buf[:, 0:4].copy().view(np.uint32)[:, 0]
             plies = buf[:, 4:6].copy().view(np.uint16)[:, 0]
             for i in range(buf.shape[0]):      # kept trimmed to the root's edges until the game's record arrives
                 ne = int(buf[i, 6])
                 row = buf[i, :16].tobytes() + buf[i, 16:16 + 2 * ne].tobytes() + buf[i, 272:272 + 4 * ne].tobytes()
-                if q is not None:              # the entry's value (and surprise, and max q) ride behind its edges
-                    row += q[i:i + 1].tobytes()
+                if cols is not None:           # the entry's side columns ride behind its edges
+                    row += cols[i].tobytes()
                 self._visits.setdefault(int(gids[i]), []).append((int(plies[i]), row))
 
     def waiting_visits(self):
@@ -703,28 +691,22 @@ class Search:
 
     @staticmethod
     def parse_visit_entry(row):
-        """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges], then with the value
-        record on its float64 q, with the surprise record on float64 q (NaN with the value record off) and s, with the
-        max-q record on float64 q, s (NaN where that record is off) and maxq) -> VisitEntry."""
+        """A ring entry trimmed to its edges (16-byte header, uint16 label[n_edges], int32 n[n_edges]), then nothing or one
+        float64 per side column (COLUMNS; NaN = none, a column that was off included) -> VisitEntry."""
         a = np.frombuffer(row, dtype=np.uint8)
         ne = int(a[6])
-        q = sp = mq = None
-        if len(a) >= 24 + 6 * ne:
-            q = float(a[16 + 6 * ne:24 + 6 * ne].view(np.float64)[0])
-            q = None if q != q else q
-        if len(a) >= 32 + 6 * ne:
-            sp = float(a[24 + 6 * ne:32 + 6 * ne].view(np.float64)[0])
-            sp = None if sp != sp else sp
-        if len(a) == 40 + 6 * ne:
-            mq = float(a[32 + 6 * ne:].view(np.float64)[0])
-            mq = None if mq != mq else mq
+        if len(a) not in (16 + 6 * ne, 16 + 6 * ne + 8 * len(COLUMNS)):
+            raise ValueError("a visit entry of %d edges has %d or %d bytes, not %d"
+                             % (ne, 16 + 6 * ne, 16 + 6 * ne + 8 * len(COLUMNS), len(a)))
+        side = {name: None if x != x else x
+                for (name, _), x in zip(COLUMNS, a[16 + 6 * ne:].view(np.float64).tolist())}
         lab = a[16:16 + 2 * ne].view(np.uint16)
         return VisitEntry(moves=(lab & 0x7FFF).astype(np.uint16), n=a[16 + 2 * ne:16 + 6 * ne].view(np.int32).copy(),
                           banned=(lab & VISIT_BANNED) != 0, sum_n=int(a[8:12].view(np.int32)[0]),
                           ply=int(a[4:6].view(np.uint16)[0]), resign=bool(a[7] & 1), fast=bool(a[7] & VISIT_FAST),
-                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]), q=q, s=sp,
-                          gumbel=bool(a[7] & VISIT_GUMBEL), early=bool(a[7] & VISIT_EARLY), maxq=mq,
-                          no_resign=bool(a[7] & VISIT_NO_RESIGN))
+                          pruned=bool(a[7] & VISIT_PRUNED), raw_total=int(a[12:16].view(np.uint32)[0]),
+                          gumbel=bool(a[7] & VISIT_GUMBEL), early=bool(a[7] & VISIT_EARLY),
+                          no_resign=bool(a[7] & VISIT_NO_RESIGN), **side)
 
     def leaf_masks(self, on=True):
         """Every new leaf's position is also written as an occupancy board (self.masks [slots, 96] int32: word = plane

@@ -206,6 +206,17 @@ int init_pool(cz_search* s)
     return e == hipSuccess ? CZ_OK : serr_hip("cz_search_create: pool initialisation", e);
 }
 
+// The side columns of a visit entry (czero.h), in CZ_VISIT_COL_* order: the column's ring, its name in error texts, and
+// whether it excludes a script (cz_search_set_script).  VisitRing keeps its named fields: it is a kernel argument.
+struct VisitCol {
+    double* VisitRing::* ring;
+    const char* name;
+    bool no_script;
+};
+const VisitCol VISIT_COLS[CZ_VISIT_COLS] = {
+    {&VisitRing::q, "value", false}, {&VisitRing::s, "surprise", false}, {&VisitRing::mq, "max-q", true}};
+static_assert(CZ_VISIT_COL_Q == 0 && CZ_VISIT_COL_S == 1 && CZ_VISIT_COL_MAXQ == 2, "czero.h: the order of VISIT_COLS");
+
 }  // namespace
 
 extern "C" {
@@ -306,9 +317,7 @@ int cz_search_destroy(cz_search* s)
 {
     if (!s) return CZ_OK;
     (void)hipFree(s->vis_mem);
-    (void)hipFree(s->V.q);
-    (void)hipFree(s->V.s);
-    (void)hipFree(s->V.mq);
+    for (const VisitCol& c : VISIT_COLS) (void)hipFree(s->V.*c.ring);
     (void)hipFree(s->book_mem);
     (void)hipFree(s->C.tab);
     (void)hipFree(s->ec_mem);
@@ -699,9 +708,19 @@ int cz_search_eval_cache_info(cz_search* s, uint64_t* out, void* stream)
 static_assert(sizeof(cz_visit_entry) == sizeof(VisitEntryHdr) && VISIT_STRIDE == 784, "czero.h: visit entry layout");
 static_assert(VISIT_MAX_EDGES == MAXMOVES, "a root has at most MAXMOVES edges");
 
-// Switch a side ring of the visit ring (one double per slot: V.q, V.s, V.mq) on or off; `what` names the caller in errors
-static int side_ring(cz_search* s, double*& ring, int on, hipStream_t st, const char* what)
+// Switch side column `col` of the visit ring (VISIT_COLS: one double per slot) on or off; `what` names the entry point in errors
+static int record_col(cz_search* s, int col, int on, void* stream, const char* what)
 {
+    char where[96];
+    const auto refuse = [&](const char* why) {
+        snprintf(where, sizeof(where), "%s: %s", what, why);
+        return serr(CZ_ERR_ARG, where);
+    };
+    if (!s) return refuse("null handle");
+    if (on && !s->V.ring) return refuse("needs cz_search_record_visits on");
+    if (on && VISIT_COLS[col].no_script && s->X.n > 0) return refuse("a script is set (cz_search_set_script)");
+    double*& ring = s->V.*VISIT_COLS[col].ring;
+    hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipStreamSynchronize(st);             // no launch in flight may still use the old buffer
     if (e != hipSuccess) return serr_hip(what, e);
     if (on && ring) return CZ_OK;                        // already on: the ring and what waits in it stay
@@ -711,7 +730,6 @@ static int side_ring(cz_search* s, double*& ring, int on, hipStream_t st, const 
     void* mem = nullptr;
     const size_t bytes = (size_t)s->V.cap * sizeof(double);
     e = hipMalloc(&mem, bytes);
-    char where[64];
     snprintf(where, sizeof(where), "%s: hipMalloc", what);
     if (e != hipSuccess) return serr_hip(where, e);
     // entries already waiting in the visit ring were written without this record: NaN, "none"
@@ -728,12 +746,10 @@ int cz_search_record_visits(cz_search* s, int on, int capacity, void* stream)
     if (capacity < 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: capacity < 0");
     if (!on && s->X.n > 0) return serr(CZ_ERR_ARG, "cz_search_record_visits: a script is set (cz_search_set_script)");
     hipStream_t st = (hipStream_t)stream;
-    // the value, the surprise and the max-q ring share the visit ring's slots: they go with it.  side_ring waits for the
-    // stream: no launch in flight may still use the old buffers
-    if (side_ring(s, s->V.q, 0, st, "cz_search_record_visits") != CZ_OK
-        || side_ring(s, s->V.s, 0, st, "cz_search_record_visits") != CZ_OK
-        || side_ring(s, s->V.mq, 0, st, "cz_search_record_visits") != CZ_OK)
-        return CZ_ERR_HIP;
+    // the side columns share the visit ring's slots: they go with it.  record_col waits for the stream: no launch in
+    // flight may still use the old buffers
+    for (int k = 0; k < CZ_VISIT_COLS; ++k)
+        if (const int rc = record_col(s, k, 0, stream, "cz_search_record_visits")) return rc;
     hipError_t e = hipSuccess;
     (void)hipFree(s->vis_mem);
     s->vis_mem = nullptr;
@@ -806,7 +822,12 @@ int cz_search_set_script(cz_search* s, const int8_t* init_boards, const uint16_t
         // a script defines the start position, the move and the end of every game: not beside what defines one of them too
         if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_set_script: needs cz_search_record_visits on");
         if (s->P.book_n > 0) return serr(CZ_ERR_ARG, "cz_search_set_script: a book is set (cz_search_set_book)");
-        if (s->V.mq) return serr(CZ_ERR_ARG, "cz_search_set_script: the max-q record is on (cz_search_record_maxq)");
+        for (const VisitCol& c : VISIT_COLS)
+            if (c.no_script && s->V.*c.ring) {
+                char buf[96];
+                snprintf(buf, sizeof(buf), "cz_search_set_script: the %s record is on", c.name);
+                return serr(CZ_ERR_ARG, buf);
+            }
         if (offsets[0] != 0) return serr(CZ_ERR_ARG, "cz_search_set_script: offsets[0] != 0");
         for (int i = 0; i < n; ++i) {
             if (offsets[i + 1] < offsets[i]) return serr(CZ_ERR_ARG, "cz_search_set_script: offsets decrease");
@@ -1161,9 +1182,7 @@ int cz_policy_target_prune(const uint16_t* labels, const int32_t* n, const doubl
 
 int cz_search_record_values(cz_search* s, int on, void* stream)
 {
-    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_values: null handle");
-    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_values: needs cz_search_record_visits on");
-    return side_ring(s, s->V.q, on, (hipStream_t)stream, "cz_search_record_values");
+    return record_col(s, CZ_VISIT_COL_Q, on, stream, "cz_search_record_values");
 }
 
 int cz_search_root_value(cz_search* s, double* q, void* stream)
@@ -1191,9 +1210,7 @@ static_assert(CZ_SURPRISE_BOUND == 70 && SURPRISE_R_FLOOR == 1e-30, "czero.h: ln
 
 int cz_search_record_surprise(cz_search* s, int on, void* stream)
 {
-    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_surprise: null handle");
-    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_surprise: needs cz_search_record_visits on");
-    return side_ring(s, s->V.s, on, (hipStream_t)stream, "cz_search_record_surprise");
+    return record_col(s, CZ_VISIT_COL_S, on, stream, "cz_search_record_surprise");
 }
 
 int cz_search_root_surprise(cz_search* s, double* out, void* stream)
@@ -1222,10 +1239,7 @@ static_assert(CZ_VISIT_NO_RESIGN == VISIT_NO_RESIGN, "czero.h: max-q record flag
 
 int cz_search_record_maxq(cz_search* s, int on, void* stream)
 {
-    if (!s) return serr(CZ_ERR_ARG, "cz_search_record_maxq: null handle");
-    if (on && !s->V.ring) return serr(CZ_ERR_ARG, "cz_search_record_maxq: needs cz_search_record_visits on");
-    if (on && s->X.n > 0) return serr(CZ_ERR_ARG, "cz_search_record_maxq: a script is set (cz_search_set_script)");
-    return side_ring(s, s->V.mq, on, (hipStream_t)stream, "cz_search_record_maxq");
+    return record_col(s, CZ_VISIT_COL_MAXQ, on, stream, "cz_search_record_maxq");
 }
 
 int cz_search_root_maxq(cz_search* s, double* out, void* stream)
@@ -1261,20 +1275,24 @@ int cz_search_set_resign_threshold(cz_search* s, double t, void* stream)
     return CZ_OK;
 }
 
-// cz_search_drain_visits, _q, _qs and _qsm: q_buf / s_buf / m_buf NULL = that ring is not copied
-static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
-                        uint64_t* dropped_out, void* stream, double* m_buf = nullptr)
+int cz_search_drain_visits_cols(cz_search* s, void* host_buf, double* const cols[CZ_VISIT_COLS], int max_entries, int* n_out,
+                                uint64_t* dropped_out, void* stream)
 {
-    if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits: bad argument");
-    if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits: visit recording is off");
-    if (q_buf && !s->V.q) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: value recording is off");
-    if (s_buf && !s->V.s) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qs: surprise recording is off");
+    if (!s || !n_out || max_entries < 0) return serr(CZ_ERR_ARG, "cz_search_drain_visits_cols: bad argument");
+    if (!s->V.ring) return serr(CZ_ERR_ARG, "cz_search_drain_visits_cols: visit recording is off");
+    if (!host_buf) cols = nullptr;                       // a count copies nothing
+    for (int c = 0; cols && c < CZ_VISIT_COLS; ++c)
+        if (cols[c] && !(s->V.*VISIT_COLS[c].ring)) {
+            char buf[96];
+            snprintf(buf, sizeof(buf), "cz_search_drain_visits_cols: the %s record is off", VISIT_COLS[c].name);
+            return serr(CZ_ERR_ARG, buf);
+        }
     hipStream_t st = (hipStream_t)stream;
     unsigned int ctl[6] = {0u, 0u, 0u, 0u, 0u, 0u};        // tail, head, -, -, dropped (64 bit): one copy
     static_assert(sizeof(unsigned long long) == 8, "dropped counter is 64-bit");
     hipError_t e = hipMemcpyAsync(ctl, s->V.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return serr_hip("cz_search_drain_visits", e);
+    if (e != hipSuccess) return serr_hip("cz_search_drain_visits_cols", e);
     unsigned long long dropped = 0ull;
     memcpy(&dropped, &ctl[4], sizeof(dropped));
     const unsigned int tail = ctl[0], head = ctl[1], cap = s->V.cap;
@@ -1284,7 +1302,7 @@ static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_b
     if (!host_buf) { *n_out = (int)valid; return CZ_OK; }
     // all or nothing: a partial drain would have to remember where the dropped reservations lie
     if (valid > (unsigned int)max_entries)
-        return serr(CZ_ERR_ARG, "cz_search_drain_visits: host_buf holds fewer entries than are waiting (ask with host_buf = NULL)");
+        return serr(CZ_ERR_ARG, "cz_search_drain_visits_cols: host_buf holds fewer entries than are waiting (ask with host_buf = NULL)");
     const unsigned int k = valid;
     unsigned int done = 0;
     while (done < k && e == hipSuccess) {                // at most two runs: the ring may wrap once
@@ -1292,48 +1310,23 @@ static int drain_visits(cz_search* s, void* host_buf, double* q_buf, double* s_b
         const unsigned int run = (cap - at) < (k - done) ? (cap - at) : (k - done);
         e = hipMemcpyAsync((char*)host_buf + (size_t)done * VISIT_STRIDE, s->V.ring + (size_t)at * VISIT_STRIDE,
                            (size_t)run * VISIT_STRIDE, hipMemcpyDeviceToHost, st);
-        if (q_buf && e == hipSuccess)
-            e = hipMemcpyAsync(q_buf + done, s->V.q + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (s_buf && e == hipSuccess)
-            e = hipMemcpyAsync(s_buf + done, s->V.s + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (m_buf && e == hipSuccess)
-            e = hipMemcpyAsync(m_buf + done, s->V.mq + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
+        for (int c = 0; cols && c < CZ_VISIT_COLS; ++c)
+            if (cols[c] && e == hipSuccess)
+                e = hipMemcpyAsync(cols[c] + done, s->V.*VISIT_COLS[c].ring + at, (size_t)run * sizeof(double),
+                                   hipMemcpyDeviceToHost, st);
         done += run;
     }
     const unsigned int new_head = tail;
     if (e == hipSuccess) e = hipMemcpyAsync(s->V.ctl + 1, &new_head, sizeof(new_head), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return serr_hip("cz_search_drain_visits", e);
+    if (e != hipSuccess) return serr_hip("cz_search_drain_visits_cols", e);
     *n_out = (int)k;
     return CZ_OK;
 }
 
 int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out, void* stream)
 {
-    return drain_visits(s, host_buf, nullptr, nullptr, max_entries, n_out, dropped_out, stream);
-}
-
-int cz_search_drain_visits_q(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out,
-                             uint64_t* dropped_out, void* stream)
-{
-    if (host_buf && !q_buf) return serr(CZ_ERR_ARG, "cz_search_drain_visits_q: null q_buf");
-    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, nullptr, max_entries, n_out, dropped_out, stream);
-}
-
-int cz_search_drain_visits_qs(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
-                              uint64_t* dropped_out, void* stream)
-{
-    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, host_buf ? s_buf : nullptr, max_entries, n_out,
-                        dropped_out, stream);
-}
-
-int cz_search_drain_visits_qsm(cz_search* s, void* host_buf, double* q_buf, double* s_buf, double* m_buf, int max_entries,
-                               int* n_out, uint64_t* dropped_out, void* stream)
-{
-    if (s && !s->V.mq) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qsm: max-q recording is off");
-    if (host_buf && !m_buf) return serr(CZ_ERR_ARG, "cz_search_drain_visits_qsm: null m_buf");
-    return drain_visits(s, host_buf, host_buf ? q_buf : nullptr, host_buf ? s_buf : nullptr, max_entries, n_out,
-                        dropped_out, stream, host_buf ? m_buf : nullptr);
+    return cz_search_drain_visits_cols(s, host_buf, nullptr, max_entries, n_out, dropped_out, stream);
 }
 
 int cz_search_reset_trees(cz_search* s, void* stream)

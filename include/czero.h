@@ -497,10 +497,39 @@ typedef struct cz_visit_entry {
 #define CZ_VISIT_PRUNED 4u
 /* Copies every entry written since the last call into HOST host_buf (784 bytes each) and frees their ring space;
  * *n_out = entries copied.  host_buf = NULL: *n_out = entries waiting, nothing is consumed.  CZ_ERR_ARG when more are
- * waiting than max_entries (nothing is consumed).  dropped_out (HOST, or NULL) = entries dropped since recording was
- * switched on.  Synchronises the stream. */
+ * waiting than max_entries, when max_entries < 0 or n_out is NULL (nothing is consumed).  dropped_out (HOST, or NULL) =
+ * entries dropped since recording was switched on.  Synchronises the stream.  This is cz_search_drain_visits_cols with
+ * cols = NULL (its error texts carry that name): the side columns of what it consumes are dropped. */
 int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n_out, uint64_t* dropped_out,
                            void* stream);
+/* ---- side columns of a visit entry (all off by default) ----
+ * The 784-byte cz_visit_entry has no free word, so a number recorded beside every entry lives in a ring of its own, one
+ * double per slot: column k of the entry in slot i is col_k[i], i the slot of the visit entry.  The kernel writes the
+ * entry and its columns in one reservation, for every ply that gets an entry (fast plies of the playout cap included);
+ * a dropped entry drops its columns.  The columns, each switched by its own cz_search_record_* below, where its
+ * arithmetic is stated:
+ *       CZ_VISIT_COL_Q     the root's search value        cz_search_record_values
+ *       CZ_VISIT_COL_S     the policy surprise            cz_search_record_surprise
+ *       CZ_VISIT_COL_MAXQ  the resignation test's max q   cz_search_record_maxq
+ * What holds for each of them: it needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting),
+ * and every call of cz_search_record_visits frees all columns with the visit ring, so switch them on after it.  Switch
+ * them on before cz_search_start_selfplay and before a graph capture, like the other setters; the call synchronises the
+ * stream.  Entries already waiting when a column is switched on report NaN in it.  Switching on what is on keeps the ring
+ * and what waits in it; on = 0 frees the buffer, and switching off what is off is no error.  Device memory: capacity * 8
+ * bytes per column.  No counter is added; the move, the tree, the visit entries (but for CZ_VISIT_NO_RESIGN, see the
+ * max-q record) and the other columns do not change.
+ * THE NEXT COLUMN is one row of VISIT_COLS in csrc/xq_search.hip, one #define here, one field of VisitRing with its block
+ * in emit_visits, and one name in COLUMNS of cchess_alphazero/_native_search.py: no drain, switch or parser is copied. */
+#define CZ_VISIT_COL_Q 0
+#define CZ_VISIT_COL_S 1
+#define CZ_VISIT_COL_MAXQ 2
+#define CZ_VISIT_COLS 3
+/* cz_search_drain_visits that also copies column k of the entries into HOST cols[k][max_entries], cols[k][i] beside
+ * entry i.  cols = NULL or cols[k] = NULL: column k is not copied, its values go with the entries consumed.  cols[k] given
+ * while record k is off: CZ_ERR_ARG, nothing is consumed.  host_buf = NULL counts, cols is ignored.  Everything else is
+ * cz_search_drain_visits: all or nothing, one read of the control words, at most two copies per ring across the wrap. */
+int cz_search_drain_visits_cols(cz_search* s, void* host_buf, double* const cols[CZ_VISIT_COLS], int max_entries,
+                                int* n_out, uint64_t* dropped_out, void* stream);
 /* ---- root value record of self-play (off by default; the reference has no such option) ----
  * The search's own estimate of the root position, recorded beside each visit entry so that a trainer can mix it with
  * the game result (Lc0's q_ratio).  on = 0 (the state after cz_search_create): no kernel, record, counter or entry
@@ -518,19 +547,8 @@ int cz_search_drain_visits(cz_search* s, void* host_buf, int max_entries, int* n
  * from -- gives NaN: "no value".  Every backed-up value lies in [-2, 2] (a network value in [-1, 1], a terminal one
  * +-2, player.py:204-208) and a finished search has no virtual loss outstanding, so |w_j| <= 2 n_j and |q_root| <= 2.
  *
- * THE RING.  The 784-byte cz_visit_entry has no free word, so the values live in a ring of their own, double q[capacity],
- * indexed by the slot of the visit entry: the kernel writes both in one reservation, a dropped entry drops its value.
- * Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting); every call of
- * cz_search_record_visits frees the value ring as well, so switch the values on after it.  Call it before
- * cz_search_start_selfplay and before a graph capture, like the other setters; synchronises the stream.  Entries
- * already waiting when it is switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.
- * No counter is added; the move, the tree and the visit entries do not change. */
+ * The ring, the switch and the drain: "side columns of a visit entry" above, column CZ_VISIT_COL_Q. */
 int cz_search_record_values(cz_search* s, int on, void* stream);
-/* cz_search_drain_visits that also copies the entries' values into HOST q_buf[max_entries], q_buf[i] beside entry i.
- * host_buf = NULL counts (q_buf unused).  CZ_ERR_ARG also when host_buf is given and q_buf is NULL or the value record
- * is off.  cz_search_drain_visits itself keeps working with the values on; it drops the values of what it consumes. */
-int cz_search_drain_visits_q(cz_search* s, void* host_buf, double* q_buf, int max_entries, int* n_out,
-                             uint64_t* dropped_out, void* stream);
 /* The value an entry of each current root would carry: q [G] float64 DEVICE.  Same inputs as cz_search_root_targets:
  * the bans of the current cz_search_set_roots, m = the counts cz_search_root_targets reports for the object's c_puct
  * and k (k = 0: the raw counts).  A root that is not in the tree reports NaN.  Works with the record off. */
@@ -559,21 +577,9 @@ int cz_root_value(const uint16_t* labels, const int32_t* m, const int32_t* n, co
  * t_j <= 1 and r_j >= 1e-30 bound every logarithm by ln 1e30, and sum t_j = 1, so 0 <= surprise <= ln 1e30 = 69.08 <
  * CZ_SURPRISE_BOUND.  log is the device library's float64 logarithm (DESIGN.md names the routine and its accuracy).
  *
- * THE RING.  Like the value record: double s[capacity], indexed by the slot of the visit entry, written by the kernel
- * in the entry's reservation for every ply that gets an entry (fast plies of the playout cap included); a dropped
- * entry drops its surprise.  Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting);
- * every call of cz_search_record_visits frees this ring as well, so switch it on after that.  Call it before
- * cz_search_start_selfplay and before a graph capture; synchronises the stream.  Entries already waiting when it is
- * switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.  No counter is added; the move,
- * the tree, the visit entries and the value ring do not change. */
+ * The ring, the switch and the drain: "side columns of a visit entry" above, column CZ_VISIT_COL_S. */
 #define CZ_SURPRISE_BOUND 70
 int cz_search_record_surprise(cz_search* s, int on, void* stream);
-/* cz_search_drain_visits that also copies the entries' values into HOST q_buf[max_entries] and their surprises into
- * HOST s_buf[max_entries], beside entry i.  q_buf / s_buf = NULL: that ring is not copied (it has to be NULL when its
- * record is off: CZ_ERR_ARG otherwise).  host_buf = NULL counts.  cz_search_drain_visits and cz_search_drain_visits_q
- * keep working with the surprise record on; they drop the surprises of what they consume. */
-int cz_search_drain_visits_qs(cz_search* s, void* host_buf, double* q_buf, double* s_buf, int max_entries, int* n_out,
-                              uint64_t* dropped_out, void* stream);
 /* The surprise an entry of each current root would carry: out [G] float64 DEVICE.  Same conventions as
  * cz_search_root_value: the bans of the current cz_search_set_roots, m = the counts cz_search_root_targets reports for
  * the object's c_puct and k (k = 0: the raw counts).  A root that is not in the tree reports NaN.  Works with the record
@@ -597,22 +603,11 @@ int cz_root_surprise(const uint16_t* labels, const int32_t* m, const float* p, c
  * enabled for the game and turns > min_resign_turn.  A root without a non-banned edge gives -100; a root that was never
  * selected from gives 0.0.  A maximum is exact, so the order of the lanes does not matter.
  *
- * THE RING.  Like the value record: double mq[capacity], indexed by the slot of the visit entry, written by the kernel
- * in the entry's reservation for every ply that gets an entry; a dropped entry drops its number.  While the record is
- * on, an entry of a game that plays on without resignation carries CZ_VISIT_NO_RESIGN (bit 5); with it off no entry
- * does.  Needs cz_search_record_visits on (CZ_ERR_ARG otherwise, the object keeps its setting); every call of
- * cz_search_record_visits frees this ring as well, so switch it on after that.  Call it before
- * cz_search_start_selfplay and before a graph capture; synchronises the stream.  Entries already waiting when it is
- * switched on report NaN.  on = 0 frees the buffer.  Device memory: capacity * 8 bytes.  No counter is added; the move,
- * the tree, the other words of the visit entries, the value and the surprise ring do not change. */
+ * The ring, the switch and the drain: "side columns of a visit entry" above, column CZ_VISIT_COL_MAXQ.  While the record
+ * is on, an entry of a game that plays on without resignation carries CZ_VISIT_NO_RESIGN (bit 5); with it off no entry
+ * does.  Not beside a script (cz_search_set_script): CZ_ERR_ARG from whichever is switched on second. */
 #define CZ_VISIT_NO_RESIGN 32u
 int cz_search_record_maxq(cz_search* s, int on, void* stream);
-/* cz_search_drain_visits_qs that also copies the entries' max q into HOST m_buf[max_entries], beside entry i.  q_buf /
- * s_buf = NULL: that ring is not copied (it has to be NULL when its record is off).  m_buf is required with host_buf, and
- * the max-q record has to be on: CZ_ERR_ARG otherwise.  host_buf = NULL counts.  The older drains keep working with the
- * max-q record on; they drop the numbers of what they consume. */
-int cz_search_drain_visits_qsm(cz_search* s, void* host_buf, double* q_buf, double* s_buf, double* m_buf, int max_entries,
-                               int* n_out, uint64_t* dropped_out, void* stream);
 /* The max q an entry of each current root would carry: out [G] float64 DEVICE, with the bans of the current
  * cz_search_set_roots.  A root that is not in the tree reports NaN, a root that was never selected from 0.0.  Works with
  * the record off. */

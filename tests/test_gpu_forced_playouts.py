@@ -40,7 +40,7 @@ def _entry_key(e):
 def _selfplay_raw(gpu, pc, seed, rounds, setup):
     """selfplay_raw with the setup BEFORE the visit ring is switched on; the entries as their rows alone."""
     recs, entries, ctr = selfplay_raw(gpu, pc, seed, rounds, G, setup_before=setup)
-    return recs, [row for row, _, _ in entries], ctr
+    return recs, [e[0] for e in entries], ctr
 
 
 @pytest.mark.parametrize("K", [1, 8])

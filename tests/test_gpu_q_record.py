@@ -1,4 +1,4 @@
-"""-m gpu: the root value record and the z/q value mix (cz_search_record_values, cz_search_drain_visits_q,
+"""-m gpu: the root value record and the z/q value mix (cz_search_record_values, cz_search_drain_visits_cols,
 cz_search_root_value, cz_root_value, cz_policy_value_loss_q; run.py self --record-q, run.py opt --q-ratio L).
 
 The yardstick of the arithmetic is tests/q_record_oracle.py (math.fsum).  Its bound, 1e-13: a root has at most 128 float64
@@ -21,7 +21,7 @@ import pytest
 import forced_playouts_oracle as fo
 import q_record_oracle as qo
 from oracle import xq_oracle as xo
-from selfplay_raw import selfplay_raw
+from selfplay_raw import COLS, drain_cols, selfplay_raw
 from test_gpu_book import _engine_cfg
 from test_gpu_forced_playouts import _book, _entry_key
 from test_gpu_search import boards_tensor, gpu, no_act_tensors, play_config, stub_eval  # noqa: F401  (gpu: fixture)
@@ -306,9 +306,9 @@ def test_selfplay_games_carry_values(gpu, K, fast_sims):
 # ---- 5. off means off ------------------------------------------------------------------------------------------------------
 def _selfplay_raw(gpu, pc, seed, rounds, setup, with_q=False):
     """selfplay_raw with the setup AFTER the visit ring is on (the value record needs it); the entries as their rows, with
-    with_q as (row, the value cz_search_drain_visits_q hands out beside it)."""
-    recs, entries, ctr = selfplay_raw(gpu, pc, seed, rounds, 32, setup_after=setup, drain="q" if with_q else "plain")
-    return recs, [(row, q) if with_q else row for row, q, _ in entries], ctr
+    with_q as (row, the value cz_search_drain_visits_cols hands out beside it)."""
+    recs, entries, ctr = selfplay_raw(gpu, pc, seed, rounds, 32, setup_after=setup, columns=("q",) if with_q else ())
+    return recs, [(row, q) if with_q else row for row, q, _, _ in entries], ctr
 
 
 @pytest.mark.parametrize("K", [1, 8])
@@ -331,6 +331,42 @@ def test_values_off_leaves_every_record_entry_and_counter(gpu, K):
     qs = np.array([np.frombuffer(q, dtype=np.float64)[0] for _, q in vis4])
     assert np.isfinite(qs).sum() > len(qs) // 2 and (np.abs(qs[np.isfinite(qs)]) <= 2.0).all()
     assert len({q for _, q in vis4}) > 8                    # (values of their entries, not a constant)
+
+
+# ---- 5b. any subset of the side columns, through the one drain -----------------------------------------------------------------
+# The run below hands selfplay_raw's drains (every 16 rounds) 6, 10 and 8 entries: a ring of 10 slots loses nothing (one of 9
+# drops an entry), and its second and third drain each cross the wrap.
+WRAP_CAPACITY = 10
+
+
+def test_every_subset_of_columns_drains_what_the_full_run_drains(gpu):
+    """Each of the 8 subsets of {values, surprise, max q} switched on and drained with exactly those columns: a column is the
+    same bytes as in the run with all three, a buffer that is not asked for is untouched, and the entries differ only by the
+    max-q record's flag.  Then all three across the ring's wrap."""
+    pc = play_config(simulation_num_per_move=16, search_threads=4, max_game_length=6)
+    switch = dict(q="record_values", s="record_surprise", maxq="record_maxq")
+    fill = np.array([-7.0]).tobytes()
+
+    def run(cols, capacity=0):
+        _, ents, ctr = selfplay_raw(gpu, pc, 31, 48, 2, setup_after=lambda s: [getattr(s, switch[c])(True) for c in cols],
+                                    capacity=capacity, columns=cols, fill=-7.0)
+        assert ctr["visits_dropped"] == 0
+        return ents
+    runs = {mask: run(tuple(c for k, c in enumerate(COLS) if mask >> k & 1)) for mask in range(8)}
+    full, none = runs[7], runs[0]
+    assert len(full) >= 16
+    for k in range(3):
+        assert len({e[1 + k] for e in full}) > 4 and all(e[1 + k] != fill for e in full)       # (numbers, not a constant)
+    assert any(e[0][7] & gpu.S.VISIT_NO_RESIGN for e in full) and not any(e[0][7] & gpu.S.VISIT_NO_RESIGN for e in none)
+    for mask, ents in runs.items():
+        # the entries' first six bytes (game, ply) are their sort key in every run: entry i is the same ply everywhere
+        assert [e[0] for e in ents] == [e[0] for e in (full if mask & 4 else none)], mask
+        for k in range(3):
+            assert [e[1 + k] for e in ents] == ([e[1 + k] for e in full] if mask >> k & 1 else [fill] * len(full)), (mask, k)
+    # the smallest ring that loses nothing here: the columns of both copy runs of a drain land beside their entries
+    wrapped = run(COLS, capacity=WRAP_CAPACITY)
+    assert len(wrapped) > WRAP_CAPACITY
+    assert wrapped == full
 
 
 # ---- 6. the loss kernel -----------------------------------------------------------------------------------------------------
@@ -491,10 +527,11 @@ def test_record_values_argument_errors_leave_the_setting(gpu):
     n = C.c_int(-1)
     buf = np.zeros((64, gpu.S.VISIT_STRIDE), dtype=np.uint8)
     qb = np.zeros(64, dtype=np.float64)
-    assert L.cz_search_drain_visits_q(s.h, None, None, 0, C.byref(n), None, st) == 0 and n.value == 0
-    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, None, 64, C.byref(n), None, st) == ERR_ARG       # no q_buf
-    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, -1, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, 64, None, None, st) == ERR_ARG
+    assert drain_cols(s, None, (None, None, None), 0, C.byref(n)) == 0 and n.value == 0
+    # a NULL column for a record that is on: not copied, no error, and the record stays on
+    assert drain_cols(s, buf, (None, None, None), 64, C.byref(n)) == 0 and n.value == 0 and s.values_on
+    assert drain_cols(s, buf, (qb, None, None), -1, C.byref(n)) == ERR_ARG
+    assert drain_cols(s, buf, (qb, None, None), 64, None) == ERR_ARG
     assert L.cz_search_root_value(s.h, None, st) == ERR_ARG
     assert L.cz_search_root_value(None, C.c_void_p(gpu.torch.empty(2, dtype=gpu.torch.float64, device="cuda").data_ptr()),
                                   st) == ERR_ARG
@@ -512,7 +549,7 @@ def test_record_values_argument_errors_leave_the_setting(gpu):
     s.record_visits(False)
     assert not s.values_on
     assert L.cz_search_record_values(s.h, 1, st) == ERR_ARG
-    assert L.cz_search_drain_visits_q(s.h, buf.ctypes.data, qb.ctypes.data, 64, C.byref(n), None, st) == ERR_ARG
+    assert drain_cols(s, buf, (qb, None, None), 64, C.byref(n)) == ERR_ARG
     s.close()
     s = gpu.S.Search(pc, 2, seed=1)
     assert np.isnan(s.root_value()).all()

@@ -1,4 +1,4 @@
-"""-m gpu: the max-q record and the resignation audit (cz_search_record_maxq, cz_search_drain_visits_qsm,
+"""-m gpu: the max-q record and the resignation audit (cz_search_record_maxq, cz_search_drain_visits_cols,
 cz_search_root_maxq, cz_root_maxq, cz_search_set_resign_threshold; run.py self --resign-audit, --resign-fp-target).
 
 The yardsticks are tests/resign_audit_oracle.py: the C oracle's games with the max q of every searched ply (float64, a
@@ -14,7 +14,7 @@ import resign_audit_oracle as ro
 import search_model as sm
 import selfplay_oracle as so
 from oracle import xq_oracle as xo
-from selfplay_raw import selfplay_raw
+from selfplay_raw import drain_cols, selfplay_raw
 from test_gpu_book import _engine_cfg
 from test_gpu_search import boards_tensor, gpu, no_act_tensors, play_config, stub_eval  # noqa: F401  (gpu: fixture)
 
@@ -195,7 +195,7 @@ def test_resign_enabled_games_lack_the_flag_and_resign_below_the_threshold(gpu):
 # ---- record on versus off ----------------------------------------------------------------------------------------------------
 def _without_bit_5(entries):
     out = []
-    for row, _, _ in entries:
+    for row, *_ in entries:
         b = bytearray(row)
         b[7] &= 0xFF ^ 32
         out.append(bytes(b))
@@ -213,13 +213,13 @@ def test_record_on_changes_bit_5_and_nothing_else(gpu, K):
     assert len(base) >= 32 and len(vis0) > len(base)
     assert off == base and vis1 == vis0 and c1 == c0            # off: every byte what it was
     assert on == base and c2 == c0                              # on: records and counters byte for byte
-    assert all(not row[7] & 32 for row, _, _ in vis0)
-    flagged = sum(bool(row[7] & 32) for row, _, _ in vis2)
+    assert all(not row[7] & 32 for row, *_ in vis0)
+    flagged = sum(bool(row[7] & 32) for row, *_ in vis2)
     assert 0 < flagged < len(vis2)                              # both kinds of game occur
-    assert _without_bit_5(vis2) == sorted(row for row, _, _ in vis0)
+    assert _without_bit_5(vis2) == sorted(row for row, *_ in vis0)
     # the flag is the game's lottery
     cfg = so.oracle_cfg(pc)
-    for row, _, _ in vis2:
+    for row, *_ in vis2:
         gid = int(np.frombuffer(row[:4], dtype=np.uint32)[0])
         assert bool(row[7] & 32) == (not so.resign_enabled(cfg, 31, gid)), gid
 
@@ -390,14 +390,14 @@ def test_argument_errors_leave_the_settings(gpu):
     buf = np.zeros((64, gpu.S.VISIT_STRIDE), dtype=np.uint8)
     mb = np.zeros(64, dtype=np.float64)
     s.record_visits(True, capacity=64)
-    assert L.cz_search_drain_visits_qsm(s.h, buf.ctypes.data, None, None, mb.ctypes.data, 64, C.byref(n), None, st) == ERR_ARG
+    assert drain_cols(s, buf, (None, None, mb), 64, C.byref(n)) == ERR_ARG     # a buffer for a record that is off
     s.record_maxq(True)
     assert s.maxq_on
-    assert L.cz_search_drain_visits_qsm(s.h, None, None, None, None, 0, C.byref(n), None, st) == 0 and n.value == 0
-    assert L.cz_search_drain_visits_qsm(s.h, buf.ctypes.data, None, None, None, 64, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_qsm(s.h, buf.ctypes.data, mb.ctypes.data, None, mb.ctypes.data, 64, C.byref(n), None,
-                                        st) == ERR_ARG                   # a q_buf with the value record off
-    assert L.cz_search_drain_visits_qsm(s.h, buf.ctypes.data, None, None, mb.ctypes.data, 64, C.byref(n), None, st) == 0
+    assert drain_cols(s, None, (None, None, None), 0, C.byref(n)) == 0 and n.value == 0
+    # a NULL column for a record that is on: not copied, no error, and the record stays on
+    assert drain_cols(s, buf, (None, None, None), 64, C.byref(n)) == 0 and n.value == 0 and s.maxq_on
+    assert drain_cols(s, buf, (mb, None, mb), 64, C.byref(n)) == ERR_ARG       # a q column with the value record off
+    assert drain_cols(s, buf, (None, None, mb), 64, C.byref(n)) == 0
     assert L.cz_search_root_maxq(s.h, None, st) == ERR_ARG
     for bad in (float("nan"), float("inf"), float("-inf")):
         assert L.cz_search_set_resign_threshold(s.h, bad, st) == ERR_ARG
@@ -405,7 +405,7 @@ def test_argument_errors_leave_the_settings(gpu):
             s.set_resign_threshold(bad)
     assert L.cz_search_set_resign_threshold(None, 0.0, st) == ERR_ARG
     assert s.resign_threshold == pc.resign_threshold
-    # the older drains keep working with the record on, and the entries carry the number through the binding
+    # the plain drain keeps working with columns on, and the entries carry the number through the binding
     s.start_selfplay(seed=1)
     ev = stub_eval(gpu, ro.SPEC)
     for _ in range(40):

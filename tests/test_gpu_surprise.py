@@ -1,4 +1,4 @@
-"""-m gpu: the policy surprise record and the surprise weighting (cz_search_record_surprise, cz_search_drain_visits_qs,
+"""-m gpu: the policy surprise record and the surprise weighting (cz_search_record_surprise, cz_search_drain_visits_cols,
 cz_search_root_surprise, cz_root_surprise, cz_policy_value_loss_w; run.py self --record-surprise, run.py opt
 --surprise-weight A).
 
@@ -22,7 +22,7 @@ import forced_playouts_oracle as fo
 import stub_net
 import surprise_oracle as so
 from oracle import xq_oracle as xo
-from selfplay_raw import selfplay_raw
+from selfplay_raw import drain_cols, selfplay_raw
 from test_gpu_book import _engine_cfg
 from test_gpu_forced_playouts import _entry_key
 from test_gpu_q_record import _games_with_q, _play
@@ -292,12 +292,12 @@ def test_selfplay_games_carry_the_oracles_surprise(gpu, k):
     eng.close()
 
 
-# ---- 4. off means off, the older drains, the full ring ---------------------------------------------------------------------
-def _selfplay_raw(gpu, pc, seed, rounds, setup, drain="q", capacity=0, G=16, before=None):
+# ---- 4. off means off, every drain, the full ring --------------------------------------------------------------------------
+def _selfplay_raw(gpu, pc, seed, rounds, setup, columns=("q",), capacity=0, G=16, before=None):
     """selfplay_raw with the playout cap (4, 0.5) and `setup` AFTER the visit ring is on (`before`: ahead of it); entries
-    (row, q bytes, s bytes), -7.0 where the drain writes none; a ring of `capacity` may drop entries."""
+    (row, q bytes, s bytes, maxq bytes), -7.0 where the drain writes none; a ring of `capacity` may drop entries."""
     return selfplay_raw(gpu, pc, seed, rounds, G, setup_before=before, setup_after=setup, capacity=capacity,
-                        playout_cap=(4, 0.5), drain=drain, fill=-7.0, no_drops=False)
+                        playout_cap=(4, 0.5), columns=columns, fill=-7.0, no_drops=False)
 
 
 def _check_raw_surprises(recs, entries):
@@ -307,7 +307,7 @@ def _check_raw_surprises(recs, entries):
         a = np.frombuffer(rec, dtype=np.uint8)
         moves[int(a[0:4].view(np.uint32)[0])] = [xo.label_str(int(l) & 0x7FFF) for l in a[16:].view(np.uint16)]
     checked = with_s = 0
-    for row, _, sb in entries:
+    for row, _, sb, _ in entries:
         a = np.frombuffer(row, dtype=np.uint8)
         gid, ply, ne = int(a[0:4].view(np.uint32)[0]), int(a[4:6].view(np.uint16)[0]), int(a[6])
         if gid not in moves or ply > len(moves[gid]):
@@ -332,7 +332,7 @@ def test_surprise_off_leaves_every_record_entry_value_and_counter(gpu):
     q_on = lambda s: s.record_values(True)  # noqa: E731
     base, vis0, c0 = _selfplay_raw(gpu, pc, 31, rounds, q_on)
     assert len(base) >= 16 and len(vis0) > len(base) and c0["visits_dropped"] == 0
-    rows_q = [(row, q) for row, q, _ in vis0]
+    rows_q = [(row, q) for row, q, _, _ in vis0]
     assert len({q for _, q in rows_q}) > 8
     # switched off, and switched on and off again: nothing differs
     for setup in (lambda s: (q_on(s), s.record_surprise(False)), lambda s: (q_on(s), s.record_surprise(True), s.record_surprise(False))):
@@ -340,21 +340,21 @@ def test_surprise_off_leaves_every_record_entry_value_and_counter(gpu):
         assert recs == base and vis == vis0 and ctr == c0
     # ON: the records, the visit ring, the value ring and the counters still hold the same bytes, through every drain
     both = lambda s: (q_on(s), s.record_surprise(True))  # noqa: E731
-    recs, vis_qs, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, drain="qs")
-    assert recs == base and ctr == c0 and [(row, q) for row, q, _ in vis_qs] == rows_q
+    recs, vis_qs, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, columns=("q", "s"))
+    assert recs == base and ctr == c0 and [(row, q) for row, q, _, _ in vis_qs] == rows_q
     checked, with_s = _check_raw_surprises(recs, vis_qs)
     assert checked > len(vis_qs) // 2 and with_s > checked // 2
-    assert len({sb for _, _, sb in vis_qs}) > 8                     # (surprises of their entries, not a constant)
-    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, drain="q")        # the older entry points drop the surprises
+    assert len({sb for _, _, sb, _ in vis_qs}) > 8                     # (surprises of their entries, not a constant)
+    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, columns=("q",))   # a column that is not asked for is dropped
     assert recs == base and ctr == c0 and vis == vis0
-    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, drain="plain")
-    assert recs == base and ctr == c0 and [row for row, _, _ in vis] == [row for row, _, _ in vis0]
-    # the surprise record alone, q_buf = NULL: the same entries and the same surprises
-    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.record_surprise(True), drain="s")
-    assert recs == base and ctr == c0 and [(row, sb) for row, _, sb in vis] == [(row, sb) for row, _, sb in vis_qs]
+    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, columns=())
+    assert recs == base and ctr == c0 and [e[0] for e in vis] == [e[0] for e in vis0]
+    # the surprise record alone, the q column NULL: the same entries and the same surprises
+    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, lambda s: s.record_surprise(True), columns=("s",))
+    assert recs == base and ctr == c0 and [(row, sb) for row, _, sb, _ in vis] == [(row, sb) for row, _, sb, _ in vis_qs]
     # a ring that fills: an entry that finds it full is dropped with its surprise, the others keep theirs -- the ring
     # wraps many times here, so a surprise in the wrong slot would show
-    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, drain="qs", capacity=24)
+    recs, vis, ctr = _selfplay_raw(gpu, pc, 31, rounds, both, columns=("q", "s"), capacity=24)
     assert recs != [] and ctr["visits_dropped"] > 0 and 24 < len(vis) < len(vis0)
     assert set(vis) <= set(vis_qs)
     checked, with_s = _check_raw_surprises(recs, vis)
@@ -368,24 +368,24 @@ def test_a_record_that_is_off_never_changes_the_others(gpu, k):
     pc = play_config(simulation_num_per_move=16, search_threads=4, tau_decay_rate=0.9, max_game_length=8,
                      enable_resign_rate=0.5, resign_threshold=-0.4, min_resign_turn=4)
 
-    def run(values, surprise, drain):
+    def run(values, surprise, columns):
         def setup(s):
             s.set_forced_playouts(k)
             s.record_values(values)
             s.record_surprise(surprise)
-        recs, vis, ctr = _selfplay_raw(gpu, pc, 31, 240, setup, drain=drain)
+        recs, vis, ctr = _selfplay_raw(gpu, pc, 31, 240, setup, columns=columns)
         assert ctr["visits_dropped"] == 0
         return recs, vis, ctr
-    recs, vis, ctr = run(True, True, "qs")
+    recs, vis, ctr = run(True, True, ("q", "s"))
     assert len(recs) >= 16 and len(vis) > len(recs)
-    assert len({q for _, q, _ in vis}) > 8 and len({sb for _, _, sb in vis}) > 8
-    assert any(row[7] & gpu.S.VISIT_PRUNED for row, _, _ in vis) == (k > 0)
-    recs_q, vis_q, ctr_q = run(True, False, "q")
-    assert recs_q == recs and ctr_q == ctr and [(row, q) for row, q, _ in vis_q] == [(row, q) for row, q, _ in vis]
-    recs_s, vis_s, ctr_s = run(False, True, "s")
-    assert recs_s == recs and ctr_s == ctr and [(row, sb) for row, _, sb in vis_s] == [(row, sb) for row, _, sb in vis]
-    recs_p, vis_p, ctr_p = run(False, False, "plain")
-    assert recs_p == recs and ctr_p == ctr and [row for row, _, _ in vis_p] == [row for row, _, _ in vis]
+    assert len({q for _, q, _, _ in vis}) > 8 and len({sb for _, _, sb, _ in vis}) > 8
+    assert any(row[7] & gpu.S.VISIT_PRUNED for row, _, _, _ in vis) == (k > 0)
+    recs_q, vis_q, ctr_q = run(True, False, ("q",))
+    assert recs_q == recs and ctr_q == ctr and [(row, q) for row, q, _, _ in vis_q] == [(row, q) for row, q, _, _ in vis]
+    recs_s, vis_s, ctr_s = run(False, True, ("s",))
+    assert recs_s == recs and ctr_s == ctr and [(row, sb) for row, _, sb, _ in vis_s] == [(row, sb) for row, _, sb, _ in vis]
+    recs_p, vis_p, ctr_p = run(False, False, ())
+    assert recs_p == recs and ctr_p == ctr and [e[0] for e in vis_p] == [e[0] for e in vis]
 
 
 # ---- 5. the loss kernel -----------------------------------------------------------------------------------------------------
@@ -629,16 +629,19 @@ def test_record_surprise_argument_errors_leave_the_setting(gpu):
     buf = np.zeros((64, gpu.S.VISIT_STRIDE), dtype=np.uint8)
     qb = np.zeros(64, dtype=np.float64)
     sb = np.zeros(64, dtype=np.float64)
-    # a buffer for a record that is off is refused; both NULL is the plain drain
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, None, sb.ctypes.data, 64, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, qb.ctypes.data, None, 64, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, None, None, 64, C.byref(n), None, st) == 0 and n.value == 0
+
+    def drain(host, q, sp, max_entries, n_out):
+        return drain_cols(s, host, (q, sp, None), max_entries, n_out)
+    # a buffer for a record that is off is refused; all NULL is the plain drain
+    assert drain(buf, None, sb, 64, C.byref(n)) == ERR_ARG
+    assert drain(buf, qb, None, 64, C.byref(n)) == ERR_ARG
+    assert drain(buf, None, None, 64, C.byref(n)) == 0 and n.value == 0
     s.record_surprise(True)
     assert s.surprise_on and not s.values_on
-    assert L.cz_search_drain_visits_qs(s.h, None, None, None, 0, C.byref(n), None, st) == 0 and n.value == 0
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, qb.ctypes.data, sb.ctypes.data, 64, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, None, sb.ctypes.data, -1, C.byref(n), None, st) == ERR_ARG
-    assert L.cz_search_drain_visits_qs(s.h, buf.ctypes.data, None, sb.ctypes.data, 64, None, None, st) == ERR_ARG
+    assert drain(None, None, None, 0, C.byref(n)) == 0 and n.value == 0
+    assert drain(buf, qb, sb, 64, C.byref(n)) == ERR_ARG
+    assert drain(buf, None, sb, -1, C.byref(n)) == ERR_ARG
+    assert drain(buf, None, sb, 64, None) == ERR_ARG
     assert L.cz_search_root_surprise(s.h, None, st) == ERR_ARG
     assert L.cz_search_root_surprise(None, C.c_void_p(gpu.torch.empty(2, dtype=gpu.torch.float64, device="cuda").data_ptr()),
                                      st) == ERR_ARG

@@ -81,3 +81,39 @@ def test_counter_names_and_the_entry_flag():
     assert e.early and e.fast and not e.pruned and not e.gumbel and len(e.n) == 2
     row[7] = 0
     assert not S.Search.parse_visit_entry(row.tobytes()).early
+
+
+def test_a_stored_entry_has_no_side_column_or_all_of_them():
+    """parse_visit_entry: the trimmed entry alone, or followed by one float64 per side column (q, s, maxq); nothing between."""
+    from cchess_alphazero import _native_search as S
+    ne = 3
+    head = np.zeros(16, dtype=np.uint8)
+    head[0:4] = np.array([7], dtype=np.uint32).view(np.uint8)            # game_id
+    head[4:6] = np.array([5], dtype=np.uint16).view(np.uint8)            # ply
+    head[6], head[7] = ne, 1 | S.VISIT_PRUNED | S.VISIT_NO_RESIGN
+    head[8:12] = np.array([40], dtype=np.int32).view(np.uint8)           # sum_n
+    head[12:16] = np.array([44], dtype=np.uint32).view(np.uint8)         # raw_total
+    labels = np.array([11, 0x8000 | 12, 13], dtype=np.uint16)
+    counts = np.array([30, 0, 9], dtype=np.int32)
+    bare = head.tobytes() + labels.tobytes() + counts.tobytes()
+    assert len(bare) == 16 + 6 * ne
+
+    def fields(e):
+        return (e.moves.tolist(), e.n.tolist(), e.banned.tolist(), e.sum_n, e.ply, e.resign, e.fast, e.pruned, e.raw_total,
+                e.gumbel, e.early, e.no_resign)
+    want = ([11, 12, 13], [30, 0, 9], [False, True, False], 40, 5, True, False, True, 44, False, False, True)
+    e = S.Search.parse_visit_entry(bare)
+    assert fields(e) == want and (e.q, e.s, e.maxq) == (None, None, None)
+    nan = float("nan")
+    for side, got in (((0.25, 1.5, -0.75), (0.25, 1.5, -0.75)), ((nan, nan, -100.0), (None, None, -100.0)),
+                      ((-2.0, nan, nan), (-2.0, None, None)), ((nan, 0.0, nan), (None, 0.0, None)),
+                      ((nan, nan, nan), (None, None, None))):
+        row = bare + np.array(side, dtype=np.float64).tobytes()
+        assert len(row) == 40 + 6 * ne
+        e = S.Search.parse_visit_entry(row)
+        assert fields(e) == want and (e.q, e.s, e.maxq) == got
+    for extra in (8, 16, 4, 32):                                         # 24 + 6 ne and 32 + 6 ne were rows once
+        with pytest.raises(ValueError):
+            S.Search.parse_visit_entry(bare + bytes(extra))
+    with pytest.raises(ValueError):
+        S.Search.parse_visit_entry(bare[:-1])
