@@ -5,6 +5,7 @@
 // the global loads and stores stay coalesced.  (The search kernel keeps one wavefront per game: there the
 // parallelism is inside a tree.)  Same semantics and move order as static_env.py, built from the same
 // per-piece generator (xq_lane.h::gen_piece) as the wave-cooperative rules.
+// Defined on placement-legal boards with at most 128 moves per side: DESIGN.md §3, "The domain of the rule kernels".
 #pragma once
 #include "xq_lane.h"
 

@@ -134,6 +134,19 @@ int tpb_board(const int8_t* board, int need_check, uint16_t* lab, int* out /* ov
     return r.n;
 }
 
+// the same for n boards with the list capacity the caller names (k_rules_tpb passes its LDS row's): rows of MAXMOVES labels
+// pre-filled with NOMOVE, the full count per board, out = n x (over, v, final_move, check)
+void tpb_boards(const int8_t* boards, int n, int need_check, int cap, uint16_t* lab, int* counts, int* out)
+{
+    for (int i = 0; i < n; ++i) {
+        uint16_t* row = lab + (size_t)i * MAXMOVES;
+        for (int k = 0; k < MAXMOVES; ++k) row[k] = (uint16_t)NOMOVE;
+        const TpbResult r = tpb_rules(boards + (size_t)i * NSQ, row, need_check != 0, cap);
+        counts[i] = r.n;
+        out[4 * i] = r.over; out[4 * i + 1] = r.v; out[4 * i + 2] = r.final_move; out[4 * i + 3] = r.check;
+    }
+}
+
 int lane_nibble_roundtrip(void)
 {
     for (int p = -7; p <= 7; ++p)
