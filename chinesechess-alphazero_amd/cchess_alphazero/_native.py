@@ -70,6 +70,8 @@ def _nn_signatures():
         "cz_heads_tail": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, vp, vp, vp, i32, i32, i32, vp, vp]),
         "cz_heads_tail_wdl": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp,
                                     vp, i32, i32, i32, vp, vp]),
+        "cz_heads_tail_ml": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                   vp, vp]),
         "cz_fc_packed_elems": (sz, [i32, i32]),
         "cz_fc_pack_weights": (i32, [vp, i32, i32, i32, vp]),
     }
@@ -128,6 +130,9 @@ def _declare(L):
         L.cz_policy_wdl_loss.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, C.c_float,
                                          C.c_float, vp, vp, vp, vp, vp, vp]
         L.cz_policy_wdl_loss.restype = i32
+    if hasattr(L, "cz_moves_left_loss"):
+        L.cz_moves_left_loss.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
+        L.cz_moves_left_loss.restype = i32
     if hasattr(L, "cz_search_create"):
         from . import _native_search
         _native_search.declare(L)
@@ -374,6 +379,24 @@ def policy_wdl_loss(logits, vlogits, idx, played, z, row_ptr=None, vis_label=Non
                                    _dev(pl, torch.float32), _dev(ce, torch.float32), _dev(se, torch.float32),
                                    _dev(gl, torch.float32), _dev(gv, torch.float32), _stream()), "cz_policy_wdl_loss")
     return pl, ce, se, gl, gv
+
+
+def moves_left_loss(x, idx, left, unit, delta, row_w=None, w_m=1.0):
+    """The moves-left output's loss (cz_moves_left_loss): x [B] float32, the head's raw output; idx int32 [B]; left int32
+    [n_pos], the positions' targets in plies; unit, delta: agent/model.py MOVES_LEFT_UNIT and MOVES_LEFT_DELTA; row_w
+    float32 [n_pos] or None (= 1).  Returns (loss [B], grad_x [B]): the
+    per-row Huber loss of softplus(x) - left[idx] / unit, unweighted, and the gradient of w_m mean(row_w[idx] loss)."""
+    import torch
+    require_gpu()
+    assert x.dim() == 1 and idx.shape == x.shape, (tuple(x.shape), tuple(idx.shape))
+    assert row_w is None or row_w.shape == left.shape, (tuple(row_w.shape), tuple(left.shape))
+    b = x.shape[0]
+    loss = torch.empty((b,), dtype=torch.float32, device=x.device)
+    gx = torch.empty((b,), dtype=torch.float32, device=x.device)
+    check(lib().cz_moves_left_loss(_dev(x, torch.float32), _dev(idx, torch.int32), b, left.shape[0], _dev(left, torch.int32),
+                                   _opt(row_w, torch.float32), float(unit), float(delta), float(w_m),
+                                   _dev(loss, torch.float32), _dev(gx, torch.float32), _stream()), "cz_moves_left_loss")
+    return loss, gx
 
 
 def check_or_catch(boards, moves):
@@ -626,6 +649,30 @@ def heads_tail_wdl(policy_feat, value_feat, wp, bias_p, w1, bias1, w2, b2, polic
                                   _ptr(wdl) if wdl is not None else None, _ptr(stats), n, _dt_code(wp.dtype),
                                   int(bool(normalize)), _ptr(count) if count is not None else None, _stream()),
           "cz_heads_tail_wdl")
+    return policy, value
+
+
+def heads_tail_ml(policy_feat, value_feat, wp, bias_p, w1, bias1, w2, b2, policy, value, stats, moves_left, wdl=None,
+                  count=None, normalize=True, value_outputs=None):
+    """heads_tail / heads_tail_wdl for a value head with a moves-left output (cz_heads_tail_ml): w2 fp32
+    [value_outputs + 1, n_hidden] on the device with the moves-left row last, b2 the matching value_outputs + 1 floats;
+    value_outputs 1 (scalar tanh head) or 3 (win / draw / loss), by default what w2's shape says.  moves_left: fp32 [N]
+    that receives the raw output x (the prediction is MOVES_LEFT_UNIT * softplus(x) plies, agent/model.py); value, and wdl
+    (value_outputs 3 only), have the bits heads_tail / heads_tail_wdl give.  The library refuses what does not fit."""
+    require_gpu()
+    n = policy_feat.shape[0]
+    vo = w2.shape[0] - 1 if value_outputs is None else int(value_outputs)
+    assert w2.dim() == 2 and w2.shape[1] == bias1.shape[0] and w2.is_contiguous() and len(b2) == w2.shape[0] and \
+        w2.shape[0] >= vo + 1, (tuple(w2.shape), b2, vo)
+    assert moves_left is None or (tuple(moves_left.shape) == (n,) and moves_left.is_contiguous()), tuple(moves_left.shape)
+    assert wdl is None or (tuple(wdl.shape) == (n, 3) and wdl.is_contiguous()), None if wdl is None else tuple(wdl.shape)
+    b2c = (C.c_float * len(b2))(*[float(b) for b in b2])
+    check(lib().cz_heads_tail_ml(_ptr(policy_feat), policy_feat.shape[1], _ptr(wp), _ptr(bias_p), policy.shape[1],
+                                 _ptr(value_feat), value_feat.shape[1], _ptr(w1), _ptr(bias1), bias1.shape[0], vo, _ptr(w2),
+                                 b2c, _ptr(policy), _ptr(value), _ptr(wdl) if wdl is not None else None,
+                                 _ptr(moves_left) if moves_left is not None else None, _ptr(stats), n, _dt_code(wp.dtype),
+                                 int(bool(normalize)), _ptr(count) if count is not None else None, _stream()),
+          "cz_heads_tail_ml")
     return policy, value
 
 

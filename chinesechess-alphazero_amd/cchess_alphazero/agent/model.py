@@ -7,6 +7,7 @@ Flatten(C,H,W) -> Dense(2086) softmax; value: Conv1x1(2) -> BN -> ReLU -> Flatte
 Dense(1) tanh.  Convs have no bias; BN eps = 1e-3 (Keras default, data/model/*.json).
 value_outputs=3 replaces the value head's end by Dense(3) softmax over (win, draw, loss) for the side to move; the value
 every consumer reads is then P(win) - P(loss).
+moves_left=True adds a second last layer beside it, Dense(1) on the same hidden layer: the moves-left output.
 
 ``InferenceNet`` is the eval-mode form used by self-play: BatchNorm folded into the convolutions and, with
 trunk="mfma" (the default), every layer on hand-written HIP kernels (csrc/xq_conv.hip, xq_nn_epilogue.hip,
@@ -15,6 +16,7 @@ with softmax / tanh); trunk="library" keeps the MIOpen / hipBLASLt path for comp
 """
 import hashlib
 import json
+import math
 import os
 from logging import getLogger
 from typing import NamedTuple, Optional
@@ -27,6 +29,17 @@ logger = getLogger(__name__)
 
 N_LABELS = 2086
 BN_EPS = 1e-3
+# The moves-left output: a raw x means m(x) = MOVES_LEFT_UNIT * softplus(x) plies until the game ends; the trainer's Huber
+# loss is taken in units with the threshold MOVES_LEFT_DELTA (16 plies: lc0's ratio of delta to scale).  The device side
+# states the same two numbers once, include/czero.h CZ_MOVES_LEFT_UNIT / CZ_MOVES_LEFT_DELTA.
+MOVES_LEFT_UNIT = 32.0
+MOVES_LEFT_DELTA = 0.5
+MOVES_LEFT_BIAS = math.log(math.e ** 2 - 1.0)       # softplus(bias) = 2: a fresh model predicts 64 plies
+
+
+def moves_left_plies(x):
+    """m(x): the plies a raw moves-left output x stands for (a tensor in, a tensor out)."""
+    return MOVES_LEFT_UNIT * F.softplus(x)
 
 
 class ResidualBlock(nn.Module):
@@ -48,8 +61,10 @@ class CChessNet(nn.Module):
 
     def __init__(self, cnn_filter_num=256, cnn_first_filter_size=5, cnn_filter_size=3, res_layer_num=7,
                  value_fc_size=256, input_depth=14, policy_filters=4, value_filters=2, n_labels=N_LABELS,
-                 value_outputs=1):
-        """value_outputs: 1 = the reference's scalar tanh value head, 3 = a win / draw / loss head (Dense(3) + softmax)."""
+                 value_outputs=1, moves_left=False):
+        """value_outputs: 1 = the reference's scalar tanh value head, 3 = a win / draw / loss head (Dense(3) + softmax).
+        moves_left: the value head gets a second last layer beside value_out, moves_left_out = Dense(1) on the same ReLU'd
+        hidden layer; its raw output x means MOVES_LEFT_UNIT * softplus(x) plies to the end of the game."""
         super().__init__()
         if value_outputs not in (1, 3):
             raise ValueError(f"value_outputs={value_outputs!r}: 1 (scalar tanh head) or 3 (win / draw / loss head)")
@@ -58,6 +73,8 @@ class CChessNet(nn.Module):
                         value_fc_size=value_fc_size, input_depth=input_depth,
                         policy_filters=policy_filters, value_filters=value_filters, n_labels=n_labels,
                         value_outputs=value_outputs)
+        if moves_left:                  # (a key of its own, present only with the output: every other net's cfg, and so its
+            self.cfg["moves_left"] = 1  #  model file, is what it was)
         f = cnn_filter_num
         self.input_conv = nn.Conv2d(input_depth, f, cnn_first_filter_size, padding=cnn_first_filter_size // 2,
                                     bias=False)
@@ -70,10 +87,18 @@ class CChessNet(nn.Module):
         self.value_bn = nn.BatchNorm2d(value_filters, eps=BN_EPS, momentum=0.01)
         self.value_dense = nn.Linear(value_filters * 90, value_fc_size)
         self.value_out = nn.Linear(value_fc_size, value_outputs)
+        if moves_left:                  # built last: every other layer draws from the seed what it drew without it
+            self.moves_left_out = nn.Linear(value_fc_size, 1)
+            with torch.no_grad():
+                self.moves_left_out.bias.fill_(MOVES_LEFT_BIAS)
 
     @property
     def wdl_head(self):
         return self.value_out.out_features == 3
+
+    @property
+    def moves_left_head(self):
+        return hasattr(self, "moves_left_out")
 
     def trunk(self, x):
         x = F.relu(self.input_bn(self.input_conv(x)))
@@ -81,23 +106,27 @@ class CChessNet(nn.Module):
             x = blk(x)
         return x
 
-    def forward(self, x, logits=False):
+    def forward(self, x, logits=False, moves_left=False):
         """-> (policy [B, 2086], value [B]); logits=True returns the policy head's logits instead of its softmax (the
         trainer's loss, worker/optimize.py, takes the logits).  A win / draw / loss net (value_outputs=3): value [B] =
-        P(win) - P(loss), and with logits=True the value head's three logits [B, 3] as well."""
+        P(win) - P(loss), and with logits=True the value head's three logits [B, 3] as well.  moves_left=True (a net built
+        with the output): a third tensor follows, the raw moves-left output x [B] (moves_left_plies gives its plies)."""
+        if moves_left and not self.moves_left_head:
+            raise RuntimeError("moves_left=True: this network has no moves-left output (CChessNet(moves_left=True))")
         x = self.trunk(x)
         p = F.relu(self.policy_bn(self.policy_conv(x)))
         p = self.policy_out(p.flatten(1))                      # Flatten order C,H,W (channels_first)
-        v = F.relu(self.value_bn(self.value_conv(x)))
-        v = F.relu(self.value_dense(v.flatten(1)))
-        v = self.value_out(v)
+        h = F.relu(self.value_bn(self.value_conv(x)))
+        h = F.relu(self.value_dense(h.flatten(1)))
+        v = self.value_out(h)
+        ml = (self.moves_left_out(h).squeeze(1),) if moves_left else ()
         if self.wdl_head:
             if logits:
-                return p, v
+                return (p, v) + ml
             w = F.softmax(v, dim=1)
-            return F.softmax(p, dim=1), w[:, 0] - w[:, 2]
+            return (F.softmax(p, dim=1), w[:, 0] - w[:, 2]) + ml
         v = torch.tanh(v)
-        return (p if logits else F.softmax(p, dim=1)), v.squeeze(1)
+        return ((p if logits else F.softmax(p, dim=1)), v.squeeze(1)) + ml
 
     def wdl(self, x):
         """[B, 3] probabilities (win, draw, loss) for the side to move; a win / draw / loss net only."""
@@ -111,7 +140,7 @@ class CChessNet(nn.Module):
         return cls(cnn_filter_num=mc.cnn_filter_num, cnn_first_filter_size=mc.cnn_first_filter_size,
                    cnn_filter_size=mc.cnn_filter_size, res_layer_num=mc.res_layer_num,
                    value_fc_size=mc.value_fc_size, input_depth=getattr(mc, "input_depth", 14),
-                   value_outputs=getattr(mc, "value_outputs", 1))
+                   value_outputs=getattr(mc, "value_outputs", 1), moves_left=bool(getattr(mc, "moves_left", False)))
 
 
 def _fold(conv, bn):
@@ -322,6 +351,10 @@ class InferenceNet(nn.Module):
             self.value_dense = nn.Linear(net.value_dense.in_features, net.value_dense.out_features)
             self.value_out = nn.Linear(net.value_out.in_features, net.value_out.out_features)
             self.wdl_head = net.value_out.out_features == 3
+            self.moves_left_head = net.moves_left_head
+            if self.moves_left_head:
+                self.moves_left_out = nn.Linear(net.moves_left_out.in_features, 1)
+                self.moves_left_out.load_state_dict(net.moves_left_out.state_dict())
             self.policy_out.load_state_dict(net.policy_out.state_dict())
             self.value_dense.load_state_dict(net.value_dense.state_dict())
             self.value_out.load_state_dict(net.value_out.state_dict())
@@ -358,6 +391,13 @@ class InferenceNet(nn.Module):
             self._tail_dtype = self._tail_pack[0].dtype
             for name, t in zip(("tail_wp", "tail_bp", "tail_w1", "tail_b1", "tail_w2"), self._tail_pack):
                 self.register_buffer(name, t.view(torch.int16) if t.dtype in (torch.bfloat16, torch.float16) else t)
+            if self.moves_left_head:
+                # cz_heads_tail_ml's last layer: the value head's rows, then the moves-left row (tail_w2 stays as it is for
+                # the launches without moves_left=)
+                self.register_buffer("tail_w2_ml", torch.cat([self.tail_w2.reshape(-1, self.tail_w2.shape[-1]),
+                                                              self._tail_ml[0]]).contiguous())
+                self._tail_b2_ml = (list(self._tail_b2) if self.wdl_head else [self._tail_b2]) + [self._tail_ml[1]]
+                del self._tail_ml
             del self._packed_in, self._in_table, self._in_bias32, self._head_w, self._head_b, self._tail_pack
         self._bufs = {}
         self._plans = {}                    # _plan's launch plans, per switch setting
@@ -401,6 +441,9 @@ class InferenceNet(nn.Module):
                            else self.value_out.weight.detach().float().reshape(-1).clone())
         self._tail_b2 = ([float(b) for b in self.value_out.bias.detach().float()] if self.wdl_head
                          else float(self.value_out.bias.detach().float().item()))
+        if self.moves_left_head:        # the moves-left row and bias in fp32, taken like the rest before the dtype conversion
+            self._tail_ml = (self.moves_left_out.weight.detach().float().clone(),
+                             float(self.moves_left_out.bias.detach().float().item()))
         self._head_w = torch.cat([self.policy_conv.weight.detach().float().flatten(1),
                                   self.value_conv.weight.detach().float().flatten(1)]).contiguous()
         self._head_b = torch.cat([self.policy_conv.bias.detach().float(), self.value_conv.bias.detach().float()])
@@ -681,7 +724,12 @@ class InferenceNet(nn.Module):
             raise RuntimeError("wdl=: this network has the scalar value head")
         return torch.tanh(v).squeeze(1) if out is None else torch.tanh(v, out=out.view(-1, 1))
 
-    def forward(self, planes, rows=None, count=None, out=None, logits=False, masks=None, wdl=None):
+    def _moves_left(self, hidden, moves_left):
+        """The torch tails' moves-left output from the hidden layer, into `moves_left` where one is given."""
+        if moves_left is not None:
+            moves_left[:hidden.shape[0]].copy_(self.moves_left_out(hidden).float().squeeze(1))
+
+    def forward(self, planes, rows=None, count=None, out=None, logits=False, masks=None, wdl=None, moves_left=None):
         """planes: the evaluation queue.  rows / count (int32 cuda tensors, cz_search_round_q): evaluate only the
         boards planes[rows[i]], i < count -- the result rows are indexed by i; rows beyond count are undefined.
         out = (policy [n, 2086] fp32, value [n] fp32): write the results there (the engine's queue tensors) instead of
@@ -690,9 +738,14 @@ class InferenceNet(nn.Module):
         masks (int32 [n, 96], Search.leaf_masks): the same positions as occupancy boards; the fused input layer of the first
         residual block takes them instead of scanning the planes (ignored on every other path).
         wdl (fp32 [n, 3], win / draw / loss networks only): receives the value head's probabilities; out[1] stays the [n]
-        value P(win) - P(loss) the search reads."""
+        value P(win) - P(loss) the search reads.
+        moves_left (fp32 [n], networks with the moves-left output only): receives that output's raw x per row
+        (moves_left_plies gives its plies); the tail launch is then cz_heads_tail_ml, and policy and value keep the bits of
+        a forward without it.  Nothing in the search reads it yet, so the load-time guard does not measure it."""
         if wdl is not None and not self.wdl_head:
             raise RuntimeError("wdl=: this network has the scalar value head")
+        if moves_left is not None and not self.moves_left_head:
+            raise RuntimeError("moves_left=: this network has no moves-left output")
         if logits and not self.supports_logits():
             raise RuntimeError("logits=True needs the hand-written dense tail")
         if rows is not None and not self.supports_compact_queue():
@@ -720,6 +773,12 @@ class InferenceNet(nn.Module):
                     key = ("tail_stats", str(planes.device))          # scratch for the rows' (max, sum): grown, never per size
                     if key not in self._bufs or self._bufs[key].shape[0] < n:
                         self._bufs[key] = torch.empty((n, 2), dtype=torch.float32, device=planes.device)
+                    if moves_left is not None:
+                        _native.heads_tail_ml(pf, vf, self.tail_wp.view(self._tail_dtype), self.tail_bp,
+                                              self.tail_w1.view(self._tail_dtype), self.tail_b1, self.tail_w2_ml,
+                                              self._tail_b2_ml, out[0], out[1], self._bufs[key], moves_left, wdl=wdl,
+                                              count=count, normalize=not logits)
+                        return out
                     if self.wdl_head:
                         _native.heads_tail_wdl(pf, vf, self.tail_wp.view(self._tail_dtype), self.tail_bp,
                                                self.tail_w1.view(self._tail_dtype), self.tail_b1, self.tail_w2,
@@ -732,6 +791,7 @@ class InferenceNet(nn.Module):
                     return out
                 p = self.policy_out(pf.to(self.dtype))
                 v = F.relu(self.value_dense(vf.to(self.dtype)))
+                self._moves_left(v, moves_left)
                 if out is not None:                            # straight into the search object's queue tensors
                     torch.softmax(p.float(), dim=1, out=out[0])
                     self._value(v, out[1], wdl)
@@ -754,6 +814,7 @@ class InferenceNet(nn.Module):
         p = self.policy_out(p.flatten(1))                # flatten of an NCHW-shaped tensor: C,H,W order
         v = F.relu(self.value_conv(x))
         v = F.relu(self.value_dense(v.flatten(1)))
+        self._moves_left(v, moves_left)
         return F.softmax(p.float(), dim=1), self._value(v, None, wdl)
 
 
@@ -1142,7 +1203,7 @@ def flops_per_position(cfg):
     mac = cfg["input_depth"] * f * k1 * k1 * 90 + 2 * n * f * f * k * k * 90
     mac += f * cfg["policy_filters"] * 90 + cfg["policy_filters"] * 90 * cfg.get("n_labels", N_LABELS)
     mac += (f * cfg["value_filters"] * 90 + cfg["value_filters"] * 90 * cfg["value_fc_size"] +
-            cfg["value_fc_size"] * cfg.get("value_outputs", 1))
+            cfg["value_fc_size"] * (cfg.get("value_outputs", 1) + cfg.get("moves_left", 0)))
     return 2 * mac
 
 

@@ -189,7 +189,8 @@ class SelfPlayEngine:
             raise RuntimeError("the engine was built on an evaluator callable, not on a network")
         # (the value head's end is not part of what must match: each InferenceNet carries its own tail and hands the search
         #  one scalar per leaf, so a scalar net may follow a win / draw / loss one and the other way round)
-        same = lambda cfg: {k: v for k, v in cfg.items() if k != "value_outputs"}
+        #  (nor is the moves-left output, which the engine does not read)
+        same = lambda cfg: {k: v for k, v in cfg.items() if k not in ("value_outputs", "moves_left")}
         if same(net.cfg) != same(self.model_cfg):
             raise ValueError(f"hot reload: topology changed ({self.model_cfg} -> {net.cfg})")
         torch.cuda.synchronize(self.device)

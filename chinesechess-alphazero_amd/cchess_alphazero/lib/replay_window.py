@@ -71,20 +71,39 @@ def mix_targets(z, q, q_ratio):
     return np.where(np.isnan(q), z, t).astype(np.float32)
 
 
+def moves_left_targets(lens):
+    """The moves-left targets of whole games (run.py opt --moves-left), game after game: lens[g] = the record items of
+    game g, and the position before item t (t = 0 .. L - 1) gets L - t, the number of items from its own to the end of its
+    game, inclusive -- the last recorded position has 1, whatever ended the game (king capture, resignation, the length
+    limit).  A record does not say that it was cut short: the games `run.py reanalyse --reanalyse-plies` truncates carry
+    targets that are too small, and nothing here or in the trainer can tell.  -> int32 [sum(lens)]."""
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if (lens < 0).any():
+        raise ValueError("moves_left_targets: a negative game length")
+    if lens.sum() == 0:
+        return np.zeros(0, dtype=np.int32)
+    return np.concatenate([np.arange(n, 0, -1, dtype=np.int32) for n in lens])
+
+
 class ReplayWindow:
     """Positions of whole record files, appended in load order.  ``capacity`` is ``trainer.dataset_size``: ``full`` turns
     true once it is reached, and the file that reaches it is kept whole (the reference's fill_queue checks the size before
     each file).  depth 28 = ``has_history`` networks (state_history_to_planes)."""
 
-    def __init__(self, capacity, depth=14, device="cuda", surprise_weight=0.0):
+    def __init__(self, capacity, depth=14, device="cuda", surprise_weight=0.0, moves_left=False):
         """surprise_weight A > 0: the window also holds ``w``, every position's training weight from the records' policy
-        surprise (surprise_weights), on the device for ``loss(..., surprise=True)``; at 0 no such array exists."""
+        surprise (surprise_weights), on the device for ``loss(..., surprise=True)``; at 0 no such array exists.
+        moves_left=True: the window also holds ``left`` (int32, on the device), every position's moves-left target
+        (moves_left_targets; weight-0 rows get theirs like every row), for ``loss(..., moves_left=...)``; with False no such
+        array exists."""
         if depth not in (14, 28):
             raise ValueError(f"depth={depth}: expected 14 or 28")
         if isinstance(surprise_weight, bool) or not 0.0 <= float(surprise_weight) <= 1.0:
             raise ValueError(f"surprise_weight={surprise_weight!r}: expected 0 <= A <= 1")
         self.surprise_weight = float(surprise_weight)
         self.w = None
+        self.moves_left = bool(moves_left)
+        self.left = None
         _native.require_gpu()
         self.capacity, self.depth = int(capacity), depth
         self.device = torch.device(device)
@@ -105,6 +124,8 @@ class ReplayWindow:
         self.s = torch.empty((n,), dtype=torch.float32, device=d)
         if self.surprise_weight:
             self.w = torch.empty((n,), dtype=torch.float32, device=d)
+        if self.moves_left:
+            self.left = torch.empty((n,), dtype=torch.int32, device=d)
         self.row_ptr = torch.zeros((n + 1,), dtype=torch.int32, device=d)
         self.vis_label = torch.empty((nnz,), dtype=torch.uint16, device=d)
         self.vis_count = torch.empty((nnz,), dtype=torch.int32, device=d)
@@ -114,7 +135,8 @@ class ReplayWindow:
         (the file that crosses the capacity gets exactly the room it needs), visit entries double up to INT32_MAX."""
         if n > self.boards.shape[0]:
             cap = min(self.capacity, max(n, 1 << 16, 2 * self.boards.shape[0])) if n <= self.capacity else n
-            for name in ("boards", "prev", "played", "z", "q", "s") + (("w",) if self.w is not None else ()):
+            for name in (("boards", "prev", "played", "z", "q", "s") + (("w",) if self.w is not None else ()) +
+                         (("left",) if self.left is not None else ())):
                 old = getattr(self, name)
                 new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
                 new[:self.n] = old[:self.n]
@@ -253,6 +275,8 @@ class ReplayWindow:
         self.s[n0:n0 + P] = torch.from_numpy(ss).to(dev)
         if self.w is not None:                  # a game's weights depend on that game's rows alone
             self.w[n0:n0 + P] = torch.from_numpy(surprise_weights(ss, train, offsets, self.surprise_weight)).to(dev)
+        if self.left is not None:
+            self.left[n0:n0 + P] = torch.from_numpy(moves_left_targets(lens)).to(dev)
         rp = (z0 + np.cumsum(nvis)).astype(np.int32)
         self.row_ptr[n0 + 1:n0 + P + 1] = torch.from_numpy(rp).to(dev)
         if nnz:
@@ -272,7 +296,8 @@ class ReplayWindow:
         device, or None: a row with a nonzero flag is the left-right mirrored position (cz_gather_planes_m)."""
         return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth, mirror=mirror)
 
-    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0, surprise=False):
+    def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0, surprise=False,
+             moves_left=None):
         """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
         differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss).  mirror: the flags given to
         ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m).  q_ratio L > 0: the value
@@ -281,9 +306,20 @@ class ReplayWindow:
         (cz_policy_value_loss_w) and in the returned means, mean(w[idx] * loss) -- still divided by B.
         v of shape [B, 3] -- the value logits of a win / draw / loss network (CChessNet(value_outputs=3)): the value loss is
         the cross-entropy against the class of z (cz_policy_wdl_loss), and a fourth entry follows, the mean squared error
-        of P(win) - P(loss) against z: the number a scalar run reports.  q_ratio must be 0 then."""
+        of P(win) - P(loss) against z: the number a scalar run reports.  q_ratio must be 0 then.
+        moves_left=(x, W) (a window built with moves_left=True): x [B] is the network's raw moves-left output and W >= 0 the
+        loss weight.  W * mean Huber loss (cz_moves_left_loss; the mean formed as the others are, surprise included) is added
+        to the first entry, differentiable in x, and the mean Huber loss follows as one more entry at the end.  Without the
+        argument the result is what it is above, from the same launches."""
         if surprise and self.w is None:
             raise ValueError("loss(surprise=True) needs a window built with surprise_weight > 0")
+        if moves_left is not None:
+            if self.left is None:
+                raise ValueError("loss(moves_left=...) needs a window built with moves_left=True")
+            x_ml, w_m = moves_left
+            res = self.loss(logits, v, idx, targets, weights, mirror=mirror, q_ratio=q_ratio, surprise=surprise)
+            ml_total, ml_mean = _MovesLeftLoss.apply(x_ml, idx, self, float(w_m), bool(surprise))
+            return (res[0] + ml_total,) + tuple(res[1:]) + (ml_mean,)
         if v.dim() == 2:
             if v.shape[1] != 3:
                 raise ValueError(f"value of shape {tuple(v.shape)}: [B] (scalar head) or [B, 3] (win / draw / loss logits)")
@@ -379,3 +415,24 @@ class _PolicyWdlLoss(torch.autograd.Function):
     def backward(ctx, g_total, _g_pm, _g_vm, _g_sm):
         gl, gv = ctx.saved_tensors
         return g_total * gl, g_total * gv, None, None, None, None, None, None, None
+
+
+class _MovesLeftLoss(torch.autograd.Function):
+    """W * mean(Huber loss of the moves-left output) of a minibatch and that mean (cz_moves_left_loss); backward hands out
+    the kernel's gradient.  surprise: the rows count with their weights, as in the other losses."""
+
+    @staticmethod
+    def forward(ctx, x, idx, win, w_m, surprise=False):
+        from cchess_alphazero.agent.model import MOVES_LEFT_DELTA, MOVES_LEFT_UNIT
+        n = win.n
+        hl, gx = _native.moves_left_loss(x.detach().contiguous(), idx, win.left[:n], MOVES_LEFT_UNIT, MOVES_LEFT_DELTA,
+                                         row_w=win.w[:n] if surprise else None, w_m=w_m)
+        ctx.save_for_backward(gx)
+        mm = (win.w[:n][idx.long()] * hl).mean() if surprise else hl.mean()
+        ctx.mark_non_differentiable(mm)
+        return w_m * mm, mm
+
+    @staticmethod
+    def backward(ctx, g_total, _g_mm):
+        gx, = ctx.saved_tensors
+        return g_total * gx, None, None, None, None

@@ -64,6 +64,11 @@ _FLAGS = [
     ("--augment", dict(choices=["none", "mirror"], default="none",
                        help="(opt) mirror: every training row of every epoch is the left-right mirrored position with "
                             "probability 1/2 (planes and policy targets, in the trainer's kernels)")),
+    ("--moves-left", dict(type=float, default=0.0, metavar="W",
+                          help="(opt) train the moves-left output (one more Dense(1) on the value head's hidden layer, "
+                               "predicting the plies until the game ends) with the loss weight W (finite, >= 0; 0 = off); a "
+                               "new model (--new, or no best model yet) is built with the output, a best model without it "
+                               "is refused")),
     ("--value-head", dict(choices=["scalar", "wdl"], default=None,
                           help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
@@ -150,6 +155,11 @@ def build_config(args):
         raise SystemExit(f"--q-ratio {args.q_ratio:g} with --value-head wdl: a scalar q does not determine a distribution "
                          "over win / draw / loss")
     config.trainer.value_head = args.value_head
+    if not 0.0 <= args.moves_left < float("inf"):           # (NaN fails both comparisons)
+        raise SystemExit(f"--moves-left {args.moves_left}: expected a finite W >= 0")
+    if args.moves_left and args.cmd != "opt":
+        raise SystemExit("--moves-left is an option of `run.py opt`")
+    config.trainer.moves_left = args.moves_left
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -43,6 +43,16 @@ Deliberate deviations from the reference:
     predicted draw probability on the validation rows beside their share of drawn results.  ``--q-ratio`` is refused
     with such a model: a scalar q does not determine a distribution.  The flag is refused when it contradicts the best
     model's head;
+  - ``--moves-left W`` (default 0: off) trains the moves-left output, lc0's moves-left head reduced to one more Dense(1)
+    on the value head's hidden layer (``CChessNet(moves_left=True)``): its raw output x means 32 softplus(x) plies until
+    the game ends.  A position's target is the number of record items from its own to the end of its game, inclusive
+    (lib/replay_window.py ``moves_left_targets``), and W times the mean Huber loss of softplus(x) - target / 32, threshold
+    0.5 (``cz_moves_left_loss``), is added to the loss; the row weights of ``--surprise-weight`` apply, the mirror leaves
+    the target as it is.  A new model (``--new``, or none there) is built with the output; a best model without it is
+    refused.  Every epoch reports ``moves_left`` / ``val_moves_left`` (the mean Huber loss) and ``val_moves_left_mae``,
+    the mean |32 softplus(x) - target| in plies on the validation rows.  With W = 0 a model that has the output trains
+    as one without it: the output gets no gradient beyond L2.  A record does not say that it was cut short, so the games
+    of ``run.py reanalyse --reanalyse-plies`` carry targets that are too small, and ``opt`` cannot tell;
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -144,6 +154,9 @@ class OptimizeWorker:
         if self.value_head not in (None, "scalar", "wdl"):
             raise ValueError(f"trainer.value_head={self.value_head!r}: expected scalar or wdl")
         self.wdl = False                # set by load_model: the model has the win / draw / loss head
+        self.moves_left_weight = float(getattr(config.trainer, "moves_left", 0.0))
+        if not 0.0 <= self.moves_left_weight < float("inf"):
+            raise ValueError(f"trainer.moves_left={self.moves_left_weight!r}: expected a finite W >= 0")
         self.rng = np.random.default_rng(config.engine.base_seed)
         # the mirror flags have their own stream: self.rng draws what it draws without the option
         self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
@@ -162,8 +175,15 @@ class OptimizeWorker:
         if self.config.opts.new or not load_best_model_weight(model):
             self.config.model.input_depth = self.depth
             self.config.model.value_outputs = 3 if self.value_head == "wdl" else 1
+            self.config.model.moves_left = bool(self.moves_left_weight)
             model.build(seed=self.config.engine.base_seed)
             save_as_best_model(model)
+        if self.moves_left_weight and not model.model.moves_left_head:
+            raise ValueError(f"--moves-left {self.moves_left_weight:g}: the best model has no moves-left output; train it "
+                             f"without the option, or start a new model with --new")
+        if model.model.moves_left_head and not self.moves_left_weight:
+            logger.info("the model has a moves-left output and --moves-left is 0: the output is not trained (it gets no "
+                        "gradient beyond L2)")
         has = "wdl" if model.model.wdl_head else "scalar"
         if self.value_head is not None and self.value_head != has:
             raise ValueError(f"--value-head {self.value_head}: the best model has the {has} value head (scalar: Dense(1) + "
@@ -202,6 +222,8 @@ class OptimizeWorker:
         from cchess_alphazero.lib.replay_window import ReplayWindow
         # (nothing is passed at 0: the window is built as it was without the option)
         extra = dict(surprise_weight=self.surprise_weight) if self.surprise_weight else {}
+        if self.moves_left_weight:
+            extra["moves_left"] = True
         return ReplayWindow(self.config.trainer.dataset_size, depth=self.depth, **extra)
 
     def training(self):
@@ -286,16 +308,22 @@ class OptimizeWorker:
             flags = self.mirror_flags(len(tr))
             flags_d = torch.from_numpy(flags).to(dev) if flags is not None else None
             net.train()
-            sums = torch.zeros(3, dtype=torch.float64, device=dev)
+            ml = bool(self.moves_left_weight)        # a step then returns a fourth figure, the mean moves-left loss
+            sums = torch.zeros(4 if ml else 3, dtype=torch.float64, device=dev)
             t0 = time.time()
             for b in range(0, len(tr), bs):
                 idx = perm[b:b + bs]
-                loss, pm, vm = self.step(idx, None if flags_d is None else flags_d[b:b + bs])
-                sums += torch.stack([loss.detach(), pm, vm]).double() * len(idx)
+                res = self.step(idx, None if flags_d is None else flags_d[b:b + bs])
+                sums += torch.stack([res[0].detach(), *res[1:]]).double() * len(idx)
             tr_loss = (sums / max(1, len(tr))).tolist()
-            extra = {}                  # (a win / draw / loss model's further validation figures; nothing is asked otherwise)
-            va_loss = (self.evaluate(va_d, **(dict(extra=extra) if self.wdl else {}))) if len(va) else [float("nan")] * 3
-            entry = dict(train=tr_loss, val=va_loss, **extra)
+            # (a win / draw / loss model's and the moves-left output's further validation figures; nothing is asked otherwise)
+            extra = {}
+            va_loss = (self.evaluate(va_d, **(dict(extra=extra) if self.wdl or ml else {}))) if len(va) else [float("nan")] * 3
+            entry = dict(train=tr_loss[:3], val=va_loss, **extra)
+            if ml:
+                entry["moves_left"] = tr_loss[3]
+                for k in ("val_moves_left", "val_moves_left_mae"):      # (`extra` keeps the win / draw / loss figures only)
+                    entry[k] = extra.pop(k, float("nan"))
             logger.info(f"epoch {ep + 1}/{epochs}: {len(tr)} positions in {time.time() - t0:.1f} s; "
                         f"loss {tr_loss[0]:.4f} policy {tr_loss[1]:.4f} value {tr_loss[2]:.4f} - "
                         f"val_loss {va_loss[0]:.4f} val_policy {va_loss[1]:.4f} val_value {va_loss[2]:.4f}")
@@ -309,6 +337,10 @@ class OptimizeWorker:
                 logger.info(f"epoch {ep + 1}/{epochs}: win / draw / loss head, value = cross-entropy; P(win) - P(loss) "
                             f"against z: val_value_z {extra['val_value_z']:.4f}; validation rows: mean P(draw) "
                             f"{extra['val_draw_pred']:.4f}, drawn results {extra['val_draw_share']:.4f}")
+            if ml:
+                logger.info(f"epoch {ep + 1}/{epochs}: moves-left output, weight {self.moves_left_weight:g}: moves_left "
+                            f"{entry['moves_left']:.4f} - val_moves_left {entry['val_moves_left']:.4f} val_moves_left_mae "
+                            f"{entry['val_moves_left_mae']:.2f} plies")
             if self.q_ratio:
                 entry["val_value_z"] = self.evaluate(va_d, q_ratio=0.0)[2] if len(va) else float("nan")
                 logger.info(f"epoch {ep + 1}/{epochs}: value targets z + {self.q_ratio:g} (q - z); against z alone: "
@@ -328,17 +360,27 @@ class OptimizeWorker:
 
     def step(self, idx, mirror=None):
         """One SGD step on the window positions idx; returns (total loss incl. L2, policy loss, value loss).  mirror:
-        uint8 [B] on the device, the rows to train on as their mirror image (planes and targets alike), or None."""
+        uint8 [B] on the device, the rows to train on as their mirror image (planes and targets alike), or None.
+        With --moves-left W > 0 the total includes W times the mean moves-left loss, which follows as a fourth entry."""
         tc = self.config.trainer
-        logits, v = self.model.model(self.window.planes(idx, mirror=mirror), logits=True)
-        # (a win / draw / loss model returns its three value logits: the window's loss takes them as they are)
-        total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
-                                         **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))[:3]
+        planes = self.window.planes(idx, mirror=mirror)
+        if self.moves_left_weight:
+            logits, v, x_ml = self.model.model(planes, logits=True, moves_left=True)
+            res = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
+                                   **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight),
+                                   moves_left=(x_ml, self.moves_left_weight))
+            total, more = res[0], (res[1], res[2], res[-1])
+        else:
+            logits, v = self.model.model(planes, logits=True)
+            # (a win / draw / loss model returns its three value logits: the window's loss takes them as they are)
+            total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
+                                             **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))[:3]
+            more = (pm, vm)
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         self.opt.step()
-        return loss, pm, vm
+        return (loss,) + more
 
     @staticmethod
     def _q_args(q_ratio):
@@ -354,21 +396,33 @@ class OptimizeWorker:
         """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the
         mirror images of all rows.  q_ratio: the value targets' mix, None = the trainer's own.  extra: a dict that, for a
         win / draw / loss model, receives val_value_z (the squared error of P(win) - P(loss) against z), val_draw_pred
-        (the mean predicted draw probability) and val_draw_share (the share of rows with z == 0)."""
+        (the mean predicted draw probability) and val_draw_share (the share of rows with z == 0); with --moves-left W > 0 it
+        receives val_moves_left (the mean Huber loss, unweighted) and val_moves_left_mae (the mean |32 softplus(x) - target|
+        in plies), and the total includes W times the former."""
         import torch
+        from cchess_alphazero.agent.model import moves_left_plies
         tc = self.config.trainer
         net = self.model.model
         net.eval()
         sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
         wdl_sums = torch.zeros(3, dtype=torch.float64, device=idx_all.device)
+        ml_sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
+        ml_args = {}
         with torch.no_grad():
             for b in range(0, idx_all.shape[0], tc.batch_size):
                 idx = idx_all[b:b + tc.batch_size]
                 flags = torch.ones(idx.shape[0], dtype=torch.uint8, device=idx.device) if mirror else None
-                logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
+                if self.moves_left_weight:
+                    logits, v, x_ml = net(self.window.planes(idx, mirror=flags), logits=True, moves_left=True)
+                    ml_args = dict(moves_left=(x_ml, self.moves_left_weight))
+                else:
+                    logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
                 res = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags,
-                                       **self._q_args(self.q_ratio if q_ratio is None else q_ratio))
+                                       **self._q_args(self.q_ratio if q_ratio is None else q_ratio), **ml_args)
                 pm, vm = res[1], res[2]
+                if ml_args:
+                    err = (moves_left_plies(x_ml.double()) - self.window.left[idx.long()].double()).abs().sum()
+                    ml_sums += torch.stack([res[-1].double() * len(idx), err])
                 sums += torch.stack([pm, vm]).double() * len(idx)
                 if v.dim() == 2:
                     draws = (self.window.z[idx.long()] == 0).double().sum()
@@ -380,6 +434,11 @@ class OptimizeWorker:
             l2 = float(self.l2_term())
         net.train()
         w = tc.loss_weights
+        if self.moves_left_weight:
+            mh, mae = (ml_sums / idx_all.shape[0]).tolist()
+            if extra is not None:
+                extra.update(val_moves_left=mh, val_moves_left_mae=mae)
+            return [w[0] * p + w[1] * v + self.moves_left_weight * mh + l2, p, v]
         return [w[0] * p + w[1] * v + l2, p, v]
 
     def backup_play_data(self, files):

@@ -13,6 +13,8 @@
 //   k_fc_tile<VALUE>    hidden = relu(feat . W1^T + b1) stays in the accumulators, value = tanh(hidden . w2 + b2)
 //   k_fc_tile<WDL>      the same hidden layer against w2[3][n_hidden]: three logits (win, draw, loss) per position, a
 //                       max-subtracted softmax in fp32, value = (e_W - e_L) / ((e_W + e_L) + e_D) (cz_heads_tail_wdl)
+//   k_fc_tile<VALUE_ML / WDL_ML>  either of the two with one more row of w2 behind the head's own: the moves-left output
+//                       x = hidden . w2[ml] + b2[ml], written raw (cz_heads_tail_ml); value and wdl keep their bits
 // Arithmetic: the same split-operand scheme as the tower (xq_conv.hip): every fp32 operand is a (hi, lo) pair of 2-byte
 // values, a product is accumulated as w_hi x_hi + w_lo x_hi + w_hi x_lo in fp32 by v_mfma_f32_32x32x16_{bf16,f16}.
 // dtype CZ_BF16: dropped term and representation error 2^-17 relative per product; CZ_F16 (round 4, what the network
@@ -59,7 +61,7 @@ constexpr int FC_STAGE_ROW = 144;     // bytes per position row of a wave's logi
 constexpr int FC_STAGE_BYTES = 32 * FC_STAGE_ROW;            // per wave
 constexpr int FC_LDS_BYTES = FC_IMG_BYTES + FC_RED_BYTES + (FC_THREADS / 64) * FC_STAGE_BYTES;
 
-enum FcMode { FC_POLICY = 0, FC_VALUE = 1, FC_WDL = 2 };
+enum FcMode { FC_POLICY = 0, FC_VALUE = 1, FC_WDL = 2, FC_VALUE_ML = 3, FC_WDL_ML = 4 };
 
 struct FcArgs {
     const float* feat;        // [n][F]
@@ -85,6 +87,18 @@ template <int MODE> struct FcArgsOf { typedef FcArgs T; };
 template <> struct FcArgsOf<FC_WDL> { typedef FcArgsWdl T; };
 // FC_WDL combines three sums per position: the third lies behind `red`, in the logit staging tiles only FC_POLICY uses
 static_assert(3 * 256 * (int)sizeof(float) <= FC_RED_BYTES + FC_STAGE_BYTES, "the third WDL sum fits the first staging tile");
+
+// The moves-left modes' arguments (cz_heads_tail_ml): the value head's own fields as they are (FC_VALUE_ML leaves the WDL ones
+// unused), and the extra row of w2 with its bias and its output.  Again a type of its own: the three modes above keep theirs.
+struct FcArgsMl : FcArgsWdl {
+    const float* w2_ml;       // [n_out]: the last row of w2
+    float b2_ml;
+    float* moves_left;        // [n] raw output x
+};
+template <> struct FcArgsOf<FC_VALUE_ML> { typedef FcArgsMl T; };
+template <> struct FcArgsOf<FC_WDL_ML> { typedef FcArgsMl T; };
+// the moves-left sum is a fourth plane behind `red`, after the two WDL-only ones (the scalar head leaves those unused)
+static_assert(4 * 256 * (int)sizeof(float) <= FC_RED_BYTES + FC_STAGE_BYTES, "the moves-left sum fits the first staging tile");
 
 // F: features per position (180 or 360: 2 or 4 head filters x 90 squares; compile-time so that the staging loop divides
 // by a constant and the K loop unrolls around a weight ring)
@@ -120,6 +134,19 @@ __device__ __forceinline__ void fc_finish_wdl(const A& a, const float* red, int 
 template <>
 __device__ __forceinline__ void fc_finish_wdl<FcArgs>(const FcArgs&, const float*, int, int, int) {}
 
+// The moves-left modes' extra running dot and its finish (the four waves' sums in wave order, like every other sum here);
+// the other modes' argument types have no such row: their dead branches call the empty overloads.
+__device__ __forceinline__ void fc_dot_ml(const FcArgsMl& a, float h, int j, float& dot_m) { dot_m += h * a.w2_ml[j]; }
+__device__ __forceinline__ void fc_finish_ml(const FcArgsMl& a, const float* red, int bt, int ln, int board)
+{
+    float d = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) d += red[768 + (bt * 4 + q) * 32 + ln];
+    a.moves_left[board] = d + a.b2_ml;
+}
+template <typename A> __device__ __forceinline__ void fc_dot_ml(const A&, float, int, float&) {}
+template <typename A> __device__ __forceinline__ void fc_finish_ml(const A&, const float*, int, int, int) {}
+
 template <int MODE, int F, typename E>
 __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>::T a, int n, const int32_t* __restrict__ n_dev)
 {
@@ -127,6 +154,8 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
     constexpr int RB = KS * 32 + 16;                  // bytes per position row of the feature image; RB / 16 is odd, so
     constexpr int PART = TILE_ROWS * RB;              // the 16 lanes of a ds_read_b128 group (16 consecutive positions, same
     constexpr int RING = 6;                           // chunk) fall on 16 different 16-byte slots of the 256-byte bank row
+    constexpr bool ML = MODE == FC_VALUE_ML || MODE == FC_WDL_ML;      // one more output row: moves left
+    constexpr int HEAD = MODE == FC_VALUE_ML ? FC_VALUE : (MODE == FC_WDL_ML ? FC_WDL : MODE);    // the value head's own mode
     static_assert(F % 4 == 0 && KS <= FC_MAX_KSTEPS, "whole float4s per row");
     __shared__ __attribute__((aligned(16))) unsigned char lds[FC_LDS_BYTES];
     n = nn_live_boards(n, n_dev);
@@ -173,6 +202,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
         float m_run = -3.0e38f, s_run = 0.0f;      // policy: running max / sum of exp of this lane's labels
         float dot = 0.0f;                          // value: partial hidden . w2 (WDL: the win row)
         float dot_d = 0.0f, dot_l = 0.0f;          // WDL: the draw and loss rows
+        float dot_m = 0.0f;                        // moves-left modes: the extra row
         const int board = row0 + bt * 32 + ln;
         // two label tiles per pass and wave (two independent MFMA chains, one set of position operands), weights through a
         // register ring RING K-steps deep: an L2 round trip is several hundred cycles, a K-step of one tile only 96
@@ -239,12 +269,13 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
                         s_run = s;
                         // into the wave's staging tile [position][32 labels]; written out in whole rows below
                         *reinterpret_cast<float4*>(stg + ln * FC_STAGE_ROW + (g * 8 + kb * 4) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-                    } else if (MODE == FC_VALUE) {
+                    } else if (HEAD == FC_VALUE) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (lab + i < a.n_out) {
                                 const float h = v[i] > 0.0f ? v[i] : 0.0f;
                                 dot += h * a.w2[lab + i];
+                                if (ML) fc_dot_ml(a, h, lab + i, dot_m);
                             }
                     } else {
 #pragma unroll
@@ -254,6 +285,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
                                 dot += h * a.w2[lab + i];
                                 dot_d += h * a.w2[a.n_out + lab + i];
                                 dot_l += h * a.w2[2 * a.n_out + lab + i];
+                                if (ML) fc_dot_ml(a, h, lab + i, dot_m);
                             }
                     }
                 }
@@ -296,12 +328,16 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
         } else {
             const float d = dot + __shfl_xor(dot, 32, 64);
             if (kb == 0) red[(bt * 4 + lq) * 32 + ln] = d;
-            if (MODE == FC_WDL) {
+            if (HEAD == FC_WDL) {
                 const float dd = dot_d + __shfl_xor(dot_d, 32, 64), dl = dot_l + __shfl_xor(dot_l, 32, 64);
                 if (kb == 0) {
                     red[256 + (bt * 4 + lq) * 32 + ln] = dd;
                     red[512 + (bt * 4 + lq) * 32 + ln] = dl;
                 }
+            }
+            if (ML) {
+                const float dm = dot_m + __shfl_xor(dot_m, 32, 64);
+                if (kb == 0) red[768 + (bt * 4 + lq) * 32 + ln] = dm;
             }
         }
         __syncthreads();
@@ -318,7 +354,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
                 for (int q = 0; q < 4; ++q)
                     s += red[256 + (bt * 4 + q) * 32 + ln] * fexp(red[(bt * 4 + q) * 32 + ln] - mx);
                 a.stats[board] = make_float2(mx, s);
-            } else if (MODE == FC_VALUE) {
+            } else if (HEAD == FC_VALUE) {
                 float d = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) d += red[(bt * 4 + q) * 32 + ln];
@@ -326,6 +362,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_tile(typename FcArgsOf<MODE>:
             } else {
                 fc_finish_wdl(a, red, bt, ln, board);
             }
+            if (ML) fc_finish_ml(a, red, bt, ln, board);
         }
         __syncthreads();                    // the image and `red` are reused by the next tile
     }
@@ -468,4 +505,43 @@ extern "C" int cz_heads_tail_wdl(const float* policy_feat, int n_policy_feat, co
         else launch_fc<FC_WDL, 360>(dtype, blocks, st, a, n_boards, n_dev);
     }
     return nn_launched("cz_heads_tail_wdl");
+}
+
+extern "C" int cz_heads_tail_ml(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
+                                int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed,
+                                const float* bias1, int n_hidden, int value_outputs, const float* w2, const float* b2,
+                                float* policy, float* value, float* wdl, float* moves_left, float* stats_scratch, int n_boards,
+                                int dtype, int normalize, const int32_t* n_dev, void* stream)
+{
+    if (!policy_feat || !wp_packed || !bias_p || !value_feat || !w1_packed || !bias1 || !w2 || !b2 || !policy || !value ||
+        !moves_left || !stats_scratch || n_boards < 0 || (dtype != CZ_BF16 && dtype != CZ_F16) || n_labels < 2 || (n_labels & 1) ||
+        n_hidden < 1 || n_policy_feat < 1 || (n_policy_feat != 180 && n_policy_feat != 360) ||
+        (n_value_feat != 180 && n_value_feat != 360) || (value_outputs != 1 && value_outputs != 3) || (wdl && value_outputs != 3))
+        return nn_error(CZ_ERR_ARG, "cz_heads_tail_ml: bad argument (n_labels even; 180 or 360 features per head: 2 or 4 filters x 90 squares; "
+                                    "dtype of the packed pairs: CZ_BF16 or CZ_F16; value_outputs 1 or 3; moves_left is required; "
+                                    "wdl only with value_outputs 3, may be NULL)");
+    if (n_boards == 0) return CZ_OK;
+    const int n_cu = nn_cu_count("cz_heads_tail_ml");
+    if (n_cu < 0) return CZ_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    const int row_tiles = (n_boards + TILE_ROWS - 1) / TILE_ROWS;
+    const unsigned blocks = nn_grid(row_tiles, 2 * n_cu);
+    launch_policy_half(policy_feat, n_policy_feat, wp_packed, bias_p, n_labels, policy, stats_scratch, n_boards, dtype, normalize,
+                       n_dev, n_cu, blocks, st);
+    {
+        FcArgsMl a{};
+        a.feat = value_feat; a.wp = w1_packed; a.bias = bias1; a.F = n_value_feat;
+        a.ksteps = (n_value_feat + 15) / 16; a.n_out = n_hidden; a.n_tiles = (n_hidden + 31) / 32;
+        a.w2 = w2; a.b2 = b2[0]; a.value = value;
+        a.w2_ml = w2 + (size_t)value_outputs * n_hidden; a.b2_ml = b2[value_outputs]; a.moves_left = moves_left;
+        if (value_outputs == 3) {
+            a.b2_draw = b2[1]; a.b2_loss = b2[2]; a.wdl = wdl;
+            if (n_value_feat == 180) launch_fc<FC_WDL_ML, 180>(dtype, blocks, st, a, n_boards, n_dev);
+            else launch_fc<FC_WDL_ML, 360>(dtype, blocks, st, a, n_boards, n_dev);
+        } else {
+            if (n_value_feat == 180) launch_fc<FC_VALUE_ML, 180>(dtype, blocks, st, a, n_boards, n_dev);
+            else launch_fc<FC_VALUE_ML, 360>(dtype, blocks, st, a, n_boards, n_dev);
+        }
+    }
+    return nn_launched("cz_heads_tail_ml");
 }

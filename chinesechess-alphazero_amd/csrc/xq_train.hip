@@ -8,6 +8,8 @@
 //                        played move's one-hot or the record's visit counts, squared value error, and their gradients;
 //                        <WDL = true> (cz_policy_wdl_loss): the same policy half, and for a win / draw / loss value head the
 //                        clipped cross-entropy of its three logits against the class of z, with its gradient
+//   k_moves_left_loss    one thread per minibatch row (cz_moves_left_loss, run.py opt --moves-left): Huber loss of softplus(x)
+//                        against the row's plies-to-the-end target in units of 32 plies, and its gradient
 //
 // Mirror augmentation (run.py opt --augment mirror): both per-step kernels take an optional per-row flag array.  A flagged
 // row is the left-right mirror image of its position (file x <-> 8 - x, a symmetry of the rules): its board is mirrored in
@@ -279,8 +281,49 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
     }
 }
 
+// The moves-left output's loss (cz_moves_left_loss): one thread per minibatch row, nothing shared between rows.  x is the
+// head's raw output; its meaning is unit * softplus(x) plies, so the loss is taken in units: Huber of softplus(x) - left / unit.
+__global__ __launch_bounds__(256) void k_moves_left_loss(
+    const float* __restrict__ x, const int32_t* __restrict__ idx, int n_rows, int n_pos, const int32_t* __restrict__ left,
+    const float* __restrict__ row_w, float unit, float delta, float w_m, float* __restrict__ loss, float* __restrict__ grad_x)
+{
+    const float c = w_m * (1.0f / (float)n_rows);
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += gridDim.x * blockDim.x) {
+        const int i = idx[r];
+        if (i < 0 || i >= n_pos) {                       // out-of-range index: zero loss and gradient, nothing read
+            loss[r] = 0.f;
+            grad_x[r] = 0.f;
+            continue;
+        }
+        const float xr = x[r];
+        const float en = expf(-fabsf(xr));               // in (0, 1]: neither form below can overflow
+        const float y = fmaxf(xr, 0.f) + log1pf(en);     // softplus(x)
+        const float sg = xr >= 0.f ? 1.f / (1.f + en) : en / (1.f + en);      // sigmoid(x) = d softplus / dx
+        const float d = y - (float)left[i] / unit;
+        const float ad = fabsf(d);
+        loss[r] = ad <= delta ? 0.5f * d * d : delta * (ad - 0.5f * delta);
+        const float cr = row_w != nullptr ? __fmul_rn(c, row_w[i]) : c;
+        grad_x[r] = cr * (fminf(fmaxf(d, -delta), delta) * sg);
+    }
+}
+
 // ---- C-ABI ----------------------------------------------------------------------------
 extern "C" {
+
+int cz_moves_left_loss(const float* x, const int32_t* idx, int n_rows, int n_pos, const int32_t* left, const float* row_w,
+                       float unit, float delta, float w_m, float* loss, float* grad_x, void* stream)
+{
+    if (n_rows == 0) return CZ_OK;
+    if (n_rows < 0 || n_pos < 0 || !x || !idx || !loss || !grad_x || (n_pos > 0 && !left) || !(unit > 0.f) || !(delta > 0.f) ||
+        !(unit < INFINITY) || !(delta < INFINITY) || !(w_m >= 0.f) || !(w_m < INFINITY)) {
+        czi_set_error("cz_moves_left_loss: bad argument (unit and delta positive and finite, w_m >= 0 and finite)");
+        return CZ_ERR_ARG;
+    }
+    const int blocks = (n_rows + 255) / 256;
+    hipLaunchKernelGGL(k_moves_left_loss, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, (hipStream_t)stream, x, idx, n_rows,
+                       n_pos, left, row_w, unit, delta, w_m, loss, grad_x);
+    return launch_status("cz_moves_left_loss: launch failed");
+}
 
 int cz_replay_games(const int8_t* init_boards, const uint16_t* labels, const int32_t* offsets, int n_games, int n_pos,
                     int8_t* boards, int32_t* prev, int32_t* bad_ply, void* stream)

@@ -1113,6 +1113,27 @@ int cz_heads_tail_wdl(const float* policy_feat, int n_policy_feat, const void* w
                       int n_hidden, const float* w2, float b2_win, float b2_draw, float b2_loss, float* policy,
                       float* value, float* wdl, float* stats_scratch, int n_boards, int dtype, int normalize,
                       const int32_t* n_dev, void* stream);
+/* The tail of a network whose value head has a moves-left output beside its own end (CChessNet(moves_left=True)): one more
+ * Dense(1) on the same ReLU'd hidden layer, predicting how many plies the game still has to run.  The model is lc0's
+ * moves-left head (a head of its own -- 1x1 convolution, a dense hidden layer, Dense(1) + ReLU -- trained with a Huber
+ * loss on a scaled ply count); the simplification here is that it shares the value head's convolution and hidden layer, so
+ * that it costs one more dot product per hidden unit and no launch.
+ * The arguments of cz_heads_tail_wdl with value_outputs (1: the scalar tanh head, 3: win / draw / loss),
+ * w2[value_outputs + 1][n_hidden] fp32 on the device with the moves-left row last, b2[value_outputs + 1] the matching biases
+ * (HOST memory, read before the call returns), and
+ *   moves_left[n] = hidden . w2[value_outputs] + b2[value_outputs]      (required)
+ * the RAW output x in fp32: its meaning, CZ_MOVES_LEFT_UNIT * softplus(x) plies, is the reader's to apply -- the tail keeps
+ * it a plain dot product, whose error has a derivable bound (tests/moves_left_check.py).  wdl is allowed with value_outputs
+ * 3 only and may be NULL.  value, and wdl where given, are bit-identical to cz_heads_tail / cz_heads_tail_wdl on the first
+ * value_outputs rows of w2 and b2: the extra dot is independent and every existing sum keeps its order.  The policy half
+ * is cz_heads_tail's launch; refusals, n_dev (rows beyond the count are neither computed nor written, in any output),
+ * dtype, normalize as there. */
+#define CZ_MOVES_LEFT_UNIT 32.0f
+int cz_heads_tail_ml(const float* policy_feat, int n_policy_feat, const void* wp_packed, const float* bias_p,
+                     int n_labels, const float* value_feat, int n_value_feat, const void* w1_packed, const float* bias1,
+                     int n_hidden, int value_outputs, const float* w2, const float* b2, float* policy, float* value,
+                     float* wdl, float* moves_left, float* stats_scratch, int n_boards, int dtype, int normalize,
+                     const int32_t* n_dev, void* stream);
 /* number of 2-byte elements of a packed dense layer (0 = bad argument); HOST: w[n_out][n_in] fp32 -> (hi, lo) pairs of
  * `dtype` (CZ_BF16 / CZ_F16) in fragment order */
 size_t cz_fc_packed_elems(int n_out, int n_in);
@@ -1228,6 +1249,22 @@ int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const 
                        const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
                        float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
                        void* stream);
+/* The loss of the moves-left output (run.py opt --moves-left W), a kernel of its own beside the policy / value loss: one
+ * thread per row.  x[n_rows]: the head's raw output; left[n_pos] (int32): a position's target, the number of record items
+ * from its own to the end of its game, inclusive (the last recorded position has 1); idx as above; row_w[n_pos] or NULL
+ * (= 1): the surprise weights.  unit: plies per unit (CZ_MOVES_LEFT_UNIT), delta: the Huber threshold in units
+ * (CZ_MOVES_LEFT_DELTA, lc0's ratio of delta to scale), both positive and finite; w_m >= 0 the loss weight.  Row r with
+ * i = idx[r], all in fp32:
+ *   y = max(x, 0) + log1p(exp(-|x|))                         softplus(x), stable for every finite x
+ *   d = y - left[i] / unit
+ *   loss[r]   = d^2 / 2 where |d| <= delta, else delta (|d| - delta / 2)       unweighted
+ *   grad_x[r] = (w_m / n_rows) clamp(d, -delta, delta) sigmoid(x), sigmoid(x) = 1 / (1 + e) for x >= 0 and e / (1 + e)
+ *               otherwise, e = exp(-|x|); the factor w_m / n_rows is multiplied by row_w[i] first (one rounded product)
+ * the gradient of w_m mean(row_w loss).  An index outside [0, n_pos) gives zeros.  Rows are independent and nothing is
+ * accumulated across them: two launches on the same inputs give the same bits. */
+#define CZ_MOVES_LEFT_DELTA 0.5f
+int cz_moves_left_loss(const float* x, const int32_t* idx, int n_rows, int n_pos, const int32_t* left, const float* row_w,
+                       float unit, float delta, float w_m, float* loss, float* grad_x, void* stream);
 
 #ifdef __cplusplus
 }
