@@ -147,6 +147,9 @@ def declare(L):
         "cz_search_set_kld_gain": [vp, d, i32, vp],
         "cz_search_set_smart_pruning": [vp, i32, vp],
         "cz_search_root_kld": [vp, vp, vp, vp],
+        "cz_search_set_moves_left": [vp, d, d, vp, vp],
+        "cz_search_node_moves_left": [vp, vp, i32, vp, vp, vp, vp, vp],
+        "cz_moves_left_quanta": [vp, vp, i32, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -258,6 +261,8 @@ class Search:
         self.solver = False                    # set_solver(): forced wins and losses are proven in the tree
         self.kld_gain, self.kld_interval = 0.0, 100   # set_kld_gain(): a ply ends once its root distribution stops moving
         self.smart_pruning = False             # set_smart_pruning(): a tau = 0 ply ends once its leader cannot be caught
+        self.moves_left_slope, self.moves_left_cap = 0.0, 0.0345   # set_moves_left(): the moves-left utility, slope 0 = off
+        self.moves_left_x = None               # ... and its rows: [slots] float32 beside policy / value, the network's raw x
 
     # -- lifetime --
     def close(self):
@@ -455,6 +460,43 @@ class Search:
             raise _native.NativeError("this libczero.so has no MCTS solver (cz_search_set_solver)")
         _native.check(self.L.cz_search_set_solver(self.h, 1 if on else 0, self._stream()), "cz_search_set_solver")
         self.solver = bool(on)
+
+    def set_moves_left(self, slope=0.0, cap=0.0345):
+        """Moves-left utility (cz_search_set_moves_left; include/czero.h has the rule): with slope > 0 the selection adds
+        u_m = -+ clamp(slope * (M_edge - M_node), cap) * f(|q|) to an edge's score, so that a winning side prefers the shorter
+        game and a losing side the longer one.  The caller writes the network's raw moves-left output of the rows it
+        evaluates to self.moves_left_x (float32 [slots], indexed as self.value is; allocated here, once).  slope 0
+        switches it off.  Switching on or off resets the trees.  Refused beside the Gumbel search, the solver, the stop
+        rules, the evaluation cache and a script, and they beside it.  Call it before start_selfplay() / set_roots() and
+        before a graph capture."""
+        import torch
+        if not hasattr(self.L, "cz_search_set_moves_left"):
+            raise _native.NativeError("this libczero.so has no moves-left utility (cz_search_set_moves_left)")
+        if slope > 0.0 and self.moves_left_x is None:
+            self.moves_left_x = torch.zeros((self.slots,), dtype=torch.float32, device=self.device)
+        ptr = C.c_void_p(self.moves_left_x.data_ptr()) if self.moves_left_x is not None else None
+        _native.check(self.L.cz_search_set_moves_left(self.h, float(slope), float(cap), ptr, self._stream()),
+                      "cz_search_set_moves_left")
+        self.moves_left_slope, self.moves_left_cap = float(slope), float(cap)
+
+    def node_moves_left(self, path=None):
+        """The moves-left records of the node node_stats(path) reports (cz_search_node_moves_left): dict(ksum int64 [G, 128]
+        and mn int32 [G, 128] per edge -- the sum of the backed-up m in quanta of 1/16 ply and how many --, k_net int32
+        [G], the node's own prediction in quanta, counts uint8 [G]).  With the option off everything is 0."""
+        import torch
+        G, M = self.G, _native.MAXMOVES
+        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        ksum = torch.empty((G, M), dtype=torch.int64, device=self.device)
+        mn = torch.empty((G, M), dtype=torch.int32, device=self.device)
+        k_net = torch.empty((G,), dtype=torch.int32, device=self.device)
+        counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
+        _native.check(self.L.cz_search_node_moves_left(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
+                                                       pa.shape[1], C.c_void_p(ksum.data_ptr()), C.c_void_p(mn.data_ptr()),
+                                                       C.c_void_p(k_net.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                       self._stream()), "cz_search_node_moves_left")
+        return dict(ksum=ksum.cpu().numpy(), mn=mn.cpu().numpy(), k_net=k_net.cpu().numpy(), counts=counts.cpu().numpy())
 
     def node_proof(self, path=None):
         """The proof state of the node node_stats(path) reports (cz_search_node_proof): dict(status int8 [G] -- PROOF_OPEN /
@@ -787,7 +829,8 @@ class Search:
         return int(out[0]), self._rows[:int(out[1])].long()
 
     def run_until_idle(self, evaluate, max_rounds=1000000):
-        """external mode: rounds until every search is complete.  evaluate(planes) -> (policy, value)."""
+        """external mode: rounds until every search is complete.  evaluate(planes) -> (policy, value), or (policy, value,
+        moves-left x) while set_moves_left() is on."""
         rounds = 0
         while rounds < max_rounds:
             self.round()
@@ -796,9 +839,11 @@ class Search:
             if pending == 0:
                 return rounds
             if rows.numel():                       # only the queue rows that carry a new leaf
-                p, v = evaluate(self.planes.index_select(0, rows))
-                self.policy.index_copy_(0, rows, p.float())
-                self.value.index_copy_(0, rows, v.float())
+                out = evaluate(self.planes.index_select(0, rows))
+                self.policy.index_copy_(0, rows, out[0].float())
+                self.value.index_copy_(0, rows, out[1].float())
+                if len(out) > 2 and self.moves_left_x is not None:
+                    self.moves_left_x.index_copy_(0, rows, out[2].float())
         raise RuntimeError("search did not finish")
 
     def stop(self):

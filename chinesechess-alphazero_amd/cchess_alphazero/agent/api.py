@@ -26,8 +26,13 @@ class DevicePipe:
         self.api = api
         self._replies = []
 
-    def evaluate_device(self, planes):
-        return self.api.predict_device(planes)
+    def evaluate_device(self, planes, moves_left=False):
+        return self.api.predict_device(planes, moves_left=moves_left)
+
+    @property
+    def moves_left_head(self):
+        """The network behind the pipe has the moves-left output (what the moves-left utility of the search needs)."""
+        return bool(getattr(self.api.net, "moves_left_head", False))
 
     # -- reference pipe protocol --
     def send(self, data):
@@ -61,12 +66,18 @@ class CChessModelAPI:
         # (the tower arithmetic is a request: it is measured against the float64 network on calibration positions and
         #  replaced by a more exact one when these weights need it -- agent/model.py guarded_inference_net)
         self.net = guarded_inference_net(agent_model.model, dtype, trunk=trunk, arith=self._arith, device=self.device,
-                                         guard=self._guard)
+                                         guard=self._guard, moves_left=self._guard_moves_left())
         self._dtype, self._trunk = dtype, trunk
         self.done = False
         self.need_reload = True
         self.reload_interval = 600.0             # seconds between checks of the best-weight file (api.py:42-44)
         self._last_check = time()
+
+    def _guard_moves_left(self):
+        """The load-time guard measures the moves-left output too while the configuration's moves-left utility is on and the
+        model has the output (a model without it is refused where the search is built)."""
+        ec = getattr(self.config, "engine", None)
+        return bool(getattr(ec, "moves_left_slope", 0.0) > 0.0 and self.agent_model.model.moves_left_head)
 
     def start(self, need_reload=True):
         self.need_reload = need_reload
@@ -82,7 +93,8 @@ class CChessModelAPI:
                     if self.agent_model.model.cfg["cnn_filter_num"] not in (32, 128, 192, 256):
                         trunk = "library"
                     self.net = guarded_inference_net(self.agent_model.model, self._dtype, trunk=trunk, arith=self._arith,
-                                                     device=self.device, guard=self._guard)
+                                                     device=self.device, guard=self._guard,
+                                                     moves_left=self._guard_moves_left())
                     return True
         except Exception as e:                    # a half-written file: keep serving the old weights
             logger.error(e)
@@ -94,10 +106,15 @@ class CChessModelAPI:
         return pipe
 
     @torch.no_grad()
-    def predict_device(self, planes):
+    def predict_device(self, planes, moves_left=False):
+        """(policy, value) of the planes; moves_left=True (a network with the output): a third tensor, its raw x [n]."""
         if self.need_reload and time() - self._last_check > self.reload_interval:
             self._last_check = time()
             self.try_reload_model()
+        if moves_left:
+            x = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
+            p, v = self.net(planes, moves_left=x)
+            return p, v, x
         return self.net(planes)
 
     def close(self):

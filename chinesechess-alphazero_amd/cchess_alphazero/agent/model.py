@@ -741,7 +741,8 @@ class InferenceNet(nn.Module):
         value P(win) - P(loss) the search reads.
         moves_left (fp32 [n], networks with the moves-left output only): receives that output's raw x per row
         (moves_left_plies gives its plies); the tail launch is then cz_heads_tail_ml, and policy and value keep the bits of
-        a forward without it.  Nothing in the search reads it yet, so the load-time guard does not measure it."""
+        a forward without it.  The search reads it while its moves-left utility is on (Search.set_moves_left), and the
+        load-time guard then measures it (guarded_inference_net(moves_left=True))."""
         if wdl is not None and not self.wdl_head:
             raise RuntimeError("wdl=: this network has the scalar value head")
         if moves_left is not None and not self.moves_left_head:
@@ -840,9 +841,13 @@ CALIBRATION_POSITIONS = 256
 def within_guard(m, tol=GUARD_TOL, logit_tol=LOGIT_TOL):
     """The guard's acceptance test on measure_against_reference's figures: finite, policy (full softmax) and value within
     `tol` on the calibration positions, the logit deviation within `logit_tol` (=> renormalised priors within 1e-4), and --
-    where the legal moves of the positions are known -- the legal-renormalised priors themselves within `tol`."""
+    where the legal moves of the positions are known -- the legal-renormalised priors themselves within `tol`.  Where the
+    raw moves-left output was measured (the search's moves-left utility is on) it is held to `logit_tol` as well: like a
+    logit it is a pre-activation, and 512 * softplus has slope <= 512, so 2e-4 of x moves a leaf's prediction by at most a
+    tenth of a quantum."""
     return bool(m["finite"] and m["policy_max_abs"] <= tol and m["value_max_abs"] <= tol and
-                m["logit_max_abs"] <= logit_tol and m.get("legal_prior_max_abs", 0.0) <= tol)
+                m["logit_max_abs"] <= logit_tol and m.get("legal_prior_max_abs", 0.0) <= tol and
+                m.get("moves_left_max_abs", 0.0) <= logit_tol)
 
 
 def calibration_planes(n=CALIBRATION_POSITIONS, input_depth=14, device=None, seed=20260924, with_legal=False):
@@ -893,12 +898,13 @@ def calibration_planes(n=CALIBRATION_POSITIONS, input_depth=14, device=None, see
 
 
 @torch.no_grad()
-def reference_forward_f64(net: CChessNet, planes, with_activations=False, with_wdl=False):
+def reference_forward_f64(net: CChessNet, planes, with_activations=False, with_wdl=False, with_moves_left=False):
     """The reference network (agent/model.py:32-83; BatchNorm in inference mode as Keras predict_on_batch runs it) in float64
     on the device of `planes`: (policy [n, 2086], value [n], logits) and, on request, two more entries: max |activation|
     of every tower tensor (input layer, each block's intermediate and output) and the [1 %, 50 %] quantiles of its nonzero
     values.  with_wdl (a win / draw / loss net): one further entry at the end, the value head's probabilities [n, 3]; the
-    value is P(win) - P(loss) either way."""
+    value is P(win) - P(loss) either way.  with_moves_left (a net with the output): the last entry is the raw moves-left
+    output x [n]."""
     import copy
     dev = planes.device
     ref = copy.deepcopy(net).eval().double().to(dev)
@@ -935,7 +941,8 @@ def reference_forward_f64(net: CChessNet, planes, with_activations=False, with_w
     p = F.relu(bn(ref.policy_bn, conv(ref.policy_conv, x)))
     logits = ref.policy_out(p.flatten(1))
     v = F.relu(bn(ref.value_bn, conv(ref.value_conv, x)))
-    v = ref.value_out(F.relu(ref.value_dense(v.flatten(1))))
+    hidden = F.relu(ref.value_dense(v.flatten(1)))
+    v = ref.value_out(hidden)
     w = None
     if ref.wdl_head:                                # the value the search reads: P(win) - P(loss)
         w = F.softmax(v, dim=1)
@@ -945,7 +952,11 @@ def reference_forward_f64(net: CChessNet, planes, with_activations=False, with_w
     out = (F.softmax(logits, dim=1), v, logits)
     if with_activations:
         out = out + (acts, small)
-    return out + (w,) if with_wdl else out
+    if with_wdl:
+        out = out + (w,)
+    if with_moves_left:
+        out = out + (ref.moves_left_out(hidden).squeeze(1),)
+    return out
 
 
 def legal_priors(p, legal):
@@ -955,10 +966,17 @@ def legal_priors(p, legal):
     return q / q.sum(1, keepdim=True).clamp_min(1e-300)
 
 
-def measure_against_reference(inf, ref_out, planes, legal=None):
+def measure_against_reference(inf, ref_out, planes, legal=None, moves_left_ref=None):
     """Max deviations of an InferenceNet from reference_forward_f64's outputs on the same planes.  legal (bool [n, 2086]):
-    also legal_prior_max_abs, the deviation of the priors renormalised over each position's legal moves."""
-    p, v = inf(planes)
+    also legal_prior_max_abs, the deviation of the priors renormalised over each position's legal moves.  moves_left_ref
+    (float64 [n], reference_forward_f64(with_moves_left=True)'s last entry; given while the search's moves-left utility is
+    on): also moves_left_max_abs, the deviation of the raw moves-left output, taken from the same forward."""
+    x = None
+    if moves_left_ref is not None:
+        x = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
+        p, v = inf(planes, moves_left=x)
+    else:
+        p, v = inf(planes)
     p, v = p.double(), v.double()
     pr, vr, lr = ref_out[:3]
     # the logit deviation up to the softmax's free constant: log p - log p_ref where both are representable
@@ -968,6 +986,9 @@ def measure_against_reference(inf, ref_out, planes, legal=None):
     out = dict(policy_max_abs=float((p - pr).abs().max()), value_max_abs=float((v - vr).abs().max()),
                logit_max_abs=float(torch.where(ok, dl, torch.zeros_like(dl)).abs().max()),
                finite=bool(torch.isfinite(p).all() and torch.isfinite(v).all()))
+    if x is not None:
+        out["moves_left_max_abs"] = float((x.double() - moves_left_ref.double()).abs().max())
+        out["finite"] = bool(out["finite"] and torch.isfinite(x).all())
     lg = None
     if getattr(inf, "supports_logits", lambda: False)():
         # the raw logit rows the engine's queue carries: the deviation over ALL labels, centred on its mean
@@ -1095,15 +1116,19 @@ def next_more_exact(name, n_blocks):
 
 
 def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", arith=None, device=None, tol=GUARD_TOL,
-                          planes=None, guard=None):
+                          planes=None, guard=None, moves_left=False):
     """InferenceNet(net, ...) on `device` with the tower arithmetic CHECKED: the requested arithmetic is measured against
     the float64 network on calibration positions and replaced by the next more exact one while policy or value deviate by
     more than `tol` (c8 -> c8>N with fewer and fewer c8 blocks -> f16x3 -> bf16x3 -> the fp32 library trunk).  The result
     carries  .arith_requested, .arith_effective, .calibration (every candidate's measurements, the tower's activation
     ranges, the c8 image's predicted saturation / underflow counts).  guard=False (or CZ_ARITH_GUARD=0) skips the
     candidate comparison -- tests of a specific kernel path want exactly what they ask for.  (A c6 request still runs the
-    float64 calibration pass then: its images' exponents come from the measured activation ranges.)"""
+    float64 calibration pass then: its images' exponents come from the measured activation ranges.)
+    moves_left (the search's moves-left utility is on; a net with the output): the raw moves-left output is measured against
+    float64 too and has to stay within LOGIT_TOL (within_guard); off, the guard measures what it measured without it."""
     from cchess_alphazero import _native
+    if moves_left and not net.moves_left_head:
+        raise RuntimeError("moves_left=True: this network has no moves-left output (CChessNet(moves_left=True))")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     requested = arith or os.environ.get("CZ_TOWER_ARITH") or "bf16x3"
     if guard is None:
@@ -1126,7 +1151,7 @@ def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", ari
         legal = None
         if planes is None:
             planes, legal = calibration_planes(CALIBRATION_POSITIONS, net.cfg["input_depth"], dev, with_legal=True)
-        ref = reference_forward_f64(net, planes, with_activations=True)
+        ref = reference_forward_f64(net, planes, with_activations=True, with_moves_left=moves_left)
         acts = ref[3]
         report = dict(tol=tol, logit_tol=LOGIT_TOL, positions=int(planes.shape[0]),
                       max_policy_probability=float(ref[0].max()),
@@ -1168,7 +1193,7 @@ def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", ari
             if cand is None:
                 cand = InferenceNet(net, dtype, trunk=trunk, arith=name, act_shift=shift,
                                     act_exps=exps if name.startswith("c6") else None).to(dev)
-            m = measure_against_reference(cand, ref, planes, legal)
+            m = measure_against_reference(cand, ref, planes, legal, moves_left_ref=ref[-1] if moves_left else None)
             m["arith"] = name
             report["candidates"].append(m)
             if within_guard(m, tol):

@@ -38,9 +38,17 @@ class VisitState:
         self.w = 0
 
 
+class MovesLeftUnavailable(ValueError):
+    """The moves-left utility was asked for and the network behind the pipe has no moves-left output."""
+
+
+MOVES_LEFT_REFUSAL = search_options.MOVES_LEFT_REFUSAL
+
+
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
-                 debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None):
+                 debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None,
+                 moves_left_slope=None, moves_left_cap=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -71,7 +79,15 @@ class CChessPlayer:
         # MCTS solver and unreachable-lead stop (search_options.py): None = config.engine's value, off by default.  After
         # action() self.proof is the root's (status, d) -- (0, 0) while the solver is off or nothing is proven.
         opts = search_options.resolve(config, solver=solver, smart_pruning=smart_pruning)
-        search_options.check(opts)
+        # moves-left utility (search_options.py MOVES_LEFT_EXCLUDES): None = config.engine's value, off by default; the pipe's
+        # network must have the output (MovesLeftUnavailable otherwise, before a device is asked for)
+        ec = getattr(config, "engine", None)
+        self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
+        self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
+        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
+        search_options.check(opts, moves_left=self.moves_left)
+        if self.moves_left and not getattr(pipes, "moves_left_head", False):
+            raise MovesLeftUnavailable(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         vars(self).update(opts)                # self.solver, self.smart_pruning
         pc = self.play_config
         # simulation count from play_config, lock-step batch from config.play (player.py:155-174)
@@ -88,9 +104,15 @@ class CChessPlayer:
         self._torch = torch
         self.proof = (0, 0)
         search_options.apply(self._search, opts)
+        if self.moves_left:
+            self._search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
 
     # -- network access: device fast path, or the reference's pipe protocol --
-    def _evaluate(self, planes):
+    def _evaluate(self, planes, moves_left=False):
+        """(policy, value) of the planes; moves_left (the utility is on: a device pipe whose network has the output): a third
+        tensor, the raw moves-left output."""
+        if moves_left:
+            return self.pipe.evaluate_device(planes, moves_left=True)
         if hasattr(self.pipe, "evaluate_device"):
             return self.pipe.evaluate_device(planes)
         self.pipe.send(list(planes.float().cpu().numpy()))
@@ -235,9 +257,11 @@ class CChessPlayer:
                 if pending == 0:
                     break
                 if rows.numel():                               # exactly the positions the reference would send (:112-120)
-                    p, v = self._evaluate(s.planes.index_select(0, rows))
+                    p, v, *x = self._evaluate(s.planes.index_select(0, rows), moves_left=self.moves_left)
                     s.policy.index_copy_(0, rows, p.float())
                     s.value.index_copy_(0, rows, v.float())
+                    if x:
+                        s.moves_left_x.index_copy_(0, rows, x[0].float())
                 if self.job_done and not stopped:
                     s.stop()                                   # the next round backs up what is in flight
                     stopped = True

@@ -102,6 +102,9 @@ class EngineConfig(_Section):
                          # follows the largest one whose false-positive share stays within P, once at least
                          # resign_audit_min_events games would have resigned there (None = ceil(5 / P))
                          resign_audit=False, resign_fp_target=0.0, resign_audit_min_events=None,
+                         # moves-left utility (run.py self / eval --moves-left-slope S --moves-left-cap C, the UCI options
+                         # MovesLeftSlope / MovesLeftCap): off at slope 0; needs a model with the moves-left output
+                         **search_options.MOVES_LEFT_DEFAULTS,
                          # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
                          **search_options.DEFAULTS)
 

@@ -23,6 +23,7 @@ from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE, array_to_state
 from cchess_alphazero.lib.data_helper import record_item
+from cchess_alphazero.search_options import MOVES_LEFT_REFUSAL
 
 logger = getLogger(__name__)
 
@@ -44,7 +45,8 @@ class SelfPlayEngine:
                  use_history=False, trunk=None, record_visits=None, book=None, book_rate=None, fast_sims=None,
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
-                 kld_gain=None, kld_interval=None, resign_audit=None, script=None):
+                 kld_gain=None, kld_interval=None, resign_audit=None, script=None, moves_left_slope=None,
+                 moves_left_cap=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -68,13 +70,25 @@ class SelfPlayEngine:
         z): game id i replays script i, every ply searched as a self-play ply is and only the move taken from the script
         (Search.set_script).  Needs record_visits; refused beside a book, the resignation audit and what
         search_options.SCRIPT_EXCLUDES lists.  start(0): slot g walks scripts g, g + G, ... and goes idle after its last;
-        drain() reports `script_index` and `script_mismatch`."""
+        drain() reports `script_index` and `script_mismatch`.
+        moves_left_slope, moves_left_cap (None = config.engine's values; slope 0 = off): the moves-left utility of the search
+        (Search.set_moves_left).  Like the script it is no row of search_options.py's table; check(moves_left=True) refuses
+        what search_options.MOVES_LEFT_EXCLUDES lists, and a script.  The network must have the moves-left output (`run.py
+        opt --moves-left`; a ValueError otherwise, here and in set_network); every forward then also fills
+        search.moves_left_x (the tail launch is cz_heads_tail_ml), and the load-time guard and audit_network measure that
+        output too.  An evaluator callable returns (policy, value, x)."""
+        ec_ = getattr(config, "engine", None)
+        self.moves_left_slope = float(getattr(ec_, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
+        self.moves_left_cap = float(getattr(ec_, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
+        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
             gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
             solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
-        search_options.check(opts, history=use_history, script=script is not None)
+        search_options.check(opts, history=use_history, script=script is not None, moves_left=self.moves_left)
+        if self.moves_left and evaluator is None and net is not None and not net.moves_left_head:
+            raise ValueError(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         self.resign_audit = bool(getattr(getattr(config, "engine", None), "resign_audit", False)
                                  if resign_audit is None else resign_audit)
         if self.resign_audit and not opts["record_visits"]:
@@ -97,6 +111,8 @@ class SelfPlayEngine:
             if net is None:
                 torch.manual_seed(0)
                 net = CChessNet.from_model_config(config.model)
+                if self.moves_left and not net.moves_left_head:
+                    raise ValueError(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
             self.model_cfg = net.cfg
             if trunk is None:
                 trunk = getattr(getattr(config, "engine", None), "net_trunk", "mfma")
@@ -142,6 +158,8 @@ class SelfPlayEngine:
             self.search.set_book(book_boards(self.book), self.book_rate)
         # every other option that is on: likewise before start() and before a graph capture
         search_options.apply(self.search, opts, skip=("eval_cache",))
+        if self.moves_left:                    # (its rows, search.moves_left_x, are allocated here: fixed for a graph capture)
+            self.search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
         self.script = script
         if script is not None:                 # last: the library checks it against everything that is on
             self.search.set_script(*script)
@@ -152,7 +170,7 @@ class SelfPlayEngine:
         engine changes here: a guard that raises (out of memory, a damaged weight file) leaves the games on the old network."""
         guard = getattr(getattr(self.config, "engine", None), "arith_guard", True)
         return guarded_inference_net(net, self.dtype, trunk=self.trunk, arith=self.arith, device=self.device,
-                                     guard=None if guard else False)
+                                     guard=None if guard else False, moves_left=self.moves_left)
 
     def _install(self, net, built=None):
         self.net = built if built is not None else self._build_net(net)
@@ -189,10 +207,13 @@ class SelfPlayEngine:
             raise RuntimeError("the engine was built on an evaluator callable, not on a network")
         # (the value head's end is not part of what must match: each InferenceNet carries its own tail and hands the search
         #  one scalar per leaf, so a scalar net may follow a win / draw / loss one and the other way round)
-        #  (nor is the moves-left output, which the engine does not read)
+        #  (nor is the moves-left output -- unless the moves-left utility reads it: then the new network needs it too, and is
+        #  refused before anything is touched, the way a guard failure is: the games stay on the old network)
         same = lambda cfg: {k: v for k, v in cfg.items() if k not in ("value_outputs", "moves_left")}
         if same(net.cfg) != same(self.model_cfg):
             raise ValueError(f"hot reload: topology changed ({self.model_cfg} -> {net.cfg})")
+        if self.moves_left and not net.moves_left_head:
+            raise ValueError("hot reload: " + MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         torch.cuda.synchronize(self.device)
         built = self._build_net(net)                           # may raise: nothing has been touched yet
         had_graph = self._graph is not None
@@ -251,7 +272,8 @@ class SelfPlayEngine:
         planes = planes[planes.flatten(1).ne(0).any(1)].contiguous()          # (a slot no leaf was ever written to is an empty board)
         if planes.shape[0] == 0:
             return None
-        m = measure_against_reference(self.net, reference_forward_f64(self._ref_net, planes), planes)
+        ref = reference_forward_f64(self._ref_net, planes, with_moves_left=self.moves_left)
+        m = measure_against_reference(self.net, ref, planes, moves_left_ref=ref[-1] if self.moves_left else None)
         m["ok"] = within_guard(m)
         m["arith"] = self.net_arith_effective
         m["positions"] = int(planes.shape[0])
@@ -311,13 +333,17 @@ class SelfPlayEngine:
     def _forward(self):
         s = self.search
         if self.evaluator is not None:
-            p, v = self.evaluator(s.planes)
+            p, v, *x = self.evaluator(s.planes)
+            if self.moves_left:
+                s.moves_left_x.copy_(x[0])
         else:
             out = (s.policy, s.value)
+            ml = s.moves_left_x if self.moves_left else None   # (the rows of `value`: by slot, or by compact row)
             if self.compact:
-                p, v = self.net(s.planes, rows=s.q_rows, count=s.q_count, out=out, logits=self.policy_logits, masks=s.masks)
+                p, v = self.net(s.planes, rows=s.q_rows, count=s.q_count, out=out, logits=self.policy_logits, masks=s.masks,
+                                moves_left=ml)
             else:
-                p, v = self.net(s.planes, out=out, logits=self.policy_logits, masks=s.masks)
+                p, v = self.net(s.planes, out=out, logits=self.policy_logits, masks=s.masks, moves_left=ml)
             if p is s.policy:                                  # written in place (the hand-written network path)
                 return
         s.policy.copy_(p)

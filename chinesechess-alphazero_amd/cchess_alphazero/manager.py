@@ -69,6 +69,13 @@ _FLAGS = [
                                "predicting the plies until the game ends) with the loss weight W (finite, >= 0; 0 = off); a "
                                "new model (--new, or no best model yet) is built with the output, a best model without it "
                                "is refused")),
+    ("--moves-left-slope", dict(type=float, default=0.0, metavar="S",
+                                help="(self, eval) moves-left utility: the search adds -+ clamp(S * (an edge's mean plies to the "
+                                     "end - the node's), cap) * f(|q|) to an edge's score, so that a winning side prefers the "
+                                     "shorter game and a losing side the longer one; needs a model with the moves-left output "
+                                     "(`run.py opt --moves-left`) (finite, >= 0; 0 = off; lc0 uses 0.0027)")),
+    ("--moves-left-cap", dict(type=float, default=0.0345, metavar="C",
+                              help="(self, eval, with --moves-left-slope) the bound of the utility before f(|q|) (finite, >= 0)")),
     ("--value-head", dict(choices=["scalar", "wdl"], default=None,
                           help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
@@ -131,11 +138,15 @@ def build_config(args):
         raise SystemExit(f"--reanalyse-plies {args.reanalyse_plies}: expected N >= 1")
     engine.reanalyse_records, engine.reanalyse_out, engine.reanalyse_plies = args.records, args.out, args.reanalyse_plies
     try:
+        ml_on = search_options.check_moves_left(args.moves_left_slope, args.moves_left_cap, flags=True)
+        if ml_on and args.cmd not in ("self", "eval", "reanalyse"):
+            raise search_options.SearchOptionError("--moves-left-slope is an option of `run.py self` and `run.py eval`")
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
-                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse)
+                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on)
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
     vars(engine).update(values)
+    engine.moves_left_slope, engine.moves_left_cap = float(args.moves_left_slope), float(args.moves_left_cap)
     # the resignation audit: game-loop options, not search options; their one check is the library's
     from cchess_alphazero.lib.resign_audit import check_options
     try:

@@ -140,6 +140,31 @@ _SCRIPT = "each defines its own root rule, start position or game end"
 SCRIPT_EXCLUDES = (("gumbel", _SCRIPT), ("solver", _SCRIPT), ("kld_gain", _SCRIPT), ("smart_pruning", _SCRIPT))
 SCRIPT_NEEDS = ("record_visits", "the new targets are the visit entries")
 
+# The moves-left utility (run.py self / eval --moves-left-slope, engine.moves_left_slope, Search.set_moves_left) is no value of
+# the table either -- it has flags of its own in manager.py and needs a network with the moves-left output, which no table
+# row can say -- but it takes part in the exclusions: check(moves_left=True) refuses these beside it, and a script.  The
+# library's setters hold the same list (csrc/xq_search.hip ML_EXCLUDES; tests/test_gpu_moves_left_search.py pins the two to
+# each other).
+_ML_WORD3 = "the Gumbel search keeps the network value in the node header word that holds the moves-left prediction"
+_ML_KERNEL = "each has a kernel instantiation of its own"
+MOVES_LEFT_EXCLUDES = (("gumbel", _ML_WORD3), ("solver", _ML_KERNEL), ("kld_gain", _ML_KERNEL), ("smart_pruning", _ML_KERNEL),
+                       ("eval_cache", _ML_KERNEL + ", and a cache entry holds no moves-left output"))
+MOVES_LEFT_SCRIPT = "reanalysis searches with the recorded games' own rule"
+MOVES_LEFT_REFUSAL = ("the moves-left utility (moves_left_slope {slope:g}) needs a model with the moves-left output: train "
+                      "one with `run.py opt --moves-left W`")
+MOVES_LEFT_DEFAULTS = dict(moves_left_slope=0.0, moves_left_cap=0.0345)
+MOVES_LEFT_LOG = ("moves-left utility: slope {moves_left_slope:g} per ply, cap {moves_left_cap:g}; a winning side prefers the "
+                  "shorter game, a losing side the longer one")
+
+
+def check_moves_left(slope, cap, flags=False):
+    """Raises SearchOptionError unless slope and cap are finite and >= 0; True when the option is on (slope > 0)."""
+    for key, flag, v in (("moves_left_slope", "--moves-left-slope", slope), ("moves_left_cap", "--moves-left-cap", cap)):
+        if not _finite(v, None):
+            raise SearchOptionError(f"{flag if flags else key} {v}: expected a finite value >= 0")
+    return slope > 0.0
+
+
 VALUES = {v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 
@@ -166,7 +191,8 @@ def check(values, flags=False, cmd=None, sims=None, **context):
     per option its ranges, the command, its context rule, what it needs, what it excludes; options in table order.
     flags: the messages name --kld-gain where they would name kld_gain.  cmd: the run.py command (None: not checked);
     sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
-    input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES)."""
+    input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES), moves_left=True for the moves-left
+    utility (checked after that: MOVES_LEFT_EXCLUDES, and a script)."""
     def name(key):
         return VALUES[key].flag if flags else key
 
@@ -196,6 +222,13 @@ def check(values, flags=False, cmd=None, sims=None, **context):
         for key, why in SCRIPT_EXCLUDES:
             if on(key):
                 raise SearchOptionError(f"a script excludes {name(key)}: {why}")
+    if context.get("moves_left"):
+        ml = "--moves-left-slope" if flags else "moves_left_slope"
+        for key, why in MOVES_LEFT_EXCLUDES:
+            if on(key):
+                raise SearchOptionError(f"{ml} excludes {name(key)}: {why}")
+        if context.get("script"):
+            raise SearchOptionError(f"{ml} excludes a script: {MOVES_LEFT_SCRIPT}")
 
 
 def apply(search, values, skip=()):

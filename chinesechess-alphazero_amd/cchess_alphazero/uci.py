@@ -24,7 +24,9 @@ ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference),
              "id version 2.4", "option name gpu spin default 0 min 0 max 7",
              "option name Threads spin default 10 min 0 max 1024",
              "option name Solver type check default false",
-             "option name SmartPruning type check default false")
+             "option name SmartPruning type check default false",
+             "option name MovesLeftSlope type string default 0",
+             "option name MovesLeftCap type string default 0.0345")
 
 
 class UCI:
@@ -100,6 +102,15 @@ class UCI:
                 self.config.engine.solver = args[3].lower() == "true"
             elif args[1] == "SmartPruning":               # unreachable-lead stop (cz_search_set_smart_pruning): likewise, for
                 self.config.engine.smart_pruning = args[3].lower() == "true"   # `go` commands with a simulation budget
+            elif args[1] in ("MovesLeftSlope", "MovesLeftCap"):   # moves-left utility (cz_search_set_moves_left): likewise
+                key = "moves_left_slope" if args[1] == "MovesLeftSlope" else "moves_left_cap"
+                try:
+                    v = float(args[3])
+                    if not 0.0 <= v < float("inf"):
+                        raise ValueError(args[3])
+                    setattr(self.config.engine, key, v)
+                except ValueError:
+                    self._say(f"info string {args[1]} {args[3]}: expected a finite value >= 0")
 
     def cmd_position(self, args):
         if not self.is_ready:
@@ -147,7 +158,7 @@ class UCI:
     def cmd_go(self, args):
         if not self.is_ready:
             return
-        from cchess_alphazero.agent.player import CChessPlayer
+        from cchess_alphazero.agent.player import CChessPlayer, MovesLeftUnavailable
         self._finish_worker()
         depth, infinite, budget = None, True, None
         for i, a in enumerate(args):
@@ -161,8 +172,14 @@ class UCI:
                 budget, depth, infinite = int(args[i + 1]) / 1000, 3000, False
         self.start_time = time()
         self.search_tree = {}
-        self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
-                                   debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2)
+        try:
+            self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
+                                       debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2)
+        except MovesLeftUnavailable as e:                 # the model has no moves-left output: say so and search without it
+            self._say(f"info string {e}")
+            self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
+                                       debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2,
+                                       moves_left_slope=0.0)
         self.player.out = self.out
         self.player._idle.clear()                         # a `stop` that beats the worker to the player must wait for it
         with self._lock:

@@ -75,10 +75,32 @@ def position_table(results, n_positions):
     return [dict(games=games[p], score=rows[p][0], table=tuple(rows[p])) for p in range(n_positions)]
 
 
+def _with_moves_left(e, slope):
+    """The evaluator `e` of an arena as a callable planes -> (policy, value, x), x the raw moves-left output: an InferenceNet or
+    a DevicePipe's evaluate_device whose network has the output (a ValueError names `run.py opt --moves-left` otherwise); any
+    other callable is the caller's and returns the three tensors itself."""
+    import torch
+    net = e if hasattr(e, "moves_left_head") else None
+    pipe = getattr(e, "__self__", None) if net is None else None
+    if net is None and not hasattr(pipe, "moves_left_head"):
+        return e
+    if not (net if net is not None else pipe).moves_left_head:
+        raise ValueError(search_options.MOVES_LEFT_REFUSAL.format(slope=slope) + " (in the arena both models need it)")
+    if pipe is not None:
+        return lambda planes: e(planes, moves_left=True)
+
+    def forward(planes):
+        x = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
+        p, v = net(planes, moves_left=x)
+        return p, v, x
+    return forward
+
+
 class EvaluateWorker:
     def __init__(self, config, pipes1=None, pipes2=None, pid=None, evaluators=None, dtype=_native.F32, seed=0):
-        """evaluators: (eval_best, eval_next), callables planes -> (policy, value) on the device.  When omitted,
-        pipes1 / pipes2 must offer ``evaluate_device`` (what ``CChessModel.get_pipes`` returns here)."""
+        """evaluators: (eval_best, eval_next), callables planes -> (policy, value) on the device -- (policy, value, x) while
+        the moves-left utility is on.  When omitted, pipes1 / pipes2 must offer ``evaluate_device`` (what
+        ``CChessModel.get_pipes`` returns here)."""
         self.config = config
         self.pid = pid
         if evaluators is None:
@@ -99,6 +121,14 @@ class EvaluateWorker:
         opts = search_options.resolve(config, leaf_mirror=None, solver=None, smart_pruning=None)
         search_options.check(opts)
         vars(self).update(opts)                # self.leaf_mirror, self.solver, self.smart_pruning
+        # moves-left utility of both models' searches (run.py eval --moves-left-slope S; search_options.MOVES_LEFT_EXCLUDES):
+        # both networks need the moves-left output
+        ec = getattr(config, "engine", None)
+        self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0))
+        self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345))
+        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
+        search_options.check(opts, moves_left=self.moves_left)
+        self._eval3 = tuple(_with_moves_left(e, self.moves_left_slope) for e in evaluators) if self.moves_left else None
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -127,7 +157,11 @@ class EvaluateWorker:
 
         def one_round():
             s.round(compact=True)
-            self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value))
+            if self.moves_left:                            # (fixed pointers: the search object's own rows)
+                self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value),
+                                   moves_left=s.moves_left_x)
+            else:
+                self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value))
         one_round()
         stream.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -161,6 +195,8 @@ class EvaluateWorker:
                            seed=self.seed + k, sims_per_round=sims_per_round) for k in range(2)]
         for s in searches:                                     # (before any round, and before the compact form's graph capture)
             search_options.apply(s, vars(self))                # (the three attributes above)
+            if self.moves_left:
+                s.set_moves_left(self.moves_left_slope, self.moves_left_cap)
 
         def counters_now():
             c = [s.counters() for s in searches]
@@ -275,7 +311,11 @@ class EvaluateWorker:
                         if pending == 0:
                             break
                         if leaf.numel():
-                            p, v = self.evaluators[k](s.planes.index_select(0, leaf))
+                            if self.moves_left:
+                                p, v, x = self._eval3[k](s.planes.index_select(0, leaf))
+                                s.moves_left_x.index_copy_(0, leaf, x.float())
+                            else:
+                                p, v = self.evaluators[k](s.planes.index_select(0, leaf))
                             s.policy.index_copy_(0, leaf, p.float())
                             s.value.index_copy_(0, leaf, v.float())
                             n_rows += int(leaf.numel())

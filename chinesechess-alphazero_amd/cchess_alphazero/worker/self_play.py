@@ -106,6 +106,10 @@ class SelfPlayWorker:
         # (the search options of config.engine are likewise set by the engine: one line for each that is on)
         for line in search_options.describe(vars(self.engine), self.config.play.simulation_num_per_move):
             logger.info(f"Process {self.pid}-{self.rank}: {line}")
+        if self.engine.moves_left:
+            logger.info(f"Process {self.pid}-{self.rank}: "
+                        + search_options.MOVES_LEFT_LOG.format(moves_left_slope=self.engine.moves_left_slope,
+                                                               moves_left_cap=self.engine.moves_left_cap))
         if self.resign_audit is not None:
             logger.info(f"Process {self.pid}-{self.rank}: resignation audit of the no-resign games, threshold "
                         f"{self.engine.resign_threshold:g}"

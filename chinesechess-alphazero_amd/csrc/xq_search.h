@@ -9,7 +9,9 @@
 //     uint16 move[nm]: everything a wave needs to price a node's edges is one contiguous run;
 //   * STAT block   = nm x 16 B {double W, int32 N, int32 child}: allocated only when a node is first selected
 //     FROM (two nodes in three are leaves that never are), edge j of a node = granule stat + j, so an edge id is a
-//     record id as well and a path entry is one word;
+//     record id as well and a path entry is one word; while the moves-left utility is on (cz_search_set_moves_left) the
+//     block is 2 nm granules: nm M records {int64 ksum, int32 mn, int32 spare} follow, edge j's at granule stat + nm + j
+//     (xq_search_ml.h), and header word 3 holds the node's own prediction in quanta instead of the net value;
 //   * chunks are taken from / returned to a device-side free ring (pool_* below) between plies and between games,
 //     never inside the simulation kernel: begin_search reserves the worst case of the coming ply.
 // The hot scratch (boards, ordered move lists, the current path, the game's chunk table) lives in LDS.

@@ -14,6 +14,8 @@
 //                     its input planes into its fixed slot (game * K + sim) of the evaluation queue.
 // With the evaluation cache on (cz_search_set_eval_cache) a fourth launch comes first: k_cache_fill stores the rows step 1
 // is about to attach, and the k_sim launches are the k_sim_cached instantiations, whose new leaves ask the table in step 4.
+// With the moves-left utility on (cz_search_set_moves_left) the k_sim launches are the k_sim_ml instantiations, and k_reserve_ml
+// runs between k_advance and k_sim(SELECT): the statistics blocks are twice the size, and it reserves the difference.
 // The host then runs ONE network forward over the whole queue.
 // There is no host decision inside a round and no device->host copy, so a round (kernel + network
 // forward) can be replayed from a HIP graph.
@@ -25,6 +27,7 @@
 // The device side is in internal headers, all of them parts of this one translation unit (each says why), in include order:
 //   xq_search_tree.h      SearchLDS, EdgeStat, GameView, node and edge accessors, counters, the generator, keys and hash, backup
 //   xq_search_attach.h    prior spreading and the attach of an evaluated leaf (prior_norm, attach_policy, attach_and_backup)
+//   xq_search_ml.h        the moves-left utility: MovesLeftState, MRec, ml_quanta, wave_add_i64, backup_m, ml_edge_d, ml_utility
 //   xq_search_select.h    RootCtx and PUCT at the root, the Gumbel helpers, gumbel_interior, select_gumbel, select_edge
 //   xq_search_solver.h    the MCTS solver: its bit fields, solve_*, select_solve
 //   xq_search_sim.h       one simulation: Deferred, write_planes, expand_node, the cache probe, run_sim, flush_deferred
@@ -33,8 +36,8 @@
 //                         new_script_game, script_move
 //   xq_search_selfplay.h  advance_game
 //   xq_search_stop.h      the early stop of a settled ply: stop_reset, ply_settled
-//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop, k_cache_fill, k_advance, k_advance_stop,
-//                         k_advance_script, k_stop_reset, k_noise
+//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop / k_sim_ml, k_reserve_ml, k_cache_fill,
+//                         k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise
 //   xq_search_aux.h       every other kernel (k_start_selfplay, k_start_script .. k_debug_sqrt) and walk_path
 // This file keeps the includes and the host side: the opaque search object and the C-ABI entry points.
 #include <hip/hip_runtime.h>
@@ -56,6 +59,7 @@ extern "C" void czi_set_error(const char* msg);   // xq_kernels.hip
 
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
+#include "xq_search_ml.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
@@ -87,6 +91,7 @@ struct cz_search {
     size_t stop_bytes = 0;
     ScriptState X{};                  // scripted games (cz_search_set_script); X.n 0 = off
     void* script_mem = nullptr;       // boards, labels, offsets and z, in one allocation
+    MovesLeftState M{};               // moves-left utility (cz_search_set_moves_left); M.slope 0 = off
 };
 
 namespace {
@@ -166,10 +171,11 @@ size_t layout(cz_search* s, char* base, bool dry)
 }
 
 // chunks a game needs for one full search on an empty tree (what it keeps through resets and between games)
-int keep_chunks_for(int sims)
+// ml: the moves-left utility is on, a statistics block carries one M record per edge (reserve_ply<true>)
+int keep_chunks_for(int sims, bool ml = false)
 {
-    constexpr long long PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + RESERVE_MOVES;
-    constexpr long long USABLE = CHUNK_GRANULES - MAXMOVES;
+    const long long PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + (ml ? 2 : 1) * RESERVE_MOVES;
+    const long long USABLE = CHUNK_GRANULES - (ml ? 2 : 1) * MAXMOVES;
     const long long need = (long long)(sims + 1) * PER_TASK + 1;
     return (int)((need + USABLE - 1) / USABLE);
 }
@@ -446,8 +452,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool solve = s->P.solver != 0;                        // (never with gum or cache: cz_search_set_solver)
     const bool stop = s->stop_mem != nullptr;                   // (never with gum, cache or solve: cz_search_set_kld_gain)
     const bool script = s->X.n > 0 && s->P.mode == MODE_SELFPLAY;   // (never with gum, solve or stop: cz_search_set_script)
+    const bool ml = s->M.slope > 0.0;                           // (never with gum, solve, stop, cache or a script: cz_search_set_moves_left)
     auto sim = [&](int mask, int cq) {
-        if (stop) {
+        if (ml) {
+            if (hist) hipLaunchKernelGGL((k_sim_ml<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
+            else hipLaunchKernelGGL((k_sim_ml<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
+        } else if (stop) {
             if (hist) hipLaunchKernelGGL((k_sim_stop<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
             else hipLaunchKernelGGL((k_sim_stop<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
         } else if (solve) {
@@ -473,6 +483,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     else if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
+    if (ml) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
@@ -502,7 +513,7 @@ int cz_search_set_sims(cz_search* s, int simulation_num_per_move)
     s->P.sims = simulation_num_per_move;
     // a game that has to drop its tree keeps enough chunks for one full search of the NEW length (never fewer than it
     // was created with: the initial pool layout gave every game that many)
-    int keep = keep_chunks_for(simulation_num_per_move);
+    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0);
     if (keep > s->P.max_chunks) keep = s->P.max_chunks;
     if (keep > s->keep_chunks_created) s->P.keep_chunks = keep;
     else s->P.keep_chunks = s->keep_chunks_created;
@@ -577,6 +588,10 @@ static_assert(features_symmetric(), "the exclusion matrix is symmetric and no fe
 // What a setter of feature f does between its argument checks and its assignment.  Switching on is refused beside an excluder:
 // CZ_ERR_ARG, "<entry>: <phrase of the first one that is on>".  Then the stream is idle: launches in flight keep the setting
 // (the table) they started with.
+// The moves-left utility (cz_search_set_moves_left) stands beside the table, as the side columns' script test does: it
+// excludes the features of ML_EXCLUDES and they exclude it, consulted last.
+constexpr unsigned ML_EXCLUDES = fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT);
+constexpr const char* ML_PHRASE = "the moves-left utility is on (cz_search_set_moves_left)";
 static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream)
 {
     for (int o = 0; on && o < F_COUNT; ++o)
@@ -585,6 +600,11 @@ static int admit(const cz_search* s, Feature f, bool on, const char* entry, void
             snprintf(buf, sizeof(buf), "%s: %s", entry, FEATURES[o].phrase);
             return serr(CZ_ERR_ARG, buf);
         }
+    if (on && (ML_EXCLUDES >> f & 1) && s->M.slope > 0.0) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", entry, ML_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : serr_hip(entry, e);
 }
@@ -955,6 +975,65 @@ int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream)
     if (!s || !out) return serr(CZ_ERR_ARG, "cz_search_root_decided: null argument");
     hipLaunchKernelGGL(k_root_decided, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, out);
     S_LAUNCH_CHECK("cz_search_root_decided");
+    return CZ_OK;
+}
+
+// ---- moves-left utility (include/czero.h) --------------------------------------------------------------------------------
+int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float* x_rows, void* stream)
+{
+    const char* const me = "cz_search_set_moves_left";
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: null handle");
+    if (!finite_nonneg(slope) || !finite_nonneg(cap))
+        return serr(CZ_ERR_ARG, "cz_search_set_moves_left: slope or cap negative or not finite");
+    const bool on = slope > 0.0;
+    if (on && !x_rows) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: x_rows is NULL");
+    for (int o = 0; on && o < F_COUNT; ++o)
+        if ((ML_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return serr_hip(me, e);
+    const bool was = s->M.slope > 0.0;
+    s->M.slope = slope;
+    s->M.cap = cap;
+    s->M.x = on ? x_rows : nullptr;
+    if (was == on) return CZ_OK;
+    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
+    int keep = keep_chunks_for(s->P.sims, on);
+    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
+    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
+    return cz_search_reset_trees(s, stream);
+}
+
+int cz_search_node_moves_left(cz_search* s, const uint16_t* path, int path_len, int64_t* ksum, int32_t* mn, int32_t* k_net,
+                              uint8_t* counts, void* stream)
+{
+    if (!s || path_len < 0 || path_len > MAXD_LDS || (path_len > 0 && !path))
+        return serr(CZ_ERR_ARG, "cz_search_node_moves_left: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (!(s->M.slope > 0.0)) {                                  // off: the trees hold no M records
+        const size_t G = (size_t)s->P.G;
+        hipError_t e = hipSuccess;
+        if (ksum) e = hipMemsetAsync(ksum, 0, sizeof(int64_t) * G * MAXMOVES, st);
+        if (e == hipSuccess && mn) e = hipMemsetAsync(mn, 0, sizeof(int32_t) * G * MAXMOVES, st);
+        if (e == hipSuccess && k_net) e = hipMemsetAsync(k_net, 0, sizeof(int32_t) * G, st);
+        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
+        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_moves_left", e);
+    }
+    hipLaunchKernelGGL(k_node_moves_left, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, (long long*)ksum, mn, k_net,
+                       counts);
+    S_LAUNCH_CHECK("cz_search_node_moves_left");
+    return CZ_OK;
+}
+
+int cz_moves_left_quanta(const float* x, int32_t* k, int n, void* stream)
+{
+    if (!x || !k || n < 0) return serr(CZ_ERR_ARG, "cz_moves_left_quanta: null argument or n < 0");
+    if (n == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_ml_quanta, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, k, n);
+    S_LAUNCH_CHECK("cz_moves_left_quanta");
     return CZ_OK;
 }
 

@@ -8,6 +8,7 @@
 // rows, the move choice, the test hooks) and walk_path.
 #pragma once
 #include "xq_search_tree.h"
+#include "xq_search_ml.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_ply.h"
@@ -182,6 +183,47 @@ __global__ __launch_bounds__(64) void k_root_stats(SearchParams P, SearchBuffers
         if (sum_n) sum_n[g] = root_sum_n;
         if (counts) counts[g] = (uint8_t)nm;
     }
+}
+
+// Moves-left utility: the M records of the root, or of the node reached from it along path[g][0 .. path_len) as in
+// k_root_stats: per edge ksum and mn (0 past the node's edges and without a statistics block), per game the node's own k.
+// Launched only while the option is on: a tree grown without it has no M records.
+__global__ __launch_bounds__(64) void k_node_moves_left(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                       int path_len, long long* __restrict__ ksum, int32_t* __restrict__ mn,
+                                                       int32_t* __restrict__ k_net, uint8_t* __restrict__ counts)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    int node = walk_path(B, gv, path, path_len);
+    if (node == 0) node = -1;                                   // (id 0 is "none": an object never given a root)
+    int nm = 0, k = 0;
+    const MRec* mb = nullptr;
+    if (node >= 0) {
+        const NodeHdr hdr = load_hdr(rec_ptr(gv, (uint32_t)node));
+        nm = (int)(hdr.meta & 0xFF);
+        k = (int)hdr.val;
+        if (hdr.stat) mb = m_block(edge_ptr(gv, hdr.stat), nm);
+    }
+    for (int j = lane; j < MAXMOVES; j += 64) {
+        MRec r{0, 0, 0};
+        if (j < nm && mb) r = mb[j];
+        if (ksum) ksum[(size_t)g * MAXMOVES + j] = r.ksum;
+        if (mn) mn[(size_t)g * MAXMOVES + j] = r.mn;
+    }
+    if (lane == 0) {
+        if (k_net) k_net[g] = k;
+        if (counts) counts[g] = (uint8_t)nm;
+    }
+}
+
+// k[i] = ml_quanta(x[i]): the attach's conversion, row by row (cz_moves_left_quanta)
+__global__ void k_ml_quanta(const float* __restrict__ x, int32_t* __restrict__ k, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) k[i] = ml_quanta(x[i]);
 }
 
 // MCTS solver: the proof state of the root, or of the node reached from it along path[g][0 .. path_len) as in k_root_stats:

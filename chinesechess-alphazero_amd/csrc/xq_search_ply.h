@@ -64,7 +64,8 @@ XQ_D void clear_tree(const SearchParams& P, const SearchBuffers& B, const GameVi
 
 // Make sure the game owns room for `tasks` more simulations (each may add one node record and one statistics block of
 // RESERVE_MOVES moves): takes chunks from the pool.  false = the pool, the game's chunk table or its hash table is
-// exhausted.
+// exhausted.  ML: the moves-left utility is on, a statistics block carries one M record per edge (k_reserve_ml).
+template <bool ML = false>
 XQ_D bool reserve_ply(const SearchParams& P, const SearchBuffers& B, const GameView& gv, uint32_t* chtab, int tasks)
 {
     const int g = gv.g;
@@ -72,8 +73,8 @@ XQ_D bool reserve_ply(const SearchParams& P, const SearchBuffers& B, const GameV
     int nch = uni(B.g_nchunks[g]);
     const int ncount = uni(B.g_node_count[g]);
     if ((long long)ncount + tasks + 1 > (long long)P.hash_cap * 7 / 8) return false;      // open addressing: keep it sparse
-    constexpr int PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + RESERVE_MOVES;
-    constexpr int USABLE = CHUNK_GRANULES - MAXMOVES;                 // a record that does not fit moves to the next chunk
+    constexpr int PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + (ML ? 2 : 1) * RESERVE_MOVES;
+    constexpr int USABLE = CHUNK_GRANULES - (ML ? 2 : 1) * MAXMOVES;  // a record that does not fit moves to the next chunk
     const long long need = (long long)(tasks + 1) * PER_TASK;
     long long have = (long long)(nch - (int)(top >> CHUNK_SHIFT)) * USABLE - (long long)(top & (uint32_t)(CHUNK_GRANULES - 1));
     bool ok = true;

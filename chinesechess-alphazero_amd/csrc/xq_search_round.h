@@ -4,12 +4,13 @@
 // text only moves between these headers, and the proof of a move is the unit's device assembly, kernel by kernel
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
-// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop; k_cache_fill, k_advance,
-// k_advance_stop, k_advance_script, k_stop_reset, k_noise.
+// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop, k_sim_ml; k_reserve_ml,
+// k_cache_fill, k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
 #include "xq_search_select.h"
+#include "xq_search_ml.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
 #include "xq_search_ply.h"
@@ -33,11 +34,14 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // SOLVE: the MCTS solver (cz_search_set_solver) is on; likewise.  The body of k_sim_solve too.
 // STOP: a stop rule (cz_search_set_kld_gain, cz_search_set_smart_pruning) is on; likewise.  The body of k_sim_stop too; S is
 // read by that instantiation alone.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false>
+// ML: the moves-left utility (cz_search_set_moves_left) is on; likewise.  The body of k_sim_ml too; M is read by that
+// instantiation alone.  Its attach turns the leaf's moves-left row into k (ml_quanta), keeps k in the node header and takes m up
+// the path (backup_m); it runs leaf by leaf without the one-leaf-ahead prefetch.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
                    int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C,
-                   const StopState& S = StopState{})
+                   const StopState& S = StopState{}, const MovesLeftState& M = MovesLeftState{})
 {
     const int g = blockIdx.x;
     // first kernel of a round: chunks returned during the previous round become takeable (see pool_commit)
@@ -90,6 +94,10 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             my_meta = *reinterpret_cast<const uint32_t*>(rec_ptr(gv, (uint32_t)sn_node) + NODE_OFF_HDR + 4);
             my_v = value[my_row];
         }
+        int my_k = 0;                                                 // (ML) the leaf's moves-left prediction in quanta
+        if constexpr (ML) {
+            if (sn_state == SIM_LEAF) my_k = ml_quanta(M.x[my_row]);
+        }
         // the leaves the cache answered (SIM_CACHED) join the walk below at their place in simulation order: their value
         // waits in s_cval, no policy row is read and nothing is prefetched for them
         uint64_t cached = 0ull;
@@ -113,7 +121,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         };
         LeafPre lp{0, 0, 0, 0.0f, 0.0f};
         uint64_t rest = leaves;
-        if (rest) {
+        if (!ML && rest) {
             const int i0 = __ffsll((long long)rest) - 1;
             pre_a(lp, i0);
             pre_b(lp, i0);
@@ -127,7 +135,14 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             const size_t slot = (size_t)__builtin_amdgcn_readlane(my_row, i);
             const double v = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_v), i));   // float(v) of a float32
             LeafPre nx{0, 0, 0, 0.0f, 0.0f};
-            if (CACHE && ((cached >> i) & 1ull)) {
+            if constexpr (ML) {
+                const int k = __builtin_amdgcn_readlane(my_k, i);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), k);
+                load_path(P, gv, L, i, depth);
+                backup_m(gv, L, depth, k);
+                backup(P, gv, L, depth, v);
+            } else if (CACHE && ((cached >> i) & 1ull)) {
                 cached_attach(gv, node, keep_v, (float)v);
                 load_path(P, gv, L, i, depth);
                 backup(P, gv, L, depth, v);
@@ -171,6 +186,11 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             }
             attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, keep_v, value[slot]);
             load_path(P, gv, L, i, depth);
+            if constexpr (ML) {
+                const int k = uni(ml_quanta(M.x[slot]));
+                if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), k);
+                backup_m(gv, L, depth, k);
+            }
             backup(P, gv, L, depth, (double)value[slot]);             // float(v) of a float32
             sim_finish(gv, i, &active);
         }
@@ -197,7 +217,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         } else if (df.lo != 0 || df.hi != 0) {
             // the descents of this phase (resumed simulations / a fresh batch) are over: the terminal and repetition
             // values they produced are applied now, in index order
-            flush_deferred<SOLVE>(P, gv, L, df, &active);
+            flush_deferred<SOLVE, ML>(P, gv, L, df, &active);
             continue;
         } else if ((mask & SIM_SELECT) && active == 0) {              // 3. next lock-step batch (player.py:169-178)
             const int tasks = uni(B.g_tasks_left[g]);
@@ -231,8 +251,8 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM, CACHE, SOLVE>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
-                                         (mask & SIM_SELECT) != 0);
+        run_sim<HIST, GUM, CACHE, SOLVE, ML>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
+                                             (mask & SIM_SELECT) != 0, M);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -300,6 +320,43 @@ __global__ __launch_bounds__(64, 4) void k_sim_stop(SearchParams P, SearchBuffer
 {
     __shared__ SearchLDS L;
     sim_body<HIST, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{}, S);
+}
+
+// k_sim with the moves-left utility on (cz_search_set_moves_left refuses the Gumbel search, the solver, the stop rules, the
+// evaluation cache and a script)
+template <bool HIST>
+__global__ __launch_bounds__(64, 4) void k_sim_ml(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                              const float* __restrict__ value, void* planes, int mask, int compact,
+                                              int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, MovesLeftState M)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{},
+                                                     StopState{}, M);
+}
+
+// The moves-left utility's share of the per-ply reservation: a statistics block is twice the size while the option is on, so
+// between k_advance (whose begin_search reserved the plain blocks) and k_sim(SELECT) every searching game tops its chunks up to
+// what its outstanding simulations can use.  A game that cannot be served here has just begun its ply (a ply under way was
+// served when it began and uses no more than that): its tree is dropped as begin_search would, the chunks it keeps hold one
+// full search of the larger blocks (keep_chunks_for).
+__global__ __launch_bounds__(64) void k_reserve_ml(SearchParams P, SearchBuffers B)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    if (uni((int)B.g_phase[g]) != PH_SEARCH) return;
+    const int tasks = uni(B.g_tasks_left[g]) + uni(B.g_active[g]);
+    if (tasks <= 0) return;
+    const GameView gv = make_view(B, P, g, L.ctr, L.chtab);
+    counters_begin(gv);
+    if (!reserve_ply<true>(P, B, gv, L.chtab, tasks) && uni(B.g_active[g]) == 0) {
+        clear_tree(P, B, gv, L.chtab);
+        count(gv, CT_TREE_RESETS);
+        const int sims = ply_is_fast(P, uniu(B.g_game_id[g]), uni(B.g_turns[g])) ? P.fast_sims : P.sims;
+        if (lane_id() == 0) B.g_tasks_left[g] = sims;
+        (void)reserve_ply<true>(P, B, gv, L.chtab, sims);
+    }
+    counters_flush(gv);
 }
 
 // The evaluation cache's only writer: the first launch of a round (before k_sim(BACKUP), which attaches the same rows),

@@ -8,6 +8,7 @@
 // gumbel_vmix), gumbel_interior, Picked, select_gumbel, select_edge.
 #pragma once
 #include "xq_search_tree.h"
+#include "xq_search_ml.h"
 
 namespace {
 
@@ -197,10 +198,13 @@ XQ_D int select_gumbel(int gumbel_m, double c_visit, double c_scale, int32_t* st
 
 // base: the node's record; sb: its stat block (nullptr: allocated in this visit, every edge is {0, 0, unknown}).
 // GUM: the k_sim instantiation that is launched while the Gumbel root search is on -- the others do not hold its code,
-// so their registers and their text are what they were without it.  net_value: the header's fourth word (GUM only).
-template <bool GUM>
+// so their registers and their text are what they were without it.  net_value: the header's fourth word (GUM: the float32
+// network value; ML: the leaf's k).
+// ML: the k_sim instantiation that is launched while the moves-left utility is on (cz_search_set_moves_left); likewise.  Every
+// lane loads its edges' M records, two integer wave sums give the parent's mean, and the score is (q + u) + u_m.
+template <bool GUM, bool ML = false>
 XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, char* base, const EdgeStat* sb, int sum_n,
-                        int nm, const RootCtx& rc, uint32_t net_value)
+                        int nm, const RootCtx& rc, uint32_t net_value, const MovesLeftState& M = MovesLeftState{})
 {
     if (GUM && rc.is_root && P.gumbel_m > 0) {                  // wave-uniform
         Picked r;                                               // (have = false: the caller reloads the edge, this is not the hot path)
@@ -241,6 +245,20 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
     int best_j = -1;
     bool win0 = false, win1 = false;
     const int halves = nm > 64 ? 2 : 1;                     // almost every position has <= 64 moves
+    double d0 = 0.0, d1 = 0.0;                              // (ML) this lane's clamped slope * (Mj - Mp) of the two halves
+    if constexpr (ML) {
+        MRec mr0{0, 0, 0}, mr1{0, 0, 0};
+        if (sb) {                                           // (a fresh statistics block: every record is {0, 0})
+            const MRec* mb = m_block(sb, nm);
+            if (lane < nm) mr0 = mb[lane];                  // one 16-byte load
+            if (lane + 64 < nm) mr1 = mb[lane + 64];
+        }
+        const long long K = (long long)(int)net_value + wave_add_i64(mr0.ksum + mr1.ksum);
+        const int N = 1 + __builtin_amdgcn_readlane(wave_incl_scan(mr0.mn + mr1.mn), 63);
+        const double Mp = ((double)K / 16.0) / (double)N;   // the node's own mean, in plies
+        d0 = ml_edge_d(M, mr0.ksum, mr0.mn, Mp);
+        d1 = ml_edge_d(M, mr1.ksum, mr1.mn, Mp);
+    }
 #pragma nounroll
     for (int h = 0; h < halves; ++h) {
         const int j = lane + 64 * h;
@@ -266,6 +284,7 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
             }
             if (valid) {
                 score = q + u;
+                if constexpr (ML) score = score + ml_utility(h == 0 ? d0 : d1, q);
                 win = q > (1.0 - 1e-7);
                 if (!(score >= -99999999.0)) valid = false;
             }

@@ -193,7 +193,10 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * A script (cz_search_set_script, below) is an eighth member, the last in that order: it is not beside the Gumbel root
  * search, the MCTS solver, the KLD-gain stop and the unreachable-lead stop, which define a root rule or a ply's end of
  * their own, and -- outside the table, refused the same way in both directions -- not beside a book (a start position of
- * its own) and the max-q record of the resignation audit (a scripted game has no resignation test). */
+ * its own) and the max-q record of the resignation audit (a scripted game has no resignation test).
+ * The moves-left utility (cz_search_set_moves_left, below) stands beside the table the same way, consulted last: it is not
+ * beside the Gumbel root search, the MCTS solver, the two stop rules, the evaluation cache and a script, in both directions;
+ * a setter refused for it names "the moves-left utility is on (cz_search_set_moves_left)". */
 
 /* Scripted games: walk stored games again (MuZero's Reanalyse).  n games: game id i < n starts from init_boards[i] (90
  * bytes, the first mover's frame, as cz_replay_games takes them), plays labels[offsets[i] .. offsets[i+1]) and ends with
@@ -806,6 +809,51 @@ int cz_search_node_proof(cz_search* s, const uint16_t* path, int path_len, int8_
                          uint8_t* mark_dist, void* stream);
 /* out [G] uint8 DEVICE: 1 where the game's current root is decided, with the bans of the current ply. */
 int cz_search_root_decided(cz_search* s, uint8_t* out, void* stream);
+/* ---- moves-left utility (off by default; the reference has no such option; lc0's moves-left utility) ----------------------
+ * run.py self / eval --moves-left-slope S [--moves-left-cap C]; the UCI options MovesLeftSlope, MovesLeftCap.  The selection
+ * prefers, among moves of like value, the shorter game while it is winning and the longer one while it is losing, by the
+ * network's moves-left output (cz_heads_tail_ml).  With the option off no kernel output, record or counter differs by a bit,
+ * and the kernels launched are the ones launched before it existed.
+ *
+ * UNITS.  The tree holds plies in quanta of 1/16 ply (CZ_MOVES_LEFT_QUANTA), as integers: every sum is exact and does not
+ * depend on the order of the backups or of the wave reductions.
+ * A LEAF'S PREDICTION.  The network's raw x becomes k = min(rint(512 * softplus(x)), 16 * 1023) quanta (512 = 16 quanta x
+ * MOVES_LEFT_UNIT 32; CZ_MOVES_LEFT_K_MAX), softplus in float32 as max(x, 0) + log1p(exp(-|x|)); a product that is not
+ * finite or negative gives 0, +infinity the cap.  Computed at attach, where the leaf's value row is read, and kept as an
+ * integer in word 3 of the node header (free while the Gumbel search is off).
+ * OTHER ENDS.  A simulation that ends on a terminal child, on a repetition or without an edge has k = 0.
+ * BACKUP.  From the leaf up with m = k, per level: m += 16, the edge's ksum += m (int64), the edge's mn += 1 (int32).  mn
+ * counts completed backups only; virtual loss does not touch these fields.
+ * STORAGE.  Each edge has an M record {int64 ksum, int32 mn, int32 spare}, one granule, directly behind the node's
+ * statistics block: edge j's record is granule stat + nm + j.  Allocated with the statistics block, only while the option is
+ * on; the per-ply chunk reservation and the chunks a game keeps count the larger block.
+ * SELECTION at a node, K = k_node + sum_j ksum_j, N = 1 + sum_j mn_j (integers), then in float64 and this order:
+ *   Mp  = ((double)K / 16.0) / (double)N
+ *   Mj  = ((double)ksum_j / 16.0) / (double)mn_j      where mn_j > 0; otherwise the edge's utility is 0
+ *   d   = slope * (Mj - Mp), clamped to [-cap, cap]
+ *   a   = min(|q_j|, 1.0)                              (terminal values are +-2)
+ *   f   = 1.6521 * a + (-0.6521) * (a * a)             (lc0's coefficients)
+ *   u_m = q_j > 0 ? -(d * f) : (q_j < 0 ? d * f : 0.0)
+ *   score = (q + u) + u_m
+ * Everything else of the selection is unchanged: the q > 1 - 1e-7 shortcut, the >= tie rule, the rejected-score test, root
+ * bans, the root prior, the forced-playout pass.
+ *
+ * cz_search_set_moves_left: slope and cap finite and >= 0, slope 0 = off.  x_rows: caller-owned DEVICE float32 [G*K], indexed
+ * exactly as `value` is (by slot, or by compact row with cz_search_round_q) and read by cz_search_round(_q) for the rows
+ * `value` is read for; NULL with slope > 0 is CZ_ERR_ARG.  Switching on or off resets the trees as cz_search_reset_trees
+ * does (the statistics blocks change size).  Switching on is refused (CZ_ERR_ARG) beside the Gumbel search (header word 3),
+ * the solver, the stop rules and the evaluation cache (each has a kernel instantiation of its own; a cache entry holds no x)
+ * and a script, and each of them is refused beside it; switching off is never refused.  Synchronises the stream. */
+#define CZ_MOVES_LEFT_QUANTA 16
+#define CZ_MOVES_LEFT_K_MAX (16 * 1023)
+int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float* x_rows, void* stream);
+/* The M records of the node cz_search_node_stats would report for the same path (path NULL / path_len 0: the root; path_len
+ * at most 128): ksum [G][128] int64 and mn [G][128] int32, 0 past the node's edges; k_net [G] int32, the node's own k; counts
+ * [G] uint8, the node's edges.  Any may be NULL; all DEVICE.  With the option off everything is 0, counts included. */
+int cz_search_node_moves_left(cz_search* s, const uint16_t* path, int path_len, int64_t* ksum, int32_t* mn, int32_t* k_net,
+                              uint8_t* counts, void* stream);
+/* k[i] = the quanta of x[i], by the attach's own conversion; x, k DEVICE [n]. */
+int cz_moves_left_quanta(const float* x, int32_t* k, int n, void* stream);
 /* ---- early stop of a settled ply (both rules off by default; the reference has no such option) ---------------------------
  * run.py self --kld-gain G [--kld-interval I]; run.py eval --smart-pruning, the UCI option SmartPruning.  Two rules end a
  * ply's search before its budget is spent.  With both off no kernel output, record or counter differs by a bit, and the

@@ -6,6 +6,7 @@ events over the next rounds (per-launch: mean / median / p99).  A/B tool for cha
 (csrc/xq_search.hip and the csrc/xq_search_*.h it is made of).
 
     python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1] [--leaf-mirror P]
+                                 [--moves-left-slope S [--moves-left-cap C]]
 """
 import argparse
 import json
@@ -25,6 +26,9 @@ def main():
     ap.add_argument("--games", type=int, default=4096)
     ap.add_argument("--masks-only", type=int, default=0, help="1: leaves written as occupancy boards only (cz_search_leaf_planes(0))")
     ap.add_argument("--leaf-mirror", type=float, default=0.0, help="rate of the random leaf mirror (cz_search_set_leaf_mirror)")
+    ap.add_argument("--moves-left-slope", type=float, default=0.0,
+                    help="slope of the moves-left utility (cz_search_set_moves_left); the stub's third output feeds it")
+    ap.add_argument("--moves-left-cap", type=float, default=0.0345)
     a = ap.parse_args()
     import types
     import stub_net
@@ -39,25 +43,32 @@ def main():
         s.leaf_planes(False)
     if a.leaf_mirror:
         s.set_leaf_mirror(a.leaf_mirror, flags=True)
+    if a.moves_left_slope:
+        import stub_moves_left
+        s.set_moves_left(a.moves_left_slope, a.moves_left_cap)
     s.start_selfplay(seed=20260923)
     planes_of = (lambda: s.queue_planes()) if a.masks_only else (lambda: s.planes)   # (the same planes either way: same trees)
 
-    def step():
-        s.round(compact=bool(a.compact))
+    def feed():
         # a near-uniform, position-dependent network: cheap, and the trees grow like the random-init net's
         p, v = stub_net.hash_stub_torch(planes_of(), 1)
         p = p * 0 + 1.0 / 2086 + p * 1e-3
+        x = stub_moves_left.ml_stub_torch(planes_of(), 1)[2] if a.moves_left_slope else None
         if a.compact:
-            n = s.slots
-            rows = s.q_rows.long().clamp_(0, n - 1)
+            rows = s.q_rows.long().clamp_(0, s.slots - 1)
             s.policy.copy_(p.index_select(0, rows))
             s.value.copy_((v * 0.05).index_select(0, rows))
+            if x is not None:
+                s.moves_left_x.copy_(x.index_select(0, rows))
         else:
             s.policy.copy_(p)
             s.value.copy_(v * 0.05)
+            if x is not None:
+                s.moves_left_x.copy_(x)
 
     for _ in range(a.rounds):
-        step()
+        s.round(compact=bool(a.compact))
+        feed()
     torch.cuda.synchronize()
     ev = []
     for _ in range(a.timed):
@@ -66,22 +77,16 @@ def main():
         s.round(compact=bool(a.compact))
         e[1].record()
         ev.append(e)
-        p, v = stub_net.hash_stub_torch(planes_of(), 1)
-        p = p * 0 + 1.0 / 2086 + p * 1e-3
-        if a.compact:
-            rows = s.q_rows.long().clamp_(0, s.slots - 1)
-            s.policy.copy_(p.index_select(0, rows))
-            s.value.copy_((v * 0.05).index_select(0, rows))
-        else:
-            s.policy.copy_(p)
-            s.value.copy_(v * 0.05)
+        feed()
     torch.cuda.synchronize()
     t = sorted(x.elapsed_time(y) for x, y in ev)
     c, m = s.counters(), s.memory_info()
     out = {"rounds_before": a.rounds, "timed": a.timed, "compact": a.compact, "masks_only": a.masks_only,
            "search_round_ms": {"mean": sum(t) / len(t), "median": t[len(t) // 2], "p99": t[int(len(t) * 0.99)], "max": t[-1]},
            "mean_depth": c["sum_depth"] / max(1, c["sims"]), "plies": c["plies"], "games": c["games"],
-           "tree_resets": c["tree_resets"], "nodes": m["nodes"], "tree_gb": m["tree_bytes"] / 1e9}
+           "tree_resets": c["tree_resets"], "overflow_sims": c["overflow_sims"], "nodes": m["nodes"],
+           "tree_gb": m["tree_bytes"] / 1e9, "tree_bytes_per_game": m["tree_bytes"] / a.games,
+           "moves_left_slope": a.moves_left_slope}
     if a.leaf_mirror:                      # (of the slots as they stand: every slot has held a leaf by now)
         out["leaf_mirror"] = a.leaf_mirror
         out["mirrored_share_of_slots"] = float(s.mirrored.float().mean())
