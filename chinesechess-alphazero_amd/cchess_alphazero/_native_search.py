@@ -150,6 +150,9 @@ def declare(L):
         "cz_search_set_moves_left": [vp, d, d, vp, vp],
         "cz_search_node_moves_left": [vp, vp, i32, vp, vp, vp, vp, vp],
         "cz_moves_left_quanta": [vp, vp, i32, vp],
+        "cz_search_set_draw": [vp, i32, d, vp, vp],
+        "cz_search_node_draws": [vp, vp, i32, vp, vp, vp, vp, vp],
+        "cz_draw_quanta": [vp, i32, vp, i32, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -263,6 +266,8 @@ class Search:
         self.smart_pruning = False             # set_smart_pruning(): a tau = 0 ply ends once its leader cannot be caught
         self.moves_left_slope, self.moves_left_cap = 0.0, 0.0345   # set_moves_left(): the moves-left utility, slope 0 = off
         self.moves_left_x = None               # ... and its rows: [slots] float32 beside policy / value, the network's raw x
+        self.draw_on, self.draw_score = False, 0.0   # set_draw(): the draw average and what a draw is worth at the root
+        self.wdl_rows = None                   # ... and its rows: [slots, 3] float32 beside policy / value, the network's W / D / L
 
     # -- lifetime --
     def close(self):
@@ -497,6 +502,44 @@ class Search:
                                                        C.c_void_p(k_net.data_ptr()), C.c_void_p(counts.data_ptr()),
                                                        self._stream()), "cz_search_node_moves_left")
         return dict(ksum=ksum.cpu().numpy(), mn=mn.cpu().numpy(), k_net=k_net.cpu().numpy(), counts=counts.cpu().numpy())
+
+    def set_draw(self, on, score=0.0):
+        """Draw average (cz_search_set_draw; include/czero.h has the rule): while on, every edge keeps the mean draw
+        probability of the simulations through it, and the selection adds sigma * dbar to an edge's score, sigma = +-score by
+        the parity of the node's depth (score in [-1, 1]: what a draw is worth to the side to move at the root; 0 changes no
+        comparison).  The caller writes the network's win / draw / loss rows of the positions it evaluates to self.wdl_rows
+        (float32 [slots, 3], indexed as self.value is; allocated here, once).  Switching on or off resets the trees; a new
+        score while on does not.  Refused beside the Gumbel search, the solver, the stop rules, the evaluation cache, a script
+        and the moves-left utility, and they beside it.  Call it before start_selfplay() / set_roots() and before a graph
+        capture."""
+        import torch
+        if not hasattr(self.L, "cz_search_set_draw"):
+            raise _native.NativeError("this libczero.so has no draw average (cz_search_set_draw)")
+        if on and self.wdl_rows is None:
+            self.wdl_rows = torch.zeros((self.slots, 3), dtype=torch.float32, device=self.device)
+        ptr = C.c_void_p(self.wdl_rows.data_ptr()) if self.wdl_rows is not None else None
+        _native.check(self.L.cz_search_set_draw(self.h, 1 if on else 0, float(score), ptr, self._stream()),
+                      "cz_search_set_draw")
+        self.draw_on, self.draw_score = bool(on), float(score) if on else 0.0
+
+    def node_draws(self, path=None):
+        """The draw records of the node node_stats(path) reports (cz_search_node_draws): dict(dsum int64 [G, 128] and dn
+        int32 [G, 128] per edge -- the sum of the backed-up draw probabilities in quanta of 2^-20 and how many --, dq_net
+        int32 [G], the node's own draw probability in quanta, counts uint8 [G]).  With the option off everything is 0."""
+        import torch
+        G, M = self.G, _native.MAXMOVES
+        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        dsum = torch.empty((G, M), dtype=torch.int64, device=self.device)
+        dn = torch.empty((G, M), dtype=torch.int32, device=self.device)
+        dq_net = torch.empty((G,), dtype=torch.int32, device=self.device)
+        counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
+        _native.check(self.L.cz_search_node_draws(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
+                                                  pa.shape[1], C.c_void_p(dsum.data_ptr()), C.c_void_p(dn.data_ptr()),
+                                                  C.c_void_p(dq_net.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                  self._stream()), "cz_search_node_draws")
+        return dict(dsum=dsum.cpu().numpy(), dn=dn.cpu().numpy(), dq_net=dq_net.cpu().numpy(), counts=counts.cpu().numpy())
 
     def node_proof(self, path=None):
         """The proof state of the node node_stats(path) reports (cz_search_node_proof): dict(status int8 [G] -- PROOF_OPEN /
@@ -830,7 +873,7 @@ class Search:
 
     def run_until_idle(self, evaluate, max_rounds=1000000):
         """external mode: rounds until every search is complete.  evaluate(planes) -> (policy, value), or (policy, value,
-        moves-left x) while set_moves_left() is on."""
+        moves-left x) while set_moves_left() is on, or (policy, value, wdl [n, 3]) while set_draw() is on."""
         rounds = 0
         while rounds < max_rounds:
             self.round()
@@ -842,7 +885,9 @@ class Search:
                 out = evaluate(self.planes.index_select(0, rows))
                 self.policy.index_copy_(0, rows, out[0].float())
                 self.value.index_copy_(0, rows, out[1].float())
-                if len(out) > 2 and self.moves_left_x is not None:
+                if len(out) > 2 and self.draw_on:  # (never beside the moves-left utility)
+                    self.wdl_rows.index_copy_(0, rows, out[2].float())
+                elif len(out) > 2 and self.moves_left_x is not None:
                     self.moves_left_x.index_copy_(0, rows, out[2].float())
         raise RuntimeError("search did not finish")
 

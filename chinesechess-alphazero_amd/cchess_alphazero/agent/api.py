@@ -26,8 +26,13 @@ class DevicePipe:
         self.api = api
         self._replies = []
 
-    def evaluate_device(self, planes, moves_left=False):
-        return self.api.predict_device(planes, moves_left=moves_left)
+    def evaluate_device(self, planes, moves_left=False, wdl=False):
+        return self.api.predict_device(planes, moves_left=moves_left, wdl=wdl)
+
+    @property
+    def wdl_head(self):
+        """The network behind the pipe has the win / draw / loss value head (what the draw average of the search needs)."""
+        return bool(getattr(self.api.net, "wdl_head", False))
 
     @property
     def moves_left_head(self):
@@ -66,7 +71,7 @@ class CChessModelAPI:
         # (the tower arithmetic is a request: it is measured against the float64 network on calibration positions and
         #  replaced by a more exact one when these weights need it -- agent/model.py guarded_inference_net)
         self.net = guarded_inference_net(agent_model.model, dtype, trunk=trunk, arith=self._arith, device=self.device,
-                                         guard=self._guard, moves_left=self._guard_moves_left())
+                                         guard=self._guard, moves_left=self._guard_moves_left(), draw=self._guard_draw())
         self._dtype, self._trunk = dtype, trunk
         self.done = False
         self.need_reload = True
@@ -78,6 +83,13 @@ class CChessModelAPI:
         model has the output (a model without it is refused where the search is built)."""
         ec = getattr(self.config, "engine", None)
         return bool(getattr(ec, "moves_left_slope", 0.0) > 0.0 and self.agent_model.model.moves_left_head)
+
+    def _guard_draw(self):
+        """Likewise the draw probability while the configuration's draw average is on and the model has the win / draw / loss
+        head."""
+        ec = getattr(self.config, "engine", None)
+        return bool((getattr(ec, "draw_score", 0.0) != 0.0 or getattr(ec, "show_wdl", False))
+                    and self.agent_model.model.wdl_head)
 
     def start(self, need_reload=True):
         self.need_reload = need_reload
@@ -94,7 +106,7 @@ class CChessModelAPI:
                         trunk = "library"
                     self.net = guarded_inference_net(self.agent_model.model, self._dtype, trunk=trunk, arith=self._arith,
                                                      device=self.device, guard=self._guard,
-                                                     moves_left=self._guard_moves_left())
+                                                     moves_left=self._guard_moves_left(), draw=self._guard_draw())
                     return True
         except Exception as e:                    # a half-written file: keep serving the old weights
             logger.error(e)
@@ -106,8 +118,9 @@ class CChessModelAPI:
         return pipe
 
     @torch.no_grad()
-    def predict_device(self, planes, moves_left=False):
-        """(policy, value) of the planes; moves_left=True (a network with the output): a third tensor, its raw x [n]."""
+    def predict_device(self, planes, moves_left=False, wdl=False):
+        """(policy, value) of the planes; moves_left=True (a network with the output): a third tensor, its raw x [n]; wdl=True
+        (a network with the win / draw / loss head): a third tensor, its probabilities [n, 3]."""
         if self.need_reload and time() - self._last_check > self.reload_interval:
             self._last_check = time()
             self.try_reload_model()
@@ -115,6 +128,10 @@ class CChessModelAPI:
             x = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
             p, v = self.net(planes, moves_left=x)
             return p, v, x
+        if wdl:
+            rows = torch.empty((planes.shape[0], 3), dtype=torch.float32, device=planes.device)
+            p, v = self.net(planes, wdl=rows)
+            return p, v, rows
         return self.net(planes)
 
     def close(self):

@@ -844,10 +844,11 @@ def within_guard(m, tol=GUARD_TOL, logit_tol=LOGIT_TOL):
     where the legal moves of the positions are known -- the legal-renormalised priors themselves within `tol`.  Where the
     raw moves-left output was measured (the search's moves-left utility is on) it is held to `logit_tol` as well: like a
     logit it is a pre-activation, and 512 * softplus has slope <= 512, so 2e-4 of x moves a leaf's prediction by at most a
-    tenth of a quantum."""
+    tenth of a quantum.  Where the draw probability was measured (the search's draw average is on) it is held to `tol`, as
+    the value is: it comes out of the same softmax."""
     return bool(m["finite"] and m["policy_max_abs"] <= tol and m["value_max_abs"] <= tol and
                 m["logit_max_abs"] <= logit_tol and m.get("legal_prior_max_abs", 0.0) <= tol and
-                m.get("moves_left_max_abs", 0.0) <= logit_tol)
+                m.get("moves_left_max_abs", 0.0) <= logit_tol and m.get("draw_max_abs", 0.0) <= tol)
 
 
 def calibration_planes(n=CALIBRATION_POSITIONS, input_depth=14, device=None, seed=20260924, with_legal=False):
@@ -966,17 +967,20 @@ def legal_priors(p, legal):
     return q / q.sum(1, keepdim=True).clamp_min(1e-300)
 
 
-def measure_against_reference(inf, ref_out, planes, legal=None, moves_left_ref=None):
+def measure_against_reference(inf, ref_out, planes, legal=None, moves_left_ref=None, draw_ref=None):
     """Max deviations of an InferenceNet from reference_forward_f64's outputs on the same planes.  legal (bool [n, 2086]):
     also legal_prior_max_abs, the deviation of the priors renormalised over each position's legal moves.  moves_left_ref
     (float64 [n], reference_forward_f64(with_moves_left=True)'s last entry; given while the search's moves-left utility is
-    on): also moves_left_max_abs, the deviation of the raw moves-left output, taken from the same forward."""
-    x = None
+    on): also moves_left_max_abs, the deviation of the raw moves-left output, taken from the same forward.  draw_ref (float64
+    [n], the draw column of reference_forward_f64(with_wdl=True)'s probabilities; given while the search's draw average is
+    on): also draw_max_abs, the deviation of the draw probability, likewise."""
+    x = wd = None
+    kw = {}
     if moves_left_ref is not None:
-        x = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
-        p, v = inf(planes, moves_left=x)
-    else:
-        p, v = inf(planes)
+        x = kw["moves_left"] = torch.empty((planes.shape[0],), dtype=torch.float32, device=planes.device)
+    if draw_ref is not None:
+        wd = kw["wdl"] = torch.empty((planes.shape[0], 3), dtype=torch.float32, device=planes.device)
+    p, v = inf(planes, **kw)
     p, v = p.double(), v.double()
     pr, vr, lr = ref_out[:3]
     # the logit deviation up to the softmax's free constant: log p - log p_ref where both are representable
@@ -989,6 +993,9 @@ def measure_against_reference(inf, ref_out, planes, legal=None, moves_left_ref=N
     if x is not None:
         out["moves_left_max_abs"] = float((x.double() - moves_left_ref.double()).abs().max())
         out["finite"] = bool(out["finite"] and torch.isfinite(x).all())
+    if wd is not None:
+        out["draw_max_abs"] = float((wd[:, 1].double() - draw_ref.double()).abs().max())
+        out["finite"] = bool(out["finite"] and torch.isfinite(wd).all())
     lg = None
     if getattr(inf, "supports_logits", lambda: False)():
         # the raw logit rows the engine's queue carries: the deviation over ALL labels, centred on its mean
@@ -1116,7 +1123,7 @@ def next_more_exact(name, n_blocks):
 
 
 def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", arith=None, device=None, tol=GUARD_TOL,
-                          planes=None, guard=None, moves_left=False):
+                          planes=None, guard=None, moves_left=False, draw=False):
     """InferenceNet(net, ...) on `device` with the tower arithmetic CHECKED: the requested arithmetic is measured against
     the float64 network on calibration positions and replaced by the next more exact one while policy or value deviate by
     more than `tol` (c8 -> c8>N with fewer and fewer c8 blocks -> f16x3 -> bf16x3 -> the fp32 library trunk).  The result
@@ -1125,8 +1132,12 @@ def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", ari
     candidate comparison -- tests of a specific kernel path want exactly what they ask for.  (A c6 request still runs the
     float64 calibration pass then: its images' exponents come from the measured activation ranges.)
     moves_left (the search's moves-left utility is on; a net with the output): the raw moves-left output is measured against
-    float64 too and has to stay within LOGIT_TOL (within_guard); off, the guard measures what it measured without it."""
+    float64 too and has to stay within LOGIT_TOL (within_guard); off, the guard measures what it measured without it.
+    draw (the search's draw average is on; a net with the win / draw / loss head): likewise the draw probability, within
+    `tol`."""
     from cchess_alphazero import _native
+    if draw and not net.wdl_head:
+        raise RuntimeError("draw=True: this network has the scalar value head (CChessNet(value_outputs=3))")
     if moves_left and not net.moves_left_head:
         raise RuntimeError("moves_left=True: this network has no moves-left output (CChessNet(moves_left=True))")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -1151,7 +1162,8 @@ def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", ari
         legal = None
         if planes is None:
             planes, legal = calibration_planes(CALIBRATION_POSITIONS, net.cfg["input_depth"], dev, with_legal=True)
-        ref = reference_forward_f64(net, planes, with_activations=True, with_moves_left=moves_left)
+        ref = reference_forward_f64(net, planes, with_activations=True, with_wdl=draw, with_moves_left=moves_left)
+        draw_ref = ref[-2 if moves_left else -1][:, 1] if draw else None     # (the entries come in this order)
         acts = ref[3]
         report = dict(tol=tol, logit_tol=LOGIT_TOL, positions=int(planes.shape[0]),
                       max_policy_probability=float(ref[0].max()),
@@ -1193,7 +1205,8 @@ def guarded_inference_net(net: CChessNet, dtype=torch.float32, trunk="mfma", ari
             if cand is None:
                 cand = InferenceNet(net, dtype, trunk=trunk, arith=name, act_shift=shift,
                                     act_exps=exps if name.startswith("c6") else None).to(dev)
-            m = measure_against_reference(cand, ref, planes, legal, moves_left_ref=ref[-1] if moves_left else None)
+            m = measure_against_reference(cand, ref, planes, legal, moves_left_ref=ref[-1] if moves_left else None,
+                                          draw_ref=draw_ref)
             m["arith"] = name
             report["candidates"].append(m)
             if within_guard(m, tol):

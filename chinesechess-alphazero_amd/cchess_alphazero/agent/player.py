@@ -45,10 +45,14 @@ class MovesLeftUnavailable(ValueError):
 MOVES_LEFT_REFUSAL = search_options.MOVES_LEFT_REFUSAL
 
 
+class DrawUnavailable(ValueError):
+    """The draw average was asked for and the network behind the pipe has the scalar value head."""
+
+
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
                  debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None,
-                 moves_left_slope=None, moves_left_cap=None):
+                 moves_left_slope=None, moves_left_cap=None, draw_score=None, show_wdl=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -85,9 +89,17 @@ class CChessPlayer:
         self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
         self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
         self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
-        search_options.check(opts, moves_left=self.moves_left)
+        # draw average (search_options.py DRAW_EXCLUDES): likewise; on with a draw score or with show_wdl, which adds `wdl W D
+        # L` to the info lines; the pipe's network must have the win / draw / loss head (DrawUnavailable otherwise)
+        self.draw_score = float(getattr(ec, "draw_score", 0.0) if draw_score is None else draw_score)
+        self.show_wdl = bool(getattr(ec, "show_wdl", False) if show_wdl is None else show_wdl)
+        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
+        self.last_wdl = None                   # show_wdl: (W, D, L) in permille of the move action() chose
+        search_options.check(opts, moves_left=self.moves_left, draw=self.draw)
         if self.moves_left and not getattr(pipes, "moves_left_head", False):
             raise MovesLeftUnavailable(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
+        if self.draw and not getattr(pipes, "wdl_head", False):
+            raise DrawUnavailable(search_options.DRAW_REFUSAL.format(score=self.draw_score, show_wdl=self.show_wdl))
         vars(self).update(opts)                # self.solver, self.smart_pruning
         pc = self.play_config
         # simulation count from play_config, lock-step batch from config.play (player.py:155-174)
@@ -106,13 +118,17 @@ class CChessPlayer:
         search_options.apply(self._search, opts)
         if self.moves_left:
             self._search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
+        if self.draw:
+            self._search.set_draw(True, self.draw_score)
 
     # -- network access: device fast path, or the reference's pipe protocol --
-    def _evaluate(self, planes, moves_left=False):
+    def _evaluate(self, planes, moves_left=False, wdl=False):
         """(policy, value) of the planes; moves_left (the utility is on: a device pipe whose network has the output): a third
-        tensor, the raw moves-left output."""
+        tensor, the raw moves-left output; wdl (the draw average is on: likewise): the win / draw / loss rows [n, 3]."""
         if moves_left:
             return self.pipe.evaluate_device(planes, moves_left=True)
+        if wdl:
+            return self.pipe.evaluate_device(planes, wdl=True)
         if hasattr(self.pipe, "evaluate_device"):
             return self.pipe.evaluate_device(planes)
         self.pipe.send(list(planes.float().cpu().numpy()))
@@ -155,6 +171,20 @@ class CChessPlayer:
             planes = senv.state_to_planes(state)
         p, v = self._evaluate(t.from_numpy(np.asarray(planes, dtype=np.float32)[None]).cuda())
         return p[0].float().cpu().numpy(), float(v[0])
+
+    def root_wdl(self, label, stats=None):
+        """show_wdl: (W, D, L) in permille of the root edge with the move label `label`, for the side to move (uci.wdl_permille);
+        None while the option is off, for a move that is not a root edge and for an edge without a visit."""
+        if not (self.draw and self.show_wdl):
+            return None
+        from cchess_alphazero.uci import wdl_permille
+        st = stats if stats is not None else self._search.root_stats()
+        dr = self._search.node_draws()
+        hit = np.nonzero(st["moves"][0, :int(st["counts"][0])] == int(label))[0]
+        if not len(hit):
+            return None
+        j = int(hit[0])
+        return wdl_permille(float(st["w"][0, j]), int(st["n"][0, j]), int(dr["dsum"][0, j]), int(dr["dn"][0, j]))
 
     def principal_variation(self, state, no_act=None, max_len=20):
         """Most-visited line from the root (print_depth_info, player.py:408-433: `>=` keeps the LAST maximum; banned
@@ -209,7 +239,9 @@ class CChessPlayer:
                 value = -value
         duration = max(time() - start_time, 1e-9)
         nps = int(depth * 100 / duration) * 1000
-        out = f"info depth {depth} score {int(value * 1000)} time {int(duration * 1000)} pv" + pv + f" nps {nps}"
+        wdl = self.root_wdl(labels[0]) if len(labels) else None      # (the reported move: the line's first)
+        shown = f"{int(value * 1000)}" + (" wdl {} {} {}".format(*wdl) if wdl else "")
+        out = f"info depth {depth} score {shown} time {int(duration * 1000)} pv" + pv + f" nps {nps}"
         stream = self.out or sys.stdout
         print(out, file=stream)
         logger.debug(out)
@@ -257,10 +289,12 @@ class CChessPlayer:
                 if pending == 0:
                     break
                 if rows.numel():                               # exactly the positions the reference would send (:112-120)
-                    p, v, *x = self._evaluate(s.planes.index_select(0, rows), moves_left=self.moves_left)
+                    p, v, *x = self._evaluate(s.planes.index_select(0, rows), moves_left=self.moves_left, wdl=self.draw)
                     s.policy.index_copy_(0, rows, p.float())
                     s.value.index_copy_(0, rows, v.float())
-                    if x:
+                    if x and self.draw:
+                        s.wdl_rows.index_copy_(0, rows, x[0].float())
+                    elif x:
                         s.moves_left_x.index_copy_(0, rows, x[0].float())
                 if self.job_done and not stopped:
                     s.stop()                                   # the next round backs up what is in flight
@@ -294,6 +328,7 @@ class CChessPlayer:
                 self.proof = (max(0, int(pr["status"][0])), int(pr["dist"][0]))
             action = int(s.choose([float(np.random.random_sample())])[0])
             self.last_action = self.labels[action] if action >= 0 else None
+            self.last_wdl = self.root_wdl(action, st) if action >= 0 else None
             if action < 0:
                 return None, list(policy)                      # resign: un-normalised counts (player.py:189-190)
             # the node behind the chosen move, for callers that read it from the tree they passed in

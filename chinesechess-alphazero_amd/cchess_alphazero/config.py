@@ -105,6 +105,9 @@ class EngineConfig(_Section):
                          # moves-left utility (run.py self / eval --moves-left-slope S --moves-left-cap C, the UCI options
                          # MovesLeftSlope / MovesLeftCap): off at slope 0; needs a model with the moves-left output
                          **search_options.MOVES_LEFT_DEFAULTS,
+                         # draw average (run.py self / eval --draw-score S, the UCI options DrawScore / UCI_ShowWDL): on when
+                         # draw_score != 0 or show_wdl; needs a model with the win / draw / loss value head
+                         **search_options.DRAW_DEFAULTS,
                          # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
                          **search_options.DEFAULTS)
 

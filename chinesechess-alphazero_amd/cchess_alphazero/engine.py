@@ -23,7 +23,7 @@ from cchess_alphazero.agent.model import CChessNet, guarded_inference_net
 from cchess_alphazero.environment.lookup_tables import ActionLabelsRed
 from cchess_alphazero.environment.static_env import INIT_STATE, array_to_state
 from cchess_alphazero.lib.data_helper import record_item
-from cchess_alphazero.search_options import MOVES_LEFT_REFUSAL
+from cchess_alphazero.search_options import DRAW_REFUSAL, MOVES_LEFT_REFUSAL
 
 logger = getLogger(__name__)
 
@@ -46,7 +46,7 @@ class SelfPlayEngine:
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
                  kld_gain=None, kld_interval=None, resign_audit=None, script=None, moves_left_slope=None,
-                 moves_left_cap=None):
+                 moves_left_cap=None, draw_score=None, show_wdl=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -76,19 +76,31 @@ class SelfPlayEngine:
         what search_options.MOVES_LEFT_EXCLUDES lists, and a script.  The network must have the moves-left output (`run.py
         opt --moves-left`; a ValueError otherwise, here and in set_network); every forward then also fills
         search.moves_left_x (the tail launch is cz_heads_tail_ml), and the load-time guard and audit_network measure that
-        output too.  An evaluator callable returns (policy, value, x)."""
+        output too.  An evaluator callable returns (policy, value, x).
+        draw_score, show_wdl (None = config.engine's values): the draw average of the search (Search.set_draw), on with a draw
+        score other than 0 or with show_wdl.  It stands beside the table the same way: check(draw=True) refuses what
+        search_options.DRAW_EXCLUDES lists, a script and the moves-left utility.  The network must have the win / draw / loss
+        value head (`run.py opt --value-head wdl`; a ValueError otherwise, here and in set_network); every forward then also
+        fills search.wdl_rows, and the load-time guard and audit_network measure the draw probability too.  An evaluator
+        callable returns (policy, value, wdl [n, 3])."""
         ec_ = getattr(config, "engine", None)
         self.moves_left_slope = float(getattr(ec_, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
         self.moves_left_cap = float(getattr(ec_, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
         self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
+        self.draw_score = float(getattr(ec_, "draw_score", 0.0) if draw_score is None else draw_score)
+        self.show_wdl = bool(getattr(ec_, "show_wdl", False) if show_wdl is None else show_wdl)
+        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
             gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
             solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
-        search_options.check(opts, history=use_history, script=script is not None, moves_left=self.moves_left)
+        search_options.check(opts, history=use_history, script=script is not None, moves_left=self.moves_left,
+                             draw=self.draw)
         if self.moves_left and evaluator is None and net is not None and not net.moves_left_head:
             raise ValueError(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
+        if self.draw and evaluator is None and net is not None and not net.wdl_head:
+            raise ValueError(DRAW_REFUSAL.format(score=self.draw_score, show_wdl=self.show_wdl))
         self.resign_audit = bool(getattr(getattr(config, "engine", None), "resign_audit", False)
                                  if resign_audit is None else resign_audit)
         if self.resign_audit and not opts["record_visits"]:
@@ -113,6 +125,8 @@ class SelfPlayEngine:
                 net = CChessNet.from_model_config(config.model)
                 if self.moves_left and not net.moves_left_head:
                     raise ValueError(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
+                if self.draw and not net.wdl_head:
+                    raise ValueError(DRAW_REFUSAL.format(score=self.draw_score, show_wdl=self.show_wdl))
             self.model_cfg = net.cfg
             if trunk is None:
                 trunk = getattr(getattr(config, "engine", None), "net_trunk", "mfma")
@@ -160,6 +174,8 @@ class SelfPlayEngine:
         search_options.apply(self.search, opts, skip=("eval_cache",))
         if self.moves_left:                    # (its rows, search.moves_left_x, are allocated here: fixed for a graph capture)
             self.search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
+        if self.draw:                          # (likewise search.wdl_rows)
+            self.search.set_draw(True, self.draw_score)
         self.script = script
         if script is not None:                 # last: the library checks it against everything that is on
             self.search.set_script(*script)
@@ -170,7 +186,7 @@ class SelfPlayEngine:
         engine changes here: a guard that raises (out of memory, a damaged weight file) leaves the games on the old network."""
         guard = getattr(getattr(self.config, "engine", None), "arith_guard", True)
         return guarded_inference_net(net, self.dtype, trunk=self.trunk, arith=self.arith, device=self.device,
-                                     guard=None if guard else False, moves_left=self.moves_left)
+                                     guard=None if guard else False, moves_left=self.moves_left, draw=self.draw)
 
     def _install(self, net, built=None):
         self.net = built if built is not None else self._build_net(net)
@@ -214,6 +230,8 @@ class SelfPlayEngine:
             raise ValueError(f"hot reload: topology changed ({self.model_cfg} -> {net.cfg})")
         if self.moves_left and not net.moves_left_head:
             raise ValueError("hot reload: " + MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
+        if self.draw and not net.wdl_head:     # (likewise the draw average and the win / draw / loss head)
+            raise ValueError("hot reload: " + DRAW_REFUSAL.format(score=self.draw_score, show_wdl=self.show_wdl))
         torch.cuda.synchronize(self.device)
         built = self._build_net(net)                           # may raise: nothing has been touched yet
         had_graph = self._graph is not None
@@ -272,8 +290,9 @@ class SelfPlayEngine:
         planes = planes[planes.flatten(1).ne(0).any(1)].contiguous()          # (a slot no leaf was ever written to is an empty board)
         if planes.shape[0] == 0:
             return None
-        ref = reference_forward_f64(self._ref_net, planes, with_moves_left=self.moves_left)
-        m = measure_against_reference(self.net, ref, planes, moves_left_ref=ref[-1] if self.moves_left else None)
+        ref = reference_forward_f64(self._ref_net, planes, with_wdl=self.draw, with_moves_left=self.moves_left)
+        m = measure_against_reference(self.net, ref, planes, moves_left_ref=ref[-1] if self.moves_left else None,
+                                      draw_ref=ref[-1][:, 1] if self.draw else None)     # (never both: they exclude each other)
         m["ok"] = within_guard(m)
         m["arith"] = self.net_arith_effective
         m["positions"] = int(planes.shape[0])
@@ -336,14 +355,17 @@ class SelfPlayEngine:
             p, v, *x = self.evaluator(s.planes)
             if self.moves_left:
                 s.moves_left_x.copy_(x[0])
+            if self.draw:
+                s.wdl_rows.copy_(x[0])
         else:
             out = (s.policy, s.value)
             ml = s.moves_left_x if self.moves_left else None   # (the rows of `value`: by slot, or by compact row)
+            kw = dict(wdl=s.wdl_rows) if self.draw else {}     # (likewise: the draw average's rows)
             if self.compact:
                 p, v = self.net(s.planes, rows=s.q_rows, count=s.q_count, out=out, logits=self.policy_logits, masks=s.masks,
-                                moves_left=ml)
+                                moves_left=ml, **kw)
             else:
-                p, v = self.net(s.planes, out=out, logits=self.policy_logits, masks=s.masks, moves_left=ml)
+                p, v = self.net(s.planes, out=out, logits=self.policy_logits, masks=s.masks, moves_left=ml, **kw)
             if p is s.policy:                                  # written in place (the hand-written network path)
                 return
         s.policy.copy_(p)

@@ -76,6 +76,11 @@ _FLAGS = [
                                      "(`run.py opt --moves-left`) (finite, >= 0; 0 = off; lc0 uses 0.0027)")),
     ("--moves-left-cap", dict(type=float, default=0.0345, metavar="C",
                               help="(self, eval, with --moves-left-slope) the bound of the utility before f(|q|) (finite, >= 0)")),
+    ("--draw-score", dict(type=float, default=0.0, metavar="S",
+                          help="(self, eval) draw score: the search keeps a mean draw probability per edge and adds +-S * that "
+                               "mean to an edge's score, S being what a draw is worth to the side to move at the root (so S < 0 "
+                               "avoids draws and S > 0 seeks them); needs a model with the win / draw / loss value head "
+                               "(`run.py opt --value-head wdl`) (finite, in [-1, 1]; 0 = off)")),
     ("--value-head", dict(choices=["scalar", "wdl"], default=None,
                           help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
@@ -141,12 +146,17 @@ def build_config(args):
         ml_on = search_options.check_moves_left(args.moves_left_slope, args.moves_left_cap, flags=True)
         if ml_on and args.cmd not in ("self", "eval", "reanalyse"):
             raise search_options.SearchOptionError("--moves-left-slope is an option of `run.py self` and `run.py eval`")
+        draw_on = search_options.check_draw(args.draw_score, flags=True)
+        if draw_on and args.cmd not in ("self", "eval", "reanalyse"):
+            raise search_options.SearchOptionError("--draw-score is an option of `run.py self` and `run.py eval`")
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
-                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on)
+                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on,
+                             draw=draw_on)
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
     vars(engine).update(values)
     engine.moves_left_slope, engine.moves_left_cap = float(args.moves_left_slope), float(args.moves_left_cap)
+    engine.draw_score = float(args.draw_score)
     # the resignation audit: game-loop options, not search options; their one check is the library's
     from cchess_alphazero.lib.resign_audit import check_options
     try:

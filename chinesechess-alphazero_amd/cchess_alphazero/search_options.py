@@ -165,6 +165,29 @@ def check_moves_left(slope, cap, flags=False):
     return slope > 0.0
 
 
+# The draw average (run.py self / eval --draw-score, engine.draw_score and engine.show_wdl, Search.set_draw) stands beside the
+# table the same way: it needs a network with the win / draw / loss value head.  check(draw=True) refuses these beside it, a
+# script, and the moves-left utility; consulted after the moves-left utility.  The library's setters hold the same list
+# (csrc/xq_search.hip DRAW_EXCLUDES; tests/test_gpu_draw_search.py pins the two to each other).
+_DRAW_WORD3 = "the Gumbel search keeps the network value in the node header word that holds the leaf's draw probability"
+DRAW_EXCLUDES = (("gumbel", _DRAW_WORD3), ("solver", _ML_KERNEL), ("kld_gain", _ML_KERNEL), ("smart_pruning", _ML_KERNEL),
+                 ("eval_cache", _ML_KERNEL + ", and a cache entry holds no draw probability"))
+DRAW_SCRIPT = "reanalysis searches with the recorded games' own rule"
+DRAW_MOVES_LEFT = "an edge's draw record lies where its moves-left record would"
+DRAW_REFUSAL = ("the draw average (draw_score {score:g}, show_wdl {show_wdl}) needs a model with the win / draw / loss value "
+                "head: train one with `run.py opt --value-head wdl`")
+DRAW_DEFAULTS = dict(draw_score=0.0, show_wdl=False)
+DRAW_LOG = ("draw average: a draw is worth {draw_score:g} to the side to move at the root; every edge keeps the mean draw "
+            "probability of its simulations")
+
+
+def check_draw(score, show_wdl=False, flags=False):
+    """Raises SearchOptionError unless score is finite and in [-1, 1]; True when the average is on (score != 0 or show_wdl)."""
+    if not (isinstance(score, (int, float)) and -1.0 <= score <= 1.0):      # (False for NaN)
+        raise SearchOptionError(f"{'--draw-score' if flags else 'draw_score'} {score}: expected a finite value in [-1, 1]")
+    return score != 0.0 or bool(show_wdl)
+
+
 VALUES = {v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 
@@ -192,7 +215,8 @@ def check(values, flags=False, cmd=None, sims=None, **context):
     flags: the messages name --kld-gain where they would name kld_gain.  cmd: the run.py command (None: not checked);
     sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
     input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES), moves_left=True for the moves-left
-    utility (checked after that: MOVES_LEFT_EXCLUDES, and a script)."""
+    utility (checked after that: MOVES_LEFT_EXCLUDES, and a script), draw=True for the draw average (checked after that:
+    DRAW_EXCLUDES, a script, and the moves-left utility)."""
     def name(key):
         return VALUES[key].flag if flags else key
 
@@ -229,6 +253,15 @@ def check(values, flags=False, cmd=None, sims=None, **context):
                 raise SearchOptionError(f"{ml} excludes {name(key)}: {why}")
         if context.get("script"):
             raise SearchOptionError(f"{ml} excludes a script: {MOVES_LEFT_SCRIPT}")
+    if context.get("draw"):
+        dr = "--draw-score" if flags else "draw_score"
+        for key, why in DRAW_EXCLUDES:
+            if on(key):
+                raise SearchOptionError(f"{dr} excludes {name(key)}: {why}")
+        if context.get("script"):
+            raise SearchOptionError(f"{dr} excludes a script: {DRAW_SCRIPT}")
+        if context.get("moves_left"):
+            raise SearchOptionError(f"{dr} excludes {'--moves-left-slope' if flags else 'moves_left_slope'}: {DRAW_MOVES_LEFT}")
 
 
 def apply(search, values, skip=()):

@@ -3,7 +3,7 @@
 Same command set, option names and output lines as the reference front-end:
     uci, isready, ucinewgame, setoption name {gpu|Threads} value N, position {fen F | startpos} [moves ...], fen F ...,
     go [depth N] [movetime MS | time MS] [infinite] [wtime MS] [btime MS], stop, quit
-    -> "info depth D score S time T [pv ...] nps N" and "bestmove M [ponder P]"
+    -> "info depth D score S [wdl W D L] time T [pv ...] nps N" and "bestmove M [ponder P]"
 `depth N` means N * 100 simulations, a clock (`wtime` / `btime`) caps the search at depth 30, `movetime` arms a timer
 that stops the search 10 ms early (uci.py:211-236).  One search at a time; the search runs on its own thread and a
 `stop` (or the timer) ends it through CChessPlayer.close_and_return_action.
@@ -26,7 +26,27 @@ ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference),
              "option name Solver type check default false",
              "option name SmartPruning type check default false",
              "option name MovesLeftSlope type string default 0",
-             "option name MovesLeftCap type string default 0.0345")
+             "option name MovesLeftCap type string default 0.0345",
+             "option name UCI_ShowWDL type check default false",
+             "option name DrawScore type string default 0")
+
+
+def wdl_permille(w, n, dsum, dn):
+    """(W, D, L) in permille for the mover of a root edge with the statistics w, n and the draw record dsum, dn (quanta of
+    2^-20, cz_search_set_draw); None when n = 0.  a = clamp(w / n, -1, 1) (terminal values are doubled), dbar = dsum / 2^20 /
+    dn (0 without a backup), dd = min(dbar, 1 - |a|), W = (1 + a - dd) / 2, L = (1 - a - dd) / 2, rounded half up; D is what
+    is left of 1000."""
+    import math
+    if n <= 0:
+        return None
+    a = max(-1.0, min(1.0, float(w) / float(n)))
+    dbar = (float(dsum) / 1048576.0) / float(dn) if dn > 0 else 0.0
+    dd = min(dbar, 1.0 - abs(a))
+    win = int(math.floor(1000.0 * ((1.0 + a - dd) / 2.0) + 0.5))
+    loss = int(math.floor(1000.0 * ((1.0 - a - dd) / 2.0) + 0.5))
+    if win + loss > 1000:                                 # (dd = 0 and both halves end on .5: the larger one gives way)
+        win, loss = (win - 1, loss) if win > loss else (win, loss - 1)
+    return win, 1000 - win - loss, loss
 
 
 class UCI:
@@ -111,6 +131,16 @@ class UCI:
                     setattr(self.config.engine, key, v)
                 except ValueError:
                     self._say(f"info string {args[1]} {args[3]}: expected a finite value >= 0")
+            elif args[1] == "UCI_ShowWDL":                # W / D / L of the reported move in every info line that has a score
+                self.config.engine.show_wdl = args[3].lower() == "true"    # (the draw average: cz_search_set_draw)
+            elif args[1] == "DrawScore":                  # what a draw is worth to the side to move: likewise
+                try:
+                    v = float(args[3])
+                    if not -1.0 <= v <= 1.0:
+                        raise ValueError(args[3])
+                    self.config.engine.draw_score = v
+                except ValueError:
+                    self._say(f"info string DrawScore {args[3]}: expected a finite value in [-1, 1]")
 
     def cmd_position(self, args):
         if not self.is_ready:
@@ -158,7 +188,7 @@ class UCI:
     def cmd_go(self, args):
         if not self.is_ready:
             return
-        from cchess_alphazero.agent.player import CChessPlayer, MovesLeftUnavailable
+        from cchess_alphazero.agent.player import CChessPlayer, DrawUnavailable, MovesLeftUnavailable
         self._finish_worker()
         depth, infinite, budget = None, True, None
         for i, a in enumerate(args):
@@ -172,14 +202,19 @@ class UCI:
                 budget, depth, infinite = int(args[i + 1]) / 1000, 3000, False
         self.start_time = time()
         self.search_tree = {}
-        try:
-            self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
-                                       debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2)
-        except MovesLeftUnavailable as e:                 # the model has no moves-left output: say so and search without it
-            self._say(f"info string {e}")
-            self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
-                                       debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2,
-                                       moves_left_slope=0.0)
+        without = {}
+        while True:
+            try:
+                self.player = CChessPlayer(self.config, search_tree=self.search_tree, pipes=self.pipe, enable_resign=False,
+                                           debugging=True, uci=True, use_history=self.use_history, side=self.turns % 2,
+                                           **without)
+                break
+            except MovesLeftUnavailable as e:             # the model has no moves-left output: say so and search without it
+                self._say(f"info string {e}")
+                without["moves_left_slope"] = 0.0
+            except DrawUnavailable as e:                  # the model has the scalar value head: likewise
+                self._say(f"info string {e}")
+                without.update(draw_score=0.0, show_wdl=False)
         self.player.out = self.out
         self.player._idle.clear()                         # a `stop` that beats the worker to the player must wait for it
         with self._lock:
@@ -251,7 +286,7 @@ class UCI:
         if ret is None:
             self._say("bestmove none")
         else:
-            self.info_best_move(*ret)
+            self.info_best_move(*ret, wdl=getattr(player, "last_wdl", None))
         if self.player is player:
             self.player = None
 
@@ -264,9 +299,10 @@ class UCI:
             self.player = None
         self._worker = None
 
-    def info_best_move(self, action, value, depth, proof=None):
+    def info_best_move(self, action, value, depth, proof=None, wdl=None):
         """proof: the root's (status, d) of the MCTS solver, when it is on: a proven root is reported as `score mate N`,
-        N moves of the side to move, negative when it is the one being mated."""
+        N moves of the side to move, negative when it is the one being mated.  wdl (UCI_ShowWDL): the played move's
+        (W, D, L) in permille for the side to move, printed behind the score."""
         if not self.is_red_turn:
             value = -value
         duration = max(time() - self.start_time, 1e-9)
@@ -274,6 +310,8 @@ class UCI:
         mate = mate_in(*proof) if proof else None
         if mate is not None:
             score = f"mate {mate}"
+        if wdl is not None:
+            score += " wdl {} {} {}".format(*wdl)
         self._say(f"info depth {depth} score {score} time {int(duration * 1000)} "
                   f"nps {int(depth * 100 / duration) * 1000}")
         ponder = None

@@ -96,6 +96,26 @@ def _with_moves_left(e, slope):
     return forward
 
 
+def _with_wdl(e, score, show_wdl):
+    """Likewise for the draw average: planes -> (policy, value, wdl [n, 3]) of an InferenceNet or a DevicePipe's
+    evaluate_device whose network has the win / draw / loss head (a ValueError names `run.py opt --value-head wdl` otherwise)."""
+    import torch
+    net = e if hasattr(e, "wdl_head") else None
+    pipe = getattr(e, "__self__", None) if net is None else None
+    if net is None and not hasattr(pipe, "wdl_head"):
+        return e
+    if not (net if net is not None else pipe).wdl_head:
+        raise ValueError(search_options.DRAW_REFUSAL.format(score=score, show_wdl=show_wdl) + " (in the arena both models need it)")
+    if pipe is not None:
+        return lambda planes: e(planes, wdl=True)
+
+    def forward(planes):
+        rows = torch.empty((planes.shape[0], 3), dtype=torch.float32, device=planes.device)
+        p, v = net(planes, wdl=rows)
+        return p, v, rows
+    return forward
+
+
 class EvaluateWorker:
     def __init__(self, config, pipes1=None, pipes2=None, pid=None, evaluators=None, dtype=_native.F32, seed=0):
         """evaluators: (eval_best, eval_next), callables planes -> (policy, value) on the device -- (policy, value, x) while
@@ -127,8 +147,15 @@ class EvaluateWorker:
         self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0))
         self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345))
         self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
-        search_options.check(opts, moves_left=self.moves_left)
+        # draw average of both models' searches (run.py eval --draw-score S; search_options.DRAW_EXCLUDES): both networks
+        # need the win / draw / loss head
+        self.draw_score = float(getattr(ec, "draw_score", 0.0))
+        self.show_wdl = bool(getattr(ec, "show_wdl", False))
+        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
+        search_options.check(opts, moves_left=self.moves_left, draw=self.draw)
         self._eval3 = tuple(_with_moves_left(e, self.moves_left_slope) for e in evaluators) if self.moves_left else None
+        if self.draw:
+            self._eval3 = tuple(_with_wdl(e, self.draw_score, self.show_wdl) for e in evaluators)
         self.concurrent = True         # the two models' searches of a ply on two streams / host threads
         # compact evaluation queue (cz_search_round_q): both evaluators are inference networks whose kernels read the
         # leaf count on the device
@@ -160,6 +187,8 @@ class EvaluateWorker:
             if self.moves_left:                            # (fixed pointers: the search object's own rows)
                 self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value),
                                    moves_left=s.moves_left_x)
+            elif self.draw:
+                self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value), wdl=s.wdl_rows)
             else:
                 self.evaluators[k](s.planes, rows=s.q_rows, count=s.q_count, out=(s.policy, s.value))
         one_round()
@@ -197,6 +226,8 @@ class EvaluateWorker:
             search_options.apply(s, vars(self))                # (the three attributes above)
             if self.moves_left:
                 s.set_moves_left(self.moves_left_slope, self.moves_left_cap)
+            if self.draw:
+                s.set_draw(True, self.draw_score)
 
         def counters_now():
             c = [s.counters() for s in searches]
@@ -314,6 +345,9 @@ class EvaluateWorker:
                             if self.moves_left:
                                 p, v, x = self._eval3[k](s.planes.index_select(0, leaf))
                                 s.moves_left_x.index_copy_(0, leaf, x.float())
+                            elif self.draw:
+                                p, v, x = self._eval3[k](s.planes.index_select(0, leaf))
+                                s.wdl_rows.index_copy_(0, leaf, x.float())
                             else:
                                 p, v = self.evaluators[k](s.planes.index_select(0, leaf))
                             s.policy.index_copy_(0, leaf, p.float())

@@ -110,6 +110,8 @@ class SelfPlayWorker:
             logger.info(f"Process {self.pid}-{self.rank}: "
                         + search_options.MOVES_LEFT_LOG.format(moves_left_slope=self.engine.moves_left_slope,
                                                                moves_left_cap=self.engine.moves_left_cap))
+        if self.engine.draw:
+            logger.info(f"Process {self.pid}-{self.rank}: " + search_options.DRAW_LOG.format(draw_score=self.engine.draw_score))
         if self.resign_audit is not None:
             logger.info(f"Process {self.pid}-{self.rank}: resignation audit of the no-resign games, threshold "
                         f"{self.engine.resign_threshold:g}"

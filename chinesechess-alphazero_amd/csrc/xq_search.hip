@@ -16,6 +16,7 @@
 // is about to attach, and the k_sim launches are the k_sim_cached instantiations, whose new leaves ask the table in step 4.
 // With the moves-left utility on (cz_search_set_moves_left) the k_sim launches are the k_sim_ml instantiations, and k_reserve_ml
 // runs between k_advance and k_sim(SELECT): the statistics blocks are twice the size, and it reserves the difference.
+// With the draw average on (cz_search_set_draw) they are the k_sim_draw instantiations, with k_reserve_ml in the same place.
 // The host then runs ONE network forward over the whole queue.
 // There is no host decision inside a round and no device->host copy, so a round (kernel + network
 // forward) can be replayed from a HIP graph.
@@ -28,6 +29,7 @@
 //   xq_search_tree.h      SearchLDS, EdgeStat, GameView, node and edge accessors, counters, the generator, keys and hash, backup
 //   xq_search_attach.h    prior spreading and the attach of an evaluated leaf (prior_norm, attach_policy, attach_and_backup)
 //   xq_search_ml.h        the moves-left utility: MovesLeftState, MRec, ml_quanta, wave_add_i64, backup_m, ml_edge_d, ml_utility
+//   xq_search_draw.h      the draw average: DrawState, DRec, draw_quanta, backup_d, draw_sigma, draw_term
 //   xq_search_select.h    RootCtx and PUCT at the root, the Gumbel helpers, gumbel_interior, select_gumbel, select_edge
 //   xq_search_solver.h    the MCTS solver: its bit fields, solve_*, select_solve
 //   xq_search_sim.h       one simulation: Deferred, write_planes, expand_node, the cache probe, run_sim, flush_deferred
@@ -36,8 +38,8 @@
 //                         new_script_game, script_move
 //   xq_search_selfplay.h  advance_game
 //   xq_search_stop.h      the early stop of a settled ply: stop_reset, ply_settled
-//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop / k_sim_ml, k_reserve_ml, k_cache_fill,
-//                         k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise
+//   xq_search_round.h     sim_body, k_sim / k_sim_cached / k_sim_solve / k_sim_stop / k_sim_ml / k_sim_draw, k_reserve_ml,
+//                         k_cache_fill, k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise
 //   xq_search_aux.h       every other kernel (k_start_selfplay, k_start_script .. k_debug_sqrt) and walk_path
 // This file keeps the includes and the host side: the opaque search object and the C-ABI entry points.
 #include <hip/hip_runtime.h>
@@ -60,6 +62,7 @@ extern "C" void czi_set_error(const char* msg);   // xq_kernels.hip
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
 #include "xq_search_ml.h"
+#include "xq_search_draw.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
@@ -92,6 +95,7 @@ struct cz_search {
     ScriptState X{};                  // scripted games (cz_search_set_script); X.n 0 = off
     void* script_mem = nullptr;       // boards, labels, offsets and z, in one allocation
     MovesLeftState M{};               // moves-left utility (cz_search_set_moves_left); M.slope 0 = off
+    DrawState D{};                    // draw average (cz_search_set_draw); D.on 0 = off
 };
 
 namespace {
@@ -171,7 +175,8 @@ size_t layout(cz_search* s, char* base, bool dry)
 }
 
 // chunks a game needs for one full search on an empty tree (what it keeps through resets and between games)
-// ml: the moves-left utility is on, a statistics block carries one M record per edge (reserve_ply<true>)
+// ml: the moves-left utility or the draw average is on, a statistics block carries one M / D record per edge
+// (reserve_ply<true>)
 int keep_chunks_for(int sims, bool ml = false)
 {
     const long long PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + (ml ? 2 : 1) * RESERVE_MOVES;
@@ -453,8 +458,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool stop = s->stop_mem != nullptr;                   // (never with gum, cache or solve: cz_search_set_kld_gain)
     const bool script = s->X.n > 0 && s->P.mode == MODE_SELFPLAY;   // (never with gum, solve or stop: cz_search_set_script)
     const bool ml = s->M.slope > 0.0;                           // (never with gum, solve, stop, cache or a script: cz_search_set_moves_left)
+    const bool draw = s->D.on != 0;                             // (never with ml or what ml is never with: cz_search_set_draw)
     auto sim = [&](int mask, int cq) {
-        if (ml) {
+        if (draw) {
+            if (hist) hipLaunchKernelGGL((k_sim_draw<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
+            else hipLaunchKernelGGL((k_sim_draw<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
+        } else if (ml) {
             if (hist) hipLaunchKernelGGL((k_sim_ml<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
             else hipLaunchKernelGGL((k_sim_ml<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
         } else if (stop) {
@@ -483,7 +492,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     else if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
-    if (ml) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
+    if (ml || draw) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
@@ -513,7 +522,7 @@ int cz_search_set_sims(cz_search* s, int simulation_num_per_move)
     s->P.sims = simulation_num_per_move;
     // a game that has to drop its tree keeps enough chunks for one full search of the NEW length (never fewer than it
     // was created with: the initial pool layout gave every game that many)
-    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0);
+    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0 || s->D.on != 0);
     if (keep > s->P.max_chunks) keep = s->P.max_chunks;
     if (keep > s->keep_chunks_created) s->P.keep_chunks = keep;
     else s->P.keep_chunks = s->keep_chunks_created;
@@ -592,6 +601,10 @@ static_assert(features_symmetric(), "the exclusion matrix is symmetric and no fe
 // excludes the features of ML_EXCLUDES and they exclude it, consulted last.
 constexpr unsigned ML_EXCLUDES = fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT);
 constexpr const char* ML_PHRASE = "the moves-left utility is on (cz_search_set_moves_left)";
+// The draw average (cz_search_set_draw) stands there too, consulted after the moves-left utility: it excludes the features of
+// DRAW_EXCLUDES and the moves-left utility (its D records lie in the M records' granules), and they exclude it.
+constexpr unsigned DRAW_EXCLUDES = ML_EXCLUDES;
+constexpr const char* DRAW_PHRASE = "the draw average is on (cz_search_set_draw)";
 static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream)
 {
     for (int o = 0; on && o < F_COUNT; ++o)
@@ -603,6 +616,11 @@ static int admit(const cz_search* s, Feature f, bool on, const char* entry, void
     if (on && (ML_EXCLUDES >> f & 1) && s->M.slope > 0.0) {
         char buf[160];
         snprintf(buf, sizeof(buf), "%s: %s", entry, ML_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
+    if (on && (DRAW_EXCLUDES >> f & 1) && s->D.on) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", entry, DRAW_PHRASE);
         return serr(CZ_ERR_ARG, buf);
     }
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
@@ -993,6 +1011,7 @@ int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float
             snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
             return serr(CZ_ERR_ARG, buf);
         }
+    if (on && s->D.on) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the draw average is on (cz_search_set_draw)");
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->M.slope > 0.0;
@@ -1034,6 +1053,68 @@ int cz_moves_left_quanta(const float* x, int32_t* k, int n, void* stream)
     if (n == 0) return CZ_OK;
     hipLaunchKernelGGL(k_ml_quanta, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, k, n);
     S_LAUNCH_CHECK("cz_moves_left_quanta");
+    return CZ_OK;
+}
+
+// ---- draw average (include/czero.h) ----------------------------------------------------------------------------------------
+int cz_search_set_draw(cz_search* s, int on_, double score, const float* wdl_rows, void* stream)
+{
+    const char* const me = "cz_search_set_draw";
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_draw: null handle");
+    if (!(score >= -1.0 && score <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_draw: score outside [-1, 1] or not finite");
+    const bool on = on_ != 0;
+    if (on && !wdl_rows) return serr(CZ_ERR_ARG, "cz_search_set_draw: wdl_rows is NULL");
+    for (int o = 0; on && o < F_COUNT; ++o)
+        if ((DRAW_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    if (on && s->M.slope > 0.0) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", me, ML_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return serr_hip(me, e);
+    const bool was = s->D.on != 0;
+    s->D.on = on ? 1 : 0;
+    s->D.score = on ? score : 0.0;
+    s->D.wdl = on ? wdl_rows : nullptr;
+    if (was == on) return CZ_OK;
+    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
+    int keep = keep_chunks_for(s->P.sims, on);
+    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
+    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
+    return cz_search_reset_trees(s, stream);
+}
+
+int cz_search_node_draws(cz_search* s, const uint16_t* path, int path_len, int64_t* dsum, int32_t* dn, int32_t* dq_net,
+                         uint8_t* counts, void* stream)
+{
+    if (!s || path_len < 0 || path_len > MAXD_LDS || (path_len > 0 && !path))
+        return serr(CZ_ERR_ARG, "cz_search_node_draws: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (!s->D.on) {                                             // off: the trees hold no D records
+        const size_t G = (size_t)s->P.G;
+        hipError_t e = hipSuccess;
+        if (dsum) e = hipMemsetAsync(dsum, 0, sizeof(int64_t) * G * MAXMOVES, st);
+        if (e == hipSuccess && dn) e = hipMemsetAsync(dn, 0, sizeof(int32_t) * G * MAXMOVES, st);
+        if (e == hipSuccess && dq_net) e = hipMemsetAsync(dq_net, 0, sizeof(int32_t) * G, st);
+        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
+        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_draws", e);
+    }
+    hipLaunchKernelGGL(k_node_draws, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, (long long*)dsum, dn, dq_net, counts);
+    S_LAUNCH_CHECK("cz_search_node_draws");
+    return CZ_OK;
+}
+
+int cz_draw_quanta(const float* d, int stride, int32_t* dq, int n, void* stream)
+{
+    if (!d || !dq || n < 0 || stride < 1) return serr(CZ_ERR_ARG, "cz_draw_quanta: null argument, n < 0 or stride < 1");
+    if (n == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_draw_quanta, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, stride, dq, n);
+    S_LAUNCH_CHECK("cz_draw_quanta");
     return CZ_OK;
 }
 

@@ -9,6 +9,7 @@
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_ml.h"
+#include "xq_search_draw.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_ply.h"
@@ -224,6 +225,47 @@ __global__ void k_ml_quanta(const float* __restrict__ x, int32_t* __restrict__ k
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) k[i] = ml_quanta(x[i]);
+}
+
+// Draw average: the D records of the root, or of the node reached from it along path[g][0 .. path_len) as in k_root_stats:
+// per edge dsum and dn (0 past the node's edges and without a statistics block), per game the node's own dq.  Launched only
+// while the option is on: a tree grown without it has no D records.
+__global__ __launch_bounds__(64) void k_node_draws(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                  int path_len, long long* __restrict__ dsum, int32_t* __restrict__ dn,
+                                                  int32_t* __restrict__ dq_net, uint8_t* __restrict__ counts)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    int node = walk_path(B, gv, path, path_len);
+    if (node == 0) node = -1;                                   // (id 0 is "none": an object never given a root)
+    int nm = 0, dq = 0;
+    const DRec* db = nullptr;
+    if (node >= 0) {
+        const NodeHdr hdr = load_hdr(rec_ptr(gv, (uint32_t)node));
+        nm = (int)(hdr.meta & 0xFF);
+        dq = (int)hdr.val;
+        if (hdr.stat) db = d_block(edge_ptr(gv, hdr.stat), nm);
+    }
+    for (int j = lane; j < MAXMOVES; j += 64) {
+        DRec r{0, 0, 0};
+        if (j < nm && db) r = db[j];
+        if (dsum) dsum[(size_t)g * MAXMOVES + j] = r.dsum;
+        if (dn) dn[(size_t)g * MAXMOVES + j] = r.dn;
+    }
+    if (lane == 0) {
+        if (dq_net) dq_net[g] = dq;
+        if (counts) counts[g] = (uint8_t)nm;
+    }
+}
+
+// dq[i] = draw_quanta(d[i * stride]): the attach's conversion of a strided column (cz_draw_quanta)
+__global__ void k_draw_quanta(const float* __restrict__ d, int stride, int32_t* __restrict__ dq, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dq[i] = draw_quanta(d[(size_t)i * stride]);
 }
 
 // MCTS solver: the proof state of the root, or of the node reached from it along path[g][0 .. path_len) as in k_root_stats:

@@ -4,13 +4,14 @@
 // text only moves between these headers, and the proof of a move is the unit's device assembly, kernel by kernel
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
-// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop, k_sim_ml; k_reserve_ml,
-// k_cache_fill, k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise.
+// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop, k_sim_ml, k_sim_draw;
+// k_reserve_ml, k_cache_fill, k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
 #include "xq_search_select.h"
 #include "xq_search_ml.h"
+#include "xq_search_draw.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
 #include "xq_search_ply.h"
@@ -37,11 +38,15 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // ML: the moves-left utility (cz_search_set_moves_left) is on; likewise.  The body of k_sim_ml too; M is read by that
 // instantiation alone.  Its attach turns the leaf's moves-left row into k (ml_quanta), keeps k in the node header and takes m up
 // the path (backup_m); it runs leaf by leaf without the one-leaf-ahead prefetch.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false>
+// DRAW: the draw average (cz_search_set_draw) is on; likewise.  The body of k_sim_draw too; D is read by that instantiation
+// alone.  Its attach turns the draw column of the leaf's win / draw / loss row into dq (draw_quanta), keeps dq in the node header
+// and takes it up the path (backup_d), d then v; leaf by leaf without the prefetch, as ML's.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false, bool DRAW = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
                    int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C,
-                   const StopState& S = StopState{}, const MovesLeftState& M = MovesLeftState{})
+                   const StopState& S = StopState{}, const MovesLeftState& M = MovesLeftState{},
+                   const DrawState& D = DrawState{})
 {
     const int g = blockIdx.x;
     // first kernel of a round: chunks returned during the previous round become takeable (see pool_commit)
@@ -98,6 +103,9 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         if constexpr (ML) {
             if (sn_state == SIM_LEAF) my_k = ml_quanta(M.x[my_row]);
         }
+        if constexpr (DRAW) {                                         // (DRAW) my_k: the leaf's draw probability in quanta
+            if (sn_state == SIM_LEAF) my_k = draw_quanta(D.wdl[3 * (size_t)my_row + 1]);
+        }
         // the leaves the cache answered (SIM_CACHED) join the walk below at their place in simulation order: their value
         // waits in s_cval, no policy row is read and nothing is prefetched for them
         uint64_t cached = 0ull;
@@ -121,7 +129,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         };
         LeafPre lp{0, 0, 0, 0.0f, 0.0f};
         uint64_t rest = leaves;
-        if (!ML && rest) {
+        if (!ML && !DRAW && rest) {
             const int i0 = __ffsll((long long)rest) - 1;
             pre_a(lp, i0);
             pre_b(lp, i0);
@@ -141,6 +149,13 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), k);
                 load_path(P, gv, L, i, depth);
                 backup_m(gv, L, depth, k);
+                backup(P, gv, L, depth, v);
+            } else if constexpr (DRAW) {
+                const int dq = __builtin_amdgcn_readlane(my_k, i);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), dq);      // (word 3, as the moves-left k)
+                load_path(P, gv, L, i, depth);
+                backup_d(gv, L, depth, dq);
                 backup(P, gv, L, depth, v);
             } else if (CACHE && ((cached >> i) & 1ull)) {
                 cached_attach(gv, node, keep_v, (float)v);
@@ -191,6 +206,11 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), k);
                 backup_m(gv, L, depth, k);
             }
+            if constexpr (DRAW) {
+                const int dq = uni(draw_quanta(D.wdl[3 * slot + 1]));
+                if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), dq);
+                backup_d(gv, L, depth, dq);
+            }
             backup(P, gv, L, depth, (double)value[slot]);             // float(v) of a float32
             sim_finish(gv, i, &active);
         }
@@ -217,7 +237,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         } else if (df.lo != 0 || df.hi != 0) {
             // the descents of this phase (resumed simulations / a fresh batch) are over: the terminal and repetition
             // values they produced are applied now, in index order
-            flush_deferred<SOLVE, ML>(P, gv, L, df, &active);
+            flush_deferred<SOLVE, ML, DRAW>(P, gv, L, df, &active);
             continue;
         } else if ((mask & SIM_SELECT) && active == 0) {              // 3. next lock-step batch (player.py:169-178)
             const int tasks = uni(B.g_tasks_left[g]);
@@ -251,8 +271,8 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM, CACHE, SOLVE, ML>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh, df, C,
-                                             (mask & SIM_SELECT) != 0, M);
+        run_sim<HIST, GUM, CACHE, SOLVE, ML, DRAW>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh,
+                                                   df, C, (mask & SIM_SELECT) != 0, M, D);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -334,7 +354,20 @@ __global__ __launch_bounds__(64, 4) void k_sim_ml(SearchParams P, SearchBuffers 
                                                      StopState{}, M);
 }
 
-// The moves-left utility's share of the per-ply reservation: a statistics block is twice the size while the option is on, so
+// k_sim with the draw average on (cz_search_set_draw refuses the Gumbel search, the solver, the stop rules, the evaluation
+// cache, a script and the moves-left utility)
+template <bool HIST>
+__global__ __launch_bounds__(64, 4) void k_sim_draw(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                                const float* __restrict__ value, void* planes, int mask, int compact,
+                                                int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, DrawState D)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, false, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count,
+                                                            EvalCache{}, StopState{}, MovesLeftState{}, D);
+}
+
+// The moves-left utility's share of the per-ply reservation (the draw average's too: its D records take the M records' place,
+// and cz_search_round launches this kernel for either): a statistics block is twice the size while the option is on, so
 // between k_advance (whose begin_search reserved the plain blocks) and k_sim(SELECT) every searching game tops its chunks up to
 // what its outstanding simulations can use.  A game that cannot be served here has just begun its ply (a ply under way was
 // served when it began and uses no more than that): its tree is dropped as begin_search would, the chunks it keeps hold one

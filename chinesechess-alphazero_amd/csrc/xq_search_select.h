@@ -9,6 +9,7 @@
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_ml.h"
+#include "xq_search_draw.h"
 
 namespace {
 
@@ -202,9 +203,12 @@ XQ_D int select_gumbel(int gumbel_m, double c_visit, double c_scale, int32_t* st
 // network value; ML: the leaf's k).
 // ML: the k_sim instantiation that is launched while the moves-left utility is on (cz_search_set_moves_left); likewise.  Every
 // lane loads its edges' M records, two integer wave sums give the parent's mean, and the score is (q + u) + u_m.
-template <bool GUM, bool ML = false>
+// DRAW: the k_sim instantiation that is launched while the draw average is on (cz_search_set_draw); likewise.  Every lane
+// loads its edges' D records, and the score is (q + u) + sigma * dbar; sigma: draw_sigma of the node's depth.
+template <bool GUM, bool ML = false, bool DRAW = false>
 XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, char* base, const EdgeStat* sb, int sum_n,
-                        int nm, const RootCtx& rc, uint32_t net_value, const MovesLeftState& M = MovesLeftState{})
+                        int nm, const RootCtx& rc, uint32_t net_value, const MovesLeftState& M = MovesLeftState{},
+                        double sigma = 0.0)
 {
     if (GUM && rc.is_root && P.gumbel_m > 0) {                  // wave-uniform
         Picked r;                                               // (have = false: the caller reloads the edge, this is not the hot path)
@@ -259,6 +263,16 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
         d0 = ml_edge_d(M, mr0.ksum, mr0.mn, Mp);
         d1 = ml_edge_d(M, mr1.ksum, mr1.mn, Mp);
     }
+    if constexpr (DRAW) {                                   // d0, d1: this lane's sigma * dbar of the two halves
+        DRec dr0{0, 0, 0}, dr1{0, 0, 0};
+        if (sb) {                                           // (a fresh statistics block: every record is {0, 0})
+            const DRec* db = d_block(sb, nm);
+            if (lane < nm) dr0 = db[lane];                  // one 16-byte load
+            if (lane + 64 < nm) dr1 = db[lane + 64];
+        }
+        d0 = draw_term(sigma, dr0.dsum, dr0.dn);
+        d1 = draw_term(sigma, dr1.dsum, dr1.dn);
+    }
 #pragma nounroll
     for (int h = 0; h < halves; ++h) {
         const int j = lane + 64 * h;
@@ -285,6 +299,7 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
             if (valid) {
                 score = q + u;
                 if constexpr (ML) score = score + ml_utility(h == 0 ? d0 : d1, q);
+                if constexpr (DRAW) score = score + (h == 0 ? d0 : d1);
                 win = q > (1.0 - 1e-7);
                 if (!(score >= -99999999.0)) valid = false;
             }

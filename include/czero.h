@@ -196,7 +196,10 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * its own) and the max-q record of the resignation audit (a scripted game has no resignation test).
  * The moves-left utility (cz_search_set_moves_left, below) stands beside the table the same way, consulted last: it is not
  * beside the Gumbel root search, the MCTS solver, the two stop rules, the evaluation cache and a script, in both directions;
- * a setter refused for it names "the moves-left utility is on (cz_search_set_moves_left)". */
+ * a setter refused for it names "the moves-left utility is on (cz_search_set_moves_left)".
+ * The draw average (cz_search_set_draw, below) stands there too, consulted after the moves-left utility: it is not beside the
+ * same six, nor beside the moves-left utility itself, in both directions; a setter refused for it names "the draw average is
+ * on (cz_search_set_draw)". */
 
 /* Scripted games: walk stored games again (MuZero's Reanalyse).  n games: game id i < n starts from init_boards[i] (90
  * bytes, the first mover's frame, as cz_replay_games takes them), plays labels[offsets[i] .. offsets[i+1]) and ends with
@@ -854,6 +857,47 @@ int cz_search_node_moves_left(cz_search* s, const uint16_t* path, int path_len, 
                               uint8_t* counts, void* stream);
 /* k[i] = the quanta of x[i], by the attach's own conversion; x, k DEVICE [n]. */
 int cz_moves_left_quanta(const float* x, int32_t* k, int n, void* stream);
+/* ---- draw average (off by default; the reference has no such option; lc0's draw score and its W / D / L display) ------------
+ * run.py self / eval --draw-score S; the UCI options UCI_ShowWDL, DrawScore.  The tree keeps a mean draw probability per
+ * edge, from the draw column of the win / draw / loss value head (cz_heads_tail_wdl), and the selection adds what a draw is
+ * worth.  With the option off no kernel output, record or counter differs by a bit, and the kernels launched are the ones
+ * launched before it existed.  With it on and score = 0 visit counts, W and priors are the plain search's bit for bit, and the
+ * records are kept.
+ *
+ * UNITS.  The tree holds draw probability as integers in quanta of 2^-20 (CZ_DRAW_QUANTA): every sum is exact in any order.
+ * A LEAF'S d = wdl[row][1] (float32) becomes dq = rint(d * 1048576): the product with a power of two is exact in float32, so dq
+ * is a pure function of d's bits.  NaN or d < 0 gives 0, d >= 1 gives 1048576.  Computed at attach, where the leaf's value row
+ * is read, and kept in word 3 of the node header (free while the Gumbel search is off).
+ * ENDS WITHOUT A NETWORK ROW.  A repetition whose value is 0 is a draw: dq = 1048576.  A terminal child (+-2), a repetition
+ * worth +-1, a depth cut-off, an overflow and "no edge" have dq = 0.
+ * BACKUP.  On every edge of the path dsum += dq (int64), dn += 1 (int32); no sign, so no flip per level.  dn counts completed
+ * backups only; virtual loss does not touch these fields.
+ * STORAGE.  Each edge has a D record {int64 dsum, int32 dn, int32 spare}, one granule, directly behind the node's statistics
+ * block: edge j's record is granule stat + nm + j -- the moves-left utility's M record's place, hence the exclusion.  Allocated
+ * with the statistics block, only while the option is on; the reservation and the chunks a game keeps count the larger block.
+ * SELECTION at a node `depth` edges below the ply's current root (root = 0), in float64 and this order, nothing fused:
+ *   sigma = (depth & 1) ? -score : score              (score: what a draw is worth to the side to move at the root)
+ *   dbar  = dn_j > 0 ? ((double)dsum_j / 1048576.0) / (double)dn_j : 0.0
+ *   edge score = (q + u) + sigma * dbar
+ * Everything else of the selection is unchanged: the q > 1 - 1e-7 shortcut on q alone, the >= tie rule, the rejected-score
+ * test, root bans, the root prior, the forced-playout pass.  The records carry no sign: a reused subtree needs no fix-up.
+ * The move played, resignation and every record column go on reading q = W / N.
+ *
+ * cz_search_set_draw: score finite and in [-1, 1].  wdl_rows: caller-owned DEVICE float32 [G*K][3], indexed exactly as `value`
+ * is and read by cz_search_round(_q) for the rows `value` is read for; NULL with `on` is CZ_ERR_ARG.  Switching on or off
+ * resets the trees as cz_search_reset_trees does (the statistics blocks change size); a new score while on resets nothing.
+ * Switching on is refused (CZ_ERR_ARG) beside the Gumbel search (header word 3), the solver, the stop rules and the evaluation
+ * cache (a kernel instantiation each; a cache entry holds no d), a script and the moves-left utility (the same granules), and
+ * each of them is refused beside it; switching off is never refused.  Synchronises the stream. */
+#define CZ_DRAW_QUANTA 1048576
+int cz_search_set_draw(cz_search* s, int on, double score, const float* wdl_rows, void* stream);
+/* The D records of the node cz_search_node_stats would report for the same path (path NULL / path_len 0: the root; path_len
+ * at most 128): dsum [G][128] int64 and dn [G][128] int32, 0 past the node's edges; dq_net [G] int32, the node's own dq; counts
+ * [G] uint8, the node's edges.  Any may be NULL; all DEVICE.  With the option off everything is 0, counts included. */
+int cz_search_node_draws(cz_search* s, const uint16_t* path, int path_len, int64_t* dsum, int32_t* dn, int32_t* dq_net,
+                         uint8_t* counts, void* stream);
+/* dq[i] = the quanta of d[i * stride], by the attach's own conversion; d DEVICE [n * stride], dq DEVICE [n]; stride >= 1. */
+int cz_draw_quanta(const float* d, int stride, int32_t* dq, int n, void* stream);
 /* ---- early stop of a settled ply (both rules off by default; the reference has no such option) ---------------------------
  * run.py self --kld-gain G [--kld-interval I]; run.py eval --smart-pruning, the UCI option SmartPruning.  Two rules end a
  * ply's search before its budget is spent.  With both off no kernel output, record or counter differs by a bit, and the

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Cost of the draw average of the search (engine.draw_score / engine.show_wdl, cz_search_set_draw) on the `normal` benchmark
+engine with a random network that has the win / draw / loss value head.
+
+    python tools/draw_score_cost.py [--rounds 1500] [--reps 2] [--scores 0,-0.5]
+    -> one JSON line, also written to --out (default profiles/draw_score_cost.json)
+
+Legs alternate average off / on with each score of --scores, --reps times over, in ONE process, each a fresh engine (same seed,
+same network), driven the way the self-play worker drives it: HIP graph replays, drained every report_every_rounds (200).
+Reports per leg expansions/s and the tree bytes per game at the end.  The off legs run the kernels that ran before the option
+existed (k_sim; the tail is cz_heads_tail_wdl in every leg); the on legs run k_sim_draw and k_reserve_ml, and their tail also
+writes the rows the search reads.  The tree kernels' round alone is tools/search_probe.py --draw-average 1's.  A random network
+shows no playing effect: no strength or draw-rate claim is made here."""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "chinesechess-alphazero_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def leg(on, score, rounds, every):
+    import torch
+    import bench
+    from cchess_alphazero.agent.model import CChessNet
+    from cchess_alphazero.engine import SelfPlayEngine
+    cfg = bench.build_config(types.SimpleNamespace(config="normal", games=None, sims_per_round=None, dtype=None,
+                                                   trunk=None))
+    cfg.model.value_outputs = 3
+    torch.manual_seed(0)
+    net = CChessNet.from_model_config(cfg.model)
+    assert net.wdl_head
+    eng = SelfPlayEngine(cfg, cfg.engine.games_per_gpu, net=net, dtype=getattr(torch, cfg.engine.net_dtype), seed=20261019,
+                         draw_score=score if on else 0.0, show_wdl=bool(on))
+    try:
+        assert eng.draw == bool(on)
+        eng.start(0, 0)
+        eng.prewarm()
+        for _ in range(20):
+            eng.step()
+        eng.capture_graph(warmup=0)
+        games = 0
+        torch.cuda.synchronize()
+        c0 = eng.counters()
+        t0 = time.perf_counter()
+        for r in range(1, rounds + 1):
+            eng.step()
+            if r % every == 0:
+                games += len(eng.drain())
+        games += len(eng.drain())
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        c1 = eng.counters()
+        m = eng.search.memory_info()
+        d = {k: c1.get(k, 0) - c0.get(k, 0) for k in ("sims", "expansions", "plies", "stat_blocks", "chunks_taken",
+                                                      "tree_resets", "overflow_sims")}
+        return dict(draw_on=bool(on), draw_score=score if on else None, rounds=rounds, seconds=dt,
+                    expansions_per_s=d["expansions"] / dt, games=games,
+                    plies=d["plies"], sims=d["sims"], stat_blocks=d["stat_blocks"], chunks_taken=d["chunks_taken"],
+                    tree_resets=d["tree_resets"], overflow_sims=d["overflow_sims"],
+                    mean_depth=(c1["sum_depth"] - c0["sum_depth"]) / max(1, d["sims"]),
+                    tree_bytes_per_game=m["tree_bytes"] / eng.search.G, nodes_per_game=m["nodes"] / eng.search.G)
+    finally:
+        eng.close()
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=1500)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--scores", default="0,-0.5", help="the draw scores of the on legs, comma-separated")
+    ap.add_argument("--every", type=int, default=200, help="drain cadence (rounds), the worker's report_every_rounds")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "draw_score_cost.json"))
+    args = ap.parse_args()
+    scores = [float(x) for x in args.scores.split(",")]
+    legs = []
+    for _ in range(args.reps):
+        for on, score in [(False, 0.0)] + [(True, s) for s in scores]:
+            legs.append(leg(on, score, args.rounds, args.every))
+            print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
+    by = {}
+    for name, sel in [("off", [x for x in legs if not x["draw_on"]])] + \
+                     [(f"on_{s:g}", [x for x in legs if x["draw_on"] and x["draw_score"] == s]) for s in scores]:
+        xs = [x["expansions_per_s"] for x in sel]
+        by[name] = dict(expansions_per_s=xs, mean=sum(xs) / len(xs), spread=(max(xs) - min(xs)) / (sum(xs) / len(xs)),
+                        tree_bytes_per_game=sum(x["tree_bytes_per_game"] for x in sel) / len(sel),
+                        nodes_per_game=sum(x["nodes_per_game"] for x in sel) / len(sel))
+    for name in by:
+        if name != "off":
+            by[name]["over_off"] = by[name]["mean"] / by["off"]["mean"]
+    out = dict(by_setting=by, legs=legs)
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

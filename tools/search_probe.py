@@ -6,7 +6,7 @@ events over the next rounds (per-launch: mean / median / p99).  A/B tool for cha
 (csrc/xq_search.hip and the csrc/xq_search_*.h it is made of).
 
     python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1] [--leaf-mirror P]
-                                 [--moves-left-slope S [--moves-left-cap C]]
+                                 [--moves-left-slope S [--moves-left-cap C]] [--draw-average 1 [--draw-score S]]
 """
 import argparse
 import json
@@ -29,6 +29,9 @@ def main():
     ap.add_argument("--moves-left-slope", type=float, default=0.0,
                     help="slope of the moves-left utility (cz_search_set_moves_left); the stub's third output feeds it")
     ap.add_argument("--moves-left-cap", type=float, default=0.0345)
+    ap.add_argument("--draw-average", type=int, default=0,
+                    help="1: the draw average (cz_search_set_draw); the draw stub's third output feeds it")
+    ap.add_argument("--draw-score", type=float, default=0.0)
     a = ap.parse_args()
     import types
     import stub_net
@@ -46,6 +49,9 @@ def main():
     if a.moves_left_slope:
         import stub_moves_left
         s.set_moves_left(a.moves_left_slope, a.moves_left_cap)
+    if a.draw_average:
+        import stub_draw
+        s.set_draw(True, a.draw_score)
     s.start_selfplay(seed=20260923)
     planes_of = (lambda: s.queue_planes()) if a.masks_only else (lambda: s.planes)   # (the same planes either way: same trees)
 
@@ -54,17 +60,22 @@ def main():
         p, v = stub_net.hash_stub_torch(planes_of(), 1)
         p = p * 0 + 1.0 / 2086 + p * 1e-3
         x = stub_moves_left.ml_stub_torch(planes_of(), 1)[2] if a.moves_left_slope else None
+        wdl = stub_draw.draw_stub_torch(planes_of(), 1)[2] if a.draw_average else None
         if a.compact:
             rows = s.q_rows.long().clamp_(0, s.slots - 1)
             s.policy.copy_(p.index_select(0, rows))
             s.value.copy_((v * 0.05).index_select(0, rows))
             if x is not None:
                 s.moves_left_x.copy_(x.index_select(0, rows))
+            if wdl is not None:
+                s.wdl_rows.copy_(wdl.index_select(0, rows))
         else:
             s.policy.copy_(p)
             s.value.copy_(v * 0.05)
             if x is not None:
                 s.moves_left_x.copy_(x)
+            if wdl is not None:
+                s.wdl_rows.copy_(wdl)
 
     for _ in range(a.rounds):
         s.round(compact=bool(a.compact))
@@ -86,7 +97,7 @@ def main():
            "mean_depth": c["sum_depth"] / max(1, c["sims"]), "plies": c["plies"], "games": c["games"],
            "tree_resets": c["tree_resets"], "overflow_sims": c["overflow_sims"], "nodes": m["nodes"],
            "tree_gb": m["tree_bytes"] / 1e9, "tree_bytes_per_game": m["tree_bytes"] / a.games,
-           "moves_left_slope": a.moves_left_slope}
+           "moves_left_slope": a.moves_left_slope, "draw_average": a.draw_average, "draw_score": a.draw_score}
     if a.leaf_mirror:                      # (of the slots as they stand: every slot has held a leaf by now)
         out["leaf_mirror"] = a.leaf_mirror
         out["mirrored_share_of_slots"] = float(s.mirrored.float().mean())
