@@ -153,6 +153,10 @@ def declare(L):
         "cz_search_set_draw": [vp, i32, d, vp, vp],
         "cz_search_node_draws": [vp, vp, i32, vp, vp, vp, vp, vp],
         "cz_draw_quanta": [vp, i32, vp, i32, vp],
+        "cz_search_set_lcb": [vp, d, d, vp],
+        "cz_search_node_values": [vp, vp, i32, vp, vp, vp, vp],
+        "cz_search_root_lcb": [vp, vp, vp, vp],
+        "cz_lcb_pick": [vp, vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -268,6 +272,7 @@ class Search:
         self.moves_left_x = None               # ... and its rows: [slots] float32 beside policy / value, the network's raw x
         self.draw_on, self.draw_score = False, 0.0   # set_draw(): the draw average and what a draw is worth at the root
         self.wdl_rows = None                   # ... and its rows: [slots, 3] float32 beside policy / value, the network's W / D / L
+        self.lcb, self.lcb_min_ratio = 0.0, 0.15   # set_lcb(): the lower-confidence-bound move choice, z 0 = off
 
     # -- lifetime --
     def close(self):
@@ -540,6 +545,48 @@ class Search:
                                                   C.c_void_p(dq_net.data_ptr()), C.c_void_p(counts.data_ptr()),
                                                   self._stream()), "cz_search_node_draws")
         return dict(dsum=dsum.cpu().numpy(), dn=dn.cpu().numpy(), dq_net=dq_net.cpu().numpy(), counts=counts.cpu().numpy())
+
+    def set_lcb(self, z=0.0, min_ratio=0.15):
+        """Lower-confidence-bound move choice (cz_search_set_lcb; include/czero.h has the rule): while on (z > 0), every edge
+        keeps the sum of the squares of its backed-up values, and where the temperature is 0 the move played -- choose(), the
+        self-play loop, the first move of pv() -- is the non-banned edge with the greatest q - z * standard error among those
+        with at least min_ratio of the most visited edge's visits, instead of the most visited one.  Visit counts, W and
+        priors are the plain search's.  Switching on or off resets the trees; a new z or ratio while on does not.  Refused
+        beside the Gumbel search, the solver, the stop rules, the evaluation cache, a script, the moves-left utility and the
+        draw average, and they beside it; a refusal leaves the attributes as they were.  Call it before start_selfplay() /
+        set_roots() and before a graph capture."""
+        if not hasattr(self.L, "cz_search_set_lcb"):
+            raise _native.NativeError("this libczero.so has no lower-confidence-bound move choice (cz_search_set_lcb)")
+        _native.check(self.L.cz_search_set_lcb(self.h, float(z), float(min_ratio), self._stream()), "cz_search_set_lcb")
+        self.lcb, self.lcb_min_ratio = float(z), float(min_ratio)
+
+    def node_values(self, path=None):
+        """The value records of the node node_stats(path) reports (cz_search_node_values): dict(s2 float64 [G, 128] and vn
+        int32 [G, 128] per edge -- the sum of the squares of the backed-up values and how many --, counts uint8 [G]).  With the
+        option off everything is 0."""
+        import torch
+        G, M = self.G, _native.MAXMOVES
+        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        s2 = torch.empty((G, M), dtype=torch.float64, device=self.device)
+        vn = torch.empty((G, M), dtype=torch.int32, device=self.device)
+        counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
+        _native.check(self.L.cz_search_node_values(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
+                                                   pa.shape[1], C.c_void_p(s2.data_ptr()), C.c_void_p(vn.data_ptr()),
+                                                   C.c_void_p(counts.data_ptr()), self._stream()), "cz_search_node_values")
+        return dict(s2=s2.cpu().numpy(), vn=vn.cpu().numpy(), counts=counts.cpu().numpy())
+
+    def root_lcb(self):
+        """The rule on every current root with the bans of the current set_roots (cz_search_root_lcb): (lcb float64 [G, 128],
+        NaN for an edge that is not eligible or past the edges; pick int32 [G], the edge index the rule picks, -1 for a root
+        that is not in the tree).  Only while set_lcb() is on."""
+        import torch
+        lcb = torch.empty((self.G, _native.MAXMOVES), dtype=torch.float64, device=self.device)
+        pick = torch.empty((self.G,), dtype=torch.int32, device=self.device)
+        _native.check(self.L.cz_search_root_lcb(self.h, C.c_void_p(lcb.data_ptr()), C.c_void_p(pick.data_ptr()),
+                                                self._stream()), "cz_search_root_lcb")
+        return lcb.cpu().numpy(), pick.cpu().numpy()
 
     def node_proof(self, path=None):
         """The proof state of the node node_stats(path) reports (cz_search_node_proof): dict(status int8 [G] -- PROOF_OPEN /
@@ -1123,6 +1170,21 @@ def gumbel_interior_pick(n, w, p, n_edges, v, c_visit, c_scale):
                                                         C.c_void_p(pick.data_ptr()), C.c_void_p(score.data_ptr()), stream),
                   "cz_gumbel_interior_pick")
     return pick, score
+
+
+def lcb_pick(labels, n, w, s2, vn, n_edges, z, min_ratio):
+    """cz_lcb_pick: the lower-confidence-bound rule of set_lcb on caller-supplied rows.  labels uint16 (bit 15 = banned), n
+    int32, w float64, s2 float64, vn int32, all [rows, 128] cuda tensors; n_edges uint8 [rows].  Returns (lcb float64 [rows,
+    128], NaN for an edge that is not eligible or past n_edges; pick int32 [rows], -1 for a row without a non-banned edge) on
+    the device."""
+    import torch
+    rows, ptrs, ne, stream = _row_args("lcb_pick", n_edges, (labels, "uint16"), (n, "int32"), (w, "float64"), (s2, "float64"),
+                                       (vn, "int32"))
+    lcb = torch.empty((rows, _native.MAXMOVES), dtype=torch.float64, device=n.device)
+    pick = torch.empty((rows,), dtype=torch.int32, device=n.device)
+    _native.check(_native.lib().cz_lcb_pick(*ptrs, ne, rows, float(z), float(min_ratio), C.c_void_p(lcb.data_ptr()),
+                                            C.c_void_p(pick.data_ptr()), stream), "cz_lcb_pick")
+    return lcb, pick
 
 
 def root_value_rows(labels, m, n, w, n_edges):

@@ -52,7 +52,7 @@ class DrawUnavailable(ValueError):
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
                  debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None,
-                 moves_left_slope=None, moves_left_cap=None, draw_score=None, show_wdl=None):
+                 moves_left_slope=None, moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -95,7 +95,11 @@ class CChessPlayer:
         self.show_wdl = bool(getattr(ec, "show_wdl", False) if show_wdl is None else show_wdl)
         self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
         self.last_wdl = None                   # show_wdl: (W, D, L) in permille of the move action() chose
-        search_options.check(opts, moves_left=self.moves_left, draw=self.draw)
+        # lower-confidence-bound move choice (search_options.py LCB_EXCLUDES): likewise; every network will do
+        self.lcb = float(getattr(ec, "lcb", 0.0) if lcb is None else lcb)
+        self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15) if lcb_min_visits is None else lcb_min_visits)
+        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
+        search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
         if self.moves_left and not getattr(pipes, "moves_left_head", False):
             raise MovesLeftUnavailable(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         if self.draw and not getattr(pipes, "wdl_head", False):
@@ -120,6 +124,8 @@ class CChessPlayer:
             self._search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
         if self.draw:
             self._search.set_draw(True, self.draw_score)
+        if self.lcb_on:
+            self._search.set_lcb(self.lcb, self.lcb_min_visits)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes, moves_left=False, wdl=False):

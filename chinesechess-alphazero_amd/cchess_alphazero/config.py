@@ -108,6 +108,9 @@ class EngineConfig(_Section):
                          # draw average (run.py self / eval --draw-score S, the UCI options DrawScore / UCI_ShowWDL): on when
                          # draw_score != 0 or show_wdl; needs a model with the win / draw / loss value head
                          **search_options.DRAW_DEFAULTS,
+                         # lower-confidence-bound move choice (run.py self / eval --lcb Z --lcb-min-visits R, the UCI options
+                         # LCB / LCBMinVisits): off at lcb 0; works with every model
+                         **search_options.LCB_DEFAULTS,
                          # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
                          **search_options.DEFAULTS)
 

@@ -46,7 +46,7 @@ class SelfPlayEngine:
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
                  kld_gain=None, kld_interval=None, resign_audit=None, script=None, moves_left_slope=None,
-                 moves_left_cap=None, draw_score=None, show_wdl=None):
+                 moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -82,7 +82,11 @@ class SelfPlayEngine:
         search_options.DRAW_EXCLUDES lists, a script and the moves-left utility.  The network must have the win / draw / loss
         value head (`run.py opt --value-head wdl`; a ValueError otherwise, here and in set_network); every forward then also
         fills search.wdl_rows, and the load-time guard and audit_network measure the draw probability too.  An evaluator
-        callable returns (policy, value, wdl [n, 3])."""
+        callable returns (policy, value, wdl [n, 3]).
+        lcb, lcb_min_visits (None = config.engine's values): the lower-confidence-bound move choice (Search.set_lcb), on with
+        lcb > 0: from the ply where the temperature reaches 0 a game plays the move with the best lower bound of its value.  It
+        stands beside the table the same way: check(lcb=True) refuses what search_options.LCB_EXCLUDES lists, a script, the
+        moves-left utility and the draw average.  Every network will do."""
         ec_ = getattr(config, "engine", None)
         self.moves_left_slope = float(getattr(ec_, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
         self.moves_left_cap = float(getattr(ec_, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
@@ -90,13 +94,16 @@ class SelfPlayEngine:
         self.draw_score = float(getattr(ec_, "draw_score", 0.0) if draw_score is None else draw_score)
         self.show_wdl = bool(getattr(ec_, "show_wdl", False) if show_wdl is None else show_wdl)
         self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
+        self.lcb = float(getattr(ec_, "lcb", 0.0) if lcb is None else lcb)
+        self.lcb_min_visits = float(getattr(ec_, "lcb_min_visits", 0.15) if lcb_min_visits is None else lcb_min_visits)
+        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
             gumbel_visit=gumbel_visit, gumbel_scale=gumbel_scale, gumbel_full=gumbel_full, eval_cache=eval_cache,
             solver=solver, kld_gain=kld_gain, kld_interval=kld_interval)
         search_options.check(opts, history=use_history, script=script is not None, moves_left=self.moves_left,
-                             draw=self.draw)
+                             draw=self.draw, lcb=self.lcb_on)
         if self.moves_left and evaluator is None and net is not None and not net.moves_left_head:
             raise ValueError(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         if self.draw and evaluator is None and net is not None and not net.wdl_head:
@@ -176,6 +183,8 @@ class SelfPlayEngine:
             self.search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
         if self.draw:                          # (likewise search.wdl_rows)
             self.search.set_draw(True, self.draw_score)
+        if self.lcb_on:
+            self.search.set_lcb(self.lcb, self.lcb_min_visits)
         self.script = script
         if script is not None:                 # last: the library checks it against everything that is on
             self.search.set_script(*script)

@@ -81,6 +81,14 @@ _FLAGS = [
                                "mean to an edge's score, S being what a draw is worth to the side to move at the root (so S < 0 "
                                "avoids draws and S > 0 seeks them); needs a model with the win / draw / loss value head "
                                "(`run.py opt --value-head wdl`) (finite, in [-1, 1]; 0 = off)")),
+    ("--lcb", dict(type=float, default=0.0, metavar="Z",
+                   help="(self, eval) lower confidence bound: where the temperature is 0 the move played is the one with the "
+                        "greatest q - Z standard errors of its backed-up values instead of the most visited one; the tree keeps "
+                        "a second moment per edge; works with every model (finite, >= 0; 0 = off; KataGo and lc0 use values "
+                        "around 2)")),
+    ("--lcb-min-visits", dict(type=float, default=0.15, metavar="R",
+                              help="(self, eval, with --lcb) a move takes part with at least R times the most visited move's "
+                                   "visits (in [0, 1])")),
     ("--value-head", dict(choices=["scalar", "wdl"], default=None,
                           help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
@@ -149,14 +157,20 @@ def build_config(args):
         draw_on = search_options.check_draw(args.draw_score, flags=True)
         if draw_on and args.cmd not in ("self", "eval", "reanalyse"):
             raise search_options.SearchOptionError("--draw-score is an option of `run.py self` and `run.py eval`")
+        lcb_on = search_options.check_lcb(args.lcb, args.lcb_min_visits, flags=True)
+        if lcb_on and args.cmd not in ("self", "eval", "reanalyse"):
+            raise search_options.SearchOptionError("--lcb is an option of `run.py self` and `run.py eval`")
+        if args.lcb_min_visits != search_options.LCB_DEFAULTS["lcb_min_visits"] and args.cmd not in ("self", "eval"):
+            raise search_options.SearchOptionError("--lcb-min-visits is an option of `run.py self` and `run.py eval`")
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
                              history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on,
-                             draw=draw_on)
+                             draw=draw_on, lcb=lcb_on)
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
     vars(engine).update(values)
     engine.moves_left_slope, engine.moves_left_cap = float(args.moves_left_slope), float(args.moves_left_cap)
     engine.draw_score = float(args.draw_score)
+    engine.lcb, engine.lcb_min_visits = float(args.lcb), float(args.lcb_min_visits)
     # the resignation audit: game-loop options, not search options; their one check is the library's
     from cchess_alphazero.lib.resign_audit import check_options
     try:

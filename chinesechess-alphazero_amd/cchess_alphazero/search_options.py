@@ -188,6 +188,32 @@ def check_draw(score, show_wdl=False, flags=False):
     return score != 0.0 or bool(show_wdl)
 
 
+# The lower-confidence-bound move choice (run.py self / eval --lcb Z --lcb-min-visits R, engine.lcb and engine.lcb_min_visits,
+# Search.set_lcb) stands beside the table the same way; it needs no special network output.  check(lcb=True) refuses these
+# beside it, a script, the moves-left utility and the draw average; consulted after the draw average.  The library's setters
+# hold the same list (csrc/xq_search.hip LCB_EXCLUDES; tests/test_gpu_lcb.py pins the two to each other).
+_LCB_KERNEL = "each has a kernel instantiation of its own"
+LCB_EXCLUDES = (("gumbel", "the Gumbel search has its own root rule and move choice"),
+                ("solver", _LCB_KERNEL + ", and the solver has its own move choice"), ("kld_gain", _LCB_KERNEL),
+                ("smart_pruning", "the unreachable-lead stop promises the move of the full search, the most visited one"),
+                ("eval_cache", _LCB_KERNEL))
+LCB_SCRIPT = "the moves of a reanalysed game are the record's, nothing is chosen"
+LCB_MOVES_LEFT = "an edge's value record lies where its moves-left record would"
+LCB_DRAW = "an edge's value record lies where its draw record would"
+LCB_DEFAULTS = dict(lcb=0.0, lcb_min_visits=0.15)
+LCB_LOG = ("lower confidence bound: at temperature 0 the move played has the greatest q - {lcb:g} standard errors among the moves "
+           "with at least {lcb_min_visits:g} of the most visited move's visits")
+
+
+def check_lcb(z, ratio, flags=False):
+    """Raises SearchOptionError unless z is finite and >= 0 and ratio is in [0, 1]; True when the option is on (z > 0)."""
+    if not (isinstance(z, (int, float)) and _finite(z, None)):
+        raise SearchOptionError(f"{'--lcb' if flags else 'lcb'} {z}: expected a finite value >= 0")
+    if not (isinstance(ratio, (int, float)) and _rate(ratio, None)):
+        raise SearchOptionError(f"{'--lcb-min-visits' if flags else 'lcb_min_visits'} {ratio}: expected a value in [0, 1]")
+    return z > 0.0
+
+
 VALUES = {v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 
@@ -216,7 +242,8 @@ def check(values, flags=False, cmd=None, sims=None, **context):
     sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
     input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES), moves_left=True for the moves-left
     utility (checked after that: MOVES_LEFT_EXCLUDES, and a script), draw=True for the draw average (checked after that:
-    DRAW_EXCLUDES, a script, and the moves-left utility)."""
+    DRAW_EXCLUDES, a script, and the moves-left utility), lcb=True for the lower-confidence-bound move choice (checked after
+    that: LCB_EXCLUDES, a script, the moves-left utility and the draw average)."""
     def name(key):
         return VALUES[key].flag if flags else key
 
@@ -262,6 +289,17 @@ def check(values, flags=False, cmd=None, sims=None, **context):
             raise SearchOptionError(f"{dr} excludes a script: {DRAW_SCRIPT}")
         if context.get("moves_left"):
             raise SearchOptionError(f"{dr} excludes {'--moves-left-slope' if flags else 'moves_left_slope'}: {DRAW_MOVES_LEFT}")
+    if context.get("lcb"):
+        lc = "--lcb" if flags else "lcb"
+        for key, why in LCB_EXCLUDES:
+            if on(key):
+                raise SearchOptionError(f"{lc} excludes {name(key)}: {why}")
+        if context.get("script"):
+            raise SearchOptionError(f"{lc} excludes a script: {LCB_SCRIPT}")
+        if context.get("moves_left"):
+            raise SearchOptionError(f"{lc} excludes {'--moves-left-slope' if flags else 'moves_left_slope'}: {LCB_MOVES_LEFT}")
+        if context.get("draw"):
+            raise SearchOptionError(f"{lc} excludes {'--draw-score' if flags else 'draw_score'}: {LCB_DRAW}")
 
 
 def apply(search, values, skip=()):

@@ -28,7 +28,9 @@ ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference),
              "option name MovesLeftSlope type string default 0",
              "option name MovesLeftCap type string default 0.0345",
              "option name UCI_ShowWDL type check default false",
-             "option name DrawScore type string default 0")
+             "option name DrawScore type string default 0",
+             "option name LCB type string default 0",
+             "option name LCBMinVisits type string default 0.15")
 
 
 def wdl_permille(w, n, dsum, dn):
@@ -141,6 +143,16 @@ class UCI:
                     self.config.engine.draw_score = v
                 except ValueError:
                     self._say(f"info string DrawScore {args[3]}: expected a finite value in [-1, 1]")
+            elif args[1] in ("LCB", "LCBMinVisits"):      # the lower-confidence-bound move choice (cz_search_set_lcb)
+                key, hi, expected = (("lcb", float("inf"), "a finite value >= 0") if args[1] == "LCB" else
+                                     ("lcb_min_visits", 1.0, "a value in [0, 1]"))
+                try:
+                    v = float(args[3])
+                    if not (0.0 <= v <= hi and v != float("inf")):
+                        raise ValueError(args[3])
+                    setattr(self.config.engine, key, v)
+                except ValueError:
+                    self._say(f"info string {args[1]} {args[3]}: expected {expected}")
 
     def cmd_position(self, args):
         if not self.is_ready:

@@ -152,7 +152,11 @@ class EvaluateWorker:
         self.draw_score = float(getattr(ec, "draw_score", 0.0))
         self.show_wdl = bool(getattr(ec, "show_wdl", False))
         self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
-        search_options.check(opts, moves_left=self.moves_left, draw=self.draw)
+        # lower-confidence-bound move choice of both models' searches (run.py eval --lcb Z; search_options.LCB_EXCLUDES)
+        self.lcb = float(getattr(ec, "lcb", 0.0))
+        self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15))
+        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
+        search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
         self._eval3 = tuple(_with_moves_left(e, self.moves_left_slope) for e in evaluators) if self.moves_left else None
         if self.draw:
             self._eval3 = tuple(_with_wdl(e, self.draw_score, self.show_wdl) for e in evaluators)
@@ -228,6 +232,8 @@ class EvaluateWorker:
                 s.set_moves_left(self.moves_left_slope, self.moves_left_cap)
             if self.draw:
                 s.set_draw(True, self.draw_score)
+            if self.lcb_on:
+                s.set_lcb(self.lcb, self.lcb_min_visits)
 
         def counters_now():
             c = [s.counters() for s in searches]

@@ -112,6 +112,9 @@ class SelfPlayWorker:
                                                                moves_left_cap=self.engine.moves_left_cap))
         if self.engine.draw:
             logger.info(f"Process {self.pid}-{self.rank}: " + search_options.DRAW_LOG.format(draw_score=self.engine.draw_score))
+        if self.engine.lcb_on:
+            logger.info(f"Process {self.pid}-{self.rank}: "
+                        + search_options.LCB_LOG.format(lcb=self.engine.lcb, lcb_min_visits=self.engine.lcb_min_visits))
         if self.resign_audit is not None:
             logger.info(f"Process {self.pid}-{self.rank}: resignation audit of the no-resign games, threshold "
                         f"{self.engine.resign_threshold:g}"

@@ -13,7 +13,9 @@
 //     block is 2 nm granules: nm M records {int64 ksum, int32 mn, int32 spare} follow, edge j's at granule stat + nm + j
 //     (xq_search_ml.h), and header word 3 holds the node's own prediction in quanta instead of the net value; while the
 //     draw average is on (cz_search_set_draw) the same granules hold nm D records {int64 dsum, int32 dn, int32 spare}
-//     and the same word the node's own draw probability in quanta (xq_search_draw.h): the two options exclude each other;
+//     and the same word the node's own draw probability in quanta (xq_search_draw.h); while the lower-confidence-bound move
+//     choice is on (cz_search_set_lcb) they hold nm V records {double s2, int32 vn, int32 spare} (xq_search_var.h): the three
+//     options exclude each other;
 //   * chunks are taken from / returned to a device-side free ring (pool_* below) between plies and between games,
 //     never inside the simulation kernel: begin_search reserves the worst case of the coming ply.
 // The hot scratch (boards, ordered move lists, the current path, the game's chunk table) lives in LDS.

@@ -17,6 +17,8 @@
 // With the moves-left utility on (cz_search_set_moves_left) the k_sim launches are the k_sim_ml instantiations, and k_reserve_ml
 // runs between k_advance and k_sim(SELECT): the statistics blocks are twice the size, and it reserves the difference.
 // With the draw average on (cz_search_set_draw) they are the k_sim_draw instantiations, with k_reserve_ml in the same place.
+// With the lower-confidence-bound move choice on (cz_search_set_lcb) they are the k_sim_var instantiations, likewise, and
+// k_advance is k_advance_lcb.
 // The host then runs ONE network forward over the whole queue.
 // There is no host decision inside a round and no device->host copy, so a round (kernel + network
 // forward) can be replayed from a HIP graph.
@@ -30,6 +32,7 @@
 //   xq_search_attach.h    prior spreading and the attach of an evaluated leaf (prior_norm, attach_policy, attach_and_backup)
 //   xq_search_ml.h        the moves-left utility: MovesLeftState, MRec, ml_quanta, wave_add_i64, backup_m, ml_edge_d, ml_utility
 //   xq_search_draw.h      the draw average: DrawState, DRec, draw_quanta, backup_d, draw_sigma, draw_term
+//   xq_search_var.h       the lower-confidence-bound move choice: LcbState, VRec, backup_v, LcbEdges, lcb_pick
 //   xq_search_select.h    RootCtx and PUCT at the root, the Gumbel helpers, gumbel_interior, select_gumbel, select_edge
 //   xq_search_solver.h    the MCTS solver: its bit fields, solve_*, select_solve
 //   xq_search_sim.h       one simulation: Deferred, write_planes, expand_node, the cache probe, run_sim, flush_deferred
@@ -63,6 +66,7 @@ extern "C" void czi_set_error(const char* msg);   // xq_kernels.hip
 #include "xq_search_attach.h"
 #include "xq_search_ml.h"
 #include "xq_search_draw.h"
+#include "xq_search_var.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
@@ -96,6 +100,7 @@ struct cz_search {
     void* script_mem = nullptr;       // boards, labels, offsets and z, in one allocation
     MovesLeftState M{};               // moves-left utility (cz_search_set_moves_left); M.slope 0 = off
     DrawState D{};                    // draw average (cz_search_set_draw); D.on 0 = off
+    LcbState Z{};                     // lower-confidence-bound move choice (cz_search_set_lcb); Z.on 0 = off
 };
 
 namespace {
@@ -175,7 +180,8 @@ size_t layout(cz_search* s, char* base, bool dry)
 }
 
 // chunks a game needs for one full search on an empty tree (what it keeps through resets and between games)
-// ml: the moves-left utility or the draw average is on, a statistics block carries one M / D record per edge
+// ml: the moves-left utility, the draw average or the lower-confidence-bound move choice is on, a statistics block carries one
+// M / D / V record per edge
 // (reserve_ply<true>)
 int keep_chunks_for(int sims, bool ml = false)
 {
@@ -459,8 +465,12 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool script = s->X.n > 0 && s->P.mode == MODE_SELFPLAY;   // (never with gum, solve or stop: cz_search_set_script)
     const bool ml = s->M.slope > 0.0;                           // (never with gum, solve, stop, cache or a script: cz_search_set_moves_left)
     const bool draw = s->D.on != 0;                             // (never with ml or what ml is never with: cz_search_set_draw)
+    const bool lcb = s->Z.on != 0;                              // (never with ml, draw or what they are never with: cz_search_set_lcb)
     auto sim = [&](int mask, int cq) {
-        if (draw) {
+        if (lcb) {
+            if (hist) hipLaunchKernelGGL((k_sim_var<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((k_sim_var<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+        } else if (draw) {
             if (hist) hipLaunchKernelGGL((k_sim_draw<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
             else hipLaunchKernelGGL((k_sim_draw<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
         } else if (ml) {
@@ -491,8 +501,9 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     else if (stop) hipLaunchKernelGGL(k_advance_stop, grid, block, 0, st, s->P, s->B, s->V, s->S);
     else if (gum && s->P.gumbel_full) hipLaunchKernelGGL(k_advance<true>, grid, block, 0, st, s->P, s->B, s->V);
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
+    else if (lcb) hipLaunchKernelGGL(k_advance_lcb, grid, block, 0, st, s->P, s->B, s->V, s->Z);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
-    if (ml || draw) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
+    if (ml || draw || lcb) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
@@ -522,7 +533,7 @@ int cz_search_set_sims(cz_search* s, int simulation_num_per_move)
     s->P.sims = simulation_num_per_move;
     // a game that has to drop its tree keeps enough chunks for one full search of the NEW length (never fewer than it
     // was created with: the initial pool layout gave every game that many)
-    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0 || s->D.on != 0);
+    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0 || s->D.on != 0 || s->Z.on != 0);
     if (keep > s->P.max_chunks) keep = s->P.max_chunks;
     if (keep > s->keep_chunks_created) s->P.keep_chunks = keep;
     else s->P.keep_chunks = s->keep_chunks_created;
@@ -605,6 +616,10 @@ constexpr const char* ML_PHRASE = "the moves-left utility is on (cz_search_set_m
 // DRAW_EXCLUDES and the moves-left utility (its D records lie in the M records' granules), and they exclude it.
 constexpr unsigned DRAW_EXCLUDES = ML_EXCLUDES;
 constexpr const char* DRAW_PHRASE = "the draw average is on (cz_search_set_draw)";
+// The lower-confidence-bound move choice (cz_search_set_lcb) stands there too, consulted after the draw average: it excludes the
+// features of LCB_EXCLUDES, the moves-left utility and the draw average (its V records lie in their granules), and they it.
+constexpr unsigned LCB_EXCLUDES = ML_EXCLUDES;
+constexpr const char* LCB_PHRASE = "the lower-confidence-bound move choice is on (cz_search_set_lcb)";
 static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream)
 {
     for (int o = 0; on && o < F_COUNT; ++o)
@@ -621,6 +636,11 @@ static int admit(const cz_search* s, Feature f, bool on, const char* entry, void
     if (on && (DRAW_EXCLUDES >> f & 1) && s->D.on) {
         char buf[160];
         snprintf(buf, sizeof(buf), "%s: %s", entry, DRAW_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
+    if (on && (LCB_EXCLUDES >> f & 1) && s->Z.on) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", entry, LCB_PHRASE);
         return serr(CZ_ERR_ARG, buf);
     }
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
@@ -1012,6 +1032,8 @@ int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float
             return serr(CZ_ERR_ARG, buf);
         }
     if (on && s->D.on) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the draw average is on (cz_search_set_draw)");
+    if (on && s->Z.on)
+        return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the lower-confidence-bound move choice is on (cz_search_set_lcb)");
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->M.slope > 0.0;
@@ -1075,6 +1097,11 @@ int cz_search_set_draw(cz_search* s, int on_, double score, const float* wdl_row
         snprintf(buf, sizeof(buf), "%s: %s", me, ML_PHRASE);
         return serr(CZ_ERR_ARG, buf);
     }
+    if (on && s->Z.on) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", me, LCB_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->D.on != 0;
@@ -1115,6 +1142,80 @@ int cz_draw_quanta(const float* d, int stride, int32_t* dq, int n, void* stream)
     if (n == 0) return CZ_OK;
     hipLaunchKernelGGL(k_draw_quanta, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, stride, dq, n);
     S_LAUNCH_CHECK("cz_draw_quanta");
+    return CZ_OK;
+}
+
+// ---- lower-confidence-bound move choice (include/czero.h) ------------------------------------------------------------------
+int cz_search_set_lcb(cz_search* s, double z, double min_ratio, void* stream)
+{
+    const char* const me = "cz_search_set_lcb";
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_lcb: null handle");
+    if (!finite_nonneg(z)) return serr(CZ_ERR_ARG, "cz_search_set_lcb: z negative or not finite");
+    if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_lcb: min_ratio outside [0, 1] or not finite");
+    const bool on = z > 0.0;
+    for (int o = 0; on && o < F_COUNT; ++o)
+        if ((LCB_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
+            return serr(CZ_ERR_ARG, buf);
+        }
+    if (on && (s->M.slope > 0.0 || s->D.on)) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "%s: %s", me, s->M.slope > 0.0 ? ML_PHRASE : DRAW_PHRASE);
+        return serr(CZ_ERR_ARG, buf);
+    }
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return serr_hip(me, e);
+    const bool was = s->Z.on != 0;
+    s->Z.on = on ? 1 : 0;
+    s->Z.z = on ? z : 0.0;
+    s->Z.ratio = min_ratio;
+    if (was == on) return CZ_OK;
+    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
+    int keep = keep_chunks_for(s->P.sims, on);
+    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
+    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
+    return cz_search_reset_trees(s, stream);
+}
+
+int cz_search_node_values(cz_search* s, const uint16_t* path, int path_len, double* s2, int32_t* vn, uint8_t* counts,
+                          void* stream)
+{
+    if (!s || path_len < 0 || path_len > MAXD_LDS || (path_len > 0 && !path))
+        return serr(CZ_ERR_ARG, "cz_search_node_values: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (!s->Z.on) {                                             // off: the trees hold no V records
+        const size_t G = (size_t)s->P.G;
+        hipError_t e = hipSuccess;
+        if (s2) e = hipMemsetAsync(s2, 0, sizeof(double) * G * MAXMOVES, st);
+        if (e == hipSuccess && vn) e = hipMemsetAsync(vn, 0, sizeof(int32_t) * G * MAXMOVES, st);
+        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
+        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_values", e);
+    }
+    hipLaunchKernelGGL(k_node_values, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, s2, vn, counts);
+    S_LAUNCH_CHECK("cz_search_node_values");
+    return CZ_OK;
+}
+
+int cz_search_root_lcb(cz_search* s, double* lcb, int32_t* pick, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_root_lcb: null handle");
+    if (!s->Z.on) return serr(CZ_ERR_ARG, "cz_search_root_lcb: the lower-confidence-bound move choice is off (cz_search_set_lcb)");
+    hipLaunchKernelGGL(k_root_lcb, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, s->Z, lcb, pick);
+    S_LAUNCH_CHECK("cz_search_root_lcb");
+    return CZ_OK;
+}
+
+int cz_lcb_pick(const uint16_t* labels, const int32_t* n, const double* w, const double* s2, const int32_t* vn,
+                const uint8_t* n_edges, int rows, double z, double min_ratio, double* out_lcb, int32_t* out_pick, void* stream)
+{
+    if (!labels || !n || !w || !s2 || !vn || !n_edges || rows < 0) return serr(CZ_ERR_ARG, "cz_lcb_pick: null argument or rows < 0");
+    if (!finite_nonneg(z) || !(min_ratio >= 0.0 && min_ratio <= 1.0))
+        return serr(CZ_ERR_ARG, "cz_lcb_pick: z negative or not finite, or min_ratio outside [0, 1]");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_lcb_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, labels, n, w, s2, vn, n_edges, rows, z, min_ratio,
+                       out_lcb, out_pick);
+    S_LAUNCH_CHECK("cz_lcb_pick");
     return CZ_OK;
 }
 
@@ -1563,7 +1664,8 @@ int cz_search_node_stats(cz_search* s, const uint16_t* path, int path_len, uint1
 int cz_search_pv(cz_search* s, int max_len, uint16_t* moves, int32_t* visits, void* stream)
 {
     if (!s || !moves || !visits || max_len < 1) return serr(CZ_ERR_ARG, "cz_search_pv: bad argument");
-    hipLaunchKernelGGL(k_pv, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, max_len, moves, visits);
+    if (s->Z.on) hipLaunchKernelGGL(k_pv_lcb, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, max_len, moves, visits, s->Z);
+    else hipLaunchKernelGGL(k_pv, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, max_len, moves, visits);
     S_LAUNCH_CHECK("cz_search_pv");
     return CZ_OK;
 }
@@ -1571,7 +1673,8 @@ int cz_search_pv(cz_search* s, int max_len, uint16_t* moves, int32_t* visits, vo
 int cz_search_choose(cz_search* s, const double* u, int32_t* action, void* stream)
 {
     if (!s || !action) return serr(CZ_ERR_ARG, "cz_search_choose: null argument");
-    if (s->P.solver) hipLaunchKernelGGL(k_choose<true>, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
+    if (s->Z.on) hipLaunchKernelGGL(k_choose_lcb, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action, s->Z);
+    else if (s->P.solver) hipLaunchKernelGGL(k_choose<true>, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
     else hipLaunchKernelGGL(k_choose<false>, dim3(s->P.G), dim3(64), 0, (hipStream_t)stream, s->P, s->B, u, action);
     S_LAUNCH_CHECK("cz_search_choose");
     return CZ_OK;

@@ -10,6 +10,7 @@
 #include "xq_search_tree.h"
 #include "xq_search_ml.h"
 #include "xq_search_draw.h"
+#include "xq_search_var.h"
 #include "xq_search_select.h"
 #include "xq_search_solver.h"
 #include "xq_search_ply.h"
@@ -514,6 +515,59 @@ __global__ __launch_bounds__(64) void k_pv(SearchParams P, SearchBuffers B, int 
     }
 }
 
+// k_pv with the lower-confidence-bound move choice on (cz_search_set_lcb): the line's first move is lcb_pick's on the root's
+// fields as they stand, so that a finished search's line starts with the move choose_action plays; below the root the line is
+// k_pv's.  A kernel of its own with k_pv's walk written out again: k_pv keeps its text (the same walk as a function of both gave
+// k_pv another instruction stream).
+__global__ __launch_bounds__(64) void k_pv_lcb(SearchParams P, SearchBuffers B, int max_len, uint16_t* __restrict__ moves,
+                                              int32_t* __restrict__ visits, LcbState Z)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    int node = B.g_root[g];
+    int d = 0;
+    for (; d < max_len && node >= 0; ++d) {
+        char* base = rec_ptr(gv, (uint32_t)node);
+        const NodeHdr hdr = load_hdr(base);
+        const int nm = (int)(hdr.meta & 0xFF);
+        if (hdr.stat == 0u || nm == 0) break;
+        const uint16_t* pm = node_mv(base, nm);
+        const EdgeStat* sb = edge_ptr(gv, hdr.stat);
+        int best_n = 0, best_j = -1;
+        if (d == 0) {                                         // the root: the rule, with the ply's bans
+            const LcbEdges E = load_lcb_root(B, gv);
+            double bound[2];
+            best_j = lcb_pick(E, Z.z, Z.ratio, bound);
+            if (best_j >= 0) best_n = best_j < 64 ? __builtin_amdgcn_readlane(E.n[0], best_j & 63)
+                                                  : __builtin_amdgcn_readlane(E.n[1], best_j & 63);
+        } else {                                              // below it: last j with n >= running maximum, as k_pv
+            for (int j = lane; j < nm; j += 64) {
+                const int n = sb[j].n;
+                if (n >= best_n) { best_n = n; best_j = j; }
+            }
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {               // arg max of (n, j)
+                const int on = __shfl_xor(best_n, s, 64), oj = __shfl_xor(best_j, s, 64);
+                if (oj >= 0 && (best_j < 0 || on > best_n || (on == best_n && oj > best_j))) { best_n = on; best_j = oj; }
+            }
+            best_n = uni(best_n); best_j = uni(best_j);
+        }
+        if (best_j < 0 || best_n <= 0) break;
+        if (lane == 0) {
+            moves[(size_t)g * max_len + d] = pm[best_j];
+            visits[(size_t)g * max_len + d] = best_n;
+        }
+        node = child_id(uni(sb[best_j].child));
+    }
+    for (int i = d + lane; i < max_len; i += 64) {
+        moves[(size_t)g * max_len + i] = (uint16_t)NOMOVE;
+        visits[(size_t)g * max_len + i] = 0;
+    }
+}
+
 template <bool SOLVE>
 __global__ __launch_bounds__(64) void k_choose(SearchParams P, SearchBuffers B, const double* __restrict__ u,
                                               int32_t* __restrict__ action)
@@ -524,6 +578,95 @@ __global__ __launch_bounds__(64) void k_choose(SearchParams P, SearchBuffers B, 
     const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, L.chtab);   // counts go straight to the global block
     const int a = choose_action<SOLVE>(P, B, gv, L, u ? u[g] : 0.5, B.g_enable_resign[g] != 0);
     if (lane_id() == 0) action[g] = a;
+}
+
+// k_choose with the lower-confidence-bound move choice on (cz_search_set_lcb refuses the solver)
+__global__ __launch_bounds__(64) void k_choose_lcb(SearchParams P, SearchBuffers B, const double* __restrict__ u,
+                                                  int32_t* __restrict__ action, LcbState Z)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, L.chtab);   // counts go straight to the global block
+    const int a = choose_action<false, true>(P, B, gv, L, u ? u[g] : 0.5, B.g_enable_resign[g] != 0, Z);
+    if (lane_id() == 0) action[g] = a;
+}
+
+// Lower-confidence-bound move choice: the V records of the root, or of the node reached from it along path[g][0 .. path_len) as
+// in k_root_stats: per edge s2 and vn (0 past the node's edges and without a statistics block).  Launched only while the option is
+// on: a tree grown without it has no V records.
+__global__ __launch_bounds__(64) void k_node_values(SearchParams P, SearchBuffers B, const uint16_t* __restrict__ path,
+                                                   int path_len, double* __restrict__ s2, int32_t* __restrict__ vn,
+                                                   uint8_t* __restrict__ counts)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    int node = walk_path(B, gv, path, path_len);
+    if (node == 0) node = -1;                                   // (id 0 is "none": an object never given a root)
+    int nm = 0;
+    const VRec* vb = nullptr;
+    if (node >= 0) {
+        const NodeHdr hdr = load_hdr(rec_ptr(gv, (uint32_t)node));
+        nm = (int)(hdr.meta & 0xFF);
+        if (hdr.stat) vb = v_block(edge_ptr(gv, hdr.stat), nm);
+    }
+    for (int j = lane; j < MAXMOVES; j += 64) {
+        VRec r{0.0, 0, 0};
+        if (j < nm && vb) r = vb[j];
+        if (s2) s2[(size_t)g * MAXMOVES + j] = r.s2;
+        if (vn) vn[(size_t)g * MAXMOVES + j] = r.vn;
+    }
+    if (lane == 0 && counts) counts[g] = (uint8_t)nm;
+}
+
+// cz_search_root_lcb: lcb_pick on every current root, with the bans of the current set_roots: lcb [G][128] (NaN for an edge that
+// is not eligible or past the edges), pick [G] (-1: the root is not in the tree, or every edge is banned).
+__global__ __launch_bounds__(64) void k_root_lcb(SearchParams P, SearchBuffers B, LcbState Z, double* __restrict__ lcb,
+                                                int32_t* __restrict__ pick)
+{
+    __shared__ uint32_t chtab[MAX_CHUNKS];
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    const GameView gv = make_view(B, P, g, B.counters + (size_t)g * CT_COUNT, chtab);
+    const int lane = lane_id();
+    const LcbEdges E = load_lcb_root(B, gv);
+    double bound[2];
+    const int j = lcb_pick(E, Z.z, Z.ratio, bound);
+    if (lcb) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) lcb[(size_t)g * MAXMOVES + lane + 64 * h] = bound[h];
+    }
+    if (pick && lane == 0) pick[g] = j;
+}
+
+// cz_lcb_pick: the same arithmetic on caller-supplied rows [rows][128], one wavefront per row
+__global__ __launch_bounds__(64) void k_lcb_rows(const uint16_t* __restrict__ labels, const int32_t* __restrict__ n,
+                                                const double* __restrict__ w, const double* __restrict__ s2,
+                                                const int32_t* __restrict__ vn, const uint8_t* __restrict__ n_edges, int rows,
+                                                double z, double ratio, double* __restrict__ out_lcb,
+                                                int32_t* __restrict__ out_pick)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const int lane = lane_id();
+    LcbEdges E{};
+    E.nm = n_edges[r] > MAXMOVES ? MAXMOVES : n_edges[r];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const size_t i = (size_t)r * MAXMOVES + lane + 64 * h;
+        if (lane + 64 * h >= E.nm) continue;
+        E.lab[h] = labels[i]; E.n[h] = n[i]; E.w[h] = w[i]; E.s2[h] = s2[i]; E.vn[h] = vn[i];
+    }
+    double bound[2];
+    const int j = lcb_pick(E, z, ratio, bound);
+    if (out_lcb) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) out_lcb[(size_t)r * MAXMOVES + lane + 64 * h] = bound[h];
+    }
+    if (out_pick && lane == 0) out_pick[r] = j;
 }
 
 // cz_search_stop: no further simulations are STARTED; the ones in flight are backed up by the next round

@@ -9,6 +9,7 @@
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_solver.h"
+#include "xq_search_var.h"
 #include "xq_search_records.h"
 
 namespace {
@@ -177,9 +178,11 @@ XQ_D double ply_tau(const SearchParams& P, int turns, int inc)
 // returns the chosen label, or -1 when the player resigns.  u is the uniform draw of np.random.choice.
 // SOLVE (the MCTS solver is on, an instantiation of its own): at a WIN root with a non-banned winning edge the move is
 // that edge (rule 1 of select_solve), whatever tau is; resignation is tested first.
-template <bool SOLVE = false>
+// LCB (the lower-confidence-bound move choice is on, cz_search_set_lcb; an instantiation of its own): at tau = 0 the move is
+// lcb_pick's on the root's fields; the resignation test and the sampling at tau > 0 are what they were.
+template <bool SOLVE = false, bool LCB = false>
 XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L, double u,
-                       bool enable_resign)
+                       bool enable_resign, const LcbState& Z = LcbState{})
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -243,6 +246,21 @@ XQ_D int choose_action(const SearchParams& P, const SearchBuffers& B, const Game
     // temperature (player.py:453-461)
     const double tau = ply_tau(P, turns, uni((int)B.g_increase_temp[g]));
     int chosen = 0;
+    if constexpr (LCB) {
+        if (tau == 0.0) {
+            // (nothing is in flight here, so vn = n on every edge; no eligible edge: the most visited one, as below)
+            const LcbEdges E = load_lcb_root(B, gv);
+            double bound[2];
+            const int pick = lcb_pick(E, Z.z, Z.ratio, bound);
+            if (pick >= 0) {
+                const int pn = pick < 64 ? __builtin_amdgcn_readlane(E.n[0], pick) : __builtin_amdgcn_readlane(E.n[1], pick - 64);
+                const int pl = pick < 64 ? __builtin_amdgcn_readlane((int)E.lab[0], pick)
+                                         : __builtin_amdgcn_readlane((int)E.lab[1], pick - 64);
+                if (pn > 0) chosen = pl & 0x7FFF;
+            }
+            return chosen;
+        }
+    }
     if (tau == 0.0) {
         if (lane == 0) {
             int best = -1, bestn = -1;                       // np.argmax: first maximum in label order

@@ -4,14 +4,15 @@
 // text only moves between these headers, and the proof of a move is the unit's device assembly, kernel by kernel
 // (EXPERIMENTS.md, "the search unit's text in headers").
 //
-// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop, k_sim_ml, k_sim_draw;
-// k_reserve_ml, k_cache_fill, k_advance, k_advance_stop, k_advance_script, k_stop_reset, k_noise.
+// The round's kernels: sim_body and its instantiations k_sim, k_sim_cached, k_sim_solve, k_sim_stop, k_sim_ml, k_sim_draw, k_sim_var;
+// k_reserve_ml, k_cache_fill, k_advance, k_advance_lcb, k_advance_stop, k_advance_script, k_stop_reset, k_noise.
 #pragma once
 #include "xq_search_tree.h"
 #include "xq_search_attach.h"
 #include "xq_search_select.h"
 #include "xq_search_ml.h"
 #include "xq_search_draw.h"
+#include "xq_search_var.h"
 #include "xq_search_solver.h"
 #include "xq_search_sim.h"
 #include "xq_search_ply.h"
@@ -41,7 +42,11 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // DRAW: the draw average (cz_search_set_draw) is on; likewise.  The body of k_sim_draw too; D is read by that instantiation
 // alone.  Its attach turns the draw column of the leaf's win / draw / loss row into dq (draw_quanta), keeps dq in the node header
 // and takes it up the path (backup_d), d then v; leaf by leaf without the prefetch, as ML's.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false, bool DRAW = false>
+// VAR: the lower-confidence-bound move choice (cz_search_set_lcb) is on; likewise.  The body of k_sim_var too.  Its attach takes
+// the leaf's squared value up the path (backup_v) before the value; leaf by leaf without the prefetch, as ML's.  The selection is
+// the plain one and no state of the option is read here: z and the ratio matter to the move choice alone.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false, bool DRAW = false,
+          bool VAR = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
                    int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C,
@@ -129,7 +134,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         };
         LeafPre lp{0, 0, 0, 0.0f, 0.0f};
         uint64_t rest = leaves;
-        if (!ML && !DRAW && rest) {
+        if (!ML && !DRAW && !VAR && rest) {
             const int i0 = __ffsll((long long)rest) - 1;
             pre_a(lp, i0);
             pre_b(lp, i0);
@@ -156,6 +161,11 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), dq);      // (word 3, as the moves-left k)
                 load_path(P, gv, L, i, depth);
                 backup_d(gv, L, depth, dq);
+                backup(P, gv, L, depth, v);
+            } else if constexpr (VAR) {
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                load_path(P, gv, L, i, depth);
+                backup_v(gv, L, depth, v);
                 backup(P, gv, L, depth, v);
             } else if (CACHE && ((cached >> i) & 1ull)) {
                 cached_attach(gv, node, keep_v, (float)v);
@@ -211,6 +221,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), dq);
                 backup_d(gv, L, depth, dq);
             }
+            if constexpr (VAR) backup_v(gv, L, depth, (double)value[slot]);
             backup(P, gv, L, depth, (double)value[slot]);             // float(v) of a float32
             sim_finish(gv, i, &active);
         }
@@ -237,7 +248,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
         } else if (df.lo != 0 || df.hi != 0) {
             // the descents of this phase (resumed simulations / a fresh batch) are over: the terminal and repetition
             // values they produced are applied now, in index order
-            flush_deferred<SOLVE, ML, DRAW>(P, gv, L, df, &active);
+            flush_deferred<SOLVE, ML, DRAW, VAR>(P, gv, L, df, &active);
             continue;
         } else if ((mask & SIM_SELECT) && active == 0) {              // 3. next lock-step batch (player.py:169-178)
             const int tasks = uni(B.g_tasks_left[g]);
@@ -271,8 +282,8 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM, CACHE, SOLVE, ML, DRAW>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar, fresh,
-                                                   df, C, (mask & SIM_SELECT) != 0, M, D);
+        run_sim<HIST, GUM, CACHE, SOLVE, ML, DRAW, VAR>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar,
+                                                        fresh, df, C, (mask & SIM_SELECT) != 0, M, D);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -366,7 +377,19 @@ __global__ __launch_bounds__(64, 4) void k_sim_draw(SearchParams P, SearchBuffer
                                                             EvalCache{}, StopState{}, MovesLeftState{}, D);
 }
 
-// The moves-left utility's share of the per-ply reservation (the draw average's too: its D records take the M records' place,
+// k_sim with the lower-confidence-bound move choice on (cz_search_set_lcb refuses the Gumbel search, the solver, the stop rules,
+// the evaluation cache, a script, the moves-left utility and the draw average)
+template <bool HIST>
+__global__ __launch_bounds__(64, 4) void k_sim_var(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
+                                               const float* __restrict__ value, void* planes, int mask, int compact,
+                                               int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
+{
+    __shared__ SearchLDS L;
+    sim_body<HIST, false, false, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows,
+                                                                   q_count, EvalCache{});
+}
+
+// The moves-left utility's share of the per-ply reservation (the draw average's and the V records' too: its D records take the M records' place,
 // and cz_search_round launches this kernel for either): a statistics block is twice the size while the option is on, so
 // between k_advance (whose begin_search reserved the plain blocks) and k_sim(SELECT) every searching game tops its chunks up to
 // what its outstanding simulations can use.  A game that cannot be served here has just begun its ply (a ply under way was
@@ -456,6 +479,7 @@ __global__ __launch_bounds__(64) void k_cache_fill(SearchParams P, SearchBuffers
 // FULL: the full Gumbel search is on (cz_search_set_gumbel_full): the visit entries hold its target.  An instantiation of
 // its own, so that the kernel launched while it is off is the text it was.
 // SOLVE: the MCTS solver is on (cz_search_set_solver): choose_action's; likewise.
+// (k_advance_lcb below is this kernel with choose_action's LCB.)
 template <bool FULL, bool SOLVE = false>
 __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B, VisitRing V)
 {
@@ -468,6 +492,27 @@ __global__ __launch_bounds__(64) void k_advance(SearchParams P, SearchBuffers B,
     if (P.mode == MODE_SELFPLAY) {
         for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
             advance_game<FULL, SOLVE>(P, B, gv, L, V);
+            if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
+        }
+    } else if (lane_id() == 0) {
+        B.g_phase[g] = PH_READY;
+    }
+    counters_flush(gv);
+}
+
+// k_advance with the lower-confidence-bound move choice on (cz_search_set_lcb): a tau = 0 ply plays lcb_pick's move.  A kernel
+// of its own, so that the ones launched while the option is off keep their names and their text.
+__global__ __launch_bounds__(64) void k_advance_lcb(SearchParams P, SearchBuffers B, VisitRing V, LcbState Z)
+{
+    __shared__ SearchLDS L;
+    const int g = blockIdx.x;
+    if (g >= P.G) return;
+    if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_active[g]) != 0 || uni(B.g_tasks_left[g]) != 0) return;
+    const GameView gv = make_view(B, P, g, L.ctr, L.chtab);
+    counters_begin(gv);
+    if (P.mode == MODE_SELFPLAY) {
+        for (int it = 0; it < 8; ++it) {          // a search with nothing to do (fully reused root) ends at once
+            advance_game<false, false, false, false, true>(P, B, gv, L, V, StopState{}, ScriptState{}, Z);
             if (uni((int)B.g_phase[g]) != PH_SEARCH || uni(B.g_tasks_left[g]) != 0) break;
         }
     } else if (lane_id() == 0) {

@@ -19,9 +19,11 @@ namespace {
 // (script_move), and everything after it is the loop's.  The game ends where the rules end it -- the script then has nothing
 // left but, possibly, the rules' final_move -- or where the script ends; its value is X.z, it is stored without a lottery and
 // flagged GAME_SCRIPTED.  Anything else is a mismatch: GAME_SCRIPT_MISMATCH, store = 0, the next script.
-template <bool FULL, bool SOLVE = false, bool STOP = false, bool SCRIPT = false>   // (emit_visits', choose_action's)
+// LCB (k_advance_lcb, cz_search_set_lcb): choose_action's; Z its state.
+template <bool FULL, bool SOLVE = false, bool STOP = false, bool SCRIPT = false, bool LCB = false>   // (emit_visits', choose_action's)
 XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
-                       const VisitRing& V, const StopState& S = StopState{}, const ScriptState& X = ScriptState{})
+                       const VisitRing& V, const StopState& S = StopState{}, const ScriptState& X = ScriptState{},
+                       const LcbState& Z = LcbState{})
 {
     const int lane = lane_id();
     const int g = gv.g;
@@ -40,7 +42,7 @@ XQ_D void advance_game(const SearchParams& P, const SearchBuffers& B, const Game
         action = script_move(B, gv, X, script_off, script_len, turns);
     } else {
         const double u = philox_uniform(P.seed, game_id, 1, (uint64_t)turns);
-        action = choose_action<SOLVE>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0);
+        action = choose_action<SOLVE, LCB>(P, B, gv, L, u, uni((int)B.g_enable_resign[g]) != 0, Z);
     }
     if (V.ring) {
         const bool fast = ply_is_fast(P, game_id, turns);

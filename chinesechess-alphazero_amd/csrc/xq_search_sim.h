@@ -12,6 +12,7 @@
 #include "xq_search_select.h"
 #include "xq_search_ml.h"
 #include "xq_search_draw.h"
+#include "xq_search_var.h"
 #include "xq_search_solver.h"
 #include "xq_evalcache.h"
 #include "../../include/czero.h"
@@ -263,12 +264,13 @@ XQ_D int edge_move(const GameView& gv, int node, int edge)
 }
 
 // backup() of a simulation that ends without a network row; ML: m goes up too, with k = 0; DRAW: d goes up too, with dq (0
-// for every such end but a repetition worth 0: flush_deferred)
-template <bool ML, bool DRAW = false>
+// for every such end but a repetition worth 0: flush_deferred); VAR: v * v goes up too (backup_v)
+template <bool ML, bool DRAW = false, bool VAR = false>
 XQ_D void backup_end(const SearchParams& P, const GameView& gv, const SearchLDS& L, int depth, double v, int dq = 0)
 {
     if constexpr (ML) backup_m(gv, L, depth, 0);
     if constexpr (DRAW) backup_d(gv, L, depth, dq);
+    if constexpr (VAR) backup_v(gv, L, depth, v);
     backup(P, gv, L, depth, v);
 }
 
@@ -282,7 +284,9 @@ XQ_D void backup_end(const SearchParams& P, const GameView& gv, const SearchLDS&
 // them (select_edge<GUM, ML>), a backup made here takes m up with k = 0; likewise an instantiation of its own.
 // DRAW: the draw average is on (cz_search_set_draw): a statistics block carries its D records in the M records' place, the
 // selection reads them with the sign of the node's depth, a backup made here takes d up with dq = 0; likewise.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool ML = false, bool DRAW = false>
+// VAR: the lower-confidence-bound move choice is on (cz_search_set_lcb): a statistics block carries its V records in the same
+// place, the selection is the plain one, a backup made here takes its squared value up (backup_v); likewise.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool ML = false, bool DRAW = false, bool VAR = false>
 XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                   const RoundIO& io, const RootCtx& rc0, int root, int sim, int node, int depth, int* active,
                   Arena& ar, bool fresh, Deferred& df, const EvalCache& C, bool probe,
@@ -306,7 +310,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         const bool made = idx < 0;
         if (idx < 0) idx = expand_node(P, B, gv, L, L.r.ml[0], nm, slot, h, ar, mir);
         else mir = (load_hdr(rec_ptr(gv, (uint32_t)idx)).meta & NODE_MIRRORED) != 0u;   // (the frame its attach will read)
-        if (idx < 0) { count(gv, CT_OVERFLOW_SIMS); backup_end<ML, DRAW>(P, gv, L, 0, 0.0); sim_finish(gv, sim, active); return; }
+        if (idx < 0) { count(gv, CT_OVERFLOW_SIMS); backup_end<ML, DRAW, VAR>(P, gv, L, 0, 0.0); sim_finish(gv, sim, active); return; }
         bool hit = false;
         if constexpr (CACHE) {
             if (probe && made) hit = cache_probe(C, gv, L.key, h, mir, nm, idx, (size_t)g * P.K + sim);
@@ -356,7 +360,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         }
         if (depth >= P.max_depth) {
             count(gv, CT_DEPTH_OVERFLOW);
-            backup_end<ML, DRAW>(P, gv, L, depth, 0.0);
+            backup_end<ML, DRAW, VAR>(P, gv, L, depth, 0.0);
             sim_finish(gv, sim, active);
             return;
         }
@@ -365,10 +369,10 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         uint32_t stat = hdr.stat;
         const bool fresh_stat = stat == 0u && nm > 0;
         if (fresh_stat) {
-            stat = heap_alloc(ar, (ML || DRAW) ? 2 * nm : nm);      // (ML / DRAW: the M / D records directly behind the statistics)
+            stat = heap_alloc(ar, (ML || DRAW || VAR) ? 2 * nm : nm);   // (ML / DRAW / VAR: the M / D / V records directly behind the statistics)
             if (stat == 0u) {
                 count(gv, CT_OVERFLOW_SIMS);
-                backup_end<ML, DRAW>(P, gv, L, depth, 0.0);
+                backup_end<ML, DRAW, VAR>(P, gv, L, depth, 0.0);
                 sim_finish(gv, sim, active);
                 return;
             }
@@ -379,7 +383,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         if (fresh_stat) {
             // edge j is initialised by the lane that owns it in select_edge (j & 63): no fence before its later loads
             for (int j = lane; j < nm; j += 64) sb[j] = EdgeStat{0.0, 0, CHILD_UNKNOWN};
-            if constexpr (ML || DRAW) {                             // (a D record is an M record's bytes)
+            if constexpr (ML || DRAW || VAR) {                      // (a D record is an M record's bytes; a V record's zero too)
                 MRec* mb = m_block(sb, nm);
                 for (int j = lane; j < nm; j += 64) mb[j] = MRec{0, 0, 0};
             }
@@ -395,7 +399,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
                                             DRAW ? draw_sigma(D, depth) : 0.0);
         }
         if (pk.j < 0) {                                             // "Best action is None": cannot happen
-            backup_end<ML, DRAW>(P, gv, L, depth, 0.0);
+            backup_end<ML, DRAW, VAR>(P, gv, L, depth, 0.0);
             sim_finish(gv, sim, active);
             return;
         }
@@ -445,7 +449,7 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
                     idx = expand_node(P, B, gv, L, L.r.ml[0], d.nmoves, slot, h, ar, mir);     // player.py:211-221
                     if (idx < 0) {
                         count(gv, CT_OVERFLOW_SIMS);
-                        backup_end<ML, DRAW>(P, gv, L, depth, 0.0);
+                        backup_end<ML, DRAW, VAR>(P, gv, L, depth, 0.0);
                         sim_finish(gv, sim, active);
                         return;
                     }
@@ -488,7 +492,8 @@ XQ_D void load_path(const SearchParams& P, const GameView& gv, SearchLDS& L, int
 // ML: m goes up with k = 0, as after every end without a network row
 // DRAW: d goes up too: a deferred value of 0 is a repetition that is a draw (the only deferred value that is 0), dq = 2^20;
 // every other one (a terminal child, a repetition worth +-1) has dq = 0
-template <bool SOLVE = false, bool ML = false, bool DRAW = false>
+// VAR: the squared value goes up too: 4 for a terminal child, 0 or 1 for a repetition
+template <bool SOLVE = false, bool ML = false, bool DRAW = false, bool VAR = false>
 XQ_D void flush_deferred(const SearchParams& P, const GameView& gv, SearchLDS& L, Deferred& df, int* active)
 {
     if (df.lo == 0 && df.hi == 0) return;
@@ -497,7 +502,7 @@ XQ_D void flush_deferred(const SearchParams& P, const GameView& gv, SearchLDS& L
         const int depth = uni(gv.s_depth[i]);
         const double v = (double)uni(gv.s_node[i]);
         load_path(P, gv, L, i, depth);
-        backup_end<ML, DRAW>(P, gv, L, depth, v, (DRAW && v == 0.0) ? DRAW_QUANTA : 0);
+        backup_end<ML, DRAW, VAR>(P, gv, L, depth, v, (DRAW && v == 0.0) ? DRAW_QUANTA : 0);
         if constexpr (SOLVE) {
             if (v == 2.0 || v == -2.0) solve_walk(gv, L, depth);
         }

@@ -199,7 +199,10 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * a setter refused for it names "the moves-left utility is on (cz_search_set_moves_left)".
  * The draw average (cz_search_set_draw, below) stands there too, consulted after the moves-left utility: it is not beside the
  * same six, nor beside the moves-left utility itself, in both directions; a setter refused for it names "the draw average is
- * on (cz_search_set_draw)". */
+ * on (cz_search_set_draw)".
+ * The lower-confidence-bound move choice (cz_search_set_lcb, below) stands there too, consulted after the draw average: it is
+ * not beside the same six, nor beside the moves-left utility or the draw average, in both directions; a setter refused for it
+ * names "the lower-confidence-bound move choice is on (cz_search_set_lcb)". */
 
 /* Scripted games: walk stored games again (MuZero's Reanalyse).  n games: game id i < n starts from init_boards[i] (90
  * bytes, the first mover's frame, as cz_replay_games takes them), plays labels[offsets[i] .. offsets[i+1]) and ends with
@@ -898,6 +901,60 @@ int cz_search_node_draws(cz_search* s, const uint16_t* path, int path_len, int64
                          uint8_t* counts, void* stream);
 /* dq[i] = the quanta of d[i * stride], by the attach's own conversion; d DEVICE [n * stride], dq DEVICE [n]; stride >= 1. */
 int cz_draw_quanta(const float* d, int stride, int32_t* dq, int n, void* stream);
+/* ---- lower confidence bound (off by default; the reference has no such option; KataGo's and lc0's LCB move choice) ----------
+ * run.py self / eval --lcb Z [--lcb-min-visits R]; the UCI options LCB, LCBMinVisits.  Where the temperature is 0 the move
+ * played is the one whose value has the best lower confidence bound, not the most visited one.  It needs no special network
+ * output.  With the option off no kernel output, record or counter differs by a bit, and the kernels launched are the ones
+ * launched before it existed.  With it on visit counts, W and priors are the plain search's bit for bit: the selection is the
+ * plain one, only the move played can differ, and with it the game that follows.
+ *
+ * STORAGE.  Each edge has a V record {double s2, int32 vn, int32 spare}, one granule, directly behind the node's statistics
+ * block: edge j's record is granule stat + nm + j -- the M and D records' place, hence the exclusions.  Allocated with the
+ * statistics block, only while the option is on; the reservation and the chunks a game keeps count the larger block.
+ * BACKUP.  On every edge of the path s2 = s2 + x * x and vn += 1, x being the value the backup adds to that edge's W beyond the
+ * virtual loss; the product is rounded, then the sum, nothing fused.  Every end of a simulation that is backed up counts: a
+ * network leaf, a terminal child (x = +-2, so 4), a repetition (0 or 1), "no edge", a depth cut-off, an overflow.  Virtual loss
+ * does not touch the record.  s2 changes where W changes and in the same order, so it is as deterministic as W.  The records
+ * carry no sign: a reused subtree needs no fix-up.
+ * THE RULE (lcb_pick, csrc/xq_search_var.h), on a node's edges with their labels (bit 0x8000 marks a root's banned moves),
+ * n, w, s2, vn, and z >= 0, R in [0, 1]; float64 in this order, every operation rounded on its own:
+ *   n_max    = the greatest n_j over the non-banned edges
+ *   eligible : not banned, vn_j >= 2, n_j > 0, (double)n_j >= R * (double)n_max
+ *   q        = w_j / (double)n_j
+ *   var      = s2_j / (double)vn_j - q * q                     (negative: 0)
+ *   var      = var * ((double)vn_j / (double)(vn_j - 1))
+ *   lcb_j    = q - z * sqrt(var / (double)vn_j)                (NaN: the edge is not eligible after all)
+ *   pick     = the eligible edge with the greatest lcb; on a tie the greater n; then the LOWEST label
+ *   no eligible edge: the most visited non-banned edge, the lowest label on a tie (the rule without the option)
+ * WHERE.  The move choice at temperature 0 alone -- self-play from the ply where the temperature reaches 0, the arena from ply
+ * 4, cz_search_choose in external mode --, after the resignation test, which goes on reading max q.  Nothing is in flight for
+ * the game then, so vn_j = n_j.  With a temperature the sampling by visit counts is unchanged.  cz_search_pv: the line's first
+ * move is the rule's on the root's fields as they stand (approximate while simulations are in flight, as the most-visited line
+ * is; on a finished search the move played), below the root the most visited edge.  Visit entries, every record column and the
+ * pruning of forced playouts (whose c* is the most visited move by definition) are unchanged.
+ *
+ * cz_search_set_lcb: z finite and >= 0, 0 = off; min_ratio (R) in [0, 1].  Switching on or off resets the trees as
+ * cz_search_reset_trees does (the statistics blocks change size); a new z or ratio while on resets nothing.  Switching on is
+ * refused (CZ_ERR_ARG) beside the Gumbel search (its own root rule and move choice), the solver, the stop rules and the
+ * evaluation cache (a kernel instantiation each; the solver has its own move choice, the unreachable-lead stop promises the most
+ * visited move), a script (its moves are the record's), the moves-left utility and the draw average (the same granules), and
+ * each of them is refused beside it, naming "the lower-confidence-bound move choice is on (cz_search_set_lcb)"; switching off
+ * is never refused.  Synchronises the stream. */
+int cz_search_set_lcb(cz_search* s, double z, double min_ratio, void* stream);
+/* The V records of the node cz_search_node_stats would report for the same path (path NULL / path_len 0: the root; path_len
+ * at most 128): s2 [G][128] float64 and vn [G][128] int32, 0 past the node's edges; counts [G] uint8, the node's edges.  Any
+ * may be NULL; all DEVICE.  With the option off everything is 0, counts included. */
+int cz_search_node_values(cz_search* s, const uint16_t* path, int path_len, double* s2, int32_t* vn, uint8_t* counts,
+                          void* stream);
+/* The rule on every current root with the bans of the current cz_search_set_roots: lcb [G][128] float64, NaN for an edge that
+ * is not eligible or past the edges; pick [G] int32, the edge index the rule picks, -1 for a root that is not in the tree.
+ * Either may be NULL; DEVICE.  CZ_ERR_ARG while the option is off. */
+int cz_search_root_lcb(cz_search* s, double* lcb, int32_t* pick, void* stream);
+/* The rule alone on caller-supplied rows [rows][128] (labels uint16 with the banned bit 0x8000, n int32, w float64, s2 float64, vn
+ * int32; n_edges [rows] uint8), one wavefront per row: out_lcb [rows][128], out_pick [rows] (-1 for a row without a non-banned
+ * edge); either may be NULL; all DEVICE. */
+int cz_lcb_pick(const uint16_t* labels, const int32_t* n, const double* w, const double* s2, const int32_t* vn,
+                const uint8_t* n_edges, int rows, double z, double min_ratio, double* out_lcb, int32_t* out_pick, void* stream);
 /* ---- early stop of a settled ply (both rules off by default; the reference has no such option) ---------------------------
  * run.py self --kld-gain G [--kld-interval I]; run.py eval --smart-pruning, the UCI option SmartPruning.  Two rules end a
  * ply's search before its budget is spent.  With both off no kernel output, record or counter differs by a bit, and the

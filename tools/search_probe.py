@@ -7,6 +7,7 @@ events over the next rounds (per-launch: mean / median / p99).  A/B tool for cha
 
     python tools/search_probe.py [--rounds 3000] [--timed 200] [--compact 1] [--masks-only 1] [--leaf-mirror P]
                                  [--moves-left-slope S [--moves-left-cap C]] [--draw-average 1 [--draw-score S]]
+                                 [--lcb Z [--lcb-min-visits R]]
 """
 import argparse
 import json
@@ -32,6 +33,9 @@ def main():
     ap.add_argument("--draw-average", type=int, default=0,
                     help="1: the draw average (cz_search_set_draw); the draw stub's third output feeds it")
     ap.add_argument("--draw-score", type=float, default=0.0)
+    ap.add_argument("--lcb", type=float, default=0.0,
+                    help="z of the lower-confidence-bound move choice (cz_search_set_lcb): k_sim_var, k_advance_lcb")
+    ap.add_argument("--lcb-min-visits", type=float, default=0.15)
     a = ap.parse_args()
     import types
     import stub_net
@@ -52,6 +56,8 @@ def main():
     if a.draw_average:
         import stub_draw
         s.set_draw(True, a.draw_score)
+    if a.lcb:
+        s.set_lcb(a.lcb, a.lcb_min_visits)
     s.start_selfplay(seed=20260923)
     planes_of = (lambda: s.queue_planes()) if a.masks_only else (lambda: s.planes)   # (the same planes either way: same trees)
 
@@ -97,7 +103,8 @@ def main():
            "mean_depth": c["sum_depth"] / max(1, c["sims"]), "plies": c["plies"], "games": c["games"],
            "tree_resets": c["tree_resets"], "overflow_sims": c["overflow_sims"], "nodes": m["nodes"],
            "tree_gb": m["tree_bytes"] / 1e9, "tree_bytes_per_game": m["tree_bytes"] / a.games,
-           "moves_left_slope": a.moves_left_slope, "draw_average": a.draw_average, "draw_score": a.draw_score}
+           "moves_left_slope": a.moves_left_slope, "draw_average": a.draw_average, "draw_score": a.draw_score,
+           "lcb": a.lcb, "lcb_min_visits": a.lcb_min_visits}
     if a.leaf_mirror:                      # (of the slots as they stand: every slot has held a leaf by now)
         out["leaf_mirror"] = a.leaf_mirror
         out["mirrored_share_of_slots"] = float(s.mirrored.float().mean())
