@@ -191,6 +191,24 @@ int keep_chunks_for(int sims, bool ml = false)
     return (int)((need + USABLE - 1) / USABLE);
 }
 
+// The pool is sized at creation (raised to the plain blocks' floor, games x keep_chunks + 1) and never grows.  An option that
+// doubles the statistics blocks may need more chunks for one full search: where the pool is below the floor of the larger
+// blocks the option's setter refuses to switch it on, so that a game that dropped its tree always holds one full search.
+// Returns false after setting the error text.
+bool pool_holds_larger_blocks(const cz_search* s, const char* me)
+{
+    int keep = keep_chunks_for(s->P.sims, true);
+    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
+    if (keep < s->keep_chunks_created) keep = s->keep_chunks_created;
+    const long long floor_chunks = (long long)s->P.G * keep + 1;
+    if (floor_chunks <= (long long)s->P.n_chunks) return true;
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s: the pool of %d chunks is below the floor of the larger statistics blocks, games x keep_chunks"
+             " + 1 = %lld", me, s->P.n_chunks, floor_chunks);
+    serr(CZ_ERR_ARG, buf);
+    return false;
+}
+
 // initial state of the pool: game g owns chunks [g * keep, (g + 1) * keep), the rest is free
 int init_pool(cz_search* s)
 {
@@ -1034,6 +1052,7 @@ int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float
     if (on && s->D.on) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the draw average is on (cz_search_set_draw)");
     if (on && s->Z.on)
         return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the lower-confidence-bound move choice is on (cz_search_set_lcb)");
+    if (on && !(s->M.slope > 0.0) && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->M.slope > 0.0;
@@ -1102,6 +1121,7 @@ int cz_search_set_draw(cz_search* s, int on_, double score, const float* wdl_row
         snprintf(buf, sizeof(buf), "%s: %s", me, LCB_PHRASE);
         return serr(CZ_ERR_ARG, buf);
     }
+    if (on && !s->D.on && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->D.on != 0;
@@ -1164,6 +1184,7 @@ int cz_search_set_lcb(cz_search* s, double z, double min_ratio, void* stream)
         snprintf(buf, sizeof(buf), "%s: %s", me, s->M.slope > 0.0 ? ML_PHRASE : DRAW_PHRASE);
         return serr(CZ_ERR_ARG, buf);
     }
+    if (on && !s->Z.on && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->Z.on != 0;

@@ -114,7 +114,14 @@ typedef struct cz_search_cfg {
     int32_t max_nodes_per_game;      /* sizes a game's hash table and chunk table; 0 = (2 * max_game_length + 4) * sims,
                                         i.e. the tree of the longest game is kept whole (self_play.py:84,98-100) */
     int32_t pool_chunks;             /* tree memory shared by all games, in chunks of 1 MiB; 0 = what the games can use,
-                                        at most 80 % of the device memory that is free at creation */
+                                        at most 80 % of the device memory that is free at creation.  Raised to the floor
+                                        games * keep_chunks + 1 (cz_search_info out[12]) of the plain statistics blocks, once,
+                                        here: the pool never grows.  The moves-left utility, the draw average and the
+                                        lower-confidence-bound move choice double a statistics block and may raise
+                                        keep_chunks: their setters refuse (CZ_ERR_ARG) to switch on where the pool is below
+                                        games * keep_chunks + 1 of the larger blocks, so that a game that dropped its tree
+                                        always holds one full search.  A caller that sets pool_chunks and one of them sizes
+                                        the pool by the keep_chunks reported while the option is on */
     int32_t max_depth;               /* longest path of one simulation: one that reaches an evaluated node with this many
                                         edges behind it backs up 0 (counter depth_overflow); 0 = 128, at most 128 */
     int32_t max_game_length;         /* config.play.max_game_length (full moves) */

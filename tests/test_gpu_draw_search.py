@@ -13,6 +13,7 @@ import time
 import numpy as np
 import pytest
 
+import composed_oracle as co
 import draw_search_oracle as do
 import search_limits as sl
 import search_model as sm
@@ -59,13 +60,15 @@ def _assert_draws_equal(got, want, what):
     assert not got["dsum"][0, nm:].any() and not got["dn"][0, nm:].any(), what
 
 
-def _walk(gpu, case, sims, use_history=False, variant="hash", score=TEST_SCORE):
+def _walk(gpu, case, sims, use_history=False, variant="hash", score=TEST_SCORE, k=0.0):
     """One case on the device and in the oracle, search by search: root statistics, D records at the root and one level down,
-    counters, the played move.  Returns (how many searches ran, the oracle)."""
-    o = do.Search(sm.play_cfg(sims), case["salt"], score=score,
+    counters, the pruned counts, the played move.  k: forced playouts on both sides.  Returns (how many searches ran, the
+    oracle)."""
+    o = do.Search(sm.play_cfg(sims), case["salt"], k, score=score,
                   net=lambda planes: sd.draw_stub_numpy(planes, case["salt"], variant))
     s = gpu.S.Search(_pc(sims), 1, seed=7, use_history=use_history)
     s.set_draw(True, score)
+    s.set_forced_playouts(k)
     ev = _eval(case["salt"], variant)
     line = [(case["state"], [sm.ban_of(case, sims)] if case["kind"] == "ban" else [])]
     done = 0
@@ -93,8 +96,10 @@ def _walk(gpu, case, sims, use_history=False, variant="hash", score=TEST_SCORE):
                 _assert_draws_equal(s.node_draws([root.labels[j]]), o.node_draws(child) if is_node else None,
                                     f"{what} child {j}")
             assert linked >= 1, what
+            co.assert_targets(s.root_targets(), o.node_stats(state), no_act, o.cfg.c_puct, k, what)
             best = o.best_move(state, no_act)
             assert xo.label_str(int(s.choose(None)[0])) == best, what
+            assert xo.label_str(int(s.pv()[0][0])) == co.pv_first(o.node_stats(state), no_act), what
             done += 1
             if case["kind"] == "reuse" and done == 1:
                 line.append((xo.step(state, best), []))

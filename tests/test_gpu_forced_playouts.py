@@ -288,7 +288,8 @@ def test_selfplay_ply_0_matches_the_oracle(gpu):
 
 
 # ---- 5. self-play, every ply, by invariant -------------------------------------------------------------------------------
-def _check_invariants(games, pc, capped):
+def _check_invariants(games, pc, capped, plays_most_visited=True):
+    """plays_most_visited=False: the move at tau = 0 is another rule's (the lower-confidence-bound move choice)."""
     n_pruned = n_fast = removed = 0
     for g in games:
         vis = g["visits"]
@@ -312,7 +313,7 @@ def _check_invariants(games, pc, capped):
                 top = np.flatnonzero(live & (e.n == e.n[live].max()))
                 star = top[np.argmin(e.moves[top])]
                 tau = pc.tau_decay_rate ** (i + 1) if i < 30 and pc.tau_decay_rate else 0.0
-                if tau < 0.1 and state not in seen and not e.resign:        # tau = 0 (a repeated position may raise it)
+                if plays_most_visited and tau < 0.1 and state not in seen and not e.resign:        # tau = 0 (a repeated position may raise it)
                     assert xo.label_str(int(e.moves[star])) == moves[i], (g["game_id"], i)
             if not e.resign:
                 seen.append(state)

@@ -15,6 +15,7 @@ import types
 import numpy as np
 import pytest
 
+import composed_oracle as co
 import lcb_oracle as lo
 import search_model as sm
 import stub_net
@@ -61,13 +62,14 @@ def _assert_values_equal(got, want, what):
     assert not got["s2"][0, nm:].any() and not got["vn"][0, nm:].any(), what
 
 
-def _walk(gpu, case, sims, z=Z, use_history=False):
+def _walk(gpu, case, sims, z=Z, use_history=False, k=0.0):
     """One case on the device and in the oracle, search by search: root statistics, V records at the root and one level below
-    the played move, the rule's bounds and pick, the played move, the line's first move.  Returns (the played moves, the most
-    visited moves)."""
-    o = lo.Search(sm.play_cfg(sims), case["salt"], 0.0, z, R)
+    the played move, the rule's bounds and pick, the pruned counts, the played move, the line's first move.  k: forced
+    playouts on both sides.  Returns (the played moves, the most visited moves)."""
+    o = lo.Search(sm.play_cfg(sims), case["salt"], k, z, R)
     s = gpu.S.Search(_pc(sims), 1, seed=7, use_history=use_history)
     s.set_lcb(z, R)
+    s.set_forced_playouts(k)
     line = [(case["state"], [sm.ban_of(case, sims)] if case["kind"] == "ban" else [])]
     played, most = [], []
     try:
@@ -93,6 +95,7 @@ def _walk(gpu, case, sims, z=Z, use_history=False):
             assert np.array_equal(np.isnan(lcb[0, :nm]), np.isnan(want_lcb)) and np.isnan(lcb[0, nm:]).all(), what
             ok = ~np.isnan(want_lcb)
             assert ok.any() and (_bits(lcb[0, :nm][ok]) == _bits(want_lcb[ok])).all(), (what, lcb[0, :nm], want_lcb)
+            co.assert_targets(s.root_targets(), ref, no_act, o.cfg.c_puct, k, what)
             best = o.best_move(state, no_act)
             assert xo.label_str(int(s.choose(None)[0])) == best, what
             assert xo.label_str(int(s.pv()[0][0])) == best, what

@@ -68,18 +68,19 @@ def flag_aware(ev, M):
         fl = flags.bool()
         x = planes.clone()
         x[fl] = planes[fl].flip(-1)
-        p, v = ev(x)
-        p = p.clone()
+        out = ev(x)                                             # (policy, value, and what else the search reads: as it is)
+        p = out[0].clone()
         p[fl] = p[fl][:, M]
-        return p, v
+        return (p,) + tuple(out[1:])
     return f
 
 
 def drive(gpu, M, K, rate, logits=False, boards_only=False, hist=False, compact=False, spec=None, seed=7, sims=SIMS,
-          evaluate=None, flags=True):
+          evaluate=None, flags=True, setup=None, probe=None):
     """One search of STATES driven round by round through round() / leaf_rows() (or the compact queue) with the flag-aware
-    stand-in.  rate None: set_leaf_mirror is never called.  Returns dict(st=root_stats, ctr, flags=[(slot, flag)] of every
-    leaf written, in round order)."""
+    stand-in.  rate None: set_leaf_mirror is never called.  setup(s): further setters, before the roots are set; an `evaluate`
+    with a third output writes it to the rows that setup's option reads (moves_left_x or wdl_rows).  Returns
+    dict(st=root_stats, ctr, flags=[(slot, flag)] of every leaf written, in round order; probe: probe(s) after the search)."""
     t = gpu.torch
     pc = play_config(simulation_num_per_move=sims, search_threads=K)
     s = gpu.S.Search(pc, G, seed=seed, use_history=hist)
@@ -91,6 +92,8 @@ def drive(gpu, M, K, rate, logits=False, boards_only=False, hist=False, compact=
     for r in rate if isinstance(rate, tuple) else (rate,):          # (a tuple: one call after the other)
         if r is not None:
             s.set_leaf_mirror(r, flags=flags)
+    if setup:
+        setup(s)
     if hist:
         roots, prev, kind = _two_ply_lines(STATES)
         s.set_roots(boards_tensor(gpu, roots), prev_boards=boards_tensor(gpu, prev),
@@ -112,16 +115,23 @@ def drive(gpu, M, K, rate, logits=False, boards_only=False, hist=False, compact=
             continue
         fl = s.mirrored[rows] if s.mirrored is not None else t.zeros(n, dtype=t.uint8, device="cuda")
         seen += sorted(zip(rows.tolist(), fl.tolist()))          # (the order of the rows within a round is arbitrary)
-        p, v = ev(s.queue_planes(rows=rows), fl)
+        p, v, *more = ev(s.queue_planes(rows=rows), fl)
         if logits:
             p = t.log(p.double()).float()
+        extra = s.wdl_rows if s.draw_on else s.moves_left_x
         if compact:
             s.policy[:n] = p
             s.value[:n] = v
+            if more:
+                extra[:n] = more[0]
         else:
             s.policy.index_copy_(0, rows, p)
             s.value.index_copy_(0, rows, v)
+            if more:
+                extra.index_copy_(0, rows, more[0])
     out = dict(st=s.root_stats(), ctr=s.counters(), flags=seen, K=s.K)
+    if probe:
+        out["probe"] = probe(s)
     s.close()
     return out
 

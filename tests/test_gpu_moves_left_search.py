@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import composed_oracle as co
 import moves_left_search_oracle as mo
 import search_model as sm
 import stub_moves_left as sml
@@ -58,13 +59,14 @@ def _assert_ml_equal(got, want, what):
     assert not got["ksum"][0, nm:].any() and not got["mn"][0, nm:].any(), what
 
 
-def _walk(gpu, case, sims, use_history=False, variant="hash"):
+def _walk(gpu, case, sims, use_history=False, variant="hash", k=0.0, slope=TEST_SLOPE, cap=TEST_CAP):
     """One case on the device and in the oracle, search by search: root statistics, M records at the root and one level down,
-    counters, the played move.  Returns how many searches ran."""
-    o = mo.Search(sm.play_cfg(sims), case["salt"], slope=TEST_SLOPE, cap=TEST_CAP,
+    counters, the pruned counts, the played move.  k: forced playouts on both sides.  Returns how many searches ran."""
+    o = mo.Search(sm.play_cfg(sims), case["salt"], k, slope=slope, cap=cap,
                   net=lambda planes: sml.ml_stub_numpy(planes, case["salt"], variant))
     s = gpu.S.Search(_pc(sims), 1, seed=7, use_history=use_history)
-    s.set_moves_left(TEST_SLOPE, TEST_CAP)
+    s.set_moves_left(slope, cap)
+    s.set_forced_playouts(k)
     ev = _eval(case["salt"], variant)
     line = [(case["state"], [sm.ban_of(case, sims)] if case["kind"] == "ban" else [])]
     done = 0
@@ -92,8 +94,10 @@ def _walk(gpu, case, sims, use_history=False, variant="hash"):
                 _assert_ml_equal(s.node_moves_left([root.labels[j]]), o.node_moves_left(child) if is_node else None,
                                  f"{what} child {j}")
             assert linked >= 1, what
+            co.assert_targets(s.root_targets(), o.node_stats(state), no_act, o.cfg.c_puct, k, what)
             best = o.best_move(state, no_act)
             assert xo.label_str(int(s.choose(None)[0])) == best, what
+            assert xo.label_str(int(s.pv()[0][0])) == co.pv_first(o.node_stats(state), no_act), what
             done += 1
             if case["kind"] == "reuse" and done == 1:
                 line.append((xo.step(state, best), []))
