@@ -157,6 +157,9 @@ def declare(L):
         "cz_search_node_values": [vp, vp, i32, vp, vp, vp, vp],
         "cz_search_root_lcb": [vp, vp, vp, vp],
         "cz_lcb_pick": [vp, vp, vp, vp, vp, vp, i32, d, d, vp, vp, vp],
+        "cz_search_set_cpuct_schedule": [vp, d, d, vp],
+        "cz_search_set_policy_temperature": [vp, d, vp],
+        "cz_debug_cpuct": [vp, i32, d, d, d, vp, vp, vp],
     }
     for name, argtypes in optional.items():
         if hasattr(L, name):
@@ -273,6 +276,8 @@ class Search:
         self.draw_on, self.draw_score = False, 0.0   # set_draw(): the draw average and what a draw is worth at the root
         self.wdl_rows = None                   # ... and its rows: [slots, 3] float32 beside policy / value, the network's W / D / L
         self.lcb, self.lcb_min_ratio = 0.0, 0.15   # set_lcb(): the lower-confidence-bound move choice, z 0 = off
+        self.cpuct_factor, self.cpuct_base = 0.0, 19652.0   # set_cpuct_schedule(): c_puct grows with the visit count, factor 0 = off
+        self.policy_temp = 1.0                 # set_policy_temperature(): the temperature of the priors' softmax, 1 = off
 
     # -- lifetime --
     def close(self):
@@ -559,6 +564,29 @@ class Search:
             raise _native.NativeError("this libczero.so has no lower-confidence-bound move choice (cz_search_set_lcb)")
         _native.check(self.L.cz_search_set_lcb(self.h, float(z), float(min_ratio), self._stream()), "cz_search_set_lcb")
         self.lcb, self.lcb_min_ratio = float(z), float(min_ratio)
+
+    def set_cpuct_schedule(self, factor=0.0, base=19652.0):
+        """The schedule of c_puct (cz_search_set_cpuct_schedule; include/czero.h has the arithmetic): the exploration constant
+        of a selection is c_puct + factor * log((1 + sum_n + base) / base), sum_n the node's own count -- at the root, below it,
+        in the solver's selection and in policy target pruning.  factor = 0 is off: c_puct as it is.  A plain parameter: it
+        runs beside every other option, resets nothing, and a refusal (factor < 0, base < 1, not finite) leaves the
+        attributes as they were."""
+        if not hasattr(self.L, "cz_search_set_cpuct_schedule"):
+            raise _native.NativeError("this libczero.so has no c_puct schedule (cz_search_set_cpuct_schedule)")
+        _native.check(self.L.cz_search_set_cpuct_schedule(self.h, float(factor), float(base), self._stream()),
+                      "cz_search_set_cpuct_schedule")
+        self.cpuct_factor, self.cpuct_base = float(factor), float(base)
+
+    def set_policy_temperature(self, T=1.0):
+        """The policy temperature (cz_search_set_policy_temperature): with logit rows (policy_logits()) a node's priors are the
+        softmax of l / T over its legal moves, 0.1 <= T <= 10; T = 1 is off.  Refused with probability rows, and
+        policy_logits(False) is refused while T != 1.  A change of T resets the trees and empties the evaluation cache: call
+        it between plies, before start_selfplay() / set_roots() and before a graph capture."""
+        if not hasattr(self.L, "cz_search_set_policy_temperature"):
+            raise _native.NativeError("this libczero.so has no policy temperature (cz_search_set_policy_temperature)")
+        _native.check(self.L.cz_search_set_policy_temperature(self.h, float(T), self._stream()),
+                      "cz_search_set_policy_temperature")
+        self.policy_temp = float(T)
 
     def node_values(self, path=None):
         """The value records of the node node_stats(path) reports (cz_search_node_values): dict(s2 float64 [G, 128] and vn
@@ -1170,6 +1198,22 @@ def gumbel_interior_pick(n, w, p, n_edges, v, c_visit, c_scale):
                                                         C.c_void_p(pick.data_ptr()), C.c_void_p(score.data_ptr()), stream),
                   "cz_gumbel_interior_pick")
     return pick, score
+
+
+def debug_cpuct(sum_n, c_puct, factor, base):
+    """cz_debug_cpuct: the schedule's device function on a list of sums.  sum_n: a contiguous cuda int32 tensor [rows].
+    Returns (c float64 [rows], c32 float32 [rows] -- the factor of the float32 product below the root) on the device."""
+    import torch
+    _native.require_gpu()
+    if sum_n.dtype != torch.int32 or sum_n.dim() != 1 or not sum_n.is_cuda or not sum_n.is_contiguous():
+        raise ValueError("debug_cpuct: sum_n must be a contiguous cuda int32 tensor [rows]")
+    rows = int(sum_n.numel())
+    c = torch.empty((rows,), dtype=torch.float64, device=sum_n.device)
+    c32 = torch.empty((rows,), dtype=torch.float32, device=sum_n.device)
+    _native.check(_native.lib().cz_debug_cpuct(C.c_void_p(sum_n.data_ptr()), rows, float(c_puct), float(factor), float(base),
+                                               C.c_void_p(c.data_ptr()), C.c_void_p(c32.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "cz_debug_cpuct")
+    return c, c32
 
 
 def lcb_pick(labels, n, w, s2, vn, n_edges, z, min_ratio):

@@ -49,10 +49,15 @@ class DrawUnavailable(ValueError):
     """The draw average was asked for and the network behind the pipe has the scalar value head."""
 
 
+class PolicyTempUnavailable(ValueError):
+    """A policy temperature was asked for and the pipe hands the search probabilities: the temperature is applied to logits."""
+
+
 class CChessPlayer:
     def __init__(self, config, search_tree=None, pipes=None, play_config=None, enable_resign=False,
                  debugging=False, uci=False, use_history=False, side=0, solver=None, smart_pruning=None,
-                 moves_left_slope=None, moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None):
+                 moves_left_slope=None, moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None,
+                 cpuct_factor=None, cpuct_base=None, policy_temp=None):
         import torch
         self.config = config
         self.play_config = play_config or self.config.play
@@ -100,6 +105,15 @@ class CChessPlayer:
         self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15) if lcb_min_visits is None else lcb_min_visits)
         self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
         search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
+        # c_puct schedule and policy temperature (search_options.py CPUCT_DEFAULTS, POLICY_TEMP_DEFAULTS): likewise; plain
+        # parameters, nothing excludes them.  The pipe hands over probabilities (the reference's protocol), in which a
+        # temperature cannot be applied: PolicyTempUnavailable, before a device is asked for
+        self.cpuct_factor = float(getattr(ec, "cpuct_factor", 0.0) if cpuct_factor is None else cpuct_factor)
+        self.cpuct_base = float(getattr(ec, "cpuct_base", 19652.0) if cpuct_base is None else cpuct_base)
+        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
+        self.policy_temp = float(getattr(ec, "policy_temp", 1.0) if policy_temp is None else policy_temp)
+        if search_options.check_policy_temp(self.policy_temp):
+            raise PolicyTempUnavailable(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="the player's pipe"))
         if self.moves_left and not getattr(pipes, "moves_left_head", False):
             raise MovesLeftUnavailable(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
         if self.draw and not getattr(pipes, "wdl_head", False):
@@ -126,6 +140,8 @@ class CChessPlayer:
             self._search.set_draw(True, self.draw_score)
         if self.lcb_on:
             self._search.set_lcb(self.lcb, self.lcb_min_visits)
+        if self.cpuct_on:
+            self._search.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes, moves_left=False, wdl=False):

@@ -111,6 +111,10 @@ class EngineConfig(_Section):
                          # lower-confidence-bound move choice (run.py self / eval --lcb Z --lcb-min-visits R, the UCI options
                          # LCB / LCBMinVisits): off at lcb 0; works with every model
                          **search_options.LCB_DEFAULTS,
+                         # c_puct schedule (run.py self / eval / reanalyse --cpuct-factor F --cpuct-base B, the UCI options
+                         # CPuctFactor / CPuctBase): off at factor 0; policy temperature (--policy-temp T, PolicyTemperature):
+                         # off at 1, needs a network that hands over logits
+                         **search_options.CPUCT_DEFAULTS, **search_options.POLICY_TEMP_DEFAULTS,
                          # record_visits, fast_sims, ... smart_pruning: the search options, all off (search_options.py)
                          **search_options.DEFAULTS)
 

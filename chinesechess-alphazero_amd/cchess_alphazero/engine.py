@@ -46,7 +46,8 @@ class SelfPlayEngine:
                  full_rate=None, forced_playouts=None, record_q=None, record_surprise=None, leaf_mirror=None,
                  gumbel=None, gumbel_visit=None, gumbel_scale=None, gumbel_full=None, eval_cache=None, solver=None,
                  kld_gain=None, kld_interval=None, resign_audit=None, script=None, moves_left_slope=None,
-                 moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None):
+                 moves_left_cap=None, draw_score=None, show_wdl=None, lcb=None, lcb_min_visits=None, cpuct_factor=None,
+                 cpuct_base=None, policy_temp=None):
         """config: the reference's Config object (config.play.* / config.model.* are read).
         net: a CChessNet (random-init if None).  evaluator: optional callable planes -> (policy, value)
         replacing the network (tests).  trunk: "mfma" (hand-written convolution kernel, the default where the
@@ -86,8 +87,20 @@ class SelfPlayEngine:
         lcb, lcb_min_visits (None = config.engine's values): the lower-confidence-bound move choice (Search.set_lcb), on with
         lcb > 0: from the ply where the temperature reaches 0 a game plays the move with the best lower bound of its value.  It
         stands beside the table the same way: check(lcb=True) refuses what search_options.LCB_EXCLUDES lists, a script, the
-        moves-left utility and the draw average.  Every network will do."""
+        moves-left utility and the draw average.  Every network will do.
+        cpuct_factor, cpuct_base, policy_temp (None = config.engine's values): the schedule of c_puct (Search.set_cpuct_schedule,
+        on with cpuct_factor > 0) and the policy temperature (Search.set_policy_temperature, on with policy_temp != 1).  Plain
+        parameters of the search: they exclude nothing.  The temperature is applied to logits: an evaluator callable, or a
+        network that hands over probabilities (engine.policy_logits = False, or one without supports_logits()), is refused
+        with a ValueError, here and in set_network."""
         ec_ = getattr(config, "engine", None)
+        self.cpuct_factor = float(getattr(ec_, "cpuct_factor", 0.0) if cpuct_factor is None else cpuct_factor)
+        self.cpuct_base = float(getattr(ec_, "cpuct_base", 19652.0) if cpuct_base is None else cpuct_base)
+        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
+        self.policy_temp = float(getattr(ec_, "policy_temp", 1.0) if policy_temp is None else policy_temp)
+        self.policy_temp_on = search_options.check_policy_temp(self.policy_temp)
+        if self.policy_temp_on and evaluator is not None:
+            raise ValueError(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="an evaluator callable"))
         self.moves_left_slope = float(getattr(ec_, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
         self.moves_left_cap = float(getattr(ec_, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
         self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
@@ -185,6 +198,12 @@ class SelfPlayEngine:
             self.search.set_draw(True, self.draw_score)
         if self.lcb_on:
             self.search.set_lcb(self.lcb, self.lcb_min_visits)
+        if self.cpuct_on:
+            self.search.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
+            logger.info(search_options.CPUCT_LOG.format(cpuct_factor=self.cpuct_factor, cpuct_base=self.cpuct_base))
+        if self.policy_temp_on:                # (after _install: the rows are logits by now, or _install has refused)
+            self.search.set_policy_temperature(self.policy_temp)
+            logger.info(search_options.POLICY_TEMP_LOG.format(policy_temp=self.policy_temp))
         self.script = script
         if script is not None:                 # last: the library checks it against everything that is on
             self.search.set_script(*script)
@@ -208,6 +227,9 @@ class SelfPlayEngine:
         # the legal moves anyway, reference player.py:272-283: the denominator cancels) -- engine.policy_logits = False opts out
         want = getattr(getattr(self.config, "engine", None), "policy_logits", True)
         self.policy_logits = bool(want and self.net.supports_logits())
+        if self.policy_temp_on and not self.policy_logits:
+            raise ValueError(search_options.POLICY_TEMP_REFUSAL.format(
+                T=self.policy_temp, who="this network" if want else "a network with engine.policy_logits = False"))
         self.search.policy_logits(self.policy_logits)
         # the leaves' occupancy boards beside their planes: the fused input layer takes them directly (engine.leaf_masks = False
         # opts out; only the hand-written trunk on byte planes reads them)
@@ -243,6 +265,8 @@ class SelfPlayEngine:
             raise ValueError("hot reload: " + DRAW_REFUSAL.format(score=self.draw_score, show_wdl=self.show_wdl))
         torch.cuda.synchronize(self.device)
         built = self._build_net(net)                           # may raise: nothing has been touched yet
+        if self.policy_temp_on and not built.supports_logits():    # (likewise the policy temperature and logit rows)
+            raise ValueError("hot reload: " + search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="this network"))
         had_graph = self._graph is not None
         self._graph = None
         torch.cuda.synchronize(self.device)

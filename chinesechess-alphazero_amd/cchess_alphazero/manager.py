@@ -89,6 +89,16 @@ _FLAGS = [
     ("--lcb-min-visits", dict(type=float, default=0.15, metavar="R",
                               help="(self, eval, with --lcb) a move takes part with at least R times the most visited move's "
                                    "visits (in [0, 1])")),
+    ("--cpuct-factor", dict(type=float, default=0.0, metavar="F",
+                            help="(self, eval, reanalyse) c_puct schedule: the exploration constant of a node grows with its "
+                                 "visit count N, c_puct + F * log((1 + N + B) / B), as in AlphaZero's paper (finite, >= 0; 0 = off: "
+                                 "the constant c_puct; lc0 uses 3.894 with --cpuct-base 38739)")),
+    ("--cpuct-base", dict(type=float, default=19652.0, metavar="B",
+                          help="(self, eval, reanalyse, with --cpuct-factor) the base B of the schedule (finite, >= 1)")),
+    ("--policy-temp", dict(type=float, default=1.0, metavar="T",
+                           help="(self, eval, reanalyse) policy temperature: a node's priors are the softmax of its legal moves' "
+                                "logits divided by T, so T > 1 flattens a policy that training on visit counts has sharpened "
+                                "(0.1 <= T <= 10; 1 = off; lc0 uses 1.4 .. 1.6); needs a network that hands over logits")),
     ("--value-head", dict(choices=["scalar", "wdl"], default=None,
                           help="(opt) the value head of a new model (--new, or no best model yet): scalar = Dense(1) + tanh, "
                                "the reference; wdl = Dense(3) + softmax over win / draw / loss, trained by cross-entropy "
@@ -162,6 +172,14 @@ def build_config(args):
             raise search_options.SearchOptionError("--lcb is an option of `run.py self` and `run.py eval`")
         if args.lcb_min_visits != search_options.LCB_DEFAULTS["lcb_min_visits"] and args.cmd not in ("self", "eval"):
             raise search_options.SearchOptionError("--lcb-min-visits is an option of `run.py self` and `run.py eval`")
+        searches = ("self", "eval", "reanalyse")
+        cpuct_on = search_options.check_cpuct(args.cpuct_factor, args.cpuct_base, flags=True)
+        if cpuct_on and args.cmd not in searches:
+            raise search_options.SearchOptionError("--cpuct-factor is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
+        if args.cpuct_base != search_options.CPUCT_DEFAULTS["cpuct_base"] and args.cmd not in searches:
+            raise search_options.SearchOptionError("--cpuct-base is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
+        if search_options.check_policy_temp(args.policy_temp, flags=True) and args.cmd not in searches:
+            raise search_options.SearchOptionError("--policy-temp is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
                              history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on,
                              draw=draw_on, lcb=lcb_on)
@@ -171,6 +189,8 @@ def build_config(args):
     engine.moves_left_slope, engine.moves_left_cap = float(args.moves_left_slope), float(args.moves_left_cap)
     engine.draw_score = float(args.draw_score)
     engine.lcb, engine.lcb_min_visits = float(args.lcb), float(args.lcb_min_visits)
+    engine.cpuct_factor, engine.cpuct_base = float(args.cpuct_factor), float(args.cpuct_base)
+    engine.policy_temp = float(args.policy_temp)
     # the resignation audit: game-loop options, not search options; their one check is the library's
     from cchess_alphazero.lib.resign_audit import check_options
     try:

@@ -214,6 +214,41 @@ def check_lcb(z, ratio, flags=False):
     return z > 0.0
 
 
+# The schedule of c_puct (run.py self / eval / reanalyse --cpuct-factor F --cpuct-base B, engine.cpuct_factor and
+# engine.cpuct_base, Search.set_cpuct_schedule) and the policy temperature (--policy-temp T, engine.policy_temp,
+# Search.set_policy_temperature) stand beside the table as well, for another reason: the table's rule "on = first value truthy,
+# default falsy" does not fit T = 1.  They are plain parameters of the kernels that run anyway, so they exclude nothing and
+# nothing excludes them: check() has no context for them.  The temperature needs logit rows, which no table row can say.
+CPUCT_DEFAULTS = dict(cpuct_factor=0.0, cpuct_base=19652.0)
+CPUCT_LOG = ("c_puct schedule: the exploration constant of a node is c_puct + {cpuct_factor:g} * log((1 + N + {cpuct_base:g}) / "
+             "{cpuct_base:g}), N the node's visit count")
+POLICY_TEMP_DEFAULTS = dict(policy_temp=1.0)
+POLICY_TEMP_LOG = "policy temperature {policy_temp:g}: a node's priors are the softmax of its legal moves' logits / {policy_temp:g}"
+POLICY_TEMP_REFUSAL = ("the policy temperature (policy_temp {T:g}) is applied to the legal moves' logits, and {who} hands the "
+                       "search probabilities")
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def check_cpuct(factor, base, flags=False):
+    """Raises SearchOptionError unless factor is finite and >= 0 and base finite and >= 1; True when the schedule is on
+    (factor > 0)."""
+    if not (_number(factor) and _finite(factor, None)):
+        raise SearchOptionError(f"{'--cpuct-factor' if flags else 'cpuct_factor'} {factor}: expected a finite value >= 0")
+    if not (_number(base) and 1.0 <= base < INF):
+        raise SearchOptionError(f"{'--cpuct-base' if flags else 'cpuct_base'} {base}: expected a finite value >= 1")
+    return factor > 0.0
+
+
+def check_policy_temp(T, flags=False):
+    """Raises SearchOptionError unless 0.1 <= T <= 10; True when the temperature is on (T != 1)."""
+    if not (_number(T) and 0.1 <= T <= 10.0):               # (False for NaN)
+        raise SearchOptionError(f"{'--policy-temp' if flags else 'policy_temp'} {T}: expected a value in [0.1, 10]")
+    return T != 1.0
+
+
 VALUES = {v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 

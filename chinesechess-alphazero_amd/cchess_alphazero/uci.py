@@ -30,7 +30,10 @@ ENGINE_ID = ("id name CCZero-MI355X", "id author https://cczero.org (reference),
              "option name UCI_ShowWDL type check default false",
              "option name DrawScore type string default 0",
              "option name LCB type string default 0",
-             "option name LCBMinVisits type string default 0.15")
+             "option name LCBMinVisits type string default 0.15",
+             "option name CPuctFactor type string default 0",
+             "option name CPuctBase type string default 19652",
+             "option name PolicyTemperature type string default 1")
 
 
 def wdl_permille(w, n, dsum, dn):
@@ -153,6 +156,18 @@ class UCI:
                     setattr(self.config.engine, key, v)
                 except ValueError:
                     self._say(f"info string {args[1]} {args[3]}: expected {expected}")
+            elif args[1] in ("CPuctFactor", "CPuctBase", "PolicyTemperature"):
+                # the schedule of c_puct and the policy temperature (cz_search_set_cpuct_schedule, _policy_temperature): likewise
+                key, lo, hi, expected = {"CPuctFactor": ("cpuct_factor", 0.0, 1.7976931348623157e308, "a finite value >= 0"),
+                                         "CPuctBase": ("cpuct_base", 1.0, 1.7976931348623157e308, "a finite value >= 1"),
+                                         "PolicyTemperature": ("policy_temp", 0.1, 10.0, "a value in [0.1, 10]")}[args[1]]
+                try:
+                    v = float(args[3])
+                    if not lo <= v <= hi:
+                        raise ValueError(args[3])
+                    setattr(self.config.engine, key, v)
+                except ValueError:
+                    self._say(f"info string {args[1]} {args[3]}: expected {expected}")
 
     def cmd_position(self, args):
         if not self.is_ready:
@@ -200,7 +215,7 @@ class UCI:
     def cmd_go(self, args):
         if not self.is_ready:
             return
-        from cchess_alphazero.agent.player import CChessPlayer, DrawUnavailable, MovesLeftUnavailable
+        from cchess_alphazero.agent.player import CChessPlayer, DrawUnavailable, MovesLeftUnavailable, PolicyTempUnavailable
         self._finish_worker()
         depth, infinite, budget = None, True, None
         for i, a in enumerate(args):
@@ -227,6 +242,9 @@ class UCI:
             except DrawUnavailable as e:                  # the model has the scalar value head: likewise
                 self._say(f"info string {e}")
                 without.update(draw_score=0.0, show_wdl=False)
+            except PolicyTempUnavailable as e:            # the pipe hands over probabilities: likewise
+                self._say(f"info string {e}")
+                without["policy_temp"] = 1.0
         self.player.out = self.out
         self.player._idle.clear()                         # a `stop` that beats the worker to the player must wait for it
         with self._lock:

@@ -157,6 +157,15 @@ class EvaluateWorker:
         self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15))
         self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
         search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
+        # c_puct schedule and policy temperature of both models' searches (run.py eval --cpuct-factor F --cpuct-base B
+        # --policy-temp T): plain parameters, nothing excludes them.  The arena's evaluators hand over probabilities, in which a
+        # temperature cannot be applied
+        self.cpuct_factor = float(getattr(ec, "cpuct_factor", 0.0))
+        self.cpuct_base = float(getattr(ec, "cpuct_base", 19652.0))
+        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
+        self.policy_temp = float(getattr(ec, "policy_temp", 1.0))
+        if search_options.check_policy_temp(self.policy_temp):
+            raise ValueError(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="the arena's evaluator"))
         self._eval3 = tuple(_with_moves_left(e, self.moves_left_slope) for e in evaluators) if self.moves_left else None
         if self.draw:
             self._eval3 = tuple(_with_wdl(e, self.draw_score, self.show_wdl) for e in evaluators)
@@ -234,6 +243,8 @@ class EvaluateWorker:
                 s.set_draw(True, self.draw_score)
             if self.lcb_on:
                 s.set_lcb(self.lcb, self.lcb_min_visits)
+            if self.cpuct_on:
+                s.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
 
         def counters_now():
             c = [s.counters() for s in searches]

@@ -154,6 +154,12 @@ struct SearchParams {
     // MCTS solver (cz_search_set_solver); read by the host alone, which launches the SOLVE instantiations of k_sim, k_advance
     // and k_choose while it is on
     int solver;             // 0 = off
+    // c_puct schedule (cz_search_set_cpuct_schedule); read through cpuct_of only: select_edge, select_solve and the callers of
+    // prune_targets
+    double cpuct_factor;    // F, 0 = off: the exploration constant is c_puct at every visit count
+    double cpuct_base;      // B >= 1
+    // policy temperature (cz_search_set_policy_temperature); read where a logit row becomes weights (prior_norm's callers)
+    float inv_temp;         // (float)(1 / T), 1 = off
 };
 constexpr int GUMBEL_MAX_M = 128;
 

@@ -19,6 +19,9 @@
 // With the draw average on (cz_search_set_draw) they are the k_sim_draw instantiations, with k_reserve_ml in the same place.
 // With the lower-confidence-bound move choice on (cz_search_set_lcb) they are the k_sim_var instantiations, likewise, and
 // k_advance is k_advance_lcb.
+// With the schedule of c_puct on (cz_search_set_cpuct_schedule) every one of these k_sim kernels is its SCHED instantiation,
+// whose selection computes the exploration constant from the node's visit count; the policy temperature
+// (cz_search_set_policy_temperature) is a factor in the attach of the same kernels.
 // The host then runs ONE network forward over the whole queue.
 // There is no host decision inside a round and no device->host copy, so a round (kernel + network
 // forward) can be replayed from a HIP graph.
@@ -311,6 +314,9 @@ int cz_search_create(const cz_search_cfg* c, cz_search** out)
     P.game_id_stride = (uint32_t)P.G;
     P.gumbel_visit = 50.0;
     P.gumbel_scale = 1.0;
+    P.cpuct_factor = 0.0;
+    P.cpuct_base = 19652.0;
+    P.inv_temp = 1.0f;
     P.ring_cap = c->ring_capacity > 0 ? c->ring_capacity : 2 * P.G + 64;
     P.record_stride = (int)((sizeof(GameRecord) + sizeof(uint16_t) * (size_t)(P.max_plies + 2) + 15) & ~(size_t)15);
     if (P.planes_dtype < CZ_F32 || P.planes_dtype > CZ_U8) { delete s; return serr(CZ_ERR_ARG, "cz_search_create: planes_dtype"); }
@@ -484,31 +490,32 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     const bool ml = s->M.slope > 0.0;                           // (never with gum, solve, stop, cache or a script: cz_search_set_moves_left)
     const bool draw = s->D.on != 0;                             // (never with ml or what ml is never with: cz_search_set_draw)
     const bool lcb = s->Z.on != 0;                              // (never with ml, draw or what they are never with: cz_search_set_lcb)
+    const bool sched = s->P.cpuct_factor > 0.0;                 // (beside every one of them: the SCHED instantiation of the same kernel)
     auto sim = [&](int mask, int cq) {
         if (lcb) {
-            if (hist) hipLaunchKernelGGL((k_sim_var<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
-            else hipLaunchKernelGGL((k_sim_var<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim_var<true, true> : k_sim_var<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((sched ? k_sim_var<false, true> : k_sim_var<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         } else if (draw) {
-            if (hist) hipLaunchKernelGGL((k_sim_draw<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
-            else hipLaunchKernelGGL((k_sim_draw<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim_draw<true, true> : k_sim_draw<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
+            else hipLaunchKernelGGL((sched ? k_sim_draw<false, true> : k_sim_draw<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->D);
         } else if (ml) {
-            if (hist) hipLaunchKernelGGL((k_sim_ml<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
-            else hipLaunchKernelGGL((k_sim_ml<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim_ml<true, true> : k_sim_ml<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
+            else hipLaunchKernelGGL((sched ? k_sim_ml<false, true> : k_sim_ml<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->M);
         } else if (stop) {
-            if (hist) hipLaunchKernelGGL((k_sim_stop<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
-            else hipLaunchKernelGGL((k_sim_stop<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim_stop<true, true> : k_sim_stop<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
+            else hipLaunchKernelGGL((sched ? k_sim_stop<false, true> : k_sim_stop<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->S);
         } else if (solve) {
-            if (hist) hipLaunchKernelGGL((k_sim_solve<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
-            else hipLaunchKernelGGL((k_sim_solve<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim_solve<true, true> : k_sim_solve<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((sched ? k_sim_solve<false, true> : k_sim_solve<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         } else if (cache) {         // (14 planes: cz_search_set_eval_cache refuses the history input)
-            if (gum) hipLaunchKernelGGL((k_sim_cached<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
-            else hipLaunchKernelGGL((k_sim_cached<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
+            if (gum) hipLaunchKernelGGL((sched ? k_sim_cached<true, true> : k_sim_cached<true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
+            else hipLaunchKernelGGL((sched ? k_sim_cached<false, true> : k_sim_cached<false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count, s->C);
         } else if (gum) {
-            if (hist) hipLaunchKernelGGL((k_sim<true, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
-            else hipLaunchKernelGGL((k_sim<false, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim<true, true, true> : k_sim<true, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((sched ? k_sim<false, true, true> : k_sim<false, true>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         } else {
-            if (hist) hipLaunchKernelGGL((k_sim<true, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
-            else hipLaunchKernelGGL((k_sim<false, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            if (hist) hipLaunchKernelGGL((sched ? k_sim<true, false, true> : k_sim<true, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
+            else hipLaunchKernelGGL((sched ? k_sim<false, false, true> : k_sim<false, false>), grid, block, 0, st, s->P, s->B, policy, value, planes, mask, cq, q_rows, q_count);
         }
     };
     // evaluation cache: the rows the BACKUP launch is about to attach go into the table first (its only writer)
@@ -578,6 +585,9 @@ int cz_search_policy_logits(cz_search* s, int on)
 {
     if (!s) return serr(CZ_ERR_ARG, "cz_search_policy_logits: null handle");
     const int mode = on ? 1 : 0;
+    if (!mode && s->P.inv_temp != 1.0f)
+        return serr(CZ_ERR_ARG, "cz_search_policy_logits: a policy temperature is set (cz_search_set_policy_temperature), it needs "
+                                "logit rows");
     if (mode != s->P.policy_logits && s->C.tab) {
         // the meaning of a row changes: what the evaluation cache holds was formed under the other one.  This entry has no
         // stream of its own, so the table is emptied between two device synchronisations.
@@ -1416,6 +1426,56 @@ int cz_gumbel_interior_pick(const int32_t* n, const double* w, const float* p, c
     hipLaunchKernelGGL(k_gumbel_interior_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, n, w, p, n_edges, v, rows,
                        c_visit, c_scale, out_pick, out_score);
     S_LAUNCH_CHECK("cz_gumbel_interior_pick");
+    return CZ_OK;
+}
+
+// ---- the schedule of c_puct and the policy temperature (include/czero.h) ---------------------------------------------------
+// Plain parameters of the kernels that are launched anyway: no entry in FEATURES, nothing excludes them.
+static bool cpuct_schedule_ok(double factor, double base) { return finite_nonneg(factor) && finite_nonneg(base) && base >= 1.0; }
+
+int cz_search_set_cpuct_schedule(cz_search* s, double factor, double base, void* stream)
+{
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_cpuct_schedule: null handle");
+    if (!cpuct_schedule_ok(factor, base))
+        return serr(CZ_ERR_ARG, "cz_search_set_cpuct_schedule: factor negative or not finite, or base below 1 or not finite");
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);   // launches in flight keep the schedule they started with
+    if (e != hipSuccess) return serr_hip("cz_search_set_cpuct_schedule", e);
+    s->P.cpuct_factor = factor;
+    s->P.cpuct_base = base;
+    return CZ_OK;
+}
+
+int cz_search_set_policy_temperature(cz_search* s, double T, void* stream)
+{
+    const char* const me = "cz_search_set_policy_temperature";
+    if (!s) return serr(CZ_ERR_ARG, "cz_search_set_policy_temperature: null handle");
+    if (!(T >= 0.1 && T <= 10.0)) return serr(CZ_ERR_ARG, "cz_search_set_policy_temperature: T outside [0.1, 10] or not finite");
+    const float inv_t = (float)(1.0 / T);
+    if (inv_t != 1.0f && !s->P.policy_logits)
+        return serr(CZ_ERR_ARG, "cz_search_set_policy_temperature: the policy rows are probabilities, a temperature needs logit rows "
+                                "(cz_search_policy_logits)");
+    hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return serr_hip(me, e);
+    if (inv_t == s->P.inv_temp) return CZ_OK;
+    s->P.inv_temp = inv_t;
+    // the stored priors were formed at the old temperature: the trees start over and the evaluation cache is emptied
+    int rc = cz_search_reset_trees(s, stream);
+    if (rc == CZ_OK) rc = cz_search_eval_cache_clear(s, stream);
+    if (rc != CZ_OK) return rc;
+    e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip(me, e);
+}
+
+int cz_debug_cpuct(const int32_t* sum_n, int rows, double c_puct, double factor, double base, double* out_c, float* out_c32,
+                   void* stream)
+{
+    if (!sum_n || !out_c || !out_c32 || rows < 0) return serr(CZ_ERR_ARG, "cz_debug_cpuct: null argument or rows < 0");
+    if (!finite_nonneg(c_puct) || !cpuct_schedule_ok(factor, base))
+        return serr(CZ_ERR_ARG, "cz_debug_cpuct: c_puct or factor negative or not finite, or base below 1 or not finite");
+    if (rows == 0) return CZ_OK;
+    hipLaunchKernelGGL(k_cpuct_rows, dim3(rows), dim3(64), 0, (hipStream_t)stream, sum_n, rows, c_puct, factor,
+                       base, out_c, out_c32);
+    S_LAUNCH_CHECK("cz_debug_cpuct");
     return CZ_OK;
 }
 

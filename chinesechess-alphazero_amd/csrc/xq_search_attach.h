@@ -16,15 +16,17 @@ namespace {
 // p_j / sum_legal p (player.py:272-283), in which the softmax's own denominator cancels -- so only the legal moves' logits
 // matter: p_j := exp(l_j - max over the node's moves).  (The engine's own queue then skips the normalising pass over all
 // 2086 columns: 546 MB of traffic per round for the 4 % of the entries that are read.)
-XQ_D void logits_to_weights(float& q0, float& q1, int nm)
+// inv_t: the policy temperature (cz_search_set_policy_temperature) as float32(1 / T), the softmax of l / T over the legal moves:
+// the difference to the maximum is scaled, one float32 product rounded on its own.  T = 1 is 1.0f, an exact product.
+XQ_D void logits_to_weights(float& q0, float& q1, int nm, float inv_t)
 {
     const int lane = lane_id();
     const bool h0 = lane < nm, h1 = lane + 64 < nm;
     float m = h0 ? q0 : -3.0e38f;
     if (h1 && q1 > m) m = q1;
     m = wave_max_f32(m);
-    q0 = h0 ? __expf(q0 - m) : 0.0f;
-    q1 = h1 ? __expf(q1 - m) : 0.0f;
+    q0 = h0 ? __expf((q0 - m) * inv_t) : 0.0f;
+    q1 = h1 ? __expf((q1 - m) * inv_t) : 0.0f;
 }
 
 // The priors of a node from its row's entries, lane j holding move j in p0 and move j + 64 in p1 (0 past the node's nm
@@ -33,9 +35,9 @@ XQ_D void logits_to_weights(float& q0, float& q1, int nm)
 // straight from the lanes' registers (a loop over an LDS copy paid an LDS round trip per term).  The one place the priors
 // are formed: the attach of an evaluated leaf and the evaluation cache's fill (k_cache_fill) both call it, so a cached
 // entry holds the attach's bits by construction.
-XQ_D float prior_norm(float& p0, float& p1, int nm, bool logits)
+XQ_D float prior_norm(float& p0, float& p1, int nm, bool logits, float inv_t)
 {
-    if (logits) logits_to_weights(p0, p1, nm);             // (raw logits: weights relative to the largest legal one)
+    if (logits) logits_to_weights(p0, p1, nm, inv_t);      // (raw logits: weights relative to the largest legal one)
     float all_p = 0.0f;
     if (nm > 0) {
         all_p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), 0));          // int 0 + float32
@@ -50,7 +52,7 @@ XQ_D float prior_norm(float& p0, float& p1, int nm, bool logits)
 // keep_v: the leaf's network value v goes into the node header as well (k_sim's keep_v: constant false outside the GUM
 // instantiations, so their text does not hold the store)
 XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float* __restrict__ prow, bool logits,
-                        bool keep_v, float v)
+                        float inv_t, bool keep_v, float v)
 {
     const int lane = lane_id();
     char* base = rec_ptr(gv, (uint32_t)node);
@@ -64,7 +66,7 @@ XQ_D void attach_policy(const GameView& gv, SearchLDS& L, int node, const float*
     float q0 = 0.0f, q1 = 0.0f;
     if (lane < nm) q0 = prow[row_col(pm[lane], mir)];
     if (lane + 64 < nm) q1 = prow[row_col(pm[lane + 64], mir)];
-    const float all_p = prior_norm(q0, q1, nm, logits);
+    const float all_p = prior_norm(q0, q1, nm, logits, inv_t);
     if (lane < nm) pp[lane] = q0 / all_p;
     if (lane + 64 < nm) pp[lane + 64] = q1 / all_p;
     // p[j] is written and later read (select_edge) by the same lane, the header by lane 0: no global fence
@@ -112,7 +114,7 @@ XQ_D void leaf_pre_b(LeafPre& lp, uint32_t meta, const float* __restrict__ prow)
 // keep_v: as attach_policy's; v is float(v) of the slot's float32, so the cast back is exact.
 template <typename Next>
 XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS& L, int node, uint32_t meta, int depth,
-                            const LeafPre& lp, double v, bool logits, bool keep_v, Next&& next)
+                            const LeafPre& lp, double v, bool logits, float inv_t, bool keep_v, Next&& next)
 {
     const int lane = lane_id();
     char* base = rec_ptr(gv, (uint32_t)node);
@@ -123,7 +125,7 @@ XQ_D void attach_and_backup(const SearchParams& P, const GameView& gv, SearchLDS
     EdgeStat* ep = nullptr;
     if (lane < depth) { ep = edge_ptr(gv, (uint32_t)lp.e); cur = *ep; }
     next();
-    const float all_p = prior_norm(p0, p1, nm, logits);    // prior spreading (select_action_q_and_u, player.py:272-284)
+    const float all_p = prior_norm(p0, p1, nm, logits, inv_t);   // prior spreading (select_action_q_and_u, player.py:272-284)
     if (lane < nm) pp[lane] = p0 / all_p;
     if (lane + 64 < nm) pp[lane + 64] = p1 / all_p;
     if (lane == 0) store_meta(base, meta & ~(uint32_t)(NODE_WAITING | NODE_MIRRORED));

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(64) void k_root_records(SearchParams P, SearchBuffe
     int m[2] = {E.n[0], E.n[1]};
     const int S = (gumbel || P.gumbel_m > 0) ? gumbel_targets<FULL>(E.nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale,
                                                                     FULL ? root_net_value(B, gv) : 0.0f)
-                                             : prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k);
+                                             : prune_targets(E.nm, E.lab, m, E.w, E.p, P.c_puct, P.cpuct_factor, P.cpuct_base, P.forced_k);
     if (n) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) n[(size_t)g * MAXMOVES + lane + 64 * h] = lane + 64 * h < E.nm ? m[h] : 0;
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(64) void k_row_records(const uint16_t* __restrict__
         return;
     }
     if (out_n) {
-        const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, c_puct, k);
+        const int S = prune_targets(E.nm, E.lab, m, E.w, E.p, c_puct, 0.0, 1.0, k);
 #pragma unroll
         for (int h = 0; h < 2; ++h) out_n[(size_t)r * MAXMOVES + lane + 64 * h] = lane + 64 * h < E.nm ? m[h] : 0;
         if (lane == 0) out_raw_total[r] = S;
@@ -464,6 +464,20 @@ __global__ __launch_bounds__(64) void k_gumbel_interior_rows(const int32_t* __re
 #pragma unroll
     for (int h = 0; h < 2; ++h) out_score[(size_t)r * MAXMOVES + lane + 64 * h] = score[h];
     if (lane == 0) out_pick[r] = pick;
+}
+
+// cz_debug_cpuct: cpuct_at, the schedule of c_puct, on a list of sums, one wavefront per sum as the selection calls it; out_c32
+// the float32 the selection below the root multiplies the prior with
+__global__ __launch_bounds__(64) void k_cpuct_rows(const int32_t* __restrict__ sum_n, int rows, double c_puct, double factor,
+                                                  double base, double* __restrict__ out_c, float* __restrict__ out_c32)
+{
+    const int r = blockIdx.x;
+    if (r >= rows) return;
+    const double c = cpuct_at(c_puct, factor, base, sum_n[r]);
+    if (lane_id() == 0) {
+        out_c[r] = c;
+        out_c32[r] = (float)c;
+    }
 }
 
 // Principal variation (print_depth_info, player.py:408-433): from the root follow the most-visited edge -- `>=` keeps

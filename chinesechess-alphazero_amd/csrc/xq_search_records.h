@@ -171,7 +171,10 @@ XQ_D int gumbel_targets(int nm, const uint16_t lab[2], int m[2], const int n[2],
 // Policy target pruning (include/czero.h, cz_search_set_forced_playouts): one wavefront, edge j = lane + 64 h.  lab[h]
 // carries VISIT_BANNED, n / w are the raw statistics, p the float32 prior WITHOUT noise; the pruned counts replace n[].
 // All arithmetic in float64, in the order czero.h writes it.  Returns S, the raw total of the non-banned edges.
-XQ_D int prune_targets(int nm, const uint16_t lab[2], int n[2], const double w[2], const float p[2], double c_puct, double k)
+// c_puct, cf, cb: the exploration constant is cpuct_at(c_puct, cf, cb, S), the schedule's value at the raw total (cf = 0:
+// c_puct itself).
+XQ_D int prune_targets(int nm, const uint16_t lab[2], int n[2], const double w[2], const float p[2], double c_puct, double cf,
+                       double cb, double k)
 {
     const int lane = lane_id();
     long long s = 0;
@@ -198,6 +201,7 @@ XQ_D int prune_targets(int nm, const uint16_t lab[2], int n[2], const double w[2
     if (S <= 0) return 0;                   // nothing searched (or everything banned): the counts stay
     const double Sd = (double)S;
     const double sq = __dsqrt_rn(Sd);
+    c_puct = cpuct_at(c_puct, cf, cb, S);
     const double e_star = bw / (double)bn + ((c_puct * (double)bp) * sq) / (double)(1 + bn);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -330,7 +334,7 @@ XQ_D void emit_visits(const SearchParams& P, const SearchBuffers& B, const GameV
     // (a Gumbel ply: the counts are the policy target pi' scaled to 65536 -- the halving counts are no target)
     const int raw_total = gumbel ? gumbel_targets<FULL>(nm, E.lab, m, E.n, E.w, E.p, P.gumbel_visit, P.gumbel_scale,
                                                         FULL ? root_net_value(B, gv) : 0.0f)
-                                 : (prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.forced_k) : 0);
+                                 : (prune ? prune_targets(nm, E.lab, m, E.w, E.p, P.c_puct, P.cpuct_factor, P.cpuct_base, P.forced_k) : 0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int j = lane + 64 * h;

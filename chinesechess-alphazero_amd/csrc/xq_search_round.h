@@ -45,8 +45,10 @@ constexpr int SIM_BACKUP = 1, SIM_SELECT = 2;
 // VAR: the lower-confidence-bound move choice (cz_search_set_lcb) is on; likewise.  The body of k_sim_var too.  Its attach takes
 // the leaf's squared value up the path (backup_v) before the value; leaf by leaf without the prefetch, as ML's.  The selection is
 // the plain one and no state of the option is read here: z and the ratio matter to the move choice alone.
+// SCHED: the schedule of c_puct (cz_search_set_cpuct_schedule) is on; likewise.  Every kernel below has the instantiation: the
+// schedule is a plain parameter that runs beside each of the options above, and only the selection differs.
 template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool STOP = false, bool ML = false, bool DRAW = false,
-          bool VAR = false>
+          bool VAR = false, bool SCHED = false>
 XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, const float* __restrict__ policy,
                    const float* __restrict__ value, void* planes, int mask, int compact,
                    int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, const EvalCache& C,
@@ -150,20 +152,20 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             LeafPre nx{0, 0, 0, 0.0f, 0.0f};
             if constexpr (ML) {
                 const int k = __builtin_amdgcn_readlane(my_k, i);
-                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, P.inv_temp, false, 0.0f);
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), k);
                 load_path(P, gv, L, i, depth);
                 backup_m(gv, L, depth, k);
                 backup(P, gv, L, depth, v);
             } else if constexpr (DRAW) {
                 const int dq = __builtin_amdgcn_readlane(my_k, i);
-                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, P.inv_temp, false, 0.0f);
                 if (lane_id() == 0) store_ml_k(rec_ptr(gv, (uint32_t)node), dq);      // (word 3, as the moves-left k)
                 load_path(P, gv, L, i, depth);
                 backup_d(gv, L, depth, dq);
                 backup(P, gv, L, depth, v);
             } else if constexpr (VAR) {
-                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, false, 0.0f);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, P.inv_temp, false, 0.0f);
                 load_path(P, gv, L, i, depth);
                 backup_v(gv, L, depth, v);
                 backup(P, gv, L, depth, v);
@@ -174,11 +176,11 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
             } else if (depth <= 64) {
                 attach_and_backup(P, gv, L, node, (uint32_t)__builtin_amdgcn_readlane((int)my_meta, i), depth, lp, v,
-                                  P.policy_logits != 0, keep_v, [&]() {
+                                  P.policy_logits != 0, P.inv_temp, keep_v, [&]() {
                                       if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
                                   });
             } else {
-                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, keep_v, (float)v);
+                attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, P.inv_temp, keep_v, (float)v);
                 load_path(P, gv, L, i, depth);
                 backup(P, gv, L, depth, v);
                 if (i_next >= 0) { pre_a(nx, i_next); pre_b(nx, i_next); }
@@ -209,7 +211,7 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
                 const int row = uni(B.s_qrow[slot]);
                 if (row >= 0) slot = (size_t)row;
             }
-            attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, keep_v, value[slot]);
+            attach_policy(gv, L, node, policy + slot * NLABELS, P.policy_logits != 0, P.inv_temp, keep_v, value[slot]);
             load_path(P, gv, L, i, depth);
             if constexpr (ML) {
                 const int k = uni(ml_quanta(M.x[slot]));
@@ -282,8 +284,8 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
             if (lane_id() == 0) B.g_tasks_left[g] = tasks - new_n;
             continue;
         } else break;
-        run_sim<HIST, GUM, CACHE, SOLVE, ML, DRAW, VAR>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active, ar,
-                                                        fresh, df, C, (mask & SIM_SELECT) != 0, M, D);
+        run_sim<HIST, GUM, CACHE, SOLVE, ML, DRAW, VAR, SCHED>(P, B, gv, L, io, rc, uni(B.g_root[g]), sim, node, depth, &active,
+                                                               ar, fresh, df, C, (mask & SIM_SELECT) != 0, M, D);
     }
     if (lane_id() == 0) { B.g_active[g] = active; B.g_node_count[g] = ar.ncount; B.g_heap_top[g] = ar.top; }
     if ((mask & SIM_SELECT) && q_rows) {
@@ -313,79 +315,79 @@ XQ_D void sim_body(SearchLDS& L, const SearchParams& P, const SearchBuffers& B, 
     counters_flush(gv);
 }
 
-template <bool HIST, bool GUM>
+template <bool HIST, bool GUM, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                            const float* __restrict__ value, void* planes, int mask, int compact,
                                            int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, GUM, false>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
+    sim_body<HIST, GUM, false, false, false, false, false, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
 }
 
 // k_sim with the evaluation cache on (14 input planes only: cz_search_set_eval_cache refuses the history input)
-template <bool GUM>
+template <bool GUM, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_cached(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                                   const float* __restrict__ value, void* planes, int mask, int compact,
                                                   int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, EvalCache C)
 {
     __shared__ SearchLDS L;
-    sim_body<false, GUM, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, C);
+    sim_body<false, GUM, true, false, false, false, false, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, C);
 }
 
 // k_sim with the MCTS solver on (cz_search_set_solver refuses the Gumbel search, forced playouts and the evaluation cache)
-template <bool HIST>
+template <bool HIST, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_solve(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                                  const float* __restrict__ value, void* planes, int mask, int compact,
                                                  int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
+    sim_body<HIST, false, false, true, false, false, false, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{});
 }
 
 // k_sim with a stop rule on (cz_search_set_kld_gain and cz_search_set_smart_pruning refuse the Gumbel search, the solver and the
 // evaluation cache)
-template <bool HIST>
+template <bool HIST, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_stop(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                                 const float* __restrict__ value, void* planes, int mask, int compact,
                                                 int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, StopState S)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{}, S);
+    sim_body<HIST, false, false, false, true, false, false, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{}, S);
 }
 
 // k_sim with the moves-left utility on (cz_search_set_moves_left refuses the Gumbel search, the solver, the stop rules, the
 // evaluation cache and a script)
-template <bool HIST>
+template <bool HIST, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_ml(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                               const float* __restrict__ value, void* planes, int mask, int compact,
                                               int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, MovesLeftState M)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{},
+    sim_body<HIST, false, false, false, false, true, false, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count, EvalCache{},
                                                      StopState{}, M);
 }
 
 // k_sim with the draw average on (cz_search_set_draw refuses the Gumbel search, the solver, the stop rules, the evaluation
 // cache, a script and the moves-left utility)
-template <bool HIST>
+template <bool HIST, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_draw(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                                 const float* __restrict__ value, void* planes, int mask, int compact,
                                                 int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count, DrawState D)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, false, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count,
+    sim_body<HIST, false, false, false, false, false, true, false, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows, q_count,
                                                             EvalCache{}, StopState{}, MovesLeftState{}, D);
 }
 
 // k_sim with the lower-confidence-bound move choice on (cz_search_set_lcb refuses the Gumbel search, the solver, the stop rules,
 // the evaluation cache, a script, the moves-left utility and the draw average)
-template <bool HIST>
+template <bool HIST, bool SCHED = false>
 __global__ __launch_bounds__(64, 4) void k_sim_var(SearchParams P, SearchBuffers B, const float* __restrict__ policy,
                                                const float* __restrict__ value, void* planes, int mask, int compact,
                                                int32_t* __restrict__ q_rows, int32_t* __restrict__ q_count)
 {
     __shared__ SearchLDS L;
-    sim_body<HIST, false, false, false, false, false, false, true>(L, P, B, policy, value, planes, mask, compact, q_rows,
+    sim_body<HIST, false, false, false, false, false, false, true, SCHED>(L, P, B, policy, value, planes, mask, compact, q_rows,
                                                                    q_count, EvalCache{});
 }
 
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(64) void k_cache_fill(SearchParams P, SearchBuffers
     if (lane + 64 < nm) lp.m1 = pm[lane + 64];
     leaf_pre_b(lp, meta, policy + (size_t)row * NLABELS);
     float p0 = lp.p0, p1 = lp.p1;
-    const float all_p = prior_norm(p0, p1, nm, P.policy_logits != 0);
+    const float all_p = prior_norm(p0, p1, nm, P.policy_logits != 0, P.inv_temp);
     if (lane < KEY_WORDS) e->key[lane] = kw;
     if (lane < nm) e->p[lane] = p0 / all_p;
     if (lane + 64 < nm) e->p[lane + 64] = p1 / all_p;

@@ -38,7 +38,24 @@ XQ_D double root_prior(const SearchParams& P, const RootCtx& rc, float p, int j)
     if (rc.noise) p_ = p_ + P.noise_eps * rc.noise[(size_t)rc.sim * MAXMOVES + j];   // player.py:304
     return p_;
 }
-XQ_D double root_u(const SearchParams& P, double p_, double xx, int n) { return P.c_puct * p_ * xx / (double)(1 + n); }
+// c: the node's exploration constant, cpuct_of(P, sum_n)
+XQ_D double root_u(double c, double p_, double xx, int n) { return c * p_ * xx / (double)(1 + n); }
+
+// ---- the schedule of c_puct (include/czero.h, cz_search_set_cpuct_schedule) ---------------------------------------------
+// c(sum_n) = c_puct + F * log((1 + sum_n + B) / B): float64, every operation rounded on its own, in the order written.  The
+// one statement of it: select_edge, select_solve, the callers of prune_targets and cz_debug_cpuct read it.  F = 0 (off) is
+// c_puct itself, bit for bit, and its float32 is c_puct_f32.  All 64 lanes call it with the same sum_n; the result is handed
+// back in scalar registers, where c_puct itself lives.
+// In k_sim the call stands in the SCHED instantiations alone (select_edge, select_solve), launched while F > 0: inlined behind
+// a wave-uniform branch, the logarithm -- the library's, and a 12-term series of our own alike -- raised the scratch of
+// every k_sim instantiation although the branch was never taken (k_sim<false, false> 44 -> 96 .. 136 bytes; EXPERIMENTS.md,
+// "c_puct schedule").
+XQ_D double cpuct_at(double c_puct, double factor, double base, int sum_n)
+{
+    if (!(factor > 0.0)) return c_puct;
+    return unid(c_puct + factor * log(((1.0 + (double)uni(sum_n)) + base) / base));
+}
+XQ_D double cpuct_of(const SearchParams& P, int sum_n) { return cpuct_at(P.c_puct, P.cpuct_factor, P.cpuct_base, sum_n); }
 
 // ---- Gumbel root search with sequential halving (include/czero.h, cz_search_set_gumbel) -------------------------------
 // seq(m, n)[t]: how many selections the edge taken by the t-th root selection of the ply must already have.  A phase of
@@ -205,7 +222,9 @@ XQ_D int select_gumbel(int gumbel_m, double c_visit, double c_scale, int32_t* st
 // lane loads its edges' M records, two integer wave sums give the parent's mean, and the score is (q + u) + u_m.
 // DRAW: the k_sim instantiation that is launched while the draw average is on (cz_search_set_draw); likewise.  Every lane
 // loads its edges' D records, and the score is (q + u) + sigma * dbar; sigma: draw_sigma of the node's depth.
-template <bool GUM, bool ML = false, bool DRAW = false>
+// SCHED: the k_sim instantiation that is launched while the schedule of c_puct is on (cz_search_set_cpuct_schedule); likewise.
+// The others read the constants P.c_puct and P.c_puct_f32 as they always did.
+template <bool GUM, bool ML = false, bool DRAW = false, bool SCHED = false>
 XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, char* base, const EdgeStat* sb, int sum_n,
                         int nm, const RootCtx& rc, uint32_t net_value, const MovesLeftState& M = MovesLeftState{},
                         double sigma = 0.0)
@@ -241,6 +260,9 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
     }
     const int lane = lane_id();
     const double xx = __dsqrt_rn((double)(sum_n + 1));
+    double c = P.c_puct;                                    // the node's exploration constant and its float32
+    float c32 = P.c_puct_f32;
+    if constexpr (SCHED) { c = cpuct_of(P, sum_n); c32 = (float)c; }
     const float* pp = node_p(base);
     const uint16_t* pm = node_mv(base, nm);
     int n0 = 0, child0 = CHILD_UNKNOWN, mv0 = 0;           // this lane's edge of the first half
@@ -291,9 +313,9 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
             double u;
             if (rc.is_root) {
                 if (rc.n_no_act) valid = !root_banned(rc, mv);
-                u = root_u(P, root_prior(P, rc, p, j), xx, n);
+                u = root_u(c, root_prior(P, rc, p, j), xx, n);
             } else {
-                const float a = P.c_puct_f32 * p;
+                const float a = c32 * p;
                 u = (double)a * xx / (double)(1 + n);
             }
             if (valid) {
@@ -320,7 +342,7 @@ XQ_D Picked select_edge(const SearchParams& P, const SearchBuffers& B, int g, ch
             if (n <= 0 || root_banned(rc, pm[j])) continue;
             const double p_ = root_prior(P, rc, pp[j], j);
             if (!((double)n * (double)n < P.forced_k * p_ * (double)sum_n)) continue;
-            if (!(es.w / (double)n + root_u(P, p_, xx, n) >= -99999999.0)) continue;
+            if (!(es.w / (double)n + root_u(c, p_, xx, n) >= -99999999.0)) continue;
             best_s = __builtin_inf();
             best_j = j;                                         // h = 1 has the larger index: wins ties
         }

@@ -286,7 +286,9 @@ XQ_D void backup_end(const SearchParams& P, const GameView& gv, const SearchLDS&
 // selection reads them with the sign of the node's depth, a backup made here takes d up with dq = 0; likewise.
 // VAR: the lower-confidence-bound move choice is on (cz_search_set_lcb): a statistics block carries its V records in the same
 // place, the selection is the plain one, a backup made here takes its squared value up (backup_v); likewise.
-template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool ML = false, bool DRAW = false, bool VAR = false>
+// SCHED: the schedule of c_puct is on (cz_search_set_cpuct_schedule): the selection computes c(sum_n); likewise.
+template <bool HIST, bool GUM, bool CACHE, bool SOLVE = false, bool ML = false, bool DRAW = false, bool VAR = false,
+          bool SCHED = false>
 XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView& gv, SearchLDS& L,
                   const RoundIO& io, const RootCtx& rc0, int root, int sim, int node, int depth, int* active,
                   Arena& ar, bool fresh, Deferred& df, const EvalCache& C, bool probe,
@@ -393,9 +395,9 @@ XQ_D void run_sim(const SearchParams& P, const SearchBuffers& B, const GameView&
         rc.sim = sim;
         Picked pk;
         if constexpr (SOLVE) {                                      // (have = false: the edge is reloaded below)
-            pk = Picked{select_solve(P, gv, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc), false, 0, CHILD_UNKNOWN, 0, 0.0};
+            pk = Picked{select_solve<SCHED>(P, gv, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc), false, 0, CHILD_UNKNOWN, 0, 0.0};
         } else {
-            pk = select_edge<GUM, ML, DRAW>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc, hdr.val, M,
+            pk = select_edge<GUM, ML, DRAW, SCHED>(P, B, g, base, fresh_stat ? nullptr : sb, hdr.sum_n, nm, rc, hdr.val, M,
                                             DRAW ? draw_sigma(D, depth) : 0.0);
         }
         if (pk.j < 0) {                                             // "Best action is None": cannot happen

@@ -94,11 +94,15 @@ XQ_D bool solve_root_decided(const SearchBuffers& B, const GameView& gv, int* ed
 //      the non-banned edges that are not losing;
 //   3. every non-banned edge losing: over all non-banned edges.
 // Edge j is loaded by the lane that owns it (j & 63), both halves held at once: the marks come with the 16-byte load.
+template <bool SCHED = false>
 XQ_D int select_solve(const SearchParams& P, const GameView& gv, char* base, const EdgeStat* sb, int sum_n, int nm,
                       const RootCtx& rc)
 {
     const int lane = lane_id();
     const double xx = __dsqrt_rn((double)(sum_n + 1));
+    double c = P.c_puct;
+    float c32 = P.c_puct_f32;
+    if constexpr (SCHED) { c = cpuct_of(P, sum_n); c32 = (float)c; }     // (the SCHED instantiations of k_sim_solve: select_edge)
     const float* pp = node_p(base);
     const uint16_t* pm = node_mv(base, nm);
     bool nb[2] = {false, false}, live[2] = {false, false}, win[2] = {false, false}, sure[2] = {false, false};
@@ -119,9 +123,9 @@ XQ_D int select_solve(const SearchParams& P, const GameView& gv, char* base, con
         double u;
         if (rc.is_root) {
             if (rc.n_no_act) valid = !root_banned(rc, mv);
-            u = root_u(P, root_prior(P, rc, p, j), xx, n);
+            u = root_u(c, root_prior(P, rc, p, j), xx, n);
         } else {
-            const float a = P.c_puct_f32 * p;
+            const float a = c32 * p;
             u = (double)a * xx / (double)(1 + n);
         }
         if (!valid) continue;

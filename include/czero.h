@@ -962,6 +962,41 @@ int cz_search_root_lcb(cz_search* s, double* lcb, int32_t* pick, void* stream);
  * edge); either may be NULL; all DEVICE. */
 int cz_lcb_pick(const uint16_t* labels, const int32_t* n, const double* w, const double* s2, const int32_t* vn,
                 const uint8_t* n_edges, int rows, double z, double min_ratio, double* out_lcb, int32_t* out_pick, void* stream);
+/* ---- the schedule of c_puct and the policy temperature (both off by default; the reference has neither) -------------------
+ * run.py self / eval / reanalyse --cpuct-factor F --cpuct-base B --policy-temp T; the UCI options CPuctFactor, CPuctBase,
+ * PolicyTemperature.  Two plain parameters of the kernels that are launched anyway: neither has a kernel instantiation or a
+ * record of its own, so both run beside every other option and a script, and no setter refuses them.
+ *
+ * THE SCHEDULE (AlphaZero's C(s); lc0's CPuctFactor / CPuctBase).  The exploration constant of a selection is
+ *   c(sum_n) = c_puct + F * log((1 + sum_n + B) / B)            float64, every operation rounded on its own, in this order
+ * sum_n being the node's own count as the selection reads it (the value whose sum_n + 1 is under the square root).  At the
+ * root u = c * p_ * xx / (1 + n) in that order; below it a = (float)c * p is the float32 product and u = (double)a * xx /
+ * (1 + n).  The solver's selection reads the same c.  Policy target pruning (cz_search_root_targets, a PRUNED visit entry)
+ * takes c(S), S the raw total of the non-banned edges; cz_policy_target_prune keeps its c_puct argument, the caller passes
+ * what it means.  The Gumbel root rule has no c_puct; below the root plain Gumbel selects by PUCT and follows the schedule,
+ * the full Gumbel search does not read it.  F = 0 (off): c is c_puct bit for bit and (float)c its float32, the simulation
+ * kernels launched are the ones that read the constant (with F > 0: their SCHED instantiations), and every search, record and
+ * counter is what it was.
+ * cz_search_set_cpuct_schedule: factor finite and >= 0, base finite and >= 1, else CZ_ERR_ARG.  Synchronises the stream;
+ * resets nothing (the trees hold no c).
+ *
+ * THE TEMPERATURE (lc0's PolicyTemperature).  With logit rows (cz_search_policy_logits) the priors of a node are the softmax of
+ * l / T over its legal moves: w_j = exp((l_j - m) * inv_T), m the greatest legal logit, inv_T = (float)(1.0 / T) computed in
+ * float64 and rounded once; float32 throughout, the product rounded on its own; then the usual float32 sum and quotients.  It
+ * is applied where the priors are formed -- the attach of a leaf and the evaluation cache's fill -- so PUCT, Gumbel's log p,
+ * the surprise record, the forced-playout threshold and the cache all see it.  T = 1 (off): inv_T = 1.0f, an exact product,
+ * today's bits.
+ * cz_search_set_policy_temperature: 0.1 <= T <= 10, else CZ_ERR_ARG; T != 1 with probability rows is CZ_ERR_ARG, and so is
+ * cz_search_policy_logits(h, 0) while T != 1.  A change of T makes the stored priors stale: the call synchronises the stream,
+ * resets the trees as cz_search_reset_trees does and empties the evaluation cache (cz_search_eval_cache_clear).  Call it
+ * between plies, never with evaluations outstanding. */
+int cz_search_set_cpuct_schedule(cz_search* s, double factor, double base, void* stream);
+int cz_search_set_policy_temperature(cz_search* s, double T, void* stream);
+/* The schedule's device function on a list of sums, one wavefront per sum as the selection calls it: out_c[i] = c(sum_n[i]) and
+ * out_c32[i] = (float)out_c[i], the factor of the float32 product below the root; sum_n [rows] int32, all DEVICE.  c_puct and
+ * factor finite and >= 0, base finite and >= 1, no NULL pointer, rows >= 0 (0: nothing is launched). */
+int cz_debug_cpuct(const int32_t* sum_n, int rows, double c_puct, double factor, double base, double* out_c, float* out_c32,
+                   void* stream);
 /* ---- early stop of a settled ply (both rules off by default; the reference has no such option) ---------------------------
  * run.py self --kld-gain G [--kld-interval I]; run.py eval --smart-pruning, the UCI option SmartPruning.  Two rules end a
  * ply's search before its budget is spent.  With both off no kernel output, record or counter differs by a bit, and the
