@@ -130,6 +130,12 @@ def _declare(L):
         L.cz_policy_wdl_loss.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, C.c_float,
                                          C.c_float, vp, vp, vp, vp, vp, vp]
         L.cz_policy_wdl_loss.restype = i32
+    if hasattr(L, "cz_policy_value_loss_l"):
+        L.cz_policy_value_loss_l.argtypes = L.cz_policy_value_loss_w.argtypes[:-1] + [vp, vp, vp, vp, vp]
+        L.cz_policy_value_loss_l.restype = i32
+    if hasattr(L, "cz_policy_wdl_loss_l"):
+        L.cz_policy_wdl_loss_l.argtypes = L.cz_policy_wdl_loss.argtypes[:-1] + [vp, vp, vp, vp, vp]
+        L.cz_policy_wdl_loss_l.restype = i32
     if hasattr(L, "cz_moves_left_loss"):
         L.cz_moves_left_loss.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp]
         L.cz_moves_left_loss.restype = i32
@@ -290,8 +296,18 @@ def gather_planes(boards, prev, idx, depth=14, out=None, mirror=None):
     return out
 
 
+def _mask_outputs(b, dev, off_mask, mask_diag):
+    """The optional per-row outputs of the masked loss entry points: (off_mask int32 [B] or None, illegal_mass and
+    illegal_margin float32 [B] or None, None)."""
+    import torch
+    om = torch.empty((b,), dtype=torch.int32, device=dev) if off_mask else None
+    im = torch.empty((b,), dtype=torch.float32, device=dev) if mask_diag else None
+    ig = torch.empty((b,), dtype=torch.float32, device=dev) if mask_diag else None
+    return om, im, ig
+
+
 def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0,
-                      mirror=None, q=None, q_ratio=0.0, row_w=None):
+                      mirror=None, q=None, q_ratio=0.0, row_w=None, boards=None, off_mask=False, mask_diag=False):
     """Per-row policy loss, squared value error and the gradients of w_p mean(policy loss) + w_v mean(sq. error) with
     respect to the logits [B, 2086] and the value [B] (cz_policy_value_loss; mode 0 played one-hot, 1 visit counts).
     logits may have a leading dimension > 2086 (a row-strided view).  Visit arrays with no entries (or None) leave every
@@ -300,7 +316,12 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
     no search value) with q_ratio L: the value target is z + L (q - z) (cz_policy_value_loss_q, mirror flags or none);
     q None calls the entry points above.  row_w: float32 [n_pos] on the device, the training weight of every window
     position (cz_policy_value_loss_w, with or without mirror flags and q): it scales the row's gradients, pl and se stay
-    the unweighted per-row values; None calls the entry points above."""
+    the unweighted per-row values; None calls the entry points above.
+    boards: int8 [n_pos, 90] on the device, the window's boards: the softmax, the loss and the gradient run over each row's
+    legal moves and its target's support (cz_policy_value_loss_l, with or without mirror flags, q and row_w); None calls the
+    entry points above.  With boards, off_mask=True appends off_mask (int32 [B]: a row's target labels outside its legal
+    moves, 0 for a valid record) to the result, and mask_diag=True appends illegal_mass and illegal_margin (float32 [B]), which
+    the kernel computes only then."""
     import torch
     require_gpu()
     assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
@@ -310,6 +331,23 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
     se = torch.empty((b,), dtype=torch.float32, device=dev)
     gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
     gv = torch.empty((b,), dtype=torch.float32, device=dev)
+    if boards is None and (off_mask or mask_diag):
+        raise ValueError("off_mask / mask_diag are outputs of the masked loss: pass boards")
+    if boards is not None:
+        assert boards.shape == (played.shape[0], NSQ), (tuple(boards.shape), tuple(played.shape))
+        assert (row_w is None or row_w.shape == z.shape) and (q is None or q.shape == z.shape)
+        om, im, ig = _mask_outputs(b, dev, off_mask, mask_diag)
+        check(lib().cz_policy_value_loss_l(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
+                                           _dev(idx, torch.int32), None if mirror is None else _flags(mirror, b), b,
+                                           played.shape[0], _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16),
+                                           _opt(vis_count, torch.int32), 0 if vis_label is None else vis_label.shape[0],
+                                           _dev(played, torch.uint16), _dev(z, torch.float32), _opt(q, torch.float32),
+                                           float(q_ratio) if q is not None else 0.0, _opt(row_w, torch.float32), int(mode),
+                                           float(w_p), float(w_v), _dev(pl, torch.float32), _dev(se, torch.float32),
+                                           _dev(gl, torch.float32), _dev(gv, torch.float32), _dev(boards, torch.int8),
+                                           _opt(om, torch.int32), _opt(im, torch.float32), _opt(ig, torch.float32), _stream()),
+              "cz_policy_value_loss_l")
+        return (pl, se, gl, gv) + ((om,) if off_mask else ()) + ((im, ig) if mask_diag else ())
     if row_w is not None:
         assert row_w.shape == z.shape and (q is None or q.shape == z.shape), (tuple(row_w.shape), tuple(z.shape))
         check(lib().cz_policy_value_loss_w(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(v, torch.float32),
@@ -353,12 +391,13 @@ def policy_value_loss(logits, v, idx, played, z, row_ptr=None, vis_label=None, v
 
 
 def policy_wdl_loss(logits, vlogits, idx, played, z, row_ptr=None, vis_label=None, vis_count=None, mode=0, w_p=1.0, w_v=1.0,
-                    mirror=None, row_w=None):
+                    mirror=None, row_w=None, boards=None, off_mask=False, mask_diag=False):
     """policy_value_loss for a network with a win / draw / loss value head (cz_policy_wdl_loss): vlogits [B, 3] float32, the
     value head's logits in the order (win, draw, loss).  Returns (pl, ce, se, gl, gv): the per-row policy loss, the value
     cross-entropy against the class of z (win z > 0, draw z == 0, loss z < 0), the squared error of p_W - p_L against z,
     and the gradients of w_p mean(pl) + w_v mean(ce) with respect to the logits [B, 2086] and the value logits [B, 3].
-    mirror / row_w / the visit arrays as in policy_value_loss; there is no q: a scalar does not determine a distribution."""
+    mirror / row_w / the visit arrays as in policy_value_loss; there is no q: a scalar does not determine a distribution.
+    boards, off_mask, mask_diag: as in policy_value_loss (cz_policy_wdl_loss_l); the further outputs follow gv."""
     import torch
     require_gpu()
     assert logits.dtype == torch.float32 and logits.is_cuda and logits.dim() == 2 and logits.shape[1] == NLABELS \
@@ -371,6 +410,21 @@ def policy_wdl_loss(logits, vlogits, idx, played, z, row_ptr=None, vis_label=Non
     se = torch.empty((b,), dtype=torch.float32, device=dev)
     gl = torch.empty((b, NLABELS), dtype=torch.float32, device=dev)
     gv = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    if boards is None and (off_mask or mask_diag):
+        raise ValueError("off_mask / mask_diag are outputs of the masked loss: pass boards")
+    if boards is not None:
+        assert boards.shape == (played.shape[0], NSQ), (tuple(boards.shape), tuple(played.shape))
+        om, im, ig = _mask_outputs(b, dev, off_mask, mask_diag)
+        check(lib().cz_policy_wdl_loss_l(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(vlogits, torch.float32),
+                                         _dev(idx, torch.int32), None if mirror is None else _flags(mirror, b), b,
+                                         played.shape[0], _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16),
+                                         _opt(vis_count, torch.int32), 0 if vis_label is None else vis_label.shape[0],
+                                         _dev(played, torch.uint16), _dev(z, torch.float32), _opt(row_w, torch.float32),
+                                         int(mode), float(w_p), float(w_v), _dev(pl, torch.float32), _dev(ce, torch.float32),
+                                         _dev(se, torch.float32), _dev(gl, torch.float32), _dev(gv, torch.float32),
+                                         _dev(boards, torch.int8), _opt(om, torch.int32), _opt(im, torch.float32),
+                                         _opt(ig, torch.float32), _stream()), "cz_policy_wdl_loss_l")
+        return (pl, ce, se, gl, gv) + ((om,) if off_mask else ()) + ((im, ig) if mask_diag else ())
     check(lib().cz_policy_wdl_loss(C.c_void_p(logits.data_ptr()), logits.stride(0), _dev(vlogits, torch.float32),
                                    _dev(idx, torch.int32), None if mirror is None else _flags(mirror, b), b, played.shape[0],
                                    _opt(row_ptr, torch.int32), _opt(vis_label, torch.uint16), _opt(vis_count, torch.int32),

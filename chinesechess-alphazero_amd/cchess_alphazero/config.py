@@ -41,7 +41,11 @@ class PlayDataConfig(_Section):
 
 
 class TrainerConfig(_Section):
-    pass
+    """The reference's trainer values, and ``policy_mask`` (run.py opt --policy-mask): ``none`` = the reference's softmax
+    over all labels, ``legal`` = over each position's legal moves."""
+
+    def __init__(self, **values):
+        super().__init__(**dict(dict(policy_mask="none"), **values))
 
 
 class ModelConfig(_Section):

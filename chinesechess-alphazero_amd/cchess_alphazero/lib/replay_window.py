@@ -297,7 +297,7 @@ class ReplayWindow:
         return _native.gather_planes(self.boards[:self.n], self.prev[:self.n], idx, self.depth, mirror=mirror)
 
     def loss(self, logits, v, idx, targets="played", weights=(1.0, 1.0), mirror=None, q_ratio=0.0, surprise=False,
-             moves_left=None):
+             moves_left=None, legal_mask=False, mask_stats=None):
         """-> (w_p * mean policy loss + w_v * mean value loss, mean policy loss, mean value loss); the first is
         differentiable in logits [B, 2086] and v [B] (gradients from cz_policy_value_loss).  mirror: the flags given to
         ``planes``: a flagged row's target is the mirrored move's (cz_policy_value_loss_m).  q_ratio L > 0: the value
@@ -310,14 +310,25 @@ class ReplayWindow:
         moves_left=(x, W) (a window built with moves_left=True): x [B] is the network's raw moves-left output and W >= 0 the
         loss weight.  W * mean Huber loss (cz_moves_left_loss; the mean formed as the others are, surprise included) is added
         to the first entry, differentiable in x, and the mean Huber loss follows as one more entry at the end.  Without the
-        argument the result is what it is above, from the same launches."""
+        argument the result is what it is above, from the same launches.
+        legal_mask=True (run.py opt --policy-mask legal): the policy softmax, loss and gradient run over each row's legal
+        moves and its target's support, the distribution the search reads (cz_policy_value_loss_l / cz_policy_wdl_loss_l: the
+        mask is generated in the loss kernel from the window's boards, mirrored with a flagged row); everything else above
+        holds as it is.  mask_stats: a dict that receives per-row tensors of the masked kernel: off_mask (int32: the row's
+        target labels outside its legal moves, 0 for a valid record), illegal_mass (the share of the full softmax outside
+        the row's index set) and illegal_margin (the best logit outside it minus the best inside).  An empty dict receives
+        all three; a dict that holds some of these keys receives those alone, and the kernel computes the last two only
+        when asked.  Without legal_mask nothing more is passed on than without these arguments."""
         if surprise and self.w is None:
             raise ValueError("loss(surprise=True) needs a window built with surprise_weight > 0")
+        if mask_stats is not None and not legal_mask:
+            raise ValueError("loss(mask_stats=...) needs legal_mask=True")
+        mk = dict(legal_mask=True, mask_stats=mask_stats) if legal_mask else {}
         if moves_left is not None:
             if self.left is None:
                 raise ValueError("loss(moves_left=...) needs a window built with moves_left=True")
             x_ml, w_m = moves_left
-            res = self.loss(logits, v, idx, targets, weights, mirror=mirror, q_ratio=q_ratio, surprise=surprise)
+            res = self.loss(logits, v, idx, targets, weights, mirror=mirror, q_ratio=q_ratio, surprise=surprise, **mk)
             ml_total, ml_mean = _MovesLeftLoss.apply(x_ml, idx, self, float(w_m), bool(surprise))
             return (res[0] + ml_total,) + tuple(res[1:]) + (ml_mean,)
         if v.dim() == 2:
@@ -327,9 +338,9 @@ class ReplayWindow:
                 raise ValueError("q_ratio > 0 with a win / draw / loss value head: a scalar q does not determine a "
                                  "distribution over win / draw / loss")
             return _PolicyWdlLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
-                                        bool(surprise))
+                                        bool(surprise), *mk.values())
         return _PolicyValueLoss.apply(logits, v, idx, self, MODES[targets], float(weights[0]), float(weights[1]), mirror,
-                                      float(q_ratio), bool(surprise))
+                                      float(q_ratio), bool(surprise), *mk.values())
 
     def value_targets(self, idx, q_ratio=0.0):
         """Host float32 [B] value targets of the positions idx as the loss kernel forms them (tests, tools): mix_targets."""
@@ -359,36 +370,81 @@ class ReplayWindow:
                 out[r, M[played[i]] if flags[r] else played[i]] = 1.0
         return out
 
+    def legal_labels(self, idx, mirror=None):
+        """Host bool [B, 2086]: the legal labels of the positions idx (tests, tools), from the rules the package's host code
+        uses (environment/static_env.py: cz_movegen on the state strings), not from the loss kernel; mirror: per-row flags
+        as in dense_targets, a flagged row's set is that of the mirrored board."""
+        from cchess_alphazero.environment.static_env import array_to_state, get_legal_moves_batch
+        idx = np.asarray(idx.cpu() if hasattr(idx, "cpu") else idx).astype(np.int64)
+        flags = np.zeros(len(idx), dtype=bool) if mirror is None else \
+            np.asarray(mirror.cpu() if hasattr(mirror, "cpu") else mirror) != 0
+        boards = self.boards[:self.n].cpu().numpy()[idx].reshape(-1, 10, 9)
+        boards = np.where(flags[:, None, None], boards[:, :, ::-1], boards).reshape(-1, 90)
+        out = np.zeros((len(idx), _native.NLABELS), dtype=bool)
+        if len(idx):
+            for r, moves in enumerate(get_legal_moves_batch([array_to_state(b) for b in boards])):
+                out[r, [_LABEL[m] for m in moves]] = True
+        return out
+
+
+MASK_STATS = ("off_mask", "illegal_mass", "illegal_margin")
+
+
+def _mask_args(win, legal_mask, mask_stats):
+    """The keywords of _native's loss functions for loss(legal_mask=..., mask_stats=...): nothing without the mask."""
+    if not legal_mask:
+        return {}
+    want = () if mask_stats is None else (tuple(mask_stats) or MASK_STATS)
+    unknown = [k for k in want if k not in MASK_STATS]
+    if unknown:
+        raise ValueError(f"mask_stats: unknown keys {unknown}: expected some of {MASK_STATS}")
+    return dict(boards=win.boards[:win.n], off_mask="off_mask" in want,
+                mask_diag="illegal_mass" in want or "illegal_margin" in want)
+
+
+def _mask_results(mask_stats, kw, more):
+    """Hand the outputs that followed the gradients (off_mask, then illegal_mass and illegal_margin) to the caller's dict."""
+    if mask_stats is None:
+        return
+    more = list(more)
+    if kw["off_mask"]:
+        mask_stats["off_mask"] = more.pop(0)
+    if kw["mask_diag"]:
+        mask_stats["illegal_mass"], mask_stats["illegal_margin"] = more
+
 
 class _PolicyValueLoss(torch.autograd.Function):
     """w_p * mean(policy loss) + w_v * mean(value loss) of a minibatch; backward hands out the kernel's gradients."""
 
     @staticmethod
-    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None, q_ratio=0.0, surprise=False):
+    def forward(ctx, logits, v, idx, win, mode, w_p, w_v, mirror=None, q_ratio=0.0, surprise=False, legal_mask=False,
+                mask_stats=None):
         n = win.n
+        mk = _mask_args(win, legal_mask, mask_stats)
         if surprise:
-            pl, se, gl, gv = _native.policy_value_loss(
+            pl, se, gl, gv, *more = _native.policy_value_loss(
                 logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
                 win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
-                q=win.q[:n] if q_ratio else None, q_ratio=q_ratio, row_w=win.w[:n])
+                q=win.q[:n] if q_ratio else None, q_ratio=q_ratio, row_w=win.w[:n], **mk)
             ctx.save_for_backward(gl, gv)
             wr = win.w[:n][idx.long()]
             pm, vm = (wr * pl).mean(), (wr * se).mean()     # the loss whose gradients the kernel returned
-            ctx.mark_non_differentiable(pm, vm)
-            return w_p * pm + w_v * vm, pm, vm
-        pl, se, gl, gv = _native.policy_value_loss(
-            logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
-            win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
-            q=win.q[:n] if q_ratio else None, q_ratio=q_ratio)
-        ctx.save_for_backward(gl, gv)
-        pm, vm = pl.mean(), se.mean()
+        else:
+            pl, se, gl, gv, *more = _native.policy_value_loss(
+                logits.detach(), v.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
+                win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
+                q=win.q[:n] if q_ratio else None, q_ratio=q_ratio, **mk)
+            ctx.save_for_backward(gl, gv)
+            pm, vm = pl.mean(), se.mean()
+        if mk:
+            _mask_results(mask_stats, mk, more)
         ctx.mark_non_differentiable(pm, vm)
         return w_p * pm + w_v * vm, pm, vm
 
     @staticmethod
     def backward(ctx, g_total, _g_pm, _g_vm):
         gl, gv = ctx.saved_tensors
-        return g_total * gl, g_total * gv, None, None, None, None, None, None, None, None
+        return (g_total * gl, g_total * gv) + (None,) * 10
 
 
 class _PolicyWdlLoss(torch.autograd.Function):
@@ -396,12 +452,15 @@ class _PolicyWdlLoss(torch.autograd.Function):
     cross-entropy; the fourth result is the mean squared error of P(win) - P(loss) against z."""
 
     @staticmethod
-    def forward(ctx, logits, vlogits, idx, win, mode, w_p, w_v, mirror=None, surprise=False):
+    def forward(ctx, logits, vlogits, idx, win, mode, w_p, w_v, mirror=None, surprise=False, legal_mask=False, mask_stats=None):
         n = win.n
-        pl, ce, se, gl, gv = _native.policy_wdl_loss(
+        mk = _mask_args(win, legal_mask, mask_stats)
+        pl, ce, se, gl, gv, *more = _native.policy_wdl_loss(
             logits.detach(), vlogits.detach().contiguous(), idx, win.played[:n], win.z[:n], win.row_ptr[:n + 1],
             win.vis_label[:win.nnz], win.vis_count[:win.nnz], mode, w_p, w_v, mirror=mirror,
-            row_w=win.w[:n] if surprise else None)
+            row_w=win.w[:n] if surprise else None, **mk)
+        if mk:
+            _mask_results(mask_stats, mk, more)
         ctx.save_for_backward(gl, gv)
         if surprise:
             wr = win.w[:n][idx.long()]
@@ -414,7 +473,7 @@ class _PolicyWdlLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_pm, _g_vm, _g_sm):
         gl, gv = ctx.saved_tensors
-        return g_total * gl, g_total * gv, None, None, None, None, None, None, None
+        return (g_total * gl, g_total * gv) + (None,) * 9
 
 
 class _MovesLeftLoss(torch.autograd.Function):

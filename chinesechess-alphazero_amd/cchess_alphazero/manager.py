@@ -64,6 +64,10 @@ _FLAGS = [
     ("--augment", dict(choices=["none", "mirror"], default="none",
                        help="(opt) mirror: every training row of every epoch is the left-right mirrored position with "
                             "probability 1/2 (planes and policy targets, in the trainer's kernels)")),
+    ("--policy-mask", dict(choices=["none", "legal"], default="none",
+                           help="(opt) legal: the policy softmax, its loss and its gradient run over each position's legal "
+                                "moves, the distribution the search reads, instead of all 2086 labels (the mask is generated "
+                                "in the loss kernel from the window's boards)")),
     ("--moves-left", dict(type=float, default=0.0, metavar="W",
                           help="(opt) train the moves-left output (one more Dense(1) on the value head's hidden layer, "
                                "predicting the plies until the game ends) with the loss weight W (finite, >= 0; 0 = off); a "
@@ -215,6 +219,9 @@ def build_config(args):
     if args.moves_left and args.cmd != "opt":
         raise SystemExit("--moves-left is an option of `run.py opt`")
     config.trainer.moves_left = args.moves_left
+    if args.policy_mask != "none" and args.cmd != "opt":
+        raise SystemExit("--policy-mask is an option of `run.py opt`")
+    config.trainer.policy_mask = args.policy_mask
     config.trainer.policy_targets = args.policy_targets
     config.trainer.augment = args.augment
     return config

@@ -53,6 +53,18 @@ Deliberate deviations from the reference:
     the mean |32 softplus(x) - target| in plies on the validation rows.  With W = 0 a model that has the output trains
     as one without it: the output gets no gradient beyond L2.  A record does not say that it was cut short, so the games
     of ``run.py reanalyse --reanalyse-plies`` carry targets that are too small, and ``opt`` cannot tell;
+  - ``--policy-mask legal`` (default ``none``: the reference, the softmax over all 2086 labels) takes the policy softmax,
+    its loss and its gradient over each row's legal moves, which is the distribution the search reads: it forms a node's
+    priors from the legal moves' logits alone, so no gradient goes into pushing some 2000 illegal labels down.  The mask is
+    generated in the loss kernel (``cz_policy_value_loss_l`` / ``cz_policy_wdl_loss_l``) from the window's 90-byte board,
+    mirrored with a flagged row; there is no dense mask and no host rule code in a step.  ``val`` and ``val_mirror`` are
+    then masked losses, and every epoch adds ``val_policy_full`` (the unmasked policy loss of the same rows, which keeps
+    runs with and without the mask comparable), ``val_illegal_mass`` (the mean share of the full softmax on illegal labels),
+    ``val_illegal_margin`` (the largest best-illegal minus best-legal logit) and ``off_mask_targets`` (target labels outside
+    the legal moves among the epoch's training and validation rows: 0 for valid records, an error in the log otherwise).
+    Nothing pushes the illegal logits of such a model down: `run.py eval`, the UCI engine and CChessPlayer hand the search
+    a full fp32 softmax, in which the best legal move's probability leaves the normal range once the margin nears
+    87 = -ln(FLT_MIN); the trainer warns from there on.  A masked model is an ordinary model file;
   - Keras' SGD folds the learning rate into its velocity, torch's does not: the two differ only in the first steps
     after a learning-rate change;
   - a model loaded from Keras HDF5 is saved back as this package's JSON + ``.pt`` (there is no HDF5 writer);
@@ -72,6 +84,7 @@ from cchess_alphazero.lib.data_helper import get_game_data_filenames
 logger = getLogger(__name__)
 
 VALIDATION_SPLIT = 0.02          # Keras fit(validation_split=0.02), optimize.py:120-133
+FULL_SOFTMAX_MARGIN = 87.0       # -ln(FLT_MIN) = 87.3: a logit this far below the row's maximum has a subnormal fp32 softmax
 
 
 def select_files(files, last_file, tc):
@@ -157,6 +170,11 @@ class OptimizeWorker:
         self.moves_left_weight = float(getattr(config.trainer, "moves_left", 0.0))
         if not 0.0 <= self.moves_left_weight < float("inf"):
             raise ValueError(f"trainer.moves_left={self.moves_left_weight!r}: expected a finite W >= 0")
+        self.policy_mask = getattr(config.trainer, "policy_mask", "none")
+        if self.policy_mask not in ("none", "legal"):
+            raise ValueError(f"trainer.policy_mask={self.policy_mask!r}: expected none or legal")
+        self.legal_mask = self.policy_mask == "legal"
+        self.off_mask_sum = None        # legal mask: target labels outside the legal moves in the steps since the last epoch
         self.rng = np.random.default_rng(config.engine.base_seed)
         # the mirror flags have their own stream: self.rng draws what it draws without the option
         self.aug_rng = np.random.default_rng([config.engine.base_seed, 1]) if self.augment == "mirror" else None
@@ -318,7 +336,9 @@ class OptimizeWorker:
             tr_loss = (sums / max(1, len(tr))).tolist()
             # (a win / draw / loss model's and the moves-left output's further validation figures; nothing is asked otherwise)
             extra = {}
-            va_loss = (self.evaluate(va_d, **(dict(extra=extra) if self.wdl or ml else {}))) if len(va) else [float("nan")] * 3
+            mask = {}                                # (--policy-mask legal: the masked kernel's validation figures)
+            va_loss = (self.evaluate(va_d, **(dict(extra=extra) if self.wdl or ml else {}),
+                                     **(dict(mask_out=mask) if self.legal_mask else {}))) if len(va) else [float("nan")] * 3
             entry = dict(train=tr_loss[:3], val=va_loss, **extra)
             if ml:
                 entry["moves_left"] = tr_loss[3]
@@ -345,6 +365,23 @@ class OptimizeWorker:
                 entry["val_value_z"] = self.evaluate(va_d, q_ratio=0.0)[2] if len(va) else float("nan")
                 logger.info(f"epoch {ep + 1}/{epochs}: value targets z + {self.q_ratio:g} (q - z); against z alone: "
                             f"val_value_z {entry['val_value_z']:.4f}")
+            if self.legal_mask:
+                off = (int(self.off_mask_sum) if self.off_mask_sum is not None else 0) + mask.get("off_mask_targets", 0)
+                self.off_mask_sum = None
+                entry.update(val_illegal_mass=mask.get("val_illegal_mass", float("nan")),
+                             val_illegal_margin=mask.get("val_illegal_margin", float("nan")), off_mask_targets=off,
+                             val_policy_full=self.evaluate(va_d, legal_mask=False)[1] if len(va) else float("nan"))
+                logger.info(f"epoch {ep + 1}/{epochs}: policy over the legal moves; over all labels: val_policy_full "
+                            f"{entry['val_policy_full']:.4f}; validation rows: mean illegal share of the full softmax "
+                            f"val_illegal_mass {entry['val_illegal_mass']:.4f}, largest best-illegal minus best-legal logit "
+                            f"val_illegal_margin {entry['val_illegal_margin']:.2f}; off_mask_targets {off}")
+                if off:
+                    logger.error(f"epoch {ep + 1}/{epochs}: {off} target labels are no legal move of their position: the "
+                                 f"records and the rules disagree (such a label stays in its row's softmax)")
+                if entry["val_illegal_margin"] >= FULL_SOFTMAX_MARGIN:
+                    logger.warning(f"epoch {ep + 1}/{epochs}: val_illegal_margin {entry['val_illegal_margin']:.1f} >= "
+                                   f"{FULL_SOFTMAX_MARGIN:g}: a full fp32 softmax (run.py eval, the UCI engine, CChessPlayer) "
+                                   f"no longer holds the best legal move's probability as a normal number")
             self.history.append(entry)
         return steps_of_pass(n - skipped, bs, epochs)
 
@@ -364,18 +401,23 @@ class OptimizeWorker:
         With --moves-left W > 0 the total includes W times the mean moves-left loss, which follows as a fourth entry."""
         tc = self.config.trainer
         planes = self.window.planes(idx, mirror=mirror)
+        stats = dict(off_mask=None)                  # --policy-mask legal: the one per-row figure a training step asks for
         if self.moves_left_weight:
             logits, v, x_ml = self.model.model(planes, logits=True, moves_left=True)
             res = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
                                    **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight),
-                                   moves_left=(x_ml, self.moves_left_weight))
+                                   moves_left=(x_ml, self.moves_left_weight), **self._m_args(self.legal_mask, stats))
             total, more = res[0], (res[1], res[2], res[-1])
         else:
             logits, v = self.model.model(planes, logits=True)
             # (a win / draw / loss model returns its three value logits: the window's loss takes them as they are)
             total, pm, vm = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=mirror,
-                                             **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight))[:3]
+                                             **self._q_args(self.q_ratio), **self._s_args(self.surprise_weight),
+                                             **self._m_args(self.legal_mask, stats))[:3]
             more = (pm, vm)
+        if stats["off_mask"] is not None:
+            off = stats["off_mask"].sum()
+            self.off_mask_sum = off if self.off_mask_sum is None else self.off_mask_sum + off
         loss = total + self.l2_term()
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -392,18 +434,31 @@ class OptimizeWorker:
         # (likewise; only training steps are weighted, evaluate() never passes it)
         return dict(surprise=True) if surprise_weight else {}
 
-    def evaluate(self, idx_all, mirror=False, q_ratio=None, extra=None):
+    @staticmethod
+    def _m_args(legal_mask, stats):
+        # (likewise: without --policy-mask legal a window's loss() is asked nothing new)
+        return dict(legal_mask=True, mask_stats=stats) if legal_mask else {}
+
+    def evaluate(self, idx_all, mirror=False, q_ratio=None, extra=None, legal_mask=None, mask_out=None):
         """Validation losses (inference-mode BatchNorm, as Keras): [total incl. L2, policy, value]; mirror=True: of the
         mirror images of all rows.  q_ratio: the value targets' mix, None = the trainer's own.  extra: a dict that, for a
         win / draw / loss model, receives val_value_z (the squared error of P(win) - P(loss) against z), val_draw_pred
         (the mean predicted draw probability) and val_draw_share (the share of rows with z == 0); with --moves-left W > 0 it
         receives val_moves_left (the mean Huber loss, unweighted) and val_moves_left_mae (the mean |32 softplus(x) - target|
-        in plies), and the total includes W times the former."""
+        in plies), and the total includes W times the former.
+        legal_mask: whether the policy loss is the masked one, None = the trainer's own (--policy-mask); mask_out: a dict
+        that, with the mask on, receives val_illegal_mass (the mean over the rows), val_illegal_margin (the maximum over
+        them) and off_mask_targets (the sum over them)."""
         import torch
         from cchess_alphazero.agent.model import moves_left_plies
         tc = self.config.trainer
         net = self.model.model
         net.eval()
+        masked = self.legal_mask if legal_mask is None else bool(legal_mask)
+        if masked:
+            mass_sum = torch.zeros((), dtype=torch.float64, device=idx_all.device)
+            margin_max = torch.full((), float("-inf"), dtype=torch.float32, device=idx_all.device)
+            off_sum = torch.zeros((), dtype=torch.int64, device=idx_all.device)
         sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
         wdl_sums = torch.zeros(3, dtype=torch.float64, device=idx_all.device)
         ml_sums = torch.zeros(2, dtype=torch.float64, device=idx_all.device)
@@ -417,9 +472,15 @@ class OptimizeWorker:
                     ml_args = dict(moves_left=(x_ml, self.moves_left_weight))
                 else:
                     logits, v = net(self.window.planes(idx, mirror=flags), logits=True)
+                stats = {}                           # the masked kernel's three per-row figures
                 res = self.window.loss(logits, v, idx, self.targets, tc.loss_weights, mirror=flags,
-                                       **self._q_args(self.q_ratio if q_ratio is None else q_ratio), **ml_args)
+                                       **self._q_args(self.q_ratio if q_ratio is None else q_ratio), **ml_args,
+                                       **self._m_args(masked, stats))
                 pm, vm = res[1], res[2]
+                if stats:
+                    mass_sum += stats["illegal_mass"].double().sum()
+                    margin_max = torch.maximum(margin_max, stats["illegal_margin"].max())
+                    off_sum += stats["off_mask"].sum()
                 if ml_args:
                     err = (moves_left_plies(x_ml.double()) - self.window.left[idx.long()].double()).abs().sum()
                     ml_sums += torch.stack([res[-1].double() * len(idx), err])
@@ -431,6 +492,9 @@ class OptimizeWorker:
             if extra is not None and self.wdl:
                 sq, dp, ds = (wdl_sums / idx_all.shape[0]).tolist()
                 extra.update(val_value_z=sq, val_draw_pred=dp, val_draw_share=ds)
+            if mask_out is not None and masked:
+                mask_out.update(val_illegal_mass=float(mass_sum) / idx_all.shape[0], val_illegal_margin=float(margin_max),
+                                off_mask_targets=int(off_sum))
             l2 = float(self.l2_term())
         net.train()
         w = tc.loss_weights

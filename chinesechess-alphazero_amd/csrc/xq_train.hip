@@ -8,6 +8,9 @@
 //                        played move's one-hot or the record's visit counts, squared value error, and their gradients;
 //                        <WDL = true> (cz_policy_wdl_loss): the same policy half, and for a win / draw / loss value head the
 //                        clipped cross-entropy of its three logits against the class of z, with its gradient
+//                        <MASK = true> (cz_policy_value_loss_l / cz_policy_wdl_loss_l, run.py opt --policy-mask legal): the
+//                        softmax, the loss and the gradient run over the row's legal moves (and its target's support) only;
+//                        the row's wavefront generates the mask from the window's board with wave_movegen
 //   k_moves_left_loss    one thread per minibatch row (cz_moves_left_loss, run.py opt --moves-left): Huber loss of softplus(x)
 //                        against the row's plies-to-the-end target in units of 32 plies, and its gradient
 //
@@ -16,6 +19,13 @@
 // LDS before the one encoder runs, and its target labels go through the label mirror M before they are scattered into the
 // row's dense target.  The flag is the same for the 64 lanes of a row's wavefront, so the branch is wave-uniform; a NULL
 // array is the unflagged kernel.
+//
+// The legal-move mask (run.py opt --policy-mask legal): the search normalises a node's priors over its legal moves alone
+// (xq_search_attach.h: logits_to_weights), so the masked loss trains that distribution.  The window keeps every position's
+// board in the mover's frame, the frame of the labels: the row's wavefront loads it (mirrored when the row is flagged), runs
+// wave_movegen and marks the list's labels in a byte mask in LDS.  A column outside the mask and outside the target's support
+// is read as -inf; everything after that is the unmasked code, so the masked kernel on x gives the bits of the unmasked one
+// on x with those columns set to -inf.  No dense mask tensor exists and no host rule code runs in a step.
 //
 // The contract (shapes, order, error reporting, bit-identity) is stated in include/czero.h.
 #include <hip/hip_runtime.h>
@@ -60,6 +70,13 @@ XQ_D double wave_sum_f64(double v)
     return v;
 }
 
+XQ_D int wave_sum_i32(int v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
 XQ_D void zero_planes(float* __restrict__ out)   // 14 planes: 315 float4
 {
     for (int q = lane_id(); q < 315; q += 64) reinterpret_cast<float4*>(out)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -68,6 +85,33 @@ XQ_D void zero_planes(float* __restrict__ out)   // 14 planes: 315 float4
 constexpr int LOSS_COLS = (NLABELS + 63) / 64;       // 33 logits per lane
 constexpr float CCE_EPS = 1e-7f;                     // Keras 2.0.8 epsilon(); the upper clip is float(1 - 1e-7)
 constexpr float CCE_HI = (float)(1.0 - 1e-7);
+
+// Per-wave LDS of the legal-move mask (k_policy_value_loss<WDL, true>): the row's board, its move list and the mask itself,
+// one byte per label column (a byte store needs no atomic where two moves carry one label).
+struct alignas(16) MaskLDS {
+    int8_t bd[BOARD_LDS];
+    MoveList ml;
+    uint16_t plist[BOARD_LDS];
+    uint8_t legal[LOSS_COLS * 64];
+};
+
+// legal[j] = 1 for every label of the move list of board `g` (mirrored first when mir), 0 elsewhere.  The list holds up to
+// MAXMOVES = 128 entries: a lane marks entry lane and entry lane + 64.
+XQ_D void mark_legal(const int8_t* __restrict__ g, bool mir, MaskLDS& m)
+{
+    const int lane = lane_id();
+    load_board(g, m.bd);
+    if (mir) mirror_board(m.bd);
+    int n = wave_movegen(m.bd, m.ml, m.plist);
+    n = n < MAXMOVES ? n : MAXMOVES;
+    for (int q = lane; q < LOSS_COLS * 16; q += 64) reinterpret_cast<uint32_t*>(m.legal)[q] = 0u;
+    wave_sync();
+    for (int k = lane; k < n; k += 64) {
+        const int lab = m.ml.lab[k];
+        if (lab < NLABELS) m.legal[lab] = 1;
+    }
+    wave_sync();
+}
 
 }  // namespace
 
@@ -141,16 +185,19 @@ __global__ __launch_bounds__(64) void k_gather_planes(const int8_t* __restrict__
     }
 }
 
-template <bool WDL>
+template <bool WDL, bool MASK>
 __global__ __launch_bounds__(64) void k_policy_value_loss(
     const float* __restrict__ logits, int ld, const float* __restrict__ v, const int32_t* __restrict__ idx,
     const uint8_t* __restrict__ mirror, int n_rows, int n_pos, const int32_t* __restrict__ row_ptr, const uint16_t* __restrict__ vis_label,
     const int32_t* __restrict__ vis_count, int nnz, const uint16_t* __restrict__ played, const float* __restrict__ z,
     const float* __restrict__ q, float q_ratio, const float* __restrict__ row_w, int mode,
     float w_p, float w_v, float* __restrict__ policy_loss, float* __restrict__ value_sqerr,
-    float* __restrict__ grad_logits, float* __restrict__ grad_v, float* __restrict__ value_ce)
+    float* __restrict__ grad_logits, float* __restrict__ grad_v, float* __restrict__ value_ce,
+    const int8_t* __restrict__ boards, int32_t* __restrict__ off_mask, float* __restrict__ illegal_mass,
+    float* __restrict__ illegal_margin)                // the last four: MASK only
 {
     __shared__ float tgt[LOSS_COLS * 64];            // the row's dense target, built from the sparse entries
+    __shared__ MaskLDS mk;                           // MASK only: never named otherwise, and then not allocated
     const int lane = lane_id();
     const float inv_b = 1.0f / (float)n_rows;
     const float c = w_p * inv_b;
@@ -169,9 +216,15 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
                 } else {
                     grad_v[r] = 0.f;
                 }
+                if constexpr (MASK) {
+                    if (off_mask != nullptr) off_mask[r] = 0;
+                    if (illegal_mass != nullptr) illegal_mass[r] = 0.f;
+                    if (illegal_margin != nullptr) illegal_margin[r] = 0.f;
+                }
             }
             continue;
         }
+        if constexpr (MASK) mark_legal(boards + (size_t)i * NSQ, mir, mk);
 #pragma unroll
         for (int k = 0; k < LOSS_COLS; ++k) tgt[lane + 64 * k] = 0.f;
         wave_sync();
@@ -203,10 +256,19 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
         const float* zr = logits + (size_t)r * ld;
         float e[LOSS_COLS];
         float mx = -INFINITY;
+        uint64_t in_a = 0;                               // MASK: bit k = this lane's column lane + 64 k is in A
+        int off = 0;                                     // MASK: this lane's target entries outside the legal set
 #pragma unroll
         for (int k = 0; k < LOSS_COLS; ++k) {
             const int j = lane + 64 * k;
             e[k] = j < NLABELS ? zr[j] : -INFINITY;
+            if constexpr (MASK) {
+                // A = the legal labels and the target's support; a column outside A is read as -inf, whatever it holds
+                const bool legal = mk.legal[j] != 0, sup = tgt[j] != 0.f;
+                if (legal || sup) in_a |= 1ull << k;
+                else e[k] = -INFINITY;
+                off += (sup && !legal) ? 1 : 0;
+            }
             mx = fmaxf(mx, e[k]);
         }
 #pragma unroll
@@ -241,6 +303,39 @@ __global__ __launch_bounds__(64) void k_policy_value_loss(
                 const float p = e[k];
                 const float tm = (p > CCE_EPS && p < CCE_HI) ? tgt[j] : 0.f;
                 g[j] = cr * (p * S - tm);
+            }
+        }
+        if constexpr (MASK) {
+            off = wave_sum_i32(off);
+            if (off_mask != nullptr && lane == 0) off_mask[r] = off;
+            if (illegal_mass != nullptr || illegal_margin != nullptr) {
+                // validation only (a training step passes NULL): the logits are read again, L2 still holds them.
+                // mo = the largest logit outside A; the full softmax over all 2086 columns has its maximum max(mx, mo).
+                float mo = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < LOSS_COLS; ++k) {
+                    const int j = lane + 64 * k;
+                    if (j < NLABELS && !((in_a >> k) & 1ull)) mo = fmaxf(mo, zr[j]);
+                }
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) mo = fmaxf(mo, __shfl_xor(mo, m, 64));
+                const float mf = fmaxf(mx, mo);
+                double s_in = 0.0, s_out = 0.0;          // fp32 exponentials, summed in float64
+#pragma unroll
+                for (int k = 0; k < LOSS_COLS; ++k) {
+                    const int j = lane + 64 * k;
+                    if (j < NLABELS) {
+                        const double ex = (double)expf(zr[j] - mf);
+                        if ((in_a >> k) & 1ull) s_in += ex;
+                        else s_out += ex;
+                    }
+                }
+                s_in = wave_sum_f64(s_in);
+                s_out = wave_sum_f64(s_out);
+                if (lane == 0) {
+                    if (illegal_mass != nullptr) illegal_mass[r] = (float)(s_out / (s_in + s_out));
+                    if (illegal_margin != nullptr) illegal_margin[r] = mo - mx;
+                }
             }
         }
         if (WDL) {
@@ -358,12 +453,23 @@ int cz_gather_planes(const int8_t* boards, const int32_t* prev, int n_pos, const
     return cz_gather_planes_m(boards, prev, n_pos, idx, nullptr, n_rows, depth, planes, stream);
 }
 
-int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
-                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
-                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
-                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
-                           void* stream)
+}  // extern "C"
+
+namespace {
+
+// cz_policy_value_loss_w and cz_policy_value_loss_l: one argument check, and the kernel with or without the legal-move mask
+// (likewise cz_policy_wdl_loss and cz_policy_wdl_loss_l below)
+template <bool MASK>
+int launch_value_loss(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                      int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                      const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                      float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                      const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream)
 {
+    if (MASK && !boards) {
+        czi_set_error("cz_policy_value_loss_l: boards is NULL");
+        return CZ_ERR_ARG;
+    }
     if (!(q_ratio >= 0.f && q_ratio <= 1.f)) {
         czi_set_error("cz_policy_value_loss_q: q_ratio outside [0, 1]");
         return CZ_ERR_ARG;
@@ -376,10 +482,62 @@ int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const in
         czi_set_error("cz_policy_value_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
         return CZ_ERR_ARG;
     }
-    hipLaunchKernelGGL(k_policy_value_loss<false>, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, v, idx,
-                       mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, row_w, mode, w_p,
-                       w_v, policy_loss, value_sqerr, grad_logits, grad_v, (float*)nullptr);
+    hipLaunchKernelGGL((k_policy_value_loss<false, MASK>), dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld,
+                       v, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q, q_ratio, row_w, mode,
+                       w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v, (float*)nullptr, boards, off_mask,
+                       illegal_mass, illegal_margin);
     return launch_status("cz_policy_value_loss: launch failed");
+}
+
+template <bool MASK>
+int launch_wdl_loss(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                    int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                    const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
+                    float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
+                    const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream)
+{
+    if (MASK && !boards) {
+        czi_set_error("cz_policy_wdl_loss_l: boards is NULL");
+        return CZ_ERR_ARG;
+    }
+    if (n_rows == 0) return CZ_OK;
+    if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !vlogits || !idx || !policy_loss ||
+        !value_ce || !value_sqerr || !grad_logits || !grad_vlogits || (n_pos > 0 && (!played || !z)) ||
+        nnz < 0 || (mode == 1 && nnz > 0 && (!row_ptr || !vis_label || !vis_count))) {
+        czi_set_error("cz_policy_wdl_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
+        return CZ_ERR_ARG;
+    }
+    hipLaunchKernelGGL((k_policy_value_loss<true, MASK>), dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld,
+                       vlogits, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, (const float*)nullptr,
+                       0.f, row_w, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_vlogits, value_ce, boards,
+                       off_mask, illegal_mass, illegal_margin);
+    return launch_status("cz_policy_wdl_loss: launch failed");
+}
+
+}  // namespace
+
+extern "C" {
+
+int cz_policy_value_loss_w(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           void* stream)
+{
+    return launch_value_loss<false>(logits, ld, v, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q,
+                                    q_ratio, row_w, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v, nullptr,
+                                    nullptr, nullptr, nullptr, stream);
+}
+
+int cz_policy_value_loss_l(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream)
+{
+    return launch_value_loss<true>(logits, ld, v, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, q,
+                                   q_ratio, row_w, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_v, boards,
+                                   off_mask, illegal_mass, illegal_margin, stream);
 }
 
 int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
@@ -388,17 +546,20 @@ int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const 
                        float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
                        void* stream)
 {
-    if (n_rows == 0) return CZ_OK;
-    if (n_rows < 0 || n_pos < 0 || ld < CZ_NLABELS || (mode != 0 && mode != 1) || !logits || !vlogits || !idx || !policy_loss ||
-        !value_ce || !value_sqerr || !grad_logits || !grad_vlogits || (n_pos > 0 && (!played || !z)) ||
-        nnz < 0 || (mode == 1 && nnz > 0 && (!row_ptr || !vis_label || !vis_count))) {
-        czi_set_error("cz_policy_wdl_loss: bad argument (ld >= 2086, mode 0 played / 1 visits)");
-        return CZ_ERR_ARG;
-    }
-    hipLaunchKernelGGL(k_policy_value_loss<true>, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, logits, ld, vlogits,
-                       idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z, (const float*)nullptr, 0.f,
-                       row_w, mode, w_p, w_v, policy_loss, value_sqerr, grad_logits, grad_vlogits, value_ce);
-    return launch_status("cz_policy_wdl_loss: launch failed");
+    return launch_wdl_loss<false>(logits, ld, vlogits, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z,
+                                  row_w, mode, w_p, w_v, policy_loss, value_ce, value_sqerr, grad_logits, grad_vlogits, nullptr,
+                                  nullptr, nullptr, nullptr, stream);
+}
+
+int cz_policy_wdl_loss_l(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                         int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                         const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
+                         float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
+                         const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream)
+{
+    return launch_wdl_loss<true>(logits, ld, vlogits, idx, mirror, n_rows, n_pos, row_ptr, vis_label, vis_count, nnz, played, z,
+                                 row_w, mode, w_p, w_v, policy_loss, value_ce, value_sqerr, grad_logits, grad_vlogits, boards,
+                                 off_mask, illegal_mass, illegal_margin, stream);
 }
 
 int cz_policy_value_loss_q(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,

@@ -1440,6 +1440,43 @@ int cz_policy_wdl_loss(const float* logits, int ld, const float* vlogits, const 
                        const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
                        float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
                        void* stream);
+/* The two losses above over the legal moves' softmax (run.py opt --policy-mask legal): the distribution the search reads,
+ * which forms a node's priors from its legal moves' logits alone.  The arguments of cz_policy_value_loss_w and
+ * cz_policy_wdl_loss, and before `stream`:
+ *   boards[n_pos][90] (DEVICE int8): the window's boards as cz_replay_games writes them, each in its mover's frame, the
+ *     frame of the labels.  NULL gives CZ_ERR_ARG.
+ *   off_mask[n_rows] (int32), illegal_mass[n_rows], illegal_margin[n_rows] (float32): per-row outputs, each may be NULL.
+ * Row r with i = idx[r]: the row's wavefront generates the ordered move list of boards[i] (of its left-right mirror image
+ * where mirror[r] is set) with the move generator of cz_movegen and marks its labels.  The row's index set A is
+ *       A = the labels of that list, together with the support of the row's target t (the labels with t_k != 0).
+ * A target label outside the list -- no valid record has one -- joins A, so the loss stays finite, and off_mask[r] counts
+ * such labels: 0 for every valid record.  Softmax, clipped cross-entropy, the clip's gradient mask and the gradient are
+ * the formulas of cz_policy_value_loss restricted to A:
+ *       p_j = exp(l_j - max_A l) / sum_A exp(l_k - max_A l) for j in A;  grad_logits[r][j] = 0.0f for j outside A.
+ * Logits outside A do not matter: none of them, whether finite, +-inf or NaN, changes policy_loss, grad_logits, the value
+ * outputs or off_mask.  The kernel reads such a column as -inf and is the unmasked code from there on, which gives the
+ * identity
+ *       cz_policy_value_loss_l(x) == cz_policy_value_loss_w(x with every column outside A set to -inf), bit for bit,
+ * in policy_loss, value_sqerr (value_ce), grad_v and grad_logits on A; outside A both gradients are 0.  The value half
+ * (scalar head, q mix, win / draw / loss head, row weights) is the unmasked entry point's.
+ * The two diagnostics are computed only where their pointer is given (a training step passes NULL, validation buffers):
+ *   illegal_mass[r]   = the share of the full softmax over all 2086 columns, its maximum taken over all columns, that
+ *                       lies outside A (fp32 exponentials summed in float64)
+ *   illegal_margin[r] = max_{j outside A} l_j - max_{j in A} l_j, one fp32 difference
+ * A network trained with the mask is not pushed to lower its illegal logits, so the margin may grow: once it nears
+ * 87 = -ln(FLT_MIN), a full fp32 softmax (what a probability-fed search receives) no longer holds the best legal move's
+ * probability as a normal number.
+ * An index outside [0, n_pos) behaves as above, no board is read, and the three new outputs get 0. */
+int cz_policy_value_loss_l(const float* logits, int ld, const float* v, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                           int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                           const uint16_t* played, const float* z, const float* q, float q_ratio, const float* row_w, int mode,
+                           float w_p, float w_v, float* policy_loss, float* value_sqerr, float* grad_logits, float* grad_v,
+                           const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream);
+int cz_policy_wdl_loss_l(const float* logits, int ld, const float* vlogits, const int32_t* idx, const uint8_t* mirror, int n_rows,
+                         int n_pos, const int32_t* row_ptr, const uint16_t* vis_label, const int32_t* vis_count, int nnz,
+                         const uint16_t* played, const float* z, const float* row_w, int mode, float w_p, float w_v,
+                         float* policy_loss, float* value_ce, float* value_sqerr, float* grad_logits, float* grad_vlogits,
+                         const int8_t* boards, int32_t* off_mask, float* illegal_mass, float* illegal_margin, void* stream);
 /* The loss of the moves-left output (run.py opt --moves-left W), a kernel of its own beside the policy / value loss: one
  * thread per row.  x[n_rows]: the head's raw output; left[n_pos] (int32): a position's target, the number of record items
  * from its own to the end of its game, inclusive (the last recorded position has 1); idx as above; row_w[n_pos] or NULL

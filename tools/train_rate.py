@@ -2,6 +2,7 @@
 """Trainer throughput (run.py opt, worker/optimize.py) on one device.
 
     python tools/train_rate.py [--games 200] [--steps 20] [--warmup 5] [--batch 512] [--mirror] [--repeats 1]
+                               [--policy-mask legal]
 
 Reports, as one JSON line:
   - the window fill rate in positions/s: ReplayWindow.add_games (cz_replay_games, sparse visit targets) and
@@ -13,6 +14,9 @@ Reports, as one JSON line:
   - with --mirror: the same steps once more with random per-row mirror flags (run.py opt --augment mirror:
     cz_gather_planes_m / cz_policy_value_loss_m), as `step_ms_<model>_mirror` beside the unflagged figures of the same
     call; --repeats N alternates the two variants N times (`..._repeats`: every repeat's medians).
+  - with --policy-mask legal: unmasked and masked steps (run.py opt --policy-mask legal: cz_policy_value_loss_l, the mask
+    generated in the loss kernel) of the same build, alternated, at least two legs each: `policy_mask_<model>` holds every
+    leg's loss launch time and whole step time for both, and the spread between the unmasked legs.
 """
 import argparse
 import json
@@ -68,7 +72,7 @@ def fill_rates(games, repeats=3):
     return {"positions": n, **{f"{k}_positions_per_s": round(n / v) for k, v in out.items()}}
 
 
-def step_times(window, filters, blocks, batch, warmup, steps, targets="visits", mirror=False):
+def step_times(window, filters, blocks, batch, warmup, steps, targets="visits", mirror=False, legal_mask=False):
     import torch
     from cchess_alphazero.agent.model import CChessNet
     from cchess_alphazero.worker.optimize import l2_parameters
@@ -87,7 +91,10 @@ def step_times(window, filters, blocks, batch, warmup, steps, targets="visits", 
         ev[1].record()
         logits, v = net(x, logits=True)
         ev[2].record()
-        total, _, _ = window.loss(logits, v, idx, targets, mirror=flags) if mirror else window.loss(logits, v, idx, targets)
+        if legal_mask:      # what a training step of --policy-mask legal asks for: the mask and off_mask, no diagnostics
+            total, _, _ = window.loss(logits, v, idx, targets, mirror=flags, legal_mask=True, mask_stats=dict(off_mask=None))
+        else:
+            total, _, _ = window.loss(logits, v, idx, targets, mirror=flags) if mirror else window.loss(logits, v, idx, targets)
         ev[3].record()
         opt.zero_grad(set_to_none=True)
         (total + 1e-4 * sum((w * w).sum() for w in l2)).backward()
@@ -116,6 +123,8 @@ def main():
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--mirror", action="store_true", help="also time the steps with random per-row mirror flags")
     ap.add_argument("--repeats", type=int, default=1, help="repeats of each variant (alternating with --mirror)")
+    ap.add_argument("--policy-mask", choices=["none", "legal"], default="none",
+                    help="legal: also time the steps with the loss over the legal moves, alternating with the unmasked steps")
     args = ap.parse_args()
     import torch
     from cchess_alphazero import _native
@@ -138,6 +147,17 @@ def main():
             res[f"step_ms_{name}_mirror"] = runs[True][0]
         if args.repeats > 1:
             res[f"step_ms_{name}_repeats"] = {"plain": runs[False], **({"mirror": runs[True]} if args.mirror else {})}
+        if args.policy_mask == "legal":
+            # unmasked, masked, unmasked, masked, ... of the same build; at least two legs each, so that the spread between
+            # two unmasked legs stands beside any difference
+            legs = {"none": [], "legal": []}
+            for _ in range(max(2, args.repeats)):
+                for m in ("none", "legal"):
+                    legs[m].append(step_times(win, f, b, args.batch, args.warmup, args.steps, legal_mask=m == "legal"))
+            res[f"policy_mask_{name}"] = {
+                **{f"{k}_ms_{m}": [leg[k] for leg in legs[m]] for k in ("loss", "total") for m in ("none", "legal")},
+                "loss_ms_unmasked_spread": round(max(x["loss"] for x in legs["none"]) - min(x["loss"] for x in legs["none"]), 4),
+                "total_ms_unmasked_spread": round(max(x["total"] for x in legs["none"]) - min(x["total"] for x in legs["none"]), 4)}
     res["batch"] = args.batch
     print(json.dumps(res))
 
