@@ -309,6 +309,20 @@ class Search:
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _need(self, fn, what):
+        """A library built before the entry point fn existed is refused by name."""
+        if not hasattr(self.L, fn):
+            raise _native.NativeError("this libczero.so has no %s (%s)" % (what, fn))
+
+    def _path(self, path):
+        """The path argument of the node_* readers (label indices, [G, L] or [L] for G = 1; None / empty = the root) on the
+        device: (the tensor, which the caller holds until its call is made; its pointer, None for the root; L)."""
+        import torch
+        pa = np.zeros((self.G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
+            np.asarray(path, dtype=np.uint16).reshape(self.G, -1)
+        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        return pt, C.c_void_p(pt.data_ptr()) if pt is not None else None, pa.shape[1]
+
     # -- modes --
     def start_selfplay(self, seed=0, first_game_id=0, game_id_stride=0):
         _native.check(self.L.cz_search_start_selfplay(self.h, int(seed), int(first_game_id), int(game_id_stride),
@@ -381,8 +395,7 @@ class Search:
         only the move is the script's.  Host arrays, copied into the search object; None / empty switches it off.  Needs
         record_visits() on.  Call it before start_selfplay(0) and before a graph capture; a slot whose next game id has no
         script goes idle (pending() counts the others).  drain_records() reports `script_index` and `script_mismatch`."""
-        if not hasattr(self.L, "cz_search_set_script"):
-            raise _native.NativeError("this libczero.so has no scripted games (cz_search_set_script)")
+        self._need("cz_search_set_script", "scripted games")
         n = 0 if init_boards is None else len(init_boards)
         ptrs = [None] * 4
         if n:
@@ -459,8 +472,7 @@ class Search:
         10 .. 24 (576 bytes per entry, an allocation of its own: device_bytes() includes it).  Refused with use_history.
         The caller empties it (clear_eval_cache) when the network behind the queue changes.  Call it before the rounds
         and before a graph capture."""
-        if not hasattr(self.L, "cz_search_set_eval_cache"):
-            raise _native.NativeError("this libczero.so has no evaluation cache (cz_search_set_eval_cache)")
+        self._need("cz_search_set_eval_cache", "evaluation cache")
         v = check_eval_cache_log2(log2_entries, "set_eval_cache: log2_entries")
         _native.check(self.L.cz_search_set_eval_cache(self.h, v, self._stream()), "cz_search_set_eval_cache")
         self.eval_cache = v
@@ -471,8 +483,7 @@ class Search:
         row, a winning root move is taken at once, a decided root starts no further simulation, and at a won root the
         played move is the winning one.  Refused beside the features include/czero.h's matrix names for it.
         Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
-        if not hasattr(self.L, "cz_search_set_solver"):
-            raise _native.NativeError("this libczero.so has no MCTS solver (cz_search_set_solver)")
+        self._need("cz_search_set_solver", "MCTS solver")
         _native.check(self.L.cz_search_set_solver(self.h, 1 if on else 0, self._stream()), "cz_search_set_solver")
         self.solver = bool(on)
 
@@ -485,8 +496,7 @@ class Search:
         rules, the evaluation cache and a script, and they beside it.  Call it before start_selfplay() / set_roots() and
         before a graph capture."""
         import torch
-        if not hasattr(self.L, "cz_search_set_moves_left"):
-            raise _native.NativeError("this libczero.so has no moves-left utility (cz_search_set_moves_left)")
+        self._need("cz_search_set_moves_left", "moves-left utility")
         if slope > 0.0 and self.moves_left_x is None:
             self.moves_left_x = torch.zeros((self.slots,), dtype=torch.float32, device=self.device)
         ptr = C.c_void_p(self.moves_left_x.data_ptr()) if self.moves_left_x is not None else None
@@ -500,17 +510,14 @@ class Search:
         [G], the node's own prediction in quanta, counts uint8 [G]).  With the option off everything is 0."""
         import torch
         G, M = self.G, _native.MAXMOVES
-        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
-            np.asarray(path, dtype=np.uint16).reshape(G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        pt, path_ptr, path_len = self._path(path)
         ksum = torch.empty((G, M), dtype=torch.int64, device=self.device)
         mn = torch.empty((G, M), dtype=torch.int32, device=self.device)
         k_net = torch.empty((G,), dtype=torch.int32, device=self.device)
         counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
-        _native.check(self.L.cz_search_node_moves_left(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
-                                                       pa.shape[1], C.c_void_p(ksum.data_ptr()), C.c_void_p(mn.data_ptr()),
-                                                       C.c_void_p(k_net.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                       self._stream()), "cz_search_node_moves_left")
+        _native.check(self.L.cz_search_node_moves_left(self.h, path_ptr, path_len, C.c_void_p(ksum.data_ptr()),
+                                                       C.c_void_p(mn.data_ptr()), C.c_void_p(k_net.data_ptr()),
+                                                       C.c_void_p(counts.data_ptr()), self._stream()), "cz_search_node_moves_left")
         return dict(ksum=ksum.cpu().numpy(), mn=mn.cpu().numpy(), k_net=k_net.cpu().numpy(), counts=counts.cpu().numpy())
 
     def set_draw(self, on, score=0.0):
@@ -523,8 +530,7 @@ class Search:
         and the moves-left utility, and they beside it.  Call it before start_selfplay() / set_roots() and before a graph
         capture."""
         import torch
-        if not hasattr(self.L, "cz_search_set_draw"):
-            raise _native.NativeError("this libczero.so has no draw average (cz_search_set_draw)")
+        self._need("cz_search_set_draw", "draw average")
         if on and self.wdl_rows is None:
             self.wdl_rows = torch.zeros((self.slots, 3), dtype=torch.float32, device=self.device)
         ptr = C.c_void_p(self.wdl_rows.data_ptr()) if self.wdl_rows is not None else None
@@ -538,17 +544,14 @@ class Search:
         int32 [G], the node's own draw probability in quanta, counts uint8 [G]).  With the option off everything is 0."""
         import torch
         G, M = self.G, _native.MAXMOVES
-        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
-            np.asarray(path, dtype=np.uint16).reshape(G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        pt, path_ptr, path_len = self._path(path)
         dsum = torch.empty((G, M), dtype=torch.int64, device=self.device)
         dn = torch.empty((G, M), dtype=torch.int32, device=self.device)
         dq_net = torch.empty((G,), dtype=torch.int32, device=self.device)
         counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
-        _native.check(self.L.cz_search_node_draws(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
-                                                  pa.shape[1], C.c_void_p(dsum.data_ptr()), C.c_void_p(dn.data_ptr()),
-                                                  C.c_void_p(dq_net.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                  self._stream()), "cz_search_node_draws")
+        _native.check(self.L.cz_search_node_draws(self.h, path_ptr, path_len, C.c_void_p(dsum.data_ptr()),
+                                                  C.c_void_p(dn.data_ptr()), C.c_void_p(dq_net.data_ptr()),
+                                                  C.c_void_p(counts.data_ptr()), self._stream()), "cz_search_node_draws")
         return dict(dsum=dsum.cpu().numpy(), dn=dn.cpu().numpy(), dq_net=dq_net.cpu().numpy(), counts=counts.cpu().numpy())
 
     def set_lcb(self, z=0.0, min_ratio=0.15):
@@ -560,8 +563,7 @@ class Search:
         beside the Gumbel search, the solver, the stop rules, the evaluation cache, a script, the moves-left utility and the
         draw average, and they beside it; a refusal leaves the attributes as they were.  Call it before start_selfplay() /
         set_roots() and before a graph capture."""
-        if not hasattr(self.L, "cz_search_set_lcb"):
-            raise _native.NativeError("this libczero.so has no lower-confidence-bound move choice (cz_search_set_lcb)")
+        self._need("cz_search_set_lcb", "lower-confidence-bound move choice")
         _native.check(self.L.cz_search_set_lcb(self.h, float(z), float(min_ratio), self._stream()), "cz_search_set_lcb")
         self.lcb, self.lcb_min_ratio = float(z), float(min_ratio)
 
@@ -571,8 +573,7 @@ class Search:
         in the solver's selection and in policy target pruning.  factor = 0 is off: c_puct as it is.  A plain parameter: it
         runs beside every other option, resets nothing, and a refusal (factor < 0, base < 1, not finite) leaves the
         attributes as they were."""
-        if not hasattr(self.L, "cz_search_set_cpuct_schedule"):
-            raise _native.NativeError("this libczero.so has no c_puct schedule (cz_search_set_cpuct_schedule)")
+        self._need("cz_search_set_cpuct_schedule", "c_puct schedule")
         _native.check(self.L.cz_search_set_cpuct_schedule(self.h, float(factor), float(base), self._stream()),
                       "cz_search_set_cpuct_schedule")
         self.cpuct_factor, self.cpuct_base = float(factor), float(base)
@@ -582,8 +583,7 @@ class Search:
         softmax of l / T over its legal moves, 0.1 <= T <= 10; T = 1 is off.  Refused with probability rows, and
         policy_logits(False) is refused while T != 1.  A change of T resets the trees and empties the evaluation cache: call
         it between plies, before start_selfplay() / set_roots() and before a graph capture."""
-        if not hasattr(self.L, "cz_search_set_policy_temperature"):
-            raise _native.NativeError("this libczero.so has no policy temperature (cz_search_set_policy_temperature)")
+        self._need("cz_search_set_policy_temperature", "policy temperature")
         _native.check(self.L.cz_search_set_policy_temperature(self.h, float(T), self._stream()),
                       "cz_search_set_policy_temperature")
         self.policy_temp = float(T)
@@ -594,15 +594,13 @@ class Search:
         option off everything is 0."""
         import torch
         G, M = self.G, _native.MAXMOVES
-        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
-            np.asarray(path, dtype=np.uint16).reshape(G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        pt, path_ptr, path_len = self._path(path)
         s2 = torch.empty((G, M), dtype=torch.float64, device=self.device)
         vn = torch.empty((G, M), dtype=torch.int32, device=self.device)
         counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
-        _native.check(self.L.cz_search_node_values(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
-                                                   pa.shape[1], C.c_void_p(s2.data_ptr()), C.c_void_p(vn.data_ptr()),
-                                                   C.c_void_p(counts.data_ptr()), self._stream()), "cz_search_node_values")
+        _native.check(self.L.cz_search_node_values(self.h, path_ptr, path_len, C.c_void_p(s2.data_ptr()),
+                                                   C.c_void_p(vn.data_ptr()), C.c_void_p(counts.data_ptr()), self._stream()),
+                      "cz_search_node_values")
         return dict(s2=s2.cpu().numpy(), vn=vn.cpu().numpy(), counts=counts.cpu().numpy())
 
     def root_lcb(self):
@@ -623,17 +621,14 @@ class Search:
         dist).  Works with the solver off."""
         import torch
         G, M = self.G, _native.MAXMOVES
-        pa = np.zeros((G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
-            np.asarray(path, dtype=np.uint16).reshape(G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        pt, path_ptr, path_len = self._path(path)
         status = torch.empty((G,), dtype=torch.int8, device=self.device)
         dist = torch.empty((G,), dtype=torch.uint8, device=self.device)
         mark = torch.empty((G, M), dtype=torch.uint8, device=self.device)
         mark_dist = torch.empty((G, M), dtype=torch.uint8, device=self.device)
-        _native.check(self.L.cz_search_node_proof(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
-                                                  pa.shape[1], C.c_void_p(status.data_ptr()), C.c_void_p(dist.data_ptr()),
-                                                  C.c_void_p(mark.data_ptr()), C.c_void_p(mark_dist.data_ptr()),
-                                                  self._stream()), "cz_search_node_proof")
+        _native.check(self.L.cz_search_node_proof(self.h, path_ptr, path_len, C.c_void_p(status.data_ptr()),
+                                                  C.c_void_p(dist.data_ptr()), C.c_void_p(mark.data_ptr()),
+                                                  C.c_void_p(mark_dist.data_ptr()), self._stream()), "cz_search_node_proof")
         return dict(status=status.cpu().numpy(), dist=dist.cpu().numpy(), mark=mark.cpu().numpy(),
                     mark_dist=mark_dist.cpu().numpy())
 
@@ -652,8 +647,7 @@ class Search:
         gained per simulation falls below `gain`.  gain 0 switches it off.  Refused beside the features include/czero.h's
         matrix names for it.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph
         capture."""
-        if not hasattr(self.L, "cz_search_set_kld_gain"):
-            raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_kld_gain)")
+        self._need("cz_search_set_kld_gain", "stop rules")
         _native.check(self.L.cz_search_set_kld_gain(self.h, float(gain), int(interval), self._stream()),
                       "cz_search_set_kld_gain")
         self.kld_gain, self.kld_interval = float(gain), int(interval)
@@ -663,8 +657,7 @@ class Search:
         tau = 0 ends once its most visited non-banned root move leads the second by more than the simulations not yet
         started -- they could not change the move.  Refused beside the features include/czero.h's matrix
         names for it.  Both modes.  Call it before start_selfplay() / set_roots() and before a graph capture."""
-        if not hasattr(self.L, "cz_search_set_smart_pruning"):
-            raise _native.NativeError("this libczero.so has no stop rules (cz_search_set_smart_pruning)")
+        self._need("cz_search_set_smart_pruning", "stop rules")
         _native.check(self.L.cz_search_set_smart_pruning(self.h, 1 if on else 0, self._stream()),
                       "cz_search_set_smart_pruning")
         self.smart_pruning = bool(on)
@@ -701,12 +694,9 @@ class Search:
         while set_gumbel is on, 0 for a node attached while it was off); NaN where the position is not linked in the tree
         or still waits for its evaluation."""
         import torch
-        pa = np.zeros((self.G, 0), dtype=np.uint16) if path is None or len(path) == 0 else \
-            np.asarray(path, dtype=np.uint16).reshape(self.G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device) if pa.shape[1] else None
+        pt, path_ptr, path_len = self._path(path)
         v = torch.empty((self.G,), dtype=torch.float32, device=self.device)
-        _native.check(self.L.cz_search_node_net_value(self.h, C.c_void_p(pt.data_ptr()) if pt is not None else None,
-                                                      pa.shape[1], C.c_void_p(v.data_ptr()), self._stream()),
+        _native.check(self.L.cz_search_node_net_value(self.h, path_ptr, path_len, C.c_void_p(v.data_ptr()), self._stream()),
                       "cz_search_node_net_value")
         return v.cpu().numpy()
 
@@ -726,8 +716,7 @@ class Search:
 
     def _record_column(self, fn, flag, on):
         """Switch one side column of the visit entries (COLUMNS) through its entry point and note it in its attribute."""
-        if not hasattr(self.L, fn):
-            raise _native.NativeError("this libczero.so has no such record (%s)" % fn)
+        self._need(fn, "such record")
         _native.check(getattr(self.L, fn)(self.h, int(bool(on)), self._stream()), fn)
         setattr(self, flag, bool(on))
 
@@ -977,15 +966,14 @@ class Search:
         if path is None or len(path) == 0:
             return self.root_stats()
         G, M = self.G, _native.MAXMOVES
-        pa = np.asarray(path, dtype=np.uint16).reshape(G, -1)
-        pt = torch.from_numpy(pa.view(np.int16).copy()).to(self.device)
+        pt, path_ptr, path_len = self._path(path)
         moves = torch.empty((G, M), dtype=torch.uint16, device=self.device)
         n = torch.empty((G, M), dtype=torch.int32, device=self.device)
         w = torch.empty((G, M), dtype=torch.float64, device=self.device)
         p = torch.empty((G, M), dtype=torch.float32, device=self.device)
         sum_n = torch.empty((G,), dtype=torch.int32, device=self.device)
         counts = torch.empty((G,), dtype=torch.uint8, device=self.device)
-        _native.check(self.L.cz_search_node_stats(self.h, C.c_void_p(pt.data_ptr()), pa.shape[1],
+        _native.check(self.L.cz_search_node_stats(self.h, path_ptr, path_len,
                                                   C.c_void_p(moves.data_ptr()), C.c_void_p(n.data_ptr()),
                                                   C.c_void_p(w.data_ptr()), C.c_void_p(p.data_ptr()),
                                                   C.c_void_p(sum_n.data_ptr()), C.c_void_p(counts.data_ptr()),

@@ -88,31 +88,19 @@ class CChessPlayer:
         # MCTS solver and unreachable-lead stop (search_options.py): None = config.engine's value, off by default.  After
         # action() self.proof is the root's (status, d) -- (0, 0) while the solver is off or nothing is proven.
         opts = search_options.resolve(config, solver=solver, smart_pruning=smart_pruning)
-        # moves-left utility (search_options.py MOVES_LEFT_EXCLUDES): None = config.engine's value, off by default; the pipe's
-        # network must have the output (MovesLeftUnavailable otherwise, before a device is asked for)
-        ec = getattr(config, "engine", None)
-        self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
-        self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
-        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
-        # draw average (search_options.py DRAW_EXCLUDES): likewise; on with a draw score or with show_wdl, which adds `wdl W D
-        # L` to the info lines; the pipe's network must have the win / draw / loss head (DrawUnavailable otherwise)
-        self.draw_score = float(getattr(ec, "draw_score", 0.0) if draw_score is None else draw_score)
-        self.show_wdl = bool(getattr(ec, "show_wdl", False) if show_wdl is None else show_wdl)
-        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
+        # The side options (search_options.py SIDE): None = config.engine's value, off by default.  The moves-left utility: the
+        # pipe's network must have the output (MovesLeftUnavailable otherwise, before a device is asked for).  The draw average:
+        # on with a draw score or with show_wdl, which adds `wdl W D L` to the info lines; the pipe's network must have the
+        # win / draw / loss head (DrawUnavailable otherwise).  The lower-confidence-bound move choice and the c_puct schedule:
+        # every network will do.  The policy temperature: the pipe hands over probabilities (the reference's protocol), in
+        # which a temperature cannot be applied: PolicyTempUnavailable, before a device is asked for.
+        side = search_options.resolve_side(
+            config, moves_left_slope=moves_left_slope, moves_left_cap=moves_left_cap, draw_score=draw_score, show_wdl=show_wdl,
+            lcb=lcb, lcb_min_visits=lcb_min_visits, cpuct_factor=cpuct_factor, cpuct_base=cpuct_base, policy_temp=policy_temp)
+        vars(self).update(side)                # self.moves_left_slope .. self.policy_temp; self.moves_left, self.draw, self.lcb_on, ..
         self.last_wdl = None                   # show_wdl: (W, D, L) in permille of the move action() chose
-        # lower-confidence-bound move choice (search_options.py LCB_EXCLUDES): likewise; every network will do
-        self.lcb = float(getattr(ec, "lcb", 0.0) if lcb is None else lcb)
-        self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15) if lcb_min_visits is None else lcb_min_visits)
-        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
         search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
-        # c_puct schedule and policy temperature (search_options.py CPUCT_DEFAULTS, POLICY_TEMP_DEFAULTS): likewise; plain
-        # parameters, nothing excludes them.  The pipe hands over probabilities (the reference's protocol), in which a
-        # temperature cannot be applied: PolicyTempUnavailable, before a device is asked for
-        self.cpuct_factor = float(getattr(ec, "cpuct_factor", 0.0) if cpuct_factor is None else cpuct_factor)
-        self.cpuct_base = float(getattr(ec, "cpuct_base", 19652.0) if cpuct_base is None else cpuct_base)
-        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
-        self.policy_temp = float(getattr(ec, "policy_temp", 1.0) if policy_temp is None else policy_temp)
-        if search_options.check_policy_temp(self.policy_temp):
+        if self.policy_temp_on:
             raise PolicyTempUnavailable(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="the player's pipe"))
         if self.moves_left and not getattr(pipes, "moves_left_head", False):
             raise MovesLeftUnavailable(MOVES_LEFT_REFUSAL.format(slope=self.moves_left_slope))
@@ -134,14 +122,7 @@ class CChessPlayer:
         self._torch = torch
         self.proof = (0, 0)
         search_options.apply(self._search, opts)
-        if self.moves_left:
-            self._search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
-        if self.draw:
-            self._search.set_draw(True, self.draw_score)
-        if self.lcb_on:
-            self._search.set_lcb(self.lcb, self.lcb_min_visits)
-        if self.cpuct_on:
-            self._search.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
+        search_options.apply_side(self._search, side)
 
     # -- network access: device fast path, or the reference's pipe protocol --
     def _evaluate(self, planes, moves_left=False, wdl=False):

@@ -73,43 +73,32 @@ class SelfPlayEngine:
         search_options.SCRIPT_EXCLUDES lists.  start(0): slot g walks scripts g, g + G, ... and goes idle after its last;
         drain() reports `script_index` and `script_mismatch`.
         moves_left_slope, moves_left_cap (None = config.engine's values; slope 0 = off): the moves-left utility of the search
-        (Search.set_moves_left).  Like the script it is no row of search_options.py's table; check(moves_left=True) refuses
-        what search_options.MOVES_LEFT_EXCLUDES lists, and a script.  The network must have the moves-left output (`run.py
+        (Search.set_moves_left).  It is a row of search_options.py's SIDE table, as the next three paragraphs' options are;
+        check(moves_left=True) refuses what search_options.MOVES_LEFT_EXCLUDES lists, and a script.  The network must have the moves-left output (`run.py
         opt --moves-left`; a ValueError otherwise, here and in set_network); every forward then also fills
         search.moves_left_x (the tail launch is cz_heads_tail_ml), and the load-time guard and audit_network measure that
         output too.  An evaluator callable returns (policy, value, x).
         draw_score, show_wdl (None = config.engine's values): the draw average of the search (Search.set_draw), on with a draw
-        score other than 0 or with show_wdl.  It stands beside the table the same way: check(draw=True) refuses what
+        score other than 0 or with show_wdl.  check(draw=True) refuses what
         search_options.DRAW_EXCLUDES lists, a script and the moves-left utility.  The network must have the win / draw / loss
         value head (`run.py opt --value-head wdl`; a ValueError otherwise, here and in set_network); every forward then also
         fills search.wdl_rows, and the load-time guard and audit_network measure the draw probability too.  An evaluator
         callable returns (policy, value, wdl [n, 3]).
         lcb, lcb_min_visits (None = config.engine's values): the lower-confidence-bound move choice (Search.set_lcb), on with
-        lcb > 0: from the ply where the temperature reaches 0 a game plays the move with the best lower bound of its value.  It
-        stands beside the table the same way: check(lcb=True) refuses what search_options.LCB_EXCLUDES lists, a script, the
+        lcb > 0: from the ply where the temperature reaches 0 a game plays the move with the best lower bound of its value.
+        check(lcb=True) refuses what search_options.LCB_EXCLUDES lists, a script, the
         moves-left utility and the draw average.  Every network will do.
         cpuct_factor, cpuct_base, policy_temp (None = config.engine's values): the schedule of c_puct (Search.set_cpuct_schedule,
         on with cpuct_factor > 0) and the policy temperature (Search.set_policy_temperature, on with policy_temp != 1).  Plain
         parameters of the search: they exclude nothing.  The temperature is applied to logits: an evaluator callable, or a
         network that hands over probabilities (engine.policy_logits = False, or one without supports_logits()), is refused
         with a ValueError, here and in set_network."""
-        ec_ = getattr(config, "engine", None)
-        self.cpuct_factor = float(getattr(ec_, "cpuct_factor", 0.0) if cpuct_factor is None else cpuct_factor)
-        self.cpuct_base = float(getattr(ec_, "cpuct_base", 19652.0) if cpuct_base is None else cpuct_base)
-        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
-        self.policy_temp = float(getattr(ec_, "policy_temp", 1.0) if policy_temp is None else policy_temp)
-        self.policy_temp_on = search_options.check_policy_temp(self.policy_temp)
+        side = search_options.resolve_side(
+            config, moves_left_slope=moves_left_slope, moves_left_cap=moves_left_cap, draw_score=draw_score, show_wdl=show_wdl,
+            lcb=lcb, lcb_min_visits=lcb_min_visits, cpuct_factor=cpuct_factor, cpuct_base=cpuct_base, policy_temp=policy_temp)
+        vars(self).update(side)                # self.moves_left_slope .. self.policy_temp; self.moves_left, self.draw, self.lcb_on, ..
         if self.policy_temp_on and evaluator is not None:
             raise ValueError(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="an evaluator callable"))
-        self.moves_left_slope = float(getattr(ec_, "moves_left_slope", 0.0) if moves_left_slope is None else moves_left_slope)
-        self.moves_left_cap = float(getattr(ec_, "moves_left_cap", 0.0345) if moves_left_cap is None else moves_left_cap)
-        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
-        self.draw_score = float(getattr(ec_, "draw_score", 0.0) if draw_score is None else draw_score)
-        self.show_wdl = bool(getattr(ec_, "show_wdl", False) if show_wdl is None else show_wdl)
-        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
-        self.lcb = float(getattr(ec_, "lcb", 0.0) if lcb is None else lcb)
-        self.lcb_min_visits = float(getattr(ec_, "lcb_min_visits", 0.15) if lcb_min_visits is None else lcb_min_visits)
-        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
         opts = search_options.resolve(
             config, record_visits=record_visits, fast_sims=fast_sims, full_rate=full_rate, forced_playouts=forced_playouts,
             record_q=record_q, record_surprise=record_surprise, leaf_mirror=leaf_mirror, gumbel=gumbel,
@@ -192,14 +181,10 @@ class SelfPlayEngine:
             self.search.set_book(book_boards(self.book), self.book_rate)
         # every other option that is on: likewise before start() and before a graph capture
         search_options.apply(self.search, opts, skip=("eval_cache",))
-        if self.moves_left:                    # (its rows, search.moves_left_x, are allocated here: fixed for a graph capture)
-            self.search.set_moves_left(self.moves_left_slope, self.moves_left_cap)
-        if self.draw:                          # (likewise search.wdl_rows)
-            self.search.set_draw(True, self.draw_score)
-        if self.lcb_on:
-            self.search.set_lcb(self.lcb, self.lcb_min_visits)
+        # (the rows of the moves-left utility and the draw average, search.moves_left_x and search.wdl_rows, are allocated here:
+        #  fixed for a graph capture)
+        search_options.apply_side(self.search, side)
         if self.cpuct_on:
-            self.search.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
             logger.info(search_options.CPUCT_LOG.format(cpuct_factor=self.cpuct_factor, cpuct_base=self.cpuct_base))
         if self.policy_temp_on:                # (after _install: the rows are logits by now, or _install has refused)
             self.search.set_policy_temperature(self.policy_temp)

@@ -165,36 +165,12 @@ def build_config(args):
         raise SystemExit(f"--reanalyse-plies {args.reanalyse_plies}: expected N >= 1")
     engine.reanalyse_records, engine.reanalyse_out, engine.reanalyse_plies = args.records, args.out, args.reanalyse_plies
     try:
-        ml_on = search_options.check_moves_left(args.moves_left_slope, args.moves_left_cap, flags=True)
-        if ml_on and args.cmd not in ("self", "eval", "reanalyse"):
-            raise search_options.SearchOptionError("--moves-left-slope is an option of `run.py self` and `run.py eval`")
-        draw_on = search_options.check_draw(args.draw_score, flags=True)
-        if draw_on and args.cmd not in ("self", "eval", "reanalyse"):
-            raise search_options.SearchOptionError("--draw-score is an option of `run.py self` and `run.py eval`")
-        lcb_on = search_options.check_lcb(args.lcb, args.lcb_min_visits, flags=True)
-        if lcb_on and args.cmd not in ("self", "eval", "reanalyse"):
-            raise search_options.SearchOptionError("--lcb is an option of `run.py self` and `run.py eval`")
-        if args.lcb_min_visits != search_options.LCB_DEFAULTS["lcb_min_visits"] and args.cmd not in ("self", "eval"):
-            raise search_options.SearchOptionError("--lcb-min-visits is an option of `run.py self` and `run.py eval`")
-        searches = ("self", "eval", "reanalyse")
-        cpuct_on = search_options.check_cpuct(args.cpuct_factor, args.cpuct_base, flags=True)
-        if cpuct_on and args.cmd not in searches:
-            raise search_options.SearchOptionError("--cpuct-factor is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
-        if args.cpuct_base != search_options.CPUCT_DEFAULTS["cpuct_base"] and args.cmd not in searches:
-            raise search_options.SearchOptionError("--cpuct-base is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
-        if search_options.check_policy_temp(args.policy_temp, flags=True) and args.cmd not in searches:
-            raise search_options.SearchOptionError("--policy-temp is an option of `run.py self`, `run.py eval` and `run.py reanalyse`")
+        side, side_on = search_options.side_of_command(args, args.cmd)     # moves_left_slope .. policy_temp (SIDE)
         search_options.check(values, flags=True, cmd=args.cmd, sims=config.play.simulation_num_per_move,
-                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, moves_left=ml_on,
-                             draw=draw_on, lcb=lcb_on)
+                             history=getattr(config.model, "input_depth", 14) == 28, script=reanalyse, **side_on)
     except search_options.SearchOptionError as e:
         raise SystemExit(str(e))
-    vars(engine).update(values)
-    engine.moves_left_slope, engine.moves_left_cap = float(args.moves_left_slope), float(args.moves_left_cap)
-    engine.draw_score = float(args.draw_score)
-    engine.lcb, engine.lcb_min_visits = float(args.lcb), float(args.lcb_min_visits)
-    engine.cpuct_factor, engine.cpuct_base = float(args.cpuct_factor), float(args.cpuct_base)
-    engine.policy_temp = float(args.policy_temp)
+    vars(engine).update(values, **side)
     # the resignation audit: game-loop options, not search options; their one check is the library's
     from cchess_alphazero.lib.resign_audit import check_options
     try:

@@ -140,11 +140,14 @@ _SCRIPT = "each defines its own root rule, start position or game end"
 SCRIPT_EXCLUDES = (("gumbel", _SCRIPT), ("solver", _SCRIPT), ("kld_gain", _SCRIPT), ("smart_pruning", _SCRIPT))
 SCRIPT_NEEDS = ("record_visits", "the new targets are the visit entries")
 
-# The moves-left utility (run.py self / eval --moves-left-slope, engine.moves_left_slope, Search.set_moves_left) is no value of
-# the table either -- it has flags of its own in manager.py and needs a network with the moves-left output, which no table
-# row can say -- but it takes part in the exclusions: check(moves_left=True) refuses these beside it, and a script.  The
-# library's setters hold the same list (csrc/xq_search.hip ML_EXCLUDES; tests/test_gpu_moves_left_search.py pins the two to
-# each other).
+# ---- the side options: what each one excludes, its defaults, its messages and its range check; SIDE below is their table ------
+# They are no rows of OPTIONS: the rule "on = first value truthy, default falsy" fits neither the draw average (on with a score
+# or with show_wdl) nor T = 1, their flags and help texts are manager._FLAGS' own, and what they need of the network (the
+# moves-left output, the win / draw / loss head, logit rows) no table row can say: the layers above ask for that themselves.
+#
+# The moves-left utility (run.py self / eval --moves-left-slope, engine.moves_left_slope, Search.set_moves_left) needs a network
+# with the moves-left output.  The library's setters hold the same list (csrc/xq_search.hip F_ML;
+# tests/test_gpu_moves_left_search.py pins the two to each other).
 _ML_WORD3 = "the Gumbel search keeps the network value in the node header word that holds the moves-left prediction"
 _ML_KERNEL = "each has a kernel instantiation of its own"
 MOVES_LEFT_EXCLUDES = (("gumbel", _ML_WORD3), ("solver", _ML_KERNEL), ("kld_gain", _ML_KERNEL), ("smart_pruning", _ML_KERNEL),
@@ -165,10 +168,9 @@ def check_moves_left(slope, cap, flags=False):
     return slope > 0.0
 
 
-# The draw average (run.py self / eval --draw-score, engine.draw_score and engine.show_wdl, Search.set_draw) stands beside the
-# table the same way: it needs a network with the win / draw / loss value head.  check(draw=True) refuses these beside it, a
-# script, and the moves-left utility; consulted after the moves-left utility.  The library's setters hold the same list
-# (csrc/xq_search.hip DRAW_EXCLUDES; tests/test_gpu_draw_search.py pins the two to each other).
+# The draw average (run.py self / eval --draw-score, engine.draw_score and engine.show_wdl, Search.set_draw) needs a network with
+# the win / draw / loss value head.  The library's setters hold the same list (csrc/xq_search.hip F_DRAW;
+# tests/test_gpu_draw_search.py pins the two to each other).
 _DRAW_WORD3 = "the Gumbel search keeps the network value in the node header word that holds the leaf's draw probability"
 DRAW_EXCLUDES = (("gumbel", _DRAW_WORD3), ("solver", _ML_KERNEL), ("kld_gain", _ML_KERNEL), ("smart_pruning", _ML_KERNEL),
                  ("eval_cache", _ML_KERNEL + ", and a cache entry holds no draw probability"))
@@ -189,9 +191,8 @@ def check_draw(score, show_wdl=False, flags=False):
 
 
 # The lower-confidence-bound move choice (run.py self / eval --lcb Z --lcb-min-visits R, engine.lcb and engine.lcb_min_visits,
-# Search.set_lcb) stands beside the table the same way; it needs no special network output.  check(lcb=True) refuses these
-# beside it, a script, the moves-left utility and the draw average; consulted after the draw average.  The library's setters
-# hold the same list (csrc/xq_search.hip LCB_EXCLUDES; tests/test_gpu_lcb.py pins the two to each other).
+# Search.set_lcb) needs no special network output.  The library's setters hold the same list (csrc/xq_search.hip F_LCB;
+# tests/test_gpu_lcb.py pins the two to each other).
 _LCB_KERNEL = "each has a kernel instantiation of its own"
 LCB_EXCLUDES = (("gumbel", "the Gumbel search has its own root rule and move choice"),
                 ("solver", _LCB_KERNEL + ", and the solver has its own move choice"), ("kld_gain", _LCB_KERNEL),
@@ -216,9 +217,8 @@ def check_lcb(z, ratio, flags=False):
 
 # The schedule of c_puct (run.py self / eval / reanalyse --cpuct-factor F --cpuct-base B, engine.cpuct_factor and
 # engine.cpuct_base, Search.set_cpuct_schedule) and the policy temperature (--policy-temp T, engine.policy_temp,
-# Search.set_policy_temperature) stand beside the table as well, for another reason: the table's rule "on = first value truthy,
-# default falsy" does not fit T = 1.  They are plain parameters of the kernels that run anyway, so they exclude nothing and
-# nothing excludes them: check() has no context for them.  The temperature needs logit rows, which no table row can say.
+# Search.set_policy_temperature) are plain parameters of the kernels that run anyway, so they exclude nothing and nothing
+# excludes them: check() has no context for them.  The temperature needs logit rows.
 CPUCT_DEFAULTS = dict(cpuct_factor=0.0, cpuct_base=19652.0)
 CPUCT_LOG = ("c_puct schedule: the exploration constant of a node is c_puct + {cpuct_factor:g} * log((1 + N + {cpuct_base:g}) / "
              "{cpuct_base:g}), N the node's visit count")
@@ -249,7 +249,35 @@ def check_policy_temp(T, flags=False):
     return T != 1.0
 
 
-VALUES = {v.key: v for o in OPTIONS for v in o.values}
+# The side options in the order they were added, which is the order check() consults them in.
+# context: its keyword of check() (None: it takes no part in the exclusions); key, flag: what names it in a message; on: the
+# name of its on-flag in resolve_side()'s result; excludes: (key of OPTIONS, reason); script: why it excludes a script;
+# earlier: (an earlier row it excludes, reason); values: {key: default}, in the order check and the setter take them;
+# check(*values, flags=) -> on, raises for a value out of range; setter, args: the Search method and its arguments, a str being
+# the value of that key (setter None: the caller's to switch on); commands: (None: the option is on | the key of a value that
+# is off its default, the run.py commands that take it, the sentence that refuses it elsewhere).  The first three let `run.py
+# reanalyse` through to check(), whose "excludes a script" gives the reason; --lcb-min-visits alone does not get that far.
+Side = namedtuple("Side", "context key flag on excludes script earlier values check setter args commands")
+_SEARCHES = ("self", "eval", "reanalyse")
+_SELF_EVAL = "{} is an option of `run.py self` and `run.py eval`"
+_EVERY_SEARCH = "{} is an option of `run.py self`, `run.py eval` and `run.py reanalyse`"
+_ML = Side("moves_left", "moves_left_slope", "--moves-left-slope", "moves_left", MOVES_LEFT_EXCLUDES, MOVES_LEFT_SCRIPT, (),
+           MOVES_LEFT_DEFAULTS, check_moves_left, "set_moves_left", ("moves_left_slope", "moves_left_cap"),
+           ((None, _SEARCHES, _SELF_EVAL.format("--moves-left-slope")),))
+_DRAW = Side("draw", "draw_score", "--draw-score", "draw", DRAW_EXCLUDES, DRAW_SCRIPT, ((_ML, DRAW_MOVES_LEFT),),
+             DRAW_DEFAULTS, check_draw, "set_draw", (True, "draw_score"), ((None, _SEARCHES, _SELF_EVAL.format("--draw-score")),))
+_LCB = Side("lcb", "lcb", "--lcb", "lcb_on", LCB_EXCLUDES, LCB_SCRIPT, ((_ML, LCB_MOVES_LEFT), (_DRAW, LCB_DRAW)),
+            LCB_DEFAULTS, check_lcb, "set_lcb", ("lcb", "lcb_min_visits"),
+            ((None, _SEARCHES, _SELF_EVAL.format("--lcb")), ("lcb_min_visits", ("self", "eval"), _SELF_EVAL.format("--lcb-min-visits"))))
+SIDE = (_ML, _DRAW, _LCB,
+        Side(None, "cpuct_factor", "--cpuct-factor", "cpuct_on", (), None, (), CPUCT_DEFAULTS, check_cpuct,
+             "set_cpuct_schedule", ("cpuct_factor", "cpuct_base"),
+             ((None, _SEARCHES, _EVERY_SEARCH.format("--cpuct-factor")), ("cpuct_base", _SEARCHES, _EVERY_SEARCH.format("--cpuct-base")))),
+        # (set by the caller: the engine after its network is installed, and the player and the arena refuse it)
+        Side(None, "policy_temp", "--policy-temp", "policy_temp_on", (), None, (), POLICY_TEMP_DEFAULTS, check_policy_temp,
+             None, None, ((None, _SEARCHES, _EVERY_SEARCH.format("--policy-temp")),)))
+
+VALUES ={v.key: v for o in OPTIONS for v in o.values}
 DEFAULTS = {k: v.default for k, v in VALUES.items()}
 
 
@@ -270,15 +298,52 @@ def resolve(config, **overrides):
     return {k: type(DEFAULTS[k])(getattr(ec, k, DEFAULTS[k]) if v is None else v) for k, v in overrides.items()}
 
 
+def resolve_side(config, **overrides):
+    """{key: value} of every value of SIDE, resolved as resolve() does (a key that is not named counts as None), and {on: bool}
+    of every row: the attributes an engine, a player and an arena worker keep (moves_left_slope .. policy_temp; moves_left,
+    draw, lcb_on, cpuct_on, policy_temp_on).  Raises SearchOptionError for the first value out of range, rows in order."""
+    ec = getattr(config, "engine", None)
+    side = {}
+    for row in SIDE:
+        for k, d in row.values.items():
+            side[k] = type(d)(getattr(ec, k, d) if overrides.get(k) is None else overrides[k])
+        side[row.on] = row.check(*[side[k] for k in row.values])
+    return side
+
+
+def side_of_command(args, cmd):
+    """The command line's half of resolve_side(): ({key: value} of every value of SIDE from the parsed arguments, {context: on}
+    for check()).  Raises SearchOptionError, per row in order, for a value out of range and then for what `run.py cmd` does not
+    take; the messages name the flags."""
+    side, context = {}, {}
+    for row in SIDE:
+        values = {k: type(d)(getattr(args, k, d)) for k, d in row.values.items()}
+        on = row.check(*values.values(), flags=True)
+        for key, commands, refusal in row.commands:
+            if (on if key is None else values[key] != row.values[key]) and cmd not in commands:
+                raise SearchOptionError(refusal)
+        side.update(values)
+        if row.context:
+            context[row.context] = on
+    return side, context
+
+
+def apply_side(search, side):
+    """Switches on, through their Search methods and in SIDE's order, the side options that are on in resolve_side()'s result
+    (all but the policy temperature, which is the caller's)."""
+    for row in SIDE:
+        if row.setter and side[row.on]:
+            getattr(search, row.setter)(*[side[a] if isinstance(a, str) else a for a in row.args])
+
+
 def check(values, flags=False, cmd=None, sims=None, **context):
     """Raises SearchOptionError for the first violation among the values given (a key that is missing is at its default):
     per option its ranges, the command, its context rule, what it needs, what it excludes; options in table order.
     flags: the messages name --kld-gain where they would name kld_gain.  cmd: the run.py command (None: not checked);
     sims: simulation_num_per_move, the bound of fast_sims (None: not checked); context: history=True for the 28-plane
-    input, script=True for scripted games (checked last: SCRIPT_NEEDS, SCRIPT_EXCLUDES), moves_left=True for the moves-left
-    utility (checked after that: MOVES_LEFT_EXCLUDES, and a script), draw=True for the draw average (checked after that:
-    DRAW_EXCLUDES, a script, and the moves-left utility), lcb=True for the lower-confidence-bound move choice (checked after
-    that: LCB_EXCLUDES, a script, the moves-left utility and the draw average)."""
+    input, script=True for scripted games (checked after the table: SCRIPT_NEEDS, SCRIPT_EXCLUDES), and a side option's context
+    (moves_left=True, draw=True, lcb=True) for one that is on (checked after that, in SIDE's order: its row's excludes, a script,
+    the earlier side options)."""
     def name(key):
         return VALUES[key].flag if flags else key
 
@@ -308,33 +373,18 @@ def check(values, flags=False, cmd=None, sims=None, **context):
         for key, why in SCRIPT_EXCLUDES:
             if on(key):
                 raise SearchOptionError(f"a script excludes {name(key)}: {why}")
-    if context.get("moves_left"):
-        ml = "--moves-left-slope" if flags else "moves_left_slope"
-        for key, why in MOVES_LEFT_EXCLUDES:
+    for row in SIDE:
+        if not (row.context and context.get(row.context)):
+            continue
+        me = row.flag if flags else row.key
+        for key, why in row.excludes:
             if on(key):
-                raise SearchOptionError(f"{ml} excludes {name(key)}: {why}")
+                raise SearchOptionError(f"{me} excludes {name(key)}: {why}")
         if context.get("script"):
-            raise SearchOptionError(f"{ml} excludes a script: {MOVES_LEFT_SCRIPT}")
-    if context.get("draw"):
-        dr = "--draw-score" if flags else "draw_score"
-        for key, why in DRAW_EXCLUDES:
-            if on(key):
-                raise SearchOptionError(f"{dr} excludes {name(key)}: {why}")
-        if context.get("script"):
-            raise SearchOptionError(f"{dr} excludes a script: {DRAW_SCRIPT}")
-        if context.get("moves_left"):
-            raise SearchOptionError(f"{dr} excludes {'--moves-left-slope' if flags else 'moves_left_slope'}: {DRAW_MOVES_LEFT}")
-    if context.get("lcb"):
-        lc = "--lcb" if flags else "lcb"
-        for key, why in LCB_EXCLUDES:
-            if on(key):
-                raise SearchOptionError(f"{lc} excludes {name(key)}: {why}")
-        if context.get("script"):
-            raise SearchOptionError(f"{lc} excludes a script: {LCB_SCRIPT}")
-        if context.get("moves_left"):
-            raise SearchOptionError(f"{lc} excludes {'--moves-left-slope' if flags else 'moves_left_slope'}: {LCB_MOVES_LEFT}")
-        if context.get("draw"):
-            raise SearchOptionError(f"{lc} excludes {'--draw-score' if flags else 'draw_score'}: {LCB_DRAW}")
+            raise SearchOptionError(f"{me} excludes a script: {row.script}")
+        for earlier, why in row.earlier:
+            if context.get(earlier.context):
+                raise SearchOptionError(f"{me} excludes {earlier.flag if flags else earlier.key}: {why}")
 
 
 def apply(search, values, skip=()):

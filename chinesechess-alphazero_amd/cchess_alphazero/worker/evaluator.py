@@ -139,32 +139,14 @@ class EvaluateWorker:
         self.seed = seed
         # of both models' searches (run.py eval --leaf-mirror P / --solver / --smart-pruning; search_options.py)
         opts = search_options.resolve(config, leaf_mirror=None, solver=None, smart_pruning=None)
-        search_options.check(opts)
         vars(self).update(opts)                # self.leaf_mirror, self.solver, self.smart_pruning
-        # moves-left utility of both models' searches (run.py eval --moves-left-slope S; search_options.MOVES_LEFT_EXCLUDES):
-        # both networks need the moves-left output
-        ec = getattr(config, "engine", None)
-        self.moves_left_slope = float(getattr(ec, "moves_left_slope", 0.0))
-        self.moves_left_cap = float(getattr(ec, "moves_left_cap", 0.0345))
-        self.moves_left = search_options.check_moves_left(self.moves_left_slope, self.moves_left_cap)
-        # draw average of both models' searches (run.py eval --draw-score S; search_options.DRAW_EXCLUDES): both networks
-        # need the win / draw / loss head
-        self.draw_score = float(getattr(ec, "draw_score", 0.0))
-        self.show_wdl = bool(getattr(ec, "show_wdl", False))
-        self.draw = search_options.check_draw(self.draw_score, self.show_wdl)
-        # lower-confidence-bound move choice of both models' searches (run.py eval --lcb Z; search_options.LCB_EXCLUDES)
-        self.lcb = float(getattr(ec, "lcb", 0.0))
-        self.lcb_min_visits = float(getattr(ec, "lcb_min_visits", 0.15))
-        self.lcb_on = search_options.check_lcb(self.lcb, self.lcb_min_visits)
+        # The side options of both models' searches (run.py eval --moves-left-slope S / --draw-score S / --lcb Z / --cpuct-factor
+        # F; search_options.py SIDE): the moves-left utility needs the moves-left output of both networks, the draw average
+        # their win / draw / loss heads.  The arena's evaluators hand over probabilities, in which a policy temperature cannot be
+        # applied
+        vars(self).update(search_options.resolve_side(config))     # self.moves_left_slope .. self.policy_temp and the on-flags
         search_options.check(opts, moves_left=self.moves_left, draw=self.draw, lcb=self.lcb_on)
-        # c_puct schedule and policy temperature of both models' searches (run.py eval --cpuct-factor F --cpuct-base B
-        # --policy-temp T): plain parameters, nothing excludes them.  The arena's evaluators hand over probabilities, in which a
-        # temperature cannot be applied
-        self.cpuct_factor = float(getattr(ec, "cpuct_factor", 0.0))
-        self.cpuct_base = float(getattr(ec, "cpuct_base", 19652.0))
-        self.cpuct_on = search_options.check_cpuct(self.cpuct_factor, self.cpuct_base)
-        self.policy_temp = float(getattr(ec, "policy_temp", 1.0))
-        if search_options.check_policy_temp(self.policy_temp):
+        if self.policy_temp_on:
             raise ValueError(search_options.POLICY_TEMP_REFUSAL.format(T=self.policy_temp, who="the arena's evaluator"))
         self._eval3 = tuple(_with_moves_left(e, self.moves_left_slope) for e in evaluators) if self.moves_left else None
         if self.draw:
@@ -236,15 +218,8 @@ class EvaluateWorker:
         searches = [Search(pc, G, planes_dtype=self.dtype, evaluate=getattr(self.config.opts, "evaluate", False),
                            seed=self.seed + k, sims_per_round=sims_per_round) for k in range(2)]
         for s in searches:                                     # (before any round, and before the compact form's graph capture)
-            search_options.apply(s, vars(self))                # (the three attributes above)
-            if self.moves_left:
-                s.set_moves_left(self.moves_left_slope, self.moves_left_cap)
-            if self.draw:
-                s.set_draw(True, self.draw_score)
-            if self.lcb_on:
-                s.set_lcb(self.lcb, self.lcb_min_visits)
-            if self.cpuct_on:
-                s.set_cpuct_schedule(self.cpuct_factor, self.cpuct_base)
+            search_options.apply(s, vars(self))                # (self.leaf_mirror, self.solver, self.smart_pruning)
+            search_options.apply_side(s, vars(self))
 
         def counters_now():
             c = [s.counters() for s in searches]

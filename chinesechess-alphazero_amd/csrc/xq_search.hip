@@ -182,16 +182,27 @@ size_t layout(cz_search* s, char* base, bool dry)
     return (size_t)(cur - base);
 }
 
+// The larger statistics blocks are in use: the moves-left utility, the draw average or the lower-confidence-bound move choice is
+// on (at most one of them: FEATURES), a block carries one M / D / V record per edge (reserve_ply<true>, k_reserve_ml).
+bool larger_blocks(const cz_search* s) { return s->M.slope > 0.0 || s->D.on != 0 || s->Z.on != 0; }
+
 // chunks a game needs for one full search on an empty tree (what it keeps through resets and between games)
-// ml: the moves-left utility, the draw average or the lower-confidence-bound move choice is on, a statistics block carries one
-// M / D / V record per edge
-// (reserve_ply<true>)
-int keep_chunks_for(int sims, bool ml = false)
+// larger: with the larger statistics blocks
+int keep_chunks_for(int sims, bool larger = false)
 {
-    const long long PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + (ml ? 2 : 1) * RESERVE_MOVES;
-    const long long USABLE = CHUNK_GRANULES - (ml ? 2 : 1) * MAXMOVES;
+    const long long PER_TASK = NODE_HDR_GRANULES + (6 * RESERVE_MOVES + 15) / 16 + (larger ? 2 : 1) * RESERVE_MOVES;
+    const long long USABLE = CHUNK_GRANULES - (larger ? 2 : 1) * MAXMOVES;
     const long long need = (long long)(sims + 1) * PER_TASK + 1;
     return (int)((need + USABLE - 1) / USABLE);
+}
+
+// P.keep_chunks for P.sims simulations with the blocks in use now: what one full search needs, within what a game can own and
+// never fewer than it was created with (the initial pool layout gave every game that many).
+void set_keep_chunks(cz_search* s)
+{
+    int keep = keep_chunks_for(s->P.sims, larger_blocks(s));
+    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
+    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
 }
 
 // The pool is sized at creation (raised to the plain blocks' floor, games x keep_chunks + 1) and never grows.  An option that
@@ -210,6 +221,18 @@ bool pool_holds_larger_blocks(const cz_search* s, const char* me)
              " + 1 = %lld", me, s->P.n_chunks, floor_chunks);
     serr(CZ_ERR_ARG, buf);
     return false;
+}
+
+// The readers of the larger blocks' records while their option is off (the trees hold no such records): every output that is
+// given is zeroed.
+struct ZeroOut { void* ptr; size_t bytes; };
+template <size_t N>
+int zero_outputs(const ZeroOut (&outs)[N], const char* entry, void* stream)
+{
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < N && e == hipSuccess; ++i)
+        if (outs[i].ptr) e = hipMemsetAsync(outs[i].ptr, 0, outs[i].bytes, (hipStream_t)stream);
+    return e == hipSuccess ? CZ_OK : serr_hip(entry, e);
 }
 
 // initial state of the pool: game g owns chunks [g * keep, (g + 1) * keep), the rest is free
@@ -528,7 +551,7 @@ static int search_round_impl(cz_search* s, const float* policy, const float* val
     else if (solve) hipLaunchKernelGGL((k_advance<false, true>), grid, block, 0, st, s->P, s->B, s->V);
     else if (lcb) hipLaunchKernelGGL(k_advance_lcb, grid, block, 0, st, s->P, s->B, s->V, s->Z);
     else hipLaunchKernelGGL(k_advance<false>, grid, block, 0, st, s->P, s->B, s->V);
-    if (ml || draw || lcb) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
+    if (larger_blocks(s)) hipLaunchKernelGGL(k_reserve_ml, grid, block, 0, st, s->P, s->B);   // the larger statistics blocks of the searches that go on
     if (noise) hipLaunchKernelGGL(k_noise, grid, nblock, 0, st, s->P, s->B);
     sim(SIM_SELECT, compact);
     S_LAUNCH_CHECK("cz_search_round");
@@ -556,12 +579,8 @@ int cz_search_set_sims(cz_search* s, int simulation_num_per_move)
         return serr(CZ_ERR_ARG, "cz_search_set_sims: below the playout cap's fast_sims (cz_search_set_playout_cap)");
     // (a search longer than the chunks a game can own ends in counted overflow_sims, it is not refused here)
     s->P.sims = simulation_num_per_move;
-    // a game that has to drop its tree keeps enough chunks for one full search of the NEW length (never fewer than it
-    // was created with: the initial pool layout gave every game that many)
-    int keep = keep_chunks_for(simulation_num_per_move, s->M.slope > 0.0 || s->D.on != 0 || s->Z.on != 0);
-    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
-    if (keep > s->keep_chunks_created) s->P.keep_chunks = keep;
-    else s->P.keep_chunks = s->keep_chunks_created;
+    // a game that has to drop its tree keeps enough chunks for one full search of the NEW length
+    set_keep_chunks(s);
     return CZ_OK;
 }
 
@@ -605,24 +624,34 @@ int cz_search_policy_logits(cz_search* s, int on)
 // ---- features that cannot run beside each other (include/czero.h has the matrix and the reasons) -------------------------
 // Host only.  A refused setter names the first excluder that is on, in this order; each phrase stands here once.
 // cchess_alphazero/search_options.py states the same pairs for the layers above (tests/test_gpu_search_options.py).
-enum Feature : int { F_FORCED, F_CAP, F_GUMBEL, F_SOLVER, F_KLD, F_LEAD, F_CACHE, F_SCRIPT, F_COUNT };
+// The last three are the options with the larger statistics blocks (larger_blocks): each excludes the other two, whose records
+// lie in the same granules, and F_BLOCKS_EXCLUDE, the features with a k_sim instantiation or a use of the blocks' words of their own.
+enum Feature : int { F_FORCED, F_CAP, F_GUMBEL, F_SOLVER, F_KLD, F_LEAD, F_CACHE, F_SCRIPT, F_ML, F_DRAW, F_LCB, F_COUNT };
 constexpr unsigned fbit(Feature f) { return 1u << f; }
+constexpr unsigned F_BLOCKS = fbit(F_ML) | fbit(F_DRAW) | fbit(F_LCB);
+constexpr unsigned F_BLOCKS_EXCLUDE = fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT);
 constexpr struct { bool (*on)(const cz_search*); const char* phrase; unsigned excludes; } FEATURES[F_COUNT] = {
     {[](const cz_search* s) { return s->P.forced_k > 0.0; }, "forced playouts are on (cz_search_set_forced_playouts)",
      fbit(F_GUMBEL) | fbit(F_SOLVER)},
     {[](const cz_search* s) { return s->P.fast_sims > 0; }, "the playout cap is on (cz_search_set_playout_cap)", fbit(F_GUMBEL)},
     {[](const cz_search* s) { return s->P.gumbel_m > 0; }, "the Gumbel root search is on (cz_search_set_gumbel)",
-     fbit(F_FORCED) | fbit(F_CAP) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_SCRIPT)},
+     fbit(F_FORCED) | fbit(F_CAP) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_SCRIPT) | F_BLOCKS},
     {[](const cz_search* s) { return s->P.solver != 0; }, "the MCTS solver is on (cz_search_set_solver)",
-     fbit(F_FORCED) | fbit(F_GUMBEL) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT)},
+     fbit(F_FORCED) | fbit(F_GUMBEL) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT) | F_BLOCKS},
     {[](const cz_search* s) { return s->S.gain > 0.0; }, "the KLD-gain stop is on (cz_search_set_kld_gain)",
-     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT)},
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT) | F_BLOCKS},
     {[](const cz_search* s) { return s->S.lead != 0; }, "the unreachable-lead stop is on (cz_search_set_smart_pruning)",
-     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT)},
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_CACHE) | fbit(F_SCRIPT) | F_BLOCKS},
     {[](const cz_search* s) { return s->C.tab != nullptr; }, "the evaluation cache is on (cz_search_set_eval_cache)",
-     fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+     fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | F_BLOCKS},
     {[](const cz_search* s) { return s->X.n > 0; }, "a script is set (cz_search_set_script)",
-     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD)},
+     fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | F_BLOCKS},
+    {[](const cz_search* s) { return s->M.slope > 0.0; }, "the moves-left utility is on (cz_search_set_moves_left)",
+     F_BLOCKS_EXCLUDE | fbit(F_DRAW) | fbit(F_LCB)},
+    {[](const cz_search* s) { return s->D.on != 0; }, "the draw average is on (cz_search_set_draw)",
+     F_BLOCKS_EXCLUDE | fbit(F_ML) | fbit(F_LCB)},
+    {[](const cz_search* s) { return s->Z.on != 0; }, "the lower-confidence-bound move choice is on (cz_search_set_lcb)",
+     F_BLOCKS_EXCLUDE | fbit(F_ML) | fbit(F_DRAW)},
 };
 constexpr bool features_symmetric()
 {
@@ -634,21 +663,10 @@ constexpr bool features_symmetric()
 static_assert(features_symmetric(), "the exclusion matrix is symmetric and no feature excludes itself");
 
 // What a setter of feature f does between its argument checks and its assignment.  Switching on is refused beside an excluder:
-// CZ_ERR_ARG, "<entry>: <phrase of the first one that is on>".  Then the stream is idle: launches in flight keep the setting
-// (the table) they started with.
-// The moves-left utility (cz_search_set_moves_left) stands beside the table, as the side columns' script test does: it
-// excludes the features of ML_EXCLUDES and they exclude it, consulted last.
-constexpr unsigned ML_EXCLUDES = fbit(F_GUMBEL) | fbit(F_SOLVER) | fbit(F_KLD) | fbit(F_LEAD) | fbit(F_CACHE) | fbit(F_SCRIPT);
-constexpr const char* ML_PHRASE = "the moves-left utility is on (cz_search_set_moves_left)";
-// The draw average (cz_search_set_draw) stands there too, consulted after the moves-left utility: it excludes the features of
-// DRAW_EXCLUDES and the moves-left utility (its D records lie in the M records' granules), and they exclude it.
-constexpr unsigned DRAW_EXCLUDES = ML_EXCLUDES;
-constexpr const char* DRAW_PHRASE = "the draw average is on (cz_search_set_draw)";
-// The lower-confidence-bound move choice (cz_search_set_lcb) stands there too, consulted after the draw average: it excludes the
-// features of LCB_EXCLUDES, the moves-left utility and the draw average (its V records lie in their granules), and they it.
-constexpr unsigned LCB_EXCLUDES = ML_EXCLUDES;
-constexpr const char* LCB_PHRASE = "the lower-confidence-bound move choice is on (cz_search_set_lcb)";
-static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream)
+// CZ_ERR_ARG, "<entry>: <phrase of the first one that is on>".  grows (a setter of F_BLOCKS that steps from off to on): then
+// the host-only pool test, pool_holds_larger_blocks.  Then the stream is idle: launches in flight keep the setting (the table)
+// they started with.
+static int admit(const cz_search* s, Feature f, bool on, const char* entry, void* stream, bool grows = false)
 {
     for (int o = 0; on && o < F_COUNT; ++o)
         if ((FEATURES[f].excludes >> o & 1) && FEATURES[o].on(s)) {
@@ -656,23 +674,18 @@ static int admit(const cz_search* s, Feature f, bool on, const char* entry, void
             snprintf(buf, sizeof(buf), "%s: %s", entry, FEATURES[o].phrase);
             return serr(CZ_ERR_ARG, buf);
         }
-    if (on && (ML_EXCLUDES >> f & 1) && s->M.slope > 0.0) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", entry, ML_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
-    if (on && (DRAW_EXCLUDES >> f & 1) && s->D.on) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", entry, DRAW_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
-    if (on && (LCB_EXCLUDES >> f & 1) && s->Z.on) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", entry, LCB_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
+    if (grows && !pool_holds_larger_blocks(s, entry)) return CZ_ERR_ARG;
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     return e == hipSuccess ? CZ_OK : serr_hip(entry, e);
+}
+
+// What a setter of F_BLOCKS does after its assignment: where it went on or off the statistics blocks change size, so the trees
+// start over, and a game keeps the chunks of one full search of the new size.
+static int blocks_changed(cz_search* s, bool was, bool on, void* stream)
+{
+    if (was == on) return CZ_OK;
+    set_keep_chunks(s);
+    return cz_search_reset_trees(s, stream);
 }
 
 // ---- evaluation cache (include/czero.h; csrc/xq_evalcache.h has the layout and who touches the table when) ----
@@ -1053,28 +1066,12 @@ int cz_search_set_moves_left(cz_search* s, double slope, double cap, const float
         return serr(CZ_ERR_ARG, "cz_search_set_moves_left: slope or cap negative or not finite");
     const bool on = slope > 0.0;
     if (on && !x_rows) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: x_rows is NULL");
-    for (int o = 0; on && o < F_COUNT; ++o)
-        if ((ML_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
-            return serr(CZ_ERR_ARG, buf);
-        }
-    if (on && s->D.on) return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the draw average is on (cz_search_set_draw)");
-    if (on && s->Z.on)
-        return serr(CZ_ERR_ARG, "cz_search_set_moves_left: the lower-confidence-bound move choice is on (cz_search_set_lcb)");
-    if (on && !(s->M.slope > 0.0) && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->M.slope > 0.0;
+    if (const int rc = admit(s, F_ML, on, me, stream, on && !was)) return rc;
     s->M.slope = slope;
     s->M.cap = cap;
     s->M.x = on ? x_rows : nullptr;
-    if (was == on) return CZ_OK;
-    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
-    int keep = keep_chunks_for(s->P.sims, on);
-    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
-    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
-    return cz_search_reset_trees(s, stream);
+    return blocks_changed(s, was, on, stream);
 }
 
 int cz_search_node_moves_left(cz_search* s, const uint16_t* path, int path_len, int64_t* ksum, int32_t* mn, int32_t* k_net,
@@ -1085,12 +1082,9 @@ int cz_search_node_moves_left(cz_search* s, const uint16_t* path, int path_len, 
     hipStream_t st = (hipStream_t)stream;
     if (!(s->M.slope > 0.0)) {                                  // off: the trees hold no M records
         const size_t G = (size_t)s->P.G;
-        hipError_t e = hipSuccess;
-        if (ksum) e = hipMemsetAsync(ksum, 0, sizeof(int64_t) * G * MAXMOVES, st);
-        if (e == hipSuccess && mn) e = hipMemsetAsync(mn, 0, sizeof(int32_t) * G * MAXMOVES, st);
-        if (e == hipSuccess && k_net) e = hipMemsetAsync(k_net, 0, sizeof(int32_t) * G, st);
-        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
-        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_moves_left", e);
+        const ZeroOut outs[] = {{ksum, sizeof(int64_t) * G * MAXMOVES}, {mn, sizeof(int32_t) * G * MAXMOVES},
+                                {k_net, sizeof(int32_t) * G}, {counts, G}};
+        return zero_outputs(outs, "cz_search_node_moves_left", stream);
     }
     hipLaunchKernelGGL(k_node_moves_left, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, (long long*)ksum, mn, k_net,
                        counts);
@@ -1115,35 +1109,12 @@ int cz_search_set_draw(cz_search* s, int on_, double score, const float* wdl_row
     if (!(score >= -1.0 && score <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_draw: score outside [-1, 1] or not finite");
     const bool on = on_ != 0;
     if (on && !wdl_rows) return serr(CZ_ERR_ARG, "cz_search_set_draw: wdl_rows is NULL");
-    for (int o = 0; on && o < F_COUNT; ++o)
-        if ((DRAW_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
-            return serr(CZ_ERR_ARG, buf);
-        }
-    if (on && s->M.slope > 0.0) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", me, ML_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
-    if (on && s->Z.on) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", me, LCB_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
-    if (on && !s->D.on && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->D.on != 0;
+    if (const int rc = admit(s, F_DRAW, on, me, stream, on && !was)) return rc;
     s->D.on = on ? 1 : 0;
     s->D.score = on ? score : 0.0;
     s->D.wdl = on ? wdl_rows : nullptr;
-    if (was == on) return CZ_OK;
-    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
-    int keep = keep_chunks_for(s->P.sims, on);
-    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
-    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
-    return cz_search_reset_trees(s, stream);
+    return blocks_changed(s, was, on, stream);
 }
 
 int cz_search_node_draws(cz_search* s, const uint16_t* path, int path_len, int64_t* dsum, int32_t* dn, int32_t* dq_net,
@@ -1154,12 +1125,9 @@ int cz_search_node_draws(cz_search* s, const uint16_t* path, int path_len, int64
     hipStream_t st = (hipStream_t)stream;
     if (!s->D.on) {                                             // off: the trees hold no D records
         const size_t G = (size_t)s->P.G;
-        hipError_t e = hipSuccess;
-        if (dsum) e = hipMemsetAsync(dsum, 0, sizeof(int64_t) * G * MAXMOVES, st);
-        if (e == hipSuccess && dn) e = hipMemsetAsync(dn, 0, sizeof(int32_t) * G * MAXMOVES, st);
-        if (e == hipSuccess && dq_net) e = hipMemsetAsync(dq_net, 0, sizeof(int32_t) * G, st);
-        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
-        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_draws", e);
+        const ZeroOut outs[] = {{dsum, sizeof(int64_t) * G * MAXMOVES}, {dn, sizeof(int32_t) * G * MAXMOVES},
+                                {dq_net, sizeof(int32_t) * G}, {counts, G}};
+        return zero_outputs(outs, "cz_search_node_draws", stream);
     }
     hipLaunchKernelGGL(k_node_draws, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, (long long*)dsum, dn, dq_net, counts);
     S_LAUNCH_CHECK("cz_search_node_draws");
@@ -1183,30 +1151,12 @@ int cz_search_set_lcb(cz_search* s, double z, double min_ratio, void* stream)
     if (!finite_nonneg(z)) return serr(CZ_ERR_ARG, "cz_search_set_lcb: z negative or not finite");
     if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return serr(CZ_ERR_ARG, "cz_search_set_lcb: min_ratio outside [0, 1] or not finite");
     const bool on = z > 0.0;
-    for (int o = 0; on && o < F_COUNT; ++o)
-        if ((LCB_EXCLUDES >> o & 1) && FEATURES[o].on(s)) {
-            char buf[160];
-            snprintf(buf, sizeof(buf), "%s: %s", me, FEATURES[o].phrase);
-            return serr(CZ_ERR_ARG, buf);
-        }
-    if (on && (s->M.slope > 0.0 || s->D.on)) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "%s: %s", me, s->M.slope > 0.0 ? ML_PHRASE : DRAW_PHRASE);
-        return serr(CZ_ERR_ARG, buf);
-    }
-    if (on && !s->Z.on && !pool_holds_larger_blocks(s, me)) return CZ_ERR_ARG;
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return serr_hip(me, e);
     const bool was = s->Z.on != 0;
+    if (const int rc = admit(s, F_LCB, on, me, stream, on && !was)) return rc;
     s->Z.on = on ? 1 : 0;
     s->Z.z = on ? z : 0.0;
     s->Z.ratio = min_ratio;
-    if (was == on) return CZ_OK;
-    // the statistics blocks change size: the trees start over, and a game keeps the chunks of one full search of the new size
-    int keep = keep_chunks_for(s->P.sims, on);
-    if (keep > s->P.max_chunks) keep = s->P.max_chunks;
-    s->P.keep_chunks = keep > s->keep_chunks_created ? keep : s->keep_chunks_created;
-    return cz_search_reset_trees(s, stream);
+    return blocks_changed(s, was, on, stream);
 }
 
 int cz_search_node_values(cz_search* s, const uint16_t* path, int path_len, double* s2, int32_t* vn, uint8_t* counts,
@@ -1217,11 +1167,8 @@ int cz_search_node_values(cz_search* s, const uint16_t* path, int path_len, doub
     hipStream_t st = (hipStream_t)stream;
     if (!s->Z.on) {                                             // off: the trees hold no V records
         const size_t G = (size_t)s->P.G;
-        hipError_t e = hipSuccess;
-        if (s2) e = hipMemsetAsync(s2, 0, sizeof(double) * G * MAXMOVES, st);
-        if (e == hipSuccess && vn) e = hipMemsetAsync(vn, 0, sizeof(int32_t) * G * MAXMOVES, st);
-        if (e == hipSuccess && counts) e = hipMemsetAsync(counts, 0, G, st);
-        return e == hipSuccess ? CZ_OK : serr_hip("cz_search_node_values", e);
+        const ZeroOut outs[] = {{s2, sizeof(double) * G * MAXMOVES}, {vn, sizeof(int32_t) * G * MAXMOVES}, {counts, G}};
+        return zero_outputs(outs, "cz_search_node_values", stream);
     }
     hipLaunchKernelGGL(k_node_values, dim3(s->P.G), dim3(64), 0, st, s->P, s->B, path, path_len, s2, vn, counts);
     S_LAUNCH_CHECK("cz_search_node_values");
@@ -1258,12 +1205,15 @@ static int stop_state_update(cz_search* s, hipStream_t st, const char* what)
 {
     const bool want = s->S.gain > 0.0 || s->S.lead != 0;
     if (want == (s->stop_mem != nullptr)) return CZ_OK;
+    const auto no_state = [s] {
+        s->S.prev_n = nullptr; s->S.prev_sum = nullptr; s->S.start_tasks = nullptr; s->S.last_gain = nullptr;
+        s->S.checks = nullptr; s->S.cut = nullptr;
+    };
     if (!want) {
         (void)hipFree(s->stop_mem);
         s->stop_mem = nullptr;
         s->stop_bytes = 0;
-        s->S.prev_n = nullptr; s->S.prev_sum = nullptr; s->S.start_tasks = nullptr; s->S.last_gain = nullptr;
-        s->S.checks = nullptr; s->S.cut = nullptr;
+        no_state();
         return CZ_OK;
     }
     const size_t G = (size_t)s->P.G;
@@ -1288,8 +1238,7 @@ static int stop_state_update(cz_search* s, hipStream_t st, const char* what)
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipFree(mem);
-        s->S.prev_n = nullptr; s->S.prev_sum = nullptr; s->S.start_tasks = nullptr; s->S.last_gain = nullptr;
-        s->S.checks = nullptr; s->S.cut = nullptr;
+        no_state();
         return serr_hip(what, e);
     }
     s->stop_mem = mem;

@@ -201,15 +201,14 @@ int cz_search_set_book(cz_search* s, const int8_t* boards, int n, double rate, v
  * search, the MCTS solver, the KLD-gain stop and the unreachable-lead stop, which define a root rule or a ply's end of
  * their own, and -- outside the table, refused the same way in both directions -- not beside a book (a start position of
  * its own) and the max-q record of the resignation audit (a scripted game has no resignation test).
- * The moves-left utility (cz_search_set_moves_left, below) stands beside the table the same way, consulted last: it is not
- * beside the Gumbel root search, the MCTS solver, the two stop rules, the evaluation cache and a script, in both directions;
- * a setter refused for it names "the moves-left utility is on (cz_search_set_moves_left)".
- * The draw average (cz_search_set_draw, below) stands there too, consulted after the moves-left utility: it is not beside the
- * same six, nor beside the moves-left utility itself, in both directions; a setter refused for it names "the draw average is
- * on (cz_search_set_draw)".
- * The lower-confidence-bound move choice (cz_search_set_lcb, below) stands there too, consulted after the draw average: it is
- * not beside the same six, nor beside the moves-left utility or the draw average, in both directions; a setter refused for it
- * names "the lower-confidence-bound move choice is on (cz_search_set_lcb)". */
+ * The moves-left utility, the draw average and the lower-confidence-bound move choice (cz_search_set_moves_left,
+ * cz_search_set_draw, cz_search_set_lcb, below) are the ninth, tenth and eleventh members, in that order: each is not beside
+ * the Gumbel root search, the MCTS solver, the two stop rules, the evaluation cache and a script, which have a kernel
+ * instantiation or a use of the node header's words of their own, nor beside the other two, whose per-edge records lie in the
+ * same granules of the larger statistics blocks.  A setter refused for one of them names "the moves-left utility is on
+ * (cz_search_set_moves_left)", "the draw average is on (cz_search_set_draw)" or "the lower-confidence-bound move choice is on
+ * (cz_search_set_lcb)".  These three check one thing more, after the exclusions and before they synchronise the stream:
+ * that the pool holds the larger blocks (below). */
 
 /* Scripted games: walk stored games again (MuZero's Reanalyse).  n games: game id i < n starts from init_boards[i] (90
  * bytes, the first mover's frame, as cz_replay_games takes them), plays labels[offsets[i] .. offsets[i+1]) and ends with
